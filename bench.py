@@ -19,12 +19,17 @@ concurrently on two HIP streams (default: configs[2], all V5).
 The JSON line carries, besides the driver's contract:
   roofline     - dominant kernel (silero_v5_step) against the fp32 MFMA peak, from HIP events
                  recorded on the launch stream around the timed region;
-  cpu_baseline - the oracle's C port (oracle/silero_oracle.c, float accumulators) timed on this
+  cpu_baseline - with --full only: the oracle's C port (oracle/silero_oracle.c, float accumulators) timed on this
                  host's cores on a bounded sample of the same workload (rank 0, N=1 only), which
                  also yields the in-run parity figure; `single_thread` inside it is the reference's own
                  configuration (one stream, one thread: silero_model.py:316-317).
+A plain run sets up, warms up, times the K steps and prints the line; everything else it measures or checks (the CPU
+baseline and the parity against it) runs only with --full.
 Before the W warm-up steps an untimed clock-ramp preamble runs the same step for ~0.4 s (`preamble_steps` in the line):
 with W = 5 and K = 20 the whole measurement is 1.4 ms long and would otherwise be taken while the GPU clocks are still rising.
+The streams are reset after the preamble, so the W + K steps always start from zero state on ring frame 0: with the same
+arguments the timed path sees the same inputs in every run.  `--dump-outputs DIR` writes what its last step computed
+(per-stream probabilities and state-machine events, float32) as DIR/<name>.npy, so two builds can be compared output for output.
 """
 
 from __future__ import annotations
@@ -151,6 +156,16 @@ def cpu_leg(ring: np.ndarray, gpu_probs: np.ndarray, budget_s: float = 12.0) -> 
     return base, parity
 
 
+def dump_outputs(out_dir: str, suffix: str, probs: list, events: list) -> None:
+    """What a caller of the timed path receives from its last step: every stream's probability and its state-machine event
+    byte (engines concatenated in stream order), as float32 .npy files - 64 KB for 8 192 streams."""
+    os.makedirs(out_dir, exist_ok=True)
+    import torch
+    torch.cuda.synchronize()
+    np.save(os.path.join(out_dir, f"probs{suffix}.npy"), torch.cat(probs).float().cpu().numpy())
+    np.save(os.path.join(out_dir, f"events{suffix}.npy"), torch.cat(events).float().cpu().numpy())
+
+
 def _free_port() -> int:
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -193,7 +208,11 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--streams", type=int, default=B_PER_GPU, help="streams per GPU (headline: 8192)")
     ap.add_argument("--mix", choices=["v5", "v4v5"], default="v5", help="v4v5 = configs[4] per-GPU share (4096 V4 + 4096 V5)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the CPU baseline leg and the parity against it")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg (of --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (probabilities, events) as DIR/<name>.npy")
     ap.add_argument("--pools", type=int, default=1, choices=[1, 2],
                     help="2 = the GPU's streams as two independent pools (an engine and a HIP stream each; what "
                          "ShardedStreamPool(devices=[0, 0]) gives a serving process): the pools' launches are not ordered against "
@@ -273,6 +292,8 @@ def main() -> int:
     first_stream, _ = sharding.stream_shard(world * B, world, rank)   # weak scaling: B streams per rank
     host_enqueue = [0.0]
     if fake:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the CPU rehearsal computes nothing to write")
         stepper, sync, kernel_s = FakeStepper(B), (lambda: None), [None]
         for i in range(args.warmup):
             stepper.step(i)
@@ -287,11 +308,11 @@ def main() -> int:
         from cutter_vad_amd.engine import Engine
         versions = [5] * args.pools if args.mix == "v5" else [5, 4]
         nb = B // len(versions)                       # streams per engine
-        engines, streams, probs, events = [], [], [], []
+        engines, slots, streams, probs, events = [], [], [], [], []
         for v in versions:
             with open(weights_io.packaged_blob_path(v), "rb") as f:
                 e = Engine(f.read(), model_version=v, device_id=local_rank, max_streams=nb, shared_gpu=args.mix != "v5")
-            e.open_streams(nb)                        # slots 0..nb-1, zero state, default thresholds
+            slots.append(e.open_streams(nb))          # slots 0..nb-1, zero state, default thresholds
             engines.append(e)
             streams.append(torch.cuda.Stream())
             probs.append(torch.empty(nb, device="cuda"))
@@ -311,8 +332,10 @@ def main() -> int:
             for s in streams[1:]:
                 ts.wait_stream(s)
 
-        gpu_probs = torch.empty(PARITY_STEPS, B, device="cuda")
-        for i in range(PARITY_STEPS):                 # from zero state: these frames are what the CPU leg replays
+        cpu_leg_on = args.full and world == 1 and not args.no_cpu and args.mix == "v5"
+        parity_steps = PARITY_STEPS if cpu_leg_on else 0
+        gpu_probs = torch.empty(parity_steps, B, device="cuda")
+        for i in range(parity_steps):                 # from zero state: these frames are what the CPU leg replays
             step(i)
             for k in range(len(versions)):
                 with torch.cuda.stream(streams[k]):
@@ -322,12 +345,15 @@ def main() -> int:
         t0, preamble = time.perf_counter(), 0
         while time.perf_counter() - t0 < PREAMBLE_S:
             for _ in range(64):
-                step(PARITY_STEPS + preamble)
+                step(parity_steps + preamble)
                 preamble += 1
             torch.cuda.synchronize()
-        base = PARITY_STEPS + preamble
+        # the ramp's length depends on the wall clock: back to zero state, so that warm-up and timed steps (ring frames 0, 1,
+        # ...) compute the same outputs in every run with the same arguments
+        for e, s in zip(engines, slots):
+            e.reset(s)
         for i in range(args.warmup):
-            step(base + i)
+            step(i)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
@@ -337,7 +363,7 @@ def main() -> int:
             e0.record(ts)
             h0 = time.perf_counter()
             for i in range(args.steps):
-                step(base + args.warmup + i)
+                step(args.warmup + i)
             host_enqueue[0] = time.perf_counter() - h0
             join()
             e1.record(ts)
@@ -346,6 +372,8 @@ def main() -> int:
         kernel_s = [e0.elapsed_time(e1) * 1e-3 / args.steps]     # avg launch duration on the launch stream(s)
         for p in probs:
             assert bool(torch.isfinite(p).all()) and float(p.min()) >= 0.0 and float(p.max()) <= 1.0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, "" if world == 1 else f"_rank{rank}", probs, events)
 
     # every rank's own figures, so that a straggler is visible behind the MAX
     per_rank = cp.gather({"rank": rank, "device": shown, "pci": pci,
@@ -441,7 +469,7 @@ def main() -> int:
             if not mixed:
                 out["roofline"]["executed_mfma_flop_per_launch"] = EXECUTED_FLOP_PER_FRAME * B
                 out["roofline"]["executed_frac_of_peak"] = EXECUTED_FLOP_PER_FRAME * B / ks / PEAK_FP32_MFMA
-            if world == 1 and not args.no_cpu and not mixed:
+            if cpu_leg_on:
                 base_, parity = cpu_leg(ring_h, gpu_probs.cpu().numpy())
                 out["cpu_baseline"] = base_
                 out["parity"] = parity

@@ -6,7 +6,6 @@ import hashlib
 import json
 import os
 import sys
-import tempfile
 
 import numpy as np
 
@@ -15,7 +14,7 @@ sys.path.insert(0, ROOT)
 from cutter_vad_amd import _ffi, VADConfig  # noqa: E402
 from tests import standin  # noqa: E402
 
-_ffi.LIB_PATH = standin.build(os.path.join(tempfile.gettempdir(), "vad_standin_lib"))
+_ffi.LIB_PATH = standin.build(os.path.join(ROOT, "build", "standin"))   # this checkout's own (git-ignored build/)
 from cutter_vad_amd.pool import EnginePool  # noqa: E402
 from cutter_vad_amd.server import ShardedStreamPool, SharedStreamPool  # noqa: E402
 from cutter_vad_amd.server import shared_pool  # noqa: E402

@@ -91,8 +91,10 @@ def test_audio_utils_match_reference_fixtures():
     assert AudioUtils.float32_to_pcm(np.array([0.5, -0.5], np.float32)) == np.array([16383, -16383], np.int16).tobytes()
     x = np.arange(10, dtype=np.float32)
     assert AudioUtils.resample_audio(x, 16000, 16000) is x
+    # a resampling error reaches the caller in the reference's wrapping; an empty array fails in scipy's own way on any machine
+    # (10 samples at 44.1 kHz only failed where no GPU was present: the generic resampler takes any rate)
     with pytest.raises(AudioProcessingError, match="Failed to resample audio from 44100Hz to 16000Hz"):
-        AudioUtils.resample_audio(x, 44100, 16000)
+        AudioUtils.resample_audio(x[:0], 44100, 16000)
 
 
 def test_wav_writer_bytes_match_reference():

@@ -14,6 +14,10 @@ for m in $MODES; do
     esac
     g++ -std=c++17 -O1 -g -fno-omit-frame-pointer $F -Itools/san_tick -Icutter_vad_amd/csrc -o "$OUT" $SRC -lpthread
     echo "== $m"
-    TSAN_OPTIONS="halt_on_error=1" ASAN_OPTIONS="detect_leaks=1" "$OUT" cutter_vad_amd/weights/silero_v5_16k.svw
+    # ThreadSanitizer's shadow layout does not fit every kernel's address randomisation ("unexpected memory mapping"): run
+    # that binary without randomisation (a personality of this one process) where the host allows it
+    PRE=()
+    if [ "$m" = thread ] && setarch "$(uname -m)" -R true 2>/dev/null; then PRE=(setarch "$(uname -m)" -R); fi
+    TSAN_OPTIONS="halt_on_error=1" ASAN_OPTIONS="detect_leaks=1" "${PRE[@]}" "$OUT" cutter_vad_amd/weights/silero_v5_16k.svw
 done
 rm -f "$OUT"
