@@ -151,6 +151,22 @@ bool check_windowed_dft(const float *stft, std::string &err, int N = 256) {
 // cos(2 pi (2 m) (64 - n) / 256) = (-1)^m cos(2 pi (2 m) n / 256) and sin(2 pi (2 m) (64 - n) / 256) = -(-1)^m sin(2 pi (2 m) n / 256),
 // and the unpaired n = 32 has cos = 0 for m odd, sin = 0 for m even: checked on the very values the blocks are built from (the
 // stored basis is tied to these analytic tables by check_windowed_dft)
+// w = w1 + w2 + w3 as three bf16 (the high halves of fp32 bit patterns), each piece cut from the remainder by truncation: 8 + 8 + 8
+// significant bits hold all 24 of a normal float.  Checked, not assumed: the sum must give w back exactly, w3 must have no bits in
+// its low half, and no piece may be a denormal (the MFMA may flush those).  The split LSTM (S_LSTM_X3) is then exact in its weights.
+bool split3_bf16(float w, uint16_t piece[3]) {
+    auto bits = [](float v) { uint32_t u; std::memcpy(&u, &v, 4); return u; };
+    auto flt = [](uint32_t u) { float v; std::memcpy(&v, &u, 4); return v; };
+    const float w1 = flt(bits(w) & 0xffff0000u), r = w - w1;
+    const float w2 = flt(bits(r) & 0xffff0000u), w3 = r - w2;
+    const float p[3] = {w1, w2, w3};
+    for (int i = 0; i < 3; ++i) {
+        if ((bits(p[i]) & 0xffffu) != 0 || (p[i] != 0.f && std::fabs(p[i]) < 1.17549435e-38f)) return false;
+        piece[i] = (uint16_t)(bits(p[i]) >> 16);
+    }
+    return (double)w1 + (double)w2 + (double)w3 == (double)w && std::isfinite(w);
+}
+
 bool check_even_bin_fold(std::string &err) {
     const double two_pi = 6.283185307179586476925286766559;
     double worst = 0;
@@ -478,6 +494,29 @@ bool pack_silero_v5_t16(const void *blob, size_t len, PackedWeights &out, std::s
     for (int w = 0; w < NWAVES; ++w) {
         out.sect[w][S_HEADB] = hb;
         out.sect[w][S_NYQ] = nb;
+    }
+    // S_LSTM_X3, appended behind everything else (the sections above keep their bytes and offsets): W_ih, W_hh of the wave's units
+    // as bf16 A fragments of v_mfma_f32_16x16x32_bf16, three exact pieces per weight (vad_layout.h)
+    for (int w = 0; w < NWAVES; ++w) {
+        out.sect[w][S_LSTM_X3] = sb.blocks();
+        for (const float *W : {w_ih, w_hh})
+            for (int s = 0; s < 4; ++s)
+                for (int q = 0; q < 4; ++q)
+                    for (int rt = 0; rt < 2; ++rt) {
+                        const size_t b0 = sb.data.size();
+                        for (int p = 0; p < 3; ++p) sb.new_block();
+                        float *blk[3] = {sb.data.data() + b0, sb.data.data() + b0 + BLK_FLOATS, sb.data.data() + b0 + 2 * BLK_FLOATS};
+                        for (int l = 0; l < 64; ++l)
+                            for (int e = 0; e < 8; ++e) {
+                                const int r = q * 128 + 32 * w + 16 * rt + (l & 15), k = 32 * s + 16 * (e >> 2) + 4 * (l >> 4) + (e & 3);
+                                uint16_t pc[3];
+                                if (!split3_bf16(W[(size_t)r * 128 + k], pc)) {
+                                    err = "Failed to load model: an LSTM weight does not split into three exact bf16 pieces";
+                                    return false;
+                                }
+                                for (int p = 0; p < 3; ++p) std::memcpy(reinterpret_cast<uint8_t *>(blk[p] + l * 4) + 2 * e, &pc[p], 2);
+                            }
+                    }
     }
     out.data = std::move(sb.data);
     return true;

@@ -5,6 +5,8 @@
 // there are.  This kernel is the same network, the same algebra (frame ingest under the recurrent gate half, 4-way folded DFT,
 // Toom-3 enc0, split-K enc2) and the same per-stream results, re-expressed on v_mfma_f32_16x16x4_f32: a workgroup (4 waves)
 // carries 16 streams, so the same batch spreads over twice as many CUs and every MFMA / VALU phase is half as long.
+// The LSTM's two halves run on v_mfma_f32_16x16x32_bf16 instead, with weights and activations as exact three-piece bf16 splits
+// (X3_HALF below; vad_layout.h S_LSTM_X3).
 // The engine picks it when a call has at most T16_MAX_STREAMS streams (engine.cpp).
 //
 // Fragment convention (v_mfma_f32_16x16x4_f32, D = A[16 x 4] B[4 x 16] + C): lane l = (n = l & 15, kq = l >> 4).
@@ -78,6 +80,10 @@ __device__ __forceinline__ f32x4 mfma16(f32x4 w, f32x4 a, f32x4 acc) {
     return acc;
 }
 
+// the LSTM's weight ring (S_LSTM_X3): units requested ahead, slots
+constexpr int X3_D = 4;
+constexpr int X3_NR = X3_D + 1;
+
 }  // namespace
 
 // A k-iteration's MFMAs with the NEXT iteration's requests issued in their shadow: ND LDS reads first, then one weight-block
@@ -89,11 +95,40 @@ __device__ __forceinline__ f32x4 mfma16(f32x4 w, f32x4 a, f32x4 acc) {
         __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                                                      \
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                                                      \
     }
-// eight accumulators, the four components of a quad in turn: consecutive MFMAs are independent
-#define T16_MMA8(G, WS, AV)                                                                                     \
-    _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                                            \
-        _Pragma("unroll") for (int k_ = 0; k_ < 8; ++k_)                                                        \
-            G[k_] = __builtin_amdgcn_mfma_f32_16x16x4f32(WS[k_][j_], (AV)[j_], G[k_], 0, 0, 0);
+// One half of the LSTM (W_ih . x or W_hh . h) on the bf16 split: 32 units u = 8 s + tile, unit u = the six MFMAs of tile u & 7 at
+// K-step s (vadk_device.h: mfma_x3) into G[tile].  Requests run X3_D units ahead through the ring xw.  The activations: lane (n, kq)
+// reads quad rows 8 s + kq and 8 s + 4 + kq of SRC (K elements 0..3 and 4..7 of its B fragment) and splits them into the three bf16
+// fragments; K-step s + 1's quads are read in unit (s, 0) and split one dword per unit in units (s, 1..4), under K-step s's MFMAs.
+// EXTRA(u): work placed in unit u; FOLD(u): unit u is fenced together with the next one (a longer region for the caller's
+// interleave hints).
+#define X3_UNIT(u, B, SRC, EXTRA, FOLD)                                                                         \
+    {                                                                                                           \
+        constexpr int s_ = (u) >> 3, k_ = (u) & 7;                                                              \
+        if constexpr ((u) + X3_D < 32) { X3_LD(B, (u) + X3_D) }                                                 \
+        if constexpr (k_ == 0 && s_ < 3) { na_ = (SRC)[(8 * s_ + 8) * QSD + nq]; nb_ = (SRC)[(8 * s_ + 12) * QSD + nq]; } \
+        EXTRA(u)                                                                                                \
+        G[k_] = mfma_x3(xw[(u) % X3_NR], F_, G[k_]);                                                            \
+        if constexpr (k_ >= 1 && k_ <= 4 && s_ < 3) split3_dword(na_, nb_, k_ - 1, N_);                         \
+        if constexpr (k_ == 7) { F_[0] = N_[0]; F_[1] = N_[1]; F_[2] = N_[2]; }                                 \
+        if constexpr (!(FOLD(u)) || k_ == 7) SB();                                                              \
+    }
+#define X3_STEP(s, B, SRC, EXTRA, FOLD)                                                                         \
+    X3_UNIT(8 * (s) + 0, B, SRC, EXTRA, FOLD) X3_UNIT(8 * (s) + 1, B, SRC, EXTRA, FOLD)                         \
+    X3_UNIT(8 * (s) + 2, B, SRC, EXTRA, FOLD) X3_UNIT(8 * (s) + 3, B, SRC, EXTRA, FOLD)                         \
+    X3_UNIT(8 * (s) + 4, B, SRC, EXTRA, FOLD) X3_UNIT(8 * (s) + 5, B, SRC, EXTRA, FOLD)                         \
+    X3_UNIT(8 * (s) + 6, B, SRC, EXTRA, FOLD) X3_UNIT(8 * (s) + 7, B, SRC, EXTRA, FOLD)
+#define X3_HALF(B, SRC, EXTRA, FOLD)                                                                            \
+    {                                                                                                           \
+        u32x4 F_[3], N_[3];                                                                                     \
+        f32x4 na_, nb_;                                                                                         \
+        {                                                                                                       \
+            const f32x4 a0_ = (SRC)[nq], b0_ = (SRC)[4 * QSD + nq];                                              \
+            _Pragma("unroll") for (int d_ = 0; d_ < 4; ++d_) split3_dword(a0_, b0_, d_, F_);                    \
+        }                                                                                                       \
+        SB();                                                                                                   \
+        X3_STEP(0, B, SRC, EXTRA, FOLD) X3_STEP(1, B, SRC, EXTRA, FOLD)                                         \
+        X3_STEP(2, B, SRC, EXTRA, FOLD) X3_STEP(3, B, SRC, EXTRA, FOLD)                                         \
+    }
 
 // RS: one tick for streams at other input rates (vad_step_rates): the tile first resamples its 16 chunks to 16 kHz into LDS -
 // AudioUtils.resample_audio's Fourier method as the folded operator of resample.hip, on 16 x 16 x 4 tiles - and the frame loop
@@ -160,7 +195,7 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
 #define WL(blk) ldw(wrs, lane16, (blk))
     const int o_stft = (int)P.sect[w][S_STFT], o_nyq = (int)P.sect[w][S_NYQ], o_e0 = (int)P.sect[w][S_ENC0];
     const int o_e1 = (int)P.sect[w][S_ENC1], o_e2 = (int)P.sect[w][S_ENC2], o_e3 = (int)P.sect[w][S_ENC3];
-    const int o_l = (int)P.sect[w][S_LSTM];
+    const int o_l = (int)P.sect[w][S_LSTM], o_x3 = (int)P.sect[w][S_LSTM_X3];
     const int T = (ONE || RS) ? 1 : KP(T);
 
     // ---- frame ingest set-up: 16 lanes per stream, 16 streams per fold call (ms = tid >> 4) ----
@@ -285,19 +320,19 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
         for (int k = 0; k < 6; ++k) smq[k] = reinterpret_cast<const f32x4 *>(KP(sm) + slot)[k];
     }
     SB();
-    f32x4 wA[8], wB[8];                            // W_hh blocks of a group, ping-pong
-#define H_LDW(WS, g, WH) _Pragma("unroll") for (int k = 0; k < 8; ++k) WS[k] = WL((WH) + 8 * (g) + k);
+    // The LSTM's weights come from S_LSTM_X3 (vad_layout.h): per half 32 units u = 8 s + tile (K-step s, tile = 2 q + rt), each the
+    // three bf16 pieces of the tile's A fragment (3 blocks).  They stream through a ring of X3_NR units, requested X3_D units ahead.
+    f32x4 xw[X3_NR][3];
+#define X3_LD(B, u) _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) xw[(u) % X3_NR][p_] = WL((B) + 3 * (u) + p_);
 #define H_FIRST(L, tt)                                                                                          \
     {                                                                                                           \
-        H_LDW(wA, 0, (L) + 8 + 64)                                                                              \
-        SB();                                                                                                   \
-        H_LDW(wB, 1, (L) + 8 + 64)                                                                              \
+        _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LD((L) + LSTM_X3_HALF_BLOCKS, u_) }             \
         if constexpr (K8) { X_ISSUE8(0, xa_, tt) X_ISSUE8(2, xb_, tt) }                                         \
         else { X_ISSUE(0, xa_, tt) X_ISSUE(1, xb_, tt) }                                                        \
         SB();                                                                                                   \
         if constexpr (RS) { X_ISSUE(2, xc_, tt) SB(); }                                                         \
     }
-    if constexpr (!RS) H_FIRST(o_l, 0)             // frames t > 0 request theirs at the end of frame t - 1; RS: at the top of the frame
+    if constexpr (!RS) H_FIRST(o_x3, 0)            // frames t > 0 request theirs at the end of frame t - 1; RS: at the top of the frame
     const f32x4 W1 = ldw(wrs, q * 16, o_nyq), W3 = ldw(wrs, (2 * QL + q) * 16, o_nyq);   // w[n], w[128 + n]  (8 kHz: w[64 + n])
     const float w64 = ldw(wrs, QL * 16, o_nyq).x;                                          // w[64]             (8 kHz: w[32])
     f32x4 cst[2];                                  // c of units 32 w + 16 rt + 4 kq + i
@@ -656,12 +691,12 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
 
     STAMP(0);
     for (int t = 0;;) {                          // T >= 1; the back edge is at the bottom, behind the next frame's first requests
-        int ws_stft = o_stft, ws_e0 = o_e0, ws_e1 = o_e1, ws_e2 = o_e2, ws_e3 = o_e3, ws_l = o_l;
-        asm volatile("" : "+s"(ws_stft), "+s"(ws_e0), "+s"(ws_e1), "+s"(ws_e2), "+s"(ws_e3), "+s"(ws_l));
-        // ---- recurrent gate half W_hh . h_{t-1} (8 k-iterations x {4 gates x 2 row tiles}) with the frame ingested under it ----
+        int ws_stft = o_stft, ws_e0 = o_e0, ws_e1 = o_e1, ws_e2 = o_e2, ws_e3 = o_e3, ws_l = o_l, ws_x3 = o_x3;
+        asm volatile("" : "+s"(ws_stft), "+s"(ws_e0), "+s"(ws_e1), "+s"(ws_e2), "+s"(ws_e3), "+s"(ws_l), "+s"(ws_x3));
+        // ---- recurrent gate half W_hh . h_{t-1} (4 K-steps x {4 gates x 2 row tiles}, bf16 split) with the frame ingested under it ----
         f32x4 G[8];                               // gate q, row tile rt -> G[2 q + rt]
         {
-            const int wh = ws_l + 8 + 64;
+            const int wh = ws_x3 + LSTM_X3_HALF_BLOCKS;
             auto decode = [&](u32x4 b) -> f32x4 {
                 f32x4 v = __builtin_bit_cast(f32x4, b);
                 if constexpr (!f32in) {
@@ -727,17 +762,12 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
         st2(&RX[er + 24 * QSL], qep);                                                                           \
         }                                                                                                       \
     }
-#define H_MMA(WS, g)                                                                                            \
-    {                                                                                                           \
-        const f32x4 av = RH[(4 * (g)) * QSD + nq];                                                             \
-        T16_MMA8(G, WS, av)                                                                                     \
-    }
 #define H_MIX                                                                                                   \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                          \
-        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);                                                      \
-        __builtin_amdgcn_sched_group_barrier(0x002, 40, 0);                                                     \
+    _Pragma("unroll") for (int i_ = 0; i_ < 6; ++i_) {                                                          \
+        __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);                                                      \
+        __builtin_amdgcn_sched_group_barrier(0x002, 28, 0);                                                     \
     }
-            if constexpr (RS) H_FIRST(ws_l, t)                 // F is dead once every wave has passed the barrier below
+            if constexpr (RS) H_FIRST(ws_x3, t)                 // F is dead once every wave has passed the barrier below
             {   // the accumulators start at the gate biases: G[2 q + rt] register i of a lane = unit 16 rt + 4 kq + i of gate q (the
                 // 16 lanes of a row group read the same 16 bytes: a broadcast).  The wave reads what the wave itself wrote.
                 const f32x4 *const bq = biasL + 32 * w + kq;
@@ -746,26 +776,18 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
             }
             __syncthreads();   // (0) h_{t-1} visible (t > 0: follows barrier (8))
             STAMP(31);
-            H_MMA(wA, 0) SB();
-            if constexpr (K8) {             // two fold calls: columns (0 | 1) by half of the workgroup, then column 2
-            H_LDW(wA, 2, wh) H_MMA(wB, 1) T16_IL(8, 1) SB();
-            H_LDW(wB, 3, wh) SB(); H_MMA(wA, 2) X_FOLD(lcol, xa_) H_MIX SB();
-            H_LDW(wA, 4, wh) H_MMA(wB, 3) T16_IL(8, 1) SB();
-            H_LDW(wB, 5, wh) SB(); H_MMA(wA, 4) X_FOLD(2, xb_) H_MIX SB();
-            H_LDW(wA, 6, wh) H_MMA(wB, 5) T16_IL(8, 1) SB();
-            H_LDW(wB, 7, wh) H_MMA(wA, 6) T16_IL(8, 1) SB();
-            H_MMA(wB, 7) SB();
-            } else {
-            H_LDW(wA, 2, wh) if constexpr (!RS) { X_ISSUE(2, xc_, t) } SB(); H_MMA(wB, 1) SB();
-            H_LDW(wB, 3, wh) SB(); H_MMA(wA, 2) X_FOLD(0, xa_) H_MIX SB();
-            H_LDW(wA, 4, wh) H_MMA(wB, 3) T16_IL(8, 1) SB();
-            H_LDW(wB, 5, wh) SB(); H_MMA(wA, 4) X_FOLD(1, xb_) H_MIX SB();
-            H_LDW(wA, 6, wh) H_MMA(wB, 5) T16_IL(8, 1) SB();
-            H_LDW(wB, 7, wh) SB(); H_MMA(wA, 6) X_FOLD(2, xc_) H_MIX SB();
-            H_MMA(wB, 7) SB();
-            }
+            // 4 K-steps x 8 tiles on the bf16 split (X3_HALF); the frame's columns are folded in the shadow of the last three units
+            // of K-steps 1, 2, 3 (8 kHz: two fold calls, columns (0 | 1) by half of the workgroup, then column 2, in K-steps 1, 2)
+#define H_EXTRA(u)                                                                                              \
+            if constexpr ((u) == 2 && !RS && !K8) { X_ISSUE(2, xc_, t) }                                        \
+            if constexpr ((u) == 15) { if constexpr (K8) { X_FOLD(lcol, xa_) } else { X_FOLD(0, xa_) } H_MIX }   \
+            if constexpr ((u) == 23) { if constexpr (K8) { X_FOLD(2, xb_) } else { X_FOLD(1, xb_) } H_MIX }      \
+            if constexpr ((u) == 31 && !K8) { X_FOLD(2, xc_) H_MIX }
+#define H_FOLDREGION(u) (((u) & 7) >= 5 && (u) >= 8 && ((u) < 24 || !K8))
+            X3_HALF(wh, RH, H_EXTRA, H_FOLDREGION)
+#undef H_EXTRA
+#undef H_FOLDREGION
 #undef H_MIX
-#undef H_MMA
 #undef X_FOLD
         }
         f32x4 Sw[2];                              // STFT blocks of k-iteration 0: cos, -sin of the odd tile
@@ -1051,7 +1073,6 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
         STAMP(10);
 
         // ---- enc3: 64 -> 128 ch, centre tap; input = relu(partial of K half 0 + K half 1) ----
-        f32x4 Lw[8];
         {
             const int ws = ws_e3 + 2;
             f32x4 acc[2] = {e3b[0], e3b[1]};
@@ -1065,7 +1086,7 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
                 av[j] = relu4(f32x4{a.x + b2.x, a.y + b2.y, a.z + b2.z, a.w + b2.w});
             }
 #pragma unroll
-            for (int k = 0; k < 8; ++k) Lw[k] = WL(ws_l + 8 + k);      // first k-iteration of the LSTM's input half
+            for (int u = 0; u < X3_D; ++u) { X3_LD(ws_x3, u) }          // the LSTM input half's first units
             SB();
 #pragma unroll
             for (int j = 0; j < 4; ++j) { acc[0] = mfma16(wv[2 * j], av[j], acc[0]); acc[1] = mfma16(wv[2 * j + 1], av[j], acc[1]); }
@@ -1079,19 +1100,12 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
         // ---- LSTM: input half W_ih . x on top of the recurrent half, cell, head partial ----
         {
             const int ws = ws_l + 8;
-            f32x4 Aw[8], Bw[8], Aa = RX[nq], Ba, hw[2];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) Aw[k] = Lw[k];
-#define L_LD(S, it) _Pragma("unroll") for (int k = 0; k < 8; ++k) S##w[k] = WL(ws + 8 * (it) + k); S##a = RX[(4 * (it)) * QSD + nq];
-#define L_MMA(S) T16_MMA8(G, S##w, S##a)
-            for (int it = 0; it < 8; it += 2) {
-                L_LD(B, it + 1) L_MMA(A) T16_IL(8, 1) SB();
-                const int itn = it + 2 < 8 ? it + 2 : 6;
-                if (it == 6) { hw[0] = WL(ws + 128); hw[1] = WL(ws + 129); SB(); }
-                L_LD(A, itn) L_MMA(B) T16_IL(8, 1) SB();
-            }
-#undef L_LD
-#undef L_MMA
+            f32x4 hw[2];
+#define L_EXTRA(u) if constexpr ((u) == 24) { hw[0] = WL(ws + 128); hw[1] = WL(ws + 129); }
+#define L_FOLDREGION(u) false
+            X3_HALF(ws_x3, RX, L_EXTRA, L_FOLDREGION)
+#undef L_EXTRA
+#undef L_FOLDREGION
             STAMP(18);
             STAMP(13);
             __syncthreads();   // (7) every wave is done reading h_{t-1}
@@ -1135,10 +1149,13 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
             }
         }
         if (++t >= T) break;
-        if constexpr (!RS) H_FIRST(o_l, t)         // the next frame's first requests
+        if constexpr (!RS) H_FIRST(ws_x3, t)       // the next frame's first requests
     }
 #undef H_FIRST
-#undef H_LDW
+#undef X3_HALF
+#undef X3_STEP
+#undef X3_UNIT
+#undef X3_LD
 #undef X_ISSUE
 #undef WL
     if (sm_thread && P.seg_frames) P.seg_frames[gf] = seg_last;

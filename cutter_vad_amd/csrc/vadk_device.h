@@ -169,6 +169,43 @@ __device__ __forceinline__ f32x4 ldw(__amdgpu_buffer_rsrc_t rs, int voff, int bl
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, blk * 1024, 0));
 }
 
+// ---- fp32-exact products on bf16 MFMAs (the 16-stream kernel's LSTM: vad_layout.h, S_LSTM_X3) ----
+// A float x with 24 significant bits is x1 + x2 + x3, each the high half of an fp32 bit pattern: x1 = hi16(x), x2 = hi16(x - x1),
+// x3 = x - x1 - x2 (both subtractions are exact, x3 has at most 8 significant bits).  With the weights split the same way on the host,
+// the six products x_i w_j with i + j <= 4 on v_mfma_f32_16x16x32_bf16 (products exact, fp32 accumulation) leave out terms of at most
+// ~2^-24 |x w|: fp32's own rounding, at 6 x 16 cycles per 16 x 16 x 32 tile instead of 8 x 32 for v_mfma_f32_16x16x4_f32.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+// dword of the three B fragments from two consecutive K values a (low half) and b (high half): 2 and + 2 sub + 3 perm per pair
+__device__ __forceinline__ void split3_pair(float a, float b, unsigned &p1, unsigned &p2, unsigned &p3) {
+    const unsigned ua = __builtin_bit_cast(unsigned, a), ub = __builtin_bit_cast(unsigned, b);
+    const float ra = a - __builtin_bit_cast(float, ua & 0xffff0000u), rb = b - __builtin_bit_cast(float, ub & 0xffff0000u);
+    const unsigned va = __builtin_bit_cast(unsigned, ra), vb = __builtin_bit_cast(unsigned, rb);
+    const float sa = ra - __builtin_bit_cast(float, va & 0xffff0000u), sb = rb - __builtin_bit_cast(float, vb & 0xffff0000u);
+    p1 = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
+    p2 = __builtin_amdgcn_perm(vb, va, 0x07060302u);
+    p3 = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, sb), __builtin_bit_cast(unsigned, sa), 0x07060302u);
+}
+// dword d (0..3) of the fragments of quads xa (K elements 0..3) and xb (4..7)
+__device__ __forceinline__ void split3_dword(f32x4 xa, f32x4 xb, int d, u32x4 *F) {
+    const f32x4 x = d < 2 ? xa : xb;
+    const float a = (d & 1) ? x.z : x.x, b = (d & 1) ? x.w : x.y;
+    unsigned p1, p2, p3;
+    split3_pair(a, b, p1, p2, p3);
+    F[0][d] = p1; F[1][d] = p2; F[2][d] = p3;
+}
+// one 16 x 16 x 32 tile: A pieces W[0..2], B pieces X[0..2], the six leading products, smallest first
+__device__ __forceinline__ f32x4 mfma_x3(const f32x4 *W, const u32x4 *X, f32x4 acc) {
+#define VADK_BF(v) __builtin_bit_cast(bf16x8, v)
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(VADK_BF(W[2]), VADK_BF(X[0]), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(VADK_BF(W[1]), VADK_BF(X[1]), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(VADK_BF(W[0]), VADK_BF(X[2]), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(VADK_BF(W[1]), VADK_BF(X[0]), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(VADK_BF(W[0]), VADK_BF(X[1]), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(VADK_BF(W[0]), VADK_BF(X[0]), acc, 0, 0, 0);
+#undef VADK_BF
+    return acc;
+}
+
 // (float) s / d for an int16 s and d = 32767 or 32768, bit for bit the IEEE quotient that numpy's true division gives
 // (vad_websocket_server.py:341): q = s * r with r = float(1 / d), then one Newton correction in two fmas.  Exhaustively equal over
 // all 65 536 values of s (tools/i16_division_check.py, tests/test_host_logic.py); 3 instructions instead of the ~10 of the
