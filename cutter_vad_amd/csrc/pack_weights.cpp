@@ -495,6 +495,23 @@ bool pack_silero_v5_t16(const void *blob, size_t len, PackedWeights &out, std::s
         out.sect[w][S_HEADB] = hb;
         out.sect[w][S_NYQ] = nb;
     }
+    // One unit of the split sections (vad_layout.h, S_LSTM_X3): the bf16 A fragment of a 16 x 32 tile, tile row r = lane & 15 and
+    // K element k = 16 (e >> 2) + 4 (lane >> 4) + (e & 3) of W(r, k), as three exact pieces (3 blocks)
+    auto x3_unit = [&](auto W, const char *what) -> bool {
+        const size_t b0 = sb.data.size();
+        for (int p = 0; p < 3; ++p) sb.new_block();
+        float *blk[3] = {sb.data.data() + b0, sb.data.data() + b0 + BLK_FLOATS, sb.data.data() + b0 + 2 * BLK_FLOATS};
+        for (int l = 0; l < 64; ++l)
+            for (int e = 0; e < 8; ++e) {
+                uint16_t pc[3];
+                if (!split3_bf16(W(l & 15, 16 * (e >> 2) + 4 * (l >> 4) + (e & 3)), pc)) {
+                    err = std::string("Failed to load model: ") + what + " weight does not split into three exact bf16 pieces";
+                    return false;
+                }
+                for (int p = 0; p < 3; ++p) std::memcpy(reinterpret_cast<uint8_t *>(blk[p] + l * 4) + 2 * e, &pc[p], 2);
+            }
+        return true;
+    };
     // S_LSTM_X3, appended behind everything else (the sections above keep their bytes and offsets): W_ih, W_hh of the wave's units
     // as bf16 A fragments of v_mfma_f32_16x16x32_bf16, three exact pieces per weight (vad_layout.h)
     for (int w = 0; w < NWAVES; ++w) {
@@ -502,23 +519,31 @@ bool pack_silero_v5_t16(const void *blob, size_t len, PackedWeights &out, std::s
         for (const float *W : {w_ih, w_hh})
             for (int s = 0; s < 4; ++s)
                 for (int q = 0; q < 4; ++q)
-                    for (int rt = 0; rt < 2; ++rt) {
-                        const size_t b0 = sb.data.size();
-                        for (int p = 0; p < 3; ++p) sb.new_block();
-                        float *blk[3] = {sb.data.data() + b0, sb.data.data() + b0 + BLK_FLOATS, sb.data.data() + b0 + 2 * BLK_FLOATS};
-                        for (int l = 0; l < 64; ++l)
-                            for (int e = 0; e < 8; ++e) {
-                                const int r = q * 128 + 32 * w + 16 * rt + (l & 15), k = 32 * s + 16 * (e >> 2) + 4 * (l >> 4) + (e & 3);
-                                uint16_t pc[3];
-                                if (!split3_bf16(W[(size_t)r * 128 + k], pc)) {
-                                    err = "Failed to load model: an LSTM weight does not split into three exact bf16 pieces";
-                                    return false;
-                                }
-                                for (int p = 0; p < 3; ++p) std::memcpy(reinterpret_cast<uint8_t *>(blk[p] + l * 4) + 2 * e, &pc[p], 2);
-                            }
-                    }
+                    for (int rt = 0; rt < 2; ++rt)
+                        if (!x3_unit([&](int r, int k) { return W[(size_t)(q * 128 + 32 * w + 16 * rt + r) * 128 + 32 * s + k]; }, "an LSTM"))
+                            return false;
     }
     out.data = std::move(sb.data);
+    // S_ENC0_X3, the second stream (vad_layout.h): encoder.0 as a direct 3-tap convolution on the bf16 split - its bias and its
+    // Nyquist-channel column (fp32, the kernel's VALU), then per K-step the three taps x two row tiles over the 128 (8 kHz: 64) other
+    // input channels in the STFT's channel order
+    sb = StreamBuilder();
+    const int ns0 = k8 ? 2 : 4;
+    for (int w = 0; w < NWAVES; ++w) {
+        out.sect[w][S_ENC0_X3] = sb.blocks();
+        for (int rt = 0; rt < 2; ++rt) sb.vector_block16([&](int c) { return eb[0][32 * w + 16 * rt + c]; });
+        for (int t = 0; t < 3; ++t)
+            for (int rt = 0; rt < 2; ++rt) sb.vector_block16([&](int c) { return convw(0, 32 * w + 16 * rt + c, NB - 1, t); });
+        for (int s = 0; s < ns0; ++s)
+            for (int t = 0; t < 3; ++t)
+                for (int rt = 0; rt < 2; ++rt)
+                    if (!x3_unit([&](int r, int k) {
+                            const int ch = 32 * s + k;
+                            return convw(0, 32 * w + 16 * rt + r, k8 ? bin_of_channel_8k(ch) : bin_of_channel_fold3(ch), t);
+                        }, "an encoder.0"))
+                        return false;
+    }
+    out.data_x = std::move(sb.data);
     return true;
 }
 

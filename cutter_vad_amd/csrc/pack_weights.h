@@ -13,6 +13,9 @@ namespace vadk {
 struct PackedWeights {
     std::vector<float> data;        // concatenated per-wave streams, multiple of BLK_FLOATS
     uint32_t sect[NWAVES][16] = {};  // block offset of every section
+    // a second stream, uploaded as a buffer of its own (StepParams::wstream_x): V5 on 16-stream tiles, the split encoders
+    // (S_ENC0_X3 - its sect entries are block offsets into THIS stream); empty for every other packing
+    std::vector<float> data_x;
     int32_t variant = 0;             // V4: 1 = the graph's 8 kHz sub-model (two time steps reach the LSTMs)
 };
 

@@ -2,11 +2,12 @@
 //
 // silero_v5.hip carries 32 streams per workgroup, so a launch of n streams occupies n / 32 of the 256 CUs: 1 024 streams
 // (BASELINE.json configs[1]) use 32 CUs, 4 096 (configs[3]) half the chip - and a tile takes the same ~47 us however few
-// there are.  This kernel is the same network, the same algebra (frame ingest under the recurrent gate half, 4-way folded DFT,
-// Toom-3 enc0, split-K enc2) and the same per-stream results, re-expressed on v_mfma_f32_16x16x4_f32: a workgroup (4 waves)
-// carries 16 streams, so the same batch spreads over twice as many CUs and every MFMA / VALU phase is half as long.
-// The LSTM's two halves run on v_mfma_f32_16x16x32_bf16 instead, with weights and activations as exact three-piece bf16 splits
-// (X3_HALF below; vad_layout.h S_LSTM_X3).
+// there are.  This kernel is the same network, much of the same algebra (frame ingest under the recurrent gate half, 4-way folded
+// DFT, split-K enc2) and the same per-stream results, re-expressed on v_mfma_f32_16x16x4_f32: a workgroup (4 waves) carries 16
+// streams, so the same batch spreads over twice as many CUs and every MFMA / VALU phase is half as long.
+// The LSTM's two halves and encoder.0 run on v_mfma_f32_16x16x32_bf16 instead, with weights and activations as exact three-piece
+// bf16 splits (X3_HALF, X3_CONV below; vad_layout.h S_LSTM_X3, S_ENC0_X3); encoder.0 as a direct 3-tap convolution, not the Toom-3
+// product of silero_v5.hip.
 // The engine picks it when a call has at most T16_MAX_STREAMS streams (engine.cpp).
 //
 // Fragment convention (v_mfma_f32_16x16x4_f32, D = A[16 x 4] B[4 x 16] + C): lane l = (n = l & 15, kq = l >> 4).
@@ -27,6 +28,7 @@
 // Weight stream: pack_silero_v5_t16.
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#include <utility>
 #include "vad_layout.h"
 #include "sm_device.h"
 #include "vadk_device.h"
@@ -48,10 +50,9 @@ namespace {
 constexpr int MT16 = 16;
 constexpr int QSL = 17;                   // loader view: rows 64 c + .. of the folded operands (po 0.. | qo 16.. | pe+ 32.. | pe- 40.. | qe- 48.. | qe+ 56..), 192 rows
 constexpr int QSD = 16;                   // dense view of the same memory, used by everything else:
-//   rows 0..159 Toom-3 planes (32 p + ch/4); the Nyquist channel takes 8 rows (values on the kq = 0 row of a group of four, zeros
-//   on the other three): 160..163 = points 0, 1, -1, 2; 164..167 = infinity; rows 0..31 later enc1 output, then the LSTM input;
-//   rows 168.. = enc0 output (168 + 32 c + ch/4), then the enc2 partials (168 + 16 half + ch/4); then h_{t-1} (32 rows)
-constexpr int T_ROW_NYQ = 160;
+//   rows 0..95 the |STFT| columns (32 c + ch/4; 8 kHz: 16 c + ch/4; the Nyquist channel is in nyqv); rows 0..31 later enc1 output,
+//   then the LSTM input; rows 168.. = enc0 output (168 + 32 c + ch/4), then the enc2 partials (168 + 16 half + ch/4); then h_{t-1}
+//   (32 rows)
 constexpr int T_ROW_E = 168;
 constexpr int T_ROWS_X = 264;
 constexpr int T_ROWS_H = 32;
@@ -80,9 +81,15 @@ __device__ __forceinline__ f32x4 mfma16(f32x4 w, f32x4 a, f32x4 acc) {
     return acc;
 }
 
-// the LSTM's weight ring (S_LSTM_X3): units requested ahead, slots
+// the weight ring of the bf16-split layers (S_LSTM_X3, S_ENC0_X3): units requested ahead, slots
 constexpr int X3_D = 4;
 constexpr int X3_NR = X3_D + 1;
+
+// f(integral_constant<int, i>) for i = 0 .. N - 1, in order: every unit of a split layer is its own code, with constant indices
+template <class F, int... I>
+__device__ __forceinline__ void x3_units(F &&f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
 
 }  // namespace
 
@@ -129,6 +136,50 @@ constexpr int X3_NR = X3_D + 1;
         X3_STEP(0, B, SRC, EXTRA, FOLD) X3_STEP(1, B, SRC, EXTRA, FOLD)                                         \
         X3_STEP(2, B, SRC, EXTRA, FOLD) X3_STEP(3, B, SRC, EXTRA, FOLD)                                         \
     }
+// A direct 3-tap convolution on the bf16 split (encoder.0: vad_layout.h S_ENC0_X3, in the second weight stream - block offset B
+// into it): NO output columns
+// out(o) = sum_tap W[tap] x[STR o + tap - 1] over the three input columns x[c] at SRC(c) (quad rows, dense view), NT row tiles per
+// wave, NS K-steps of 32 channels.  Unit u = (K-step s, tap, tile) = (s * 3 + tap) * NT + tile: the tap's A fragment (3 blocks at
+// B + 3 u, ring slot (U0 + u) % X3_NR) feeds every output column that the tap reaches, mfma_x3 into ACC[o][tile] - the unit is
+// loaded once and used up to three times.  All three columns' activations are split once per K-step: K-step s + 1's quads are read
+// in the K-step's first unit and split one column per unit in units 1, 2, 3 (NT = 1: 1, 2, 2) under K-step s's MFMAs.  Requests
+// run X3_D units ahead.  EXTRA(u): work placed in unit u.
+#define X3_CONV(NS, NT, STR, NO, B, U0, SRC, ACC, EXTRA)                                              \
+    {                                                                                                           \
+        constexpr int NU_ = (NS) * 3 * (NT);                                                                    \
+        u32x4 F_[3][3], N_[3][3];                                                                               \
+        f32x4 na_[3], nb_[3];                                                                                   \
+        _Pragma("unroll") for (int c_ = 0; c_ < 3; ++c_) {                                                      \
+            const f32x4 a0_ = SRC(c_)[nq], b0_ = SRC(c_)[4 * QSD + nq];                                          \
+            _Pragma("unroll") for (int d_ = 0; d_ < 4; ++d_) split3_dword(a0_, b0_, d_, F_[c_]);                \
+        }                                                                                                       \
+        SB();                                                                                                   \
+        x3_units([&](auto uc_) {                                                                                \
+            constexpr int u_ = decltype(uc_)::value, s_ = u_ / (3 * (NT)), r_ = u_ % (3 * (NT));                \
+            constexpr int t_ = r_ / (NT), tl_ = r_ % (NT);                                                      \
+            if constexpr (u_ + X3_D < NU_) { X3_LDX((B) + 3 * (u_ + X3_D), (U0) + u_ + X3_D) }                  \
+            if constexpr (r_ == 0 && s_ + 1 < (NS)) {                                                           \
+                _Pragma("unroll") for (int c_ = 0; c_ < 3; ++c_) {                                              \
+                    na_[c_] = SRC(c_)[(8 * s_ + 8) * QSD + nq]; nb_[c_] = SRC(c_)[(8 * s_ + 12) * QSD + nq];    \
+                }                                                                                               \
+            }                                                                                                   \
+            EXTRA(u_)                                                                                           \
+            _Pragma("unroll") for (int o_ = 0; o_ < (NO); ++o_) {                                               \
+                const int c_ = (STR) * o_ + t_ - 1;                                                             \
+                if (c_ >= 0 && c_ < 3) ACC[o_][tl_] = mfma_x3(xw[((U0) + u_) % X3_NR], F_[c_], ACC[o_][tl_]);    \
+            }                                                                                                   \
+            if constexpr (s_ + 1 < (NS)) {                                                                      \
+                _Pragma("unroll") for (int c_ = 0; c_ < 3; ++c_)                                                \
+                    if (r_ == (1 + c_ < 3 * (NT) - 1 ? 1 + c_ : 3 * (NT) - 1))                                  \
+                        _Pragma("unroll") for (int d_ = 0; d_ < 4; ++d_) split3_dword(na_[c_], nb_[c_], d_, N_[c_]); \
+                if constexpr (r_ == 3 * (NT) - 1) {                                                             \
+                    _Pragma("unroll") for (int c_ = 0; c_ < 3; ++c_)                                            \
+                        _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) F_[c_][p_] = N_[c_][p_];               \
+                }                                                                                               \
+            }                                                                                                   \
+            SB();                                                                                               \
+        }, std::make_integer_sequence<int, NU_>{});                                                             \
+    }
 
 // RS: one tick for streams at other input rates (vad_step_rates): the tile first resamples its 16 chunks to 16 kHz into LDS -
 // AudioUtils.resample_audio's Fourier method as the folded operator of resample.hip, on 16 x 16 x 4 tiles - and the frame loop
@@ -154,9 +205,7 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
     static_assert(!(RS && K8), "the fused resampler feeds the 16 kHz model");
     constexpr int QL = K8 ? 8 : 16;               // loader lanes per stream = quads per quarter column
     constexpr int CS = 4 * QL;                    // folded-operand rows per column
-    constexpr int PS = K8 ? 16 : 32;              // quad rows per Toom-3 plane
-    constexpr int ROWN = K8 ? 80 : T_ROW_NYQ;     // the Nyquist channel's rows (8: values on the kq = 0 row of each group of four)
-    constexpr int NJ0 = K8 ? 4 : 8;               // k-iterations of enc0
+    constexpr int PS = K8 ? 16 : 32;              // quad rows per |STFT| column (enc0's input)
     __shared__ f32x4 lds[T_LDS_F4 + (RS ? MT16 * FQ : 0)];     // RS: + the tile's 16 kHz frames F (one workgroup per CU either way)
     f32x4 *const RX = lds;
     f32x4 *const RE = lds + T_ROW_E * QSD;
@@ -193,7 +242,10 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(KP(wstream)), 0, (int)KP(wstream_bytes), 0x00020000);
     const int lane16 = lane * 16;
 #define WL(blk) ldw(wrs, lane16, (blk))
-    const int o_stft = (int)P.sect[w][S_STFT], o_nyq = (int)P.sect[w][S_NYQ], o_e0 = (int)P.sect[w][S_ENC0];
+    // the second weight stream: encoder.0 on the bf16 split (S_ENC0_X3)
+    const __amdgpu_buffer_rsrc_t wrx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.wstream_x), 0, (int)P.wstream_x_bytes, 0x00020000);
+#define WX(blk) ldw(wrx, lane16, (blk))
+    const int o_stft = (int)P.sect[w][S_STFT], o_nyq = (int)P.sect[w][S_NYQ], o_x0 = (int)P.sect[w][S_ENC0_X3];
     const int o_e1 = (int)P.sect[w][S_ENC1], o_e2 = (int)P.sect[w][S_ENC2], o_e3 = (int)P.sect[w][S_ENC3];
     const int o_l = (int)P.sect[w][S_LSTM], o_x3 = (int)P.sect[w][S_LSTM_X3];
     const int T = (ONE || RS) ? 1 : KP(T);
@@ -322,8 +374,11 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
     SB();
     // The LSTM's weights come from S_LSTM_X3 (vad_layout.h): per half 32 units u = 8 s + tile (K-step s, tile = 2 q + rt), each the
     // three bf16 pieces of the tile's A fragment (3 blocks).  They stream through a ring of X3_NR units, requested X3_D units ahead.
+    // encoder.0 streams its own through the same ring (S_ENC0_X3, X3_CONV).
     f32x4 xw[X3_NR][3];
-#define X3_LD(B, u) _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) xw[(u) % X3_NR][p_] = WL((B) + 3 * (u) + p_);
+#define X3_LDR(blk, slot) _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) xw[(slot) % X3_NR][p_] = WL((blk) + p_);
+#define X3_LD(B, u) X3_LDR((B) + 3 * (u), (u))
+#define X3_LDX(blk, slot) _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) xw[(slot) % X3_NR][p_] = WX((blk) + p_);
 #define H_FIRST(L, tt)                                                                                          \
     {                                                                                                           \
         _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LD((L) + LSTM_X3_HALF_BLOCKS, u_) }             \
@@ -691,8 +746,8 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
 
     STAMP(0);
     for (int t = 0;;) {                          // T >= 1; the back edge is at the bottom, behind the next frame's first requests
-        int ws_stft = o_stft, ws_e0 = o_e0, ws_e1 = o_e1, ws_e2 = o_e2, ws_e3 = o_e3, ws_l = o_l, ws_x3 = o_x3;
-        asm volatile("" : "+s"(ws_stft), "+s"(ws_e0), "+s"(ws_e1), "+s"(ws_e2), "+s"(ws_e3), "+s"(ws_l), "+s"(ws_x3));
+        int ws_stft = o_stft, ws_x0 = o_x0, ws_e1 = o_e1, ws_e2 = o_e2, ws_e3 = o_e3, ws_l = o_l, ws_x3 = o_x3;
+        asm volatile("" : "+s"(ws_stft), "+s"(ws_x0), "+s"(ws_e1), "+s"(ws_e2), "+s"(ws_e3), "+s"(ws_l), "+s"(ws_x3));
         // ---- recurrent gate half W_hh . h_{t-1} (4 K-steps x {4 gates x 2 row tiles}, bf16 split) with the frame ingested under it ----
         f32x4 G[8];                               // gate q, row tile rt -> G[2 q + rt]
         {
@@ -816,7 +871,11 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
             if (pair < 48 && pt == 0) nyqv[c * 16 + ms] = fabsf(a + fcor[(c * 3 + 0) * 16 + ms] + fcor[(c * 3 + 1) * 16 + ms]);
         }
 
-        f32x4 e0b[2], E0w[10];
+        // enc0's fp32 blocks (bias, Nyquist taps) and its first X3_D units, requested before barrier (1b)
+        f32x4 e0f[ENC0_X3_F32_BLOCKS];
+#define E0_FIRST                                                                                                \
+    _Pragma("unroll") for (int k = 0; k < ENC0_X3_F32_BLOCKS; ++k) e0f[k] = WX(ws_x0 + k);                      \
+    _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LDX(ws_x0 + ENC0_X3_F32_BLOCKS + 3 * u_, u_) }
         if constexpr (K8) {
             // ---- STFT, 8 kHz sub-model: 64 complex bins = four 16-row tiles, ONE per wave (pack_dft4_wave_128_t16): wave w owns the
             //      bins 2 (16 (w & 1) + r) + (w >> 1), r = 0..15 - waves 0 / 1 the even bins (pe | qe), 2 / 3 the odd ones (po | qo);
@@ -850,28 +909,13 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
                 }
                 SB();
             }
-            e0b[0] = WL(ws_e0); e0b[1] = WL(ws_e0 + 1);
-#pragma unroll
-            for (int k = 0; k < 10; ++k) E0w[k] = WL(ws_e0 + 2 + k);
+            E0_FIRST
             SB();
             __syncthreads();   // (1b) every wave is done reading the folded operands: the magnitudes may overwrite them
-            {   // |.| -> Toom-3 evaluation planes, rows 16 p + channel / 4 = 16 p + 4 w + kq
-                f32x4 mg[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) mg[c] = pk::mag(sre[c], sim[c]);
-                const f32x4 s02 = pk::add(mg[0], mg[2]);
+            {   // |.| of the three columns -> rows 16 c + channel / 4 = 16 c + 4 w + kq
                 f32x4 *o = RX + (4 * w) * QSD + nq;
-                st2(o, mg[0]);
-                st2(o + PS * QSD, pk::add(s02, mg[1]));
-                st2(o + 2 * PS * QSD, pk::sub(s02, mg[1]));
-                st2(o + 3 * PS * QSD, pk::fma(pk::splat(4.f), mg[2], pk::fma(pk::splat(2.f), mg[1], mg[0])));
-                st2(o + 4 * PS * QSD, mg[2]);
-            }
-            if (tid < 64) {      // |X64|: values on the kq = 0 rows (80, 84), zeros on the other three of each group
-                const float n0 = nyqv[n], n1 = nyqv[16 + n], n2 = nyqv[32 + n];
-                const f32x4 z4 = f32x4{0.f, 0.f, 0.f, 0.f};
-                RX[ROWN * QSD + nq] = kq == 0 ? f32x4{n0, (n0 + n2) + n1, (n0 + n2) - n1, fmaf(4.f, n2, fmaf(2.f, n1, n0))} : z4;
-                RX[(ROWN + 4) * QSD + nq] = kq == 0 ? f32x4{n2, 0.f, 0.f, 0.f} : z4;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) st2(o + PS * c * QSD, pk::mag(sre[c], sim[c]));
             }
         } else
         // ---- STFT: wave w owns bins bin_of_channel_fold3(32 w + 16 rt + r): row tile 0 = 16 odd bins, cos on po, -sin on qo, K = 64
@@ -925,93 +969,51 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
 #undef S_MMA
 #undef S_ROW_R
 #undef S_ROW_I
-            e0b[0] = WL(ws_e0); e0b[1] = WL(ws_e0 + 1);
-#pragma unroll
-            for (int k = 0; k < 10; ++k) E0w[k] = WL(ws_e0 + 2 + k);
+            E0_FIRST
             SB();
             __syncthreads();   // (1b) every wave is done reading the folded operands: the magnitudes may overwrite them
-            // |.| -> Toom-3 evaluation planes, rows 32 p + 8 w + 4 rt + kq
+            // |.| of the three columns -> rows 32 c + 8 w + 4 rt + kq
 #pragma unroll
             for (int rt = 0; rt < 2; ++rt) {
-                f32x4 mg[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) mg[c] = pk::mag(are[c][rt], aim[c][rt]);
-                const f32x4 s02 = pk::add(mg[0], mg[2]);
                 f32x4 *o = RX + (8 * w + 4 * rt) * QSD + nq;
-                st2(o, mg[0]);
-                st2(o + 32 * QSD, pk::add(s02, mg[1]));
-                st2(o + 64 * QSD, pk::sub(s02, mg[1]));
-                st2(o + 96 * QSD, pk::fma(pk::splat(4.f), mg[2], pk::fma(pk::splat(2.f), mg[1], mg[0])));
-                st2(o + 128 * QSD, mg[2]);
-            }
-            if (tid < 64) {      // |X128|: values on the kq = 0 rows (160, 164), zeros on the other three of each group
-                const float n0 = nyqv[n], n1 = nyqv[16 + n], n2 = nyqv[32 + n];
-                const f32x4 z4 = f32x4{0.f, 0.f, 0.f, 0.f};
-                RX[T_ROW_NYQ * QSD + nq] = kq == 0 ? f32x4{n0, (n0 + n2) + n1, (n0 + n2) - n1, fmaf(4.f, n2, fmaf(2.f, n1, n0))} : z4;
-                RX[(T_ROW_NYQ + 4) * QSD + nq] = kq == 0 ? f32x4{n2, 0.f, 0.f, 0.f} : z4;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) st2(o + PS * c * QSD, pk::mag(are[c][rt], aim[c][rt]));
             }
         }
+#undef E0_FIRST
         STAMP(3);
         __syncthreads();   // (2) magnitudes complete
         STAMP(4);
 
-        // ---- enc0 (Toom-3): five point-wise contractions over 128 channels (8 k-iterations) + the Nyquist channel ----
+        // ---- enc0: 129 (8 kHz: 65) -> 128 ch, k3 s1 p1, 3 -> 3 columns, as a direct 3-tap convolution on the bf16 split (X3_CONV):
+        //      per K-step 3 taps x 2 row tiles = 6 units, 7 column products per tile; the Nyquist channel and the bias on the VALU ----
+        constexpr int NU0 = (K8 ? 2 : 4) * 3 * 2;     // enc0's units: its K-steps x 3 taps x 2 row tiles
         f32x4 e1b[2], E1w[2];
         {
-            const int ws = ws_e0 + 2;
-            f32x4 acc[5][2];
+            f32x4 acc[3][2];
+            {   // accumulators start at the bias plus the Nyquist channel's terms sum_tap W[tap] |X_N|[o + tap - 1], exact fp32 fmas
+                const float nv[3] = {nyqv[n], nyqv[16 + n], nyqv[32 + n]};
 #pragma unroll
-            for (int p = 0; p < 5; ++p) acc[p][0] = acc[p][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-            f32x4 Aw[10], Bw[10], Aa[5], Ba[5];
+                for (int o = 0; o < 3; ++o)
 #pragma unroll
-            for (int k = 0; k < 10; ++k) Aw[k] = E0w[k];
+                    for (int rt = 0; rt < 2; ++rt) {
+                        f32x4 a = e0f[rt];
 #pragma unroll
-            for (int p = 0; p < 5; ++p) Aa[p] = RX[(PS * p) * QSD + nq];
-#define E0_LD(S, jj)                                                                       \
-    _Pragma("unroll") for (int k = 0; k < 10; ++k) S##w[k] = WL(ws + 10 * (jj) + k);       \
-    _Pragma("unroll") for (int p = 0; p < 5; ++p) S##a[p] = RX[(PS * p + 4 * (jj)) * QSD + nq];
-#define E0_MMA(S)                                                                          \
-    _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                       \
-        _Pragma("unroll") for (int p = 0; p < 5; ++p) {                                    \
-            acc[p][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(S##w[2 * p][j_], S##a[p][j_], acc[p][0], 0, 0, 0);         \
-            acc[p][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(S##w[2 * p + 1][j_], S##a[p][j_], acc[p][1], 0, 0, 0);     \
-        }
-            for (int j = 0; j < NJ0; j += 2) {
-                E0_LD(B, j + 1) E0_MMA(A) T16_IL(10, 5) SB();
-                const int jn = j + 2 < NJ0 ? j + 2 : NJ0 - 2;
-                E0_LD(A, jn) E0_MMA(B) T16_IL(10, 5) SB();
+                        for (int t = 0; t < 3; ++t)
+                            if (o + t - 1 >= 0 && o + t - 1 < 3) a = pk::fma(e0f[2 + 2 * t + rt], pk::splat(nv[o + t - 1]), a);
+                        acc[o][rt] = a;
+                    }
             }
-#undef E0_LD
-#undef E0_MMA
-            {   // input channel 128 (Nyquist bin): K = 4 MFMAs whose k = 1..3 slots are zero on both operands
-                const f32x4 an = RX[ROWN * QSD + nq], bn = RX[(ROWN + 4) * QSD + nq];
-                const f32x4 wa0 = WL(ws + 10 * NJ0), wa1 = WL(ws + 10 * NJ0 + 1), wb0 = WL(ws + 10 * NJ0 + 2), wb1 = WL(ws + 10 * NJ0 + 3);
-                e1b[0] = WL(ws_e1); e1b[1] = WL(ws_e1 + 1);
-                E1w[0] = WL(ws_e1 + 2); E1w[1] = WL(ws_e1 + 3);
-                SB();
-                acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa0.x, an.x, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa1.x, an.x, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa0.y, an.y, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa1.y, an.y, acc[1][1], 0, 0, 0);
-                acc[2][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa0.z, an.z, acc[2][0], 0, 0, 0);
-                acc[2][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa1.z, an.z, acc[2][1], 0, 0, 0);
-                acc[3][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa0.w, an.w, acc[3][0], 0, 0, 0);
-                acc[3][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa1.w, an.w, acc[3][1], 0, 0, 0);
-                acc[4][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wb0.x, bn.x, acc[4][0], 0, 0, 0);
-                acc[4][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wb1.x, bn.x, acc[4][1], 0, 0, 0);
-            }
+#define E0_SRC(c) (RX + PS * (c) * QSD)
+#define E0_EXTRA(u) if constexpr ((u) == NU0 - X3_D) { e1b[0] = WL(ws_e1); e1b[1] = WL(ws_e1 + 1); E1w[0] = WL(ws_e1 + 2); E1w[1] = WL(ws_e1 + 3); }
+            X3_CONV(K8 ? 2 : 4, 2, 1, 3, ws_x0 + ENC0_X3_F32_BLOCKS, 0, E0_SRC, acc, E0_EXTRA)
+#undef E0_SRC
+#undef E0_EXTRA
 #pragma unroll
-            for (int rt = 0; rt < 2; ++rt) {      // interpolation (P(1), P(-1) arrive halved) + bias + ReLU -> rows 168 + 32 c + 8 w + 4 rt + kq
-                const f32x4 bias = e0b[rt];
-                const f32x4 y0 = acc[0][rt], y4 = acc[4][rt];
-                const f32x4 bb = pk::sub(acc[1][rt], acc[2][rt]);
-                const f32x4 y2 = pk::sub(pk::sub(pk::add(acc[1][rt], acc[2][rt]), y0), y4);
-                const f32x4 t2 = pk::fma(y4, pk::splat(-16.0f), pk::fma(y2, pk::splat(-4.0f), pk::sub(acc[3][rt], y0)));
-                const f32x4 y3 = pk::fma(bb, pk::splat(-1.0f / 3.0f), pk::mul(t2, pk::splat(1.0f / 6.0f)));
+            for (int rt = 0; rt < 2; ++rt) {      // ReLU -> rows 168 + 32 o + 8 w + 4 rt + kq
                 f32x4 *o = RE + (8 * w + 4 * rt) * QSD + nq;
-                o[0] = relu4(pk::add(pk::sub(bb, y3), bias));
-                o[32 * QSD] = relu4(pk::add(y2, bias));
-                o[64 * QSD] = relu4(pk::add(y3, bias));
+#pragma unroll
+                for (int c = 0; c < 3; ++c) o[32 * c * QSD] = relu4(acc[c][rt]);
             }
         }
         STAMP(5);
@@ -1152,10 +1154,14 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
         if constexpr (!RS) H_FIRST(ws_x3, t)       // the next frame's first requests
     }
 #undef H_FIRST
+#undef X3_CONV
 #undef X3_HALF
 #undef X3_STEP
 #undef X3_UNIT
 #undef X3_LD
+#undef X3_LDR
+#undef X3_LDX
+#undef WX
 #undef X_ISSUE
 #undef WL
     if (sm_thread && P.seg_frames) P.seg_frames[gf] = seg_last;

@@ -51,13 +51,21 @@ constexpr int ENC1_BLOCKS = 4 + 2 * 16;
 constexpr int ENC2_BLOCKS = 4 + 2 * 8;     // packed for waves 0,1; waves 2,3 read the second K half of the same streams
 constexpr int ENC3_BLOCKS = 4 + 8;
 constexpr int LSTM_BLOCKS = 16 + 64 + 64 + 4;  // bias(4 gates), W_ih, W_hh, head weights
-enum Section { S_STFT = 0, S_NYQ, S_ENC0, S_ENC1, S_ENC2, S_ENC3, S_LSTM, S_HEADB, S_LSTM_X3, S_COUNT };  // S_HEADB: 1 block, float 0 = head bias
+enum Section { S_STFT = 0, S_NYQ, S_ENC0, S_ENC1, S_ENC2, S_ENC3, S_LSTM, S_HEADB, S_LSTM_X3, S_ENC0_X3, S_COUNT };  // S_HEADB: 1 block, float 0 = head bias
 // S_LSTM_X3 (16-stream kernel only, pack_silero_v5_t16): the wave's W_ih and W_hh rows once more, as three exact bf16 pieces
 // w = w1 + w2 + w3 (w1 = hi16(w), w2 = hi16(w - w1), w3 = w - w1 - w2) for v_mfma_f32_16x16x32_bf16.  Per half (W_ih, then W_hh):
 // 4 K-steps s x 8 row tiles (gate q, rt: tile 2 q + rt) x 3 pieces, block (s * 8 + tile) * 3 + piece.  A block is the tile's A
 // fragment: lane (row l & 15, kq = l >> 4) holds 8 bf16, elements 0..3 = K 32 s + 4 kq + 0..3 and elements 4..7 = K 32 s + 16 +
 // 4 kq + 0..3 - the two activation quads 8 s + kq and 8 s + 4 + kq that the lane reads as it does for the fp32 form.
 constexpr int LSTM_X3_HALF_BLOCKS = 4 * 8 * 3;
+// S_ENC0_X3 (16-stream kernel only): the SECOND weight stream (PackedWeights::data_x, StepParams::wstream_x; its sect entries are
+// block offsets into it) - the first stream keeps every byte it had.  encoder.0 as a DIRECT 3-tap convolution, out(o) = sum_tap
+// W[tap] x[o + tap - 1] (x[-1] = x[3] = 0).  Wave w = output channels 32 w + 16 rt + r: ENC0_X3_F32_BLOCKS fp32 blocks in the D
+// layout of a row tile (vector_block16) - the bias (rt 0, 1), then the Nyquist input channel's taps 0, 1, 2 (rt 0, 1 each) - then
+// one unit of three blocks per (K-step s < 4 (8 kHz: 2), tap, rt): block ENC0_X3_F32_BLOCKS + 3 ((s * 3 + tap) * 2 + rt) + piece,
+// the pieces of the tile's A fragment as in S_LSTM_X3 (lane (row l & 15, kq), element e = K 32 s + 16 (e >> 2) + 4 kq + (e & 3)),
+// piece 0 first; input channel K = the STFT's channel order (bin_of_channel_fold3 / bin_of_channel_8k).
+constexpr int ENC0_X3_F32_BLOCKS = 2 + 3 * 2;
 __host__ __device__ constexpr int bin_of_channel(int ch) {
     return (ch >> 5) < 2 ? 64 * (ch >> 5) + 2 * (ch & 31) : 64 * ((ch >> 5) - 2) + 2 * (ch & 31) + 1;
 }
@@ -181,6 +189,8 @@ struct StepParams {
     int32_t fmt;                   // vad_frame_format
     float thresh;                  // denoise gate, < 0 = off
     int32_t variant;               // 1 = the graph's 8 kHz sub-model (pack_weights.h): V4 two LSTM steps per frame, V5 256-sample frames
+    const float *wstream_x;        // second weight stream (PackedWeights::data_x), or nullptr
+    uint32_t wstream_x_bytes;
 #ifdef VADK_STAMPS
     unsigned long long *stamps;    // diagnostic builds only (tools/kbench.cpp): [block][wave][16] s_memtime stamps
 #endif

@@ -76,6 +76,13 @@ int main(int argc, char **argv) {
     CK(hipMalloc(&d_probs, (size_t)B * T * 4));
     p.wstream = d_w;
     p.wstream_bytes = (uint32_t)(pw.data.size() * 4);
+    if (!pw.data_x.empty()) {        // the second stream (the 16-stream V5 packing's split encoder.0)
+        float *d_wx;
+        CK(hipMalloc(&d_wx, pw.data_x.size() * 4));
+        CK(hipMemcpy(d_wx, pw.data_x.data(), pw.data_x.size() * 4, hipMemcpyHostToDevice));
+        p.wstream_x = d_wx;
+        p.wstream_x_bytes = (uint32_t)(pw.data_x.size() * 4);
+    }
     memcpy(p.sect, pw.sect, sizeof pw.sect);
     p.state = d_state; p.sm = d_sm; p.slots = nullptr; p.probs = d_probs; p.events = nullptr; p.seg_frames = nullptr;
     p.n = B; p.T = T; p.fmt = 0; p.thresh = 0.01f;
