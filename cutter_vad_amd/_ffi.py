@@ -26,6 +26,7 @@ VAD_ERR_BUSY = -8
 
 VAD_FMT_F32, VAD_FMT_I16_32767, VAD_FMT_I16_32768 = 0, 1, 2
 VAD_EV_START, VAD_EV_END, VAD_EV_CONTINUE = 1, 2, 4
+VAD_EV_REJECTED = 0x80          # ABI 5: the frame held a NaN / Inf sample (include/vad_engine.h); probability NaN, state untouched
 VAD_FRAME_SAMPLES = 512
 VAD_STATE_FLOATS = 256
 VAD_STREAM_SAVE_BYTES = 1120
@@ -110,6 +111,7 @@ class TickWork(C.Structure):
 
 
 VAD_WORK_START, VAD_WORK_END, VAD_WORK_CONTINUE, VAD_WORK_PAYLOAD, VAD_WORK_LONG = 1, 2, 4, 8, 16
+VAD_WORK_REJECTED = 32
 
 # name -> (restype, argtypes); mirrors include/vad_engine.h one-to-one
 _vp, _i64p, _f32p, _u8p, _i32p = C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)

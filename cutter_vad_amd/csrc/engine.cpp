@@ -2243,6 +2243,10 @@ int vad_tick_run(vad_engine *e, float denoise_thresh, vad_tick_result *out) {
                         auto it = e->tick_tails.find((int64_t)sl);
                         if (it != e->tick_tails.end() && !it->second.empty()) tails = &it->second;
                     }
+                    if (ev & VAD_EV_REJECTED) {            // a non-finite frame: as if never pushed (its staged tail is spent)
+                        if (tails) tails->pop_front();
+                        continue;
+                    }
                     if (!st.active && !above) {                                            // idle stream: nothing is kept (:873-874)
                         if (!st.pre.empty()) st.pre.clear(e->seg_arena);
                         if (tails) tails->pop_front();
@@ -2297,13 +2301,20 @@ int vad_tick_run_work(vad_engine *e, float denoise_thresh, vad_tick_result *out,
         const int64_t sl = out->slots[k];
         if (sl < 0 || sl >= work->n_slots) return e->fail(VAD_ERR_INVALID_ARG, "vad_tick_run_work: slot %lld beyond the caller's arrays (%lld)", (long long)sl, (long long)work->n_slots);
         const uint8_t ev = out->events[k];
+        const bool long_frame = k < first_rate_entry && out->nsamples[k] > e->frame_samples;
+        if (ev & VAD_EV_REJECTED) {                             // the slot's last_prob / frames_done / active stay as they were
+            e->work_index.push_back((int32_t)k);
+            e->work_kind.push_back((uint8_t)(VAD_WORK_REJECTED | (long_frame ? VAD_WORK_LONG : 0)));
+            e->work_samples.push_back(0);
+            continue;
+        }
         const bool was = work->active[sl] != 0, started = (ev & VAD_EV_START) != 0, ended = (ev & VAD_EV_END) != 0;
         work->last_prob[sl] = out->probs[k];
         work->frames_done[sl] += 1;
         work->active[sl] = (uint8_t)((was || started) && !ended);
         uint8_t kind = (uint8_t)((started ? VAD_WORK_START : 0) | (ended ? VAD_WORK_END : 0));
         if (was && work->continue_cb[sl]) kind |= (uint8_t)(VAD_WORK_CONTINUE | (work->continue_payload[sl] ? VAD_WORK_PAYLOAD : 0));
-        if (k < first_rate_entry && out->nsamples[k] > e->frame_samples) kind |= VAD_WORK_LONG;
+        if (long_frame) kind |= VAD_WORK_LONG;
         if (kind) {
             e->work_index.push_back((int32_t)k);
             e->work_kind.push_back(kind);

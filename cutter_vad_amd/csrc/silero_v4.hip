@@ -79,7 +79,9 @@ __device__ __forceinline__ float lognorm(float mag, float mm) { return log1p20(m
 template <bool K8>
 __global__ void __launch_bounds__(NTHREADS, 1) silero_v4_step(const StepParams P, const int tframe) {
     using namespace vadk::v4;
-    __shared__ f32x4 lds[V4_LDS_F4];
+    __shared__ f32x4 lds[V4_LDS_F4 + 4];
+    // [2][32] bytes: stream s's frame rejected (VAD_EV_REJECTED) when flagL[s] | flagL[32 + s] - one per half of its samples
+    uint8_t *const flagL = reinterpret_cast<uint8_t *>(lds + V4_LDS_F4);
     // =================================================================================================
     //  STFT part
     // =================================================================================================
@@ -134,12 +136,18 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v4_step(const StepParams P
                 const int idx = it * NTHREADS + tid;
                 xv[it] = __builtin_amdgcn_raw_buffer_load_b128(frs, (((tile0 + (idx >> 7)) * T + tframe) * 128 + (idx & 127)) * 16, 0, 0);
             }
+            // stream 2 it + (w >> 1) has its quads 64 (w & 1) .. + 63 in wave w: a ballot per stream, bit `it` of a uniform mask
+            uint32_t badm = 0;
 #pragma unroll
             for (int it = 0; it < 16; ++it) {
                 const int idx = it * NTHREADS + tid;
-                XP[(idx >> 7) * XPQ + 24 + (idx & 127)] = gate4(__builtin_bit_cast(f32x4, xv[it]), thr);
+                const f32x4 v = __builtin_bit_cast(f32x4, xv[it]);
+                badm |= (__builtin_amdgcn_ballot_w64(nonfinite(absmax4(0.f, v))) != 0 ? 1u : 0u) << it;
+                XP[(idx >> 7) * XPQ + 24 + (idx & 127)] = gate4(v, thr);
             }
+            flagL[(w & 1) * 32 + 2 * (lane & 15) + (w >> 1)] = (uint8_t)((badm >> (lane & 15)) & 1u);
         } else {
+            if (tid < 64) flagL[tid] = 0;              // int16 samples are finite
             const float sc = P.fmt == 1 ? 32767.0f : 32768.0f, rsc = 1.0f / sc;
             u32x2 sv[16];
 #pragma unroll
@@ -774,7 +782,7 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v4_step(const StepParams P
                 CELL(x) CELL(y) CELL(z) CELL(w)
 #undef CELL
                 cprev[layer][e] = cn;
-                if (step == T3 - 1 && live) {
+                if (step == T3 - 1 && live && !(flagL[m] | flagL[32 + m])) {    // a rejected frame leaves h and c as they were
                     *reinterpret_cast<f32x4 *>(st + 128 + 64 * layer + unit) = cn;
                     *reinterpret_cast<f32x4 *>(st + 64 * layer + unit) = hn;
                 }
@@ -805,11 +813,13 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v4_step(const StepParams P
         if (K8)     // ReduceMean over the two time steps
             p = (p + sigmoidf_(hb + ((headp[128 + tid] + headp[160 + tid]) + (headp[192 + tid] + headp[224 + tid])))) * 0.5f;
         p = fminf(p, 1.0f);
-        P.probs[(size_t)(tile0 + tid) * T + tframe] = p;
+        // rejected (include/vad_engine.h): NaN and VAD_EV_REJECTED alone, no sm_step, the state machine as it was
+        const bool bad = (flagL[tid] | flagL[32 + tid]) != 0;
+        P.probs[(size_t)(tile0 + tid) * T + tframe] = bad ? __builtin_nanf("") : p;
         SmSlot sm = smL[tid];
         int seg = 0;
-        const int ev = sm_step(sm, p, &seg);
-        P.sm[sm_slot] = sm;
+        const int ev = bad ? EV_REJECTED : sm_step(sm, p, &seg);
+        if (!bad) P.sm[sm_slot] = sm;
         if (P.events) P.events[(size_t)(tile0 + tid) * T + tframe] = (uint8_t)ev;
         if (P.seg_frames) {
             if (ev & 2) P.seg_frames[tile0 + tid] = seg;

@@ -52,7 +52,7 @@ constexpr int T_MISC_FLOATS = 16 + 8 * 16 + 2 * 4 * 16;      // mm [16], colmean
 constexpr int K2_F4 = T_ROWS * QSD + T_MISC_FLOATS / 4 + 128;   // + partial log sums [4 waves][8 columns][16]
 constexpr int R_NY = 64;                          // tail: |X128| [8 columns][16 streams] as floats in rows 64, 65 (past the partial tiles)
 constexpr int T16_LDS_F4 = K1_F4 > K2_F4 ? K1_F4 : K2_F4;
-static_assert(T16_LDS_F4 * 16 <= 80 * 1024, "two workgroups per CU");
+static_assert((T16_LDS_F4 + 2) * 16 <= 80 * 1024, "two workgroups per CU");   // + 2: the frame's rejection flags
 
 __device__ __forceinline__ f32x4 ldt(__amdgpu_buffer_rsrc_t rs, int row, int blk) {   // table row (float4) of a VALU table
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, row * 16, blk * 1024, 0));
@@ -124,7 +124,8 @@ __device__ __forceinline__ f32x4 log1p20_4(f32x4 mag) {     // the same three op
 template <bool K8>
 __global__ void __launch_bounds__(NTHREADS, 2) silero_v4_step16(const StepParams P, const int tframe) {
     using namespace vadk::v4;
-    __shared__ f32x4 lds[T16_LDS_F4];
+    __shared__ f32x4 lds[T16_LDS_F4 + 2];
+    uint8_t *const flagL = reinterpret_cast<uint8_t *>(lds + T16_LDS_F4);   // [16] stream s's frame rejected (VAD_EV_REJECTED)
     f32x4 *const XP = lds;
     f32x4 *const UV = lds + U_XS;
     float *const nyqv = reinterpret_cast<float *>(UV + U_UV);    // [2][16] |X128| of the two columns in flight
@@ -177,6 +178,7 @@ __global__ void __launch_bounds__(NTHREADS, 2) silero_v4_step16(const StepParams
     const float thr = P.thresh;
     const bool f32in = P.fmt == 0;
     const float isc = P.fmt == 1 ? 32767.0f : 32768.0f, risc = 1.0f / isc;
+    float xm = 0.f;                  // float32: running max |x| of this thread's raw samples, before the gate (vadk_device.h absmax4)
     u32x4 xv[8];
     const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void *>(P.frames), 0, (int)((unsigned)P.n * (unsigned)T * (f32in ? 2048u : 1024u)), 0x00020000);
@@ -199,6 +201,8 @@ __global__ void __launch_bounds__(NTHREADS, 2) silero_v4_step16(const StepParams
             const int s0 = (int)(short)(xv[it].x & 0xffffu), s1 = (int)(short)(xv[it].x >> 16);             \
             const int s2 = (int)(short)(xv[it].y & 0xffffu), s3 = (int)(short)(xv[it].y >> 16);             \
             v_ = f32x4{i16_div(s0, isc, risc), i16_div(s1, isc, risc), i16_div(s2, isc, risc), i16_div(s3, isc, risc)};   \
+        } else {                                                                                            \
+            xm = absmax4(xm, v_);                                                                           \
         }                                                                                                   \
         XP[fms * XPQ + 24 + 16 * (it) + fq] = gate4(v_, thr);                                               \
     }
@@ -382,7 +386,12 @@ __global__ void __launch_bounds__(NTHREADS, 2) silero_v4_step16(const StepParams
             }
         nyq[grp] = nyqv[((tid >> 4) & 1) * 16 + n];
         if (grp == 0) { X_PUT(4) X_PUT(5) }
-        if (grp == 1) { X_PUT(6) X_PUT(7) }
+        if (grp == 1) {
+            X_PUT(6) X_PUT(7)
+            // every sample is staged: the 16 lanes of stream fms vote, all write the verdict; the barrier below publishes it
+            const unsigned long long b_ = __builtin_amdgcn_ballot_w64(nonfinite(xm));
+            flagL[fms] = (uint8_t)(((b_ >> (lane & 48)) & 0xffffull) != 0);
+        }
         if (grp == 0) STAMP(5);
         __syncthreads();       // every wave done with UV / fcor / dcv before the next fold overwrites them
         if (grp == 0) STAMP(6);
@@ -795,7 +804,7 @@ __global__ void __launch_bounds__(NTHREADS, 2) silero_v4_step16(const StepParams
                 CELL(x) CELL(y) CELL(z) CELL(w)
 #undef CELL
                 cprev[layer] = cn;
-                if (step == T3 - 1 && live) {
+                if (step == T3 - 1 && live && !flagL[n]) {     // a rejected frame leaves h and c as they were
                     *reinterpret_cast<f32x4 *>(st + 128 + 64 * layer + unit) = cn;
                     *reinterpret_cast<f32x4 *>(st + 64 * layer + unit) = hn;
                 }
@@ -821,13 +830,15 @@ __global__ void __launch_bounds__(NTHREADS, 2) silero_v4_step16(const StepParams
         if (K8)     // ReduceMean over the two time steps
             p = (p + sigmoidf_(hb + ((headp[64 + tid] + headp[80 + tid]) + (headp[96 + tid] + headp[112 + tid])))) * 0.5f;
         p = fminf(p, 1.0f);
-        P.probs[(size_t)(tile0 + tid) * T + tframe] = p;
+        // rejected (include/vad_engine.h): NaN and VAD_EV_REJECTED alone, no sm_step, the state machine as it was
+        const bool bad = flagL[tid] != 0;
+        P.probs[(size_t)(tile0 + tid) * T + tframe] = bad ? __builtin_nanf("") : p;
         SmSlot sm;
 #pragma unroll
         for (int k = 0; k < 6; ++k) reinterpret_cast<f32x4 *>(&sm)[k] = smq[k];
         int seg = 0;
-        const int ev = sm_step(sm, p, &seg);
-        P.sm[slot] = sm;
+        const int ev = bad ? EV_REJECTED : sm_step(sm, p, &seg);
+        if (!bad) P.sm[slot] = sm;
         if (P.events) P.events[(size_t)(tile0 + tid) * T + tframe] = (uint8_t)ev;
         if (P.seg_frames) {
             if (ev & 2) P.seg_frames[tile0 + tid] = seg;

@@ -60,7 +60,7 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step(const float *k_wst
     constexpr int ROWN = K8 ? ROW_NYQ_8K : ROW_NYQ;
     constexpr int NJ = K8 ? 4 : 8;                // k-iterations of the folded DFT
     constexpr int NJ0 = K8 ? 8 : 16;              // k-iterations of enc0
-    __shared__ f32x4 lds[LDS_F4];
+    __shared__ f32x4 lds[LDS_F4 + (F32IN ? 2 : 0)];     // float32: + the frame's rejection flags
     f32x4 *const RX = lds;                       // the activation region (row map: vad_layout.h)
     f32x4 *const RE = lds + ROW_E * QS;          // its upper half
     f32x4 *const RH = lds + ROWS_X * QS;         // h
@@ -70,6 +70,7 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step(const float *k_wst
     SmSlot *const smL = reinterpret_cast<SmSlot *>(fcor + 288 + 64);   // the tile's 32 state machines, resident for the call
     f32x4 *const biasL = reinterpret_cast<f32x4 *>(smL + MT);          // gate biases, compact: [4 waves][4 gates][8 quads of units]
     constexpr int FCOR_SINK = 288;               // [64] floats after fcor: where lanes q != 0 drop their (unused) correction terms
+    uint8_t *const flagL = reinterpret_cast<uint8_t *>(lds + LDS_F4);   // F32IN: [32] bytes, stream s's frame rejected (VAD_EV_REJECTED)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -213,16 +214,27 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step(const float *k_wst
             // with sched_group_barrier: its LDS writes and the W_hh requests overlap the MFMAs; its VALU work does NOT
             // (tools/ubench/mfma_valu.hip: an fp32 MFMA and VALU instructions of the same wave serialise, 64 + 4.4 n
             // cycles), so the fold costs what its instruction count says.
-            // int16 payloads are raw bits: decode (true division, like np.int16 -> float32 / 32767.0), then gate
-            auto decode = [&](u32x4 b) -> f32x4 {
+            // int16 payloads are raw bits: decode (true division, like np.int16 -> float32 / 32767.0), then gate.  float32: the
+            // running max |x| of the raw samples of stream half rr (vadk_device.h absmax4), before the gate
+            float xm[2] = {0.f, 0.f};
+            auto decode = [&](u32x4 b, float &m_) -> f32x4 {
                 f32x4 v = __builtin_bit_cast(f32x4, b);
                 if constexpr (!f32in) {
                     const int s0 = (int)(short)(b.x & 0xffffu), s1 = (int)(short)(b.x >> 16);
                     const int s2 = (int)(short)(b.y & 0xffffu), s3 = (int)(short)(b.y >> 16);
                     v = f32x4{i16_div(s0, sc, rsc), i16_div(s1, sc, rsc), i16_div(s2, sc, rsc), i16_div(s3, sc, rsc)};
+                } else {
+                    m_ = absmax4(m_, v);
                 }
                 return gate4(v, thr);
             };
+            // after the frame's last fold call: the QL loader lanes of a stream vote (a ballot, no branch) and all of them write
+            // the verdict; barrier (1) publishes it to the cell and the head
+#define X_FLAG(MS, XM)                                                                                          \
+    if constexpr (f32in) {                                                                                      \
+        const unsigned long long b_ = __builtin_amdgcn_ballot_w64(nonfinite(XM));                               \
+        flagL[MS] = (uint8_t)(((b_ >> (lane & (64 - QL))) & ((1ull << QL) - 1)) != 0);                          \
+    }
             // reversed reads come from the other lanes of the row: row_mirror hands lane q the value of lane 15 - q
             // (quad 31 - q of B, 63 - q of D); one more row_shr:1 gives quad 32 - q / 64 - q (lane 0 keeps `edge`)
             // (8 kHz: 8 lanes per stream - row_half_mirror, and lane 8 of a row, which row_shr:1 would feed from the
@@ -239,14 +251,14 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step(const float *k_wst
             };
             // Fold of (column c, stream half rr): n = 4q + j.  y1 = w[n] x[n] (A), y3 = w[128+n] x[128+n] (C),
             // y2 = w[128-n] x[128-n] (B reversed), y4 = w[256-n] x[256-n] (D reversed); w is symmetric about 128.
-#define X_FOLD1(c, rr, XR) X_FOLDG(c, (rr) * 16 + (tid >> 4), XR, (rr) * 4)
-#define X_FOLD8(c, XR, XO) X_FOLDG(c, tid >> 3, XR, XO)
-#define X_FOLDG(c, MS, XR, XO)                                                                                  \
+#define X_FOLD1(c, rr, XR) X_FOLDG(c, (rr) * 16 + (tid >> 4), XR, (rr) * 4, xm[rr])
+#define X_FOLD8(c, XR, XO) X_FOLDG(c, tid >> 3, XR, XO, xm[0])
+#define X_FOLDG(c, MS, XR, XO, XM)                                                                                \
     {                                                                                                           \
         _Pragma("clang fp contract(off)")   /* same roundings in the f32 and int16 instantiations */            \
         const int ms = (MS);                                                                                    \
-        const f32x4 xA = decode(XR[(XO) + 0]), xB = decode(XR[(XO) + 1]);                                       \
-        const f32x4 xC = decode(XR[(XO) + 2]), xD = decode(XR[(XO) + 3]);                                       \
+        const f32x4 xA = decode(XR[(XO) + 0], XM), xB = decode(XR[(XO) + 1], XM);                               \
+        const f32x4 xC = decode(XR[(XO) + 2], XM), xD = decode(XR[(XO) + 3], XM);                               \
         const float mBx = mirror(xB.x), mDx = mirror(xD.x);                                                     \
         const f32x4 y1 = pk::mul(xA, W1), y3 = pk::mul(xC, W3);                                                 \
         const f32x4 y2 = pk::mul(f32x4{shr1(xC.x, mBx), mirror(xB.w), mirror(xB.z), mirror(xB.y)}, W3);         \
@@ -324,13 +336,13 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step(const float *k_wst
             H_LDW(wB, 5, wh) X_ISSUE(2, xa_, t) SB(); H_MMA(wA, 4) X_FOLD1(1, 0, xb_) H_MIX(6) SB(); STAMP(24);
             H_LDW(wA, 6, wh) SB(); H_MMA(wB, 5) X_FOLD1(1, 1, xb_) H_MIX(6) SB(); STAMP(25);
             H_LDW(wB, 7, wh) SB(); H_MMA(wA, 6) X_FOLD1(2, 0, xa_) H_MIX(6) SB(); STAMP(26);
-            H_MMA(wB, 7) X_FOLD1(2, 1, xa_) H_MIX(6) SB(); STAMP(27);
+            H_MMA(wB, 7) X_FOLD1(2, 1, xa_) X_FLAG(tid >> 4, xm[0]) X_FLAG(16 + (tid >> 4), xm[1]) H_MIX(6) SB(); STAMP(27);
             } else {           // 8 kHz: three columns of 32 quads, one fold call each (8 lanes per stream)
             H_MMA(wA, 0) SB();
             H_LDW(wA, 2, wh) X_ISSUE8(2, xb_, 0, t) SB(); H_MMA(wB, 1) SB();
             H_LDW(wB, 3, wh) SB(); H_MMA(wA, 2) X_FOLD8(0, xa_, 0) H_MIX(6) SB();
             H_LDW(wA, 4, wh) SB(); H_MMA(wB, 3) X_FOLD8(1, xa_, 4) H_MIX(6) SB();
-            H_LDW(wB, 5, wh) SB(); H_MMA(wA, 4) X_FOLD8(2, xb_, 0) H_MIX(6) SB();
+            H_LDW(wB, 5, wh) SB(); H_MMA(wA, 4) X_FOLD8(2, xb_, 0) X_FLAG(tid >> 3, xm[0]) H_MIX(6) SB();
             H_LDW(wA, 6, wh) SB(); H_MMA(wB, 5) SB();
             H_LDW(wB, 7, wh) SB(); H_MMA(wA, 6) SB();
             H_MMA(wB, 7) SB();
@@ -340,6 +352,7 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step(const float *k_wst
 #undef X_FOLD1
 #undef X_FOLD8
 #undef X_FOLDG
+#undef X_FLAG
         }
         // weights of the first STFT iteration are requested before the barrier (they never depend on LDS)
         f32x4 Are = WL(ws_stft), Aim = WL(ws_stft + 1);
@@ -757,6 +770,8 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step(const float *k_wst
             __syncthreads();   // (7) every wave is done reading h_{t-1}; region A free for the next frame
             STAMP(14);
             f32x4 part4 = f32x4{0.f, 0.f, 0.f, 0.f};
+            // a rejected frame (float32 only) leaves the stream's h and c as they were: not stored, and held for the next frame
+            const bool bad = f32in && flagL[m] != 0;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const f32x4 i4 = quad_of(gi, g), f4 = quad_of(gfo, g), g4 = quad_of(gg, g), o4 = quad_of(go, g);
@@ -764,11 +779,17 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step(const float *k_wst
                 const f32x4 hw = g == 0 ? hw0 : (g == 1 ? hw1 : (g == 2 ? hw2 : hw3));
                 // c' = sigma(f) c + sigma(i) tanh(g); h' = sigma(o) tanh(c'); head partial += w relu(h') - a quad at a time, the
                 // full-rate arithmetic packed (pk::), the transcendentals per component
-                const f32x4 cn = pk::fma(pk::sigmoid4(f4), c4, pk::mul(pk::sigmoid4(i4), pk::tanh4(g4)));
-                const f32x4 hn = pk::mul(pk::sigmoid4(o4), pk::tanh4(cn));
+                f32x4 cn = pk::fma(pk::sigmoid4(f4), c4, pk::mul(pk::sigmoid4(i4), pk::tanh4(g4)));
+                f32x4 hn = pk::mul(pk::sigmoid4(o4), pk::tanh4(cn));
                 part4 = pk::fma(hw, relu4(hn), part4);
+                if constexpr (f32in && !ONE) {    // (the head ignores z of a rejected stream)
+                    const f32x4 hp = RH[(8 * w + 2 * g) * QS + hq];     // h_{t-1}: this thread's own place, every reader is past (7)
+                    hn = bad ? hp : hn;
+                    cn = bad ? c4 : cn;
+                }
                 RH[(8 * w + 2 * g) * QS + hq] = hn;
-                if (t == T - 1 && live) {   // last frame of the call: h' and c' go back to HBM under barrier (8), head and state machine
+                // (one frame: a rejected stream skips the store; more: the held values go back, the last accepted frame's)
+                if (t == T - 1 && live && !(ONE && bad)) {   // last frame of the call: h' and c' go back to HBM under barrier (8), head and state machine
                     *reinterpret_cast<f32x4 *>(KP(state) + (size_t)slot * 256 + 32 * w + 8 * g + 4 * h) = hn;
                     *reinterpret_cast<f32x4 *>(KP(state) + (size_t)slot * 256 + 128 + 32 * w + 8 * g + 4 * h) = cn;
                 }
@@ -791,11 +812,13 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step(const float *k_wst
             const float z = hb + ((headp[tid] + headp[32 + tid]) + (headp[64 + tid] + headp[96 + tid]));
             const float p = fminf(sigmoidf_(z), 1.0f);
             if (sm_thread) {
-                P.probs[(size_t)(tile0 + tid) * T + t] = p;
+                // rejected (include/vad_engine.h): NaN and VAD_EV_REJECTED alone, no sm_step, the state machine as it was
+                const bool bad = f32in && flagL[tid] != 0;
+                P.probs[(size_t)(tile0 + tid) * T + t] = bad ? __builtin_nanf("") : p;
                 SmSlot sm = smL[tid];
                 int seg = 0;
-                const int ev = sm_step(sm, p, &seg);
-                if (t == T - 1) KP(sm)[sm_slot] = sm;
+                const int ev = bad ? EV_REJECTED : sm_step(sm, p, &seg);
+                if (t == T - 1) { if (!(ONE && bad)) KP(sm)[sm_slot] = sm; }
                 else smL[tid] = sm;
                 if (ev & 2) seg_last = seg;
                 if (P.events) P.events[(size_t)(tile0 + tid) * T + t] = (uint8_t)ev;

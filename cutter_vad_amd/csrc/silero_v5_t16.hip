@@ -61,6 +61,10 @@ static_assert(T_ROWS_X * QSD >= (T_FOLD_SINK + 32) * QSL, "the loader view (and 
 constexpr int T_LDS_F4 = (T_ROWS_X + T_ROWS_H) * QSD + 16 + 12 + 36 + 16 + 96 + 128;   // + head partials [4][16], |X128| [3][16], fold corrections [3][3][16], sink [64], state machines [16] x 96 B, gate biases [4 waves][4 gates][32 units]
 constexpr int T_LSTM_BIAS_BLOCK = 8 + 64 + 64 + 2;   // block of a wave's LSTM section that holds its gate biases compact: floats [gate][unit]
 static_assert(T_LDS_F4 * 16 <= 80 * 1024, "stays under half a CU's LDS");
+// float32 instantiations: + the frame's rejection flags (VAD_EV_REJECTED), one byte per (loader column half, stream), behind
+// everything else
+constexpr int T_FLAG_F4 = 2;
+static_assert((T_LDS_F4 + T_FLAG_F4) * 16 <= 80 * 1024, "the flags stay under half a CU's LDS");
 // RS instantiation (fused resample -> step).  The resampler's folded input chunks (2 buffers x {ue, ve, uo, vo} x 16 quad rows,
 // loader stride) are staged in the activation region, which is idle until the frame loop starts; the tile's 16 kHz frames
 // F [16 streams][129 quads] (128 + 1 of padding: the recombination stores scalars down a column of streams) have 33 KB of their
@@ -206,7 +210,7 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
     constexpr int QL = K8 ? 8 : 16;               // loader lanes per stream = quads per quarter column
     constexpr int CS = 4 * QL;                    // folded-operand rows per column
     constexpr int PS = K8 ? 16 : 32;              // quad rows per |STFT| column (enc0's input)
-    __shared__ f32x4 lds[T_LDS_F4 + (RS ? MT16 * FQ : 0)];     // RS: + the tile's 16 kHz frames F (one workgroup per CU either way)
+    __shared__ f32x4 lds[T_LDS_F4 + (RS ? MT16 * FQ : 0) + (F32IN ? T_FLAG_F4 : 0)];     // RS: + the tile's 16 kHz frames F (one workgroup per CU either way)
     f32x4 *const RX = lds;
     f32x4 *const RE = lds + T_ROW_E * QSD;
     f32x4 *const RH = lds + T_ROWS_X * QSD;
@@ -216,6 +220,8 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
     constexpr int FCOR_SINK = 144;               // [64] floats after fcor
     SmSlot *const smL = reinterpret_cast<SmSlot *>(fcor + 144 + 64);
     f32x4 *const biasL = reinterpret_cast<f32x4 *>(smL + MT16);          // gate biases, compact: [4 waves][4 gates][8 quads of units]
+    // F32IN: [2][16] bytes, stream s rejected when flagL[s] (8 kHz: flagL[s] | flagL[16 + s], the two halves of the workgroup)
+    uint8_t *const flagL = reinterpret_cast<uint8_t *>(lds + T_LDS_F4 + (RS ? MT16 * FQ : 0));
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -752,15 +758,25 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
         f32x4 G[8];                               // gate q, row tile rt -> G[2 q + rt]
         {
             const int wh = ws_x3 + LSTM_X3_HALF_BLOCKS;
+            float xm = 0.f;                       // float32: running max |x| of this thread's raw samples (vadk_device.h absmax4)
             auto decode = [&](u32x4 b) -> f32x4 {
                 f32x4 v = __builtin_bit_cast(f32x4, b);
                 if constexpr (!f32in) {
                     const int s0 = (int)(short)(b.x & 0xffffu), s1 = (int)(short)(b.x >> 16);
                     const int s2 = (int)(short)(b.y & 0xffffu), s3 = (int)(short)(b.y >> 16);
                     v = f32x4{i16_div(s0, sc, rsc), i16_div(s1, sc, rsc), i16_div(s2, sc, rsc), i16_div(s3, sc, rsc)};
+                } else {
+                    xm = absmax4(xm, v);          // before the gate: gate on and off reject the same frames
                 }
                 return gate4(v, thr);
             };
+            // after the frame's last fold call: the stream's QL loader lanes of this row vote (a ballot, no branch), every one of
+            // them writes the verdict; barrier (1) publishes it to the cell and the head
+#define X_FLAG                                                                                                  \
+    if constexpr (f32in) {                                                                                      \
+        const unsigned long long b_ = __builtin_amdgcn_ballot_w64(nonfinite(xm));                               \
+        flagL[(K8 ? 16 * lcol : 0) + lms] = (uint8_t)(((b_ >> (lane & (64 - QL))) & ((1ull << QL) - 1)) != 0);   \
+    }
             // (8 kHz: 8 lanes per stream - row_half_mirror, and lane 8 of a row, which row_shr:1 would feed from the neighbouring
             // stream's lane 7, takes `edge` by a select)
             auto mirror = [](float v) -> float {
@@ -836,14 +852,15 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
 #define H_EXTRA(u)                                                                                              \
             if constexpr ((u) == 2 && !RS && !K8) { X_ISSUE(2, xc_, t) }                                        \
             if constexpr ((u) == 15) { if constexpr (K8) { X_FOLD(lcol, xa_) } else { X_FOLD(0, xa_) } H_MIX }   \
-            if constexpr ((u) == 23) { if constexpr (K8) { X_FOLD(2, xb_) } else { X_FOLD(1, xb_) } H_MIX }      \
-            if constexpr ((u) == 31 && !K8) { X_FOLD(2, xc_) H_MIX }
+            if constexpr ((u) == 23) { if constexpr (K8) { X_FOLD(2, xb_) X_FLAG } else { X_FOLD(1, xb_) } H_MIX }   \
+            if constexpr ((u) == 31 && !K8) { X_FOLD(2, xc_) X_FLAG H_MIX }
 #define H_FOLDREGION(u) (((u) & 7) >= 5 && (u) >= 8 && ((u) < 24 || !K8))
             X3_HALF(wh, RH, H_EXTRA, H_FOLDREGION)
 #undef H_EXTRA
 #undef H_FOLDREGION
 #undef H_MIX
 #undef X_FOLD
+#undef X_FLAG
         }
         f32x4 Sw[2];                              // STFT blocks of k-iteration 0: cos, -sin of the odd tile
 #pragma unroll
@@ -1113,16 +1130,24 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
             __syncthreads();   // (7) every wave is done reading h_{t-1}
             STAMP(14);
             f32x4 part4 = f32x4{0.f, 0.f, 0.f, 0.f};
+            // a rejected frame (float32 only) leaves the stream's h and c as they were: not stored, and held for the next frame
+            const bool bad = f32in && (K8 ? (flagL[n] | flagL[16 + n]) : flagL[n]) != 0;
 #pragma unroll
             for (int rt = 0; rt < 2; ++rt) {
                 const f32x4 i4 = G[0 + rt], f4 = G[2 + rt], g4 = G[4 + rt], o4 = G[6 + rt], c4 = cst[rt], hwv = hw[rt];
                 // c' = sigma(f) c + sigma(i) tanh(g); h' = sigma(o) tanh(c'); head partial += w relu(h') - a quad at a time, the
                 // full-rate arithmetic packed (pk::), the transcendentals per component
-                const f32x4 cn = pk::fma(pk::sigmoid4(f4), c4, pk::mul(pk::sigmoid4(i4), pk::tanh4(g4)));
-                const f32x4 hn = pk::mul(pk::sigmoid4(o4), pk::tanh4(cn));
+                f32x4 cn = pk::fma(pk::sigmoid4(f4), c4, pk::mul(pk::sigmoid4(i4), pk::tanh4(g4)));
+                f32x4 hn = pk::mul(pk::sigmoid4(o4), pk::tanh4(cn));
                 part4 = pk::fma(hwv, relu4(hn), part4);
+                if constexpr (f32in && !ONE && !RS) {   // (the head ignores z of a rejected stream)
+                    const f32x4 hp = RH[(8 * w + 4 * rt) * QSD + nq];   // h_{t-1}: this thread's own place, every reader is past (7)
+                    hn = bad ? hp : hn;
+                    cn = bad ? c4 : cn;
+                }
                 RH[(8 * w + 4 * rt) * QSD + nq] = hn;
-                if (t == T - 1 && live) {
+                // (one frame: a rejected stream skips the store; more: the held values go back, the last accepted frame's)
+                if (t == T - 1 && live && !((ONE || RS) && bad)) {
                     *reinterpret_cast<f32x4 *>(KP(state) + (size_t)slot * 256 + 32 * w + 16 * rt + 4 * kq) = hn;
                     *reinterpret_cast<f32x4 *>(KP(state) + (size_t)slot * 256 + 128 + 32 * w + 16 * rt + 4 * kq) = cn;
                 }
@@ -1140,11 +1165,13 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
             const float z = hb + ((headp[tid] + headp[16 + tid]) + (headp[32 + tid] + headp[48 + tid]));
             const float p = fminf(sigmoidf_(z), 1.0f);
             if (sm_thread) {
-                P.probs[(size_t)gf * T + t] = p;                       // tid < 16: this thread's column is stream gf
+                // rejected (include/vad_engine.h): NaN and VAD_EV_REJECTED alone, no sm_step, the state machine as it was
+                const bool bad = f32in && (K8 ? (flagL[tid] | flagL[16 + tid]) : flagL[tid]) != 0;
+                P.probs[(size_t)gf * T + t] = bad ? __builtin_nanf("") : p;   // tid < 16: this thread's column is stream gf
                 SmSlot sm = smL[tid];
                 int seg = 0;
-                const int ev = sm_step(sm, p, &seg);
-                if (t == T - 1) KP(sm)[sm_slot] = sm;
+                const int ev = bad ? EV_REJECTED : sm_step(sm, p, &seg);
+                if (t == T - 1) { if (!((ONE || RS) && bad)) KP(sm)[sm_slot] = sm; }
                 else smL[tid] = sm;
                 if (ev & 2) seg_last = seg;
                 if (P.events) P.events[(size_t)gf * T + t] = (uint8_t)ev;

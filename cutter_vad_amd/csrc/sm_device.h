@@ -5,6 +5,9 @@
 
 namespace vadk {
 
+// include/vad_engine.h VAD_EV_REJECTED: the frame held a NaN / Inf sample; probability NaN, no sm_step, state untouched
+constexpr int EV_REJECTED = 0x80;
+
 // ---- hysteresis state machine, one stream, one frame (core/silero_model.py:790-949) ----
 __device__ __forceinline__ int sm_step(SmSlot &s, float p, int *seg_out) {
     int ev = 0;

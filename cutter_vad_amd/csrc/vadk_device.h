@@ -228,5 +228,14 @@ __device__ __forceinline__ f32x4 gate4(f32x4 v, float thr) {
     return v;
 }
 
+// Non-finite input (include/vad_engine.h, VAD_EV_REJECTED): a running maximum of |x| over the raw samples, before the gate, with
+// IEEE maximum semantics - a NaN operand makes the result NaN (v_maximum3_f32, the |.| as source modifiers; fmaxf would drop it).
+// The frame is rejected when the maximum of its samples is NaN or +Inf: nonfinite(m).
+__device__ __forceinline__ float absmax4(float m, f32x4 v) {
+    const float a = __builtin_elementwise_maximum(m, __builtin_elementwise_maximum(fabsf(v.x), fabsf(v.y)));
+    return __builtin_elementwise_maximum(a, __builtin_elementwise_maximum(fabsf(v.z), fabsf(v.w)));
+}
+__device__ __forceinline__ bool nonfinite(float m) { return !(m <= 3.40282347e+38f); }
+
 } }  // namespace vadk::dev
 

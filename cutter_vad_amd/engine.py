@@ -33,6 +33,12 @@ class Engine:
 
     ``weights`` is an SVW blob (``weights_io.load_weight_blob``).  ``denoise`` is the gate
     threshold of ``AudioUtils.denoise_audio`` (0.01) or ``None`` to disable it.
+
+    Rejected frames (ABI 5, ``include/vad_engine.h``): a float32 frame with a NaN / Inf sample the model would read gives
+    that stream probability NaN, event ``_ffi.VAD_EV_REJECTED`` alone and seg 0, and leaves its (h, c) and state machine
+    exactly as they were; the other streams of the call are unaffected and the call does not raise.  This holds for every
+    ``step*``, ``submit`` / ``collect``, ``step_rates*`` and the tick entries (``tick_run_work`` lists such an entry as
+    ``_ffi.VAD_WORK_REJECTED`` and leaves the slot's ``last_prob`` / ``frames_done`` / ``active``).
     """
 
     def __init__(self, weights: bytes, model_version: int = 5, device_id: int = 0, max_streams: int = 8192,
@@ -186,7 +192,7 @@ class Engine:
         return s, f, _FMT[f.dtype]
 
     def step(self, slots, frames, denoise: Optional[float] = 0.01, i16_scale: int = 32767) -> np.ndarray:
-        """One 512-sample frame per listed stream -> probabilities [n]."""
+        """One 512-sample frame per listed stream -> probabilities [n] (NaN for a rejected non-finite frame)."""
         s, f, fmt = self._prep(slots, frames, None)
         if fmt != _ffi.VAD_FMT_F32 and i16_scale == 32768:
             fmt = _ffi.VAD_FMT_I16_32768
@@ -197,7 +203,8 @@ class Engine:
         return probs
 
     def step_events(self, slots, frames, denoise: Optional[float] = 0.01, i16_scale: int = 32767):
-        """-> (probs [n], event bits [n] uint8, finished-segment frames [n] int32)."""
+        """-> (probs [n], event bits [n] uint8, finished-segment frames [n] int32); a rejected non-finite frame: NaN,
+        ``VAD_EV_REJECTED``, 0."""
         s, f, fmt = self._prep(slots, frames, None)
         if fmt != _ffi.VAD_FMT_F32 and i16_scale == 32768:
             fmt = _ffi.VAD_FMT_I16_32768
@@ -210,7 +217,8 @@ class Engine:
         return probs, ev, seg
 
     def step_multi(self, slots, frames, denoise: Optional[float] = 0.01, i16_scale: int = 32767):
-        """frames [n, T, 512]: T consecutive frames per stream -> (probs [n,T], events [n,T])."""
+        """frames [n, T, 512]: T consecutive frames per stream -> (probs [n,T], events [n,T]).  A rejected non-finite frame
+        (NaN, ``VAD_EV_REJECTED``) is skipped: the stream's next frame continues from the state before it."""
         f0 = np.asarray(frames)
         if f0.ndim != 3:
             raise AudioProcessingError(f"Model prediction failed: frames must be [n, T, 512], got {f0.shape}")

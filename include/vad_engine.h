@@ -42,7 +42,7 @@ extern "C" {
 #define VAD_API
 #endif
 
-#define VAD_ABI_VERSION 4
+#define VAD_ABI_VERSION 5
 #define VAD_FRAME_SAMPLES 512   /* core/silero_model.py:464-468: frames are padded/truncated to 512 (Silero V5 8 kHz engines: 256, see vad_info) */
 #define VAD_STATE_FLOATS 256    /* V5: state[2][1][128]; V4: h[2][1][64] then c[2][1][64]  (silero_model.py:391-401) */
 
@@ -66,6 +66,23 @@ typedef enum vad_frame_format {
 
 /* event bits produced by the per-stream hysteresis state machine (core/silero_model.py:790-949) */
 enum { VAD_EV_START = 1, VAD_EV_END = 2, VAD_EV_CONTINUE = 4 };
+
+/* ABI 5: non-finite frames are rejected per stream, inside the step kernels (core/silero_model.py:779 validates every frame
+ * before the model; utils/audio.py:227-228).  Applies to every float32 entry point: vad_step*, vad_step_device, vad_step_submit,
+ * vad_step_rates*, and float32 frames of vad_tick_push*.  int16 samples are always finite.
+ *   - A stream's frame is REJECTED when any sample the model reads is NaN or +-Inf: the 512 samples (Silero V5 8 kHz: 256) after
+ *     pad / truncate; vad_step_rates*: any sample of the input chunk (each one reaches the resampled frame).  The check comes
+ *     before the denoise gate, so gate on and off give the same verdict.
+ *   - A rejected frame gives probs = quiet NaN, events = VAD_EV_REJECTED and no other bit, seg_frames = 0 (for that frame).  The
+ *     stream's (h, c) and state machine stay exactly as they were (a byte-equal vad_stream_save blob); in a multi-frame call the
+ *     next frame continues from the state after the previous one, as if the rejected frame had not been submitted.
+ *   - Other streams of the call are unaffected; the call still returns VAD_OK.
+ *   - vad_tick_run reports the entry the same way; the segment assembler skips it entirely (no pre-roll or segment audio, no
+ *     state-machine bookkeeping; a long frame's staged tail is dropped); vad_tick_run_work lists it as VAD_WORK_REJECTED.
+ *   - Not covered: finite samples so large (|x| above ~1e18) that the model's own arithmetic overflows.  Those give a NaN
+ *     probability and DO advance the state; the serving layer's host checks (utils/audio.py) still apply.
+ */
+#define VAD_EV_REJECTED 0x80
 
 typedef struct vad_engine vad_engine;
 
@@ -365,6 +382,8 @@ VAD_API int vad_tick_run(vad_engine *e, float denoise_thresh, vad_tick_result *o
 #define VAD_WORK_CONTINUE 4
 #define VAD_WORK_PAYLOAD 8
 #define VAD_WORK_LONG 16
+#define VAD_WORK_REJECTED 32   /* ABI 5: the entry's frame was rejected (VAD_EV_REJECTED): the slot's last_prob / frames_done / active are
+                                  left as they were; LONG keeps its meaning */
 typedef struct vad_tick_work {
     uint32_t struct_size;          /* sizeof(vad_tick_work) */
     int64_t n_slots;               /* length of the five arrays below */

@@ -1,6 +1,7 @@
 // TEST-ONLY host stand-ins for the vadk_launch_* entry points of the .hip files (see hip/hip_runtime_api.h): the "model" is
 // p = clamp(|first sample of the frame|, 0, 1) - the harness scripts a stream's probabilities through its audio - and the events
-// come from the REAL state machine (csrc/sm_device.h) on the slot's SmSlot, exactly as the kernels apply it.
+// come from the REAL state machine (csrc/sm_device.h) on the slot's SmSlot, exactly as the kernels apply it.  A float32 frame
+// with a NaN / Inf sample is rejected as the kernels reject it (include/vad_engine.h VAD_EV_REJECTED): NaN, the bit, no state change.
 #include "../../include/vad_engine.h"
 #include <hip/hip_runtime.h>
 
@@ -26,12 +27,25 @@ static float first_sample(const void *frames, size_t index, int fmt, int frame_s
     return (float)q / (fmt == VAD_FMT_I16_32767 ? 32767.0f : 32768.0f);
 }
 
+static bool has_nonfinite(const void *frames, size_t index, int fmt, int frame_samples) {
+    if (fmt != VAD_FMT_F32) return false;
+    const float *x = static_cast<const float *>(frames) + index * (size_t)frame_samples;
+    for (int k = 0; k < frame_samples; ++k)
+        if (!std::isfinite(x[k])) return true;
+    return false;
+}
+
 static hipError_t fake_step(const StepParams *p, int frame_samples) {
     for (int i = 0; i < p->n; ++i) {
         const int slot = p->slots ? p->slots[i] : i;
         SmSlot &s = p->sm[slot];
         int seg_last = 0;
         for (int t = 0; t < p->T; ++t) {
+            if (has_nonfinite(p->frames, (size_t)i * p->T + t, p->fmt, frame_samples)) {
+                p->probs[(size_t)i * p->T + t] = std::nanf("");
+                if (p->events) p->events[(size_t)i * p->T + t] = (uint8_t)EV_REJECTED;
+                continue;
+            }
             float x = first_sample(p->frames, (size_t)i * p->T + t, p->fmt, frame_samples);
             if (p->thresh >= 0.f && !(std::fabs(x) > p->thresh)) x = 0.f;
             const float prob = std::fmin(1.0f, std::fabs(x));
