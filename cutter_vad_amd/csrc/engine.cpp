@@ -145,6 +145,8 @@ struct vad_engine {
     size_t wbytes16 = 0;
     float *d_wstream16x = nullptr;   // the 16-stream packing's second stream (V5: encoder.0 on bf16 splits), or nullptr
     size_t wbytes16x = 0;
+    float *d_wstream16y = nullptr;   // ... and its third (V5: encoder.1 on bf16 splits), or nullptr
+    size_t wbytes16y = 0;
     uint32_t sect16[vadk::NWAVES][16] = {};
     int tile_policy = 0;                     // 0 = by batch size, 16 / 32 = forced (vad_debug_set_tile)
     bool rates_fused = true;                 // vad_debug_set_tile(-1 / -2): two-launch / fused form of vad_step_rates (benchmarks)
@@ -529,6 +531,8 @@ int launch(vad_engine *e, const vadk::StepParams &p, hipStream_t s) {
         p16.wstream_bytes = (uint32_t)e->wbytes16;
         p16.wstream_x = e->d_wstream16x;
         p16.wstream_x_bytes = (uint32_t)e->wbytes16x;
+        p16.wstream_y = e->d_wstream16y;
+        p16.wstream_y_bytes = (uint32_t)e->wbytes16y;
         std::memcpy(p16.sect, e->sect16, sizeof p16.sect);
         const int tiles16 = (p.n + 15) / 16;
         r = vadk_launch_silero_v4_t16(&p16, (!e->shared_gpu && tiles16 <= e->prop.multiProcessorCount) ? 1 : 0, s);
@@ -538,6 +542,8 @@ int launch(vad_engine *e, const vadk::StepParams &p, hipStream_t s) {
         p16.wstream_bytes = (uint32_t)e->wbytes16;
         p16.wstream_x = e->d_wstream16x;
         p16.wstream_x_bytes = (uint32_t)e->wbytes16x;
+        p16.wstream_y = e->d_wstream16y;
+        p16.wstream_y_bytes = (uint32_t)e->wbytes16y;
         std::memcpy(p16.sect, e->sect16, sizeof p16.sect);
         r = vadk_launch_silero_v5_t16(&p16, s);
     } else if (e->version == 5) r = vadk_launch_silero_v5(&p, s);
@@ -726,6 +732,9 @@ int vad_engine_create(const vad_engine_desc *desc, vad_engine **out) {
         e->wbytes16x = pw16.data_x.size() * sizeof(float);
         if (!pw16.data_x.empty() && (r = weights_acquire(e->device, pw16.data_x, &e->d_wstream16x)) != hipSuccess)
             return bail(r, "hipMalloc / hipMemcpy(weights, 16-stream tiles, second stream)");
+        e->wbytes16y = pw16.data_y.size() * sizeof(float);
+        if (!pw16.data_y.empty() && (r = weights_acquire(e->device, pw16.data_y, &e->d_wstream16y)) != hipSuccess)
+            return bail(r, "hipMalloc / hipMemcpy(weights, 16-stream tiles, third stream)");
         std::memcpy(e->sect16, pw16.sect, sizeof pw16.sect);
     }
     const size_t sb = sizeof(float) * VAD_STATE_FLOATS * (size_t)e->max_streams;
@@ -763,6 +772,7 @@ void vad_engine_destroy(vad_engine *e) {
     weights_release(e->d_wstream);
     weights_release(e->d_wstream16);
     weights_release(e->d_wstream16x);
+    weights_release(e->d_wstream16y);
     void *bufs[] = {e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots,
                     e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
     for (void *b : bufs)
@@ -816,7 +826,7 @@ int vad_engine_info(const vad_engine *e, vad_info *info) {
     info->open_streams = e->open_count;
     info->compute_units = e->prop.multiProcessorCount;
     info->streams_per_workgroup = vadk::MT;
-    info->weight_bytes_device = (int64_t)(e->wbytes + e->wbytes16 + e->wbytes16x);
+    info->weight_bytes_device = (int64_t)(e->wbytes + e->wbytes16 + e->wbytes16x + e->wbytes16y);
     info->state_bytes_device = (int64_t)(sizeof(float) * VAD_STATE_FLOATS + sizeof(vadk::SmSlot)) * e->max_streams;
     info->steps = e->steps;
     info->frames = e->frames;
@@ -1575,6 +1585,8 @@ int step_rates_enqueue(vad_engine *e, int32_t nseg, const float *const *d_in, co
         p.wstream_bytes = (uint32_t)e->wbytes16;
         p.wstream_x = e->d_wstream16x;
         p.wstream_x_bytes = (uint32_t)e->wbytes16x;
+        p.wstream_y = e->d_wstream16y;
+        p.wstream_y_bytes = (uint32_t)e->wbytes16y;
         std::memcpy(p.sect, e->sect16, sizeof p.sect);
         p.slots = d_slots;
         p.frames = nullptr;
@@ -2446,9 +2458,10 @@ int vad_debug_pack_weights(int32_t model_version, const void *weights, size_t we
     vadk::PackedWeights pw;
     std::string perr;
     // model_version 516 / 416: Silero V5 / V4 packed for the 16-stream tile kernels (tests/kernel_model.py models both packings);
-    // 5161: the second stream of the 516 packing (PackedWeights::data_x: encoder.0 on bf16 splits), with the same section table
+    // 5161: the second stream of the 516 packing (PackedWeights::data_x: encoder.0 on bf16 splits), with the same section table;
+    // 5162: its third (PackedWeights::data_y: encoder.1 on bf16 splits)
     const bool ok = model_version == 5     ? vadk::pack_silero_v5(weights, weights_len, pw, perr)
-                    : model_version == 516 || model_version == 5161 ? vadk::pack_silero_v5_t16(weights, weights_len, pw, perr)
+                    : model_version == 516 || model_version == 5161 || model_version == 5162 ? vadk::pack_silero_v5_t16(weights, weights_len, pw, perr)
                     : model_version == 4   ? vadk::pack_silero_v4(weights, weights_len, pw, perr)
                     : model_version == 416 ? vadk::pack_silero_v4_t16(weights, weights_len, pw, perr)
                                            : false;
@@ -2457,6 +2470,7 @@ int vad_debug_pack_weights(int32_t model_version, const void *weights, size_t we
         return VAD_ERR_BAD_WEIGHTS;
     }
     if (model_version == 5161) pw.data = std::move(pw.data_x);
+    if (model_version == 5162) pw.data = std::move(pw.data_y);
     if (n_floats) *n_floats = pw.data.size();
     if (sect_out) std::memcpy(sect_out, pw.sect, sizeof pw.sect);
     if (out) {

@@ -544,6 +544,17 @@ bool pack_silero_v5_t16(const void *blob, size_t len, PackedWeights &out, std::s
                         return false;
     }
     out.data_x = std::move(sb.data);
+    // S_ENC1_X3, the third stream (vad_layout.h): encoder.1 on the bf16 split - per wave one 16-row tile: its bias, then per K-step
+    // the three taps over the 32 input channels of the step, in enc0's output order
+    sb = StreamBuilder();
+    for (int w = 0; w < NWAVES; ++w) {
+        out.sect[w][S_ENC1_X3] = sb.blocks();
+        sb.vector_block16([&](int c) { return eb[1][16 * w + c]; });
+        for (int s = 0; s < 4; ++s)
+            for (int t = 0; t < 3; ++t)
+                if (!x3_unit([&](int r, int k) { return convw(1, 16 * w + r, 32 * s + k, t); }, "an encoder.1")) return false;
+    }
+    out.data_y = std::move(sb.data);
     return true;
 }
 

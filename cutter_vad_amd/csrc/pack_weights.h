@@ -16,6 +16,8 @@ struct PackedWeights {
     // a second stream, uploaded as a buffer of its own (StepParams::wstream_x): V5 on 16-stream tiles, the split encoders
     // (S_ENC0_X3 - its sect entries are block offsets into THIS stream); empty for every other packing
     std::vector<float> data_x;
+    // a third one (StepParams::wstream_y): V5 on 16-stream tiles, encoder.1 on the bf16 split (S_ENC1_X3, offsets into THIS stream)
+    std::vector<float> data_y;
     int32_t variant = 0;             // V4: 1 = the graph's 8 kHz sub-model (two time steps reach the LSTMs)
 };
 

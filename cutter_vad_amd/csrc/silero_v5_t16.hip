@@ -5,9 +5,10 @@
 // there are.  This kernel is the same network, much of the same algebra (frame ingest under the recurrent gate half, 4-way folded
 // DFT, split-K enc2) and the same per-stream results, re-expressed on v_mfma_f32_16x16x4_f32: a workgroup (4 waves) carries 16
 // streams, so the same batch spreads over twice as many CUs and every MFMA / VALU phase is half as long.
-// The LSTM's two halves and encoder.0 run on v_mfma_f32_16x16x32_bf16 instead, with weights and activations as exact three-piece
-// bf16 splits (X3_HALF, X3_CONV below; vad_layout.h S_LSTM_X3, S_ENC0_X3); encoder.0 as a direct 3-tap convolution, not the Toom-3
-// product of silero_v5.hip.
+// The LSTM's two halves, encoder.0 and encoder.1 run on v_mfma_f32_16x16x32_bf16 instead, with weights and activations as exact
+// three-piece bf16 splits (X3_HALF, X3_CONV below; vad_layout.h S_LSTM_X3, S_ENC0_X3, S_ENC1_X3); the encoders as direct 3-tap
+// convolutions, not the Toom-3 product of silero_v5.hip.  An activation that feeds such a layer is cut into its pieces ONCE, by the
+// lane that produces it, and lies in LDS as the consumers' B fragments ("activation planes", at QSD below).
 // The engine picks it when a call has at most T16_MAX_STREAMS streams (engine.cpp).
 //
 // Fragment convention (v_mfma_f32_16x16x4_f32, D = A[16 x 4] B[4 x 16] + C): lane l = (n = l & 15, kq = l >> 4).
@@ -50,15 +51,27 @@ namespace {
 constexpr int MT16 = 16;
 constexpr int QSL = 17;                   // loader view: rows 64 c + .. of the folded operands (po 0.. | qo 16.. | pe+ 32.. | pe- 40.. | qe- 48.. | qe+ 56..), 192 rows
 constexpr int QSD = 16;                   // dense view of the same memory, used by everything else:
-//   rows 0..95 the |STFT| columns (32 c + ch/4; 8 kHz: 16 c + ch/4; the Nyquist channel is in nyqv); rows 0..31 later enc1 output,
-//   then the LSTM input; rows 168.. = enc0 output (168 + 32 c + ch/4), then the enc2 partials (168 + 16 half + ch/4); then h_{t-1}
-//   (32 rows)
+//   rows 0..143 the |STFT| columns as activation planes (below; 48 c + 12 s + 4 p + kq; 8 kHz: 24 c + ..; the Nyquist channel is in
+//   nyqv); rows 0..31 later enc1's output (fp32: 16 c + ch/4), then rows 0..47 the LSTM input as planes; rows 144..287 = enc0's output
+//   as planes (144 + 48 c + ..), then rows 168..199 the enc2 partials (fp32: 168 + 16 half + ch/4); rows 248..295 = h_{t-1} as planes.
+// Activation planes: a tensor that feeds a bf16-split layer is cut into its three bf16 pieces by the lane that PRODUCES it, once,
+// and lies in LDS as the consumers' B fragments: a plane group = one K-step s (32 channels) of the 16 streams = 12 quad rows, piece p
+// of lane (n, kq)'s fragment = the 16 bytes at quad row 12 s + 4 p + kq, stream n - one ds_read_b128 per piece for each of the four
+// waves that consume it, no VALU work (before: every wave cut every activation it read, 11 instructions per pair of values).
+// Live ranges: the h planes are read in the recurrent half only (barrier (0) .. (1)) and written by the prologue and by the cell
+// behind barrier (7), so they may lie under enc0's output (written behind (2), last read before (4)), in every instantiation (the
+// rejected-frame hold keeps h_{t-1} in registers), and lie past the loader view (238 rows, live (0) .. (1b)); the |STFT| planes are
+// written behind (1b) and read until (3); enc1's output is written behind (3) and read until (5), the enc2 partials behind (4)
+// until (6); the x planes are written behind (5), when enc1's output and the |STFT| planes are dead, and read until (7).
+constexpr int T_ROW_E0 = 144;
 constexpr int T_ROW_E = 168;
-constexpr int T_ROWS_X = 264;
-constexpr int T_ROWS_H = 32;
+constexpr int T_ROW_H = 248;
+constexpr int T_ROWS_H = 48;
+constexpr int T_ROWS = T_ROW_H + T_ROWS_H;
+static_assert(T_ROW_E0 + 144 <= T_ROWS && T_ROW_E + 32 <= T_ROWS, "enc0's output and the enc2 partials end inside the activation region");
 constexpr int T_FOLD_SINK = 192;          // loader view: 32 rows behind the three columns, where the loader lanes q >= 8 drop their duplicate quads
-static_assert(T_ROWS_X * QSD >= (T_FOLD_SINK + 32) * QSL, "the loader view (and its sink rows) must end before h");
-constexpr int T_LDS_F4 = (T_ROWS_X + T_ROWS_H) * QSD + 16 + 12 + 36 + 16 + 96 + 128;   // + head partials [4][16], |X128| [3][16], fold corrections [3][3][16], sink [64], state machines [16] x 96 B, gate biases [4 waves][4 gates][32 units]
+static_assert(T_ROW_H * QSD >= (T_FOLD_SINK + 32) * QSL, "the loader view (and its sink rows) must end before h");
+constexpr int T_LDS_F4 = T_ROWS * QSD + 16 + 12 + 36 + 16 + 96 + 128;   // + head partials [4][16], |X128| [3][16], fold corrections [3][3][16], sink [64], state machines [16] x 96 B, gate biases [4 waves][4 gates][32 units]
 constexpr int T_LSTM_BIAS_BLOCK = 8 + 64 + 64 + 2;   // block of a wave's LSTM section that holds its gate biases compact: floats [gate][unit]
 static_assert(T_LDS_F4 * 16 <= 80 * 1024, "stays under half a CU's LDS");
 // float32 instantiations: + the frame's rejection flags (VAD_EV_REJECTED), one byte per (loader column half, stream), behind
@@ -85,6 +98,23 @@ __device__ __forceinline__ f32x4 mfma16(f32x4 w, f32x4 a, f32x4 acc) {
     return acc;
 }
 
+// A wave's two D quads (row tiles 0, 1) of a lane -> the three pieces of K-step s = w's fragment, into the plane group at grp (= the
+// group's first row + the lane's nq); a single D quad (8 kHz |STFT|: a wave owns one row tile) -> half of each piece
+__device__ __forceinline__ void st_planes(f32x4 *grp, f32x4 xa, f32x4 xb) {
+    u32x4 F[3];
+    split3_frag(xa, xb, F);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) grp[4 * p * QSD] = __builtin_bit_cast(f32x4, F[p]);
+}
+__device__ __forceinline__ void st_planes_half(f32x4 *grp, int half, f32x4 x) {
+    u32x2 H[3];
+    split3_half(x, H);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) reinterpret_cast<f32x2 *>(grp + 4 * p * QSD)[half] = __builtin_bit_cast(f32x2, H[p]);
+}
+// piece p of the lane's fragment of K-step s
+#define PL_RD(SRC, s, p) __builtin_bit_cast(u32x4, (SRC)[(12 * (s) + 4 * (p)) * QSD + nq])
+
 // the weight ring of the bf16-split layers (S_LSTM_X3, S_ENC0_X3): units requested ahead, slots
 constexpr int X3_D = 4;
 constexpr int X3_NR = X3_D + 1;
@@ -108,18 +138,17 @@ __device__ __forceinline__ void x3_units(F &&f, std::integer_sequence<int, I...>
     }
 // One half of the LSTM (W_ih . x or W_hh . h) on the bf16 split: 32 units u = 8 s + tile, unit u = the six MFMAs of tile u & 7 at
 // K-step s (vadk_device.h: mfma_x3) into G[tile].  Requests run X3_D units ahead through the ring xw.  The activations: lane (n, kq)
-// reads quad rows 8 s + kq and 8 s + 4 + kq of SRC (K elements 0..3 and 4..7 of its B fragment) and splits them into the three bf16
-// fragments; K-step s + 1's quads are read in unit (s, 0) and split one dword per unit in units (s, 1..4), under K-step s's MFMAs.
+// reads its fragment's three pieces of K-step s from the plane groups at SRC (quad rows 12 s + 4 p + kq), ready made; K-step s + 1's
+// are read in unit (s, 0), under K-step s's MFMAs.
 // EXTRA(u): work placed in unit u; FOLD(u): unit u is fenced together with the next one (a longer region for the caller's
 // interleave hints).
 #define X3_UNIT(u, B, SRC, EXTRA, FOLD)                                                                         \
     {                                                                                                           \
         constexpr int s_ = (u) >> 3, k_ = (u) & 7;                                                              \
         if constexpr ((u) + X3_D < 32) { X3_LD(B, (u) + X3_D) }                                                 \
-        if constexpr (k_ == 0 && s_ < 3) { na_ = (SRC)[(8 * s_ + 8) * QSD + nq]; nb_ = (SRC)[(8 * s_ + 12) * QSD + nq]; } \
+        if constexpr (k_ == 0 && s_ < 3) { _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) N_[p_] = PL_RD(SRC, s_ + 1, p_); } \
         EXTRA(u)                                                                                                \
         G[k_] = mfma_x3(xw[(u) % X3_NR], F_, G[k_]);                                                            \
-        if constexpr (k_ >= 1 && k_ <= 4 && s_ < 3) split3_dword(na_, nb_, k_ - 1, N_);                         \
         if constexpr (k_ == 7) { F_[0] = N_[0]; F_[1] = N_[1]; F_[2] = N_[2]; }                                 \
         if constexpr (!(FOLD(u)) || k_ == 7) SB();                                                              \
     }
@@ -131,41 +160,32 @@ __device__ __forceinline__ void x3_units(F &&f, std::integer_sequence<int, I...>
 #define X3_HALF(B, SRC, EXTRA, FOLD)                                                                            \
     {                                                                                                           \
         u32x4 F_[3], N_[3];                                                                                     \
-        f32x4 na_, nb_;                                                                                         \
-        {                                                                                                       \
-            const f32x4 a0_ = (SRC)[nq], b0_ = (SRC)[4 * QSD + nq];                                              \
-            _Pragma("unroll") for (int d_ = 0; d_ < 4; ++d_) split3_dword(a0_, b0_, d_, F_);                    \
-        }                                                                                                       \
+        _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) F_[p_] = PL_RD(SRC, 0, p_);                            \
         SB();                                                                                                   \
         X3_STEP(0, B, SRC, EXTRA, FOLD) X3_STEP(1, B, SRC, EXTRA, FOLD)                                         \
         X3_STEP(2, B, SRC, EXTRA, FOLD) X3_STEP(3, B, SRC, EXTRA, FOLD)                                         \
     }
 // A direct 3-tap convolution on the bf16 split (encoder.0: vad_layout.h S_ENC0_X3, in the second weight stream - block offset B
-// into it): NO output columns
-// out(o) = sum_tap W[tap] x[STR o + tap - 1] over the three input columns x[c] at SRC(c) (quad rows, dense view), NT row tiles per
+// into it; LDM = the stream's unit loader, X3_LDX / X3_LDY): NO output columns
+// out(o) = sum_tap W[tap] x[STR o + tap - 1] over the three input columns x[c], plane groups at SRC(c), NT row tiles per
 // wave, NS K-steps of 32 channels.  Unit u = (K-step s, tap, tile) = (s * 3 + tap) * NT + tile: the tap's A fragment (3 blocks at
 // B + 3 u, ring slot (U0 + u) % X3_NR) feeds every output column that the tap reaches, mfma_x3 into ACC[o][tile] - the unit is
-// loaded once and used up to three times.  All three columns' activations are split once per K-step: K-step s + 1's quads are read
-// in the K-step's first unit and split one column per unit in units 1, 2, 3 (NT = 1: 1, 2, 2) under K-step s's MFMAs.  Requests
+// loaded once and used up to three times.  K-step s + 1's nine pieces (three columns) are read in K-step s's first unit.  Requests
 // run X3_D units ahead.  EXTRA(u): work placed in unit u.
-#define X3_CONV(NS, NT, STR, NO, B, U0, SRC, ACC, EXTRA)                                              \
+#define X3_CONV(NS, NT, STR, NO, LDM, B, U0, SRC, ACC, EXTRA)                                         \
     {                                                                                                           \
         constexpr int NU_ = (NS) * 3 * (NT);                                                                    \
         u32x4 F_[3][3], N_[3][3];                                                                               \
-        f32x4 na_[3], nb_[3];                                                                                   \
-        _Pragma("unroll") for (int c_ = 0; c_ < 3; ++c_) {                                                      \
-            const f32x4 a0_ = SRC(c_)[nq], b0_ = SRC(c_)[4 * QSD + nq];                                          \
-            _Pragma("unroll") for (int d_ = 0; d_ < 4; ++d_) split3_dword(a0_, b0_, d_, F_[c_]);                \
-        }                                                                                                       \
+        _Pragma("unroll") for (int c_ = 0; c_ < 3; ++c_)                                                        \
+            _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) F_[c_][p_] = PL_RD(SRC(c_), 0, p_);                \
         SB();                                                                                                   \
         x3_units([&](auto uc_) {                                                                                \
             constexpr int u_ = decltype(uc_)::value, s_ = u_ / (3 * (NT)), r_ = u_ % (3 * (NT));                \
             constexpr int t_ = r_ / (NT), tl_ = r_ % (NT);                                                      \
-            if constexpr (u_ + X3_D < NU_) { X3_LDX((B) + 3 * (u_ + X3_D), (U0) + u_ + X3_D) }                  \
+            if constexpr (u_ + X3_D < NU_) { LDM((B) + 3 * (u_ + X3_D), (U0) + u_ + X3_D) }                     \
             if constexpr (r_ == 0 && s_ + 1 < (NS)) {                                                           \
-                _Pragma("unroll") for (int c_ = 0; c_ < 3; ++c_) {                                              \
-                    na_[c_] = SRC(c_)[(8 * s_ + 8) * QSD + nq]; nb_[c_] = SRC(c_)[(8 * s_ + 12) * QSD + nq];    \
-                }                                                                                               \
+                _Pragma("unroll") for (int c_ = 0; c_ < 3; ++c_)                                                \
+                    _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) N_[c_][p_] = PL_RD(SRC(c_), s_ + 1, p_);   \
             }                                                                                                   \
             EXTRA(u_)                                                                                           \
             _Pragma("unroll") for (int o_ = 0; o_ < (NO); ++o_) {                                               \
@@ -173,9 +193,6 @@ __device__ __forceinline__ void x3_units(F &&f, std::integer_sequence<int, I...>
                 if (c_ >= 0 && c_ < 3) ACC[o_][tl_] = mfma_x3(xw[((U0) + u_) % X3_NR], F_[c_], ACC[o_][tl_]);    \
             }                                                                                                   \
             if constexpr (s_ + 1 < (NS)) {                                                                      \
-                _Pragma("unroll") for (int c_ = 0; c_ < 3; ++c_)                                                \
-                    if (r_ == (1 + c_ < 3 * (NT) - 1 ? 1 + c_ : 3 * (NT) - 1))                                  \
-                        _Pragma("unroll") for (int d_ = 0; d_ < 4; ++d_) split3_dword(na_[c_], nb_[c_], d_, N_[c_]); \
                 if constexpr (r_ == 3 * (NT) - 1) {                                                             \
                     _Pragma("unroll") for (int c_ = 0; c_ < 3; ++c_)                                            \
                         _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) F_[c_][p_] = N_[c_][p_];               \
@@ -209,11 +226,12 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
     static_assert(!(RS && K8), "the fused resampler feeds the 16 kHz model");
     constexpr int QL = K8 ? 8 : 16;               // loader lanes per stream = quads per quarter column
     constexpr int CS = 4 * QL;                    // folded-operand rows per column
-    constexpr int PS = K8 ? 16 : 32;              // quad rows per |STFT| column (enc0's input)
+    constexpr int PP = K8 ? 24 : 48;              // quad rows per |STFT| column (enc0's input) as planes: 12 per K-step
     __shared__ f32x4 lds[T_LDS_F4 + (RS ? MT16 * FQ : 0) + (F32IN ? T_FLAG_F4 : 0)];     // RS: + the tile's 16 kHz frames F (one workgroup per CU either way)
     f32x4 *const RX = lds;
     f32x4 *const RE = lds + T_ROW_E * QSD;
-    f32x4 *const RH = lds + T_ROWS_X * QSD;
+    f32x4 *const RP0 = lds + T_ROW_E0 * QSD;
+    f32x4 *const RH = lds + T_ROW_H * QSD;
     float *const headp = reinterpret_cast<float *>(RH + T_ROWS_H * QSD);   // [4][16]
     float *const nyqv = headp + 64;              // [3][16]
     float *const fcor = nyqv + 48;               // [3 columns][y128, a64, b64][16 streams]
@@ -251,8 +269,11 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
     // the second weight stream: encoder.0 on the bf16 split (S_ENC0_X3)
     const __amdgpu_buffer_rsrc_t wrx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.wstream_x), 0, (int)P.wstream_x_bytes, 0x00020000);
 #define WX(blk) ldw(wrx, lane16, (blk))
+    // the third: encoder.1 on the bf16 split (S_ENC1_X3)
+    const __amdgpu_buffer_rsrc_t wry = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.wstream_y), 0, (int)P.wstream_y_bytes, 0x00020000);
+#define WY(blk) ldw(wry, lane16, (blk))
     const int o_stft = (int)P.sect[w][S_STFT], o_nyq = (int)P.sect[w][S_NYQ], o_x0 = (int)P.sect[w][S_ENC0_X3];
-    const int o_e1 = (int)P.sect[w][S_ENC1], o_e2 = (int)P.sect[w][S_ENC2], o_e3 = (int)P.sect[w][S_ENC3];
+    const int o_y1 = (int)P.sect[w][S_ENC1_X3], o_e2 = (int)P.sect[w][S_ENC2], o_e3 = (int)P.sect[w][S_ENC3];
     const int o_l = (int)P.sect[w][S_LSTM], o_x3 = (int)P.sect[w][S_LSTM_X3];
     const int T = (ONE || RS) ? 1 : KP(T);
 
@@ -357,17 +378,17 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
     // (requesting the first part's first chunk right here, IN FRONT of the state loads, was measured: 48.6 - 49.7 us against
     //  47.9 - 48.2 for 4 096 streams at 48 kHz on one box - it delays the state loads queued behind it.  Behind them: below.)
 
-    // ---- prologue: h_{t-1} -> LDS quads (32 rows x 16 streams), c_{t-1} -> registers, state machines -> LDS ----
+    // ---- prologue: h_{t-1} -> LDS planes (wave w cuts K-step w: the quads of units 32 w + 16 rt + 4 kq .., the cell's own layout),
+    //      c_{t-1} -> registers, state machines -> LDS ----
     // Request order = the order in which the frame loop needs things (vmcnt retires in issue order): h, the wave's gate biases
     // (compact: 128 floats, kept in LDS for the call) and the tile's state machines (their 16 threads only), then - not RS, where
     // a whole resampling phase sits in front of the frame loop - the frame loop's first requests: the W_hh blocks of its first two
     // groups and the frame's first two columns depend on kernel arguments only, and W_hh is the coldest part of the weight
     // stream; then the window and c.  Streams past n (the last tile's tail) read slot 0's state and compute on it: a stream is
     // a column of every MFMA, nothing crosses columns, and every store of the kernel is guarded by `live`.
-    f32x4 hv[2];
-    const int fm = tid & 15, part = tid >> 4;      // fm == n: ONE slot lookup serves h, c and the state machine
+    f32x4 hv[2];                                   // (tid & 15 == n: ONE slot lookup serves h, c and the state machine)
 #pragma unroll
-    for (int qq = 0; qq < 2; ++qq) hv[qq] = reinterpret_cast<const f32x4 *>(KP(state) + (size_t)slot * 256)[part * 2 + qq];
+    for (int rt = 0; rt < 2; ++rt) hv[rt] = *reinterpret_cast<const f32x4 *>(KP(state) + (size_t)slot * 256 + 32 * w + 16 * rt + 4 * kq);
     SB();
     auto bias2 = __builtin_amdgcn_raw_buffer_load_b64(wrs, lane * 8, (o_l + T_LSTM_BIAS_BLOCK) * 1024, 0);
     const bool sm_thread = (tid < MT16) && live;
@@ -385,6 +406,7 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
 #define X3_LDR(blk, slot) _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) xw[(slot) % X3_NR][p_] = WL((blk) + p_);
 #define X3_LD(B, u) X3_LDR((B) + 3 * (u), (u))
 #define X3_LDX(blk, slot) _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) xw[(slot) % X3_NR][p_] = WX((blk) + p_);
+#define X3_LDY(blk, slot) _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) xw[(slot) % X3_NR][p_] = WY((blk) + p_);
 #define H_FIRST(L, tt)                                                                                          \
     {                                                                                                           \
         _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LD((L) + LSTM_X3_HALF_BLOCKS, u_) }             \
@@ -412,8 +434,7 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
         }
     }
     SB();
-#pragma unroll
-    for (int qq = 0; qq < 2; ++qq) RH[(part * 2 + qq) * QSD + fm] = hv[qq];
+    st_planes(RH + 12 * w * QSD + nq, hv[0], hv[1]);
     reinterpret_cast<decltype(bias2) *>(biasL + 32 * w)[lane] = bias2;
     int seg_last = 0;
     if (tid < MT16) {
@@ -752,8 +773,8 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
 
     STAMP(0);
     for (int t = 0;;) {                          // T >= 1; the back edge is at the bottom, behind the next frame's first requests
-        int ws_stft = o_stft, ws_x0 = o_x0, ws_e1 = o_e1, ws_e2 = o_e2, ws_e3 = o_e3, ws_l = o_l, ws_x3 = o_x3;
-        asm volatile("" : "+s"(ws_stft), "+s"(ws_x0), "+s"(ws_e1), "+s"(ws_e2), "+s"(ws_e3), "+s"(ws_l), "+s"(ws_x3));
+        int ws_stft = o_stft, ws_x0 = o_x0, ws_y1 = o_y1, ws_e2 = o_e2, ws_e3 = o_e3, ws_l = o_l, ws_x3 = o_x3;
+        asm volatile("" : "+s"(ws_stft), "+s"(ws_x0), "+s"(ws_y1), "+s"(ws_e2), "+s"(ws_e3), "+s"(ws_l), "+s"(ws_x3));
         // ---- recurrent gate half W_hh . h_{t-1} (4 K-steps x {4 gates x 2 row tiles}, bf16 split) with the frame ingested under it ----
         f32x4 G[8];                               // gate q, row tile rt -> G[2 q + rt]
         {
@@ -929,10 +950,11 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
             E0_FIRST
             SB();
             __syncthreads();   // (1b) every wave is done reading the folded operands: the magnitudes may overwrite them
-            {   // |.| of the three columns -> rows 16 c + channel / 4 = 16 c + 4 w + kq
-                f32x4 *o = RX + (4 * w) * QSD + nq;
+            {   // |.| of the three columns -> planes: the wave's row tile (channels 16 w + 4 kq + i) is half w & 1 of K-step w >> 1's
+                // fragments, plane group 24 c + 12 (w >> 1)
+                f32x4 *o = RX + 12 * (w >> 1) * QSD + nq;
 #pragma unroll
-                for (int c = 0; c < 3; ++c) st2(o + PS * c * QSD, pk::mag(sre[c], sim[c]));
+                for (int c = 0; c < 3; ++c) st_planes_half(o + PP * c * QSD, w & 1, pk::mag(sre[c], sim[c]));
             }
         } else
         // ---- STFT: wave w owns bins bin_of_channel_fold3(32 w + 16 rt + r): row tile 0 = 16 odd bins, cos on po, -sin on qo, K = 64
@@ -989,13 +1011,10 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
             E0_FIRST
             SB();
             __syncthreads();   // (1b) every wave is done reading the folded operands: the magnitudes may overwrite them
-            // |.| of the three columns -> rows 32 c + 8 w + 4 rt + kq
+            // |.| of the three columns -> planes: the wave's two row tiles are K-step w's fragments, plane group 48 c + 12 w
 #pragma unroll
-            for (int rt = 0; rt < 2; ++rt) {
-                f32x4 *o = RX + (8 * w + 4 * rt) * QSD + nq;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) st2(o + PS * c * QSD, pk::mag(are[c][rt], aim[c][rt]));
-            }
+            for (int c = 0; c < 3; ++c)
+                st_planes(RX + (PP * c + 12 * w) * QSD + nq, pk::mag(are[c][0], aim[c][0]), pk::mag(are[c][1], aim[c][1]));
         }
 #undef E0_FIRST
         STAMP(3);
@@ -1005,7 +1024,7 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
         // ---- enc0: 129 (8 kHz: 65) -> 128 ch, k3 s1 p1, 3 -> 3 columns, as a direct 3-tap convolution on the bf16 split (X3_CONV):
         //      per K-step 3 taps x 2 row tiles = 6 units, 7 column products per tile; the Nyquist channel and the bias on the VALU ----
         constexpr int NU0 = (K8 ? 2 : 4) * 3 * 2;     // enc0's units: its K-steps x 3 taps x 2 row tiles
-        f32x4 e1b[2], E1w[2];
+        f32x4 e1b;
         {
             f32x4 acc[3][2];
             {   // accumulators start at the bias plus the Nyquist channel's terms sum_tap W[tap] |X_N|[o + tap - 1], exact fp32 fmas
@@ -1021,48 +1040,43 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
                         acc[o][rt] = a;
                     }
             }
-#define E0_SRC(c) (RX + PS * (c) * QSD)
-#define E0_EXTRA(u) if constexpr ((u) == NU0 - X3_D) { e1b[0] = WL(ws_e1); e1b[1] = WL(ws_e1 + 1); E1w[0] = WL(ws_e1 + 2); E1w[1] = WL(ws_e1 + 3); }
-            X3_CONV(K8 ? 2 : 4, 2, 1, 3, ws_x0 + ENC0_X3_F32_BLOCKS, 0, E0_SRC, acc, E0_EXTRA)
+            // enc1's bias and its first X3_D units ride in enc0's last units: the ring goes on, unit v of enc1 in slot NU0 + v
+#define E0_SRC(c) (RX + PP * (c) * QSD)
+#define E0_EXTRA(u)                                                                                             \
+            if constexpr ((u) == NU0 - X3_D) e1b = WY(ws_y1);                                                   \
+            if constexpr ((u) + X3_D >= NU0) { X3_LDY(ws_y1 + ENC1_X3_F32_BLOCKS + 3 * ((u) + X3_D - NU0), (u) + X3_D) }
+            X3_CONV(K8 ? 2 : 4, 2, 1, 3, X3_LDX, ws_x0 + ENC0_X3_F32_BLOCKS, 0, E0_SRC, acc, E0_EXTRA)
 #undef E0_SRC
 #undef E0_EXTRA
+            // ReLU -> planes: the wave's channels 32 w .. are K-step w of enc1's fragments, plane group 144 + 48 c + 12 w
 #pragma unroll
-            for (int rt = 0; rt < 2; ++rt) {      // ReLU -> rows 168 + 32 o + 8 w + 4 rt + kq
-                f32x4 *o = RE + (8 * w + 4 * rt) * QSD + nq;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) o[32 * c * QSD] = relu4(acc[c][rt]);
-            }
+            for (int c = 0; c < 3; ++c) st_planes(RP0 + (48 * c + 12 * w) * QSD + nq, relu4(acc[c][0]), relu4(acc[c][1]));
         }
         STAMP(5);
         __syncthreads();   // (3) enc0 out
         STAMP(6);
 
-        // ---- enc1: 128 -> 64 ch, k3 s2 p1, 3 -> 2 columns; wave w: n-tile w & 1, column w >> 1; 16 k-iterations ----
+        // ---- enc1: 128 -> 64 ch, k3 s2 p1, 3 -> 2 columns, on the bf16 split (X3_CONV, S_ENC1_X3): wave w = channels 16 w .. 16 w + 15
+        //      (one row tile) of BOTH output columns; per K-step 3 taps = 3 units, 4 column products (tap 0 -> column 1 on x1, tap 1 ->
+        //      column 0 on x0 and column 1 on x2, tap 2 -> column 0 on x1): 96 bf16 MFMAs where the fp32 form had 128 of twice the length ----
         f32x4 e2b[2], E2w[2], e3b[2], E3w[2];
         {
-            const int nt = w & 1, tp = w >> 1;
-            const int ws = ws_e1 + 2;
-            f32x4 acc[2] = {e1b[0], e1b[1]};
-#define E1_ROW(it) (RE + ((tp + ((it) >> 3)) * 32 + 4 * ((it) & 7)) * QSD + nq)
-            f32x4 Aw[2] = {E1w[0], E1w[1]}, Bw[2], Aa = *E1_ROW(0), Ba;
-            for (int it = 0; it < 16; it += 2) {
-                Bw[0] = WL(ws + 2 * (it + 1)); Bw[1] = WL(ws + 2 * (it + 1) + 1); Ba = *E1_ROW(it + 1); SB();
-                acc[0] = mfma16(Aw[0], Aa, acc[0]); acc[1] = mfma16(Aw[1], Aa, acc[1]); SB();
-                const int itn = it + 2 < 16 ? it + 2 : 14;
-                Aw[0] = WL(ws + 2 * itn); Aw[1] = WL(ws + 2 * itn + 1); Aa = *E1_ROW(itn); SB();
-                if (it == 14) {     // next layers' first blocks (enc2: this wave's K half)
-                    const int ge = 2 + 8 * (w >> 1);
-                    e2b[0] = WL(ws_e2); e2b[1] = WL(ws_e2 + 1);
-                    E2w[0] = WL(ws_e2 + ge); E2w[1] = WL(ws_e2 + ge + 1);
-                    e3b[0] = WL(ws_e3); e3b[1] = WL(ws_e3 + 1);
-                    E3w[0] = WL(ws_e3 + 2); E3w[1] = WL(ws_e3 + 3);
-                    SB();
-                }
-                acc[0] = mfma16(Bw[0], Ba, acc[0]); acc[1] = mfma16(Bw[1], Ba, acc[1]); SB();
+            constexpr int NU1 = 4 * 3;
+            f32x4 acc[2][1] = {{e1b}, {e1b}};
+#define E1_SRC(c) (RP0 + 48 * (c) * QSD)
+#define E1_EXTRA(u)                                                                                             \
+            if constexpr ((u) == NU1 - X3_D) {     /* next layers' first blocks (enc2: this wave's K half) */    \
+                const int ge = 2 + 8 * (w >> 1);                                                                \
+                e2b[0] = WL(ws_e2); e2b[1] = WL(ws_e2 + 1);                                                     \
+                E2w[0] = WL(ws_e2 + ge); E2w[1] = WL(ws_e2 + ge + 1);                                           \
+                e3b[0] = WL(ws_e3); e3b[1] = WL(ws_e3 + 1);                                                     \
+                E3w[0] = WL(ws_e3 + 2); E3w[1] = WL(ws_e3 + 3);                                                 \
             }
-#undef E1_ROW
+            X3_CONV(4, 1, 2, 2, X3_LDY, ws_y1 + ENC1_X3_F32_BLOCKS, NU0, E1_SRC, acc, E1_EXTRA)
+#undef E1_SRC
+#undef E1_EXTRA
 #pragma unroll
-            for (int rt = 0; rt < 2; ++rt) RX[(16 * tp + 8 * nt + 4 * rt) * QSD + nq] = relu4(acc[rt]);
+            for (int o = 0; o < 2; ++o) RX[(16 * o + 4 * w) * QSD + nq] = relu4(acc[o][0]);      // fp32, rows 16 o + channel / 4, for enc2
         }
         STAMP(7);
         __syncthreads();   // (4) enc1 out in rows 0..31
@@ -1109,11 +1123,10 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
             SB();
 #pragma unroll
             for (int j = 0; j < 4; ++j) { acc[0] = mfma16(wv[2 * j], av[j], acc[0]); acc[1] = mfma16(wv[2 * j + 1], av[j], acc[1]); }
-#pragma unroll
-            for (int rt = 0; rt < 2; ++rt) RX[(8 * w + 4 * rt) * QSD + nq] = relu4(acc[rt]);
+            st_planes(RX + 12 * w * QSD + nq, relu4(acc[0]), relu4(acc[1]));      // channels 32 w .. = K-step w of the LSTM's input half
         }
         STAMP(11);
-        __syncthreads();   // (6) LSTM input x in rows 0..31
+        __syncthreads();   // (6) LSTM input x as planes in rows 0..47
         STAMP(12);
 
         // ---- LSTM: input half W_ih . x on top of the recurrent half, cell, head partial ----
@@ -1132,6 +1145,7 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
             f32x4 part4 = f32x4{0.f, 0.f, 0.f, 0.f};
             // a rejected frame (float32 only) leaves the stream's h and c as they were: not stored, and held for the next frame
             const bool bad = f32in && (K8 ? (flagL[n] | flagL[16 + n]) : flagL[n]) != 0;
+            f32x4 hq[2];
 #pragma unroll
             for (int rt = 0; rt < 2; ++rt) {
                 const f32x4 i4 = G[0 + rt], f4 = G[2 + rt], g4 = G[4 + rt], o4 = G[6 + rt], c4 = cst[rt], hwv = hw[rt];
@@ -1141,11 +1155,11 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
                 f32x4 hn = pk::mul(pk::sigmoid4(o4), pk::tanh4(cn));
                 part4 = pk::fma(hwv, relu4(hn), part4);
                 if constexpr (f32in && !ONE && !RS) {   // (the head ignores z of a rejected stream)
-                    const f32x4 hp = RH[(8 * w + 4 * rt) * QSD + nq];   // h_{t-1}: this thread's own place, every reader is past (7)
-                    hn = bad ? hp : hn;
+                    hn = bad ? hv[rt] : hn;             // h_{t-1}: the lane's own units, kept in registers beside c (LDS holds pieces)
                     cn = bad ? c4 : cn;
+                    hv[rt] = hn;
                 }
-                RH[(8 * w + 4 * rt) * QSD + nq] = hn;
+                hq[rt] = hn;
                 // (one frame: a rejected stream skips the store; more: the held values go back, the last accepted frame's)
                 if (t == T - 1 && live && !((ONE || RS) && bad)) {
                     *reinterpret_cast<f32x4 *>(KP(state) + (size_t)slot * 256 + 32 * w + 16 * rt + 4 * kq) = hn;
@@ -1153,6 +1167,8 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
                 }
                 cst[rt] = cn;
             }
+            // h_t for the next frame's recurrent half, as planes (a single-frame call has no next frame)
+            if constexpr (!ONE && !RS) st_planes(RH + 12 * w * QSD + nq, hq[0], hq[1]);
             float part_ = (part4.x + part4.y) + (part4.z + part4.w);
             part_ += __shfl_xor(part_, 16);
             part_ += __shfl_xor(part_, 32);
@@ -1188,6 +1204,9 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(const float *k_w
 #undef X3_LD
 #undef X3_LDR
 #undef X3_LDX
+#undef PL_RD
+#undef X3_LDY
+#undef WY
 #undef WX
 #undef X_ISSUE
 #undef WL

@@ -51,7 +51,7 @@ constexpr int ENC1_BLOCKS = 4 + 2 * 16;
 constexpr int ENC2_BLOCKS = 4 + 2 * 8;     // packed for waves 0,1; waves 2,3 read the second K half of the same streams
 constexpr int ENC3_BLOCKS = 4 + 8;
 constexpr int LSTM_BLOCKS = 16 + 64 + 64 + 4;  // bias(4 gates), W_ih, W_hh, head weights
-enum Section { S_STFT = 0, S_NYQ, S_ENC0, S_ENC1, S_ENC2, S_ENC3, S_LSTM, S_HEADB, S_LSTM_X3, S_ENC0_X3, S_COUNT };  // S_HEADB: 1 block, float 0 = head bias
+enum Section { S_STFT = 0, S_NYQ, S_ENC0, S_ENC1, S_ENC2, S_ENC3, S_LSTM, S_HEADB, S_LSTM_X3, S_ENC0_X3, S_ENC1_X3, S_COUNT };  // S_HEADB: 1 block, float 0 = head bias
 // S_LSTM_X3 (16-stream kernel only, pack_silero_v5_t16): the wave's W_ih and W_hh rows once more, as three exact bf16 pieces
 // w = w1 + w2 + w3 (w1 = hi16(w), w2 = hi16(w - w1), w3 = w - w1 - w2) for v_mfma_f32_16x16x32_bf16.  Per half (W_ih, then W_hh):
 // 4 K-steps s x 8 row tiles (gate q, rt: tile 2 q + rt) x 3 pieces, block (s * 8 + tile) * 3 + piece.  A block is the tile's A
@@ -66,6 +66,14 @@ constexpr int LSTM_X3_HALF_BLOCKS = 4 * 8 * 3;
 // the pieces of the tile's A fragment as in S_LSTM_X3 (lane (row l & 15, kq), element e = K 32 s + 16 (e >> 2) + 4 kq + (e & 3)),
 // piece 0 first; input channel K = the STFT's channel order (bin_of_channel_fold3 / bin_of_channel_8k).
 constexpr int ENC0_X3_F32_BLOCKS = 2 + 3 * 2;
+// S_ENC1_X3 (16-stream kernel only): the THIRD weight stream (PackedWeights::data_y, StepParams::wstream_y; sect entries are block
+// offsets into it) - the first two streams keep every byte they had, S_ENC1 stays in the first, unread by the 16-stream kernel.
+// encoder.1 (128 -> 64 channels, k3 s2 p1, 3 -> 2 columns) as a direct convolution on the bf16 split: wave w = output channels
+// 16 w + r, ONE row tile, for both output columns.  ENC1_X3_F32_BLOCKS fp32 block (the bias, vector_block16), then one unit of three
+// blocks per (K-step s < 4, tap): block ENC1_X3_F32_BLOCKS + 3 (s * 3 + tap) + piece, the tile's A fragment as in S_LSTM_X3 over
+// the input channels 32 s .. 32 s + 31 in their natural order (enc0's output channel = the K index of its activation planes).
+constexpr int ENC1_X3_F32_BLOCKS = 1;
+constexpr int ENC1_X3_BLOCKS = ENC1_X3_F32_BLOCKS + 3 * 4 * 3;
 __host__ __device__ constexpr int bin_of_channel(int ch) {
     return (ch >> 5) < 2 ? 64 * (ch >> 5) + 2 * (ch & 31) : 64 * ((ch >> 5) - 2) + 2 * (ch & 31) + 1;
 }
@@ -177,6 +185,10 @@ struct StepParams {
     const float *wstream;          // packed weight streams
     uint32_t wstream_bytes;
     uint32_t sect[NWAVES][16];     // block offset of each section, per wave
+    // (the second and third streams' sizes sit where the compiler would pad: the struct is a by-value kernel argument and keeps the
+    //  size it had with one stream.  16 bytes more put silero_v4_step16's last argument into a seventh 64-byte line of the kernarg
+    //  segment: + 0.3 us per step of the V4 + V5 mix, measured - profiles/r08_planes_other_configs.jsonl)
+    uint32_t wstream_y_bytes;
     float *state;                  // [max_streams][256]
     SmSlot *sm;                    // [max_streams]
     const int32_t *slots;          // [n] or nullptr (identity)
@@ -189,12 +201,16 @@ struct StepParams {
     int32_t fmt;                   // vad_frame_format
     float thresh;                  // denoise gate, < 0 = off
     int32_t variant;               // 1 = the graph's 8 kHz sub-model (pack_weights.h): V4 two LSTM steps per frame, V5 256-sample frames
-    const float *wstream_x;        // second weight stream (PackedWeights::data_x), or nullptr
     uint32_t wstream_x_bytes;
+    const float *wstream_x;        // second weight stream (PackedWeights::data_x), or nullptr
+    const float *wstream_y;        // third weight stream (PackedWeights::data_y), or nullptr
 #ifdef VADK_STAMPS
     unsigned long long *stamps;    // diagnostic builds only (tools/kbench.cpp): [block][wave][16] s_memtime stamps
 #endif
 };
+#ifndef VADK_STAMPS
+static_assert(sizeof(StepParams) == 368, "StepParams keeps its size (see above)");
+#endif
 
 // resampler launch parameters (csrc/resample.hip)
 struct ResampleSeg {

@@ -175,7 +175,10 @@ __device__ __forceinline__ f32x4 ldw(__amdgpu_buffer_rsrc_t rs, int voff, int bl
 // the six products x_i w_j with i + j <= 4 on v_mfma_f32_16x16x32_bf16 (products exact, fp32 accumulation) leave out terms of at most
 // ~2^-24 |x w|: fp32's own rounding, at 6 x 16 cycles per 16 x 16 x 32 tile instead of 8 x 32 for v_mfma_f32_16x16x4_f32.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-// dword of the three B fragments from two consecutive K values a (low half) and b (high half): 2 and + 2 sub + 3 perm per pair
+// dword of the three B fragments from two consecutive K values a (low half) and b (high half): 4 v_and + 4 v_sub_f32 + 3 v_perm_b32
+// = 11 instructions per pair of values, 44 per fragment.  The 16-stream kernel therefore splits an activation ONCE,
+// where it is produced (split3_frag / split3_half below), and its consumers read finished pieces from LDS (silero_v5_t16.hip:
+// activation planes).
 __device__ __forceinline__ void split3_pair(float a, float b, unsigned &p1, unsigned &p2, unsigned &p3) {
     const unsigned ua = __builtin_bit_cast(unsigned, a), ub = __builtin_bit_cast(unsigned, b);
     const float ra = a - __builtin_bit_cast(float, ua & 0xffff0000u), rb = b - __builtin_bit_cast(float, ub & 0xffff0000u);
@@ -192,6 +195,22 @@ __device__ __forceinline__ void split3_dword(f32x4 xa, f32x4 xb, int d, u32x4 *F
     unsigned p1, p2, p3;
     split3_pair(a, b, p1, p2, p3);
     F[0][d] = p1; F[1][d] = p2; F[2][d] = p3;
+}
+// The producer's side of the split.  A wave's two D quads of a lane (stream n, rq) - row tiles rt = 0, 1: channels 32 w + 16 rt +
+// 4 rq + i - ARE the K elements 0..3 and 4..7 of lane (n, kq = rq)'s B fragment of K-step s = w, so the lane that computed the
+// values cuts them: the three pieces F[0..2] of that fragment, the same numbers split3_dword gives a consumer that reads the fp32
+// quads back.
+__device__ __forceinline__ void split3_frag(f32x4 xa, f32x4 xb, u32x4 *F) {
+#pragma unroll
+    for (int d = 0; d < 4; ++d) split3_dword(xa, xb, d, F);
+}
+// half a fragment (one D quad = K elements 0..3 or 4..7): dwords 0, 1 or 2, 3 of the three pieces
+__device__ __forceinline__ void split3_half(f32x4 x, u32x2 *H) {
+    unsigned lo[3], hi[3];
+    split3_pair(x.x, x.y, lo[0], lo[1], lo[2]);
+    split3_pair(x.z, x.w, hi[0], hi[1], hi[2]);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) H[p] = u32x2{lo[p], hi[p]};
 }
 // one 16 x 16 x 32 tile: A pieces W[0..2], B pieces X[0..2], the six leading products, smallest first
 __device__ __forceinline__ f32x4 mfma_x3(const f32x4 *W, const u32x4 *X, f32x4 acc) {

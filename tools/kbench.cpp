@@ -83,6 +83,13 @@ int main(int argc, char **argv) {
         p.wstream_x = d_wx;
         p.wstream_x_bytes = (uint32_t)(pw.data_x.size() * 4);
     }
+    if (!pw.data_y.empty()) {        // the third stream (the 16-stream V5 packing's split encoder.1)
+        float *d_wy;
+        CK(hipMalloc(&d_wy, pw.data_y.size() * 4));
+        CK(hipMemcpy(d_wy, pw.data_y.data(), pw.data_y.size() * 4, hipMemcpyHostToDevice));
+        p.wstream_y = d_wy;
+        p.wstream_y_bytes = (uint32_t)(pw.data_y.size() * 4);
+    }
     memcpy(p.sect, pw.sect, sizeof pw.sect);
     p.state = d_state; p.sm = d_sm; p.slots = nullptr; p.probs = d_probs; p.events = nullptr; p.seg_frames = nullptr;
     p.n = B; p.T = T; p.fmt = 0; p.thresh = 0.01f;

@@ -11,7 +11,7 @@ hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-mfma-vgpr-form -mllvm 
 /tmp/kb16 "$REPO/cutter_vad_amd/weights/silero_v5_16k.svw" $B 200 > "$OUT/${TAG}_kb16.log" 2>&1
 cd /tmp && export TMPDIR=/tmp
 i=0
-for grp in "MfmaUtil" "VALUBusy" "LdsBankConflict" "SQ_INSTS_VALU_MFMA_F32 SQ_INSTS_VALU" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES" "FETCH_SIZE" "WRITE_SIZE"; do
+for grp in "MfmaUtil" "VALUBusy" "LdsBankConflict" "SQ_INSTS_VALU_MFMA_F32 SQ_INSTS_VALU" "SQ_INSTS_VALU_MFMA_BF16" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES" "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
   KB_RING=32 rocprofv3 --pmc $grp --kernel-trace -d "$OUT/${TAG}_sq16/p$i" -o kb -- /tmp/kb16 "$REPO/cutter_vad_amd/weights/silero_v5_16k.svw" $B 12 > "$OUT/${TAG}_sq16_p$i.log" 2>&1 || echo "pass $i ($grp) failed" >> "$OUT/${TAG}_sq16_progress.log"
   echo "pass $i done: $grp" >> "$OUT/${TAG}_sq16_progress.log"
