@@ -25,6 +25,8 @@ VAD_ERR_UNSUPPORTED = -7
 VAD_ERR_BUSY = -8
 
 VAD_FMT_F32, VAD_FMT_I16_32767, VAD_FMT_I16_32768 = 0, 1, 2
+VAD_FMT_ULAW8, VAD_FMT_ALAW8 = 3, 4         # ITU-T G.711, one byte per sample (include/vad_engine.h)
+G711_LAWS = {"ulaw": VAD_FMT_ULAW8, "alaw": VAD_FMT_ALAW8}
 VAD_EV_START, VAD_EV_END, VAD_EV_CONTINUE = 1, 2, 4
 VAD_EV_REJECTED = 0x80          # ABI 5: the frame held a NaN / Inf sample (include/vad_engine.h); probability NaN, state untouched
 VAD_FRAME_SAMPLES = 512
@@ -160,6 +162,7 @@ SIGNATURES = {
                                          C.POINTER(C.c_uint32)]),
     "vad_host_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "vad_host_free": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vad_g711_decode": (C.c_int, [C.c_int, _vp, C.c_int64, _vp]),
     "vad_tick_pending": (C.c_int, [_vp, C.c_int64, _i64p]),
     "vad_tick_push_gather": (C.c_int, [_vp, _i64p, C.c_int64, C.POINTER(C.c_char_p), C.c_int32, C.c_int, C.c_int, _i32p]),
     "vad_tick_push_status": (C.c_int, [_vp, _i64p, C.c_int64, _vp, C.c_int32, C.c_int, C.c_int, _i32p]),

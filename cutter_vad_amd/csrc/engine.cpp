@@ -27,6 +27,7 @@
 #include <string>
 #include <thread>
 #include <unordered_map>
+#include <array>
 #include <vector>
 
 #include "pack_weights.h"
@@ -43,6 +44,7 @@ extern "C" hipError_t vadk_launch_slot_control(vadk::SmSlot *sm, float *state, c
                                                const vadk::SmSlot *def, const vad_thresholds *d_thr, int nthr, hipStream_t stream);
 extern "C" hipError_t vadk_launch_sm_replay(vadk::SmSlot *sm, int slot, const float *probs, int n, uint8_t *events,
                                             int32_t *seg, hipStream_t stream);
+extern "C" hipError_t vadk_launch_g711_expand(const void *d_in, int16_t *d_out, int64_t nbytes, int alaw, hipStream_t stream);
 
 namespace {
 
@@ -128,6 +130,8 @@ struct vad_engine {
     uint8_t *d_events = nullptr; size_t d_events_cap = 0;
     int32_t *d_seg = nullptr;  size_t d_seg_cap = 0;
     int32_t *d_slots = nullptr; size_t d_slots_cap = 0;
+    // G.711 frames expanded to int16 for the kernels whose loaders do not decode them (launch())
+    int16_t *d_g711 = nullptr; size_t d_g711_cap = 0;
     // small calls (a few streams: the one-wrapper-per-client pattern): ONE pinned block in, ONE pinned block out
     static constexpr size_t SMALL_BYTES = 256u << 10;
     uint8_t *h_small_in = nullptr, *h_small_out = nullptr;   // hipHostMalloc
@@ -490,7 +494,31 @@ int ensure(vad_engine *e, T *&ptr, size_t &cap, size_t need) {
     return VAD_OK;
 }
 
-size_t frame_bytes(const vad_engine *e, int fmt) { return (fmt == VAD_FMT_F32 ? 4u : 2u) * (size_t)e->frame_samples; }
+bool is_g711(int fmt) { return fmt == VAD_FMT_ULAW8 || fmt == VAD_FMT_ALAW8; }
+size_t sample_bytes(int fmt) { return fmt == VAD_FMT_F32 ? 4u : is_g711(fmt) ? 1u : 2u; }
+size_t frame_bytes(const vad_engine *e, int fmt) { return sample_bytes(fmt) * (size_t)e->frame_samples; }
+
+// ITU-T G.711: code -> 16-bit linear PCM, the two laws as tables [law][code] (include/vad_engine.h: VAD_FMT_ULAW8 / VAD_FMT_ALAW8)
+const int16_t *g711_table(int fmt) {
+    static const std::array<std::array<int16_t, 256>, 2> tab = [] {
+        std::array<std::array<int16_t, 256>, 2> t{};
+        for (int b = 0; b < 256; ++b) {
+            const int u = ~b & 0xFF;
+            const int m = (((u & 0x0F) << 3) + 0x84) << ((u & 0x70) >> 4);
+            t[0][(size_t)b] = (int16_t)((u & 0x80) ? 0x84 - m : m - 0x84);
+            const int a = b ^ 0x55, seg = (a & 0x70) >> 4;
+            int v = (a & 0x0F) << 4;
+            v = seg == 0 ? v + 8 : seg == 1 ? v + 0x108 : (v + 0x108) << (seg - 1);
+            t[1][(size_t)b] = (int16_t)((a & 0x80) ? v : -v);
+        }
+        return t;
+    }();
+    return tab[fmt == VAD_FMT_ALAW8 ? 1 : 0].data();
+}
+void g711_to_i16(int fmt, const uint8_t *in, size_t n, int16_t *out) {
+    const int16_t *t = g711_table(fmt);
+    for (size_t i = 0; i < n; ++i) out[i] = t[in[i]];
+}
 
 // The kernels address frames through a 32-bit buffer descriptor with signed 32-bit offset arithmetic: one call may not
 // span 2 GiB of frames (1 M float32 frames).  Rejected here instead of wrapping silently.
@@ -498,9 +526,11 @@ int check_call_size(vad_engine *e, int64_t n, int32_t T, int fmt) {
     if (n < 0 || T < 1 || n > e->max_streams)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: bad stream or frame count (n = %lld, T = %d, max_streams = %d)",
                        (long long)n, T, e->max_streams);
-    if ((uint64_t)n * (uint64_t)T * frame_bytes(e, fmt) >= (1ull << 31))
+    // (G.711: sized as the int16 frames the expansion in launch() may turn them into)
+    const uint64_t fb = is_g711(fmt) ? frame_bytes(e, VAD_FMT_I16_32768) : frame_bytes(e, fmt);
+    if ((uint64_t)n * (uint64_t)T * fb >= (1ull << 31))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: n * T * frame bytes = %llu exceeds the 2 GiB one call may address",
-                       (unsigned long long)((uint64_t)n * (uint64_t)T * frame_bytes(e, fmt)));
+                       (unsigned long long)((uint64_t)n * (uint64_t)T * fb));
     return VAD_OK;
 }
 
@@ -520,9 +550,21 @@ int check_slots(vad_engine *e, const int64_t *slots, int64_t n) {
     return VAD_OK;
 }
 
-int launch(vad_engine *e, const vadk::StepParams &p, hipStream_t s) {
+int launch(vad_engine *e, const vadk::StepParams &p_in, hipStream_t s) {
     hipError_t r = hipErrorInvalidValue;
+    vadk::StepParams p = p_in;
     const bool t16 = e->d_wstream16 && (e->tile_policy == 16 || (e->tile_policy == 0 && !e->shared_gpu && (p.T == 1 || p.n <= vad_engine::T16_MAX_STREAMS)));
+    if (is_g711(p.fmt) && !(e->version == 5 && t16)) {
+        // only the 16-stream V5 kernel decodes G.711 in its loader: every other kernel gets the frames expanded to int16 in HBM by
+        // a small kernel in front of it on the same stream (the link still carried one byte per sample) and runs as I16_32768
+        const size_t nb = (size_t)p.n * (size_t)p.T * (size_t)e->frame_samples;
+        if (int rc = ensure(e, e->d_g711, e->d_g711_cap, 2 * nb)) return rc;
+        r = vadk_launch_g711_expand(p.frames, e->d_g711, (int64_t)nb, p.fmt == VAD_FMT_ALAW8 ? 1 : 0, s);
+        if (r != hipSuccess) return e->hip_fail(r, "kernel launch (G.711 expansion)");
+        p.frames = e->d_g711;
+        p.fmt = VAD_FMT_I16_32768;
+        r = hipErrorInvalidValue;
+    }
     if (e->version == 4 && e->d_wstream16 && e->tile_policy != 32) {
         // Silero V4: 16-stream tiles, two workgroups per CU (each fills the other's waits) - one per CU while the call has no
         // more tiles than the GPU has CUs, so that a small batch spreads out instead of pairing up
@@ -561,7 +603,7 @@ int step_host(vad_engine *e, const int64_t *slots, int64_t n, int32_t T, const v
     std::lock_guard<std::mutex> lk(e->mu);
     if (n < 0 || T < 1 || (n > 0 && (!slots || !frames || !probs)))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: null buffer or bad count");
-    if (fmt < VAD_FMT_F32 || fmt > VAD_FMT_I16_32768)
+    if (fmt < VAD_FMT_F32 || fmt > VAD_FMT_ALAW8)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: unknown frame format %d", fmt);
     if (n == 0) return VAD_OK;
     if (int rc = check_call_size(e, n, T, fmt)) return rc;
@@ -773,7 +815,7 @@ void vad_engine_destroy(vad_engine *e) {
     weights_release(e->d_wstream16);
     weights_release(e->d_wstream16x);
     weights_release(e->d_wstream16y);
-    void *bufs[] = {e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots,
+    void *bufs[] = {e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots, e->d_g711,
                     e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
@@ -1021,6 +1063,12 @@ int vad_stream_set_thresholds_many(vad_engine *e, const int64_t *slots, int64_t 
     return slot_control(e, slots, n, CTL_SET_THRESHOLDS, t, nt);
 }
 
+int vad_g711_decode(int frame_fmt, const uint8_t *in, int64_t n, int16_t *out) {
+    if (!is_g711(frame_fmt) || n < 0 || (n > 0 && (!in || !out))) return VAD_ERR_INVALID_ARG;
+    g711_to_i16(frame_fmt, in, (size_t)n, out);
+    return VAD_OK;
+}
+
 int vad_step(vad_engine *e, const int64_t *slots, int64_t n, const void *frames, int frame_fmt, float denoise_thresh,
              float *probs_out) {
     return step_host(e, slots, n, 1, frames, frame_fmt, denoise_thresh, probs_out, nullptr, nullptr);
@@ -1049,10 +1097,12 @@ int vad_step_multi_device(vad_engine *e, const int32_t *d_slots, int64_t n, int3
                           float denoise_thresh, float *d_probs, uint8_t *d_events, int32_t *d_seg_frames, void *stream) {
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
-    if (frame_fmt < VAD_FMT_F32 || frame_fmt > VAD_FMT_I16_32768)
+    if (frame_fmt < VAD_FMT_F32 || frame_fmt > VAD_FMT_ALAW8)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: unknown frame format %d", frame_fmt);
     if (int rc = check_call_size(e, n, T, frame_fmt)) return rc;
     if (n > 0 && (!d_frames || !d_probs)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: null buffer");
+    if (is_g711(frame_fmt) && (reinterpret_cast<uintptr_t>(d_frames) & 3))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: G.711 frames on the device must be 4-byte aligned");
     if (n == 0) return VAD_OK;
     HIP_TRY(e, hipSetDevice(e->device));
     vadk::StepParams p = e->base;
@@ -1073,7 +1123,7 @@ int vad_step_submit(vad_engine *e, const int64_t *slots, int64_t n, int32_t T, c
                     int64_t *ticket) {
     if (!e || !ticket) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
-    if (fmt < VAD_FMT_F32 || fmt > VAD_FMT_I16_32768)
+    if (fmt < VAD_FMT_F32 || fmt > VAD_FMT_ALAW8)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: unknown frame format %d", fmt);
     if (int rc = check_call_size(e, n, T, fmt)) return rc;
     if (n < 1 || !slots || !frames) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: null buffer or bad count");
@@ -1700,6 +1750,18 @@ int vad_step_rates(vad_engine *e, int32_t nseg, const float *const *in, const in
 
 // ---- tick assembler: the multi-stream caller's side of vad_step_events, in C ---------------------------------------------
 namespace {
+// per-frame pointers to G.711 codes -> the same frames as int16 in `pcm`, `ptr` pointing at them (a null frame stays null)
+void g711_gather_decode(int fmt, const void *const *frames, int64_t n, int32_t nsamples, std::vector<int16_t> &pcm,
+                        std::vector<const void *> &ptr) {
+    pcm.resize((size_t)n * (size_t)nsamples);
+    ptr.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        int16_t *row = pcm.data() + (size_t)i * (size_t)nsamples;
+        if (frames[i]) g711_to_i16(fmt, static_cast<const uint8_t *>(frames[i]), (size_t)nsamples, row);
+        ptr[(size_t)i] = frames[i] ? row : nullptr;
+    }
+}
+
 // one frame of `slot` into the staging of the coming tick (tick_mu held).  With `defer` the row is assigned and its address handed
 // back in defer->dst, the samples are NOT copied: the caller carries that out later (a batch converting int16 chunks on the copy
 // crew); `pending` is then the caller's plan so far - it points into this buffer and is carried out before the buffer moves.
@@ -1771,8 +1833,16 @@ int tick_push_locked(vad_engine *e, int64_t slot, const void *samples, int32_t n
 }
 }  // namespace
 
+// G.711 frames are decoded here, on the host, on push: they join the VAD_FMT_I16_32768 groups, so the tick's groups, its result
+// layout, the segment arena and the WAV payload are what they are for a client that sent the decoded PCM16 itself
 int vad_tick_push(vad_engine *e, int64_t slot, const void *samples, int32_t nsamples, int frame_fmt, int gate_on) {
     if (!e) return VAD_ERR_INVALID_ARG;
+    if (is_g711(frame_fmt) && samples && nsamples >= 1) {
+        thread_local std::vector<int16_t> pcm;
+        pcm.resize((size_t)nsamples);
+        g711_to_i16(frame_fmt, static_cast<const uint8_t *>(samples), (size_t)nsamples, pcm.data());
+        return vad_tick_push(e, slot, pcm.data(), nsamples, VAD_FMT_I16_32768, gate_on);
+    }
     std::lock_guard<std::mutex> lk(e->tick_mu);
     if (!samples || nsamples < 1 || frame_fmt < VAD_FMT_F32 || frame_fmt > VAD_FMT_I16_32768)
         return e->fail(VAD_ERR_INVALID_ARG, "tick: null frame, empty frame or unknown format");
@@ -1782,7 +1852,7 @@ int vad_tick_push(vad_engine *e, int64_t slot, const void *samples, int32_t nsam
 int vad_tick_push_rate(vad_engine *e, int64_t slot, const void *samples, int32_t nsamples, int frame_fmt, int gate_on, int32_t sr_in) {
     if (!e) return VAD_ERR_INVALID_ARG;
     if (sr_in == e->sample_rate) return vad_tick_push(e, slot, samples, nsamples, frame_fmt, gate_on);
-    if (!samples || nsamples < 1 || frame_fmt < VAD_FMT_F32 || frame_fmt > VAD_FMT_I16_32768) {
+    if (!samples || nsamples < 1 || frame_fmt < VAD_FMT_F32 || frame_fmt > VAD_FMT_ALAW8) {
         std::lock_guard<std::mutex> lk(e->tick_mu);
         return e->fail(VAD_ERR_INVALID_ARG, "tick: null frame, empty frame or unknown format");
     }
@@ -1802,7 +1872,13 @@ int vad_tick_push_rate(vad_engine *e, int64_t slot, const void *samples, int32_t
     // staged as float32 (the resampler's input type): int16 wire frames are scaled here - before the lock - with numpy's true division
     thread_local std::vector<float> cvt;
     const float *src = static_cast<const float *>(samples);
-    if (frame_fmt != VAD_FMT_F32) {
+    if (is_g711(frame_fmt)) {
+        cvt.resize((size_t)nsamples);
+        const int16_t *t = g711_table(frame_fmt);
+        const uint8_t *q = static_cast<const uint8_t *>(samples);
+        for (int32_t k = 0; k < nsamples; ++k) cvt[(size_t)k] = (float)t[q[k]] / 32768.0f;
+        src = cvt.data();
+    } else if (frame_fmt != VAD_FMT_F32) {
         cvt.resize((size_t)nsamples);
         const float sc = frame_fmt == VAD_FMT_I16_32767 ? 32767.0f : 32768.0f;
         const int16_t *q = static_cast<const int16_t *>(samples);
@@ -1851,6 +1927,11 @@ int vad_tick_take_segment(vad_engine *e, int64_t slot, float *out, int64_t cap, 
 
 int vad_tick_push_many(vad_engine *e, const int64_t *slots, int64_t n, const void *frames, int32_t nsamples, int frame_fmt, int gate_on) {
     if (!e || n < 0 || (n > 0 && (!slots || !frames))) return VAD_ERR_INVALID_ARG;
+    if (is_g711(frame_fmt) && n > 0 && nsamples >= 1) {
+        std::vector<int16_t> pcm((size_t)n * (size_t)nsamples);
+        g711_to_i16(frame_fmt, static_cast<const uint8_t *>(frames), pcm.size(), pcm.data());
+        return vad_tick_push_many(e, slots, n, pcm.data(), nsamples, VAD_FMT_I16_32768, gate_on);
+    }
     std::lock_guard<std::mutex> lk(e->tick_mu);             // one lock for the batch
     if (n > 0 && (nsamples < 1 || frame_fmt < VAD_FMT_F32 || frame_fmt > VAD_FMT_I16_32768))
         return e->fail(VAD_ERR_INVALID_ARG, "tick: empty frame or unknown format");
@@ -1864,6 +1945,11 @@ int vad_tick_push_many(vad_engine *e, const int64_t *slots, int64_t n, const voi
 int vad_tick_push_status(vad_engine *e, const int64_t *slots, int64_t n, const void *frames, int32_t nsamples, int frame_fmt, int gate_on,
                          int32_t *status) {
     if (!e || n < 0 || (n > 0 && (!slots || !frames || !status))) return VAD_ERR_INVALID_ARG;
+    if (is_g711(frame_fmt) && n > 0 && nsamples >= 1) {
+        std::vector<int16_t> pcm((size_t)n * (size_t)nsamples);
+        g711_to_i16(frame_fmt, static_cast<const uint8_t *>(frames), pcm.size(), pcm.data());
+        return vad_tick_push_status(e, slots, n, pcm.data(), nsamples, VAD_FMT_I16_32768, gate_on, status);
+    }
     std::lock_guard<std::mutex> lk(e->tick_mu);
     if (n > 0 && (nsamples < 1 || frame_fmt < VAD_FMT_F32 || frame_fmt > VAD_FMT_I16_32768))
         return e->fail(VAD_ERR_INVALID_ARG, "tick: empty frame or unknown format");
@@ -1880,6 +1966,12 @@ int vad_tick_push_status(vad_engine *e, const int64_t *slots, int64_t n, const v
 int vad_tick_push_gather(vad_engine *e, const int64_t *slots, int64_t n, const void *const *frames, int32_t nsamples, int frame_fmt,
                          int gate_on, int32_t *status) {
     if (!e || n < 0 || (n > 0 && (!slots || !frames || !status))) return VAD_ERR_INVALID_ARG;
+    if (is_g711(frame_fmt) && n > 0 && nsamples >= 1) {
+        std::vector<int16_t> pcm;
+        std::vector<const void *> ptr;
+        g711_gather_decode(frame_fmt, frames, n, nsamples, pcm, ptr);
+        return vad_tick_push_gather(e, slots, n, ptr.data(), nsamples, VAD_FMT_I16_32768, gate_on, status);
+    }
     std::lock_guard<std::mutex> lk(e->tick_mu);
     if (n > 0 && (nsamples < 1 || frame_fmt < VAD_FMT_F32 || frame_fmt > VAD_FMT_I16_32768))
         return e->fail(VAD_ERR_INVALID_ARG, "tick: empty frame or unknown format");
@@ -1897,6 +1989,12 @@ int vad_tick_push_rate_gather(vad_engine *e, const int64_t *slots, int64_t n, co
                               int gate_on, int32_t sr_in, int32_t *status) {
     if (!e || n < 0 || (n > 0 && (!slots || !frames || !status))) return VAD_ERR_INVALID_ARG;
     if (sr_in == e->sample_rate) return vad_tick_push_gather(e, slots, n, frames, nsamples, frame_fmt, gate_on, status);
+    if (is_g711(frame_fmt) && n > 0 && nsamples >= 1) {     // decoded first, then scaled to float32 like a client's own PCM16
+        std::vector<int16_t> pcm;
+        std::vector<const void *> ptr;
+        g711_gather_decode(frame_fmt, frames, n, nsamples, pcm, ptr);
+        return vad_tick_push_rate_gather(e, slots, n, ptr.data(), nsamples, VAD_FMT_I16_32768, gate_on, sr_in, status);
+    }
     std::lock_guard<std::mutex> lk(e->tick_mu);             // one lock for the batch
     auto all = [&](int rc) {
         for (int64_t i = 0; i < n; ++i) status[i] = rc;

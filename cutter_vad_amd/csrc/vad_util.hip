@@ -62,3 +62,40 @@ extern "C" hipError_t vadk_launch_sm_replay(SmSlot *sm, int slot, const float *p
     hipLaunchKernelGGL(vadk_sm_replay, dim3(1), dim3(64), 0, stream, sm, slot, probs, n, events, seg);
     return hipGetLastError();
 }
+
+// ITU-T G.711 codes -> 16-bit linear PCM in front of the step kernels whose loaders do not decode them (engine.cpp: launch()):
+// 16 codes per thread in (four dwords: the caller's pointer is only promised 4-byte alignment), two 16-byte stores out (the
+// engine's own buffer).  nbytes is a multiple of 16 (whole frames of 256 / 512 codes).
+__device__ __forceinline__ uint32_t g711_pcm(uint32_t b, bool alaw) {
+    const uint32_t u = ~b & 0xFFu, tu = (((u & 0x0Fu) << 3) + 0x84u) << ((u & 0x70u) >> 4);
+    const int su = (u & 0x80u) ? 0x84 - (int)tu : (int)tu - 0x84;
+    const uint32_t a = b ^ 0x55u, seg = (a & 0x70u) >> 4, m = (a & 0x0Fu) << 4;
+    const int ta = (int)(seg == 0 ? m + 8u : (m + 0x108u) << (seg == 0 ? 0u : seg - 1u));
+    const int sa = (a & 0x80u) ? ta : -ta;
+    return (uint32_t)(alaw ? sa : su) & 0xFFFFu;
+}
+
+extern "C" __global__ void __launch_bounds__(256) vadk_g711_expand(const uint32_t *in, uint4 *out, int64_t n16, int alaw) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n16) return;
+    const bool al = alaw != 0;
+    uint32_t o[8];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t w = in[4 * i + k];
+        o[2 * k] = g711_pcm(w & 0xFFu, al) | (g711_pcm((w >> 8) & 0xFFu, al) << 16);
+        o[2 * k + 1] = g711_pcm((w >> 16) & 0xFFu, al) | (g711_pcm(w >> 24, al) << 16);
+    }
+    out[2 * i] = uint4{o[0], o[1], o[2], o[3]};
+    out[2 * i + 1] = uint4{o[4], o[5], o[6], o[7]};
+}
+
+extern "C" hipError_t vadk_launch_g711_expand(const void *d_in, int16_t *d_out, int64_t nbytes, int alaw, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (nbytes <= 0) return hipSuccess;
+    if ((nbytes & 15) || (reinterpret_cast<uintptr_t>(d_in) & 3)) return hipErrorInvalidValue;
+    const int64_t n16 = nbytes / 16;
+    hipLaunchKernelGGL(vadk_g711_expand, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, stream,
+                       static_cast<const uint32_t *>(d_in), reinterpret_cast<uint4 *>(d_out), n16, alaw);
+    return hipGetLastError();
+}

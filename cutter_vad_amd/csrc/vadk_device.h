@@ -2,6 +2,7 @@
 // fenced scheduling, buffer-descriptor weight loads, fast activation functions.  See vad_layout.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "vad_layout.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -234,6 +235,35 @@ __device__ __forceinline__ float i16_div(int s, float d, float r) {
     const float q = x * r;
     const float e = __builtin_fmaf(-q, d, x);
     return __builtin_fmaf(e, r, q);
+}
+
+// ITU-T G.711 in a loader: the four codes of one dword -> decode(code) / 32768 as float32, exactly (every code decodes to an
+// int16, and s / 32768 is exact), branch-free, without building the integer: a code IS a small float - sign, 3 exponent bits, 4
+// mantissa bits - so its 7 low bits, shifted to bits 19..25, land on a float32's exponent and mantissa fields.
+//   mu-law (u = ~b): |s| + 132 = (2 m + 33) << (e + 2) = 1.mmmm1b x 2^(e + 7): fields e | mmmm1 under the exponent base 112 give
+//     (|s| + 132) / 2^22; minus 132 / 2^22, times +-128 (the sign from bit 7, u & 0x80 = negative).  The product goes through an
+//     fma with +0.0f: both zero codes (0x7F, 0xFF) give +0.0f, as (float)(short)0 does on the int16 path, never -0.0f.
+//   A-law (a = b ^ 0x55): |s| = (2 m + 1) << 3 for e = 0, (2 m + 33) << (e + 2) above: fields e | mmmm1 under the exponent base
+//     0 are that very number x 2^-134, the e = 0 codes as float32 denormals (the kernels run with float32 denormals on - the
+//     compiler's default for gfx9, .amdhsa_float_denorm_mode_32 3); times +-2^119 (a & 0x80 = positive).  No zero code.
+// About 6 (mu-law) / 5 (A-law) VALU instructions per sample; tests/test_gpu_g711.py feeds all 256 codes of both laws.
+template <bool ALAW>
+__device__ __forceinline__ f32x4 g711_quad(uint32_t b) {
+    const uint32_t w = b ^ (ALAW ? 0xD5D5D5D5u : 0xFFFFFFFFu);      // low 7 bits: the fields; bit 7 set = negative, for both laws
+    auto one = [&](auto kc) -> float {
+        constexpr int k = decltype(kc)::value;
+        uint32_t x;                                                 // byte k's fields at bits 19..25
+        if constexpr (k < 3) x = w << (19 - 8 * k);
+        else x = w >> 5;
+        const uint32_t sx = w << (24 - 8 * k);                      // byte k's sign at bit 31
+        const uint32_t fb = (x & (0x7Fu << 19)) | (ALAW ? 1u << 18 : (112u << 23) | (1u << 18));
+        const float f = __builtin_bit_cast(float, fb);
+        const float sg = __builtin_bit_cast(float, (sx & 0x80000000u) | (ALAW ? 0x7B000000u : 0x43000000u));   // +-2^119 | +-128
+        if constexpr (ALAW) return f * sg;
+        else return __builtin_fmaf(sg, f - 0x1.08p-15f, 0.0f);      // 132 / 2^22
+    };
+    return f32x4{one(std::integral_constant<int, 0>{}), one(std::integral_constant<int, 1>{}),
+                 one(std::integral_constant<int, 2>{}), one(std::integral_constant<int, 3>{})};
 }
 
 __device__ __forceinline__ f32x4 gate4(f32x4 v, float thr) {

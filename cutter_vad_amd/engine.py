@@ -24,6 +24,18 @@ TICK_RATES = (8000, 24000, 48000)     # tick groups 6.. : 6 + 3 * gate_on + inde
 TICK_RATE_CHUNK = (256, 768, 1536)    # samples of such a chunk = one 16 kHz frame's worth
 
 
+def _law_format(law: Optional[str], frames=None) -> Optional[int]:
+    """``law`` = None: no G.711 (-> None).  "ulaw" / "alaw": the frame format for ITU-T G.711 codes, one byte per sample;
+    ``frames`` (an array) must then be uint8.  Without ``law`` a uint8 array keeps its old meaning (numbers, converted to float32)."""
+    if law is None:
+        return None
+    if law not in _ffi.G711_LAWS:
+        raise AudioProcessingError(f"Model prediction failed: unknown G.711 law {law!r} (expected 'ulaw' or 'alaw')")
+    if frames is not None and not isinstance(frames, (bytes, bytearray, memoryview)) and np.asarray(frames).dtype != np.uint8:
+        raise AudioProcessingError(f"Model prediction failed: G.711 frames must be uint8 codes, got {np.asarray(frames).dtype}")
+    return _ffi.G711_LAWS[law]
+
+
 def _ptr(a: np.ndarray, ty):
     return a.ctypes.data_as(C.POINTER(ty))
 
@@ -180,21 +192,24 @@ class Engine:
         return ev, seg
 
     # ------------------------------------------------------------------ hot path
-    def _prep(self, slots, frames, T: Optional[int]) -> Tuple[np.ndarray, np.ndarray, int]:
+    def _prep(self, slots, frames, T: Optional[int], law: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray, int]:
         s = np.ascontiguousarray(slots, dtype=np.int64).reshape(-1)
         f = np.asarray(frames)
-        if f.dtype not in _FMT:
+        g711 = _law_format(law, f)
+        if g711 is None and f.dtype not in _FMT:
             f = f.astype(np.float32)
         f = np.ascontiguousarray(f)
         want = (s.size, self.frame_samples) if T is None else (s.size, T, self.frame_samples)
         if f.shape != want:
             raise AudioProcessingError(f"Model prediction failed: frames have shape {f.shape}, expected {want}")
-        return s, f, _FMT[f.dtype]
+        return s, f, (_FMT[f.dtype] if g711 is None else g711)
 
-    def step(self, slots, frames, denoise: Optional[float] = 0.01, i16_scale: int = 32767) -> np.ndarray:
-        """One 512-sample frame per listed stream -> probabilities [n] (NaN for a rejected non-finite frame)."""
-        s, f, fmt = self._prep(slots, frames, None)
-        if fmt != _ffi.VAD_FMT_F32 and i16_scale == 32768:
+    def step(self, slots, frames, denoise: Optional[float] = 0.01, i16_scale: int = 32767, law: Optional[str] = None) -> np.ndarray:
+        """One 512-sample frame per listed stream -> probabilities [n] (NaN for a rejected non-finite frame).
+        ``law`` = "ulaw" / "alaw": ``frames`` are uint8 ITU-T G.711 codes, decoded on the GPU (``VAD_FMT_ULAW8 / ALAW8``); the
+        results equal those of the decoded int16 samples with ``i16_scale=32768``.  The same on every entry point that takes it."""
+        s, f, fmt = self._prep(slots, frames, None, law)
+        if fmt == _ffi.VAD_FMT_I16_32767 and i16_scale == 32768:
             fmt = _ffi.VAD_FMT_I16_32768
         probs = np.empty(s.size, np.float32)
         thr = -1.0 if denoise is None else float(denoise)
@@ -202,11 +217,11 @@ class Engine:
                                        _ptr(probs, C.c_float)))
         return probs
 
-    def step_events(self, slots, frames, denoise: Optional[float] = 0.01, i16_scale: int = 32767):
+    def step_events(self, slots, frames, denoise: Optional[float] = 0.01, i16_scale: int = 32767, law: Optional[str] = None):
         """-> (probs [n], event bits [n] uint8, finished-segment frames [n] int32); a rejected non-finite frame: NaN,
         ``VAD_EV_REJECTED``, 0."""
-        s, f, fmt = self._prep(slots, frames, None)
-        if fmt != _ffi.VAD_FMT_F32 and i16_scale == 32768:
+        s, f, fmt = self._prep(slots, frames, None, law)
+        if fmt == _ffi.VAD_FMT_I16_32767 and i16_scale == 32768:
             fmt = _ffi.VAD_FMT_I16_32768
         probs = np.empty(s.size, np.float32)
         ev = np.zeros(s.size, np.uint8)
@@ -216,15 +231,15 @@ class Engine:
                                               thr, _ptr(probs, C.c_float), _ptr(ev, C.c_uint8), _ptr(seg, C.c_int32)))
         return probs, ev, seg
 
-    def step_multi(self, slots, frames, denoise: Optional[float] = 0.01, i16_scale: int = 32767):
+    def step_multi(self, slots, frames, denoise: Optional[float] = 0.01, i16_scale: int = 32767, law: Optional[str] = None):
         """frames [n, T, 512]: T consecutive frames per stream -> (probs [n,T], events [n,T]).  A rejected non-finite frame
         (NaN, ``VAD_EV_REJECTED``) is skipped: the stream's next frame continues from the state before it."""
         f0 = np.asarray(frames)
         if f0.ndim != 3:
             raise AudioProcessingError(f"Model prediction failed: frames must be [n, T, 512], got {f0.shape}")
         T = int(f0.shape[1])
-        s, f, fmt = self._prep(slots, f0, T)
-        if fmt != _ffi.VAD_FMT_F32 and i16_scale == 32768:
+        s, f, fmt = self._prep(slots, f0, T, law)
+        if fmt == _ffi.VAD_FMT_I16_32767 and i16_scale == 32768:
             fmt = _ffi.VAD_FMT_I16_32768
         probs = np.empty((s.size, T), np.float32)
         ev = np.zeros((s.size, T), np.uint8)
@@ -248,13 +263,18 @@ class Engine:
                                                     d_events or None, d_seg or None, stream or None))
 
     # ------------------------------------------------------------------ tick assembler (shared-pool serving)
-    def tick_push(self, slot: int, frame, gate_on: bool = True, i16_scale: int = 32767, sample_rate: Optional[int] = None) -> None:
+    def tick_push(self, slot: int, frame, gate_on: bool = True, i16_scale: int = 32767, sample_rate: Optional[int] = None,
+                  law: Optional[str] = None) -> None:
         """Queue one frame for ``slot`` (``vad_tick_push``): ``bytes`` = little-endian int16 PCM as it came off the wire,
         or a float32 array.  Written straight into the coming tick's page-locked staging; padded / truncated to the
         model's frame length.  ``sample_rate`` other than the engine's (8000 / 24000 / 48000 on a 16 kHz engine): the chunk
         that yields one frame, resampled on the GPU inside the tick (``vad_tick_push_rate``)."""
         i16_fmt = _ffi.VAD_FMT_I16_32768 if i16_scale == 32768 else _ffi.VAD_FMT_I16_32767
-        if isinstance(frame, (bytes, bytearray, memoryview)):
+        g711 = _law_format(law, frame)
+        if g711 is not None:                          # G.711 codes (bytes or uint8): decoded on push, staged as int16 / 32768
+            buf = frame if isinstance(frame, bytes) else np.ascontiguousarray(frame).tobytes() if isinstance(frame, np.ndarray) else bytes(frame)
+            count, fmt = len(buf), g711
+        elif isinstance(frame, (bytes, bytearray, memoryview)):
             buf, count, fmt = bytes(frame), len(frame) // 2, i16_fmt
         else:
             f = np.ascontiguousarray(frame)
@@ -268,11 +288,14 @@ class Engine:
         else:
             self._check(self._lib.vad_tick_push_rate(self._h, int(slot), buf, count, fmt, int(gate_on), int(sample_rate)))
 
-    def tick_push_many(self, slots, frames, gate_on: bool = True, i16_scale: int = 32767) -> None:
-        """frames [n, L] (float32 or int16), one per listed slot (``vad_tick_push_many``)."""
+    def tick_push_many(self, slots, frames, gate_on: bool = True, i16_scale: int = 32767, law: Optional[str] = None) -> None:
+        """frames [n, L] (float32 or int16; uint8 G.711 codes with ``law``), one per listed slot (``vad_tick_push_many``)."""
         s = np.ascontiguousarray(slots, dtype=np.int64).reshape(-1)
         f = np.ascontiguousarray(frames)
-        if f.dtype == np.int16:
+        g711 = _law_format(law, f)
+        if g711 is not None:
+            fmt = g711
+        elif f.dtype == np.int16:
             fmt = _ffi.VAD_FMT_I16_32768 if i16_scale == 32768 else _ffi.VAD_FMT_I16_32767
         else:
             f = np.ascontiguousarray(f, np.float32)
@@ -293,11 +316,18 @@ class Engine:
         self._check(self._lib.vad_tick_take_segment(self._h, int(slot), _ptr(out, C.c_float), out.size, C.byref(n)), VADError)
         return out
 
-    def tick_push_status(self, slots, frames, nsamples: int, gate_on: bool = True, i16_scale: int = 32767) -> np.ndarray:
+    def tick_push_status(self, slots, frames, nsamples: int, gate_on: bool = True, i16_scale: int = 32767,
+                         law: Optional[str] = None) -> np.ndarray:
         """``frames``: int16 / float32 array [n, nsamples] or the same as one bytes object of int16 PCM; every frame is tried,
         -> int32 status per frame (``vad_tick_push_status``; 0 = queued)."""
         s = np.ascontiguousarray(slots, dtype=np.int64).reshape(-1)
-        if isinstance(frames, (bytes, bytearray, memoryview)):
+        g711 = _law_format(law, frames)
+        if g711 is not None:                          # G.711 codes: bytes or a uint8 array, nsamples bytes per frame
+            f = np.ascontiguousarray(np.frombuffer(frames, np.uint8) if isinstance(frames, (bytes, bytearray, memoryview)) else frames)
+            if f.size != int(nsamples) * s.size:
+                raise AudioProcessingError(f"Model prediction failed: {f.size} bytes for {s.size} G.711 frames of {nsamples} samples")
+            buf, ptr, fmt = f, f.ctypes.data_as(C.c_void_p), g711
+        elif isinstance(frames, (bytes, bytearray, memoryview)):
             buf, fmt = frames, (_ffi.VAD_FMT_I16_32768 if i16_scale == 32768 else _ffi.VAD_FMT_I16_32767)
             if len(frames) != 2 * int(nsamples) * s.size:
                 raise AudioProcessingError(f"Model prediction failed: {len(frames)} bytes for {s.size} int16 frames of {nsamples} samples")
@@ -316,7 +346,8 @@ class Engine:
         del buf
         return status
 
-    def tick_push_gather(self, slots, frames, nsamples: int, gate_on: bool = True, i16_scale: int = 32767) -> np.ndarray:
+    def tick_push_gather(self, slots, frames, nsamples: int, gate_on: bool = True, i16_scale: int = 32767,
+                         law: Optional[str] = None) -> np.ndarray:
         """``frames``: a sequence of ``bytes`` objects (int16 PCM, ``nsamples`` samples each), one per listed slot; they are
         copied from where they are into the tick's staging (``vad_tick_push_gather``) -> int32 status per frame."""
         s = np.ascontiguousarray(slots, dtype=np.int64).reshape(-1)
@@ -326,22 +357,26 @@ class Engine:
         ptrs = (C.c_char_p * n)(*frames)               # borrows the bytes objects' buffers: `frames` stays alive through the call
         status = np.zeros(n, np.int32)
         fmt = _ffi.VAD_FMT_I16_32768 if i16_scale == 32768 else _ffi.VAD_FMT_I16_32767
+        fmt = _law_format(law) or fmt                  # G.711: ``frames`` hold nsamples one-byte codes each
         self._lib.vad_tick_push_gather(self._h, _ptr(s, C.c_int64), n, ptrs, int(nsamples), fmt, int(gate_on), _ptr(status, C.c_int32))
         return status
 
-    def tick_push_rate_gather(self, slots, frames, sample_rate: int, gate_on: bool = True, i16_scale: int = 32767) -> np.ndarray:
+    def tick_push_rate_gather(self, slots, frames, sample_rate: int, gate_on: bool = True, i16_scale: int = 32767,
+                              law: Optional[str] = None) -> np.ndarray:
         """``frames``: a sequence of ``bytes`` objects, one int16 chunk of ``512 * sample_rate / 16000`` samples per listed slot, all
         at ONE input rate (``vad_tick_push_rate_gather``) -> int32 status per chunk."""
         s = np.ascontiguousarray(slots, dtype=np.int64).reshape(-1)
         n = s.size
         if len(frames) != n:
             raise AudioProcessingError(f"Model prediction failed: {len(frames)} frames for {n} slots")
-        nsamples = len(frames[0]) // 2 if n else 0
-        if any(len(f) != 2 * nsamples for f in frames):
+        g711 = _law_format(law)
+        width = 1 if g711 is not None else 2           # bytes per sample on the wire
+        nsamples = len(frames[0]) // width if n else 0
+        if any(len(f) != width * nsamples for f in frames):
             raise AudioProcessingError("Model prediction failed: chunks of one call must have one length")
         ptrs = (C.c_char_p * n)(*frames)
         status = np.zeros(n, np.int32)
-        fmt = _ffi.VAD_FMT_I16_32768 if i16_scale == 32768 else _ffi.VAD_FMT_I16_32767
+        fmt = g711 or (_ffi.VAD_FMT_I16_32768 if i16_scale == 32768 else _ffi.VAD_FMT_I16_32767)
         self._lib.vad_tick_push_rate_gather(self._h, _ptr(s, C.c_int64), n, ptrs, int(nsamples), fmt, int(gate_on), int(sample_rate),
                                             _ptr(status, C.c_int32))
         return status
@@ -473,14 +508,14 @@ class Engine:
         return bytes(buf)
 
     # ------------------------------------------------------------------ pipelined host ingest
-    def submit(self, slots, frames, denoise: Optional[float] = 0.01, i16_scale: int = 32767) -> int:
+    def submit(self, slots, frames, denoise: Optional[float] = 0.01, i16_scale: int = 32767, law: Optional[str] = None) -> int:
         """Enqueue copy-in -> step -> copy-out for ``frames`` [n, frame] or [n, T, frame] and return a ticket
         (``vad_step_submit``).  ``slots`` / ``frames`` must stay alive and unchanged until ``collect(ticket)``; frames in a
         ``pinned_array`` are DMA'd asynchronously, so the copy of this ticket overlaps the kernel of the previous one."""
         f0 = np.asarray(frames)
         T = int(f0.shape[1]) if f0.ndim == 3 else 1
-        s, f, fmt = self._prep(slots, f0, T if f0.ndim == 3 else None)
-        if fmt != _ffi.VAD_FMT_F32 and i16_scale == 32768:
+        s, f, fmt = self._prep(slots, f0, T if f0.ndim == 3 else None, law)
+        if fmt == _ffi.VAD_FMT_I16_32767 and i16_scale == 32768:
             fmt = _ffi.VAD_FMT_I16_32768
         thr = -1.0 if denoise is None else float(denoise)
         t = C.c_int64()

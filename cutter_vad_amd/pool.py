@@ -139,9 +139,12 @@ class StreamBatch:
             self.engine.close_stream(int(s))
             self.slots.remove(int(s))
 
-    def step(self, frames: np.ndarray, slots: Optional[Sequence[int]] = None):
+    def step(self, frames: np.ndarray, slots: Optional[Sequence[int]] = None, law: Optional[str] = None):
+        """``law`` = "ulaw" / "alaw": ``frames`` are uint8 ITU-T G.711 codes (``Engine.step``)."""
         s = np.asarray(self.slots if slots is None else slots, dtype=np.int64)
         thr = 0.01 if self.config.enable_denoising else None
+        if law is not None:
+            return self.engine.step_events(s, frames, denoise=thr, law=law)
         return self.engine.step_events(s, frames, denoise=thr)
 
     def step_rates(self, segments, slots: Optional[Sequence[int]] = None):

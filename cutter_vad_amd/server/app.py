@@ -12,7 +12,8 @@ TIMEOUT) (:83-124).
 What differs from the reference is only where the model runs: the socket's receive loop just queues the frame
 on its :class:`PooledSession`; one ticker task steps ALL sessions per tick with a single launch and posts the
 events back to each socket.  Opus / AAC need PyAV, which this image does not have: those modes are refused with
-the reference's own message (:645-655).
+the reference's own message (:645-655).  Beyond the reference: ``mode=ulaw`` / ``mode=alaw`` take ITU-T G.711 frames (one byte per
+sample, ``sample_width`` 1 implied), decoded to PCM16 on arrival - the client gets what ``mode=pcm&sample_width=2`` gives for the decoded audio.
 """
 
 from __future__ import annotations
@@ -58,6 +59,12 @@ def parse_query_params(query_string: str) -> Dict[str, Any]:
     return out
 
 
+# ITU-T G.711 on the wire (RTP PCMU / PCMA: what an 8 kHz telephony leg carries): one byte per sample.  No reference counterpart
+# (its modes are pcm / opus / aac, vad_websocket_server.py:551-611); a frame is decoded to PCM16 and takes the pcm path from there.
+G711_MODES = ("ulaw", "alaw")
+_FRAMED_MODES = ("pcm",) + G711_MODES            # modes whose binary messages are frames of a fixed byte count
+
+
 def default_client_config() -> Dict[str, Any]:
     return {"audio": {"mode": "pcm", "sample_rate": 16000, "channels": 1, "sample_width": 2, "frame_duration_ms": 30},
             "vad": {"start_probability": 0.4, "end_probability": 0.3, "start_frame_count": 6, "end_frame_count": 12,
@@ -68,7 +75,12 @@ def default_client_config() -> Dict[str, Any]:
 def create_client_config(query_params: Dict[str, Any], config_message: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     """Defaults <- query parameters <- CONFIG message (:551-611)."""
     cfg = default_client_config()
-    for layer in (query_params, {k: v for k, v in (config_message or {}).items() if v is not None}):
+    layers = (query_params, {k: v for k, v in (config_message or {}).items() if v is not None})
+    if not any("sample_width" in layer for layer in layers):
+        mode = [layer["mode"] for layer in layers if "mode" in layer]
+        if mode and str(mode[-1]) in G711_MODES:
+            cfg["audio"]["sample_width"] = 1          # the pcm default (2) does not apply to one-byte codes
+    for layer in layers:
         for k, v in layer.items():
             if k in _AUDIO_KEYS:
                 cfg["audio"][k] = v
@@ -165,7 +177,7 @@ class ClientSession:
         self.voice_start_time: Optional[float] = None
         self.last_voice_time: Optional[float] = None
         self.timeout_task: Optional[asyncio.Task] = None
-        self.expected_frame_bytes = int(frame_bytes(cfg)) if cfg["audio"]["mode"] == "pcm" else 0
+        self.expected_frame_bytes = int(frame_bytes(cfg)) if cfg["audio"]["mode"] in _FRAMED_MODES else 0
         self.outbox: "asyncio.Queue[Optional[str]]" = asyncio.Queue()
         self.session: Optional[PooledSession] = None
         self.session_error: Optional[str] = None
@@ -240,15 +252,19 @@ class ClientSession:
     # -- audio (:326-380)
     def process_audio_frame(self, data: bytes) -> None:
         a = self.cfg["audio"]
-        if a["mode"] != "pcm":
+        if a["mode"] not in _FRAMED_MODES:
             self.send_error(f"No decoder available for {a['mode']}")
+            return
+        g711 = a["mode"] in G711_MODES
+        if g711 and a["sample_width"] != 1:
+            self.send_error(f"Unsupported sample width: {a['sample_width']}")
             return
         if len(data) != self.expected_frame_bytes:
             self.send_error(f"Invalid frame size: expected {self.expected_frame_bytes}, got {len(data)}")
             return
         x = None
-        if a["sample_width"] == 2:
-            pass          # int16 little-endian: the bytes travel to the GPU as they are, scaled by 1/32767 in the kernel
+        if g711 or a["sample_width"] == 2:
+            pass          # G.711 codes (decoded to int16 on submit) | int16 little-endian: the bytes travel to the GPU as they are, scaled by 1/32767 in the kernel
         elif a["sample_width"] == 4:
             x = np.frombuffer(data, dtype=np.float32)
         else:
@@ -258,7 +274,9 @@ class ClientSession:
             # multi-channel frames go to the model interleaved, as the reference hands them over (:369)
             if self.session_error is not None or self.session is None:
                 raise RuntimeError(self.session_error or "VAD wrapper not initialized")
-            if x is None:
+            if g711:
+                self.session.submit_g711(data, a["mode"])
+            elif x is None:
                 self.session.submit_pcm16(data)
             else:
                 self.session.submit(x)
@@ -295,7 +313,7 @@ class ClientSession:
     def update_config(self, cfg: Dict[str, Any]) -> None:
         old, self.cfg = self.cfg, cfg
         if old["audio"] != cfg["audio"]:
-            self.expected_frame_bytes = int(frame_bytes(cfg)) if cfg["audio"]["mode"] == "pcm" else 0
+            self.expected_frame_bytes = int(frame_bytes(cfg)) if cfg["audio"]["mode"] in _FRAMED_MODES else 0
         if old["vad"] != cfg["vad"] or old["audio"]["sample_rate"] != cfg["audio"]["sample_rate"] \
                 or old["audio"]["frame_duration_ms"] != cfg["audio"]["frame_duration_ms"]:
             self._open(cfg)
@@ -402,7 +420,7 @@ def create_app(pool: Optional[SharedStreamPool] = None, tick_interval: float = 0
                 await refuse(websocket, f"Invalid configuration: {e}")
                 return
             mode = cfg["audio"]["mode"]
-            if mode not in ("pcm", "opus", "aac"):
+            if mode not in ("pcm", "opus", "aac") + G711_MODES:
                 await refuse(websocket, f"Unsupported audio mode: {mode}")
                 return
             if mode in ("opus", "aac"):

@@ -50,6 +50,7 @@ from ..core.silero_model import SileroVADModel
 from ..engine import TICK_RATES
 from ..pool import EnginePool, default_pool, resolve_model_path
 from ..utils.audio import AudioUtils
+from ..utils.g711 import g711_decode
 from ..utils.wav_writer import WAVWriter
 
 def _load_wirebox():
@@ -138,6 +139,12 @@ class PooledSession:
     def _submit_pcm16_general(self, data: bytes) -> None:
         while self.pool.submit_pcm16(self, data) is _RETRY:
             pass
+
+    def submit_g711(self, data: bytes, law: str) -> None:
+        """One wire frame of ITU-T G.711 codes (``law`` = "ulaw" | "alaw", one byte per sample: RTP PCMU / PCMA): decoded with the
+        engine library's table and handed to ``submit_pcm16`` - inbox, back-pressure, migration and the int16 convention are those
+        of a client that decoded to PCM16 itself."""
+        self.submit_pcm16(g711_decode(data, law).tobytes())
 
     def is_voice_active(self) -> bool:
         return self.active

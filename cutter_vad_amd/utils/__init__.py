@@ -1,0 +1,1 @@
+from .g711 import g711_decode  # noqa: F401

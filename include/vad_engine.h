@@ -61,8 +61,20 @@ typedef enum vad_status {
 typedef enum vad_frame_format {
     VAD_FMT_F32 = 0,            /* float32 in [-1,1]: what VADWrapper.process_audio_data hands down (vad_wrapper.py:598) */
     VAD_FMT_I16_32767 = 1,      /* int16 PCM scaled by 1/32767 (websocket server convention, vad_websocket_server.py:341) */
-    VAD_FMT_I16_32768 = 2       /* int16 PCM scaled by 1/32768 (AudioUtils.pcm_to_float32, utils/audio.py:308) */
+    VAD_FMT_I16_32768 = 2,      /* int16 PCM scaled by 1/32768 (AudioUtils.pcm_to_float32, utils/audio.py:308) */
+    VAD_FMT_ULAW8 = 3,          /* ITU-T G.711 mu-law (RTP PCMU), 1 byte per sample, value = decode(b) / 32768 */
+    VAD_FMT_ALAW8 = 4           /* ITU-T G.711 A-law  (RTP PCMA), 1 byte per sample, value = decode(b) / 32768 */
 } vad_frame_format;
+/* G.711 frames (the wire format of 8 kHz telephony; no reference counterpart - its server takes PCM16 / float32 only,
+ * vad_websocket_server.py:326-382): a frame row is frame_samples BYTES.  Every entry point that takes a frame_fmt accepts the two
+ * formats, and gives bit for bit what it gives for the decoded int16 samples under VAD_FMT_I16_32768 (every code decodes to an
+ * int16, and s / 32768 is exact in float32).  Silero V5's 16-stream kernel decodes in its loader; the other kernels are fed
+ * through a small expansion kernel into engine-owned HBM, so the link carries one byte per sample either way.  Device pointers
+ * to G.711 frames must be 4-byte aligned (the loader reads four samples as one dword).  The tick assembler decodes on push:
+ * G.711 frames join the VAD_FMT_I16_32768 groups (4 / 5) of vad_tick_result, as 16-bit PCM.  The presence of vad_g711_decode is
+ * how a caller detects the feature (VAD_ABI_VERSION is unchanged: nothing existing moved).
+ * vad_g711_decode: the decoder itself, on the host: in [n] codes -> out [n] int16; VAD_ERR_INVALID_ARG for any other format. */
+VAD_API int vad_g711_decode(int frame_fmt, const uint8_t *in, int64_t n, int16_t *out);
 
 /* event bits produced by the per-stream hysteresis state machine (core/silero_model.py:790-949) */
 enum { VAD_EV_START = 1, VAD_EV_END = 2, VAD_EV_CONTINUE = 4 };

@@ -339,6 +339,76 @@ def int16_ingest():
     return out
 
 
+def g711_ingest():
+    """ITU-T G.711 frames (VAD_FMT_ULAW8 / VAD_FMT_ALAW8, one byte per sample) beside int16 and float32, Silero V5 16 kHz and 8 kHz:
+    (1) vad_step on 8 192 streams from pageable and page-locked host memory (H2D + kernel + D2H + sync per step), (2) the
+    pipelined submit / collect rate from page-locked memory, (3) the kernel alone on device-resident frames, 8 192 and 1 024
+    streams (HIP events; VAD_BENCH_K=700 gives the 2 100 steps DESIGN 2.1c quotes).  The codes are uniform random bytes: the
+    kernel's time does not depend on the values.  Every figure is the median of three repetitions, all three reported."""
+    import time
+    import numpy as np
+    from cutter_vad_amd import _ffi
+    B = 8192
+    out = []
+    for rate, fs in ((16000, 512), (8000, 256)):
+        eng = Engine(open(weights_io.packaged_blob_path(5, rate), "rb").read(), model_version=5, max_streams=B, sample_rate=rate)
+        slots = eng.open_streams(B)
+        has_g711 = hasattr(_ffi, "VAD_FMT_ULAW8")             # the same entry runs on a checkout without the formats
+        rng = np.random.default_rng(0)
+        x32 = (0.1 * rng.standard_normal((4, B, fs))).astype(np.float32)
+        x16 = np.clip(x32 * 32767.0, -32768, 32767).astype(np.int16)
+        xu8 = rng.integers(0, 256, (4, B, fs), dtype=np.uint8)
+        forms = [("f32", x32, {}), ("int16", x16, {})] + ([("ulaw", xu8, {"law": "ulaw"})] if has_g711 else [])
+        for name, x, kw in forms:
+            pin = eng.pinned_array(x.shape, x.dtype)
+            pin[:] = x
+            for where, buf in (("pageable", x), ("page-locked", pin)):
+                for i in range(5):
+                    eng.step(slots, buf[i % 4], **kw)
+                reps = []
+                for _ in range(3):                          # three repetitions: their spread is the run-to-run figure
+                    t0 = time.perf_counter()
+                    for i in range(40):
+                        eng.step(slots, buf[i % 4], **kw)
+                    reps.append((time.perf_counter() - t0) / 40)
+                out.append({"config": f"g711_ingest: V5 {rate} Hz, batch={B}, vad_step from {where} host memory, {name} frames",
+                            "us_per_step": float(np.median(reps)) * 1e6, "us_per_step_runs": [r * 1e6 for r in reps],
+                            "bytes_per_step": int(x[0].nbytes)})
+            t = [eng.submit(slots, pin[0], **kw)]
+            for i in range(1, 10):
+                t.append(eng.submit(slots, pin[i % 4], **kw))
+                eng.collect(t.pop(0))
+            reps = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                for i in range(100):
+                    t.append(eng.submit(slots, pin[i % 4], **kw))
+                    eng.collect(t.pop(0))
+                reps.append((time.perf_counter() - t0) / 100)
+            eng.collect(t.pop(0))
+            out.append({"config": f"g711_ingest: V5 {rate} Hz, batch={B}, pipelined submit / collect from page-locked memory, {name} frames",
+                        "us_per_step": float(np.median(reps)) * 1e6, "us_per_step_runs": [r * 1e6 for r in reps],
+                        "frames_per_s": B / float(np.median(reps))})
+        # the kernel alone: device-resident frames
+        i16 = torch.from_numpy(x16).cuda()
+        u8 = torch.from_numpy(xu8).cuda()
+        probs = torch.empty(B, device="cuda")
+        ts = torch.cuda.Stream()
+        dev = [("int16", i16, _ffi.VAD_FMT_I16_32768)]
+        if has_g711:
+            dev += [("ulaw", u8, _ffi.VAD_FMT_ULAW8), ("alaw", u8, _ffi.VAD_FMT_ALAW8)]
+        for n in (B, 1024):
+            row = {"config": f"g711_ingest: V5 {rate} Hz, batch={n}, device-resident frames, kernel time (HIP events, {3 * K} steps)"}
+            for name, ring, fmt in dev:
+                reps = [timed(lambda i: eng.step_device(n, ring[i % 4].data_ptr(), probs.data_ptr(), fmt=fmt, stream=ts.cuda_stream), [ts])
+                        for _ in range(3)]
+                row[f"us_per_step_{name}"] = float(np.median(reps)) * 1e6
+                row[f"us_per_step_{name}_runs"] = [r * 1e6 for r in reps]
+            out.append(row)
+        eng.close()
+    return out
+
+
 def single_stream_wrapper():
     """configs[0]: ONE stream through the drop-in VADWrapper (host framing + one launch + sync + callbacks per chunk)."""
     import time

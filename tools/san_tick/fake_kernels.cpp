@@ -21,8 +21,22 @@ hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipSt
 
 using namespace vadk;
 
+// ITU-T G.711 code -> 16-bit linear PCM (include/vad_engine.h has the two formulas)
+static int16_t g711_pcm(uint8_t b, bool alaw) {
+    if (!alaw) {
+        const int u = ~b & 0xFF, t = (((u & 0x0F) << 3) + 0x84) << ((u & 0x70) >> 4);
+        return (int16_t)((u & 0x80) ? 0x84 - t : t - 0x84);
+    }
+    const int a = b ^ 0x55, seg = (a & 0x70) >> 4;
+    int t = (a & 0x0F) << 4;
+    t = seg == 0 ? t + 8 : seg == 1 ? t + 0x108 : (t + 0x108) << (seg - 1);
+    return (int16_t)((a & 0x80) ? t : -t);
+}
+
 static float first_sample(const void *frames, size_t index, int fmt, int frame_samples) {
     if (fmt == VAD_FMT_F32) return static_cast<const float *>(frames)[index * (size_t)frame_samples];
+    if (fmt == VAD_FMT_ULAW8 || fmt == VAD_FMT_ALAW8)
+        return (float)g711_pcm(static_cast<const uint8_t *>(frames)[index * (size_t)frame_samples], fmt == VAD_FMT_ALAW8) / 32768.0f;
     const int16_t q = static_cast<const int16_t *>(frames)[index * (size_t)frame_samples];
     return (float)q / (fmt == VAD_FMT_I16_32767 ? 32767.0f : 32768.0f);
 }
@@ -89,6 +103,11 @@ extern "C" hipError_t vadk_launch_resample(const ResampleParams *p, hipStream_t)
             std::memset(o, 0, 512 * sizeof(float));
             o[0] = p->seg[k].in[(size_t)i * p->seg[k].n_in];
         }
+    return hipSuccess;
+}
+
+extern "C" hipError_t vadk_launch_g711_expand(const void *d_in, int16_t *d_out, int64_t nbytes, int alaw, hipStream_t) {
+    for (int64_t i = 0; i < nbytes; ++i) d_out[i] = g711_pcm(static_cast<const uint8_t *>(d_in)[i], alaw != 0);
     return hipSuccess;
 }
 
