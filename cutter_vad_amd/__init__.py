@@ -15,6 +15,7 @@ from .core.vad_wrapper import VADWrapper
 from .core.async_vad_wrapper import AsyncVADWrapper
 from .engine import Engine
 from .pool import EnginePool, StreamBatch, default_pool
+from .scan import scan_recordings, speech_segments
 from .utils.audio import AudioUtils
 from .utils.wav_writer import WAVWriter
 
@@ -22,4 +23,5 @@ __version__ = "0.1.0"
 
 __all__ = ["VADWrapper", "AsyncVADWrapper", "VADConfig", "SampleRate", "SileroModelVersion", "VADError", "ModelNotFoundError",
            "ConfigurationError", "AudioProcessingError", "ModelInitializationError", "CallbackError", "AudioUtils",
-           "WAVWriter", "Engine", "EnginePool", "StreamBatch", "default_pool"]
+           "WAVWriter", "Engine", "EnginePool", "StreamBatch", "default_pool", "scan_recordings",
+           "speech_segments"]

@@ -112,6 +112,10 @@ class TickWork(C.Structure):
     ]
 
 
+class ScanItem(C.Structure):
+    _fields_ = [("slot", C.c_int64), ("sample_offset", C.c_int64), ("nsamples", C.c_int64)]
+
+
 VAD_WORK_START, VAD_WORK_END, VAD_WORK_CONTINUE, VAD_WORK_PAYLOAD, VAD_WORK_LONG = 1, 2, 4, 8, 16
 VAD_WORK_REJECTED = 32
 
@@ -180,6 +184,12 @@ SIGNATURES = {
     "vad_debug_sm_replay": (C.c_int, [_vp, C.c_int64, _f32p, C.c_int64, _u8p, _i32p]),
     "vad_engine_synchronize": (C.c_int, [_vp]),
     "vad_debug_set_tile": (C.c_int, [_vp, C.c_int32]),
+    "vad_scan_frame_count": (C.c_int64, [_vp, C.c_int64, C.c_int32]),
+    "vad_scan": (C.c_int, [_vp, C.POINTER(ScanItem), C.c_int64, _vp, C.c_int64, C.c_int, C.c_int32, C.c_float, _i64p,
+                           _f32p, _u8p, _i32p]),
+    "vad_scan_device": (C.c_int, [_vp, C.POINTER(ScanItem), C.c_int64, _vp, C.c_int64, C.c_int, C.c_int32, C.c_float, _i64p,
+                                  _vp, _vp, _vp, _vp]),
+    "vad_debug_scan_launch_frames": (C.c_int, [_vp, C.c_int32]),
 }
 
 _lib = None

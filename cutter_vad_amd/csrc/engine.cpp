@@ -39,6 +39,8 @@ extern "C" hipError_t vadk_launch_silero_v4(const vadk::StepParams *p, hipStream
 extern "C" hipError_t vadk_launch_silero_v5_t16(const vadk::StepParams *p, hipStream_t stream);
 extern "C" hipError_t vadk_launch_silero_v4_t16(const vadk::StepParams *p, int one_per_cu, hipStream_t stream);
 extern "C" hipError_t vadk_launch_silero_v5_t16_rates(const vadk::StepParams *p, const vadk::RateParams *r, hipStream_t stream);
+extern "C" hipError_t vadk_launch_silero_v5_scan16(const vadk::StepParams *p, const vadk::ScanItem *items, const vadk::ScanArgs *a,
+                                                   hipStream_t stream);
 extern "C" hipError_t vadk_launch_resample(const vadk::ResampleParams *p, hipStream_t stream);
 extern "C" hipError_t vadk_launch_slot_control(vadk::SmSlot *sm, float *state, const int32_t *d_slots, int n, int op,
                                                const vadk::SmSlot *def, const vad_thresholds *d_thr, int nthr, hipStream_t stream);
@@ -130,6 +132,18 @@ struct vad_engine {
     uint8_t *d_events = nullptr; size_t d_events_cap = 0;
     int32_t *d_seg = nullptr;  size_t d_seg_cap = 0;
     int32_t *d_slots = nullptr; size_t d_slots_cap = 0;
+    // whole recordings (vad_scan): the audio block and the work items on the device; the item table as it was uploaded (it must
+    // outlive the copy).  One launch covers at most scan_launch_frames frames of every recording: 0 = SCAN_LAUNCH_FRAMES, chosen
+    // with the aim that a launch with one tile per CU stays of the order of 10 ms on a GPU that others share.  An expectation, not
+    // a measurement: the one figure at hand is the single-frame form's 25.5 us per frame of 4 096 streams (README, "other configs"),
+    // the frame loop's own per-frame time is what tools/bench_configs.py scan_ingest (b) measures
+    static constexpr int SCAN_LAUNCH_FRAMES = 192;
+    int scan_launch_frames = 0;
+    void *d_audio = nullptr; size_t d_audio_cap = 0;
+    vadk::ScanItem *d_items = nullptr; size_t d_items_cap = 0;
+    std::vector<vadk::ScanItem> scan_items;
+    hipEvent_t scan_done = nullptr;          // vad_scan_device: recorded behind its last launch, which may still read d_items
+    bool scan_pending = false;               // (an event, not the caller's stream: the caller may destroy that once its work is done)
     // G.711 frames expanded to int16 for the kernels whose loaders do not decode them (launch())
     int16_t *d_g711 = nullptr; size_t d_g711_cap = 0;
     // small calls (a few streams: the one-wrapper-per-client pattern): ONE pinned block in, ONE pinned block out
@@ -816,9 +830,10 @@ void vad_engine_destroy(vad_engine *e) {
     weights_release(e->d_wstream16x);
     weights_release(e->d_wstream16y);
     void *bufs[] = {e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots, e->d_g711,
-                    e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
+                    e->d_audio, e->d_items, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
+    if (e->scan_done) (void)hipEventDestroy(e->scan_done);
     for (auto &pb : e->pipe) {
         if (pb.d_frames) (void)hipFree(pb.d_frames);
         if (pb.d_io) (void)hipFree(pb.d_io);
@@ -1116,6 +1131,184 @@ int vad_step_multi_device(vad_engine *e, const int32_t *d_slots, int64_t n, int3
     p.fmt = frame_fmt;
     p.thresh = denoise_thresh;
     return launch(e, p, stream ? static_cast<hipStream_t>(stream) : e->stream);
+}
+
+// ---- whole recordings --------------------------------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+int64_t scan_frames(int64_t nsamples, int64_t frame, int64_t hop) { return nsamples < frame ? 0 : (nsamples - frame) / hop + 1; }
+
+// the item table of an earlier vad_scan_device may still be read by its launches: they finish before the table is rebuilt
+int scan_wait(vad_engine *e) {
+    if (e->scan_pending) {
+        HIP_TRY(e, hipEventSynchronize(e->scan_done));
+        e->scan_pending = false;
+    }
+    return VAD_OK;
+}
+
+// argument checks and the plan of a scan: e->scan_items = one work item per recording, sorted by frame count (stable, descending) so
+// that the 16 streams of a tile end together; out0 = out_start[i] - out_base.  *total = frames of all recordings.
+int scan_plan(vad_engine *e, const vad_scan_item *items, int64_t n, int64_t audio_samples, int fmt, int32_t hop,
+              const int64_t *out_start, int64_t out_base, int64_t *total) {
+    if (e->version != 5)
+        return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: vad_scan needs a Silero V5 engine; frame the recordings on the host and use vad_step_multi");
+    if (e->shared_gpu)
+        return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: vad_scan runs on 16-stream tiles, which a VAD_ENGINE_SHARED_GPU engine "
+                                            "does not use; frame the recordings on the host and use vad_step_multi");
+    if (!e->d_wstream16) return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: vad_scan: the engine has no 16-stream kernel; use vad_step_multi");
+    if (n < 0 || audio_samples < 0 || (n > 0 && (!items || !out_start)))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: null buffer or bad count");
+    if (fmt < VAD_FMT_F32 || fmt > VAD_FMT_ALAW8)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: unknown frame format %d", fmt);
+    if (n > e->max_streams)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: %lld recordings, max_streams = %d", (long long)n, e->max_streams);
+    if (hop < 4 || (hop & 3))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: hop = %d must be a positive multiple of 4 samples", hop);
+    // the kernel addresses the block through a 32-bit buffer descriptor
+    if ((uint64_t)audio_samples * sample_bytes(fmt) >= (1ull << 31))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: %llu bytes of audio exceed the 2 GiB one call may address",
+                       (unsigned long long)((uint64_t)audio_samples * sample_bytes(fmt)));
+    e->scan_items.resize((size_t)n);
+    std::vector<int64_t> slots((size_t)n);
+    int64_t sum = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const vad_scan_item &it = items[i];
+        if (it.sample_offset < 0 || (it.sample_offset & 3))
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: recording %lld starts at sample %lld, not a multiple of 4",
+                           (long long)i, (long long)it.sample_offset);
+        if (it.nsamples < 0 || it.sample_offset > audio_samples || it.nsamples > audio_samples - it.sample_offset)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: recording %lld (samples %lld .. +%lld) leaves the audio block of %lld samples",
+                           (long long)i, (long long)it.sample_offset, (long long)it.nsamples, (long long)audio_samples);
+        const int64_t nf = scan_frames(it.nsamples, e->frame_samples, hop);
+        if (out_start[i] < out_base || out_start[i + 1] - out_start[i] != nf)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: out_start gives recording %lld %lld entries, it has %lld frames",
+                           (long long)i, (long long)(out_start[i + 1] - out_start[i]), (long long)nf);
+        if (out_start[i + 1] - out_base > INT32_MAX)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: more than 2^31 - 1 frames in one call");
+        slots[(size_t)i] = it.slot;
+        e->scan_items[(size_t)i] = vadk::ScanItem{(int32_t)it.slot, (uint32_t)(it.sample_offset >> 2), (int32_t)nf, (uint32_t)(out_start[i] - out_base)};
+        sum += nf;
+    }
+    if (int rc = check_slots(e, slots.data(), n)) return rc;
+    std::stable_sort(e->scan_items.begin(), e->scan_items.end(),
+                     [](const vadk::ScanItem &a, const vadk::ScanItem &b) { return a.nframes > b.nframes; });
+    *total = sum;
+    return VAD_OK;
+}
+
+// the launches of a planned scan (e->d_items holds e->scan_items): windows of at most scan_launch_frames frames, each over the
+// items that still have frames in it - a prefix of the sorted table.  State travels through HBM between them, as between two
+// vad_step_multi calls.
+int scan_launches(vad_engine *e, const void *d_audio, int64_t audio_samples, int fmt, int32_t hop, float thr, float *d_probs,
+                  uint8_t *d_events, int32_t *d_seg, int64_t total, hipStream_t s) {
+    const std::vector<vadk::ScanItem> &it = e->scan_items;
+    const int maxf = it.empty() ? 0 : it.front().nframes;
+    const int cap = e->scan_launch_frames > 0 ? e->scan_launch_frames : vad_engine::SCAN_LAUNCH_FRAMES;
+    vadk::StepParams p = e->base;
+    p.wstream = e->d_wstream16;
+    p.wstream_bytes = (uint32_t)e->wbytes16;
+    p.wstream_x = e->d_wstream16x;
+    p.wstream_x_bytes = (uint32_t)e->wbytes16x;
+    p.wstream_y = e->d_wstream16y;
+    p.wstream_y_bytes = (uint32_t)e->wbytes16y;
+    std::memcpy(p.sect, e->sect16, sizeof p.sect);
+    p.slots = nullptr;
+    p.frames = d_audio;
+    p.probs = d_probs;
+    p.events = d_events;
+    p.seg_frames = d_seg;
+    p.fmt = fmt;
+    p.thresh = thr;
+    vadk::ScanArgs a{};
+    a.audio_bytes = (uint32_t)((uint64_t)audio_samples * sample_bytes(fmt));
+    a.hopq = (uint32_t)hop >> 2;
+    size_t live = it.size();
+    for (int t0 = 0; t0 < maxf; t0 += cap) {
+        while (live > 0 && it[live - 1].nframes <= t0) --live;
+        p.n = (int32_t)live;
+        p.T = std::min(cap, maxf - t0);
+        a.t0 = t0;
+        const hipError_t r = vadk_launch_silero_v5_scan16(&p, e->d_items, &a, s);
+        if (r != hipSuccess) return e->hip_fail(r, "kernel launch (scan)");
+        e->steps += 1;
+    }
+    e->frames += total;
+    return VAD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t vad_scan_frame_count(const vad_engine *e, int64_t nsamples, int32_t hop) {
+    if (!e || hop < 1 || nsamples < 0) return -1;
+    return scan_frames(nsamples, e->frame_samples, hop);
+}
+
+int vad_debug_scan_launch_frames(vad_engine *e, int32_t frames) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (frames < 0) return e->fail(VAD_ERR_INVALID_ARG, "vad_debug_scan_launch_frames: frames per launch >= 1, or 0 for the default");
+    e->scan_launch_frames = frames;
+    return VAD_OK;
+}
+
+int vad_scan(vad_engine *e, const vad_scan_item *items, int64_t n, const void *audio, int64_t audio_samples, int frame_fmt,
+             int32_t hop, float denoise_thresh, const int64_t *out_start, float *probs_out, uint8_t *events_out,
+             int32_t *seg_frames_out) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    int64_t total = 0;
+    const int64_t base = (n > 0 && out_start) ? out_start[0] : 0;
+    if (base < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: out_start[0] is negative");
+    if (int rc = scan_plan(e, items, n, audio_samples, frame_fmt, hop, out_start, base, &total)) return rc;
+    if (total == 0) return VAD_OK;
+    if (!audio || !probs_out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: null buffer");
+    const size_t ab = (size_t)audio_samples * sample_bytes(frame_fmt);
+    if (int rc = ensure(e, e->d_audio, e->d_audio_cap, ab + 16)) return rc;
+    if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
+    if (int rc = ensure(e, e->d_probs, e->d_probs_cap, sizeof(float) * (size_t)total)) return rc;
+    if (int rc = ensure(e, e->d_events, e->d_events_cap, (size_t)total)) return rc;
+    if (int rc = ensure(e, e->d_seg, e->d_seg_cap, sizeof(int32_t) * (size_t)total)) return rc;
+    // the audio crosses the link once, in its wire format
+    HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, ab, hipMemcpyHostToDevice, e->stream));
+    if (int rc = scan_launches(e, e->d_audio, audio_samples, frame_fmt, hop, denoise_thresh, e->d_probs, e->d_events, e->d_seg, total, e->stream))
+        return rc;
+    HIP_TRY(e, hipMemcpyAsync(probs_out + base, e->d_probs, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost, e->stream));
+    if (events_out) HIP_TRY(e, hipMemcpyAsync(events_out + base, e->d_events, (size_t)total, hipMemcpyDeviceToHost, e->stream));
+    if (seg_frames_out) HIP_TRY(e, hipMemcpyAsync(seg_frames_out + base, e->d_seg, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return VAD_OK;
+}
+
+int vad_scan_device(vad_engine *e, const vad_scan_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int frame_fmt,
+                    int32_t hop, float denoise_thresh, const int64_t *out_start, float *d_probs, uint8_t *d_events,
+                    int32_t *d_seg_frames, void *stream) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    int64_t total = 0;
+    if (int rc = scan_plan(e, items, n, audio_samples, frame_fmt, hop, out_start, 0, &total)) return rc;
+    if (total == 0) return VAD_OK;
+    if (!d_audio || !d_probs) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan_device: null buffer");
+    if (reinterpret_cast<uintptr_t>(d_audio) & 3)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan_device: the audio block must be 4-byte aligned");
+    if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, s));
+    if (!e->scan_done) HIP_TRY(e, hipEventCreateWithFlags(&e->scan_done, hipEventDisableTiming));
+    const int rc = scan_launches(e, d_audio, audio_samples, frame_fmt, hop, denoise_thresh, d_probs, d_events, d_seg_frames, total, s);
+    // (also behind a failed launch: the copy of the table and the launches before it are on the stream)
+    HIP_TRY(e, hipEventRecord(e->scan_done, s));
+    e->scan_pending = true;
+    return rc;
 }
 
 // ---- pipelined host ingest ---------------------------------------------------------------------------------------

@@ -213,7 +213,13 @@ __device__ __forceinline__ void x3_units(F &&f, std::integer_sequence<int, I...>
 // ONE: one frame per stream in the call (k_T == 1), instantiated without the frame loop (silero_v5.hip has the reasons); the fused
 // resample -> step launch is always one frame.
 // FMT: the wire format of the frames - 0 float32, 1 int16 (either scale), 2 / 3 ITU-T G.711 mu-law / A-law, one byte per sample.
-// The kernel's body is silero_v5_t16_body.h, shared by the two __global__ entries below.
+// SCAN (silero_v5_scan16): whole recordings.  The frame loop reads contiguous audio and a table of work items (vad_layout.h:
+// ScanItem) instead of [n][T][frame]: frame t of the loader's stream is addressed at quad quad0 + t hop / 4, so overlapping frames
+// (hop < frame) are never materialised, and the streams of a tile may have different frame counts - the items arrive sorted by
+// count (descending), the tile's loop runs to its first item's count, and a stream whose recording has ended is HELD exactly as a
+// rejected float32 frame holds one (h, c selected from the previous values, no sm_step), in every format, and writes no result.
+// Results go to out0 + t (CSR); the finished segment's length is written on every END, 0 on the recording's other frames.
+// The kernel's body is silero_v5_t16_body.h, shared by the three __global__ entries below.
 // One workgroup per CU also here.  Built for two (a tick's segments are padded to whole tiles, so it can have a few more tiles
 // than CUs), the dispatcher packs consecutive workgroups onto the same CU: 258 tiles ran on ~130 CUs, 69.9 us per tick against
 // 55.6 for the two-launch form - so the engine uses this launch only when the tick has at most one tile per CU.
@@ -221,9 +227,15 @@ __device__ __forceinline__ void x3_units(F &&f, std::integer_sequence<int, I...>
 #define STEP16_PARAMS const float *k_wstream, float *k_state, SmSlot *k_sm, const int32_t *k_slots, const void *k_frames, const int k_n, \
                       const uint32_t k_wstream_bytes, const int k_T, const StepParams P, const RateParams R
 // float32 / int16 frames (and the fused resampler); tests/test_occupancy_contract.py knows these by name
+// (entries that are no scan: the body's SCAN branches are discarded, these two names only have to exist)
+#define STEP16_NO_SCAN                                  \
+    constexpr bool SCAN = false;                        \
+    constexpr const ScanItem *k_items = nullptr;        \
+    constexpr ScanArgs S{};
 template <bool F32IN_, bool RS, bool K8 = false, bool ONE = false>
 __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(STEP16_PARAMS) {
     constexpr int FMT = F32IN_ ? 0 : 1;
+    STEP16_NO_SCAN
 #include "silero_v5_t16_body.h"
 }
 // ITU-T G.711 frames (VAD_FMT_ULAW8 / VAD_FMT_ALAW8), decoded in the loader
@@ -231,8 +243,21 @@ template <bool ALAW, bool K8, bool ONE>
 __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16_g711(STEP16_PARAMS) {
     constexpr int FMT = ALAW ? 3 : 2;
     constexpr bool RS = false;
+    STEP16_NO_SCAN
 #include "silero_v5_t16_body.h"
 }
+// whole recordings (vad_scan): k_items [k_n] work items, k_frames the audio block, k_T the frames of the launch's window
+template <int FMT_, bool K8>
+__global__ void __launch_bounds__(NTHREADS, 1) silero_v5_scan16(const float *k_wstream, float *k_state, SmSlot *k_sm, const ScanItem *k_items,
+                                                                const void *k_frames, const int k_n, const uint32_t k_wstream_bytes,
+                                                                const int k_T, const StepParams P, const ScanArgs S) {
+    constexpr int FMT = FMT_;
+    constexpr bool RS = false, ONE = false, SCAN = true;
+    constexpr const int32_t *k_slots = nullptr;
+    const RateParams R{};
+#include "silero_v5_t16_body.h"
+}
+#undef STEP16_NO_SCAN
 #undef STEP16_PARAMS
 #undef X3_CONV
 #undef X3_HALF
@@ -275,6 +300,28 @@ extern "C" hipError_t vadk_launch_silero_v5_t16(const vadk::StepParams *p, hipSt
     }
 #undef T16_LAUNCH_G711
 #undef T16_LAUNCH
+    return hipGetLastError();
+}
+
+// whole recordings: p->n items (sorted by frame count, descending), p->frames = the audio block, p->T = frames of this launch's window
+// [a->t0, a->t0 + p->T), p->probs / events / seg_frames = the CSR arrays; p->fmt as in vadk_launch_silero_v5_t16
+extern "C" hipError_t vadk_launch_silero_v5_scan16(const vadk::StepParams *p, const vadk::ScanItem *items, const vadk::ScanArgs *a,
+                                                   hipStream_t stream) {
+    (void)hipGetLastError();
+    const int tiles = (p->n + MT16 - 1) / MT16;
+    if (tiles <= 0) return hipSuccess;
+    if (p->T < 1 || p->fmt < 0 || p->fmt > 4 || a->hopq < 1 || a->t0 < 0 || (a->audio_bytes >> 31)) return hipErrorInvalidValue;
+    if ((reinterpret_cast<uintptr_t>(p->frames) & 3) || (reinterpret_cast<uintptr_t>(items) & 15)) return hipErrorInvalidValue;
+#define SCAN16_LAUNCH(F, K)                                                                                                    \
+    hipLaunchKernelGGL((silero_v5_scan16<F, K>), dim3(tiles), dim3(vadk::NTHREADS), 0, stream, p->wstream, p->state, p->sm, items, \
+                       p->frames, (int)p->n, p->wstream_bytes, (int)p->T, *p, *a)
+    const int f = p->fmt == 0 ? 0 : p->fmt <= 2 ? 1 : p->fmt - 1;      // vad_frame_format -> FMT
+    if (p->variant != 0) {
+        if (f == 0) SCAN16_LAUNCH(0, true); else if (f == 1) SCAN16_LAUNCH(1, true); else if (f == 2) SCAN16_LAUNCH(2, true); else SCAN16_LAUNCH(3, true);
+    } else {
+        if (f == 0) SCAN16_LAUNCH(0, false); else if (f == 1) SCAN16_LAUNCH(1, false); else if (f == 2) SCAN16_LAUNCH(2, false); else SCAN16_LAUNCH(3, false);
+    }
+#undef SCAN16_LAUNCH
     return hipGetLastError();
 }
 

@@ -1,15 +1,17 @@
 // The body of the 16-stream Silero V5 step kernel: the text between the braces of a __global__ function, included by
-// silero_v5_t16.hip once per entry point (silero_v5_step16, silero_v5_step16_g711) - textually, not as a __device__ function the
+// silero_v5_t16.hip once per entry point (silero_v5_step16, silero_v5_step16_g711, silero_v5_scan16) - textually, not as a __device__ function the
 // entries call: the compiler schedules and allocates an inlined callee differently (other register counts for every existing
 // instantiation), and the float32 / int16 kernels were to stay instruction for instruction what they were.  The including
 // function provides the arguments k_wstream .. k_T, P, R and the constants FMT (wire format: 0 float32, 1 int16 of either scale,
-// 2 / 3 ITU-T G.711 mu-law / A-law, one byte per sample), RS, K8, ONE (silero_v5_t16.hip explains them).
+// 2 / 3 ITU-T G.711 mu-law / A-law, one byte per sample), RS, K8, ONE, SCAN (silero_v5_t16.hip explains them).  SCAN: the entry
+// also provides k_items and S (vad_layout.h: ScanItem, ScanArgs); the other entries a null k_items and an empty S.
 #define KP(f) k_##f
     using namespace vadk::v5;
     constexpr bool F32IN = FMT == 0;
     constexpr bool G711 = FMT >= 2;
     static_assert(!RS || F32IN, "resampled frames are float32");
     static_assert(!(RS && K8), "the fused resampler feeds the 16 kHz model");
+    static_assert(!SCAN || (!RS && !ONE), "a scan is the frame-loop form on audio in HBM");
     constexpr int QL = K8 ? 8 : 16;               // loader lanes per stream = quads per quarter column
     constexpr int CS = 4 * QL;                    // folded-operand rows per column
     constexpr int PP = K8 ? 24 : 48;              // quad rows per |STFT| column (enc0's input) as planes: 12 per K-step
@@ -48,7 +50,19 @@
         live = vcol < R.total;
     }
     const int tile0 = (int)blockIdx.x * MT16;                      // (not RS: the tile's first stream in the call's arrays)
-    const int slot = live ? (KP(slots) ? KP(slots)[gf] : gf) : 0;
+    // SCAN: the stream of this lane's MFMA column is work item vcol: its slot, how many of its frames lie at and behind the
+    // launch's first (ncol; frame t of the launch is held for this column when t >= ncol) and where its results go; the
+    // loader's stream (item tile0 + lms, below) gives this thread the quad its frames start at.  Items past the table: no frames.
+    int slot, ncol = 0;
+    uint32_t obase = 0;
+    if constexpr (SCAN) {
+        const u32x4 it = live ? *reinterpret_cast<const u32x4 *>(k_items + vcol) : u32x4{0u, 0u, 0u, 0u};
+        slot = (int)it.x;
+        ncol = (int)it.z - S.t0;
+        obase = it.w + (uint32_t)S.t0;
+    } else {
+        slot = live ? (KP(slots) ? KP(slots)[gf] : gf) : 0;
+    }
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(KP(wstream)), 0, (int)KP(wstream_bytes), 0x00020000);
     const int lane16 = lane * 16;
 #define WL(blk) ldw(wrs, lane16, (blk))
@@ -61,7 +75,12 @@
     const int o_stft = (int)P.sect[w][S_STFT], o_nyq = (int)P.sect[w][S_NYQ], o_x0 = (int)P.sect[w][S_ENC0_X3];
     const int o_y1 = (int)P.sect[w][S_ENC1_X3], o_e2 = (int)P.sect[w][S_ENC2], o_e3 = (int)P.sect[w][S_ENC3];
     const int o_l = (int)P.sect[w][S_LSTM], o_x3 = (int)P.sect[w][S_LSTM_X3];
-    const int T = (ONE || RS) ? 1 : KP(T);
+    // SCAN: the items are sorted by frame count, so the tile's first item has the most: its count, clipped to the launch's window
+    int T = (ONE || RS) ? 1 : KP(T);
+    if constexpr (SCAN) {
+        T = min(T, k_items[tile0].nframes - S.t0);
+        if (T < 1) return;                        // nothing of this tile in the window (block-uniform, before every barrier)
+    }
 
     // ---- frame ingest set-up: 16 lanes per stream, 16 streams per fold call (ms = tid >> 4) ----
     const float thr = P.thresh;
@@ -73,7 +92,8 @@
     constexpr int qsh = f32in ? 4 : G711 ? 2 : 3;           // a quad of samples: 16 / 8 / 4 bytes
     const float sc = P.fmt == 1 ? 32767.0f : 32768.0f, rsc = 1.0f / sc;
     const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<void *>(KP(frames)), 0, (int)((unsigned)KP(n) * (unsigned)T * ((f32in ? 2048u : G711 ? 512u : 1024u) >> (K8 ? 1 : 0))), 0x00020000);
+        const_cast<void *>(KP(frames)), 0,
+        SCAN ? (int)S.audio_bytes : (int)((unsigned)KP(n) * (unsigned)T * ((f32in ? 2048u : G711 ? 512u : 1024u) >> (K8 ? 1 : 0))), 0x00020000);
     // one quad of raw samples: 16 bytes (float32; int16 uses the first 8), G.711: the quad is one dword, fetched as such
     using XQ = std::conditional_t<G711, uint32_t, u32x4>;
     auto x_load = [&](int off) -> XQ {
@@ -82,10 +102,22 @@
     };
     XQ xa_[4], xb_[4], xc_[4];                     // raw quads of the three columns
     f32x4 *const F4 = lds + T_LDS_F4;              // RS: the tile's resampled frames
+    // SCAN: frame tt of the launch, for the loader's stream, starts at quad xq0 + tt hopq of the audio block - frames overlap in
+    // memory when hop < frame, nothing is copied.  Unsigned: a stream past its end keeps walking (into its neighbour's samples, or
+    // past the block, where the descriptor answers 0); what it loads reaches selects only.
+    uint32_t xq0 = 0;
+    if constexpr (SCAN) {
+        const int li = tile0 + lms;
+        xq0 = (li < KP(n) ? k_items[li].quad0 : 0u) + (uint32_t)S.t0 * S.hopq;
+    }
 #define X_ISSUE(c, XR, tt)                                                                                      \
     if constexpr (RS) {                                                                                         \
         _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                           \
             XR[k] = __builtin_bit_cast(u32x4, F4[(tid >> 4) * FQ + 32 * (c) + q + 16 * k]);                     \
+    } else if constexpr (SCAN) {                                                                                \
+        const uint32_t fq = xq0 + (uint32_t)(tt) * S.hopq + 32 * (c) + q;                                       \
+        _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                           \
+            XR[k] = x_load((int)((fq + 16 * k) << qsh));                                                        \
     } else {                                                                                                    \
         const int fq = ((tile0 + (tid >> 4)) * T + (tt)) * 128 + 32 * (c) + q;                                  \
         _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                           \
@@ -97,9 +129,15 @@
 #define X_ISSUE8(c0, XR, tt)                                                                                    \
     {                                                                                                           \
         const int cc_ = (c0) + lcol < 2 ? (c0) + lcol : 2;                                                      \
+        if constexpr (SCAN) {                                                                                   \
+            const uint32_t fq = xq0 + (uint32_t)(tt) * S.hopq + 16 * cc_ + q;                                   \
+            _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                       \
+                XR[k] = x_load((int)((fq + 8 * k) << qsh));                                                     \
+        } else {                                                                                                \
         const int fq = ((tile0 + lms) * T + (tt)) * 64 + 16 * cc_ + q;                                          \
         _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                           \
             XR[k] = x_load((fq + 8 * k) << qsh);                                                                \
+        }                                                                                                       \
     }
 
     // ---- RS: the tile's parts.  A part = the columns c0 .. c1 - 1 of this tile that belong to one segment (one input rate); a tile
@@ -939,7 +977,9 @@
             STAMP(14);
             f32x4 part4 = f32x4{0.f, 0.f, 0.f, 0.f};
             // a rejected frame (float32 only) leaves the stream's h and c as they were: not stored, and held for the next frame
-            const bool bad = f32in && (K8 ? (flagL[n] | flagL[16 + n]) : flagL[n]) != 0;
+            // SCAN: so does, in every format, a frame past the end of the stream's recording
+            const bool rej = f32in && (K8 ? (flagL[n] | flagL[16 + n]) : flagL[n]) != 0;
+            const bool bad = SCAN ? (rej || t >= ncol) : rej;
             f32x4 hq[2];
 #pragma unroll
             for (int rt = 0; rt < 2; ++rt) {
@@ -949,7 +989,7 @@
                 f32x4 cn = pk::fma(pk::sigmoid4(f4), c4, pk::mul(pk::sigmoid4(i4), pk::tanh4(g4)));
                 f32x4 hn = pk::mul(pk::sigmoid4(o4), pk::tanh4(cn));
                 part4 = pk::fma(hwv, relu4(hn), part4);
-                if constexpr (f32in && !ONE && !RS) {   // (the head ignores z of a rejected stream)
+                if constexpr ((f32in || SCAN) && !ONE && !RS) {   // (the head ignores z of a rejected stream)
                     hn = bad ? hv[rt] : hn;             // h_{t-1}: the lane's own units, kept in registers beside c (LDS holds pieces)
                     cn = bad ? c4 : cn;
                     hv[rt] = hn;
@@ -978,6 +1018,22 @@
             if (sm_thread) {
                 // rejected (include/vad_engine.h): NaN and VAD_EV_REJECTED alone, no sm_step, the state machine as it was
                 const bool bad = f32in && (K8 ? (flagL[tid] | flagL[16 + tid]) : flagL[tid]) != 0;
+                if constexpr (SCAN) {
+                    // tid < 16: this thread's column is the item whose ncol / obase it holds.  A frame past the recording's end
+                    // writes nothing and steps nothing; the slot goes back as it is.  seg: the finished segment's length on
+                    // every END, 0 on every other frame of the recording (one entry per frame)
+                    SmSlot sm = smL[tid];
+                    if (t < ncol) {
+                        const size_t o = (size_t)obase + (size_t)t;
+                        int seg = 0;
+                        const int ev = bad ? EV_REJECTED : sm_step(sm, p, &seg);
+                        P.probs[o] = bad ? __builtin_nanf("") : p;
+                        if (P.events) P.events[o] = (uint8_t)ev;
+                        if (P.seg_frames) P.seg_frames[o] = (ev & 2) ? seg : 0;
+                    }
+                    if (t == T - 1) KP(sm)[sm_slot] = sm;
+                    else smL[tid] = sm;
+                } else {
                 P.probs[(size_t)gf * T + t] = bad ? __builtin_nanf("") : p;   // tid < 16: this thread's column is stream gf
                 SmSlot sm = smL[tid];
                 int seg = 0;
@@ -986,6 +1042,7 @@
                 else smL[tid] = sm;
                 if (ev & 2) seg_last = seg;
                 if (P.events) P.events[(size_t)gf * T + t] = (uint8_t)ev;
+                }
             }
         }
         if (++t >= T) break;
@@ -1000,5 +1057,5 @@
 #undef WX
 #undef X_ISSUE
 #undef WL
-    if (sm_thread && P.seg_frames) P.seg_frames[gf] = seg_last;
+    if constexpr (!SCAN) { if (sm_thread && P.seg_frames) P.seg_frames[gf] = seg_last; }
 #undef KP

@@ -212,6 +212,25 @@ struct StepParams {
 static_assert(sizeof(StepParams) == 368, "StepParams keeps its size (see above)");
 #endif
 
+// whole recordings, framed by the kernel's loader (csrc/silero_v5_t16.hip: silero_v5_scan16; vad_scan).  A launch reads one
+// contiguous block of audio and a table of work items, one per stream, sorted by nframes (descending): frame t of an item are
+// the samples from 4 (quad0 + t hopq) on, its results go to entry out0 + t of the call's probs / events / seg arrays.
+struct ScanItem {
+    int32_t slot;
+    uint32_t quad0;           // sample_offset / 4
+    int32_t nframes;
+    uint32_t out0;            // index of the recording's frame 0 in the outputs (CSR)
+};
+static_assert(sizeof(ScanItem) == 16, "ScanItem layout");
+// a launch's arguments next to StepParams (which keeps its size): StepParams.n = items, .T = frames of the window, .frames = the
+// audio block; probs / events / seg_frames = the CSR arrays (seg_frames: one entry per FRAME here)
+struct ScanArgs {
+    uint32_t audio_bytes;     // the buffer descriptor's range: the whole block; loads past it return 0
+    uint32_t hopq;            // hop / 4
+    int32_t t0;               // the launch covers frames t0 .. t0 + T - 1 of every item
+    int32_t pad;
+};
+
 // resampler launch parameters (csrc/resample.hip)
 struct ResampleSeg {
     const float *wstream;     // folded operator (pack_weights.cpp: pack_resample_operator)

@@ -11,6 +11,7 @@ exception classes with the same message prefixes (SURVEY §8 b).
 from __future__ import annotations
 
 import ctypes as C
+import threading
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -60,6 +61,8 @@ class Engine:
         self._rate_gather_fn = int(C.cast(self._lib.vad_tick_push_rate_gather, C.c_void_p).value)
         self._h = C.c_void_p()
         self._tickets = {}                  # ticket -> the buffers a pipelined call still reads (submit / collect)
+        self._scan_block = None             # scan(): the page-locked block the recordings are packed into ...
+        self._scan_lock = threading.Lock()  # ... held from the packing to the return of vad_scan: engines are shared between threads
         self.last_tick_us = (0.0, 0.0, 0.0)
         self.last_tick_dropped = 0
         self.last_tick_staged_next = 0
@@ -81,6 +84,7 @@ class Engine:
     # ------------------------------------------------------------------ lifetime
     def close(self) -> None:
         h, self._h = self._h, C.c_void_p()
+        self._scan_block = None             # the engine releases its page-locked blocks
         if h:
             self._lib.vad_engine_destroy(h)
 
@@ -261,6 +265,96 @@ class Engine:
         thr = -1.0 if denoise is None else float(denoise)
         self._check(self._lib.vad_step_multi_device(self._h, d_slots or None, n, T, d_frames, fmt, thr, d_probs,
                                                     d_events or None, d_seg or None, stream or None))
+
+    # ------------------------------------------------------------------ whole recordings
+    def scan_frame_count(self, nsamples: int, hop: Optional[int] = None) -> int:
+        """Frames of a recording of ``nsamples`` samples at ``hop`` (``vad_scan_frame_count``; the tail is dropped)."""
+        hop = self.frame_samples // 2 if hop is None else int(hop)
+        n = int(self._lib.vad_scan_frame_count(self._h, int(nsamples), hop))
+        if n < 0:
+            raise AudioProcessingError(f"Model prediction failed: bad sample count or hop ({nsamples}, {hop})")
+        return n
+
+    def set_scan_launch_frames(self, frames: int = 0) -> None:
+        """Diagnostic (``vad_debug_scan_launch_frames``): frames per launch of ``scan``; 0 = the default.  Results do not depend on it."""
+        self._check(self._lib.vad_debug_scan_launch_frames(self._h, int(frames)), VADError)
+
+    def _scan_pack(self, recordings, law: Optional[str]):
+        """The recordings (1-D arrays of one dtype) packed into the engine's page-locked block, each starting on a multiple of 4
+        samples -> (block, samples, frame format, sample offsets, lengths)."""
+        recs = [np.asarray(r) for r in recordings]
+        g711 = _law_format(law, recs[0] if recs else None)
+        if g711 is None:
+            recs = [r if r.dtype in _FMT else r.astype(np.float32) for r in recs]
+        dt = recs[0].dtype if recs else np.dtype(np.float32)
+        for r in recs:
+            if r.ndim != 1 or r.dtype != dt:
+                raise AudioProcessingError(f"Model prediction failed: recordings must be 1-D arrays of one dtype, got {r.shape} {r.dtype} next to {dt}")
+        lens = np.array([r.size for r in recs], np.int64)
+        offs = np.zeros(len(recs), np.int64)
+        if len(recs) > 1:
+            offs[1:] = np.cumsum((lens[:-1] + 3) & ~3)
+        total = int(offs[-1] + lens[-1]) if recs else 0
+        need = max(total, 1) * dt.itemsize
+        if self._scan_block is None or self._scan_block.size < need:      # grown on demand, kept: pinning is the slow part
+            if self._scan_block is not None:
+                self._check(self._lib.vad_host_free(self._h, self._scan_block.ctypes.data_as(C.c_void_p)), VADError)
+                self._scan_block = None
+            self._scan_block = self.pinned_array(need + need // 4, np.uint8)
+        block = self._scan_block[:need].view(dt)
+        for i, (r, o) in enumerate(zip(recs, offs)):
+            block[o:o + r.size] = r
+            block[o + r.size:(offs[i + 1] if i + 1 < len(recs) else o + r.size)] = 0      # the padding to a multiple of 4
+        return block, total, (_FMT[dt] if g711 is None else g711), offs, lens
+
+    def scan(self, slots, recordings, hop: Optional[int] = None, law: Optional[str] = None, i16_scale: int = 32767,
+             denoise: Optional[float] = 0.01):
+        """Whole recordings of different lengths, framed on the GPU (``vad_scan``): ``recordings`` is a list of 1-D arrays
+        (float32, int16, or uint8 G.711 codes with ``law``), recording i continues stream ``slots[i]``.  Frame t of a recording
+        = its samples ``t * hop .. t * hop + frame_samples - 1``; ``hop`` defaults to ``frame_samples // 2``
+        (``AudioUtils.split_into_frames`` as ``VADWrapper`` calls it), ``hop = frame_samples`` is Silero's back-to-back framing.
+        -> (probs, events, seg_frames): three lists with one array per recording (views of the call's CSR arrays), one entry per
+        frame; ``seg_frames`` holds the finished segment's length on every ``VAD_EV_END`` frame and 0 elsewhere
+        (``cutter_vad_amd.scan.speech_segments`` turns the two into sample ranges)."""
+        s = np.ascontiguousarray(slots, dtype=np.int64).reshape(-1)
+        recordings = list(recordings)
+        if s.size != len(recordings):
+            raise AudioProcessingError(f"Model prediction failed: {s.size} slots for {len(recordings)} recordings")
+        hop = self.frame_samples // 2 if hop is None else int(hop)
+        with self._scan_lock:
+            block, total, fmt, offs, lens = self._scan_pack(recordings, law)
+            if fmt == _ffi.VAD_FMT_I16_32767 and i16_scale == 32768:
+                fmt = _ffi.VAD_FMT_I16_32768
+            items = (_ffi.ScanItem * max(1, s.size))()
+            start = np.zeros(s.size + 1, np.int64)
+            for i in range(s.size):
+                items[i] = _ffi.ScanItem(int(s[i]), int(offs[i]), int(lens[i]))
+                start[i + 1] = start[i] + (self.scan_frame_count(int(lens[i]), hop) if hop >= 1 else 0)
+            nf = int(start[-1])
+            probs = np.empty(nf, np.float32)
+            ev = np.zeros(nf, np.uint8)
+            seg = np.zeros(nf, np.int32)
+            thr = -1.0 if denoise is None else float(denoise)
+            self._check(self._lib.vad_scan(self._h, items, s.size, block.ctypes.data_as(C.c_void_p), total, fmt, hop, thr,
+                                           _ptr(start, C.c_int64), _ptr(probs, C.c_float), _ptr(ev, C.c_uint8), _ptr(seg, C.c_int32)))
+        cut = lambda a: [a[start[i]:start[i + 1]] for i in range(s.size)]
+        return cut(probs), cut(ev), cut(seg)
+
+    def scan_device(self, slots, offsets, lengths, d_audio: int, audio_samples: int, d_probs: int, d_events: int = 0, d_seg: int = 0,
+                    hop: Optional[int] = None, fmt: int = _ffi.VAD_FMT_F32, denoise: Optional[float] = 0.01, stream: int = 0) -> np.ndarray:
+        """``scan`` on device pointers (integers): recording i = ``lengths[i]`` samples from sample ``offsets[i]`` (a multiple
+        of 4) of the block at ``d_audio``; results go to the CSR positions this returns (``out_start`` [n + 1]).  Asynchronous."""
+        s = np.ascontiguousarray(slots, dtype=np.int64).reshape(-1)
+        hop = self.frame_samples // 2 if hop is None else int(hop)
+        items = (_ffi.ScanItem * max(1, s.size))()
+        start = np.zeros(s.size + 1, np.int64)
+        for i in range(s.size):
+            items[i] = _ffi.ScanItem(int(s[i]), int(offsets[i]), int(lengths[i]))
+            start[i + 1] = start[i] + self.scan_frame_count(int(lengths[i]), hop)
+        thr = -1.0 if denoise is None else float(denoise)
+        self._check(self._lib.vad_scan_device(self._h, items, s.size, d_audio, int(audio_samples), fmt, hop, thr, _ptr(start, C.c_int64),
+                                              d_probs, d_events or None, d_seg or None, stream or None))
+        return start
 
     # ------------------------------------------------------------------ tick assembler (shared-pool serving)
     def tick_push(self, slot: int, frame, gate_on: bool = True, i16_scale: int = 32767, sample_rate: Optional[int] = None,

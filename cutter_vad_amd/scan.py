@@ -1,0 +1,58 @@
+"""Whole recordings -> speech segments: the corpus caller's face of ``Engine.scan`` (``vad_scan``, include/vad_engine.h).
+
+``VADWrapper.process_audio_data`` stays on its own path (its callback-abort contract needs the frame-by-frame replay); this
+module is for callers who hold many finished recordings of different lengths and want the segments of each.
+"""
+
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _ffi
+from .core.config import VADConfig
+from .core.exceptions import ConfigurationError
+
+
+def speech_segments(events, seg_frames, frame: int, hop: int) -> List[Tuple[int, int]]:
+    """The finished segments of one recording as sample ranges ``[(start_sample, end_sample), ...]`` (end exclusive), from the
+    per-frame ``events`` and ``seg_frames`` of ``Engine.scan``: a ``VAD_EV_END`` at frame ``e`` with length ``L`` covers the
+    frames ``e - L + 1 .. e``, i.e. the samples ``[(e - L + 1) * hop, e * hop + frame)``.  A segment still open at the
+    recording's last frame has no END and is not listed."""
+    ev = np.asarray(events)
+    seg = np.asarray(seg_frames)
+    out = []
+    for e in np.flatnonzero((ev & _ffi.VAD_EV_END) != 0):
+        L = int(seg[e])
+        out.append(((int(e) - L + 1) * hop, int(e) * hop + frame))
+    return out
+
+
+def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
+                    law: Optional[str] = None) -> List[List[Tuple[int, int]]]:
+    """Speech segments of every recording, one launch sequence for the lot: opens one stream per recording with the config's
+    thresholds, scans (frames of ``engine.frame_samples`` at ``hop``, default half a frame as ``VADWrapper`` frames a chunk;
+    the config's denoise gate), closes the streams -> per recording ``[(start_sample, end_sample), ...]``.
+    ``engine``: an :class:`~cutter_vad_amd.engine.Engine`; default: the process-wide pool's engine for the config."""
+    from .pool import default_pool, resolve_model_path
+    cfg = config or VADConfig()
+    if engine is None:
+        engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
+    frame = engine.frame_samples
+    if cfg.buffer_size != frame:
+        raise ConfigurationError(f"scan_recordings frames at the model's frame size: buffer_size = {cfg.buffer_size}, "
+                                 f"the engine's frames have {frame} samples")
+    hop = frame // 2 if hop is None else int(hop)
+    recordings = list(recordings)
+    if not recordings:
+        return []
+    slots = engine.open_streams(len(recordings))
+    try:
+        engine.set_thresholds_many(slots, (cfg.vad_start_probability, cfg.vad_end_probability, cfg.voice_start_ratio,
+                                           cfg.voice_end_ratio, cfg.voice_start_frame_count, cfg.voice_end_frame_count))
+        _probs, ev, seg = engine.scan(slots, recordings, hop=hop, law=law, denoise=0.01 if cfg.enable_denoising else None)
+    finally:
+        for s in slots:
+            engine.close_stream(int(s))
+    return [speech_segments(e, g, frame, hop) for e, g in zip(ev, seg)]

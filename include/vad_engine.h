@@ -241,6 +241,53 @@ VAD_API int vad_step_multi_device(vad_engine *e, const int32_t *d_slots, int64_t
                                   int32_t *d_seg_frames, void *stream);
 
 /*
+ * Whole recordings (Silero V5).  n recordings of different lengths lie in ONE block of audio (`audio`, audio_samples samples in
+ * `frame_fmt`); recording i is the nsamples samples from sample_offset on and runs on stream `slot`, continuing from that
+ * stream's state.  The kernel's loader frames them itself: frame t of a recording = its samples t * hop .. t * hop + frame - 1
+ * (frame = vad_info.frame_samples), a trailing part shorter than a frame is dropped (AudioUtils.split_into_frames,
+ * utils/audio.py:183).  hop = frame / 2 is that function's framing, hop = frame Silero's own back-to-back one.  Nothing is
+ * framed or converted on the host, the block crosses the link once in its wire format, and recordings of different lengths
+ * share launches: a stream whose recording has ended is held (its (h, c) and state machine stay exactly as its last frame left
+ * them) while the longer ones go on.
+ *   Results are CSR: recording i owns the entries out_start[i] .. out_start[i + 1] - 1 of probs_out / events_out /
+ * seg_frames_out, and out_start[i + 1] - out_start[i] must equal vad_scan_frame_count(e, nsamples_i, hop), else
+ * VAD_ERR_INVALID_ARG.  probs / events mean what they mean in vad_step_multi (a float32 frame with a NaN / Inf sample:
+ * VAD_EV_REJECTED, NaN, state untouched); seg_frames_out[k] is the finished segment's length in frames on a VAD_EV_END frame
+ * and 0 on every other one - every segment of a recording, not only the last.  Entries outside out_start[0] .. out_start[n]
+ * are not written.
+ *   VAD_ERR_INVALID_ARG, with a message: hop < 4 or not a multiple of 4; a sample_offset that is not a multiple of 4; a
+ * recording that leaves the block; 2 GiB or more of audio in one call (the kernel addresses the block through a 32-bit buffer
+ * descriptor); n > max_streams.  VAD_ERR_BAD_SLOT: a slot that is not open, or listed twice.
+ *   One launch covers at most a fixed number of frames of every recording (so that no launch occupies a shared GPU for
+ * seconds); state travels through device memory between launches as between two vad_step_multi calls, so the results do not
+ * depend on that number.  vad_info.steps grows by the number of launches, vad_info.frames by the number of frames.
+ *   Silero V4 engines and VAD_ENGINE_SHARED_GPU engines return VAD_ERR_UNSUPPORTED: there is no fallback kernel behind this
+ * entry point; frame such recordings on the host and use vad_step_multi.
+ *   VAD_ABI_VERSION is unchanged (nothing existing moved): the presence of vad_scan is how a caller detects the feature.
+ */
+typedef struct vad_scan_item {
+    int64_t slot;
+    int64_t sample_offset;   /* first sample of the recording in the block; a multiple of 4 */
+    int64_t nsamples;
+} vad_scan_item;
+/* frames of a recording of nsamples samples: nsamples < frame ? 0 : (nsamples - frame) / hop + 1; -1 for a bad argument */
+VAD_API int64_t vad_scan_frame_count(const vad_engine *e, int64_t nsamples, int32_t hop);
+VAD_API int vad_scan(vad_engine *e, const vad_scan_item *items, int64_t n, const void *audio, int64_t audio_samples, int frame_fmt,
+                     int32_t hop, float denoise_thresh, const int64_t *out_start /*[n + 1]*/, float *probs_out,
+                     uint8_t *events_out /*or NULL*/, int32_t *seg_frames_out /*or NULL*/);
+/*
+ * The same on device memory: d_audio (4-byte aligned), d_probs, d_events (or NULL) and d_seg_frames (or NULL) live on the engine's
+ * GPU; items and out_start are host arrays (the slots are checked).  Enqueues on `stream` (NULL = the engine's own) and returns;
+ * a following vad_scan / vad_scan_device first waits for these launches (they read the engine's item table) - on an event the
+ * engine recorded behind them, not on `stream`, which the caller may destroy once its own work has finished.
+ */
+VAD_API int vad_scan_device(vad_engine *e, const vad_scan_item *items, int64_t n, const void *d_audio, int64_t audio_samples,
+                            int frame_fmt, int32_t hop, float denoise_thresh, const int64_t *out_start /*[n + 1]*/, float *d_probs,
+                            uint8_t *d_events, int32_t *d_seg_frames, void *stream);
+/* Diagnostic: frames one launch of vad_scan covers at most; 0 = the default.  Results do not depend on it. */
+VAD_API int vad_debug_scan_launch_frames(vad_engine *e, int32_t frames);
+
+/*
  * Pipelined host ingest.  vad_step* on host pointers are copy -> kernel -> copy -> wait; at 8 192 streams the PCIe copy is
  * 5-8 x the kernel, so a serving loop should overlap the copy of tick t+1 with the kernel of tick t:
  *

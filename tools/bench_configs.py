@@ -409,6 +409,122 @@ def g711_ingest():
     return out
 
 
+def scan_ingest():
+    """Whole recordings (vad_scan), two things on one box, interleaved, three runs each:
+    (a) a corpus of int16 recordings of 5 - 30 s (seeded lengths; VAD_SCAN_BENCH_N of them, default 1 024) from page-locked host
+        memory: Engine.scan against the route a caller had before it - AudioUtils.split_into_frames on the host to float32, then
+        vad_step_multi on all streams, padded to the longest recording (in windows of T frames: one call addresses < 2 GiB);
+    (b) the kernel alone: vad_scan_device against vad_step_multi_device at n = 1 024 / 4 096, T = 32, on the same pre-framed
+        float32 audio in HBM (hop = frame, one length: only the addressing differs), HIP events around every call."""
+    import time
+    import numpy as np
+    from cutter_vad_amd import _ffi
+    from cutter_vad_amd.utils.audio import AudioUtils
+    out = []
+    N = int(os.environ.get("VAD_SCAN_BENCH_N", "1024"))
+    part = os.environ.get("VAD_SCAN_BENCH_PART", "ab")
+    eng = Engine(blob(5), max_streams=4096)
+    frame, hop = eng.frame_samples, eng.frame_samples // 2
+    if "a" in part:
+        rng = np.random.default_rng(0)
+        lens = rng.integers(5 * 16000, 30 * 16000 + 1, N)
+        offs = np.concatenate([[0], np.cumsum((lens[:-1] + 3) & ~3)])
+        total = int(offs[-1] + lens[-1])
+        block = eng.pinned_array(total, np.int16)
+        block[:] = (2000.0 * rng.standard_normal(total)).astype(np.int16)
+        recs = [block[o:o + n] for o, n in zip(offs, lens)]
+        slots = eng.open_streams(N)
+        counts = np.array([eng.scan_frame_count(int(n), hop) for n in lens])
+        TW = max(1, min(int(counts.max()), ((1 << 31) - 1) // (N * frame * 4)))
+        buf = np.zeros((N, TW, frame), np.float32)
+
+        def route_scan():
+            t0 = time.perf_counter()
+            probs, _, _ = eng.scan(slots, recs, hop=hop)
+            return time.perf_counter() - t0, sum(p.size for p in probs)
+
+        def route_frames():
+            t0 = time.perf_counter()
+            framed = [AudioUtils.split_into_frames(r.astype(np.float32) / np.float32(32767.0), frame, hop) for r in recs]
+            t_split = time.perf_counter() - t0
+            for w0 in range(0, int(counts.max()), TW):
+                tw = min(TW, int(counts.max()) - w0)
+                buf[:, :tw] = 0
+                for i, f in enumerate(framed):
+                    k = max(0, min(tw, len(f) - w0))
+                    buf[i, :k] = f[w0:w0 + k]
+                eng.step_multi(slots, buf[:, :tw])
+            return time.perf_counter() - t0, t_split
+
+        route_scan()                                    # warm: buffers, code objects
+        runs_scan, runs_frames, splits = [], [], []
+        for _ in range(3):
+            eng.reset(slots)
+            dt, nf = route_scan()
+            runs_scan.append(dt)
+            eng.reset(slots)
+            dt, ts = route_frames()
+            runs_frames.append(dt)
+            splits.append(ts)
+        out.append({"config": f"scan_ingest (a): {N} int16 recordings of 5 - 30 s, page-locked host memory, hop = frame / 2",
+                    "frames": int(counts.sum()), "frames_padded": int(N * counts.max()), "audio_MB": total * 2 / 1e6,
+                    "framed_float32_MB_padded": N * int(counts.max()) * frame * 4 / 1e6,
+                    "s_scan_runs": runs_scan, "s_split_then_step_multi_runs": runs_frames, "s_of_that_host_split_runs": splits,
+                    "s_scan": float(np.median(runs_scan)), "s_split_then_step_multi": float(np.median(runs_frames)),
+                    "ratio": float(np.median(runs_frames) / np.median(runs_scan))})
+        for s in slots:
+            eng.close_stream(int(s))
+        del buf
+    if "b" in part:
+        T = 32
+        for n in (1024, 4096):
+            slots = eng.open_streams(n)
+            d_slots = torch.from_numpy(np.asarray(slots, np.int32)).cuda()
+            x = (0.1 * torch.randn(n, T, frame, device="cuda")).contiguous()
+            d_p = torch.empty(n * T, device="cuda")
+            d_e = torch.empty(n * T, dtype=torch.uint8, device="cuda")
+            d_s = torch.empty(n * T, dtype=torch.int32, device="cuda")
+            ts = torch.cuda.Stream()
+            offsets, lengths = np.arange(n, dtype=np.int64) * T * frame, np.full(n, T * frame, np.int64)
+
+            def one(scan):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record(ts)
+                if scan:
+                    eng.scan_device(slots, offsets, lengths, x.data_ptr(), n * T * frame, d_p.data_ptr(), d_e.data_ptr(), d_s.data_ptr(),
+                                    hop=frame, fmt=_ffi.VAD_FMT_F32, stream=ts.cuda_stream)
+                else:
+                    eng.step_multi_device(n, T, x.data_ptr(), d_p.data_ptr(), d_slots.data_ptr(), d_e.data_ptr(), d_s[:n].data_ptr(),
+                                          stream=ts.cuda_stream)
+                e1.record(ts)
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1) * 1e-3
+
+            for _ in range(5):
+                one(True), one(False)
+            reps = max(10, K // 20)
+            row = {"config": f"scan_ingest (b): kernel alone, n={n}, T={T}, float32 in HBM, hop = frame; median of {reps} calls per run"}
+            runs = {"scan": [], "step_multi": []}
+            for _ in range(3):
+                a, b = [], []
+                for _ in range(reps):
+                    a.append(one(True))
+                    b.append(one(False))
+                runs["scan"].append(float(np.median(a)))
+                runs["step_multi"].append(float(np.median(b)))
+            for k, v in runs.items():
+                row[f"us_per_call_{k}_runs"] = [r * 1e6 for r in v]
+                row[f"us_per_frame_{k}"] = float(np.median(v)) * 1e6 / T
+            row["scan_over_step_multi"] = float(np.median(runs["scan"]) / np.median(runs["step_multi"]))
+            out.append(row)
+            eng.synchronize()
+            for s in slots:
+                eng.close_stream(int(s))
+    eng.close()
+    return out
+
+
 def single_stream_wrapper():
     """configs[0]: ONE stream through the drop-in VADWrapper (host framing + one launch + sync + callbacks per chunk)."""
     import time

@@ -80,6 +80,40 @@ extern "C" hipError_t vadk_launch_silero_v4(const StepParams *p, hipStream_t) { 
 extern "C" hipError_t vadk_launch_silero_v5_t16(const StepParams *p, hipStream_t) { return fake_step(p, 512); }
 extern "C" hipError_t vadk_launch_silero_v4_t16(const StepParams *p, int, hipStream_t) { return fake_step(p, 512); }
 
+// whole recordings (csrc/silero_v5_t16.hip: silero_v5_scan16), the same rule as fake_step: p = |first sample of the frame|, the
+// real state machine, a float32 frame with a NaN / Inf sample rejected; a stream past its recording's end is held (nothing
+// stepped, nothing written).  The "frames" are addressed as the kernel addresses them: sample 4 (quad0 + t hopq) of the block.
+extern "C" hipError_t vadk_launch_silero_v5_scan16(const StepParams *p, const ScanItem *items, const ScanArgs *a, hipStream_t) {
+    const int frame_samples = p->variant ? 256 : 512;
+    for (int i = 0; i < p->n; ++i) {
+        const ScanItem &it = items[i];
+        SmSlot &s = p->sm[it.slot];
+        for (int t = a->t0; t < a->t0 + p->T && t < it.nframes; ++t) {
+            const size_t first = 4 * ((size_t)it.quad0 + (size_t)t * a->hopq), o = (size_t)it.out0 + (size_t)t;
+            bool bad = false;
+            if (p->fmt == VAD_FMT_F32)
+                for (int k = 0; k < frame_samples; ++k) bad = bad || !std::isfinite(static_cast<const float *>(p->frames)[first + k]);
+            if (bad) {
+                p->probs[o] = std::nanf("");
+                if (p->events) p->events[o] = (uint8_t)EV_REJECTED;
+                if (p->seg_frames) p->seg_frames[o] = 0;
+                continue;
+            }
+            // (first_sample indexes frames of `stride` samples: a stride of one sample addresses the block itself)
+            float x = first_sample(p->frames, first, p->fmt, 1);
+            if (p->thresh >= 0.f && !(std::fabs(x) > p->thresh)) x = 0.f;
+            const float prob = std::fmin(1.0f, std::fabs(x));
+            int sg = 0;
+            const int ev = sm_step(s, prob, &sg);
+            p->probs[o] = prob;
+            if (p->events) p->events[o] = (uint8_t)ev;
+            if (p->seg_frames) p->seg_frames[o] = (ev & 2) ? sg : 0;
+            p->state[(size_t)it.slot * 256] += 1.0f;
+        }
+    }
+    return hipSuccess;
+}
+
 extern "C" hipError_t vadk_launch_silero_v5_t16_rates(const StepParams *p, const RateParams *r, hipStream_t) {
     for (int k = 0; k < r->nseg; ++k) {
         StepParams q = *p;
