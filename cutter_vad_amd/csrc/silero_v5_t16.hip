@@ -41,8 +41,31 @@ using namespace vadk;
     do {                                                                                           \
         if (lane == 0) P.stamps[((size_t)blockIdx.x * NWAVES + w) * 32 + (k)] = clock64();          \
     } while (0)
+template <class V>
+__device__ __forceinline__ void stamp_wait(V v) {
+    if constexpr (sizeof(V) == 4) asm volatile("" ::"v"(v) : "memory");
+    else asm volatile("" ::"v"(v.x) : "memory");
+}
+// in front of the stamp, v has arrived in its registers | every memory operation of the wave is acknowledged
+// (not in the fused resampler's entry: its build with these stamps does not get through the register allocator)
+#define STAMP_ON(k, v)                                                                             \
+    do {                                                                                           \
+        if constexpr (!RS) {                                                                       \
+            stamp_wait(v);                                                                         \
+            STAMP(k);                                                                              \
+        }                                                                                          \
+    } while (0)
+#define STAMP_DRAIN(k)                                                                             \
+    do {                                                                                           \
+        if constexpr (!RS) {                                                                       \
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                       \
+            STAMP(k);                                                                              \
+        }                                                                                          \
+    } while (0)
 #else
 #define STAMP(k) do { } while (0)
+#define STAMP_ON(k, v) do { } while (0)
+#define STAMP_DRAIN(k) do { } while (0)
 #endif
 using namespace vadk::dev;
 

@@ -32,6 +32,7 @@
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if constexpr (!RS) STAMP(19);                 // kernel entry
     const int n = lane & 15;                      // stream of this lane's MFMA column
     const int kq = lane >> 4;                     // channel group (B operand) = row quad of the D tile
     const int nq = kq * QSD + n;                  // lane's offset inside a group of 4 quad rows (dense view)
@@ -94,13 +95,23 @@
     const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void *>(KP(frames)), 0,
         SCAN ? (int)S.audio_bytes : (int)((unsigned)KP(n) * (unsigned)T * ((f32in ? 2048u : G711 ? 512u : 1024u) >> (K8 ? 1 : 0))), 0x00020000);
+    // The frames are read once and are two thirds of what a one-frame launch fetches (8 192 streams: 16.8 MB beside 9 MB of state):
+    // requested non-temporal, they stream past the L2 lines that hold the state and the weights
+    // (16 kHz model; the 8 kHz sub-model's loader is what it was: at 8 192 streams it measured 1.2 us slower with this and the late
+    //  request below, once - profiles/r09_launch_ends_other_configs.jsonl)
+    constexpr int X_NT = K8 ? 0 : 2;               // the buffer loads' cache policy bits: nt
     // one quad of raw samples: 16 bytes (float32; int16 uses the first 8), G.711: the quad is one dword, fetched as such
     using XQ = std::conditional_t<G711, uint32_t, u32x4>;
     auto x_load = [&](int off) -> XQ {
-        if constexpr (G711) return __builtin_amdgcn_raw_buffer_load_b32(frs, off, 0, 0);
-        else return __builtin_amdgcn_raw_buffer_load_b128(frs, off, 0, 0);
+        if constexpr (G711) return __builtin_amdgcn_raw_buffer_load_b32(frs, off, 0, X_NT);
+        else return __builtin_amdgcn_raw_buffer_load_b128(frs, off, 0, X_NT);
     };
     XQ xa_[4], xb_[4], xc_[4];                     // raw quads of the three columns
+    // 16 kHz, frames from memory: column c + 1's quads k = 0, 1 ARE column c's k = 2, 3, in the same thread - they are requested and
+    // decoded once, by column c, and X_FOLD hands them on decoded (RS reads its columns from LDS and keeps all four; 8 kHz: the
+    // next column belongs to another thread)
+    constexpr bool XCARRY = !RS && !K8;
+#define X_K0(c) ((XCARRY && (c) > 0) ? 2 : 0)
     f32x4 *const F4 = lds + T_LDS_F4;              // RS: the tile's resampled frames
     // SCAN: frame tt of the launch, for the loader's stream, starts at quad xq0 + tt hopq of the audio block - frames overlap in
     // memory when hop < frame, nothing is copied.  Unsigned: a stream past its end keeps walking (into its neighbour's samples, or
@@ -116,11 +127,11 @@
             XR[k] = __builtin_bit_cast(u32x4, F4[(tid >> 4) * FQ + 32 * (c) + q + 16 * k]);                     \
     } else if constexpr (SCAN) {                                                                                \
         const uint32_t fq = xq0 + (uint32_t)(tt) * S.hopq + 32 * (c) + q;                                       \
-        _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                           \
+        _Pragma("unroll") for (int k = X_K0(c); k < 4; ++k)                                                     \
             XR[k] = x_load((int)((fq + 16 * k) << qsh));                                                        \
     } else {                                                                                                    \
         const int fq = ((tile0 + (tid >> 4)) * T + (tt)) * 128 + 32 * (c) + q;                                  \
-        _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                           \
+        _Pragma("unroll") for (int k = X_K0(c); k < 4; ++k)                                                     \
             XR[k] = x_load((fq + 16 * k) << qsh);                                                               \
     }
 
@@ -212,10 +223,10 @@
     //      c_{t-1} -> registers, state machines -> LDS ----
     // Request order = the order in which the frame loop needs things (vmcnt retires in issue order): h, the wave's gate biases
     // (compact: 128 floats, kept in LDS for the call) and the tile's state machines (their 16 threads only), then - not RS, where
-    // a whole resampling phase sits in front of the frame loop - the frame loop's first requests: the W_hh blocks of its first two
-    // groups and the frame's first two columns depend on kernel arguments only, and W_hh is the coldest part of the weight
-    // stream; then the window and c.  Streams past n (the last tile's tail) read slot 0's state and compute on it: a stream is
-    // a column of every MFMA, nothing crosses columns, and every store of the kernel is guarded by `live`.
+    // a whole resampling phase sits in front of the frame loop - the frame loop's first weight requests: the W_hh blocks of its
+    // first units depend on kernel arguments only, and W_hh is the coldest part of the weight stream; then the window and c, and
+    // behind the wait for h the frame's first two columns (below).  Streams past n (the last tile's tail) read slot 0's state and
+    // compute on it: a stream is a column of every MFMA, nothing crosses columns, and every store of the kernel is guarded by `live`.
     f32x4 hv[2];                                   // (tid & 15 == n: ONE slot lookup serves h, c and the state machine)
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt) hv[rt] = *reinterpret_cast<const f32x4 *>(KP(state) + (size_t)slot * 256 + 32 * w + 16 * rt + 4 * kq);
@@ -237,15 +248,20 @@
 #define X3_LD(B, u) X3_LDR((B) + 3 * (u), (u))
 #define X3_LDX(blk, slot) _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) xw[(slot) % X3_NR][p_] = WX((blk) + p_);
 #define X3_LDY(blk, slot) _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) xw[(slot) % X3_NR][p_] = WY((blk) + p_);
-#define H_FIRST(L, tt)                                                                                          \
+#define H_FIRSTX(tt)                                                                                            \
     {                                                                                                           \
-        _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LD((L) + LSTM_X3_HALF_BLOCKS, u_) }             \
         if constexpr (K8) { X_ISSUE8(0, xa_, tt) X_ISSUE8(2, xb_, tt) }                                         \
         else { X_ISSUE(0, xa_, tt) X_ISSUE(1, xb_, tt) }                                                        \
+    }
+#define H_FIRST(L, tt, WITHX)                                                                                   \
+    {                                                                                                           \
+        _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LD((L) + LSTM_X3_HALF_BLOCKS, u_) }             \
+        if constexpr (WITHX) H_FIRSTX(tt)                                                                       \
         SB();                                                                                                   \
         if constexpr (RS) { X_ISSUE(2, xc_, tt) SB(); }                                                         \
     }
-    if constexpr (!RS) H_FIRST(o_x3, 0)            // frames t > 0 request theirs at the end of frame t - 1; RS: at the top of the frame
+    if constexpr (!RS) STAMP(29);
+    if constexpr (!RS) H_FIRST(o_x3, 0, K8)        // frames t > 0 request theirs at the end of frame t - 1; RS: at the top of the frame
     const f32x4 W1 = ldw(wrs, q * 16, o_nyq), W3 = ldw(wrs, (2 * QL + q) * 16, o_nyq);   // w[n], w[128 + n]  (8 kHz: w[64 + n])
     const float w64 = ldw(wrs, QL * 16, o_nyq).x;                                          // w[64]             (8 kHz: w[32])
     f32x4 cst[2];                                  // c of units 32 w + 16 rt + 4 kq + i
@@ -264,7 +280,13 @@
         }
     }
     SB();
+    STAMP_ON(30, hv[1]);                           // h has arrived
     st_planes(RH + 12 * w * QSD + nq, hv[0], hv[1]);
+    // The call's first frame is requested HERE, behind the wait for h, and not with the first weight blocks: with two tiles per CU all
+    // asking at once the memory system serves the launch's first requests roughly in order (8 192 streams: h arrives 7.5 k cycles
+    // after kernel entry, 3.0 k at 4 096), and the frame's 32 KB per tile in front of h and c only delay what the first MFMAs wait
+    // for; the first fold is 15 units of MFMAs away.  Same box: 36.81 -> 36.54 us per headline step.
+    if constexpr (!RS && !K8) { SB(); H_FIRSTX(0) SB(); }
     reinterpret_cast<decltype(bias2) *>(biasL + 32 * w)[lane] = bias2;
     int seg_last = 0;
     if (tid < MT16) {
@@ -609,6 +631,7 @@
         f32x4 G[8];                               // gate q, row tile rt -> G[2 q + rt]
         {
             const int wh = ws_x3 + LSTM_X3_HALF_BLOCKS;
+            f32x4 xcA, xcB;                       // XCARRY: the decoded quads k = 2, 3 of the column folded last
             float xm = 0.f;                       // float32: running max |x| of this thread's raw samples (vadk_device.h absmax4)
             auto decode = [&](XQ b) -> f32x4 {
                 f32x4 v;
@@ -644,11 +667,16 @@
                 return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x108, 0xf, 0xf, true));
             };
             // the fold of silero_v5.hip, one call per column: stream ms = tid >> 4, n = 4 q + j
-#define X_FOLD(c, XR)                                                                                           \
+#define X_FOLD(c, XR, NEXT)                                                                                     \
     {                                                                                                           \
         _Pragma("clang fp contract(off)")                                                                       \
         const int ms = lms;                                                                                     \
-        const f32x4 xA = decode(XR[0]), xB = decode(XR[1]), xC = decode(XR[2]), xD = decode(XR[3]);             \
+        STAMP_ON(20 + (NEXT), XR[3]);                                                                           \
+        f32x4 xA, xB;                                                                                           \
+        if constexpr (XCARRY && (NEXT)) { xA = xcA; xB = xcB; }                                                 \
+        else { xA = decode(XR[0]); xB = decode(XR[1]); }                                                        \
+        const f32x4 xC = decode(XR[2]), xD = decode(XR[3]);                                                     \
+        if constexpr (XCARRY) { xcA = xC; xcB = xD; }                                                           \
         const float mBx = mirror(xB.x), mDx = mirror(xD.x);                                                     \
         const f32x4 y1 = pk::mul(xA, W1), y3 = pk::mul(xC, W3);                                                 \
         const f32x4 y2 = pk::mul(f32x4{shr1(xC.x, mBx), mirror(xB.w), mirror(xB.z), mirror(xB.y)}, W3);         \
@@ -692,7 +720,7 @@
         __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);                                                      \
         __builtin_amdgcn_sched_group_barrier(0x002, 28, 0);                                                     \
     }
-            if constexpr (RS) H_FIRST(ws_x3, t)                 // F is dead once every wave has passed the barrier below
+            if constexpr (RS) H_FIRST(ws_x3, t, true)           // F is dead once every wave has passed the barrier below
             {   // the accumulators start at the gate biases: G[2 q + rt] register i of a lane = unit 16 rt + 4 kq + i of gate q (the
                 // 16 lanes of a row group read the same 16 bytes: a broadcast).  The wave reads what the wave itself wrote.
                 const f32x4 *const bq = biasL + 32 * w + kq;
@@ -705,9 +733,9 @@
             // of K-steps 1, 2, 3 (8 kHz: two fold calls, columns (0 | 1) by half of the workgroup, then column 2, in K-steps 1, 2)
 #define H_EXTRA(u)                                                                                              \
             if constexpr ((u) == 2 && !RS && !K8) { X_ISSUE(2, xc_, t) }                                        \
-            if constexpr ((u) == 15) { if constexpr (K8) { X_FOLD(lcol, xa_) } else { X_FOLD(0, xa_) } H_MIX }   \
-            if constexpr ((u) == 23) { if constexpr (K8) { X_FOLD(2, xb_) X_FLAG } else { X_FOLD(1, xb_) } H_MIX }   \
-            if constexpr ((u) == 31 && !K8) { X_FOLD(2, xc_) X_FLAG H_MIX }
+            if constexpr ((u) == 15) { if constexpr (K8) { X_FOLD(lcol, xa_, 0) } else { X_FOLD(0, xa_, 0) } H_MIX }   \
+            if constexpr ((u) == 23) { if constexpr (K8) { X_FOLD(2, xb_, 1) X_FLAG } else { X_FOLD(1, xb_, 1) } H_MIX }   \
+            if constexpr ((u) == 31 && !K8) { X_FOLD(2, xc_, 2) X_FLAG H_MIX }
 #define H_FOLDREGION(u) (((u) & 7) >= 5 && (u) >= 8 && ((u) < 24 || !K8))
             X3_HALF(wh, RH, H_EXTRA, H_FOLDREGION)
 #undef H_EXTRA
@@ -1046,9 +1074,10 @@
             }
         }
         if (++t >= T) break;
-        if constexpr (!RS) H_FIRST(ws_x3, t)       // the next frame's first requests
+        if constexpr (!RS) H_FIRST(ws_x3, t, true) // the next frame's first requests
     }
 #undef H_FIRST
+#undef H_FIRSTX
 #undef X3_LD
 #undef X3_LDR
 #undef X3_LDX
@@ -1056,6 +1085,9 @@
 #undef WY
 #undef WX
 #undef X_ISSUE
+#undef X_K0
 #undef WL
     if constexpr (!SCAN) { if (sm_thread && P.seg_frames) P.seg_frames[gf] = seg_last; }
+    if constexpr (!RS) STAMP(27);                 // the wave's last store is issued ...
+    STAMP_DRAIN(28);                              // ... and acknowledged
 #undef KP

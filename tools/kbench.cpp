@@ -180,9 +180,16 @@ int main(int argc, char **argv) {
         }
         double l1 = 0, l2 = 0, l3 = 0;
         for (int b = 0; b < tiles; ++b) { l1 += (double)(S(b, w, 16) - S(b, w, 2)); l2 += (double)(S(b, w, 17) - S(b, w, 4)); l3 += (double)(S(b, w, 18) - S(b, w, 12)); }
+#ifdef KB_TILE16      // the 16-stream body stamps the end of the LSTM's main loop only, and one ingest group per STFT column
+        printf("  total=%.0f | mainloops: lstm=%.0f\n", tot, l3 / tiles);
+        const int ngroups = 3;
+        printf("        ingest groups (a column's quads have arrived, in front of its fold; cycles since frame start):");
+#else
         printf("  total=%.0f | mainloops: stft=%.0f enc0=%.0f lstm=%.0f\n", tot, l1 / tiles, l2 / tiles, l3 / tiles);
+        const int ngroups = 8;
         printf("        ingest groups (cycles since frame start):");
-        for (int k = 20; k < 28; ++k) {
+#endif
+        for (int k = 20; k < 20 + ngroups; ++k) {
             double acc = 0;
             for (int b = 0; b < tiles; ++b) acc += (double)(S(b, w, k) - S(b, w, 0));
             printf(" g%d=%.0f", k - 20, acc / tiles);
@@ -195,11 +202,20 @@ int main(int argc, char **argv) {
         for (int b = 0; b < tiles; ++b) {
             a29 += (double)(S(b, w, 29) - S(b, w, 19)); a30 += (double)(S(b, w, 30) - S(b, w, 19)); a31 += (double)(S(b, w, 31) - S(b, w, 19));
         }
+#ifdef KB_TILE16
+        {   // every wave: barrier (8) -> its last store issued (27) -> all its stores acknowledged (28)
+            double ti = 0, ta = 0;
+            for (int b = 0; b < tiles; ++b) { ti += (double)(S(b, w, 27) - S(b, w, 15)); ta += (double)(S(b, w, 28) - S(b, w, 27)); }
+            printf("        tail: barrier (8) -> last store issued = %.0f, -> stores acknowledged = +%.0f;  kernel entry -> end = %.0f\n", ti / tiles,
+                   ta / tiles, pro / tiles + tot + (ti + ta) / tiles);
+        }
+#else
         if (w == 0 && S(0, 0, 28)) {
             double tl = 0;
             for (int b = 0; b < tiles; ++b) tl += (double)(S(b, 0, 28) - S(b, 0, 15));
             printf("        head + state machine (32 lanes of wave 0, behind barrier (8)) = %.0f\n", tl / tiles);
         }
+#endif
         if (S(0, w, 29)) printf("        since kernel entry: all first requests issued %.0f, h in LDS %.0f, past barrier (0) %.0f\n", a29 / tiles, a30 / tiles, a31 / tiles);
     }
 #endif
