@@ -55,6 +55,19 @@ def make_engine(lib):
         e.close()
 
 
+@pytest.fixture(scope="module")
+def rate_engine(make_engine):
+    """one engine per sample rate for the cases that open their slots, scan and close them again"""
+    made = {}
+
+    def get(rate):
+        if rate not in made:
+            made[rate] = make_engine(rate=rate)
+        return made[rate]
+
+    return get
+
+
 def _raw(lib, eng, items, audio, fmt, hop, out_start, audio_samples=None, n_out=None, fill=None, device=False):
     """vad_scan (or vad_scan_device: the stand-in's device memory is host memory) -> (rc, message, probs, events, seg)"""
     arr = (_ffi.ScanItem * max(1, len(items)))(*[_ffi.ScanItem(*map(int, it)) for it in items])
@@ -151,12 +164,13 @@ def test_refusals_have_a_status_and_a_message(lib, make_engine):
         assert (probs == np.float32(-7.0)).all()
 
 
-def _ragged(frame, hop, kind, seed):
-    """37 recordings (the last tile is partial) with 0, 1 and up to 23 frames, in no order of length; every frame's first sample
-    is its own scripted value.  -> (recordings, per recording the probabilities the stand-in gives)"""
+def _ragged(frame, hop, kind, seed, counts=None):
+    """37 recordings (the last tile is partial) with 0, 1 and up to 23 frames, in no order of length (or the frame counts given);
+    every frame's first sample is its own scripted value.  -> (recordings, per recording the probabilities the stand-in gives)"""
     rng = np.random.default_rng(seed)
-    counts = [0, 1, 0, 23, 2, 1] + [int(c) for c in rng.integers(0, 20, 31)]
-    assert len(counts) == 37
+    if counts is None:
+        counts = [0, 1, 0, 23, 2, 1] + [int(c) for c in rng.integers(0, 20, 31)]
+        assert len(counts) == 37
     recs, want = [], []
     for i, c in enumerate(counts):
         ns = (frame + (c - 1) * hop + int(rng.integers(0, hop))) if c else int(rng.integers(0, frame))
@@ -175,12 +189,13 @@ def _ragged(frame, hop, kind, seed):
     return recs, want
 
 
-@pytest.mark.parametrize("cap", [1, 3, 0])
-@pytest.mark.parametrize("kind", list(FMT))
-def test_ragged_batch_lands_at_the_callers_csr_positions(lib, make_engine, kind, cap):
-    eng = make_engine()
-    frame, hop = eng.frame_samples, eng.frame_samples // 2
-    recs, want = _ragged(frame, hop, kind, seed=len(kind) + cap)
+HOPS = {"half": lambda f: f // 2, "hop4": lambda f: 4, "quarter4": lambda f: f // 4 + 4, "frame4": lambda f: f + 4,
+        "16frames4": lambda f: 16 * f + 4}
+
+
+def _scan_and_check(eng, recs, want, hop, kind, cap, launches):
+    """eng.scan(recs) on fresh slots under launch cap `cap`: the stand-in's probabilities at the CSR positions, every stream
+    stepped once per frame of its own recording, `launches` launches and sum(counts) frames on the engine's counters"""
     slots = eng.open_streams(len(recs))
     eng.set_scan_launch_frames(cap)
     try:
@@ -188,17 +203,109 @@ def test_ragged_batch_lands_at_the_callers_csr_positions(lib, make_engine, kind,
         law = kind if kind in G.LAWS else None
         probs, ev, seg = eng.scan(slots, recs, hop=hop, law=law, i16_scale=32768 if kind == "i16_32768" else 32767, denoise=None)
         after = eng.info()
+        assert len(probs) == len(recs)
         for i in range(len(recs)):
             assert np.array_equal(probs[i], want[i]), (i, probs[i], want[i])
             assert ev[i].shape == want[i].shape and seg[i].shape == want[i].shape
-            # the stand-in's "h" counts the frames a stream has seen: none past the recording's end
-            assert eng.get_state(int(slots[i]))[0] == want[i].size
-        longest = max(w.size for w in want)
-        per = cap if cap else 192
-        assert after["steps"] - before["steps"] == -(-longest // per)
+        # the stand-in's "h" counts the frames a stream has seen: none past the recording's end
+        seen = [eng.get_state(int(s))[0] for s in slots]
+        assert seen == [w.size for w in want]
+        assert after["steps"] - before["steps"] == launches
         assert after["frames"] - before["frames"] == sum(w.size for w in want)
     finally:
         eng.set_scan_launch_frames(0)
+        for s in slots:
+            eng.close_stream(int(s))
+
+
+def _ragged_cases():
+    """every format x launch caps 1, 3 and the default, at every hop the argument check has a path for and both sub-models (the
+    cases at 16 kHz and hop = frame / 2 keep the ids they had before the hop and the rate became parameters)"""
+    out = []
+    for rate in (16000, 8000):
+        for hop_name in HOPS:
+            for kind in FMT:
+                for cap in (1, 3, 0):
+                    first = rate == 16000 and hop_name == "half"
+                    out.append(pytest.param(kind, cap, rate, hop_name, id=f"{kind}-{cap}" if first else f"{kind}-{cap}-{rate}-{hop_name}"))
+    return out
+
+
+@pytest.mark.parametrize("kind,cap,rate,hop_name", _ragged_cases())
+def test_ragged_batch_lands_at_the_callers_csr_positions(lib, rate_engine, kind, cap, rate, hop_name):
+    eng = rate_engine(rate)
+    frame = eng.frame_samples
+    hop = HOPS[hop_name](frame)
+    recs, want = _ragged(frame, hop, kind, seed=len(kind) + cap)
+    longest = max(w.size for w in want)
+    per = cap if cap else 192
+    _scan_and_check(eng, recs, want, hop, kind, cap, -(-longest // per))
+
+
+@pytest.mark.parametrize("hop_name", ["hop4", "quarter4"])
+@pytest.mark.parametrize("rate", [16000, 8000])
+def test_default_cap_cuts_385_frames_into_three_launches(lib, rate_engine, rate, hop_name):
+    """the product's own windows t0 = 0, 192, 384: recordings that end exactly on a window's edge (192, 384), one frame behind it
+    (193, 385) and far in front of it"""
+    eng = rate_engine(rate)
+    frame = eng.frame_samples
+    hop = HOPS[hop_name](frame)
+    counts = [0, 1, 193, 2, 385, 192, 384, 40, 0, 17, 191, 33, 3, 385, 5, 194, 8, 1, 29, 383]
+    recs, want = _ragged(frame, hop, "f32", seed=41, counts=counts)
+    _scan_and_check(eng, recs, want, hop, "f32", 0, 3)
+
+
+def test_4100_recordings_on_16_stream_tiles(lib, make_engine):
+    """more recordings WITH a frame than any other multi-frame path keeps on 16-stream tiles: a launch covers the recordings that
+    still have frames in its window, so 4 100 of them are 257 tiles, the last one with 4 streams; 8 more have no frame"""
+    eng = make_engine(max_streams=8192)
+    frame = eng.frame_samples
+    hop = frame // 4 + 4
+    rng = np.random.default_rng(43)
+    counts = [int(c) for c in rng.integers(1, 7, 4100)]
+    for k in rng.choice(4100, 8, replace=False):
+        counts.insert(int(k), 0)
+    assert set(counts) == set(range(7)) and sum(c > 0 for c in counts) == 4100 > 4096
+    recs, want = _ragged(frame, hop, "f32", seed=44, counts=counts)
+    for cap in (0, 2):
+        _scan_and_check(eng, recs, want, hop, "f32", cap, -(-6 // (cap or 192)))
+
+
+def test_a_batch_without_frames_launches_nothing_and_touches_nothing(lib, make_engine):
+    """recordings that all have 0 frames, and n = 0: VAD_OK, no launch, the outputs and every stream's state as they were"""
+    eng = make_engine()
+    frame, hop = eng.frame_samples, eng.frame_samples // 4 + 4
+    rng = np.random.default_rng(47)
+    slots = eng.open_streams(5)
+    try:
+        eng.set_thresholds_many(slots, (0.5, 0.5, 0.8, 0.95, 2, 2))
+        for _ in range(3):                                 # a history: neither (h, c) nor the state machine is the fresh one
+            eng.step(slots, rng.uniform(0.6, 0.9, (5, frame)).astype(np.float32), denoise=None)
+        saved = [eng.save_stream(int(s)) for s in slots]
+        state = [eng.get_state(int(s)).copy() for s in slots]
+        assert all(st[0] == 3 for st in state)
+        steps = eng.info()["steps"]
+        frames = eng.info()["frames"]
+        lens = [0, frame - 1, 17, frame - 4, 3]
+        audio = rng.uniform(0.5, 0.9, 4 * frame).astype(np.float32)
+        offs = np.concatenate([[0], np.cumsum([(n + 3) & ~3 for n in lens[:-1]])])
+        items = [(int(s), int(o), n) for s, o, n in zip(slots, offs, lens)]
+        for device in (False, True):
+            rc, msg, probs, ev, seg = _raw(lib, eng, items, audio, FMT["f32"], hop, [0] * 6, n_out=9, device=device)
+            assert rc == _ffi.VAD_OK, msg
+            assert (probs == np.float32(-7.0)).all() and (ev == 0x55).all() and (seg == -9).all()
+            rc, msg, probs, ev, seg = _raw(lib, eng, [], audio, FMT["f32"], hop, [0], n_out=9, device=device)
+            assert rc == _ffi.VAD_OK, msg
+            assert (probs == np.float32(-7.0)).all() and (ev == 0x55).all() and (seg == -9).all()
+        got = eng.scan(slots, [audio[o:o + n] for o, n in zip(offs, lens)], hop=hop, denoise=None)
+        assert all(len(part) == 5 and all(a.size == 0 for a in part) for part in got)
+        got = eng.scan([], [], hop=hop)
+        assert got == ([], [], [])
+        assert eng.info()["steps"] == steps and eng.info()["frames"] == frames
+        assert [eng.save_stream(int(s)) for s in slots] == saved
+        for s, st in zip(slots, state):
+            assert np.array_equal(eng.get_state(int(s)), st)
+    finally:
         for s in slots:
             eng.close_stream(int(s))
 
@@ -307,6 +414,57 @@ def test_speech_segments_on_hand_built_arrays():
     assert speech_segments(np.zeros(0, np.uint8), np.zeros(0, np.int32), 512, 256) == []
     rej = np.array([_ffi.VAD_EV_REJECTED, 4 | E], np.uint8)
     assert speech_segments(rej, np.array([0, 2], np.int32), 512, 256) == [(0, 768)]
+
+
+@pytest.mark.parametrize("rate", [16000, 8000])
+def test_segments_at_a_hop_longer_than_the_frame(lib, make_engine, rate):
+    """hop = frame + 4: 4 samples between consecutive frames belong to none.  Each range is [(e - L + 1) hop, e hop + frame) and
+    lies inside its recording - on hand-built event arrays, and from scan_recordings on scripted audio"""
+    from cutter_vad_amd import VADConfig
+    from cutter_vad_amd.scan import scan_recordings
+    E, S = _ffi.VAD_EV_END, _ffi.VAD_EV_START
+    frame = 512 if rate == 16000 else 256
+    hop = frame + 4
+    ev = np.array([0, S, 4, 4, 4 | E, 0, S, 4, 4 | E], np.uint8)
+    seg = np.array([0, 0, 0, 0, 4, 0, 0, 0, 3], np.int32)
+    ns = frame + 8 * hop + 3                            # a recording of 9 frames and a tail
+    got = speech_segments(ev, seg, frame, hop)
+    assert got == [(hop, 4 * hop + frame), (6 * hop, 8 * hop + frame)]
+    assert all(0 <= a < b <= ns for a, b in got)
+    assert got[1][1] == ns - 3                          # the last frame's last sample: the tail is in no segment
+
+    eng = make_engine(rate=rate)
+    assert eng.frame_samples == frame
+    scripts = [np.array([0.0] * 3 + [0.9] * 6 + [0.0] * 5 + [0.9] * 4 + [0.0] * 4 + [0.9] * 2, np.float32),
+               np.array([0.9] * 5, np.float32), np.zeros(0, np.float32), np.array([0.9] * 4 + [0.0] * 3, np.float32)]
+    recs = []
+    for k, s in enumerate(scripts):
+        x = np.zeros(frame + (s.size - 1) * hop + k if s.size else 9, np.float32)
+        x[:s.size * hop:hop] = s                        # the stand-in's p = |first sample of the frame|
+        recs.append(x)
+    cfg = VADConfig(sample_rate=rate, buffer_size=frame, vad_start_probability=0.5, vad_end_probability=0.5,
+                    voice_start_frame_count=2, voice_end_frame_count=2, enable_denoising=False)
+    got = scan_recordings(recs, cfg, engine=eng, hop=hop)
+    slot = eng.open_streams(1)
+    try:
+        eng.set_thresholds_many(slot, (0.5, 0.5, 0.8, 0.95, 2, 2))
+        want = []
+        for s in scripts:
+            eng.reset(slot)
+            eng.set_thresholds_many(slot, (0.5, 0.5, 0.8, 0.95, 2, 2))
+            if s.size == 0:
+                want.append([])
+                continue
+            ev_r, seg_r = eng.debug_sm_replay(int(slot[0]), s)
+            ends = np.flatnonzero(ev_r & E)
+            want.append([((int(e) - int(seg_r[e]) + 1) * hop, int(e) * hop + frame) for e in ends])
+    finally:
+        eng.close_stream(int(slot[0]))
+    assert got == want
+    assert [len(g) for g in got] == [2, 0, 0, 1], got
+    for x, segs in zip(recs, got):
+        for a, b in segs:
+            assert 0 <= a < b <= x.size and a % hop == 0 and (b - frame) % hop == 0
 
 
 def _hipcc():
