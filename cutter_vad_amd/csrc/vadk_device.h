@@ -227,9 +227,11 @@ __device__ __forceinline__ f32x4 mfma_x3(const f32x4 *W, const u32x4 *X, f32x4 a
 }
 
 // (float) s / d for an int16 s and d = 32767 or 32768, bit for bit the IEEE quotient that numpy's true division gives
-// (vad_websocket_server.py:341): q = s * r with r = float(1 / d), then one Newton correction in two fmas.  Exhaustively equal over
-// all 65 536 values of s (tools/i16_division_check.py, tests/test_host_logic.py); 3 instructions instead of the ~10 of the
-// v_div_scale / v_rcp / v_div_fmas / v_div_fixup sequence - 64 samples per thread in the V5 kernel.
+// (vad_websocket_server.py:341): q = s * r with r = float(1 / d), then one Newton correction in two fmas.  The FORMULA is
+// exhaustively equal over all 65 536 values of s (tools/i16_division_check.py, tests/test_host_logic.py: exact rationals on the
+// CPU); the COMPILED code of every loader is held to it by tests/test_gpu_gate_edges.py, which gates at |s / d| itself for the 768
+// magnitudes that q alone mis-rounds for d = 32767.  3 instructions instead of the ~10 of the v_div_scale / v_rcp / v_div_fmas /
+// v_div_fixup sequence - 64 samples per thread in the V5 kernel.
 __device__ __forceinline__ float i16_div(int s, float d, float r) {
     const float x = (float)s;
     const float q = x * r;
