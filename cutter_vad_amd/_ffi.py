@@ -116,6 +116,13 @@ class ScanItem(C.Structure):
     _fields_ = [("slot", C.c_int64), ("sample_offset", C.c_int64), ("nsamples", C.c_int64)]
 
 
+class ScanChItem(C.Structure):
+    _fields_ = [("slot", C.c_int64), ("sample_offset", C.c_int64), ("nsamples", C.c_int64), ("channel", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+VAD_SCAN_MIX = -1
+
 VAD_WORK_START, VAD_WORK_END, VAD_WORK_CONTINUE, VAD_WORK_PAYLOAD, VAD_WORK_LONG = 1, 2, 4, 8, 16
 VAD_WORK_REJECTED = 32
 
@@ -189,6 +196,10 @@ SIGNATURES = {
                            _f32p, _u8p, _i32p]),
     "vad_scan_device": (C.c_int, [_vp, C.POINTER(ScanItem), C.c_int64, _vp, C.c_int64, C.c_int, C.c_int32, C.c_float, _i64p,
                                   _vp, _vp, _vp, _vp]),
+    "vad_scan_channels": (C.c_int, [_vp, C.POINTER(ScanChItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_float,
+                                    _i64p, _f32p, _u8p, _i32p]),
+    "vad_scan_channels_device": (C.c_int, [_vp, C.POINTER(ScanChItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32,
+                                           C.c_float, _i64p, _vp, _vp, _vp, _vp]),
     "vad_debug_scan_launch_frames": (C.c_int, [_vp, C.c_int32]),
 }
 

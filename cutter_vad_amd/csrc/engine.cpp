@@ -1149,47 +1149,68 @@ int scan_wait(vad_engine *e) {
     return VAD_OK;
 }
 
+// what an item of either entry point asks for: vad_scan's items are the channel-0 case
+int32_t scan_item_channel(const vad_scan_item &) { return 0; }
+int32_t scan_item_reserved(const vad_scan_item &) { return 0; }
+int32_t scan_item_channel(const vad_scan_ch_item &it) { return it.channel; }
+int32_t scan_item_reserved(const vad_scan_ch_item &it) { return it.reserved; }
+
 // argument checks and the plan of a scan: e->scan_items = one work item per recording, sorted by frame count (stable, descending) so
 // that the 16 streams of a tile end together; out0 = out_start[i] - out_base.  *total = frames of all recordings.
-int scan_plan(vad_engine *e, const vad_scan_item *items, int64_t n, int64_t audio_samples, int fmt, int32_t hop,
+// `who` = the entry point's name in the messages; channels: the block's interleaved channels (vad_scan: 1) - offsets, lengths
+// and hop count sample frames, and an item's channel (or VAD_SCAN_MIX) travels in the top bits of its quad0 (vad_layout.h).
+template <class Item>
+int scan_plan(vad_engine *e, const char *who, const Item *items, int64_t n, int64_t audio_samples, int32_t channels, int fmt, int32_t hop,
               const int64_t *out_start, int64_t out_base, int64_t *total) {
     if (e->version != 5)
-        return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: vad_scan needs a Silero V5 engine; frame the recordings on the host and use vad_step_multi");
+        return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s needs a Silero V5 engine; frame the recordings on the host and use vad_step_multi", who);
     if (e->shared_gpu)
-        return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: vad_scan runs on 16-stream tiles, which a VAD_ENGINE_SHARED_GPU engine "
-                                            "does not use; frame the recordings on the host and use vad_step_multi");
-    if (!e->d_wstream16) return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: vad_scan: the engine has no 16-stream kernel; use vad_step_multi");
+        return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s runs on 16-stream tiles, which a VAD_ENGINE_SHARED_GPU engine "
+                                            "does not use; frame the recordings on the host and use vad_step_multi", who);
+    if (!e->d_wstream16) return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s: the engine has no 16-stream kernel; use vad_step_multi", who);
     if (n < 0 || audio_samples < 0 || (n > 0 && (!items || !out_start)))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: null buffer or bad count");
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer or bad count", who);
     if (fmt < VAD_FMT_F32 || fmt > VAD_FMT_ALAW8)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: unknown frame format %d", fmt);
+    if (channels != 1 && channels != 2)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: channels = %d, the block holds 1 or 2 interleaved channels", who, channels);
     if (n > e->max_streams)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: %lld recordings, max_streams = %d", (long long)n, e->max_streams);
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %lld recordings, max_streams = %d", who, (long long)n, e->max_streams);
     if (hop < 4 || (hop & 3))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: hop = %d must be a positive multiple of 4 samples", hop);
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: hop = %d must be a positive multiple of 4 samples", who, hop);
     // the kernel addresses the block through a 32-bit buffer descriptor
-    if ((uint64_t)audio_samples * sample_bytes(fmt) >= (1ull << 31))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: %llu bytes of audio exceed the 2 GiB one call may address",
-                       (unsigned long long)((uint64_t)audio_samples * sample_bytes(fmt)));
+    const uint64_t frame_bytes = (uint64_t)channels * sample_bytes(fmt);
+    if ((uint64_t)audio_samples >= (1ull << 31) || (uint64_t)audio_samples * frame_bytes >= (1ull << 31))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %llu bytes of audio exceed the 2 GiB one call may address", who,
+                       (unsigned long long)((uint64_t)audio_samples * frame_bytes));
     e->scan_items.resize((size_t)n);
     std::vector<int64_t> slots((size_t)n);
     int64_t sum = 0;
     for (int64_t i = 0; i < n; ++i) {
-        const vad_scan_item &it = items[i];
+        const Item &it = items[i];
         if (it.sample_offset < 0 || (it.sample_offset & 3))
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: recording %lld starts at sample %lld, not a multiple of 4",
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: recording %lld starts at sample %lld, not a multiple of 4", who,
                            (long long)i, (long long)it.sample_offset);
         if (it.nsamples < 0 || it.sample_offset > audio_samples || it.nsamples > audio_samples - it.sample_offset)
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: recording %lld (samples %lld .. +%lld) leaves the audio block of %lld samples",
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: recording %lld (samples %lld .. +%lld) leaves the audio block of %lld samples", who,
                            (long long)i, (long long)it.sample_offset, (long long)it.nsamples, (long long)audio_samples);
+        const int32_t ch = scan_item_channel(it);
+        if (ch != VAD_SCAN_MIX && (ch < 0 || ch >= channels))
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: recording %lld names channel %d of %d (0 .. channels - 1, or VAD_SCAN_MIX)", who,
+                           (long long)i, ch, channels);
+        if (scan_item_reserved(it) != 0)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: recording %lld: reserved = %d must be 0", who, (long long)i,
+                           scan_item_reserved(it));
         const int64_t nf = scan_frames(it.nsamples, e->frame_samples, hop);
         if (out_start[i] < out_base || out_start[i + 1] - out_start[i] != nf)
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: out_start gives recording %lld %lld entries, it has %lld frames",
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start gives recording %lld %lld entries, it has %lld frames", who,
                            (long long)i, (long long)(out_start[i + 1] - out_start[i]), (long long)nf);
         if (out_start[i + 1] - out_base > INT32_MAX)
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: more than 2^31 - 1 frames in one call");
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 frames in one call", who);
         slots[(size_t)i] = it.slot;
-        e->scan_items[(size_t)i] = vadk::ScanItem{(int32_t)it.slot, (uint32_t)(it.sample_offset >> 2), (int32_t)nf, (uint32_t)(out_start[i] - out_base)};
+        const uint32_t mode = channels == 1 ? vadk::SCAN_LEFT : ch == VAD_SCAN_MIX ? vadk::SCAN_MIX : (uint32_t)ch;
+        e->scan_items[(size_t)i] = vadk::ScanItem{(int32_t)it.slot, (uint32_t)(it.sample_offset >> 2) | (mode << vadk::SCAN_MODE_SHIFT), (int32_t)nf,
+                                                  (uint32_t)(out_start[i] - out_base)};
         sum += nf;
     }
     if (int rc = check_slots(e, slots.data(), n)) return rc;
@@ -1202,7 +1223,7 @@ int scan_plan(vad_engine *e, const vad_scan_item *items, int64_t n, int64_t audi
 // the launches of a planned scan (e->d_items holds e->scan_items): windows of at most scan_launch_frames frames, each over the
 // items that still have frames in it - a prefix of the sorted table.  State travels through HBM between them, as between two
 // vad_step_multi calls.
-int scan_launches(vad_engine *e, const void *d_audio, int64_t audio_samples, int fmt, int32_t hop, float thr, float *d_probs,
+int scan_launches(vad_engine *e, const void *d_audio, int64_t audio_samples, int32_t channels, int fmt, int32_t hop, float thr, float *d_probs,
                   uint8_t *d_events, int32_t *d_seg, int64_t total, hipStream_t s) {
     const std::vector<vadk::ScanItem> &it = e->scan_items;
     const int maxf = it.empty() ? 0 : it.front().nframes;
@@ -1223,8 +1244,9 @@ int scan_launches(vad_engine *e, const void *d_audio, int64_t audio_samples, int
     p.fmt = fmt;
     p.thresh = thr;
     vadk::ScanArgs a{};
-    a.audio_bytes = (uint32_t)((uint64_t)audio_samples * sample_bytes(fmt));
+    a.audio_bytes = (uint32_t)((uint64_t)audio_samples * (uint64_t)channels * sample_bytes(fmt));
     a.hopq = (uint32_t)hop >> 2;
+    a.channels = channels;
     size_t live = it.size();
     for (int t0 = 0; t0 < maxf; t0 += cap) {
         while (live > 0 && it[live - 1].nframes <= t0) --live;
@@ -1256,20 +1278,26 @@ int vad_debug_scan_launch_frames(vad_engine *e, int32_t frames) {
     return VAD_OK;
 }
 
-int vad_scan(vad_engine *e, const vad_scan_item *items, int64_t n, const void *audio, int64_t audio_samples, int frame_fmt,
-             int32_t hop, float denoise_thresh, const int64_t *out_start, float *probs_out, uint8_t *events_out,
-             int32_t *seg_frames_out) {
+}  // extern "C"
+
+namespace {
+
+// vad_scan and vad_scan_channels: the block crosses the link once, in its wire format, interleaved as it is
+template <class Item>
+int scan_host(vad_engine *e, const char *who, const Item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
+              int frame_fmt, int32_t hop, float denoise_thresh, const int64_t *out_start, float *probs_out, uint8_t *events_out,
+              int32_t *seg_frames_out) {
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
     HIP_TRY(e, hipSetDevice(e->device));
     if (int rc = scan_wait(e)) return rc;
     int64_t total = 0;
     const int64_t base = (n > 0 && out_start) ? out_start[0] : 0;
-    if (base < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: out_start[0] is negative");
-    if (int rc = scan_plan(e, items, n, audio_samples, frame_fmt, hop, out_start, base, &total)) return rc;
+    if (base < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start[0] is negative", who);
+    if (int rc = scan_plan(e, who, items, n, audio_samples, channels, frame_fmt, hop, out_start, base, &total)) return rc;
     if (total == 0) return VAD_OK;
-    if (!audio || !probs_out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan: null buffer");
-    const size_t ab = (size_t)audio_samples * sample_bytes(frame_fmt);
+    if (!audio || !probs_out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    const size_t ab = (size_t)audio_samples * (size_t)channels * sample_bytes(frame_fmt);
     if (int rc = ensure(e, e->d_audio, e->d_audio_cap, ab + 16)) return rc;
     if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
     if (int rc = ensure(e, e->d_probs, e->d_probs_cap, sizeof(float) * (size_t)total)) return rc;
@@ -1278,7 +1306,7 @@ int vad_scan(vad_engine *e, const vad_scan_item *items, int64_t n, const void *a
     // the audio crosses the link once, in its wire format
     HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, ab, hipMemcpyHostToDevice, e->stream));
-    if (int rc = scan_launches(e, e->d_audio, audio_samples, frame_fmt, hop, denoise_thresh, e->d_probs, e->d_events, e->d_seg, total, e->stream))
+    if (int rc = scan_launches(e, e->d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, e->d_probs, e->d_events, e->d_seg, total, e->stream))
         return rc;
     HIP_TRY(e, hipMemcpyAsync(probs_out + base, e->d_probs, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost, e->stream));
     if (events_out) HIP_TRY(e, hipMemcpyAsync(events_out + base, e->d_events, (size_t)total, hipMemcpyDeviceToHost, e->stream));
@@ -1287,28 +1315,64 @@ int vad_scan(vad_engine *e, const vad_scan_item *items, int64_t n, const void *a
     return VAD_OK;
 }
 
-int vad_scan_device(vad_engine *e, const vad_scan_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int frame_fmt,
-                    int32_t hop, float denoise_thresh, const int64_t *out_start, float *d_probs, uint8_t *d_events,
-                    int32_t *d_seg_frames, void *stream) {
+// vad_scan_device and vad_scan_channels_device (the plan's refusals carry the host entry point's name, `plan_who`, as they did
+// before there were two); a two-channel block is read in quads of sample frames, 8 bytes of G.711
+template <class Item>
+int scan_dev(vad_engine *e, const char *who, const char *plan_who, const Item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
+             int frame_fmt, int32_t hop, float denoise_thresh, const int64_t *out_start, float *d_probs, uint8_t *d_events,
+             int32_t *d_seg_frames, void *stream) {
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
     HIP_TRY(e, hipSetDevice(e->device));
     if (int rc = scan_wait(e)) return rc;
     int64_t total = 0;
-    if (int rc = scan_plan(e, items, n, audio_samples, frame_fmt, hop, out_start, 0, &total)) return rc;
+    if (int rc = scan_plan(e, plan_who, items, n, audio_samples, channels, frame_fmt, hop, out_start, 0, &total)) return rc;
     if (total == 0) return VAD_OK;
-    if (!d_audio || !d_probs) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan_device: null buffer");
-    if (reinterpret_cast<uintptr_t>(d_audio) & 3)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_scan_device: the audio block must be 4-byte aligned");
+    if (!d_audio || !d_probs) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    const uintptr_t align = channels == 2 ? 8 : 4;
+    if (reinterpret_cast<uintptr_t>(d_audio) & (align - 1))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the audio block must be %d-byte aligned", who, (int)align);
     if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
     HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, s));
     if (!e->scan_done) HIP_TRY(e, hipEventCreateWithFlags(&e->scan_done, hipEventDisableTiming));
-    const int rc = scan_launches(e, d_audio, audio_samples, frame_fmt, hop, denoise_thresh, d_probs, d_events, d_seg_frames, total, s);
+    const int rc = scan_launches(e, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, d_probs, d_events, d_seg_frames, total, s);
     // (also behind a failed launch: the copy of the table and the launches before it are on the stream)
     HIP_TRY(e, hipEventRecord(e->scan_done, s));
     e->scan_pending = true;
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vad_scan(vad_engine *e, const vad_scan_item *items, int64_t n, const void *audio, int64_t audio_samples, int frame_fmt,
+             int32_t hop, float denoise_thresh, const int64_t *out_start, float *probs_out, uint8_t *events_out,
+             int32_t *seg_frames_out) {
+    return scan_host(e, "vad_scan", items, n, audio, audio_samples, 1, frame_fmt, hop, denoise_thresh, out_start, probs_out, events_out,
+                     seg_frames_out);
+}
+
+int vad_scan_device(vad_engine *e, const vad_scan_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int frame_fmt,
+                    int32_t hop, float denoise_thresh, const int64_t *out_start, float *d_probs, uint8_t *d_events,
+                    int32_t *d_seg_frames, void *stream) {
+    return scan_dev(e, "vad_scan_device", "vad_scan", items, n, d_audio, audio_samples, 1, frame_fmt, hop, denoise_thresh, out_start, d_probs, d_events,
+                    d_seg_frames, stream);
+}
+
+int vad_scan_channels(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
+                      int frame_fmt, int32_t hop, float denoise_thresh, const int64_t *out_start, float *probs_out, uint8_t *events_out,
+                      int32_t *seg_frames_out) {
+    return scan_host(e, "vad_scan_channels", items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, out_start, probs_out,
+                     events_out, seg_frames_out);
+}
+
+int vad_scan_channels_device(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *d_audio, int64_t audio_samples,
+                             int32_t channels, int frame_fmt, int32_t hop, float denoise_thresh, const int64_t *out_start, float *d_probs,
+                             uint8_t *d_events, int32_t *d_seg_frames, void *stream) {
+    return scan_dev(e, "vad_scan_channels_device", "vad_scan_channels", items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, out_start,
+                    d_probs, d_events, d_seg_frames, stream);
 }
 
 // ---- pipelined host ingest ---------------------------------------------------------------------------------------

@@ -44,6 +44,7 @@ using namespace vadk;
 template <class V>
 __device__ __forceinline__ void stamp_wait(V v) {
     if constexpr (sizeof(V) == 4) asm volatile("" ::"v"(v) : "memory");
+    else if constexpr (sizeof(V) == 32) asm volatile("" ::"v"(v.b.x) : "memory");      // a two-channel float32 quad: its second load
     else asm volatile("" ::"v"(v.x) : "memory");
 }
 // in front of the stamp, v has arrived in its registers | every memory operation of the wave is acknowledged
@@ -242,7 +243,14 @@ __device__ __forceinline__ void x3_units(F &&f, std::integer_sequence<int, I...>
 // count (descending), the tile's loop runs to its first item's count, and a stream whose recording has ended is HELD exactly as a
 // rejected float32 frame holds one (h, c selected from the previous values, no sm_step), in every format, and writes no result.
 // Results go to out0 + t (CSR); the finished segment's length is written on every END, 0 on the recording's other frames.
-// The kernel's body is silero_v5_t16_body.h, shared by the three __global__ entries below.
+// CH = 2 (silero_v5_stereo16): the same scan over interleaved two-channel recordings L0 R0 L1 R1 ..  All positions count sample
+// frames; a quad of four sample frames is twice the mono quad's bytes (float32: two b128 loads, int16: the b128 the mono loader
+// issues anyway, G.711: a b64), both channels are decoded and the item's mode - in the top bits of its quad0, vad_layout.h -
+// selects the left one, the right one or their mean (dL + dR) * 0.5f = AudioUtils.convert_to_mono, in front of the non-finite
+// check and the gate.  The VALU instructions this adds (178 per wave in the int16 body) lie in the fold's slot under the recurrent
+// MFMAs but do not all hide there: + 1.8 % per frame at 4 096 streams, within the spread at 1 024; everything behind
+// the decode is the scan's.  The channel count belongs to the call, the mode to the item: two items may name the same samples.
+// The kernel's body is silero_v5_t16_body.h, shared by the four __global__ entries below.
 // One workgroup per CU also here.  Built for two (a tick's segments are padded to whole tiles, so it can have a few more tiles
 // than CUs), the dispatcher packs consecutive workgroups onto the same CU: 258 tiles ran on ~130 CUs, 69.9 us per tick against
 // 55.6 for the two-launch form - so the engine uses this launch only when the tick has at most one tile per CU.
@@ -253,6 +261,7 @@ __device__ __forceinline__ void x3_units(F &&f, std::integer_sequence<int, I...>
 // (entries that are no scan: the body's SCAN branches are discarded, these two names only have to exist)
 #define STEP16_NO_SCAN                                  \
     constexpr bool SCAN = false;                        \
+    constexpr int CH = 1;                               \
     constexpr const ScanItem *k_items = nullptr;        \
     constexpr ScanArgs S{};
 template <bool F32IN_, bool RS, bool K8 = false, bool ONE = false>
@@ -276,6 +285,19 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_scan16(const float *k_w
                                                                 const int k_T, const StepParams P, const ScanArgs S) {
     constexpr int FMT = FMT_;
     constexpr bool RS = false, ONE = false, SCAN = true;
+    constexpr int CH = 1;
+    constexpr const int32_t *k_slots = nullptr;
+    const RateParams R{};
+#include "silero_v5_t16_body.h"
+}
+// whole two-channel recordings, interleaved (vad_scan_channels): the scan with every position counted in sample frames
+template <int FMT_, bool K8>
+__global__ void __launch_bounds__(NTHREADS, 1) silero_v5_stereo16(const float *k_wstream, float *k_state, SmSlot *k_sm, const ScanItem *k_items,
+                                                                  const void *k_frames, const int k_n, const uint32_t k_wstream_bytes,
+                                                                  const int k_T, const StepParams P, const ScanArgs S) {
+    constexpr int FMT = FMT_;
+    constexpr bool RS = false, ONE = false, SCAN = true;
+    constexpr int CH = 2;
     constexpr const int32_t *k_slots = nullptr;
     const RateParams R{};
 #include "silero_v5_t16_body.h"
@@ -328,6 +350,7 @@ extern "C" hipError_t vadk_launch_silero_v5_t16(const vadk::StepParams *p, hipSt
 
 // whole recordings: p->n items (sorted by frame count, descending), p->frames = the audio block, p->T = frames of this launch's window
 // [a->t0, a->t0 + p->T), p->probs / events / seg_frames = the CSR arrays; p->fmt as in vadk_launch_silero_v5_t16
+// a->channels = 2: the block is interleaved two-channel audio (silero_v5_stereo16; 8-byte aligned: G.711's quad of sample frames)
 extern "C" hipError_t vadk_launch_silero_v5_scan16(const vadk::StepParams *p, const vadk::ScanItem *items, const vadk::ScanArgs *a,
                                                    hipStream_t stream) {
     (void)hipGetLastError();
@@ -335,15 +358,26 @@ extern "C" hipError_t vadk_launch_silero_v5_scan16(const vadk::StepParams *p, co
     if (tiles <= 0) return hipSuccess;
     if (p->T < 1 || p->fmt < 0 || p->fmt > 4 || a->hopq < 1 || a->t0 < 0 || (a->audio_bytes >> 31)) return hipErrorInvalidValue;
     if ((reinterpret_cast<uintptr_t>(p->frames) & 3) || (reinterpret_cast<uintptr_t>(items) & 15)) return hipErrorInvalidValue;
+    if (a->channels < 0 || a->channels > 2 || (a->channels == 2 && (reinterpret_cast<uintptr_t>(p->frames) & 7))) return hipErrorInvalidValue;
 #define SCAN16_LAUNCH(F, K)                                                                                                    \
     hipLaunchKernelGGL((silero_v5_scan16<F, K>), dim3(tiles), dim3(vadk::NTHREADS), 0, stream, p->wstream, p->state, p->sm, items, \
                        p->frames, (int)p->n, p->wstream_bytes, (int)p->T, *p, *a)
+#define STEREO16_LAUNCH(F, K)                                                                                                  \
+    hipLaunchKernelGGL((silero_v5_stereo16<F, K>), dim3(tiles), dim3(vadk::NTHREADS), 0, stream, p->wstream, p->state, p->sm, items, \
+                       p->frames, (int)p->n, p->wstream_bytes, (int)p->T, *p, *a)
     const int f = p->fmt == 0 ? 0 : p->fmt <= 2 ? 1 : p->fmt - 1;      // vad_frame_format -> FMT
-    if (p->variant != 0) {
+    if (a->channels == 2) {
+        if (p->variant != 0) {
+            if (f == 0) STEREO16_LAUNCH(0, true); else if (f == 1) STEREO16_LAUNCH(1, true); else if (f == 2) STEREO16_LAUNCH(2, true); else STEREO16_LAUNCH(3, true);
+        } else {
+            if (f == 0) STEREO16_LAUNCH(0, false); else if (f == 1) STEREO16_LAUNCH(1, false); else if (f == 2) STEREO16_LAUNCH(2, false); else STEREO16_LAUNCH(3, false);
+        }
+    } else if (p->variant != 0) {
         if (f == 0) SCAN16_LAUNCH(0, true); else if (f == 1) SCAN16_LAUNCH(1, true); else if (f == 2) SCAN16_LAUNCH(2, true); else SCAN16_LAUNCH(3, true);
     } else {
         if (f == 0) SCAN16_LAUNCH(0, false); else if (f == 1) SCAN16_LAUNCH(1, false); else if (f == 2) SCAN16_LAUNCH(2, false); else SCAN16_LAUNCH(3, false);
     }
+#undef STEREO16_LAUNCH
 #undef SCAN16_LAUNCH
     return hipGetLastError();
 }

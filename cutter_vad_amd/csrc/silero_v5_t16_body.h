@@ -5,6 +5,7 @@
 // function provides the arguments k_wstream .. k_T, P, R and the constants FMT (wire format: 0 float32, 1 int16 of either scale,
 // 2 / 3 ITU-T G.711 mu-law / A-law, one byte per sample), RS, K8, ONE, SCAN (silero_v5_t16.hip explains them).  SCAN: the entry
 // also provides k_items and S (vad_layout.h: ScanItem, ScanArgs); the other entries a null k_items and an empty S.
+// CH: the channels of the audio block, 1 everywhere but in the scan of interleaved two-channel recordings (silero_v5_stereo16).
 #define KP(f) k_##f
     using namespace vadk::v5;
     constexpr bool F32IN = FMT == 0;
@@ -12,6 +13,7 @@
     static_assert(!RS || F32IN, "resampled frames are float32");
     static_assert(!(RS && K8), "the fused resampler feeds the 16 kHz model");
     static_assert(!SCAN || (!RS && !ONE), "a scan is the frame-loop form on audio in HBM");
+    static_assert(CH == 1 || (CH == 2 && SCAN), "two interleaved channels: whole recordings only");
     constexpr int QL = K8 ? 8 : 16;               // loader lanes per stream = quads per quarter column
     constexpr int CS = 4 * QL;                    // folded-operand rows per column
     constexpr int PP = K8 ? 24 : 48;              // quad rows per |STFT| column (enc0's input) as planes: 12 per K-step
@@ -90,7 +92,7 @@
     const int lms = K8 ? (tid >> 3) & 15 : tid >> 4;      // the loader's stream of this thread
     const int lcol = tid >> 7;                            // K8: which of a fold call's two columns
     constexpr bool f32in = F32IN;
-    constexpr int qsh = f32in ? 4 : G711 ? 2 : 3;           // a quad of samples: 16 / 8 / 4 bytes
+    constexpr int qsh = (f32in ? 4 : G711 ? 2 : 3) + (CH == 2 ? 1 : 0);   // a quad of samples: 16 / 8 / 4 bytes, of every channel
     const float sc = P.fmt == 1 ? 32767.0f : 32768.0f, rsc = 1.0f / sc;
     const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void *>(KP(frames)), 0,
@@ -101,9 +103,15 @@
     //  request below, once - profiles/r09_launch_ends_other_configs.jsonl)
     constexpr int X_NT = K8 ? 0 : 2;               // the buffer loads' cache policy bits: nt
     // one quad of raw samples: 16 bytes (float32; int16 uses the first 8), G.711: the quad is one dword, fetched as such
-    using XQ = std::conditional_t<G711, uint32_t, u32x4>;
+    // CH == 2: a quad of sample frames L0 R0 L1 R1 L2 R2 L3 R3 - twice the bytes: two b128 | the int16 loader's b128, all of it | b64
+    struct XQ2F { u32x4 a, b; };
+    using XQ = std::conditional_t<CH == 2, std::conditional_t<f32in, XQ2F, std::conditional_t<G711, u32x2, u32x4>>,
+                                  std::conditional_t<G711, uint32_t, u32x4>>;
     auto x_load = [&](int off) -> XQ {
-        if constexpr (G711) return __builtin_amdgcn_raw_buffer_load_b32(frs, off, 0, X_NT);
+        if constexpr (CH == 2 && f32in)
+            return XQ2F{__builtin_amdgcn_raw_buffer_load_b128(frs, off, 0, X_NT), __builtin_amdgcn_raw_buffer_load_b128(frs, off + 16, 0, X_NT)};   // (both offsets range-checked)
+        else if constexpr (CH == 2 && G711) return __builtin_amdgcn_raw_buffer_load_b64(frs, off, 0, X_NT);
+        else if constexpr (G711) return __builtin_amdgcn_raw_buffer_load_b32(frs, off, 0, X_NT);
         else return __builtin_amdgcn_raw_buffer_load_b128(frs, off, 0, X_NT);
     };
     XQ xa_[4], xb_[4], xc_[4];                     // raw quads of the three columns
@@ -116,10 +124,19 @@
     // SCAN: frame tt of the launch, for the loader's stream, starts at quad xq0 + tt hopq of the audio block - frames overlap in
     // memory when hop < frame, nothing is copied.  Unsigned: a stream past its end keeps walking (into its neighbour's samples, or
     // past the block, where the descriptor answers 0); what it loads reaches selects only.
+    // CH == 2: positions count sample frames, and the item's quad0 carries the stream's channel mode in its two top bits
+    // (SCAN_MODE_SHIFT: 0 left, 1 right, 2 the mean of the two - a block is under 2 GiB, so a quad index stays below 2^29).
     uint32_t xq0 = 0;
+    [[maybe_unused]] uint32_t xmode = 0;
     if constexpr (SCAN) {
         const int li = tile0 + lms;
+        if constexpr (CH == 2) {
+            const uint32_t qm = li < KP(n) ? k_items[li].quad0 : 0u;
+            xmode = qm >> SCAN_MODE_SHIFT;
+            xq0 = (qm & ((1u << SCAN_MODE_SHIFT) - 1u)) + (uint32_t)S.t0 * S.hopq;
+        } else {
         xq0 = (li < KP(n) ? k_items[li].quad0 : 0u) + (uint32_t)S.t0 * S.hopq;
+        }
     }
 #define X_ISSUE(c, XR, tt)                                                                                      \
     if constexpr (RS) {                                                                                         \
@@ -635,7 +652,31 @@
             float xm = 0.f;                       // float32: running max |x| of this thread's raw samples (vadk_device.h absmax4)
             auto decode = [&](XQ b) -> f32x4 {
                 f32x4 v;
-                if constexpr (G711) {
+                if constexpr (CH == 2) {
+                    // both channels through the mono decoders, then the stream's own: left | right | (dL + dR) * 0.5f, which is
+                    // np.mean(x, axis=1) of a float32 [N, 2] array bit for bit (an add, then a multiply: nothing to contract).
+                    // The rejection and the gate see what the model sees: the selected channel or the mixed values.
+                    f32x4 dl, dr;
+                    if constexpr (G711) {
+                        dl = g711_quad<FMT == 3>(__builtin_amdgcn_perm(b.y, b.x, 0x06040200u));    // codes L0 L1 L2 L3
+                        dr = g711_quad<FMT == 3>(__builtin_amdgcn_perm(b.y, b.x, 0x07050301u));
+                    } else if constexpr (!f32in) {
+                        dl = f32x4{i16_div((int)(short)(b.x & 0xffffu), sc, rsc), i16_div((int)(short)(b.y & 0xffffu), sc, rsc),
+                                   i16_div((int)(short)(b.z & 0xffffu), sc, rsc), i16_div((int)(short)(b.w & 0xffffu), sc, rsc)};
+                        dr = f32x4{i16_div((int)(short)(b.x >> 16), sc, rsc), i16_div((int)(short)(b.y >> 16), sc, rsc),
+                                   i16_div((int)(short)(b.z >> 16), sc, rsc), i16_div((int)(short)(b.w >> 16), sc, rsc)};
+                    } else {
+                        dl = __builtin_bit_cast(f32x4, u32x4{b.a.x, b.a.z, b.b.x, b.b.z});
+                        dr = __builtin_bit_cast(f32x4, u32x4{b.a.y, b.a.w, b.b.y, b.b.w});
+                    }
+                    const bool right = xmode == 1u, mix = xmode >= 2u;
+                    const f32x4 mx = pk::mul(pk::add(dl, dr), f32x4{0.5f, 0.5f, 0.5f, 0.5f});
+                    v.x = mix ? mx.x : right ? dr.x : dl.x;
+                    v.y = mix ? mx.y : right ? dr.y : dl.y;
+                    v.z = mix ? mx.z : right ? dr.z : dl.z;
+                    v.w = mix ? mx.w : right ? dr.w : dl.w;
+                    if constexpr (f32in) xm = absmax4(xm, v);
+                } else if constexpr (G711) {
                     v = g711_quad<FMT == 3>(b);
                 } else if constexpr (!f32in) {
                     const int s0 = (int)(short)(b.x & 0xffffu), s1 = (int)(short)(b.x >> 16);

@@ -217,18 +217,24 @@ static_assert(sizeof(StepParams) == 368, "StepParams keeps its size (see above)"
 // the samples from 4 (quad0 + t hopq) on, its results go to entry out0 + t of the call's probs / events / seg arrays.
 struct ScanItem {
     int32_t slot;
-    uint32_t quad0;           // sample_offset / 4
+    uint32_t quad0;           // sample_offset / 4; two-channel blocks: | the stream's channel mode << SCAN_MODE_SHIFT
     int32_t nframes;
     uint32_t out0;            // index of the recording's frame 0 in the outputs (CSR)
 };
 static_assert(sizeof(ScanItem) == 16, "ScanItem layout");
+// Interleaved two-channel blocks (vad_scan_channels; silero_v5_stereo16): positions count sample frames (one sample of every
+// channel), and each item says what its stream hears - the left channel, the right one, or the float32 mean of the decoded pair
+// (AudioUtils.convert_to_mono).  A block is under 2 GiB, so quad0 < 2^29 and its two top bits are free; a mono item, and the left
+// channel, encode as quad0 itself.
+constexpr int SCAN_MODE_SHIFT = 30;
+enum : uint32_t { SCAN_LEFT = 0, SCAN_RIGHT = 1, SCAN_MIX = 2 };
 // a launch's arguments next to StepParams (which keeps its size): StepParams.n = items, .T = frames of the window, .frames = the
 // audio block; probs / events / seg_frames = the CSR arrays (seg_frames: one entry per FRAME here)
 struct ScanArgs {
     uint32_t audio_bytes;     // the buffer descriptor's range: the whole block; loads past it return 0
     uint32_t hopq;            // hop / 4
     int32_t t0;               // the launch covers frames t0 .. t0 + T - 1 of every item
-    int32_t pad;
+    int32_t channels;         // interleaved channels of the block: 2, or 0 / 1 = mono
 };
 
 // resampler launch parameters (csrc/resample.hip)

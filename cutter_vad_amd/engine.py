@@ -280,72 +280,147 @@ class Engine:
         self._check(self._lib.vad_debug_scan_launch_frames(self._h, int(frames)), VADError)
 
     def _scan_pack(self, recordings, law: Optional[str]):
-        """The recordings (1-D arrays of one dtype) packed into the engine's page-locked block, each starting on a multiple of 4
-        samples -> (block, samples, frame format, sample offsets, lengths)."""
+        """The recordings (1-D arrays of one dtype, or C-contiguous [nsamples, 2] arrays of one dtype: interleaved channels,
+        copied as they are) packed into the engine's page-locked block, each starting on a multiple of 4 sample frames
+        -> (block, sample frames, frame format, offsets, lengths, channels)."""
         recs = [np.asarray(r) for r in recordings]
+        ch = 2 if recs and all(r.ndim == 2 for r in recs) else 1
+        if ch == 1 and any(r.ndim == 2 for r in recs):
+            raise AudioProcessingError("Model prediction failed: one call takes recordings that are all 1-D or all [nsamples, 2]; "
+                                       "scan the two kinds in two calls (scan_recordings does)")
         g711 = _law_format(law, recs[0] if recs else None)
         if g711 is None:
             recs = [r if r.dtype in _FMT else r.astype(np.float32) for r in recs]
         dt = recs[0].dtype if recs else np.dtype(np.float32)
         for r in recs:
-            if r.ndim != 1 or r.dtype != dt:
+            if ch == 1 and (r.ndim != 1 or r.dtype != dt):
                 raise AudioProcessingError(f"Model prediction failed: recordings must be 1-D arrays of one dtype, got {r.shape} {r.dtype} next to {dt}")
-        lens = np.array([r.size for r in recs], np.int64)
+            if ch == 2 and (r.shape[1] != 2 or r.dtype != dt or not r.flags.c_contiguous):
+                raise AudioProcessingError(f"Model prediction failed: two-channel recordings must be C-contiguous [nsamples, 2] arrays of one "
+                                           f"dtype, got {r.shape} {r.dtype} next to {dt}")
+        lens = np.array([r.shape[0] for r in recs], np.int64)
         offs = np.zeros(len(recs), np.int64)
         if len(recs) > 1:
             offs[1:] = np.cumsum((lens[:-1] + 3) & ~3)
         total = int(offs[-1] + lens[-1]) if recs else 0
-        need = max(total, 1) * dt.itemsize
+        need = max(total, 1) * ch * dt.itemsize
         if self._scan_block is None or self._scan_block.size < need:      # grown on demand, kept: pinning is the slow part
             if self._scan_block is not None:
                 self._check(self._lib.vad_host_free(self._h, self._scan_block.ctypes.data_as(C.c_void_p)), VADError)
                 self._scan_block = None
             self._scan_block = self.pinned_array(need + need // 4, np.uint8)
         block = self._scan_block[:need].view(dt)
+        if ch == 2:
+            block = block.reshape(-1, 2)
         for i, (r, o) in enumerate(zip(recs, offs)):
-            block[o:o + r.size] = r
-            block[o + r.size:(offs[i + 1] if i + 1 < len(recs) else o + r.size)] = 0      # the padding to a multiple of 4
-        return block, total, (_FMT[dt] if g711 is None else g711), offs, lens
+            block[o:o + lens[i]] = r
+            block[o + lens[i]:(offs[i + 1] if i + 1 < len(recs) else o + lens[i])] = 0      # the padding to a multiple of 4
+        return block, total, (_FMT[dt] if g711 is None else g711), offs, lens, ch
+
+    @staticmethod
+    def _scan_channel(c) -> int:
+        if isinstance(c, str):
+            if c == "mix":
+                return _ffi.VAD_SCAN_MIX
+        elif int(c) in (0, 1):
+            return int(c)
+        raise AudioProcessingError(f"Model prediction failed: channel must be 'mix', 0, 1, a sequence of these, or 'split', got {c!r}")
 
     def scan(self, slots, recordings, hop: Optional[int] = None, law: Optional[str] = None, i16_scale: int = 32767,
-             denoise: Optional[float] = 0.01):
+             denoise: Optional[float] = 0.01, channel="mix"):
         """Whole recordings of different lengths, framed on the GPU (``vad_scan``): ``recordings`` is a list of 1-D arrays
         (float32, int16, or uint8 G.711 codes with ``law``), recording i continues stream ``slots[i]``.  Frame t of a recording
         = its samples ``t * hop .. t * hop + frame_samples - 1``; ``hop`` defaults to ``frame_samples // 2``
         (``AudioUtils.split_into_frames`` as ``VADWrapper`` calls it), ``hop = frame_samples`` is Silero's back-to-back framing.
         -> (probs, events, seg_frames): three lists with one array per recording (views of the call's CSR arrays), one entry per
         frame; ``seg_frames`` holds the finished segment's length on every ``VAD_EV_END`` frame and 0 elsewhere
-        (``cutter_vad_amd.scan.speech_segments`` turns the two into sample ranges)."""
-        s = np.ascontiguousarray(slots, dtype=np.int64).reshape(-1)
-        recordings = list(recordings)
-        if s.size != len(recordings):
-            raise AudioProcessingError(f"Model prediction failed: {s.size} slots for {len(recordings)} recordings")
+        (``cutter_vad_amd.scan.speech_segments`` turns the two into sample ranges).
+        Two-channel recordings (``vad_scan_channels``): every recording a C-contiguous ``[nsamples, 2]`` array, interleaved as WAV
+        readers deliver it and scanned as it is.  ``channel`` says what a stream hears: ``"mix"`` (the default: the float32 mean
+        of the decoded pair, what ``VADWrapper`` makes of such an array), ``0``, ``1``, a sequence of these per recording, or
+        ``"split"``: both channels of every recording, each on its own stream - ``slots`` is ``[n, 2]``, a recording is packed
+        once and every returned array gets a leading axis of 2.  1-D recordings ignore ``channel``."""
+        recordings = [np.asarray(r) for r in recordings]
+        n = len(recordings)
+        two = any(r.ndim == 2 for r in recordings)
+        split = two and isinstance(channel, str) and channel == "split"
+        s = np.ascontiguousarray(slots, dtype=np.int64)
+        if split:
+            if s.shape != (n, 2):
+                raise AudioProcessingError(f"Model prediction failed: channel='split' takes slots of shape ({n}, 2), got {s.shape}")
+            chans = [(0, 1)] * n
+        else:
+            s = s.reshape(-1)
+            if s.size != n:
+                raise AudioProcessingError(f"Model prediction failed: {s.size} slots for {n} recordings")
+            if not two:
+                chans = [(0,)] * n
+            elif isinstance(channel, (str, int, np.integer)):
+                chans = [(self._scan_channel(channel),)] * n
+            else:
+                chans = [(self._scan_channel(c),) for c in channel]
+                if len(chans) != n:
+                    raise AudioProcessingError(f"Model prediction failed: {len(chans)} channels for {n} recordings")
+        per = 2 if split else 1
+        s = s.reshape(n, per)
         hop = self.frame_samples // 2 if hop is None else int(hop)
         with self._scan_lock:
-            block, total, fmt, offs, lens = self._scan_pack(recordings, law)
+            block, total, fmt, offs, lens, _ = self._scan_pack(recordings, law)
             if fmt == _ffi.VAD_FMT_I16_32767 and i16_scale == 32768:
                 fmt = _ffi.VAD_FMT_I16_32768
-            items = (_ffi.ScanItem * max(1, s.size))()
-            start = np.zeros(s.size + 1, np.int64)
-            for i in range(s.size):
-                items[i] = _ffi.ScanItem(int(s[i]), int(offs[i]), int(lens[i]))
-                start[i + 1] = start[i] + (self.scan_frame_count(int(lens[i]), hop) if hop >= 1 else 0)
+            # one item per (recording, channel listed for it); a 1-D corpus goes through vad_scan as it always did
+            items = ((_ffi.ScanChItem if two else _ffi.ScanItem) * max(1, n * per))()
+            start = np.zeros(n * per + 1, np.int64)
+            for i in range(n):
+                nf = self.scan_frame_count(int(lens[i]), hop) if hop >= 1 else 0
+                for k, c in enumerate(chans[i]):
+                    j = i * per + k
+                    where = (int(s[i, k]), int(offs[i]), int(lens[i]))
+                    items[j] = _ffi.ScanChItem(*where, c, 0) if two else _ffi.ScanItem(*where)
+                    start[j + 1] = start[j] + nf
             nf = int(start[-1])
             probs = np.empty(nf, np.float32)
             ev = np.zeros(nf, np.uint8)
             seg = np.zeros(nf, np.int32)
             thr = -1.0 if denoise is None else float(denoise)
-            self._check(self._lib.vad_scan(self._h, items, s.size, block.ctypes.data_as(C.c_void_p), total, fmt, hop, thr,
-                                           _ptr(start, C.c_int64), _ptr(probs, C.c_float), _ptr(ev, C.c_uint8), _ptr(seg, C.c_int32)))
-        cut = lambda a: [a[start[i]:start[i + 1]] for i in range(s.size)]
+            out = (_ptr(start, C.c_int64), _ptr(probs, C.c_float), _ptr(ev, C.c_uint8), _ptr(seg, C.c_int32))
+            if two:
+                self._check(self._lib.vad_scan_channels(self._h, items, n * per, block.ctypes.data_as(C.c_void_p), total, 2, fmt, hop, thr, *out))
+            else:
+                self._check(self._lib.vad_scan(self._h, items, n, block.ctypes.data_as(C.c_void_p), total, fmt, hop, thr, *out))
+        if split:
+            cut = lambda a: [a[start[2 * i]:start[2 * i + 2]].reshape(2, -1) for i in range(n)]
+        else:
+            cut = lambda a: [a[start[i]:start[i + 1]] for i in range(n)]
         return cut(probs), cut(ev), cut(seg)
 
     def scan_device(self, slots, offsets, lengths, d_audio: int, audio_samples: int, d_probs: int, d_events: int = 0, d_seg: int = 0,
-                    hop: Optional[int] = None, fmt: int = _ffi.VAD_FMT_F32, denoise: Optional[float] = 0.01, stream: int = 0) -> np.ndarray:
+                    hop: Optional[int] = None, fmt: int = _ffi.VAD_FMT_F32, denoise: Optional[float] = 0.01, stream: int = 0,
+                    channels: int = 1, channel=None) -> np.ndarray:
         """``scan`` on device pointers (integers): recording i = ``lengths[i]`` samples from sample ``offsets[i]`` (a multiple
-        of 4) of the block at ``d_audio``; results go to the CSR positions this returns (``out_start`` [n + 1]).  Asynchronous."""
+        of 4) of the block at ``d_audio``; results go to the CSR positions this returns (``out_start`` [n + 1]).  Asynchronous.
+        ``channels = 2`` (``vad_scan_channels_device``): the block is interleaved two-channel audio (8-byte aligned), offsets,
+        lengths and ``audio_samples`` count sample frames, and ``channel`` is ``"mix"`` (the default), ``0``, ``1`` or one of these
+        per item - list a recording twice, with two slots, to scan both of its channels."""
         s = np.ascontiguousarray(slots, dtype=np.int64).reshape(-1)
         hop = self.frame_samples // 2 if hop is None else int(hop)
+        if channels != 1 or channel is not None:
+            channel = "mix" if channel is None else channel
+            if isinstance(channel, (str, int, np.integer)):
+                chans = [_ffi.VAD_SCAN_MIX if channels == 1 and channel == "mix" else self._scan_channel(channel)] * s.size
+            else:
+                chans = [self._scan_channel(c) for c in channel]
+                if len(chans) != s.size:
+                    raise AudioProcessingError(f"Model prediction failed: {len(chans)} channels for {s.size} recordings")
+            citems = (_ffi.ScanChItem * max(1, s.size))()
+            start = np.zeros(s.size + 1, np.int64)
+            for i in range(s.size):
+                citems[i] = _ffi.ScanChItem(int(s[i]), int(offsets[i]), int(lengths[i]), chans[i], 0)
+                start[i + 1] = start[i] + self.scan_frame_count(int(lengths[i]), hop)
+            thr = -1.0 if denoise is None else float(denoise)
+            self._check(self._lib.vad_scan_channels_device(self._h, citems, s.size, d_audio, int(audio_samples), int(channels), fmt, hop, thr,
+                                                           _ptr(start, C.c_int64), d_probs, d_events or None, d_seg or None, stream or None))
+            return start
         items = (_ffi.ScanItem * max(1, s.size))()
         start = np.zeros(s.size + 1, np.int64)
         for i in range(s.size):

@@ -30,12 +30,20 @@ def speech_segments(events, seg_frames, frame: int, hop: int) -> List[Tuple[int,
 
 
 def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
-                    law: Optional[str] = None) -> List[List[Tuple[int, int]]]:
+                    law: Optional[str] = None, channel="mix") -> List[List[Tuple[int, int]]]:
     """Speech segments of every recording, one launch sequence for the lot: opens one stream per recording with the config's
     thresholds, scans (frames of ``engine.frame_samples`` at ``hop``, default half a frame as ``VADWrapper`` frames a chunk;
     the config's denoise gate), closes the streams -> per recording ``[(start_sample, end_sample), ...]``.
-    ``engine``: an :class:`~cutter_vad_amd.engine.Engine`; default: the process-wide pool's engine for the config."""
+    ``engine``: an :class:`~cutter_vad_amd.engine.Engine`; default: the process-wide pool's engine for the config.
+    A recording may be a ``[nsamples, 2]`` array, interleaved channels as WAV readers deliver a recorded call; a corpus may hold
+    both kinds (at most two scans, results in the caller's order).  ``channel``: what is scanned of a two-channel recording -
+    ``"mix"`` (the default: the mean of the channels, as ``VADWrapper`` mixes such an array down), ``0`` or ``1``: one segment
+    list per recording; ``"split"``: one list per CHANNEL - ``[segments]`` for a 1-D recording, ``[left, right]`` for a 2-D one."""
     from .pool import default_pool, resolve_model_path
+    split = isinstance(channel, str) and channel == "split"
+    # checked here, not by the scan: a corpus of 1-D recordings alone never shows the value to Engine.scan
+    if not (channel in ("mix", "split") if isinstance(channel, str) else isinstance(channel, (int, np.integer)) and int(channel) in (0, 1)):
+        raise ConfigurationError("channel", repr(channel), f"scan_recordings: channel is 'mix', 0, 1 or 'split' for the whole corpus, got {channel!r}")
     cfg = config or VADConfig()
     if engine is None:
         engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
@@ -44,15 +52,28 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
         raise ConfigurationError(f"scan_recordings frames at the model's frame size: buffer_size = {cfg.buffer_size}, "
                                  f"the engine's frames have {frame} samples")
     hop = frame // 2 if hop is None else int(hop)
-    recordings = list(recordings)
+    recordings = [np.asarray(r) for r in recordings]
     if not recordings:
         return []
-    slots = engine.open_streams(len(recordings))
-    try:
-        engine.set_thresholds_many(slots, (cfg.vad_start_probability, cfg.vad_end_probability, cfg.voice_start_ratio,
-                                           cfg.voice_end_ratio, cfg.voice_start_frame_count, cfg.voice_end_frame_count))
-        _probs, ev, seg = engine.scan(slots, recordings, hop=hop, law=law, denoise=0.01 if cfg.enable_denoising else None)
-    finally:
-        for s in slots:
-            engine.close_stream(int(s))
-    return [speech_segments(e, g, frame, hop) for e, g in zip(ev, seg)]
+    out: List = [None] * len(recordings)
+    for two in (False, True):
+        idx = [i for i, r in enumerate(recordings) if (r.ndim == 2) == two]
+        if not idx:
+            continue
+        per = 2 if two and split else 1
+        slots = engine.open_streams(len(idx) * per)
+        try:
+            engine.set_thresholds_many(slots, (cfg.vad_start_probability, cfg.vad_end_probability, cfg.voice_start_ratio,
+                                               cfg.voice_end_ratio, cfg.voice_start_frame_count, cfg.voice_end_frame_count))
+            _probs, ev, seg = engine.scan(np.asarray(slots).reshape(len(idx), per) if per == 2 else slots, [recordings[i] for i in idx],
+                                          hop=hop, law=law, denoise=0.01 if cfg.enable_denoising else None, channel=channel)
+        finally:
+            for s in slots:
+                engine.close_stream(int(s))
+        for i, e, g in zip(idx, ev, seg):
+            if per == 2:
+                out[i] = [speech_segments(e[c], g[c], frame, hop) for c in range(2)]
+            else:
+                sg = speech_segments(e, g, frame, hop)
+                out[i] = [sg] if split else sg
+    return out

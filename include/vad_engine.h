@@ -284,6 +284,40 @@ VAD_API int vad_scan(vad_engine *e, const vad_scan_item *items, int64_t n, const
 VAD_API int vad_scan_device(vad_engine *e, const vad_scan_item *items, int64_t n, const void *d_audio, int64_t audio_samples,
                             int frame_fmt, int32_t hop, float denoise_thresh, const int64_t *out_start /*[n + 1]*/, float *d_probs,
                             uint8_t *d_events, int32_t *d_seg_frames, void *stream);
+/*
+ * Whole recordings with interleaved channels (Silero V5): the two-channel call recording - agent left, customer right, samples
+ * L0 R0 L1 R1 .. as every WAV reader hands them over ([nsamples, 2]) - scanned as it is, de-interleaved by the kernel's loader.
+ * `channels` is 1 or 2 and belongs to the call: the block holds audio_samples SAMPLE FRAMES (one sample of every channel), and
+ * sample_offset, nsamples and hop count sample frames too, under vad_scan's rules (offset and hop multiples of 4).  What a stream
+ * hears belongs to the item: `channel` = 0 .. channels - 1, or VAD_SCAN_MIX = the mean of the two channels, computed on the decoded
+ * float32 values as (L + R) * 0.5f - bit for bit AudioUtils.convert_to_mono's np.mean(x, axis=1) on the decoded array, which is what
+ * VADWrapper.process_audio_data makes of such a recording.  The denoise gate and the non-finite check (float32) follow the
+ * selection: a NaN in the other channel does not reject a channel-selected stream, +Inf left with -Inf right rejects a mixed one.
+ * With channels == 1 either accepted value means the mono samples, and the call is vad_scan.  `reserved` must be 0.
+ *   Two items may name the same samples with different channels and different slots: that is how both speakers of a call are
+ * scanned - the block crosses the link once, and the two streams sit side by side in a tile, on the same cache lines.
+ *   Everything else is vad_scan's: CSR results, held streams, launches, statuses.  VAD_ERR_INVALID_ARG, with a message, also for
+ * channels outside {1, 2}, a channel out of range, a non-zero reserved, and 2 GiB or more in audio_samples * channels * bytes
+ * per sample.  A refused call writes nothing.  Silero V4 and VAD_ENGINE_SHARED_GPU engines: VAD_ERR_UNSUPPORTED.
+ *   vad_scan_channels_device: a block of two channels must be 8-byte aligned (the loader reads a quad of G.711 sample frames as
+ * one 8-byte word, wider ones in other formats), else VAD_ERR_INVALID_ARG; one channel: 4 bytes, as vad_scan_device.
+ *   VAD_ABI_VERSION is unchanged: the presence of vad_scan_channels is how a caller detects the feature.
+ */
+#define VAD_SCAN_MIX (-1)
+typedef struct vad_scan_ch_item {
+    int64_t slot;
+    int64_t sample_offset;   /* first sample frame of the recording in the block; a multiple of 4 */
+    int64_t nsamples;        /* sample frames */
+    int32_t channel;         /* 0 .. channels - 1, or VAD_SCAN_MIX */
+    int32_t reserved;        /* 0 */
+} vad_scan_ch_item;
+VAD_API int vad_scan_channels(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples,
+                              int32_t channels, int frame_fmt, int32_t hop, float denoise_thresh, const int64_t *out_start /*[n + 1]*/,
+                              float *probs_out, uint8_t *events_out /*or NULL*/, int32_t *seg_frames_out /*or NULL*/);
+VAD_API int vad_scan_channels_device(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *d_audio, int64_t audio_samples,
+                                     int32_t channels, int frame_fmt, int32_t hop, float denoise_thresh,
+                                     const int64_t *out_start /*[n + 1]*/, float *d_probs, uint8_t *d_events, int32_t *d_seg_frames,
+                                     void *stream);
 /* Diagnostic: frames one launch of vad_scan covers at most; 0 = the default.  Results do not depend on it. */
 VAD_API int vad_debug_scan_launch_frames(vad_engine *e, int32_t frames);
 

@@ -525,6 +525,114 @@ def scan_ingest():
     return out
 
 
+def scan_stereo():
+    """Two-channel recordings (vad_scan_channels), interleaved runs, three each:
+    (a) the kernel alone, audio resident in HBM: vad_scan_channels_device in split mode (both channels of every recording, 2 n
+        streams) on n = 512 and 2 048 interleaved int16 recordings against vad_scan_device on the 2 n mono recordings a host
+        gets by de-interleaving them - the same samples, the same streams in the same order; HIP events around every call, after
+        warm-up calls that are scans themselves.  Lengths are seeded, 5 - 30 s at n = 512; at n = 2 048 5 - 20 s, so that the
+        block (4 bytes per sample frame) stays under the 2 GiB one call addresses;
+    (b) host-inclusive, n = 512 from page-locked memory: Engine.scan(channel="split") against numpy's de-interleave (one
+        strided copy per channel and recording) followed by Engine.scan."""
+    import time
+    import numpy as np
+    from cutter_vad_amd import _ffi
+    out = []
+    eng = Engine(blob(5), max_streams=4096)
+    frame, hop = eng.frame_samples, eng.frame_samples // 2
+    for n, longest in ((512, 30), (2048, 20)):
+        rng = np.random.default_rng(n)
+        lens = rng.integers(5 * 16000, longest * 16000 + 1, n)
+        pad = (lens + 3) & ~3
+        offs = np.concatenate([[0], np.cumsum(pad[:-1])])
+        total = int(offs[-1] + lens[-1])
+        assert total * 4 < (1 << 31)
+        block = eng.pinned_array((total, 2), np.int16) if n == 512 else np.empty((total, 2), np.int16)
+        for o in range(0, total, 1 << 24):
+            block[o:o + (1 << 24)] = (2000.0 * rng.standard_normal((min(1 << 24, total - o), 2))).astype(np.int16)
+        recs = [block[o:o + k] for o, k in zip(offs, lens)]
+        # the host's de-interleave: left and right of recording i one after the other, each on a multiple of 4 samples
+        moffs = np.concatenate([[0], np.cumsum(np.repeat(pad, 2))[:-1]])
+        mono = np.zeros(int(moffs[-1] + lens[-1]), np.int16)
+        for i, r in enumerate(recs):
+            for c in range(2):
+                mono[moffs[2 * i + c]:moffs[2 * i + c] + lens[i]] = r[:, c]
+        slots = eng.open_streams(2 * n)
+        counts = np.array([eng.scan_frame_count(int(k), hop) for k in lens])
+        nf = 2 * int(counts.sum())
+        d_st, d_mo = torch.from_numpy(block).cuda(), torch.from_numpy(mono).cuda()
+        d_p = torch.empty(nf, device="cuda")
+        d_e = torch.empty(nf, dtype=torch.uint8, device="cuda")
+        d_s = torch.empty(nf, dtype=torch.int32, device="cuda")
+        ts = torch.cuda.Stream()
+        st_off, st_len, st_ch = np.repeat(offs, 2), np.repeat(lens, 2), [0, 1] * n
+
+        def one(stereo):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record(ts)
+            if stereo:
+                eng.scan_device(slots, st_off, st_len, d_st.data_ptr(), total, d_p.data_ptr(), d_e.data_ptr(), d_s.data_ptr(), hop=hop,
+                                fmt=_ffi.VAD_FMT_I16_32767, stream=ts.cuda_stream, channels=2, channel=st_ch)
+            else:
+                eng.scan_device(slots, moffs, st_len, d_mo.data_ptr(), mono.size, d_p.data_ptr(), d_e.data_ptr(), d_s.data_ptr(), hop=hop,
+                                fmt=_ffi.VAD_FMT_I16_32767, stream=ts.cuda_stream)
+            e1.record(ts)
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) * 1e-3
+
+        for _ in range(2):
+            one(True), one(False)
+        runs = {"channels_split": [], "mono_deinterleaved": []}
+        for _ in range(3):
+            runs["channels_split"].append(one(True))
+            runs["mono_deinterleaved"].append(one(False))
+        row = {"config": f"scan_stereo (a): kernel alone, {n} interleaved int16 recordings of 5 - {longest} s in HBM = {2 * n} streams, hop = frame / 2",
+               "frames": nf, "launches_per_call": -(-int(counts.max()) // 192), "audio_MB": total * 4 / 1e6}
+        for k, v in runs.items():
+            row[f"ms_{k}_runs"] = [r * 1e3 for r in v]
+            row[f"ms_{k}"] = float(np.median(v)) * 1e3
+            row[f"us_per_launched_frame_{k}"] = float(np.median(v)) * 1e6 / int(counts.max())
+        row["spread_mono_pct"] = 100.0 * (max(runs["mono_deinterleaved"]) - min(runs["mono_deinterleaved"])) / float(np.median(runs["mono_deinterleaved"]))
+        row["channels_over_mono"] = float(np.median(runs["channels_split"]) / np.median(runs["mono_deinterleaved"]))
+        out.append(row)
+        del d_st, d_mo
+        if n == 512:
+            sl2 = np.asarray(slots).reshape(n, 2)
+
+            def route_split():
+                t0 = time.perf_counter()
+                probs, _, _ = eng.scan(sl2, recs, hop=hop, channel="split")
+                return time.perf_counter() - t0, 0.0
+
+            def route_deinterleave():
+                t0 = time.perf_counter()
+                chans = [np.ascontiguousarray(r[:, c]) for r in recs for c in range(2)]
+                t_copy = time.perf_counter() - t0
+                eng.scan(slots, chans, hop=hop)
+                return time.perf_counter() - t0, t_copy
+
+            route_split(), route_deinterleave()         # warm: the engine's page-locked block grows to its size
+            a, b, copies = [], [], []
+            for _ in range(3):
+                eng.reset(slots)
+                a.append(route_split()[0])
+                eng.reset(slots)
+                dt, tc = route_deinterleave()
+                b.append(dt)
+                copies.append(tc)
+            out.append({"config": f"scan_stereo (b): host-inclusive, {n} interleaved int16 recordings of 5 - {longest} s, page-locked host memory",
+                        "frames": nf, "audio_MB": total * 4 / 1e6, "s_scan_split_runs": a, "s_deinterleave_then_scan_runs": b,
+                        "s_of_that_strided_copies_runs": copies, "s_scan_split": float(np.median(a)),
+                        "s_deinterleave_then_scan": float(np.median(b)), "ratio": float(np.median(b) / np.median(a))})
+        eng.synchronize()
+        for s in slots:
+            eng.close_stream(int(s))
+        torch.cuda.empty_cache()
+    eng.close()
+    return out
+
+
 def single_stream_wrapper():
     """configs[0]: ONE stream through the drop-in VADWrapper (host framing + one launch + sync + callbacks per chunk)."""
     import time

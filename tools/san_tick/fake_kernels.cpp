@@ -83,24 +83,33 @@ extern "C" hipError_t vadk_launch_silero_v4_t16(const StepParams *p, int, hipStr
 // whole recordings (csrc/silero_v5_t16.hip: silero_v5_scan16), the same rule as fake_step: p = |first sample of the frame|, the
 // real state machine, a float32 frame with a NaN / Inf sample rejected; a stream past its recording's end is held (nothing
 // stepped, nothing written).  The "frames" are addressed as the kernel addresses them: sample 4 (quad0 + t hopq) of the block.
+// a->channels == 2 (silero_v5_stereo16): the block is interleaved, positions count sample frames, and the item's mode (the top
+// bits of quad0) picks the left samples, the right ones or the float32 mean of the decoded pair - the same rule on those.
 extern "C" hipError_t vadk_launch_silero_v5_scan16(const StepParams *p, const ScanItem *items, const ScanArgs *a, hipStream_t) {
     const int frame_samples = p->variant ? 256 : 512;
     for (int i = 0; i < p->n; ++i) {
         const ScanItem &it = items[i];
         SmSlot &s = p->sm[it.slot];
+        const bool two = a->channels == 2;
+        const uint32_t mode = two ? it.quad0 >> SCAN_MODE_SHIFT : 0u, quad0 = two ? it.quad0 & ((1u << SCAN_MODE_SHIFT) - 1u) : it.quad0;
+        // sample k of the stream, decoded (first_sample indexes frames of `stride` samples: a stride of one addresses the block itself)
+        auto sample = [&](size_t k) -> float {
+            if (!two) return first_sample(p->frames, k, p->fmt, 1);
+            const float l = first_sample(p->frames, 2 * k, p->fmt, 1), r = first_sample(p->frames, 2 * k + 1, p->fmt, 1);
+            return mode == SCAN_MIX ? (l + r) * 0.5f : mode == SCAN_RIGHT ? r : l;
+        };
         for (int t = a->t0; t < a->t0 + p->T && t < it.nframes; ++t) {
-            const size_t first = 4 * ((size_t)it.quad0 + (size_t)t * a->hopq), o = (size_t)it.out0 + (size_t)t;
+            const size_t first = 4 * ((size_t)quad0 + (size_t)t * a->hopq), o = (size_t)it.out0 + (size_t)t;
             bool bad = false;
             if (p->fmt == VAD_FMT_F32)
-                for (int k = 0; k < frame_samples; ++k) bad = bad || !std::isfinite(static_cast<const float *>(p->frames)[first + k]);
+                for (int k = 0; k < frame_samples; ++k) bad = bad || !std::isfinite(sample(first + k));
             if (bad) {
                 p->probs[o] = std::nanf("");
                 if (p->events) p->events[o] = (uint8_t)EV_REJECTED;
                 if (p->seg_frames) p->seg_frames[o] = 0;
                 continue;
             }
-            // (first_sample indexes frames of `stride` samples: a stride of one sample addresses the block itself)
-            float x = first_sample(p->frames, first, p->fmt, 1);
+            float x = sample(first);
             if (p->thresh >= 0.f && !(std::fabs(x) > p->thresh)) x = 0.f;
             const float prob = std::fmin(1.0f, std::fabs(x));
             int sg = 0;
