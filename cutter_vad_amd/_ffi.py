@@ -123,6 +123,18 @@ class ScanChItem(C.Structure):
 
 VAD_SCAN_MIX = -1
 
+
+class CutItem(C.Structure):
+    _fields_ = [("sample_offset", C.c_int64), ("first_frame", C.c_int64), ("nframes", C.c_int64), ("out_sample", C.c_int64),
+                ("channel", C.c_int32), ("reserved", C.c_int32)]
+
+
+VAD_CUT_FRAMES, VAD_CUT_RANGE = 0, 1
+VAD_CUT_PCM16, VAD_CUT_F32 = 0, 1
+VAD_CUT_WG_SAMPLES = 4096
+CUT_LAYOUTS = {"frames": VAD_CUT_FRAMES, "range": VAD_CUT_RANGE}
+CUT_OUTPUTS = {"pcm16": VAD_CUT_PCM16, "f32": VAD_CUT_F32}
+
 VAD_WORK_START, VAD_WORK_END, VAD_WORK_CONTINUE, VAD_WORK_PAYLOAD, VAD_WORK_LONG = 1, 2, 4, 8, 16
 VAD_WORK_REJECTED = 32
 
@@ -201,6 +213,11 @@ SIGNATURES = {
     "vad_scan_channels_device": (C.c_int, [_vp, C.POINTER(ScanChItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32,
                                            C.c_float, _i64p, _vp, _vp, _vp, _vp]),
     "vad_debug_scan_launch_frames": (C.c_int, [_vp, C.c_int32]),
+    "vad_cut_samples": (C.c_int64, [_vp, C.c_int64, C.c_int32, C.c_int32]),
+    "vad_scan_cut": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_float, C.c_int32,
+                               C.c_int32, _vp, C.c_int64]),
+    "vad_scan_cut_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_float,
+                                      C.c_int32, C.c_int32, _vp, C.c_int64, _vp]),
 }
 
 _lib = None

@@ -41,6 +41,7 @@ extern "C" hipError_t vadk_launch_silero_v4_t16(const vadk::StepParams *p, int o
 extern "C" hipError_t vadk_launch_silero_v5_t16_rates(const vadk::StepParams *p, const vadk::RateParams *r, hipStream_t stream);
 extern "C" hipError_t vadk_launch_silero_v5_scan16(const vadk::StepParams *p, const vadk::ScanItem *items, const vadk::ScanArgs *a,
                                                    hipStream_t stream);
+extern "C" hipError_t vadk_launch_scan_cut(const vadk::CutArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_resample(const vadk::ResampleParams *p, hipStream_t stream);
 extern "C" hipError_t vadk_launch_slot_control(vadk::SmSlot *sm, float *state, const int32_t *d_slots, int n, int op,
                                                const vadk::SmSlot *def, const vad_thresholds *d_thr, int nthr, hipStream_t stream);
@@ -144,6 +145,14 @@ struct vad_engine {
     std::vector<vadk::ScanItem> scan_items;
     hipEvent_t scan_done = nullptr;          // vad_scan_device: recorded behind its last launch, which may still read d_items
     bool scan_pending = false;               // (an event, not the caller's stream: the caller may destroy that once its work is done)
+    // vad_scan_cut: what d_audio holds - the block the last vad_scan / vad_scan_channels / vad_scan_cut of host audio uploaded
+    // (d_audio is written by scan_host and cut_run alone) - and the cut's tables as they were uploaded, segments then workgroups
+    bool audio_resident = false;
+    size_t audio_bytes = 0; int32_t audio_channels = 0; int audio_fmt = 0;
+    uint8_t *d_cut = nullptr; size_t d_cut_cap = 0;
+    void *d_cut_out = nullptr; size_t d_cut_out_cap = 0;
+    std::vector<vadk::CutSeg> cut_segs;
+    std::vector<vadk::CutWork> cut_work;
     // G.711 frames expanded to int16 for the kernels whose loaders do not decode them (launch())
     int16_t *d_g711 = nullptr; size_t d_g711_cap = 0;
     // small calls (a few streams: the one-wrapper-per-client pattern): ONE pinned block in, ONE pinned block out
@@ -830,7 +839,7 @@ void vad_engine_destroy(vad_engine *e) {
     weights_release(e->d_wstream16x);
     weights_release(e->d_wstream16y);
     void *bufs[] = {e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots, e->d_g711,
-                    e->d_audio, e->d_items, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
+                    e->d_audio, e->d_items, e->d_cut, e->d_cut_out, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->scan_done) (void)hipEventDestroy(e->scan_done);
@@ -1298,6 +1307,7 @@ int scan_host(vad_engine *e, const char *who, const Item *items, int64_t n, cons
     if (total == 0) return VAD_OK;
     if (!audio || !probs_out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
     const size_t ab = (size_t)audio_samples * (size_t)channels * sample_bytes(frame_fmt);
+    e->audio_resident = false;
     if (int rc = ensure(e, e->d_audio, e->d_audio_cap, ab + 16)) return rc;
     if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
     if (int rc = ensure(e, e->d_probs, e->d_probs_cap, sizeof(float) * (size_t)total)) return rc;
@@ -1306,6 +1316,8 @@ int scan_host(vad_engine *e, const char *who, const Item *items, int64_t n, cons
     // the audio crosses the link once, in its wire format
     HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, ab, hipMemcpyHostToDevice, e->stream));
+    e->audio_resident = true;                // for a following vad_scan_cut(audio = NULL), whatever becomes of the launches
+    e->audio_bytes = ab; e->audio_channels = channels; e->audio_fmt = frame_fmt;
     if (int rc = scan_launches(e, e->d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, e->d_probs, e->d_events, e->d_seg, total, e->stream))
         return rc;
     HIP_TRY(e, hipMemcpyAsync(probs_out + base, e->d_probs, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost, e->stream));
@@ -1373,6 +1385,199 @@ int vad_scan_channels_device(vad_engine *e, const vad_scan_ch_item *items, int64
                              uint8_t *d_events, int32_t *d_seg_frames, void *stream) {
     return scan_dev(e, "vad_scan_channels_device", "vad_scan_channels", items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, out_start,
                     d_probs, d_events, d_seg_frames, stream);
+}
+
+// ---- finished segments cut out of a scanned block (vad_scan_cut) --------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+static_assert(VAD_CUT_WG_SAMPLES == 4 * vadk::CUT_WG_QUADS, "the header's workgroup share is the kernel's");
+
+int64_t cut_samples(int64_t frame, int64_t nframes, int64_t hop, int32_t layout) {
+    return layout == VAD_CUT_FRAMES ? nframes * frame : (nframes - 1) * hop + frame;
+}
+
+// vad_scan_cut (DEV = false: host audio, or NULL = the resident block, and a host `out`) and vad_scan_cut_device.  Every check
+// comes before the first write; the tables (e->cut_segs, e->cut_work: one entry per workgroup) are built on the way.
+template <bool DEV>
+int cut_run(vad_engine *e, const char *who, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
+            int fmt, int32_t hop, float thr, int32_t layout, int32_t out_fmt, void *out, int64_t out_samples, void *stream) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    hipStream_t s = (DEV && stream) ? static_cast<hipStream_t>(stream) : e->stream;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    if (n < 0 || audio_samples < 0 || out_samples < 0 || (n > 0 && !items))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer or bad count", who);
+    if (fmt < VAD_FMT_F32 || fmt > VAD_FMT_ALAW8)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: unknown frame format %d", fmt);
+    if (channels != 1 && channels != 2)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: channels = %d, the block holds 1 or 2 interleaved channels", who, channels);
+    if (layout != VAD_CUT_FRAMES && layout != VAD_CUT_RANGE)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: layout = %d is neither VAD_CUT_FRAMES nor VAD_CUT_RANGE", who, layout);
+    if (out_fmt != VAD_CUT_PCM16 && out_fmt != VAD_CUT_F32)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_fmt = %d is neither VAD_CUT_PCM16 nor VAD_CUT_F32", who, out_fmt);
+    if (hop < 4 || (hop & 3))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: hop = %d must be a positive multiple of 4 samples", who, hop);
+    // the kernel addresses the block through a 32-bit buffer descriptor
+    const uint64_t fbytes = (uint64_t)channels * sample_bytes(fmt);
+    if ((uint64_t)audio_samples >= (1ull << 31) || (uint64_t)audio_samples * fbytes >= (1ull << 31))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %llu bytes of audio exceed the 2 GiB one call may address", who,
+                       (unsigned long long)((uint64_t)audio_samples * fbytes));
+    if (n == 0) return VAD_OK;
+    const int64_t frame = e->frame_samples;
+    const uint32_t frameq = (uint32_t)frame >> 2;
+    uint32_t fshift = 0;
+    while ((1u << fshift) < frameq) ++fshift;
+    // the kernel finds a quad's frame with a shift and a mask: 512 and 256 samples today
+    if ((frame & 3) || (1u << fshift) != frameq)
+        return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s: frames of %lld samples: the cut kernel needs a power of two", who, (long long)frame);
+    struct Span { int64_t lo, hi; int64_t i; };
+    std::vector<Span> spans((size_t)n);
+    e->cut_segs.resize((size_t)n);
+    e->cut_work.clear();
+    for (int64_t i = 0; i < n; ++i) {
+        const vad_cut_item &it = items[i];
+        if (it.sample_offset < 0 || (it.sample_offset & 3))
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: its recording starts at sample %lld, not a multiple of 4", who,
+                           (long long)i, (long long)it.sample_offset);
+        if (it.first_frame < 0 || it.nframes < 1)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: first_frame = %lld, nframes = %lld (>= 0 and >= 1)", who,
+                           (long long)i, (long long)it.first_frame, (long long)it.nframes);
+        // (all of it below 2^31 before it is multiplied: a segment that fits the block has fewer frames than the block has samples)
+        if (it.sample_offset > audio_samples || it.first_frame > audio_samples || it.nframes > audio_samples ||
+            it.sample_offset + (it.first_frame + it.nframes - 1) * (int64_t)hop + frame > audio_samples)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld (recording at %lld, frames %lld .. +%lld) leaves the audio block of %lld samples",
+                           who, (long long)i, (long long)it.sample_offset, (long long)it.first_frame, (long long)it.nframes, (long long)audio_samples);
+        if (it.channel != VAD_SCAN_MIX && (it.channel < 0 || it.channel >= channels))
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld names channel %d of %d (0 .. channels - 1, or VAD_SCAN_MIX)", who,
+                           (long long)i, it.channel, channels);
+        if (it.reserved != 0)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: reserved = %d must be 0", who, (long long)i, it.reserved);
+        const int64_t count = cut_samples(frame, it.nframes, hop, layout);
+        if (it.out_sample < 0 || (it.out_sample & 3) || it.out_sample > out_samples || count > out_samples - it.out_sample)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: out_sample = %lld (+%lld samples) must be a multiple of 4 inside "
+                           "the output of %lld samples", who, (long long)i, (long long)it.out_sample, (long long)count, (long long)out_samples);
+        if (count >= (int64_t)4 << 31)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld has %lld output samples, a segment may have less than 2^33", who,
+                           (long long)i, (long long)count);
+        spans[(size_t)i] = Span{it.out_sample, it.out_sample + count, i};
+        const uint32_t mode = channels == 1 ? vadk::SCAN_LEFT : it.channel == VAD_SCAN_MIX ? vadk::SCAN_MIX : (uint32_t)it.channel;
+        const uint32_t nq = (uint32_t)(count >> 2);
+        e->cut_segs[(size_t)i] = vadk::CutSeg{(uint32_t)((it.sample_offset + it.first_frame * (int64_t)hop) >> 2) | (mode << vadk::SCAN_MODE_SHIFT), nq,
+                                              (uint64_t)it.out_sample >> 2};
+        for (uint32_t q = 0; q < nq; q += vadk::CUT_WG_QUADS) e->cut_work.push_back(vadk::CutWork{(uint32_t)i, q});
+        if (e->cut_work.size() > (size_t)INT32_MAX)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d samples in one call", who, VAD_CUT_WG_SAMPLES);
+    }
+    std::sort(spans.begin(), spans.end(), [](const Span &a, const Span &b) { return a.lo < b.lo; });
+    for (size_t k = 1; k < spans.size(); ++k)
+        if (spans[k].lo < spans[k - 1].hi)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output ranges of segments %lld and %lld overlap", who,
+                           (long long)spans[k - 1].i, (long long)spans[k].i);
+    if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    const size_t ab = (size_t)audio_samples * (size_t)fbytes, ob = out_fmt == VAD_CUT_PCM16 ? 2 : 4;
+    const void *d_audio = audio;
+    void *d_out = out;
+    const int64_t out_lo = spans.front().lo, out_hi = spans.back().hi;
+    if (DEV) {
+        if (!audio) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+        const uintptr_t align = channels == 2 ? 8 : 4;
+        if (reinterpret_cast<uintptr_t>(audio) & (align - 1))
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the audio block must be %d-byte aligned", who, (int)align);
+        if (reinterpret_cast<uintptr_t>(out) & 15)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output must be 16-byte aligned", who);
+    } else {
+        if (!audio) {
+            // the block that the last scan uploaded is still in device memory: it crosses the link once
+            if (!e->audio_resident)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the engine holds no resident block: no vad_scan or "
+                               "vad_scan_channels has uploaded one", who);
+            if (e->audio_fmt != fmt)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the resident block has frame format %d, not %d", who,
+                               e->audio_fmt, fmt);
+            if (e->audio_channels != channels)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the resident block has %d channels, not %d", who,
+                               e->audio_channels, channels);
+            if (e->audio_bytes != ab)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the resident block has %llu bytes, not the %llu of "
+                               "%lld samples", who, (unsigned long long)e->audio_bytes, (unsigned long long)ab, (long long)audio_samples);
+        } else {
+            e->audio_resident = false;
+            if (int rc = ensure(e, e->d_audio, e->d_audio_cap, ab + 16)) return rc;
+        }
+        if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, (size_t)(out_hi - out_lo) * ob)) return rc;
+        d_audio = e->d_audio;
+        d_out = e->d_cut_out;
+        // on the device the output starts at the first segment's first sample
+        for (vadk::CutSeg &sg : e->cut_segs) sg.quad_out -= (uint64_t)out_lo >> 2;
+    }
+    const size_t sb = sizeof(vadk::CutSeg) * (size_t)n, wb = sizeof(vadk::CutWork) * e->cut_work.size();
+    if (int rc = ensure(e, e->d_cut, e->d_cut_cap, sb + wb)) return rc;
+    if (!DEV && audio) {
+        HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, ab, hipMemcpyHostToDevice, s));
+        e->audio_resident = true;
+        e->audio_bytes = ab; e->audio_channels = channels; e->audio_fmt = fmt;
+    }
+    HIP_TRY(e, hipMemcpyAsync(e->d_cut, e->cut_segs.data(), sb, hipMemcpyHostToDevice, s));
+    HIP_TRY(e, hipMemcpyAsync(e->d_cut + sb, e->cut_work.data(), wb, hipMemcpyHostToDevice, s));
+    vadk::CutArgs a{};
+    a.audio = d_audio;
+    a.out = d_out;
+    a.segs = reinterpret_cast<const vadk::CutSeg *>(e->d_cut);
+    a.work = reinterpret_cast<const vadk::CutWork *>(e->d_cut + sb);
+    a.audio_bytes = (uint32_t)ab;
+    a.nwork = (uint32_t)e->cut_work.size();
+    a.hopq = (uint32_t)hop >> 2;
+    a.frame_shift = layout == VAD_CUT_FRAMES ? fshift : 31u;
+    a.fmt = fmt;
+    a.channels = channels;
+    a.out_fmt = out_fmt;
+    a.thresh = thr;
+    const hipError_t r = vadk_launch_scan_cut(&a, s);
+    if (DEV) {
+        // the launch reads the engine's tables: the next scan or cut waits for it, as behind vad_scan_device
+        if (!e->scan_done) HIP_TRY(e, hipEventCreateWithFlags(&e->scan_done, hipEventDisableTiming));
+        HIP_TRY(e, hipEventRecord(e->scan_done, s));
+        e->scan_pending = true;
+        if (r != hipSuccess) return e->hip_fail(r, "kernel launch (scan cut)");
+        return VAD_OK;
+    }
+    if (r != hipSuccess) return e->hip_fail(r, "kernel launch (scan cut)");
+    // only speech crosses the link back: one copy per run of adjoining segments (packed payloads: one), the gaps stay the caller's
+    for (size_t k = 0; k < spans.size();) {
+        size_t m = k + 1;
+        while (m < spans.size() && spans[m].lo == spans[m - 1].hi) ++m;
+        HIP_TRY(e, hipMemcpyAsync(static_cast<uint8_t *>(out) + (size_t)spans[k].lo * ob, static_cast<uint8_t *>(d_out) + (size_t)(spans[k].lo - out_lo) * ob,
+                                  (size_t)(spans[m - 1].hi - spans[k].lo) * ob, hipMemcpyDeviceToHost, s));
+        k = m;
+    }
+    HIP_TRY(e, hipStreamSynchronize(s));
+    return VAD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t vad_cut_samples(const vad_engine *e, int64_t nframes, int32_t hop, int32_t layout) {
+    if (!e || nframes < 1 || hop < 4 || (hop & 3) || (layout != VAD_CUT_FRAMES && layout != VAD_CUT_RANGE)) return -1;
+    if (nframes > (INT64_MAX >> 1) / std::max<int64_t>(hop, e->frame_samples)) return -1;
+    return cut_samples(e->frame_samples, nframes, hop, layout);
+}
+
+int vad_scan_cut(vad_engine *e, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt,
+                 int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *out, int64_t out_samples) {
+    return cut_run<false>(e, "vad_scan_cut", items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, out,
+                          out_samples, nullptr);
+}
+
+int vad_scan_cut_device(vad_engine *e, const vad_cut_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
+                        int frame_fmt, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *d_out, int64_t out_samples,
+                        void *stream) {
+    return cut_run<true>(e, "vad_scan_cut_device", items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt,
+                         d_out, out_samples, stream);
 }
 
 // ---- pipelined host ingest ---------------------------------------------------------------------------------------

@@ -237,6 +237,40 @@ struct ScanArgs {
     int32_t channels;         // interleaved channels of the block: 2, or 0 / 1 = mono
 };
 
+// finished segments cut out of a scanned block (csrc/scan_cut.hip: vadk_scan_cut; vad_scan_cut).  The unit is the loader's quad:
+// output quad oq of a segment comes from input quad quad_in + (oq >> frame_shift) * hopq + (oq & (frame / 4 - 1)) - the segment's
+// frames back to back (VAD_CUT_FRAMES) - or from quad_in + oq (VAD_CUT_RANGE: frame_shift = 31, hopq unused), and goes to quad
+// quad_out + oq of the output.  A workgroup of CUT_THREADS threads serves CUT_WG_QUADS consecutive output quads of ONE segment in
+// CUT_PASSES passes of one quad per thread; the host lists the workgroups (CutWork), so no thread searches the segment table.
+constexpr int CUT_THREADS = 256;
+constexpr int CUT_PASSES = 4;
+constexpr int CUT_WG_QUADS = CUT_THREADS * CUT_PASSES;
+struct CutSeg {
+    uint32_t quad_in;         // (sample_offset + first_frame * hop) / 4 | the channel mode << SCAN_MODE_SHIFT, as ScanItem::quad0
+    uint32_t nquads;          // output quads of the segment, < 2^31
+    uint64_t quad_out;        // out_sample / 4
+};
+static_assert(sizeof(CutSeg) == 16, "CutSeg layout");
+struct CutWork {
+    uint32_t seg;             // index into the segment table
+    uint32_t quad0;           // first output quad of this workgroup's share, a multiple of CUT_WG_QUADS
+};
+static_assert(sizeof(CutWork) == 8, "CutWork layout");
+struct CutArgs {
+    const void *audio;        // the block, in its wire format
+    void *out;                // int16 or float32 samples
+    const CutSeg *segs;
+    const CutWork *work;      // [nwork]: one entry per workgroup
+    uint32_t audio_bytes;     // the buffer descriptor's range
+    uint32_t nwork;
+    uint32_t hopq;            // hop / 4
+    uint32_t frame_shift;     // log2(frame / 4), or 31: the sample range once
+    int32_t fmt;              // vad_frame_format
+    int32_t channels;         // 1 or 2
+    int32_t out_fmt;          // 0 = int16 PCM, 1 = float32
+    float thresh;             // denoise gate, < 0 = off
+};
+
 // resampler launch parameters (csrc/resample.hip)
 struct ResampleSeg {
     const float *wstream;     // folded operator (pack_weights.cpp: pack_resample_operator)

@@ -62,7 +62,8 @@ class Engine:
         self._h = C.c_void_p()
         self._tickets = {}                  # ticket -> the buffers a pipelined call still reads (submit / collect)
         self._scan_block = None             # scan(): the page-locked block the recordings are packed into ...
-        self._scan_lock = threading.Lock()  # ... held from the packing to the return of vad_scan: engines are shared between threads
+        self._scan_lock = threading.RLock()  # ... held from the packing to the return of vad_scan: engines are shared between threads
+        self._scan_last = None              # what scan() packed last (cut(audio=None) cuts that block): see scan_session()
         self.last_tick_us = (0.0, 0.0, 0.0)
         self.last_tick_dropped = 0
         self.last_tick_staged_next = 0
@@ -384,10 +385,13 @@ class Engine:
             seg = np.zeros(nf, np.int32)
             thr = -1.0 if denoise is None else float(denoise)
             out = (_ptr(start, C.c_int64), _ptr(probs, C.c_float), _ptr(ev, C.c_uint8), _ptr(seg, C.c_int32))
+            self._scan_last = None
             if two:
                 self._check(self._lib.vad_scan_channels(self._h, items, n * per, block.ctypes.data_as(C.c_void_p), total, 2, fmt, hop, thr, *out))
             else:
                 self._check(self._lib.vad_scan(self._h, items, n, block.ctypes.data_as(C.c_void_p), total, fmt, hop, thr, *out))
+            if nf:                          # (a scan without a frame uploads nothing)
+                self._scan_last = {"samples": total, "channels": 2 if two else 1, "fmt": fmt, "offsets": offs, "lengths": lens}
         if split:
             cut = lambda a: [a[start[2 * i]:start[2 * i + 2]].reshape(2, -1) for i in range(n)]
         else:
@@ -429,6 +433,107 @@ class Engine:
         thr = -1.0 if denoise is None else float(denoise)
         self._check(self._lib.vad_scan_device(self._h, items, s.size, d_audio, int(audio_samples), fmt, hop, thr, _ptr(start, C.c_int64),
                                               d_probs, d_events or None, d_seg or None, stream or None))
+        return start
+
+    # ------------------------------------------------------------------ finished segments' audio
+    def scan_session(self):
+        """The lock that makes packing + scanning one critical section, re-entrant: ``with engine.scan_session():`` around a
+        ``scan`` and the ``cut(audio=None)`` behind it keeps another thread's scan from replacing the block in between."""
+        return self._scan_lock
+
+    @property
+    def last_scan(self) -> Optional[dict]:
+        """What ``scan`` packed last - ``samples``, ``channels``, ``fmt``, ``offsets``, ``lengths`` (sample frames of the block) -
+        or None; meaningful inside ``scan_session()``."""
+        return self._scan_last
+
+    def cut_samples(self, nframes: int, hop: Optional[int] = None, layout="frames") -> int:
+        """Samples of a segment of ``nframes`` frames (``vad_cut_samples``): ``nframes * frame_samples`` for ``"frames"``,
+        ``(nframes - 1) * hop + frame_samples`` for ``"range"``."""
+        hop = self.frame_samples // 2 if hop is None else int(hop)
+        n = int(self._lib.vad_cut_samples(self._h, int(nframes), hop, self._cut_enum(_ffi.CUT_LAYOUTS, "layout", layout)))
+        if n < 0:
+            raise AudioProcessingError(f"Model prediction failed: bad frame count, hop or layout ({nframes}, {hop}, {layout!r})")
+        return n
+
+    @staticmethod
+    def _cut_enum(table, what, v) -> int:
+        if isinstance(v, str) and v in table:
+            return table[v]
+        raise AudioProcessingError(f"Model prediction failed: {what} is one of {sorted(table)}, got {v!r}")
+
+    def _cut_items(self, segments, hop: int, layout: int, channels: int, out_samples=None):
+        """segments: (sample_offset, first_frame, nframes[, channel]) each -> (items, out_start [n + 1]): payloads packed in the
+        order listed, unless ``out_samples`` gives every segment's first output sample"""
+        segs = [tuple(sg) for sg in segments]
+        n = len(segs)
+        items = (_ffi.CutItem * max(1, n))()
+        start = np.zeros(n + 1, np.int64)
+        frame = self.frame_samples
+        for i, sg in enumerate(segs):
+            if len(sg) not in (3, 4):
+                raise AudioProcessingError(f"Model prediction failed: a segment is (sample_offset, first_frame, nframes[, channel]), got {sg!r}")
+            ch = (_ffi.VAD_SCAN_MIX if channels == 2 else 0) if len(sg) == 3 else self._scan_channel(sg[3])
+            nf = int(sg[2])
+            count = nf * frame if layout == _ffi.VAD_CUT_FRAMES else (nf - 1) * hop + frame
+            o = int(start[i]) if out_samples is None else int(out_samples[i])
+            items[i] = _ffi.CutItem(int(sg[0]), int(sg[1]), nf, o, ch, 0)
+            start[i + 1] = start[i] + max(count, 0)
+        return items, start
+
+    def cut(self, segments, hop: Optional[int] = None, law: Optional[str] = None, i16_scale: int = 32767, denoise: Optional[float] = 0.01,
+            layout="frames", out="pcm16", audio=None):
+        """The audio of finished segments (``vad_scan_cut``): ``segments`` lists ``(sample_offset, first_frame, nframes[, channel])``
+        - the recording's first sample frame in the block, the segment's first frame (``e - L + 1`` for an END at frame ``e`` with
+        ``seg_frames`` ``L``) and its length in frames; ``channel`` as in ``scan`` (default: ``"mix"`` of a two-channel block).
+        ``layout="frames"``: the frames back to back (the reference's ``voice_end`` payload), ``"range"``: the sample range once.
+        ``out="pcm16"``: int16, ``clip(x * 32767)`` toward zero - a WAV payload; ``"f32"``: the gated float32 the model read.
+        -> (data, start): the payloads packed in one array, segment i = ``data[start[i]:start[i + 1]]``.
+        ``audio=None``: the block ``scan`` packed last, which is still on the GPU - nothing is uploaded; format, channels and
+        size are that scan's (``law`` / ``i16_scale`` are ignored).  Another thread's ``scan`` would replace the block: hold
+        ``scan_session()`` around the scan and the cut.  ``audio``: a block of its own, a 1-D array or a C-contiguous
+        ``[nsamples, 2]`` array (float32, int16, or uint8 codes with ``law``); it is uploaded and becomes the resident block."""
+        lay, of = self._cut_enum(_ffi.CUT_LAYOUTS, "layout", layout), self._cut_enum(_ffi.CUT_OUTPUTS, "out", out)
+        hop = self.frame_samples // 2 if hop is None else int(hop)
+        with self._scan_lock:
+            if audio is None:
+                last = self._scan_last
+                if last is None:
+                    raise AudioProcessingError("Model prediction failed: cut(audio=None) follows a scan() of this engine that uploaded a block")
+                total, channels, fmt, ptr = last["samples"], last["channels"], last["fmt"], None
+            else:
+                block = np.asarray(audio)
+                g711 = _law_format(law, block)
+                if g711 is None and block.dtype not in _FMT:
+                    block = block.astype(np.float32)
+                if block.ndim not in (1, 2) or (block.ndim == 2 and block.shape[1] != 2):
+                    raise AudioProcessingError(f"Model prediction failed: the audio block is 1-D or [nsamples, 2], got {block.shape}")
+                block = np.ascontiguousarray(block)
+                total, channels = int(block.shape[0]), block.ndim
+                fmt = g711 if g711 is not None else _FMT[block.dtype]
+                if fmt == _ffi.VAD_FMT_I16_32767 and i16_scale == 32768:
+                    fmt = _ffi.VAD_FMT_I16_32768
+                ptr = block.ctypes.data_as(C.c_void_p)
+                self._scan_last = None      # the engine's resident block is this one now, not the last scan's
+            items, start = self._cut_items(segments, hop, lay, channels)
+            data = np.empty(int(start[-1]), np.int16 if of == _ffi.VAD_CUT_PCM16 else np.float32)
+            thr = -1.0 if denoise is None else float(denoise)
+            self._check(self._lib.vad_scan_cut(self._h, items, len(start) - 1, ptr, total, channels, fmt, hop, thr, lay, of,
+                                               data.ctypes.data_as(C.c_void_p), data.size))
+        return data, start
+
+    def cut_device(self, segments, d_audio: int, audio_samples: int, d_out: int, out_samples: int, hop: Optional[int] = None,
+                   fmt: int = _ffi.VAD_FMT_F32, channels: int = 1, denoise: Optional[float] = 0.01, layout="frames", out="pcm16",
+                   stream: int = 0, out_start=None) -> np.ndarray:
+        """``cut`` on device pointers (integers; ``vad_scan_cut_device``): the block at ``d_audio`` (4-byte aligned, 8 for two
+        channels), the payloads to ``d_out`` (16-byte aligned, room for ``out_samples`` samples), packed in the order listed
+        or at ``out_start[i]`` (multiples of 4).  Asynchronous on ``stream``.  -> start [n + 1] of the packed order."""
+        lay, of = self._cut_enum(_ffi.CUT_LAYOUTS, "layout", layout), self._cut_enum(_ffi.CUT_OUTPUTS, "out", out)
+        hop = self.frame_samples // 2 if hop is None else int(hop)
+        items, start = self._cut_items(segments, hop, lay, int(channels), out_start)
+        thr = -1.0 if denoise is None else float(denoise)
+        self._check(self._lib.vad_scan_cut_device(self._h, items, len(start) - 1, d_audio or None, int(audio_samples), int(channels), int(fmt),
+                                                  hop, thr, lay, of, d_out or None, int(out_samples), stream or None))
         return start
 
     # ------------------------------------------------------------------ tick assembler (shared-pool serving)

@@ -1,4 +1,5 @@
-"""Whole recordings -> speech segments: the corpus caller's face of ``Engine.scan`` (``vad_scan``, include/vad_engine.h).
+"""Whole recordings -> speech segments, and their audio: the corpus caller's face of ``Engine.scan`` and ``Engine.cut``
+(``vad_scan``, ``vad_scan_cut``, include/vad_engine.h).
 
 ``VADWrapper.process_audio_data`` stays on its own path (its callback-abort contract needs the frame-by-frame replay); this
 module is for callers who hold many finished recordings of different lengths and want the segments of each.
@@ -76,4 +77,75 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
             else:
                 sg = speech_segments(e, g, frame, hop)
                 out[i] = [sg] if split else sg
+    return out
+
+
+def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
+                   law: Optional[str] = None, channel="mix", layout: str = "frames", wav: bool = True) -> List:
+    """``scan_recordings`` with each finished segment's audio: per recording ``[(start_sample, end_sample, payload), ...]`` (per
+    channel for ``"split"``, as there).  ``payload`` is what ``VADWrapper``'s ``voice_end`` callback delivers for the same
+    recording - the segment's frames back to back, decoded, mixed and gated as the model read them, as 16-bit PCM behind the WAV
+    header of ``config.output_wav_sample_rate`` - or, with ``wav=False``, the int16 samples themselves; ``layout="range"`` gives
+    the samples ``[start_sample, end_sample)`` once.  The corpus crosses the link once: one scan, then one cut of the block that
+    the scan left on the GPU (``Engine.cut(audio=None)``, under ``Engine.scan_session()``), and one copy back of the speech alone
+    - two of each for a corpus of 1-D and 2-D recordings."""
+    from .pool import default_pool, resolve_model_path
+    from .utils.wav_writer import WAVWriter
+    split = isinstance(channel, str) and channel == "split"
+    if not (channel in ("mix", "split") if isinstance(channel, str) else isinstance(channel, (int, np.integer)) and int(channel) in (0, 1)):
+        raise ConfigurationError("channel", repr(channel), f"cut_recordings: channel is 'mix', 0, 1 or 'split' for the whole corpus, got {channel!r}")
+    if layout not in _ffi.CUT_LAYOUTS:
+        raise ConfigurationError("layout", repr(layout), f"cut_recordings: layout is 'frames' or 'range', got {layout!r}")
+    cfg = config or VADConfig()
+    if engine is None:
+        engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
+    frame = engine.frame_samples
+    if cfg.buffer_size != frame:
+        raise ConfigurationError(f"cut_recordings frames at the model's frame size: buffer_size = {cfg.buffer_size}, "
+                                 f"the engine's frames have {frame} samples")
+    hop = frame // 2 if hop is None else int(hop)
+    recordings = [np.asarray(r) for r in recordings]
+    if not recordings:
+        return []
+    writer = WAVWriter(cfg.output_wav_sample_rate, 16, 1)
+    denoise = 0.01 if cfg.enable_denoising else None
+    out: List = [None] * len(recordings)
+    for two in (False, True):
+        idx = [i for i, r in enumerate(recordings) if (r.ndim == 2) == two]
+        if not idx:
+            continue
+        per = 2 if two and split else 1
+        chans = (0, 1) if per == 2 else (channel if two else 0,)
+        slots = engine.open_streams(len(idx) * per)
+        try:
+            engine.set_thresholds_many(slots, (cfg.vad_start_probability, cfg.vad_end_probability, cfg.voice_start_ratio,
+                                               cfg.voice_end_ratio, cfg.voice_start_frame_count, cfg.voice_end_frame_count))
+            with engine.scan_session():
+                _probs, ev, seg = engine.scan(np.asarray(slots).reshape(len(idx), per) if per == 2 else slots, [recordings[i] for i in idx],
+                                              hop=hop, law=law, denoise=denoise, channel=channel)
+                # (recording, channel) -> its sample ranges; the cut's table lists them in that order
+                ranges = [[speech_segments(e[c], g[c], frame, hop) if per == 2 else speech_segments(e, g, frame, hop) for c in range(per)]
+                          for e, g in zip(ev, seg)]
+                table = [(int(engine.last_scan["offsets"][k]), a // hop, (b - a - frame) // hop + 1, chans[c])
+                         for k, rc in enumerate(ranges) for c, rg in enumerate(rc) for a, b in rg]
+                if table:
+                    data, start = engine.cut(table, hop=hop, denoise=denoise, layout=layout)
+        finally:
+            for s in slots:
+                engine.close_stream(int(s))
+        j = 0
+        for i, rc in zip(idx, ranges):
+            lists = []
+            for rg in rc:
+                one = []
+                for a, b in rg:
+                    pcm = data[start[j]:start[j + 1]]
+                    j += 1
+                    if wav:
+                        raw = pcm.tobytes()
+                        one.append((a, b, writer.header(len(raw)) + raw))
+                    else:
+                        one.append((a, b, pcm.copy()))
+                lists.append(one)
+            out[i] = lists if split else lists[0]
     return out

@@ -322,6 +322,62 @@ VAD_API int vad_scan_channels_device(vad_engine *e, const vad_scan_ch_item *item
 VAD_API int vad_debug_scan_launch_frames(vad_engine *e, int32_t frames);
 
 /*
+ * The audio of finished segments, cut out of a scanned block: the second pass behind vad_scan / vad_scan_channels.  The
+ * reference's product is a segment's audio - VADProcessor._finalize_voice_segment concatenates the segment's processed frames and
+ * hands WAVWriter.write_wav_data(...) to voice_end_callback (core/silero_model.py, utils/wav_writer.py:41); the streaming side
+ * delivers that through vad_tick_take_segment*, this is the corpus side.  A kernel gathers each listed segment's samples from the
+ * block in its wire format, decodes, channel-selects and gates them exactly as the model's loader did - a sample of the payload is
+ * bit for bit the float32 the model read: s / 32767 or s / 32768, the G.711 value, (L + R) * 0.5f for VAD_SCAN_MIX, then
+ * |x| > denoise_thresh ? x : 0 (denoise_thresh < 0: no gate) - and writes them packed.  Only speech crosses the link back.
+ *   A segment: an END event at frame e of a recording with seg_frames L covers the frames first_frame = e - L + 1 .. e; frame t of
+ * a recording starts at sample frame sample_offset + t * hop of the block (sample_offset: the RECORDING's, as in its scan item).
+ *   layout: VAD_CUT_FRAMES - the L frames back to back, L * frame samples, a sample once per frame that holds it: the bytes of the
+ * reference's voice_end payload.  VAD_CUT_RANGE - the sample range once, (L - 1) * hop + frame samples.  vad_cut_samples gives
+ * either count (-1: nframes < 1, hop < 4 or not a multiple of 4, an unknown layout).
+ *   out_fmt: VAD_CUT_PCM16 - int16, np.clip(x * 32767, -32768, 32767).astype(np.int16): one float32 multiply, the clamp, the
+ * conversion toward zero (a WAV payload behind a 44-byte header).  VAD_CUT_F32 - the gated value itself, what
+ * vad_tick_take_segment keeps.  Segment i's samples go to out[out_sample .. out_sample + vad_cut_samples(..) - 1]; out holds
+ * out_samples samples, and samples outside every segment's range are not written.
+ *   audio: the block, as vad_scan_channels takes it (channels = 1: vad_scan's).  vad_scan_cut with audio == NULL cuts the block that
+ * this engine's last vad_scan / vad_scan_channels (or vad_scan_cut with an audio) uploaded and that is still in device memory -
+ * this is how a corpus crosses the link once.  The engine remembers that block's size in bytes, channel count and frame format;
+ * audio_samples, channels and frame_fmt must name them, else - or with no such block - VAD_ERR_INVALID_ARG with a message that says
+ * which it was.  With an audio the call uploads it, and it becomes the resident block.
+ *   Works on every engine, Silero V4 and VAD_ENGINE_SHARED_GPU included: only vad_info.frame_samples enters, no model kernel
+ * runs and no stream is touched.  Like the scans, a call first waits for the launches of an earlier vad_scan*_device /
+ * vad_scan_cut_device (they read the engine's tables).
+ *   VAD_ERR_INVALID_ARG, each with a message, and nothing is written: layout, out_fmt or frame_fmt out of range; channels outside
+ * {1, 2}; hop < 4 or not a multiple of 4; a sample_offset that is negative or not a multiple of 4; first_frame < 0 or nframes < 1; a
+ * segment whose last sample frame sample_offset + (first_frame + nframes - 1) * hop + frame exceeds audio_samples; a channel out of
+ * range; a non-zero reserved; an out_sample that is negative, not a multiple of 4, or with its segment's samples past
+ * out_samples; two segments whose output ranges overlap; a block of 2 GiB or more (a segment of 2^33 samples or more).  n == 0:
+ * VAD_OK.  A float32 block with non-finite samples: what VAD_CUT_PCM16 writes for such a sample is unspecified, the call completes
+ * normally - the segment table is the caller's.
+ *   vad_scan_cut_device: d_audio (4-byte aligned, 8 for two channels) and d_out (16-byte aligned) live on the engine's GPU; enqueues
+ * on `stream` (NULL = the engine's own) and returns.
+ *   A workgroup of the kernel serves VAD_CUT_WG_SAMPLES consecutive output samples of one segment.
+ *   VAD_ABI_VERSION is unchanged: the presence of vad_scan_cut is how a caller detects the feature.
+ */
+enum { VAD_CUT_FRAMES = 0, VAD_CUT_RANGE = 1 };
+enum { VAD_CUT_PCM16 = 0, VAD_CUT_F32 = 1 };
+#define VAD_CUT_WG_SAMPLES 4096
+typedef struct vad_cut_item {
+    int64_t sample_offset;   /* the RECORDING's first sample frame in the block (the scan item's); a multiple of 4 */
+    int64_t first_frame;     /* e - L + 1 for an END at frame e with seg_frames L */
+    int64_t nframes;         /* L >= 1 */
+    int64_t out_sample;      /* first output sample of this segment in out; a multiple of 4 */
+    int32_t channel;         /* 0 .. channels - 1, or VAD_SCAN_MIX, as vad_scan_ch_item */
+    int32_t reserved;        /* 0 */
+} vad_cut_item;
+VAD_API int64_t vad_cut_samples(const vad_engine *e, int64_t nframes, int32_t hop, int32_t layout);
+VAD_API int vad_scan_cut(vad_engine *e, const vad_cut_item *items, int64_t n, const void *audio /*or NULL*/, int64_t audio_samples,
+                         int32_t channels, int frame_fmt, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt,
+                         void *out, int64_t out_samples);
+VAD_API int vad_scan_cut_device(vad_engine *e, const vad_cut_item *items, int64_t n, const void *d_audio, int64_t audio_samples,
+                                int32_t channels, int frame_fmt, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt,
+                                void *d_out, int64_t out_samples, void *stream);
+
+/*
  * Pipelined host ingest.  vad_step* on host pointers are copy -> kernel -> copy -> wait; at 8 192 streams the PCIe copy is
  * 5-8 x the kernel, so a serving loop should overlap the copy of tick t+1 with the kernel of tick t:
  *

@@ -633,6 +633,171 @@ def scan_stereo():
     return out
 
 
+def scan_cut():
+    """Finished segments' audio (vad_scan_cut):
+    (a) the kernel alone, HIP events: 2 048 int16 recordings of 5 - 20 s in HBM, synthetic segments of 1 - 3 s that cover about half
+        of every recording, FRAMES layout at hop = frame / 2, PCM16 out.  The kernel is launched through the library's own
+        launcher (vadk_launch_scan_cut) on tables that already lie in device memory - built here as the engine builds them, and
+        the payload is compared with vad_scan_cut_device's - against hipMemcpyAsync device-to-device of the payload's byte count
+        in the same run (it reads and writes what the kernel gathers and writes: the yardstick, no code of the project).  The
+        whole call, vad_scan_cut_device with the upload of its tables, is timed beside them;
+    (b) host-inclusive: cut_recordings (interleaved int16 speech, mix, page-locked memory) against the same build's
+        scan_recordings followed by the numpy pass that produces the same bytes; runs interleaved, three each after two warm-ups."""
+    import ctypes as C
+    import time
+    import numpy as np
+    from cutter_vad_amd import VADConfig, _ffi, cut_recordings, scan_recordings
+    from cutter_vad_amd.utils.wav_writer import WAVWriter
+    out = []
+    eng = Engine(blob(5), max_streams=4096)
+    frame, hop = eng.frame_samples, eng.frame_samples // 2
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    n = 2048
+    rng = np.random.default_rng(n)
+    lens = rng.integers(5 * 16000, 20 * 16000 + 1, n)
+    offs = np.concatenate([[0], np.cumsum((lens[:-1] + 3) & ~3)])
+    total = int(offs[-1] + lens[-1])
+    d_audio = torch.randint(-3000, 3000, (total,), dtype=torch.int16, device="cuda")
+    segs = []
+    for o, k in zip(offs, lens):
+        nf, t = (int(k) - frame) // hop + 1, 0
+        while True:
+            L = int(rng.integers(16000 // hop, 3 * 16000 // hop))       # speech of 1 - 3 s, then as much silence
+            if t + L > nf:
+                break
+            segs.append((int(o), t, L))
+            t += 2 * L
+    out_samples = sum(L for _, _, L in segs) * frame
+    d_out = torch.empty(out_samples, dtype=torch.int16, device="cuda")
+    d_copy = torch.empty(out_samples, dtype=torch.int16, device="cuda")
+    ts = torch.cuda.Stream()
+
+    # the call builds its tables on the host and uploads them before the launch.  A matrix product on the same stream in front of
+    # the first event keeps the GPU busy meanwhile, so the events bracket the table's upload (16 bytes per segment, 8 per
+    # workgroup) and the kernel, not the host's loop; the ctypes items are built once, outside
+    items, _ = eng._cut_items(segs, hop, _ffi.VAD_CUT_FRAMES, 1)
+    busy = torch.randn(6144, 6144, device="cuda")
+
+    # the same tables as the engine's (vad_layout.h: CutSeg, CutWork, CutArgs), in device memory before the clock starts
+    wgq = _ffi.VAD_CUT_WG_SAMPLES // 4
+    seg_t = np.zeros(len(segs), np.dtype([("quad_in", "<u4"), ("nquads", "<u4"), ("quad_out", "<u8")]))
+    work, o = [], 0
+    for i, (off, first, L) in enumerate(segs):
+        seg_t[i] = ((off + first * hop) // 4, L * frame // 4, o // 4)
+        work += [(i, q) for q in range(0, L * frame // 4, wgq)]
+        o += L * frame
+    work_t = np.array(work, np.uint32)
+    d_seg, d_work = torch.from_numpy(seg_t.view(np.uint8)).cuda(), torch.from_numpy(work_t.view(np.uint8).reshape(-1)).cuda()
+    d_out2 = torch.zeros(out_samples, dtype=torch.int16, device="cuda")
+
+    class CutArgs(C.Structure):
+        _fields_ = [("audio", C.c_void_p), ("out", C.c_void_p), ("segs", C.c_void_p), ("work", C.c_void_p), ("audio_bytes", C.c_uint32),
+                    ("nwork", C.c_uint32), ("hopq", C.c_uint32), ("frame_shift", C.c_uint32), ("fmt", C.c_int32), ("channels", C.c_int32),
+                    ("out_fmt", C.c_int32), ("thresh", C.c_float)]
+
+    args = CutArgs(d_audio.data_ptr(), d_out2.data_ptr(), d_seg.data_ptr(), d_work.data_ptr(), 2 * total, len(work), hop // 4,
+                   (frame // 4).bit_length() - 1, _ffi.VAD_FMT_I16_32767, 1, _ffi.VAD_CUT_PCM16, 0.01)
+    launch = eng._lib.vadk_launch_scan_cut
+    launch.argtypes, launch.restype = [C.POINTER(CutArgs), C.c_void_p], C.c_int
+
+    def one(kind):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        with torch.cuda.stream(ts):
+            torch.mm(busy, busy)
+        e0.record(ts)
+        if kind == "kernel":
+            assert launch(C.byref(args), ts.cuda_stream) == 0
+        elif kind == "call":
+            rc = eng._lib.vad_scan_cut_device(eng.handle, items, len(segs), d_audio.data_ptr(), total, 1, _ffi.VAD_FMT_I16_32767, hop, 0.01,
+                                              _ffi.VAD_CUT_FRAMES, _ffi.VAD_CUT_PCM16, d_out.data_ptr(), out_samples, ts.cuda_stream)
+            assert rc == 0, rc
+        else:
+            assert hip.hipMemcpyAsync(d_copy.data_ptr(), d_out.data_ptr(), 2 * out_samples, 3, ts.cuda_stream) == 0
+        e1.record(ts)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e-3
+
+    kinds = ("kernel", "call", "memcpy_d2d")
+    for _ in range(2):
+        for k in kinds:
+            one(k)
+    assert torch.equal(d_out, d_out2), "the launcher on the tables built here must write the call's payload"
+    runs = {k: [] for k in kinds}
+    for _ in range(3):
+        for k in kinds:
+            runs[k].append(one(k))
+    moved = 4.0 * out_samples                                           # int16 gathered + int16 written
+    row = {"config": f"scan_cut (a): kernel alone (kernel), and vad_scan_cut_device with the upload of its tables (call), {n} int16 recordings of 5 - 20 s in HBM, {len(segs)} segments over "
+                     "about half of every recording, FRAMES at hop = frame / 2, PCM16 out",
+           "segments": len(segs), "audio_MB": total * 2 / 1e6, "payload_MB": out_samples * 2 / 1e6,
+           "workgroups": sum(-(-L * frame // _ffi.VAD_CUT_WG_SAMPLES) for _, _, L in segs)}
+    row["table_MB"] = (16 * len(segs) + 8 * row["workgroups"]) / 1e6
+    for k, v in runs.items():
+        row[f"ms_{k}_runs"] = [r * 1e3 for r in v]
+        row[f"ms_{k}"] = float(np.median(v)) * 1e3
+        row[f"GBps_{k}"] = moved / float(np.median(v)) / 1e9
+    row["spread_memcpy_pct"] = 100.0 * (max(runs["memcpy_d2d"]) - min(runs["memcpy_d2d"])) / float(np.median(runs["memcpy_d2d"]))
+    row["kernel_rate_over_memcpy_rate"] = float(np.median(runs["memcpy_d2d"]) / np.median(runs["kernel"]))
+    row["call_rate_over_memcpy_rate"] = float(np.median(runs["memcpy_d2d"]) / np.median(runs["call"]))
+    out.append(row)
+    del d_audio, d_out, d_out2, d_copy
+    torch.cuda.empty_cache()
+
+    # (b) speech, so that the scan finds segments: the golden clip against itself 3 s later, cut at seeded places
+    gold = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "speech16k_i16.npz")
+    pcm = np.load(gold)["pcm"].astype(np.int16)
+    pair = np.stack([pcm, np.roll(pcm, 3 * 16000)], axis=1)
+    m = 256
+    rng = np.random.default_rng(m)
+    lens = rng.integers(5 * 16000, min(30 * 16000, pcm.size) + 1, m)
+    pad = (lens + 3) & ~3
+    offs = np.concatenate([[0], np.cumsum(pad[:-1])])
+    block = eng.pinned_array((int(offs[-1] + lens[-1]), 2), np.int16)
+    for o, k in zip(offs, lens):
+        a = int(rng.integers(0, pcm.size - int(k) + 1))
+        block[o:o + k] = pair[a:a + k]
+    recs = [block[o:o + k] for o, k in zip(offs, lens)]
+    cfg = VADConfig(vad_start_probability=0.4, vad_end_probability=0.3, voice_start_frame_count=6, voice_end_frame_count=12)
+    writer = WAVWriter(cfg.output_wav_sample_rate, 16, 1)
+
+    def route_cut():
+        t0 = time.perf_counter()
+        got = cut_recordings(recs, cfg, engine=eng)
+        return time.perf_counter() - t0, got
+
+    def route_numpy():
+        t0 = time.perf_counter()
+        got = []
+        for x, sg in zip(recs, scan_recordings(recs, cfg, engine=eng)):
+            one_rec = []
+            for a, b in sg:
+                v = np.mean(x[a:b].astype(np.float32) / np.float32(32767.0), axis=1)
+                v = np.where(np.abs(v) > np.float32(0.01), v, np.float32(0.0)).astype(np.float32)
+                fr = np.concatenate([v[t:t + frame] for t in range(0, b - a - frame + 1, hop)])
+                one_rec.append((a, b, writer.write_wav_data(fr)))
+            got.append(one_rec)
+        return time.perf_counter() - t0, got
+
+    (_, g1), (_, g2) = route_cut(), route_numpy()
+    assert g1 == g2, "the two routes must produce the same bytes"
+    route_cut(), route_numpy()
+    a, b = [], []
+    for _ in range(3):
+        a.append(route_cut()[0])
+        b.append(route_numpy()[0])
+    nseg = sum(len(g) for g in g1)
+    out.append({"config": f"scan_cut (b): host-inclusive, {m} interleaved int16 recordings of 5 - 30 s of speech (mix), page-locked host memory, "
+                          "client thresholds", "segments": nseg, "audio_MB": block.nbytes / 1e6,
+                "payload_MB": sum(len(w) - 44 for g in g1 for _, _, w in g) / 1e6, "s_cut_recordings_runs": a,
+                "s_scan_recordings_then_numpy_runs": b, "s_cut_recordings": float(np.median(a)),
+                "s_scan_recordings_then_numpy": float(np.median(b)), "spread_cut_pct": 100.0 * (max(a) - min(a)) / float(np.median(a)),
+                "ratio": float(np.median(b) / np.median(a))})
+    eng.close()
+    return out
+
+
 def single_stream_wrapper():
     """configs[0]: ONE stream through the drop-in VADWrapper (host framing + one launch + sync + callbacks per chunk)."""
     import time

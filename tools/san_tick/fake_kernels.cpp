@@ -123,6 +123,39 @@ extern "C" hipError_t vadk_launch_silero_v5_scan16(const StepParams *p, const Sc
     return hipSuccess;
 }
 
+// finished segments cut out of a block (csrc/scan_cut.hip: vadk_scan_cut), the kernel's arithmetic in plain C++, quad by quad as
+// its workgroups are listed: decode (s / 32767 or s / 32768 as IEEE quotients, G.711 / 32768), left | right | (L + R) * 0.5f, the
+// strict gate, then the float32 itself or clip(x * 32767, -32768, 32767) converted toward zero
+extern "C" hipError_t vadk_launch_scan_cut(const CutArgs *a, hipStream_t) {
+    const uint32_t fmask = a->frame_shift >= 31u ? 0x7fffffffu : (1u << a->frame_shift) - 1u;
+    const size_t ch = a->channels == 2 ? 2 : 1;
+    for (uint32_t b = 0; b < a->nwork; ++b) {
+        const CutWork w = a->work[b];
+        const CutSeg sg = a->segs[w.seg];
+        const uint32_t mode = sg.quad_in >> SCAN_MODE_SHIFT, qin = sg.quad_in & ((1u << SCAN_MODE_SHIFT) - 1u);
+        for (uint32_t oq = w.quad0; oq < w.quad0 + (uint32_t)CUT_WG_QUADS && oq < sg.nquads; ++oq) {
+            const uint32_t iq = qin + (oq >> a->frame_shift) * a->hopq + (oq & fmask);
+            for (int k = 0; k < 4; ++k) {
+                const size_t i = 4 * (size_t)iq + k, o = 4 * ((size_t)sg.quad_out + oq) + k;
+                if ((i + 1) * ch * (a->fmt == VAD_FMT_F32 ? 4 : a->fmt >= VAD_FMT_ULAW8 ? 1 : 2) > a->audio_bytes) return hipErrorInvalidValue;
+                float x;
+                if (ch == 1) x = first_sample(a->audio, i, a->fmt, 1);
+                else {
+                    const float l = first_sample(a->audio, 2 * i, a->fmt, 1), r = first_sample(a->audio, 2 * i + 1, a->fmt, 1);
+                    x = mode == SCAN_MIX ? (l + r) * 0.5f : mode == SCAN_RIGHT ? r : l;
+                }
+                if (a->thresh >= 0.f && !(std::fabs(x) > a->thresh)) x = 0.f;
+                if (a->out_fmt == VAD_CUT_F32) static_cast<float *>(a->out)[o] = x;
+                else {
+                    const float v = x * 32767.0f;
+                    static_cast<int16_t *>(a->out)[o] = (int16_t)(int)(v < -32768.0f ? -32768.0f : v > 32767.0f ? 32767.0f : v);
+                }
+            }
+        }
+    }
+    return hipSuccess;
+}
+
 extern "C" hipError_t vadk_launch_silero_v5_t16_rates(const StepParams *p, const RateParams *r, hipStream_t) {
     for (int k = 0; k < r->nseg; ++k) {
         StepParams q = *p;
