@@ -11,6 +11,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvad_engine.so")
 
@@ -135,6 +137,16 @@ VAD_CUT_WG_SAMPLES = 4096
 CUT_LAYOUTS = {"frames": VAD_CUT_FRAMES, "range": VAD_CUT_RANGE}
 CUT_OUTPUTS = {"pcm16": VAD_CUT_PCM16, "f32": VAD_CUT_F32}
 
+
+class Segment(C.Structure):
+    _fields_ = [("item", C.c_int32), ("first_frame", C.c_int32), ("nframes", C.c_int32), ("counted", C.c_int32),
+                ("mean_prob", C.c_float), ("max_prob", C.c_float)]
+
+
+# the same record as a numpy structured dtype: a table of vad_segment is np.ndarray(count, SEGMENT_DTYPE)
+SEGMENT_DTYPE = np.dtype([("item", np.int32), ("first_frame", np.int32), ("nframes", np.int32), ("counted", np.int32),
+                          ("mean_prob", np.float32), ("max_prob", np.float32)])
+
 VAD_WORK_START, VAD_WORK_END, VAD_WORK_CONTINUE, VAD_WORK_PAYLOAD, VAD_WORK_LONG = 1, 2, 4, 8, 16
 VAD_WORK_REJECTED = 32
 
@@ -218,6 +230,10 @@ SIGNATURES = {
                                C.c_int32, _vp, C.c_int64]),
     "vad_scan_cut_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_float,
                                       C.c_int32, C.c_int32, _vp, C.c_int64, _vp]),
+    "vad_segments_device": (C.c_int, [_vp, _vp, _vp, _vp, _i64p, C.c_int64, _vp, C.c_int64, _vp, _vp]),
+    "vad_scan_segments": (C.c_int, [_vp, C.POINTER(ScanChItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_float,
+                                    C.POINTER(Segment), C.c_int64, _i64p]),
+    "vad_scan_segments_read": (C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(Segment)]),
 }
 
 _lib = None

@@ -42,6 +42,7 @@ extern "C" hipError_t vadk_launch_silero_v5_t16_rates(const vadk::StepParams *p,
 extern "C" hipError_t vadk_launch_silero_v5_scan16(const vadk::StepParams *p, const vadk::ScanItem *items, const vadk::ScanArgs *a,
                                                    hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_cut(const vadk::CutArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_scan_segments(const vadk::SegArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_resample(const vadk::ResampleParams *p, hipStream_t stream);
 extern "C" hipError_t vadk_launch_slot_control(vadk::SmSlot *sm, float *state, const int32_t *d_slots, int n, int op,
                                                const vadk::SmSlot *def, const vad_thresholds *d_thr, int nthr, hipStream_t stream);
@@ -153,6 +154,14 @@ struct vad_engine {
     void *d_cut_out = nullptr; size_t d_cut_out_cap = 0;
     std::vector<vadk::CutSeg> cut_segs;
     std::vector<vadk::CutWork> cut_work;
+    // vad_segments_device / vad_scan_segments: the extraction's work area - out_start as int32 [n + 1] (the host copy as it was
+    // uploaded), then the chunk counts - and, for vad_scan_segments, the items' CSR positions, the count and the retained table
+    uint8_t *d_segwork = nullptr; size_t d_segwork_cap = 0;
+    std::vector<int32_t> seg_start;
+    std::vector<int64_t> seg_out_start;
+    long long *d_nsegs = nullptr; size_t d_nsegs_cap = 0;
+    vadk::SegRecord *d_segtab = nullptr; size_t d_segtab_cap = 0;
+    int64_t segtab_count = -1;               // records of the table in d_segtab; -1: none
     // G.711 frames expanded to int16 for the kernels whose loaders do not decode them (launch())
     int16_t *d_g711 = nullptr; size_t d_g711_cap = 0;
     // small calls (a few streams: the one-wrapper-per-client pattern): ONE pinned block in, ONE pinned block out
@@ -839,7 +848,7 @@ void vad_engine_destroy(vad_engine *e) {
     weights_release(e->d_wstream16x);
     weights_release(e->d_wstream16y);
     void *bufs[] = {e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots, e->d_g711,
-                    e->d_audio, e->d_items, e->d_cut, e->d_cut_out, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
+                    e->d_audio, e->d_items, e->d_cut, e->d_cut_out, e->d_segwork, e->d_nsegs, e->d_segtab, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->scan_done) (void)hipEventDestroy(e->scan_done);
@@ -1168,16 +1177,18 @@ int32_t scan_item_reserved(const vad_scan_ch_item &it) { return it.reserved; }
 // that the 16 streams of a tile end together; out0 = out_start[i] - out_base.  *total = frames of all recordings.
 // `who` = the entry point's name in the messages; channels: the block's interleaved channels (vad_scan: 1) - offsets, lengths
 // and hop count sample frames, and an item's channel (or VAD_SCAN_MIX) travels in the top bits of its quad0 (vad_layout.h).
+// own_start (vad_scan_segments, which has no out_start argument): the plan lays the results out itself - the items in the order
+// given, packed from 0 - and leaves the positions [n + 1] there; out_start is not looked at.
 template <class Item>
 int scan_plan(vad_engine *e, const char *who, const Item *items, int64_t n, int64_t audio_samples, int32_t channels, int fmt, int32_t hop,
-              const int64_t *out_start, int64_t out_base, int64_t *total) {
+              const int64_t *out_start, int64_t out_base, int64_t *total, std::vector<int64_t> *own_start = nullptr) {
     if (e->version != 5)
         return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s needs a Silero V5 engine; frame the recordings on the host and use vad_step_multi", who);
     if (e->shared_gpu)
         return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s runs on 16-stream tiles, which a VAD_ENGINE_SHARED_GPU engine "
                                             "does not use; frame the recordings on the host and use vad_step_multi", who);
     if (!e->d_wstream16) return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s: the engine has no 16-stream kernel; use vad_step_multi", who);
-    if (n < 0 || audio_samples < 0 || (n > 0 && (!items || !out_start)))
+    if (n < 0 || audio_samples < 0 || (n > 0 && (!items || (!out_start && !own_start))))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer or bad count", who);
     if (fmt < VAD_FMT_F32 || fmt > VAD_FMT_ALAW8)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: unknown frame format %d", fmt);
@@ -1193,6 +1204,7 @@ int scan_plan(vad_engine *e, const char *who, const Item *items, int64_t n, int6
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %llu bytes of audio exceed the 2 GiB one call may address", who,
                        (unsigned long long)((uint64_t)audio_samples * frame_bytes));
     e->scan_items.resize((size_t)n);
+    if (own_start) own_start->assign((size_t)n + 1, 0);
     std::vector<int64_t> slots((size_t)n);
     int64_t sum = 0;
     for (int64_t i = 0; i < n; ++i) {
@@ -1211,15 +1223,17 @@ int scan_plan(vad_engine *e, const char *who, const Item *items, int64_t n, int6
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: recording %lld: reserved = %d must be 0", who, (long long)i,
                            scan_item_reserved(it));
         const int64_t nf = scan_frames(it.nsamples, e->frame_samples, hop);
-        if (out_start[i] < out_base || out_start[i + 1] - out_start[i] != nf)
+        if (own_start) (*own_start)[(size_t)i + 1] = (*own_start)[(size_t)i] + nf;
+        else if (out_start[i] < out_base || out_start[i + 1] - out_start[i] != nf)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start gives recording %lld %lld entries, it has %lld frames", who,
                            (long long)i, (long long)(out_start[i + 1] - out_start[i]), (long long)nf);
-        if (out_start[i + 1] - out_base > INT32_MAX)
+        const int64_t pos = own_start ? (*own_start)[(size_t)i] : out_start[i] - out_base;
+        if (pos + nf > INT32_MAX)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 frames in one call", who);
         slots[(size_t)i] = it.slot;
         const uint32_t mode = channels == 1 ? vadk::SCAN_LEFT : ch == VAD_SCAN_MIX ? vadk::SCAN_MIX : (uint32_t)ch;
         e->scan_items[(size_t)i] = vadk::ScanItem{(int32_t)it.slot, (uint32_t)(it.sample_offset >> 2) | (mode << vadk::SCAN_MODE_SHIFT), (int32_t)nf,
-                                                  (uint32_t)(out_start[i] - out_base)};
+                                                  (uint32_t)pos};
         sum += nf;
     }
     if (int rc = check_slots(e, slots.data(), n)) return rc;
@@ -1291,7 +1305,26 @@ int vad_debug_scan_launch_frames(vad_engine *e, int32_t frames) {
 
 namespace {
 
-// vad_scan and vad_scan_channels: the block crosses the link once, in its wire format, interleaved as it is
+// a planned scan of host audio (vad_scan, vad_scan_channels, vad_scan_segments): the block crosses the link once, in its wire format,
+// interleaved as it is, and becomes the resident one; the launches write the engine's own d_probs / d_events / d_seg
+int scan_upload_launch(vad_engine *e, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t hop,
+                       float denoise_thresh, int64_t total) {
+    const size_t ab = (size_t)audio_samples * (size_t)channels * sample_bytes(frame_fmt);
+    e->audio_resident = false;
+    if (int rc = ensure(e, e->d_audio, e->d_audio_cap, ab + 16)) return rc;
+    if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
+    if (int rc = ensure(e, e->d_probs, e->d_probs_cap, sizeof(float) * (size_t)total)) return rc;
+    if (int rc = ensure(e, e->d_events, e->d_events_cap, (size_t)total)) return rc;
+    if (int rc = ensure(e, e->d_seg, e->d_seg_cap, sizeof(int32_t) * (size_t)total)) return rc;
+    // the audio crosses the link once, in its wire format
+    HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, ab, hipMemcpyHostToDevice, e->stream));
+    e->audio_resident = true;                // for a following vad_scan_cut(audio = NULL), whatever becomes of the launches
+    e->audio_bytes = ab; e->audio_channels = channels; e->audio_fmt = frame_fmt;
+    return scan_launches(e, e->d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, e->d_probs, e->d_events, e->d_seg, total, e->stream);
+}
+
+// vad_scan and vad_scan_channels
 template <class Item>
 int scan_host(vad_engine *e, const char *who, const Item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
               int frame_fmt, int32_t hop, float denoise_thresh, const int64_t *out_start, float *probs_out, uint8_t *events_out,
@@ -1306,20 +1339,7 @@ int scan_host(vad_engine *e, const char *who, const Item *items, int64_t n, cons
     if (int rc = scan_plan(e, who, items, n, audio_samples, channels, frame_fmt, hop, out_start, base, &total)) return rc;
     if (total == 0) return VAD_OK;
     if (!audio || !probs_out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    const size_t ab = (size_t)audio_samples * (size_t)channels * sample_bytes(frame_fmt);
-    e->audio_resident = false;
-    if (int rc = ensure(e, e->d_audio, e->d_audio_cap, ab + 16)) return rc;
-    if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
-    if (int rc = ensure(e, e->d_probs, e->d_probs_cap, sizeof(float) * (size_t)total)) return rc;
-    if (int rc = ensure(e, e->d_events, e->d_events_cap, (size_t)total)) return rc;
-    if (int rc = ensure(e, e->d_seg, e->d_seg_cap, sizeof(int32_t) * (size_t)total)) return rc;
-    // the audio crosses the link once, in its wire format
-    HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, ab, hipMemcpyHostToDevice, e->stream));
-    e->audio_resident = true;                // for a following vad_scan_cut(audio = NULL), whatever becomes of the launches
-    e->audio_bytes = ab; e->audio_channels = channels; e->audio_fmt = frame_fmt;
-    if (int rc = scan_launches(e, e->d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, e->d_probs, e->d_events, e->d_seg, total, e->stream))
-        return rc;
+    if (int rc = scan_upload_launch(e, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, total)) return rc;
     HIP_TRY(e, hipMemcpyAsync(probs_out + base, e->d_probs, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost, e->stream));
     if (events_out) HIP_TRY(e, hipMemcpyAsync(events_out + base, e->d_events, (size_t)total, hipMemcpyDeviceToHost, e->stream));
     if (seg_frames_out) HIP_TRY(e, hipMemcpyAsync(seg_frames_out + base, e->d_seg, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, e->stream));
@@ -1578,6 +1598,145 @@ int vad_scan_cut_device(vad_engine *e, const vad_cut_item *items, int64_t n, con
                         void *stream) {
     return cut_run<true>(e, "vad_scan_cut_device", items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt,
                          d_out, out_samples, stream);
+}
+
+// ---- the segment table of a scan (vad_segments_device, vad_scan_segments) -----------------------------------------
+}  // extern "C"
+
+namespace {
+
+static_assert(sizeof(vad_segment) == sizeof(vadk::SegRecord), "the header's record is the kernel's");
+
+// the launches of an extraction on `s`: out_start (checked: starts at 0 or above, never decreases, ends at 2^31 - 1 or below) goes
+// to the device as int32 next to the chunk counts; seg_cap >= 0, the table at d_segs has room for it
+int seg_launches(vad_engine *e, const uint8_t *d_events, const int32_t *d_seg, const float *d_probs, const int64_t *out_start, int64_t n,
+                 vadk::SegRecord *d_segs, int64_t seg_cap, long long *d_nsegs, hipStream_t s) {
+    const int64_t total = n > 0 ? out_start[n] : 0;
+    vadk::SegArgs a{};
+    a.first = n > 0 ? (uint32_t)out_start[0] : 0u;
+    a.total = (uint32_t)total;
+    a.nchunks = (uint32_t)((total + vadk::SEG_WG_FRAMES - 1) / vadk::SEG_WG_FRAMES);
+    a.seg_cap = (uint32_t)std::min<int64_t>(seg_cap, INT32_MAX);
+    a.n = (int32_t)n;
+    a.events = d_events;
+    a.seg_frames = d_seg;
+    a.probs = d_probs;
+    a.segs = d_segs;
+    a.nsegs = d_nsegs;
+    if (a.nchunks) {
+        const size_t sb = (sizeof(int32_t) * (size_t)(n + 1) + 15) & ~(size_t)15;
+        if (int rc = ensure(e, e->d_segwork, e->d_segwork_cap, sb + sizeof(uint32_t) * (size_t)a.nchunks)) return rc;
+        e->seg_start.resize((size_t)n + 1);
+        for (int64_t i = 0; i <= n; ++i) e->seg_start[(size_t)i] = (int32_t)out_start[i];
+        HIP_TRY(e, hipMemcpyAsync(e->d_segwork, e->seg_start.data(), sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice, s));
+        a.out_start = reinterpret_cast<const int32_t *>(e->d_segwork);
+        a.chunk = reinterpret_cast<uint32_t *>(e->d_segwork + sb);
+    }
+    const hipError_t r = vadk_launch_scan_segments(&a, s);
+    if (r != hipSuccess) return e->hip_fail(r, "kernel launch (scan segments)");
+    return VAD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vad_segments_device(vad_engine *e, const uint8_t *d_events, const int32_t *d_seg_frames, const float *d_probs, const int64_t *out_start,
+                        int64_t n, vad_segment *d_segs, int64_t seg_cap, int64_t *d_nsegs, void *stream) {
+    static const char *who = "vad_segments_device";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    if (n < 0 || seg_cap < 0)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n = %lld, seg_cap = %lld: bad count", who, (long long)n, (long long)seg_cap);
+    if (n > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 items", who);
+    if ((n > 0 && !out_start) || !d_nsegs || (seg_cap > 0 && !d_segs))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if (n > 0 && out_start[0] < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start[0] is negative", who);
+    for (int64_t i = 0; i < n; ++i)
+        if (out_start[i + 1] < out_start[i])
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start decreases at item %lld (%lld after %lld)", who, (long long)i,
+                           (long long)out_start[i + 1], (long long)out_start[i]);
+    const int64_t total = n > 0 ? out_start[n] : 0;
+    if (total > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 frames in one call", who);
+    if (total > 0 && (!d_events || !d_seg_frames || !d_probs))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if ((reinterpret_cast<uintptr_t>(d_events) & 15) || (reinterpret_cast<uintptr_t>(d_segs) & 15))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the events and the segment table must be 16-byte aligned", who);
+    if ((reinterpret_cast<uintptr_t>(d_seg_frames) & 3) || (reinterpret_cast<uintptr_t>(d_probs) & 3))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: seg_frames and probs must be 4-byte aligned", who);
+    if (reinterpret_cast<uintptr_t>(d_nsegs) & 7)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the count must be 8-byte aligned", who);
+    if (!e->scan_done) HIP_TRY(e, hipEventCreateWithFlags(&e->scan_done, hipEventDisableTiming));
+    const int rc = seg_launches(e, d_events, d_seg_frames, d_probs, out_start, n, reinterpret_cast<vadk::SegRecord *>(d_segs), seg_cap,
+                                reinterpret_cast<long long *>(d_nsegs), s);
+    // the launches read the engine's work area: the next scan, cut or extraction waits for them, as behind vad_scan_device
+    HIP_TRY(e, hipEventRecord(e->scan_done, s));
+    e->scan_pending = true;
+    return rc;
+}
+
+int vad_scan_segments(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
+                      int frame_fmt, int32_t hop, float denoise_thresh, vad_segment *segs_out, int64_t seg_cap, int64_t *nsegs_out) {
+    static const char *who = "vad_scan_segments";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    // the CSR positions the caller of vad_scan_channels would have passed are the plan's to make: the items packed in their order
+    std::vector<int64_t> &start = e->seg_out_start;
+    int64_t total = 0;
+    if (int rc = scan_plan(e, who, items, n, audio_samples, channels, frame_fmt, hop, (const int64_t *)nullptr, 0, &total, &start)) return rc;
+    if (seg_cap < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: seg_cap = %lld: bad count", who, (long long)seg_cap);
+    if (!nsegs_out || (seg_cap > 0 && !segs_out) || (total > 0 && !audio))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    e->segtab_count = -1;
+    if (total == 0) {                        // nothing to scan: an empty table
+        e->segtab_count = 0;
+        *nsegs_out = 0;
+        return VAD_OK;
+    }
+    if (int rc = scan_upload_launch(e, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, total)) return rc;
+    if (int rc = ensure(e, e->d_nsegs, e->d_nsegs_cap, sizeof(long long))) return rc;
+    // the table's size is known only behind the count: room for the caller's capacity and for a segment per 16 frames first, and
+    // the extraction once more (the per-frame arrays are still there) in the rare case that the table is larger
+    int64_t room = std::min(total, std::max<int64_t>({seg_cap, total / 16 + 256, (int64_t)(e->d_segtab_cap / sizeof(vadk::SegRecord))}));
+    long long count = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (int rc = ensure(e, e->d_segtab, e->d_segtab_cap, sizeof(vadk::SegRecord) * (size_t)room)) return rc;
+        if (int rc = seg_launches(e, e->d_events, e->d_seg, e->d_probs, start.data(), n, e->d_segtab, room, e->d_nsegs, e->stream)) return rc;
+        HIP_TRY(e, hipMemcpyAsync(&count, e->d_nsegs, sizeof count, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(e, hipStreamSynchronize(e->stream));
+        if (count <= room) break;
+        room = count;
+    }
+    const int64_t take = std::min<int64_t>(count, seg_cap);
+    if (take > 0) {
+        HIP_TRY(e, hipMemcpyAsync(segs_out, e->d_segtab, sizeof(vad_segment) * (size_t)take, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(e, hipStreamSynchronize(e->stream));
+    }
+    e->segtab_count = count;
+    *nsegs_out = count;
+    return VAD_OK;
+}
+
+int vad_scan_segments_read(vad_engine *e, int64_t first, int64_t count, vad_segment *out) {
+    static const char *who = "vad_scan_segments_read";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->segtab_count < 0)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the engine holds no segment table: no vad_scan_segments has built one", who);
+    if (first < 0 || count < 0 || first > e->segtab_count || count > e->segtab_count - first)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: records %lld .. +%lld leave the table of %lld", who, (long long)first,
+                       (long long)count, (long long)e->segtab_count);
+    if (count == 0) return VAD_OK;
+    if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    HIP_TRY(e, hipSetDevice(e->device));
+    HIP_TRY(e, hipMemcpyAsync(out, e->d_segtab + first, sizeof(vad_segment) * (size_t)count, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return VAD_OK;
 }
 
 // ---- pipelined host ingest ---------------------------------------------------------------------------------------

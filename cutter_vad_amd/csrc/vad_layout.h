@@ -271,6 +271,36 @@ struct CutArgs {
     float thresh;             // denoise gate, < 0 = off
 };
 
+// the segment table of a scan (csrc/scan_segments.hip; vad_segments_device, vad_scan_segments).  Flat index k of the scan's CSR
+// arrays is an END iff (events[k] & SEG_EV_MASK) == SEG_EV_END; every END becomes one SegRecord (the header's vad_segment), in
+// ascending k.  Three passes fix that order: a workgroup of SEG_THREADS threads counts the ENDs of SEG_WG_FRAMES consecutive frames
+// (16 event bytes per thread, one load), one workgroup turns the chunk counts into their exclusive prefix (SEG_THREADS chunks per
+// round) and writes the grand total, and the fill pass reads each chunk again and writes its records from the chunk's prefix on.
+// A fourth kernel, one wave per written record, adds the statistics.
+constexpr int SEG_THREADS = 256;
+constexpr int SEG_WG_FRAMES = 16 * SEG_THREADS;
+constexpr int SEG_PROB_SHIFT = 30;            // a probability enters the mean as (int64) rint((double)p * 2^30): the sum is exact in any order
+constexpr uint32_t SEG_EV_MASK = 0x82, SEG_EV_END = 0x02;     // VAD_EV_END set, VAD_EV_REJECTED clear
+struct SegRecord {
+    int32_t item, first_frame, nframes, counted;
+    float mean_prob, max_prob;
+};
+static_assert(sizeof(SegRecord) == 24, "SegRecord layout");
+struct SegArgs {
+    const uint8_t *events;    // [total], 16-byte aligned
+    const int32_t *seg_frames;
+    const float *probs;
+    const int32_t *out_start; // [n + 1] on the device: item i owns the flat indices out_start[i] .. out_start[i + 1] - 1
+    uint32_t *chunk;          // [nchunks]: the count pass's counts, then their exclusive prefix
+    SegRecord *segs;          // [seg_cap]
+    long long *nsegs;         // the true count
+    uint32_t first;           // out_start[0]: flat indices below it belong to no item and are not looked at
+    uint32_t total;           // out_start[n] <= 2^31 - 1
+    uint32_t nchunks;         // ceil(total / SEG_WG_FRAMES)
+    uint32_t seg_cap;         // records at positions >= seg_cap are dropped (the host clamps a larger capacity to 2^31 - 1)
+    int32_t n;                // items
+};
+
 // resampler launch parameters (csrc/resample.hip)
 struct ResampleSeg {
     const float *wstream;     // folded operator (pack_weights.cpp: pack_resample_operator)

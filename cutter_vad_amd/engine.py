@@ -341,6 +341,32 @@ class Engine:
         of the decoded pair, what ``VADWrapper`` makes of such an array), ``0``, ``1``, a sequence of these per recording, or
         ``"split"``: both channels of every recording, each on its own stream - ``slots`` is ``[n, 2]``, a recording is packed
         once and every returned array gets a leading axis of 2.  1-D recordings ignore ``channel``."""
+        hop = self.frame_samples // 2 if hop is None else int(hop)
+        thr = -1.0 if denoise is None else float(denoise)
+        with self._scan_lock:
+            n, per, two, split, block, total, fmt, offs, lens, items, start = self._scan_plan(slots, recordings, hop, law, i16_scale, channel)
+            nf = int(start[-1])
+            probs = np.empty(nf, np.float32)
+            ev = np.zeros(nf, np.uint8)
+            seg = np.zeros(nf, np.int32)
+            out = (_ptr(start, C.c_int64), _ptr(probs, C.c_float), _ptr(ev, C.c_uint8), _ptr(seg, C.c_int32))
+            self._scan_last = None
+            if two:
+                self._check(self._lib.vad_scan_channels(self._h, items, n * per, block.ctypes.data_as(C.c_void_p), total, 2, fmt, hop, thr, *out))
+            else:
+                self._check(self._lib.vad_scan(self._h, items, n, block.ctypes.data_as(C.c_void_p), total, fmt, hop, thr, *out))
+            if nf:                          # (a scan without a frame uploads nothing)
+                self._scan_last = {"samples": total, "channels": 2 if two else 1, "fmt": fmt, "offsets": offs, "lengths": lens}
+        if split:
+            cut = lambda a: [a[start[2 * i]:start[2 * i + 2]].reshape(2, -1) for i in range(n)]
+        else:
+            cut = lambda a: [a[start[i]:start[i + 1]] for i in range(n)]
+        return cut(probs), cut(ev), cut(seg)
+
+    def _scan_plan(self, slots, recordings, hop: int, law: Optional[str], i16_scale: int, channel):
+        """What ``scan`` and ``scan_segments`` share, under ``_scan_lock``: the slots and channels checked, the recordings packed
+        (``_scan_pack``), one item per (recording, channel listed for it) and the items' CSR positions
+        -> (n, per, two, split, block, sample frames, frame format, offsets, lengths, items, start [n * per + 1])."""
         recordings = [np.asarray(r) for r in recordings]
         n = len(recordings)
         two = any(r.ndim == 2 for r in recordings)
@@ -364,39 +390,61 @@ class Engine:
                     raise AudioProcessingError(f"Model prediction failed: {len(chans)} channels for {n} recordings")
         per = 2 if split else 1
         s = s.reshape(n, per)
+        block, total, fmt, offs, lens, _ = self._scan_pack(recordings, law)
+        if fmt == _ffi.VAD_FMT_I16_32767 and i16_scale == 32768:
+            fmt = _ffi.VAD_FMT_I16_32768
+        # one item per (recording, channel listed for it); a 1-D corpus goes through vad_scan as it always did
+        items = ((_ffi.ScanChItem if two else _ffi.ScanItem) * max(1, n * per))()
+        start = np.zeros(n * per + 1, np.int64)
+        for i in range(n):
+            nf = self.scan_frame_count(int(lens[i]), hop) if hop >= 1 else 0
+            for k, c in enumerate(chans[i]):
+                j = i * per + k
+                where = (int(s[i, k]), int(offs[i]), int(lens[i]))
+                items[j] = _ffi.ScanChItem(*where, c, 0) if two else _ffi.ScanItem(*where)
+                start[j + 1] = start[j] + nf
+        return n, per, two, split, block, total, fmt, offs, lens, items, start
+
+    def scan_segments(self, slots, recordings, hop: Optional[int] = None, law: Optional[str] = None, i16_scale: int = 32767,
+                      denoise: Optional[float] = 0.01, channel="mix") -> np.ndarray:
+        """``scan`` that answers with the finished segments alone (``vad_scan_segments``): the same arguments, packing, streams
+        and resident block (``cut(audio=None)`` works behind it), but the per-frame results stay on the GPU, where kernels turn
+        them into one record per ``VAD_EV_END`` -> a structured array (``_ffi.SEGMENT_DTYPE``) in item order, then frame order:
+        ``item`` (recording i, or ``2 * i + channel`` for ``"split"``), ``first_frame`` and ``nframes`` (``segment_ranges`` gives
+        the sample ranges ``speech_segments`` would), ``counted``, ``mean_prob`` and ``max_prob`` - the number, the mean and the
+        maximum of the segment's accepted probabilities from the recording's frame 0 on."""
         hop = self.frame_samples // 2 if hop is None else int(hop)
+        thr = -1.0 if denoise is None else float(denoise)
         with self._scan_lock:
-            block, total, fmt, offs, lens, _ = self._scan_pack(recordings, law)
-            if fmt == _ffi.VAD_FMT_I16_32767 and i16_scale == 32768:
-                fmt = _ffi.VAD_FMT_I16_32768
-            # one item per (recording, channel listed for it); a 1-D corpus goes through vad_scan as it always did
-            items = ((_ffi.ScanChItem if two else _ffi.ScanItem) * max(1, n * per))()
-            start = np.zeros(n * per + 1, np.int64)
-            for i in range(n):
-                nf = self.scan_frame_count(int(lens[i]), hop) if hop >= 1 else 0
-                for k, c in enumerate(chans[i]):
-                    j = i * per + k
-                    where = (int(s[i, k]), int(offs[i]), int(lens[i]))
-                    items[j] = _ffi.ScanChItem(*where, c, 0) if two else _ffi.ScanItem(*where)
-                    start[j + 1] = start[j] + nf
-            nf = int(start[-1])
-            probs = np.empty(nf, np.float32)
-            ev = np.zeros(nf, np.uint8)
-            seg = np.zeros(nf, np.int32)
-            thr = -1.0 if denoise is None else float(denoise)
-            out = (_ptr(start, C.c_int64), _ptr(probs, C.c_float), _ptr(ev, C.c_uint8), _ptr(seg, C.c_int32))
+            n, per, two, split, block, total, fmt, offs, lens, items, start = self._scan_plan(slots, recordings, hop, law, i16_scale, channel)
+            if not two:                     # the entry point takes channel items; of a one-channel block every item hears channel 0
+                mono = items
+                items = (_ffi.ScanChItem * max(1, n))()
+                for i in range(n):
+                    items[i] = _ffi.ScanChItem(mono[i].slot, mono[i].sample_offset, mono[i].nsamples, 0, 0)
+            # a guess first - a segment per 64 frames - then vad_scan_segments_read for what did not fit: the table stays on the GPU
+            table = np.zeros(int(start[-1]) // 64 + 16, _ffi.SEGMENT_DTYPE)
+            count = C.c_int64(0)
             self._scan_last = None
-            if two:
-                self._check(self._lib.vad_scan_channels(self._h, items, n * per, block.ctypes.data_as(C.c_void_p), total, 2, fmt, hop, thr, *out))
-            else:
-                self._check(self._lib.vad_scan(self._h, items, n, block.ctypes.data_as(C.c_void_p), total, fmt, hop, thr, *out))
-            if nf:                          # (a scan without a frame uploads nothing)
+            self._check(self._lib.vad_scan_segments(self._h, items, n * per, block.ctypes.data_as(C.c_void_p), total, 2 if two else 1, fmt, hop,
+                                                    thr, table.ctypes.data_as(C.POINTER(_ffi.Segment)), table.size, C.byref(count)))
+            if int(start[-1]):
                 self._scan_last = {"samples": total, "channels": 2 if two else 1, "fmt": fmt, "offsets": offs, "lengths": lens}
-        if split:
-            cut = lambda a: [a[start[2 * i]:start[2 * i + 2]].reshape(2, -1) for i in range(n)]
-        else:
-            cut = lambda a: [a[start[i]:start[i + 1]] for i in range(n)]
-        return cut(probs), cut(ev), cut(seg)
+            if count.value > table.size:
+                rest = np.zeros(count.value - table.size, _ffi.SEGMENT_DTYPE)
+                self._check(self._lib.vad_scan_segments_read(self._h, table.size, rest.size, rest.ctypes.data_as(C.POINTER(_ffi.Segment))))
+                table = np.concatenate([table, rest])
+        return table[:count.value]
+
+    def segments_device(self, d_events: int, d_seg: int, d_probs: int, out_start, d_segs: int, seg_cap: int, d_nsegs: int,
+                        stream: int = 0) -> None:
+        """The segment table of a scan on device pointers (integers; ``vad_segments_device``): ``d_events`` (16-byte aligned),
+        ``d_seg`` and ``d_probs`` as ``scan_device`` wrote them, ``out_start`` the positions it returned; the first
+        ``min(count, seg_cap)`` records go to ``d_segs`` (16-byte aligned, 24 bytes each: ``_ffi.SEGMENT_DTYPE``), the true count
+        to the int64 at ``d_nsegs``.  Asynchronous on ``stream``; every engine has it."""
+        start = np.ascontiguousarray(out_start, dtype=np.int64).reshape(-1)
+        self._check(self._lib.vad_segments_device(self._h, d_events or None, d_seg or None, d_probs or None, _ptr(start, C.c_int64),
+                                                  max(start.size - 1, 0), d_segs or None, int(seg_cap), d_nsegs or None, stream or None))
 
     def scan_device(self, slots, offsets, lengths, d_audio: int, audio_samples: int, d_probs: int, d_events: int = 0, d_seg: int = 0,
                     hop: Optional[int] = None, fmt: int = _ffi.VAD_FMT_F32, denoise: Optional[float] = 0.01, stream: int = 0,

@@ -30,8 +30,51 @@ def speech_segments(events, seg_frames, frame: int, hop: int) -> List[Tuple[int,
     return out
 
 
+def segment_ranges(table, frame: int, hop: int) -> List[Tuple[int, int]]:
+    """The records of ``Engine.scan_segments`` (a structured array with ``first_frame`` and ``nframes``) as the sample ranges
+    ``speech_segments`` gives: ``(first_frame * hop, (first_frame + nframes - 1) * hop + frame)`` each, in the table's order."""
+    return [(f * hop, (f + n - 1) * hop + frame) for f, n in zip(table["first_frame"].tolist(), table["nframes"].tolist())]
+
+
+def _frame_stats(probs, events, e: int, L: int) -> Tuple[float, float]:
+    """mean_prob and max_prob of ``vad_segment`` (include/vad_engine.h) from per-frame results, for engines without the kernel"""
+    t0 = max(e - L + 1, 0)
+    p = np.asarray(probs[t0:e + 1], np.float32)[(np.asarray(events[t0:e + 1]) & _ffi.VAD_EV_REJECTED) == 0]
+    if p.size == 0:
+        return 0.0, 0.0
+    fixed = int(np.rint(p.astype(np.float64) * 2.0 ** 30).astype(np.int64).sum())
+    return float(np.float32(fixed / (p.size * 2.0 ** 30))), float(p.max())
+
+
+def _scan_ranges(engine, slots, recordings, per: int, frame: int, hop: int, law, denoise, channel, stats: bool = False) -> List[List[List]]:
+    """One scan of ``recordings`` (all 1-D or all two-channel) on ``slots`` -> per recording, per channel scanned of it (``per``),
+    the finished segments ``(start_sample, end_sample)`` - with ``stats``: ``(start_sample, end_sample, mean_prob, max_prob)``.
+    An engine with ``scan_segments`` builds the table on the GPU and copies back that alone; any other goes through the per-frame
+    results of ``scan``.  Same ranges either way."""
+    sl = np.asarray(slots).reshape(len(recordings), per) if per == 2 else slots
+    if hasattr(engine, "scan_segments"):
+        table = engine.scan_segments(sl, recordings, hop=hop, law=law, denoise=denoise, channel=channel)
+        out = [[[] for _ in range(per)] for _ in recordings]
+        extra = zip(table["mean_prob"].tolist(), table["max_prob"].tolist())
+        for item, rg, st in zip(table["item"].tolist(), segment_ranges(table, frame, hop), extra):
+            out[item // per][item % per].append(rg + st if stats else rg)
+        return out
+    probs, ev, seg = engine.scan(sl, recordings, hop=hop, law=law, denoise=denoise, channel=channel)
+    out = []
+    for p, e, g in zip(probs, ev, seg):
+        one = []
+        for c in range(per):
+            pc, ec, gc = (p[c], e[c], g[c]) if per == 2 else (p, e, g)
+            rgs = speech_segments(ec, gc, frame, hop)
+            if stats:
+                rgs = [(a, b) + _frame_stats(pc, ec, (b - frame) // hop, (b - a - frame) // hop + 1) for a, b in rgs]
+            one.append(rgs)
+        out.append(one)
+    return out
+
+
 def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
-                    law: Optional[str] = None, channel="mix") -> List[List[Tuple[int, int]]]:
+                    law: Optional[str] = None, channel="mix", stats: bool = False) -> List[List[Tuple]]:
     """Speech segments of every recording, one launch sequence for the lot: opens one stream per recording with the config's
     thresholds, scans (frames of ``engine.frame_samples`` at ``hop``, default half a frame as ``VADWrapper`` frames a chunk;
     the config's denoise gate), closes the streams -> per recording ``[(start_sample, end_sample), ...]``.
@@ -66,17 +109,13 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
         try:
             engine.set_thresholds_many(slots, (cfg.vad_start_probability, cfg.vad_end_probability, cfg.voice_start_ratio,
                                                cfg.voice_end_ratio, cfg.voice_start_frame_count, cfg.voice_end_frame_count))
-            _probs, ev, seg = engine.scan(np.asarray(slots).reshape(len(idx), per) if per == 2 else slots, [recordings[i] for i in idx],
-                                          hop=hop, law=law, denoise=0.01 if cfg.enable_denoising else None, channel=channel)
+            ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, 0.01 if cfg.enable_denoising else None,
+                                  channel, stats)
         finally:
             for s in slots:
                 engine.close_stream(int(s))
-        for i, e, g in zip(idx, ev, seg):
-            if per == 2:
-                out[i] = [speech_segments(e[c], g[c], frame, hop) for c in range(2)]
-            else:
-                sg = speech_segments(e, g, frame, hop)
-                out[i] = [sg] if split else sg
+        for i, rc in zip(idx, ranges):
+            out[i] = rc if split else rc[0]
     return out
 
 
@@ -121,11 +160,8 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
             engine.set_thresholds_many(slots, (cfg.vad_start_probability, cfg.vad_end_probability, cfg.voice_start_ratio,
                                                cfg.voice_end_ratio, cfg.voice_start_frame_count, cfg.voice_end_frame_count))
             with engine.scan_session():
-                _probs, ev, seg = engine.scan(np.asarray(slots).reshape(len(idx), per) if per == 2 else slots, [recordings[i] for i in idx],
-                                              hop=hop, law=law, denoise=denoise, channel=channel)
                 # (recording, channel) -> its sample ranges; the cut's table lists them in that order
-                ranges = [[speech_segments(e[c], g[c], frame, hop) if per == 2 else speech_segments(e, g, frame, hop) for c in range(per)]
-                          for e, g in zip(ev, seg)]
+                ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, denoise, channel)
                 table = [(int(engine.last_scan["offsets"][k]), a // hop, (b - a - frame) // hop + 1, chans[c])
                          for k, rc in enumerate(ranges) for c, rg in enumerate(rc) for a, b in rg]
                 if table:

@@ -378,6 +378,63 @@ VAD_API int vad_scan_cut_device(vad_engine *e, const vad_cut_item *items, int64_
                                 void *d_out, int64_t out_samples, void *stream);
 
 /*
+ * The segment table of a scan, built on the GPU: what a corpus caller wants of vad_scan / vad_scan_channels is a few segments per
+ * recording, not three values per frame.  Kernels read the CSR arrays a scan left in device memory and write one vad_segment per
+ * finished segment, packed; only that table crosses the link back.
+ *   END rule: flat index k of the CSR arrays is an END iff (events[k] & 0x82) == 0x02 - VAD_EV_END set, VAD_EV_REJECTED clear.  Its
+ * item is the last i with out_start[i] <= k (items without frames own no index); with e = k - out_start[i] and L = seg_frames[k] the
+ * record holds item = i, first_frame = e - L + 1, nframes = L.  first_frame is negative when the stream entered the recording inside
+ * a segment (a slot continued from an earlier call), as cutter_vad_amd.scan.speech_segments reports such a segment.  A segment still
+ * open at a recording's last frame has no END and no record.
+ *   Order: ascending k - the caller's item order, then frame order - whatever the GPU's scheduling.
+ *   Statistics: over the frames t = max(first_frame, 0) .. e of the item whose events have VAD_EV_REJECTED clear: `counted` is their
+ * number, max_prob their maximum, and mean_prob = (float)((double)S / ((double)counted * 0x1p30)) with
+ * S = sum of (int64) rint((double)p * 0x1p30) - a fixed-point sum, exact in any order, so the value does not depend on how the
+ * kernel strides over a segment.  (counted == 0 needs nframes < 1, which no scan writes: both statistics are 0 then.  An accepted
+ * frame whose probability is NaN - see VAD_EV_REJECTED, "not covered" - leaves both unspecified.)
+ *   Truncation: the first min(count, seg_cap) records are written, in that order; the true count always.
+ *
+ * vad_segments_device: the extraction alone.  d_events (16-byte aligned), d_seg_frames and d_probs (4-byte aligned) are the flat CSR
+ * arrays on the engine's GPU, as vad_scan_device / vad_scan_channels_device wrote them (all three are needed; the events are read in
+ * aligned 16-byte lines, so up to 15 bytes behind the last event are loaded - from the array's own last page - and ignored); out_start is the
+ * host array [n + 1] of that call; d_segs (16-byte aligned, room for seg_cap records) and d_nsegs (an int64, 8-byte aligned) live on
+ * the GPU too.  Enqueues on `stream` (NULL = the engine's own) and returns.  Works on every engine, Silero V4 and
+ * VAD_ENGINE_SHARED_GPU included: no model kernel runs and no stream (slot) is touched.  Like the scans, the call first waits for
+ * earlier *_device launches that read the engine's tables (its own copy of out_start is one).
+ *   VAD_ERR_INVALID_ARG, each with a message, and nothing is written: n < 0 or seg_cap < 0; a null out_start with n > 0; a null
+ * d_nsegs; a null d_events, d_seg_frames or d_probs when there are frames; a null d_segs with seg_cap > 0; an out_start that starts
+ * below 0 or decreases; out_start[n] > 2^31 - 1; a misaligned pointer.  out_start[n] == 0 (or n == 0): VAD_OK, *d_nsegs = 0.
+ *
+ * vad_scan_segments: vad_scan_channels (channels = 1: vad_scan) without its per-frame results.  Every check, refusal and message of
+ * vad_scan_channels applies, under this function's name; Silero V4 and VAD_ENGINE_SHARED_GPU engines: VAD_ERR_UNSUPPORTED.  Further
+ * VAD_ERR_INVALID_ARG: seg_cap < 0, a null nsegs_out, a null segs_out with seg_cap > 0.  The call uploads the block, runs the scan's
+ * launches, then the extraction on the engine's own arrays (items in the order given, out_start = the running sum of
+ * vad_scan_frame_count), and copies back the count and the first min(count, seg_cap) records: no per-frame array reaches the host.
+ * Streams are left as the scan leaves them, vad_info counts the same launches and frames, and the block stays resident:
+ * vad_scan_cut(audio = NULL) works behind it.
+ *   Lifetime of the table: the WHOLE table (all `count` records, not seg_cap) stays in device memory until this engine's next
+ * vad_scan_segments that passes its checks; vad_scan_segments_read copies the records [first, first + count) of it - a caller whose
+ * seg_cap was too small reads the rest without scanning again.  VAD_ERR_INVALID_ARG with a message when the engine holds no table,
+ * for a negative first or count, a range that leaves the table, or a null out with count > 0.
+ *   VAD_ABI_VERSION is unchanged: the presence of vad_scan_segments is how a caller detects the feature.
+ */
+typedef struct vad_segment {
+    int32_t item;        /* index into the call's items */
+    int32_t first_frame; /* e - L + 1; may be negative when the stream entered the recording inside a segment */
+    int32_t nframes;     /* L */
+    int32_t counted;     /* frames that entered the two statistics */
+    float   mean_prob;
+    float   max_prob;
+} vad_segment;
+VAD_API int vad_segments_device(vad_engine *e, const uint8_t *d_events, const int32_t *d_seg_frames, const float *d_probs,
+                                const int64_t *out_start /*host [n + 1]*/, int64_t n, vad_segment *d_segs, int64_t seg_cap,
+                                int64_t *d_nsegs /*on the GPU*/, void *stream);
+VAD_API int vad_scan_segments(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples,
+                              int32_t channels, int frame_fmt, int32_t hop, float denoise_thresh, vad_segment *segs_out, int64_t seg_cap,
+                              int64_t *nsegs_out);
+VAD_API int vad_scan_segments_read(vad_engine *e, int64_t first, int64_t count, vad_segment *out);
+
+/*
  * Pipelined host ingest.  vad_step* on host pointers are copy -> kernel -> copy -> wait; at 8 192 streams the PCIe copy is
  * 5-8 x the kernel, so a serving loop should overlap the copy of tick t+1 with the kernel of tick t:
  *

@@ -11,7 +11,10 @@ import json
 import os
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+# VAD_BENCH_TREE (the scan_segments comparison of two commits, nothing else; never set by the product or the tests): import the
+# package from another checkout, its library built, and time it with this file's code.  It holds for whatever config is run with it
+# - the package is imported once, here - so set it for scan_segments alone: an older tree need not have what the other configs call.
+sys.path.insert(0, os.environ.get("VAD_BENCH_TREE") or os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from cutter_vad_amd import weights_io  # noqa: E402
@@ -796,6 +799,57 @@ def scan_cut():
                 "ratio": float(np.median(b) / np.median(a))})
     eng.close()
     return out
+
+
+def scan_segments():
+    """The corpus path end to end: scan_recordings and cut_recordings on VAD_SCAN_BENCH_N (default 1 024) int16
+    recordings of 5 - 30 s of speech - the golden clip, repeated, cut at seeded places - from page-locked host memory, client
+    thresholds, hop = frame / 2; one warm-up, then three timed calls of each, the median reported.  The functions are the public
+    ones, so the same code times a checkout without Engine.scan_segments (VAD_BENCH_TREE = its path): run the two trees in
+    turn, three processes each, and compare the medians against the spread of the older tree's three.  The bytes copied back
+    per scan are arithmetic on the counts: 9 per frame (probs, events, seg_frames) on the per-frame path, 8 + 24 per segment
+    on the table's."""
+    import time
+    import numpy as np
+    import cutter_vad_amd
+    from cutter_vad_amd import VADConfig, cut_recordings, scan_recordings
+    N = int(os.environ.get("VAD_SCAN_BENCH_N", "1024"))
+    eng = Engine(blob(5), max_streams=max(N, 16))
+    frame, hop = eng.frame_samples, eng.frame_samples // 2
+    gold = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "speech16k_i16.npz")
+    pcm = np.tile(np.load(gold)["pcm"].astype(np.int16), 3)
+    rng = np.random.default_rng(N)
+    lens = rng.integers(5 * 16000, 30 * 16000 + 1, N)
+    recs = []
+    for k in lens:
+        a = int(rng.integers(0, pcm.size - int(k) + 1))
+        recs.append(pcm[a:a + int(k)].copy())
+    cfg = VADConfig(vad_start_probability=0.4, vad_end_probability=0.3, voice_start_frame_count=6, voice_end_frame_count=12)
+    runs = {"scan_recordings": [], "cut_recordings": []}
+    segs = scan_recordings(recs, cfg, engine=eng)
+    cuts = cut_recordings(recs, cfg, engine=eng)
+    assert [[c[:2] for c in r] for r in cuts] == segs
+    for _ in range(3):
+        t0 = time.perf_counter()
+        scan_recordings(recs, cfg, engine=eng)
+        runs["scan_recordings"].append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        cut_recordings(recs, cfg, engine=eng)
+        runs["cut_recordings"].append(time.perf_counter() - t0)
+    frames = int(sum(eng.scan_frame_count(int(k), hop) for k in lens))
+    nseg = sum(len(r) for r in segs)
+    table = hasattr(eng, "scan_segments")
+    row = {"config": f"scan_segments: scan_recordings and cut_recordings, {N} int16 recordings of 5 - 30 s of speech in host memory, "
+                     "client thresholds, hop = frame / 2", "tree": os.path.dirname(os.path.dirname(os.path.abspath(cutter_vad_amd.__file__))),
+           "path": "segment table built on the GPU" if table else "per-frame results reduced on the host",
+           "recordings": N, "frames": frames, "segments": nseg, "audio_MB": float(lens.sum()) * 2 / 1e6,
+           "d2h_bytes_per_scan": 8 + 24 * nseg if table else 9 * frames,
+           "payload_MB_per_cut": sum(len(w) - 44 for r in cuts for _, _, w in r) / 1e6}
+    for k, v in runs.items():
+        row[f"s_{k}_runs"] = v
+        row[f"s_{k}"] = float(np.median(v))
+    eng.close()
+    return row
 
 
 def single_stream_wrapper():

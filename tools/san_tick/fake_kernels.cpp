@@ -156,6 +156,40 @@ extern "C" hipError_t vadk_launch_scan_cut(const CutArgs *a, hipStream_t) {
     return hipSuccess;
 }
 
+// the segment table of a scan (csrc/scan_segments.hip), the kernels' arithmetic in plain C++ and in one sweep: an END is a byte with
+// VAD_EV_END set and VAD_EV_REJECTED clear, its item the last one whose first index is not above it, the records in ascending
+// index up to seg_cap, the true count always; the statistics over the accepted frames max(first_frame, 0) .. e, the mean from the
+// fixed-point sum of rint(p * 2^30)
+extern "C" hipError_t vadk_launch_scan_segments(const SegArgs *a, hipStream_t) {
+    long long count = 0;
+    int32_t item = 0;
+    for (uint32_t k = a->first; k < a->total; ++k) {
+        if ((a->events[k] & SEG_EV_MASK) != SEG_EV_END) continue;
+        while ((uint32_t)a->out_start[item + 1] <= k) ++item;      // k < out_start[n]: stops at n - 1 or before
+        if (count < (long long)a->seg_cap) {
+            const uint32_t base = (uint32_t)a->out_start[item], e = k - base, L = (uint32_t)a->seg_frames[k];
+            SegRecord r{item, (int32_t)(e - L + 1u), (int32_t)L, 0, 0.0f, 0.0f};
+            long long S = 0;
+            float mx = -INFINITY;
+            for (uint32_t t = r.first_frame > 0 ? (uint32_t)r.first_frame : 0u; t <= e; ++t) {
+                if (a->events[base + t] & EV_REJECTED) continue;
+                const float p = a->probs[base + t];
+                r.counted += 1;
+                S += (long long)std::rint((double)p * (double)(1ll << SEG_PROB_SHIFT));
+                mx = std::fmax(mx, p);
+            }
+            if (r.counted > 0) {
+                r.mean_prob = (float)((double)S / ((double)r.counted * (double)(1ll << SEG_PROB_SHIFT)));
+                r.max_prob = mx;
+            }
+            a->segs[count] = r;
+        }
+        ++count;
+    }
+    *a->nsegs = count;
+    return hipSuccess;
+}
+
 extern "C" hipError_t vadk_launch_silero_v5_t16_rates(const StepParams *p, const RateParams *r, hipStream_t) {
     for (int k = 0; k < r->nseg; ++k) {
         StepParams q = *p;
