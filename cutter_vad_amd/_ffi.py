@@ -225,6 +225,11 @@ SIGNATURES = {
     "vad_scan_channels_device": (C.c_int, [_vp, C.POINTER(ScanChItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32,
                                            C.c_float, _i64p, _vp, _vp, _vp, _vp]),
     "vad_debug_scan_launch_frames": (C.c_int, [_vp, C.c_int32]),
+    "vad_scan_rate_frame_count": (C.c_int64, [_vp, C.c_int64, C.c_int32, C.c_int32]),
+    "vad_scan_rate": (C.c_int, [_vp, C.POINTER(ScanChItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32, C.c_float,
+                                _i64p, _f32p, _u8p, _i32p]),
+    "vad_scan_rate_device": (C.c_int, [_vp, C.POINTER(ScanChItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32,
+                                       C.c_float, _i64p, _vp, _vp, _vp, _vp]),
     "vad_cut_samples": (C.c_int64, [_vp, C.c_int64, C.c_int32, C.c_int32]),
     "vad_scan_cut": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_float, C.c_int32,
                                C.c_int32, _vp, C.c_int64]),

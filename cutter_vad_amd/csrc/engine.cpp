@@ -43,6 +43,7 @@ extern "C" hipError_t vadk_launch_silero_v5_scan16(const vadk::StepParams *p, co
                                                    hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_cut(const vadk::CutArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_segments(const vadk::SegArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_scan_resample(const vadk::ScanResampleArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_resample(const vadk::ResampleParams *p, hipStream_t stream);
 extern "C" hipError_t vadk_launch_slot_control(vadk::SmSlot *sm, float *state, const int32_t *d_slots, int n, int op,
                                                const vadk::SmSlot *def, const vad_thresholds *d_thr, int nthr, hipStream_t stream);
@@ -143,6 +144,12 @@ struct vad_engine {
     int scan_launch_frames = 0;
     void *d_audio = nullptr; size_t d_audio_cap = 0;
     vadk::ScanItem *d_items = nullptr; size_t d_items_cap = 0;
+    // vad_scan_rate: one launch window's resampled frames [live][W][512] f32 and its item table, written by vadk_scan_resample and
+    // read by the model launch behind it.  live * W * 2 KiB stays within SCAN_RATE_WIN_BYTES (which the window size W is cut to):
+    // far under the 2 GiB a buffer descriptor addresses.
+    static constexpr size_t SCAN_RATE_WIN_BYTES = size_t(256) << 20;
+    float *d_win = nullptr; size_t d_win_cap = 0;
+    vadk::ScanItem *d_items_win = nullptr; size_t d_items_win_cap = 0;
     std::vector<vadk::ScanItem> scan_items;
     hipEvent_t scan_done = nullptr;          // vad_scan_device: recorded behind its last launch, which may still read d_items
     bool scan_pending = false;               // (an event, not the caller's stream: the caller may destroy that once its work is done)
@@ -848,7 +855,7 @@ void vad_engine_destroy(vad_engine *e) {
     weights_release(e->d_wstream16x);
     weights_release(e->d_wstream16y);
     void *bufs[] = {e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots, e->d_g711,
-                    e->d_audio, e->d_items, e->d_cut, e->d_cut_out, e->d_segwork, e->d_nsegs, e->d_segtab, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
+                    e->d_audio, e->d_items, e->d_win, e->d_items_win, e->d_cut, e->d_cut_out, e->d_segwork, e->d_nsegs, e->d_segtab, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->scan_done) (void)hipEventDestroy(e->scan_done);
@@ -1179,9 +1186,10 @@ int32_t scan_item_reserved(const vad_scan_ch_item &it) { return it.reserved; }
 // and hop count sample frames, and an item's channel (or VAD_SCAN_MIX) travels in the top bits of its quad0 (vad_layout.h).
 // own_start (vad_scan_segments, which has no out_start argument): the plan lays the results out itself - the items in the order
 // given, packed from 0 - and leaves the positions [n + 1] there; out_start is not looked at.
+// frame (vad_scan_rate): the samples of one frame in the block - a chunk at the input rate; 0 = the engine's own frames.
 template <class Item>
 int scan_plan(vad_engine *e, const char *who, const Item *items, int64_t n, int64_t audio_samples, int32_t channels, int fmt, int32_t hop,
-              const int64_t *out_start, int64_t out_base, int64_t *total, std::vector<int64_t> *own_start = nullptr) {
+              const int64_t *out_start, int64_t out_base, int64_t *total, std::vector<int64_t> *own_start = nullptr, int64_t frame = 0) {
     if (e->version != 5)
         return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s needs a Silero V5 engine; frame the recordings on the host and use vad_step_multi", who);
     if (e->shared_gpu)
@@ -1222,7 +1230,7 @@ int scan_plan(vad_engine *e, const char *who, const Item *items, int64_t n, int6
         if (scan_item_reserved(it) != 0)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: recording %lld: reserved = %d must be 0", who, (long long)i,
                            scan_item_reserved(it));
-        const int64_t nf = scan_frames(it.nsamples, e->frame_samples, hop);
+        const int64_t nf = scan_frames(it.nsamples, frame > 0 ? frame : e->frame_samples, hop);
         if (own_start) (*own_start)[(size_t)i + 1] = (*own_start)[(size_t)i] + nf;
         else if (out_start[i] < out_base || out_start[i + 1] - out_start[i] != nf)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start gives recording %lld %lld entries, it has %lld frames", who,
@@ -1969,6 +1977,179 @@ int vad_resample_multi_device(vad_engine *e, int32_t nseg, const float *const *d
     hipError_t r = vadk_launch_resample(&p, stream ? static_cast<hipStream_t>(stream) : e->stream);
     if (r != hipSuccess) return e->hip_fail(r, "resample kernel launch");
     return VAD_OK;
+}
+
+// ---- whole recordings at 8 / 24 / 48 kHz (vad_scan_rate): framed at the input rate, resampled chunk by chunk, then scanned ------
+namespace {
+
+// what comes before the plan's checks: the engine's model rate and the input rate.  *chunk = sample frames of one chunk at sr_in, or
+// 0: the recordings are at 16 kHz already and the call is vad_scan_channels (AudioUtils.resample_audio returns its input).
+int scan_rate_check(vad_engine *e, const char *who, int32_t sr_in, int *chunk) {
+    if (e->version == 5 && e->frame_samples != VAD_FRAME_SAMPLES)
+        return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s: this engine runs an 8 kHz sub-model on %d-sample frames; "
+                       "resampled recordings need the 16 kHz one", who, e->frame_samples);
+    *chunk = sr_in == 16000 ? 0 : resample_chunk_len(sr_in);
+    if (sr_in != 16000 && *chunk == 0)
+        return e->fail(VAD_ERR_UNSUPPORTED, "Failed to resample audio from %dHz to 16000Hz: %s: supported input rates are 8000, 16000, 24000, 48000", sr_in, who);
+    return VAD_OK;
+}
+
+// the launches of a planned rate scan (e->d_items holds e->scan_items, planned on chunks of `chunk` sample frames): per window of W
+// chunks one vadk_scan_resample - the window's chunks of the live items -> 512-sample frames in d_win, and the window's item table
+// - and behind it, on the same stream, the scan kernel over d_win as a mono float32 block whose frames lie back to back.  State
+// travels through HBM between the windows, as in scan_launches; the gate and the non-finite check act on the resampled frame.
+int scan_rate_launches(vad_engine *e, const void *d_audio, int64_t audio_samples, int32_t channels, int fmt, int chunk, int32_t hop, float thr,
+                       float *d_probs, uint8_t *d_events, int32_t *d_seg, int64_t total, hipStream_t s) {
+    const std::vector<vadk::ScanItem> &it = e->scan_items;
+    const int maxf = it.empty() ? 0 : it.front().nframes;
+    size_t live = it.size();
+    while (live > 0 && it[live - 1].nframes <= 0) --live;
+    if (live == 0) return VAD_OK;
+    const int cap = e->scan_launch_frames > 0 ? e->scan_launch_frames : vad_engine::SCAN_LAUNCH_FRAMES;
+    const size_t fit = vad_engine::SCAN_RATE_WIN_BYTES / (live * 2048u);
+    const int W = std::max(1, (int)std::min<size_t>((size_t)std::min(cap, maxf), fit));
+    const size_t win_bytes = live * (size_t)W * 2048u;
+    if (win_bytes >= (size_t(1) << 31))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %zu recordings with chunks in one call: one frame of each exceeds the 2 GiB a launch may address", live);
+    vad_engine::ResampleOp *op = nullptr;
+    if (int rc = get_resample_op(e, chunk, &op)) return rc;
+    if (int rc = ensure(e, e->d_win, e->d_win_cap, win_bytes)) return rc;
+    if (int rc = ensure(e, e->d_items_win, e->d_items_win_cap, sizeof(vadk::ScanItem) * live)) return rc;
+    vadk::ScanResampleArgs r{};
+    r.wstream = op->d_w;
+    r.wstream_bytes = (uint32_t)op->bytes;
+    r.tile_blocks = op->tile_blocks;
+    r.row128_block = op->row128_block;
+    r.audio_bytes = (uint32_t)((uint64_t)audio_samples * (uint64_t)channels * sample_bytes(fmt));
+    r.audio = d_audio;
+    r.items = e->d_items;
+    r.items_win = e->d_items_win;
+    r.win = e->d_win;
+    r.W = W;
+    r.n_in = chunk;
+    r.hopq = (uint32_t)hop >> 2;
+    r.fmt = fmt;
+    r.channels = channels;
+    vadk::StepParams p = e->base;
+    p.wstream = e->d_wstream16;
+    p.wstream_bytes = (uint32_t)e->wbytes16;
+    p.wstream_x = e->d_wstream16x;
+    p.wstream_x_bytes = (uint32_t)e->wbytes16x;
+    p.wstream_y = e->d_wstream16y;
+    p.wstream_y_bytes = (uint32_t)e->wbytes16y;
+    std::memcpy(p.sect, e->sect16, sizeof p.sect);
+    p.slots = nullptr;
+    p.frames = e->d_win;
+    p.probs = d_probs;
+    p.events = d_events;
+    p.seg_frames = d_seg;
+    p.fmt = VAD_FMT_F32;
+    p.thresh = thr;
+    vadk::ScanArgs a{};
+    a.hopq = VAD_FRAME_SAMPLES / 4;
+    a.t0 = 0;
+    a.channels = 1;
+    for (int t0 = 0; t0 < maxf; t0 += W) {
+        while (live > 0 && it[live - 1].nframes <= t0) --live;
+        r.live = (int32_t)live;
+        r.t0 = t0;
+        hipError_t rr = vadk_launch_scan_resample(&r, s);
+        if (rr != hipSuccess) return e->hip_fail(rr, "kernel launch (scan resample)");
+        p.n = (int32_t)live;
+        p.T = std::min(W, maxf - t0);
+        a.audio_bytes = (uint32_t)(live * (size_t)W * 2048u);
+        rr = vadk_launch_silero_v5_scan16(&p, e->d_items_win, &a, s);
+        if (rr != hipSuccess) return e->hip_fail(rr, "kernel launch (scan)");
+        e->steps += 1;
+    }
+    e->frames += total;
+    return VAD_OK;
+}
+
+}  // namespace
+
+int64_t vad_scan_rate_frame_count(const vad_engine *e, int64_t nsamples, int32_t sr_in, int32_t hop) {
+    if (!e || hop < 1 || nsamples < 0) return -1;
+    const int chunk = sr_in == 16000 ? e->frame_samples : resample_chunk_len(sr_in);
+    if (chunk == 0) return -1;
+    return scan_frames(nsamples, chunk, hop);
+}
+
+int vad_scan_rate(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
+                  int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, const int64_t *out_start, float *probs_out,
+                  uint8_t *events_out, int32_t *seg_frames_out) {
+    static const char *who = "vad_scan_rate";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    int chunk = 0;
+    {
+        std::lock_guard<std::mutex> lk(e->mu);
+        if (int rc = scan_rate_check(e, who, sr_in, &chunk)) return rc;
+    }
+    if (chunk == 0)
+        return scan_host(e, who, items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, out_start, probs_out, events_out,
+                         seg_frames_out);
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    int64_t total = 0;
+    const int64_t base = (n > 0 && out_start) ? out_start[0] : 0;
+    if (base < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start[0] is negative", who);
+    if (int rc = scan_plan(e, who, items, n, audio_samples, channels, frame_fmt, hop, out_start, base, &total, nullptr, chunk)) return rc;
+    if (total == 0) return VAD_OK;
+    if (!audio || !probs_out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    const size_t ab = (size_t)audio_samples * (size_t)channels * sample_bytes(frame_fmt);
+    // the block crosses the link once, in its wire format - but it is no block vad_scan_cut(audio = NULL) could cut: its positions
+    // and hop count samples at another rate than the engine's
+    e->audio_resident = false;
+    if (int rc = ensure(e, e->d_audio, e->d_audio_cap, ab + 16)) return rc;
+    if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
+    if (int rc = ensure(e, e->d_probs, e->d_probs_cap, sizeof(float) * (size_t)total)) return rc;
+    if (int rc = ensure(e, e->d_events, e->d_events_cap, (size_t)total)) return rc;
+    if (int rc = ensure(e, e->d_seg, e->d_seg_cap, sizeof(int32_t) * (size_t)total)) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, ab, hipMemcpyHostToDevice, e->stream));
+    if (int rc = scan_rate_launches(e, e->d_audio, audio_samples, channels, frame_fmt, chunk, hop, denoise_thresh, e->d_probs, e->d_events, e->d_seg,
+                                    total, e->stream))
+        return rc;
+    HIP_TRY(e, hipMemcpyAsync(probs_out + base, e->d_probs, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost, e->stream));
+    if (events_out) HIP_TRY(e, hipMemcpyAsync(events_out + base, e->d_events, (size_t)total, hipMemcpyDeviceToHost, e->stream));
+    if (seg_frames_out) HIP_TRY(e, hipMemcpyAsync(seg_frames_out + base, e->d_seg, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return VAD_OK;
+}
+
+int vad_scan_rate_device(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
+                         int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, const int64_t *out_start, float *d_probs,
+                         uint8_t *d_events, int32_t *d_seg_frames, void *stream) {
+    static const char *who = "vad_scan_rate_device";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    int chunk = 0;
+    {
+        std::lock_guard<std::mutex> lk(e->mu);
+        if (int rc = scan_rate_check(e, who, sr_in, &chunk)) return rc;
+    }
+    if (chunk == 0)
+        return scan_dev(e, who, who, items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, out_start, d_probs, d_events,
+                        d_seg_frames, stream);
+    std::lock_guard<std::mutex> lk(e->mu);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    int64_t total = 0;
+    if (int rc = scan_plan(e, who, items, n, audio_samples, channels, frame_fmt, hop, out_start, 0, &total, nullptr, chunk)) return rc;
+    if (total == 0) return VAD_OK;
+    if (!d_audio || !d_probs) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    const uintptr_t align = channels == 2 ? 8 : 4;
+    if (reinterpret_cast<uintptr_t>(d_audio) & (align - 1))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the audio block must be %d-byte aligned", who, (int)align);
+    if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, s));
+    if (!e->scan_done) HIP_TRY(e, hipEventCreateWithFlags(&e->scan_done, hipEventDisableTiming));
+    const int rc = scan_rate_launches(e, d_audio, audio_samples, channels, frame_fmt, chunk, hop, denoise_thresh, d_probs, d_events, d_seg_frames, total, s);
+    // (also behind a failed launch: the copy of the table and the launches before it are on the stream)
+    HIP_TRY(e, hipEventRecord(e->scan_done, s));
+    e->scan_pending = true;
+    return rc;
 }
 
 // ---- AudioUtils.resample_audio for any (length, rates): whole-array Fourier resampling, operator evaluated on the fly -----

@@ -321,6 +321,27 @@ struct ResampleParams {
     int32_t tile_start[RESAMPLE_MAX_SEGS + 1];
 };
 
+// whole recordings at 8 / 24 / 48 kHz (csrc/scan_resample.hip: vadk_scan_resample; vad_scan_rate).  One launch serves one window
+// of W frames of the `live` first items of the scan's sorted table: row i W + tt = chunk t0 + tt of item i - the n_in sample
+// frames from 4 (quad0_i + (t0 + tt) hopq) on, decoded and channel-selected as the scans' loaders do - resampled to 512 samples at
+// win + 512 (i W + tt); rows past an item's last chunk are not written.  The same launch writes the window's item table,
+// items_win[i] = {slot_i, i W 128, clamp(nframes_i - t0, 0, W), out0_i + t0}: the model launch behind it (silero_v5_scan16,
+// unchanged) scans `win` as a mono float32 block with hop = frame = 512.
+struct ScanResampleArgs {
+    const float *wstream;     // folded operator (pack_resample_operator), as ResampleSeg
+    uint32_t wstream_bytes, tile_blocks, row128_block;
+    uint32_t audio_bytes;     // the buffer descriptor's range: the whole block
+    const void *audio;        // the block, in its wire format
+    const ScanItem *items;    // the scan's sorted table
+    ScanItem *items_win;      // [live]
+    float *win;               // [live][W][512]
+    int32_t live, W, t0;
+    int32_t n_in;             // chunk length: 256 / 768 / 1536
+    uint32_t hopq;            // hop / 4, in input sample frames
+    int32_t fmt;              // vad_frame_format
+    int32_t channels;         // 1 or 2
+};
+
 // fused resample -> Silero V5 step on 16-stream tiles (csrc/silero_v5_t16.hip, RS instantiation): one launch for a tick whose
 // streams arrive at different rates.  Segment k = n streams of one input rate; stream0 = index of its first stream in the
 // call's slots / probs / events arrays.  The tiles walk the segments back to back in the order given here: tile b carries the

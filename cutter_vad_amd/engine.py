@@ -268,12 +268,32 @@ class Engine:
                                                     d_events or None, d_seg or None, stream or None))
 
     # ------------------------------------------------------------------ whole recordings
-    def scan_frame_count(self, nsamples: int, hop: Optional[int] = None) -> int:
-        """Frames of a recording of ``nsamples`` samples at ``hop`` (``vad_scan_frame_count``; the tail is dropped)."""
-        hop = self.frame_samples // 2 if hop is None else int(hop)
-        n = int(self._lib.vad_scan_frame_count(self._h, int(nsamples), hop))
+    def _scan_rate(self, sample_rate: Optional[int]) -> Optional[int]:
+        """``sample_rate`` of ``scan`` / ``scan_frame_count``: None for the engine's own rate (today's path), else the input rate"""
+        return None if sample_rate is None or int(sample_rate) == int(self.sample_rate) else int(sample_rate)
+
+    def scan_chunk_samples(self, sample_rate: Optional[int] = None) -> int:
+        """Samples of one frame as ``scan`` frames a recording at ``sample_rate``: ``frame_samples`` at the engine's own rate,
+        ``512 * sample_rate / 16000`` (256 / 768 / 1536) at 8 / 24 / 48 kHz."""
+        sr = self._scan_rate(sample_rate)
+        if sr is None or sr == 16000:
+            return self.frame_samples
+        if sr not in (8000, 24000, 48000):
+            raise AudioProcessingError(f"Failed to resample audio from {sr}Hz to 16000Hz: supported input rates are 8000, 16000, 24000, 48000")
+        return 512 * sr // 16000
+
+    def scan_frame_count(self, nsamples: int, hop: Optional[int] = None, sample_rate: Optional[int] = None) -> int:
+        """Frames of a recording of ``nsamples`` samples at ``hop`` (``vad_scan_frame_count``; the tail is dropped).
+        ``sample_rate``: the recording's rate (``vad_scan_rate_frame_count``: chunks of ``scan_chunk_samples(sample_rate)``, ``hop`` in
+        input samples); None or the engine's own rate: the engine's frames."""
+        sr = self._scan_rate(sample_rate)
+        hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
+        if sr is None:
+            n = int(self._lib.vad_scan_frame_count(self._h, int(nsamples), hop))
+        else:
+            n = int(self._lib.vad_scan_rate_frame_count(self._h, int(nsamples), sr, hop))
         if n < 0:
-            raise AudioProcessingError(f"Model prediction failed: bad sample count or hop ({nsamples}, {hop})")
+            raise AudioProcessingError(f"Model prediction failed: bad sample count, hop or rate ({nsamples}, {hop}, {sample_rate})")
         return n
 
     def set_scan_launch_frames(self, frames: int = 0) -> None:
@@ -328,7 +348,7 @@ class Engine:
         raise AudioProcessingError(f"Model prediction failed: channel must be 'mix', 0, 1, a sequence of these, or 'split', got {c!r}")
 
     def scan(self, slots, recordings, hop: Optional[int] = None, law: Optional[str] = None, i16_scale: int = 32767,
-             denoise: Optional[float] = 0.01, channel="mix"):
+             denoise: Optional[float] = 0.01, channel="mix", sample_rate: Optional[int] = None):
         """Whole recordings of different lengths, framed on the GPU (``vad_scan``): ``recordings`` is a list of 1-D arrays
         (float32, int16, or uint8 G.711 codes with ``law``), recording i continues stream ``slots[i]``.  Frame t of a recording
         = its samples ``t * hop .. t * hop + frame_samples - 1``; ``hop`` defaults to ``frame_samples // 2``
@@ -340,22 +360,31 @@ class Engine:
         readers deliver it and scanned as it is.  ``channel`` says what a stream hears: ``"mix"`` (the default: the float32 mean
         of the decoded pair, what ``VADWrapper`` makes of such an array), ``0``, ``1``, a sequence of these per recording, or
         ``"split"``: both channels of every recording, each on its own stream - ``slots`` is ``[n, 2]``, a recording is packed
-        once and every returned array gets a leading axis of 2.  1-D recordings ignore ``channel``."""
-        hop = self.frame_samples // 2 if hop is None else int(hop)
+        once and every returned array gets a leading axis of 2.  1-D recordings ignore ``channel``.
+        ``sample_rate``: the recordings' rate when it is not the engine's - 8000, 24000 or 48000 on a 16 kHz Silero V5 engine
+        (``vad_scan_rate``): the recordings are packed and uploaded at that rate, framed in chunks of ``scan_chunk_samples(sample_rate)``
+        at ``hop`` INPUT samples (default half a chunk), and each chunk is resampled on the GPU to the frame the model steps -
+        ``Engine.resample`` of the decoded chunk, byte for byte.  One result per chunk; no block stays for ``cut(audio=None)``.
+        None, or the engine's own rate: the path above."""
+        sr = self._scan_rate(sample_rate)
+        hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
         thr = -1.0 if denoise is None else float(denoise)
         with self._scan_lock:
-            n, per, two, split, block, total, fmt, offs, lens, items, start = self._scan_plan(slots, recordings, hop, law, i16_scale, channel)
+            n, per, two, split, block, total, fmt, offs, lens, items, start = self._scan_plan(slots, recordings, hop, law, i16_scale, channel, sr)
             nf = int(start[-1])
             probs = np.empty(nf, np.float32)
             ev = np.zeros(nf, np.uint8)
             seg = np.zeros(nf, np.int32)
             out = (_ptr(start, C.c_int64), _ptr(probs, C.c_float), _ptr(ev, C.c_uint8), _ptr(seg, C.c_int32))
             self._scan_last = None
-            if two:
+            if sr is not None:
+                self._check(self._lib.vad_scan_rate(self._h, items, n * per, block.ctypes.data_as(C.c_void_p), total, 2 if two else 1, fmt, sr,
+                                                    hop, thr, *out))
+            elif two:
                 self._check(self._lib.vad_scan_channels(self._h, items, n * per, block.ctypes.data_as(C.c_void_p), total, 2, fmt, hop, thr, *out))
             else:
                 self._check(self._lib.vad_scan(self._h, items, n, block.ctypes.data_as(C.c_void_p), total, fmt, hop, thr, *out))
-            if nf:                          # (a scan without a frame uploads nothing)
+            if nf and sr is None:           # (a scan without a frame uploads nothing, a rate scan leaves nothing to cut)
                 self._scan_last = {"samples": total, "channels": 2 if two else 1, "fmt": fmt, "offsets": offs, "lengths": lens}
         if split:
             cut = lambda a: [a[start[2 * i]:start[2 * i + 2]].reshape(2, -1) for i in range(n)]
@@ -363,9 +392,10 @@ class Engine:
             cut = lambda a: [a[start[i]:start[i + 1]] for i in range(n)]
         return cut(probs), cut(ev), cut(seg)
 
-    def _scan_plan(self, slots, recordings, hop: int, law: Optional[str], i16_scale: int, channel):
+    def _scan_plan(self, slots, recordings, hop: int, law: Optional[str], i16_scale: int, channel, rate: Optional[int] = None):
         """What ``scan`` and ``scan_segments`` share, under ``_scan_lock``: the slots and channels checked, the recordings packed
-        (``_scan_pack``), one item per (recording, channel listed for it) and the items' CSR positions
+        (``_scan_pack``), one item per (recording, channel listed for it) and the items' CSR positions; ``rate`` (``scan`` at another
+        sample rate): frames are counted in chunks at that rate, and the items are channel items whatever the recordings' shape
         -> (n, per, two, split, block, sample frames, frame format, offsets, lengths, items, start [n * per + 1])."""
         recordings = [np.asarray(r) for r in recordings]
         n = len(recordings)
@@ -394,14 +424,15 @@ class Engine:
         if fmt == _ffi.VAD_FMT_I16_32767 and i16_scale == 32768:
             fmt = _ffi.VAD_FMT_I16_32768
         # one item per (recording, channel listed for it); a 1-D corpus goes through vad_scan as it always did
-        items = ((_ffi.ScanChItem if two else _ffi.ScanItem) * max(1, n * per))()
+        ch_items = two or rate is not None
+        items = ((_ffi.ScanChItem if ch_items else _ffi.ScanItem) * max(1, n * per))()
         start = np.zeros(n * per + 1, np.int64)
         for i in range(n):
-            nf = self.scan_frame_count(int(lens[i]), hop) if hop >= 1 else 0
+            nf = self.scan_frame_count(int(lens[i]), hop, rate) if hop >= 1 else 0
             for k, c in enumerate(chans[i]):
                 j = i * per + k
                 where = (int(s[i, k]), int(offs[i]), int(lens[i]))
-                items[j] = _ffi.ScanChItem(*where, c, 0) if two else _ffi.ScanItem(*where)
+                items[j] = _ffi.ScanChItem(*where, c, 0) if ch_items else _ffi.ScanItem(*where)
                 start[j + 1] = start[j] + nf
         return n, per, two, split, block, total, fmt, offs, lens, items, start
 
@@ -448,15 +479,17 @@ class Engine:
 
     def scan_device(self, slots, offsets, lengths, d_audio: int, audio_samples: int, d_probs: int, d_events: int = 0, d_seg: int = 0,
                     hop: Optional[int] = None, fmt: int = _ffi.VAD_FMT_F32, denoise: Optional[float] = 0.01, stream: int = 0,
-                    channels: int = 1, channel=None) -> np.ndarray:
+                    channels: int = 1, channel=None, sample_rate: Optional[int] = None) -> np.ndarray:
         """``scan`` on device pointers (integers): recording i = ``lengths[i]`` samples from sample ``offsets[i]`` (a multiple
         of 4) of the block at ``d_audio``; results go to the CSR positions this returns (``out_start`` [n + 1]).  Asynchronous.
         ``channels = 2`` (``vad_scan_channels_device``): the block is interleaved two-channel audio (8-byte aligned), offsets,
         lengths and ``audio_samples`` count sample frames, and ``channel`` is ``"mix"`` (the default), ``0``, ``1`` or one of these
-        per item - list a recording twice, with two slots, to scan both of its channels."""
+        per item - list a recording twice, with two slots, to scan both of its channels.
+        ``sample_rate`` as in ``scan`` (``vad_scan_rate_device``): the block is at that rate, offsets, lengths and ``hop`` count input samples."""
         s = np.ascontiguousarray(slots, dtype=np.int64).reshape(-1)
-        hop = self.frame_samples // 2 if hop is None else int(hop)
-        if channels != 1 or channel is not None:
+        sr = self._scan_rate(sample_rate)
+        hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
+        if channels != 1 or channel is not None or sr is not None:
             channel = "mix" if channel is None else channel
             if isinstance(channel, (str, int, np.integer)):
                 chans = [_ffi.VAD_SCAN_MIX if channels == 1 and channel == "mix" else self._scan_channel(channel)] * s.size
@@ -468,8 +501,12 @@ class Engine:
             start = np.zeros(s.size + 1, np.int64)
             for i in range(s.size):
                 citems[i] = _ffi.ScanChItem(int(s[i]), int(offsets[i]), int(lengths[i]), chans[i], 0)
-                start[i + 1] = start[i] + self.scan_frame_count(int(lengths[i]), hop)
+                start[i + 1] = start[i] + self.scan_frame_count(int(lengths[i]), hop, sr)
             thr = -1.0 if denoise is None else float(denoise)
+            if sr is not None:
+                self._check(self._lib.vad_scan_rate_device(self._h, citems, s.size, d_audio, int(audio_samples), int(channels), fmt, sr, hop, thr,
+                                                           _ptr(start, C.c_int64), d_probs, d_events or None, d_seg or None, stream or None))
+                return start
             self._check(self._lib.vad_scan_channels_device(self._h, citems, s.size, d_audio, int(audio_samples), int(channels), fmt, hop, thr,
                                                            _ptr(start, C.c_int64), d_probs, d_events or None, d_seg or None, stream or None))
             return start

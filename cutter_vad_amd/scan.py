@@ -46,20 +46,23 @@ def _frame_stats(probs, events, e: int, L: int) -> Tuple[float, float]:
     return float(np.float32(fixed / (p.size * 2.0 ** 30))), float(p.max())
 
 
-def _scan_ranges(engine, slots, recordings, per: int, frame: int, hop: int, law, denoise, channel, stats: bool = False) -> List[List[List]]:
+def _scan_ranges(engine, slots, recordings, per: int, frame: int, hop: int, law, denoise, channel, stats: bool = False,
+                 rate: Optional[int] = None) -> List[List[List]]:
     """One scan of ``recordings`` (all 1-D or all two-channel) on ``slots`` -> per recording, per channel scanned of it (``per``),
     the finished segments ``(start_sample, end_sample)`` - with ``stats``: ``(start_sample, end_sample, mean_prob, max_prob)``.
     An engine with ``scan_segments`` builds the table on the GPU and copies back that alone; any other goes through the per-frame
-    results of ``scan``.  Same ranges either way."""
+    results of ``scan``.  Same ranges either way.  ``rate``: the recordings' sample rate when it is not the engine's (``frame`` and
+    ``hop`` are then a chunk and a hop in input samples): the per-frame path, the segment table has no rate form yet."""
     sl = np.asarray(slots).reshape(len(recordings), per) if per == 2 else slots
-    if hasattr(engine, "scan_segments"):
+    if rate is None and hasattr(engine, "scan_segments"):
         table = engine.scan_segments(sl, recordings, hop=hop, law=law, denoise=denoise, channel=channel)
         out = [[[] for _ in range(per)] for _ in recordings]
         extra = zip(table["mean_prob"].tolist(), table["max_prob"].tolist())
         for item, rg, st in zip(table["item"].tolist(), segment_ranges(table, frame, hop), extra):
             out[item // per][item % per].append(rg + st if stats else rg)
         return out
-    probs, ev, seg = engine.scan(sl, recordings, hop=hop, law=law, denoise=denoise, channel=channel)
+    kw = {} if rate is None else {"sample_rate": rate}
+    probs, ev, seg = engine.scan(sl, recordings, hop=hop, law=law, denoise=denoise, channel=channel, **kw)
     out = []
     for p, e, g in zip(probs, ev, seg):
         one = []
@@ -74,7 +77,7 @@ def _scan_ranges(engine, slots, recordings, per: int, frame: int, hop: int, law,
 
 
 def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
-                    law: Optional[str] = None, channel="mix", stats: bool = False) -> List[List[Tuple]]:
+                    law: Optional[str] = None, channel="mix", stats: bool = False, sample_rate: Optional[int] = None) -> List[List[Tuple]]:
     """Speech segments of every recording, one launch sequence for the lot: opens one stream per recording with the config's
     thresholds, scans (frames of ``engine.frame_samples`` at ``hop``, default half a frame as ``VADWrapper`` frames a chunk;
     the config's denoise gate), closes the streams -> per recording ``[(start_sample, end_sample), ...]``.
@@ -82,7 +85,11 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
     A recording may be a ``[nsamples, 2]`` array, interleaved channels as WAV readers deliver a recorded call; a corpus may hold
     both kinds (at most two scans, results in the caller's order).  ``channel``: what is scanned of a two-channel recording -
     ``"mix"`` (the default: the mean of the channels, as ``VADWrapper`` mixes such an array down), ``0`` or ``1``: one segment
-    list per recording; ``"split"``: one list per CHANNEL - ``[segments]`` for a 1-D recording, ``[left, right]`` for a 2-D one."""
+    list per recording; ``"split"``: one list per CHANNEL - ``[segments]`` for a 1-D recording, ``[left, right]`` for a 2-D one.
+    ``sample_rate``: the RECORDINGS' rate when it is not the engine's: 8000, 24000 or 48000 on a 16 kHz Silero V5 engine.  The corpus
+    is uploaded at that rate and resampled on the GPU chunk by chunk (``Engine.scan(sample_rate=...)``); chunks have
+    ``512 * sample_rate / 16000`` samples, ``hop`` counts input samples (default half a chunk) and the ranges returned are in
+    INPUT-rate samples.  None, or the engine's rate: as above."""
     from .pool import default_pool, resolve_model_path
     split = isinstance(channel, str) and channel == "split"
     # checked here, not by the scan: a corpus of 1-D recordings alone never shows the value to Engine.scan
@@ -95,6 +102,11 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
     if cfg.buffer_size != frame:
         raise ConfigurationError(f"scan_recordings frames at the model's frame size: buffer_size = {cfg.buffer_size}, "
                                  f"the engine's frames have {frame} samples")
+    rate = None if sample_rate is None or int(sample_rate) == int(engine.sample_rate) else int(sample_rate)
+    if rate is not None:
+        if rate not in (8000, 16000, 24000, 48000):
+            raise ConfigurationError("sample_rate", repr(sample_rate), f"scan_recordings: recordings at 8000, 16000, 24000 or 48000 Hz, got {sample_rate!r}")
+        frame = engine.scan_chunk_samples(rate)      # the ranges count input samples
     hop = frame // 2 if hop is None else int(hop)
     recordings = [np.asarray(r) for r in recordings]
     if not recordings:
@@ -110,7 +122,7 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
             engine.set_thresholds_many(slots, (cfg.vad_start_probability, cfg.vad_end_probability, cfg.voice_start_ratio,
                                                cfg.voice_end_ratio, cfg.voice_start_frame_count, cfg.voice_end_frame_count))
             ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, 0.01 if cfg.enable_denoising else None,
-                                  channel, stats)
+                                  channel, stats, rate)
         finally:
             for s in slots:
                 engine.close_stream(int(s))

@@ -320,6 +320,39 @@ VAD_API int vad_scan_channels_device(vad_engine *e, const vad_scan_ch_item *item
                                      void *stream);
 /* Diagnostic: frames one launch of vad_scan covers at most; 0 = the default.  Results do not depend on it. */
 VAD_API int vad_debug_scan_launch_frames(vad_engine *e, int32_t frames);
+/*
+ * Whole recordings at another rate than the model's (Silero V5, 16 kHz engine): sr_in = 8000, 24000 or 48000, the rates of
+ * vad_step_rates and of the reference's SampleRate.  The block is vad_scan_channels's, in its wire format and AT THE INPUT RATE:
+ * nothing is resampled or mixed on the host.  A recording is framed at the input rate, as vad_step_rates' callers frame a stream:
+ * chunk t = its sample frames t * hop .. t * hop + chunk - 1 with chunk = 512 * sr_in / 16000 (256 / 768 / 1536) and hop in input
+ * sample frames (a positive multiple of 4; AudioUtils.split_into_frames(x, chunk, chunk / 2) is hop = chunk / 2); a tail shorter
+ * than a chunk is dropped - vad_scan_rate_frame_count(e, nsamples, sr_in, hop) chunks, -1 for bad arguments.  A kernel decodes and
+ * channel-selects each chunk as the scans' loader does (s / 32767 or s / 32768, G.711, (L + R) * 0.5f for VAD_SCAN_MIX) and
+ * resamples it to one 512-sample frame with the operator vad_resample applies - byte for byte the frame vad_resample gives for the
+ * decoded float32 chunk - and the scan kernel steps the model over those frames.  The denoise gate and the non-finite check
+ * (VAD_EV_REJECTED) act on the RESAMPLED frame, where the two-launch form of vad_step_rates has them: a NaN or Inf sample anywhere
+ * in a chunk rejects that chunk's frame, state untouched.
+ *   Everything that is not about the rate is vad_scan_channels's, under this function's name: items, CSR results (one entry per
+ * chunk, seg_frames on every END), the 2 GiB limit, offsets and hops that are multiples of 4, the device block's alignment, slot
+ * checks, a refused call writes nothing, the wait for an earlier *_device call's launches.  Results do not depend on
+ * vad_debug_scan_launch_frames; the frames of one launch window live in an engine-owned buffer of at most 256 MiB, which may cut
+ * the window shorter.  vad_info.steps grows by the model launches, frames by the chunks.
+ *   sr_in == 16000 IS vad_scan_channels (AudioUtils.resample_audio returns its input).  Any other rate: VAD_ERR_UNSUPPORTED
+ * ("supported input rates are ..").  VAD_ERR_UNSUPPORTED also for engines of the 8 kHz sub-model, Silero V4 and
+ * VAD_ENGINE_SHARED_GPU engines.
+ *   A rate scan leaves NO block resident: vad_scan_cut(audio = NULL) behind it is refused (positions and hop of a cut count
+ * samples at the engine's rate).  (sr_in == 16000: vad_scan_channels's block, as there.)
+ *   VAD_ABI_VERSION is unchanged: the presence of vad_scan_rate is how a caller detects the feature.
+ */
+VAD_API int64_t vad_scan_rate_frame_count(const vad_engine *e, int64_t nsamples, int32_t sr_in, int32_t hop);
+VAD_API int vad_scan_rate(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples,
+                          int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh,
+                          const int64_t *out_start /*[n + 1]*/, float *probs_out, uint8_t *events_out /*or NULL*/,
+                          int32_t *seg_frames_out /*or NULL*/);
+VAD_API int vad_scan_rate_device(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *d_audio, int64_t audio_samples,
+                                 int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh,
+                                 const int64_t *out_start /*[n + 1]*/, float *d_probs, uint8_t *d_events, int32_t *d_seg_frames,
+                                 void *stream);
 
 /*
  * The audio of finished segments, cut out of a scanned block: the second pass behind vad_scan / vad_scan_channels.  The

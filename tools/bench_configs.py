@@ -852,6 +852,73 @@ def scan_segments():
     return row
 
 
+def scan_rate():
+    """Whole recordings at 48 kHz, resampled on the GPU in the scan: vad_scan_rate_device on VAD_SCAN_BENCH_N (default
+    4 096) int16 recordings of 30 s at 48 kHz - the golden clip, every sample three times - already in device memory, hop = chunk / 2,
+    against vad_scan_device on recordings of the same durations at 16 kHz, which the parent commit has.  One call addresses under
+    2 GiB, and 30 s at 48 kHz are 2.88 MB: the corpus goes through in calls of 728 recordings (the same grouping for both rates), on
+    one device block per rate that every call of that rate reads.  One warm-up pass over the corpus, then three timed ones (wall
+    clock around the calls and the engine's synchronize); the medians and their ratio go to profiles/scan_rate.json."""
+    import time
+    import numpy as np
+    N = int(os.environ.get("VAD_SCAN_BENCH_N", "4096"))
+    per_call, seconds = 728, 30
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    pcm = np.load(os.path.join(root, "tests", "golden", "speech16k_i16.npz"))["pcm"].astype(np.int16)
+    one16 = np.resize(pcm, seconds * 16000)
+    eng = Engine(blob(5), max_streams=max(per_call, 16))
+    slots = eng.open_streams(per_call)
+    groups = [min(per_call, N - a) for a in range(0, N, per_call)]
+    row = {"config": f"scan_rate: {N} int16 recordings of {seconds} s in device memory, hop = chunk / 2, calls of {per_call} recordings",
+           "recordings": N, "calls": len(groups)}
+    for sr in (48000, 16000):
+        one = np.repeat(one16, sr // 16000)
+        chunk = eng.scan_chunk_samples(sr)
+        hop = chunk // 2
+        block = torch.from_numpy(np.tile(one, per_call)).cuda()
+        offs = np.arange(per_call, dtype=np.int64) * one.size
+        lens = np.full(per_call, one.size, np.int64)
+        nf = eng.scan_frame_count(one.size, hop, sample_rate=sr)
+        probs = torch.empty(per_call * nf, device="cuda")
+        ev = torch.empty(per_call * nf, dtype=torch.uint8, device="cuda")
+        seg = torch.empty(per_call * nf, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+
+        def corpus():
+            for g in groups:
+                eng.reset(slots)
+                eng.scan_device(slots[:g], offs[:g], lens[:g], block.data_ptr(), g * one.size, probs.data_ptr(), ev.data_ptr(), seg.data_ptr(),
+                                hop=hop, fmt=1, denoise=0.01, sample_rate=sr)
+            eng.synchronize()
+
+        corpus()
+        runs = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            corpus()
+            runs.append(time.perf_counter() - t0)
+        key = f"{sr // 1000}k"
+        row[f"s_{key}_runs"] = runs
+        row[f"s_{key}"] = float(np.median(runs))
+        row[f"frames_{key}"] = N * nf
+        row[f"audio_GB_{key}"] = N * one.size * 2 / 1e9
+        del block, probs, ev, seg
+        torch.cuda.empty_cache()
+    row["entry_points"] = {"48k": "vad_scan_rate_device", "16k": "vad_scan_device"}
+    row["s_48k_over_s_16k"] = row["s_48k"] / row["s_16k"]
+    row["us_per_frame_48k"] = row["s_48k"] / row["frames_48k"] * 1e6
+    row["us_per_frame_16k"] = row["s_16k"] / row["frames_16k"] * 1e6
+    eng.close()
+    with open(os.path.join(root, "profiles", "scan_rate.json"), "w") as f:
+        json.dump({"what": "whole recordings at 48 kHz resampled on the GPU in a scan (vad_scan_rate, csrc/scan_resample.hip): DESIGN 2.1j",
+                   "how": "python tools/bench_configs.py scan_rate on one MI355X, one process: per rate one warm-up pass over the corpus, "
+                          "then three timed passes (time.perf_counter around the six vad_scan*_device calls of 728 recordings and the "
+                          "engine's synchronize); s_48k and s_16k are the medians.  One process on one box: the spread between "
+                          "processes is not known", "result": row}, f, indent=1)
+        f.write("\n")
+    return row
+
+
 def single_stream_wrapper():
     """configs[0]: ONE stream through the drop-in VADWrapper (host framing + one launch + sync + callbacks per chunk)."""
     import time

@@ -216,6 +216,37 @@ extern "C" hipError_t vadk_launch_resample(const ResampleParams *p, hipStream_t)
     return hipSuccess;
 }
 
+// one window of a rate scan (csrc/scan_resample.hip: vadk_scan_resample), the rule of vadk_launch_resample above on chunks framed
+// out of the block as the kernel frames them: row i W + tt = a frame of zeros whose first sample is the first decoded, channel-
+// selected sample of chunk t0 + tt of item i (a NaN when the float32 chunk holds a NaN / Inf, as the real operator spreads one
+// over the frame); rows past an item's last chunk are not written.  And the window's item table, as the kernel writes it.
+extern "C" hipError_t vadk_launch_scan_resample(const ScanResampleArgs *a, hipStream_t) {
+    const bool two = a->channels == 2;
+    const size_t fb = (size_t)(two ? 2 : 1) * (a->fmt == VAD_FMT_F32 ? 4 : a->fmt >= VAD_FMT_ULAW8 ? 1 : 2);
+    for (int i = 0; i < a->live; ++i) {
+        const ScanItem it = a->items[i];
+        const uint32_t mode = it.quad0 >> SCAN_MODE_SHIFT, quad0 = it.quad0 & ((1u << SCAN_MODE_SHIFT) - 1u);
+        auto sample = [&](size_t k) -> float {
+            if (!two) return first_sample(a->audio, k, a->fmt, 1);
+            const float l = first_sample(a->audio, 2 * k, a->fmt, 1), r = first_sample(a->audio, 2 * k + 1, a->fmt, 1);
+            return mode == SCAN_MIX ? (l + r) * 0.5f : mode == SCAN_RIGHT ? r : l;
+        };
+        const int left = it.nframes - a->t0, nw = left < 0 ? 0 : left > a->W ? a->W : left;
+        for (int tt = 0; tt < nw; ++tt) {
+            const size_t first = 4 * ((size_t)quad0 + (size_t)(a->t0 + tt) * a->hopq);
+            if ((first + (size_t)a->n_in) * fb > a->audio_bytes) return hipErrorInvalidValue;
+            float *o = a->win + ((size_t)i * a->W + tt) * 512;
+            std::memset(o, 0, 512 * sizeof(float));
+            o[0] = sample(first);
+            if (a->fmt == VAD_FMT_F32)
+                for (int k = 0; k < a->n_in; ++k)
+                    if (!std::isfinite(sample(first + k))) o[0] = std::nanf("");
+        }
+        a->items_win[i] = ScanItem{it.slot, (uint32_t)i * (uint32_t)a->W * 128u, nw, it.out0 + (uint32_t)a->t0};
+    }
+    return hipSuccess;
+}
+
 extern "C" hipError_t vadk_launch_g711_expand(const void *d_in, int16_t *d_out, int64_t nbytes, int alaw, hipStream_t) {
     for (int64_t i = 0; i < nbytes; ++i) d_out[i] = g711_pcm(static_cast<const uint8_t *>(d_in)[i], alaw != 0);
     return hipSuccess;
