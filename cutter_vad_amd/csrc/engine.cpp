@@ -37,6 +37,7 @@
 extern "C" hipError_t vadk_launch_silero_v5(const vadk::StepParams *p, hipStream_t stream);
 extern "C" hipError_t vadk_launch_silero_v4(const vadk::StepParams *p, hipStream_t stream);
 extern "C" hipError_t vadk_launch_silero_v5_t16(const vadk::StepParams *p, hipStream_t stream);
+extern "C" hipError_t vadk_launch_silero_v5_t16_pair(const vadk::StepParams *p, hipStream_t stream);
 extern "C" hipError_t vadk_launch_silero_v4_t16(const vadk::StepParams *p, int one_per_cu, hipStream_t stream);
 extern "C" hipError_t vadk_launch_silero_v5_t16_rates(const vadk::StepParams *p, const vadk::RateParams *r, hipStream_t stream);
 extern "C" hipError_t vadk_launch_silero_v5_scan16(const vadk::StepParams *p, const vadk::ScanItem *items, const vadk::ScanArgs *a,
@@ -192,6 +193,8 @@ struct vad_engine {
     size_t wbytes16y = 0;
     uint32_t sect16[vadk::NWAVES][16] = {};
     int tile_policy = 0;                     // 0 = by batch size, 16 / 32 = forced (vad_debug_set_tile)
+    int pair_policy = 0;                     // paired 16-stream tiles: 0 = when a one-frame call has more tiles than CUs, 1 = at every size,
+                                             // -1 = never (vad_debug_set_tile(-3 / -4); 0 / 16 / 32 reset it)
     bool rates_fused = true;                 // vad_debug_set_tile(-1 / -2): two-launch / fused form of vad_step_rates (benchmarks)
     bool shared_gpu = false;                 // VAD_ENGINE_SHARED_GPU: keep to 32-stream tiles (n / 32 CUs), leave the rest to the co-tenant
     int sample_rate = 16000;
@@ -626,6 +629,14 @@ int launch(vad_engine *e, const vadk::StepParams &p_in, hipStream_t s) {
         p16.wstream_y = e->d_wstream16y;
         p16.wstream_y_bytes = (uint32_t)e->wbytes16y;
         std::memcpy(p16.sect, e->sect16, sizeof p16.sect);
+        // One frame per stream of the 16 kHz model, float32 or int16, and more tiles than CUs - so that a CU gets two anyway: the two
+        // as ONE workgroup that shares every bf16 weight fragment between them (silero_v5_pair16).  Up to one tile per CU the tiles
+        // spread out, as before.
+        const int tiles16 = (int)((p.n + 15) / 16);
+        const bool pairable = p.T == 1 && p.variant == 0 && p.fmt >= 0 && p.fmt <= 2;
+        if (pairable && (e->pair_policy > 0 || (e->pair_policy == 0 && tiles16 > e->prop.multiProcessorCount)))
+            r = vadk_launch_silero_v5_t16_pair(&p16, s);
+        else
         r = vadk_launch_silero_v5_t16(&p16, s);
     } else if (e->version == 5) r = vadk_launch_silero_v5(&p, s);
     else if (e->version == 4) r = vadk_launch_silero_v4(&p, s);
@@ -3390,11 +3401,16 @@ int vad_debug_set_tile(vad_engine *e, int32_t streams_per_tile) {
         e->rates_fused = streams_per_tile == -2;
         return VAD_OK;
     }
+    if (streams_per_tile == -3 || streams_per_tile == -4) {       // paired 16-stream tiles: -3 = at every size, -4 = never
+        e->pair_policy = streams_per_tile == -3 ? 1 : -1;
+        return VAD_OK;
+    }
     if (streams_per_tile != 0 && streams_per_tile != 16 && streams_per_tile != 32)
         return e->fail(VAD_ERR_INVALID_ARG, "tile: 0 (by batch size), 16 or 32");
     if (streams_per_tile == 16 && !e->d_wstream16)
         return e->fail(VAD_ERR_UNSUPPORTED, "Silero V5's 8 kHz sub-model has no 16-stream tile kernel");
     e->tile_policy = streams_per_tile;
+    e->pair_policy = 0;
     return VAD_OK;
 }
 

@@ -9,7 +9,7 @@
 // three-piece bf16 splits (X3_HALF, X3_CONV below; vad_layout.h S_LSTM_X3, S_ENC0_X3, S_ENC1_X3); the encoders as direct 3-tap
 // convolutions, not the Toom-3 product of silero_v5.hip.  An activation that feeds such a layer is cut into its pieces ONCE, by the
 // lane that produces it, and lies in LDS as the consumers' B fragments ("activation planes", at QSD below).
-// The engine picks it when a call has at most T16_MAX_STREAMS streams (engine.cpp).
+// The engine runs it for every one-frame call and for multi-frame calls of at most T16_MAX_STREAMS streams (engine.cpp: launch()).
 //
 // Fragment convention (v_mfma_f32_16x16x4_f32, D = A[16 x 4] B[4 x 16] + C): lane l = (n = l & 15, kq = l >> 4).
 //   A: lane (row n, kq) holds W[row][k = kq]       B: lane (stream n, kq) holds X[k = kq][n]
@@ -24,8 +24,13 @@
 // Two workgroups per CU were measured (__launch_bounds__(256, 2): 256 registers, 14 spilled; 8 192 streams = 512 tiles):
 // 51.8 us against 53.6 us for the two tiles of a CU one after the other and 49.5 us for the 32-stream tile kernel, and
 // +1.2 us on every batch of <= 4 096 streams - the second wave of a SIMD only hides waits; fp32 MFMAs and VALU work share the
-// vector datapath on this chip, also across waves.  So: one workgroup per CU, all 512 registers, and the engine uses this
-// kernel for calls of at most 4 096 streams (256 tiles = one per CU) and the 32-stream tiles above that.
+// vector datapath on this chip, also across waves.  That was the fp32 kernel of round 3.  What the engine does today: the
+// single-frame instantiations (ONE) fit a CU twice (<= 256 registers, <= 80 KB of LDS: tests/test_occupancy_contract.py), and every
+// one-frame call runs on 16-stream tiles - up to one tile per CU (4 096 streams on 256 CUs) as silero_v5_step16, the tiles spread
+// out; with more tiles than CUs (16 kHz model, float32 / int16) as silero_v5_pair16 below: the two tiles a CU gets anyway as ONE
+// workgroup of eight waves that fetches every bf16 weight fragment once for both (G.711 and the 8 kHz sub-model: two workgroups of
+// silero_v5_step16 per CU, as before).  Multi-frame calls use this kernel up to 4 096 streams, one workgroup per CU with all 512
+// registers, and the 32-stream tiles above that.
 // Weight stream: pack_silero_v5_t16.
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -39,7 +44,7 @@ using namespace vadk;
 #ifdef VADK_STAMPS      // tools/kbench.sh -DKB_TILE16 -DVADK_STAMPS: the same phase indices as silero_v5.hip
 #define STAMP(k)                                                                                   \
     do {                                                                                           \
-        if (lane == 0) P.stamps[((size_t)blockIdx.x * NWAVES + w) * 32 + (k)] = clock64();          \
+        if (lane == 0) P.stamps[((size_t)tilei * NWAVES + w) * 32 + (k)] = clock64();          \
     } while (0)
 template <class V>
 __device__ __forceinline__ void stamp_wait(V v) {
@@ -189,6 +194,33 @@ __device__ __forceinline__ void x3_units(F &&f, std::integer_sequence<int, I...>
         X3_STEP(0, B, SRC, EXTRA, FOLD) X3_STEP(1, B, SRC, EXTRA, FOLD)                                         \
         X3_STEP(2, B, SRC, EXTRA, FOLD) X3_STEP(3, B, SRC, EXTRA, FOLD)                                         \
     }
+// The paired form (silero_v5_pair16): wave (hf, w) computes row tile rt = hf of the four gates for BOTH half-tiles' streams - 16 units
+// v = 4 s + q per half, unit v = the existing unit 8 s + 2 q + hf of S_LSTM_X3 (X3_LDP), its three blocks feeding two mfma_x3: on the
+// wave's own tile's B fragments (SRC0, into Gp[q][0]) and on the partner half's (SRC1, Gp[q][1]).  An accumulator sees what it saw.
+#define X3P_UNIT(v, B, SRC0, SRC1, EXTRA, FOLD)                                                                 \
+    {                                                                                                           \
+        constexpr int s_ = (v) >> 2, q_ = (v) & 3;                                                              \
+        if constexpr ((v) + X3_D < 16) { X3_LDP(B, (v) + X3_D) }                                                \
+        if constexpr (q_ == 0 && s_ < 3) {                                                                      \
+            _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) { N0_[p_] = PL_RD(SRC0, s_ + 1, p_); N1_[p_] = PL_RD(SRC1, s_ + 1, p_); } \
+        }                                                                                                       \
+        EXTRA(v)                                                                                                \
+        Gp[q_][0] = mfma_x3(xw[(v) % X3_NR], F0_, Gp[q_][0]);                                                   \
+        Gp[q_][1] = mfma_x3(xw[(v) % X3_NR], F1_, Gp[q_][1]);                                                   \
+        if constexpr (q_ == 3) { _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) { F0_[p_] = N0_[p_]; F1_[p_] = N1_[p_]; } } \
+        if constexpr (!(FOLD(v)) || q_ == 3) SB();                                                              \
+    }
+#define X3P_STEP(s, B, SRC0, SRC1, EXTRA, FOLD)                                                                 \
+    X3P_UNIT(4 * (s) + 0, B, SRC0, SRC1, EXTRA, FOLD) X3P_UNIT(4 * (s) + 1, B, SRC0, SRC1, EXTRA, FOLD)         \
+    X3P_UNIT(4 * (s) + 2, B, SRC0, SRC1, EXTRA, FOLD) X3P_UNIT(4 * (s) + 3, B, SRC0, SRC1, EXTRA, FOLD)
+#define X3P_HALF(B, SRC0, SRC1, EXTRA, FOLD)                                                                    \
+    {                                                                                                           \
+        u32x4 F0_[3], F1_[3], N0_[3], N1_[3];                                                                   \
+        _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) { F0_[p_] = PL_RD(SRC0, 0, p_); F1_[p_] = PL_RD(SRC1, 0, p_); } \
+        SB();                                                                                                   \
+        X3P_STEP(0, B, SRC0, SRC1, EXTRA, FOLD) X3P_STEP(1, B, SRC0, SRC1, EXTRA, FOLD)                         \
+        X3P_STEP(2, B, SRC0, SRC1, EXTRA, FOLD) X3P_STEP(3, B, SRC0, SRC1, EXTRA, FOLD)                         \
+    }
 // A direct 3-tap convolution on the bf16 split (encoder.0: vad_layout.h S_ENC0_X3, in the second weight stream - block offset B
 // into it; LDM = the stream's unit loader, X3_LDX / X3_LDY): NO output columns
 // out(o) = sum_tap W[tap] x[STR o + tap - 1] over the three input columns x[c], plane groups at SRC(c), NT row tiles per
@@ -264,9 +296,23 @@ __device__ __forceinline__ void x3_units(F &&f, std::integer_sequence<int, I...>
     constexpr int CH = 1;                               \
     constexpr const ScanItem *k_items = nullptr;        \
     constexpr ScanArgs S{};
+#define STEP16_NO_PAIR constexpr bool PAIR = false;
 template <bool F32IN_, bool RS, bool K8 = false, bool ONE = false>
 __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(STEP16_PARAMS) {
     constexpr int FMT = F32IN_ ? 0 : 1;
+    STEP16_NO_SCAN
+    STEP16_NO_PAIR
+#include "silero_v5_t16_body.h"
+}
+// One-frame calls with more tiles than CUs (16 kHz model, float32 / int16): the TWO tiles of a CU as one workgroup of eight waves.
+// Wave (hf, w) is wave w of half-tile hf = tile 2 blockIdx.x + hf, with its own half of the LDS, and runs the body as it is, behind
+// barriers the halves share - but for the bf16-split LSTM halves and encoder.0, where it computes ONE row tile (rt = hf) for BOTH
+// half-tiles' streams: every weight fragment that reaches the CU's registers feeds two stream tiles, and the bytes those layers
+// stream per wave halve.  The body's PAIR branches; results bit for bit those of silero_v5_step16<., false, false, true>.
+template <bool F32IN_>
+__global__ void __launch_bounds__(2 * NTHREADS, 1) silero_v5_pair16(STEP16_PARAMS) {
+    constexpr int FMT = F32IN_ ? 0 : 1;
+    constexpr bool RS = false, K8 = false, ONE = true, PAIR = true;
     STEP16_NO_SCAN
 #include "silero_v5_t16_body.h"
 }
@@ -276,6 +322,7 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16_g711(STEP16_PARA
     constexpr int FMT = ALAW ? 3 : 2;
     constexpr bool RS = false;
     STEP16_NO_SCAN
+    STEP16_NO_PAIR
 #include "silero_v5_t16_body.h"
 }
 // whole recordings (vad_scan): k_items [k_n] work items, k_frames the audio block, k_T the frames of the launch's window
@@ -288,6 +335,7 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_scan16(const float *k_w
     constexpr int CH = 1;
     constexpr const int32_t *k_slots = nullptr;
     const RateParams R{};
+    STEP16_NO_PAIR
 #include "silero_v5_t16_body.h"
 }
 // whole two-channel recordings, interleaved (vad_scan_channels): the scan with every position counted in sample frames
@@ -300,11 +348,16 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_stereo16(const float *k
     constexpr int CH = 2;
     constexpr const int32_t *k_slots = nullptr;
     const RateParams R{};
+    STEP16_NO_PAIR
 #include "silero_v5_t16_body.h"
 }
+#undef STEP16_NO_PAIR
 #undef STEP16_NO_SCAN
 #undef STEP16_PARAMS
 #undef X3_CONV
+#undef X3P_HALF
+#undef X3P_STEP
+#undef X3P_UNIT
 #undef X3_HALF
 #undef X3_STEP
 #undef X3_UNIT
@@ -345,6 +398,18 @@ extern "C" hipError_t vadk_launch_silero_v5_t16(const vadk::StepParams *p, hipSt
     }
 #undef T16_LAUNCH_G711
 #undef T16_LAUNCH
+    return hipGetLastError();
+}
+
+// the paired form of a one-frame call on the 16 kHz model, float32 or int16 frames: tiles 2 b and 2 b + 1 in workgroup b
+extern "C" hipError_t vadk_launch_silero_v5_t16_pair(const vadk::StepParams *p, hipStream_t stream) {
+    (void)hipGetLastError();
+    const int tiles = (p->n + MT16 - 1) / MT16;
+    if (tiles <= 0) return hipSuccess;
+    if (p->T != 1 || p->variant != 0 || p->fmt < 0 || p->fmt > 2) return hipErrorInvalidValue;
+    const vadk::RateParams none{};
+    if (p->fmt == 0) hipLaunchKernelGGL((silero_v5_pair16<true>), dim3((tiles + 1) / 2), dim3(2 * vadk::NTHREADS), 0, stream, V5_ARGS, none);
+    else hipLaunchKernelGGL((silero_v5_pair16<false>), dim3((tiles + 1) / 2), dim3(2 * vadk::NTHREADS), 0, stream, V5_ARGS, none);
     return hipGetLastError();
 }
 

@@ -6,6 +6,8 @@
 // 2 / 3 ITU-T G.711 mu-law / A-law, one byte per sample), RS, K8, ONE, SCAN (silero_v5_t16.hip explains them).  SCAN: the entry
 // also provides k_items and S (vad_layout.h: ScanItem, ScanArgs); the other entries a null k_items and an empty S.
 // CH: the channels of the audio block, 1 everywhere but in the scan of interleaved two-channel recordings (silero_v5_stereo16).
+// PAIR (silero_v5_pair16): the workgroup is TWO tiles - 512 threads, wave (hf, w) = wave w of half-tile hf with its own half of the LDS;
+// `tid` is the thread's index inside its half, tilei its tile, ldsO the partner half's LDS.  Both halves run every barrier.
 #define KP(f) k_##f
     using namespace vadk::v5;
     constexpr bool F32IN = FMT == 0;
@@ -14,14 +16,20 @@
     static_assert(!(RS && K8), "the fused resampler feeds the 16 kHz model");
     static_assert(!SCAN || (!RS && !ONE), "a scan is the frame-loop form on audio in HBM");
     static_assert(CH == 1 || (CH == 2 && SCAN), "two interleaved channels: whole recordings only");
+    static_assert(!PAIR || (ONE && !RS && !K8 && !G711 && !SCAN), "paired tiles: one-frame calls of the 16 kHz model, float32 / int16");
     constexpr int QL = K8 ? 8 : 16;               // loader lanes per stream = quads per quarter column
     constexpr int CS = 4 * QL;                    // folded-operand rows per column
     constexpr int PP = K8 ? 24 : 48;              // quad rows per |STFT| column (enc0's input) as planes: 12 per K-step
-    __shared__ f32x4 lds[T_LDS_F4 + (RS ? MT16 * FQ : 0) + (F32IN ? T_FLAG_F4 : 0)];     // RS: + the tile's 16 kHz frames F (one workgroup per CU either way)
-    f32x4 *const RX = lds;
-    f32x4 *const RE = lds + T_ROW_E * QSD;
-    f32x4 *const RP0 = lds + T_ROW_E0 * QSD;
-    f32x4 *const RH = lds + T_ROW_H * QSD;
+    constexpr int LDS_HALF = T_LDS_F4 + (RS ? MT16 * FQ : 0) + (F32IN ? T_FLAG_F4 : 0);
+    static_assert(!PAIR || 2 * LDS_HALF * 16 <= 160 * 1024, "both halves' LDS on one CU");
+    __shared__ f32x4 lds[(PAIR ? 2 : 1) * LDS_HALF];     // RS: + the tile's 16 kHz frames F (one workgroup per CU either way)
+    const int hf = PAIR ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8) : 0;
+    f32x4 *const ldsH = PAIR ? lds + hf * LDS_HALF : lds;     // the tile's LDS (PAIR: its half of the workgroup's)
+    [[maybe_unused]] f32x4 *const ldsO = PAIR ? lds + (1 - hf) * LDS_HALF : lds;
+    f32x4 *const RX = ldsH;
+    f32x4 *const RE = ldsH + T_ROW_E * QSD;
+    f32x4 *const RP0 = ldsH + T_ROW_E0 * QSD;
+    f32x4 *const RH = ldsH + T_ROW_H * QSD;
     float *const headp = reinterpret_cast<float *>(RH + T_ROWS_H * QSD);   // [4][16]
     float *const nyqv = headp + 64;              // [3][16]
     float *const fcor = nyqv + 48;               // [3 columns][y128, a64, b64][16 streams]
@@ -29,11 +37,12 @@
     SmSlot *const smL = reinterpret_cast<SmSlot *>(fcor + 144 + 64);
     f32x4 *const biasL = reinterpret_cast<f32x4 *>(smL + MT16);          // gate biases, compact: [4 waves][4 gates][8 quads of units]
     // F32IN: [2][16] bytes, stream s rejected when flagL[s] (8 kHz: flagL[s] | flagL[16 + s], the two halves of the workgroup)
-    uint8_t *const flagL = reinterpret_cast<uint8_t *>(lds + T_LDS_F4 + (RS ? MT16 * FQ : 0));
+    uint8_t *const flagL = reinterpret_cast<uint8_t *>(ldsH + T_LDS_F4 + (RS ? MT16 * FQ : 0));
 
-    const int tid = threadIdx.x;
+    const int tid = PAIR ? (int)threadIdx.x & 255 : (int)threadIdx.x;
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    [[maybe_unused]] const int tilei = PAIR ? 2 * (int)blockIdx.x + hf : (int)blockIdx.x;
     if constexpr (!RS) STAMP(19);                 // kernel entry
     const int n = lane & 15;                      // stream of this lane's MFMA column
     const int kq = lane >> 4;                     // channel group (B operand) = row quad of the D tile
@@ -41,7 +50,7 @@
     const int nqL = kq * QSL + n;                 // the same in the loader view
     // RS: the tile carries the virtual streams 16 b .. 16 b + 15 of the segments laid end to end (vad_layout.h); which segment a
     // column belongs to is a handful of compares on kernel arguments
-    const int vcol = (int)blockIdx.x * MT16 + n;
+    const int vcol = (PAIR ? tilei : (int)blockIdx.x) * MT16 + n;
     int gf = vcol;
     bool live = vcol < KP(n);
     if constexpr (RS) {
@@ -52,7 +61,7 @@
         gf = s0 + vcol - vs;
         live = vcol < R.total;
     }
-    const int tile0 = (int)blockIdx.x * MT16;                      // (not RS: the tile's first stream in the call's arrays)
+    const int tile0 = (PAIR ? tilei : (int)blockIdx.x) * MT16;                      // (not RS: the tile's first stream in the call's arrays)
     // SCAN: the stream of this lane's MFMA column is work item vcol: its slot, how many of its frames lie at and behind the
     // launch's first (ncol; frame t of the launch is held for this column when t >= ncol) and where its results go; the
     // loader's stream (item tile0 + lms, below) gives this thread the quad its frames start at.  Items past the table: no frames.
@@ -120,7 +129,7 @@
     // next column belongs to another thread)
     constexpr bool XCARRY = !RS && !K8;
 #define X_K0(c) ((XCARRY && (c) > 0) ? 2 : 0)
-    f32x4 *const F4 = lds + T_LDS_F4;              // RS: the tile's resampled frames
+    f32x4 *const F4 = ldsH + T_LDS_F4;              // RS: the tile's resampled frames
     // SCAN: frame tt of the launch, for the loader's stream, starts at quad xq0 + tt hopq of the audio block - frames overlap in
     // memory when hop < frame, nothing is copied.  Unsigned: a stream past its end keeps walking (into its neighbour's samples, or
     // past the block, where the descriptor answers 0); what it loads reaches selects only.
@@ -263,6 +272,9 @@
     f32x4 xw[X3_NR][3];
 #define X3_LDR(blk, slot) _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) xw[(slot) % X3_NR][p_] = WL((blk) + p_);
 #define X3_LD(B, u) X3_LDR((B) + 3 * (u), (u))
+    // PAIR: unit v = 4 s + q of a wave's 16 = the stream's unit 8 s + 2 q + hf, ring slot v
+#define X3_LDP(B, v) X3_LDR((B) + 3 * (8 * ((v) >> 2) + 2 * ((v) & 3) + hf), (v))
+#define X3_LDU(B, u) if constexpr (PAIR) { X3_LDP(B, u) } else { X3_LD(B, u) }
 #define X3_LDX(blk, slot) _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) xw[(slot) % X3_NR][p_] = WX((blk) + p_);
 #define X3_LDY(blk, slot) _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) xw[(slot) % X3_NR][p_] = WY((blk) + p_);
 #define H_FIRSTX(tt)                                                                                            \
@@ -272,7 +284,7 @@
     }
 #define H_FIRST(L, tt, WITHX)                                                                                   \
     {                                                                                                           \
-        _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LD((L) + LSTM_X3_HALF_BLOCKS, u_) }             \
+        _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LDU((L) + LSTM_X3_HALF_BLOCKS, u_) }            \
         if constexpr (WITHX) H_FIRSTX(tt)                                                                       \
         SB();                                                                                                   \
         if constexpr (RS) { X_ISSUE(2, xc_, tt) SB(); }                                                         \
@@ -646,6 +658,7 @@
         asm volatile("" : "+s"(ws_stft), "+s"(ws_x0), "+s"(ws_y1), "+s"(ws_e2), "+s"(ws_e3), "+s"(ws_l), "+s"(ws_x3));
         // ---- recurrent gate half W_hh . h_{t-1} (4 K-steps x {4 gates x 2 row tiles}, bf16 split) with the frame ingested under it ----
         f32x4 G[8];                               // gate q, row tile rt -> G[2 q + rt]
+        [[maybe_unused]] f32x4 Gp[4][2];          // PAIR: gate q's row tile hf of the wave's own tile [0] and of the partner half's [1]
         {
             const int wh = ws_x3 + LSTM_X3_HALF_BLOCKS;
             f32x4 xcA, xcB;                       // XCARRY: the decoded quads k = 2, 3 of the column folded last
@@ -765,8 +778,13 @@
             {   // the accumulators start at the gate biases: G[2 q + rt] register i of a lane = unit 16 rt + 4 kq + i of gate q (the
                 // 16 lanes of a row group read the same 16 bytes: a broadcast).  The wave reads what the wave itself wrote.
                 const f32x4 *const bq = biasL + 32 * w + kq;
+                if constexpr (PAIR) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) Gp[k][0] = Gp[k][1] = bq[k * 8 + hf * 4];
+                } else {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) G[k] = bq[(k >> 1) * 8 + (k & 1) * 4];
+                }
             }
             __syncthreads();   // (0) h_{t-1} visible (t > 0: follows barrier (8))
             STAMP(31);
@@ -778,7 +796,26 @@
             if constexpr ((u) == 23) { if constexpr (K8) { X_FOLD(2, xb_, 1) X_FLAG } else { X_FOLD(1, xb_, 1) } H_MIX }   \
             if constexpr ((u) == 31 && !K8) { X_FOLD(2, xc_, 2) X_FLAG H_MIX }
 #define H_FOLDREGION(u) (((u) & 7) >= 5 && (u) >= 8 && ((u) < 24 || !K8))
+            // PAIR: the same work at the matching places of the 16-unit sequence - a unit is twelve MFMAs, the fold regions two units
+#define HP_MIX                                                                                                  \
+    _Pragma("unroll") for (int i_ = 0; i_ < 6; ++i_) {                                                          \
+        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                                                      \
+        __builtin_amdgcn_sched_group_barrier(0x002, 28, 0);                                                     \
+    }
+#define HP_EXTRA(v)                                                                                             \
+            if constexpr ((v) == 1) { X_ISSUE(2, xc_, t) }                                                      \
+            if constexpr ((v) == 7) { X_FOLD(0, xa_, 0) HP_MIX }                                                \
+            if constexpr ((v) == 11) { X_FOLD(1, xb_, 1) HP_MIX }                                               \
+            if constexpr ((v) == 15) { X_FOLD(2, xc_, 2) X_FLAG HP_MIX }
+#define HP_FOLDREGION(v) (((v) & 3) >= 2 && (v) >= 4)
+            if constexpr (PAIR) {
+                X3P_HALF(wh, RH, (ldsO + T_ROW_H * QSD), HP_EXTRA, HP_FOLDREGION)
+            } else {
             X3_HALF(wh, RH, H_EXTRA, H_FOLDREGION)
+            }
+#undef HP_EXTRA
+#undef HP_FOLDREGION
+#undef HP_MIX
 #undef H_EXTRA
 #undef H_FOLDREGION
 #undef H_MIX
@@ -813,9 +850,18 @@
 
         // enc0's fp32 blocks (bias, Nyquist taps) and its first X3_D units, requested before barrier (1b)
         f32x4 e0f[ENC0_X3_F32_BLOCKS];
+    // PAIR: the wave's row tile is hf - its bias in e0f[0], its three Nyquist taps in e0f[1 ..]; unit v = (K-step, tap) = the stream's
+    // unit 2 v + hf
+#define E0P_BLK(v) (ws_x0 + ENC0_X3_F32_BLOCKS + 3 * (2 * (v) + hf))
 #define E0_FIRST                                                                                                \
+    if constexpr (PAIR) {                                                                                       \
+        e0f[0] = WX(ws_x0 + hf);                                                                                \
+        _Pragma("unroll") for (int k = 0; k < 3; ++k) e0f[1 + k] = WX(ws_x0 + 2 + 2 * k + hf);                  \
+        _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LDX(E0P_BLK(u_), u_) }                         \
+    } else {                                                                                                    \
     _Pragma("unroll") for (int k = 0; k < ENC0_X3_F32_BLOCKS; ++k) e0f[k] = WX(ws_x0 + k);                      \
-    _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LDX(ws_x0 + ENC0_X3_F32_BLOCKS + 3 * u_, u_) }
+    _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LDX(ws_x0 + ENC0_X3_F32_BLOCKS + 3 * u_, u_) }     \
+    }
         if constexpr (K8) {
             // ---- STFT, 8 kHz sub-model: 64 complex bins = four 16-row tiles, ONE per wave (pack_dft4_wave_128_t16): wave w owns the
             //      bins 2 (16 (w & 1) + r) + (w >> 1), r = 0..15 - waves 0 / 1 the even bins (pe | qe), 2 / 3 the odd ones (po | qo);
@@ -925,9 +971,78 @@
 
         // ---- enc0: 129 (8 kHz: 65) -> 128 ch, k3 s1 p1, 3 -> 3 columns, as a direct 3-tap convolution on the bf16 split (X3_CONV):
         //      per K-step 3 taps x 2 row tiles = 6 units, 7 column products per tile; the Nyquist channel and the bias on the VALU ----
-        constexpr int NU0 = (K8 ? 2 : 4) * 3 * 2;     // enc0's units: its K-steps x 3 taps x 2 row tiles
+        constexpr int NU0 = (K8 ? 2 : 4) * 3 * (PAIR ? 1 : 2);     // enc0's units: its K-steps x 3 taps x 2 row tiles (PAIR: one)
         f32x4 e1b;
-        {
+        // enc1's bias and its first X3_D units ride in enc0's last units: the ring goes on, unit v of enc1 in slot NU0 + v
+#define E0_EXTRA(u)                                                                                             \
+            if constexpr ((u) == NU0 - X3_D) e1b = WY(ws_y1);                                                   \
+            if constexpr ((u) + X3_D >= NU0) { X3_LDY(ws_y1 + ENC1_X3_F32_BLOCKS + 3 * ((u) + X3_D - NU0), (u) + X3_D) }
+        if constexpr (PAIR) {
+            // wave (hf, w): row tile hf (channels 32 w + 16 hf ..) of the three output columns for BOTH half-tiles: 12 units of 3 KiB
+            // where a tile's wave streams 24, the same 336 MFMAs.  acc[o][st], F_[st][c]: st = 0 the wave's own tile, 1 the partner's.
+            // One K-step's 18 pieces are held; the next K-step's replace them as the taps let go of them: column 0 behind tap 1,
+            // column 2 behind tap 2, column 1 - read by tap 2 and at once by the next tap 0 - through N1_, requested in tap 1.
+            f32x4 acc[3][2];
+            const float *const nyqO = reinterpret_cast<const float *>(ldsO + (T_ROW_H + T_ROWS_H) * QSD) + 64;
+#pragma unroll
+            for (int st = 0; st < 2; ++st) {
+                const float *const nq_ = st ? nyqO : nyqv;
+                const float nv[3] = {nq_[n], nq_[16 + n], nq_[32 + n]};
+#pragma unroll
+                for (int o = 0; o < 3; ++o) {
+                    f32x4 a = e0f[0];
+#pragma unroll
+                    for (int t = 0; t < 3; ++t)
+                        if (o + t - 1 >= 0 && o + t - 1 < 3) a = pk::fma(e0f[1 + t], pk::splat(nv[o + t - 1]), a);
+                    acc[o][st] = a;
+                }
+            }
+#define E0P_SRC(st, c) (((st) ? ldsO : RX) + PP * (c) * QSD)
+            u32x4 F_[2][3][3], N1_[2][3];
+#pragma unroll
+            for (int st = 0; st < 2; ++st)
+#pragma unroll
+                for (int c_ = 0; c_ < 3; ++c_)
+#pragma unroll
+                    for (int p_ = 0; p_ < 3; ++p_) F_[st][c_][p_] = PL_RD(E0P_SRC(st, c_), 0, p_);
+            SB();
+            x3_units([&](auto uc_) {
+                constexpr int v_ = decltype(uc_)::value, s_ = v_ / 3, t_ = v_ % 3;
+                if constexpr (v_ + X3_D < NU0) { X3_LDX(E0P_BLK(v_ + X3_D), v_ + X3_D) }
+                if constexpr (t_ == 1 && s_ + 1 < 4) {
+#pragma unroll
+                    for (int st = 0; st < 2; ++st)
+#pragma unroll
+                        for (int p_ = 0; p_ < 3; ++p_) N1_[st][p_] = PL_RD(E0P_SRC(st, 1), s_ + 1, p_);
+                }
+                E0_EXTRA(v_)
+#pragma unroll
+                for (int o_ = 0; o_ < 3; ++o_) {
+                    const int c_ = o_ + t_ - 1;
+                    if (c_ >= 0 && c_ < 3) {
+#pragma unroll
+                        for (int st = 0; st < 2; ++st) acc[o_][st] = mfma_x3(xw[v_ % X3_NR], F_[st][c_], acc[o_][st]);
+                    }
+                }
+                if constexpr (s_ + 1 < 4 && t_ >= 1) {
+#pragma unroll
+                    for (int st = 0; st < 2; ++st)
+#pragma unroll
+                        for (int p_ = 0; p_ < 3; ++p_) {
+                            if constexpr (t_ == 1) F_[st][0][p_] = PL_RD(E0P_SRC(st, 0), s_ + 1, p_);
+                            else { F_[st][1][p_] = N1_[st][p_]; F_[st][2][p_] = PL_RD(E0P_SRC(st, 2), s_ + 1, p_); }
+                        }
+                }
+                SB();
+            }, std::make_integer_sequence<int, NU0>{});
+#undef E0P_SRC
+            // ReLU -> planes: half hf of K-step w's fragments in each half-tile's plane group 144 + 48 c + 12 w
+#pragma unroll
+            for (int st = 0; st < 2; ++st)
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    st_planes_half((st ? ldsO : ldsH) + (T_ROW_E0 + 48 * c + 12 * w) * QSD + nq, hf, relu4(acc[c][st]));
+        } else {
             f32x4 acc[3][2];
             {   // accumulators start at the bias plus the Nyquist channel's terms sum_tap W[tap] |X_N|[o + tap - 1], exact fp32 fmas
                 const float nv[3] = {nyqv[n], nyqv[16 + n], nyqv[32 + n]};
@@ -942,18 +1057,15 @@
                         acc[o][rt] = a;
                     }
             }
-            // enc1's bias and its first X3_D units ride in enc0's last units: the ring goes on, unit v of enc1 in slot NU0 + v
 #define E0_SRC(c) (RX + PP * (c) * QSD)
-#define E0_EXTRA(u)                                                                                             \
-            if constexpr ((u) == NU0 - X3_D) e1b = WY(ws_y1);                                                   \
-            if constexpr ((u) + X3_D >= NU0) { X3_LDY(ws_y1 + ENC1_X3_F32_BLOCKS + 3 * ((u) + X3_D - NU0), (u) + X3_D) }
             X3_CONV(K8 ? 2 : 4, 2, 1, 3, X3_LDX, ws_x0 + ENC0_X3_F32_BLOCKS, 0, E0_SRC, acc, E0_EXTRA)
 #undef E0_SRC
-#undef E0_EXTRA
             // ReLU -> planes: the wave's channels 32 w .. are K-step w of enc1's fragments, plane group 144 + 48 c + 12 w
 #pragma unroll
             for (int c = 0; c < 3; ++c) st_planes(RP0 + (48 * c + 12 * w) * QSD + nq, relu4(acc[c][0]), relu4(acc[c][1]));
         }
+#undef E0_EXTRA
+#undef E0P_BLK
         STAMP(5);
         __syncthreads();   // (3) enc0 out
         STAMP(6);
@@ -1021,7 +1133,7 @@
                 av[j] = relu4(f32x4{a.x + b2.x, a.y + b2.y, a.z + b2.z, a.w + b2.w});
             }
 #pragma unroll
-            for (int u = 0; u < X3_D; ++u) { X3_LD(ws_x3, u) }          // the LSTM input half's first units
+            for (int u = 0; u < X3_D; ++u) { X3_LDU(ws_x3, u) }         // the LSTM input half's first units
             SB();
 #pragma unroll
             for (int j = 0; j < 4; ++j) { acc[0] = mfma16(wv[2 * j], av[j], acc[0]); acc[1] = mfma16(wv[2 * j + 1], av[j], acc[1]); }
@@ -1037,13 +1149,35 @@
             f32x4 hw[2];
 #define L_EXTRA(u) if constexpr ((u) == 24) { hw[0] = WL(ws + 128); hw[1] = WL(ws + 129); }
 #define L_FOLDREGION(u) false
+#define LP_EXTRA(v) if constexpr ((v) == 12) { hw[0] = WL(ws + 128); hw[1] = WL(ws + 129); }
+            // PAIR, hand-back: the cell below owns both row tiles of its own tile's streams.  The wave gives the partner tile's four quads
+            // (that tile's row tile hf) to wave (1 - hf, w) through the partner half's LDS - rows 144 + 16 w + 4 q + kq: enc0's output,
+            // dead there since barrier (4), and the enc2 partials, dead since (6) - across barrier (7), and takes its own tile's row
+            // tile 1 - hf from where its partner put them.  Eight LDS operations per lane; the arithmetic is what it was.
+            if constexpr (PAIR) {
+                X3P_HALF(ws_x3, RX, ldsO, LP_EXTRA, L_FOLDREGION)
+                f32x4 *const hb = ldsO + (T_ROW_E0 + 16 * w) * QSD + nq;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) hb[4 * k * QSD] = Gp[k][1];
+            } else {
             X3_HALF(ws_x3, RX, L_EXTRA, L_FOLDREGION)
+            }
+#undef LP_EXTRA
 #undef L_EXTRA
 #undef L_FOLDREGION
             STAMP(18);
             STAMP(13);
             __syncthreads();   // (7) every wave is done reading h_{t-1}
             STAMP(14);
+            if constexpr (PAIR) {
+                const f32x4 *const hb = ldsH + (T_ROW_E0 + 16 * w) * QSD + nq;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const f32x4 o = hb[4 * k * QSD];
+                    G[2 * k] = hf ? o : Gp[k][0];
+                    G[2 * k + 1] = hf ? Gp[k][0] : o;
+                }
+            }
             f32x4 part4 = f32x4{0.f, 0.f, 0.f, 0.f};
             // a rejected frame (float32 only) leaves the stream's h and c as they were: not stored, and held for the next frame
             // SCAN: so does, in every format, a frame past the end of the stream's recording
@@ -1119,6 +1253,8 @@
     }
 #undef H_FIRST
 #undef H_FIRSTX
+#undef X3_LDU
+#undef X3_LDP
 #undef X3_LD
 #undef X3_LDR
 #undef X3_LDX

@@ -120,7 +120,9 @@ class Engine:
         return out
 
     def set_tile(self, streams_per_tile: int = 0) -> None:
-        """Diagnostic (``vad_debug_set_tile``): 0 = pick the kernel shape by batch size, 16 / 32 = force it."""
+        """Diagnostic (``vad_debug_set_tile``): 0 = pick the kernel shape by batch size, 16 / 32 = force it (each also sets the
+        pairing of 16-stream tiles back to its default: one-frame V5 calls with more tiles than CUs); -3 = pair at every size,
+        -4 = never pair; -1 / -2 = ``vad_step_rates`` as two launches / fused."""
         self._check(self._lib.vad_debug_set_tile(self._h, int(streams_per_tile)), VADError)
 
     def synchronize(self) -> None:

@@ -722,6 +722,10 @@ VAD_API int vad_debug_sm_replay(vad_engine *e, int64_t slot, const float *probs,
  * 16-stream tiles, two workgroups per CU.  16 / 32 force one shape (the test-suite checks that both give the same results to
  * rounding; tools/bench_configs.py times them).
  * -1 / -2: vad_step_rates as two launches (resample, then model) / as the fused launch (default), for the same comparison.
+ * Paired tiles: a one-frame call of Silero V5's 16 kHz model on 16-stream tiles, float32 or int16 frames, with MORE tiles than the
+ * device has compute units runs two tiles per workgroup (512 threads; the tiles share every bf16 weight fragment the CU fetches) -
+ * the same results bit for bit; up to one tile per CU nothing changes.  -3 pairs at every size (the test-suite), -4 never pairs (A/B
+ * runs on one build); they leave the tile shape as it is, and 0, 16 and 32 set the pairing back to this default.
  */
 VAD_API int vad_debug_set_tile(vad_engine *e, int32_t streams_per_tile);
 

@@ -23,7 +23,13 @@
 extern "C" hipError_t vadk_launch_silero_v5(const vadk::StepParams *p, hipStream_t stream);
 #ifdef KB_TILE16      // tools/kbench16.sh: the 16-stream tile kernel (link silero_v5_t16.hip instead of silero_v5.hip)
 extern "C" hipError_t vadk_launch_silero_v5_t16(const vadk::StepParams *p, hipStream_t stream);
-#define vadk_launch_silero_v5 vadk_launch_silero_v5_t16
+extern "C" hipError_t vadk_launch_silero_v5_t16_pair(const vadk::StepParams *p, hipStream_t stream);
+// KB_PAIR=1: the paired launch (two tiles per workgroup, one-frame calls only); the stamps stay indexed by tile and wave
+static bool kb_pair = false;
+static hipError_t kb_launch16(const vadk::StepParams *p, hipStream_t stream) {
+    return kb_pair ? vadk_launch_silero_v5_t16_pair(p, stream) : vadk_launch_silero_v5_t16(p, stream);
+}
+#define vadk_launch_silero_v5 kb_launch16
 #define PACK vadk::pack_silero_v5_t16
 #else
 #define PACK vadk::pack_silero_v5
@@ -43,6 +49,11 @@ int main(int argc, char **argv) {
     const int B = argc > 2 ? atoi(argv[2]) : 8192;
     const int K = argc > 3 ? atoi(argv[3]) : 100;
     const int T = argc > 4 ? atoi(argv[4]) : 1;
+#ifdef KB_TILE16
+    kb_pair = getenv("KB_PAIR") && atoi(getenv("KB_PAIR")) != 0;
+    if (kb_pair && T != 1) { fprintf(stderr, "KB_PAIR: one frame per call\n"); return 1; }
+    if (kb_pair) printf("paired launch: %d workgroups of 512 threads\n", ((B + 15) / 16 + 1) / 2);
+#endif
     FILE *f = fopen(blob_path, "rb");
     if (!f) { perror(blob_path); return 1; }
     std::vector<unsigned char> blob;
@@ -102,7 +113,7 @@ int main(int argc, char **argv) {
     if (getenv("KB_EVENTS")) { unsigned char *d_ev; CK(hipMalloc(&d_ev, (size_t)B * T)); p.events = d_ev; }
 #ifdef VADK_STAMPS
 #ifdef KB_TILE16
-    const int tiles = (B + 15) / 16;
+    const int tiles = ((B + 15) / 16 + 1) & ~1;      // (a paired launch's last workgroup stamps both its halves)
 #else
     const int tiles = (B + vadk::MT - 1) / vadk::MT;
 #endif

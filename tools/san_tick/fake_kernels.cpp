@@ -78,6 +78,7 @@ static hipError_t fake_step(const StepParams *p, int frame_samples) {
 extern "C" hipError_t vadk_launch_silero_v5(const StepParams *p, hipStream_t) { return fake_step(p, p->variant ? 256 : 512); }
 extern "C" hipError_t vadk_launch_silero_v4(const StepParams *p, hipStream_t) { return fake_step(p, 512); }
 extern "C" hipError_t vadk_launch_silero_v5_t16(const StepParams *p, hipStream_t) { return fake_step(p, p->variant ? 256 : 512); }
+extern "C" hipError_t vadk_launch_silero_v5_t16_pair(const StepParams *p, hipStream_t) { return fake_step(p, 512); }
 extern "C" hipError_t vadk_launch_silero_v4_t16(const StepParams *p, int, hipStream_t) { return fake_step(p, 512); }
 
 // whole recordings (csrc/silero_v5_t16.hip: silero_v5_scan16), the same rule as fake_step: p = |first sample of the frame|, the

@@ -5,6 +5,9 @@
 //   fp32  : v_mfma_f32_16x16x4_f32, per K = 32: 4 weight blocks, 2 LDS reads, 16 MFMAs
 //   bf16x6: operands as three bf16 pieces each (weights pre-split, activations pre-split in LDS), the six leading cross terms on
 //           v_mfma_f32_16x16x32_bf16: per K = 32: 6 weight blocks, 3 LDS reads, 12 MFMAs
+//   bf16x6 paired: a 512-thread workgroup (eight waves, two per SIMD, one workgroup per CU), ONE row tile per wave, each 3 KiB
+//           weight unit feeding the six MFMAs of TWO B fragments (two stream tiles): per K = 32: 3 weight blocks, 6 LDS reads,
+//           12 MFMAs - the MFMAs of the two-workgroup form above on half its weight bytes (silero_v5_pair16's LSTM halves)
 // and the VALU cost of splitting a float into its three pieces.  Prints cycles per K = 32 step per wave and the ratio.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o /tmp/ub tools/ubench_split_bf16.cpp && /tmp/ub [workgroups_per_cu=1]
 #include <hip/hip_runtime.h>
@@ -102,6 +105,45 @@ __global__ void __launch_bounds__(256, OCC) k_bf16x6(const float *W, float *out,
 #undef X
 }
 
+__global__ void __launch_bounds__(512, 1) k_bf16x6_pair(const float *W, float *out, unsigned long long *cyc) {
+    constexpr int TILE_F4 = 260 * 16;      // a stream tile's planes: rows 0 .. 255 + 3 of every read
+    __shared__ f32x4 lds[2 * TILE_F4];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int i = tid; i < 2 * TILE_F4; i += 512) lds[i] = f32x4{0.001f * i, 0.5f, -0.25f, 1.f};
+    __syncthreads();
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(W), 0, WBLOCKS * 1024, 0x00020000);
+    f32x4 acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};     // stream tile st -> acc[2 st], acc[2 st + 1]
+    int blk = (blockIdx.x * 8 + w) * 37 % (WBLOCKS - 8);
+    u32x4 Aw[3], Bw[3];          // the row tile's three pieces
+    u32x4 Aa[6], Ba[6];          // activation pieces of the two stream tiles: [3 st + p]
+#define LD(S, st)                                                                                           \
+    _Pragma("unroll") for (int k = 0; k < 3; ++k) S##w[k] = ldw(rs, lane * 16, blk + k);                    \
+    blk = blk + 3 >= WBLOCKS - 3 ? 0 : blk + 3;                                                             \
+    _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                            \
+        _Pragma("unroll") for (int p = 0; p < 3; ++p)                                                        \
+            S##a[3 * t + p] = __builtin_bit_cast(u32x4, lds[t * TILE_F4 + (((st) * 12 + 4 * p) & 255) * 16 + lane]);
+#define X(wv, av, a_) a_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wv), __builtin_bit_cast(bf16x8, av), a_, 0, 0, 0);
+#define MMA(S)                                                                                              \
+    _Pragma("unroll") for (int t = 0; t < 2; ++t) {                                                          \
+        X(S##w[0], S##a[3 * t], acc[2 * t]) X(S##w[0], S##a[3 * t + 1], acc[2 * t + 1]) X(S##w[1], S##a[3 * t], acc[2 * t])   \
+        X(S##w[0], S##a[3 * t + 2], acc[2 * t + 1]) X(S##w[1], S##a[3 * t + 1], acc[2 * t]) X(S##w[2], S##a[3 * t], acc[2 * t + 1]) \
+    }
+    const unsigned long long t0 = clock64();
+    LD(A, 0)
+    for (int st = 0; st < STEPS; st += 2) {
+        LD(B, st + 1) SB();
+        MMA(A) SB();
+        LD(A, st + 2) SB();
+        MMA(B) SB();
+    }
+    const unsigned long long t1 = clock64();
+    out[blockIdx.x * 512 + tid] = acc[0].x + acc[1].y + acc[2].z + acc[3].w;
+    if (lane == 0) cyc[blockIdx.x * 8 + w] = t1 - t0;
+#undef LD
+#undef MMA
+#undef X
+}
+
 // VALU cost of the split: x -> (bf16 x1, bf16 x2, bf16 x3), 64 values per lane
 __global__ void __launch_bounds__(256) k_split(const float *in, unsigned *out, unsigned long long *cyc) {
     const int tid = threadIdx.x;
@@ -160,6 +202,14 @@ int main(int argc, char **argv) {
         b = report("bf16x6 16x16x32, 12 MFMAs/step", STEPS);
     }
     printf("workgroups per CU: %d   fp32 / bf16x6 = %.2f\n", occ, f / b);
+    if (occ == 2) {              // the same waves per CU as the two-workgroup form, as one workgroup of eight
+        double pr = 0;
+        for (int rep = 0; rep < 3; ++rep) {
+            hipLaunchKernelGGL(k_bf16x6_pair, dim3(256), dim3(512), 0, 0, W, out, cyc);
+            pr = report("bf16x6 paired, 12 MFMAs/step", STEPS);
+        }
+        printf("one workgroup of 512 per CU: bf16x6 / bf16x6 paired = %.2f (12 MFMAs of 16 cycles = 192 per step, two waves per SIMD: 384)\n", b / pr);
+    }
     hipLaunchKernelGGL(k_split, dim3(blocks), dim3(256), 0, 0, in, o2, cyc);
     report("split into three bf16 pieces", 64);
     return 0;
