@@ -239,6 +239,13 @@ SIGNATURES = {
     "vad_scan_segments": (C.c_int, [_vp, C.POINTER(ScanChItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_float,
                                     C.POINTER(Segment), C.c_int64, _i64p]),
     "vad_scan_segments_read": (C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(Segment)]),
+    "vad_scan_rate_segments": (C.c_int, [_vp, C.POINTER(ScanChItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32,
+                                         C.c_float, C.POINTER(Segment), C.c_int64, _i64p]),
+    "vad_rate_cut_samples": (C.c_int64, [_vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "vad_scan_rate_cut": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32, C.c_float,
+                                    C.c_int32, C.c_int32, _vp, C.c_int64]),
+    "vad_scan_rate_cut_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32,
+                                           C.c_float, C.c_int32, C.c_int32, _vp, C.c_int64, _vp]),
 }
 
 _lib = None

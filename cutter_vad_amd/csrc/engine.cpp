@@ -45,6 +45,7 @@ extern "C" hipError_t vadk_launch_silero_v5_scan16(const vadk::StepParams *p, co
 extern "C" hipError_t vadk_launch_scan_cut(const vadk::CutArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_segments(const vadk::SegArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_resample(const vadk::ScanResampleArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_cut_resample(const vadk::CutResampleArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_resample(const vadk::ResampleParams *p, hipStream_t stream);
 extern "C" hipError_t vadk_launch_slot_control(vadk::SmSlot *sm, float *state, const int32_t *d_slots, int n, int op,
                                                const vadk::SmSlot *def, const vad_thresholds *d_thr, int nthr, hipStream_t stream);
@@ -155,9 +156,14 @@ struct vad_engine {
     hipEvent_t scan_done = nullptr;          // vad_scan_device: recorded behind its last launch, which may still read d_items
     bool scan_pending = false;               // (an event, not the caller's stream: the caller may destroy that once its work is done)
     // vad_scan_cut: what d_audio holds - the block the last vad_scan / vad_scan_channels / vad_scan_cut of host audio uploaded
-    // (d_audio is written by scan_host and cut_run alone) - and the cut's tables as they were uploaded, segments then workgroups
+    // (d_audio is written by the scans' uploads and cut_run alone) - and the cut's tables as they were uploaded, segments then
+    // workgroups.  audio_rate: 0 = a block at the engine's own rate (vad_scan_cut's), else the input rate of a RATE block
+    // (vad_scan_rate_segments, vad_scan_rate_cut with an audio), which vad_scan_rate_cut alone accepts: whatever uploads into
+    // d_audio says which of the two it left.  cut_rows / cut_tiles: vad_scan_rate_cut's tables for vadk_cut_resample.
     bool audio_resident = false;
-    size_t audio_bytes = 0; int32_t audio_channels = 0; int audio_fmt = 0;
+    size_t audio_bytes = 0; int32_t audio_channels = 0; int audio_fmt = 0; int32_t audio_rate = 0;
+    std::vector<vadk::CutResampleSeg> cut_rows;
+    std::vector<uint32_t> cut_tiles;
     uint8_t *d_cut = nullptr; size_t d_cut_cap = 0;
     void *d_cut_out = nullptr; size_t d_cut_out_cap = 0;
     std::vector<vadk::CutSeg> cut_segs;
@@ -1339,7 +1345,7 @@ int scan_upload_launch(vad_engine *e, int64_t n, const void *audio, int64_t audi
     HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, ab, hipMemcpyHostToDevice, e->stream));
     e->audio_resident = true;                // for a following vad_scan_cut(audio = NULL), whatever becomes of the launches
-    e->audio_bytes = ab; e->audio_channels = channels; e->audio_fmt = frame_fmt;
+    e->audio_bytes = ab; e->audio_channels = channels; e->audio_fmt = frame_fmt; e->audio_rate = 0;
     return scan_launches(e, e->d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, e->d_probs, e->d_events, e->d_seg, total, e->stream);
 }
 
@@ -1433,15 +1439,34 @@ namespace {
 
 static_assert(VAD_CUT_WG_SAMPLES == 4 * vadk::CUT_WG_QUADS, "the header's workgroup share is the kernel's");
 
-int64_t cut_samples(int64_t frame, int64_t nframes, int64_t hop, int32_t layout) {
-    return layout == VAD_CUT_FRAMES ? nframes * frame : (nframes - 1) * hop + frame;
+// frame: the samples of one frame in the block; out_frame: the samples a frame has in a VAD_CUT_FRAMES payload
+int64_t cut_samples(int64_t frame, int64_t nframes, int64_t hop, int32_t layout, int64_t out_frame) {
+    return layout == VAD_CUT_FRAMES ? nframes * out_frame : (nframes - 1) * hop + frame;
+}
+
+// (defined with the resampler, further down, inside that section's extern "C" block)
+extern "C" {
+int resample_chunk_len(int sr_in);
+int get_resample_op(vad_engine *e, int n_in, vad_engine::ResampleOp **out, bool t16 = false);
+}
+
+// rows of one window of vad_scan_rate_cut's frames: what the engine's window buffer holds, in whole tiles; the launch-frames knob
+// of the scans (vad_debug_scan_launch_frames) cuts it to that many tiles, so that a test reaches the window loop with a small call
+uint32_t cut_window_rows(const vad_engine *e) {
+    const size_t full = vad_engine::SCAN_RATE_WIN_BYTES / 2048u;
+    return (uint32_t)(e->scan_launch_frames > 0 ? std::min<size_t>(full, (size_t)e->scan_launch_frames * vadk::MT) : full);
 }
 
 // vad_scan_cut (DEV = false: host audio, or NULL = the resident block, and a host `out`) and vad_scan_cut_device.  Every check
 // comes before the first write; the tables (e->cut_segs, e->cut_work: one entry per workgroup) are built on the way.
+// chunk > 0 (vad_scan_rate_cut / _device): the block is at sr_in, a frame in it is a chunk of `chunk` sample frames, and the
+// resident block must be a rate block of that rate.  VAD_CUT_RANGE is then the same kernel on the input-rate block with the gate
+// off (no input-rate sample was ever gated); VAD_CUT_FRAMES resamples the listed chunks window by window into e->d_win
+// (vadk_cut_resample) and cuts each window as a mono float32 block of back-to-back frames with the same kernel, which gates.
 template <bool DEV>
 int cut_run(vad_engine *e, const char *who, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
-            int fmt, int32_t hop, float thr, int32_t layout, int32_t out_fmt, void *out, int64_t out_samples, void *stream) {
+            int fmt, int32_t hop, float thr, int32_t layout, int32_t out_fmt, void *out, int64_t out_samples, void *stream, int chunk = 0,
+            int32_t sr_in = 0) {
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
     hipStream_t s = (DEV && stream) ? static_cast<hipStream_t>(stream) : e->stream;
@@ -1465,17 +1490,21 @@ int cut_run(vad_engine *e, const char *who, const vad_cut_item *items, int64_t n
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %llu bytes of audio exceed the 2 GiB one call may address", who,
                        (unsigned long long)((uint64_t)audio_samples * fbytes));
     if (n == 0) return VAD_OK;
-    const int64_t frame = e->frame_samples;
-    const uint32_t frameq = (uint32_t)frame >> 2;
+    const bool rate = chunk > 0, rate_frames = rate && layout == VAD_CUT_FRAMES;
+    const int64_t frame = rate ? chunk : e->frame_samples, out_frame = rate ? VAD_FRAME_SAMPLES : frame;
+    const uint32_t frameq = (uint32_t)out_frame >> 2;
     uint32_t fshift = 0;
     while ((1u << fshift) < frameq) ++fshift;
-    // the kernel finds a quad's frame with a shift and a mask: 512 and 256 samples today
-    if ((frame & 3) || (1u << fshift) != frameq)
-        return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s: frames of %lld samples: the cut kernel needs a power of two", who, (long long)frame);
+    // the kernel finds a quad's frame with a shift and a mask: 512 and 256 samples today (the sample range once needs neither:
+    // chunks of 768 and 1536 samples pass)
+    if (layout == VAD_CUT_FRAMES && ((out_frame & 3) || (1u << fshift) != frameq))
+        return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s: frames of %lld samples: the cut kernel needs a power of two", who, (long long)out_frame);
     struct Span { int64_t lo, hi; int64_t i; };
     std::vector<Span> spans((size_t)n);
     e->cut_segs.resize((size_t)n);
     e->cut_work.clear();
+    e->cut_rows.clear();
+    int64_t rows = 0;                        // rate_frames: the frames of the segments listed so far
     for (int64_t i = 0; i < n; ++i) {
         const vad_cut_item &it = items[i];
         if (it.sample_offset < 0 || (it.sample_offset & 3))
@@ -1494,7 +1523,7 @@ int cut_run(vad_engine *e, const char *who, const vad_cut_item *items, int64_t n
                            (long long)i, it.channel, channels);
         if (it.reserved != 0)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: reserved = %d must be 0", who, (long long)i, it.reserved);
-        const int64_t count = cut_samples(frame, it.nframes, hop, layout);
+        const int64_t count = cut_samples(frame, it.nframes, hop, layout, out_frame);
         if (it.out_sample < 0 || (it.out_sample & 3) || it.out_sample > out_samples || count > out_samples - it.out_sample)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: out_sample = %lld (+%lld samples) must be a multiple of 4 inside "
                            "the output of %lld samples", who, (long long)i, (long long)it.out_sample, (long long)count, (long long)out_samples);
@@ -1506,6 +1535,14 @@ int cut_run(vad_engine *e, const char *who, const vad_cut_item *items, int64_t n
         const uint32_t nq = (uint32_t)(count >> 2);
         e->cut_segs[(size_t)i] = vadk::CutSeg{(uint32_t)((it.sample_offset + it.first_frame * (int64_t)hop) >> 2) | (mode << vadk::SCAN_MODE_SHIFT), nq,
                                               (uint64_t)it.out_sample >> 2};
+        if (rate_frames) {
+            // the kernels' work is listed per window, behind the checks
+            e->cut_rows.push_back(vadk::CutResampleSeg{e->cut_segs[(size_t)i].quad_in, (uint32_t)rows});
+            rows += it.nframes;
+            if (rows > INT32_MAX)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 frames in one call", who);
+            continue;
+        }
         for (uint32_t q = 0; q < nq; q += vadk::CUT_WG_QUADS) e->cut_work.push_back(vadk::CutWork{(uint32_t)i, q});
         if (e->cut_work.size() > (size_t)INT32_MAX)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d samples in one call", who, VAD_CUT_WG_SAMPLES);
@@ -1530,9 +1567,16 @@ int cut_run(vad_engine *e, const char *who, const vad_cut_item *items, int64_t n
     } else {
         if (!audio) {
             // the block that the last scan uploaded is still in device memory: it crosses the link once
-            if (!e->audio_resident)
+            // (a rate block is none of vad_scan_cut's: its positions and hop count samples at another rate than the engine's)
+            if (!rate && (!e->audio_resident || e->audio_rate != 0))
                 return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the engine holds no resident block: no vad_scan or "
                                "vad_scan_channels has uploaded one", who);
+            if (rate && (!e->audio_resident || e->audio_rate == 0))
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the engine holds no resident rate block: no "
+                               "vad_scan_rate_segments or vad_scan_rate_cut has uploaded one", who);
+            if (rate && e->audio_rate != sr_in)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the resident block has sample rate %d, not %d", who,
+                               e->audio_rate, sr_in);
             if (e->audio_fmt != fmt)
                 return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the resident block has frame format %d, not %d", who,
                                e->audio_fmt, fmt);
@@ -1552,15 +1596,56 @@ int cut_run(vad_engine *e, const char *who, const vad_cut_item *items, int64_t n
         // on the device the output starts at the first segment's first sample
         for (vadk::CutSeg &sg : e->cut_segs) sg.quad_out -= (uint64_t)out_lo >> 2;
     }
-    const size_t sb = sizeof(vadk::CutSeg) * (size_t)n, wb = sizeof(vadk::CutWork) * e->cut_work.size();
-    if (int rc = ensure(e, e->d_cut, e->d_cut_cap, sb + wb)) return rc;
+    // rate_frames: one window of rows at a time goes through e->d_win.  Per window the cut kernel's segments - one per (segment
+    // of the call, window), with its place in the window and in the output - and workgroups; per tile of the call the segment
+    // that owns its first row (vad_layout.h: CutResampleArgs)
+    struct Win { uint32_t r0, r1; size_t seg0, work0, nwork; };
+    std::vector<Win> wins;
+    vad_engine::ResampleOp *op = nullptr;
+    if (rate_frames) {
+        if (int rc = get_resample_op(e, chunk, &op)) return rc;
+        const uint32_t total = (uint32_t)rows, wr = cut_window_rows(e);
+        std::vector<vadk::CutSeg> wsegs;
+        e->cut_rows.push_back(vadk::CutResampleSeg{0u, total});
+        const std::vector<vadk::CutResampleSeg> &cr = e->cut_rows;
+        size_t si = 0;
+        for (uint32_t r0 = 0; r0 < total; r0 += wr) {
+            const uint32_t r1 = (uint32_t)std::min<uint64_t>(total, (uint64_t)r0 + wr);
+            Win w{r0, r1, wsegs.size(), e->cut_work.size(), 0};
+            while (si < (size_t)n && cr[si].row0 < r1) {
+                const uint32_t lo = std::max(cr[si].row0, r0), hi = std::min(cr[si + 1].row0, r1), nq = (hi - lo) * 128u;
+                const uint32_t local = (uint32_t)(wsegs.size() - w.seg0);
+                wsegs.push_back(vadk::CutSeg{(lo - r0) * 128u, nq, e->cut_segs[si].quad_out + (uint64_t)(lo - cr[si].row0) * 128u});
+                for (uint32_t q = 0; q < nq; q += vadk::CUT_WG_QUADS) e->cut_work.push_back(vadk::CutWork{local, q});
+                if (cr[si + 1].row0 > r1) break;     // the segment goes on in the next window
+                ++si;
+            }
+            w.nwork = e->cut_work.size() - w.work0;
+            wins.push_back(w);
+        }
+        e->cut_tiles.resize(((size_t)total + vadk::MT - 1) / vadk::MT);
+        si = 0;
+        for (size_t t = 0; t < e->cut_tiles.size(); ++t) {
+            while (cr[si + 1].row0 <= (uint32_t)(t * vadk::MT)) ++si;
+            e->cut_tiles[t] = (uint32_t)si;
+        }
+        e->cut_segs.swap(wsegs);
+        if (int rc = ensure(e, e->d_win, e->d_win_cap, (size_t)std::min(total, wr) * 2048u)) return rc;
+    }
+    const size_t sb = sizeof(vadk::CutSeg) * e->cut_segs.size(), wb = sizeof(vadk::CutWork) * e->cut_work.size();
+    const size_t rb = sizeof(vadk::CutResampleSeg) * e->cut_rows.size(), tb = rate_frames ? sizeof(uint32_t) * e->cut_tiles.size() : 0;
+    if (int rc = ensure(e, e->d_cut, e->d_cut_cap, sb + wb + rb + tb)) return rc;
     if (!DEV && audio) {
         HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, ab, hipMemcpyHostToDevice, s));
         e->audio_resident = true;
-        e->audio_bytes = ab; e->audio_channels = channels; e->audio_fmt = fmt;
+        e->audio_bytes = ab; e->audio_channels = channels; e->audio_fmt = fmt; e->audio_rate = rate ? sr_in : 0;
     }
     HIP_TRY(e, hipMemcpyAsync(e->d_cut, e->cut_segs.data(), sb, hipMemcpyHostToDevice, s));
     HIP_TRY(e, hipMemcpyAsync(e->d_cut + sb, e->cut_work.data(), wb, hipMemcpyHostToDevice, s));
+    if (rate_frames) {
+        HIP_TRY(e, hipMemcpyAsync(e->d_cut + sb + wb, e->cut_rows.data(), rb, hipMemcpyHostToDevice, s));
+        HIP_TRY(e, hipMemcpyAsync(e->d_cut + sb + wb + rb, e->cut_tiles.data(), tb, hipMemcpyHostToDevice, s));
+    }
     vadk::CutArgs a{};
     a.audio = d_audio;
     a.out = d_out;
@@ -1573,17 +1658,53 @@ int cut_run(vad_engine *e, const char *who, const vad_cut_item *items, int64_t n
     a.fmt = fmt;
     a.channels = channels;
     a.out_fmt = out_fmt;
-    a.thresh = thr;
-    const hipError_t r = vadk_launch_scan_cut(&a, s);
+    a.thresh = rate && !rate_frames ? -1.0f : thr;
+    hipError_t r = hipSuccess;
+    const char *what = "kernel launch (scan cut)";
+    if (rate_frames) {
+        vadk::CutResampleArgs ra{};
+        ra.wstream = op->d_w;
+        ra.wstream_bytes = (uint32_t)op->bytes;
+        ra.tile_blocks = op->tile_blocks;
+        ra.row128_block = op->row128_block;
+        ra.audio_bytes = (uint32_t)ab;
+        ra.audio = d_audio;
+        ra.segs = reinterpret_cast<const vadk::CutResampleSeg *>(e->d_cut + sb + wb);
+        ra.tile_seg = reinterpret_cast<const uint32_t *>(e->d_cut + sb + wb + rb);
+        ra.win = e->d_win;
+        ra.n_in = chunk;
+        ra.hopq = (uint32_t)hop >> 2;
+        ra.fmt = fmt;
+        ra.channels = channels;
+        // the window as the cut kernel sees it: mono float32 frames of 512 samples, back to back
+        a.audio = e->d_win;
+        a.hopq = VAD_FRAME_SAMPLES / 4;
+        a.fmt = VAD_FMT_F32;
+        a.channels = 1;
+        for (const Win &w : wins) {
+            ra.r0 = w.r0;
+            ra.rows_end = w.r1;
+            r = vadk_launch_cut_resample(&ra, s);
+            if (r != hipSuccess) { what = "kernel launch (cut resample)"; break; }
+            a.segs = reinterpret_cast<const vadk::CutSeg *>(e->d_cut) + w.seg0;
+            a.work = reinterpret_cast<const vadk::CutWork *>(e->d_cut + sb) + w.work0;
+            a.nwork = (uint32_t)w.nwork;
+            a.audio_bytes = (w.r1 - w.r0) * 2048u;
+            r = vadk_launch_scan_cut(&a, s);
+            if (r != hipSuccess) break;
+        }
+    } else {
+        r = vadk_launch_scan_cut(&a, s);
+    }
     if (DEV) {
         // the launch reads the engine's tables: the next scan or cut waits for it, as behind vad_scan_device
         if (!e->scan_done) HIP_TRY(e, hipEventCreateWithFlags(&e->scan_done, hipEventDisableTiming));
         HIP_TRY(e, hipEventRecord(e->scan_done, s));
         e->scan_pending = true;
-        if (r != hipSuccess) return e->hip_fail(r, "kernel launch (scan cut)");
+        if (r != hipSuccess) return e->hip_fail(r, what);
         return VAD_OK;
     }
-    if (r != hipSuccess) return e->hip_fail(r, "kernel launch (scan cut)");
+    if (r != hipSuccess) return e->hip_fail(r, what);
     // only speech crosses the link back: one copy per run of adjoining segments (packed payloads: one), the gaps stay the caller's
     for (size_t k = 0; k < spans.size();) {
         size_t m = k + 1;
@@ -1603,7 +1724,7 @@ extern "C" {
 int64_t vad_cut_samples(const vad_engine *e, int64_t nframes, int32_t hop, int32_t layout) {
     if (!e || nframes < 1 || hop < 4 || (hop & 3) || (layout != VAD_CUT_FRAMES && layout != VAD_CUT_RANGE)) return -1;
     if (nframes > (INT64_MAX >> 1) / std::max<int64_t>(hop, e->frame_samples)) return -1;
-    return cut_samples(e->frame_samples, nframes, hop, layout);
+    return cut_samples(e->frame_samples, nframes, hop, layout, e->frame_samples);
 }
 
 int vad_scan_cut(vad_engine *e, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt,
@@ -1697,17 +1818,33 @@ int vad_segments_device(vad_engine *e, const uint8_t *d_events, const int32_t *d
     return rc;
 }
 
-int vad_scan_segments(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
-                      int frame_fmt, int32_t hop, float denoise_thresh, vad_segment *segs_out, int64_t seg_cap, int64_t *nsegs_out) {
-    static const char *who = "vad_scan_segments";
+}  // extern "C"
+
+namespace {
+
+// (defined with the rate scan, further down, inside that section's extern "C" block)
+extern "C" {
+int scan_rate_check(vad_engine *e, const char *who, int32_t sr_in, int *chunk);
+int scan_rate_upload_launch(vad_engine *e, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt, int chunk,
+                            int32_t sr_in, int32_t hop, float denoise_thresh, int64_t total, bool resident);
+}
+
+// vad_scan_segments and vad_scan_rate_segments (by_rate: the recordings are at sr_in): the scan of host audio into the engine's own
+// arrays, then the extraction
+int scan_segments_run(vad_engine *e, const char *who, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples,
+                      int32_t channels, int frame_fmt, bool by_rate, int32_t sr_in, int32_t hop, float denoise_thresh, vad_segment *segs_out,
+                      int64_t seg_cap, int64_t *nsegs_out) {
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
+    int chunk = 0;                           // 0: frames of the engine's own (16 kHz recordings are vad_scan_segments's)
+    if (by_rate)
+        if (int rc = scan_rate_check(e, who, sr_in, &chunk)) return rc;
     HIP_TRY(e, hipSetDevice(e->device));
     if (int rc = scan_wait(e)) return rc;
     // the CSR positions the caller of vad_scan_channels would have passed are the plan's to make: the items packed in their order
     std::vector<int64_t> &start = e->seg_out_start;
     int64_t total = 0;
-    if (int rc = scan_plan(e, who, items, n, audio_samples, channels, frame_fmt, hop, (const int64_t *)nullptr, 0, &total, &start)) return rc;
+    if (int rc = scan_plan(e, who, items, n, audio_samples, channels, frame_fmt, hop, (const int64_t *)nullptr, 0, &total, &start, chunk)) return rc;
     if (seg_cap < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: seg_cap = %lld: bad count", who, (long long)seg_cap);
     if (!nsegs_out || (seg_cap > 0 && !segs_out) || (total > 0 && !audio))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
@@ -1717,7 +1854,11 @@ int vad_scan_segments(vad_engine *e, const vad_scan_ch_item *items, int64_t n, c
         *nsegs_out = 0;
         return VAD_OK;
     }
-    if (int rc = scan_upload_launch(e, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, total)) return rc;
+    if (chunk == 0) {
+        if (int rc = scan_upload_launch(e, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, total)) return rc;
+    } else if (int rc = scan_rate_upload_launch(e, n, audio, audio_samples, channels, frame_fmt, chunk, sr_in, hop, denoise_thresh, total, true)) {
+        return rc;
+    }
     if (int rc = ensure(e, e->d_nsegs, e->d_nsegs_cap, sizeof(long long))) return rc;
     // the table's size is known only behind the count: room for the caller's capacity and for a segment per 16 frames first, and
     // the extraction once more (the per-frame arrays are still there) in the rare case that the table is larger
@@ -1739,6 +1880,16 @@ int vad_scan_segments(vad_engine *e, const vad_scan_ch_item *items, int64_t n, c
     e->segtab_count = count;
     *nsegs_out = count;
     return VAD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vad_scan_segments(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
+                      int frame_fmt, int32_t hop, float denoise_thresh, vad_segment *segs_out, int64_t seg_cap, int64_t *nsegs_out) {
+    return scan_segments_run(e, "vad_scan_segments", items, n, audio, audio_samples, channels, frame_fmt, false, 0, hop, denoise_thresh, segs_out,
+                             seg_cap, nsegs_out);
 }
 
 int vad_scan_segments_read(vad_engine *e, int64_t first, int64_t count, vad_segment *out) {
@@ -1879,7 +2030,7 @@ int resample_chunk_len(int sr_in) {
     }
 }
 
-int get_resample_op(vad_engine *e, int n_in, vad_engine::ResampleOp **out, bool t16 = false) {
+int get_resample_op(vad_engine *e, int n_in, vad_engine::ResampleOp **out, bool t16) {
     auto &ops = t16 ? e->resample_ops16 : e->resample_ops;
     for (auto &op : ops)
         if (op.n_in == n_in) {
@@ -2077,6 +2228,28 @@ int scan_rate_launches(vad_engine *e, const void *d_audio, int64_t audio_samples
     return VAD_OK;
 }
 
+// a planned rate scan of host audio (vad_scan_rate, vad_scan_rate_segments): the block crosses the link once, in its wire format; the
+// launches write the engine's own d_probs / d_events / d_seg.  resident: the block stays as a RATE block of sr_in for
+// vad_scan_rate_cut(audio = NULL) - never as a block of vad_scan_cut's, whose positions and hop count samples at the engine's rate
+int scan_rate_upload_launch(vad_engine *e, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt, int chunk,
+                            int32_t sr_in, int32_t hop, float denoise_thresh, int64_t total, bool resident) {
+    const size_t ab = (size_t)audio_samples * (size_t)channels * sample_bytes(frame_fmt);
+    e->audio_resident = false;
+    if (int rc = ensure(e, e->d_audio, e->d_audio_cap, ab + 16)) return rc;
+    if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
+    if (int rc = ensure(e, e->d_probs, e->d_probs_cap, sizeof(float) * (size_t)total)) return rc;
+    if (int rc = ensure(e, e->d_events, e->d_events_cap, (size_t)total)) return rc;
+    if (int rc = ensure(e, e->d_seg, e->d_seg_cap, sizeof(int32_t) * (size_t)total)) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, ab, hipMemcpyHostToDevice, e->stream));
+    if (resident) {
+        e->audio_resident = true;            // whatever becomes of the launches, as in scan_upload_launch
+        e->audio_bytes = ab; e->audio_channels = channels; e->audio_fmt = frame_fmt; e->audio_rate = sr_in;
+    }
+    return scan_rate_launches(e, e->d_audio, audio_samples, channels, frame_fmt, chunk, hop, denoise_thresh, e->d_probs, e->d_events, e->d_seg, total,
+                              e->stream);
+}
+
 }  // namespace
 
 int64_t vad_scan_rate_frame_count(const vad_engine *e, int64_t nsamples, int32_t sr_in, int32_t hop) {
@@ -2108,20 +2281,8 @@ int vad_scan_rate(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const
     if (int rc = scan_plan(e, who, items, n, audio_samples, channels, frame_fmt, hop, out_start, base, &total, nullptr, chunk)) return rc;
     if (total == 0) return VAD_OK;
     if (!audio || !probs_out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    const size_t ab = (size_t)audio_samples * (size_t)channels * sample_bytes(frame_fmt);
-    // the block crosses the link once, in its wire format - but it is no block vad_scan_cut(audio = NULL) could cut: its positions
-    // and hop count samples at another rate than the engine's
-    e->audio_resident = false;
-    if (int rc = ensure(e, e->d_audio, e->d_audio_cap, ab + 16)) return rc;
-    if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
-    if (int rc = ensure(e, e->d_probs, e->d_probs_cap, sizeof(float) * (size_t)total)) return rc;
-    if (int rc = ensure(e, e->d_events, e->d_events_cap, (size_t)total)) return rc;
-    if (int rc = ensure(e, e->d_seg, e->d_seg_cap, sizeof(int32_t) * (size_t)total)) return rc;
-    HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, ab, hipMemcpyHostToDevice, e->stream));
-    if (int rc = scan_rate_launches(e, e->d_audio, audio_samples, channels, frame_fmt, chunk, hop, denoise_thresh, e->d_probs, e->d_events, e->d_seg,
-                                    total, e->stream))
-        return rc;
+    // the block crosses the link once, in its wire format, and no block stays: vad_scan_rate leaves nothing to cut
+    if (int rc = scan_rate_upload_launch(e, n, audio, audio_samples, channels, frame_fmt, chunk, sr_in, hop, denoise_thresh, total, false)) return rc;
     HIP_TRY(e, hipMemcpyAsync(probs_out + base, e->d_probs, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost, e->stream));
     if (events_out) HIP_TRY(e, hipMemcpyAsync(events_out + base, e->d_events, (size_t)total, hipMemcpyDeviceToHost, e->stream));
     if (seg_frames_out) HIP_TRY(e, hipMemcpyAsync(seg_frames_out + base, e->d_seg, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, e->stream));
@@ -2161,6 +2322,64 @@ int vad_scan_rate_device(vad_engine *e, const vad_scan_ch_item *items, int64_t n
     HIP_TRY(e, hipEventRecord(e->scan_done, s));
     e->scan_pending = true;
     return rc;
+}
+
+// ---- segment tables and segment audio behind a rate scan (vad_scan_rate_segments, vad_scan_rate_cut) -------------------------------
+int vad_scan_rate_segments(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
+                           int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, vad_segment *segs_out, int64_t seg_cap,
+                           int64_t *nsegs_out) {
+    // (sr_in == 16000: scan_rate_check answers chunk = 0, and the call is vad_scan_segments under this name)
+    return scan_segments_run(e, "vad_scan_rate_segments", items, n, audio, audio_samples, channels, frame_fmt, true, sr_in, hop, denoise_thresh,
+                             segs_out, seg_cap, nsegs_out);
+}
+
+namespace {
+
+// what comes before cut_run's checks: the engine's frames and the input rate.  No model runs, so Silero V4 and
+// VAD_ENGINE_SHARED_GPU engines pass (every engine can hold a resample operator: get_resample_op); an engine whose frames are not
+// the 512 samples the operator writes - an 8 kHz sub-model - does not.  *chunk = 0: 16 kHz, the call is vad_scan_cut.
+int rate_cut_check(vad_engine *e, const char *who, int32_t sr_in, int *chunk) {
+    if (e->frame_samples != VAD_FRAME_SAMPLES || e->sample_rate != 16000)
+        return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s: this engine runs an 8 kHz sub-model on %d-sample frames; "
+                       "resampled recordings need the 16 kHz one", who, e->frame_samples);
+    return scan_rate_check(e, who, sr_in, chunk);
+}
+
+}  // namespace
+
+int64_t vad_rate_cut_samples(const vad_engine *e, int64_t nframes, int32_t sr_in, int32_t hop, int32_t layout) {
+    if (sr_in == 16000) return vad_cut_samples(e, nframes, hop, layout);
+    const int chunk = resample_chunk_len(sr_in);
+    if (!e || chunk == 0 || nframes < 1 || hop < 4 || (hop & 3) || (layout != VAD_CUT_FRAMES && layout != VAD_CUT_RANGE)) return -1;
+    if (nframes > (INT64_MAX >> 1) / std::max<int64_t>(hop, chunk)) return -1;
+    return cut_samples(chunk, nframes, hop, layout, VAD_FRAME_SAMPLES);
+}
+
+int vad_scan_rate_cut(vad_engine *e, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt,
+                      int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *out, int64_t out_samples) {
+    static const char *who = "vad_scan_rate_cut";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    int chunk = 0;
+    {
+        std::lock_guard<std::mutex> lk(e->mu);
+        if (int rc = rate_cut_check(e, who, sr_in, &chunk)) return rc;
+    }
+    return cut_run<false>(e, who, items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, out, out_samples, nullptr,
+                          chunk, sr_in);
+}
+
+int vad_scan_rate_cut_device(vad_engine *e, const vad_cut_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
+                             int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *d_out,
+                             int64_t out_samples, void *stream) {
+    static const char *who = "vad_scan_rate_cut_device";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    int chunk = 0;
+    {
+        std::lock_guard<std::mutex> lk(e->mu);
+        if (int rc = rate_cut_check(e, who, sr_in, &chunk)) return rc;
+    }
+    return cut_run<true>(e, who, items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, d_out, out_samples,
+                         stream, chunk, sr_in);
 }
 
 // ---- AudioUtils.resample_audio for any (length, rates): whole-array Fourier resampling, operator evaluated on the fly -----

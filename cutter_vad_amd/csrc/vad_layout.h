@@ -342,6 +342,35 @@ struct ScanResampleArgs {
     int32_t channels;         // 1 or 2
 };
 
+// the frames of finished segments of a block at 8 / 24 / 48 kHz (csrc/scan_cut_resample.hip: vadk_cut_resample;
+// vad_scan_rate_cut, VAD_CUT_FRAMES).  The rows of a call are the frames of its segments in listing order, packed: segment s owns
+// the rows row0_s .. row0_{s+1} - 1 (segs has one record more than the call has segments, its row0 the total), and row r of it is
+// the n_in sample frames from 4 ((quad_in_s & mask) + (r - row0_s) hopq) on.  A launch serves the rows r0 .. rows_end - 1 - one
+// window of the engine's buffer, r0 a multiple of the tile's 32 rows - and writes row r resampled to 512 samples at
+// win + 512 (r - r0).  tile_seg[r / 32] is the segment that owns row 32 (r / 32): every segment has a row, so a thread finds its
+// row's segment at most 31 records further on.  vadk_scan_cut (unchanged) then cuts `win` as a mono float32 block with
+// hop = frame = 512, which is where the gate and the conversion to PCM16 happen.
+struct CutResampleSeg {
+    uint32_t quad_in;         // (sample_offset + first_frame * hop) / 4 | the channel mode << SCAN_MODE_SHIFT, as CutSeg::quad_in
+    uint32_t row0;            // rows of the segments listed before this one
+};
+static_assert(sizeof(CutResampleSeg) == 8, "CutResampleSeg layout");
+struct CutResampleArgs {
+    const float *wstream;     // folded operator (pack_resample_operator), as ResampleSeg
+    uint32_t wstream_bytes, tile_blocks, row128_block;
+    uint32_t audio_bytes;     // the buffer descriptor's range: the whole block
+    const void *audio;        // the block, in its wire format
+    const CutResampleSeg *segs;   // [segments + 1]
+    const uint32_t *tile_seg; // [ceil(rows / 32)], indexed by the row's tile in the whole call
+    float *win;               // [rows_end - r0][512]
+    uint32_t r0, rows_end;
+    int32_t n_in;             // chunk length: 256 / 768 / 1536
+    uint32_t hopq;            // hop / 4, in input sample frames
+    int32_t fmt;              // vad_frame_format
+    int32_t channels;         // 1 or 2
+};
+static_assert(sizeof(CutResampleArgs) == 80, "CutResampleArgs layout");
+
 // fused resample -> Silero V5 step on 16-stream tiles (csrc/silero_v5_t16.hip, RS instantiation): one launch for a tick whose
 // streams arrive at different rates.  Segment k = n streams of one input rate; stream0 = index of its first stream in the
 // call's slots / probs / events arrays.  The tiles walk the segments back to back in the order given here: tile b carries the

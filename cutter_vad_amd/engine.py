@@ -366,8 +366,8 @@ class Engine:
         ``sample_rate``: the recordings' rate when it is not the engine's - 8000, 24000 or 48000 on a 16 kHz Silero V5 engine
         (``vad_scan_rate``): the recordings are packed and uploaded at that rate, framed in chunks of ``scan_chunk_samples(sample_rate)``
         at ``hop`` INPUT samples (default half a chunk), and each chunk is resampled on the GPU to the frame the model steps -
-        ``Engine.resample`` of the decoded chunk, byte for byte.  One result per chunk; no block stays for ``cut(audio=None)``.
-        None, or the engine's own rate: the path above."""
+        ``Engine.resample`` of the decoded chunk, byte for byte.  One result per chunk; no block stays for ``cut(audio=None)``
+        (``scan_segments(sample_rate=...)`` is the scan that keeps it).  None, or the engine's own rate: the path above."""
         sr = self._scan_rate(sample_rate)
         hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
         thr = -1.0 if denoise is None else float(denoise)
@@ -439,18 +439,21 @@ class Engine:
         return n, per, two, split, block, total, fmt, offs, lens, items, start
 
     def scan_segments(self, slots, recordings, hop: Optional[int] = None, law: Optional[str] = None, i16_scale: int = 32767,
-                      denoise: Optional[float] = 0.01, channel="mix") -> np.ndarray:
+                      denoise: Optional[float] = 0.01, channel="mix", sample_rate: Optional[int] = None) -> np.ndarray:
         """``scan`` that answers with the finished segments alone (``vad_scan_segments``): the same arguments, packing, streams
         and resident block (``cut(audio=None)`` works behind it), but the per-frame results stay on the GPU, where kernels turn
         them into one record per ``VAD_EV_END`` -> a structured array (``_ffi.SEGMENT_DTYPE``) in item order, then frame order:
         ``item`` (recording i, or ``2 * i + channel`` for ``"split"``), ``first_frame`` and ``nframes`` (``segment_ranges`` gives
         the sample ranges ``speech_segments`` would), ``counted``, ``mean_prob`` and ``max_prob`` - the number, the mean and the
-        maximum of the segment's accepted probabilities from the recording's frame 0 on."""
-        hop = self.frame_samples // 2 if hop is None else int(hop)
+        maximum of the segment's accepted probabilities from the recording's frame 0 on.
+        ``sample_rate`` as in ``scan`` (``vad_scan_rate_segments``): frames are chunks at that rate, ``hop`` counts input samples,
+        and the block stays on the GPU as a block of that rate - ``cut(audio=None)`` behind it cuts at that rate."""
+        sr = self._scan_rate(sample_rate)
+        hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
         thr = -1.0 if denoise is None else float(denoise)
         with self._scan_lock:
-            n, per, two, split, block, total, fmt, offs, lens, items, start = self._scan_plan(slots, recordings, hop, law, i16_scale, channel)
-            if not two:                     # the entry point takes channel items; of a one-channel block every item hears channel 0
+            n, per, two, split, block, total, fmt, offs, lens, items, start = self._scan_plan(slots, recordings, hop, law, i16_scale, channel, sr)
+            if not two and sr is None:      # the entry point takes channel items; of a one-channel block every item hears channel 0
                 mono = items
                 items = (_ffi.ScanChItem * max(1, n))()
                 for i in range(n):
@@ -459,10 +462,16 @@ class Engine:
             table = np.zeros(int(start[-1]) // 64 + 16, _ffi.SEGMENT_DTYPE)
             count = C.c_int64(0)
             self._scan_last = None
-            self._check(self._lib.vad_scan_segments(self._h, items, n * per, block.ctypes.data_as(C.c_void_p), total, 2 if two else 1, fmt, hop,
-                                                    thr, table.ctypes.data_as(C.POINTER(_ffi.Segment)), table.size, C.byref(count)))
+            where = (self._h, items, n * per, block.ctypes.data_as(C.c_void_p), total, 2 if two else 1, fmt)
+            res = (thr, table.ctypes.data_as(C.POINTER(_ffi.Segment)), table.size, C.byref(count))
+            if sr is not None:
+                self._check(self._lib.vad_scan_rate_segments(*where, sr, hop, *res))
+            else:
+                self._check(self._lib.vad_scan_segments(*where, hop, *res))
             if int(start[-1]):
                 self._scan_last = {"samples": total, "channels": 2 if two else 1, "fmt": fmt, "offsets": offs, "lengths": lens}
+                if sr is not None:
+                    self._scan_last["rate"] = sr
             if count.value > table.size:
                 rest = np.zeros(count.value - table.size, _ffi.SEGMENT_DTYPE)
                 self._check(self._lib.vad_scan_segments_read(self._h, table.size, rest.size, rest.ctypes.data_as(C.POINTER(_ffi.Segment))))
@@ -530,15 +539,23 @@ class Engine:
 
     @property
     def last_scan(self) -> Optional[dict]:
-        """What ``scan`` packed last - ``samples``, ``channels``, ``fmt``, ``offsets``, ``lengths`` (sample frames of the block) -
-        or None; meaningful inside ``scan_session()``."""
+        """What ``scan`` packed last - ``samples``, ``channels``, ``fmt``, ``offsets``, ``lengths`` (sample frames of the block), and
+        ``rate`` when it is a block at another rate than the engine's (``scan_segments(sample_rate=...)``) - or None; meaningful
+        inside ``scan_session()``."""
         return self._scan_last
 
-    def cut_samples(self, nframes: int, hop: Optional[int] = None, layout="frames") -> int:
+    def cut_samples(self, nframes: int, hop: Optional[int] = None, layout="frames", sample_rate: Optional[int] = None) -> int:
         """Samples of a segment of ``nframes`` frames (``vad_cut_samples``): ``nframes * frame_samples`` for ``"frames"``,
-        ``(nframes - 1) * hop + frame_samples`` for ``"range"``."""
-        hop = self.frame_samples // 2 if hop is None else int(hop)
-        n = int(self._lib.vad_cut_samples(self._h, int(nframes), hop, self._cut_enum(_ffi.CUT_LAYOUTS, "layout", layout)))
+        ``(nframes - 1) * hop + frame_samples`` for ``"range"``.  ``sample_rate`` (``vad_rate_cut_samples``): a segment of a block at
+        that rate - ``nframes * 512`` samples at 16 kHz for ``"frames"``, ``(nframes - 1) * hop + scan_chunk_samples(sample_rate)``
+        input samples for ``"range"``."""
+        sr = self._scan_rate(sample_rate)
+        hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
+        lay = self._cut_enum(_ffi.CUT_LAYOUTS, "layout", layout)
+        if sr is None:
+            n = int(self._lib.vad_cut_samples(self._h, int(nframes), hop, lay))
+        else:
+            n = int(self._lib.vad_rate_cut_samples(self._h, int(nframes), sr, hop, lay))
         if n < 0:
             raise AudioProcessingError(f"Model prediction failed: bad frame count, hop or layout ({nframes}, {hop}, {layout!r})")
         return n
@@ -549,27 +566,29 @@ class Engine:
             return table[v]
         raise AudioProcessingError(f"Model prediction failed: {what} is one of {sorted(table)}, got {v!r}")
 
-    def _cut_items(self, segments, hop: int, layout: int, channels: int, out_samples=None):
+    def _cut_items(self, segments, hop: int, layout: int, channels: int, out_samples=None, rate: Optional[int] = None):
         """segments: (sample_offset, first_frame, nframes[, channel]) each -> (items, out_start [n + 1]): payloads packed in the
-        order listed, unless ``out_samples`` gives every segment's first output sample"""
+        order listed, unless ``out_samples`` gives every segment's first output sample; ``rate``: a block at that rate - a frame
+        is a chunk in the block and 512 samples in a ``"frames"`` payload"""
         segs = [tuple(sg) for sg in segments]
         n = len(segs)
         items = (_ffi.CutItem * max(1, n))()
         start = np.zeros(n + 1, np.int64)
-        frame = self.frame_samples
+        frame = self.frame_samples if rate is None else self.scan_chunk_samples(rate)
+        out_frame = self.frame_samples if rate is None else 512
         for i, sg in enumerate(segs):
             if len(sg) not in (3, 4):
                 raise AudioProcessingError(f"Model prediction failed: a segment is (sample_offset, first_frame, nframes[, channel]), got {sg!r}")
             ch = (_ffi.VAD_SCAN_MIX if channels == 2 else 0) if len(sg) == 3 else self._scan_channel(sg[3])
             nf = int(sg[2])
-            count = nf * frame if layout == _ffi.VAD_CUT_FRAMES else (nf - 1) * hop + frame
+            count = nf * out_frame if layout == _ffi.VAD_CUT_FRAMES else (nf - 1) * hop + frame
             o = int(start[i]) if out_samples is None else int(out_samples[i])
             items[i] = _ffi.CutItem(int(sg[0]), int(sg[1]), nf, o, ch, 0)
             start[i + 1] = start[i] + max(count, 0)
         return items, start
 
     def cut(self, segments, hop: Optional[int] = None, law: Optional[str] = None, i16_scale: int = 32767, denoise: Optional[float] = 0.01,
-            layout="frames", out="pcm16", audio=None):
+            layout="frames", out="pcm16", audio=None, sample_rate: Optional[int] = None):
         """The audio of finished segments (``vad_scan_cut``): ``segments`` lists ``(sample_offset, first_frame, nframes[, channel])``
         - the recording's first sample frame in the block, the segment's first frame (``e - L + 1`` for an END at frame ``e`` with
         ``seg_frames`` ``L``) and its length in frames; ``channel`` as in ``scan`` (default: ``"mix"`` of a two-channel block).
@@ -579,14 +598,23 @@ class Engine:
         ``audio=None``: the block ``scan`` packed last, which is still on the GPU - nothing is uploaded; format, channels and
         size are that scan's (``law`` / ``i16_scale`` are ignored).  Another thread's ``scan`` would replace the block: hold
         ``scan_session()`` around the scan and the cut.  ``audio``: a block of its own, a 1-D array or a C-contiguous
-        ``[nsamples, 2]`` array (float32, int16, or uint8 codes with ``law``); it is uploaded and becomes the resident block."""
+        ``[nsamples, 2]`` array (float32, int16, or uint8 codes with ``law``); it is uploaded and becomes the resident block.
+        ``sample_rate`` (``vad_scan_rate_cut``): the block is at 8000, 24000 or 48000 Hz - ``first_frame`` / ``nframes`` count chunks of
+        ``scan_chunk_samples(sample_rate)`` at ``hop`` input samples.  ``"frames"``: each chunk resampled on the GPU to the 512 samples
+        the model read (``Engine.resample`` of the decoded chunk, byte for byte), then gated; ``"range"``: the segment's own samples at
+        the input rate, NOT gated.  With ``audio=None`` behind ``scan_segments(sample_rate=...)`` the rate is that scan's; another
+        ``sample_rate`` given then is an error.  With an ``audio``, ``sample_rate`` names its rate."""
         lay, of = self._cut_enum(_ffi.CUT_LAYOUTS, "layout", layout), self._cut_enum(_ffi.CUT_OUTPUTS, "out", out)
-        hop = self.frame_samples // 2 if hop is None else int(hop)
+        sr = self._scan_rate(sample_rate)
         with self._scan_lock:
             if audio is None:
                 last = self._scan_last
                 if last is None:
                     raise AudioProcessingError("Model prediction failed: cut(audio=None) follows a scan() of this engine that uploaded a block")
+                if sample_rate is not None and sr != last.get("rate"):
+                    raise AudioProcessingError(f"Model prediction failed: cut(audio=None, sample_rate={sample_rate}): the block of the last scan "
+                                               f"is at {last.get('rate', self.sample_rate)} Hz")
+                sr = last.get("rate")
                 total, channels, fmt, ptr = last["samples"], last["channels"], last["fmt"], None
             else:
                 block = np.asarray(audio)
@@ -602,25 +630,35 @@ class Engine:
                     fmt = _ffi.VAD_FMT_I16_32768
                 ptr = block.ctypes.data_as(C.c_void_p)
                 self._scan_last = None      # the engine's resident block is this one now, not the last scan's
-            items, start = self._cut_items(segments, hop, lay, channels)
+            hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
+            items, start = self._cut_items(segments, hop, lay, channels, rate=sr)
             data = np.empty(int(start[-1]), np.int16 if of == _ffi.VAD_CUT_PCM16 else np.float32)
             thr = -1.0 if denoise is None else float(denoise)
-            self._check(self._lib.vad_scan_cut(self._h, items, len(start) - 1, ptr, total, channels, fmt, hop, thr, lay, of,
-                                               data.ctypes.data_as(C.c_void_p), data.size))
+            res = (thr, lay, of, data.ctypes.data_as(C.c_void_p), data.size)
+            if sr is not None:
+                self._check(self._lib.vad_scan_rate_cut(self._h, items, len(start) - 1, ptr, total, channels, fmt, sr, hop, *res))
+            else:
+                self._check(self._lib.vad_scan_cut(self._h, items, len(start) - 1, ptr, total, channels, fmt, hop, *res))
         return data, start
 
     def cut_device(self, segments, d_audio: int, audio_samples: int, d_out: int, out_samples: int, hop: Optional[int] = None,
                    fmt: int = _ffi.VAD_FMT_F32, channels: int = 1, denoise: Optional[float] = 0.01, layout="frames", out="pcm16",
-                   stream: int = 0, out_start=None) -> np.ndarray:
+                   stream: int = 0, out_start=None, sample_rate: Optional[int] = None) -> np.ndarray:
         """``cut`` on device pointers (integers; ``vad_scan_cut_device``): the block at ``d_audio`` (4-byte aligned, 8 for two
         channels), the payloads to ``d_out`` (16-byte aligned, room for ``out_samples`` samples), packed in the order listed
-        or at ``out_start[i]`` (multiples of 4).  Asynchronous on ``stream``.  -> start [n + 1] of the packed order."""
+        or at ``out_start[i]`` (multiples of 4).  Asynchronous on ``stream``.  -> start [n + 1] of the packed order.
+        ``sample_rate`` as in ``cut`` (``vad_scan_rate_cut_device``): the block is at that rate."""
         lay, of = self._cut_enum(_ffi.CUT_LAYOUTS, "layout", layout), self._cut_enum(_ffi.CUT_OUTPUTS, "out", out)
-        hop = self.frame_samples // 2 if hop is None else int(hop)
-        items, start = self._cut_items(segments, hop, lay, int(channels), out_start)
+        sr = self._scan_rate(sample_rate)
+        hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
+        items, start = self._cut_items(segments, hop, lay, int(channels), out_start, rate=sr)
         thr = -1.0 if denoise is None else float(denoise)
-        self._check(self._lib.vad_scan_cut_device(self._h, items, len(start) - 1, d_audio or None, int(audio_samples), int(channels), int(fmt),
-                                                  hop, thr, lay, of, d_out or None, int(out_samples), stream or None))
+        where = (self._h, items, len(start) - 1, d_audio or None, int(audio_samples), int(channels), int(fmt))
+        res = (thr, lay, of, d_out or None, int(out_samples), stream or None)
+        if sr is not None:
+            self._check(self._lib.vad_scan_rate_cut_device(*where, sr, hop, *res))
+        else:
+            self._check(self._lib.vad_scan_cut_device(*where, hop, *res))
         return start
 
     # ------------------------------------------------------------------ tick assembler (shared-pool serving)

@@ -52,16 +52,16 @@ def _scan_ranges(engine, slots, recordings, per: int, frame: int, hop: int, law,
     the finished segments ``(start_sample, end_sample)`` - with ``stats``: ``(start_sample, end_sample, mean_prob, max_prob)``.
     An engine with ``scan_segments`` builds the table on the GPU and copies back that alone; any other goes through the per-frame
     results of ``scan``.  Same ranges either way.  ``rate``: the recordings' sample rate when it is not the engine's (``frame`` and
-    ``hop`` are then a chunk and a hop in input samples): the per-frame path, the segment table has no rate form yet."""
+    ``hop`` are then a chunk and a hop in input samples; ``vad_scan_rate_segments`` builds the table)."""
     sl = np.asarray(slots).reshape(len(recordings), per) if per == 2 else slots
-    if rate is None and hasattr(engine, "scan_segments"):
-        table = engine.scan_segments(sl, recordings, hop=hop, law=law, denoise=denoise, channel=channel)
+    kw = {} if rate is None else {"sample_rate": rate}
+    if hasattr(engine, "scan_segments"):
+        table = engine.scan_segments(sl, recordings, hop=hop, law=law, denoise=denoise, channel=channel, **kw)
         out = [[[] for _ in range(per)] for _ in recordings]
         extra = zip(table["mean_prob"].tolist(), table["max_prob"].tolist())
         for item, rg, st in zip(table["item"].tolist(), segment_ranges(table, frame, hop), extra):
             out[item // per][item % per].append(rg + st if stats else rg)
         return out
-    kw = {} if rate is None else {"sample_rate": rate}
     probs, ev, seg = engine.scan(sl, recordings, hop=hop, law=law, denoise=denoise, channel=channel, **kw)
     out = []
     for p, e, g in zip(probs, ev, seg):
@@ -132,14 +132,20 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
 
 
 def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
-                   law: Optional[str] = None, channel="mix", layout: str = "frames", wav: bool = True) -> List:
+                   law: Optional[str] = None, channel="mix", layout: str = "frames", wav: bool = True,
+                   sample_rate: Optional[int] = None) -> List:
     """``scan_recordings`` with each finished segment's audio: per recording ``[(start_sample, end_sample, payload), ...]`` (per
     channel for ``"split"``, as there).  ``payload`` is what ``VADWrapper``'s ``voice_end`` callback delivers for the same
     recording - the segment's frames back to back, decoded, mixed and gated as the model read them, as 16-bit PCM behind the WAV
     header of ``config.output_wav_sample_rate`` - or, with ``wav=False``, the int16 samples themselves; ``layout="range"`` gives
     the samples ``[start_sample, end_sample)`` once.  The corpus crosses the link once: one scan, then one cut of the block that
     the scan left on the GPU (``Engine.cut(audio=None)``, under ``Engine.scan_session()``), and one copy back of the speech alone
-    - two of each for a corpus of 1-D and 2-D recordings."""
+    - two of each for a corpus of 1-D and 2-D recordings.
+    ``sample_rate`` as in ``scan_recordings``: the recordings are at 8000, 24000 or 48000 Hz, ``hop`` and the ranges count INPUT-rate
+    samples, and the scan is the rate scan (``Engine.scan_segments(sample_rate=...)``).  ``layout="frames"`` is still the
+    ``voice_end`` payload - the 16 kHz frames the model read, each chunk resampled on the GPU and gated, behind the header of
+    ``config.output_wav_sample_rate``; ``layout="range"`` gives the samples ``[start_sample, end_sample)`` of the recording itself,
+    at its own rate and not gated, behind a header that carries ``sample_rate``."""
     from .pool import default_pool, resolve_model_path
     from .utils.wav_writer import WAVWriter
     split = isinstance(channel, str) and channel == "split"
@@ -154,11 +160,16 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
     if cfg.buffer_size != frame:
         raise ConfigurationError(f"cut_recordings frames at the model's frame size: buffer_size = {cfg.buffer_size}, "
                                  f"the engine's frames have {frame} samples")
+    rate = None if sample_rate is None or int(sample_rate) == int(engine.sample_rate) else int(sample_rate)
+    if rate is not None:
+        if rate not in (8000, 16000, 24000, 48000):
+            raise ConfigurationError("sample_rate", repr(sample_rate), f"cut_recordings: recordings at 8000, 16000, 24000 or 48000 Hz, got {sample_rate!r}")
+        frame = engine.scan_chunk_samples(rate)      # the ranges count input samples
     hop = frame // 2 if hop is None else int(hop)
     recordings = [np.asarray(r) for r in recordings]
     if not recordings:
         return []
-    writer = WAVWriter(cfg.output_wav_sample_rate, 16, 1)
+    writer = WAVWriter(rate if rate is not None and layout == "range" else cfg.output_wav_sample_rate, 16, 1)
     denoise = 0.01 if cfg.enable_denoising else None
     out: List = [None] * len(recordings)
     for two in (False, True):
@@ -173,7 +184,7 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
                                                cfg.voice_end_ratio, cfg.voice_start_frame_count, cfg.voice_end_frame_count))
             with engine.scan_session():
                 # (recording, channel) -> its sample ranges; the cut's table lists them in that order
-                ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, denoise, channel)
+                ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, denoise, channel, rate=rate)
                 table = [(int(engine.last_scan["offsets"][k]), a // hop, (b - a - frame) // hop + 1, chans[c])
                          for k, rc in enumerate(ranges) for c, rg in enumerate(rc) for a, b in rg]
                 if table:

@@ -340,8 +340,9 @@ VAD_API int vad_debug_scan_launch_frames(vad_engine *e, int32_t frames);
  *   sr_in == 16000 IS vad_scan_channels (AudioUtils.resample_audio returns its input).  Any other rate: VAD_ERR_UNSUPPORTED
  * ("supported input rates are ..").  VAD_ERR_UNSUPPORTED also for engines of the 8 kHz sub-model, Silero V4 and
  * VAD_ENGINE_SHARED_GPU engines.
- *   A rate scan leaves NO block resident: vad_scan_cut(audio = NULL) behind it is refused (positions and hop of a cut count
- * samples at the engine's rate).  (sr_in == 16000: vad_scan_channels's block, as there.)
+ *   vad_scan_rate leaves NO block resident: vad_scan_cut(audio = NULL) behind it is refused (positions and hop of a cut count
+ * samples at the engine's rate), and so is vad_scan_rate_cut(audio = NULL) - the scan that keeps its block for a cut is
+ * vad_scan_rate_segments, below.  (sr_in == 16000: vad_scan_channels's block, as there.)
  *   VAD_ABI_VERSION is unchanged: the presence of vad_scan_rate is how a caller detects the feature.
  */
 VAD_API int64_t vad_scan_rate_frame_count(const vad_engine *e, int64_t nsamples, int32_t sr_in, int32_t hop);
@@ -466,6 +467,60 @@ VAD_API int vad_scan_segments(vad_engine *e, const vad_scan_ch_item *items, int6
                               int32_t channels, int frame_fmt, int32_t hop, float denoise_thresh, vad_segment *segs_out, int64_t seg_cap,
                               int64_t *nsegs_out);
 VAD_API int vad_scan_segments_read(vad_engine *e, int64_t first, int64_t count, vad_segment *out);
+
+/*
+ * Segment tables and segment audio for recordings at 8 / 24 / 48 kHz: vad_scan_segments and vad_scan_cut behind vad_scan_rate.
+ * Positions, lengths and hop count sample frames at sr_in throughout; a frame of a recording is a chunk of 512 * sr_in / 16000
+ * sample frames (256 / 768 / 1536), chunk t of a recording the sample frames sample_offset + t * hop .. + chunk - 1.
+ *
+ * vad_scan_rate_segments: vad_scan_rate without its per-frame results, exactly as vad_scan_segments is to vad_scan_channels.  Every
+ * check, refusal and message of vad_scan_rate applies, under this function's name, and vad_scan_segments's further ones (seg_cap
+ * < 0, a null nsegs_out, a null segs_out with seg_cap > 0).  The call uploads the block, runs the rate scan's launches into the
+ * engine's own arrays, then the extraction (items in the order given, out_start = the running sum of vad_scan_rate_frame_count),
+ * and copies back the count and the first min(count, seg_cap) records; first_frame and nframes count chunks, the statistics
+ * follow the vad_segment rule, and the whole table stays in device memory for vad_scan_segments_read.  Streams, vad_info.steps and
+ * vad_info.frames are left as vad_scan_rate leaves them.  sr_in == 16000 IS vad_scan_segments.
+ *   The block stays resident AS A RATE BLOCK: the engine remembers its size in bytes, channel count, frame format and sr_in, and
+ * only vad_scan_rate_cut(audio = NULL) naming the same four accepts it; vad_scan_cut(audio = NULL) behind it is refused as with
+ * no resident block.  The two kinds of resident block share one buffer and exclude each other: whatever uploads a block (any
+ * scan or cut of host audio) replaces the other kind - or, as vad_scan_rate does, leaves none.
+ *
+ * vad_scan_rate_cut / vad_scan_rate_cut_device: vad_scan_cut / vad_scan_cut_device for such a block.  vad_cut_item is unchanged;
+ * first_frame and nframes count chunks.
+ *   VAD_CUT_FRAMES: the frames the model read - the reference's voice_end payload for such a recording.  Each of the segment's
+ * nframes chunks is decoded and channel-selected as the scans' loader does, resampled to 512 samples by the operator vad_resample
+ * applies (byte for byte vad_resample of the decoded float32 chunk, as in vad_scan_rate), then gated on the RESAMPLED value
+ * (|x| > denoise_thresh ? x : 0; denoise_thresh < 0: no gate) where the rate scan's model launch gates; the frames are written
+ * back to back, nframes * 512 samples at 16 kHz.
+ *   VAD_CUT_RANGE: the segment's own audio at the INPUT rate, once: (nframes - 1) * hop + chunk samples, decoded and
+ * channel-selected, and NOT gated, whatever denoise_thresh says - the model gated resampled frames, no input-rate sample was ever
+ * gated.
+ *   vad_rate_cut_samples gives either count (-1: nframes < 1, hop < 4 or not a multiple of 4, an unknown layout or rate;
+ * sr_in == 16000: vad_cut_samples).  out_fmt, out_sample, the non-overlap of the output ranges, the alignment rules, audio == NULL
+ * (the resident RATE block; a refusal says which of rate, format, channels and size differs), "with an audio the call uploads
+ * it, and it becomes the resident (rate) block", "a refused call writes nothing", non-finite float32 input (an unspecified
+ * payload, the call completes) and the wait for earlier *_device launches are vad_scan_cut's; so are the checks, each before the
+ * first write, with the chunk as the frame in the block-bounds check.  VAD_ERR_UNSUPPORTED: a rate outside 8000 / 16000 / 24000 /
+ * 48000, and an engine of an 8 kHz sub-model (whose frames are not the 512 samples the operator writes), with vad_scan_rate's
+ * messages.  sr_in == 16000 IS vad_scan_cut / vad_scan_cut_device.
+ *   Works on Silero V4 and VAD_ENGINE_SHARED_GPU engines (at 16 kHz) as well: no model kernel runs, no stream is touched, and
+ * every engine holds the resample operators vad_resample uses.
+ *   VAD_CUT_FRAMES goes through an engine-owned window of at most 256 MiB of resampled frames (131 072 of them); a larger call is
+ * served window by window, with the same bytes.  vad_debug_scan_launch_frames(f > 0) cuts the window to 32 * f frames (tests).
+ *   vad_scan_rate_cut_device enqueues on `stream` (NULL = the engine's own) and returns, like vad_scan_cut_device; its launches
+ * read the engine's tables and window buffer, so the next scan, cut or extraction waits for them.
+ *   VAD_ABI_VERSION is unchanged: the presence of vad_scan_rate_segments / vad_scan_rate_cut is how a caller detects the feature.
+ */
+VAD_API int vad_scan_rate_segments(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples,
+                                   int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh,
+                                   vad_segment *segs_out, int64_t seg_cap, int64_t *nsegs_out);
+VAD_API int64_t vad_rate_cut_samples(const vad_engine *e, int64_t nframes, int32_t sr_in, int32_t hop, int32_t layout);
+VAD_API int vad_scan_rate_cut(vad_engine *e, const vad_cut_item *items, int64_t n, const void *audio /*or NULL*/, int64_t audio_samples,
+                              int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout,
+                              int32_t out_fmt, void *out, int64_t out_samples);
+VAD_API int vad_scan_rate_cut_device(vad_engine *e, const vad_cut_item *items, int64_t n, const void *d_audio, int64_t audio_samples,
+                                     int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout,
+                                     int32_t out_fmt, void *d_out, int64_t out_samples, void *stream);
 
 /*
  * Pipelined host ingest.  vad_step* on host pointers are copy -> kernel -> copy -> wait; at 8 192 streams the PCIe copy is

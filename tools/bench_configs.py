@@ -919,6 +919,86 @@ def scan_rate():
     return row
 
 
+def scan_rate_cut():
+    """The audio of finished segments of recordings at 48 kHz, resampled on the GPU in the cut: vad_scan_rate_cut_device
+    (VAD_CUT_FRAMES, PCM16) on VAD_SCAN_BENCH_N (default 4 096) int16 recordings of 30 s at 48 kHz - the golden clip, every sample
+    three times - already in device memory, hop = chunk / 2, against vad_scan_cut_device on recordings of the same durations at
+    16 kHz, which the parent commit has.  The segments of a recording come from vad_scan_rate_segments (vad_scan_segments at 16 kHz)
+    on a few copies of it, client thresholds; every recording of the corpus is that recording, so it has those segments.  The corpus
+    goes through in calls of 728 recordings (one call addresses under 2 GiB), on one device block per rate, into one device output
+    that every call of that rate overwrites.  One warm-up pass over the corpus, then three timed ones (wall clock around the calls
+    and the engine's synchronize, alternating the two rates); the medians and their ratio go to profiles/scan_rate_cut.json."""
+    import time
+    import numpy as np
+    N = int(os.environ.get("VAD_SCAN_BENCH_N", "4096"))
+    per_call, seconds = int(os.environ.get("VAD_SCAN_BENCH_PER_CALL", "728")), 30
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    pcm = np.load(os.path.join(root, "tests", "golden", "speech16k_i16.npz"))["pcm"].astype(np.int16)
+    one16 = np.resize(pcm, seconds * 16000)
+    eng = Engine(blob(5), max_streams=16)
+    slots = eng.open_streams(4)
+    groups = [min(per_call, N - a) for a in range(0, N, per_call)]
+    row = {"config": f"scan_rate_cut: {N} int16 recordings of {seconds} s in device memory, hop = chunk / 2, frames as PCM16, calls of "
+                     f"{per_call} recordings", "recordings": N, "calls": len(groups)}
+    passes = {}
+    for sr in (48000, 16000):
+        one = np.repeat(one16, sr // 16000)
+        chunk = eng.scan_chunk_samples(sr)
+        hop = chunk // 2
+        eng.reset(slots)
+        eng.set_thresholds_many(slots, (0.4, 0.3, 0.8, 0.95, 6, 12))
+        table = eng.scan_segments(slots, [one] * 4, hop=hop, denoise=0.01, sample_rate=sr)
+        mine = [(int(r["first_frame"]), int(r["nframes"])) for r in table if r["item"] == 0]
+        assert mine and all([(int(r["first_frame"]), int(r["nframes"])) for r in table if r["item"] == k] == mine for k in range(4))
+        block = torch.from_numpy(np.tile(one, per_call)).cuda()
+        segs = [(k * one.size, f, n) for k in range(per_call) for f, n in mine]
+        per_rec = sum(n for _, n in mine) * 512
+        d_out = torch.empty(per_call * per_rec, dtype=torch.int16, device="cuda")
+        torch.cuda.synchronize()
+
+        # the calls' item tables, built once: the timed window holds the C entry points alone
+        tables = {g: eng._cut_items(segs[:g * len(mine)], hop, 0, 1, rate=None if sr == 16000 else sr)[0] for g in set(groups)}
+
+        def corpus(sr=sr, block=block, tables=tables, d_out=d_out, hop=hop, size=one.size, nseg=len(mine), per_rec=per_rec):
+            for g in groups:
+                where = (eng.handle, tables[g], g * nseg, block.data_ptr(), g * size, 1, 1)
+                res = (0.01, 0, 0, d_out.data_ptr(), g * per_rec, None)
+                rc = eng._lib.vad_scan_rate_cut_device(*where, sr, hop, *res) if sr != 16000 else eng._lib.vad_scan_cut_device(*where, hop, *res)
+                assert rc == 0, rc
+            eng.synchronize()
+
+        key = f"{sr // 1000}k"
+        passes[key] = corpus
+        row[f"segments_per_recording_{key}"] = len(mine)
+        row[f"frames_cut_{key}"] = N * per_rec // 512
+        row[f"payload_GB_{key}"] = N * per_rec * 2 / 1e9
+        row[f"audio_GB_{key}"] = N * one.size * 2 / 1e9
+    runs = {k: [] for k in passes}
+    for fn in passes.values():
+        fn()
+    for _ in range(3):
+        for k, fn in passes.items():
+            t0 = time.perf_counter()
+            fn()
+            runs[k].append(time.perf_counter() - t0)
+    for k, v in runs.items():
+        row[f"s_{k}_runs"] = v
+        row[f"s_{k}"] = float(np.median(v))
+        row[f"us_per_frame_{k}"] = row[f"s_{k}"] / row[f"frames_cut_{k}"] * 1e6
+    row["entry_points"] = {"48k": "vad_scan_rate_cut_device", "16k": "vad_scan_cut_device"}
+    row["s_48k_over_s_16k"] = row["s_48k"] / row["s_16k"]
+    eng.close()
+    with open(os.path.join(root, "profiles", "scan_rate_cut.json"), "w") as f:
+        json.dump({"what": "finished segments' frames of recordings at 48 kHz, resampled on the GPU in the cut (vad_scan_rate_cut, "
+                           "csrc/scan_cut_resample.hip): DESIGN 2.1k",
+                   "how": "python tools/bench_configs.py scan_rate_cut on one MI355X, one process: one warm-up pass over the corpus per "
+                          "rate, then three timed passes per rate, alternating (time.perf_counter around the vad_scan*_cut_device calls "
+                          "of 728 recordings - table building and upload included - and the engine's synchronize); s_48k and s_16k are "
+                          "the medians.  One process on one box: the spread between processes is not known", "result": row}, f, indent=1)
+        f.write("\n")
+    return row
+
+
 def single_stream_wrapper():
     """configs[0]: ONE stream through the drop-in VADWrapper (host framing + one launch + sync + callbacks per chunk)."""
     import time

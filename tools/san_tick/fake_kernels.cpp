@@ -248,6 +248,39 @@ extern "C" hipError_t vadk_launch_scan_resample(const ScanResampleArgs *a, hipSt
     return hipSuccess;
 }
 
+// one window of a rate cut's frames (csrc/scan_cut_resample.hip: vadk_cut_resample), under the rule of vadk_launch_scan_resample
+// above: row r of the call = a frame of zeros whose first sample is the first decoded, channel-selected sample of chunk r - row0 of
+// the segment that owns the row (a NaN when the float32 chunk holds a NaN / Inf), written at row r - r0 of the window.  The row's
+// segment is found as the kernel finds it: from the tile's first segment on.
+extern "C" hipError_t vadk_launch_cut_resample(const CutResampleArgs *a, hipStream_t) {
+    const bool two = a->channels == 2;
+    const size_t fb = (size_t)(two ? 2 : 1) * (a->fmt == VAD_FMT_F32 ? 4 : a->fmt >= VAD_FMT_ULAW8 ? 1 : 2);
+    if (a->r0 % (uint32_t)MT) return hipErrorInvalidValue;
+    for (uint32_t r = a->r0; r < a->rows_end; ++r) {
+        uint32_t s = a->tile_seg[r / (uint32_t)MT];
+        if (a->segs[s].row0 > r - r % (uint32_t)MT) return hipErrorInvalidValue;
+        int steps = 0;
+        while (a->segs[s + 1].row0 <= r) ++s, ++steps;
+        if (steps >= MT) return hipErrorInvalidValue;
+        const CutResampleSeg sg = a->segs[s];
+        const uint32_t mode = sg.quad_in >> SCAN_MODE_SHIFT, quad0 = sg.quad_in & ((1u << SCAN_MODE_SHIFT) - 1u);
+        auto sample = [&](size_t k) -> float {
+            if (!two) return first_sample(a->audio, k, a->fmt, 1);
+            const float l = first_sample(a->audio, 2 * k, a->fmt, 1), rr = first_sample(a->audio, 2 * k + 1, a->fmt, 1);
+            return mode == SCAN_MIX ? (l + rr) * 0.5f : mode == SCAN_RIGHT ? rr : l;
+        };
+        const size_t first = 4 * ((size_t)quad0 + (size_t)(r - sg.row0) * a->hopq);
+        if ((first + (size_t)a->n_in) * fb > a->audio_bytes) return hipErrorInvalidValue;
+        float *o = a->win + (size_t)(r - a->r0) * 512;
+        std::memset(o, 0, 512 * sizeof(float));
+        o[0] = sample(first);
+        if (a->fmt == VAD_FMT_F32)
+            for (int k = 0; k < a->n_in; ++k)
+                if (!std::isfinite(sample(first + k))) o[0] = std::nanf("");
+    }
+    return hipSuccess;
+}
+
 extern "C" hipError_t vadk_launch_g711_expand(const void *d_in, int16_t *d_out, int64_t nbytes, int alaw, hipStream_t) {
     for (int64_t i = 0; i < nbytes; ++i) d_out[i] = g711_pcm(static_cast<const uint8_t *>(d_in)[i], alaw != 0);
     return hipSuccess;
