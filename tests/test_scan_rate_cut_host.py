@@ -275,6 +275,45 @@ def test_frames_start_with_their_chunks_first_sample_and_range_is_the_block_itse
         lib.vad_debug_scan_launch_frames(eng.handle, 0)
 
 
+@pytest.mark.parametrize("sr,kind,two,gate,out_fmt", [(24000, "i16_32767", False, 0.01, PCM16), (48000, "f32", True, None, F32)],
+                         ids=["24000-i16-mono-gate-pcm16", "48000-f32-stereo-nogate-f32"])
+def test_cut_windows_of_32_64_and_160_rows_change_no_byte(lib, make_engine, sr, kind, two, gate, out_fmt):
+    """tests/test_gpu_scan_rate_cut.py's SEGS table (300 rows) over its block at hop = chunk / 2, under launch caps 1, 2 and 5: windows
+    of 32, 64 and 160 rows, every boundary inside a segment, tiles that three segments share.  The stand-in's cut reads window row
+    r - r0 through the per-window CutSeg {(lo - r0) * 128, (hi - lo) * 128, quad_out + (lo - row0) * 128}, and refuses a tile_seg entry
+    that does not own its tile's first row: the payload is the uncapped call's, and frame j of a segment = zeros behind the gated
+    first sample of its chunk."""
+    from tests.test_gpu_scan_rate_cut import SEGS, _block, _items
+    eng = make_engine()
+    chunk = CHUNK[sr]
+    hop = chunk // 2
+    assert sum(nf for _, _, nf in SEGS) == 300
+    block, offs, lens = _block(kind, sr, hop, two, seed=53)
+    items, total = _items(SEGS, offs, hop, chunk, FRAMES, two)
+    thr = -1.0 if gate is None else gate
+    outs = {}
+    try:
+        for cap in (0, 1, 2, 5):
+            lib.vad_debug_scan_launch_frames(eng.handle, cap)
+            for device in (False, True):
+                rc, msg, out = rate_cut(lib, eng, items, block, 2 if two else 1, FMT[kind], sr, hop, FRAMES, out_fmt, total, thr=thr, device=device)
+                assert rc == _ffi.VAD_OK, (cap, msg)
+                outs[cap, device] = out
+    finally:
+        lib.vad_debug_scan_launch_frames(eng.handle, 0)
+    base = outs[0, False]
+    written = np.zeros(base.size, bool)
+    for off, first, nf, o, c in items:
+        f = np.zeros((nf, 512), np.float32)
+        f[:, 0] = R.gate(R.heard(block, kind, c)[off + first * hop:off + (first + nf) * hop:hop][:nf], gate)
+        want = f.reshape(-1) if out_fmt == F32 else R.pcm16(f.reshape(-1))
+        assert np.array_equal(base[o:o + want.size], want), (off, first, nf)
+        written[o:o + want.size] = True
+    assert untouched(base[~written]) and (~written).sum() >= 12 + 8 and base[written].any()
+    for key, out in outs.items():
+        assert out.tobytes() == base.tobytes(), key
+
+
 def test_a_float_chunk_with_a_nan_completes(lib, make_engine):
     eng = make_engine()
     x = np.full(4 * 256, 0.25, np.float32)

@@ -241,6 +241,30 @@ def test_caps_1_2_and_5_give_the_ragged_corpus_identical_results_at_the_csr_posi
         assert launches == -(-longest // (cap or 192)) and frames == sum(f.shape[0] for f in first)
 
 
+def test_a_window_cut_by_the_window_buffer_not_by_the_cap(lib, make_engine):
+    """1 366 live recordings of up to 100 chunks (tests/test_gpu_scan_rate_edges.py's batch, 8 kHz, hop 4): the 256 MiB window buffer
+    holds 131 072 // 1 366 = 95 chunks of each, so the scan is two windows - t0 = 0 with W = 95, and t0 = 95 over the recordings that
+    go on - where the cap of 192 and the longest recording would give one.  The stand-in's model reads frame t of item i at row
+    i * W + t - t0 of the window through the window's item table, so a wrong W, live count or t0 in either launch moves a
+    probability; no stream steps past its last chunk.  Windows of 32 chunks (the cap binds): four launches, the same results."""
+    from tests.test_gpu_scan_rate_edges import WIN_ROWS, buffer_window_counts, launches
+    eng = make_engine(max_streams=2048)
+    sr, chunk, hop = 8000, 256, 4
+    counts = [int(c) for c in buffer_window_counts()]
+    live, longest = sum(c > 0 for c in counts), max(counts)
+    fit = WIN_ROWS // live
+    assert live == 1366 and fit == 95 < longest == 100 and {0, 1, 95, 96} <= set(counts)
+    recs, first = _ragged(chunk, hop, "f32", seed=19, counts=counts)
+    perm = np.random.default_rng(20).permutation(len(recs))
+    for cap, want in ((0, -(-longest // fit)), (32, -(-longest // 32))):
+        assert want == launches(counts, cap) == (4 if cap else 2)
+        probs, got, frames, seen = _scan(eng, [recs[i] for i in perm], hop, "f32", sr, cap)
+        for k, i in enumerate(perm):
+            assert np.array_equal(probs[k], np.abs(first[i])), (cap, i)
+        assert seen == [counts[i] for i in perm]
+        assert got == want and frames == sum(counts)
+
+
 @pytest.mark.parametrize("channel", ["mix", 0, 1, "split"])
 def test_two_channel_recordings_are_selected_before_the_chunk_is_resampled(lib, make_engine, channel):
     eng = make_engine()
