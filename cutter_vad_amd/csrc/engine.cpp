@@ -159,7 +159,7 @@ struct vad_engine {
     // (d_audio is written by the scans' uploads and cut_run alone) - and the cut's tables as they were uploaded, segments then
     // workgroups.  audio_rate: 0 = a block at the engine's own rate (vad_scan_cut's), else the input rate of a RATE block
     // (vad_scan_rate_segments, vad_scan_rate_cut with an audio), which vad_scan_rate_cut alone accepts: whatever uploads into
-    // d_audio says which of the two it left.  cut_rows / cut_tiles: vad_scan_rate_cut's tables for vadk_cut_resample.
+    // d_audio says which of the two it left (set_resident).  cut_rows / cut_tiles: vad_scan_rate_cut's tables for vadk_cut_resample.
     bool audio_resident = false;
     size_t audio_bytes = 0; int32_t audio_channels = 0; int audio_fmt = 0; int32_t audio_rate = 0;
     std::vector<vadk::CutResampleSeg> cut_rows;
@@ -598,6 +598,19 @@ int check_slots(vad_engine *e, const int64_t *slots, int64_t n) {
     return VAD_OK;
 }
 
+// `p` as the 16-stream kernels read it: their weight streams and section table in place of the 32-stream kernels'
+vadk::StepParams params16(const vad_engine *e, const vadk::StepParams &p) {
+    vadk::StepParams p16 = p;
+    p16.wstream = e->d_wstream16;
+    p16.wstream_bytes = (uint32_t)e->wbytes16;
+    p16.wstream_x = e->d_wstream16x;
+    p16.wstream_x_bytes = (uint32_t)e->wbytes16x;
+    p16.wstream_y = e->d_wstream16y;
+    p16.wstream_y_bytes = (uint32_t)e->wbytes16y;
+    std::memcpy(p16.sect, e->sect16, sizeof p16.sect);
+    return p16;
+}
+
 int launch(vad_engine *e, const vadk::StepParams &p_in, hipStream_t s) {
     hipError_t r = hipErrorInvalidValue;
     vadk::StepParams p = p_in;
@@ -616,25 +629,11 @@ int launch(vad_engine *e, const vadk::StepParams &p_in, hipStream_t s) {
     if (e->version == 4 && e->d_wstream16 && e->tile_policy != 32) {
         // Silero V4: 16-stream tiles, two workgroups per CU (each fills the other's waits) - one per CU while the call has no
         // more tiles than the GPU has CUs, so that a small batch spreads out instead of pairing up
-        vadk::StepParams p16 = p;
-        p16.wstream = e->d_wstream16;
-        p16.wstream_bytes = (uint32_t)e->wbytes16;
-        p16.wstream_x = e->d_wstream16x;
-        p16.wstream_x_bytes = (uint32_t)e->wbytes16x;
-        p16.wstream_y = e->d_wstream16y;
-        p16.wstream_y_bytes = (uint32_t)e->wbytes16y;
-        std::memcpy(p16.sect, e->sect16, sizeof p16.sect);
+        const vadk::StepParams p16 = params16(e, p);
         const int tiles16 = (p.n + 15) / 16;
         r = vadk_launch_silero_v4_t16(&p16, (!e->shared_gpu && tiles16 <= e->prop.multiProcessorCount) ? 1 : 0, s);
     } else if (e->version == 5 && t16) {
-        vadk::StepParams p16 = p;
-        p16.wstream = e->d_wstream16;
-        p16.wstream_bytes = (uint32_t)e->wbytes16;
-        p16.wstream_x = e->d_wstream16x;
-        p16.wstream_x_bytes = (uint32_t)e->wbytes16x;
-        p16.wstream_y = e->d_wstream16y;
-        p16.wstream_y_bytes = (uint32_t)e->wbytes16y;
-        std::memcpy(p16.sect, e->sect16, sizeof p16.sect);
+        const vadk::StepParams p16 = params16(e, p);
         // One frame per stream of the 16 kHz model, float32 or int16, and more tiles than CUs - so that a CU gets two anyway: the two
         // as ONE workgroup that shares every bf16 weight fragment between them (silero_v5_pair16).  Up to one tile per CU the tiles
         // spread out, as before.
@@ -1175,19 +1174,107 @@ int vad_step_multi_device(vad_engine *e, const int32_t *d_slots, int64_t n, int3
     return launch(e, p, stream ? static_cast<hipStream_t>(stream) : e->stream);
 }
 
-// ---- whole recordings --------------------------------------------------------------------------------------------
 }  // extern "C"
 
+// ---- whole recordings (vad_scan, vad_scan_channels, vad_scan_rate) -------------------------------------------------
+// One host body and one device body serve every entry point.  The input rate is data: `chunk`, the sample frames of one frame in
+// the block (0 = the engine's own frames, a block at the engine's rate), and sr_in.  The entry points take e->mu, once, settle the
+// rate (scan_rate_check) and call the body.
 namespace {
 
 int64_t scan_frames(int64_t nsamples, int64_t frame, int64_t hop) { return nsamples < frame ? 0 : (nsamples - frame) / hop + 1; }
 
-// the item table of an earlier vad_scan_device may still be read by its launches: they finish before the table is rebuilt
+// chunk length that yields 512 samples at 16 kHz (AudioUtils.resample_audio: int(len * 16000 / sr), audio.py:46)
+int resample_chunk_len(int sr_in) {
+    switch (sr_in) {
+        case 8000: return 256;
+        case 24000: return 768;
+        case 48000: return 1536;
+        default: return 0;
+    }
+}
+
+// the operator that resamples chunks of n_in samples, packed and uploaded when it is first asked for: the rate scans', the rate
+// cuts' and the resampler's (t16: in the layout of the 16-stream rates kernel)
+int get_resample_op(vad_engine *e, int n_in, vad_engine::ResampleOp **out, bool t16 = false) {
+    auto &ops = t16 ? e->resample_ops16 : e->resample_ops;
+    for (auto &op : ops)
+        if (op.n_in == n_in) {
+            *out = &op;
+            return VAD_OK;
+        }
+    std::vector<float> packed;
+    std::string perr;
+    vad_engine::ResampleOp op;
+    op.n_in = n_in;
+    op.tile_blocks = t16 ? vadk::pack_resample_operator_t16(n_in, packed, &op.row128_block, perr)
+                         : vadk::pack_resample_operator(n_in, packed, &op.row128_block, perr);
+    if (op.tile_blocks == 0) return e->fail(VAD_ERR_INVALID_ARG, "Failed to resample audio: %s", perr.c_str());
+    op.bytes = packed.size() * sizeof(float);
+    hipError_t r = hipMalloc((void **)&op.d_w, op.bytes);
+    if (r != hipSuccess) return e->hip_fail(r, "hipMalloc(resample operator)");
+    r = hipMemcpy(op.d_w, packed.data(), op.bytes, hipMemcpyHostToDevice);
+    if (r != hipSuccess) {
+        (void)hipFree(op.d_w);
+        return e->hip_fail(r, "hipMemcpy(resample operator)");
+    }
+    ops.push_back(op);
+    *out = &ops.back();
+    return VAD_OK;
+}
+
+// the tables of an earlier device call (vad_scan_device, vad_scan_cut_device, vad_segments_device) may still be read by its
+// launches: they finish before a table is rebuilt
 int scan_wait(vad_engine *e) {
     if (e->scan_pending) {
         HIP_TRY(e, hipEventSynchronize(e->scan_done));
         e->scan_pending = false;
     }
+    return VAD_OK;
+}
+
+// ... and the device call's side of it: an event behind its last launch on `s` (an event, not the caller's stream: the caller may
+// destroy that once its work is done)
+int scan_mark_pending(vad_engine *e, hipStream_t s) {
+    if (!e->scan_done) HIP_TRY(e, hipEventCreateWithFlags(&e->scan_done, hipEventDisableTiming));
+    HIP_TRY(e, hipEventRecord(e->scan_done, s));
+    e->scan_pending = true;
+    return VAD_OK;
+}
+
+// the block in e->d_audio stays for a following cut with audio = NULL.  rate: 0 = a block at the engine's own rate (vad_scan_cut's),
+// else a RATE block of that input rate (vad_scan_rate_cut's: its positions and hop count samples at that rate)
+void set_resident(vad_engine *e, size_t bytes, int32_t channels, int fmt, int32_t rate) {
+    e->audio_resident = true;
+    e->audio_bytes = bytes; e->audio_channels = channels; e->audio_fmt = fmt; e->audio_rate = rate;
+}
+
+// What a scan and a cut check about their block, in one wording.  Two functions, not one: each caller has checks of its own between
+// them (scan_plan: max_streams; cut_check: layout and out_fmt), and which refusal a call with several faults gets is behaviour.
+int check_block_format(vad_engine *e, const char *who, int fmt, int32_t channels) {
+    if (fmt < VAD_FMT_F32 || fmt > VAD_FMT_ALAW8)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: unknown frame format %d", fmt);
+    if (channels != 1 && channels != 2)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: channels = %d, the block holds 1 or 2 interleaved channels", who, channels);
+    return VAD_OK;
+}
+
+int check_block_extent(vad_engine *e, const char *who, int32_t hop, int64_t audio_samples, int32_t channels, int fmt) {
+    if (hop < 4 || (hop & 3))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: hop = %d must be a positive multiple of 4 samples", who, hop);
+    // the kernel addresses the block through a 32-bit buffer descriptor
+    const uint64_t fbytes = (uint64_t)channels * sample_bytes(fmt);
+    if ((uint64_t)audio_samples >= (1ull << 31) || (uint64_t)audio_samples * fbytes >= (1ull << 31))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %llu bytes of audio exceed the 2 GiB one call may address", who,
+                       (unsigned long long)((uint64_t)audio_samples * fbytes));
+    return VAD_OK;
+}
+
+// a block in device memory is read in quads of sample frames: 4 bytes of G.711, 8 of a two-channel block
+int check_device_audio(vad_engine *e, const char *who, const void *d_audio, int32_t channels) {
+    const uintptr_t align = channels == 2 ? 8 : 4;
+    if (reinterpret_cast<uintptr_t>(d_audio) & (align - 1))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the audio block must be %d-byte aligned", who, (int)align);
     return VAD_OK;
 }
 
@@ -1215,19 +1302,10 @@ int scan_plan(vad_engine *e, const char *who, const Item *items, int64_t n, int6
     if (!e->d_wstream16) return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s: the engine has no 16-stream kernel; use vad_step_multi", who);
     if (n < 0 || audio_samples < 0 || (n > 0 && (!items || (!out_start && !own_start))))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer or bad count", who);
-    if (fmt < VAD_FMT_F32 || fmt > VAD_FMT_ALAW8)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: unknown frame format %d", fmt);
-    if (channels != 1 && channels != 2)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: channels = %d, the block holds 1 or 2 interleaved channels", who, channels);
+    if (int rc = check_block_format(e, who, fmt, channels)) return rc;
     if (n > e->max_streams)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %lld recordings, max_streams = %d", who, (long long)n, e->max_streams);
-    if (hop < 4 || (hop & 3))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: hop = %d must be a positive multiple of 4 samples", who, hop);
-    // the kernel addresses the block through a 32-bit buffer descriptor
-    const uint64_t frame_bytes = (uint64_t)channels * sample_bytes(fmt);
-    if ((uint64_t)audio_samples >= (1ull << 31) || (uint64_t)audio_samples * frame_bytes >= (1ull << 31))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %llu bytes of audio exceed the 2 GiB one call may address", who,
-                       (unsigned long long)((uint64_t)audio_samples * frame_bytes));
+    if (int rc = check_block_extent(e, who, hop, audio_samples, channels, fmt)) return rc;
     e->scan_items.resize((size_t)n);
     if (own_start) own_start->assign((size_t)n + 1, 0);
     std::vector<int64_t> slots((size_t)n);
@@ -1268,22 +1346,15 @@ int scan_plan(vad_engine *e, const char *who, const Item *items, int64_t n, int6
     return VAD_OK;
 }
 
-// the launches of a planned scan (e->d_items holds e->scan_items): windows of at most scan_launch_frames frames, each over the
-// items that still have frames in it - a prefix of the sorted table.  State travels through HBM between them, as between two
-// vad_step_multi calls.
+// the launches of a planned scan at the engine's rate (e->d_items holds e->scan_items): windows of at most scan_launch_frames
+// frames, each over the items that still have frames in it - a prefix of the sorted table.  State travels through HBM between
+// them, as between two vad_step_multi calls.
 int scan_launches(vad_engine *e, const void *d_audio, int64_t audio_samples, int32_t channels, int fmt, int32_t hop, float thr, float *d_probs,
                   uint8_t *d_events, int32_t *d_seg, int64_t total, hipStream_t s) {
     const std::vector<vadk::ScanItem> &it = e->scan_items;
     const int maxf = it.empty() ? 0 : it.front().nframes;
     const int cap = e->scan_launch_frames > 0 ? e->scan_launch_frames : vad_engine::SCAN_LAUNCH_FRAMES;
-    vadk::StepParams p = e->base;
-    p.wstream = e->d_wstream16;
-    p.wstream_bytes = (uint32_t)e->wbytes16;
-    p.wstream_x = e->d_wstream16x;
-    p.wstream_x_bytes = (uint32_t)e->wbytes16x;
-    p.wstream_y = e->d_wstream16y;
-    p.wstream_y_bytes = (uint32_t)e->wbytes16y;
-    std::memcpy(p.sect, e->sect16, sizeof p.sect);
+    vadk::StepParams p = params16(e, e->base);
     p.slots = nullptr;
     p.frames = d_audio;
     p.probs = d_probs;
@@ -1309,6 +1380,155 @@ int scan_launches(vad_engine *e, const void *d_audio, int64_t audio_samples, int
     return VAD_OK;
 }
 
+// what comes before the plan's checks in a call that names its input rate: the engine's model rate and the input rate.  *chunk =
+// sample frames of one chunk at sr_in, or 0: the recordings are at 16 kHz already and the call is vad_scan_channels under another
+// name (AudioUtils.resample_audio returns its input).
+int scan_rate_check(vad_engine *e, const char *who, int32_t sr_in, int *chunk) {
+    if (e->version == 5 && e->frame_samples != VAD_FRAME_SAMPLES)
+        return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s: this engine runs an 8 kHz sub-model on %d-sample frames; "
+                       "resampled recordings need the 16 kHz one", who, e->frame_samples);
+    *chunk = sr_in == 16000 ? 0 : resample_chunk_len(sr_in);
+    if (sr_in != 16000 && *chunk == 0)
+        return e->fail(VAD_ERR_UNSUPPORTED, "Failed to resample audio from %dHz to 16000Hz: %s: supported input rates are 8000, 16000, 24000, 48000", sr_in, who);
+    return VAD_OK;
+}
+
+// the launches of a planned rate scan (e->d_items holds e->scan_items, planned on chunks of `chunk` sample frames): per window of W
+// chunks one vadk_scan_resample - the window's chunks of the live items -> 512-sample frames in d_win, and the window's item table
+// - and behind it, on the same stream, the scan kernel over d_win as a mono float32 block whose frames lie back to back.  State
+// travels through HBM between the windows, as in scan_launches; the gate and the non-finite check act on the resampled frame.
+int scan_rate_launches(vad_engine *e, const void *d_audio, int64_t audio_samples, int32_t channels, int fmt, int chunk, int32_t hop, float thr,
+                       float *d_probs, uint8_t *d_events, int32_t *d_seg, int64_t total, hipStream_t s) {
+    const std::vector<vadk::ScanItem> &it = e->scan_items;
+    const int maxf = it.empty() ? 0 : it.front().nframes;
+    size_t live = it.size();
+    while (live > 0 && it[live - 1].nframes <= 0) --live;
+    if (live == 0) return VAD_OK;
+    const int cap = e->scan_launch_frames > 0 ? e->scan_launch_frames : vad_engine::SCAN_LAUNCH_FRAMES;
+    const size_t fit = vad_engine::SCAN_RATE_WIN_BYTES / (live * 2048u);
+    const int W = std::max(1, (int)std::min<size_t>((size_t)std::min(cap, maxf), fit));
+    const size_t win_bytes = live * (size_t)W * 2048u;
+    if (win_bytes >= (size_t(1) << 31))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %zu recordings with chunks in one call: one frame of each exceeds the 2 GiB a launch may address", live);
+    vad_engine::ResampleOp *op = nullptr;
+    if (int rc = get_resample_op(e, chunk, &op)) return rc;
+    if (int rc = ensure(e, e->d_win, e->d_win_cap, win_bytes)) return rc;
+    if (int rc = ensure(e, e->d_items_win, e->d_items_win_cap, sizeof(vadk::ScanItem) * live)) return rc;
+    vadk::ScanResampleArgs r{};
+    r.wstream = op->d_w;
+    r.wstream_bytes = (uint32_t)op->bytes;
+    r.tile_blocks = op->tile_blocks;
+    r.row128_block = op->row128_block;
+    r.audio_bytes = (uint32_t)((uint64_t)audio_samples * (uint64_t)channels * sample_bytes(fmt));
+    r.audio = d_audio;
+    r.items = e->d_items;
+    r.items_win = e->d_items_win;
+    r.win = e->d_win;
+    r.W = W;
+    r.n_in = chunk;
+    r.hopq = (uint32_t)hop >> 2;
+    r.fmt = fmt;
+    r.channels = channels;
+    vadk::StepParams p = params16(e, e->base);
+    p.slots = nullptr;
+    p.frames = e->d_win;
+    p.probs = d_probs;
+    p.events = d_events;
+    p.seg_frames = d_seg;
+    p.fmt = VAD_FMT_F32;
+    p.thresh = thr;
+    vadk::ScanArgs a{};
+    a.hopq = VAD_FRAME_SAMPLES / 4;
+    a.t0 = 0;
+    a.channels = 1;
+    for (int t0 = 0; t0 < maxf; t0 += W) {
+        while (live > 0 && it[live - 1].nframes <= t0) --live;
+        r.live = (int32_t)live;
+        r.t0 = t0;
+        hipError_t rr = vadk_launch_scan_resample(&r, s);
+        if (rr != hipSuccess) return e->hip_fail(rr, "kernel launch (scan resample)");
+        p.n = (int32_t)live;
+        p.T = std::min(W, maxf - t0);
+        a.audio_bytes = (uint32_t)(live * (size_t)W * 2048u);
+        rr = vadk_launch_silero_v5_scan16(&p, e->d_items_win, &a, s);
+        if (rr != hipSuccess) return e->hip_fail(rr, "kernel launch (scan)");
+        e->steps += 1;
+    }
+    e->frames += total;
+    return VAD_OK;
+}
+
+// the launches of a planned scan on `s`, by the rate of its block: two loops that share nothing but params16
+int scan_enqueue(vad_engine *e, const void *d_audio, int64_t audio_samples, int32_t channels, int fmt, int chunk, int32_t hop, float thr,
+                 float *d_probs, uint8_t *d_events, int32_t *d_seg, int64_t total, hipStream_t s) {
+    if (chunk > 0) return scan_rate_launches(e, d_audio, audio_samples, channels, fmt, chunk, hop, thr, d_probs, d_events, d_seg, total, s);
+    return scan_launches(e, d_audio, audio_samples, channels, fmt, hop, thr, d_probs, d_events, d_seg, total, s);
+}
+
+// a planned scan of host audio (scan_host, scan_segments_run): the block crosses the link once, in its wire format, interleaved as
+// it is; the launches write the engine's own d_probs / d_events / d_seg.  resident: the block stays for a cut with audio = NULL,
+// as a block at the engine's rate (chunk == 0) or as a rate block of sr_in - whatever becomes of the launches
+int scan_upload_launch(vad_engine *e, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt, int chunk,
+                       int32_t sr_in, int32_t hop, float denoise_thresh, int64_t total, bool resident) {
+    const size_t ab = (size_t)audio_samples * (size_t)channels * sample_bytes(frame_fmt);
+    e->audio_resident = false;
+    if (int rc = ensure(e, e->d_audio, e->d_audio_cap, ab + 16)) return rc;
+    if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
+    if (int rc = ensure(e, e->d_probs, e->d_probs_cap, sizeof(float) * (size_t)total)) return rc;
+    if (int rc = ensure(e, e->d_events, e->d_events_cap, (size_t)total)) return rc;
+    if (int rc = ensure(e, e->d_seg, e->d_seg_cap, sizeof(int32_t) * (size_t)total)) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, ab, hipMemcpyHostToDevice, e->stream));
+    if (resident) set_resident(e, ab, channels, frame_fmt, chunk > 0 ? sr_in : 0);
+    return scan_enqueue(e, e->d_audio, audio_samples, channels, frame_fmt, chunk, hop, denoise_thresh, e->d_probs, e->d_events, e->d_seg, total,
+                        e->stream);
+}
+
+// vad_scan, vad_scan_channels and vad_scan_rate, with e->mu held.  A block at the engine's rate becomes the resident one;
+// vad_scan_rate at another rate leaves nothing to cut, and no block stays
+template <class Item>
+int scan_host(vad_engine *e, const char *who, const Item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
+              int frame_fmt, int chunk, int32_t sr_in, int32_t hop, float denoise_thresh, const int64_t *out_start, float *probs_out,
+              uint8_t *events_out, int32_t *seg_frames_out) {
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    int64_t total = 0;
+    const int64_t base = (n > 0 && out_start) ? out_start[0] : 0;
+    if (base < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start[0] is negative", who);
+    if (int rc = scan_plan(e, who, items, n, audio_samples, channels, frame_fmt, hop, out_start, base, &total, nullptr, chunk)) return rc;
+    if (total == 0) return VAD_OK;
+    if (!audio || !probs_out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if (int rc = scan_upload_launch(e, n, audio, audio_samples, channels, frame_fmt, chunk, sr_in, hop, denoise_thresh, total, chunk == 0)) return rc;
+    HIP_TRY(e, hipMemcpyAsync(probs_out + base, e->d_probs, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost, e->stream));
+    if (events_out) HIP_TRY(e, hipMemcpyAsync(events_out + base, e->d_events, (size_t)total, hipMemcpyDeviceToHost, e->stream));
+    if (seg_frames_out) HIP_TRY(e, hipMemcpyAsync(seg_frames_out + base, e->d_seg, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return VAD_OK;
+}
+
+// vad_scan_device, vad_scan_channels_device and vad_scan_rate_device, with e->mu held.  The plan's refusals carry `plan_who` - for
+// the first two the host entry point's name, as they did before there were two.  Returns after enqueueing: the next call that
+// rebuilds the tables waits (scan_mark_pending)
+template <class Item>
+int scan_dev(vad_engine *e, const char *who, const char *plan_who, const Item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
+             int frame_fmt, int chunk, int32_t hop, float denoise_thresh, const int64_t *out_start, float *d_probs, uint8_t *d_events,
+             int32_t *d_seg_frames, void *stream) {
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    int64_t total = 0;
+    if (int rc = scan_plan(e, plan_who, items, n, audio_samples, channels, frame_fmt, hop, out_start, 0, &total, nullptr, chunk)) return rc;
+    if (total == 0) return VAD_OK;
+    if (!d_audio || !d_probs) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if (int rc = check_device_audio(e, who, d_audio, channels)) return rc;
+    if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, s));
+    const int rc = scan_enqueue(e, d_audio, audio_samples, channels, frame_fmt, chunk, hop, denoise_thresh, d_probs, d_events, d_seg_frames, total, s);
+    // (also behind a failed launch: the copy of the table and the launches before it are on the stream)
+    if (int rc2 = scan_mark_pending(e, s)) return rc2;
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1316,6 +1536,13 @@ extern "C" {
 int64_t vad_scan_frame_count(const vad_engine *e, int64_t nsamples, int32_t hop) {
     if (!e || hop < 1 || nsamples < 0) return -1;
     return scan_frames(nsamples, e->frame_samples, hop);
+}
+
+int64_t vad_scan_rate_frame_count(const vad_engine *e, int64_t nsamples, int32_t sr_in, int32_t hop) {
+    if (!e || hop < 1 || nsamples < 0) return -1;
+    const int chunk = sr_in == 16000 ? e->frame_samples : resample_chunk_len(sr_in);
+    if (chunk == 0) return -1;
+    return scan_frames(nsamples, chunk, hop);
 }
 
 int vad_debug_scan_launch_frames(vad_engine *e, int32_t frames) {
@@ -1326,115 +1553,71 @@ int vad_debug_scan_launch_frames(vad_engine *e, int32_t frames) {
     return VAD_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
-// a planned scan of host audio (vad_scan, vad_scan_channels, vad_scan_segments): the block crosses the link once, in its wire format,
-// interleaved as it is, and becomes the resident one; the launches write the engine's own d_probs / d_events / d_seg
-int scan_upload_launch(vad_engine *e, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t hop,
-                       float denoise_thresh, int64_t total) {
-    const size_t ab = (size_t)audio_samples * (size_t)channels * sample_bytes(frame_fmt);
-    e->audio_resident = false;
-    if (int rc = ensure(e, e->d_audio, e->d_audio_cap, ab + 16)) return rc;
-    if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
-    if (int rc = ensure(e, e->d_probs, e->d_probs_cap, sizeof(float) * (size_t)total)) return rc;
-    if (int rc = ensure(e, e->d_events, e->d_events_cap, (size_t)total)) return rc;
-    if (int rc = ensure(e, e->d_seg, e->d_seg_cap, sizeof(int32_t) * (size_t)total)) return rc;
-    // the audio crosses the link once, in its wire format
-    HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, ab, hipMemcpyHostToDevice, e->stream));
-    e->audio_resident = true;                // for a following vad_scan_cut(audio = NULL), whatever becomes of the launches
-    e->audio_bytes = ab; e->audio_channels = channels; e->audio_fmt = frame_fmt; e->audio_rate = 0;
-    return scan_launches(e, e->d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, e->d_probs, e->d_events, e->d_seg, total, e->stream);
-}
-
-// vad_scan and vad_scan_channels
-template <class Item>
-int scan_host(vad_engine *e, const char *who, const Item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
-              int frame_fmt, int32_t hop, float denoise_thresh, const int64_t *out_start, float *probs_out, uint8_t *events_out,
-              int32_t *seg_frames_out) {
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
-    int64_t total = 0;
-    const int64_t base = (n > 0 && out_start) ? out_start[0] : 0;
-    if (base < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start[0] is negative", who);
-    if (int rc = scan_plan(e, who, items, n, audio_samples, channels, frame_fmt, hop, out_start, base, &total)) return rc;
-    if (total == 0) return VAD_OK;
-    if (!audio || !probs_out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    if (int rc = scan_upload_launch(e, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, total)) return rc;
-    HIP_TRY(e, hipMemcpyAsync(probs_out + base, e->d_probs, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost, e->stream));
-    if (events_out) HIP_TRY(e, hipMemcpyAsync(events_out + base, e->d_events, (size_t)total, hipMemcpyDeviceToHost, e->stream));
-    if (seg_frames_out) HIP_TRY(e, hipMemcpyAsync(seg_frames_out + base, e->d_seg, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    return VAD_OK;
-}
-
-// vad_scan_device and vad_scan_channels_device (the plan's refusals carry the host entry point's name, `plan_who`, as they did
-// before there were two); a two-channel block is read in quads of sample frames, 8 bytes of G.711
-template <class Item>
-int scan_dev(vad_engine *e, const char *who, const char *plan_who, const Item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
-             int frame_fmt, int32_t hop, float denoise_thresh, const int64_t *out_start, float *d_probs, uint8_t *d_events,
-             int32_t *d_seg_frames, void *stream) {
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
-    int64_t total = 0;
-    if (int rc = scan_plan(e, plan_who, items, n, audio_samples, channels, frame_fmt, hop, out_start, 0, &total)) return rc;
-    if (total == 0) return VAD_OK;
-    if (!d_audio || !d_probs) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    const uintptr_t align = channels == 2 ? 8 : 4;
-    if (reinterpret_cast<uintptr_t>(d_audio) & (align - 1))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the audio block must be %d-byte aligned", who, (int)align);
-    if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
-    HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, s));
-    if (!e->scan_done) HIP_TRY(e, hipEventCreateWithFlags(&e->scan_done, hipEventDisableTiming));
-    const int rc = scan_launches(e, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, d_probs, d_events, d_seg_frames, total, s);
-    // (also behind a failed launch: the copy of the table and the launches before it are on the stream)
-    HIP_TRY(e, hipEventRecord(e->scan_done, s));
-    e->scan_pending = true;
-    return rc;
-}
-
-}  // namespace
-
-extern "C" {
-
 int vad_scan(vad_engine *e, const vad_scan_item *items, int64_t n, const void *audio, int64_t audio_samples, int frame_fmt,
              int32_t hop, float denoise_thresh, const int64_t *out_start, float *probs_out, uint8_t *events_out,
              int32_t *seg_frames_out) {
-    return scan_host(e, "vad_scan", items, n, audio, audio_samples, 1, frame_fmt, hop, denoise_thresh, out_start, probs_out, events_out,
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return scan_host(e, "vad_scan", items, n, audio, audio_samples, 1, frame_fmt, 0, 0, hop, denoise_thresh, out_start, probs_out, events_out,
                      seg_frames_out);
 }
 
 int vad_scan_device(vad_engine *e, const vad_scan_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int frame_fmt,
                     int32_t hop, float denoise_thresh, const int64_t *out_start, float *d_probs, uint8_t *d_events,
                     int32_t *d_seg_frames, void *stream) {
-    return scan_dev(e, "vad_scan_device", "vad_scan", items, n, d_audio, audio_samples, 1, frame_fmt, hop, denoise_thresh, out_start, d_probs, d_events,
-                    d_seg_frames, stream);
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return scan_dev(e, "vad_scan_device", "vad_scan", items, n, d_audio, audio_samples, 1, frame_fmt, 0, hop, denoise_thresh, out_start, d_probs,
+                    d_events, d_seg_frames, stream);
 }
 
 int vad_scan_channels(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
                       int frame_fmt, int32_t hop, float denoise_thresh, const int64_t *out_start, float *probs_out, uint8_t *events_out,
                       int32_t *seg_frames_out) {
-    return scan_host(e, "vad_scan_channels", items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, out_start, probs_out,
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return scan_host(e, "vad_scan_channels", items, n, audio, audio_samples, channels, frame_fmt, 0, 0, hop, denoise_thresh, out_start, probs_out,
                      events_out, seg_frames_out);
 }
 
 int vad_scan_channels_device(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *d_audio, int64_t audio_samples,
                              int32_t channels, int frame_fmt, int32_t hop, float denoise_thresh, const int64_t *out_start, float *d_probs,
                              uint8_t *d_events, int32_t *d_seg_frames, void *stream) {
-    return scan_dev(e, "vad_scan_channels_device", "vad_scan_channels", items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, out_start,
-                    d_probs, d_events, d_seg_frames, stream);
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return scan_dev(e, "vad_scan_channels_device", "vad_scan_channels", items, n, d_audio, audio_samples, channels, frame_fmt, 0, hop, denoise_thresh,
+                    out_start, d_probs, d_events, d_seg_frames, stream);
 }
 
-// ---- finished segments cut out of a scanned block (vad_scan_cut) --------------------------------------------------
+// recordings at 8 / 24 / 48 kHz: framed at the input rate, resampled chunk by chunk, then scanned (sr_in = 16000: vad_scan_channels
+// and vad_scan_channels_device under these names)
+int vad_scan_rate(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
+                  int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, const int64_t *out_start, float *probs_out,
+                  uint8_t *events_out, int32_t *seg_frames_out) {
+    static const char *who = "vad_scan_rate";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int chunk = 0;
+    if (int rc = scan_rate_check(e, who, sr_in, &chunk)) return rc;
+    return scan_host(e, who, items, n, audio, audio_samples, channels, frame_fmt, chunk, sr_in, hop, denoise_thresh, out_start, probs_out, events_out,
+                     seg_frames_out);
+}
+
+int vad_scan_rate_device(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
+                         int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, const int64_t *out_start, float *d_probs,
+                         uint8_t *d_events, int32_t *d_seg_frames, void *stream) {
+    static const char *who = "vad_scan_rate_device";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int chunk = 0;
+    if (int rc = scan_rate_check(e, who, sr_in, &chunk)) return rc;
+    return scan_dev(e, who, who, items, n, d_audio, audio_samples, channels, frame_fmt, chunk, hop, denoise_thresh, out_start, d_probs, d_events,
+                    d_seg_frames, stream);
+}
+
 }  // extern "C"
 
+// ---- finished segments cut out of a scanned block (vad_scan_cut, vad_scan_rate_cut) --------------------------------------
 namespace {
 
 static_assert(VAD_CUT_WG_SAMPLES == 4 * vadk::CUT_WG_QUADS, "the header's workgroup share is the kernel's");
@@ -1444,12 +1627,6 @@ int64_t cut_samples(int64_t frame, int64_t nframes, int64_t hop, int32_t layout,
     return layout == VAD_CUT_FRAMES ? nframes * out_frame : (nframes - 1) * hop + frame;
 }
 
-// (defined with the resampler, further down, inside that section's extern "C" block)
-extern "C" {
-int resample_chunk_len(int sr_in);
-int get_resample_op(vad_engine *e, int n_in, vad_engine::ResampleOp **out, bool t16 = false);
-}
-
 // rows of one window of vad_scan_rate_cut's frames: what the engine's window buffer holds, in whole tiles; the launch-frames knob
 // of the scans (vad_debug_scan_launch_frames) cuts it to that many tiles, so that a test reaches the window loop with a small call
 uint32_t cut_window_rows(const vad_engine *e) {
@@ -1457,56 +1634,73 @@ uint32_t cut_window_rows(const vad_engine *e) {
     return (uint32_t)(e->scan_launch_frames > 0 ? std::min<size_t>(full, (size_t)e->scan_launch_frames * vadk::MT) : full);
 }
 
-// vad_scan_cut (DEV = false: host audio, or NULL = the resident block, and a host `out`) and vad_scan_cut_device.  Every check
-// comes before the first write; the tables (e->cut_segs, e->cut_work: one entry per workgroup) are built on the way.
-// chunk > 0 (vad_scan_rate_cut / _device): the block is at sr_in, a frame in it is a chunk of `chunk` sample frames, and the
-// resident block must be a rate block of that rate.  VAD_CUT_RANGE is then the same kernel on the input-rate block with the gate
-// off (no input-rate sample was ever gated); VAD_CUT_FRAMES resamples the listed chunks window by window into e->d_win
-// (vadk_cut_resample) and cuts each window as a mono float32 block of back-to-back frames with the same kernel, which gates.
-template <bool DEV>
-int cut_run(vad_engine *e, const char *who, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
-            int fmt, int32_t hop, float thr, int32_t layout, int32_t out_fmt, void *out, int64_t out_samples, void *stream, int chunk = 0,
-            int32_t sr_in = 0) {
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    hipStream_t s = (DEV && stream) ? static_cast<hipStream_t>(stream) : e->stream;
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
-    if (n < 0 || audio_samples < 0 || out_samples < 0 || (n > 0 && !items))
+// what comes before cut_run's checks in a rate cut: the engine's frames and the input rate.  No model runs, so Silero V4 and
+// VAD_ENGINE_SHARED_GPU engines pass (every engine can hold a resample operator: get_resample_op); an engine whose frames are not
+// the 512 samples the operator writes - an 8 kHz sub-model - does not.  *chunk = 0: 16 kHz, the call is vad_scan_cut.
+int rate_cut_check(vad_engine *e, const char *who, int32_t sr_in, int *chunk) {
+    if (e->frame_samples != VAD_FRAME_SAMPLES || e->sample_rate != 16000)
+        return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s: this engine runs an 8 kHz sub-model on %d-sample frames; "
+                       "resampled recordings need the 16 kHz one", who, e->frame_samples);
+    return scan_rate_check(e, who, sr_in, chunk);
+}
+
+struct CutSpan { int64_t lo, hi, i; };                           // the output samples [lo, hi) of segment i
+struct CutWin { uint32_t r0, r1; size_t seg0, work0, nwork; };   // rows [r0, r1) of a rate cut's frames: their part of the tables
+
+// What cut_run carries from one phase to the next; each phase is a function below, in the order it runs.  The tables themselves
+// are the engine's (e->cut_segs, e->cut_work: one entry per workgroup; e->cut_rows, e->cut_tiles: a rate cut's frames).
+// chunk > 0 (vad_scan_rate_cut / _device): the block is at sr_in and a frame in it is a chunk of `chunk` sample frames.
+// VAD_CUT_RANGE is then the same kernel on the input-rate block with the gate off (no input-rate sample was ever gated);
+// VAD_CUT_FRAMES (rate_frames) resamples the listed chunks window by window into e->d_win (vadk_cut_resample) and cuts each
+// window as a mono float32 block of back-to-back frames with the same kernel, which gates.
+struct CutPlan {
+    // the call
+    const char *who; const vad_cut_item *items; int64_t n, audio_samples; int32_t channels; int fmt; int32_t hop; float thr;
+    int32_t layout, out_fmt; int64_t out_samples; int chunk; int32_t sr_in;
+    // a. cut_check
+    bool rate, rate_frames;
+    uint32_t fshift;                         // log2 of the quads of a payload frame
+    int64_t rows;                            // rate_frames: the frames of all segments
+    size_t ab, ob;                           // bytes of the block, and of one output sample
+    std::vector<CutSpan> spans;              // by lo
+    // b. cut_block_device / cut_block_host: the block the kernels read, and where they write
+    const void *d_audio; void *d_out;
+    // c. cut_windows
+    vad_engine::ResampleOp *op; std::vector<CutWin> wins;
+    // d. cut_upload: bytes of the tables, which lie in e->d_cut in this order - segments, workgroups, rows, tiles
+    size_t sb, wb, rb, tb;
+};
+
+// a. every refusal that needs no device pointer, and the tables: e->cut_segs, e->cut_work (rate_frames: e->cut_rows - the work is
+// listed per window, by cut_windows) and the output spans.  Writes nothing to the device.  A call without segments (n == 0) is
+// done behind the checks of its own arguments
+int cut_check(vad_engine *e, CutPlan &c) {
+    const char *who = c.who;
+    const int64_t n = c.n, audio_samples = c.audio_samples, hop = c.hop;
+    if (n < 0 || audio_samples < 0 || c.out_samples < 0 || (n > 0 && !c.items))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer or bad count", who);
-    if (fmt < VAD_FMT_F32 || fmt > VAD_FMT_ALAW8)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: unknown frame format %d", fmt);
-    if (channels != 1 && channels != 2)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: channels = %d, the block holds 1 or 2 interleaved channels", who, channels);
-    if (layout != VAD_CUT_FRAMES && layout != VAD_CUT_RANGE)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: layout = %d is neither VAD_CUT_FRAMES nor VAD_CUT_RANGE", who, layout);
-    if (out_fmt != VAD_CUT_PCM16 && out_fmt != VAD_CUT_F32)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_fmt = %d is neither VAD_CUT_PCM16 nor VAD_CUT_F32", who, out_fmt);
-    if (hop < 4 || (hop & 3))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: hop = %d must be a positive multiple of 4 samples", who, hop);
-    // the kernel addresses the block through a 32-bit buffer descriptor
-    const uint64_t fbytes = (uint64_t)channels * sample_bytes(fmt);
-    if ((uint64_t)audio_samples >= (1ull << 31) || (uint64_t)audio_samples * fbytes >= (1ull << 31))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %llu bytes of audio exceed the 2 GiB one call may address", who,
-                       (unsigned long long)((uint64_t)audio_samples * fbytes));
+    if (int rc = check_block_format(e, who, c.fmt, c.channels)) return rc;
+    if (c.layout != VAD_CUT_FRAMES && c.layout != VAD_CUT_RANGE)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: layout = %d is neither VAD_CUT_FRAMES nor VAD_CUT_RANGE", who, c.layout);
+    if (c.out_fmt != VAD_CUT_PCM16 && c.out_fmt != VAD_CUT_F32)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_fmt = %d is neither VAD_CUT_PCM16 nor VAD_CUT_F32", who, c.out_fmt);
+    if (int rc = check_block_extent(e, who, c.hop, audio_samples, c.channels, c.fmt)) return rc;
     if (n == 0) return VAD_OK;
-    const bool rate = chunk > 0, rate_frames = rate && layout == VAD_CUT_FRAMES;
-    const int64_t frame = rate ? chunk : e->frame_samples, out_frame = rate ? VAD_FRAME_SAMPLES : frame;
+    c.rate = c.chunk > 0;
+    c.rate_frames = c.rate && c.layout == VAD_CUT_FRAMES;
+    const int64_t frame = c.rate ? c.chunk : e->frame_samples, out_frame = c.rate ? VAD_FRAME_SAMPLES : frame;
     const uint32_t frameq = (uint32_t)out_frame >> 2;
-    uint32_t fshift = 0;
-    while ((1u << fshift) < frameq) ++fshift;
+    while ((1u << c.fshift) < frameq) ++c.fshift;
     // the kernel finds a quad's frame with a shift and a mask: 512 and 256 samples today (the sample range once needs neither:
     // chunks of 768 and 1536 samples pass)
-    if (layout == VAD_CUT_FRAMES && ((out_frame & 3) || (1u << fshift) != frameq))
+    if (c.layout == VAD_CUT_FRAMES && ((out_frame & 3) || (1u << c.fshift) != frameq))
         return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s: frames of %lld samples: the cut kernel needs a power of two", who, (long long)out_frame);
-    struct Span { int64_t lo, hi; int64_t i; };
-    std::vector<Span> spans((size_t)n);
+    c.spans.resize((size_t)n);
     e->cut_segs.resize((size_t)n);
     e->cut_work.clear();
     e->cut_rows.clear();
-    int64_t rows = 0;                        // rate_frames: the frames of the segments listed so far
     for (int64_t i = 0; i < n; ++i) {
-        const vad_cut_item &it = items[i];
+        const vad_cut_item &it = c.items[i];
         if (it.sample_offset < 0 || (it.sample_offset & 3))
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: its recording starts at sample %lld, not a multiple of 4", who,
                            (long long)i, (long long)it.sample_offset);
@@ -1515,31 +1709,30 @@ int cut_run(vad_engine *e, const char *who, const vad_cut_item *items, int64_t n
                            (long long)i, (long long)it.first_frame, (long long)it.nframes);
         // (all of it below 2^31 before it is multiplied: a segment that fits the block has fewer frames than the block has samples)
         if (it.sample_offset > audio_samples || it.first_frame > audio_samples || it.nframes > audio_samples ||
-            it.sample_offset + (it.first_frame + it.nframes - 1) * (int64_t)hop + frame > audio_samples)
+            it.sample_offset + (it.first_frame + it.nframes - 1) * hop + frame > audio_samples)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld (recording at %lld, frames %lld .. +%lld) leaves the audio block of %lld samples",
                            who, (long long)i, (long long)it.sample_offset, (long long)it.first_frame, (long long)it.nframes, (long long)audio_samples);
-        if (it.channel != VAD_SCAN_MIX && (it.channel < 0 || it.channel >= channels))
+        if (it.channel != VAD_SCAN_MIX && (it.channel < 0 || it.channel >= c.channels))
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld names channel %d of %d (0 .. channels - 1, or VAD_SCAN_MIX)", who,
-                           (long long)i, it.channel, channels);
+                           (long long)i, it.channel, c.channels);
         if (it.reserved != 0)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: reserved = %d must be 0", who, (long long)i, it.reserved);
-        const int64_t count = cut_samples(frame, it.nframes, hop, layout, out_frame);
-        if (it.out_sample < 0 || (it.out_sample & 3) || it.out_sample > out_samples || count > out_samples - it.out_sample)
+        const int64_t count = cut_samples(frame, it.nframes, hop, c.layout, out_frame);
+        if (it.out_sample < 0 || (it.out_sample & 3) || it.out_sample > c.out_samples || count > c.out_samples - it.out_sample)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: out_sample = %lld (+%lld samples) must be a multiple of 4 inside "
-                           "the output of %lld samples", who, (long long)i, (long long)it.out_sample, (long long)count, (long long)out_samples);
+                           "the output of %lld samples", who, (long long)i, (long long)it.out_sample, (long long)count, (long long)c.out_samples);
         if (count >= (int64_t)4 << 31)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld has %lld output samples, a segment may have less than 2^33", who,
                            (long long)i, (long long)count);
-        spans[(size_t)i] = Span{it.out_sample, it.out_sample + count, i};
-        const uint32_t mode = channels == 1 ? vadk::SCAN_LEFT : it.channel == VAD_SCAN_MIX ? vadk::SCAN_MIX : (uint32_t)it.channel;
+        c.spans[(size_t)i] = CutSpan{it.out_sample, it.out_sample + count, i};
+        const uint32_t mode = c.channels == 1 ? vadk::SCAN_LEFT : it.channel == VAD_SCAN_MIX ? vadk::SCAN_MIX : (uint32_t)it.channel;
         const uint32_t nq = (uint32_t)(count >> 2);
-        e->cut_segs[(size_t)i] = vadk::CutSeg{(uint32_t)((it.sample_offset + it.first_frame * (int64_t)hop) >> 2) | (mode << vadk::SCAN_MODE_SHIFT), nq,
+        e->cut_segs[(size_t)i] = vadk::CutSeg{(uint32_t)((it.sample_offset + it.first_frame * hop) >> 2) | (mode << vadk::SCAN_MODE_SHIFT), nq,
                                               (uint64_t)it.out_sample >> 2};
-        if (rate_frames) {
-            // the kernels' work is listed per window, behind the checks
-            e->cut_rows.push_back(vadk::CutResampleSeg{e->cut_segs[(size_t)i].quad_in, (uint32_t)rows});
-            rows += it.nframes;
-            if (rows > INT32_MAX)
+        if (c.rate_frames) {
+            e->cut_rows.push_back(vadk::CutResampleSeg{e->cut_segs[(size_t)i].quad_in, (uint32_t)c.rows});
+            c.rows += it.nframes;
+            if (c.rows > INT32_MAX)
                 return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 frames in one call", who);
             continue;
         }
@@ -1547,174 +1740,211 @@ int cut_run(vad_engine *e, const char *who, const vad_cut_item *items, int64_t n
         if (e->cut_work.size() > (size_t)INT32_MAX)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d samples in one call", who, VAD_CUT_WG_SAMPLES);
     }
-    std::sort(spans.begin(), spans.end(), [](const Span &a, const Span &b) { return a.lo < b.lo; });
-    for (size_t k = 1; k < spans.size(); ++k)
-        if (spans[k].lo < spans[k - 1].hi)
+    std::sort(c.spans.begin(), c.spans.end(), [](const CutSpan &a, const CutSpan &b) { return a.lo < b.lo; });
+    for (size_t k = 1; k < c.spans.size(); ++k)
+        if (c.spans[k].lo < c.spans[k - 1].hi)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output ranges of segments %lld and %lld overlap", who,
-                           (long long)spans[k - 1].i, (long long)spans[k].i);
-    if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    const size_t ab = (size_t)audio_samples * (size_t)fbytes, ob = out_fmt == VAD_CUT_PCM16 ? 2 : 4;
-    const void *d_audio = audio;
-    void *d_out = out;
-    const int64_t out_lo = spans.front().lo, out_hi = spans.back().hi;
-    if (DEV) {
-        if (!audio) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-        const uintptr_t align = channels == 2 ? 8 : 4;
-        if (reinterpret_cast<uintptr_t>(audio) & (align - 1))
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the audio block must be %d-byte aligned", who, (int)align);
-        if (reinterpret_cast<uintptr_t>(out) & 15)
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output must be 16-byte aligned", who);
+                           (long long)c.spans[k - 1].i, (long long)c.spans[k].i);
+    c.ab = (size_t)audio_samples * (size_t)c.channels * sample_bytes(c.fmt);
+    c.ob = c.out_fmt == VAD_CUT_PCM16 ? 2 : 4;
+    return VAD_OK;
+}
+
+// b. the block the call reads and the output it writes.  A device call: the caller's two pointers
+int cut_block_device(vad_engine *e, CutPlan &c, const void *d_audio, void *d_out) {
+    if (!d_audio) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", c.who);
+    if (int rc = check_device_audio(e, c.who, d_audio, c.channels)) return rc;
+    if (reinterpret_cast<uintptr_t>(d_out) & 15)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output must be 16-byte aligned", c.who);
+    c.d_audio = d_audio;
+    c.d_out = d_out;
+    return VAD_OK;
+}
+
+// ... a host call: e->d_audio - the resident block (audio = NULL: what the last scan or cut uploaded is still in device memory and
+// crosses the link once; a rate block is none of vad_scan_cut's, and the other way round), or room for the upload - and e->d_cut_out
+int cut_block_host(vad_engine *e, CutPlan &c, const void *audio) {
+    const char *who = c.who;
+    if (!audio) {
+        if (!c.rate && (!e->audio_resident || e->audio_rate != 0))
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the engine holds no resident block: no vad_scan or "
+                           "vad_scan_channels has uploaded one", who);
+        if (c.rate && (!e->audio_resident || e->audio_rate == 0))
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the engine holds no resident rate block: no "
+                           "vad_scan_rate_segments or vad_scan_rate_cut has uploaded one", who);
+        if (c.rate && e->audio_rate != c.sr_in)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the resident block has sample rate %d, not %d", who,
+                           e->audio_rate, c.sr_in);
+        if (e->audio_fmt != c.fmt)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the resident block has frame format %d, not %d", who,
+                           e->audio_fmt, c.fmt);
+        if (e->audio_channels != c.channels)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the resident block has %d channels, not %d", who,
+                           e->audio_channels, c.channels);
+        if (e->audio_bytes != c.ab)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the resident block has %llu bytes, not the %llu of "
+                           "%lld samples", who, (unsigned long long)e->audio_bytes, (unsigned long long)c.ab, (long long)c.audio_samples);
     } else {
-        if (!audio) {
-            // the block that the last scan uploaded is still in device memory: it crosses the link once
-            // (a rate block is none of vad_scan_cut's: its positions and hop count samples at another rate than the engine's)
-            if (!rate && (!e->audio_resident || e->audio_rate != 0))
-                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the engine holds no resident block: no vad_scan or "
-                               "vad_scan_channels has uploaded one", who);
-            if (rate && (!e->audio_resident || e->audio_rate == 0))
-                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the engine holds no resident rate block: no "
-                               "vad_scan_rate_segments or vad_scan_rate_cut has uploaded one", who);
-            if (rate && e->audio_rate != sr_in)
-                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the resident block has sample rate %d, not %d", who,
-                               e->audio_rate, sr_in);
-            if (e->audio_fmt != fmt)
-                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the resident block has frame format %d, not %d", who,
-                               e->audio_fmt, fmt);
-            if (e->audio_channels != channels)
-                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the resident block has %d channels, not %d", who,
-                               e->audio_channels, channels);
-            if (e->audio_bytes != ab)
-                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the resident block has %llu bytes, not the %llu of "
-                               "%lld samples", who, (unsigned long long)e->audio_bytes, (unsigned long long)ab, (long long)audio_samples);
-        } else {
-            e->audio_resident = false;
-            if (int rc = ensure(e, e->d_audio, e->d_audio_cap, ab + 16)) return rc;
+        e->audio_resident = false;
+        if (int rc = ensure(e, e->d_audio, e->d_audio_cap, c.ab + 16)) return rc;
+    }
+    const int64_t out_lo = c.spans.front().lo, out_hi = c.spans.back().hi;
+    if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, (size_t)(out_hi - out_lo) * c.ob)) return rc;
+    c.d_audio = e->d_audio;
+    c.d_out = e->d_cut_out;
+    // on the device the output starts at the first segment's first sample
+    for (vadk::CutSeg &sg : e->cut_segs) sg.quad_out -= (uint64_t)out_lo >> 2;
+    return VAD_OK;
+}
+
+// c. rate_frames: one window of rows at a time goes through e->d_win.  Per window the cut kernel's segments - one per (segment of
+// the call, window), with its place in the window and in the output - and workgroups; per tile of the call the segment that owns
+// its first row (vad_layout.h: CutResampleArgs)
+int cut_windows(vad_engine *e, CutPlan &c) {
+    if (int rc = get_resample_op(e, c.chunk, &c.op)) return rc;
+    const uint32_t total = (uint32_t)c.rows, wr = cut_window_rows(e);
+    std::vector<vadk::CutSeg> wsegs;
+    e->cut_rows.push_back(vadk::CutResampleSeg{0u, total});
+    const std::vector<vadk::CutResampleSeg> &cr = e->cut_rows;
+    size_t si = 0;
+    for (uint32_t r0 = 0; r0 < total; r0 += wr) {
+        const uint32_t r1 = (uint32_t)std::min<uint64_t>(total, (uint64_t)r0 + wr);
+        CutWin w{r0, r1, wsegs.size(), e->cut_work.size(), 0};
+        while (si < (size_t)c.n && cr[si].row0 < r1) {
+            const uint32_t lo = std::max(cr[si].row0, r0), hi = std::min(cr[si + 1].row0, r1), nq = (hi - lo) * 128u;
+            const uint32_t local = (uint32_t)(wsegs.size() - w.seg0);
+            wsegs.push_back(vadk::CutSeg{(lo - r0) * 128u, nq, e->cut_segs[si].quad_out + (uint64_t)(lo - cr[si].row0) * 128u});
+            for (uint32_t q = 0; q < nq; q += vadk::CUT_WG_QUADS) e->cut_work.push_back(vadk::CutWork{local, q});
+            if (cr[si + 1].row0 > r1) break;     // the segment goes on in the next window
+            ++si;
         }
-        if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, (size_t)(out_hi - out_lo) * ob)) return rc;
-        d_audio = e->d_audio;
-        d_out = e->d_cut_out;
-        // on the device the output starts at the first segment's first sample
-        for (vadk::CutSeg &sg : e->cut_segs) sg.quad_out -= (uint64_t)out_lo >> 2;
+        w.nwork = e->cut_work.size() - w.work0;
+        c.wins.push_back(w);
     }
-    // rate_frames: one window of rows at a time goes through e->d_win.  Per window the cut kernel's segments - one per (segment
-    // of the call, window), with its place in the window and in the output - and workgroups; per tile of the call the segment
-    // that owns its first row (vad_layout.h: CutResampleArgs)
-    struct Win { uint32_t r0, r1; size_t seg0, work0, nwork; };
-    std::vector<Win> wins;
-    vad_engine::ResampleOp *op = nullptr;
-    if (rate_frames) {
-        if (int rc = get_resample_op(e, chunk, &op)) return rc;
-        const uint32_t total = (uint32_t)rows, wr = cut_window_rows(e);
-        std::vector<vadk::CutSeg> wsegs;
-        e->cut_rows.push_back(vadk::CutResampleSeg{0u, total});
-        const std::vector<vadk::CutResampleSeg> &cr = e->cut_rows;
-        size_t si = 0;
-        for (uint32_t r0 = 0; r0 < total; r0 += wr) {
-            const uint32_t r1 = (uint32_t)std::min<uint64_t>(total, (uint64_t)r0 + wr);
-            Win w{r0, r1, wsegs.size(), e->cut_work.size(), 0};
-            while (si < (size_t)n && cr[si].row0 < r1) {
-                const uint32_t lo = std::max(cr[si].row0, r0), hi = std::min(cr[si + 1].row0, r1), nq = (hi - lo) * 128u;
-                const uint32_t local = (uint32_t)(wsegs.size() - w.seg0);
-                wsegs.push_back(vadk::CutSeg{(lo - r0) * 128u, nq, e->cut_segs[si].quad_out + (uint64_t)(lo - cr[si].row0) * 128u});
-                for (uint32_t q = 0; q < nq; q += vadk::CUT_WG_QUADS) e->cut_work.push_back(vadk::CutWork{local, q});
-                if (cr[si + 1].row0 > r1) break;     // the segment goes on in the next window
-                ++si;
-            }
-            w.nwork = e->cut_work.size() - w.work0;
-            wins.push_back(w);
-        }
-        e->cut_tiles.resize(((size_t)total + vadk::MT - 1) / vadk::MT);
-        si = 0;
-        for (size_t t = 0; t < e->cut_tiles.size(); ++t) {
-            while (cr[si + 1].row0 <= (uint32_t)(t * vadk::MT)) ++si;
-            e->cut_tiles[t] = (uint32_t)si;
-        }
-        e->cut_segs.swap(wsegs);
-        if (int rc = ensure(e, e->d_win, e->d_win_cap, (size_t)std::min(total, wr) * 2048u)) return rc;
+    e->cut_tiles.resize(((size_t)total + vadk::MT - 1) / vadk::MT);
+    si = 0;
+    for (size_t t = 0; t < e->cut_tiles.size(); ++t) {
+        while (cr[si + 1].row0 <= (uint32_t)(t * vadk::MT)) ++si;
+        e->cut_tiles[t] = (uint32_t)si;
     }
-    const size_t sb = sizeof(vadk::CutSeg) * e->cut_segs.size(), wb = sizeof(vadk::CutWork) * e->cut_work.size();
-    const size_t rb = sizeof(vadk::CutResampleSeg) * e->cut_rows.size(), tb = rate_frames ? sizeof(uint32_t) * e->cut_tiles.size() : 0;
-    if (int rc = ensure(e, e->d_cut, e->d_cut_cap, sb + wb + rb + tb)) return rc;
-    if (!DEV && audio) {
-        HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, ab, hipMemcpyHostToDevice, s));
-        e->audio_resident = true;
-        e->audio_bytes = ab; e->audio_channels = channels; e->audio_fmt = fmt; e->audio_rate = rate ? sr_in : 0;
+    e->cut_segs.swap(wsegs);
+    return ensure(e, e->d_win, e->d_win_cap, (size_t)std::min(total, wr) * 2048u);
+}
+
+// d. the first writes: host audio (which becomes the resident block, of the call's rate) and the tables, on `s` ...
+int cut_upload(vad_engine *e, CutPlan &c, const void *audio, hipStream_t s) {
+    c.sb = sizeof(vadk::CutSeg) * e->cut_segs.size();
+    c.wb = sizeof(vadk::CutWork) * e->cut_work.size();
+    c.rb = sizeof(vadk::CutResampleSeg) * e->cut_rows.size();
+    c.tb = c.rate_frames ? sizeof(uint32_t) * e->cut_tiles.size() : 0;
+    if (int rc = ensure(e, e->d_cut, e->d_cut_cap, c.sb + c.wb + c.rb + c.tb)) return rc;
+    if (audio) {
+        HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, c.ab, hipMemcpyHostToDevice, s));
+        set_resident(e, c.ab, c.channels, c.fmt, c.rate ? c.sr_in : 0);
     }
-    HIP_TRY(e, hipMemcpyAsync(e->d_cut, e->cut_segs.data(), sb, hipMemcpyHostToDevice, s));
-    HIP_TRY(e, hipMemcpyAsync(e->d_cut + sb, e->cut_work.data(), wb, hipMemcpyHostToDevice, s));
-    if (rate_frames) {
-        HIP_TRY(e, hipMemcpyAsync(e->d_cut + sb + wb, e->cut_rows.data(), rb, hipMemcpyHostToDevice, s));
-        HIP_TRY(e, hipMemcpyAsync(e->d_cut + sb + wb + rb, e->cut_tiles.data(), tb, hipMemcpyHostToDevice, s));
+    HIP_TRY(e, hipMemcpyAsync(e->d_cut, e->cut_segs.data(), c.sb, hipMemcpyHostToDevice, s));
+    HIP_TRY(e, hipMemcpyAsync(e->d_cut + c.sb, e->cut_work.data(), c.wb, hipMemcpyHostToDevice, s));
+    if (c.rate_frames) {
+        HIP_TRY(e, hipMemcpyAsync(e->d_cut + c.sb + c.wb, e->cut_rows.data(), c.rb, hipMemcpyHostToDevice, s));
+        HIP_TRY(e, hipMemcpyAsync(e->d_cut + c.sb + c.wb + c.rb, e->cut_tiles.data(), c.tb, hipMemcpyHostToDevice, s));
     }
+    return VAD_OK;
+}
+
+// ... and the launches: one cut, or per window of a rate cut's frames the resampler and the cut of what it wrote
+int cut_launches(vad_engine *e, const CutPlan &c, hipStream_t s) {
     vadk::CutArgs a{};
-    a.audio = d_audio;
-    a.out = d_out;
+    a.audio = c.d_audio;
+    a.out = c.d_out;
     a.segs = reinterpret_cast<const vadk::CutSeg *>(e->d_cut);
-    a.work = reinterpret_cast<const vadk::CutWork *>(e->d_cut + sb);
-    a.audio_bytes = (uint32_t)ab;
+    a.work = reinterpret_cast<const vadk::CutWork *>(e->d_cut + c.sb);
+    a.audio_bytes = (uint32_t)c.ab;
     a.nwork = (uint32_t)e->cut_work.size();
-    a.hopq = (uint32_t)hop >> 2;
-    a.frame_shift = layout == VAD_CUT_FRAMES ? fshift : 31u;
-    a.fmt = fmt;
-    a.channels = channels;
-    a.out_fmt = out_fmt;
-    a.thresh = rate && !rate_frames ? -1.0f : thr;
-    hipError_t r = hipSuccess;
-    const char *what = "kernel launch (scan cut)";
-    if (rate_frames) {
-        vadk::CutResampleArgs ra{};
-        ra.wstream = op->d_w;
-        ra.wstream_bytes = (uint32_t)op->bytes;
-        ra.tile_blocks = op->tile_blocks;
-        ra.row128_block = op->row128_block;
-        ra.audio_bytes = (uint32_t)ab;
-        ra.audio = d_audio;
-        ra.segs = reinterpret_cast<const vadk::CutResampleSeg *>(e->d_cut + sb + wb);
-        ra.tile_seg = reinterpret_cast<const uint32_t *>(e->d_cut + sb + wb + rb);
-        ra.win = e->d_win;
-        ra.n_in = chunk;
-        ra.hopq = (uint32_t)hop >> 2;
-        ra.fmt = fmt;
-        ra.channels = channels;
-        // the window as the cut kernel sees it: mono float32 frames of 512 samples, back to back
-        a.audio = e->d_win;
-        a.hopq = VAD_FRAME_SAMPLES / 4;
-        a.fmt = VAD_FMT_F32;
-        a.channels = 1;
-        for (const Win &w : wins) {
-            ra.r0 = w.r0;
-            ra.rows_end = w.r1;
-            r = vadk_launch_cut_resample(&ra, s);
-            if (r != hipSuccess) { what = "kernel launch (cut resample)"; break; }
-            a.segs = reinterpret_cast<const vadk::CutSeg *>(e->d_cut) + w.seg0;
-            a.work = reinterpret_cast<const vadk::CutWork *>(e->d_cut + sb) + w.work0;
-            a.nwork = (uint32_t)w.nwork;
-            a.audio_bytes = (w.r1 - w.r0) * 2048u;
-            r = vadk_launch_scan_cut(&a, s);
-            if (r != hipSuccess) break;
-        }
-    } else {
-        r = vadk_launch_scan_cut(&a, s);
-    }
-    if (DEV) {
-        // the launch reads the engine's tables: the next scan or cut waits for it, as behind vad_scan_device
-        if (!e->scan_done) HIP_TRY(e, hipEventCreateWithFlags(&e->scan_done, hipEventDisableTiming));
-        HIP_TRY(e, hipEventRecord(e->scan_done, s));
-        e->scan_pending = true;
-        if (r != hipSuccess) return e->hip_fail(r, what);
+    a.hopq = (uint32_t)c.hop >> 2;
+    a.frame_shift = c.layout == VAD_CUT_FRAMES ? c.fshift : 31u;
+    a.fmt = c.fmt;
+    a.channels = c.channels;
+    a.out_fmt = c.out_fmt;
+    a.thresh = c.rate && !c.rate_frames ? -1.0f : c.thr;
+    if (!c.rate_frames) {
+        const hipError_t r = vadk_launch_scan_cut(&a, s);
+        if (r != hipSuccess) return e->hip_fail(r, "kernel launch (scan cut)");
         return VAD_OK;
     }
-    if (r != hipSuccess) return e->hip_fail(r, what);
-    // only speech crosses the link back: one copy per run of adjoining segments (packed payloads: one), the gaps stay the caller's
+    vadk::CutResampleArgs ra{};
+    ra.wstream = c.op->d_w;
+    ra.wstream_bytes = (uint32_t)c.op->bytes;
+    ra.tile_blocks = c.op->tile_blocks;
+    ra.row128_block = c.op->row128_block;
+    ra.audio_bytes = (uint32_t)c.ab;
+    ra.audio = c.d_audio;
+    ra.segs = reinterpret_cast<const vadk::CutResampleSeg *>(e->d_cut + c.sb + c.wb);
+    ra.tile_seg = reinterpret_cast<const uint32_t *>(e->d_cut + c.sb + c.wb + c.rb);
+    ra.win = e->d_win;
+    ra.n_in = c.chunk;
+    ra.hopq = (uint32_t)c.hop >> 2;
+    ra.fmt = c.fmt;
+    ra.channels = c.channels;
+    // the window as the cut kernel sees it: mono float32 frames of 512 samples, back to back
+    a.audio = e->d_win;
+    a.hopq = VAD_FRAME_SAMPLES / 4;
+    a.fmt = VAD_FMT_F32;
+    a.channels = 1;
+    for (const CutWin &w : c.wins) {
+        ra.r0 = w.r0;
+        ra.rows_end = w.r1;
+        hipError_t r = vadk_launch_cut_resample(&ra, s);
+        if (r != hipSuccess) return e->hip_fail(r, "kernel launch (cut resample)");
+        a.segs = reinterpret_cast<const vadk::CutSeg *>(e->d_cut) + w.seg0;
+        a.work = reinterpret_cast<const vadk::CutWork *>(e->d_cut + c.sb) + w.work0;
+        a.nwork = (uint32_t)w.nwork;
+        a.audio_bytes = (w.r1 - w.r0) * 2048u;
+        r = vadk_launch_scan_cut(&a, s);
+        if (r != hipSuccess) return e->hip_fail(r, "kernel launch (scan cut)");
+    }
+    return VAD_OK;
+}
+
+// e. a host call: only speech crosses the link back - one copy per run of adjoining segments (packed payloads: one), the gaps stay
+// the caller's
+int cut_copy_back(vad_engine *e, const CutPlan &c, void *out, hipStream_t s) {
+    const std::vector<CutSpan> &spans = c.spans;
+    const int64_t out_lo = spans.front().lo;
     for (size_t k = 0; k < spans.size();) {
         size_t m = k + 1;
         while (m < spans.size() && spans[m].lo == spans[m - 1].hi) ++m;
-        HIP_TRY(e, hipMemcpyAsync(static_cast<uint8_t *>(out) + (size_t)spans[k].lo * ob, static_cast<uint8_t *>(d_out) + (size_t)(spans[k].lo - out_lo) * ob,
-                                  (size_t)(spans[m - 1].hi - spans[k].lo) * ob, hipMemcpyDeviceToHost, s));
+        HIP_TRY(e, hipMemcpyAsync(static_cast<uint8_t *>(out) + (size_t)spans[k].lo * c.ob, static_cast<uint8_t *>(c.d_out) + (size_t)(spans[k].lo - out_lo) * c.ob,
+                                  (size_t)(spans[m - 1].hi - spans[k].lo) * c.ob, hipMemcpyDeviceToHost, s));
         k = m;
     }
     HIP_TRY(e, hipStreamSynchronize(s));
     return VAD_OK;
+}
+
+// vad_scan_cut and vad_scan_rate_cut (dev = false: host audio, or NULL = the resident block, and a host `out`) and their _device
+// forms, with e->mu held.  Every check comes before the first write: phases a to c refuse or size buffers, cut_upload writes first.
+int cut_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples,
+            int32_t channels, int fmt, int32_t hop, float thr, int32_t layout, int32_t out_fmt, void *out, int64_t out_samples, void *stream,
+            int chunk = 0, int32_t sr_in = 0) {
+    hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    CutPlan c{who, items, n, audio_samples, channels, fmt, hop, thr, layout, out_fmt, out_samples, chunk, sr_in};
+    if (int rc = cut_check(e, c)) return rc;
+    if (n == 0) return VAD_OK;
+    if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if (int rc = dev ? cut_block_device(e, c, audio, out) : cut_block_host(e, c, audio)) return rc;
+    if (c.rate_frames)
+        if (int rc = cut_windows(e, c)) return rc;
+    if (int rc = cut_upload(e, c, dev ? nullptr : audio, s)) return rc;
+    const int rc = cut_launches(e, c, s);
+    if (dev) {
+        // the launches read the engine's tables: the next scan or cut waits for them, as behind vad_scan_device
+        if (int rc2 = scan_mark_pending(e, s)) return rc2;
+        return rc;
+    }
+    if (rc) return rc;
+    return cut_copy_back(e, c, out, s);
 }
 
 }  // namespace
@@ -1727,22 +1957,57 @@ int64_t vad_cut_samples(const vad_engine *e, int64_t nframes, int32_t hop, int32
     return cut_samples(e->frame_samples, nframes, hop, layout, e->frame_samples);
 }
 
+int64_t vad_rate_cut_samples(const vad_engine *e, int64_t nframes, int32_t sr_in, int32_t hop, int32_t layout) {
+    if (sr_in == 16000) return vad_cut_samples(e, nframes, hop, layout);
+    const int chunk = resample_chunk_len(sr_in);
+    if (!e || chunk == 0 || nframes < 1 || hop < 4 || (hop & 3) || (layout != VAD_CUT_FRAMES && layout != VAD_CUT_RANGE)) return -1;
+    if (nframes > (INT64_MAX >> 1) / std::max<int64_t>(hop, chunk)) return -1;
+    return cut_samples(chunk, nframes, hop, layout, VAD_FRAME_SAMPLES);
+}
+
 int vad_scan_cut(vad_engine *e, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt,
                  int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *out, int64_t out_samples) {
-    return cut_run<false>(e, "vad_scan_cut", items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, out,
-                          out_samples, nullptr);
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return cut_run(e, false, "vad_scan_cut", items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, out,
+                   out_samples, nullptr);
 }
 
 int vad_scan_cut_device(vad_engine *e, const vad_cut_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
                         int frame_fmt, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *d_out, int64_t out_samples,
                         void *stream) {
-    return cut_run<true>(e, "vad_scan_cut_device", items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt,
-                         d_out, out_samples, stream);
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return cut_run(e, true, "vad_scan_cut_device", items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt,
+                   d_out, out_samples, stream);
 }
 
-// ---- the segment table of a scan (vad_segments_device, vad_scan_segments) -----------------------------------------
+int vad_scan_rate_cut(vad_engine *e, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt,
+                      int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *out, int64_t out_samples) {
+    static const char *who = "vad_scan_rate_cut";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int chunk = 0;
+    if (int rc = rate_cut_check(e, who, sr_in, &chunk)) return rc;
+    return cut_run(e, false, who, items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, out, out_samples, nullptr,
+                   chunk, sr_in);
+}
+
+int vad_scan_rate_cut_device(vad_engine *e, const vad_cut_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
+                             int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *d_out,
+                             int64_t out_samples, void *stream) {
+    static const char *who = "vad_scan_rate_cut_device";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int chunk = 0;
+    if (int rc = rate_cut_check(e, who, sr_in, &chunk)) return rc;
+    return cut_run(e, true, who, items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, d_out, out_samples,
+                   stream, chunk, sr_in);
+}
+
 }  // extern "C"
 
+// ---- the segment table of a scan (vad_segments_device, vad_scan_segments, vad_scan_rate_segments) ---------------------------
 namespace {
 
 static_assert(sizeof(vad_segment) == sizeof(vadk::SegRecord), "the header's record is the kernel's");
@@ -1774,6 +2039,50 @@ int seg_launches(vad_engine *e, const uint8_t *d_events, const int32_t *d_seg, c
     }
     const hipError_t r = vadk_launch_scan_segments(&a, s);
     if (r != hipSuccess) return e->hip_fail(r, "kernel launch (scan segments)");
+    return VAD_OK;
+}
+
+// vad_scan_segments and vad_scan_rate_segments (chunk > 0: the recordings are at sr_in), with e->mu held: the scan of host audio
+// into the engine's own arrays - the block stays resident, of its rate - then the extraction
+int scan_segments_run(vad_engine *e, const char *who, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples,
+                      int32_t channels, int frame_fmt, int chunk, int32_t sr_in, int32_t hop, float denoise_thresh, vad_segment *segs_out,
+                      int64_t seg_cap, int64_t *nsegs_out) {
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    // the CSR positions the caller of vad_scan_channels would have passed are the plan's to make: the items packed in their order
+    std::vector<int64_t> &start = e->seg_out_start;
+    int64_t total = 0;
+    if (int rc = scan_plan(e, who, items, n, audio_samples, channels, frame_fmt, hop, (const int64_t *)nullptr, 0, &total, &start, chunk)) return rc;
+    if (seg_cap < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: seg_cap = %lld: bad count", who, (long long)seg_cap);
+    if (!nsegs_out || (seg_cap > 0 && !segs_out) || (total > 0 && !audio))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    e->segtab_count = -1;
+    if (total == 0) {                        // nothing to scan: an empty table
+        e->segtab_count = 0;
+        *nsegs_out = 0;
+        return VAD_OK;
+    }
+    if (int rc = scan_upload_launch(e, n, audio, audio_samples, channels, frame_fmt, chunk, sr_in, hop, denoise_thresh, total, true)) return rc;
+    if (int rc = ensure(e, e->d_nsegs, e->d_nsegs_cap, sizeof(long long))) return rc;
+    // the table's size is known only behind the count: room for the caller's capacity and for a segment per 16 frames first, and
+    // the extraction once more (the per-frame arrays are still there) in the rare case that the table is larger
+    int64_t room = std::min(total, std::max<int64_t>({seg_cap, total / 16 + 256, (int64_t)(e->d_segtab_cap / sizeof(vadk::SegRecord))}));
+    long long count = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (int rc = ensure(e, e->d_segtab, e->d_segtab_cap, sizeof(vadk::SegRecord) * (size_t)room)) return rc;
+        if (int rc = seg_launches(e, e->d_events, e->d_seg, e->d_probs, start.data(), n, e->d_segtab, room, e->d_nsegs, e->stream)) return rc;
+        HIP_TRY(e, hipMemcpyAsync(&count, e->d_nsegs, sizeof count, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(e, hipStreamSynchronize(e->stream));
+        if (count <= room) break;
+        room = count;
+    }
+    const int64_t take = std::min<int64_t>(count, seg_cap);
+    if (take > 0) {
+        HIP_TRY(e, hipMemcpyAsync(segs_out, e->d_segtab, sizeof(vad_segment) * (size_t)take, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(e, hipStreamSynchronize(e->stream));
+    }
+    e->segtab_count = count;
+    *nsegs_out = count;
     return VAD_OK;
 }
 
@@ -1809,87 +2118,32 @@ int vad_segments_device(vad_engine *e, const uint8_t *d_events, const int32_t *d
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: seg_frames and probs must be 4-byte aligned", who);
     if (reinterpret_cast<uintptr_t>(d_nsegs) & 7)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the count must be 8-byte aligned", who);
-    if (!e->scan_done) HIP_TRY(e, hipEventCreateWithFlags(&e->scan_done, hipEventDisableTiming));
     const int rc = seg_launches(e, d_events, d_seg_frames, d_probs, out_start, n, reinterpret_cast<vadk::SegRecord *>(d_segs), seg_cap,
                                 reinterpret_cast<long long *>(d_nsegs), s);
     // the launches read the engine's work area: the next scan, cut or extraction waits for them, as behind vad_scan_device
-    HIP_TRY(e, hipEventRecord(e->scan_done, s));
-    e->scan_pending = true;
+    if (int rc2 = scan_mark_pending(e, s)) return rc2;
     return rc;
 }
 
-}  // extern "C"
-
-namespace {
-
-// (defined with the rate scan, further down, inside that section's extern "C" block)
-extern "C" {
-int scan_rate_check(vad_engine *e, const char *who, int32_t sr_in, int *chunk);
-int scan_rate_upload_launch(vad_engine *e, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt, int chunk,
-                            int32_t sr_in, int32_t hop, float denoise_thresh, int64_t total, bool resident);
-}
-
-// vad_scan_segments and vad_scan_rate_segments (by_rate: the recordings are at sr_in): the scan of host audio into the engine's own
-// arrays, then the extraction
-int scan_segments_run(vad_engine *e, const char *who, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples,
-                      int32_t channels, int frame_fmt, bool by_rate, int32_t sr_in, int32_t hop, float denoise_thresh, vad_segment *segs_out,
-                      int64_t seg_cap, int64_t *nsegs_out) {
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    int chunk = 0;                           // 0: frames of the engine's own (16 kHz recordings are vad_scan_segments's)
-    if (by_rate)
-        if (int rc = scan_rate_check(e, who, sr_in, &chunk)) return rc;
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
-    // the CSR positions the caller of vad_scan_channels would have passed are the plan's to make: the items packed in their order
-    std::vector<int64_t> &start = e->seg_out_start;
-    int64_t total = 0;
-    if (int rc = scan_plan(e, who, items, n, audio_samples, channels, frame_fmt, hop, (const int64_t *)nullptr, 0, &total, &start, chunk)) return rc;
-    if (seg_cap < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: seg_cap = %lld: bad count", who, (long long)seg_cap);
-    if (!nsegs_out || (seg_cap > 0 && !segs_out) || (total > 0 && !audio))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    e->segtab_count = -1;
-    if (total == 0) {                        // nothing to scan: an empty table
-        e->segtab_count = 0;
-        *nsegs_out = 0;
-        return VAD_OK;
-    }
-    if (chunk == 0) {
-        if (int rc = scan_upload_launch(e, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, total)) return rc;
-    } else if (int rc = scan_rate_upload_launch(e, n, audio, audio_samples, channels, frame_fmt, chunk, sr_in, hop, denoise_thresh, total, true)) {
-        return rc;
-    }
-    if (int rc = ensure(e, e->d_nsegs, e->d_nsegs_cap, sizeof(long long))) return rc;
-    // the table's size is known only behind the count: room for the caller's capacity and for a segment per 16 frames first, and
-    // the extraction once more (the per-frame arrays are still there) in the rare case that the table is larger
-    int64_t room = std::min(total, std::max<int64_t>({seg_cap, total / 16 + 256, (int64_t)(e->d_segtab_cap / sizeof(vadk::SegRecord))}));
-    long long count = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        if (int rc = ensure(e, e->d_segtab, e->d_segtab_cap, sizeof(vadk::SegRecord) * (size_t)room)) return rc;
-        if (int rc = seg_launches(e, e->d_events, e->d_seg, e->d_probs, start.data(), n, e->d_segtab, room, e->d_nsegs, e->stream)) return rc;
-        HIP_TRY(e, hipMemcpyAsync(&count, e->d_nsegs, sizeof count, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(e, hipStreamSynchronize(e->stream));
-        if (count <= room) break;
-        room = count;
-    }
-    const int64_t take = std::min<int64_t>(count, seg_cap);
-    if (take > 0) {
-        HIP_TRY(e, hipMemcpyAsync(segs_out, e->d_segtab, sizeof(vad_segment) * (size_t)take, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(e, hipStreamSynchronize(e->stream));
-    }
-    e->segtab_count = count;
-    *nsegs_out = count;
-    return VAD_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 int vad_scan_segments(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
                       int frame_fmt, int32_t hop, float denoise_thresh, vad_segment *segs_out, int64_t seg_cap, int64_t *nsegs_out) {
-    return scan_segments_run(e, "vad_scan_segments", items, n, audio, audio_samples, channels, frame_fmt, false, 0, hop, denoise_thresh, segs_out,
-                             seg_cap, nsegs_out);
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return scan_segments_run(e, "vad_scan_segments", items, n, audio, audio_samples, channels, frame_fmt, 0, 0, hop, denoise_thresh, segs_out, seg_cap,
+                             nsegs_out);
+}
+
+// (sr_in == 16000: scan_rate_check answers chunk = 0, and the call is vad_scan_segments under this name)
+int vad_scan_rate_segments(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
+                           int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, vad_segment *segs_out, int64_t seg_cap,
+                           int64_t *nsegs_out) {
+    static const char *who = "vad_scan_rate_segments";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int chunk = 0;
+    if (int rc = scan_rate_check(e, who, sr_in, &chunk)) return rc;
+    return scan_segments_run(e, who, items, n, audio, audio_samples, channels, frame_fmt, chunk, sr_in, hop, denoise_thresh, segs_out, seg_cap,
+                             nsegs_out);
 }
 
 int vad_scan_segments_read(vad_engine *e, int64_t first, int64_t count, vad_segment *out) {
@@ -2018,44 +2272,10 @@ int vad_step_collect(vad_engine *e, int64_t ticket, float *probs_out, uint8_t *e
     return VAD_OK;
 }
 
+}  // extern "C"
+
+// ---- chunks of 8 / 24 / 48 kHz audio resampled to 512 samples at 16 kHz (vad_resample) --------------------------------------
 namespace {
-
-// chunk length that yields 512 samples at 16 kHz (AudioUtils.resample_audio: int(len * 16000 / sr), audio.py:46)
-int resample_chunk_len(int sr_in) {
-    switch (sr_in) {
-        case 8000: return 256;
-        case 24000: return 768;
-        case 48000: return 1536;
-        default: return 0;
-    }
-}
-
-int get_resample_op(vad_engine *e, int n_in, vad_engine::ResampleOp **out, bool t16) {
-    auto &ops = t16 ? e->resample_ops16 : e->resample_ops;
-    for (auto &op : ops)
-        if (op.n_in == n_in) {
-            *out = &op;
-            return VAD_OK;
-        }
-    std::vector<float> packed;
-    std::string perr;
-    vad_engine::ResampleOp op;
-    op.n_in = n_in;
-    op.tile_blocks = t16 ? vadk::pack_resample_operator_t16(n_in, packed, &op.row128_block, perr)
-                         : vadk::pack_resample_operator(n_in, packed, &op.row128_block, perr);
-    if (op.tile_blocks == 0) return e->fail(VAD_ERR_INVALID_ARG, "Failed to resample audio: %s", perr.c_str());
-    op.bytes = packed.size() * sizeof(float);
-    hipError_t r = hipMalloc((void **)&op.d_w, op.bytes);
-    if (r != hipSuccess) return e->hip_fail(r, "hipMalloc(resample operator)");
-    r = hipMemcpy(op.d_w, packed.data(), op.bytes, hipMemcpyHostToDevice);
-    if (r != hipSuccess) {
-        (void)hipFree(op.d_w);
-        return e->hip_fail(r, "hipMemcpy(resample operator)");
-    }
-    ops.push_back(op);
-    *out = &ops.back();
-    return VAD_OK;
-}
 
 // fills one segment descriptor (validates the chunk convention, builds / finds the operator)
 int resample_segment(vad_engine *e, const float *d_in, int64_t n, int32_t n_in, int32_t sr_in, float *d_out, vadk::ResampleSeg &sg) {
@@ -2089,6 +2309,8 @@ int resample_launch(vad_engine *e, const float *d_in, int64_t n, int32_t n_in, i
 }
 
 }  // namespace
+
+extern "C" {
 
 int vad_resample(vad_engine *e, const float *in, int64_t n, int32_t n_in, int32_t sr_in, float *out) {
     if (!e) return VAD_ERR_INVALID_ARG;
@@ -2141,246 +2363,7 @@ int vad_resample_multi_device(vad_engine *e, int32_t nseg, const float *const *d
     return VAD_OK;
 }
 
-// ---- whole recordings at 8 / 24 / 48 kHz (vad_scan_rate): framed at the input rate, resampled chunk by chunk, then scanned ------
-namespace {
-
-// what comes before the plan's checks: the engine's model rate and the input rate.  *chunk = sample frames of one chunk at sr_in, or
-// 0: the recordings are at 16 kHz already and the call is vad_scan_channels (AudioUtils.resample_audio returns its input).
-int scan_rate_check(vad_engine *e, const char *who, int32_t sr_in, int *chunk) {
-    if (e->version == 5 && e->frame_samples != VAD_FRAME_SAMPLES)
-        return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s: this engine runs an 8 kHz sub-model on %d-sample frames; "
-                       "resampled recordings need the 16 kHz one", who, e->frame_samples);
-    *chunk = sr_in == 16000 ? 0 : resample_chunk_len(sr_in);
-    if (sr_in != 16000 && *chunk == 0)
-        return e->fail(VAD_ERR_UNSUPPORTED, "Failed to resample audio from %dHz to 16000Hz: %s: supported input rates are 8000, 16000, 24000, 48000", sr_in, who);
-    return VAD_OK;
-}
-
-// the launches of a planned rate scan (e->d_items holds e->scan_items, planned on chunks of `chunk` sample frames): per window of W
-// chunks one vadk_scan_resample - the window's chunks of the live items -> 512-sample frames in d_win, and the window's item table
-// - and behind it, on the same stream, the scan kernel over d_win as a mono float32 block whose frames lie back to back.  State
-// travels through HBM between the windows, as in scan_launches; the gate and the non-finite check act on the resampled frame.
-int scan_rate_launches(vad_engine *e, const void *d_audio, int64_t audio_samples, int32_t channels, int fmt, int chunk, int32_t hop, float thr,
-                       float *d_probs, uint8_t *d_events, int32_t *d_seg, int64_t total, hipStream_t s) {
-    const std::vector<vadk::ScanItem> &it = e->scan_items;
-    const int maxf = it.empty() ? 0 : it.front().nframes;
-    size_t live = it.size();
-    while (live > 0 && it[live - 1].nframes <= 0) --live;
-    if (live == 0) return VAD_OK;
-    const int cap = e->scan_launch_frames > 0 ? e->scan_launch_frames : vad_engine::SCAN_LAUNCH_FRAMES;
-    const size_t fit = vad_engine::SCAN_RATE_WIN_BYTES / (live * 2048u);
-    const int W = std::max(1, (int)std::min<size_t>((size_t)std::min(cap, maxf), fit));
-    const size_t win_bytes = live * (size_t)W * 2048u;
-    if (win_bytes >= (size_t(1) << 31))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %zu recordings with chunks in one call: one frame of each exceeds the 2 GiB a launch may address", live);
-    vad_engine::ResampleOp *op = nullptr;
-    if (int rc = get_resample_op(e, chunk, &op)) return rc;
-    if (int rc = ensure(e, e->d_win, e->d_win_cap, win_bytes)) return rc;
-    if (int rc = ensure(e, e->d_items_win, e->d_items_win_cap, sizeof(vadk::ScanItem) * live)) return rc;
-    vadk::ScanResampleArgs r{};
-    r.wstream = op->d_w;
-    r.wstream_bytes = (uint32_t)op->bytes;
-    r.tile_blocks = op->tile_blocks;
-    r.row128_block = op->row128_block;
-    r.audio_bytes = (uint32_t)((uint64_t)audio_samples * (uint64_t)channels * sample_bytes(fmt));
-    r.audio = d_audio;
-    r.items = e->d_items;
-    r.items_win = e->d_items_win;
-    r.win = e->d_win;
-    r.W = W;
-    r.n_in = chunk;
-    r.hopq = (uint32_t)hop >> 2;
-    r.fmt = fmt;
-    r.channels = channels;
-    vadk::StepParams p = e->base;
-    p.wstream = e->d_wstream16;
-    p.wstream_bytes = (uint32_t)e->wbytes16;
-    p.wstream_x = e->d_wstream16x;
-    p.wstream_x_bytes = (uint32_t)e->wbytes16x;
-    p.wstream_y = e->d_wstream16y;
-    p.wstream_y_bytes = (uint32_t)e->wbytes16y;
-    std::memcpy(p.sect, e->sect16, sizeof p.sect);
-    p.slots = nullptr;
-    p.frames = e->d_win;
-    p.probs = d_probs;
-    p.events = d_events;
-    p.seg_frames = d_seg;
-    p.fmt = VAD_FMT_F32;
-    p.thresh = thr;
-    vadk::ScanArgs a{};
-    a.hopq = VAD_FRAME_SAMPLES / 4;
-    a.t0 = 0;
-    a.channels = 1;
-    for (int t0 = 0; t0 < maxf; t0 += W) {
-        while (live > 0 && it[live - 1].nframes <= t0) --live;
-        r.live = (int32_t)live;
-        r.t0 = t0;
-        hipError_t rr = vadk_launch_scan_resample(&r, s);
-        if (rr != hipSuccess) return e->hip_fail(rr, "kernel launch (scan resample)");
-        p.n = (int32_t)live;
-        p.T = std::min(W, maxf - t0);
-        a.audio_bytes = (uint32_t)(live * (size_t)W * 2048u);
-        rr = vadk_launch_silero_v5_scan16(&p, e->d_items_win, &a, s);
-        if (rr != hipSuccess) return e->hip_fail(rr, "kernel launch (scan)");
-        e->steps += 1;
-    }
-    e->frames += total;
-    return VAD_OK;
-}
-
-// a planned rate scan of host audio (vad_scan_rate, vad_scan_rate_segments): the block crosses the link once, in its wire format; the
-// launches write the engine's own d_probs / d_events / d_seg.  resident: the block stays as a RATE block of sr_in for
-// vad_scan_rate_cut(audio = NULL) - never as a block of vad_scan_cut's, whose positions and hop count samples at the engine's rate
-int scan_rate_upload_launch(vad_engine *e, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt, int chunk,
-                            int32_t sr_in, int32_t hop, float denoise_thresh, int64_t total, bool resident) {
-    const size_t ab = (size_t)audio_samples * (size_t)channels * sample_bytes(frame_fmt);
-    e->audio_resident = false;
-    if (int rc = ensure(e, e->d_audio, e->d_audio_cap, ab + 16)) return rc;
-    if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
-    if (int rc = ensure(e, e->d_probs, e->d_probs_cap, sizeof(float) * (size_t)total)) return rc;
-    if (int rc = ensure(e, e->d_events, e->d_events_cap, (size_t)total)) return rc;
-    if (int rc = ensure(e, e->d_seg, e->d_seg_cap, sizeof(int32_t) * (size_t)total)) return rc;
-    HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, ab, hipMemcpyHostToDevice, e->stream));
-    if (resident) {
-        e->audio_resident = true;            // whatever becomes of the launches, as in scan_upload_launch
-        e->audio_bytes = ab; e->audio_channels = channels; e->audio_fmt = frame_fmt; e->audio_rate = sr_in;
-    }
-    return scan_rate_launches(e, e->d_audio, audio_samples, channels, frame_fmt, chunk, hop, denoise_thresh, e->d_probs, e->d_events, e->d_seg, total,
-                              e->stream);
-}
-
-}  // namespace
-
-int64_t vad_scan_rate_frame_count(const vad_engine *e, int64_t nsamples, int32_t sr_in, int32_t hop) {
-    if (!e || hop < 1 || nsamples < 0) return -1;
-    const int chunk = sr_in == 16000 ? e->frame_samples : resample_chunk_len(sr_in);
-    if (chunk == 0) return -1;
-    return scan_frames(nsamples, chunk, hop);
-}
-
-int vad_scan_rate(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
-                  int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, const int64_t *out_start, float *probs_out,
-                  uint8_t *events_out, int32_t *seg_frames_out) {
-    static const char *who = "vad_scan_rate";
-    if (!e) return VAD_ERR_INVALID_ARG;
-    int chunk = 0;
-    {
-        std::lock_guard<std::mutex> lk(e->mu);
-        if (int rc = scan_rate_check(e, who, sr_in, &chunk)) return rc;
-    }
-    if (chunk == 0)
-        return scan_host(e, who, items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, out_start, probs_out, events_out,
-                         seg_frames_out);
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
-    int64_t total = 0;
-    const int64_t base = (n > 0 && out_start) ? out_start[0] : 0;
-    if (base < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start[0] is negative", who);
-    if (int rc = scan_plan(e, who, items, n, audio_samples, channels, frame_fmt, hop, out_start, base, &total, nullptr, chunk)) return rc;
-    if (total == 0) return VAD_OK;
-    if (!audio || !probs_out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    // the block crosses the link once, in its wire format, and no block stays: vad_scan_rate leaves nothing to cut
-    if (int rc = scan_rate_upload_launch(e, n, audio, audio_samples, channels, frame_fmt, chunk, sr_in, hop, denoise_thresh, total, false)) return rc;
-    HIP_TRY(e, hipMemcpyAsync(probs_out + base, e->d_probs, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost, e->stream));
-    if (events_out) HIP_TRY(e, hipMemcpyAsync(events_out + base, e->d_events, (size_t)total, hipMemcpyDeviceToHost, e->stream));
-    if (seg_frames_out) HIP_TRY(e, hipMemcpyAsync(seg_frames_out + base, e->d_seg, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    return VAD_OK;
-}
-
-int vad_scan_rate_device(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
-                         int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, const int64_t *out_start, float *d_probs,
-                         uint8_t *d_events, int32_t *d_seg_frames, void *stream) {
-    static const char *who = "vad_scan_rate_device";
-    if (!e) return VAD_ERR_INVALID_ARG;
-    int chunk = 0;
-    {
-        std::lock_guard<std::mutex> lk(e->mu);
-        if (int rc = scan_rate_check(e, who, sr_in, &chunk)) return rc;
-    }
-    if (chunk == 0)
-        return scan_dev(e, who, who, items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, out_start, d_probs, d_events,
-                        d_seg_frames, stream);
-    std::lock_guard<std::mutex> lk(e->mu);
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
-    int64_t total = 0;
-    if (int rc = scan_plan(e, who, items, n, audio_samples, channels, frame_fmt, hop, out_start, 0, &total, nullptr, chunk)) return rc;
-    if (total == 0) return VAD_OK;
-    if (!d_audio || !d_probs) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    const uintptr_t align = channels == 2 ? 8 : 4;
-    if (reinterpret_cast<uintptr_t>(d_audio) & (align - 1))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the audio block must be %d-byte aligned", who, (int)align);
-    if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
-    HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, s));
-    if (!e->scan_done) HIP_TRY(e, hipEventCreateWithFlags(&e->scan_done, hipEventDisableTiming));
-    const int rc = scan_rate_launches(e, d_audio, audio_samples, channels, frame_fmt, chunk, hop, denoise_thresh, d_probs, d_events, d_seg_frames, total, s);
-    // (also behind a failed launch: the copy of the table and the launches before it are on the stream)
-    HIP_TRY(e, hipEventRecord(e->scan_done, s));
-    e->scan_pending = true;
-    return rc;
-}
-
-// ---- segment tables and segment audio behind a rate scan (vad_scan_rate_segments, vad_scan_rate_cut) -------------------------------
-int vad_scan_rate_segments(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
-                           int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, vad_segment *segs_out, int64_t seg_cap,
-                           int64_t *nsegs_out) {
-    // (sr_in == 16000: scan_rate_check answers chunk = 0, and the call is vad_scan_segments under this name)
-    return scan_segments_run(e, "vad_scan_rate_segments", items, n, audio, audio_samples, channels, frame_fmt, true, sr_in, hop, denoise_thresh,
-                             segs_out, seg_cap, nsegs_out);
-}
-
-namespace {
-
-// what comes before cut_run's checks: the engine's frames and the input rate.  No model runs, so Silero V4 and
-// VAD_ENGINE_SHARED_GPU engines pass (every engine can hold a resample operator: get_resample_op); an engine whose frames are not
-// the 512 samples the operator writes - an 8 kHz sub-model - does not.  *chunk = 0: 16 kHz, the call is vad_scan_cut.
-int rate_cut_check(vad_engine *e, const char *who, int32_t sr_in, int *chunk) {
-    if (e->frame_samples != VAD_FRAME_SAMPLES || e->sample_rate != 16000)
-        return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s: this engine runs an 8 kHz sub-model on %d-sample frames; "
-                       "resampled recordings need the 16 kHz one", who, e->frame_samples);
-    return scan_rate_check(e, who, sr_in, chunk);
-}
-
-}  // namespace
-
-int64_t vad_rate_cut_samples(const vad_engine *e, int64_t nframes, int32_t sr_in, int32_t hop, int32_t layout) {
-    if (sr_in == 16000) return vad_cut_samples(e, nframes, hop, layout);
-    const int chunk = resample_chunk_len(sr_in);
-    if (!e || chunk == 0 || nframes < 1 || hop < 4 || (hop & 3) || (layout != VAD_CUT_FRAMES && layout != VAD_CUT_RANGE)) return -1;
-    if (nframes > (INT64_MAX >> 1) / std::max<int64_t>(hop, chunk)) return -1;
-    return cut_samples(chunk, nframes, hop, layout, VAD_FRAME_SAMPLES);
-}
-
-int vad_scan_rate_cut(vad_engine *e, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt,
-                      int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *out, int64_t out_samples) {
-    static const char *who = "vad_scan_rate_cut";
-    if (!e) return VAD_ERR_INVALID_ARG;
-    int chunk = 0;
-    {
-        std::lock_guard<std::mutex> lk(e->mu);
-        if (int rc = rate_cut_check(e, who, sr_in, &chunk)) return rc;
-    }
-    return cut_run<false>(e, who, items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, out, out_samples, nullptr,
-                          chunk, sr_in);
-}
-
-int vad_scan_rate_cut_device(vad_engine *e, const vad_cut_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
-                             int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *d_out,
-                             int64_t out_samples, void *stream) {
-    static const char *who = "vad_scan_rate_cut_device";
-    if (!e) return VAD_ERR_INVALID_ARG;
-    int chunk = 0;
-    {
-        std::lock_guard<std::mutex> lk(e->mu);
-        if (int rc = rate_cut_check(e, who, sr_in, &chunk)) return rc;
-    }
-    return cut_run<true>(e, who, items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, d_out, out_samples,
-                         stream, chunk, sr_in);
-}
+}  // extern "C"
 
 // ---- AudioUtils.resample_audio for any (length, rates): whole-array Fourier resampling, operator evaluated on the fly -----
 namespace {
@@ -2544,6 +2527,8 @@ int rsg_run(vad_engine *e, const void *d_in, int in_f64, int64_t rows, int64_t n
 
 }  // namespace
 
+extern "C" {
+
 int vad_resample_generic(vad_engine *e, const void *in, int in_f64, int64_t rows, int64_t n_in, int64_t n_out, float *out) {
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
@@ -2600,6 +2585,8 @@ int vad_debug_resample_generic_entries(int64_t n_in, int64_t n_out, int64_t m0, 
         for (int64_t n = 0; n < n_in; ++n) R[(size_t)(m - m0) * (size_t)n_in + (size_t)n] = vadk::rsg_entry(t, m, n);
     return VAD_OK;
 }
+
+}  // extern "C"
 
 // ---- one tick for streams at other input rates: resample on the GPU -> model step, chained on the device -----------------
 namespace {
@@ -2662,14 +2649,7 @@ int step_rates_enqueue(vad_engine *e, int32_t nseg, const float *const *d_in, co
         }
         rp.nseg = ns;
         rp.total = vstart;
-        vadk::StepParams p = e->base;
-        p.wstream = e->d_wstream16;
-        p.wstream_bytes = (uint32_t)e->wbytes16;
-        p.wstream_x = e->d_wstream16x;
-        p.wstream_x_bytes = (uint32_t)e->wbytes16x;
-        p.wstream_y = e->d_wstream16y;
-        p.wstream_y_bytes = (uint32_t)e->wbytes16y;
-        std::memcpy(p.sect, e->sect16, sizeof p.sect);
+        vadk::StepParams p = params16(e, e->base);
         p.slots = d_slots;
         p.frames = nullptr;
         p.probs = d_probs;
@@ -2723,6 +2703,8 @@ int step_rates_enqueue(vad_engine *e, int32_t nseg, const float *const *d_in, co
     return launch(e, p, s);
 }
 }  // namespace
+
+extern "C" {
 
 int vad_step_rates_device(vad_engine *e, int32_t nseg, const float *const *d_in, const int64_t *n, const int32_t *sr_in,
                           const int32_t *d_slots, float denoise_thresh, float *d_probs, uint8_t *d_events, int32_t *d_seg_frames,
@@ -2779,6 +2761,8 @@ int vad_step_rates(vad_engine *e, int32_t nseg, const float *const *in, const in
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     return VAD_OK;
 }
+
+}  // extern "C"
 
 // ---- tick assembler: the multi-stream caller's side of vad_step_events, in C ---------------------------------------------
 namespace {
@@ -2864,6 +2848,8 @@ int tick_push_locked(vad_engine *e, int64_t slot, const void *samples, int32_t n
     return VAD_OK;
 }
 }  // namespace
+
+extern "C" {
 
 // G.711 frames are decoded here, on the host, on push: they join the VAD_FMT_I16_32768 groups, so the tick's groups, its result
 // layout, the segment arena and the WAV payload are what they are for a client that sent the decoded PCM16 itself
@@ -3096,11 +3082,15 @@ int vad_tick_pending(vad_engine *e, int64_t slot, int64_t *frames) {
     return VAD_OK;
 }
 
+}  // extern "C"
+
 // ---- a stream's segment audio as bytes: what moves with vad_stream_save when a session changes engines ------------------------
 namespace {
 struct SegBlobHeader { uint32_t magic, active; uint32_t nruns[3]; uint32_t pad; uint64_t bytes[3]; };
 constexpr uint32_t SEG_BLOB_MAGIC = 0x31474553u;       // "SEG1"
 }  // namespace
+
+extern "C" {
 
 int vad_tick_segment_save(vad_engine *e, int64_t slot, void *buf, int64_t cap, int64_t *nbytes) {
     if (!e || !nbytes) return VAD_ERR_INVALID_ARG;
@@ -3184,6 +3174,8 @@ int vad_tick_segment_restore(vad_engine *e, int64_t slot, const void *buf, int64
     return VAD_OK;
 }
 
+}  // extern "C"
+
 namespace {
 // the HIP half of a tick: copies in, launches, results back (mu held).  Fills the result pointers on success.
 int tick_execute(vad_engine *e, vad_engine::TickBuf *tbs, float denoise_thresh, vad_tick_result *out, int64_t total, size_t frame_total,
@@ -3240,6 +3232,8 @@ int tick_execute(vad_engine *e, vad_engine::TickBuf *tbs, float denoise_thresh, 
     return VAD_OK;
 }
 }  // namespace
+
+extern "C" {
 
 int vad_tick_run(vad_engine *e, float denoise_thresh, vad_tick_result *out) {
     if (!e || !out || out->struct_size < sizeof(vad_tick_result)) return VAD_ERR_INVALID_ARG;

@@ -150,6 +150,28 @@ def test_refusals_have_a_status_and_a_message(lib, make_engine):
     assert (probs == np.float32(-7.0)).all()
 
 
+def test_a_call_with_several_faults_gets_the_first_refusal_of_the_plan(lib, make_engine):
+    """The order of the plan's checks is behaviour: frame format, channels, max_streams, hop, the 2 GiB limit, then the items.
+    Every fault at once, then one mended at a time."""
+    eng = make_engine(max_streams=2)
+    slots = [int(s) for s in eng.open_streams(2)]
+    x = np.zeros((64, 2), np.float32)
+    items = [(slots[0], 2, 16, 0), (slots[1], 0, 16, 0), (slots[0], 0, 16, 0)]     # three recordings, the first at an odd sample
+    faults = dict(fmt=9, channels=3, n=3, hop=6, audio_samples=1 << 30)
+    mended = dict(fmt=FMT["f32"], channels=2, n=2, hop=256, audio_samples=64)
+    inv = _ffi.VAD_ERR_INVALID_ARG
+    for key, pattern in (("fmt", "unknown frame format 9"), ("channels", "channels = 3"), ("n", "3 recordings, max_streams = 2"),
+                         ("hop", "hop = 6 must be"), ("audio_samples", "exceed the 2 GiB"), (None, "starts at sample 2")):
+        for device in (False, True):
+            kw = faults
+            rc, msg, probs, _, _ = _raw(lib, eng, items[:kw["n"]], x, kw["channels"], kw["fmt"], kw["hop"], [0] * (kw["n"] + 1), n_out=4,
+                                        audio_samples=kw["audio_samples"], device=device)
+            assert rc == inv and re.search(pattern, msg), (key, device, rc, msg)
+            assert (probs == np.float32(-7.0)).all()
+        if key:
+            faults = dict(faults, **{key: mended[key]})
+
+
 @pytest.mark.parametrize("kw", [dict(version=4), dict(shared_gpu=True)], ids=["v4", "shared_gpu"])
 def test_v4_and_shared_gpu_engines_are_unsupported(lib, make_engine, kw):
     other = make_engine(**kw)

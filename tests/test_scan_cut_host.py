@@ -176,6 +176,29 @@ def test_refusals_have_a_message_and_write_nothing(lib, make_engine):
     assert lib.vad_scan_cut(None, None, 0, None, 0, 1, 0, 256, -1.0, 0, 0, None, 0) == INV
 
 
+def test_a_call_with_several_faults_gets_the_first_refusal(lib, make_engine):
+    """The order of the checks is behaviour: frame format, channels, layout, out_fmt, hop, the 2 GiB limit, the segments, the
+    output pointer, and last the device form's audio alignment.  Every fault at once, then one mended at a time."""
+    eng = make_engine()
+    base = np.zeros(2 * 512 + 16, np.uint8)
+    odd = base[(4 - base.ctypes.data) % 8:][:2 * 512]          # one frame of two-channel G.711, 4 bytes off an 8-byte boundary
+    faults = dict(fmt=9, channels=3, layout=2, out_fmt=2, hop=6, audio_samples=1 << 30, items=[(2, 0, 1, 0, 0)])
+    mended = dict(fmt=FMT["ulaw"], channels=2, layout=RANGE, out_fmt=PCM16, hop=8, audio_samples=512, items=[(0, 0, 1, 0, 0)])
+    order = (("fmt", "unknown frame format 9"), ("channels", "channels = 3"), ("layout", "layout = 2"), ("out_fmt", "out_fmt = 2"),
+             ("hop", "hop = 6 must be"), ("audio_samples", "exceed the 2 GiB"), ("items", "starts at sample 2"),
+             (None, "the audio block must be 8-byte aligned"))
+    for device in (False, True):
+        kw = dict(faults)
+        for key, pattern in order:
+            if key is None and not device:
+                break                                           # host memory needs no alignment
+            rc, msg, out = raw_cut(lib, eng, kw["items"], odd, kw["channels"], kw["fmt"], kw["hop"], kw["layout"], kw["out_fmt"], 512,
+                                   audio_samples=kw["audio_samples"], device=device)
+            assert rc == INV and re.search(pattern, msg) and untouched(out), (key, device, rc, msg)
+            if key:
+                kw[key] = mended[key]
+
+
 # ---- the resident block -----------------------------------------------------------------------------------------------
 def test_null_audio_cuts_the_block_the_last_scan_uploaded(lib, make_engine):
     eng = make_engine()

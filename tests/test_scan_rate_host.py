@@ -178,6 +178,16 @@ def test_refusals_have_a_status_the_functions_name_and_write_nothing(lib, make_e
                 assert _untouched(probs, ev, seg)
 
 
+def test_the_rate_is_settled_before_the_plan_checks_anything(lib, make_engine):
+    """A call with an unsupported rate AND arguments the plan refuses hears about the rate, on both entry points."""
+    eng = make_engine()
+    a = int(eng.open_streams(1)[0])
+    x = np.zeros(2048, np.float32)
+    for device in (False, True):
+        rc, msg, probs, ev, seg = _raw(lib, eng, [(a, 2, 1536)], x, 9, 44100, 6, [0, 1], channels=3, device=device)
+        assert rc == UNSUPPORTED and "supported input rates" in msg and _untouched(probs, ev, seg), (device, rc, msg)
+
+
 def _ragged(chunk, hop, kind, seed, two=False, counts=None):
     """37 recordings with 0, 1 and up to 23 chunks in no order of length, most with a tail that is dropped; every chunk's first
     sample is its own value -> (recordings, per recording the float32 values of the first samples, decoded: [chunks] or [chunks, 2])"""
