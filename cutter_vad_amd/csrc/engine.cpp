@@ -44,6 +44,9 @@ extern "C" hipError_t vadk_launch_silero_v5_scan16(const vadk::StepParams *p, co
                                                    hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_cut(const vadk::CutArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_segments(const vadk::SegArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_seg_stats(const vadk::SegArgs *a, uint32_t most, hipStream_t stream);
+extern "C" hipError_t vadk_launch_reseg_count(const vadk::ResegArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_reseg_fill(const vadk::ResegArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_resample(const vadk::ScanResampleArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_cut_resample(const vadk::CutResampleArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_resample(const vadk::ResampleParams *p, hipStream_t stream);
@@ -176,6 +179,13 @@ struct vad_engine {
     long long *d_nsegs = nullptr; size_t d_nsegs_cap = 0;
     vadk::SegRecord *d_segtab = nullptr; size_t d_segtab_cap = 0;
     int64_t segtab_count = -1;               // records of the table in d_segtab; -1: none
+    // vad_resegment_device / vad_scan_resegment: the replay's work area (reseg_launches lays it out; reseg_up = the part that was
+    // uploaded, as it was), vad_scan_resegment's own table, and the mark that d_probs / d_events / seg_out_start hold the results of
+    // a vad_scan_segments / vad_scan_rate_segments: scan_segments_run sets it, whatever writes or reallocates the two arrays clears it
+    uint8_t *d_reseg = nullptr; size_t d_reseg_cap = 0;
+    std::vector<uint8_t> reseg_up;
+    vadk::SegRecord *d_resegtab = nullptr; size_t d_resegtab_cap = 0;
+    bool scan_results = false;
     // G.711 frames expanded to int16 for the kernels whose loaders do not decode them (launch())
     int16_t *d_g711 = nullptr; size_t d_g711_cap = 0;
     // small calls (a few streams: the one-wrapper-per-client pattern): ONE pinned block in, ONE pinned block out
@@ -664,6 +674,7 @@ int step_host(vad_engine *e, const int64_t *slots, int64_t n, int32_t T, const v
     if (int rc = check_call_size(e, n, T, fmt)) return rc;
     if (int rc = check_slots(e, slots, n)) return rc;
     HIP_TRY(e, hipSetDevice(e->device));
+    e->scan_results = false;
     const size_t fb = frame_bytes(e, fmt) * (size_t)n * T;
     // ---- small calls: frames + slots travel as one pinned block, probs + seg + events come back as one; one
     //      synchronisation.  (The general path below issues 2 pageable H2D copies, waits, launches, 3 D2H copies, waits.)
@@ -870,7 +881,7 @@ void vad_engine_destroy(vad_engine *e) {
     weights_release(e->d_wstream16);
     weights_release(e->d_wstream16x);
     weights_release(e->d_wstream16y);
-    void *bufs[] = {e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots, e->d_g711,
+    void *bufs[] = {e->d_reseg, e->d_resegtab, e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots, e->d_g711,
                     e->d_audio, e->d_items, e->d_win, e->d_items_win, e->d_cut, e->d_cut_out, e->d_segwork, e->d_nsegs, e->d_segtab, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
@@ -1472,6 +1483,7 @@ int scan_upload_launch(vad_engine *e, int64_t n, const void *audio, int64_t audi
                        int32_t sr_in, int32_t hop, float denoise_thresh, int64_t total, bool resident) {
     const size_t ab = (size_t)audio_samples * (size_t)channels * sample_bytes(frame_fmt);
     e->audio_resident = false;
+    e->scan_results = false;
     if (int rc = ensure(e, e->d_audio, e->d_audio_cap, ab + 16)) return rc;
     if (int rc = ensure(e, e->d_items, e->d_items_cap, sizeof(vadk::ScanItem) * (size_t)n)) return rc;
     if (int rc = ensure(e, e->d_probs, e->d_probs_cap, sizeof(float) * (size_t)total)) return rc;
@@ -2051,6 +2063,7 @@ int scan_segments_run(vad_engine *e, const char *who, const vad_scan_ch_item *it
     if (int rc = scan_wait(e)) return rc;
     // the CSR positions the caller of vad_scan_channels would have passed are the plan's to make: the items packed in their order
     std::vector<int64_t> &start = e->seg_out_start;
+    e->scan_results = false;                 // the plan rewrites the positions
     int64_t total = 0;
     if (int rc = scan_plan(e, who, items, n, audio_samples, channels, frame_fmt, hop, (const int64_t *)nullptr, 0, &total, &start, chunk)) return rc;
     if (seg_cap < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: seg_cap = %lld: bad count", who, (long long)seg_cap);
@@ -2059,6 +2072,7 @@ int scan_segments_run(vad_engine *e, const char *who, const vad_scan_ch_item *it
     e->segtab_count = -1;
     if (total == 0) {                        // nothing to scan: an empty table
         e->segtab_count = 0;
+        e->scan_results = true;
         *nsegs_out = 0;
         return VAD_OK;
     }
@@ -2082,6 +2096,7 @@ int scan_segments_run(vad_engine *e, const char *who, const vad_scan_ch_item *it
         HIP_TRY(e, hipStreamSynchronize(e->stream));
     }
     e->segtab_count = count;
+    e->scan_results = true;
     *nsegs_out = count;
     return VAD_OK;
 }
@@ -2163,6 +2178,153 @@ int vad_scan_segments_read(vad_engine *e, int64_t first, int64_t count, vad_segm
     return VAD_OK;
 }
 
+}  // extern "C"
+
+// ---- segment tables at other thresholds, from a scan's per-frame results (vad_resegment_device, vad_scan_resegment) -----------
+namespace {
+
+static_assert(VAD_RESEGMENT_MAX_SETS == vadk::RESEG_MAX_SETS, "the header's limit is the kernel's");
+
+// what both entry points check about the sets and the capacity
+int reseg_check_sets(vad_engine *e, const char *who, const vad_thresholds *t, int64_t nt, int64_t seg_cap) {
+    if (nt < 1 || nt > vadk::RESEG_MAX_SETS)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: nt = %lld: 1 .. %d threshold sets in one call", who, (long long)nt,
+                       vadk::RESEG_MAX_SETS);
+    if (seg_cap < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: seg_cap = %lld: bad count", who, (long long)seg_cap);
+    if (!t) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    return VAD_OK;
+}
+
+// The first half of a replay on `s`: out_start (checked as seg_launches wants it), the sets and their lane numbers go up in one
+// block; the initial state machines are built by the kernel that serves vad_stream_open and vad_stream_set_thresholds - default,
+// then the set's thresholds - on nt scratch records of the work area (no stream's slot, no (h, c)); then the count and the prefix.
+// d_set_start == nullptr: the counts go to the work area (a->set_start says where).
+int reseg_count(vad_engine *e, const uint8_t *d_events, const float *d_probs, const int64_t *out_start, int64_t n, const vad_thresholds *t,
+                int64_t nt, long long *d_set_start, hipStream_t s, vadk::ResegArgs *a) {
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_slots = up16(sizeof(int32_t) * (size_t)(n + 1)), o_thr = o_slots + up16(sizeof(int32_t) * (size_t)nt);
+    const size_t up_bytes = o_thr + up16(sizeof(vad_thresholds) * (size_t)nt), o_sm = up_bytes;
+    const size_t o_set = o_sm + up16(sizeof(vadk::SmSlot) * (size_t)nt), o_cnt = o_set + up16(sizeof(long long) * (size_t)(nt + 1));
+    if (int rc = ensure(e, e->d_reseg, e->d_reseg_cap, o_cnt + sizeof(uint32_t) * (size_t)nt * (size_t)n + 16)) return rc;
+    e->reseg_up.assign(up_bytes, 0);
+    int32_t *h_start = reinterpret_cast<int32_t *>(e->reseg_up.data()), *h_slots = reinterpret_cast<int32_t *>(e->reseg_up.data() + o_slots);
+    for (int64_t i = 0; i <= n; ++i) h_start[i] = n > 0 ? (int32_t)out_start[i] : 0;
+    for (int64_t k = 0; k < nt; ++k) h_slots[k] = (int32_t)k;
+    std::memcpy(e->reseg_up.data() + o_thr, t, sizeof(vad_thresholds) * (size_t)nt);
+    HIP_TRY(e, hipMemcpyAsync(e->d_reseg, e->reseg_up.data(), up_bytes, hipMemcpyHostToDevice, s));
+    vadk::SmSlot *d_sm0 = reinterpret_cast<vadk::SmSlot *>(e->d_reseg + o_sm);
+    HIP_TRY(e, vadk_launch_slot_control(d_sm0, nullptr, reinterpret_cast<const int32_t *>(e->d_reseg + o_slots), (int)nt,
+                                        CTL_DEFAULT_SM | CTL_SET_THRESHOLDS, &kDefaultSm,
+                                        reinterpret_cast<const vad_thresholds *>(e->d_reseg + o_thr), (int)nt, s));
+    int shift = 0;
+    while ((int64_t(1) << shift) < nt) ++shift;
+    *a = vadk::ResegArgs{};
+    a->events = d_events;
+    a->probs = d_probs;
+    a->out_start = reinterpret_cast<const int32_t *>(e->d_reseg);
+    a->sm0 = d_sm0;
+    a->cnt = reinterpret_cast<uint32_t *>(e->d_reseg + o_cnt);
+    a->set_start = d_set_start ? d_set_start : reinterpret_cast<long long *>(e->d_reseg + o_set);
+    a->n = (int32_t)n;
+    a->nt = (int32_t)nt;
+    a->set_shift = shift;
+    const hipError_t r = vadk_launch_reseg_count(a, s);
+    if (r != hipSuccess) return e->hip_fail(r, "kernel launch (resegment count)");
+    return VAD_OK;
+}
+
+// ... and the second: the records into d_segs (room for seg_cap of them), then their statistics; `most` bounds the records written
+int reseg_fill(vad_engine *e, vadk::ResegArgs *a, vadk::SegRecord *d_segs, int64_t seg_cap, int64_t most, hipStream_t s) {
+    a->segs = d_segs;
+    a->seg_cap = (uint32_t)std::min<int64_t>(seg_cap, INT32_MAX);
+    hipError_t r = vadk_launch_reseg_fill(a, s);
+    if (r != hipSuccess) return e->hip_fail(r, "kernel launch (resegment fill)");
+    vadk::SegArgs st{};
+    st.events = a->events;
+    st.probs = a->probs;
+    st.out_start = a->out_start;
+    st.segs = d_segs;
+    st.nsegs = a->set_start + a->nt;
+    st.seg_cap = a->seg_cap;
+    st.n = a->n;
+    r = vadk_launch_seg_stats(&st, (uint32_t)std::min<int64_t>(most, (int64_t)a->seg_cap), s);
+    if (r != hipSuccess) return e->hip_fail(r, "kernel launch (segment statistics)");
+    return VAD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vad_resegment_device(vad_engine *e, const uint8_t *d_events, const float *d_probs, const int64_t *out_start, int64_t n,
+                         const vad_thresholds *t, int64_t nt, vad_segment *d_segs, int64_t seg_cap, int64_t *d_set_start, void *stream) {
+    static const char *who = "vad_resegment_device";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    if (int rc = reseg_check_sets(e, who, t, nt, seg_cap)) return rc;
+    if (n < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n = %lld: bad count", who, (long long)n);
+    if (n * nt > INT32_MAX)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %lld items x %lld sets: more than 2^31 - 1 replays in one call", who,
+                       (long long)n, (long long)nt);
+    if ((n > 0 && !out_start) || !d_set_start || (seg_cap > 0 && !d_segs))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if (n > 0 && out_start[0] < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start[0] is negative", who);
+    for (int64_t i = 0; i < n; ++i)
+        if (out_start[i + 1] < out_start[i])
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start decreases at item %lld (%lld after %lld)", who, (long long)i,
+                           (long long)out_start[i + 1], (long long)out_start[i]);
+    const int64_t total = n > 0 ? out_start[n] : 0;
+    if (total > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 frames in one call", who);
+    if (total > 0 && (!d_events || !d_probs)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if ((reinterpret_cast<uintptr_t>(d_events) & 15) || (reinterpret_cast<uintptr_t>(d_segs) & 15))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the events and the segment table must be 16-byte aligned", who);
+    if (reinterpret_cast<uintptr_t>(d_probs) & 3) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: probs must be 4-byte aligned", who);
+    if (reinterpret_cast<uintptr_t>(d_set_start) & 7)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the set counts must be 8-byte aligned", who);
+    vadk::ResegArgs a;
+    int rc = reseg_count(e, d_events, d_probs, out_start, n, t, nt, reinterpret_cast<long long *>(d_set_start), s, &a);
+    // a segment has a frame that starts it and a later one that ends it: at most total / 2 records per set
+    if (rc == VAD_OK && seg_cap > 0) rc = reseg_fill(e, &a, reinterpret_cast<vadk::SegRecord *>(d_segs), seg_cap, (total / 2 + 1) * nt, s);
+    // the launches read the engine's work area: the next scan, cut, extraction or replay waits for them, as behind vad_scan_device
+    if (int rc2 = scan_mark_pending(e, s)) return rc2;
+    return rc;
+}
+
+int vad_scan_resegment(vad_engine *e, const vad_thresholds *t, int64_t nt, vad_segment *segs_out, int64_t seg_cap, int64_t *set_start_out) {
+    static const char *who = "vad_scan_resegment";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    if (int rc = reseg_check_sets(e, who, t, nt, seg_cap)) return rc;
+    if (!set_start_out || (seg_cap > 0 && !segs_out)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if (!e->scan_results || e->seg_out_start.empty())
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: no scan results are resident: the engine's last vad_scan_segments or "
+                                            "vad_scan_rate_segments failed, or a later call has reused its per-frame arrays", who);
+    const int64_t n = (int64_t)e->seg_out_start.size() - 1;
+    std::vector<long long> counts((size_t)nt + 1, 0);
+    if (e->seg_out_start[(size_t)n] > 0) {
+        vadk::ResegArgs a;
+        if (int rc = reseg_count(e, e->d_events, e->d_probs, e->seg_out_start.data(), n, t, nt, nullptr, e->stream, &a)) return rc;
+        HIP_TRY(e, hipMemcpyAsync(counts.data(), a.set_start, sizeof(long long) * counts.size(), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(e, hipStreamSynchronize(e->stream));
+        if (counts[(size_t)nt] > INT32_MAX)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %lld records: more than 2^31 - 1 in one call", who, counts[(size_t)nt]);
+        const int64_t take = std::min<int64_t>(counts[(size_t)nt], seg_cap);
+        if (take > 0) {
+            if (int rc = ensure(e, e->d_resegtab, e->d_resegtab_cap, sizeof(vadk::SegRecord) * (size_t)take)) return rc;
+            if (int rc = reseg_fill(e, &a, e->d_resegtab, take, take, e->stream)) return rc;
+            HIP_TRY(e, hipMemcpyAsync(segs_out, e->d_resegtab, sizeof(vad_segment) * (size_t)take, hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(e, hipStreamSynchronize(e->stream));
+        }
+    }
+    for (int64_t k = 0; k <= nt; ++k) set_start_out[k] = counts[(size_t)k];
+    return VAD_OK;
+}
+
 // ---- pipelined host ingest ---------------------------------------------------------------------------------------
 int vad_step_submit(vad_engine *e, const int64_t *slots, int64_t n, int32_t T, const void *frames, int fmt, float thr,
                     int64_t *ticket) {
@@ -2178,6 +2340,7 @@ int vad_step_submit(vad_engine *e, const int64_t *slots, int64_t n, int32_t T, c
                        vad_engine::PIPE_DEPTH, (long long)pb.ticket);
     if (int rc = check_slots(e, slots, n)) return rc;
     HIP_TRY(e, hipSetDevice(e->device));
+    e->scan_results = false;
     if (!pb.copied) {
         HIP_TRY(e, hipEventCreateWithFlags(&pb.copied, hipEventDisableTiming));
         HIP_TRY(e, hipEventCreateWithFlags(&pb.done, hipEventDisableTiming));
@@ -2737,6 +2900,7 @@ int vad_step_rates(vad_engine *e, int32_t nseg, const float *const *in, const in
     if (total == 0) return VAD_OK;
     if (int rc = check_slots(e, slots, total)) return rc;
     HIP_TRY(e, hipSetDevice(e->device));
+    e->scan_results = false;
     if (int rc = ensure(e, e->d_rs_in, e->d_rs_in_cap, sizeof(float) * in_floats)) return rc;
     if (int rc = ensure(e, e->d_probs, e->d_probs_cap, sizeof(float) * total)) return rc;
     if (int rc = ensure(e, e->d_events, e->d_events_cap, (size_t)total)) return rc;
@@ -3251,6 +3415,7 @@ int vad_tick_run(vad_engine *e, float denoise_thresh, vad_tick_result *out) {
     out->group_start[vad_engine::TICK_GROUPS] = 0;
     // `mu` first (lock order), for the whole tick: slots cannot be opened or closed under it
     std::lock_guard<std::mutex> lk(e->mu);
+    e->scan_results = false;
     int b;
     vad_engine::TickBuf *tbs;
     {   // swap the staging buffers; every slot that has more frames waiting gets its next one into the new buffer, in the order
@@ -3634,6 +3799,7 @@ int vad_debug_sm_replay(vad_engine *e, int64_t slot, const float *probs, int64_t
     if (slot < 0 || slot >= e->max_streams || !e->open[(size_t)slot])
         return e->fail(VAD_ERR_BAD_SLOT, "slot %lld is not an open stream", (long long)slot);
     HIP_TRY(e, hipSetDevice(e->device));
+    e->scan_results = false;
     if (int rc = ensure(e, e->d_probs, e->d_probs_cap, sizeof(float) * n)) return rc;
     if (int rc = ensure(e, e->d_events, e->d_events_cap, (size_t)n)) return rc;
     if (int rc = ensure(e, e->d_seg, e->d_seg_cap, sizeof(int32_t) * n)) return rc;

@@ -177,3 +177,14 @@ extern "C" hipError_t vadk_launch_scan_segments(const SegArgs *a, hipStream_t st
     hipLaunchKernelGGL(vadk_seg_stats, dim3(blocks < 2048u ? blocks : 2048u), dim3(SEG_THREADS), 0, stream, *a);
     return hipGetLastError();
 }
+
+// the statistics alone, for a table whose item, first_frame and nframes another file's kernels wrote (csrc/scan_resegment.hip): the
+// first min(*a->nsegs, a->seg_cap) records of a->segs, from a->events, a->probs and a->out_start; `most` bounds that number on the
+// host (the grid; the kernel strides over whatever the count turns out to be)
+extern "C" hipError_t vadk_launch_seg_stats(const SegArgs *a, uint32_t most, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (most == 0 || a->seg_cap == 0) return hipSuccess;
+    const uint32_t blocks = (most + SEG_WAVES - 1) / SEG_WAVES;
+    hipLaunchKernelGGL(vadk_seg_stats, dim3(blocks < 2048u ? blocks : 2048u), dim3(SEG_THREADS), 0, stream, *a);
+    return hipGetLastError();
+}

@@ -301,6 +301,29 @@ struct SegArgs {
     int32_t n;                // items
 };
 
+// segment tables at other thresholds from a scan's per-frame results (csrc/scan_resegment.hip; vad_resegment_device,
+// vad_scan_resegment).  Thread (item i, set k) replays the accepted frames of item i through a state machine that starts as
+// sm0[k] - what a stream just opened and given the set's thresholds holds - and every END becomes one SegRecord; the records are
+// ordered by set, then item, then frame.  Sets run along the lanes, padded to the power of two 1 << set_shift, so the lanes of a
+// wave that share an item read the same addresses.  Two replays around a prefix fix the order: the first counts the ENDs of
+// (item, set) into cnt[k n + i], one workgroup turns cnt into its exclusive prefix in that order and writes set_start[0 .. nt]
+// (the records of the sets before k; [nt] = all), the second writes record j of (item, set) at cnt[k n + i] + j.
+constexpr int RESEG_THREADS = 256;
+constexpr int RESEG_MAX_SETS = 64;            // one wave holds a recording's sets
+struct ResegArgs {
+    const uint8_t *events;    // [out_start[n]]: VAD_EV_REJECTED alone is read
+    const float *probs;
+    const int32_t *out_start; // [n + 1] on the device, as SegArgs::out_start
+    const SmSlot *sm0;        // [nt]
+    uint32_t *cnt;            // [nt n]: counts, then their exclusive prefix (saturated at 2^32 - 1: no position below seg_cap)
+    SegRecord *segs;          // [seg_cap]
+    long long *set_start;     // [nt + 1]: the true counts
+    uint32_t seg_cap;         // records at positions >= seg_cap are dropped (<= 2^31 - 1)
+    int32_t n;                // items; n nt <= 2^31 - 1
+    int32_t nt;               // sets, 1 .. RESEG_MAX_SETS
+    int32_t set_shift;        // log2 of the lanes one item takes
+};
+
 // resampler launch parameters (csrc/resample.hip)
 struct ResampleSeg {
     const float *wstream;     // folded operator (pack_weights.cpp: pack_resample_operator)

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import threading
-from typing import Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -487,6 +487,39 @@ class Engine:
         start = np.ascontiguousarray(out_start, dtype=np.int64).reshape(-1)
         self._check(self._lib.vad_segments_device(self._h, d_events or None, d_seg or None, d_probs or None, _ptr(start, C.c_int64),
                                                   max(start.size - 1, 0), d_segs or None, int(seg_cap), d_nsegs or None, stream or None))
+
+    @staticmethod
+    def _threshold_sets(thresholds):
+        rows = [tuple(r) for r in thresholds]
+        return (_ffi.Thresholds * max(1, len(rows)))(*[_ffi.Thresholds(*r) for r in rows]), len(rows)
+
+    def resegment(self, thresholds) -> List[np.ndarray]:
+        """Segment tables at other thresholds from the per-frame results the last ``scan_segments`` left on the GPU
+        (``vad_scan_resegment``): no upload, no model launch, no stream touched.  ``thresholds``: a sequence of up to 64 6-tuples in
+        ``set_thresholds_many``'s order -> one table (``_ffi.SEGMENT_DTYPE``) per set, each what ``scan_segments`` returns for the
+        same recordings on freshly opened streams with that set.  The resident block stays: ``cut(audio=None)`` works on any of
+        the tables.  Call it inside ``scan_session()``, behind the ``scan_segments``: another thread's scan, or any step on this
+        engine, replaces the results (the call then raises)."""
+        sets, nt = self._threshold_sets(thresholds)
+        start = np.zeros(nt + 1, np.int64)
+        with self._scan_lock:
+            self._check(self._lib.vad_scan_resegment(self._h, sets, nt, None, 0, _ptr(start, C.c_int64)))
+            table = np.zeros(int(start[-1]), _ffi.SEGMENT_DTYPE)
+            if table.size:
+                self._check(self._lib.vad_scan_resegment(self._h, sets, nt, table.ctypes.data_as(C.POINTER(_ffi.Segment)), table.size,
+                                                         _ptr(start, C.c_int64)))
+        return [table[int(start[k]):int(start[k + 1])] for k in range(nt)]
+
+    def resegment_device(self, d_events: int, d_probs: int, out_start, thresholds, d_segs: int, seg_cap: int, d_set_start: int,
+                         stream: int = 0) -> None:
+        """``resegment`` on device pointers (integers; ``vad_resegment_device``): ``d_events`` (16-byte aligned) and ``d_probs`` as
+        ``scan_device`` wrote them, ``out_start`` the positions it returned; the first ``min(total, seg_cap)`` records - by set,
+        then item, then frame - go to ``d_segs`` (16-byte aligned, ``_ffi.SEGMENT_DTYPE``), the running counts per set to the
+        int64 ``[len(thresholds) + 1]`` at ``d_set_start``.  Asynchronous on ``stream``; every engine has it."""
+        sets, nt = self._threshold_sets(thresholds)
+        start = np.ascontiguousarray(out_start, dtype=np.int64).reshape(-1)
+        self._check(self._lib.vad_resegment_device(self._h, d_events or None, d_probs or None, _ptr(start, C.c_int64), max(start.size - 1, 0),
+                                                   sets, nt, d_segs or None, int(seg_cap), d_set_start or None, stream or None))
 
     def scan_device(self, slots, offsets, lengths, d_audio: int, audio_samples: int, d_probs: int, d_events: int = 0, d_seg: int = 0,
                     hop: Optional[int] = None, fmt: int = _ffi.VAD_FMT_F32, denoise: Optional[float] = 0.01, stream: int = 0,

@@ -46,6 +46,16 @@ def _frame_stats(probs, events, e: int, L: int) -> Tuple[float, float]:
     return float(np.float32(fixed / (p.size * 2.0 ** 30))), float(p.max())
 
 
+def _table_ranges(table, n: int, per: int, frame: int, hop: int, stats: bool) -> List[List[List]]:
+    """A segment table of ``n`` recordings with ``per`` items each (``item = recording * per + channel``) -> per recording, per
+    channel, the ranges ``(start_sample, end_sample)`` - with ``stats``: ``(start_sample, end_sample, mean_prob, max_prob)``."""
+    out = [[[] for _ in range(per)] for _ in range(n)]
+    extra = zip(table["mean_prob"].tolist(), table["max_prob"].tolist())
+    for item, rg, st in zip(table["item"].tolist(), segment_ranges(table, frame, hop), extra):
+        out[item // per][item % per].append(rg + st if stats else rg)
+    return out
+
+
 def _scan_ranges(engine, slots, recordings, per: int, frame: int, hop: int, law, denoise, channel, stats: bool = False,
                  rate: Optional[int] = None) -> List[List[List]]:
     """One scan of ``recordings`` (all 1-D or all two-channel) on ``slots`` -> per recording, per channel scanned of it (``per``),
@@ -57,11 +67,7 @@ def _scan_ranges(engine, slots, recordings, per: int, frame: int, hop: int, law,
     kw = {} if rate is None else {"sample_rate": rate}
     if hasattr(engine, "scan_segments"):
         table = engine.scan_segments(sl, recordings, hop=hop, law=law, denoise=denoise, channel=channel, **kw)
-        out = [[[] for _ in range(per)] for _ in recordings]
-        extra = zip(table["mean_prob"].tolist(), table["max_prob"].tolist())
-        for item, rg, st in zip(table["item"].tolist(), segment_ranges(table, frame, hop), extra):
-            out[item // per][item % per].append(rg + st if stats else rg)
-        return out
+        return _table_ranges(table, len(recordings), per, frame, hop, stats)
     probs, ev, seg = engine.scan(sl, recordings, hop=hop, law=law, denoise=denoise, channel=channel, **kw)
     out = []
     for p, e, g in zip(probs, ev, seg):
@@ -128,6 +134,75 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
                 engine.close_stream(int(s))
         for i, rc in zip(idx, ranges):
             out[i] = rc if split else rc[0]
+    return out
+
+
+def _thresholds_of(cfg: VADConfig) -> Tuple:
+    return (cfg.vad_start_probability, cfg.vad_end_probability, cfg.voice_start_ratio, cfg.voice_end_ratio, cfg.voice_start_frame_count,
+            cfg.voice_end_frame_count)
+
+
+def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConfig], engine=None, hop: Optional[int] = None,
+                     law: Optional[str] = None, channel="mix", stats: bool = False, sample_rate: Optional[int] = None) -> List[List]:
+    """``scan_recordings`` under several configs for the price of one scan: ``sweep_recordings(recs, cfgs, **kw)[j] ==
+    scan_recordings(recs, cfgs[j], **kw)``.  The model runs once per kind of recording (1-D, 2-D), with the first config's
+    thresholds; the segment tables of all configs then come from ONE replay of the per-frame probabilities that scan left on the
+    GPU (``Engine.resegment``, 64 configs per replay: the model's output does not depend on the thresholds).  The configs may differ
+    in the six threshold fields alone; they must agree on what the probabilities depend on - ``model_version``, ``sample_rate``,
+    ``buffer_size``, ``enable_denoising`` and ``model_path`` - or ``ConfigurationError`` names the field.  An engine object without
+    ``resegment`` is served config by config."""
+    from .pool import default_pool, resolve_model_path
+    configs = list(configs)
+    if not configs:
+        return []
+    cfg = configs[0]
+    for other in configs[1:]:
+        for field in ("model_version", "sample_rate", "buffer_size", "enable_denoising", "model_path"):
+            if getattr(other, field) != getattr(cfg, field):
+                raise ConfigurationError(field, repr(getattr(other, field)),
+                                         f"sweep_recordings: the configs of one sweep share {field} (the probabilities depend on it): "
+                                         f"{getattr(cfg, field)!r} and {getattr(other, field)!r}")
+    if engine is None:
+        engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
+    if not hasattr(engine, "resegment") or not hasattr(engine, "scan_segments"):
+        return [scan_recordings(recordings, c, engine=engine, hop=hop, law=law, channel=channel, stats=stats, sample_rate=sample_rate)
+                for c in configs]
+    split = isinstance(channel, str) and channel == "split"
+    if not (channel in ("mix", "split") if isinstance(channel, str) else isinstance(channel, (int, np.integer)) and int(channel) in (0, 1)):
+        raise ConfigurationError("channel", repr(channel), f"sweep_recordings: channel is 'mix', 0, 1 or 'split' for the whole corpus, got {channel!r}")
+    frame = engine.frame_samples
+    if cfg.buffer_size != frame:
+        raise ConfigurationError("buffer_size", repr(cfg.buffer_size), f"sweep_recordings frames at the model's frame size: buffer_size = "
+                                 f"{cfg.buffer_size}, the engine's frames have {frame} samples")
+    rate = None if sample_rate is None or int(sample_rate) == int(engine.sample_rate) else int(sample_rate)
+    if rate is not None:
+        if rate not in (8000, 16000, 24000, 48000):
+            raise ConfigurationError("sample_rate", repr(sample_rate), f"sweep_recordings: recordings at 8000, 16000, 24000 or 48000 Hz, got {sample_rate!r}")
+        frame = engine.scan_chunk_samples(rate)      # the ranges count input samples
+    hop = frame // 2 if hop is None else int(hop)
+    recordings = [np.asarray(r) for r in recordings]
+    out: List[List] = [[None] * len(recordings) for _ in configs]
+    kw = {} if rate is None else {"sample_rate": rate}
+    for two in (False, True):
+        idx = [i for i, r in enumerate(recordings) if (r.ndim == 2) == two]
+        if not idx:
+            continue
+        per = 2 if two and split else 1
+        slots = engine.open_streams(len(idx) * per)
+        try:
+            engine.set_thresholds_many(slots, _thresholds_of(cfg))
+            sl = np.asarray(slots).reshape(len(idx), per) if per == 2 else slots
+            with engine.scan_session():
+                engine.scan_segments(sl, [recordings[i] for i in idx], hop=hop, law=law, denoise=0.01 if cfg.enable_denoising else None,
+                                     channel=channel, **kw)
+                sets = [_thresholds_of(c) for c in configs]
+                tables = [t for k in range(0, len(sets), 64) for t in engine.resegment(sets[k:k + 64])]      # 64 sets per replay
+        finally:
+            for s in slots:
+                engine.close_stream(int(s))
+        for res, table in zip(out, tables):
+            for i, rc in zip(idx, _table_ranges(table, len(idx), per, frame, hop, stats)):
+                res[i] = rc if split else rc[0]
     return out
 
 

@@ -523,6 +523,56 @@ VAD_API int vad_scan_rate_cut_device(vad_engine *e, const vad_cut_item *items, i
                                      int32_t out_fmt, void *d_out, int64_t out_samples, void *stream);
 
 /*
+ * Segment tables at other thresholds, without running the model again.  The model's output does not depend on the six values of
+ * vad_thresholds: the state machine runs behind the probability head and never feeds back into (h, c).  The per-frame probabilities
+ * a scan left in device memory therefore answer every other setting, and these calls replay them through the state machine under
+ * up to VAD_RESEGMENT_MAX_SETS sets at once, on the GPU: nothing is uploaded but the sets, no model kernel runs, no stream (slot)
+ * is touched.  A threshold sweep over an archive is one scan plus one replay.
+ *   Replay rule, the same for every set k in 0 .. nt - 1 and every item i: start from the state machine of a stream that was just
+ * opened and then given t[k] (vad_stream_open, vad_stream_set_thresholds: the defaults with the six values written into them);
+ * walk the item's flat indices out_start[i] .. out_start[i + 1] - 1 in order; a frame whose event byte has VAD_EV_REJECTED set is
+ * skipped as the model kernels skip it (no step of the state machine), every other frame is one step on probs[index].  Of the
+ * events only the REJECTED bit is read - the START / END / CONTINUE bits of the scan's own thresholds are ignored, and seg_frames
+ * is not needed.  Each END at frame e with length L gives one vad_segment {item = i, first_frame = e - L + 1, nframes = L} whose
+ * counted, mean_prob and max_prob follow the vad_segment rule to the bit.
+ *   Every recording starts from a FRESH state machine here, also where the scan itself continued its slots from an earlier call:
+ * the table of set k is, byte for byte, what vad_scan_segments (or vad_scan_rate_segments) returns for the same items on freshly
+ * reset streams whose thresholds are t[k] - same records, same order, same statistics - so first_frame is never negative.
+ *   Order: by set, then item, then frame.  set_start[k] is the number of records of the sets before k and set_start[nt] the total:
+ * always the true counts.  The first min(total, seg_cap) records of that order are written; a caller that wants exact room calls
+ * once with seg_cap = 0 and again with the total (the replay is cheap: no second resident table is kept, and
+ * vad_scan_segments_read's table is not touched).
+ *   Left alone: the streams and their (h, c), vad_info.steps and vad_info.frames, the resident block of either kind
+ * (vad_scan_cut / vad_scan_rate_cut with audio = NULL work on any of the new tables), the resident segment table.
+ *
+ * vad_resegment_device: the replay on device pointers - d_events (16-byte aligned) and d_probs (4-byte aligned) as a *_device scan
+ * wrote them, out_start the host array [n + 1] of that call, d_segs (16-byte aligned, room for seg_cap records) and d_set_start
+ * (int64 [nt + 1], 8-byte aligned) on the GPU.  Enqueues on `stream` (NULL = the engine's own) and returns.  Works on every engine,
+ * Silero V4, VAD_ENGINE_SHARED_GPU and the 8 kHz sub-models included.  Like the scans, the call first waits for earlier *_device
+ * launches that read the engine's tables, and the next such call waits for this one's.
+ *   VAD_ERR_INVALID_ARG, each with a message, and nothing is written: nt < 1 or nt > VAD_RESEGMENT_MAX_SETS (the kernel puts a
+ * recording's sets in one wave); seg_cap < 0; a null t; n < 0; n * nt > 2^31 - 1; a null out_start with n > 0; a null d_set_start;
+ * a null d_segs with seg_cap > 0; an out_start that starts below 0 or decreases; out_start[n] > 2^31 - 1; a null d_events or
+ * d_probs when there are frames; a misaligned pointer.  (A total above 2^31 - 1 records cannot be known before the launches here:
+ * set_start is true all the same, and no record at a position of 2^31 - 1 or above is written.)
+ *
+ * vad_scan_resegment: the same on the per-frame results that this engine's last vad_scan_segments / vad_scan_rate_segments left in
+ * its own arrays, for the items of that call in their order; segs_out, seg_cap and set_start_out [nt + 1] are host memory.  The
+ * engine marks those arrays as a scan's results when such a call succeeds (one without frames included: every count is 0) and
+ * drops the mark in whatever writes or reallocates them - vad_step and its kin, vad_scan / vad_scan_channels / vad_scan_rate,
+ * vad_step_rates, vad_tick_run, vad_step_submit, vad_debug_sm_replay, a failed vad_scan_segments.  Without the mark:
+ * VAD_ERR_INVALID_ARG, "vad_scan_resegment: no scan results are resident".  Further VAD_ERR_INVALID_ARG, each with a message and
+ * nothing written: nt, seg_cap and t as above, a null set_start_out, a null segs_out with seg_cap > 0, a total above 2^31 - 1 records.
+ *   VAD_ABI_VERSION is unchanged: the presence of vad_scan_resegment is how a caller detects the feature.
+ */
+#define VAD_RESEGMENT_MAX_SETS 64
+VAD_API int vad_resegment_device(vad_engine *e, const uint8_t *d_events, const float *d_probs, const int64_t *out_start /*host [n + 1]*/,
+                                 int64_t n, const vad_thresholds *t, int64_t nt, vad_segment *d_segs, int64_t seg_cap,
+                                 int64_t *d_set_start /*on the GPU, [nt + 1]*/, void *stream);
+VAD_API int vad_scan_resegment(vad_engine *e, const vad_thresholds *t, int64_t nt, vad_segment *segs_out, int64_t seg_cap,
+                               int64_t *set_start_out /*[nt + 1]*/);
+
+/*
  * Pipelined host ingest.  vad_step* on host pointers are copy -> kernel -> copy -> wait; at 8 192 streams the PCIe copy is
  * 5-8 x the kernel, so a serving loop should overlap the copy of tick t+1 with the kernel of tick t:
  *

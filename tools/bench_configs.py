@@ -852,6 +852,110 @@ def scan_segments():
     return row
 
 
+def scan_resegment():
+    """A threshold sweep over an archive: VAD_SCAN_BENCH_N (default 1 024) int16 recordings of 30 s at 16 kHz in one call,
+    hop 256.  (a) Engine.scan_segments once, then Engine.resegment with 1, 8 and 64 threshold sets - the replay of the probabilities
+    the scan left on the GPU; (b) the way to the same tables without it: per set, the streams reset, the thresholds set and a full
+    Engine.scan_segments; (c) Engine.resegment_device alone on synthetic probabilities, ONE recording of 112 500 frames (an hour at
+    hop 512) under 64 sets, next to one default launch window of a scan (192 frames of the N recordings, Engine.scan_device on
+    device memory), HIP-event timed.  One warm-up, then three timed passes of each; medians, wall clock for (a) and (b)."""
+    import time
+    import numpy as np
+    N = int(os.environ.get("VAD_SCAN_BENCH_N", "1024"))
+    eng = Engine(blob(5), max_streams=max(N, 16))
+    frame, hop = eng.frame_samples, 256
+    gold = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "speech16k_i16.npz")
+    pcm = np.tile(np.load(gold)["pcm"].astype(np.int16), 3)
+    rng = np.random.default_rng(N)
+    ns = 30 * 16000
+    recs = [pcm[a:a + ns] for a in rng.integers(0, pcm.size - ns + 1, N)]
+    base = [(0.4, 0.3, 0.8, 0.95, 6, 12), (0.7, 0.7, 0.8, 0.95, 10, 50), (0.3, 0.2, 0.8, 0.95, 2, 2), (0.5, 0.35, 0.6, 0.9, 4, 57),
+            (0.85, 0.6, 0.5, 0.75, 3, 8)]
+    sets = [(a - 0.004 * (k // 5), b - 0.003 * (k // 5), c, d, m + (k // 5) % 3, n + (k // 5) % 4) for k in range(64) for a, b, c, d, m, n in [base[k % 5]]]
+    slots = eng.open_streams(N)
+    med = lambda v: float(np.median(v))
+    note = lambda what: print(f"scan_resegment: {what}", file=sys.stderr, flush=True)      # a pass of (b) takes a while
+
+    def full_scan(thr):
+        eng.reset(slots)
+        eng.set_thresholds_many(slots, thr)
+        return eng.scan_segments(slots, recs, hop=hop, denoise=0.01)
+
+    row = {"config": f"scan_resegment: {N} int16 recordings of 30 s at 16 kHz in one call, hop {hop}", "recordings": N,
+           "frames": N * eng.scan_frame_count(ns, hop), "passes": 3}
+    with eng.scan_session():
+        first = full_scan(sets[0])                       # the warm-up of both paths
+        assert np.array_equal(eng.resegment(sets[:1])[0], first)
+        runs = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            full_scan(sets[0])
+            runs.append(time.perf_counter() - t0)
+        row["a_s_scan_segments_runs"], row["a_s_scan_segments"] = runs, med(runs)
+        note(f"scan_segments {runs}")
+        for nt in (1, 8, 64):
+            runs = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                tables = eng.resegment(sets[:nt])
+                runs.append(time.perf_counter() - t0)
+            row[f"a_s_resegment_nt{nt}_runs"], row[f"a_s_resegment_nt{nt}"] = runs, med(runs)
+            row[f"records_nt{nt}"] = int(sum(len(t) for t in tables))
+            note(f"resegment nt = {nt} {runs}")
+        for nt in (1, 8, 64):
+            runs = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                for thr in sets[:nt]:
+                    full_scan(thr)
+                runs.append(time.perf_counter() - t0)
+                note(f"full scans nt = {nt} {runs[-1]:.3f} s")
+            row[f"b_s_full_scans_nt{nt}_runs"], row[f"b_s_full_scans_nt{nt}"] = runs, med(runs)
+            row[f"ratio_b_over_a_nt{nt}"] = row[f"b_s_full_scans_nt{nt}"] / (row["a_s_scan_segments"] + row[f"a_s_resegment_nt{nt}"])
+    # (c) device pointers, no model: one long recording under 64 sets, and one launch window of a scan for scale
+    T = 112500
+    run = rng.integers(1, 40, T)
+    p, k, speech = np.empty(T, np.float32), 0, False
+    while k < T:
+        r = int(run[k])
+        p[k:k + r] = rng.uniform(0.5, 0.95, min(r, T - k)) if speech else rng.uniform(0.0, 0.45, min(r, T - k))
+        k, speech = k + r, not speech
+    d_p = torch.from_numpy(p).cuda()
+    d_ev = torch.zeros(T, dtype=torch.uint8, device="cuda")
+    d_tab = torch.zeros(24 * (1 << 20), dtype=torch.uint8, device="cuda")
+    d_cnt = torch.zeros(65, dtype=torch.int64, device="cuda")
+    ts = torch.cuda.Stream()
+
+    def event_timed(fn):
+        fn()
+        torch.cuda.synchronize()
+        out = []
+        for _ in range(3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(ts)
+            fn()
+            e1.record(ts)
+            torch.cuda.synchronize()
+            out.append(e0.elapsed_time(e1) * 1e-3)
+        return out
+
+    runs = event_timed(lambda: eng.resegment_device(d_ev.data_ptr(), d_p.data_ptr(), [0, T], sets, d_tab.data_ptr(), 1 << 20, d_cnt.data_ptr(),
+                                                    stream=ts.cuda_stream))
+    row["c_s_resegment_device_1x112500_nt64_runs"], row["c_s_resegment_device_1x112500_nt64"] = runs, med(runs)
+    row["c_records"] = int(d_cnt.cpu()[64])
+    win = frame + 191 * hop
+    d_audio = torch.from_numpy(np.concatenate([r[:win] for r in recs])).cuda()
+    d_probs = torch.zeros(N * 192, dtype=torch.float32, device="cuda")
+    d_events = torch.zeros(N * 192, dtype=torch.uint8, device="cuda")
+    offs, lens = np.arange(N) * win, np.full(N, win)
+    runs = event_timed(lambda: eng.scan_device(slots, offs, lens, d_audio.data_ptr(), N * win, d_probs.data_ptr(), d_events.data_ptr(), hop=hop,
+                                               fmt=1, stream=ts.cuda_stream))
+    row["c_s_scan_window_192_frames_runs"], row["c_s_scan_window_192_frames"] = runs, med(runs)
+    row["ratio_c_replay_over_window"] = row["c_s_resegment_device_1x112500_nt64"] / row["c_s_scan_window_192_frames"]
+    eng.close()
+    return row
+
+
 def scan_rate():
     """Whole recordings at 48 kHz, resampled on the GPU in the scan: vad_scan_rate_device on VAD_SCAN_BENCH_N (default
     4 096) int16 recordings of 30 s at 48 kHz - the golden clip, every sample three times - already in device memory, hop = chunk / 2,

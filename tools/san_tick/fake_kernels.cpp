@@ -191,6 +191,75 @@ extern "C" hipError_t vadk_launch_scan_segments(const SegArgs *a, hipStream_t) {
     return hipSuccess;
 }
 
+// the statistics of a table's first min(*nsegs, seg_cap) records (csrc/scan_segments.hip: vadk_launch_seg_stats), as above
+extern "C" hipError_t vadk_launch_seg_stats(const SegArgs *a, uint32_t, hipStream_t) {
+    const long long all = *a->nsegs, nrec = all < (long long)a->seg_cap ? all : (long long)a->seg_cap;
+    for (long long q = 0; q < nrec; ++q) {
+        SegRecord &r = a->segs[q];
+        const uint32_t base = (uint32_t)a->out_start[r.item], e = (uint32_t)r.first_frame + (uint32_t)r.nframes - 1u;
+        long long S = 0;
+        float mx = -INFINITY;
+        r.counted = 0;
+        r.mean_prob = r.max_prob = 0.0f;
+        for (uint32_t t = r.first_frame > 0 ? (uint32_t)r.first_frame : 0u; t <= e; ++t) {
+            if (a->events[base + t] & EV_REJECTED) continue;
+            const float p = a->probs[base + t];
+            r.counted += 1;
+            S += (long long)std::rint((double)p * (double)(1ll << SEG_PROB_SHIFT));
+            mx = std::fmax(mx, p);
+        }
+        if (r.counted > 0) {
+            r.mean_prob = (float)((double)S / ((double)r.counted * (double)(1ll << SEG_PROB_SHIFT)));
+            r.max_prob = mx;
+        }
+    }
+    return hipSuccess;
+}
+
+// segment tables at other thresholds (csrc/scan_resegment.hip), in plain C++ over the real sm_step: per (set, item) in the output's
+// order, the accepted frames of the item through a copy of sm0[set].  The count call leaves cnt as the exclusive prefix and the true
+// counts in set_start; the fill call replays again and writes what lies below seg_cap.
+static uint32_t fake_reseg_replay(const ResegArgs *a, int32_t set, int32_t item, bool fill, unsigned long long base) {
+    SmSlot s = a->sm0[set];
+    const uint32_t k0 = (uint32_t)a->out_start[item], k1 = (uint32_t)a->out_start[item + 1];
+    uint32_t j = 0;
+    for (uint32_t k = k0; k < k1; ++k) {
+        if (a->events[k] & EV_REJECTED) continue;
+        int L = 0;
+        if (!(sm_step(s, a->probs[k], &L) & 2)) continue;
+        if (fill && base + j < (unsigned long long)a->seg_cap) {
+            SegRecord &r = a->segs[base + j];
+            r.item = item;
+            r.first_frame = (int32_t)(k - k0) - L + 1;
+            r.nframes = L;
+        }
+        ++j;
+    }
+    return j;
+}
+
+extern "C" hipError_t vadk_launch_reseg_count(const ResegArgs *a, hipStream_t) {
+    unsigned long long carry = 0;
+    for (int32_t set = 0; set < a->nt; ++set) {
+        a->set_start[set] = (long long)carry;
+        for (int32_t item = 0; item < a->n; ++item) {
+            const uint32_t c = fake_reseg_replay(a, set, item, false, 0);
+            a->cnt[(size_t)set * (size_t)a->n + (size_t)item] = carry > 0xffffffffull ? 0xffffffffu : (uint32_t)carry;
+            carry += c;
+        }
+    }
+    a->set_start[a->nt] = (long long)carry;
+    return hipSuccess;
+}
+
+extern "C" hipError_t vadk_launch_reseg_fill(const ResegArgs *a, hipStream_t) {
+    if (a->seg_cap == 0) return hipSuccess;
+    for (int32_t set = 0; set < a->nt; ++set)
+        for (int32_t item = 0; item < a->n; ++item)
+            (void)fake_reseg_replay(a, set, item, true, a->cnt[(size_t)set * (size_t)a->n + (size_t)item]);
+    return hipSuccess;
+}
+
 extern "C" hipError_t vadk_launch_silero_v5_t16_rates(const StepParams *p, const RateParams *r, hipStream_t) {
     for (int k = 0; k < r->nseg; ++k) {
         StepParams q = *p;
