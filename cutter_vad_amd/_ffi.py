@@ -241,6 +241,10 @@ SIGNATURES = {
     "vad_scan_segments_read": (C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(Segment)]),
     "vad_resegment_device": (C.c_int, [_vp, _vp, _vp, _i64p, C.c_int64, C.POINTER(Thresholds), C.c_int64, _vp, C.c_int64, _vp, _vp]),
     "vad_scan_resegment": (C.c_int, [_vp, C.POINTER(Thresholds), C.c_int64, C.POINTER(Segment), C.c_int64, _i64p]),
+    "vad_scan_tails": (C.c_int, [_vp, C.POINTER(Segment), C.c_int64]),
+    "vad_scan_resegment_tails": (C.c_int, [_vp, C.POINTER(Thresholds), C.c_int64, C.POINTER(Segment), C.c_int64]),
+    "vad_tails_device": (C.c_int, [_vp, _i64p, _vp, _vp, _i64p, C.c_int64, _vp, _vp]),
+    "vad_resegment_tails_device": (C.c_int, [_vp, _vp, _vp, _i64p, C.c_int64, C.POINTER(Thresholds), C.c_int64, _vp, _vp]),
     "vad_scan_rate_segments": (C.c_int, [_vp, C.POINTER(ScanChItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32,
                                          C.c_float, C.POINTER(Segment), C.c_int64, _i64p]),
     "vad_rate_cut_samples": (C.c_int64, [_vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),

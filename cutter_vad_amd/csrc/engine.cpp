@@ -47,6 +47,9 @@ extern "C" hipError_t vadk_launch_scan_segments(const vadk::SegArgs *a, hipStrea
 extern "C" hipError_t vadk_launch_seg_stats(const vadk::SegArgs *a, uint32_t most, hipStream_t stream);
 extern "C" hipError_t vadk_launch_reseg_count(const vadk::ResegArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_reseg_fill(const vadk::ResegArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_reseg_tails(const vadk::ResegArgs *a, uint32_t *tail_len, hipStream_t stream);
+extern "C" hipError_t vadk_launch_tail_snapshot(const vadk::TailArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_seg_tails(const vadk::TailArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_resample(const vadk::ScanResampleArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_cut_resample(const vadk::CutResampleArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_resample(const vadk::ResampleParams *p, hipStream_t stream);
@@ -186,6 +189,11 @@ struct vad_engine {
     std::vector<uint8_t> reseg_up;
     vadk::SegRecord *d_resegtab = nullptr; size_t d_resegtab_cap = 0;
     bool scan_results = false;
+    // the tails (vad_scan_tails and its kin): d_tail_len = the snapshot scan_segments_run takes of its streams' state machines, one
+    // length per item of seg_out_start, written by nothing else; d_tailwork = the work area of a tails call (tail_area lays it out)
+    uint32_t *d_tail_len = nullptr; size_t d_tail_len_cap = 0;
+    uint8_t *d_tailwork = nullptr; size_t d_tailwork_cap = 0;
+    std::vector<int32_t> tail_up;
     // G.711 frames expanded to int16 for the kernels whose loaders do not decode them (launch())
     int16_t *d_g711 = nullptr; size_t d_g711_cap = 0;
     // small calls (a few streams: the one-wrapper-per-client pattern): ONE pinned block in, ONE pinned block out
@@ -881,7 +889,7 @@ void vad_engine_destroy(vad_engine *e) {
     weights_release(e->d_wstream16);
     weights_release(e->d_wstream16x);
     weights_release(e->d_wstream16y);
-    void *bufs[] = {e->d_reseg, e->d_resegtab, e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots, e->d_g711,
+    void *bufs[] = {e->d_tail_len, e->d_tailwork, e->d_reseg, e->d_resegtab, e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots, e->d_g711,
                     e->d_audio, e->d_items, e->d_win, e->d_items_win, e->d_cut, e->d_cut_out, e->d_segwork, e->d_nsegs, e->d_segtab, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
@@ -2054,6 +2062,32 @@ int seg_launches(vad_engine *e, const uint8_t *d_events, const int32_t *d_seg, c
     return VAD_OK;
 }
 
+// The first half of a tails call on `s`: the work area sized for n items under nt sets, and out_start (checked as seg_launches wants
+// it) with - slots != nullptr - the items' slots behind it go up as int32 in one block.  a->tail_len and a->tails point into the
+// work area; a caller with arrays of its own for either replaces them.
+int tail_setup(vad_engine *e, const uint8_t *d_events, const float *d_probs, const int64_t *out_start, int64_t n, int64_t nt, const int64_t *slots,
+               hipStream_t s, vadk::TailArgs *a) {
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t ints = (size_t)(n + 1) + (slots ? (size_t)n : 0), o_len = up16(sizeof(int32_t) * ints);
+    const size_t o_rec = o_len + up16(sizeof(uint32_t) * (size_t)nt * (size_t)n);
+    if (int rc = ensure(e, e->d_tailwork, e->d_tailwork_cap, o_rec + sizeof(vadk::SegRecord) * (size_t)nt * (size_t)n + 16)) return rc;
+    e->tail_up.resize(ints);
+    for (int64_t i = 0; i <= n; ++i) e->tail_up[(size_t)i] = (int32_t)out_start[i];
+    for (int64_t i = 0; slots && i < n; ++i) e->tail_up[(size_t)(n + 1 + i)] = (int32_t)slots[i];
+    HIP_TRY(e, hipMemcpyAsync(e->d_tailwork, e->tail_up.data(), sizeof(int32_t) * ints, hipMemcpyHostToDevice, s));
+    *a = vadk::TailArgs{};
+    a->events = d_events;
+    a->probs = d_probs;
+    a->out_start = reinterpret_cast<const int32_t *>(e->d_tailwork);
+    a->sm = e->d_sm;
+    a->slots = slots ? a->out_start + (n + 1) : nullptr;
+    a->tail_len = reinterpret_cast<uint32_t *>(e->d_tailwork + o_len);
+    a->tails = reinterpret_cast<vadk::SegRecord *>(e->d_tailwork + o_rec);
+    a->n = (int32_t)n;
+    a->nt = (int32_t)nt;
+    return VAD_OK;
+}
+
 // vad_scan_segments and vad_scan_rate_segments (chunk > 0: the recordings are at sr_in), with e->mu held: the scan of host audio
 // into the engine's own arrays - the block stays resident, of its rate - then the extraction
 int scan_segments_run(vad_engine *e, const char *who, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples,
@@ -2077,6 +2111,18 @@ int scan_segments_run(vad_engine *e, const char *who, const vad_scan_ch_item *it
         return VAD_OK;
     }
     if (int rc = scan_upload_launch(e, n, audio, audio_samples, channels, frame_fmt, chunk, sr_in, hop, denoise_thresh, total, true)) return rc;
+    {   // the tails' lengths, out of the streams' state machines as the model launches leave them (vad_scan_tails): one small
+        // launch on the same stream, no model launch - vad_info.steps and .frames do not move; whatever a later call does to the
+        // slots comes behind it
+        std::vector<int64_t> slots((size_t)n);
+        for (int64_t i = 0; i < n; ++i) slots[(size_t)i] = items[i].slot;
+        if (int rc = ensure(e, e->d_tail_len, e->d_tail_len_cap, sizeof(uint32_t) * (size_t)n)) return rc;
+        vadk::TailArgs ta;
+        if (int rc = tail_setup(e, e->d_events, e->d_probs, start.data(), n, 1, slots.data(), e->stream, &ta)) return rc;
+        ta.tail_len = e->d_tail_len;
+        const hipError_t r = vadk_launch_tail_snapshot(&ta, e->stream);
+        if (r != hipSuccess) return e->hip_fail(r, "kernel launch (tail snapshot)");
+    }
     if (int rc = ensure(e, e->d_nsegs, e->d_nsegs_cap, sizeof(long long))) return rc;
     // the table's size is known only behind the count: room for the caller's capacity and for a segment per 16 frames first, and
     // the extraction once more (the per-frame arrays are still there) in the rare case that the table is larger
@@ -2199,13 +2245,16 @@ int reseg_check_sets(vad_engine *e, const char *who, const vad_thresholds *t, in
 // block; the initial state machines are built by the kernel that serves vad_stream_open and vad_stream_set_thresholds - default,
 // then the set's thresholds - on nt scratch records of the work area (no stream's slot, no (h, c)); then the count and the prefix.
 // d_set_start == nullptr: the counts go to the work area (a->set_start says where).
+// tail_len != nullptr (the tails): the count replay alone, in the form that also keeps the length of the segment open behind each
+// item's last frame - *tail_len = those lengths [nt n], in the work area; no prefix, set_start is not written.
 int reseg_count(vad_engine *e, const uint8_t *d_events, const float *d_probs, const int64_t *out_start, int64_t n, const vad_thresholds *t,
-                int64_t nt, long long *d_set_start, hipStream_t s, vadk::ResegArgs *a) {
+                int64_t nt, long long *d_set_start, hipStream_t s, vadk::ResegArgs *a, uint32_t **tail_len = nullptr) {
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t o_slots = up16(sizeof(int32_t) * (size_t)(n + 1)), o_thr = o_slots + up16(sizeof(int32_t) * (size_t)nt);
     const size_t up_bytes = o_thr + up16(sizeof(vad_thresholds) * (size_t)nt), o_sm = up_bytes;
     const size_t o_set = o_sm + up16(sizeof(vadk::SmSlot) * (size_t)nt), o_cnt = o_set + up16(sizeof(long long) * (size_t)(nt + 1));
-    if (int rc = ensure(e, e->d_reseg, e->d_reseg_cap, o_cnt + sizeof(uint32_t) * (size_t)nt * (size_t)n + 16)) return rc;
+    const size_t o_tail = o_cnt + up16(sizeof(uint32_t) * (size_t)nt * (size_t)n);
+    if (int rc = ensure(e, e->d_reseg, e->d_reseg_cap, o_tail + (tail_len ? sizeof(uint32_t) * (size_t)nt * (size_t)n : 0) + 16)) return rc;
     e->reseg_up.assign(up_bytes, 0);
     int32_t *h_start = reinterpret_cast<int32_t *>(e->reseg_up.data()), *h_slots = reinterpret_cast<int32_t *>(e->reseg_up.data() + o_slots);
     for (int64_t i = 0; i <= n; ++i) h_start[i] = n > 0 ? (int32_t)out_start[i] : 0;
@@ -2228,7 +2277,8 @@ int reseg_count(vad_engine *e, const uint8_t *d_events, const float *d_probs, co
     a->n = (int32_t)n;
     a->nt = (int32_t)nt;
     a->set_shift = shift;
-    const hipError_t r = vadk_launch_reseg_count(a, s);
+    if (tail_len) *tail_len = reinterpret_cast<uint32_t *>(e->d_reseg + o_tail);
+    const hipError_t r = tail_len ? vadk_launch_reseg_tails(a, *tail_len, s) : vadk_launch_reseg_count(a, s);
     if (r != hipSuccess) return e->hip_fail(r, "kernel launch (resegment count)");
     return VAD_OK;
 }
@@ -2323,6 +2373,159 @@ int vad_scan_resegment(vad_engine *e, const vad_thresholds *t, int64_t nt, vad_s
     }
     for (int64_t k = 0; k <= nt; ++k) set_start_out[k] = counts[(size_t)k];
     return VAD_OK;
+}
+
+}  // extern "C"
+
+// ---- the segment still open at a recording's last frame (vad_scan_tails, vad_scan_resegment_tails, the two device forms) ------
+namespace {
+
+// what the device forms check about the positions, in vad_segments_device's wording -> *total = out_start[n]
+int tail_check_start(vad_engine *e, const char *who, const int64_t *out_start, int64_t n, int64_t *total) {
+    if (n > 0 && out_start[0] < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start[0] is negative", who);
+    for (int64_t i = 0; i < n; ++i)
+        if (out_start[i + 1] < out_start[i])
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start decreases at item %lld (%lld after %lld)", who, (long long)i,
+                           (long long)out_start[i + 1], (long long)out_start[i]);
+    *total = n > 0 ? out_start[n] : 0;
+    if (*total > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 frames in one call", who);
+    return VAD_OK;
+}
+
+// what the host forms check: the mark, and that the caller's n is the scan's -> *total = the scan's frames
+int tail_check_resident(vad_engine *e, const char *who, const void *tails_out, int64_t n, int64_t *total) {
+    if (!e->scan_results || e->seg_out_start.empty())
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: no scan results are resident: the engine's last vad_scan_segments or "
+                                            "vad_scan_rate_segments failed, or a later call has reused its per-frame arrays", who);
+    const int64_t have = (int64_t)e->seg_out_start.size() - 1;
+    if (n != have)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n = %lld: the scan had %lld items", who, (long long)n, (long long)have);
+    if (n > 0 && !tails_out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    *total = e->seg_out_start[(size_t)n];
+    return VAD_OK;
+}
+
+int tail_records(vad_engine *e, const vadk::TailArgs *a, hipStream_t s) {
+    const hipError_t r = vadk_launch_seg_tails(a, s);
+    if (r != hipSuccess) return e->hip_fail(r, "kernel launch (segment tails)");
+    return VAD_OK;
+}
+
+int tail_download(vad_engine *e, const vadk::TailArgs &a, vad_segment *tails_out) {
+    HIP_TRY(e, hipMemcpyAsync(tails_out, a.tails, sizeof(vad_segment) * (size_t)a.n * (size_t)a.nt, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return VAD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vad_scan_tails(vad_engine *e, vad_segment *tails_out, int64_t n) {
+    static const char *who = "vad_scan_tails";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    int64_t total = 0;
+    if (int rc = tail_check_resident(e, who, tails_out, n, &total)) return rc;
+    if (n == 0) return VAD_OK;
+    if (total == 0) {                        // no frame, no tail (and no snapshot was taken)
+        std::memset(tails_out, 0, sizeof(vad_segment) * (size_t)n);
+        return VAD_OK;
+    }
+    vadk::TailArgs a;
+    if (int rc = tail_setup(e, e->d_events, e->d_probs, e->seg_out_start.data(), n, 1, nullptr, e->stream, &a)) return rc;
+    a.tail_len = e->d_tail_len;
+    if (int rc = tail_records(e, &a, e->stream)) return rc;
+    return tail_download(e, a, tails_out);
+}
+
+int vad_scan_resegment_tails(vad_engine *e, const vad_thresholds *t, int64_t nt, vad_segment *tails_out, int64_t n) {
+    static const char *who = "vad_scan_resegment_tails";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    if (int rc = reseg_check_sets(e, who, t, nt, 0)) return rc;
+    int64_t total = 0;
+    if (int rc = tail_check_resident(e, who, tails_out, n, &total)) return rc;
+    if (n == 0) return VAD_OK;
+    if (total == 0) {
+        std::memset(tails_out, 0, sizeof(vad_segment) * (size_t)n * (size_t)nt);
+        return VAD_OK;
+    }
+    vadk::ResegArgs ra;
+    vadk::TailArgs a;
+    // (the positions go up twice, once per work area: a few bytes per item)
+    if (int rc = tail_setup(e, e->d_events, e->d_probs, e->seg_out_start.data(), n, nt, nullptr, e->stream, &a)) return rc;
+    if (int rc = reseg_count(e, e->d_events, e->d_probs, e->seg_out_start.data(), n, t, nt, nullptr, e->stream, &ra, &a.tail_len)) return rc;
+    if (int rc = tail_records(e, &a, e->stream)) return rc;
+    return tail_download(e, a, tails_out);
+}
+
+int vad_tails_device(vad_engine *e, const int64_t *slots, const uint8_t *d_events, const float *d_probs, const int64_t *out_start, int64_t n,
+                     vad_segment *d_tails, void *stream) {
+    static const char *who = "vad_tails_device";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    if (n < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n = %lld: bad count", who, (long long)n);
+    if (n > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 items", who);
+    if (n > 0 && (!slots || !out_start || !d_tails)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    int64_t total = 0;
+    if (int rc = tail_check_start(e, who, out_start, n, &total)) return rc;
+    if (total > 0 && (!d_events || !d_probs)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if ((reinterpret_cast<uintptr_t>(d_events) & 15) || (reinterpret_cast<uintptr_t>(d_tails) & 15))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the events and the tails must be 16-byte aligned", who);
+    if (reinterpret_cast<uintptr_t>(d_probs) & 3) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: probs must be 4-byte aligned", who);
+    if (int rc = check_slots(e, slots, n)) return rc;
+    if (n == 0) return VAD_OK;
+    vadk::TailArgs a;
+    int rc = tail_setup(e, d_events, d_probs, out_start, n, 1, slots, s, &a);
+    if (rc == VAD_OK) {
+        a.tails = reinterpret_cast<vadk::SegRecord *>(d_tails);
+        const hipError_t r = vadk_launch_tail_snapshot(&a, s);
+        rc = r != hipSuccess ? e->hip_fail(r, "kernel launch (tail snapshot)") : tail_records(e, &a, s);
+    }
+    // the launches read the engine's work area: the next scan, cut, extraction or replay waits for them, as behind vad_scan_device
+    if (int rc2 = scan_mark_pending(e, s)) return rc2;
+    return rc;
+}
+
+int vad_resegment_tails_device(vad_engine *e, const uint8_t *d_events, const float *d_probs, const int64_t *out_start, int64_t n,
+                               const vad_thresholds *t, int64_t nt, vad_segment *d_tails, void *stream) {
+    static const char *who = "vad_resegment_tails_device";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    if (int rc = reseg_check_sets(e, who, t, nt, 0)) return rc;
+    if (n < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n = %lld: bad count", who, (long long)n);
+    if (n * nt > INT32_MAX)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %lld items x %lld sets: more than 2^31 - 1 replays in one call", who,
+                       (long long)n, (long long)nt);
+    if (n > 0 && (!out_start || !d_tails)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    int64_t total = 0;
+    if (int rc = tail_check_start(e, who, out_start, n, &total)) return rc;
+    if (total > 0 && (!d_events || !d_probs)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if ((reinterpret_cast<uintptr_t>(d_events) & 15) || (reinterpret_cast<uintptr_t>(d_tails) & 15))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the events and the tails must be 16-byte aligned", who);
+    if (reinterpret_cast<uintptr_t>(d_probs) & 3) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: probs must be 4-byte aligned", who);
+    if (n == 0) return VAD_OK;
+    vadk::ResegArgs ra;
+    vadk::TailArgs a;
+    int rc = tail_setup(e, d_events, d_probs, out_start, n, nt, nullptr, s, &a);
+    if (rc == VAD_OK) rc = reseg_count(e, d_events, d_probs, out_start, n, t, nt, nullptr, s, &ra, &a.tail_len);
+    if (rc == VAD_OK) {
+        a.tails = reinterpret_cast<vadk::SegRecord *>(d_tails);
+        rc = tail_records(e, &a, s);
+    }
+    if (int rc2 = scan_mark_pending(e, s)) return rc2;
+    return rc;
 }
 
 // ---- pipelined host ingest ---------------------------------------------------------------------------------------

@@ -13,6 +13,9 @@
 // Sets run along the lanes, 1 << set_shift of them per item: the lanes of a wave that share an item load the same probability and
 // event addresses (one request each), and with 64 sets a wave is one recording.  Lanes whose items differ in length run to the
 // longest.  Four frames are loaded ahead of their four steps, so a thread waits for memory once per four frames.
+//   tails  - vadk_tails_reseg_count (vad_scan_resegment_tails, vad_resegment_tails_device): the count replay once more, which also
+//            keeps the state machine it ends with - inside a segment: its seg_frames, else 0, into tail_len[set n + item] - for
+//            csrc/scan_tails.hip's vadk_seg_tails.  A kernel of its own: the three above compile to what they were without it.
 #include <hip/hip_runtime.h>
 #include "../../include/vad_engine.h"
 #include "sm_device.h"
@@ -28,9 +31,10 @@ namespace {
 constexpr int RESEG_WAVES = RESEG_THREADS / 64;
 constexpr int RESEG_AHEAD = 4;                // frames loaded before the first of them is stepped
 
-// the accepted frames of `item` through `s`; FILL: END number j is written at base + j -> the number of ENDs
+// the accepted frames of `item` through `s`; FILL: END number j is written at base + j -> the number of ENDs; `last`: where the
+// state machine behind the item's last frame goes (the tails)
 template <bool FILL>
-__device__ __forceinline__ uint32_t reseg_replay(const ResegArgs &a, int32_t item, SmSlot s, unsigned long long base) {
+__device__ __forceinline__ uint32_t reseg_replay(const ResegArgs &a, int32_t item, SmSlot s, unsigned long long base, SmSlot *last = nullptr) {
     const uint32_t k0 = (uint32_t)a.out_start[item], k1 = (uint32_t)a.out_start[item + 1];      // k0 <= k1 <= 2^31 - 1
     uint32_t j = 0;
     auto step = [&](uint32_t k, uint32_t ev, float p) {
@@ -62,6 +66,7 @@ __device__ __forceinline__ uint32_t reseg_replay(const ResegArgs &a, int32_t ite
         for (int u = 0; u < RESEG_AHEAD; ++u) step(k + (uint32_t)u, ev[u], p[u]);
     }
     for (; k < k1; ++k) step(k, a.events[k], a.probs[k]);
+    if (last) *last = s;
     return j;
 }
 
@@ -80,6 +85,18 @@ __global__ void __launch_bounds__(RESEG_THREADS) vadk_reseg_count(const ResegArg
     int32_t item, set;
     if (!reseg_thread(a, &item, &set)) return;
     a.cnt[(size_t)set * (size_t)a.n + (size_t)item] = reseg_replay<false>(a, item, a.sm0[set], 0ull);
+}
+
+// the count replay that also keeps what vadk_tail_snapshot reads out of a stream's slot (csrc/scan_tails.hip): the seg_frames of a
+// state machine that ends the item inside a segment, else 0.  A fresh state machine is not active before its first frame, so an
+// item without frames has no tail.
+__global__ void __launch_bounds__(RESEG_THREADS) vadk_tails_reseg_count(const ResegArgs a, uint32_t *tail_len) {
+    int32_t item, set;
+    if (!reseg_thread(a, &item, &set)) return;
+    SmSlot s;
+    a.cnt[(size_t)set * (size_t)a.n + (size_t)item] = reseg_replay<false>(a, item, a.sm0[set], 0ull, &s);
+    const bool any = a.out_start[item + 1] > a.out_start[item];
+    tail_len[(size_t)set * (size_t)a.n + (size_t)item] = any && s.active != 0 && s.seg_frames >= 1 ? (uint32_t)s.seg_frames : 0u;
 }
 
 __global__ void __launch_bounds__(RESEG_THREADS) vadk_reseg_fill(const ResegArgs a) {
@@ -143,6 +160,15 @@ extern "C" hipError_t vadk_launch_reseg_count(const ResegArgs *a, hipStream_t st
         if ((r = hipGetLastError()) != hipSuccess) return r;
     }
     hipLaunchKernelGGL(vadk_reseg_prefix, dim3(1), dim3(RESEG_THREADS), 0, stream, *a);
+    return hipGetLastError();
+}
+
+// the count replay alone, with the tails' lengths: tail_len[set n + item] (no prefix: a->set_start is not written)
+extern "C" hipError_t vadk_launch_reseg_tails(const ResegArgs *a, uint32_t *tail_len, hipStream_t stream) {
+    (void)hipGetLastError();
+    const unsigned blocks = reseg_blocks(a);
+    if (blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(vadk_tails_reseg_count, dim3(blocks), dim3(RESEG_THREADS), 0, stream, *a, tail_len);
     return hipGetLastError();
 }
 

@@ -324,6 +324,24 @@ struct ResegArgs {
     int32_t set_shift;        // log2 of the lanes one item takes
 };
 
+// the segment still open at a recording's last frame (csrc/scan_tails.hip; vad_scan_tails, vad_scan_resegment_tails and the two
+// device forms).  tail_len[k n + i] is the seg_frames of the state machine of (set k, item i) behind the item's last frame where it
+// is inside a segment, else 0: vadk_tail_snapshot reads it out of the streams' slots (nt = 1; slots in the caller's item order),
+// csrc/scan_resegment.hip's vadk_tails_reseg_count out of its threads' registers.  vadk_seg_tails, one wave per entry, turns every
+// entry into one SegRecord - all zero where tail_len is 0 - with the statistics of vadk_seg_stats.
+constexpr int TAIL_THREADS = 256;
+struct TailArgs {
+    const uint8_t *events;    // [out_start[n]]: VAD_EV_REJECTED alone is read
+    const float *probs;
+    const int32_t *out_start; // [n + 1] on the device, as SegArgs::out_start
+    const SmSlot *sm;         // the engine's slots (vadk_tail_snapshot)
+    const int32_t *slots;     // [n]: item i's stream (vadk_tail_snapshot)
+    uint32_t *tail_len;       // [nt n]
+    SegRecord *tails;         // [nt n] (vadk_seg_tails)
+    int32_t n;                // items; n nt <= 2^31 - 1
+    int32_t nt;               // sets; 1 on the scan path
+};
+
 // resampler launch parameters (csrc/resample.hip)
 struct ResampleSeg {
     const float *wstream;     // folded operator (pack_weights.cpp: pack_resample_operator)

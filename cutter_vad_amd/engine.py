@@ -64,6 +64,7 @@ class Engine:
         self._scan_block = None             # scan(): the page-locked block the recordings are packed into ...
         self._scan_lock = threading.RLock()  # ... held from the packing to the return of vad_scan: engines are shared between threads
         self._scan_last = None              # what scan() packed last (cut(audio=None) cuts that block): see scan_session()
+        self._tail_items = None             # items of the last scan_segments (scan_tails asks for as many records)
         self.last_tick_us = (0.0, 0.0, 0.0)
         self.last_tick_dropped = 0
         self.last_tick_staged_next = 0
@@ -462,12 +463,14 @@ class Engine:
             table = np.zeros(int(start[-1]) // 64 + 16, _ffi.SEGMENT_DTYPE)
             count = C.c_int64(0)
             self._scan_last = None
+            self._tail_items = None
             where = (self._h, items, n * per, block.ctypes.data_as(C.c_void_p), total, 2 if two else 1, fmt)
             res = (thr, table.ctypes.data_as(C.POINTER(_ffi.Segment)), table.size, C.byref(count))
             if sr is not None:
                 self._check(self._lib.vad_scan_rate_segments(*where, sr, hop, *res))
             else:
                 self._check(self._lib.vad_scan_segments(*where, hop, *res))
+            self._tail_items = n * per           # what scan_tails asks for
             if int(start[-1]):
                 self._scan_last = {"samples": total, "channels": 2 if two else 1, "fmt": fmt, "offsets": offs, "lengths": lens}
                 if sr is not None:
@@ -520,6 +523,49 @@ class Engine:
         start = np.ascontiguousarray(out_start, dtype=np.int64).reshape(-1)
         self._check(self._lib.vad_resegment_device(self._h, d_events or None, d_probs or None, _ptr(start, C.c_int64), max(start.size - 1, 0),
                                                    sets, nt, d_segs or None, int(seg_cap), d_set_start or None, stream or None))
+
+    def scan_tails(self) -> np.ndarray:
+        """The segment still open at the last frame of each item of the last ``scan_segments`` (``vad_scan_tails``) -> one record
+        (``_ffi.SEGMENT_DTYPE``) per item, in item order: ``first_frame = frames - nframes`` (negative when the slot entered the
+        recording inside a segment) and the statistics of a table's record; ``nframes == 0`` - the whole record is zero - where the
+        recording ended outside speech.  The scan saved the lengths itself: resetting, closing or retuning its streams behind it
+        does not change the answer.  No model launch, no stream touched, the tables and the resident block left alone.  Call it
+        inside ``scan_session()``, behind the ``scan_segments``."""
+        with self._scan_lock:
+            n = 0 if self._tail_items is None else self._tail_items
+            tails = np.zeros(n, _ffi.SEGMENT_DTYPE)
+            self._check(self._lib.vad_scan_tails(self._h, tails.ctypes.data_as(C.POINTER(_ffi.Segment)) if n else None, n))
+        return tails
+
+    def resegment_tails(self, thresholds) -> List[np.ndarray]:
+        """``scan_tails`` at other thresholds (``vad_scan_resegment_tails``): per set of ``thresholds`` (as ``resegment`` takes
+        them) the tails of fresh state machines with that set, replayed over the per-frame results the last ``scan_segments`` left
+        on the GPU -> one array of ``scan_tails``' shape per set."""
+        sets, nt = self._threshold_sets(thresholds)
+        with self._scan_lock:
+            n = 0 if self._tail_items is None else self._tail_items
+            tails = np.zeros(nt * n, _ffi.SEGMENT_DTYPE)
+            self._check(self._lib.vad_scan_resegment_tails(self._h, sets, nt, tails.ctypes.data_as(C.POINTER(_ffi.Segment)) if tails.size else None, n))
+        return [tails[k * n:(k + 1) * n] for k in range(nt)]
+
+    def tails_device(self, slots, d_events: int, d_probs: int, out_start, d_tails: int, stream: int = 0) -> None:
+        """``scan_tails`` on device pointers (integers; ``vad_tails_device``): ``slots`` the streams of the items in item order,
+        ``d_events`` (16-byte aligned) and ``d_probs`` as ``scan_device`` wrote them, ``out_start`` the positions it returned; one
+        record per item goes to ``d_tails`` (16-byte aligned, ``_ffi.SEGMENT_DTYPE``).  The launch reads the slots' state machines
+        when it runs: enqueue it on ``stream`` behind the scan.  Every engine has it."""
+        sl = np.ascontiguousarray(slots, dtype=np.int64).reshape(-1)
+        start = np.ascontiguousarray(out_start, dtype=np.int64).reshape(-1)
+        self._check(self._lib.vad_tails_device(self._h, _ptr(sl, C.c_int64), d_events or None, d_probs or None, _ptr(start, C.c_int64),
+                                               max(start.size - 1, 0), d_tails or None, stream or None))
+
+    def resegment_tails_device(self, d_events: int, d_probs: int, out_start, thresholds, d_tails: int, stream: int = 0) -> None:
+        """``resegment_tails`` on device pointers (``vad_resegment_tails_device``): entry ``k * n + i`` of ``d_tails`` (16-byte
+        aligned, ``len(thresholds) * n`` records) is the tail of set ``k``, item ``i``.  Asynchronous on ``stream``; every engine
+        has it."""
+        sets, nt = self._threshold_sets(thresholds)
+        start = np.ascontiguousarray(out_start, dtype=np.int64).reshape(-1)
+        self._check(self._lib.vad_resegment_tails_device(self._h, d_events or None, d_probs or None, _ptr(start, C.c_int64),
+                                                         max(start.size - 1, 0), sets, nt, d_tails or None, stream or None))
 
     def scan_device(self, slots, offsets, lengths, d_audio: int, audio_samples: int, d_probs: int, d_events: int = 0, d_seg: int = 0,
                     hop: Optional[int] = None, fmt: int = _ffi.VAD_FMT_F32, denoise: Optional[float] = 0.01, stream: int = 0,

@@ -20,7 +20,7 @@ def speech_segments(events, seg_frames, frame: int, hop: int) -> List[Tuple[int,
     """The finished segments of one recording as sample ranges ``[(start_sample, end_sample), ...]`` (end exclusive), from the
     per-frame ``events`` and ``seg_frames`` of ``Engine.scan``: a ``VAD_EV_END`` at frame ``e`` with length ``L`` covers the
     frames ``e - L + 1 .. e``, i.e. the samples ``[(e - L + 1) * hop, e * hop + frame)``.  A segment still open at the
-    recording's last frame has no END and is not listed."""
+    recording's last frame has no END and is not listed (``scan_recordings(open_end=True)`` lists it)."""
     ev = np.asarray(events)
     seg = np.asarray(seg_frames)
     out = []
@@ -56,15 +56,33 @@ def _table_ranges(table, n: int, per: int, frame: int, hop: int, stats: bool) ->
     return out
 
 
+def _with_tails(table, tails):
+    """``table`` with the tails that exist (``nframes > 0``) behind it: ``_table_ranges`` then lists each as its item's last range"""
+    return np.concatenate([table, tails[tails["nframes"] > 0]])
+
+
+def _need_tails(engine, who: str, what: str = "scan_tails") -> None:
+    if not hasattr(engine, what):
+        raise ConfigurationError("open_end", "True", f"{who}: open_end=True needs an engine with {what} (the length of a segment still open "
+                                 f"at a recording's last frame is the state machine's to tell), {type(engine).__name__} has none")
+
+
 def _scan_ranges(engine, slots, recordings, per: int, frame: int, hop: int, law, denoise, channel, stats: bool = False,
-                 rate: Optional[int] = None) -> List[List[List]]:
+                 rate: Optional[int] = None, open_end: bool = False) -> List[List[List]]:
     """One scan of ``recordings`` (all 1-D or all two-channel) on ``slots`` -> per recording, per channel scanned of it (``per``),
     the finished segments ``(start_sample, end_sample)`` - with ``stats``: ``(start_sample, end_sample, mean_prob, max_prob)``.
     An engine with ``scan_segments`` builds the table on the GPU and copies back that alone; any other goes through the per-frame
     results of ``scan``.  Same ranges either way.  ``rate``: the recordings' sample rate when it is not the engine's (``frame`` and
-    ``hop`` are then a chunk and a hop in input samples; ``vad_scan_rate_segments`` builds the table)."""
+    ``hop`` are then a chunk and a hop in input samples; ``vad_scan_rate_segments`` builds the table).  ``open_end``: the segment
+    still open at an item's last frame (``Engine.scan_tails``) is its last range."""
     sl = np.asarray(slots).reshape(len(recordings), per) if per == 2 else slots
     kw = {} if rate is None else {"sample_rate": rate}
+    if open_end:
+        _need_tails(engine, "scan_recordings")
+        with engine.scan_session():
+            table = engine.scan_segments(sl, recordings, hop=hop, law=law, denoise=denoise, channel=channel, **kw)
+            table = _with_tails(table, engine.scan_tails())
+        return _table_ranges(table, len(recordings), per, frame, hop, stats)
     if hasattr(engine, "scan_segments"):
         table = engine.scan_segments(sl, recordings, hop=hop, law=law, denoise=denoise, channel=channel, **kw)
         return _table_ranges(table, len(recordings), per, frame, hop, stats)
@@ -83,7 +101,8 @@ def _scan_ranges(engine, slots, recordings, per: int, frame: int, hop: int, law,
 
 
 def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
-                    law: Optional[str] = None, channel="mix", stats: bool = False, sample_rate: Optional[int] = None) -> List[List[Tuple]]:
+                    law: Optional[str] = None, channel="mix", stats: bool = False, sample_rate: Optional[int] = None,
+                    open_end: bool = False) -> List[List[Tuple]]:
     """Speech segments of every recording, one launch sequence for the lot: opens one stream per recording with the config's
     thresholds, scans (frames of ``engine.frame_samples`` at ``hop``, default half a frame as ``VADWrapper`` frames a chunk;
     the config's denoise gate), closes the streams -> per recording ``[(start_sample, end_sample), ...]``.
@@ -95,7 +114,11 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
     ``sample_rate``: the RECORDINGS' rate when it is not the engine's: 8000, 24000 or 48000 on a 16 kHz Silero V5 engine.  The corpus
     is uploaded at that rate and resampled on the GPU chunk by chunk (``Engine.scan(sample_rate=...)``); chunks have
     ``512 * sample_rate / 16000`` samples, ``hop`` counts input samples (default half a chunk) and the ranges returned are in
-    INPUT-rate samples.  None, or the engine's rate: as above."""
+    INPUT-rate samples.  None, or the engine's rate: as above.
+    ``open_end``: a recording that stops inside speech - before the ``voice_end_frame_count`` low frames an END needs - has no END
+    for its last segment, and by default that segment is not listed (a stream may go on).  ``True`` appends it, as the last range
+    of its recording or channel: from the first frame the state machine buffered for it to the recording's last frame, with its
+    mean and maximum under ``stats=True`` (``Engine.scan_tails``; an engine object without it: ``ConfigurationError``)."""
     from .pool import default_pool, resolve_model_path
     split = isinstance(channel, str) and channel == "split"
     # checked here, not by the scan: a corpus of 1-D recordings alone never shows the value to Engine.scan
@@ -104,6 +127,8 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
     cfg = config or VADConfig()
     if engine is None:
         engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
+    if open_end:
+        _need_tails(engine, "scan_recordings")
     frame = engine.frame_samples
     if cfg.buffer_size != frame:
         raise ConfigurationError(f"scan_recordings frames at the model's frame size: buffer_size = {cfg.buffer_size}, "
@@ -128,7 +153,7 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
             engine.set_thresholds_many(slots, (cfg.vad_start_probability, cfg.vad_end_probability, cfg.voice_start_ratio,
                                                cfg.voice_end_ratio, cfg.voice_start_frame_count, cfg.voice_end_frame_count))
             ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, 0.01 if cfg.enable_denoising else None,
-                                  channel, stats, rate)
+                                  channel, stats, rate, open_end)
         finally:
             for s in slots:
                 engine.close_stream(int(s))
@@ -143,14 +168,16 @@ def _thresholds_of(cfg: VADConfig) -> Tuple:
 
 
 def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConfig], engine=None, hop: Optional[int] = None,
-                     law: Optional[str] = None, channel="mix", stats: bool = False, sample_rate: Optional[int] = None) -> List[List]:
+                     law: Optional[str] = None, channel="mix", stats: bool = False, sample_rate: Optional[int] = None,
+                     open_end: bool = False) -> List[List]:
     """``scan_recordings`` under several configs for the price of one scan: ``sweep_recordings(recs, cfgs, **kw)[j] ==
     scan_recordings(recs, cfgs[j], **kw)``.  The model runs once per kind of recording (1-D, 2-D), with the first config's
     thresholds; the segment tables of all configs then come from ONE replay of the per-frame probabilities that scan left on the
     GPU (``Engine.resegment``, 64 configs per replay: the model's output does not depend on the thresholds).  The configs may differ
     in the six threshold fields alone; they must agree on what the probabilities depend on - ``model_version``, ``sample_rate``,
     ``buffer_size``, ``enable_denoising`` and ``model_path`` - or ``ConfigurationError`` names the field.  An engine object without
-    ``resegment`` is served config by config."""
+    ``resegment`` is served config by config.  ``open_end`` as in ``scan_recordings``: each config's open segments come from the
+    same replay (``Engine.resegment_tails``)."""
     from .pool import default_pool, resolve_model_path
     configs = list(configs)
     if not configs:
@@ -165,8 +192,10 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
     if engine is None:
         engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
     if not hasattr(engine, "resegment") or not hasattr(engine, "scan_segments"):
-        return [scan_recordings(recordings, c, engine=engine, hop=hop, law=law, channel=channel, stats=stats, sample_rate=sample_rate)
-                for c in configs]
+        return [scan_recordings(recordings, c, engine=engine, hop=hop, law=law, channel=channel, stats=stats, sample_rate=sample_rate,
+                                open_end=open_end) for c in configs]
+    if open_end:
+        _need_tails(engine, "sweep_recordings", "resegment_tails")
     split = isinstance(channel, str) and channel == "split"
     if not (channel in ("mix", "split") if isinstance(channel, str) else isinstance(channel, (int, np.integer)) and int(channel) in (0, 1)):
         raise ConfigurationError("channel", repr(channel), f"sweep_recordings: channel is 'mix', 0, 1 or 'split' for the whole corpus, got {channel!r}")
@@ -197,6 +226,9 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
                                      channel=channel, **kw)
                 sets = [_thresholds_of(c) for c in configs]
                 tables = [t for k in range(0, len(sets), 64) for t in engine.resegment(sets[k:k + 64])]      # 64 sets per replay
+                if open_end:
+                    tails = [t for k in range(0, len(sets), 64) for t in engine.resegment_tails(sets[k:k + 64])]
+                    tables = [_with_tails(t, tl) for t, tl in zip(tables, tails)]
         finally:
             for s in slots:
                 engine.close_stream(int(s))
@@ -208,7 +240,7 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
 
 def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
                    law: Optional[str] = None, channel="mix", layout: str = "frames", wav: bool = True,
-                   sample_rate: Optional[int] = None) -> List:
+                   sample_rate: Optional[int] = None, open_end: bool = False) -> List:
     """``scan_recordings`` with each finished segment's audio: per recording ``[(start_sample, end_sample, payload), ...]`` (per
     channel for ``"split"``, as there).  ``payload`` is what ``VADWrapper``'s ``voice_end`` callback delivers for the same
     recording - the segment's frames back to back, decoded, mixed and gated as the model read them, as 16-bit PCM behind the WAV
@@ -220,7 +252,8 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
     samples, and the scan is the rate scan (``Engine.scan_segments(sample_rate=...)``).  ``layout="frames"`` is still the
     ``voice_end`` payload - the 16 kHz frames the model read, each chunk resampled on the GPU and gated, behind the header of
     ``config.output_wav_sample_rate``; ``layout="range"`` gives the samples ``[start_sample, end_sample)`` of the recording itself,
-    at its own rate and not gated, behind a header that carries ``sample_rate``."""
+    at its own rate and not gated, behind a header that carries ``sample_rate``.
+    ``open_end`` as in ``scan_recordings``: the segment still open at a recording's last frame is cut like any other."""
     from .pool import default_pool, resolve_model_path
     from .utils.wav_writer import WAVWriter
     split = isinstance(channel, str) and channel == "split"
@@ -231,6 +264,8 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
     cfg = config or VADConfig()
     if engine is None:
         engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
+    if open_end:
+        _need_tails(engine, "cut_recordings")
     frame = engine.frame_samples
     if cfg.buffer_size != frame:
         raise ConfigurationError(f"cut_recordings frames at the model's frame size: buffer_size = {cfg.buffer_size}, "
@@ -259,7 +294,8 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
                                                cfg.voice_end_ratio, cfg.voice_start_frame_count, cfg.voice_end_frame_count))
             with engine.scan_session():
                 # (recording, channel) -> its sample ranges; the cut's table lists them in that order
-                ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, denoise, channel, rate=rate)
+                ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, denoise, channel, rate=rate,
+                                      open_end=open_end)
                 table = [(int(engine.last_scan["offsets"][k]), a // hop, (b - a - frame) // hop + 1, chans[c])
                          for k, rc in enumerate(ranges) for c, rg in enumerate(rc) for a, b in rg]
                 if table:

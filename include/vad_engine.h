@@ -419,7 +419,7 @@ VAD_API int vad_scan_cut_device(vad_engine *e, const vad_cut_item *items, int64_
  * item is the last i with out_start[i] <= k (items without frames own no index); with e = k - out_start[i] and L = seg_frames[k] the
  * record holds item = i, first_frame = e - L + 1, nframes = L.  first_frame is negative when the stream entered the recording inside
  * a segment (a slot continued from an earlier call), as cutter_vad_amd.scan.speech_segments reports such a segment.  A segment still
- * open at a recording's last frame has no END and no record.
+ * open at a recording's last frame has no END and no record in this table; vad_scan_tails (below) reports it, in an array of its own.
  *   Order: ascending k - the caller's item order, then frame order - whatever the GPU's scheduling.
  *   Statistics: over the frames t = max(first_frame, 0) .. e of the item whose events have VAD_EV_REJECTED clear: `counted` is their
  * number, max_prob their maximum, and mean_prob = (float)((double)S / ((double)counted * 0x1p30)) with
@@ -571,6 +571,49 @@ VAD_API int vad_resegment_device(vad_engine *e, const uint8_t *d_events, const f
                                  int64_t *d_set_start /*on the GPU, [nt + 1]*/, void *stream);
 VAD_API int vad_scan_resegment(vad_engine *e, const vad_thresholds *t, int64_t nt, vad_segment *segs_out, int64_t seg_cap,
                                int64_t *set_start_out /*[nt + 1]*/);
+
+/*
+ * Tails: the segment still open at a recording's last frame.  An END needs voice_end_frame_count low frames (50 by default: 0.8 s at
+ * a hop of 256 samples), so a recording that stops sooner behind its last word has no END for it and the tables above do not list
+ * it.  That is right for a stream, which may go on; a scan is handed finished recordings.  The length of an open segment includes
+ * the frames buffered before its START, which only the state machine knows - so the engine reports it: one vad_segment per item, in
+ * an array of its own.  Tails never enter a segment table: no table of the calls above changes by a byte.
+ *   Definition.  Item i has nf frames; S is its stream's state machine behind the last of them.  The item has a tail iff nf >= 1,
+ * S.active is set and L = S.seg_frames >= 1.  The record is then {item = i, first_frame = nf - L, nframes = L} - the END formula
+ * e - L + 1 with e = nf - 1; first_frame is negative when the slot entered the recording inside a segment - and counted, mean_prob
+ * and max_prob follow the vad_segment rule over the frames max(first_frame, 0) .. nf - 1: the fixed-point sum, rejected frames left
+ * out, both statistics 0 when counted == 0.  No tail: all 24 bytes of the record are zero (nframes == 0 says so).
+ *   In a replay S is the fresh state machine of set k stepped over the item's accepted frames (vad_scan_resegment's rule), and
+ * entry [k * n + i] is the tail of set k, item i.
+ *
+ * vad_scan_tails: the tails of this engine's last vad_scan_segments / vad_scan_rate_segments, tails_out [n] in host memory, n = that
+ * call's item count.  The scan itself saves each item's length in an engine-owned array - one small launch behind its model
+ * launches, which is no model launch: vad_info.steps and vad_info.frames count what they counted - so vad_stream_reset, _close,
+ * _restore or _set_thresholds behind the scan do not change the answer.  Needs the mark of vad_scan_resegment (without it:
+ * VAD_ERR_INVALID_ARG, "vad_scan_tails: no scan results are resident"); further VAD_ERR_INVALID_ARG, nothing written: n is not the
+ * scan's item count; a null tails_out with n > 0.  Touches no stream, not the table of vad_scan_segments_read, not
+ * vad_scan_resegment's, not the resident block: vad_scan_cut(audio = NULL) cuts a tail like any other record.
+ *
+ * vad_scan_resegment_tails: the tails under nt other threshold sets, tails_out [nt * n]; the mark, n and tails_out as above, t and
+ * nt as vad_scan_resegment checks them.
+ *
+ * vad_tails_device: the tails of the items a *_device scan ran on `slots` (host [n], the items' streams in item order; checked as
+ * the scans check them: open, none twice - VAD_ERR_BAD_SLOT).  d_events (16-byte aligned) and d_probs as that scan wrote them,
+ * out_start its host array [n + 1], d_tails (16-byte aligned, [n]) on the GPU.  The launch reads the slots' state machines when it
+ * runs on `stream` (NULL = the engine's own): enqueue it behind the scan and before anything else that steps those streams.
+ * vad_resegment_tails_device: the replay form, d_tails [nt * n]; its checks are vad_resegment_device's (no seg_cap, d_segs or
+ * d_set_start here; a null d_tails with n > 0 is refused).  Both work on every engine - Silero V4, VAD_ENGINE_SHARED_GPU and the
+ * 8 kHz sub-models included: no model kernel runs - both wait for earlier *_device launches as the scans do, and the next such call
+ * waits for theirs.  A refused call writes nothing.
+ *   VAD_ABI_VERSION is unchanged: the presence of vad_scan_tails is how a caller detects the feature.
+ */
+VAD_API int vad_scan_tails(vad_engine *e, vad_segment *tails_out /*[n]*/, int64_t n);
+VAD_API int vad_scan_resegment_tails(vad_engine *e, const vad_thresholds *t, int64_t nt, vad_segment *tails_out /*[nt * n]*/, int64_t n);
+VAD_API int vad_tails_device(vad_engine *e, const int64_t *slots /*host [n]*/, const uint8_t *d_events, const float *d_probs,
+                             const int64_t *out_start /*host [n + 1]*/, int64_t n, vad_segment *d_tails /*on the GPU, [n]*/, void *stream);
+VAD_API int vad_resegment_tails_device(vad_engine *e, const uint8_t *d_events, const float *d_probs, const int64_t *out_start /*host [n + 1]*/,
+                                       int64_t n, const vad_thresholds *t, int64_t nt, vad_segment *d_tails /*on the GPU, [nt * n]*/,
+                                       void *stream);
 
 /*
  * Pipelined host ingest.  vad_step* on host pointers are copy -> kernel -> copy -> wait; at 8 192 streams the PCIe copy is

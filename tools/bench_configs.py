@@ -956,6 +956,60 @@ def scan_resegment():
     return row
 
 
+def scan_tails():
+    """What the tails cost, on scan_resegment's corpus: VAD_SCAN_BENCH_N (default 1 024) int16 recordings of 30 s at
+    16 kHz in one call, hop 256.  Engine.scan_segments - with VAD_BENCH_TREE set to a checkout of the parent commit the same lines
+    time the scan without the snapshot launch; the difference is that launch - then, where the engine has them, Engine.scan_tails and
+    Engine.resegment_tails with 1 and 64 sets.  One warm-up, then three timed passes of each in one process; wall clock, medians."""
+    import time
+    import numpy as np
+    import cutter_vad_amd
+    N = int(os.environ.get("VAD_SCAN_BENCH_N", "1024"))
+    eng = Engine(blob(5), max_streams=max(N, 16))
+    hop = 256
+    gold = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "speech16k_i16.npz")
+    pcm = np.tile(np.load(gold)["pcm"].astype(np.int16), 3)
+    rng = np.random.default_rng(N)
+    ns = 30 * 16000
+    recs = [pcm[a:a + ns] for a in rng.integers(0, pcm.size - ns + 1, N)]
+    base = [(0.4, 0.3, 0.8, 0.95, 6, 12), (0.7, 0.7, 0.8, 0.95, 10, 50), (0.3, 0.2, 0.8, 0.95, 2, 2), (0.5, 0.35, 0.6, 0.9, 4, 57),
+            (0.85, 0.6, 0.5, 0.75, 3, 8)]
+    sets = [(a - 0.004 * (k // 5), b - 0.003 * (k // 5), c, d, m + (k // 5) % 3, n + (k // 5) % 4) for k in range(64) for a, b, c, d, m, n in [base[k % 5]]]
+    slots = eng.open_streams(N)
+    med = lambda v: float(np.median(v))
+
+    def passes(fn):
+        fn()
+        runs = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            out = fn()
+            runs.append(time.perf_counter() - t0)
+        return runs, out
+
+    def full_scan():
+        eng.reset(slots)
+        eng.set_thresholds_many(slots, sets[1])
+        return eng.scan_segments(slots, recs, hop=hop, denoise=0.01)
+
+    row = {"config": f"scan_tails: {N} int16 recordings of 30 s at 16 kHz in one call, hop {hop}, the default thresholds",
+           "tree": os.path.dirname(os.path.dirname(os.path.abspath(cutter_vad_amd.__file__))), "recordings": N,
+           "frames": N * eng.scan_frame_count(ns, hop), "passes": 3}
+    with eng.scan_session():
+        runs, table = passes(full_scan)
+        row["s_scan_segments_runs"], row["s_scan_segments"], row["records"] = runs, med(runs), int(len(table))
+        row["s_scan_segments_spread"] = max(runs) - min(runs)
+        if hasattr(eng, "scan_tails"):
+            runs, tails = passes(eng.scan_tails)
+            row["s_scan_tails_runs"], row["s_scan_tails"], row["tails"] = runs, med(runs), int((tails["nframes"] > 0).sum())
+            for nt in (1, 64):
+                runs, per_set = passes(lambda: eng.resegment_tails(sets[:nt]))
+                row[f"s_resegment_tails_nt{nt}_runs"], row[f"s_resegment_tails_nt{nt}"] = runs, med(runs)
+                row[f"tails_nt{nt}"] = int(sum((t["nframes"] > 0).sum() for t in per_set))
+    eng.close()
+    return row
+
+
 def scan_rate():
     """Whole recordings at 48 kHz, resampled on the GPU in the scan: vad_scan_rate_device on VAD_SCAN_BENCH_N (default
     4 096) int16 recordings of 30 s at 48 kHz - the golden clip, every sample three times - already in device memory, hop = chunk / 2,

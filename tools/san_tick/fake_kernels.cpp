@@ -252,6 +252,61 @@ extern "C" hipError_t vadk_launch_reseg_count(const ResegArgs *a, hipStream_t) {
     return hipSuccess;
 }
 
+// the tails (csrc/scan_tails.hip; csrc/scan_resegment.hip: vadk_tails_reseg_count), in plain C++: the length of the segment open
+// behind an item's last frame out of the stream's slot, or out of a replay over the real sm_step; then one record per entry
+static uint32_t fake_tail_len(const SmSlot &s, bool any) { return any && s.active != 0 && s.seg_frames >= 1 ? (uint32_t)s.seg_frames : 0u; }
+
+extern "C" hipError_t vadk_launch_tail_snapshot(const TailArgs *a, hipStream_t) {
+    for (int32_t i = 0; i < a->n; ++i) a->tail_len[i] = fake_tail_len(a->sm[a->slots[i]], a->out_start[i + 1] > a->out_start[i]);
+    return hipSuccess;
+}
+
+extern "C" hipError_t vadk_launch_reseg_tails(const ResegArgs *a, uint32_t *tail_len, hipStream_t) {
+    for (int32_t set = 0; set < a->nt; ++set)
+        for (int32_t item = 0; item < a->n; ++item) {
+            SmSlot s = a->sm0[set];
+            const uint32_t k0 = (uint32_t)a->out_start[item], k1 = (uint32_t)a->out_start[item + 1];
+            uint32_t j = 0;
+            for (uint32_t k = k0; k < k1; ++k) {
+                if (a->events[k] & EV_REJECTED) continue;
+                int L = 0;
+                j += (sm_step(s, a->probs[k], &L) & 2) ? 1u : 0u;
+            }
+            a->cnt[(size_t)set * (size_t)a->n + (size_t)item] = j;
+            tail_len[(size_t)set * (size_t)a->n + (size_t)item] = fake_tail_len(s, k1 > k0);
+        }
+    return hipSuccess;
+}
+
+extern "C" hipError_t vadk_launch_seg_tails(const TailArgs *a, hipStream_t) {
+    for (long long q = 0; q < (long long)a->n * a->nt; ++q) {
+        SegRecord r{0, 0, 0, 0, 0.0f, 0.0f};
+        const uint32_t L = a->tail_len[q];
+        const int32_t item = (int32_t)(q % a->n);
+        const uint32_t base = (uint32_t)a->out_start[item], nf = (uint32_t)a->out_start[item + 1] - base;
+        if (L != 0u && L <= 0x7fffffffu && nf != 0u) {
+            r.item = item;
+            r.first_frame = (int32_t)nf - (int32_t)L;
+            r.nframes = (int32_t)L;
+            long long S = 0;
+            float mx = -INFINITY;
+            for (uint32_t t = L < nf ? nf - L : 0u; t < nf; ++t) {
+                if (a->events[base + t] & EV_REJECTED) continue;
+                const float p = a->probs[base + t];
+                r.counted += 1;
+                S += (long long)std::rint((double)p * (double)(1ll << SEG_PROB_SHIFT));
+                mx = std::fmax(mx, p);
+            }
+            if (r.counted > 0) {
+                r.mean_prob = (float)((double)S / ((double)r.counted * (double)(1ll << SEG_PROB_SHIFT)));
+                r.max_prob = mx;
+            }
+        }
+        a->tails[q] = r;
+    }
+    return hipSuccess;
+}
+
 extern "C" hipError_t vadk_launch_reseg_fill(const ResegArgs *a, hipStream_t) {
     if (a->seg_cap == 0) return hipSuccess;
     for (int32_t set = 0; set < a->nt; ++set)
