@@ -147,6 +147,14 @@ class Segment(C.Structure):
 SEGMENT_DTYPE = np.dtype([("item", np.int32), ("first_frame", np.int32), ("nframes", np.int32), ("counted", np.int32),
                           ("mean_prob", np.float32), ("max_prob", np.float32)])
 
+class Refine(C.Structure):
+    _fields_ = [("pad_before", C.c_int32), ("pad_after", C.c_int32), ("merge_gap", C.c_int32), ("min_frames", C.c_int32),
+                ("max_frames", C.c_int32), ("reserved", C.c_int32)]
+
+
+# a host table of no records still needs an address: a null segs_in names vad_scan_refine's resident table
+EMPTY_TABLE = np.zeros(1, SEGMENT_DTYPE)
+
 VAD_WORK_START, VAD_WORK_END, VAD_WORK_CONTINUE, VAD_WORK_PAYLOAD, VAD_WORK_LONG = 1, 2, 4, 8, 16
 VAD_WORK_REJECTED = 32
 
@@ -245,6 +253,9 @@ SIGNATURES = {
     "vad_scan_resegment_tails": (C.c_int, [_vp, C.POINTER(Thresholds), C.c_int64, C.POINTER(Segment), C.c_int64]),
     "vad_tails_device": (C.c_int, [_vp, _i64p, _vp, _vp, _i64p, C.c_int64, _vp, _vp]),
     "vad_resegment_tails_device": (C.c_int, [_vp, _vp, _vp, _i64p, C.c_int64, C.POINTER(Thresholds), C.c_int64, _vp, _vp]),
+    "vad_refine_device": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _i64p, C.c_int64, C.POINTER(Refine), _vp, C.c_int64, _vp, _vp]),
+    "vad_scan_refine": (C.c_int, [_vp, C.POINTER(Segment), C.c_int64, C.POINTER(Segment), C.POINTER(Refine), C.POINTER(Segment), C.c_int64,
+                                  _i64p]),
     "vad_scan_rate_segments": (C.c_int, [_vp, C.POINTER(ScanChItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32,
                                          C.c_float, C.POINTER(Segment), C.c_int64, _i64p]),
     "vad_rate_cut_samples": (C.c_int64, [_vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),

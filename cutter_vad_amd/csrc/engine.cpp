@@ -50,6 +50,8 @@ extern "C" hipError_t vadk_launch_reseg_fill(const vadk::ResegArgs *a, hipStream
 extern "C" hipError_t vadk_launch_reseg_tails(const vadk::ResegArgs *a, uint32_t *tail_len, hipStream_t stream);
 extern "C" hipError_t vadk_launch_tail_snapshot(const vadk::TailArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_seg_tails(const vadk::TailArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_refine_count(const vadk::RefineArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_refine_fill(const vadk::RefineArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_resample(const vadk::ScanResampleArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_cut_resample(const vadk::CutResampleArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_resample(const vadk::ResampleParams *p, hipStream_t stream);
@@ -194,6 +196,12 @@ struct vad_engine {
     uint32_t *d_tail_len = nullptr; size_t d_tail_len_cap = 0;
     uint8_t *d_tailwork = nullptr; size_t d_tailwork_cap = 0;
     std::vector<int32_t> tail_up;
+    // vad_refine_device / vad_scan_refine: the work area (refine_count lays it out: out_start as int32, the items' first records,
+    // their counts; refine_up = out_start as it was uploaded), and vad_scan_refine's input - count, table, tails - and output
+    uint8_t *d_refine = nullptr; size_t d_refine_cap = 0;
+    std::vector<int32_t> refine_up;
+    uint8_t *d_refine_in = nullptr; size_t d_refine_in_cap = 0;
+    vadk::SegRecord *d_refine_out = nullptr; size_t d_refine_out_cap = 0;
     // G.711 frames expanded to int16 for the kernels whose loaders do not decode them (launch())
     int16_t *d_g711 = nullptr; size_t d_g711_cap = 0;
     // small calls (a few streams: the one-wrapper-per-client pattern): ONE pinned block in, ONE pinned block out
@@ -889,7 +897,7 @@ void vad_engine_destroy(vad_engine *e) {
     weights_release(e->d_wstream16);
     weights_release(e->d_wstream16x);
     weights_release(e->d_wstream16y);
-    void *bufs[] = {e->d_tail_len, e->d_tailwork, e->d_reseg, e->d_resegtab, e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots, e->d_g711,
+    void *bufs[] = {e->d_refine, e->d_refine_in, e->d_refine_out, e->d_tail_len, e->d_tailwork, e->d_reseg, e->d_resegtab, e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots, e->d_g711,
                     e->d_audio, e->d_items, e->d_win, e->d_items_win, e->d_cut, e->d_cut_out, e->d_segwork, e->d_nsegs, e->d_segtab, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
@@ -2526,6 +2534,185 @@ int vad_resegment_tails_device(vad_engine *e, const uint8_t *d_events, const flo
     }
     if (int rc2 = scan_mark_pending(e, s)) return rc2;
     return rc;
+}
+
+}  // extern "C"
+
+// ---- segment tables refined: padded, merged, thinned, split (vad_refine_device, vad_scan_refine) ------------------------------
+namespace {
+
+static_assert(sizeof(vad_refine) == 24, "vad_refine layout");
+
+// what both entry points check about the rule and the capacity
+int refine_check_rule(vad_engine *e, const char *who, const vad_refine *r, int64_t seg_cap) {
+    if (!r) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null rule", who);
+    if (r->pad_before < 0 || r->pad_after < 0)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: pad_before = %d, pad_after = %d: a pad is 0 or more frames", who,
+                       (int)r->pad_before, (int)r->pad_after);
+    if (r->merge_gap < -1)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: merge_gap = %d: -1 (never join) or a gap of 0 or more frames", who,
+                       (int)r->merge_gap);
+    if (r->max_frames < 0 || r->max_frames == 1)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: max_frames = %d: 0 (no limit) or at least 2 frames", who, (int)r->max_frames);
+    if (r->reserved != 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: reserved = %d: must be 0", who, (int)r->reserved);
+    if (seg_cap < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: seg_cap = %lld: bad count", who, (long long)seg_cap);
+    return VAD_OK;
+}
+
+// The first half of a refinement on `s`: out_start (checked as seg_launches wants it) goes up, then heads, count and prefix - the
+// true count is in *d_nsegs_out behind them.
+int refine_count(vad_engine *e, const vadk::SegRecord *d_segs_in, const long long *d_nsegs_in, int64_t in_cap, const vadk::SegRecord *d_tails,
+                 const uint8_t *d_events, const float *d_probs, const int64_t *out_start, int64_t n, const vad_refine *r, long long *d_nsegs_out,
+                 hipStream_t s, vadk::RefineArgs *a) {
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_first = up16(sizeof(int32_t) * (size_t)(n + 1)), o_cnt = o_first + up16(sizeof(uint32_t) * (size_t)n);
+    if (int rc = ensure(e, e->d_refine, e->d_refine_cap, o_cnt + sizeof(unsigned long long) * (size_t)n + 16)) return rc;
+    e->refine_up.resize((size_t)n + 1);
+    for (int64_t i = 0; i <= n; ++i) e->refine_up[(size_t)i] = n > 0 ? (int32_t)out_start[i] : 0;
+    HIP_TRY(e, hipMemcpyAsync(e->d_refine, e->refine_up.data(), sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice, s));
+    *a = vadk::RefineArgs{};
+    a->segs_in = d_segs_in;
+    a->nsegs_in = d_nsegs_in;
+    a->tails = d_tails;
+    a->events = d_events;
+    a->probs = d_probs;
+    a->out_start = reinterpret_cast<const int32_t *>(e->d_refine);
+    a->first = reinterpret_cast<uint32_t *>(e->d_refine + o_first);
+    a->cnt = reinterpret_cast<unsigned long long *>(e->d_refine + o_cnt);
+    a->nsegs_out = d_nsegs_out;
+    a->in_cap = (uint32_t)in_cap;
+    a->n = (int32_t)n;
+    a->pad_before = r->pad_before;
+    a->pad_after = r->pad_after;
+    a->merge_gap = r->merge_gap;
+    a->min_frames = r->min_frames;
+    a->max_frames = r->max_frames;
+    const hipError_t rr = vadk_launch_refine_count(a, s);
+    if (rr != hipSuccess) return e->hip_fail(rr, "kernel launch (refine count)");
+    return VAD_OK;
+}
+
+// ... and the second: the records into d_segs (room for seg_cap of them), their cuts, then their statistics
+int refine_fill(vad_engine *e, vadk::RefineArgs *a, vadk::SegRecord *d_segs, int64_t seg_cap, hipStream_t s) {
+    a->segs_out = d_segs;
+    a->seg_cap = (uint32_t)std::min<int64_t>(seg_cap, INT32_MAX);
+    hipError_t r = vadk_launch_refine_fill(a, s);
+    if (r != hipSuccess) return e->hip_fail(r, "kernel launch (refine fill)");
+    vadk::SegArgs st{};
+    st.events = a->events;
+    st.probs = a->probs;
+    st.out_start = a->out_start;
+    st.segs = d_segs;
+    st.nsegs = a->nsegs_out;
+    st.seg_cap = a->seg_cap;
+    st.n = a->n;
+    r = a->n > 0 ? vadk_launch_seg_stats(&st, a->seg_cap, s) : hipSuccess;
+    if (r != hipSuccess) return e->hip_fail(r, "kernel launch (segment statistics)");
+    return VAD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vad_refine_device(vad_engine *e, const vad_segment *d_segs_in, const int64_t *d_nsegs_in, int64_t in_cap, const vad_segment *d_tails,
+                      const uint8_t *d_events, const float *d_probs, const int64_t *out_start, int64_t n, const vad_refine *r,
+                      vad_segment *d_segs_out, int64_t seg_cap, int64_t *d_nsegs_out, void *stream) {
+    static const char *who = "vad_refine_device";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    if (int rc = refine_check_rule(e, who, r, seg_cap)) return rc;
+    if (n < 0 || in_cap < 0)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n = %lld, in_cap = %lld: bad count", who, (long long)n, (long long)in_cap);
+    if (n > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 items", who);
+    if (in_cap > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 input records", who);
+    if ((n > 0 && !out_start) || !d_nsegs_in || !d_nsegs_out || (in_cap > 0 && !d_segs_in) || (seg_cap > 0 && !d_segs_out))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    int64_t total = 0;
+    if (int rc = tail_check_start(e, who, out_start, n, &total)) return rc;
+    if (total > 0 && (!d_events || !d_probs)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if ((reinterpret_cast<uintptr_t>(d_events) & 15) || (reinterpret_cast<uintptr_t>(d_segs_in) & 15) || (reinterpret_cast<uintptr_t>(d_tails) & 15) ||
+        (reinterpret_cast<uintptr_t>(d_segs_out) & 15))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the events, the segment tables and the tails must be 16-byte aligned", who);
+    if (reinterpret_cast<uintptr_t>(d_probs) & 3) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: probs must be 4-byte aligned", who);
+    if ((reinterpret_cast<uintptr_t>(d_nsegs_in) & 7) || (reinterpret_cast<uintptr_t>(d_nsegs_out) & 7))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the counts must be 8-byte aligned", who);
+    vadk::RefineArgs a;
+    int rc = refine_count(e, reinterpret_cast<const vadk::SegRecord *>(d_segs_in), reinterpret_cast<const long long *>(d_nsegs_in), in_cap,
+                          reinterpret_cast<const vadk::SegRecord *>(d_tails), d_events, d_probs, out_start, n, r,
+                          reinterpret_cast<long long *>(d_nsegs_out), s, &a);
+    if (rc == VAD_OK && seg_cap > 0) rc = refine_fill(e, &a, reinterpret_cast<vadk::SegRecord *>(d_segs_out), seg_cap, s);
+    // the launches read the engine's work area: the next scan, cut, extraction, replay or refinement waits for them
+    if (int rc2 = scan_mark_pending(e, s)) return rc2;
+    return rc;
+}
+
+int vad_scan_refine(vad_engine *e, const vad_segment *segs_in, int64_t nsegs_in, const vad_segment *tails_in, const vad_refine *r,
+                    vad_segment *segs_out, int64_t seg_cap, int64_t *nsegs_out) {
+    static const char *who = "vad_scan_refine";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    if (int rc = refine_check_rule(e, who, r, seg_cap)) return rc;
+    if (!nsegs_out || (seg_cap > 0 && !segs_out)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if (!e->scan_results || e->seg_out_start.empty())
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: no scan results are resident: the engine's last vad_scan_segments or "
+                                            "vad_scan_rate_segments failed, or a later call has reused its per-frame arrays", who);
+    const int64_t n = (int64_t)e->seg_out_start.size() - 1;
+    if (segs_in) {
+        if (nsegs_in < 0 || nsegs_in > INT32_MAX)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: nsegs_in = %lld: bad count", who, (long long)nsegs_in);
+        for (int64_t k = 0; k < nsegs_in; ++k) {
+            if (segs_in[k].item < 0 || segs_in[k].item >= n)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: record %lld names item %d: the scan had %lld items", who, (long long)k,
+                               (int)segs_in[k].item, (long long)n);
+            if (k > 0 && segs_in[k].item < segs_in[k - 1].item)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the items decrease at record %lld (%d after %d)", who, (long long)k,
+                               (int)segs_in[k].item, (int)segs_in[k - 1].item);
+            if (segs_in[k].nframes < 1)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: record %lld has nframes = %d", who, (long long)k, (int)segs_in[k].nframes);
+        }
+    } else {
+        if (e->segtab_count < 0)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the engine holds no segment table: no vad_scan_segments has built one", who);
+        nsegs_in = e->segtab_count;
+    }
+    if (n == 0 || e->seg_out_start[(size_t)n] == 0) {       // no frame: every record is clipped away
+        *nsegs_out = 0;
+        return VAD_OK;
+    }
+    // count, table and tails of a host input, and the output count, in one engine-owned block
+    const size_t o_tab = 16, o_tails = o_tab + sizeof(vad_segment) * (size_t)(segs_in ? nsegs_in : 0);
+    if (int rc = ensure(e, e->d_refine_in, e->d_refine_in_cap, o_tails + (tails_in ? sizeof(vad_segment) * (size_t)n : 0) + 16)) return rc;
+    const long long head[2] = {(long long)nsegs_in, 0};
+    HIP_TRY(e, hipMemcpyAsync(e->d_refine_in, head, sizeof head, hipMemcpyHostToDevice, e->stream));
+    if (segs_in && nsegs_in > 0)
+        HIP_TRY(e, hipMemcpyAsync(e->d_refine_in + o_tab, segs_in, sizeof(vad_segment) * (size_t)nsegs_in, hipMemcpyHostToDevice, e->stream));
+    if (tails_in) HIP_TRY(e, hipMemcpyAsync(e->d_refine_in + o_tails, tails_in, sizeof(vad_segment) * (size_t)n, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));             // `head` is this frame's, the rest the caller's
+    long long *d_count = reinterpret_cast<long long *>(e->d_refine_in);
+    vadk::RefineArgs a;
+    if (int rc = refine_count(e, segs_in ? reinterpret_cast<const vadk::SegRecord *>(e->d_refine_in + o_tab) : e->d_segtab, d_count, nsegs_in,
+                              tails_in ? reinterpret_cast<const vadk::SegRecord *>(e->d_refine_in + o_tails) : nullptr, e->d_events, e->d_probs,
+                              e->seg_out_start.data(), n, r, d_count + 1, e->stream, &a))
+        return rc;
+    long long count = 0;
+    HIP_TRY(e, hipMemcpyAsync(&count, d_count + 1, sizeof count, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    if (count > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %lld records: more than 2^31 - 1 in one call", who, count);
+    const int64_t take = std::min<int64_t>(count, seg_cap);
+    if (take > 0) {
+        if (int rc = ensure(e, e->d_refine_out, e->d_refine_out_cap, sizeof(vadk::SegRecord) * (size_t)take)) return rc;
+        if (int rc = refine_fill(e, &a, e->d_refine_out, take, e->stream)) return rc;
+        HIP_TRY(e, hipMemcpyAsync(segs_out, e->d_refine_out, sizeof(vad_segment) * (size_t)take, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(e, hipStreamSynchronize(e->stream));
+    }
+    *nsegs_out = count;
+    return VAD_OK;
 }
 
 // ---- pipelined host ingest ---------------------------------------------------------------------------------------

@@ -342,6 +342,34 @@ struct TailArgs {
     int32_t nt;               // sets; 1 on the scan path
 };
 
+// a segment table refined - clipped, merged, dropped, padded, split - by the rule of include/vad_engine.h's vad_refine
+// (csrc/scan_refine.hip; vad_refine_device, vad_scan_refine).  The input is the first min(*nsegs_in, in_cap) records of segs_in and,
+// where tails is given, the tail of each item as its last record.  first[i] is the table position of the first record that names
+// item i behind a record that does not (the head of the item's first run; REFINE_NONE: no record names it): a thread per item walks
+// that run twice around a prefix - cnt[i] = the item's output records, then their exclusive prefix, the total in *nsegs_out - and
+// the second walk writes the records; a piece of a split carries its window in the fields the statistics overwrite later
+// (counted = the half width h, the bits of mean_prob = REFINE_CUT_FIRST | REFINE_CUT_END: which of its two ends is searched), and
+// one wave per written record then moves those ends to the quietest accepted frame of their windows.
+constexpr int REFINE_THREADS = 256;
+constexpr uint32_t REFINE_NONE = 0xffffffffu;
+constexpr int REFINE_CUT_FIRST = 1, REFINE_CUT_END = 2;
+struct RefineArgs {
+    const SegRecord *segs_in; // [in_cap]
+    const long long *nsegs_in;
+    const SegRecord *tails;   // [n], or nullptr
+    const uint8_t *events;    // [out_start[n]]: VAD_EV_REJECTED alone is read
+    const float *probs;
+    const int32_t *out_start; // [n + 1] on the device, as SegArgs::out_start
+    uint32_t *first;          // [n]
+    unsigned long long *cnt;  // [n]
+    SegRecord *segs_out;      // [seg_cap]
+    long long *nsegs_out;     // the true count
+    uint32_t in_cap;          // <= 2^31 - 1
+    uint32_t seg_cap;         // records at positions >= seg_cap are dropped (<= 2^31 - 1)
+    int32_t n;                // items
+    int32_t pad_before, pad_after, merge_gap, min_frames, max_frames;      // vad_refine, checked by the host
+};
+
 // resampler launch parameters (csrc/resample.hip)
 struct ResampleSeg {
     const float *wstream;     // folded operator (pack_weights.cpp: pack_resample_operator)

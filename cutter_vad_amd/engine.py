@@ -567,6 +567,54 @@ class Engine:
         self._check(self._lib.vad_resegment_tails_device(self._h, d_events or None, d_probs or None, _ptr(start, C.c_int64),
                                                          max(start.size - 1, 0), sets, nt, d_tails or None, stream or None))
 
+    @staticmethod
+    def _refine_rule(rule) -> _ffi.Refine:
+        """``SegmentRefine``, any object with its six fields, or a 6-sequence in the struct's order -> ``vad_refine``"""
+        names = ("pad_before", "pad_after", "merge_gap", "min_frames", "max_frames", "reserved")
+        vals = [getattr(rule, k) for k in names] if hasattr(rule, "pad_before") else list(rule)
+        if len(vals) != 6:
+            raise AudioProcessingError(f"Model prediction failed: a refine rule has six fields, got {len(vals)}")
+        return _ffi.Refine(*[int(v) for v in vals])
+
+    def refine(self, rule, table: Optional[np.ndarray] = None, tails: Optional[np.ndarray] = None) -> np.ndarray:
+        """A segment table padded, merged, thinned and split on the GPU (``vad_scan_refine``; the rule is ``vad_refine``'s in
+        include/vad_engine.h, ``rule`` a :class:`~cutter_vad_amd.scan.SegmentRefine`), against the per-frame results the last
+        ``scan_segments`` left there: a long segment is cut at the quietest frame near the cut point, and ``counted``,
+        ``mean_prob`` and ``max_prob`` are those of the new ranges.  ``table``: what ``scan_segments`` returned or one table of
+        ``resegment`` (sorted by item); None: the scan's own table, which never left the GPU.  ``tails``: ``scan_tails()`` or one
+        array of ``resegment_tails`` - each item's open segment joins its records as the last one.  No upload but these, no model
+        launch, no stream touched; the resident block stays, and ``cut(audio=None)`` cuts the refined records like any others.  Call
+        it inside ``scan_session()``, behind the ``scan_segments``."""
+        rl = self._refine_rule(rule)
+        seg_p = C.POINTER(_ffi.Segment)
+        tab = None if table is None else np.ascontiguousarray(table, dtype=_ffi.SEGMENT_DTYPE).reshape(-1)
+        tl = None if tails is None else np.ascontiguousarray(tails, dtype=_ffi.SEGMENT_DTYPE).reshape(-1)
+        with self._scan_lock:
+            if tl is not None and tl.size != (self._tail_items or 0):
+                raise AudioProcessingError(f"Model prediction failed: refine: {tl.size} tails for the {self._tail_items or 0} items of the scan")
+            src = None if tab is None else tab if tab.size else _ffi.EMPTY_TABLE      # a null table names the resident one
+            where = (self._h, None if src is None else src.ctypes.data_as(seg_p), 0 if tab is None else tab.size,
+                     None if tl is None or tl.size == 0 else tl.ctypes.data_as(seg_p), C.byref(rl))
+            count = C.c_int64(0)
+            self._check(self._lib.vad_scan_refine(*where, None, 0, C.byref(count)))
+            out = np.zeros(count.value, _ffi.SEGMENT_DTYPE)
+            if out.size:
+                self._check(self._lib.vad_scan_refine(*where, out.ctypes.data_as(seg_p), out.size, C.byref(count)))
+        return out[:count.value]
+
+    def refine_device(self, d_segs_in: int, d_nsegs_in: int, in_cap: int, d_tails: int, d_events: int, d_probs: int, out_start, rule,
+                      d_segs_out: int, seg_cap: int, d_nsegs_out: int, stream: int = 0) -> None:
+        """``refine`` on device pointers (integers; ``vad_refine_device``): the first ``min(*d_nsegs_in, in_cap)`` records at
+        ``d_segs_in`` as ``segments_device`` wrote them, ``d_tails`` 0 or the ``n`` records of ``tails_device``, ``d_events`` and
+        ``d_probs`` as ``scan_device`` wrote them, ``out_start`` the positions it returned; the first ``min(count, seg_cap)``
+        refined records go to ``d_segs_out``, the true count to the int64 at ``d_nsegs_out``.  Tables, tails and events 16-byte
+        aligned, the counts 8-byte.  Asynchronous on ``stream``; every engine has it."""
+        rl = self._refine_rule(rule)
+        start = np.ascontiguousarray(out_start, dtype=np.int64).reshape(-1)
+        self._check(self._lib.vad_refine_device(self._h, d_segs_in or None, d_nsegs_in or None, int(in_cap), d_tails or None, d_events or None,
+                                                d_probs or None, _ptr(start, C.c_int64), max(start.size - 1, 0), C.byref(rl), d_segs_out or None,
+                                                int(seg_cap), d_nsegs_out or None, stream or None))
+
     def scan_device(self, slots, offsets, lengths, d_audio: int, audio_samples: int, d_probs: int, d_events: int = 0, d_seg: int = 0,
                     hop: Optional[int] = None, fmt: int = _ffi.VAD_FMT_F32, denoise: Optional[float] = 0.01, stream: int = 0,
                     channels: int = 1, channel=None, sample_rate: Optional[int] = None) -> np.ndarray:

@@ -7,6 +7,7 @@ module is for callers who hold many finished recordings of different lengths and
 
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -14,6 +15,33 @@ import numpy as np
 from . import _ffi
 from .core.config import VADConfig
 from .core.exceptions import ConfigurationError
+
+
+@dataclass(frozen=True)
+class SegmentRefine:
+    """How a segment table is refined behind the state machine (``vad_refine``, include/vad_engine.h, which has the rule in full;
+    ``Engine.refine``).  All six count FRAMES: ``pad_before`` / ``pad_after`` frames of context around each segment (neighbours
+    closer than both pads share the gap), ``merge_gap`` joins segments of a recording whose pause is that many frames or fewer
+    (-1: never), ``min_frames`` drops joined segments shorter than that, before padding (<= 1: keep all), ``max_frames`` splits
+    longer ones at the quietest frame near each cut point (0: no limit, else >= 2).  The default changes nothing."""
+    pad_before: int = 0
+    pad_after: int = 0
+    merge_gap: int = -1
+    min_frames: int = 0
+    max_frames: int = 0
+    reserved: int = 0
+
+    @classmethod
+    def from_durations(cls, hop: int, sample_rate: int, pad_ms: float = 0, merge_gap_ms: Optional[float] = None, min_speech_ms: float = 0,
+                       max_speech_s: Optional[float] = None) -> "SegmentRefine":
+        """The rule in the units of Silero's ``get_speech_timestamps`` (``speech_pad_ms``, ``min_silence_duration_ms``,
+        ``min_speech_duration_ms``, ``max_speech_duration_s``) at a scan's ``hop`` (samples between frames) and ``sample_rate``: a
+        duration becomes the nearest whole number of hops; ``max_speech_s`` is rounded DOWN, so that no record is longer, and is at
+        least 2 frames.  None: no merging, no limit."""
+        frames = lambda ms: int(round(float(ms) * sample_rate / (1000.0 * hop)))
+        pad = frames(pad_ms)
+        return cls(pad, pad, -1 if merge_gap_ms is None else frames(merge_gap_ms), frames(min_speech_ms),
+                   0 if max_speech_s is None else max(int(float(max_speech_s) * sample_rate // hop), 2))
 
 
 def speech_segments(events, seg_frames, frame: int, hop: int) -> List[Tuple[int, int]]:
@@ -67,16 +95,31 @@ def _need_tails(engine, who: str, what: str = "scan_tails") -> None:
                                  f"at a recording's last frame is the state machine's to tell), {type(engine).__name__} has none")
 
 
+def _need_refine(engine, who: str) -> None:
+    if not hasattr(engine, "refine"):
+        raise ConfigurationError("refine", "given", f"{who}: refine= needs an engine with refine (the split reads the per-frame probabilities "
+                                 f"a scan left on the GPU), {type(engine).__name__} has none")
+
+
 def _scan_ranges(engine, slots, recordings, per: int, frame: int, hop: int, law, denoise, channel, stats: bool = False,
-                 rate: Optional[int] = None, open_end: bool = False) -> List[List[List]]:
+                 rate: Optional[int] = None, open_end: bool = False, refine=None) -> List[List[List]]:
     """One scan of ``recordings`` (all 1-D or all two-channel) on ``slots`` -> per recording, per channel scanned of it (``per``),
     the finished segments ``(start_sample, end_sample)`` - with ``stats``: ``(start_sample, end_sample, mean_prob, max_prob)``.
     An engine with ``scan_segments`` builds the table on the GPU and copies back that alone; any other goes through the per-frame
     results of ``scan``.  Same ranges either way.  ``rate``: the recordings' sample rate when it is not the engine's (``frame`` and
     ``hop`` are then a chunk and a hop in input samples; ``vad_scan_rate_segments`` builds the table).  ``open_end``: the segment
-    still open at an item's last frame (``Engine.scan_tails``) is its last range."""
+    still open at an item's last frame (``Engine.scan_tails``) is its last range.  ``refine``: the table - and, with
+    ``open_end``, the tails as each item's last record - goes through ``Engine.refine`` on the GPU; the statistics are the refined records'."""
     sl = np.asarray(slots).reshape(len(recordings), per) if per == 2 else slots
     kw = {} if rate is None else {"sample_rate": rate}
+    if refine is not None:
+        _need_refine(engine, "scan_recordings")
+        if open_end:
+            _need_tails(engine, "scan_recordings")
+        with engine.scan_session():
+            engine.scan_segments(sl, recordings, hop=hop, law=law, denoise=denoise, channel=channel, **kw)
+            table = engine.refine(refine, None, engine.scan_tails() if open_end else None)      # the scan's own table, on the GPU
+        return _table_ranges(table, len(recordings), per, frame, hop, stats)
     if open_end:
         _need_tails(engine, "scan_recordings")
         with engine.scan_session():
@@ -102,7 +145,7 @@ def _scan_ranges(engine, slots, recordings, per: int, frame: int, hop: int, law,
 
 def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
                     law: Optional[str] = None, channel="mix", stats: bool = False, sample_rate: Optional[int] = None,
-                    open_end: bool = False) -> List[List[Tuple]]:
+                    open_end: bool = False, refine: Optional[SegmentRefine] = None) -> List[List[Tuple]]:
     """Speech segments of every recording, one launch sequence for the lot: opens one stream per recording with the config's
     thresholds, scans (frames of ``engine.frame_samples`` at ``hop``, default half a frame as ``VADWrapper`` frames a chunk;
     the config's denoise gate), closes the streams -> per recording ``[(start_sample, end_sample), ...]``.
@@ -118,7 +161,10 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
     ``open_end``: a recording that stops inside speech - before the ``voice_end_frame_count`` low frames an END needs - has no END
     for its last segment, and by default that segment is not listed (a stream may go on).  ``True`` appends it, as the last range
     of its recording or channel: from the first frame the state machine buffered for it to the recording's last frame, with its
-    mean and maximum under ``stats=True`` (``Engine.scan_tails``; an engine object without it: ``ConfigurationError``)."""
+    mean and maximum under ``stats=True`` (``Engine.scan_tails``; an engine object without it: ``ConfigurationError``).
+    ``refine``: a :class:`SegmentRefine` - the segments are padded, merged, thinned and split on the GPU before they are listed
+    (``Engine.refine``; an engine object without it: ``ConfigurationError``): the ranges and, under ``stats=True``, the statistics
+    are the refined records', and with ``open_end=True`` the open segment is refined with the others as its recording's last."""
     from .pool import default_pool, resolve_model_path
     split = isinstance(channel, str) and channel == "split"
     # checked here, not by the scan: a corpus of 1-D recordings alone never shows the value to Engine.scan
@@ -129,6 +175,8 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
         engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
     if open_end:
         _need_tails(engine, "scan_recordings")
+    if refine is not None:
+        _need_refine(engine, "scan_recordings")
     frame = engine.frame_samples
     if cfg.buffer_size != frame:
         raise ConfigurationError(f"scan_recordings frames at the model's frame size: buffer_size = {cfg.buffer_size}, "
@@ -153,7 +201,7 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
             engine.set_thresholds_many(slots, (cfg.vad_start_probability, cfg.vad_end_probability, cfg.voice_start_ratio,
                                                cfg.voice_end_ratio, cfg.voice_start_frame_count, cfg.voice_end_frame_count))
             ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, 0.01 if cfg.enable_denoising else None,
-                                  channel, stats, rate, open_end)
+                                  channel, stats, rate, open_end, refine)
         finally:
             for s in slots:
                 engine.close_stream(int(s))
@@ -169,7 +217,7 @@ def _thresholds_of(cfg: VADConfig) -> Tuple:
 
 def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConfig], engine=None, hop: Optional[int] = None,
                      law: Optional[str] = None, channel="mix", stats: bool = False, sample_rate: Optional[int] = None,
-                     open_end: bool = False) -> List[List]:
+                     open_end: bool = False, refine: Optional[SegmentRefine] = None) -> List[List]:
     """``scan_recordings`` under several configs for the price of one scan: ``sweep_recordings(recs, cfgs, **kw)[j] ==
     scan_recordings(recs, cfgs[j], **kw)``.  The model runs once per kind of recording (1-D, 2-D), with the first config's
     thresholds; the segment tables of all configs then come from ONE replay of the per-frame probabilities that scan left on the
@@ -177,7 +225,8 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
     in the six threshold fields alone; they must agree on what the probabilities depend on - ``model_version``, ``sample_rate``,
     ``buffer_size``, ``enable_denoising`` and ``model_path`` - or ``ConfigurationError`` names the field.  An engine object without
     ``resegment`` is served config by config.  ``open_end`` as in ``scan_recordings``: each config's open segments come from the
-    same replay (``Engine.resegment_tails``)."""
+    same replay (``Engine.resegment_tails``).  ``refine`` as there too: each config's replayed table, with its tails, goes through
+    ``Engine.refine``."""
     from .pool import default_pool, resolve_model_path
     configs = list(configs)
     if not configs:
@@ -193,9 +242,11 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
         engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
     if not hasattr(engine, "resegment") or not hasattr(engine, "scan_segments"):
         return [scan_recordings(recordings, c, engine=engine, hop=hop, law=law, channel=channel, stats=stats, sample_rate=sample_rate,
-                                open_end=open_end) for c in configs]
+                                open_end=open_end, refine=refine) for c in configs]
     if open_end:
         _need_tails(engine, "sweep_recordings", "resegment_tails")
+    if refine is not None:
+        _need_refine(engine, "sweep_recordings")
     split = isinstance(channel, str) and channel == "split"
     if not (channel in ("mix", "split") if isinstance(channel, str) else isinstance(channel, (int, np.integer)) and int(channel) in (0, 1)):
         raise ConfigurationError("channel", repr(channel), f"sweep_recordings: channel is 'mix', 0, 1 or 'split' for the whole corpus, got {channel!r}")
@@ -228,6 +279,9 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
                 tables = [t for k in range(0, len(sets), 64) for t in engine.resegment(sets[k:k + 64])]      # 64 sets per replay
                 if open_end:
                     tails = [t for k in range(0, len(sets), 64) for t in engine.resegment_tails(sets[k:k + 64])]
+                if refine is not None:
+                    tables = [engine.refine(refine, t, tails[k] if open_end else None) for k, t in enumerate(tables)]
+                elif open_end:
                     tables = [_with_tails(t, tl) for t, tl in zip(tables, tails)]
         finally:
             for s in slots:
@@ -240,7 +294,7 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
 
 def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
                    law: Optional[str] = None, channel="mix", layout: str = "frames", wav: bool = True,
-                   sample_rate: Optional[int] = None, open_end: bool = False) -> List:
+                   sample_rate: Optional[int] = None, open_end: bool = False, refine: Optional[SegmentRefine] = None) -> List:
     """``scan_recordings`` with each finished segment's audio: per recording ``[(start_sample, end_sample, payload), ...]`` (per
     channel for ``"split"``, as there).  ``payload`` is what ``VADWrapper``'s ``voice_end`` callback delivers for the same
     recording - the segment's frames back to back, decoded, mixed and gated as the model read them, as 16-bit PCM behind the WAV
@@ -253,7 +307,8 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
     ``voice_end`` payload - the 16 kHz frames the model read, each chunk resampled on the GPU and gated, behind the header of
     ``config.output_wav_sample_rate``; ``layout="range"`` gives the samples ``[start_sample, end_sample)`` of the recording itself,
     at its own rate and not gated, behind a header that carries ``sample_rate``.
-    ``open_end`` as in ``scan_recordings``: the segment still open at a recording's last frame is cut like any other."""
+    ``open_end`` as in ``scan_recordings``: the segment still open at a recording's last frame is cut like any other.
+    ``refine`` as in ``scan_recordings``: the audio is that of the refined records."""
     from .pool import default_pool, resolve_model_path
     from .utils.wav_writer import WAVWriter
     split = isinstance(channel, str) and channel == "split"
@@ -266,6 +321,8 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
         engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
     if open_end:
         _need_tails(engine, "cut_recordings")
+    if refine is not None:
+        _need_refine(engine, "cut_recordings")
     frame = engine.frame_samples
     if cfg.buffer_size != frame:
         raise ConfigurationError(f"cut_recordings frames at the model's frame size: buffer_size = {cfg.buffer_size}, "
@@ -295,7 +352,7 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
             with engine.scan_session():
                 # (recording, channel) -> its sample ranges; the cut's table lists them in that order
                 ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, denoise, channel, rate=rate,
-                                      open_end=open_end)
+                                      open_end=open_end, refine=refine)
                 table = [(int(engine.last_scan["offsets"][k]), a // hop, (b - a - frame) // hop + 1, chans[c])
                          for k, rc in enumerate(ranges) for c, rg in enumerate(rc) for a, b in rg]
                 if table:

@@ -616,6 +616,83 @@ VAD_API int vad_resegment_tails_device(vad_engine *e, const uint8_t *d_events, c
                                        void *stream);
 
 /*
+ * Refinement: a segment table padded, merged, thinned and split for what reads it - an ASR model, a dataset cutter - on the GPU,
+ * where the per-frame probabilities that decide a split still are.  The tables above are the raw output of the reference's hysteresis
+ * state machine; this pass is what Silero's get_speech_timestamps has as speech_pad_ms, min_silence_duration_ms,
+ * min_speech_duration_ms and max_speech_duration_s.  No model kernel runs and no stream (slot) is touched; only the refined table
+ * crosses the link.
+ *   All counts are frames, as in every table; hop and frame length turn them into samples.  Per item i with
+ * nf = out_start[i + 1] - out_start[i] frames, take the item's input records in table order; if tails are given and
+ * tails[i].nframes > 0, the item's tail (its first_frame and nframes; entry i belongs to item i) follows as its last record.
+ *   1. Clip.  [s, e) = [max(first_frame, 0), min(first_frame + nframes, nf)).  A record with item outside 0 .. n - 1, nframes < 1 or
+ *      s >= e is treated as absent.
+ *   2. Merge.  Record b joins its predecessor a of the same item iff merge_gap >= 0 and s_b - e_a <= merge_gap.  The rule is pairwise
+ *      and local, so chains join transitively and - with merge_gap >= 0 - overlapping records always join.  A group is
+ *      [s of its first record, e of its last record).
+ *   3. Drop.  A group with e - s < min_frames is removed - and one with e - s < 1, which needs records of an item out of frame order.
+ *   4. Pad.  For a surviving group s' = max(s - pad_before, 0) and e' = min(e + pad_after, nf), except between a neighbouring pair of
+ *      surviving groups of one item whose gap g = s_next - e_cur < pad_before + pad_after: g <= 0 gives no padding on that side of
+ *      either; otherwise the earlier group gets a = floor(g * pad_after / (pad_before + pad_after)) frames behind it and the later one
+ *      g - a in front (the product in 64 bits).  Then a <= pad_after, g - a <= pad_before, and the two records touch and never overlap.
+ *   5. Split, when max_frames > 0 and len = e' - s' > max_frames: k = ceil(len / max_frames) pieces, sz = ceil(len / k),
+ *      h = (max_frames - sz) / 2 rounded down; for j = 1 .. k - 1 the nominal cut is c_j = s' + floor(j * len / k), and boundary b_j is
+ *      the frame t of [c_j - h, c_j + h] with the smallest probability among the frames whose event byte has VAD_EV_REJECTED clear,
+ *      the lowest t of equals; b_j = c_j where every frame of the window is rejected.  Piece j is [b_j, b_{j+1}) with b_0 = s' and
+ *      b_k = e'.  Every piece has 1 .. max_frames frames and the windows of neighbouring boundaries never meet (checked by brute
+ *      force for max_frames 2 .. 79 and every len up to 8 * max_frames + 2, every boundary at either end of its window; the
+ *      test-suite repeats it).
+ *   6. Output.  One vad_segment {item, first_frame, nframes} per piece, in item order, then in the order the groups were formed;
+ *      counted, mean_prob and max_prob follow the vad_segment rule over the new range, the fixed-point sum included.  Truncation as
+ *      everywhere: the first min(count, seg_cap) records are written, the true count always.
+ * The neutral rule {0, 0, -1, 0, 0, 0} returns a table that is byte-equal to its input, for tables whose records lie inside their items.
+ *   "The item's records": in a table sorted by item - every table of the calls above, and every table vad_scan_refine accepts - all
+ * records that name the item.  The device form cannot look at a table that lives on the GPU before it launches, so it takes the
+ * item's FIRST RUN: the records from the first one that names the item and follows one that does not (or opens the table) up to
+ * the next record of another item value, in range or not.  Later records that name the item again are treated as absent.  No
+ * table content makes a kernel read or write outside the arrays it was given.
+ *
+ * vad_refine_device: on device pointers.  d_segs_in (16-byte aligned, in_cap records) and d_nsegs_in (an int64, 8-byte aligned) as
+ * vad_segments_device wrote them: the first min(*d_nsegs_in, in_cap) records are read.  d_tails: NULL, or n records (16-byte aligned)
+ * as vad_tails_device wrote them.  d_events (16-byte aligned) and d_probs (4-byte aligned) as a *_device scan wrote them, out_start
+ * its host array [n + 1].  d_segs_out (16-byte aligned, room for seg_cap records, no part of an input) and d_nsegs_out (int64,
+ * 8-byte aligned) on the GPU.  Enqueues on `stream` (NULL = the engine's own) and returns.  Works on every engine - Silero V4,
+ * VAD_ENGINE_SHARED_GPU and the 8 kHz sub-models included; waits for earlier *_device launches as the scans do, and the next such
+ * call waits for this one's.
+ *   VAD_ERR_INVALID_ARG, each with a message, and nothing is written: a null r; a negative pad_before or pad_after; merge_gap < -1;
+ * max_frames of 1 or negative; reserved != 0; n < 0, in_cap < 0 or seg_cap < 0; n or in_cap above 2^31 - 1; a null out_start with
+ * n > 0; a null d_nsegs_in or d_nsegs_out; a null d_segs_in with in_cap > 0; a null d_segs_out with seg_cap > 0; an out_start that
+ * starts below 0 or decreases; out_start[n] > 2^31 - 1; a null d_events or d_probs when there are frames; a misaligned pointer.
+ * n == 0: VAD_OK, *d_nsegs_out = 0.
+ *
+ * vad_scan_refine: the same on the per-frame results that this engine's last vad_scan_segments / vad_scan_rate_segments left in its
+ * own arrays, for the items of that call.  segs_in: a host table of nsegs_in records - a set of vad_scan_resegment's, one set per
+ * call, or any other - or NULL: the resident table of that scan (nsegs_in is then not read).  tails_in: NULL, or the host array
+ * [n] of vad_scan_tails / one set of vad_scan_resegment_tails.  segs_out (room for seg_cap records) and nsegs_out are host memory.
+ * Needs the mark of vad_scan_resegment; without it VAD_ERR_INVALID_ARG, "vad_scan_refine: no scan results are resident".  A host
+ * table is checked before anything is written: nsegs_in >= 0 and at most 2^31 - 1, items in 0 .. n - 1 and not decreasing,
+ * nframes >= 1.  Further VAD_ERR_INVALID_ARG, each with a message and nothing written: the rule as above; seg_cap < 0; a null
+ * nsegs_out; a null segs_out with seg_cap > 0; a null segs_in with nsegs_in > 0 is the resident table, never an error; more than
+ * 2^31 - 1 output records.  Touches no stream, not the resident table, not the tails, not vad_scan_resegment's table and not the
+ * resident block: vad_scan_cut(audio = NULL) cuts refined records like any others.
+ *   VAD_ABI_VERSION is unchanged: the presence of vad_scan_refine is how a caller detects the feature.
+ */
+typedef struct vad_refine {
+    int32_t pad_before;  /* frames added in front of a segment, >= 0 */
+    int32_t pad_after;   /* frames added behind it, >= 0 */
+    int32_t merge_gap;   /* join neighbours of an item whose gap is <= this many frames; -1: never join */
+    int32_t min_frames;  /* drop joined segments shorter than this (before padding); <= 1: keep all */
+    int32_t max_frames;  /* 0: no limit; otherwise >= 2: no output record is longer */
+    int32_t reserved;    /* 0 */
+} vad_refine;
+VAD_API int vad_refine_device(vad_engine *e, const vad_segment *d_segs_in, const int64_t *d_nsegs_in /*on the GPU*/, int64_t in_cap,
+                              const vad_segment *d_tails /*on the GPU, [n], or NULL*/, const uint8_t *d_events, const float *d_probs,
+                              const int64_t *out_start /*host [n + 1]*/, int64_t n, const vad_refine *r, vad_segment *d_segs_out,
+                              int64_t seg_cap, int64_t *d_nsegs_out /*on the GPU*/, void *stream);
+VAD_API int vad_scan_refine(vad_engine *e, const vad_segment *segs_in /*host, or NULL: the resident table*/, int64_t nsegs_in,
+                            const vad_segment *tails_in /*host [n], or NULL*/, const vad_refine *r, vad_segment *segs_out,
+                            int64_t seg_cap, int64_t *nsegs_out);
+
+/*
  * Pipelined host ingest.  vad_step* on host pointers are copy -> kernel -> copy -> wait; at 8 192 streams the PCIe copy is
  * 5-8 x the kernel, so a serving loop should overlap the copy of tick t+1 with the kernel of tick t:
  *

@@ -1010,6 +1010,111 @@ def scan_tails():
     return row
 
 
+def scan_refine():
+    """What the refinement costs, on scan_resegment's corpus: VAD_SCAN_BENCH_N (default 1 024) int16 recordings of 30 s at
+    16 kHz in one call, hop 256.  (a) Engine.scan_segments, then Engine.refine on the table and the tails that scan left on the GPU,
+    under a pad + merge + 30 s split rule (no recording is longer, so nothing is split) and under a rule whose pads share gaps, which
+    drops blips and splits at 1 s, so that every step and the cut search run;
+    (b) the way to the same records today: Engine.scan, which copies the per-frame results back, then the numpy reference
+    (tests/refine_ref.py) on the same table and tails - its records are compared with (a)'s; (c) Engine.refine_device alone on
+    synthetic per-frame arrays: ONE recording of 1 125 000 frames (10 hours at hop 512) with the segments its alternating runs give,
+    HIP-event timed - the count and fill walks are one thread for it.  One warm-up, then three timed passes of each; medians."""
+    import time
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from cutter_vad_amd import SegmentRefine
+    from tests import refine_ref
+    N = int(os.environ.get("VAD_SCAN_BENCH_N", "1024"))
+    eng = Engine(blob(5), max_streams=max(N, 16))
+    hop = 256
+    gold = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "speech16k_i16.npz")
+    pcm = np.tile(np.load(gold)["pcm"].astype(np.int16), 3)
+    rng = np.random.default_rng(N)
+    ns = 30 * 16000
+    recs = [pcm[a:a + ns] for a in rng.integers(0, pcm.size - ns + 1, N)]
+    thr = (0.4, 0.3, 0.8, 0.95, 6, 12)
+    rules = {"30s": SegmentRefine.from_durations(hop, 16000, pad_ms=100, merge_gap_ms=300, max_speech_s=30),
+             "1s": SegmentRefine.from_durations(hop, 16000, pad_ms=200, merge_gap_ms=100, min_speech_ms=250, max_speech_s=1)}
+    slots = eng.open_streams(N)
+    med = lambda v: float(np.median(v))
+
+    def passes(fn):
+        fn()
+        runs = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            out = fn()
+            runs.append(time.perf_counter() - t0)
+        return runs, out
+
+    def fresh():
+        eng.reset(slots)
+        eng.set_thresholds_many(slots, thr)
+
+    row = {"config": f"scan_refine: {N} int16 recordings of 30 s at 16 kHz in one call, hop {hop}", "recordings": N,
+           "frames": N * eng.scan_frame_count(ns, hop), "passes": 3, "rules": {k: list(refine_ref.rule_of(v)) for k, v in rules.items()}}
+    with eng.scan_session():
+        runs, per_frame = passes(lambda: (fresh(), eng.scan(slots, recs, hop=hop, denoise=0.01))[1])
+        row["b_s_scan_per_frame_runs"], row["b_s_scan_per_frame"] = runs, med(runs)
+        probs, ev, _ = per_frame
+        start = np.concatenate([[0], np.cumsum([len(p) for p in probs])]).astype(np.int64)
+        flat_p, flat_e = np.concatenate(probs).astype(np.float32), np.concatenate(ev).astype(np.uint8)
+        runs, table = passes(lambda: (fresh(), eng.scan_segments(slots, recs, hop=hop, denoise=0.01))[1])
+        row["a_s_scan_segments_runs"], row["a_s_scan_segments"], row["records_in"] = runs, med(runs), int(len(table))
+        tails = eng.scan_tails()
+        row["tails_in"] = int((tails["nframes"] > 0).sum())
+        for name, rule in rules.items():
+            runs, fine = passes(lambda: eng.refine(rule, None, tails))
+            row[f"a_s_refine_{name}_runs"], row[f"a_s_refine_{name}"], row[f"records_{name}"] = runs, med(runs), int(len(fine))
+            t0 = time.perf_counter()
+            want = refine_ref.refine(table, tails, flat_e, flat_p, start, rule)
+            row[f"b_s_numpy_refine_{name}"] = time.perf_counter() - t0
+            row[f"equal_{name}"] = bool(refine_ref.same(np.ascontiguousarray(fine), want))
+            row[f"census_{name}"] = refine_ref.census(table, tails, start, rule)
+            row[f"ratio_b_over_a_{name}"] = (row["b_s_scan_per_frame"] + row[f"b_s_numpy_refine_{name}"]) / (row["a_s_scan_segments"] + row[f"a_s_refine_{name}"])
+    # (c) device pointers, no model: one recording of 10 hours
+    T = 1125000
+    run = rng.integers(1, 40, T)
+    p, k, speech, rows = np.empty(T, np.float32), 0, False, []
+    while k < T:
+        r = min(int(run[k]), T - k)
+        p[k:k + r] = rng.uniform(0.5, 0.95, r) if speech else rng.uniform(0.0, 0.45, r)
+        if speech:
+            rows.append((0, k, r, 0, 0.0, 0.0))
+        k, speech = k + r, not speech
+    tab = np.array(rows, refine_ref.DTYPE)
+    d_p = torch.from_numpy(p).cuda()
+    d_ev = torch.zeros(T, dtype=torch.uint8, device="cuda")
+    d_in = torch.from_numpy(tab.view(np.uint8).copy()).cuda()
+    d_nin = torch.tensor([len(tab)], dtype=torch.int64, device="cuda")
+    d_out = torch.zeros(24 * (1 << 18), dtype=torch.uint8, device="cuda")
+    d_cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+    ts = torch.cuda.Stream()
+    rule = SegmentRefine(6, 6, 19, 16, 938)              # the 30 s rule at hop 512
+
+    def event_timed(fn):
+        fn()
+        torch.cuda.synchronize()
+        out = []
+        for _ in range(3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(ts)
+            fn()
+            e1.record(ts)
+            torch.cuda.synchronize()
+            out.append(e0.elapsed_time(e1) * 1e-3)
+        return out
+
+    runs = event_timed(lambda: eng.refine_device(d_in.data_ptr(), d_nin.data_ptr(), len(tab), 0, d_ev.data_ptr(), d_p.data_ptr(), [0, T], rule,
+                                                 d_out.data_ptr(), 1 << 18, d_cnt.data_ptr(), stream=ts.cuda_stream))
+    row["c_s_refine_device_1x1125000_runs"], row["c_s_refine_device_1x1125000"] = runs, med(runs)
+    row["c_records_in"], row["c_records"] = int(len(tab)), int(d_cnt.cpu()[0])
+    got = d_out.cpu().numpy()[:24 * row["c_records"]].view(refine_ref.DTYPE)
+    row["c_equal"] = bool(refine_ref.same(np.ascontiguousarray(got), refine_ref.refine(tab, None, np.zeros(T, np.uint8), p, [0, T], rule)))
+    eng.close()
+    return row
+
+
 def scan_rate():
     """Whole recordings at 48 kHz, resampled on the GPU in the scan: vad_scan_rate_device on VAD_SCAN_BENCH_N (default
     4 096) int16 recordings of 30 s at 48 kHz - the golden clip, every sample three times - already in device memory, hop = chunk / 2,

@@ -5,7 +5,9 @@
 #include "../../include/vad_engine.h"
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
+#include <vector>
 
 #include "resample_generic.h"
 #include "sm_device.h"
@@ -312,6 +314,86 @@ extern "C" hipError_t vadk_launch_reseg_fill(const ResegArgs *a, hipStream_t) {
     for (int32_t set = 0; set < a->nt; ++set)
         for (int32_t item = 0; item < a->n; ++item)
             (void)fake_reseg_replay(a, set, item, true, a->cnt[(size_t)set * (size_t)a->n + (size_t)item]);
+    return hipSuccess;
+}
+
+// the refinement (csrc/scan_refine.hip), as a plain statement of include/vad_engine.h's rule: the item's first run and its tail are
+// clipped into a list, the list is merged into groups, the groups are thinned, padded and split, step by step, each on the whole list
+static std::vector<SegRecord> fake_refine_item(const RefineArgs *a, int32_t item) {
+    struct Span { long long s, e; };
+    const long long nf = std::max(a->out_start[item + 1] - a->out_start[item], 0);
+    const long long rows = std::min<long long>(std::max<long long>(*a->nsegs_in, 0), a->in_cap);
+    std::vector<Span> recs, groups, kept, padded;
+    auto clip = [&](const SegRecord &x) {
+        const long long s = std::max<long long>(x.first_frame, 0), e = std::min<long long>((long long)x.first_frame + x.nframes, nf);
+        if (x.nframes >= 1 && s < e) recs.push_back({s, e});
+    };
+    long long r = 0;
+    while (r < rows && !(a->segs_in[r].item == item && (r == 0 || a->segs_in[r - 1].item != item))) ++r;
+    for (; r < rows && a->segs_in[r].item == item; ++r) clip(a->segs_in[r]);
+    if (a->tails && a->tails[item].nframes > 0) clip(a->tails[item]);
+    for (size_t q = 0; q < recs.size(); ++q) {
+        if (q > 0 && a->merge_gap >= 0 && recs[q].s - recs[q - 1].e <= a->merge_gap) groups.back().e = recs[q].e;
+        else groups.push_back(recs[q]);
+    }
+    for (const Span &g : groups)
+        if (g.e - g.s >= 1 && g.e - g.s >= a->min_frames) kept.push_back(g);
+    const long long pb = a->pad_before, pa = a->pad_after;
+    for (size_t q = 0; q < kept.size(); ++q) {
+        long long left = pb, right = pa;
+        if (q > 0) {
+            const long long g = kept[q].s - kept[q - 1].e;
+            if (g < pb + pa) left = g <= 0 ? 0 : g - g * pa / (pb + pa);
+        }
+        if (q + 1 < kept.size()) {
+            const long long g = kept[q + 1].s - kept[q].e;
+            if (g < pb + pa) right = g <= 0 ? 0 : g * pa / (pb + pa);
+        }
+        padded.push_back({std::max(kept[q].s - left, 0ll), std::min(kept[q].e + right, nf)});
+    }
+    std::vector<SegRecord> out;
+    const uint32_t base = (uint32_t)a->out_start[item];
+    for (const Span &g : padded) {
+        const long long len = g.e - g.s, mf = a->max_frames;
+        if (mf <= 0 || len <= mf) {
+            out.push_back(SegRecord{item, (int32_t)g.s, (int32_t)len, 0, 0.0f, 0.0f});
+            continue;
+        }
+        const long long k = (len + mf - 1) / mf, sz = (len + k - 1) / k, h = (mf - sz) / 2;
+        long long b = g.s;
+        for (long long j = 1; j <= k; ++j) {
+            long long next = g.e;
+            if (j < k) {
+                const long long c = g.s + j * len / k;
+                next = c;
+                float best = INFINITY;
+                bool any = false;
+                for (long long t = std::max(c - h, 0ll); t <= std::min(c + h, nf - 1); ++t)
+                    if (!(a->events[base + t] & EV_REJECTED) && (!any || a->probs[base + t] < best)) best = a->probs[base + t], next = t, any = true;
+            }
+            out.push_back(SegRecord{item, (int32_t)b, (int32_t)(next - b), 0, 0.0f, 0.0f});
+            b = next;
+        }
+    }
+    return out;
+}
+
+extern "C" hipError_t vadk_launch_refine_count(const RefineArgs *a, hipStream_t) {
+    unsigned long long carry = 0;
+    for (int32_t i = 0; i < a->n; ++i) {
+        a->cnt[i] = carry;
+        carry += fake_refine_item(a, i).size();
+    }
+    *a->nsegs_out = (long long)carry;
+    return hipSuccess;
+}
+
+extern "C" hipError_t vadk_launch_refine_fill(const RefineArgs *a, hipStream_t) {
+    for (int32_t i = 0; i < a->n; ++i) {
+        const std::vector<SegRecord> recs = fake_refine_item(a, i);
+        for (size_t j = 0; j < recs.size(); ++j)
+            if (a->cnt[i] + j < (unsigned long long)a->seg_cap) a->segs_out[a->cnt[i] + j] = recs[j];
+    }
     return hipSuccess;
 }
 
