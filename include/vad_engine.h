@@ -637,7 +637,9 @@ VAD_API int vad_resegment_tails_device(vad_engine *e, const uint8_t *d_events, c
  *   5. Split, when max_frames > 0 and len = e' - s' > max_frames: k = ceil(len / max_frames) pieces, sz = ceil(len / k),
  *      h = (max_frames - sz) / 2 rounded down; for j = 1 .. k - 1 the nominal cut is c_j = s' + floor(j * len / k), and boundary b_j is
  *      the frame t of [c_j - h, c_j + h] with the smallest probability among the frames whose event byte has VAD_EV_REJECTED clear,
- *      the lowest t of equals; b_j = c_j where every frame of the window is rejected.  Piece j is [b_j, b_{j+1}) with b_0 = s' and
+ *      the lowest t of equals; b_j = c_j where every frame of the window is rejected.  The probabilities of accepted frames are taken
+ *      to have the sign bit clear, as every kernel of this engine writes them; a caller's own d_probs with negative values or -0.0
+ *      orders them by bit pattern, that is above every non-negative value.  Piece j is [b_j, b_{j+1}) with b_0 = s' and
  *      b_k = e'.  Every piece has 1 .. max_frames frames and the windows of neighbouring boundaries never meet (checked by brute
  *      force for max_frames 2 .. 79 and every len up to 8 * max_frames + 2, every boundary at either end of its window; the
  *      test-suite repeats it).

@@ -1,7 +1,9 @@
 """The numpy reference of the refinement (vad_refine_device, vad_scan_refine; include/vad_engine.h: vad_refine) for
 tests/test_scan_refine_host.py (CPU stand-in) and tests/test_gpu_scan_refine.py: the six steps of the header's text, one after the
-other on whole lists, the statistics by cutter_vad_amd.scan._frame_stats' fixed-point formula - never the code under test.  No test,
-no library: importing it loads neither the stand-in nor the engine."""
+other on whole lists, the statistics by cutter_vad_amd.scan._frame_stats' fixed-point formula - never the code under test.  It is
+the rule for probabilities with the sign bit clear, which is what the engine's kernels write: step 5 compares values (np.argmin),
+and the header's order of a caller's negative values and -0.0 - by bit pattern, above every non-negative one - is not stated here.
+No test, no library: importing it loads neither the stand-in nor the engine."""
 import numpy as np
 
 DTYPE = np.dtype([("item", np.int32), ("first_frame", np.int32), ("nframes", np.int32), ("counted", np.int32),
@@ -85,7 +87,10 @@ def refine_item(records, nf, rule, probs, events):
             c += s
             lo, hi = max(c - h, 0), min(c + h, nf - 1)
             ok = np.flatnonzero((events[lo:hi + 1] & REJECTED) == 0)
-            bounds.append(c if ok.size == 0 else lo + int(ok[np.argmin(probs[lo:hi + 1][ok])]))       # argmin: the first of equals
+            # argmin: the first of equals.  By VALUE: the rule for probabilities with the sign bit clear, which is what every kernel
+            # of the engine writes (+0.0, denormals and 1.0 included: value and bit pattern order them alike).  The header orders a
+            # caller's negative values and -0.0 by bit pattern, above every non-negative one; this reference does not state that case.
+            bounds.append(c if ok.size == 0 else lo + int(ok[np.argmin(probs[lo:hi + 1][ok])]))
         bounds.append(e)
         out += [(a, b - a) for a, b in zip(bounds, bounds[1:])]
     return out
@@ -118,20 +123,35 @@ def refine(table, tails, events, probs, out_start, rule):
     return np.array(rows, DTYPE)
 
 
-def census(table, tails, out_start, rule):
+def census(table, tails, out_start, rule, events=None, probs=None, index_range=None):
     """what a rule does to a table, by the reference alone: the number of merges (records that joined a predecessor), drops, pairs
-    of neighbours that shared a gap, and segments that were split"""
+    of neighbours that shared a gap, and segments that were split.  With the per-frame arrays also `moved`: the boundaries of step 5
+    with b_j != c_j - and `moved_in_range`, those among them whose piece [b_j, b_j+1) has an output index in index_range = (lo, hi),
+    lo <= index < hi"""
     pb, pa, gap, min_frames, max_frames = rule_of(rule)
     start = np.asarray(out_start, np.int64)
     n = max(start.size - 1, 0)
     per = item_records(table, n)
     seen = {"merges": 0, "drops": 0, "shared": 0, "splits": 0}
+    if probs is not None:
+        events, probs = np.asarray(events, np.uint8), np.asarray(probs, np.float32)
+        seen["moved"] = seen["moved_in_range"] = 0
+    lo_idx, hi_idx = index_range if index_range is not None else (0, 1 << 62)
+    at = 0
     for i in range(n):
         nf = int(start[i + 1] - start[i])
         recs = list(per[i])
         if tails is not None and int(tails["nframes"][i]) > 0:
             recs.append((int(tails["first_frame"][i]), int(tails["nframes"][i])))
         dummy_p, dummy_e = np.zeros(nf, np.float32), np.zeros(nf, np.uint8)
+        if probs is not None:           # a window of rejected frames leaves the nominal cut: the same pieces, every b_j = c_j
+            real = refine_item(recs, nf, rule, probs[start[i]:start[i + 1]], events[start[i]:start[i + 1]])
+            nominal = refine_item(recs, nf, rule, dummy_p, dummy_e | REJECTED)
+            assert len(real) == len(nominal)
+            for j, ((b, _), (c, _)) in enumerate(zip(real, nominal)):
+                seen["moved"] += b != c
+                seen["moved_in_range"] += b != c and lo_idx <= at + j < hi_idx
+            at += len(real)
         merged = refine_item(recs, nf, (0, 0, gap, 0, 0, 0), dummy_p, dummy_e)
         present = refine_item(recs, nf, NEUTRAL, dummy_p, dummy_e)
         kept = refine_item(recs, nf, (0, 0, gap, min_frames, 0, 0), dummy_p, dummy_e)

@@ -40,8 +40,8 @@ def _on_gpu():
     return dev, back, torch.cuda.synchronize
 
 
-def _check(e, c, what, caps=None):
-    want = cases.want(c)
+def _check(e, c, what, caps=None, want=None):
+    want = cases.want(c) if want is None else want
     dev, back, sync = _on_gpu()
     for cap in caps or (len(want) + 3, len(want) // 2):
         sync()
@@ -98,6 +98,32 @@ def test_the_named_cases_equal_the_reference(eng, name):
         first = want[want["item"] == 3]
         k, h, cuts = refine_ref.split_plan(50, 20)
         assert int(first["first_frame"][1]) == 10 + cuts[0] - 1 and int(first["first_frame"][2]) == 10 + cuts[1]
+
+
+@pytest.mark.parametrize("name", cases.PAST)
+def test_past_a_wave_a_workgroup_and_a_grid(eng, name):
+    """what the count / prefix / fill / cuts kernels do beyond one wave, one workgroup and one grid - tests/refine_cases.py: past,
+    each case's conditions asserted there on the reference before the engine runs.  edges<n>: the prefix's sums across waves and its
+    second round, init / count / fill in more than one workgroup, a cap inside a split group; w199, w499, w133: the lane loop of
+    the cut going round two to eight times, equal minima a round apart; many: the cut kernel's grid stride and more than 8192
+    records through the statistics; heads: first records at rows 255, 256, 257 and 512; bits: +0.0, denormals and 1.0 as minima."""
+    c, want, caps = cases.past(name)
+    _check(eng, c, name, caps=caps, want=want)
+
+
+def test_every_cap_of_a_small_table(eng):
+    c = cases.splits(np.random.default_rng(7))
+    want = cases.want(c)
+    _check(eng, c, "splits, every cap", caps=cases.every_cap(c, want), want=want)
+
+
+def test_negative_probabilities_order_by_bit_pattern(eng):
+    """include/vad_engine.h, step 5: a caller's -0.0 and negative values lie above every non-negative probability - by hand, the
+    reference does not state this case"""
+    c, rows = cases.negzero(np.random.default_rng(0))
+    dev, back, sync = _on_gpu()
+    count, got, clean = cases.run(eng, c, 6, dev, back, lambda: (eng.synchronize(), sync()))
+    assert count == 4 and clean and [tuple(r)[:3] for r in got.tolist()] == rows, got
 
 
 @pytest.mark.parametrize("version,rate", [(4, 16000), (5, 8000)], ids=["v4", "v5_8k"])

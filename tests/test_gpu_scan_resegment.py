@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from cutter_vad_amd import _ffi, weights_io
-from tests import reseg_ref, seg_ref
+from tests import reseg_cases, reseg_ref, seg_ref
 from tests.test_gpu_scan import GOLD, THR, _engine, _recordings
 
 pytestmark = pytest.mark.gpu
@@ -233,6 +233,33 @@ def test_the_device_form_on_a_v4_engine(engines):
             v4.close_stream(int(s))
     finally:
         v4.close()
+
+
+@pytest.mark.parametrize("n,nsets", [(n, 5) for n in reseg_cases.NS] + [(257, 1), (257, 64)])
+def test_tables_past_a_wave_and_a_workgroup(engines, n, nsets):
+    """vadk_reseg_prefix's sums across waves (n > 64), its second and third round (n > 256, n > 512) and the total carried from one
+    set into the next between rounds, and reseg_replay's ENDs in the frames behind its last group of four - hand-built arrays
+    (tests/reseg_cases.py, every condition asserted there on the reference), no model run: the records, set_start as a whole, the
+    bytes around both outputs and the inputs, at caps above and below the total, 0, and inside the second set"""
+    import torch
+    eng, _ = engines
+    ev, probs, start, sets, want, (counts, caps) = reseg_cases.built(n, nsets)
+    whole = np.concatenate(want)
+    print(f"resegment_device [n = {n}, {nsets} sets]: {len(probs)} frames, set_start {counts.tolist()[:9]}, caps {caps}")
+    d_ev, d_p = torch.from_numpy(ev).cuda(), torch.from_numpy(probs).cuda()
+    for cap in caps:
+        tab = torch.full(((cap + 4) * 24,), SENT, dtype=torch.uint8, device="cuda")
+        cnt = torch.full((len(sets) + 3,), -7, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        eng.resegment_device(d_ev.data_ptr(), d_p.data_ptr(), start, sets, tab.data_ptr() + 48, cap, cnt.data_ptr() + 8)
+        eng.synchronize()
+        torch.cuda.synchronize()
+        assert cnt.cpu().numpy().tolist() == [-7] + counts.tolist() + [-7], cap
+        raw, k = tab.cpu().numpy(), min(cap, len(whole))
+        assert (raw[:48] == SENT).all() and (raw[48 + k * 24:] == SENT).all(), cap
+        got = raw[48:48 + k * 24].view(seg_ref.DTYPE)
+        assert got.tobytes() == whole[:k].tobytes(), (cap, got[:3], whole[:3])
+    assert d_ev.cpu().numpy().tobytes() == ev.tobytes() and d_p.cpu().numpy().tobytes() == probs.tobytes()
 
 
 def test_sweep_recordings_is_scan_recordings_per_config():

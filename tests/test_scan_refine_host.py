@@ -217,6 +217,37 @@ def test_the_device_form_equals_the_reference(make_engine, name):
         assert count == len(want) and clean and same(got, want[:cap]), (name, cap, count, len(want))
 
 
+@pytest.mark.parametrize("name", cases.PAST)
+def test_the_cases_past_a_wave_a_workgroup_and_a_grid(make_engine, name):
+    """the GPU suite's structural cases (tests/refine_cases.py: past) with every condition they are for asserted on the reference, and
+    the stand-in's records at their caps: item counts around 64 and 256, windows wider than a wave, more records than the cut
+    kernel's grid, heads at workgroup edges, the bit patterns of +0.0, denormals and 1.0"""
+    eng = make_engine()
+    c, want, caps = cases.past(name)
+    for cap in tuple(caps) + (0,):
+        count, got, clean = cases.run(eng, c, cap)
+        assert count == len(want) and clean and same(got, want[:cap]), (name, cap, count, len(want))
+
+
+def test_every_cap_of_a_small_table(make_engine):
+    eng = make_engine()
+    c = cases.splits(np.random.default_rng(7))
+    want = cases.want(c)
+    for cap in cases.every_cap(c, want):
+        count, got, clean = cases.run(eng, c, cap)
+        assert count == len(want) and clean and same(got, want[:cap]), cap
+
+
+def test_negative_probabilities_order_by_bit_pattern(make_engine):
+    """the header's sentence on a caller's own d_probs: -0.0 and negative values lie above every non-negative probability.  The
+    reference states the rule for the sign bit clear only and takes the -0.0 as a minimum; stand-in and kernel follow the header."""
+    c, rows = cases.negzero(np.random.default_rng(0))
+    by_value = [tuple(r)[:3] for r in cases.want(c).tolist()]
+    assert by_value == [(0, 8, 7), (0, 15, 14), (1, 8, 7), (1, 15, 14)] != rows
+    count, got, clean = cases.run(make_engine(), c, 6)
+    assert count == 4 and clean and [tuple(r)[:3] for r in got.tolist()] == rows
+
+
 @pytest.mark.parametrize("kw", [dict(version=4), dict(shared_gpu=True), dict(rate=8000)], ids=["v4", "shared_gpu", "v5_8k"])
 def test_every_engine_has_the_device_form(make_engine, kw):
     eng = make_engine(**kw)

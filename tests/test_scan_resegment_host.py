@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from cutter_vad_amd import _ffi, weights_io
-from tests import reseg_ref, seg_ref, standin
+from tests import reseg_cases, reseg_ref, seg_ref, standin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["vad_resegment_device", "vad_scan_resegment"]
@@ -354,6 +354,23 @@ def test_every_engine_replays_on_device_pointers(lib, make_engine, kw):
     for st, n in (([0, 0, 0], None), ([5], None), (None, 0)):
         rc, msg, tab, set_start = raw_device(lib, eng, None, None, st, sets, 4, n=n)
         assert rc == 0 and set_start[:6].tolist() == [0] * 6 and untouched(tab), msg
+
+
+@pytest.mark.parametrize("n,nsets", [(n, 5) for n in reseg_cases.NS] + [(257, 1), (257, 64)])
+def test_tables_past_a_wave_and_a_workgroup(lib, make_engine, n, nsets):
+    """the GPU suite's hand-built arrays (tests/reseg_cases.py) with every condition they are for asserted on the reference, and the
+    stand-in's tables at their caps"""
+    eng = make_engine()
+    ev0, probs, start, sets, want, (counts, caps) = reseg_cases.built(n, nsets)
+    ev = aligned(len(ev0), np.uint8)
+    ev[:] = ev0
+    whole = np.concatenate(want)
+    for cap in caps:
+        rc, msg, tab, set_start = raw_device(lib, eng, ev, probs, start, sets, cap)
+        assert rc == 0, msg
+        assert set_start[:len(sets) + 1].tolist() == counts.tolist() and untouched(set_start[len(sets) + 1:])
+        k = min(cap, len(whole))
+        assert tab[:k].tobytes() == whole[:k].tobytes() and untouched(tab[k:]), (n, nsets, cap)
 
 
 def test_device_form_refusals_have_a_message_and_write_nothing(lib, make_engine):

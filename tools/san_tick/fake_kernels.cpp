@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 #include "resample_generic.h"
@@ -366,10 +367,15 @@ static std::vector<SegRecord> fake_refine_item(const RefineArgs *a, int32_t item
             if (j < k) {
                 const long long c = g.s + j * len / k;
                 next = c;
-                float best = INFINITY;
+                // "smallest" is by bit pattern, as the header says: value order for every probability with the sign bit clear
+                uint32_t best = 0;
                 bool any = false;
-                for (long long t = std::max(c - h, 0ll); t <= std::min(c + h, nf - 1); ++t)
-                    if (!(a->events[base + t] & EV_REJECTED) && (!any || a->probs[base + t] < best)) best = a->probs[base + t], next = t, any = true;
+                for (long long t = std::max(c - h, 0ll); t <= std::min(c + h, nf - 1); ++t) {
+                    if (a->events[base + t] & EV_REJECTED) continue;
+                    uint32_t bits;
+                    std::memcpy(&bits, &a->probs[base + t], sizeof bits);
+                    if (!any || bits < best) best = bits, next = t, any = true;
+                }
             }
             out.push_back(SegRecord{item, (int32_t)b, (int32_t)(next - b), 0, 0.0f, 0.0f});
             b = next;
