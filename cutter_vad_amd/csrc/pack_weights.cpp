@@ -555,6 +555,25 @@ bool pack_silero_v5_t16(const void *blob, size_t len, PackedWeights &out, std::s
                 if (!x3_unit([&](int r, int k) { return convw(1, 16 * w + r, 32 * s + k, t); }, "an encoder.1")) return false;
     }
     out.data_y = std::move(sb.data);
+    // the fourth block range (vad_layout.h, ENC23_X3_BLOCKS): encoder.2 and encoder.3 on the bf16 split, ENC23_X3_BLOCKS blocks per
+    // wave and no sect entry - wave w's blocks start at w * ENC23_X3_BLOCKS.  encoder.2: one row tile per wave over both input columns
+    // (column c meets tap 1 + c), encoder.3: two row tiles on the centre tap; input channels in their natural order
+    sb = StreamBuilder();
+    for (int w = 0; w < NWAVES; ++w) {
+        sb.vector_block16([&](int c) { return eb[2][16 * w + c]; });
+        for (int col = 0; col < 2; ++col)
+            for (int s = 0; s < 2; ++s)
+                if (!x3_unit([&](int r, int k) { return convw(2, 16 * w + r, 32 * s + k, 1 + col); }, "an encoder.2")) return false;
+        for (int rt = 0; rt < 2; ++rt) sb.vector_block16([&](int c) { return eb[3][32 * w + 16 * rt + c]; });
+        for (int s = 0; s < 2; ++s)
+            for (int rt = 0; rt < 2; ++rt)
+                if (!x3_unit([&](int r, int k) { return convw(3, 32 * w + 16 * rt + r, 32 * s + k, 1); }, "an encoder.3")) return false;
+    }
+    if (sb.blocks() != (uint32_t)(NWAVES * ENC23_X3_BLOCKS)) {
+        err = "Failed to load model: encoder.2 / encoder.3 split blocks do not match ENC23_X3_BLOCKS";
+        return false;
+    }
+    out.data_z = std::move(sb.data);
     return true;
 }
 

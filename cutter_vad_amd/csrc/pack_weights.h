@@ -18,6 +18,9 @@ struct PackedWeights {
     std::vector<float> data_x;
     // a third one (StepParams::wstream_y): V5 on 16-stream tiles, encoder.1 on the bf16 split (S_ENC1_X3, offsets into THIS stream)
     std::vector<float> data_y;
+    // the fourth block range (vad_layout.h, ENC23_X3_BLOCKS): encoder.2 and encoder.3 on the bf16 split, uploaded behind data_y in
+    // the same buffer; filled by pack_silero_v5_t16 only
+    std::vector<float> data_z;
     int32_t variant = 0;             // V4: 1 = the graph's 8 kHz sub-model (two time steps reach the LSTMs)
 };
 

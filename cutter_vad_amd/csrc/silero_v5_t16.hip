@@ -3,12 +3,13 @@
 // silero_v5.hip carries 32 streams per workgroup, so a launch of n streams occupies n / 32 of the 256 CUs: 1 024 streams
 // (BASELINE.json configs[1]) use 32 CUs, 4 096 (configs[3]) half the chip - and a tile takes the same ~47 us however few
 // there are.  This kernel is the same network, much of the same algebra (frame ingest under the recurrent gate half, 4-way folded
-// DFT, split-K enc2) and the same per-stream results, re-expressed on v_mfma_f32_16x16x4_f32: a workgroup (4 waves) carries 16
+// DFT) and the same per-stream results, re-expressed on v_mfma_f32_16x16x4_f32: a workgroup (4 waves) carries 16
 // streams, so the same batch spreads over twice as many CUs and every MFMA / VALU phase is half as long.
-// The LSTM's two halves, encoder.0 and encoder.1 run on v_mfma_f32_16x16x32_bf16 instead, with weights and activations as exact
-// three-piece bf16 splits (X3_HALF, X3_CONV below; vad_layout.h S_LSTM_X3, S_ENC0_X3, S_ENC1_X3); the encoders as direct 3-tap
-// convolutions, not the Toom-3 product of silero_v5.hip.  An activation that feeds such a layer is cut into its pieces ONCE, by the
-// lane that produces it, and lies in LDS as the consumers' B fragments ("activation planes", at QSD below).
+// The LSTM's two halves and the four encoder layers run on v_mfma_f32_16x16x32_bf16 instead, with weights and activations as exact
+// three-piece bf16 splits (X3_HALF, X3_CONV below; vad_layout.h S_LSTM_X3, S_ENC0_X3, S_ENC1_X3, ENC23_X3_BLOCKS); the encoders as
+// direct convolutions, not the Toom-3 product of silero_v5.hip, enc2 over its whole K in one wave, not split-K - the STFT alone is
+// fp32.  An activation that feeds such a layer is cut into its pieces ONCE, by the lane that produces it, and lies in LDS as the
+// consumers' B fragments ("activation planes", at QSD below).
 // The engine runs it for every one-frame call and for multi-frame calls of at most T16_MAX_STREAMS streams (engine.cpp: launch()).
 //
 // Fragment convention (v_mfma_f32_16x16x4_f32, D = A[16 x 4] B[4 x 16] + C): lane l = (n = l & 15, kq = l >> 4).
@@ -81,8 +82,9 @@ constexpr int MT16 = 16;
 constexpr int QSL = 17;                   // loader view: rows 64 c + .. of the folded operands (po 0.. | qo 16.. | pe+ 32.. | pe- 40.. | qe- 48.. | qe+ 56..), 192 rows
 constexpr int QSD = 16;                   // dense view of the same memory, used by everything else:
 //   rows 0..143 the |STFT| columns as activation planes (below; 48 c + 12 s + 4 p + kq; 8 kHz: 24 c + ..; the Nyquist channel is in
-//   nyqv); rows 0..31 later enc1's output (fp32: 16 c + ch/4), then rows 0..47 the LSTM input as planes; rows 144..287 = enc0's output
-//   as planes (144 + 48 c + ..), then rows 168..199 the enc2 partials (fp32: 168 + 16 half + ch/4); rows 248..295 = h_{t-1} as planes.
+//   nyqv); rows 0..47 later enc1's output as planes (24 c + 12 s + ..: the four K-steps of enc2), then the LSTM input as planes; rows
+//   144..287 = enc0's output as planes (144 + 48 c + ..), then rows 168..191 enc2's output as planes (168 + 12 s + ..); rows 248..295 =
+//   h_{t-1} as planes.
 // Activation planes: a tensor that feeds a bf16-split layer is cut into its three bf16 pieces by the lane that PRODUCES it, once,
 // and lies in LDS as the consumers' B fragments: a plane group = one K-step s (32 channels) of the 16 streams = 12 quad rows, piece p
 // of lane (n, kq)'s fragment = the 16 bytes at quad row 12 s + 4 p + kq, stream n - one ds_read_b128 per piece for each of the four
@@ -90,14 +92,19 @@ constexpr int QSD = 16;                   // dense view of the same memory, used
 // Live ranges: the h planes are read in the recurrent half only (barrier (0) .. (1)) and written by the prologue and by the cell
 // behind barrier (7), so they may lie under enc0's output (written behind (2), last read before (4)), in every instantiation (the
 // rejected-frame hold keeps h_{t-1} in registers), and lie past the loader view (238 rows, live (0) .. (1b)); the |STFT| planes are
-// written behind (1b) and read until (3); enc1's output is written behind (3) and read until (5), the enc2 partials behind (4)
-// until (6); the x planes are written behind (5), when enc1's output and the |STFT| planes are dead, and read until (7).
+// written behind (1b) and read until (3); enc1's planes are written behind (3) and read until (5), enc2's planes behind (4)
+// until (6); the x planes are written behind (5), when enc1's planes and the |STFT| planes are dead, and read until (7).
 constexpr int T_ROW_E0 = 144;
 constexpr int T_ROW_E = 168;
 constexpr int T_ROW_H = 248;
 constexpr int T_ROWS_H = 48;
 constexpr int T_ROWS = T_ROW_H + T_ROWS_H;
-static_assert(T_ROW_E0 + 144 <= T_ROWS && T_ROW_E + 32 <= T_ROWS, "enc0's output and the enc2 partials end inside the activation region");
+constexpr int T_ROWS_E1 = 48;             // enc1's output: 2 columns x 2 K-steps of planes, rows 0..47
+constexpr int T_ROWS_E2 = 24;             // enc2's output: 2 K-steps of planes at T_ROW_E
+static_assert(T_ROW_E0 + 144 <= T_ROWS && T_ROW_E + 32 <= T_ROWS, "enc0's output and enc2's output end inside the activation region");
+static_assert(T_ROWS_E1 <= T_ROW_E0, "enc1's planes are written while other waves still read enc0's output");
+static_assert(T_ROW_E >= T_ROWS_E1 && T_ROW_E >= 48, "enc2's planes are written while enc1's are read, and read while the x planes are written");
+static_assert(T_ROW_E >= T_ROW_E0 && T_ROW_E + T_ROWS_E2 <= T_ROW_H, "enc2's planes lie in enc0's dead output and stay clear of h");
 constexpr int T_FOLD_SINK = 192;          // loader view: 32 rows behind the three columns, where the loader lanes q >= 8 drop their duplicate quads
 static_assert(T_ROW_H * QSD >= (T_FOLD_SINK + 32) * QSL, "the loader view (and its sink rows) must end before h");
 constexpr int T_LDS_F4 = T_ROWS * QSD + 16 + 12 + 36 + 16 + 96 + 128;   // + head partials [4][16], |X128| [3][16], fold corrections [3][3][16], sink [64], state machines [16] x 96 B, gate biases [4 waves][4 gates][32 units]
@@ -166,60 +173,61 @@ __device__ __forceinline__ void x3_units(F &&f, std::integer_sequence<int, I...>
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                                                      \
     }
 // One half of the LSTM (W_ih . x or W_hh . h) on the bf16 split: 32 units u = 8 s + tile, unit u = the six MFMAs of tile u & 7 at
-// K-step s (vadk_device.h: mfma_x3) into G[tile].  Requests run X3_D units ahead through the ring xw.  The activations: lane (n, kq)
+// K-step s (vadk_device.h: mfma_x3) into G[tile].  Requests run X3_D units ahead through the ring xw, unit u in slot (U0 + u) % X3_NR
+// (U0: where the layer in front left the ring - the input half follows enc3's units).  The activations: lane (n, kq)
 // reads its fragment's three pieces of K-step s from the plane groups at SRC (quad rows 12 s + 4 p + kq), ready made; K-step s + 1's
 // are read in unit (s, 0), under K-step s's MFMAs.
 // EXTRA(u): work placed in unit u; FOLD(u): unit u is fenced together with the next one (a longer region for the caller's
 // interleave hints).
-#define X3_UNIT(u, B, SRC, EXTRA, FOLD)                                                                         \
+#define X3_UNIT(u, U0, B, SRC, EXTRA, FOLD)                                                                     \
     {                                                                                                           \
         constexpr int s_ = (u) >> 3, k_ = (u) & 7;                                                              \
-        if constexpr ((u) + X3_D < 32) { X3_LD(B, (u) + X3_D) }                                                 \
+        if constexpr ((u) + X3_D < 32) { X3_LD(B, (u) + X3_D, U0) }                                             \
         if constexpr (k_ == 0 && s_ < 3) { _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) N_[p_] = PL_RD(SRC, s_ + 1, p_); } \
         EXTRA(u)                                                                                                \
-        G[k_] = mfma_x3(xw[(u) % X3_NR], F_, G[k_]);                                                            \
+        G[k_] = mfma_x3(xw[((U0) + (u)) % X3_NR], F_, G[k_]);                                                   \
         if constexpr (k_ == 7) { F_[0] = N_[0]; F_[1] = N_[1]; F_[2] = N_[2]; }                                 \
         if constexpr (!(FOLD(u)) || k_ == 7) SB();                                                              \
     }
-#define X3_STEP(s, B, SRC, EXTRA, FOLD)                                                                         \
-    X3_UNIT(8 * (s) + 0, B, SRC, EXTRA, FOLD) X3_UNIT(8 * (s) + 1, B, SRC, EXTRA, FOLD)                         \
-    X3_UNIT(8 * (s) + 2, B, SRC, EXTRA, FOLD) X3_UNIT(8 * (s) + 3, B, SRC, EXTRA, FOLD)                         \
-    X3_UNIT(8 * (s) + 4, B, SRC, EXTRA, FOLD) X3_UNIT(8 * (s) + 5, B, SRC, EXTRA, FOLD)                         \
-    X3_UNIT(8 * (s) + 6, B, SRC, EXTRA, FOLD) X3_UNIT(8 * (s) + 7, B, SRC, EXTRA, FOLD)
-#define X3_HALF(B, SRC, EXTRA, FOLD)                                                                            \
+#define X3_STEP(s, U0, B, SRC, EXTRA, FOLD)                                                                     \
+    X3_UNIT(8 * (s) + 0, U0, B, SRC, EXTRA, FOLD) X3_UNIT(8 * (s) + 1, U0, B, SRC, EXTRA, FOLD)                 \
+    X3_UNIT(8 * (s) + 2, U0, B, SRC, EXTRA, FOLD) X3_UNIT(8 * (s) + 3, U0, B, SRC, EXTRA, FOLD)                 \
+    X3_UNIT(8 * (s) + 4, U0, B, SRC, EXTRA, FOLD) X3_UNIT(8 * (s) + 5, U0, B, SRC, EXTRA, FOLD)                 \
+    X3_UNIT(8 * (s) + 6, U0, B, SRC, EXTRA, FOLD) X3_UNIT(8 * (s) + 7, U0, B, SRC, EXTRA, FOLD)
+#define X3_HALF(U0, B, SRC, EXTRA, FOLD)                                                                        \
     {                                                                                                           \
         u32x4 F_[3], N_[3];                                                                                     \
         _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) F_[p_] = PL_RD(SRC, 0, p_);                            \
         SB();                                                                                                   \
-        X3_STEP(0, B, SRC, EXTRA, FOLD) X3_STEP(1, B, SRC, EXTRA, FOLD)                                         \
-        X3_STEP(2, B, SRC, EXTRA, FOLD) X3_STEP(3, B, SRC, EXTRA, FOLD)                                         \
+        X3_STEP(0, U0, B, SRC, EXTRA, FOLD) X3_STEP(1, U0, B, SRC, EXTRA, FOLD)                                 \
+        X3_STEP(2, U0, B, SRC, EXTRA, FOLD) X3_STEP(3, U0, B, SRC, EXTRA, FOLD)                                 \
     }
 // The paired form (silero_v5_pair16): wave (hf, w) computes row tile rt = hf of the four gates for BOTH half-tiles' streams - 16 units
 // v = 4 s + q per half, unit v = the existing unit 8 s + 2 q + hf of S_LSTM_X3 (X3_LDP), its three blocks feeding two mfma_x3: on the
 // wave's own tile's B fragments (SRC0, into Gp[q][0]) and on the partner half's (SRC1, Gp[q][1]).  An accumulator sees what it saw.
-#define X3P_UNIT(v, B, SRC0, SRC1, EXTRA, FOLD)                                                                 \
+#define X3P_UNIT(v, U0, B, SRC0, SRC1, EXTRA, FOLD)                                                             \
     {                                                                                                           \
         constexpr int s_ = (v) >> 2, q_ = (v) & 3;                                                              \
-        if constexpr ((v) + X3_D < 16) { X3_LDP(B, (v) + X3_D) }                                                \
+        if constexpr ((v) + X3_D < 16) { X3_LDP(B, (v) + X3_D, U0) }                                            \
         if constexpr (q_ == 0 && s_ < 3) {                                                                      \
             _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) { N0_[p_] = PL_RD(SRC0, s_ + 1, p_); N1_[p_] = PL_RD(SRC1, s_ + 1, p_); } \
         }                                                                                                       \
         EXTRA(v)                                                                                                \
-        Gp[q_][0] = mfma_x3(xw[(v) % X3_NR], F0_, Gp[q_][0]);                                                   \
-        Gp[q_][1] = mfma_x3(xw[(v) % X3_NR], F1_, Gp[q_][1]);                                                   \
+        Gp[q_][0] = mfma_x3(xw[((U0) + (v)) % X3_NR], F0_, Gp[q_][0]);                                          \
+        Gp[q_][1] = mfma_x3(xw[((U0) + (v)) % X3_NR], F1_, Gp[q_][1]);                                          \
         if constexpr (q_ == 3) { _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) { F0_[p_] = N0_[p_]; F1_[p_] = N1_[p_]; } } \
         if constexpr (!(FOLD(v)) || q_ == 3) SB();                                                              \
     }
-#define X3P_STEP(s, B, SRC0, SRC1, EXTRA, FOLD)                                                                 \
-    X3P_UNIT(4 * (s) + 0, B, SRC0, SRC1, EXTRA, FOLD) X3P_UNIT(4 * (s) + 1, B, SRC0, SRC1, EXTRA, FOLD)         \
-    X3P_UNIT(4 * (s) + 2, B, SRC0, SRC1, EXTRA, FOLD) X3P_UNIT(4 * (s) + 3, B, SRC0, SRC1, EXTRA, FOLD)
-#define X3P_HALF(B, SRC0, SRC1, EXTRA, FOLD)                                                                    \
+#define X3P_STEP(s, U0, B, SRC0, SRC1, EXTRA, FOLD)                                                             \
+    X3P_UNIT(4 * (s) + 0, U0, B, SRC0, SRC1, EXTRA, FOLD) X3P_UNIT(4 * (s) + 1, U0, B, SRC0, SRC1, EXTRA, FOLD) \
+    X3P_UNIT(4 * (s) + 2, U0, B, SRC0, SRC1, EXTRA, FOLD) X3P_UNIT(4 * (s) + 3, U0, B, SRC0, SRC1, EXTRA, FOLD)
+#define X3P_HALF(U0, B, SRC0, SRC1, EXTRA, FOLD)                                                                \
     {                                                                                                           \
         u32x4 F0_[3], F1_[3], N0_[3], N1_[3];                                                                   \
         _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) { F0_[p_] = PL_RD(SRC0, 0, p_); F1_[p_] = PL_RD(SRC1, 0, p_); } \
         SB();                                                                                                   \
-        X3P_STEP(0, B, SRC0, SRC1, EXTRA, FOLD) X3P_STEP(1, B, SRC0, SRC1, EXTRA, FOLD)                         \
-        X3P_STEP(2, B, SRC0, SRC1, EXTRA, FOLD) X3P_STEP(3, B, SRC0, SRC1, EXTRA, FOLD)                         \
+        X3P_STEP(0, U0, B, SRC0, SRC1, EXTRA, FOLD) X3P_STEP(1, U0, B, SRC0, SRC1, EXTRA, FOLD)                 \
+        X3P_STEP(2, U0, B, SRC0, SRC1, EXTRA, FOLD) X3P_STEP(3, U0, B, SRC0, SRC1, EXTRA, FOLD)                 \
     }
 // A direct 3-tap convolution on the bf16 split (encoder.0: vad_layout.h S_ENC0_X3, in the second weight stream - block offset B
 // into it; LDM = the stream's unit loader, X3_LDX / X3_LDY): NO output columns

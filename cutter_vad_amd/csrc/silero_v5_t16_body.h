@@ -85,7 +85,8 @@
     const __amdgpu_buffer_rsrc_t wry = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P.wstream_y), 0, (int)P.wstream_y_bytes, 0x00020000);
 #define WY(blk) ldw(wry, lane16, (blk))
     const int o_stft = (int)P.sect[w][S_STFT], o_nyq = (int)P.sect[w][S_NYQ], o_x0 = (int)P.sect[w][S_ENC0_X3];
-    const int o_y1 = (int)P.sect[w][S_ENC1_X3], o_e2 = (int)P.sect[w][S_ENC2], o_e3 = (int)P.sect[w][S_ENC3];
+    // enc2 and enc3 on the bf16 split: the fourth block range, behind the third stream in its buffer (vad_layout.h, ENC23_X3_BLOCKS)
+    const int o_y1 = (int)P.sect[w][S_ENC1_X3], o_z = 4 * ENC1_X3_BLOCKS + w * ENC23_X3_BLOCKS;
     const int o_l = (int)P.sect[w][S_LSTM], o_x3 = (int)P.sect[w][S_LSTM_X3];
     // SCAN: the items are sorted by frame count, so the tile's first item has the most: its count, clipped to the launch's window
     int T = (ONE || RS) ? 1 : KP(T);
@@ -271,10 +272,11 @@
     // encoder.0 streams its own through the same ring (S_ENC0_X3, X3_CONV).
     f32x4 xw[X3_NR][3];
 #define X3_LDR(blk, slot) _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) xw[(slot) % X3_NR][p_] = WL((blk) + p_);
-#define X3_LD(B, u) X3_LDR((B) + 3 * (u), (u))
-    // PAIR: unit v = 4 s + q of a wave's 16 = the stream's unit 8 s + 2 q + hf, ring slot v
-#define X3_LDP(B, v) X3_LDR((B) + 3 * (8 * ((v) >> 2) + 2 * ((v) & 3) + hf), (v))
-#define X3_LDU(B, u) if constexpr (PAIR) { X3_LDP(B, u) } else { X3_LD(B, u) }
+    // (U0: the ring slot of the half's unit 0 - 0 for the recurrent half, behind enc3's units for the input half)
+#define X3_LD(B, u, U0) X3_LDR((B) + 3 * (u), (U0) + (u))
+    // PAIR: unit v = 4 s + q of a wave's 16 = the stream's unit 8 s + 2 q + hf, ring slot U0 + v
+#define X3_LDP(B, v, U0) X3_LDR((B) + 3 * (8 * ((v) >> 2) + 2 * ((v) & 3) + hf), (U0) + (v))
+#define X3_LDU(B, u, U0) if constexpr (PAIR) { X3_LDP(B, u, U0) } else { X3_LD(B, u, U0) }
 #define X3_LDX(blk, slot) _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) xw[(slot) % X3_NR][p_] = WX((blk) + p_);
 #define X3_LDY(blk, slot) _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) xw[(slot) % X3_NR][p_] = WY((blk) + p_);
 #define H_FIRSTX(tt)                                                                                            \
@@ -284,7 +286,7 @@
     }
 #define H_FIRST(L, tt, WITHX)                                                                                   \
     {                                                                                                           \
-        _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LDU((L) + LSTM_X3_HALF_BLOCKS, u_) }            \
+        _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LDU((L) + LSTM_X3_HALF_BLOCKS, u_, 0) }         \
         if constexpr (WITHX) H_FIRSTX(tt)                                                                       \
         SB();                                                                                                   \
         if constexpr (RS) { X_ISSUE(2, xc_, tt) SB(); }                                                         \
@@ -654,8 +656,8 @@
 
     STAMP(0);
     for (int t = 0;;) {                          // T >= 1; the back edge is at the bottom, behind the next frame's first requests
-        int ws_stft = o_stft, ws_x0 = o_x0, ws_y1 = o_y1, ws_e2 = o_e2, ws_e3 = o_e3, ws_l = o_l, ws_x3 = o_x3;
-        asm volatile("" : "+s"(ws_stft), "+s"(ws_x0), "+s"(ws_y1), "+s"(ws_e2), "+s"(ws_e3), "+s"(ws_l), "+s"(ws_x3));
+        int ws_stft = o_stft, ws_x0 = o_x0, ws_y1 = o_y1, ws_z = o_z, ws_l = o_l, ws_x3 = o_x3;
+        asm volatile("" : "+s"(ws_stft), "+s"(ws_x0), "+s"(ws_y1), "+s"(ws_z), "+s"(ws_l), "+s"(ws_x3));
         // ---- recurrent gate half W_hh . h_{t-1} (4 K-steps x {4 gates x 2 row tiles}, bf16 split) with the frame ingested under it ----
         f32x4 G[8];                               // gate q, row tile rt -> G[2 q + rt]
         [[maybe_unused]] f32x4 Gp[4][2];          // PAIR: gate q's row tile hf of the wave's own tile [0] and of the partner half's [1]
@@ -809,9 +811,9 @@
             if constexpr ((v) == 15) { X_FOLD(2, xc_, 2) X_FLAG HP_MIX }
 #define HP_FOLDREGION(v) (((v) & 3) >= 2 && (v) >= 4)
             if constexpr (PAIR) {
-                X3P_HALF(wh, RH, (ldsO + T_ROW_H * QSD), HP_EXTRA, HP_FOLDREGION)
+                X3P_HALF(0, wh, RH, (ldsO + T_ROW_H * QSD), HP_EXTRA, HP_FOLDREGION)
             } else {
-            X3_HALF(wh, RH, H_EXTRA, H_FOLDREGION)
+            X3_HALF(0, wh, RH, H_EXTRA, H_FOLDREGION)
             }
 #undef HP_EXTRA
 #undef HP_FOLDREGION
@@ -1073,70 +1075,78 @@
         // ---- enc1: 128 -> 64 ch, k3 s2 p1, 3 -> 2 columns, on the bf16 split (X3_CONV, S_ENC1_X3): wave w = channels 16 w .. 16 w + 15
         //      (one row tile) of BOTH output columns; per K-step 3 taps = 3 units, 4 column products (tap 0 -> column 1 on x1, tap 1 ->
         //      column 0 on x0 and column 1 on x2, tap 2 -> column 0 on x1): 96 bf16 MFMAs where the fp32 form had 128 of twice the length ----
-        f32x4 e2b[2], E2w[2], e3b[2], E3w[2];
+        // The ring goes on through enc2 and enc3 (vad_layout.h, ENC23_X3_BLOCKS; the blocks lie behind the third stream) into the LSTM's
+        // input half: enc2's unit v in slot XU_2 + v, enc3's in XU_3 + v, the input half's from XU_L on - every unit requests the
+        // one X3_D units behind it, whichever layer that belongs to.
+        constexpr int NU1 = 4 * 3, NU2 = 4, NU3 = 4, XU_2 = NU0 + NU1, XU_3 = XU_2 + NU2, XU_L = XU_3 + NU3;
+        static_assert(NU2 == X3_D && NU3 == X3_D, "enc1's last X3_D units request enc2's units, enc2's units enc3's, enc3's the input half's first");
+        f32x4 e2b, e3b[2];
         {
-            constexpr int NU1 = 4 * 3;
             f32x4 acc[2][1] = {{e1b}, {e1b}};
 #define E1_SRC(c) (RP0 + 48 * (c) * QSD)
 #define E1_EXTRA(u)                                                                                             \
-            if constexpr ((u) == NU1 - X3_D) {     /* next layers' first blocks (enc2: this wave's K half) */    \
-                const int ge = 2 + 8 * (w >> 1);                                                                \
-                e2b[0] = WL(ws_e2); e2b[1] = WL(ws_e2 + 1);                                                     \
-                E2w[0] = WL(ws_e2 + ge); E2w[1] = WL(ws_e2 + ge + 1);                                           \
-                e3b[0] = WL(ws_e3); e3b[1] = WL(ws_e3 + 1);                                                     \
-                E3w[0] = WL(ws_e3 + 2); E3w[1] = WL(ws_e3 + 3);                                                 \
-            }
+            if constexpr ((u) == NU1 - X3_D) {     /* the fp32 blocks of the next two layers: their biases */    \
+                e2b = WY(ws_z);                                                                                 \
+                e3b[0] = WY(ws_z + ENC2_X3_BLOCKS); e3b[1] = WY(ws_z + ENC2_X3_BLOCKS + 1);                     \
+            }                                                                                                   \
+            if constexpr ((u) + X3_D >= NU1) { X3_LDY(ws_z + 1 + 3 * ((u) + X3_D - NU1), XU_2 + (u) + X3_D - NU1) }
             X3_CONV(4, 1, 2, 2, X3_LDY, ws_y1 + ENC1_X3_F32_BLOCKS, NU0, E1_SRC, acc, E1_EXTRA)
 #undef E1_SRC
 #undef E1_EXTRA
+            // ReLU -> planes: the wave's channels 16 w .. are half w & 1 of K-step w >> 1 of their column; column o's two K-steps are enc2's
+            // units 2 o, 2 o + 1, plane group 24 o + 12 (w >> 1) (the |STFT| planes there are dead behind barrier (3))
 #pragma unroll
-            for (int o = 0; o < 2; ++o) RX[(16 * o + 4 * w) * QSD + nq] = relu4(acc[o][0]);      // fp32, rows 16 o + channel / 4, for enc2
+            for (int o = 0; o < 2; ++o) st_planes_half(RX + (24 * o + 12 * (w >> 1)) * QSD + nq, w & 1, relu4(acc[o][0]));
         }
         STAMP(7);
-        __syncthreads();   // (4) enc1 out in rows 0..31
+        __syncthreads();   // (4) enc1 out as planes in rows 0..47
         STAMP(8);
 
-        // ---- enc2: 64 -> 64 ch, k3 s2 p1, 2 -> 1 column; split-K: wave w = tile w & 1, K half (= input column) w >> 1 ----
+        // ---- enc2: 64 -> 64 ch, k3 s2 p1, 2 -> 1 column, on the bf16 split: wave w = channels 16 w .. 16 w + 15 (one row tile) over the
+        //      whole K = 128: four units (input column c on tap 1 + c - tap 0 meets the padding only -, K-step s) = enc1's plane group
+        //      2 c + s, one accumulator from the bias on: 24 bf16 MFMAs where the split-K fp32 form had 32 of twice the length and a
+        //      round trip of the partial sums through LDS ----
         {
-            const int kh = w >> 1;
-            const int ws = ws_e2 + 2 + 8 * kh;     // this half's 4 k-iterations x 2 row tiles
-            f32x4 acc[2];
-            acc[0] = kh == 0 ? e2b[0] : f32x4{0.f, 0.f, 0.f, 0.f};
-            acc[1] = kh == 0 ? e2b[1] : f32x4{0.f, 0.f, 0.f, 0.f};
-            f32x4 wv[8], av[4];
-            wv[0] = E2w[0]; wv[1] = E2w[1];
+            f32x4 acc = e2b;
+            u32x4 F_[2][3];
 #pragma unroll
-            for (int k = 2; k < 8; ++k) wv[k] = WL(ws + k);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) av[j] = RX[(16 * kh + 4 * j) * QSD + nq];
+            for (int p_ = 0; p_ < 3; ++p_) F_[0][p_] = PL_RD(RX, 0, p_);
             SB();
+            x3_units([&](auto uc_) {
+                constexpr int v_ = decltype(uc_)::value;
+                X3_LDY(ws_z + ENC2_X3_BLOCKS + 2 + 3 * v_, XU_3 + v_)              // enc3's unit v
+                if constexpr (v_ + 1 < NU2) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { acc[0] = mfma16(wv[2 * j], av[j], acc[0]); acc[1] = mfma16(wv[2 * j + 1], av[j], acc[1]); }
-#pragma unroll
-            for (int rt = 0; rt < 2; ++rt) RE[(16 * kh + 8 * (w & 1) + 4 * rt) * QSD + nq] = acc[rt];
+                    for (int p_ = 0; p_ < 3; ++p_) F_[(v_ + 1) & 1][p_] = PL_RD(RX, v_ + 1, p_);
+                }
+                acc = mfma_x3(xw[(XU_2 + v_) % X3_NR], F_[v_ & 1], acc);
+                SB();
+            }, std::make_integer_sequence<int, NU2>{});
+            // ReLU -> planes: half w & 1 of K-step w >> 1 of enc3's input (enc0's output there is dead behind barrier (4))
+            st_planes_half(RE + 12 * (w >> 1) * QSD + nq, w & 1, relu4(acc));
         }
         STAMP(9);
-        __syncthreads();   // (5) enc2 partials
+        __syncthreads();   // (5) enc2 out as planes
         STAMP(10);
 
-        // ---- enc3: 64 -> 128 ch, centre tap; input = relu(partial of K half 0 + K half 1) ----
+        // ---- enc3: 64 -> 128 ch, centre tap, on the bf16 split: two row tiles over two K-steps, units (K-step s, rt); a K-step's
+        //      pieces are read once for both row tiles ----
         {
-            const int ws = ws_e3 + 2;
             f32x4 acc[2] = {e3b[0], e3b[1]};
-            f32x4 wv[8], av[4];
-            wv[0] = E3w[0]; wv[1] = E3w[1];
+            u32x4 F_[2][3];
 #pragma unroll
-            for (int k = 2; k < 8; ++k) wv[k] = WL(ws + k);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f32x4 a = RE[(4 * j) * QSD + nq], b2 = RE[(16 + 4 * j) * QSD + nq];
-                av[j] = relu4(f32x4{a.x + b2.x, a.y + b2.y, a.z + b2.z, a.w + b2.w});
-            }
-#pragma unroll
-            for (int u = 0; u < X3_D; ++u) { X3_LDU(ws_x3, u) }         // the LSTM input half's first units
+            for (int p_ = 0; p_ < 3; ++p_) F_[0][p_] = PL_RD(RE, 0, p_);
             SB();
+            x3_units([&](auto uc_) {
+                constexpr int v_ = decltype(uc_)::value, s_ = v_ >> 1, rt_ = v_ & 1;
+                X3_LDU(ws_x3, v_, XU_L)                                             // the LSTM input half's unit v
+                if constexpr (v_ == 0) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { acc[0] = mfma16(wv[2 * j], av[j], acc[0]); acc[1] = mfma16(wv[2 * j + 1], av[j], acc[1]); }
+                    for (int p_ = 0; p_ < 3; ++p_) F_[1][p_] = PL_RD(RE, 1, p_);
+                }
+                acc[rt_] = mfma_x3(xw[(XU_3 + v_) % X3_NR], F_[s_], acc[rt_]);
+                SB();
+            }, std::make_integer_sequence<int, NU3>{});
             st_planes(RX + 12 * w * QSD + nq, relu4(acc[0]), relu4(acc[1]));      // channels 32 w .. = K-step w of the LSTM's input half
         }
         STAMP(11);
@@ -1152,15 +1162,15 @@
 #define LP_EXTRA(v) if constexpr ((v) == 12) { hw[0] = WL(ws + 128); hw[1] = WL(ws + 129); }
             // PAIR, hand-back: the cell below owns both row tiles of its own tile's streams.  The wave gives the partner tile's four quads
             // (that tile's row tile hf) to wave (1 - hf, w) through the partner half's LDS - rows 144 + 16 w + 4 q + kq: enc0's output,
-            // dead there since barrier (4), and the enc2 partials, dead since (6) - across barrier (7), and takes its own tile's row
+            // dead there since barrier (4), and enc2's planes, dead since (6) - across barrier (7), and takes its own tile's row
             // tile 1 - hf from where its partner put them.  Eight LDS operations per lane; the arithmetic is what it was.
             if constexpr (PAIR) {
-                X3P_HALF(ws_x3, RX, ldsO, LP_EXTRA, L_FOLDREGION)
+                X3P_HALF(XU_L, ws_x3, RX, ldsO, LP_EXTRA, L_FOLDREGION)
                 f32x4 *const hb = ldsO + (T_ROW_E0 + 16 * w) * QSD + nq;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) hb[4 * k * QSD] = Gp[k][1];
             } else {
-            X3_HALF(ws_x3, RX, L_EXTRA, L_FOLDREGION)
+            X3_HALF(XU_L, ws_x3, RX, L_EXTRA, L_FOLDREGION)
             }
 #undef LP_EXTRA
 #undef L_EXTRA

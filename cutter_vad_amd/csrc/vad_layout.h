@@ -74,6 +74,20 @@ constexpr int ENC0_X3_F32_BLOCKS = 2 + 3 * 2;
 // the input channels 32 s .. 32 s + 31 in their natural order (enc0's output channel = the K index of its activation planes).
 constexpr int ENC1_X3_F32_BLOCKS = 1;
 constexpr int ENC1_X3_BLOCKS = ENC1_X3_F32_BLOCKS + 3 * 4 * 3;
+// The FOURTH block range (16-stream kernel only; PackedWeights::data_z): encoder.2 and encoder.3 on the bf16 split.  It has no sect
+// entry, no host vector among the first three and no field of StepParams: the engine uploads it BEHIND the third stream, in the same
+// allocation (StepParams::wstream_y_bytes covers both), and wave w finds its ENC23_X3_BLOCKS blocks at block
+// 4 * ENC1_X3_BLOCKS + w * ENC23_X3_BLOCKS of that buffer.  The first three streams keep every byte; S_ENC2 / S_ENC3 stay in the first,
+// unread by the 16-stream kernels (the 32-stream packing and tests/kernel_model.py have their own).
+//   encoder.2 (64 -> 64 channels, k3 s2 p1, 2 -> 1 column; tap 0 meets the padding only): wave w = output channels 16 w + r, ONE row
+//   tile over the whole K = 128 - one fp32 block (the bias, vector_block16), then four units of three blocks, the tile's A fragment as
+//   in S_LSTM_X3: (column 0, K-step 0), (column 0, K-step 1), (column 1, K-step 0), (column 1, K-step 1), column c on tap 1 + c;
+//   encoder.3 (64 -> 128 channels, centre tap): wave w = channels 32 w + 16 rt + r - two fp32 blocks (the bias of rt 0, 1), then four
+//   units (K-step s, rt): block 2 + 3 (2 s + rt) + piece of its part.
+// Input channels in their natural order (enc1's and enc2's output channel = the K index of their activation planes).
+constexpr int ENC2_X3_BLOCKS = 1 + 4 * 3;
+constexpr int ENC3_X3_BLOCKS = 2 + 4 * 3;
+constexpr int ENC23_X3_BLOCKS = ENC2_X3_BLOCKS + ENC3_X3_BLOCKS;
 __host__ __device__ constexpr int bin_of_channel(int ch) {
     return (ch >> 5) < 2 ? 64 * (ch >> 5) + 2 * (ch & 31) : 64 * ((ch >> 5) - 2) + 2 * (ch & 31) + 1;
 }

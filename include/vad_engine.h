@@ -900,7 +900,8 @@ VAD_API int vad_step_rates(vad_engine *e, int32_t nseg, const float *const *in, 
  * CPU test-suite to check the packed layout against a NumPy model of the kernel's dataflow.
  * model_version 4, 5; 416, 516 = the packings of the 16-stream tile kernels; 5161 = the second
  * stream of the 516 packing (encoder.0 on bf16 splits, uploaded as a buffer of its own); 5162 =
- * its third stream (encoder.1 on bf16 splits), with the same section table.
+ * its third stream (encoder.1 on bf16 splits), with the same section table; 5163 = the blocks
+ * uploaded behind the third stream (encoder.2 and encoder.3 on bf16 splits, no section entry).
  */
 VAD_API int vad_debug_pack_weights(int32_t model_version, const void *weights, size_t weights_len, float *out,
                                    size_t out_floats, size_t *n_floats, uint32_t *sect_out);

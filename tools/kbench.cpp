@@ -94,7 +94,8 @@ int main(int argc, char **argv) {
         p.wstream_x = d_wx;
         p.wstream_x_bytes = (uint32_t)(pw.data_x.size() * 4);
     }
-    if (!pw.data_y.empty()) {        // the third stream (the 16-stream V5 packing's split encoder.1)
+    if (!pw.data_y.empty()) {        // the third stream (the 16-stream V5 packing's split encoder.1), the split enc2 / enc3 behind it
+        pw.data_y.insert(pw.data_y.end(), pw.data_z.begin(), pw.data_z.end());
         float *d_wy;
         CK(hipMalloc(&d_wy, pw.data_y.size() * 4));
         CK(hipMemcpy(d_wy, pw.data_y.data(), pw.data_y.size() * 4, hipMemcpyHostToDevice));
