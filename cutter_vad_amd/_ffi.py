@@ -138,6 +138,14 @@ CUT_LAYOUTS = {"frames": VAD_CUT_FRAMES, "range": VAD_CUT_RANGE}
 CUT_OUTPUTS = {"pcm16": VAD_CUT_PCM16, "f32": VAD_CUT_F32}
 
 
+class Level(C.Structure):
+    _fields_ = [("energy_q32", C.c_int64), ("peak", C.c_float), ("clipped", C.c_int32)]
+
+
+# the same record as a numpy structured dtype: the levels of n segments are np.ndarray(n, LEVEL_DTYPE)
+LEVEL_DTYPE = np.dtype([("energy_q32", np.int64), ("peak", np.float32), ("clipped", np.int32)])
+
+
 class Segment(C.Structure):
     _fields_ = [("item", C.c_int32), ("first_frame", C.c_int32), ("nframes", C.c_int32), ("counted", C.c_int32),
                 ("mean_prob", C.c_float), ("max_prob", C.c_float)]
@@ -263,6 +271,14 @@ SIGNATURES = {
                                     C.c_int32, C.c_int32, _vp, C.c_int64]),
     "vad_scan_rate_cut_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32,
                                            C.c_float, C.c_int32, C.c_int32, _vp, C.c_int64, _vp]),
+    "vad_scan_levels": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32, C.c_float,
+                                  C.c_float, C.POINTER(Level)]),
+    "vad_scan_levels_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32,
+                                         C.c_float, C.c_float, _vp, _vp]),
+    "vad_scan_cut_gain": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32,
+                                    C.c_float, C.c_int32, C.c_int32, _vp, C.c_int64]),
+    "vad_scan_cut_gain_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32,
+                                           C.c_int32, C.c_float, C.c_int32, C.c_int32, _vp, C.c_int64, _vp]),
 }
 
 _lib = None

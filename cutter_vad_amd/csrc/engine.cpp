@@ -43,6 +43,8 @@ extern "C" hipError_t vadk_launch_silero_v5_t16_rates(const vadk::StepParams *p,
 extern "C" hipError_t vadk_launch_silero_v5_scan16(const vadk::StepParams *p, const vadk::ScanItem *items, const vadk::ScanArgs *a,
                                                    hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_cut(const vadk::CutArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_scan_cut_gain(const vadk::CutArgs *a, const float *gains, hipStream_t stream);
+extern "C" hipError_t vadk_launch_seg_levels(const vadk::CutArgs *a, float clip, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_segments(const vadk::SegArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_seg_stats(const vadk::SegArgs *a, uint32_t most, hipStream_t stream);
 extern "C" hipError_t vadk_launch_reseg_count(const vadk::ResegArgs *a, hipStream_t stream);
@@ -172,6 +174,7 @@ struct vad_engine {
     size_t audio_bytes = 0; int32_t audio_channels = 0; int audio_fmt = 0; int32_t audio_rate = 0;
     std::vector<vadk::CutResampleSeg> cut_rows;
     std::vector<uint32_t> cut_tiles;
+    std::vector<float> cut_gains;            // vad_scan_cut_gain: one factor per entry of cut_segs
     uint8_t *d_cut = nullptr; size_t d_cut_cap = 0;
     void *d_cut_out = nullptr; size_t d_cut_out_cap = 0;
     std::vector<vadk::CutSeg> cut_segs;
@@ -1688,6 +1691,9 @@ struct CutPlan {
     // the call
     const char *who; const vad_cut_item *items; int64_t n, audio_samples; int32_t channels; int fmt; int32_t hop; float thr;
     int32_t layout, out_fmt; int64_t out_samples; int chunk; int32_t sr_in;
+    // vad_scan_cut_gain: a factor per segment (host), or nullptr.  vad_scan_levels: the call reduces where a cut stores - layout and
+    // out_fmt are the range once as float32, no item's out_sample is read, and `out` is the records
+    const float *gains; bool levels; float clip;
     // a. cut_check
     bool rate, rate_frames;
     uint32_t fshift;                         // log2 of the quads of a payload frame
@@ -1699,7 +1705,7 @@ struct CutPlan {
     // c. cut_windows
     vad_engine::ResampleOp *op; std::vector<CutWin> wins;
     // d. cut_upload: bytes of the tables, which lie in e->d_cut in this order - segments, workgroups, rows, tiles
-    size_t sb, wb, rb, tb;
+    size_t sb, wb, rb, tb, gb;
 };
 
 // a. every refusal that needs no device pointer, and the tables: e->cut_segs, e->cut_work (rate_frames: e->cut_rows - the work is
@@ -1716,6 +1722,8 @@ int cut_check(vad_engine *e, CutPlan &c) {
     if (c.out_fmt != VAD_CUT_PCM16 && c.out_fmt != VAD_CUT_F32)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_fmt = %d is neither VAD_CUT_PCM16 nor VAD_CUT_F32", who, c.out_fmt);
     if (int rc = check_block_extent(e, who, c.hop, audio_samples, c.channels, c.fmt)) return rc;
+    if (c.levels && c.clip != c.clip)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: clip_thresh is NaN", who);
     if (n == 0) return VAD_OK;
     c.rate = c.chunk > 0;
     c.rate_frames = c.rate && c.layout == VAD_CUT_FRAMES;
@@ -1749,17 +1757,20 @@ int cut_check(vad_engine *e, CutPlan &c) {
         if (it.reserved != 0)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: reserved = %d must be 0", who, (long long)i, it.reserved);
         const int64_t count = cut_samples(frame, it.nframes, hop, c.layout, out_frame);
-        if (it.out_sample < 0 || (it.out_sample & 3) || it.out_sample > c.out_samples || count > c.out_samples - it.out_sample)
+        if (!c.levels && (it.out_sample < 0 || (it.out_sample & 3) || it.out_sample > c.out_samples || count > c.out_samples - it.out_sample))
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: out_sample = %lld (+%lld samples) must be a multiple of 4 inside "
                            "the output of %lld samples", who, (long long)i, (long long)it.out_sample, (long long)count, (long long)c.out_samples);
         if (count >= (int64_t)4 << 31)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld has %lld output samples, a segment may have less than 2^33", who,
                            (long long)i, (long long)count);
+        if (c.gains && !std::isfinite(c.gains[i]))
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: its gain is %s, a gain is a finite number", who, (long long)i,
+                           std::isnan(c.gains[i]) ? "NaN" : "infinite");
         c.spans[(size_t)i] = CutSpan{it.out_sample, it.out_sample + count, i};
         const uint32_t mode = c.channels == 1 ? vadk::SCAN_LEFT : it.channel == VAD_SCAN_MIX ? vadk::SCAN_MIX : (uint32_t)it.channel;
         const uint32_t nq = (uint32_t)(count >> 2);
         e->cut_segs[(size_t)i] = vadk::CutSeg{(uint32_t)((it.sample_offset + it.first_frame * hop) >> 2) | (mode << vadk::SCAN_MODE_SHIFT), nq,
-                                              (uint64_t)it.out_sample >> 2};
+                                              c.levels ? 0u : (uint64_t)it.out_sample >> 2};
         if (c.rate_frames) {
             e->cut_rows.push_back(vadk::CutResampleSeg{e->cut_segs[(size_t)i].quad_in, (uint32_t)c.rows});
             c.rows += it.nframes;
@@ -1771,6 +1782,8 @@ int cut_check(vad_engine *e, CutPlan &c) {
         if (e->cut_work.size() > (size_t)INT32_MAX)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d samples in one call", who, VAD_CUT_WG_SAMPLES);
     }
+    if (c.gains) e->cut_gains.assign(c.gains, c.gains + n);
+    if (c.levels) c.spans.clear();           // no payload: segments may share samples
     std::sort(c.spans.begin(), c.spans.end(), [](const CutSpan &a, const CutSpan &b) { return a.lo < b.lo; });
     for (size_t k = 1; k < c.spans.size(); ++k)
         if (c.spans[k].lo < c.spans[k - 1].hi)
@@ -1785,7 +1798,9 @@ int cut_check(vad_engine *e, CutPlan &c) {
 int cut_block_device(vad_engine *e, CutPlan &c, const void *d_audio, void *d_out) {
     if (!d_audio) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", c.who);
     if (int rc = check_device_audio(e, c.who, d_audio, c.channels)) return rc;
-    if (reinterpret_cast<uintptr_t>(d_out) & 15)
+    if (c.levels && (reinterpret_cast<uintptr_t>(d_out) & 7))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the levels must be 8-byte aligned", c.who);
+    if (!c.levels && (reinterpret_cast<uintptr_t>(d_out) & 15))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output must be 16-byte aligned", c.who);
     c.d_audio = d_audio;
     c.d_out = d_out;
@@ -1819,9 +1834,14 @@ int cut_block_host(vad_engine *e, CutPlan &c, const void *audio) {
         e->audio_resident = false;
         if (int rc = ensure(e, e->d_audio, e->d_audio_cap, c.ab + 16)) return rc;
     }
+    c.d_audio = e->d_audio;
+    if (c.levels) {
+        if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, (size_t)c.n * sizeof(vad_level))) return rc;
+        c.d_out = e->d_cut_out;
+        return VAD_OK;
+    }
     const int64_t out_lo = c.spans.front().lo, out_hi = c.spans.back().hi;
     if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, (size_t)(out_hi - out_lo) * c.ob)) return rc;
-    c.d_audio = e->d_audio;
     c.d_out = e->d_cut_out;
     // on the device the output starts at the first segment's first sample
     for (vadk::CutSeg &sg : e->cut_segs) sg.quad_out -= (uint64_t)out_lo >> 2;
@@ -1835,6 +1855,7 @@ int cut_windows(vad_engine *e, CutPlan &c) {
     if (int rc = get_resample_op(e, c.chunk, &c.op)) return rc;
     const uint32_t total = (uint32_t)c.rows, wr = cut_window_rows(e);
     std::vector<vadk::CutSeg> wsegs;
+    std::vector<float> wgains;               // a window's segment carries its call segment's gain
     e->cut_rows.push_back(vadk::CutResampleSeg{0u, total});
     const std::vector<vadk::CutResampleSeg> &cr = e->cut_rows;
     size_t si = 0;
@@ -1845,6 +1866,7 @@ int cut_windows(vad_engine *e, CutPlan &c) {
             const uint32_t lo = std::max(cr[si].row0, r0), hi = std::min(cr[si + 1].row0, r1), nq = (hi - lo) * 128u;
             const uint32_t local = (uint32_t)(wsegs.size() - w.seg0);
             wsegs.push_back(vadk::CutSeg{(lo - r0) * 128u, nq, e->cut_segs[si].quad_out + (uint64_t)(lo - cr[si].row0) * 128u});
+            if (c.gains) wgains.push_back(e->cut_gains[si]);
             for (uint32_t q = 0; q < nq; q += vadk::CUT_WG_QUADS) e->cut_work.push_back(vadk::CutWork{local, q});
             if (cr[si + 1].row0 > r1) break;     // the segment goes on in the next window
             ++si;
@@ -1859,6 +1881,7 @@ int cut_windows(vad_engine *e, CutPlan &c) {
         e->cut_tiles[t] = (uint32_t)si;
     }
     e->cut_segs.swap(wsegs);
+    if (c.gains) e->cut_gains.swap(wgains);
     return ensure(e, e->d_win, e->d_win_cap, (size_t)std::min(total, wr) * 2048u);
 }
 
@@ -1868,7 +1891,8 @@ int cut_upload(vad_engine *e, CutPlan &c, const void *audio, hipStream_t s) {
     c.wb = sizeof(vadk::CutWork) * e->cut_work.size();
     c.rb = sizeof(vadk::CutResampleSeg) * e->cut_rows.size();
     c.tb = c.rate_frames ? sizeof(uint32_t) * e->cut_tiles.size() : 0;
-    if (int rc = ensure(e, e->d_cut, e->d_cut_cap, c.sb + c.wb + c.rb + c.tb)) return rc;
+    c.gb = c.gains ? sizeof(float) * e->cut_gains.size() : 0;
+    if (int rc = ensure(e, e->d_cut, e->d_cut_cap, c.sb + c.wb + c.rb + c.tb + c.gb)) return rc;
     if (audio) {
         HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, c.ab, hipMemcpyHostToDevice, s));
         set_resident(e, c.ab, c.channels, c.fmt, c.rate ? c.sr_in : 0);
@@ -1879,6 +1903,8 @@ int cut_upload(vad_engine *e, CutPlan &c, const void *audio, hipStream_t s) {
         HIP_TRY(e, hipMemcpyAsync(e->d_cut + c.sb + c.wb, e->cut_rows.data(), c.rb, hipMemcpyHostToDevice, s));
         HIP_TRY(e, hipMemcpyAsync(e->d_cut + c.sb + c.wb + c.rb, e->cut_tiles.data(), c.tb, hipMemcpyHostToDevice, s));
     }
+    if (c.gains) HIP_TRY(e, hipMemcpyAsync(e->d_cut + c.sb + c.wb + c.rb + c.tb, e->cut_gains.data(), c.gb, hipMemcpyHostToDevice, s));
+    if (c.levels) HIP_TRY(e, hipMemsetAsync(c.d_out, 0, (size_t)c.n * sizeof(vad_level), s));
     return VAD_OK;
 }
 
@@ -1897,8 +1923,14 @@ int cut_launches(vad_engine *e, const CutPlan &c, hipStream_t s) {
     a.channels = c.channels;
     a.out_fmt = c.out_fmt;
     a.thresh = c.rate && !c.rate_frames ? -1.0f : c.thr;
+    const float *d_gains = reinterpret_cast<const float *>(e->d_cut + c.sb + c.wb + c.rb + c.tb);
+    if (c.levels) {
+        const hipError_t r = vadk_launch_seg_levels(&a, c.clip, s);
+        if (r != hipSuccess) return e->hip_fail(r, "kernel launch (segment levels)");
+        return VAD_OK;
+    }
     if (!c.rate_frames) {
-        const hipError_t r = vadk_launch_scan_cut(&a, s);
+        const hipError_t r = c.gains ? vadk_launch_scan_cut_gain(&a, d_gains, s) : vadk_launch_scan_cut(&a, s);
         if (r != hipSuccess) return e->hip_fail(r, "kernel launch (scan cut)");
         return VAD_OK;
     }
@@ -1930,7 +1962,7 @@ int cut_launches(vad_engine *e, const CutPlan &c, hipStream_t s) {
         a.work = reinterpret_cast<const vadk::CutWork *>(e->d_cut + c.sb) + w.work0;
         a.nwork = (uint32_t)w.nwork;
         a.audio_bytes = (w.r1 - w.r0) * 2048u;
-        r = vadk_launch_scan_cut(&a, s);
+        r = c.gains ? vadk_launch_scan_cut_gain(&a, d_gains + w.seg0, s) : vadk_launch_scan_cut(&a, s);
         if (r != hipSuccess) return e->hip_fail(r, "kernel launch (scan cut)");
     }
     return VAD_OK;
@@ -1939,6 +1971,11 @@ int cut_launches(vad_engine *e, const CutPlan &c, hipStream_t s) {
 // e. a host call: only speech crosses the link back - one copy per run of adjoining segments (packed payloads: one), the gaps stay
 // the caller's
 int cut_copy_back(vad_engine *e, const CutPlan &c, void *out, hipStream_t s) {
+    if (c.levels) {
+        HIP_TRY(e, hipMemcpyAsync(out, c.d_out, (size_t)c.n * sizeof(vad_level), hipMemcpyDeviceToHost, s));
+        HIP_TRY(e, hipStreamSynchronize(s));
+        return VAD_OK;
+    }
     const std::vector<CutSpan> &spans = c.spans;
     const int64_t out_lo = spans.front().lo;
     for (size_t k = 0; k < spans.size();) {
@@ -1954,13 +1991,16 @@ int cut_copy_back(vad_engine *e, const CutPlan &c, void *out, hipStream_t s) {
 
 // vad_scan_cut and vad_scan_rate_cut (dev = false: host audio, or NULL = the resident block, and a host `out`) and their _device
 // forms, with e->mu held.  Every check comes before the first write: phases a to c refuse or size buffers, cut_upload writes first.
+// vad_scan_cut_gain (with_gains: `gains` is the host array [n], a factor per segment, which the gained kernel applies) and
+// vad_scan_levels (levels: `out` is n vad_level records, cleared on the stream ahead of the reducing kernel) ride the same phases.
 int cut_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples,
             int32_t channels, int fmt, int32_t hop, float thr, int32_t layout, int32_t out_fmt, void *out, int64_t out_samples, void *stream,
-            int chunk = 0, int32_t sr_in = 0) {
+            int chunk = 0, int32_t sr_in = 0, const float *gains = nullptr, bool with_gains = false, bool levels = false, float clip = 0.0f) {
     hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
     HIP_TRY(e, hipSetDevice(e->device));
     if (int rc = scan_wait(e)) return rc;
-    CutPlan c{who, items, n, audio_samples, channels, fmt, hop, thr, layout, out_fmt, out_samples, chunk, sr_in};
+    CutPlan c{who, items, n, audio_samples, channels, fmt, hop, thr, layout, out_fmt, out_samples, chunk, sr_in, gains, levels, clip};
+    if (with_gains && n > 0 && !gains) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null gains", who);
     if (int rc = cut_check(e, c)) return rc;
     if (n == 0) return VAD_OK;
     if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
@@ -2034,6 +2074,59 @@ int vad_scan_rate_cut_device(vad_engine *e, const vad_cut_item *items, int64_t n
     if (int rc = rate_cut_check(e, who, sr_in, &chunk)) return rc;
     return cut_run(e, true, who, items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, d_out, out_samples,
                    stream, chunk, sr_in);
+}
+
+// sr_in of the calls that take both kinds of block: 0 or the engine's own rate = a block at the engine's rate (*chunk = 0)
+static int levels_rate(vad_engine *e, const char *who, int32_t sr_in, int *chunk) {
+    *chunk = 0;
+    if (sr_in == 0 || sr_in == e->sample_rate) return VAD_OK;
+    return rate_cut_check(e, who, sr_in, chunk);
+}
+
+int vad_scan_levels(vad_engine *e, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt,
+                    int32_t sr_in, int32_t hop, float denoise_thresh, float clip_thresh, vad_level *levels_out) {
+    static const char *who = "vad_scan_levels";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int chunk = 0;
+    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
+    return cut_run(e, false, who, items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, VAD_CUT_RANGE, VAD_CUT_F32, levels_out, 0,
+                   nullptr, chunk, chunk ? sr_in : 0, nullptr, false, true, clip_thresh);
+}
+
+int vad_scan_levels_device(vad_engine *e, const vad_cut_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
+                           int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, float clip_thresh, vad_level *d_levels, void *stream) {
+    static const char *who = "vad_scan_levels_device";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int chunk = 0;
+    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
+    return cut_run(e, true, who, items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, VAD_CUT_RANGE, VAD_CUT_F32, d_levels, 0,
+                   stream, chunk, chunk ? sr_in : 0, nullptr, false, true, clip_thresh);
+}
+
+int vad_scan_cut_gain(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const void *audio, int64_t audio_samples,
+                      int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *out,
+                      int64_t out_samples) {
+    static const char *who = "vad_scan_cut_gain";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int chunk = 0;
+    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
+    return cut_run(e, false, who, items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, out, out_samples, nullptr,
+                   chunk, chunk ? sr_in : 0, gains, true);
+}
+
+int vad_scan_cut_gain_device(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const void *d_audio, int64_t audio_samples,
+                             int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt,
+                             void *d_out, int64_t out_samples, void *stream) {
+    static const char *who = "vad_scan_cut_gain_device";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int chunk = 0;
+    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
+    return cut_run(e, true, who, items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, d_out, out_samples,
+                   stream, chunk, chunk ? sr_in : 0, gains, true);
 }
 
 }  // extern "C"

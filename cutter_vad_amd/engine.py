@@ -714,8 +714,40 @@ class Engine:
             start[i + 1] = start[i] + max(count, 0)
         return items, start
 
+    def _cut_block(self, who: str, audio, law: Optional[str], i16_scale: int, sample_rate: Optional[int]):
+        """The block a cut or a levels call names, with ``_scan_lock`` held -> (rate or None, sample frames, channels, fmt,
+        pointer or None, the array that owns the pointer): ``audio=None`` is the block the last scan packed."""
+        sr = self._scan_rate(sample_rate)
+        if audio is None:
+            last = self._scan_last
+            if last is None:
+                raise AudioProcessingError(f"Model prediction failed: {who}(audio=None) follows a scan() of this engine that uploaded a block")
+            if sample_rate is not None and sr != last.get("rate"):
+                raise AudioProcessingError(f"Model prediction failed: {who}(audio=None, sample_rate={sample_rate}): the block of the last scan "
+                                           f"is at {last.get('rate', self.sample_rate)} Hz")
+            return last.get("rate"), last["samples"], last["channels"], last["fmt"], None, None
+        block = np.asarray(audio)
+        g711 = _law_format(law, block)
+        if g711 is None and block.dtype not in _FMT:
+            block = block.astype(np.float32)
+        if block.ndim not in (1, 2) or (block.ndim == 2 and block.shape[1] != 2):
+            raise AudioProcessingError(f"Model prediction failed: the audio block is 1-D or [nsamples, 2], got {block.shape}")
+        block = np.ascontiguousarray(block)
+        fmt = g711 if g711 is not None else _FMT[block.dtype]
+        if fmt == _ffi.VAD_FMT_I16_32767 and i16_scale == 32768:
+            fmt = _ffi.VAD_FMT_I16_32768
+        self._scan_last = None      # the engine's resident block is this one now, not the last scan's
+        return sr, int(block.shape[0]), block.ndim, fmt, block.ctypes.data_as(C.c_void_p), block
+
+    @staticmethod
+    def _cut_gains(gains, n: int) -> np.ndarray:
+        g = np.ascontiguousarray(np.asarray(gains, np.float32).reshape(-1))
+        if g.size != n:
+            raise AudioProcessingError(f"Model prediction failed: gains has {g.size} entries for {n} segments")
+        return g
+
     def cut(self, segments, hop: Optional[int] = None, law: Optional[str] = None, i16_scale: int = 32767, denoise: Optional[float] = 0.01,
-            layout="frames", out="pcm16", audio=None, sample_rate: Optional[int] = None):
+            layout="frames", out="pcm16", audio=None, sample_rate: Optional[int] = None, gains=None):
         """The audio of finished segments (``vad_scan_cut``): ``segments`` lists ``(sample_offset, first_frame, nframes[, channel])``
         - the recording's first sample frame in the block, the segment's first frame (``e - L + 1`` for an END at frame ``e`` with
         ``seg_frames`` ``L``) and its length in frames; ``channel`` as in ``scan`` (default: ``"mix"`` of a two-channel block).
@@ -730,63 +762,84 @@ class Engine:
         ``scan_chunk_samples(sample_rate)`` at ``hop`` input samples.  ``"frames"``: each chunk resampled on the GPU to the 512 samples
         the model read (``Engine.resample`` of the decoded chunk, byte for byte), then gated; ``"range"``: the segment's own samples at
         the input rate, NOT gated.  With ``audio=None`` behind ``scan_segments(sample_rate=...)`` the rate is that scan's; another
-        ``sample_rate`` given then is an error.  With an ``audio``, ``sample_rate`` names its rate."""
+        ``sample_rate`` given then is an error.  With an ``audio``, ``sample_rate`` names its rate.
+        ``gains`` (``vad_scan_cut_gain``): one finite float32 factor per segment; a sample is the gated value times its segment's
+        factor (one float32 multiply) ahead of the conversion.  All ones: the bytes of the call without it."""
         lay, of = self._cut_enum(_ffi.CUT_LAYOUTS, "layout", layout), self._cut_enum(_ffi.CUT_OUTPUTS, "out", out)
-        sr = self._scan_rate(sample_rate)
         with self._scan_lock:
-            if audio is None:
-                last = self._scan_last
-                if last is None:
-                    raise AudioProcessingError("Model prediction failed: cut(audio=None) follows a scan() of this engine that uploaded a block")
-                if sample_rate is not None and sr != last.get("rate"):
-                    raise AudioProcessingError(f"Model prediction failed: cut(audio=None, sample_rate={sample_rate}): the block of the last scan "
-                                               f"is at {last.get('rate', self.sample_rate)} Hz")
-                sr = last.get("rate")
-                total, channels, fmt, ptr = last["samples"], last["channels"], last["fmt"], None
-            else:
-                block = np.asarray(audio)
-                g711 = _law_format(law, block)
-                if g711 is None and block.dtype not in _FMT:
-                    block = block.astype(np.float32)
-                if block.ndim not in (1, 2) or (block.ndim == 2 and block.shape[1] != 2):
-                    raise AudioProcessingError(f"Model prediction failed: the audio block is 1-D or [nsamples, 2], got {block.shape}")
-                block = np.ascontiguousarray(block)
-                total, channels = int(block.shape[0]), block.ndim
-                fmt = g711 if g711 is not None else _FMT[block.dtype]
-                if fmt == _ffi.VAD_FMT_I16_32767 and i16_scale == 32768:
-                    fmt = _ffi.VAD_FMT_I16_32768
-                ptr = block.ctypes.data_as(C.c_void_p)
-                self._scan_last = None      # the engine's resident block is this one now, not the last scan's
+            sr, total, channels, fmt, ptr, _keep = self._cut_block("cut", audio, law, i16_scale, sample_rate)
             hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
             items, start = self._cut_items(segments, hop, lay, channels, rate=sr)
+            n = len(start) - 1
             data = np.empty(int(start[-1]), np.int16 if of == _ffi.VAD_CUT_PCM16 else np.float32)
             thr = -1.0 if denoise is None else float(denoise)
             res = (thr, lay, of, data.ctypes.data_as(C.c_void_p), data.size)
-            if sr is not None:
-                self._check(self._lib.vad_scan_rate_cut(self._h, items, len(start) - 1, ptr, total, channels, fmt, sr, hop, *res))
+            if gains is not None:
+                g = self._cut_gains(gains, n)
+                self._check(self._lib.vad_scan_cut_gain(self._h, items, n, _ptr(g, C.c_float), ptr, total, channels, fmt, sr or 0, hop, *res))
+            elif sr is not None:
+                self._check(self._lib.vad_scan_rate_cut(self._h, items, n, ptr, total, channels, fmt, sr, hop, *res))
             else:
-                self._check(self._lib.vad_scan_cut(self._h, items, len(start) - 1, ptr, total, channels, fmt, hop, *res))
+                self._check(self._lib.vad_scan_cut(self._h, items, n, ptr, total, channels, fmt, hop, *res))
         return data, start
 
     def cut_device(self, segments, d_audio: int, audio_samples: int, d_out: int, out_samples: int, hop: Optional[int] = None,
                    fmt: int = _ffi.VAD_FMT_F32, channels: int = 1, denoise: Optional[float] = 0.01, layout="frames", out="pcm16",
-                   stream: int = 0, out_start=None, sample_rate: Optional[int] = None) -> np.ndarray:
+                   stream: int = 0, out_start=None, sample_rate: Optional[int] = None, gains=None) -> np.ndarray:
         """``cut`` on device pointers (integers; ``vad_scan_cut_device``): the block at ``d_audio`` (4-byte aligned, 8 for two
         channels), the payloads to ``d_out`` (16-byte aligned, room for ``out_samples`` samples), packed in the order listed
         or at ``out_start[i]`` (multiples of 4).  Asynchronous on ``stream``.  -> start [n + 1] of the packed order.
-        ``sample_rate`` as in ``cut`` (``vad_scan_rate_cut_device``): the block is at that rate."""
+        ``sample_rate`` as in ``cut`` (``vad_scan_rate_cut_device``): the block is at that rate.  ``gains`` as in ``cut``
+        (``vad_scan_cut_gain_device``): a host array, read before the call returns."""
         lay, of = self._cut_enum(_ffi.CUT_LAYOUTS, "layout", layout), self._cut_enum(_ffi.CUT_OUTPUTS, "out", out)
         sr = self._scan_rate(sample_rate)
         hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
         items, start = self._cut_items(segments, hop, lay, int(channels), out_start, rate=sr)
         thr = -1.0 if denoise is None else float(denoise)
-        where = (self._h, items, len(start) - 1, d_audio or None, int(audio_samples), int(channels), int(fmt))
+        n = len(start) - 1
+        where = (d_audio or None, int(audio_samples), int(channels), int(fmt))
         res = (thr, lay, of, d_out or None, int(out_samples), stream or None)
-        if sr is not None:
-            self._check(self._lib.vad_scan_rate_cut_device(*where, sr, hop, *res))
+        if gains is not None:
+            g = self._cut_gains(gains, n)
+            self._check(self._lib.vad_scan_cut_gain_device(self._h, items, n, _ptr(g, C.c_float), *where, sr or 0, hop, *res))
+        elif sr is not None:
+            self._check(self._lib.vad_scan_rate_cut_device(self._h, items, n, *where, sr, hop, *res))
         else:
-            self._check(self._lib.vad_scan_cut_device(*where, hop, *res))
+            self._check(self._lib.vad_scan_cut_device(self._h, items, n, *where, hop, *res))
         return start
+
+    # ------------------------------------------------------------------ segment levels
+    def levels(self, segments, hop: Optional[int] = None, denoise: Optional[float] = 0.01, clip: float = 0.95, audio=None,
+               law: Optional[str] = None, i16_scale: int = 32767, sample_rate: Optional[int] = None) -> np.ndarray:
+        """Energy, peak and clipped samples of finished segments (``vad_scan_levels``), reduced on the GPU: ``segments`` as in
+        ``cut``.  -> a structured array ``(energy_q32, peak, clipped)``, one record per segment: statistics of exactly the float32
+        values ``cut(segments, layout="range", out="f32")`` with the same arguments gives - ``energy_q32`` the fixed-point sum of
+        ``min(rint(x * x * 2^32), 2^32)`` (``cutter_vad_amd.scan.level_stats`` turns it into energy and RMS), ``peak`` ``max |x|``,
+        ``clipped`` the samples with ``|x| >= clip`` (``AudioUtils.detect_clipping``'s threshold).  ``audio``, ``law``, ``i16_scale``,
+        ``sample_rate`` and the ``scan_session()`` rule as in ``cut``; on a block at another rate the samples are input-rate samples
+        and never gated.  Segments may share samples.  16 bytes per segment cross the link back."""
+        with self._scan_lock:
+            sr, total, channels, fmt, ptr, _keep = self._cut_block("levels", audio, law, i16_scale, sample_rate)
+            hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
+            items, start = self._cut_items(segments, hop, _ffi.VAD_CUT_RANGE, channels, rate=sr)
+            n = len(start) - 1
+            out = np.zeros(n, _ffi.LEVEL_DTYPE)
+            thr = -1.0 if denoise is None else float(denoise)
+            self._check(self._lib.vad_scan_levels(self._h, items, n, ptr, total, channels, fmt, sr or 0, hop, thr, float(clip),
+                                                  out.ctypes.data_as(C.POINTER(_ffi.Level))))
+        return out
+
+    def levels_device(self, segments, d_audio: int, audio_samples: int, d_levels: int, hop: Optional[int] = None,
+                      fmt: int = _ffi.VAD_FMT_F32, channels: int = 1, denoise: Optional[float] = 0.01, clip: float = 0.95, stream: int = 0,
+                      sample_rate: Optional[int] = None) -> None:
+        """``levels`` on device pointers (integers; ``vad_scan_levels_device``): the block at ``d_audio`` as ``cut_device`` takes it,
+        one 16-byte record per segment to ``d_levels`` (8-byte aligned).  Asynchronous on ``stream``."""
+        sr = self._scan_rate(sample_rate)
+        hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
+        items, start = self._cut_items(segments, hop, _ffi.VAD_CUT_RANGE, int(channels), rate=sr)
+        thr = -1.0 if denoise is None else float(denoise)
+        self._check(self._lib.vad_scan_levels_device(self._h, items, len(start) - 1, d_audio or None, int(audio_samples), int(channels), int(fmt),
+                                                     sr or 0, hop, thr, float(clip), d_levels or None, stream or None))
 
     # ------------------------------------------------------------------ tick assembler (shared-pool serving)
     def tick_push(self, slot: int, frame, gate_on: bool = True, i16_scale: int = 32767, sample_rate: Optional[int] = None,

@@ -101,15 +101,56 @@ def _need_refine(engine, who: str) -> None:
                                  f"a scan left on the GPU), {type(engine).__name__} has none")
 
 
+def _need_levels(engine, who: str, what: str = "levels=True") -> None:
+    if not hasattr(engine, "levels"):
+        raise ConfigurationError("levels", "given", f"{who}: {what} needs an engine with levels (the statistics are reduced from the block "
+                                 f"a scan left on the GPU), {type(engine).__name__} has none")
+
+
+def level_stats(levels, nsamples) -> Tuple[np.ndarray, np.ndarray]:
+    """``Engine.levels`` records and the segments' sample counts -> ``(energy, rms)`` as float64 arrays: ``energy = energy_q32 /
+    2^32`` (``AudioUtils.calculate_energy`` of the segment, samples beyond full scale counted as 1) and ``rms = sqrt(energy /
+    nsamples)`` (``AudioUtils.calculate_rms``; 0 for a segment without samples)."""
+    energy = np.asarray(levels["energy_q32"], np.float64) / 2.0 ** 32
+    ns = np.asarray(nsamples, np.float64)
+    return energy, np.sqrt(np.divide(energy, ns, out=np.zeros_like(energy), where=ns > 0))
+
+
+def _cut_table(engine, ranges, chans, frame: int, hop: int) -> List[Tuple]:
+    """ranges per (recording, channel) of the scan the engine packed last -> the segments ``Engine.cut`` / ``Engine.levels`` take, in
+    the order listed"""
+    return [(int(engine.last_scan["offsets"][k]), a // hop, (b - a - frame) // hop + 1, chans[c])
+            for k, rc in enumerate(ranges) for c, rg in enumerate(rc) for a, b, *_ in rg]
+
+
+def _append_levels(engine, ranges, chans, frame: int, hop: int, denoise) -> List[List[List]]:
+    """every range of ``ranges`` with ``(rms, peak, clipped)`` behind what it holds: one ``Engine.levels`` call on the listed ranges,
+    on the block the scan left on the GPU (the caller holds ``scan_session()``)"""
+    table = _cut_table(engine, ranges, chans, frame, hop)
+    if not table:
+        return ranges
+    lv = engine.levels(table, hop=hop, denoise=denoise)
+    _, rms = level_stats(lv, [(n - 1) * hop + frame for _, _, n, _ in table])
+    extra = iter(zip(rms.tolist(), lv["peak"].tolist(), lv["clipped"].tolist()))
+    return [[[tuple(rg) + next(extra) for rg in one] for one in rc] for rc in ranges]
+
+
 def _scan_ranges(engine, slots, recordings, per: int, frame: int, hop: int, law, denoise, channel, stats: bool = False,
-                 rate: Optional[int] = None, open_end: bool = False, refine=None) -> List[List[List]]:
+                 rate: Optional[int] = None, open_end: bool = False, refine=None, levels: bool = False) -> List[List[List]]:
     """One scan of ``recordings`` (all 1-D or all two-channel) on ``slots`` -> per recording, per channel scanned of it (``per``),
     the finished segments ``(start_sample, end_sample)`` - with ``stats``: ``(start_sample, end_sample, mean_prob, max_prob)``.
     An engine with ``scan_segments`` builds the table on the GPU and copies back that alone; any other goes through the per-frame
     results of ``scan``.  Same ranges either way.  ``rate``: the recordings' sample rate when it is not the engine's (``frame`` and
     ``hop`` are then a chunk and a hop in input samples; ``vad_scan_rate_segments`` builds the table).  ``open_end``: the segment
     still open at an item's last frame (``Engine.scan_tails``) is its last range.  ``refine``: the table - and, with
-    ``open_end``, the tails as each item's last record - goes through ``Engine.refine`` on the GPU; the statistics are the refined records'."""
+    ``open_end``, the tails as each item's last record - goes through ``Engine.refine`` on the GPU; the statistics are the refined records'.
+    ``levels``: every range listed gets ``(rms, peak, clipped)`` appended (``Engine.levels`` on the ranges as listed)."""
+    if levels:
+        _need_levels(engine, "scan_recordings")
+        two = recordings[0].ndim == 2
+        with engine.scan_session():
+            ranges = _scan_ranges(engine, slots, recordings, per, frame, hop, law, denoise, channel, stats, rate, open_end, refine)
+            return _append_levels(engine, ranges, (0, 1) if per == 2 else (channel if two else 0,), frame, hop, denoise)
     sl = np.asarray(slots).reshape(len(recordings), per) if per == 2 else slots
     kw = {} if rate is None else {"sample_rate": rate}
     if refine is not None:
@@ -145,7 +186,7 @@ def _scan_ranges(engine, slots, recordings, per: int, frame: int, hop: int, law,
 
 def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
                     law: Optional[str] = None, channel="mix", stats: bool = False, sample_rate: Optional[int] = None,
-                    open_end: bool = False, refine: Optional[SegmentRefine] = None) -> List[List[Tuple]]:
+                    open_end: bool = False, refine: Optional[SegmentRefine] = None, levels: bool = False) -> List[List[Tuple]]:
     """Speech segments of every recording, one launch sequence for the lot: opens one stream per recording with the config's
     thresholds, scans (frames of ``engine.frame_samples`` at ``hop``, default half a frame as ``VADWrapper`` frames a chunk;
     the config's denoise gate), closes the streams -> per recording ``[(start_sample, end_sample), ...]``.
@@ -164,7 +205,12 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
     mean and maximum under ``stats=True`` (``Engine.scan_tails``; an engine object without it: ``ConfigurationError``).
     ``refine``: a :class:`SegmentRefine` - the segments are padded, merged, thinned and split on the GPU before they are listed
     (``Engine.refine``; an engine object without it: ``ConfigurationError``): the ranges and, under ``stats=True``, the statistics
-    are the refined records', and with ``open_end=True`` the open segment is refined with the others as its recording's last."""
+    are the refined records', and with ``open_end=True`` the open segment is refined with the others as its recording's last.
+    ``levels``: ``True`` appends ``(rms, peak, clipped)`` to every range listed - refined records and open segments too - behind
+    ``stats``' two values when both are given: the root mean square, the largest magnitude and the number of samples at or above
+    0.95 (``AudioUtils.calculate_rms`` / ``detect_clipping``) of the range's samples as the model heard them - decoded, mixed and
+    gated; input-rate samples, not gated, under ``sample_rate`` - reduced on the GPU from the block the scan left there
+    (``Engine.levels``; an engine object without it: ``ConfigurationError``)."""
     from .pool import default_pool, resolve_model_path
     split = isinstance(channel, str) and channel == "split"
     # checked here, not by the scan: a corpus of 1-D recordings alone never shows the value to Engine.scan
@@ -177,6 +223,8 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
         _need_tails(engine, "scan_recordings")
     if refine is not None:
         _need_refine(engine, "scan_recordings")
+    if levels:
+        _need_levels(engine, "scan_recordings")
     frame = engine.frame_samples
     if cfg.buffer_size != frame:
         raise ConfigurationError(f"scan_recordings frames at the model's frame size: buffer_size = {cfg.buffer_size}, "
@@ -201,7 +249,7 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
             engine.set_thresholds_many(slots, (cfg.vad_start_probability, cfg.vad_end_probability, cfg.voice_start_ratio,
                                                cfg.voice_end_ratio, cfg.voice_start_frame_count, cfg.voice_end_frame_count))
             ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, 0.01 if cfg.enable_denoising else None,
-                                  channel, stats, rate, open_end, refine)
+                                  channel, stats, rate, open_end, refine, levels)
         finally:
             for s in slots:
                 engine.close_stream(int(s))
@@ -217,7 +265,7 @@ def _thresholds_of(cfg: VADConfig) -> Tuple:
 
 def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConfig], engine=None, hop: Optional[int] = None,
                      law: Optional[str] = None, channel="mix", stats: bool = False, sample_rate: Optional[int] = None,
-                     open_end: bool = False, refine: Optional[SegmentRefine] = None) -> List[List]:
+                     open_end: bool = False, refine: Optional[SegmentRefine] = None, levels: bool = False) -> List[List]:
     """``scan_recordings`` under several configs for the price of one scan: ``sweep_recordings(recs, cfgs, **kw)[j] ==
     scan_recordings(recs, cfgs[j], **kw)``.  The model runs once per kind of recording (1-D, 2-D), with the first config's
     thresholds; the segment tables of all configs then come from ONE replay of the per-frame probabilities that scan left on the
@@ -226,7 +274,7 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
     ``buffer_size``, ``enable_denoising`` and ``model_path`` - or ``ConfigurationError`` names the field.  An engine object without
     ``resegment`` is served config by config.  ``open_end`` as in ``scan_recordings``: each config's open segments come from the
     same replay (``Engine.resegment_tails``).  ``refine`` as there too: each config's replayed table, with its tails, goes through
-    ``Engine.refine``."""
+    ``Engine.refine``.  ``levels`` as there: one ``Engine.levels`` call per config on that config's ranges."""
     from .pool import default_pool, resolve_model_path
     configs = list(configs)
     if not configs:
@@ -242,11 +290,13 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
         engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
     if not hasattr(engine, "resegment") or not hasattr(engine, "scan_segments"):
         return [scan_recordings(recordings, c, engine=engine, hop=hop, law=law, channel=channel, stats=stats, sample_rate=sample_rate,
-                                open_end=open_end, refine=refine) for c in configs]
+                                open_end=open_end, refine=refine, levels=levels) for c in configs]
     if open_end:
         _need_tails(engine, "sweep_recordings", "resegment_tails")
     if refine is not None:
         _need_refine(engine, "sweep_recordings")
+    if levels:
+        _need_levels(engine, "sweep_recordings")
     split = isinstance(channel, str) and channel == "split"
     if not (channel in ("mix", "split") if isinstance(channel, str) else isinstance(channel, (int, np.integer)) and int(channel) in (0, 1)):
         raise ConfigurationError("channel", repr(channel), f"sweep_recordings: channel is 'mix', 0, 1 or 'split' for the whole corpus, got {channel!r}")
@@ -283,18 +333,23 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
                     tables = [engine.refine(refine, t, tails[k] if open_end else None) for k, t in enumerate(tables)]
                 elif open_end:
                     tables = [_with_tails(t, tl) for t, tl in zip(tables, tails)]
+                listed = [_table_ranges(t, len(idx), per, frame, hop, stats) for t in tables]
+                if levels:
+                    chans = (0, 1) if per == 2 else (channel if two else 0,)
+                    listed = [_append_levels(engine, r, chans, frame, hop, 0.01 if cfg.enable_denoising else None) for r in listed]
         finally:
             for s in slots:
                 engine.close_stream(int(s))
-        for res, table in zip(out, tables):
-            for i, rc in zip(idx, _table_ranges(table, len(idx), per, frame, hop, stats)):
+        for res, ranges in zip(out, listed):
+            for i, rc in zip(idx, ranges):
                 res[i] = rc if split else rc[0]
     return out
 
 
 def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
                    law: Optional[str] = None, channel="mix", layout: str = "frames", wav: bool = True,
-                   sample_rate: Optional[int] = None, open_end: bool = False, refine: Optional[SegmentRefine] = None) -> List:
+                   sample_rate: Optional[int] = None, open_end: bool = False, refine: Optional[SegmentRefine] = None,
+                   normalize: Optional[float] = None) -> List:
     """``scan_recordings`` with each finished segment's audio: per recording ``[(start_sample, end_sample, payload), ...]`` (per
     channel for ``"split"``, as there).  ``payload`` is what ``VADWrapper``'s ``voice_end`` callback delivers for the same
     recording - the segment's frames back to back, decoded, mixed and gated as the model read them, as 16-bit PCM behind the WAV
@@ -308,7 +363,11 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
     ``config.output_wav_sample_rate``; ``layout="range"`` gives the samples ``[start_sample, end_sample)`` of the recording itself,
     at its own rate and not gated, behind a header that carries ``sample_rate``.
     ``open_end`` as in ``scan_recordings``: the segment still open at a recording's last frame is cut like any other.
-    ``refine`` as in ``scan_recordings``: the audio is that of the refined records."""
+    ``refine`` as in ``scan_recordings``: the audio is that of the refined records.
+    ``normalize``: a target level, as ``AudioUtils.normalize_audio(target_level=...)`` per segment: each segment's samples are
+    multiplied by ``np.float32(np.float32(normalize) / peak)`` ahead of the conversion to PCM - by 1 where the peak is 0 - with the
+    peak of ``Engine.levels`` on the same table (the segment's sample range), so the corpus still crosses the link once and the
+    factor is applied on the GPU (``Engine.cut(gains=...)``; an engine object without ``levels``: ``ConfigurationError``)."""
     from .pool import default_pool, resolve_model_path
     from .utils.wav_writer import WAVWriter
     split = isinstance(channel, str) and channel == "split"
@@ -323,6 +382,8 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
         _need_tails(engine, "cut_recordings")
     if refine is not None:
         _need_refine(engine, "cut_recordings")
+    if normalize is not None:
+        _need_levels(engine, "cut_recordings", "normalize=")
     frame = engine.frame_samples
     if cfg.buffer_size != frame:
         raise ConfigurationError(f"cut_recordings frames at the model's frame size: buffer_size = {cfg.buffer_size}, "
@@ -353,9 +414,13 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
                 # (recording, channel) -> its sample ranges; the cut's table lists them in that order
                 ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, denoise, channel, rate=rate,
                                       open_end=open_end, refine=refine)
-                table = [(int(engine.last_scan["offsets"][k]), a // hop, (b - a - frame) // hop + 1, chans[c])
-                         for k, rc in enumerate(ranges) for c, rg in enumerate(rc) for a, b in rg]
-                if table:
+                table = _cut_table(engine, ranges, chans, frame, hop)
+                if table and normalize is not None:
+                    peak = engine.levels(table, hop=hop, denoise=denoise)["peak"]
+                    usable = np.isfinite(peak) & (peak > 0)
+                    gains = np.where(usable, np.float32(normalize) / np.where(usable, peak, np.float32(1)), np.float32(1)).astype(np.float32)
+                    data, start = engine.cut(table, hop=hop, denoise=denoise, layout=layout, gains=gains)
+                elif table:
                     data, start = engine.cut(table, hop=hop, denoise=denoise, layout=layout)
         finally:
             for s in slots:

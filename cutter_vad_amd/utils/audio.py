@@ -3,8 +3,10 @@
 Only the ``AudioUtils`` members that the reference calls on (or right next to) the per-frame
 path are restated (/root/reference/src/real_time_vad/utils/audio.py): validation, mono mixdown,
 framing, the denoise gate as applied to the audio KEPT for segments, PCM conversions, and
-``resample_audio``.  The offline helpers (normalise / window / RMS / file I/O) are out of scope
-(SURVEY §2 row 6).
+``resample_audio``, and the level helpers a corpus caller applies right behind the VAD -
+``calculate_rms``, ``calculate_energy``, ``detect_clipping``, ``normalize_audio``, whose GPU
+counterparts on scanned blocks are ``Engine.levels`` and ``Engine.cut(gains=...)``.  The other
+offline helpers (window / file I/O) are out of scope.
 
 On the hot path itself the gate and the int16 scaling are fused into the HIP kernel's load
 (csrc/silero_v5.hip); ``resample_audio`` is a HIP kernel behind ``vad_resample`` — none of the
@@ -67,6 +69,33 @@ class AudioUtils:
             return np.where(np.abs(audio_data) > noise_threshold, audio_data, 0.0)
         except Exception as e:  # pragma: no cover
             raise AudioProcessingError(f"Failed to denoise audio: {e}")
+
+    @staticmethod
+    def normalize_audio(audio_data: np.ndarray, target_level: float = 0.9) -> np.ndarray:
+        """audio.py:58-75: scaled so that the largest magnitude becomes ``target_level``; an all-zero array is returned as it is.
+        (Per segment of a scanned corpus, on the GPU: ``cut_recordings(normalize=...)``.)"""
+        try:
+            peak = np.max(np.abs(audio_data))
+            if peak > 0:
+                return audio_data * (target_level / peak)
+            return audio_data
+        except Exception as e:
+            raise AudioProcessingError(f"Failed to normalize audio: {e}")
+
+    @staticmethod
+    def detect_clipping(audio_data: np.ndarray, threshold: float = 0.95) -> bool:
+        """audio.py:124-135: whether any sample's magnitude reaches ``threshold`` (``>=``).  (``Engine.levels`` counts them.)"""
+        return np.any(np.abs(audio_data) >= threshold)
+
+    @staticmethod
+    def calculate_rms(audio_data: np.ndarray) -> float:
+        """audio.py:138-148: the root of the mean square, in the array's own precision"""
+        return np.sqrt(np.mean(audio_data ** 2))
+
+    @staticmethod
+    def calculate_energy(audio_data: np.ndarray) -> float:
+        """audio.py:151-161: the sum of squares, in the array's own precision"""
+        return np.sum(audio_data ** 2)
 
     @staticmethod
     def pcm_to_float32(pcm_data: bytes, bit_depth: int = 16) -> np.ndarray:

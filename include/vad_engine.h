@@ -695,6 +695,67 @@ VAD_API int vad_scan_refine(vad_engine *e, const vad_segment *segs_in /*host, or
                             int64_t seg_cap, int64_t *nsegs_out);
 
 /*
+ * Segment levels and gained cuts: how loud a segment is, and its audio times a factor, without the samples crossing the link.
+ * The reference has AudioUtils.calculate_rms, calculate_energy, detect_clipping(threshold = 0.95) and
+ * normalize_audio(target_level = 0.9) for this, on a host array (utils/audio.py); a corpus caller filters on RMS, peak and clipping
+ * right behind the VAD and often peak-normalises what it cuts.
+ *
+ * vad_scan_levels: one vad_level per listed segment.  THE RULE: the levels of a segment are statistics of exactly the float32
+ * values that vad_scan_cut / vad_scan_rate_cut with VAD_CUT_RANGE, VAD_CUT_F32 and the same arguments would write for it - decoded,
+ * channel-selected and gated; on a rate block input-rate samples, never gated, as there.  A kernel reads the block in its wire
+ * format and reduces where the cut stores; 16 bytes per segment cross the link back.
+ *   energy_q32 = sum over the samples of min(rint(x * x * 2^32), 2^32), with x * x and the scaling in float64 (both exact for a
+ * float32 x) and rint to nearest-even: a fixed-point sum, exact in any order.  A sample with |x| >= 1 counts as 1.  For int16 / 32768
+ * and G.711 blocks (x = s / 32768) no term is rounded at all: energy_q32 = 4 * sum of s^2.  energy = energy_q32 / 2^32
+ * (calculate_energy), rms = sqrt(energy / samples) (calculate_rms).  A block is under 2^31 samples: the sum cannot overflow.
+ *   peak = max |x|, taken as the maximum of the bit patterns of |x| (0 for an all-zero segment).
+ *   clipped = the samples with |x| >= clip_thresh, compared in float32 (detect_clipping's >=).  clip_thresh <= 0 counts every
+ * sample; +Inf none.
+ *   All three are integer reductions: the records do not depend on the GPU's scheduling, and two calls give the same bytes.
+ *   A float32 block with non-finite samples: the peak of a segment that holds one is not finite (a NaN's pattern beats +Inf, +Inf
+ * beats every finite value), its other two fields are unspecified; other segments are unaffected, the call completes normally.
+ *   sr_in: 0 or the engine's own rate - a block at the engine's rate, every rule of vad_scan_cut applies; 8000 / 24000 / 48000 on a
+ * 16 kHz engine - a rate block, every rule of vad_scan_rate_cut applies (first_frame and nframes count chunks), including which
+ * resident block audio == NULL may name.  The items are vad_cut_item; out_sample is NOT read, so two items may name the same
+ * samples.  A segment has vad_cut_samples / vad_rate_cut_samples(.., VAD_CUT_RANGE) samples.
+ *   audio == NULL: the resident block, as in the cuts; with an audio the call uploads it, and it becomes the resident block.
+ * Works on every engine, Silero V4 and VAD_ENGINE_SHARED_GPU included: no model kernel runs, no stream is touched.  The call first
+ * waits for earlier *_device launches that read the engine's tables.
+ *   VAD_ERR_INVALID_ARG, each with a message and nothing written: every refusal of vad_scan_cut / vad_scan_rate_cut that concerns
+ * the block and the items, in the same words under this function's name; a NaN clip_thresh; a null levels_out with n > 0.
+ * n == 0: VAD_OK.
+ *   vad_scan_levels_device: d_audio as vad_scan_cut_device takes it, d_levels (8-byte aligned, n records) on the engine's GPU;
+ * enqueues a clear of the records and the kernel on `stream` (NULL = the engine's own) and returns.
+ *
+ * vad_scan_cut_gain / vad_scan_cut_gain_device: vad_scan_cut / vad_scan_rate_cut (sr_in as above) with a factor per segment: a
+ * sample of segment i is the gated value times gains[i] - one float32 multiply of its own - and then the float32 itself or
+ * clip(. * 32767, -32768, 32767) toward zero, as there.  gains is a HOST array [n] in both forms.  On a rate block the factor
+ * applies to the input-rate samples of VAD_CUT_RANGE and, for VAD_CUT_FRAMES, to the resampled and gated frames.  gains[i] == 1.0f
+ * for all i gives the bytes of the call without gains.  gain = (float) target / peak, with the peak of vad_scan_levels on the same
+ * table, is AudioUtils.normalize_audio per segment.  Every rule and refusal of the cut applies under the new names; further
+ * VAD_ERR_INVALID_ARG: a null gains with n > 0, and a gain that is NaN or infinite, with a message that names the segment.
+ *   VAD_ABI_VERSION is unchanged: the presence of vad_scan_levels / vad_scan_cut_gain is how a caller detects the feature.
+ */
+typedef struct vad_level {
+    int64_t energy_q32;  /* sum of min(rint(x * x * 2^32), 2^32) over the segment's samples */
+    float   peak;        /* max |x| */
+    int32_t clipped;     /* samples with |x| >= clip_thresh */
+} vad_level;
+VAD_API int vad_scan_levels(vad_engine *e, const vad_cut_item *items, int64_t n, const void *audio /*or NULL*/, int64_t audio_samples,
+                            int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, float clip_thresh,
+                            vad_level *levels_out /*[n]*/);
+VAD_API int vad_scan_levels_device(vad_engine *e, const vad_cut_item *items, int64_t n, const void *d_audio, int64_t audio_samples,
+                                   int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, float clip_thresh,
+                                   vad_level *d_levels /*on the GPU, [n]*/, void *stream);
+VAD_API int vad_scan_cut_gain(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains /*host [n]*/,
+                              const void *audio /*or NULL*/, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in,
+                              int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *out, int64_t out_samples);
+VAD_API int vad_scan_cut_gain_device(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains /*host [n]*/,
+                                     const void *d_audio, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in,
+                                     int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *d_out,
+                                     int64_t out_samples, void *stream);
+
+/*
  * Pipelined host ingest.  vad_step* on host pointers are copy -> kernel -> copy -> wait; at 8 192 streams the PCIe copy is
  * 5-8 x the kernel, so a serving loop should overlap the copy of tick t+1 with the kernel of tick t:
  *

@@ -1115,6 +1115,133 @@ def scan_refine():
     return row
 
 
+def scan_levels():
+    """What segment levels and gained cuts cost, on scan_refine's corpus: VAD_SCAN_BENCH_N (default 1 024) int16
+    recordings of 30 s at 16 kHz, hop 256, the table of its scan.  (a) Engine.levels on the block the scan left on the GPU;
+    (b) the way to the same numbers without it: Engine.cut(layout="range", out="f32") of the same table, then the statistics in numpy
+    (tests/levels_ref.py) - its records are compared with (a)'s; (a) and (b) alternate; (c) on device pointers, HIP-event timed, the
+    same table: vad_scan_levels_device against vad_scan_cut_device(RANGE, F32), which reads the same bytes and writes 4 per sample -
+    the traffic yardstick; (d) the cut with a gain per segment against the cut without, host calls and device forms (frames, PCM16).
+    One warm-up, then three timed passes of each; medians."""
+    import ctypes as C
+    import time
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from cutter_vad_amd import level_stats
+    from tests import levels_ref
+    N = int(os.environ.get("VAD_SCAN_BENCH_N", "1024"))
+    eng = Engine(blob(5), max_streams=max(N, 16))
+    hop, frame = 256, 512
+    gold = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "speech16k_i16.npz")
+    pcm = np.tile(np.load(gold)["pcm"].astype(np.int16), 3)
+    rng = np.random.default_rng(N)
+    ns = 30 * 16000
+    recs = [pcm[a:a + ns] for a in rng.integers(0, pcm.size - ns + 1, N)]
+    slots = eng.open_streams(N)
+    eng.set_thresholds_many(slots, (0.4, 0.3, 0.8, 0.95, 6, 12))
+    med = lambda v: float(np.median(v))
+    row = {"config": f"scan_levels: {N} int16 recordings of 30 s at 16 kHz in one call, hop {hop}", "recordings": N, "passes": 3}
+    with eng.scan_session():
+        table = eng.scan_segments(slots, recs, hop=hop, denoise=0.01)
+        last = eng.last_scan
+        offs = [int(o) for o in last["offsets"]]
+        segs = [(offs[i], f, n) for i, f, n in zip(table["item"].tolist(), table["first_frame"].tolist(), table["nframes"].tolist())]
+        counts = np.array([(n - 1) * hop + frame for _, _, n in segs], np.int64)
+        row.update(segments=len(segs), speech_samples=int(counts.sum()), block_samples=int(last["samples"]))
+
+        def route_a():
+            return eng.levels(segs, hop=hop, denoise=0.01)
+
+        def route_b():
+            t0 = time.perf_counter()
+            data, start = eng.cut(segs, hop=hop, denoise=0.01, layout="range", out="f32")
+            t1 = time.perf_counter()
+            rec = levels_ref.records([data[start[i]:start[i + 1]] for i in range(len(segs))])
+            return rec, t1 - t0, time.perf_counter() - t1
+
+        got, (want, _, _) = route_a(), route_b()
+        row["equal_a_b"] = bool(got.tobytes() == want.tobytes())
+        a_runs, b_runs, b_cut, b_np = [], [], [], []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            route_a()
+            a_runs.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            _, c, s = route_b()
+            b_runs.append(time.perf_counter() - t0)
+            b_cut.append(c)
+            b_np.append(s)
+        row.update(a_s_levels_runs=a_runs, a_s_levels=med(a_runs), b_s_cut_numpy_runs=b_runs, b_s_cut_numpy=med(b_runs), b_s_cut_f32=med(b_cut),
+                   b_s_numpy=med(b_np), ratio_b_over_a=med(b_runs) / med(a_runs), bytes_back_a=16 * len(segs), bytes_back_b=int(4 * counts.sum()))
+        _, rms = level_stats(got, counts)
+        row.update(rms_median=float(np.median(rms)), peak_max=float(got["peak"].max()), clipped_total=int(got["clipped"].sum()))
+        # (d) host calls: the gain rides along the cut
+        gains = rng.uniform(0.5, 2.0, len(segs)).astype(np.float32)
+        for name, kw in (("d_s_cut", {}), ("d_s_cut_gain", {"gains": gains})):
+            eng.cut(segs, hop=hop, denoise=0.01, **kw)
+            runs = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                eng.cut(segs, hop=hop, denoise=0.01, **kw)
+                runs.append(time.perf_counter() - t0)
+            row[name + "_runs"], row[name] = runs, med(runs)
+    # (c), (d) on device pointers: the kernels alone
+    block = np.zeros(last["samples"], np.int16)
+    for r, o in zip(recs, offs):
+        block[o:o + r.size] = r
+    d_audio = torch.from_numpy(block).cuda()
+    frames_out = int(sum(n for _, _, n in segs)) * frame
+    d_out = torch.empty(max(int(counts.sum()), (frames_out + 1) // 2) + 16, dtype=torch.float32, device="cuda")
+    d_lv = torch.zeros(2 * len(segs), dtype=torch.int64, device="cuda")
+    ts = torch.cuda.Stream()
+    fmt = last["fmt"]
+
+    # a call builds its tables on the host and uploads them before the launch.  The ctypes items are built once, outside, and a
+    # matrix product on the same stream in front of the first event keeps the GPU busy while the host checks and builds, so the
+    # events bracket the upload of the tables (16 bytes per segment, 8 per workgroup), the clear and the kernel - as scan_cut (a) does
+    from cutter_vad_amd import _ffi
+    busy = torch.randn(6144, 6144, device="cuda")
+    lib, h, n = eng._lib, eng.handle, len(segs)
+    it_range, _ = eng._cut_items(segs, hop, _ffi.VAD_CUT_RANGE, 1)
+    it_frames, _ = eng._cut_items(segs, hop, _ffi.VAD_CUT_FRAMES, 1)
+    gp = gains.ctypes.data_as(C.POINTER(C.c_float))
+    where = (d_audio.data_ptr(), block.size, 1, fmt)
+
+    def event_timed(fn):
+        out = []
+        for k in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            with torch.cuda.stream(ts):
+                torch.mm(busy, busy)
+            e0.record(ts)
+            assert fn() == 0
+            e1.record(ts)
+            torch.cuda.synchronize()
+            if k >= 2:                           # two warm-ups
+                out.append(e0.elapsed_time(e1) * 1e-3)
+        return out
+
+    tail = (d_out.data_ptr(), frames_out, ts.cuda_stream)
+    calls = {"c_s_levels_device": lambda: lib.vad_scan_levels_device(h, it_range, n, *where, 0, hop, 0.01, 0.95, d_lv.data_ptr(), ts.cuda_stream),
+             "c_s_cut_range_f32_device": lambda: lib.vad_scan_cut_device(h, it_range, n, *where, hop, 0.01, _ffi.VAD_CUT_RANGE, _ffi.VAD_CUT_F32,
+                                                                         d_out.data_ptr(), int(counts.sum()), ts.cuda_stream),
+             "d_s_cut_frames_pcm16_device": lambda: lib.vad_scan_cut_device(h, it_frames, n, *where, hop, 0.01, _ffi.VAD_CUT_FRAMES,
+                                                                            _ffi.VAD_CUT_PCM16, *tail),
+             "d_s_cut_gain_frames_pcm16_device": lambda: lib.vad_scan_cut_gain_device(h, it_frames, n, gp, *where, 0, hop, 0.01, _ffi.VAD_CUT_FRAMES,
+                                                                                      _ffi.VAD_CUT_PCM16, *tail)}
+    for name, fn in calls.items():
+        runs = event_timed(fn)
+        row[name + "_runs"], row[name] = runs, med(runs)
+    row["c_equal"] = bool(d_lv.cpu().numpy().tobytes() == got.tobytes())
+    read = int(counts.sum()) * 2
+    row["c_levels_GBps_read"] = read / row["c_s_levels_device"] / 1e9
+    row["c_cut_GBps_read_plus_written"] = (read + 4 * int(counts.sum())) / row["c_s_cut_range_f32_device"] / 1e9
+    row["c_ratio_levels_over_cut"] = row["c_s_levels_device"] / row["c_s_cut_range_f32_device"]
+    eng.close()
+    return row
+
+
 def scan_rate():
     """Whole recordings at 48 kHz, resampled on the GPU in the scan: vad_scan_rate_device on VAD_SCAN_BENCH_N (default
     4 096) int16 recordings of 30 s at 48 kHz - the golden clip, every sample three times - already in device memory, hop = chunk / 2,

@@ -129,8 +129,11 @@ extern "C" hipError_t vadk_launch_silero_v5_scan16(const StepParams *p, const Sc
 
 // finished segments cut out of a block (csrc/scan_cut.hip: vadk_scan_cut), the kernel's arithmetic in plain C++, quad by quad as
 // its workgroups are listed: decode (s / 32767 or s / 32768 as IEEE quotients, G.711 / 32768), left | right | (L + R) * 0.5f, the
-// strict gate, then the float32 itself or clip(x * 32767, -32768, 32767) converted toward zero
-extern "C" hipError_t vadk_launch_scan_cut(const CutArgs *a, hipStream_t) {
+// strict gate, then the float32 itself or clip(x * 32767, -32768, 32767) converted toward zero.  gains (vadk_scan_cut_gain): the
+// gated value times gains[segment], one float32 multiply, ahead of either.  levels (csrc/scan_levels.hip: vadk_seg_levels): nothing
+// is stored - the gated values of a segment are folded into its vad_level (a.out, zeroed by the caller): energy_q32 +=
+// min(rint((double)x * x * 2^32), 2^32), peak = the larger bit pattern of |x|, clipped += |x| >= clip in float32
+static hipError_t fake_cut(const CutArgs *a, const float *gains, bool levels, float clip) {
     const uint32_t fmask = a->frame_shift >= 31u ? 0x7fffffffu : (1u << a->frame_shift) - 1u;
     const size_t ch = a->channels == 2 ? 2 : 1;
     for (uint32_t b = 0; b < a->nwork; ++b) {
@@ -149,6 +152,19 @@ extern "C" hipError_t vadk_launch_scan_cut(const CutArgs *a, hipStream_t) {
                     x = mode == SCAN_MIX ? (l + r) * 0.5f : mode == SCAN_RIGHT ? r : l;
                 }
                 if (a->thresh >= 0.f && !(std::fabs(x) > a->thresh)) x = 0.f;
+                if (levels) {
+                    vad_level &lv = static_cast<vad_level *>(a->out)[w.seg];
+                    const float ax = std::fabs(x);
+                    uint32_t bits, top;
+                    std::memcpy(&bits, &ax, 4);
+                    std::memcpy(&top, &lv.peak, 4);
+                    if (bits > top) lv.peak = ax;
+                    lv.clipped += ax >= clip ? 1 : 0;
+                    const double q = std::rint((double)x * (double)x * 4294967296.0);
+                    lv.energy_q32 += (int64_t)(q < 4294967296.0 ? q : 4294967296.0);      // (a NaN counts as 1: unspecified)
+                    continue;
+                }
+                if (gains) x = x * gains[w.seg];
                 if (a->out_fmt == VAD_CUT_F32) static_cast<float *>(a->out)[o] = x;
                 else {
                     const float v = x * 32767.0f;
@@ -159,6 +175,10 @@ extern "C" hipError_t vadk_launch_scan_cut(const CutArgs *a, hipStream_t) {
     }
     return hipSuccess;
 }
+
+extern "C" hipError_t vadk_launch_scan_cut(const CutArgs *a, hipStream_t) { return fake_cut(a, nullptr, false, 0.f); }
+extern "C" hipError_t vadk_launch_scan_cut_gain(const CutArgs *a, const float *gains, hipStream_t) { return fake_cut(a, gains, false, 0.f); }
+extern "C" hipError_t vadk_launch_seg_levels(const CutArgs *a, float clip, hipStream_t) { return fake_cut(a, nullptr, true, clip); }
 
 // the segment table of a scan (csrc/scan_segments.hip), the kernels' arithmetic in plain C++ and in one sweep: an END is a byte with
 // VAD_EV_END set and VAD_EV_REJECTED clear, its item the last one whose first index is not above it, the records in ascending
