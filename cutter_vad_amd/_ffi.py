@@ -134,6 +134,7 @@ class CutItem(C.Structure):
 VAD_CUT_FRAMES, VAD_CUT_RANGE = 0, 1
 VAD_CUT_PCM16, VAD_CUT_F32 = 0, 1
 VAD_CUT_WG_SAMPLES = 4096
+VAD_RENDER_MAX_RAMP = 65536
 CUT_LAYOUTS = {"frames": VAD_CUT_FRAMES, "range": VAD_CUT_RANGE}
 CUT_OUTPUTS = {"pcm16": VAD_CUT_PCM16, "f32": VAD_CUT_F32}
 
@@ -279,6 +280,10 @@ SIGNATURES = {
                                     C.c_float, C.c_int32, C.c_int32, _vp, C.c_int64]),
     "vad_scan_cut_gain_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32,
                                            C.c_int32, C.c_float, C.c_int32, C.c_int32, _vp, C.c_int64, _vp]),
+    "vad_scan_render": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32,
+                                  C.c_int32, C.c_float, C.c_int32, _vp, C.c_int64]),
+    "vad_scan_render_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int,
+                                         C.c_int32, C.c_int32, C.c_float, C.c_int32, _vp, C.c_int64, _vp]),
 }
 
 _lib = None

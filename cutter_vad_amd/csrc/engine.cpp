@@ -45,6 +45,7 @@ extern "C" hipError_t vadk_launch_silero_v5_scan16(const vadk::StepParams *p, co
 extern "C" hipError_t vadk_launch_scan_cut(const vadk::CutArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_cut_gain(const vadk::CutArgs *a, const float *gains, hipStream_t stream);
 extern "C" hipError_t vadk_launch_seg_levels(const vadk::CutArgs *a, float clip, hipStream_t stream);
+extern "C" hipError_t vadk_launch_scan_render(const vadk::RenderArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_segments(const vadk::SegArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_seg_stats(const vadk::SegArgs *a, uint32_t most, hipStream_t stream);
 extern "C" hipError_t vadk_launch_reseg_count(const vadk::ResegArgs *a, hipStream_t stream);
@@ -179,6 +180,9 @@ struct vad_engine {
     void *d_cut_out = nullptr; size_t d_cut_out_cap = 0;
     std::vector<vadk::CutSeg> cut_segs;
     std::vector<vadk::CutWork> cut_work;
+    // vad_scan_render: the workgroups of its output regions and its copy of the caller's ramp, as they were uploaded
+    std::vector<vadk::RenderWork> render_work;
+    std::vector<float> render_ramp;
     // vad_segments_device / vad_scan_segments: the extraction's work area - out_start as int32 [n + 1] (the host copy as it was
     // uploaded), then the chunk counts - and, for vad_scan_segments, the items' CSR positions, the count and the retained table
     uint8_t *d_segwork = nullptr; size_t d_segwork_cap = 0;
@@ -1694,6 +1698,9 @@ struct CutPlan {
     // vad_scan_cut_gain: a factor per segment (host), or nullptr.  vad_scan_levels: the call reduces where a cut stores - layout and
     // out_fmt are the range once as float32, no item's out_sample is read, and `out` is the records
     const float *gains; bool levels; float clip;
+    // vad_scan_render: the output ranges of two segments may overlap (three may not), every output sample is written, and a
+    // sample is faded by `ramp` (host, nramp entries) from both ends of its segment; layout is the range once
+    bool render; const float *ramp; int32_t nramp;
     // a. cut_check
     bool rate, rate_frames;
     uint32_t fshift;                         // log2 of the quads of a payload frame
@@ -1707,6 +1714,22 @@ struct CutPlan {
     // d. cut_upload: bytes of the tables, which lie in e->d_cut in this order - segments, workgroups, rows, tiles
     size_t sb, wb, rb, tb, gb;
 };
+
+// vad_scan_render's own arguments, between the block's checks and the items': the output's length and the ramp
+int render_check(vad_engine *e, const CutPlan &c) {
+    const char *who = c.who;
+    if (c.out_samples & 3)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_samples = %lld must be a multiple of 4", who, (long long)c.out_samples);
+    if (c.nramp < 0 || c.nramp > VAD_RENDER_MAX_RAMP || (c.nramp & 3))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: nramp = %d must be a multiple of 4 from 0 to %d", who, c.nramp,
+                       VAD_RENDER_MAX_RAMP);
+    if (c.nramp > 0 && !c.ramp) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null ramp", who);
+    for (int32_t k = 0; k < c.nramp; ++k)
+        if (!std::isfinite(c.ramp[k]))
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: ramp[%d] is %s, a ramp entry is a finite number", who, k,
+                           std::isnan(c.ramp[k]) ? "NaN" : "infinite");
+    return VAD_OK;
+}
 
 // a. every refusal that needs no device pointer, and the tables: e->cut_segs, e->cut_work (rate_frames: e->cut_rows - the work is
 // listed per window, by cut_windows) and the output spans.  Writes nothing to the device.  A call without segments (n == 0) is
@@ -1724,6 +1747,10 @@ int cut_check(vad_engine *e, CutPlan &c) {
     if (int rc = check_block_extent(e, who, c.hop, audio_samples, c.channels, c.fmt)) return rc;
     if (c.levels && c.clip != c.clip)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: clip_thresh is NaN", who);
+    if (c.render)
+        if (int rc = render_check(e, c)) return rc;
+    c.ab = (size_t)audio_samples * (size_t)c.channels * sample_bytes(c.fmt);
+    c.ob = c.out_fmt == VAD_CUT_PCM16 ? 2 : 4;
     if (n == 0) return VAD_OK;
     c.rate = c.chunk > 0;
     c.rate_frames = c.rate && c.layout == VAD_CUT_FRAMES;
@@ -1778,6 +1805,7 @@ int cut_check(vad_engine *e, CutPlan &c) {
                 return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 frames in one call", who);
             continue;
         }
+        if (c.render) continue;              // its workgroups follow the output, not the segments: render_regions
         for (uint32_t q = 0; q < nq; q += vadk::CUT_WG_QUADS) e->cut_work.push_back(vadk::CutWork{(uint32_t)i, q});
         if (e->cut_work.size() > (size_t)INT32_MAX)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d samples in one call", who, VAD_CUT_WG_SAMPLES);
@@ -1785,12 +1813,10 @@ int cut_check(vad_engine *e, CutPlan &c) {
     if (c.gains) e->cut_gains.assign(c.gains, c.gains + n);
     if (c.levels) c.spans.clear();           // no payload: segments may share samples
     std::sort(c.spans.begin(), c.spans.end(), [](const CutSpan &a, const CutSpan &b) { return a.lo < b.lo; });
-    for (size_t k = 1; k < c.spans.size(); ++k)
+    for (size_t k = 1; k < c.spans.size() && !c.render; ++k)
         if (c.spans[k].lo < c.spans[k - 1].hi)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output ranges of segments %lld and %lld overlap", who,
                            (long long)c.spans[k - 1].i, (long long)c.spans[k].i);
-    c.ab = (size_t)audio_samples * (size_t)c.channels * sample_bytes(c.fmt);
-    c.ob = c.out_fmt == VAD_CUT_PCM16 ? 2 : 4;
     return VAD_OK;
 }
 
@@ -1840,6 +1866,7 @@ int cut_block_host(vad_engine *e, CutPlan &c, const void *audio) {
         c.d_out = e->d_cut_out;
         return VAD_OK;
     }
+    if (c.render) return VAD_OK;             // the whole output, from sample 0: render_run sizes it
     const int64_t out_lo = c.spans.front().lo, out_hi = c.spans.back().hi;
     if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, (size_t)(out_hi - out_lo) * c.ob)) return rc;
     c.d_out = e->d_cut_out;
@@ -2018,6 +2045,119 @@ int cut_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items,
     return cut_copy_back(e, c, out, s);
 }
 
+// vad_scan_render: the output [0, out_samples) swept into REGIONS - maximal intervals that the same none, one or two segments
+// cover - and each region into workgroups of CUT_WG_QUADS output quads (e->render_work).  c.spans is sorted by lo; the ends of the
+// spans are a second sorted list, and the sweep merges the two, ends first where they meet a start: a segment that ends where
+// another begins does not overlap it.  A start that finds two segments open is the triple cover the call refuses.
+int render_regions(vad_engine *e, const CutPlan &c) {
+    std::vector<CutSpan> ends(c.spans);
+    std::sort(ends.begin(), ends.end(), [](const CutSpan &a, const CutSpan &b) { return a.hi < b.hi; });
+    e->render_work.clear();
+    int64_t open[2] = {-1, -1}, at = 0;
+    int nopen = 0;
+    // the region [at, hi) under the segments now open; false: more workgroups than a launch has (checked before any is listed - a
+    // gap may be as long as the caller's out_samples says)
+    auto emit = [&](int64_t hi) {
+        const int64_t q0 = at >> 2, q1 = hi >> 2;
+        if (q1 <= q0) return true;
+        if ((q1 - q0 + vadk::CUT_WG_QUADS - 1) / vadk::CUT_WG_QUADS + (int64_t)e->render_work.size() > (int64_t)INT32_MAX) return false;
+        const uint32_t a = nopen > 0 ? (uint32_t)open[0] : vadk::RENDER_NONE, b = nopen > 1 ? (uint32_t)open[1] : vadk::RENDER_NONE;
+        for (int64_t q = q0; q < q1; q += vadk::CUT_WG_QUADS)
+            e->render_work.push_back(vadk::RenderWork{a, b, (uint64_t)q, (uint32_t)std::min<int64_t>(vadk::CUT_WG_QUADS, q1 - q), 0u});
+        at = hi;
+        return true;
+    };
+    auto too_many = [&]() {
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d samples in one call", c.who, VAD_CUT_WG_SAMPLES);
+    };
+    size_t is = 0, ie = 0;
+    while (ie < ends.size()) {
+        if (is < c.spans.size() && c.spans[is].lo < ends[ie].hi) {
+            const CutSpan &sp = c.spans[is++];
+            if (!emit(sp.lo)) return too_many();
+            if (nopen == 2)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: output sample %lld is covered by the segments %lld, %lld and %lld, "
+                               "at most two may overlap", c.who, (long long)sp.lo, (long long)open[0], (long long)open[1], (long long)sp.i);
+            open[nopen++] = sp.i;
+        } else {
+            const CutSpan &sp = ends[ie++];
+            if (!emit(sp.hi)) return too_many();
+            if (open[0] == sp.i) open[0] = open[1];
+            --nopen;
+        }
+    }
+    if (!emit(c.out_samples)) return too_many();
+    return VAD_OK;
+}
+
+// vad_scan_render / _device with e->mu held: cut_check's refusals under this name (without the overlap of two), the regions, then
+// the block and the output as the cuts find them, one upload of the tables - segments, ramp, workgroups, gains, in this order in
+// e->d_cut - and one launch, which writes every quad of the output: the gaps are zeroed by workgroups of the same launch (no
+// memset per gap, and no second pass over the samples a memset of the whole output would cost).
+int render_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const float *gains, const float *ramp, int32_t nramp,
+               const void *audio, int64_t audio_samples, int32_t channels, int fmt, int32_t sr_in, int chunk, int32_t hop, float thr, int32_t out_fmt,
+               void *out, int64_t out_samples, void *stream) {
+    hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    CutPlan c{who, items, n, audio_samples, channels, fmt, hop, thr, VAD_CUT_RANGE, out_fmt, out_samples, chunk, sr_in, gains, false, 0.0f, true, ramp, nramp};
+    if (int rc = cut_check(e, c)) return rc;
+    if (n == 0) e->cut_segs.clear();
+    if (int rc = render_regions(e, c)) return rc;
+    if (out_samples == 0) return VAD_OK;
+    if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if (dev) {
+        if (n > 0) {
+            if (int rc = cut_block_device(e, c, audio, out)) return rc;
+        } else if (reinterpret_cast<uintptr_t>(out) & 15) {
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output must be 16-byte aligned", who);
+        }
+        c.d_out = out;
+    } else {
+        if (n > 0)
+            if (int rc = cut_block_host(e, c, audio)) return rc;
+        if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, (size_t)out_samples * c.ob)) return rc;
+        c.d_out = e->d_cut_out;
+    }
+    const size_t sb = sizeof(vadk::CutSeg) * e->cut_segs.size(), pb = sizeof(float) * (size_t)nramp;
+    const size_t wb = sizeof(vadk::RenderWork) * e->render_work.size(), gb = gains && n > 0 ? sizeof(float) * (size_t)n : 0;
+    if (int rc = ensure(e, e->d_cut, e->d_cut_cap, sb + pb + wb + gb)) return rc;
+    if (!dev && audio && n > 0) {
+        HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, c.ab, hipMemcpyHostToDevice, s));
+        set_resident(e, c.ab, c.channels, c.fmt, c.rate ? c.sr_in : 0);
+    }
+    e->render_ramp.assign(ramp, ramp + nramp);
+    if (sb) HIP_TRY(e, hipMemcpyAsync(e->d_cut, e->cut_segs.data(), sb, hipMemcpyHostToDevice, s));
+    if (pb) HIP_TRY(e, hipMemcpyAsync(e->d_cut + sb, e->render_ramp.data(), pb, hipMemcpyHostToDevice, s));
+    HIP_TRY(e, hipMemcpyAsync(e->d_cut + sb + pb, e->render_work.data(), wb, hipMemcpyHostToDevice, s));
+    if (gb) HIP_TRY(e, hipMemcpyAsync(e->d_cut + sb + pb + wb, e->cut_gains.data(), gb, hipMemcpyHostToDevice, s));
+    vadk::RenderArgs a{};
+    a.audio = n > 0 ? c.d_audio : nullptr;
+    a.out = c.d_out;
+    a.segs = reinterpret_cast<const vadk::CutSeg *>(e->d_cut);
+    a.work = reinterpret_cast<const vadk::RenderWork *>(e->d_cut + sb + pb);
+    a.gains = gb ? reinterpret_cast<const float *>(e->d_cut + sb + pb + wb) : nullptr;
+    a.ramp = pb ? reinterpret_cast<const float *>(e->d_cut + sb) : nullptr;
+    a.audio_bytes = n > 0 ? (uint32_t)c.ab : 0u;
+    a.nwork = (uint32_t)e->render_work.size();
+    a.nrampq = (uint32_t)nramp >> 2;
+    a.fmt = fmt;
+    a.channels = channels;
+    a.out_fmt = out_fmt;
+    a.thresh = c.rate ? -1.0f : thr;             // no input-rate sample was ever gated
+    const hipError_t r = vadk_launch_scan_render(&a, s);
+    const int rc = r != hipSuccess ? e->hip_fail(r, "kernel launch (scan render)") : VAD_OK;
+    if (dev) {
+        // the launch reads the engine's tables: the next scan or cut waits for it, as behind vad_scan_device
+        if (int rc2 = scan_mark_pending(e, s)) return rc2;
+        return rc;
+    }
+    if (rc) return rc;
+    HIP_TRY(e, hipMemcpyAsync(out, c.d_out, (size_t)out_samples * c.ob, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    return VAD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2127,6 +2267,30 @@ int vad_scan_cut_gain_device(vad_engine *e, const vad_cut_item *items, int64_t n
     if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
     return cut_run(e, true, who, items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, d_out, out_samples,
                    stream, chunk, chunk ? sr_in : 0, gains, true);
+}
+
+int vad_scan_render(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const float *ramp, int32_t nramp, const void *audio,
+                    int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int32_t out_fmt,
+                    void *out, int64_t out_samples) {
+    static const char *who = "vad_scan_render";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int chunk = 0;
+    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
+    return render_run(e, false, who, items, n, gains, ramp, nramp, audio, audio_samples, channels, frame_fmt, chunk ? sr_in : 0, chunk, hop,
+                      denoise_thresh, out_fmt, out, out_samples, nullptr);
+}
+
+int vad_scan_render_device(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const float *ramp, int32_t nramp,
+                           const void *d_audio, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop,
+                           float denoise_thresh, int32_t out_fmt, void *d_out, int64_t out_samples, void *stream) {
+    static const char *who = "vad_scan_render_device";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int chunk = 0;
+    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
+    return render_run(e, true, who, items, n, gains, ramp, nramp, d_audio, audio_samples, channels, frame_fmt, chunk ? sr_in : 0, chunk, hop,
+                      denoise_thresh, out_fmt, d_out, out_samples, stream);
 }
 
 }  // extern "C"

@@ -285,6 +285,38 @@ struct CutArgs {
     float thresh;             // denoise gate, < 0 = off
 };
 
+// one finished piece of audio out of a scanned block (csrc/scan_render.hip: vadk_scan_render; vad_scan_render).  The kernel is
+// driven by the OUTPUT: the host sweeps the segments' output spans into regions - maximal runs of output quads covered by the same
+// none, one or two segments - and lists a workgroup per CUT_WG_QUADS quads of a region, so the kind of a workgroup is uniform.
+// The segments are CutSeg, the sample range once (input quad quad_in + k for local quad k = output quad - quad_out).  ramp holds
+// nrampq quads of the caller's fade table: local quad k of a segment is multiplied by ramp quad k if k < nrampq (the fade-in) and
+// then by ramp quad nquads - 1 - k with its four components reversed if that index is below nrampq (the fade-out).
+constexpr uint32_t RENDER_NONE = 0xffffffffu;
+struct RenderWork {
+    uint32_t seg_a, seg_b;    // the segments that cover this share: both RENDER_NONE = a gap (zeros), seg_b RENDER_NONE = one
+    uint64_t quad_out;        // first output quad of this workgroup's share
+    uint32_t nquads;          // 1 .. CUT_WG_QUADS
+    uint32_t reserved;
+};
+static_assert(sizeof(RenderWork) == 24, "RenderWork layout");
+struct RenderArgs {
+    const void *audio;        // the block, in its wire format
+    void *out;                // int16 or float32 samples: every quad of it is in exactly one workgroup's share
+    const CutSeg *segs;
+    const RenderWork *work;   // [nwork]: one entry per workgroup
+    const float *gains;       // [segments] or nullptr: no factor
+    const float *ramp;        // [4 nrampq], or nullptr with nrampq = 0
+    uint32_t audio_bytes;     // the buffer descriptor's range
+    uint32_t nwork;
+    uint32_t nrampq;          // nramp / 4
+    int32_t fmt;              // vad_frame_format
+    int32_t channels;         // 1 or 2
+    int32_t out_fmt;          // 0 = int16 PCM, 1 = float32
+    float thresh;             // denoise gate, < 0 = off
+    uint32_t reserved;
+};
+static_assert(sizeof(RenderArgs) == 80, "RenderArgs layout");
+
 // the segment table of a scan (csrc/scan_segments.hip; vad_segments_device, vad_scan_segments).  Flat index k of the scan's CSR
 // arrays is an END iff (events[k] & SEG_EV_MASK) == SEG_EV_END; every END becomes one SegRecord (the header's vad_segment), in
 // ascending k.  Three passes fix that order: a workgroup of SEG_THREADS threads counts the ENDs of SEG_WG_FRAMES consecutive frames

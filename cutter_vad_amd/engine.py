@@ -841,6 +841,55 @@ class Engine:
         self._check(self._lib.vad_scan_levels_device(self._h, items, len(start) - 1, d_audio or None, int(audio_samples), int(channels), int(fmt),
                                                      sr or 0, hop, thr, float(clip), d_levels or None, stream or None))
 
+    # ------------------------------------------------------------------ rendered audio
+    @staticmethod
+    def _render_ramp(ramp) -> np.ndarray:
+        return np.zeros(0, np.float32) if ramp is None else np.ascontiguousarray(np.asarray(ramp, np.float32).reshape(-1))
+
+    def render(self, segments, out_start, out_samples: int, hop: Optional[int] = None, ramp=None, gains=None, denoise: Optional[float] = 0.01,
+               out="pcm16", audio=None, law: Optional[str] = None, i16_scale: int = 32767, sample_rate: Optional[int] = None) -> np.ndarray:
+        """One finished piece of audio (``vad_scan_render``): the sample range of segment i - ``segments`` as in ``cut`` - goes to
+        ``out_start[i]`` (a multiple of 4) of an output of ``out_samples`` samples (a multiple of 4), faded by ``ramp`` - a float32
+        table, ``cutter_vad_amd.scan.fade_ramp`` makes the usual ones - read forwards from the segment's first sample and from its
+        last; where TWO segments share output samples their faded samples are added (a crossfade; three are refused), and every
+        sample no segment covers is zero.  ``gains`` as in ``cut``; ``out="pcm16"`` / ``"f32"`` as there.  -> the ``out_samples``
+        samples.  A sample of a segment is what ``cut(layout="range", out="f32", gains=gains)`` gives, times the two ramp entries,
+        each a float32 multiply.  ``audio``, ``law``, ``i16_scale``, ``sample_rate`` and the ``scan_session()`` rule as in ``cut``;
+        on a block at another rate the samples are input-rate samples and never gated."""
+        of = self._cut_enum(_ffi.CUT_OUTPUTS, "out", out)
+        r = self._render_ramp(ramp)
+        with self._scan_lock:
+            sr, total, channels, fmt, ptr, _keep = self._cut_block("render", audio, law, i16_scale, sample_rate)
+            hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
+            items, start = self._cut_items(segments, hop, _ffi.VAD_CUT_RANGE, channels, out_samples=out_start, rate=sr)
+            n = len(start) - 1
+            data = np.empty(max(int(out_samples), 0), np.int16 if of == _ffi.VAD_CUT_PCM16 else np.float32)
+            thr = -1.0 if denoise is None else float(denoise)
+            g = None if gains is None else self._cut_gains(gains, n)
+            self._check(self._lib.vad_scan_render(self._h, items, n, None if g is None else _ptr(g, C.c_float),
+                                                  _ptr(r, C.c_float) if r.size else None, r.size, ptr, total, channels, fmt, sr or 0, hop, thr,
+                                                  of, data.ctypes.data_as(C.c_void_p), int(out_samples)))
+        return data
+
+    def render_device(self, segments, out_start, d_audio: int, audio_samples: int, d_out: int, out_samples: int, hop: Optional[int] = None,
+                      ramp=None, gains=None, fmt: int = _ffi.VAD_FMT_F32, channels: int = 1, denoise: Optional[float] = 0.01, out="pcm16",
+                      stream: int = 0, sample_rate: Optional[int] = None) -> None:
+        """``render`` on device pointers (integers; ``vad_scan_render_device``): the block at ``d_audio`` as ``cut_device`` takes it,
+        all ``out_samples`` samples to ``d_out`` (16-byte aligned) - no memset by the caller.  ``ramp`` and ``gains`` are host
+        arrays, read before the call returns.  Asynchronous on ``stream``."""
+        of = self._cut_enum(_ffi.CUT_OUTPUTS, "out", out)
+        r = self._render_ramp(ramp)
+        sr = self._scan_rate(sample_rate)
+        hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
+        items, start = self._cut_items(segments, hop, _ffi.VAD_CUT_RANGE, int(channels), out_start, rate=sr)
+        n = len(start) - 1
+        thr = -1.0 if denoise is None else float(denoise)
+        g = None if gains is None else self._cut_gains(gains, n)
+        self._check(self._lib.vad_scan_render_device(self._h, items, n, None if g is None else _ptr(g, C.c_float),
+                                                     _ptr(r, C.c_float) if r.size else None, r.size, d_audio or None, int(audio_samples),
+                                                     int(channels), int(fmt), sr or 0, hop, thr, of, d_out or None, int(out_samples),
+                                                     stream or None))
+
     # ------------------------------------------------------------------ tick assembler (shared-pool serving)
     def tick_push(self, slot: int, frame, gate_on: bool = True, i16_scale: int = 32767, sample_rate: Optional[int] = None,
                   law: Optional[str] = None) -> None:

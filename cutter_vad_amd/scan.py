@@ -107,6 +107,25 @@ def _need_levels(engine, who: str, what: str = "levels=True") -> None:
                                  f"a scan left on the GPU), {type(engine).__name__} has none")
 
 
+def _need_render(engine, who: str) -> None:
+    if not hasattr(engine, "render"):
+        raise ConfigurationError("render", "given", f"{who} needs an engine with render (the audio is assembled from the block a scan "
+                                 f"left on the GPU), {type(engine).__name__} has none")
+
+
+def fade_ramp(n: int, shape: str = "linear") -> np.ndarray:
+    """A fade table of ``n`` entries for ``Engine.render``, rising from just above 0 to just below 1: ``"linear"`` is
+    ``(k + 0.5) / n``, ``"cosine"`` is ``0.5 - 0.5 cos(pi (k + 0.5) / n)`` - computed in float64 and rounded once to float32.
+    Two linear ramps that cross sum to exactly 1 in float64; the half-sample offset keeps a faded edge from starting on a zero."""
+    n = int(n)
+    if n < 0:
+        raise ConfigurationError("n", repr(n), f"fade_ramp: n is 0 or more, got {n}")
+    if shape not in ("linear", "cosine"):
+        raise ConfigurationError("shape", repr(shape), f"fade_ramp: shape is 'linear' or 'cosine', got {shape!r}")
+    t = (np.arange(n, dtype=np.float64) + 0.5) / max(n, 1)
+    return (t if shape == "linear" else 0.5 - 0.5 * np.cos(np.pi * t)).astype(np.float32)
+
+
 def level_stats(levels, nsamples) -> Tuple[np.ndarray, np.ndarray]:
     """``Engine.levels`` records and the segments' sample counts -> ``(energy, rms)`` as float64 arrays: ``energy = energy_q32 /
     2^32`` (``AudioUtils.calculate_energy`` of the segment, samples beyond full scale counted as 1) and ``rms = sqrt(energy /
@@ -439,5 +458,147 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
                     else:
                         one.append((a, b, pcm.copy()))
                 lists.append(one)
+            out[i] = lists if split else lists[0]
+    return out
+
+
+def _join_places(counts: Sequence[int], nramp: int, gap: int) -> List[int]:
+    """where the segments of one piece start in ``mode="join"``: back to back - neighbours ``gap`` samples apart, or, with no gap,
+    overlapping by ``min(nramp, S_i / 2, S_{i+1} / 2)`` rounded down to a multiple of 4: a segment's two overlaps never meet, so no
+    sample is covered three times, even around a segment shorter than the ramp"""
+    at, places = 0, []
+    for i, s in enumerate(counts):
+        places.append(at)
+        if i + 1 < len(counts):
+            at += s + gap if gap > 0 else s - min(nramp, s // 2, counts[i + 1] // 2) // 4 * 4
+    return places
+
+
+def render_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
+                      law: Optional[str] = None, channel="mix", sample_rate: Optional[int] = None, open_end: bool = False,
+                      refine: Optional[SegmentRefine] = None, normalize: Optional[float] = None, mode: str = "join", fade_ms: float = 10.0,
+                      gap_ms: float = 0.0, shape: str = "linear", wav: bool = True) -> List:
+    """One finished piece of audio per recording: per recording ``(payload, timeline)`` (per channel for ``"split"``, as in
+    ``scan_recordings``).  ``mode="join"`` is silence removal: the recording's speech segments (their sample ranges, as
+    ``cut_recordings(layout="range")`` cuts them) back to back, each faded in and out over ``fade_ms`` by a ``fade_ramp`` of
+    ``shape``; with ``gap_ms == 0`` neighbours overlap by the ramp (by half the shorter segment where that is less) and crossfade,
+    with ``gap_ms > 0`` they lie that much silence apart.  ``mode="mask"`` is a VAD-driven noise gate: the output has the
+    recording's own length, each segment sits where it was, its edges faded, and every sample outside speech is zero; ranges of a
+    recording that touch or overlap are first merged into one.  ``payload``: 16-bit PCM behind a WAV header - of ``sample_rate``
+    when given, else ``config.output_wav_sample_rate`` - or, with ``wav=False``, the int16 samples.  ``timeline``:
+    ``[(out_start, src_start, nsamples), ...]``, which maps the output back to the recording.  ``fade_ms`` and ``gap_ms`` are
+    rounded to a multiple of 4 samples at the payload's rate.  One scan, at most one ``Engine.levels`` call (``normalize``, as in
+    ``cut_recordings``: per listed segment - in ``"mask"`` per merged one) and one ``Engine.render`` of the block the scan left
+    on the GPU, under ``Engine.scan_session()``: only the finished audio crosses the link back.  ``hop``, ``law``, ``sample_rate``,
+    ``open_end`` and ``refine`` as in ``cut_recordings``; on recordings at another rate the samples are the recording's own,
+    never gated.  An engine object without ``render``: ``ConfigurationError``."""
+    from .pool import default_pool, resolve_model_path
+    from .utils.wav_writer import WAVWriter
+    who = "render_recordings"
+    split = isinstance(channel, str) and channel == "split"
+    if not (channel in ("mix", "split") if isinstance(channel, str) else isinstance(channel, (int, np.integer)) and int(channel) in (0, 1)):
+        raise ConfigurationError("channel", repr(channel), f"{who}: channel is 'mix', 0, 1 or 'split' for the whole corpus, got {channel!r}")
+    if mode not in ("join", "mask"):
+        raise ConfigurationError("mode", repr(mode), f"{who}: mode is 'join' or 'mask', got {mode!r}")
+    if not (fade_ms >= 0 and gap_ms >= 0):
+        raise ConfigurationError("fade_ms", repr((fade_ms, gap_ms)), f"{who}: fade_ms and gap_ms are 0 or more, got {fade_ms!r} and {gap_ms!r}")
+    cfg = config or VADConfig()
+    if engine is None:
+        engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
+    _need_render(engine, who)
+    if open_end:
+        _need_tails(engine, who)
+    if refine is not None:
+        _need_refine(engine, who)
+    if normalize is not None:
+        _need_levels(engine, who, "normalize=")
+    frame = engine.frame_samples
+    if cfg.buffer_size != frame:
+        raise ConfigurationError(f"{who} frames at the model's frame size: buffer_size = {cfg.buffer_size}, "
+                                 f"the engine's frames have {frame} samples")
+    rate = None if sample_rate is None or int(sample_rate) == int(engine.sample_rate) else int(sample_rate)
+    if rate is not None:
+        if rate not in (8000, 16000, 24000, 48000):
+            raise ConfigurationError("sample_rate", repr(sample_rate), f"{who}: recordings at 8000, 16000, 24000 or 48000 Hz, got {sample_rate!r}")
+        frame = engine.scan_chunk_samples(rate)      # the ranges count input samples
+    hop = frame // 2 if hop is None else int(hop)
+    hz = rate if rate is not None else int(engine.sample_rate)
+    nramp, gap = int(round(fade_ms * hz / 4000.0)) * 4, int(round(gap_ms * hz / 4000.0)) * 4
+    if nramp > _ffi.VAD_RENDER_MAX_RAMP:
+        raise ConfigurationError("fade_ms", repr(fade_ms), f"{who}: a fade of {nramp} samples, a ramp has {_ffi.VAD_RENDER_MAX_RAMP} at the most")
+    ramp = fade_ramp(nramp, shape)
+    recordings = [np.asarray(r) for r in recordings]
+    if not recordings:
+        return []
+    writer = WAVWriter(int(sample_rate) if sample_rate is not None else cfg.output_wav_sample_rate, 16, 1)
+    denoise = 0.01 if cfg.enable_denoising else None
+    out: List = [None] * len(recordings)
+    for two in (False, True):
+        idx = [i for i, r in enumerate(recordings) if (r.ndim == 2) == two]
+        if not idx:
+            continue
+        per = 2 if two and split else 1
+        chans = (0, 1) if per == 2 else (channel if two else 0,)
+        slots = engine.open_streams(len(idx) * per)
+        try:
+            engine.set_thresholds_many(slots, (cfg.vad_start_probability, cfg.vad_end_probability, cfg.voice_start_ratio,
+                                               cfg.voice_end_ratio, cfg.voice_start_frame_count, cfg.voice_end_frame_count))
+            with engine.scan_session():
+                ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, denoise, channel, rate=rate,
+                                      open_end=open_end, refine=refine)
+                ranges = [[[(a, b) for a, b, *_ in rg] for rg in rc] for rc in ranges]
+                if mode == "mask":
+                    # touching or overlapping ranges of one piece (neighbours from a split, small hops) become one, on the same hop grid
+                    merged = []
+                    for rc in ranges:
+                        pieces = []
+                        for rg in rc:
+                            one: List[Tuple[int, int]] = []
+                            for a, b in sorted(rg):
+                                if one and a <= one[-1][1]:
+                                    one[-1] = (one[-1][0], max(one[-1][1], b))
+                                else:
+                                    one.append((a, b))
+                            pieces.append(one)
+                        merged.append(pieces)
+                    ranges = merged
+                table = _cut_table(engine, ranges, chans, frame, hop)
+                # every piece - (recording, channel) - owns a stretch of the one output, a multiple of 4 samples long
+                places, lengths, base = [], [], 0
+                for k, rc in enumerate(ranges):
+                    for rg in rc:
+                        counts = [b - a for a, b in rg]
+                        if mode == "mask":
+                            at, size = [a for a, _ in rg], (int(recordings[idx[k]].shape[0]) + 3) // 4 * 4
+                        else:
+                            at = _join_places(counts, nramp, gap)
+                            size = at[-1] + counts[-1] if counts else 0
+                        places += [base + p for p in at]
+                        lengths.append((base, size, at, counts))
+                        base += size
+                gains = None
+                if table and normalize is not None:
+                    peak = engine.levels(table, hop=hop, denoise=denoise)["peak"]
+                    usable = np.isfinite(peak) & (peak > 0)
+                    gains = np.where(usable, np.float32(normalize) / np.where(usable, peak, np.float32(1)), np.float32(1)).astype(np.float32)
+                data = engine.render(table, places, base, hop=hop, ramp=ramp, gains=gains, denoise=denoise)
+        finally:
+            for s in slots:
+                engine.close_stream(int(s))
+        j = 0
+        for k, (i, rc) in enumerate(zip(idx, ranges)):
+            lists = []
+            for rg in rc:
+                lo, size, at, counts = lengths[j]
+                j += 1
+                if mode == "mask":
+                    size = int(recordings[i].shape[0])      # the padding to a multiple of 4 is trimmed
+                pcm = data[lo:lo + size]
+                timeline = [(p, a, s) for p, (a, _), s in zip(at, rg, counts)]
+                if wav:
+                    raw = pcm.tobytes()
+                    lists.append((writer.header(len(raw)) + raw, timeline))
+                else:
+                    lists.append((pcm.copy(), timeline))
             out[i] = lists if split else lists[0]
     return out

@@ -756,6 +756,59 @@ VAD_API int vad_scan_cut_gain_device(vad_engine *e, const vad_cut_item *items, i
                                      int64_t out_samples, void *stream);
 
 /*
+ * Rendered audio: one finished piece of audio per call - the segments of a block faded at their edges, crossfaded where two of
+ * them share output samples, joined, everything else silence.  The two standard products of a VAD come out of it by where the caller
+ * places the segments: silence removal (the segments back to back, neighbours overlapping by the ramp or a fixed pause apart) and
+ * a VAD-driven noise gate (each segment at first_frame * hop of an output as long as the recording).  vad_scan_cut writes hard
+ * edges, refuses two segments that share an output sample and leaves every sample outside a segment unwritten; this call is driven
+ * by the OUTPUT instead.
+ *
+ * vad_scan_render.  The items are vad_cut_item, always in the VAD_CUT_RANGE layout: segment i has
+ * S_i = vad_cut_samples / vad_rate_cut_samples(nframes, .., VAD_CUT_RANGE) samples and covers out[out_sample .. out_sample + S_i).
+ * THE RULE:
+ *   1. v_i[k] is the float32 that vad_scan_cut_gain with VAD_CUT_RANGE, VAD_CUT_F32 and the same arguments writes for sample k of
+ * segment i: decoded, channel-selected and gated - on a rate block (sr_in as in vad_scan_levels) the input-rate sample, never
+ * gated - times gains[i] (a host array [n]; gains == NULL: no factor).
+ *   2. w_i[k] = (v_i[k] * a) * b, two float32 multiplies of their own, never fused, in that order: a = ramp[k] if k < nramp, else
+ * 1.0f; b = ramp[S_i - 1 - k] if S_i - 1 - k < nramp, else 1.0f.  The one table (host, nramp entries) serves the fade-in, read
+ * forwards from the segment's first sample, and the fade-out, read forwards from its last sample; in a segment shorter than
+ * 2 * nramp both act on the samples where they meet.  nramp == 0: no ramp.  The shape of the ramp is the caller's: the kernel never
+ * computes one, there is no transcendental and no division in the rule.
+ *   3. Output sample s is +0.0f where no segment covers it, w itself where one does, and the float32 sum w_i + w_j - one add,
+ * commutative: the bytes depend neither on the order of the items nor on scheduling - where two do.  Three or more: refused.  Then
+ * the cut's conversion: VAD_CUT_F32 stores the value, VAD_CUT_PCM16 clip(x * 32767, -32768, 32767) toward zero.
+ *   4. EVERY sample of out[0 .. out_samples) is written, gaps as zeros: the host form copies the whole range back, the device form
+ * needs no memset by the caller.  A pause between joined segments is the caller placing them apart.
+ *   audio == NULL: the resident block, as in the cuts; with an audio the call uploads it and it becomes the resident block (n == 0
+ * uploads nothing).  Works on every engine, Silero V4 and VAD_ENGINE_SHARED_GPU included: no model kernel runs.  The call first
+ * waits for earlier *_device launches that read the engine's tables.
+ *   VAD_ERR_INVALID_ARG, each with a message under this function's name and nothing written, in THIS ORDER (a call with several
+ * faults gets the first): sr_in (vad_scan_levels'); a negative n, audio_samples or out_samples, null items with n > 0; the frame
+ * format and channels; out_fmt; hop and the block's extent; out_samples not a multiple of 4; nramp < 0, above
+ * VAD_RENDER_MAX_RAMP or not a multiple of 4; a null ramp with nramp > 0; a ramp entry that is NaN or infinite (the message names
+ * the lowest index); then per item in listing order every refusal of vad_scan_cut_gain that concerns the item (its recording's
+ * offset, frames, extent in the block, channel, reserved, out_sample and length inside the output, a non-finite gain); an output
+ * sample covered by three segments (the message names the sample and all three) or an output of more than 2^31 - 1 workgroups,
+ * whichever the sweep over the output meets first; a null out with out_samples > 0; and last what
+ * concerns the pointers: with audio == NULL the resident block's refusals, in the device form the alignment of d_audio and d_out.
+ * The overlap of TWO segments, which the cuts refuse, is accepted here.  n == 0 with out_samples > 0: VAD_OK, all zeros.
+ *   vad_scan_render_device: d_audio and d_out (16-byte aligned, out_samples samples) as vad_scan_cut_device takes them; gains and
+ * ramp stay HOST arrays, read before the call returns; enqueues on `stream` (NULL = the engine's own) and returns.
+ *   A workgroup of the kernel serves up to VAD_CUT_WG_SAMPLES consecutive output samples with one cover set; gaps are zeroed by
+ * workgroups of the same launch.
+ *   VAD_ABI_VERSION is unchanged: the presence of vad_scan_render is how a caller detects the feature.
+ */
+#define VAD_RENDER_MAX_RAMP 65536      /* samples: 1.36 s at 48 kHz, a 256 KiB table */
+VAD_API int vad_scan_render(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains /*host [n] or NULL*/,
+                            const float *ramp /*host [nramp] or NULL*/, int32_t nramp, const void *audio /*or NULL*/,
+                            int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh,
+                            int32_t out_fmt, void *out, int64_t out_samples);
+VAD_API int vad_scan_render_device(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains /*host [n] or NULL*/,
+                                   const float *ramp /*host [nramp] or NULL*/, int32_t nramp, const void *d_audio,
+                                   int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop,
+                                   float denoise_thresh, int32_t out_fmt, void *d_out, int64_t out_samples, void *stream);
+
+/*
  * Pipelined host ingest.  vad_step* on host pointers are copy -> kernel -> copy -> wait; at 8 192 streams the PCIe copy is
  * 5-8 x the kernel, so a serving loop should overlap the copy of tick t+1 with the kernel of tick t:
  *

@@ -1389,6 +1389,142 @@ def scan_rate_cut():
     return row
 
 
+def scan_render():
+    """What one finished piece of audio per recording costs, on scan_levels' corpus: VAD_SCAN_BENCH_N (default 1 024)
+    int16 recordings of 30 s at 16 kHz, hop 256, the table of its scan.  (a) silence removal: every recording's segments joined
+    with a 10 ms linear crossfade to PCM16 - Engine.render on the block the scan left on the GPU, against today's way to the same
+    bytes: Engine.cut(layout="range", out="f32") of the same table, then the fades, the overlap-add and the conversion in numpy;
+    the two alternate and their bytes are compared.  (b) the kernel call alone on device pointers, HIP-event timed as scan_levels'
+    (c): vad_scan_render_device without overlaps or ramp - the segments packed back to back - against
+    vad_scan_cut_gain_device(VAD_CUT_RANGE, gains of ones) on the same table and output format, which writes the same bytes.
+    One warm-up, then three timed passes of each; medians; the result goes to profiles/scan_render.json."""
+    import ctypes as C
+    import json
+    import time
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    from cutter_vad_amd import _ffi, fade_ramp
+    from cutter_vad_amd.scan import _join_places
+    N = int(os.environ.get("VAD_SCAN_BENCH_N", "1024"))
+    eng = Engine(blob(5), max_streams=max(N, 16))
+    hop, frame, nramp = 256, 512, 160
+    pcm = np.tile(np.load(os.path.join(root, "tests", "golden", "speech16k_i16.npz"))["pcm"].astype(np.int16), 3)
+    rng = np.random.default_rng(N)
+    ns = 30 * 16000
+    recs = [pcm[a:a + ns] for a in rng.integers(0, pcm.size - ns + 1, N)]
+    slots = eng.open_streams(N)
+    eng.set_thresholds_many(slots, (0.4, 0.3, 0.8, 0.95, 6, 12))
+    med = lambda v: float(np.median(v))
+    ramp = fade_ramp(nramp)
+    row = {"config": f"scan_render: {N} int16 recordings of 30 s at 16 kHz in one call, hop {hop}, joined with a 10 ms crossfade to PCM16",
+           "recordings": N, "passes": 3}
+    with eng.scan_session():
+        table = eng.scan_segments(slots, recs, hop=hop, denoise=0.01)
+        last = eng.last_scan
+        offs = [int(o) for o in last["offsets"]]
+        item = table["item"].tolist()
+        segs = [(offs[i], f, n) for i, f, n in zip(item, table["first_frame"].tolist(), table["nframes"].tolist())]
+        counts = [(n - 1) * hop + frame for _, _, n in segs]
+        # a recording's segments back to back, crossfaded; the recordings' pieces one behind the other in one output
+        places, base, k = [], 0, 0
+        while k < len(segs):
+            m = k
+            while m < len(segs) and item[m] == item[k]:
+                m += 1
+            at = _join_places(counts[k:m], nramp, 0)
+            places += [base + p for p in at]
+            base += at[-1] + counts[m - 1]
+            k = m
+        row.update(segments=len(segs), speech_samples=int(sum(counts)), out_samples=base, block_samples=int(last["samples"]))
+
+        def route_a():
+            return eng.render(segs, places, base, hop=hop, ramp=ramp, denoise=0.01)
+
+        def route_b():
+            t0 = time.perf_counter()
+            data, start = eng.cut(segs, hop=hop, denoise=0.01, layout="range", out="f32")
+            t1 = time.perf_counter()
+            acc = np.zeros(base, np.float32)
+            for i, p in enumerate(places):
+                w = data[start[i]:start[i + 1]].copy()
+                m = min(nramp, w.size)
+                w[:m] *= ramp[:m]
+                w[w.size - m:] *= ramp[:m][::-1]
+                acc[p:p + w.size] += w
+            out = np.clip(acc * 32767, -32768, 32767).astype(np.int16)
+            return out, t1 - t0, time.perf_counter() - t1
+
+        got, (want, _, _) = route_a(), route_b()
+        # (numpy adds a segment to +0.0f where the kernel stores it: the same value, and PCM16 has one zero)
+        row["a_equal"] = bool(got.tobytes() == want.tobytes())
+        a_runs, b_runs, b_cut, b_np = [], [], [], []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            route_a()
+            a_runs.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            _, c, s = route_b()
+            b_runs.append(time.perf_counter() - t0)
+            b_cut.append(c)
+            b_np.append(s)
+        row.update(a_s_render_runs=a_runs, a_s_render=med(a_runs), a_s_cut_numpy_runs=b_runs, a_s_cut_numpy=med(b_runs), a_s_cut_f32=med(b_cut),
+                   a_s_numpy=med(b_np), a_ratio_cut_numpy_over_render=med(b_runs) / med(a_runs), a_bytes_back_render=2 * base, a_bytes_back_cut=int(4 * sum(counts)))
+    # (b) on device pointers: the kernels alone, the segments packed back to back
+    block = np.zeros(last["samples"], np.int16)
+    for r, o in zip(recs, offs):
+        block[o:o + r.size] = r
+    d_audio = torch.from_numpy(block).cuda()
+    total = int(sum(counts))
+    d_out = torch.empty(total + 16, dtype=torch.int16, device="cuda")
+    d_ref = torch.empty(total + 16, dtype=torch.int16, device="cuda")
+    ts = torch.cuda.Stream()
+    fmt = last["fmt"]
+    busy = torch.randn(6144, 6144, device="cuda")
+    lib, h, n = eng._lib, eng.handle, len(segs)
+    items, _ = eng._cut_items(segs, hop, _ffi.VAD_CUT_RANGE, 1)
+    ones = np.ones(n, np.float32)
+    gp = ones.ctypes.data_as(C.POINTER(C.c_float))
+    where = (d_audio.data_ptr(), block.size, 1, fmt)
+
+    def event_timed(fn):
+        out = []
+        for k in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            with torch.cuda.stream(ts):
+                torch.mm(busy, busy)
+            e0.record(ts)
+            assert fn() == 0
+            e1.record(ts)
+            torch.cuda.synchronize()
+            if k >= 2:                           # two warm-ups
+                out.append(e0.elapsed_time(e1) * 1e-3)
+        return out
+
+    calls = {"b_s_render_device": lambda: lib.vad_scan_render_device(h, items, n, None, None, 0, *where, 0, hop, 0.01, _ffi.VAD_CUT_PCM16,
+                                                                     d_out.data_ptr(), total, ts.cuda_stream),
+             "b_s_cut_gain_range_device": lambda: lib.vad_scan_cut_gain_device(h, items, n, gp, *where, 0, hop, 0.01, _ffi.VAD_CUT_RANGE,
+                                                                               _ffi.VAD_CUT_PCM16, d_ref.data_ptr(), total, ts.cuda_stream)}
+    for name, fn in calls.items():
+        runs = event_timed(fn)
+        row[name + "_runs"], row[name] = runs, med(runs)
+    row["b_equal"] = bool(torch.equal(d_out[:total], d_ref[:total]))
+    row["b_GBps_read_plus_written"] = 4 * total / row["b_s_render_device"] / 1e9
+    row["b_ratio_render_over_cut"] = row["b_s_render_device"] / row["b_s_cut_gain_range_device"]
+    eng.close()
+    with open(os.path.join(root, "profiles", "scan_render.json"), "w") as f:
+        json.dump({"what": "One finished piece of audio per recording (vad_scan_render, csrc/scan_render.hip): DESIGN 2.1q",
+                   "how": "python tools/bench_configs.py scan_render on one MI355X, one process.  (a) Engine.render and Engine.cut(range, "
+                          "f32) + numpy alternate, wall clock around the Python calls, one warm-up and three timed passes, medians; the latter uses "
+                          "only code the parent has.  (b) device forms: HIP events behind a matrix product that keeps the stream busy while "
+                          "the host builds the tables, ctypes items built outside the clock, two warm-ups and three timed passes.  Not "
+                          "measured: other corpus sizes, formats, rates and ramps, the mask mode, the spread between processes and boxes",
+                   "runs": [row]}, f, indent=1)
+        f.write("\n")
+    return row
+
+
 def single_stream_wrapper():
     """configs[0]: ONE stream through the drop-in VADWrapper (host framing + one launch + sync + callbacks per chunk)."""
     import time

@@ -180,6 +180,51 @@ extern "C" hipError_t vadk_launch_scan_cut(const CutArgs *a, hipStream_t) { retu
 extern "C" hipError_t vadk_launch_scan_cut_gain(const CutArgs *a, const float *gains, hipStream_t) { return fake_cut(a, gains, false, 0.f); }
 extern "C" hipError_t vadk_launch_seg_levels(const CutArgs *a, float clip, hipStream_t) { return fake_cut(a, nullptr, true, clip); }
 
+// one finished piece of audio (csrc/scan_render.hip: vadk_scan_render), the kernel's arithmetic in plain C++, output quad by output
+// quad as its workgroups are listed: per covering segment the cut's decoded, channel-selected, gated sample, times the gain, times
+// the fade-in entry (or 1), times the fade-out entry (or 1) - three float32 multiplies - then the sum of the two where two segments
+// cover the sample, zero where none does, and the cut's conversion
+static hipError_t fake_render(const RenderArgs *a) {
+    const size_t ch = a->channels == 2 ? 2 : 1;
+    const uint32_t nramp = 4 * a->nrampq;
+    for (uint32_t b = 0; b < a->nwork; ++b) {
+        const RenderWork w = a->work[b];
+        if (w.nquads < 1 || w.nquads > (uint32_t)CUT_WG_QUADS) return hipErrorInvalidValue;
+        for (uint64_t s = 4 * w.quad_out; s < 4 * (w.quad_out + w.nquads); ++s) {
+            float acc = 0.f;
+            for (int src = 0; src < 2; ++src) {
+                const uint32_t si = src == 0 ? w.seg_a : w.seg_b;
+                if (si == RENDER_NONE) continue;
+                const CutSeg sg = a->segs[si];
+                const uint32_t mode = sg.quad_in >> SCAN_MODE_SHIFT, qin = sg.quad_in & ((1u << SCAN_MODE_SHIFT) - 1u);
+                if (s < 4 * sg.quad_out || s >= 4 * (sg.quad_out + sg.nquads)) return hipErrorInvalidValue;
+                const uint64_t k = s - 4 * sg.quad_out, back = 4 * (uint64_t)sg.nquads - 1 - k;
+                const size_t i = 4 * (size_t)qin + k;
+                if ((i + 1) * ch * (a->fmt == VAD_FMT_F32 ? 4 : a->fmt >= VAD_FMT_ULAW8 ? 1 : 2) > a->audio_bytes) return hipErrorInvalidValue;
+                float x;
+                if (ch == 1) x = first_sample(a->audio, i, a->fmt, 1);
+                else {
+                    const float l = first_sample(a->audio, 2 * i, a->fmt, 1), r = first_sample(a->audio, 2 * i + 1, a->fmt, 1);
+                    x = mode == SCAN_MIX ? (l + r) * 0.5f : mode == SCAN_RIGHT ? r : l;
+                }
+                if (a->thresh >= 0.f && !(std::fabs(x) > a->thresh)) x = 0.f;
+                if (a->gains) x = x * a->gains[si];
+                volatile float y = x * (k < nramp ? a->ramp[k] : 1.0f);            // (volatile: each product is rounded on its own)
+                volatile float z = y * (back < nramp ? a->ramp[back] : 1.0f);
+                acc = src == 0 || w.seg_a == RENDER_NONE ? (float)z : acc + z;
+            }
+            if (a->out_fmt == VAD_CUT_F32) static_cast<float *>(a->out)[s] = acc;
+            else {
+                const float v = acc * 32767.0f;
+                static_cast<int16_t *>(a->out)[s] = (int16_t)(int)(v < -32768.0f ? -32768.0f : v > 32767.0f ? 32767.0f : v);
+            }
+        }
+    }
+    return hipSuccess;
+}
+
+extern "C" hipError_t vadk_launch_scan_render(const RenderArgs *a, hipStream_t) { return fake_render(a); }
+
 // the segment table of a scan (csrc/scan_segments.hip), the kernels' arithmetic in plain C++ and in one sweep: an END is a byte with
 // VAD_EV_END set and VAD_EV_REJECTED clear, its item the last one whose first index is not above it, the records in ascending
 // index up to seg_cap, the true count always; the statistics over the accepted frames max(first_frame, 0) .. e, the mean from the
