@@ -866,6 +866,7 @@ int vad_engine_create(const vad_engine_desc *desc, vad_engine **out) {
         // the third stream and, behind it in the same buffer, the fourth block range (vad_layout.h, ENC23_X3_BLOCKS; V5 only): one
         // allocation, one descriptor in the kernel, shared between engines on the concatenated bytes
         pw16.data_y.insert(pw16.data_y.end(), pw16.data_z.begin(), pw16.data_z.end());
+        pw16.data_y.insert(pw16.data_y.end(), pw16.data_d.begin(), pw16.data_d.end());      // the fifth (DFT_X3_BLOCKS) behind the fourth
         e->wbytes16y = pw16.data_y.size() * sizeof(float);
         if (!pw16.data_y.empty() && (r = weights_acquire(e->device, pw16.data_y, &e->d_wstream16y)) != hipSuccess)
             return bail(r, "hipMalloc / hipMemcpy(weights, 16-stream tiles, third stream)");
@@ -4399,8 +4400,9 @@ int vad_debug_pack_weights(int32_t model_version, const void *weights, size_t we
     // model_version 516 / 416: Silero V5 / V4 packed for the 16-stream tile kernels (tests/kernel_model.py models both packings);
     // 5161: the second stream of the 516 packing (PackedWeights::data_x: encoder.0 on bf16 splits), with the same section table;
     // 5162: its third (PackedWeights::data_y: encoder.1 on bf16 splits); 5163: the block range uploaded behind the third
-    // (PackedWeights::data_z: encoder.2 and encoder.3 on bf16 splits)
-    const bool t16 = model_version == 516 || (model_version >= 5161 && model_version <= 5163);
+    // (PackedWeights::data_z: encoder.2 and encoder.3 on bf16 splits); 5164: the one behind that (PackedWeights::data_d: the STFT's
+    // odd-bin tile on bf16 splits, 16 kHz model only)
+    const bool t16 = model_version == 516 || (model_version >= 5161 && model_version <= 5164);
     const bool ok = model_version == 5     ? vadk::pack_silero_v5(weights, weights_len, pw, perr)
                     : t16                  ? vadk::pack_silero_v5_t16(weights, weights_len, pw, perr)
                     : model_version == 4   ? vadk::pack_silero_v4(weights, weights_len, pw, perr)
@@ -4413,6 +4415,7 @@ int vad_debug_pack_weights(int32_t model_version, const void *weights, size_t we
     if (model_version == 5161) pw.data = std::move(pw.data_x);
     if (model_version == 5162) pw.data = std::move(pw.data_y);
     if (model_version == 5163) pw.data = std::move(pw.data_z);
+    if (model_version == 5164) pw.data = std::move(pw.data_d);
     if (n_floats) *n_floats = pw.data.size();
     if (sect_out) std::memcpy(sect_out, pw.sect, sizeof pw.sect);
     if (out) {

@@ -574,6 +574,26 @@ bool pack_silero_v5_t16(const void *blob, size_t len, PackedWeights &out, std::s
         return false;
     }
     out.data_z = std::move(sb.data);
+    // the fifth block range (vad_layout.h, DFT_X3_BLOCKS; 16 kHz model): the odd-bin tile of pack_dft_fold3_wave on the bf16 split -
+    // per wave the cos rows, then the -sin rows, each in two K-steps of 32 folded samples; the values are the ones S_STFT holds
+    sb = StreamBuilder();
+    if (!k8) {
+        const double two_pi = 6.283185307179586476925286766559;
+        for (int w = 0; w < NWAVES; ++w)
+            for (int part = 0; part < 2; ++part)
+                for (int s = 0; s < 2; ++s)
+                    if (!x3_unit([&](int r, int kk) {
+                            const int k = bin_of_channel_fold3(32 * w + r), n = 32 * s + kk;
+                            const double ph = two_pi * (double)((k * n) & 255) / 256.0;
+                            return n == 0 ? 0.f : (float)(part == 0 ? std::cos(ph) : -std::sin(ph));
+                        }, "a DFT"))
+                        return false;
+        if (sb.blocks() != (uint32_t)(NWAVES * DFT_X3_BLOCKS)) {
+            err = "Failed to load model: the DFT's split blocks do not match DFT_X3_BLOCKS";
+            return false;
+        }
+    }
+    out.data_d = std::move(sb.data);
     return true;
 }
 

@@ -21,6 +21,9 @@ struct PackedWeights {
     // the fourth block range (vad_layout.h, ENC23_X3_BLOCKS): encoder.2 and encoder.3 on the bf16 split, uploaded behind data_y in
     // the same buffer; filled by pack_silero_v5_t16 only
     std::vector<float> data_z;
+    // the fifth block range (vad_layout.h, DFT_X3_BLOCKS): the STFT's odd-bin tile on the bf16 split, uploaded behind data_z in the
+    // same buffer; filled by pack_silero_v5_t16 for the 16 kHz model only
+    std::vector<float> data_d;
     int32_t variant = 0;             // V4: 1 = the graph's 8 kHz sub-model (two time steps reach the LSTMs)
 };
 

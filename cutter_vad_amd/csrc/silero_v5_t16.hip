@@ -7,9 +7,10 @@
 // streams, so the same batch spreads over twice as many CUs and every MFMA / VALU phase is half as long.
 // The LSTM's two halves and the four encoder layers run on v_mfma_f32_16x16x32_bf16 instead, with weights and activations as exact
 // three-piece bf16 splits (X3_HALF, X3_CONV below; vad_layout.h S_LSTM_X3, S_ENC0_X3, S_ENC1_X3, ENC23_X3_BLOCKS); the encoders as
-// direct convolutions, not the Toom-3 product of silero_v5.hip, enc2 over its whole K in one wave, not split-K - the STFT alone is
-// fp32.  An activation that feeds such a layer is cut into its pieces ONCE, by the lane that produces it, and lies in LDS as the
-// consumers' B fragments ("activation planes", at QSD below).
+// direct convolutions, not the Toom-3 product of silero_v5.hip, enc2 over its whole K in one wave, not split-K - and so does the
+// odd-bin tile of the 16 kHz model's STFT (DFT_X3_BLOCKS); its even-bin tile and the 8 kHz sub-model's STFT alone are fp32.  An
+// activation that feeds such a layer is cut into its pieces ONCE, by the lane that produces it, and lies in LDS as the consumers'
+// B fragments ("activation planes", at QSD below).
 // The engine runs it for every one-frame call and for multi-frame calls of at most T16_MAX_STREAMS streams (engine.cpp: launch()).
 //
 // Fragment convention (v_mfma_f32_16x16x4_f32, D = A[16 x 4] B[4 x 16] + C): lane l = (n = l & 15, kq = l >> 4).
@@ -79,7 +80,7 @@ using namespace vadk::dev;
 namespace {
 
 constexpr int MT16 = 16;
-constexpr int QSL = 17;                   // loader view: rows 64 c + .. of the folded operands (po 0.. | qo 16.. | pe+ 32.. | pe- 40.. | qe- 48.. | qe+ 56..), 192 rows
+constexpr int QSL = 17;                   // loader view (padded stride): the transposed stores of the fold - 16 kHz: the even tile's operands (T_EVEN_Q below), 8 kHz: all four
 constexpr int QSD = 16;                   // dense view of the same memory, used by everything else:
 //   rows 0..143 the |STFT| columns as activation planes (below; 48 c + 12 s + 4 p + kq; 8 kHz: 24 c + ..; the Nyquist channel is in
 //   nyqv); rows 0..47 later enc1's output as planes (24 c + 12 s + ..: the four K-steps of enc2), then the LSTM input as planes; rows
@@ -91,7 +92,7 @@ constexpr int QSD = 16;                   // dense view of the same memory, used
 // waves that consume it, no VALU work (before: every wave cut every activation it read, 11 instructions per pair of values).
 // Live ranges: the h planes are read in the recurrent half only (barrier (0) .. (1)) and written by the prologue and by the cell
 // behind barrier (7), so they may lie under enc0's output (written behind (2), last read before (4)), in every instantiation (the
-// rejected-frame hold keeps h_{t-1} in registers), and lie past the loader view (238 rows, live (0) .. (1b)); the |STFT| planes are
+// rejected-frame hold keeps h_{t-1} in registers), and lie past the folded operands (T_ROWS_DFT, T_EVEN_Q below, live (0) .. (1b)); the |STFT| planes are
 // written behind (1b) and read until (3); enc1's planes are written behind (3) and read until (5), enc2's planes behind (4)
 // until (6); the x planes are written behind (5), when enc1's planes and the |STFT| planes are dead, and read until (7).
 constexpr int T_ROW_E0 = 144;
@@ -105,8 +106,28 @@ static_assert(T_ROW_E0 + 144 <= T_ROWS && T_ROW_E + 32 <= T_ROWS, "enc0's output
 static_assert(T_ROWS_E1 <= T_ROW_E0, "enc1's planes are written while other waves still read enc0's output");
 static_assert(T_ROW_E >= T_ROWS_E1 && T_ROW_E >= 48, "enc2's planes are written while enc1's are read, and read while the x planes are written");
 static_assert(T_ROW_E >= T_ROW_E0 && T_ROW_E + T_ROWS_E2 <= T_ROW_H, "enc2's planes lie in enc0's dead output and stay clear of h");
-constexpr int T_FOLD_SINK = 192;          // loader view: 32 rows behind the three columns, where the loader lanes q >= 8 drop their duplicate quads
-static_assert(T_ROW_H * QSD >= (T_FOLD_SINK + 32) * QSL, "the loader view (and its sink rows) must end before h");
+// The folded STFT operands, live (0) .. (1b).  8 kHz sub-model: the loader view from row 0 on (96 rows).  16 kHz model: the odd tile
+// runs on the bf16 split (vad_layout.h, DFT_X3_BLOCKS), so the loader cuts po | qo into planes, DENSE view: column c = rows 48 c ..
+// 48 c + 47 = four plane groups 2 part + s (part 0 po, 1 qo; K-step s = the folded samples n = 32 s .. 32 s + 31), where the |STFT|
+// planes of the same column follow them behind (1b).  Inside a row of such a group the stream is XOR-swizzled, stream n of lane
+// (n, kq)'s fragment of K-step s at quad n ^ (kq | 4 s): the 16 loader lanes of a stream hold the 8 (kq, s) x 2 halves of ONE stream
+// and would otherwise write 8 bytes each into the same 16-byte column of banks (an 8-way conflict of ds_write_b64's 16-lane
+// groups); swizzled they cover all 32 banks, and a reader's 16-lane groups of ds_read_b128 (kq pairs 0 | 1 and 2 | 3 on
+// complementary streams) still cover a whole row each.  The even tile's operands stay fp32 in the LOADER view behind the planes:
+// T_EVEN_ROWS rows of QSL quads from quad T_EVEN_Q on, column c: pe+ 32 c + q', qe- 32 c + 8 + q', pe- 32 c + 16 + q', qe+ 32 c + 24 + q'
+// (q' = 0..7, n = 4 q' .. 4 q' + 3; slot n = 0 of pe+ holds pe[32], of qe+ qe[32]).
+constexpr int T_ROWS_DFT = 144;           // dense rows of the po | qo planes
+constexpr int T_EVEN_Q = T_ROWS_DFT * QSD;
+constexpr int T_EVEN_ROWS = 96;
+static_assert(T_ROWS_DFT == 3 * 4 * 12, "three columns of four plane groups");
+static_assert(T_EVEN_Q + T_EVEN_ROWS * QSL <= T_ROW_H * QSD, "the planes and the even operands behind them must end before h");
+// The loader view proper - rows of QSL quads from row 0 on: the 8 kHz sub-model's folded operands (96 rows) and the resampler's
+// staging (128 rows) - ends at this row.  (The name is from the layout in which the 16 kHz fold dropped duplicate quads into 32 sink
+// rows from here on; the fold has none any more, and tests/test_act_planes_pack.py still holds the 32 rows behind it clear of h.)
+constexpr int T_FOLD_SINK = 192;
+static_assert(96 <= T_FOLD_SINK && T_FOLD_SINK * QSL <= T_ROW_H * QSD, "the 8 kHz sub-model's loader view must end before h");
+static_assert(T_ROWS_DFT <= T_ROW_E0 && T_EVEN_Q >= T_ROW_E0 * QSD,
+              "the magnitudes (rows 0..143, behind (1b)) take the planes' place; enc0's output (behind (2)) starts where the even operands did");
 constexpr int T_LDS_F4 = T_ROWS * QSD + 16 + 12 + 36 + 16 + 96 + 128;   // + head partials [4][16], |X128| [3][16], fold corrections [3][3][16], sink [64], state machines [16] x 96 B, gate biases [4 waves][4 gates][32 units]
 constexpr int T_LSTM_BIAS_BLOCK = 8 + 64 + 64 + 2;   // block of a wave's LSTM section that holds its gate biases compact: floats [gate][unit]
 static_assert(T_LDS_F4 * 16 <= 80 * 1024, "stays under half a CU's LDS");
@@ -123,7 +144,7 @@ static_assert((T_LDS_F4 + T_FLAG_F4) * 16 <= 80 * 1024, "the flags stay under ha
 constexpr int FQ = 129;
 constexpr int RS_CH_ROWS = 16;
 constexpr int RS_BUF = 4 * RS_CH_ROWS * QSL;
-static_assert(2 * RS_BUF <= 192 * QSL, "resampler staging must fit the loader view");
+static_assert(2 * RS_BUF <= T_FOLD_SINK * QSL, "resampler staging must fit the loader view");
 static_assert((T_LDS_F4 + MT16 * FQ) * 16 <= 160 * 1024, "RS: common layout + F must fit one CU");
 
 __device__ __forceinline__ f32x4 mfma16(f32x4 w, f32x4 a, f32x4 acc) {

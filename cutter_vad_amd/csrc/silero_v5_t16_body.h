@@ -27,6 +27,7 @@
     f32x4 *const ldsH = PAIR ? lds + hf * LDS_HALF : lds;     // the tile's LDS (PAIR: its half of the workgroup's)
     [[maybe_unused]] f32x4 *const ldsO = PAIR ? lds + (1 - hf) * LDS_HALF : lds;
     f32x4 *const RX = ldsH;
+    [[maybe_unused]] f32x4 *const REV = ldsH + T_EVEN_Q;   // 16 kHz: the even tile's folded operands, loader view
     f32x4 *const RE = ldsH + T_ROW_E * QSD;
     f32x4 *const RP0 = ldsH + T_ROW_E0 * QSD;
     f32x4 *const RH = ldsH + T_ROW_H * QSD;
@@ -271,6 +272,13 @@
     // three bf16 pieces of the tile's A fragment (3 blocks).  They stream through a ring of X3_NR units, requested X3_D units ahead.
     // encoder.0 streams its own through the same ring (S_ENC0_X3, X3_CONV).
     f32x4 xw[X3_NR][3];
+    // 16 kHz: the ring runs on from the recurrent half through the STFT's odd tile (vad_layout.h, DFT_X3_BLOCKS: four units, in the third
+    // stream's buffer) into encoder.0, whose unit 0 sits in slot 0: the recurrent half's NH units start at XU_H with XU_H + NH + 4 = 0
+    // (mod X3_NR), the DFT's unit v has slot XU_D + v
+    constexpr int NH = PAIR ? 16 : 32, XU_H = K8 ? 0 : (2 * X3_NR - (NH + 4) % X3_NR) % X3_NR, XU_D = XU_H + NH;
+    static_assert(K8 || (XU_D + 4) % X3_NR == 0, "encoder.0's units follow the DFT's in the ring");
+    [[maybe_unused]] const int o_d = 4 * ENC1_X3_BLOCKS + 4 * ENC23_X3_BLOCKS + w * DFT_X3_BLOCKS;
+#define X3_LDD(v, slot) X3_LDY(o_d + 3 * (v), slot)
 #define X3_LDR(blk, slot) _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_) xw[(slot) % X3_NR][p_] = WL((blk) + p_);
     // (U0: the ring slot of the half's unit 0 - 0 for the recurrent half, behind enc3's units for the input half)
 #define X3_LD(B, u, U0) X3_LDR((B) + 3 * (u), (U0) + (u))
@@ -286,7 +294,7 @@
     }
 #define H_FIRST(L, tt, WITHX)                                                                                   \
     {                                                                                                           \
-        _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LDU((L) + LSTM_X3_HALF_BLOCKS, u_, 0) }         \
+        _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LDU((L) + LSTM_X3_HALF_BLOCKS, u_, XU_H) }         \
         if constexpr (WITHX) H_FIRSTX(tt)                                                                       \
         SB();                                                                                                   \
         if constexpr (RS) { X_ISSUE(2, xc_, tt) SB(); }                                                         \
@@ -722,6 +730,13 @@
             auto shl8 = [](float v) -> float {        // row_shl:8: lane q gets lane q + 8 (lanes 8..15: zero)
                 return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x108, 0xf, 0xf, true));
             };
+            // row_ror:8 with bank mask 0xc: lanes 8..15 of a row get lane q - 8's `hi`, lanes 0..7 keep their own `lo`
+            [[maybe_unused]] auto ror8hi = [](float lo, float hi) -> float {
+                return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, lo), __builtin_bit_cast(int, hi), 0x128, 0xf, 0xc, false));
+            };
+            // 16 kHz: where the lane's halves of po's fragments go inside a column's plane groups (K-step q >> 3, kq = q & 3, the
+            // stream swizzled: silero_v5_t16.hip, T_ROWS_DFT)
+            [[maybe_unused]] const int fold_og = (12 * (q >> 3) + (q & 3)) * QSD + (lms ^ ((q & 3) | ((q >> 3) << 2)));
             // the fold of silero_v5.hip, one call per column: stream ms = tid >> 4, n = 4 q + j
 #define X_FOLD(c, XR, NEXT)                                                                                     \
     {                                                                                                           \
@@ -753,22 +768,25 @@
             st2(&RX[(CS * (c) + 2 * QL + q) * QSL + ms], qe);                                                   \
             st2(&RX[(CS * (c) + 3 * QL + q) * QSL + ms], qo);                                                   \
         } else {                                                                                                \
-        /* the odd bins contract po | qo as they are; the even bins' operands fold once more, about n = 32 (vad_layout.h,            \
-           bin_of_channel_fold3; silero_v5.hip has the lane algebra).  Lanes q < 8 hold n = 0..31 and store; lanes q >= 8 hold the \
-           same values again and drop them into sink rows (a select on the address, no branch: the fold stays in the MFMAs' basic \
-           block).  Slot n = 0 carries the unpaired n = 32 (lane 8, component 0): pe[32] | qe[32] */                  \
+        /* the odd bins contract po | qo on the bf16 split: the lane cuts its two quads - half (q >> 2) & 1 of lane (ms, kq = q & 3)'s \
+           fragments of K-step q >> 3 - into the column's plane groups (silero_v5_t16.hip, T_ROWS_DFT).  The even bins' operands fold   \
+           once more, about n = 32 (vad_layout.h, bin_of_channel_fold3; silero_v5.hip has the lane algebra): lanes q < 8 hold n =      \
+           0..31, lanes q >= 8 the same values again - so lane q < 8 stores pe+ and pe-, lane q + 8 fetches that lane's qe- and qe+     \
+           (row_ror:8 into lanes 8..15 only, the other lanes keep pe+-: the select rides in the DPP's bank mask) and stores those,       \
+           rows q and 16 + q of the column for every lane: no sink rows, no branch, half the stores.  Slot n = 0 carries the unpaired \
+           n = 32 (lane 8, component 0): pe[32] | qe[32] */                                                    \
         const f32x4 pm = f32x4{shr1(0.f, mirror(pe.x)), mirror(pe.w), mirror(pe.z), mirror(pe.y)};               \
         const f32x4 qm = f32x4{shr1(0.f, mirror(qe.x)), mirror(qe.w), mirror(qe.z), mirror(qe.y)};               \
         f32x4 pep = pk::add(pe, pm), pen = pk::sub(pe, pm), qen = pk::sub(qe, qm), qep = pk::add(qe, qm);       \
         const float pe32 = shl8(pe.x), qe32 = shl8(qe.x);                                                       \
         pep.x = q0 ? pe32 : pep.x; pen.x = q0 ? 0.f : pen.x; qen.x = q0 ? 0.f : qen.x; qep.x = q0 ? qe32 : qep.x;   \
-        st2(&RX[(64 * (c) + q) * QSL + ms], po);                                                               \
-        st2(&RX[(64 * (c) + 16 + q) * QSL + ms], qo);                                                          \
-        const int er = (q < 8 ? 64 * (c) + 32 + q : T_FOLD_SINK - 8 + q) * QSL + ms;                            \
-        st2(&RX[er], pep);                                                                                      \
-        st2(&RX[er + 8 * QSL], pen);                                                                            \
-        st2(&RX[er + 16 * QSL], qen);                                                                           \
-        st2(&RX[er + 24 * QSL], qep);                                                                           \
+        f32x4 *const og = RX + (PP * (c)) * QSD + fold_og;                                                      \
+        st_planes_half(og, (q >> 2) & 1, po);                                                                   \
+        st_planes_half(og + 24 * QSD, (q >> 2) & 1, qo);                                                        \
+        const f32x4 eA = f32x4{ror8hi(pep.x, qen.x), ror8hi(pep.y, qen.y), ror8hi(pep.z, qen.z), ror8hi(pep.w, qen.w)};   \
+        const f32x4 eB = f32x4{ror8hi(pen.x, qep.x), ror8hi(pen.y, qep.y), ror8hi(pen.z, qep.z), ror8hi(pen.w, qep.w)};   \
+        st2(&REV[(32 * (c) + q) * QSL + ms], eA);                                                               \
+        st2(&REV[(32 * (c) + 16 + q) * QSL + ms], eB);                                                          \
         }                                                                                                       \
     }
 #define H_MIX                                                                                                   \
@@ -793,6 +811,7 @@
             // 4 K-steps x 8 tiles on the bf16 split (X3_HALF); the frame's columns are folded in the shadow of the last three units
             // of K-steps 1, 2, 3 (8 kHz: two fold calls, columns (0 | 1) by half of the workgroup, then column 2, in K-steps 1, 2)
 #define H_EXTRA(u)                                                                                              \
+            if constexpr (!K8 && (u) + X3_D >= 32) { X3_LDD((u) + X3_D - 32, XU_H + (u) + X3_D) }                \
             if constexpr ((u) == 2 && !RS && !K8) { X_ISSUE(2, xc_, t) }                                        \
             if constexpr ((u) == 15) { if constexpr (K8) { X_FOLD(lcol, xa_, 0) } else { X_FOLD(0, xa_, 0) } H_MIX }   \
             if constexpr ((u) == 23) { if constexpr (K8) { X_FOLD(2, xb_, 1) X_FLAG } else { X_FOLD(1, xb_, 1) } H_MIX }   \
@@ -805,15 +824,16 @@
         __builtin_amdgcn_sched_group_barrier(0x002, 28, 0);                                                     \
     }
 #define HP_EXTRA(v)                                                                                             \
+            if constexpr ((v) + X3_D >= 16) { X3_LDD((v) + X3_D - 16, XU_H + (v) + X3_D) }                      \
             if constexpr ((v) == 1) { X_ISSUE(2, xc_, t) }                                                      \
             if constexpr ((v) == 7) { X_FOLD(0, xa_, 0) HP_MIX }                                                \
             if constexpr ((v) == 11) { X_FOLD(1, xb_, 1) HP_MIX }                                               \
             if constexpr ((v) == 15) { X_FOLD(2, xc_, 2) X_FLAG HP_MIX }
 #define HP_FOLDREGION(v) (((v) & 3) >= 2 && (v) >= 4)
             if constexpr (PAIR) {
-                X3P_HALF(0, wh, RH, (ldsO + T_ROW_H * QSD), HP_EXTRA, HP_FOLDREGION)
+                X3P_HALF(XU_H, wh, RH, (ldsO + T_ROW_H * QSD), HP_EXTRA, HP_FOLDREGION)
             } else {
-            X3_HALF(0, wh, RH, H_EXTRA, H_FOLDREGION)
+            X3_HALF(XU_H, wh, RH, H_EXTRA, H_FOLDREGION)
             }
 #undef HP_EXTRA
 #undef HP_FOLDREGION
@@ -824,9 +844,9 @@
 #undef X_FOLD
 #undef X_FLAG
         }
-        f32x4 Sw[2];                              // STFT blocks of k-iteration 0: cos, -sin of the odd tile
+        f32x4 Sw[2];                              // the STFT's first fp32 blocks, cos and -sin: 8 kHz k-iteration 0, 16 kHz the even tile's first
 #pragma unroll
-        for (int k = 0; k < 2; ++k) Sw[k] = WL(ws_stft + k);
+        for (int k = 0; k < 2; ++k) Sw[k] = WL(ws_stft + (K8 ? 0 : 8) + k);
         SB();
         STAMP(1);
         __syncthreads();   // (1) folded x visible
@@ -841,7 +861,7 @@
 #pragma unroll
                 // 16 kHz: sum_n pe[n] (-1)^n = the same sum over the pe+ rows (slot 0 = pe[32], sign +); 8 kHz: over its 8 pe rows
                 for (int i = 0; i < 2; ++i) {
-                    const f32x4 pp = RX[(CS * c + (K8 ? 0 : 32) + pt * 2 + i) * QSL + ms];
+                    const f32x4 pp = K8 ? RX[(CS * c + pt * 2 + i) * QSL + ms] : REV[(32 * c + pt * 2 + i) * QSL + ms];
                     a += (pp.x - pp.y) + (pp.z - pp.w);
                 }
             }
@@ -850,20 +870,15 @@
             if (pair < 48 && pt == 0) nyqv[c * 16 + ms] = fabsf(a + fcor[(c * 3 + 0) * 16 + ms] + fcor[(c * 3 + 1) * 16 + ms]);
         }
 
-        // enc0's fp32 blocks (bias, Nyquist taps) and its first X3_D units, requested before barrier (1b)
+        // enc0's fp32 blocks (bias, Nyquist taps) and its first X3_D units, requested before barrier (1b): 8 kHz in one block behind
+        // the STFT (E0_FIRST), 16 kHz by the DFT's ring units, one each, and the fp32 blocks behind them
         f32x4 e0f[ENC0_X3_F32_BLOCKS];
     // PAIR: the wave's row tile is hf - its bias in e0f[0], its three Nyquist taps in e0f[1 ..]; unit v = (K-step, tap) = the stream's
     // unit 2 v + hf
 #define E0P_BLK(v) (ws_x0 + ENC0_X3_F32_BLOCKS + 3 * (2 * (v) + hf))
 #define E0_FIRST                                                                                                \
-    if constexpr (PAIR) {                                                                                       \
-        e0f[0] = WX(ws_x0 + hf);                                                                                \
-        _Pragma("unroll") for (int k = 0; k < 3; ++k) e0f[1 + k] = WX(ws_x0 + 2 + 2 * k + hf);                  \
-        _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LDX(E0P_BLK(u_), u_) }                         \
-    } else {                                                                                                    \
     _Pragma("unroll") for (int k = 0; k < ENC0_X3_F32_BLOCKS; ++k) e0f[k] = WX(ws_x0 + k);                      \
-    _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LDX(ws_x0 + ENC0_X3_F32_BLOCKS + 3 * u_, u_) }     \
-    }
+    _Pragma("unroll") for (int u_ = 0; u_ < X3_D; ++u_) { X3_LDX(ws_x0 + ENC0_X3_F32_BLOCKS + 3 * u_, u_) }
         if constexpr (K8) {
             // ---- STFT, 8 kHz sub-model: 64 complex bins = four 16-row tiles, ONE per wave (pack_dft4_wave_128_t16): wave w owns the
             //      bins 2 (16 (w & 1) + r) + (w >> 1), r = 0..15 - waves 0 / 1 the even bins (pe | qe), 2 / 3 the odd ones (po | qo);
@@ -907,9 +922,10 @@
                 for (int c = 0; c < 3; ++c) st_planes_half(o + PP * c * QSD, w & 1, pk::mag(sre[c], sim[c]));
             }
         } else
-        // ---- STFT: wave w owns bins bin_of_channel_fold3(32 w + 16 rt + r): row tile 0 = 16 odd bins, cos on po, -sin on qo, K = 64
-        //      (k-iterations 0..3); row tile 1 = 16 even bins on the once-more-folded operands pe+- | qe-+ (waves 2, 3 | 0, 1), K = 32
-        //      (k-iterations 4, 5); 3 columns.  144 MFMAs per wave instead of 192 ----
+        // ---- STFT: wave w owns bins bin_of_channel_fold3(32 w + 16 rt + r).  Row tile 0 = 16 odd bins, cos on po, -sin on qo, K = 64, on
+        //      the bf16 split: four ring units (part, K-step s) = 2 part + s of vad_layout.h's DFT_X3_BLOCKS, each feeding the three
+        //      columns' plane groups (72 bf16 MFMAs where the fp32 form had 96 of twice the length).  Row tile 1 = 16 even bins on the
+        //      once-more-folded operands pe+- | qe-+ (waves 2, 3 | 0, 1), K = 32: two fp32 k-iterations, 48 MFMAs ----
         {
             f32x4 are[3][2], aim[3][2];
 #pragma unroll
@@ -923,18 +939,57 @@
                 are[c][1] = f32x4{re1, re1, re1, re1};
                 aim[c][1] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
-            const int eR = w < 2 ? 40 : 32, eI = w < 2 ? 56 : 48;
-            const f32x4 *const XB = RX + nqL;                                                   // loader view
-#define S_ROW_R(t) ((t) < 4 ? 4 * (t) : eR + 4 * ((t) - 4))
-#define S_ROW_I(t) ((t) < 4 ? 16 + 4 * (t) : eI + 4 * ((t) - 4))
+            // the odd tile.  Piece p of the lane's fragment of plane group g of column c (the stream swizzled as the loader wrote it);
+            // a column's pieces of unit v + 1 are read behind its MFMAs of unit v.  Every unit requests the encoder.0 unit X3_D units
+            // behind it in the ring.
+            const int nqs[2] = {kq * QSD + (n ^ kq), kq * QSD + (n ^ (kq | 4))};
+#define D_RD(c, g, p) __builtin_bit_cast(u32x4, RX[(PP * (c) + 12 * (g) + 4 * (p)) * QSD + nqs[(g) & 1]])
+            const int eR = w < 2 ? 16 : 0, eI = w < 2 ? 24 : 8;
+            const f32x4 *const XB = REV + nqL;                                                  // loader view
             f32x4 Aw[2], Bw[2], Au[3], Av[3], Bu[3], Bv[3];
+            {
+                u32x4 F_[3][3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+#pragma unroll
+                    for (int p_ = 0; p_ < 3; ++p_) F_[c][p_] = D_RD(c, 0, p_);
+                SB();
+                x3_units([&](auto uc_) {
+                    constexpr int v_ = decltype(uc_)::value;
+                    if constexpr (PAIR) { X3_LDX(E0P_BLK(v_), v_) } else { X3_LDX(ws_x0 + ENC0_X3_F32_BLOCKS + 3 * v_, v_) }
+                    if constexpr (v_ == 3) {              // the even tile's first operands (its first blocks: Sw)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) { Au[c] = XB[(32 * c + eR) * QSL]; Av[c] = XB[(32 * c + eI) * QSL]; }
+                    }
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        if constexpr (v_ < 2) are[c][0] = mfma_x3(xw[(XU_D + v_) % X3_NR], F_[c], are[c][0]);
+                        else aim[c][0] = mfma_x3(xw[(XU_D + v_) % X3_NR], F_[c], aim[c][0]);
+                        if constexpr (v_ + 1 < 4) {
+#pragma unroll
+                            for (int p_ = 0; p_ < 3; ++p_) F_[c][p_] = D_RD(c, v_ + 1, p_);
+                        }
+                    }
+                    SB();
+                }, std::make_integer_sequence<int, 4>{});
+            }
+#undef D_RD
+            // encoder.0's fp32 blocks (bias, Nyquist taps), behind its first units
+            if constexpr (PAIR) {
+                e0f[0] = WX(ws_x0 + hf);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) e0f[1 + k] = WX(ws_x0 + 2 + 2 * k + hf);
+            } else {
+#pragma unroll
+                for (int k = 0; k < ENC0_X3_F32_BLOCKS; ++k) e0f[k] = WX(ws_x0 + k);
+            }
+            SB();
+            // the even tile: k-iterations 4, 5 of S_STFT
 #pragma unroll
             for (int k = 0; k < 2; ++k) Aw[k] = Sw[k];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { Au[c] = XB[(64 * c + S_ROW_R(0)) * QSL]; Av[c] = XB[(64 * c + S_ROW_I(0)) * QSL]; }
 #define S_LD(S, tt)                                                                        \
     _Pragma("unroll") for (int k = 0; k < 2; ++k) S##w[k] = WL(ws_stft + 2 * (tt) + k);    \
-    _Pragma("unroll") for (int c = 0; c < 3; ++c) { S##u[c] = XB[(64 * c + S_ROW_R(tt)) * QSL]; S##v[c] = XB[(64 * c + S_ROW_I(tt)) * QSL]; }
+    _Pragma("unroll") for (int c = 0; c < 3; ++c) { S##u[c] = XB[(32 * c + eR + 4 * ((tt) - 4)) * QSL]; S##v[c] = XB[(32 * c + eI + 4 * ((tt) - 4)) * QSL]; }
 #define S_MMA(S, rt)                                                                       \
     _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                       \
         _Pragma("unroll") for (int c = 0; c < 3; ++c) {                                    \
@@ -947,18 +1002,11 @@
         __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                                 \
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                 \
     }
-            S_LD(B, 1) S_MMA(A, 0) S_IL SB();
-            S_LD(A, 2) S_MMA(B, 0) S_IL SB();
-            S_LD(B, 3) S_MMA(A, 0) S_IL SB();
-            S_LD(A, 4) S_MMA(B, 0) S_IL SB();
             S_LD(B, 5) S_MMA(A, 1) S_IL SB();
             S_MMA(B, 1) SB();
 #undef S_IL
 #undef S_LD
 #undef S_MMA
-#undef S_ROW_R
-#undef S_ROW_I
-            E0_FIRST
             SB();
             __syncthreads();   // (1b) every wave is done reading the folded operands: the magnitudes may overwrite them
             // |.| of the three columns -> planes: the wave's two row tiles are K-step w's fragments, plane group 48 c + 12 w
@@ -1268,6 +1316,7 @@
 #undef X3_LD
 #undef X3_LDR
 #undef X3_LDX
+#undef X3_LDD
 #undef X3_LDY
 #undef WY
 #undef WX

@@ -88,6 +88,15 @@ constexpr int ENC1_X3_BLOCKS = ENC1_X3_F32_BLOCKS + 3 * 4 * 3;
 constexpr int ENC2_X3_BLOCKS = 1 + 4 * 3;
 constexpr int ENC3_X3_BLOCKS = 2 + 4 * 3;
 constexpr int ENC23_X3_BLOCKS = ENC2_X3_BLOCKS + ENC3_X3_BLOCKS;
+// The FIFTH block range (16-stream kernel, 16 kHz model only; PackedWeights::data_d): the odd-bin row tile of the STFT on the bf16
+// split.  Like the fourth it has no sect entry and no field of StepParams: the engine uploads it behind the fourth, in the third
+// stream's allocation, and wave w finds its DFT_X3_BLOCKS blocks at block 4 * ENC1_X3_BLOCKS + 4 * ENC23_X3_BLOCKS + w * DFT_X3_BLOCKS
+// of that buffer.  S_STFT stays whole in the first stream; its odd-tile blocks (k-iterations 0..3) are no longer read by this kernel.
+//   Wave w = the 16 odd bins bin_of_channel_fold3(32 w + r): four units of three blocks, unit 2 part + s - part 0 the cos rows
+//   (contracted with po), part 1 the -sin rows (with qo), K-step s = the folded samples n = 32 s .. 32 s + 31 - each the tile's A
+//   fragment as in S_LSTM_X3 (lane (row l & 15, kq), element e = n 32 s + 16 (e >> 2) + 4 kq + (e & 3)), the very fp32 table values of
+//   S_STFT cut into three exact pieces; n = 0 is the zero slot it is there (the loader writes 0 into po[0] and qo[0]).
+constexpr int DFT_X3_BLOCKS = 4 * 3;
 __host__ __device__ constexpr int bin_of_channel(int ch) {
     return (ch >> 5) < 2 ? 64 * (ch >> 5) + 2 * (ch & 31) : 64 * ((ch >> 5) - 2) + 2 * (ch & 31) + 1;
 }

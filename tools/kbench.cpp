@@ -96,6 +96,7 @@ int main(int argc, char **argv) {
     }
     if (!pw.data_y.empty()) {        // the third stream (the 16-stream V5 packing's split encoder.1), the split enc2 / enc3 behind it
         pw.data_y.insert(pw.data_y.end(), pw.data_z.begin(), pw.data_z.end());
+        pw.data_y.insert(pw.data_y.end(), pw.data_d.begin(), pw.data_d.end());      // and the split DFT behind those
         float *d_wy;
         CK(hipMalloc(&d_wy, pw.data_y.size() * 4));
         CK(hipMemcpy(d_wy, pw.data_y.data(), pw.data_y.size() * 4, hipMemcpyHostToDevice));
