@@ -124,6 +124,7 @@ class ScanChItem(C.Structure):
 
 
 VAD_SCAN_MIX = -1
+VAD_SCAN_BOTH = -2     # vad_scan_cut_stereo / vad_scan_render_stereo: both channels are written
 
 
 class CutItem(C.Structure):
@@ -284,6 +285,14 @@ SIGNATURES = {
                                   C.c_int32, C.c_float, C.c_int32, _vp, C.c_int64]),
     "vad_scan_render_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int,
                                          C.c_int32, C.c_int32, C.c_float, C.c_int32, _vp, C.c_int64, _vp]),
+    "vad_scan_cut_stereo": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32,
+                                      C.c_float, C.c_int32, C.c_int32, _vp, C.c_int64]),
+    "vad_scan_cut_stereo_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32,
+                                             C.c_int32, C.c_float, C.c_int32, C.c_int32, _vp, C.c_int64, _vp]),
+    "vad_scan_render_stereo": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int,
+                                         C.c_int32, C.c_int32, C.c_float, C.c_int32, _vp, C.c_int64]),
+    "vad_scan_render_stereo_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32,
+                                                C.c_int, C.c_int32, C.c_int32, C.c_float, C.c_int32, _vp, C.c_int64, _vp]),
 }
 
 _lib = None

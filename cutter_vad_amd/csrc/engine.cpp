@@ -46,6 +46,8 @@ extern "C" hipError_t vadk_launch_scan_cut(const vadk::CutArgs *a, hipStream_t s
 extern "C" hipError_t vadk_launch_scan_cut_gain(const vadk::CutArgs *a, const float *gains, hipStream_t stream);
 extern "C" hipError_t vadk_launch_seg_levels(const vadk::CutArgs *a, float clip, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_render(const vadk::RenderArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_scan_cut_stereo(const vadk::CutArgs *a, const float *gains, hipStream_t stream);
+extern "C" hipError_t vadk_launch_scan_render_stereo(const vadk::RenderArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_segments(const vadk::SegArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_seg_stats(const vadk::SegArgs *a, uint32_t most, hipStream_t stream);
 extern "C" hipError_t vadk_launch_reseg_count(const vadk::ResegArgs *a, hipStream_t stream);
@@ -1702,11 +1704,14 @@ struct CutPlan {
     // vad_scan_render: the output ranges of two segments may overlap (three may not), every output sample is written, and a
     // sample is faded by `ramp` (host, nramp entries) from both ends of its segment; layout is the range once
     bool render; const float *ramp; int32_t nramp;
+    // vad_scan_cut_stereo / vad_scan_render_stereo: both channels of a two-channel block, interleaved.  Positions and counts stay
+    // sample FRAMES, so the tables are the mono call's: an output frame has twice the bytes (ob), and the launcher is another
+    bool stereo;
     // a. cut_check
     bool rate, rate_frames;
     uint32_t fshift;                         // log2 of the quads of a payload frame
     int64_t rows;                            // rate_frames: the frames of all segments
-    size_t ab, ob;                           // bytes of the block, and of one output sample
+    size_t ab, ob;                           // bytes of the block, and of one output sample (stereo: sample frame)
     std::vector<CutSpan> spans;              // by lo
     // b. cut_block_device / cut_block_host: the block the kernels read, and where they write
     const void *d_audio; void *d_out;
@@ -1741,8 +1746,14 @@ int cut_check(vad_engine *e, CutPlan &c) {
     if (n < 0 || audio_samples < 0 || c.out_samples < 0 || (n > 0 && !c.items))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer or bad count", who);
     if (int rc = check_block_format(e, who, c.fmt, c.channels)) return rc;
+    if (c.stereo && c.channels != 2)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: channels = %d: two-channel blocks only", who, c.channels);
     if (c.layout != VAD_CUT_FRAMES && c.layout != VAD_CUT_RANGE)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: layout = %d is neither VAD_CUT_FRAMES nor VAD_CUT_RANGE", who, c.layout);
+    // two resampled rows per chunk would have to pass vadk_cut_resample's window: not built
+    if (c.stereo && c.chunk > 0 && c.layout == VAD_CUT_FRAMES)
+        return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s: VAD_CUT_FRAMES on a block at %d Hz: both channels of resampled frames "
+                       "are not supported, VAD_CUT_RANGE is", who, c.sr_in);
     if (c.out_fmt != VAD_CUT_PCM16 && c.out_fmt != VAD_CUT_F32)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_fmt = %d is neither VAD_CUT_PCM16 nor VAD_CUT_F32", who, c.out_fmt);
     if (int rc = check_block_extent(e, who, c.hop, audio_samples, c.channels, c.fmt)) return rc;
@@ -1751,7 +1762,7 @@ int cut_check(vad_engine *e, CutPlan &c) {
     if (c.render)
         if (int rc = render_check(e, c)) return rc;
     c.ab = (size_t)audio_samples * (size_t)c.channels * sample_bytes(c.fmt);
-    c.ob = c.out_fmt == VAD_CUT_PCM16 ? 2 : 4;
+    c.ob = (size_t)(c.out_fmt == VAD_CUT_PCM16 ? 2 : 4) * (c.stereo ? 2 : 1);
     if (n == 0) return VAD_OK;
     c.rate = c.chunk > 0;
     c.rate_frames = c.rate && c.layout == VAD_CUT_FRAMES;
@@ -1779,7 +1790,10 @@ int cut_check(vad_engine *e, CutPlan &c) {
             it.sample_offset + (it.first_frame + it.nframes - 1) * hop + frame > audio_samples)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld (recording at %lld, frames %lld .. +%lld) leaves the audio block of %lld samples",
                            who, (long long)i, (long long)it.sample_offset, (long long)it.first_frame, (long long)it.nframes, (long long)audio_samples);
-        if (it.channel != VAD_SCAN_MIX && (it.channel < 0 || it.channel >= c.channels))
+        if (c.stereo && it.channel != VAD_SCAN_BOTH)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld names channel %d: both channels are written, "
+                           "an item's channel is VAD_SCAN_BOTH", who, (long long)i, it.channel);
+        if (!c.stereo && it.channel != VAD_SCAN_MIX && (it.channel < 0 || it.channel >= c.channels))
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld names channel %d of %d (0 .. channels - 1, or VAD_SCAN_MIX)", who,
                            (long long)i, it.channel, c.channels);
         if (it.reserved != 0)
@@ -1795,7 +1809,7 @@ int cut_check(vad_engine *e, CutPlan &c) {
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: its gain is %s, a gain is a finite number", who, (long long)i,
                            std::isnan(c.gains[i]) ? "NaN" : "infinite");
         c.spans[(size_t)i] = CutSpan{it.out_sample, it.out_sample + count, i};
-        const uint32_t mode = c.channels == 1 ? vadk::SCAN_LEFT : it.channel == VAD_SCAN_MIX ? vadk::SCAN_MIX : (uint32_t)it.channel;
+        const uint32_t mode = c.channels == 1 || c.stereo ? vadk::SCAN_LEFT : it.channel == VAD_SCAN_MIX ? vadk::SCAN_MIX : (uint32_t)it.channel;
         const uint32_t nq = (uint32_t)(count >> 2);
         e->cut_segs[(size_t)i] = vadk::CutSeg{(uint32_t)((it.sample_offset + it.first_frame * hop) >> 2) | (mode << vadk::SCAN_MODE_SHIFT), nq,
                                               c.levels ? 0u : (uint64_t)it.out_sample >> 2};
@@ -1958,7 +1972,9 @@ int cut_launches(vad_engine *e, const CutPlan &c, hipStream_t s) {
         return VAD_OK;
     }
     if (!c.rate_frames) {
-        const hipError_t r = c.gains ? vadk_launch_scan_cut_gain(&a, d_gains, s) : vadk_launch_scan_cut(&a, s);
+        const hipError_t r = c.stereo  ? vadk_launch_scan_cut_stereo(&a, c.gains ? d_gains : nullptr, s)
+                             : c.gains ? vadk_launch_scan_cut_gain(&a, d_gains, s)
+                                       : vadk_launch_scan_cut(&a, s);
         if (r != hipSuccess) return e->hip_fail(r, "kernel launch (scan cut)");
         return VAD_OK;
     }
@@ -2023,11 +2039,13 @@ int cut_copy_back(vad_engine *e, const CutPlan &c, void *out, hipStream_t s) {
 // vad_scan_levels (levels: `out` is n vad_level records, cleared on the stream ahead of the reducing kernel) ride the same phases.
 int cut_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples,
             int32_t channels, int fmt, int32_t hop, float thr, int32_t layout, int32_t out_fmt, void *out, int64_t out_samples, void *stream,
-            int chunk = 0, int32_t sr_in = 0, const float *gains = nullptr, bool with_gains = false, bool levels = false, float clip = 0.0f) {
+            int chunk = 0, int32_t sr_in = 0, const float *gains = nullptr, bool with_gains = false, bool levels = false, float clip = 0.0f,
+            bool stereo = false) {
     hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
     HIP_TRY(e, hipSetDevice(e->device));
     if (int rc = scan_wait(e)) return rc;
     CutPlan c{who, items, n, audio_samples, channels, fmt, hop, thr, layout, out_fmt, out_samples, chunk, sr_in, gains, levels, clip};
+    c.stereo = stereo;
     if (with_gains && n > 0 && !gains) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null gains", who);
     if (int rc = cut_check(e, c)) return rc;
     if (n == 0) return VAD_OK;
@@ -2097,11 +2115,12 @@ int render_regions(vad_engine *e, const CutPlan &c) {
 // memset per gap, and no second pass over the samples a memset of the whole output would cost).
 int render_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const float *gains, const float *ramp, int32_t nramp,
                const void *audio, int64_t audio_samples, int32_t channels, int fmt, int32_t sr_in, int chunk, int32_t hop, float thr, int32_t out_fmt,
-               void *out, int64_t out_samples, void *stream) {
+               void *out, int64_t out_samples, void *stream, bool stereo = false) {
     hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
     HIP_TRY(e, hipSetDevice(e->device));
     if (int rc = scan_wait(e)) return rc;
-    CutPlan c{who, items, n, audio_samples, channels, fmt, hop, thr, VAD_CUT_RANGE, out_fmt, out_samples, chunk, sr_in, gains, false, 0.0f, true, ramp, nramp};
+    CutPlan c{who, items, n, audio_samples, channels, fmt, hop, thr, VAD_CUT_RANGE, out_fmt, out_samples, chunk, sr_in, gains, false, 0.0f, true, ramp, nramp,
+              stereo};
     if (int rc = cut_check(e, c)) return rc;
     if (n == 0) e->cut_segs.clear();
     if (int rc = render_regions(e, c)) return rc;
@@ -2146,7 +2165,7 @@ int render_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *ite
     a.channels = channels;
     a.out_fmt = out_fmt;
     a.thresh = c.rate ? -1.0f : thr;             // no input-rate sample was ever gated
-    const hipError_t r = vadk_launch_scan_render(&a, s);
+    const hipError_t r = stereo ? vadk_launch_scan_render_stereo(&a, s) : vadk_launch_scan_render(&a, s);
     const int rc = r != hipSuccess ? e->hip_fail(r, "kernel launch (scan render)") : VAD_OK;
     if (dev) {
         // the launch reads the engine's tables: the next scan or cut waits for it, as behind vad_scan_device
@@ -2292,6 +2311,56 @@ int vad_scan_render_device(vad_engine *e, const vad_cut_item *items, int64_t n, 
     if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
     return render_run(e, true, who, items, n, gains, ramp, nramp, d_audio, audio_samples, channels, frame_fmt, chunk ? sr_in : 0, chunk, hop,
                       denoise_thresh, out_fmt, d_out, out_samples, stream);
+}
+
+// both channels of a two-channel block, interleaved (csrc/scan_cut_stereo.hip, csrc/scan_render_stereo.hip): the mono calls'
+// plans, tables and checks under these names, sample FRAMES where those count samples
+int vad_scan_cut_stereo(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const void *audio, int64_t audio_samples,
+                        int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt,
+                        void *out, int64_t out_samples) {
+    static const char *who = "vad_scan_cut_stereo";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int chunk = 0;
+    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
+    return cut_run(e, false, who, items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, out, out_samples, nullptr,
+                   chunk, chunk ? sr_in : 0, gains, false, false, 0.0f, true);
+}
+
+int vad_scan_cut_stereo_device(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const void *d_audio, int64_t audio_samples,
+                               int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt,
+                               void *d_out, int64_t out_samples, void *stream) {
+    static const char *who = "vad_scan_cut_stereo_device";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int chunk = 0;
+    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
+    return cut_run(e, true, who, items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, d_out, out_samples,
+                   stream, chunk, chunk ? sr_in : 0, gains, false, false, 0.0f, true);
+}
+
+int vad_scan_render_stereo(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const float *ramp, int32_t nramp,
+                           const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop,
+                           float denoise_thresh, int32_t out_fmt, void *out, int64_t out_samples) {
+    static const char *who = "vad_scan_render_stereo";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int chunk = 0;
+    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
+    return render_run(e, false, who, items, n, gains, ramp, nramp, audio, audio_samples, channels, frame_fmt, chunk ? sr_in : 0, chunk, hop,
+                      denoise_thresh, out_fmt, out, out_samples, nullptr, true);
+}
+
+int vad_scan_render_stereo_device(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const float *ramp, int32_t nramp,
+                                  const void *d_audio, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop,
+                                  float denoise_thresh, int32_t out_fmt, void *d_out, int64_t out_samples, void *stream) {
+    static const char *who = "vad_scan_render_stereo_device";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    int chunk = 0;
+    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
+    return render_run(e, true, who, items, n, gains, ramp, nramp, d_audio, audio_samples, channels, frame_fmt, chunk ? sr_in : 0, chunk, hop,
+                      denoise_thresh, out_fmt, d_out, out_samples, stream, true);
 }
 
 }  // extern "C"

@@ -890,6 +890,98 @@ class Engine:
                                                      int(channels), int(fmt), sr or 0, hop, thr, of, d_out or None, int(out_samples),
                                                      stream or None))
 
+    # ------------------------------------------------------------------ two-channel segment audio
+    def _stereo_items(self, segments, hop: int, layout: int, out_samples=None, rate: Optional[int] = None):
+        """``_cut_items`` for the stereo calls: a segment is (sample_offset, first_frame, nframes) - no channel, both are written -
+        and positions count sample frames"""
+        segs = [tuple(sg) for sg in segments]
+        for sg in segs:
+            if len(sg) != 3:
+                raise AudioProcessingError(f"Model prediction failed: a segment of a stereo cut is (sample_offset, first_frame, nframes): "
+                                           f"both channels are written, got {sg!r}")
+        items, start = self._cut_items(segs, hop, layout, 2, out_samples, rate=rate)
+        for i in range(len(segs)):
+            items[i].channel = _ffi.VAD_SCAN_BOTH
+        return items, start
+
+    def cut_stereo(self, segments, hop: Optional[int] = None, law: Optional[str] = None, i16_scale: int = 32767,
+                   denoise: Optional[float] = 0.01, layout="frames", out="pcm16", audio=None, sample_rate: Optional[int] = None, gains=None):
+        """``cut`` of a two-channel block with BOTH channels kept (``vad_scan_cut_stereo``): ``segments`` lists
+        ``(sample_offset, first_frame, nframes)`` - a fourth element is refused.  -> (data, start): ``data`` is ``[frames, 2]``,
+        segment i = ``data[start[i]:start[i + 1]]``; ``start`` counts sample frames.  ``data[:, c]`` is bit for bit what ``cut`` with
+        the same arguments gives for segments that name channel ``c``; the gate acts per value.  Every other argument as in ``cut``;
+        ``layout="frames"`` with a ``sample_rate`` other than the engine's is not supported (``"range"`` is)."""
+        lay, of = self._cut_enum(_ffi.CUT_LAYOUTS, "layout", layout), self._cut_enum(_ffi.CUT_OUTPUTS, "out", out)
+        with self._scan_lock:
+            sr, total, channels, fmt, ptr, _keep = self._cut_block("cut_stereo", audio, law, i16_scale, sample_rate)
+            hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
+            items, start = self._stereo_items(segments, hop, lay, rate=sr)
+            n = len(start) - 1
+            data = np.empty((int(start[-1]), 2), np.int16 if of == _ffi.VAD_CUT_PCM16 else np.float32)
+            thr = -1.0 if denoise is None else float(denoise)
+            g = None if gains is None else self._cut_gains(gains, n)
+            self._check(self._lib.vad_scan_cut_stereo(self._h, items, n, None if g is None else _ptr(g, C.c_float), ptr, total, channels, fmt,
+                                                      sr or 0, hop, thr, lay, of, data.ctypes.data_as(C.c_void_p), data.shape[0]))
+        return data, start
+
+    def cut_stereo_device(self, segments, d_audio: int, audio_samples: int, d_out: int, out_samples: int, hop: Optional[int] = None,
+                          fmt: int = _ffi.VAD_FMT_F32, channels: int = 2, denoise: Optional[float] = 0.01, layout="frames", out="pcm16",
+                          stream: int = 0, out_start=None, sample_rate: Optional[int] = None, gains=None) -> np.ndarray:
+        """``cut_stereo`` on device pointers (integers; ``vad_scan_cut_stereo_device``): the two-channel block at ``d_audio`` (8-byte
+        aligned), the payloads to ``d_out`` (16-byte aligned, room for ``out_samples`` sample frames = ``2 * out_samples`` values),
+        packed in the order listed or at sample frame ``out_start[i]`` (multiples of 4).  Asynchronous on ``stream``.
+        -> start [n + 1] of the packed order, in sample frames."""
+        lay, of = self._cut_enum(_ffi.CUT_LAYOUTS, "layout", layout), self._cut_enum(_ffi.CUT_OUTPUTS, "out", out)
+        sr = self._scan_rate(sample_rate)
+        hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
+        items, start = self._stereo_items(segments, hop, lay, out_start, rate=sr)
+        thr = -1.0 if denoise is None else float(denoise)
+        n = len(start) - 1
+        g = None if gains is None else self._cut_gains(gains, n)
+        self._check(self._lib.vad_scan_cut_stereo_device(self._h, items, n, None if g is None else _ptr(g, C.c_float), d_audio or None,
+                                                         int(audio_samples), int(channels), int(fmt), sr or 0, hop, thr, lay, of,
+                                                         d_out or None, int(out_samples), stream or None))
+        return start
+
+    def render_stereo(self, segments, out_start, out_samples: int, hop: Optional[int] = None, ramp=None, gains=None,
+                      denoise: Optional[float] = 0.01, out="pcm16", audio=None, law: Optional[str] = None, i16_scale: int = 32767,
+                      sample_rate: Optional[int] = None) -> np.ndarray:
+        """``render`` of a two-channel block with BOTH channels kept (``vad_scan_render_stereo``): ``segments`` as in ``cut_stereo``,
+        ``out_start`` and ``out_samples`` in sample frames.  -> ``[out_samples, 2]``; column ``c`` is bit for bit what ``render``
+        gives when every segment names channel ``c`` - gain and ramp are the same for both channels of a sample frame."""
+        of = self._cut_enum(_ffi.CUT_OUTPUTS, "out", out)
+        r = self._render_ramp(ramp)
+        with self._scan_lock:
+            sr, total, channels, fmt, ptr, _keep = self._cut_block("render_stereo", audio, law, i16_scale, sample_rate)
+            hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
+            items, start = self._stereo_items(segments, hop, _ffi.VAD_CUT_RANGE, out_start, rate=sr)
+            n = len(start) - 1
+            data = np.empty((max(int(out_samples), 0), 2), np.int16 if of == _ffi.VAD_CUT_PCM16 else np.float32)
+            thr = -1.0 if denoise is None else float(denoise)
+            g = None if gains is None else self._cut_gains(gains, n)
+            self._check(self._lib.vad_scan_render_stereo(self._h, items, n, None if g is None else _ptr(g, C.c_float),
+                                                         _ptr(r, C.c_float) if r.size else None, r.size, ptr, total, channels, fmt, sr or 0,
+                                                         hop, thr, of, data.ctypes.data_as(C.c_void_p), int(out_samples)))
+        return data
+
+    def render_stereo_device(self, segments, out_start, d_audio: int, audio_samples: int, d_out: int, out_samples: int,
+                             hop: Optional[int] = None, ramp=None, gains=None, fmt: int = _ffi.VAD_FMT_F32, channels: int = 2,
+                             denoise: Optional[float] = 0.01, out="pcm16", stream: int = 0, sample_rate: Optional[int] = None) -> None:
+        """``render_stereo`` on device pointers (integers; ``vad_scan_render_stereo_device``): the two-channel block at ``d_audio``,
+        all ``out_samples`` sample frames (``2 * out_samples`` values) to ``d_out`` (16-byte aligned).  Asynchronous on ``stream``."""
+        of = self._cut_enum(_ffi.CUT_OUTPUTS, "out", out)
+        r = self._render_ramp(ramp)
+        sr = self._scan_rate(sample_rate)
+        hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
+        items, start = self._stereo_items(segments, hop, _ffi.VAD_CUT_RANGE, out_start, rate=sr)
+        n = len(start) - 1
+        thr = -1.0 if denoise is None else float(denoise)
+        g = None if gains is None else self._cut_gains(gains, n)
+        self._check(self._lib.vad_scan_render_stereo_device(self._h, items, n, None if g is None else _ptr(g, C.c_float),
+                                                            _ptr(r, C.c_float) if r.size else None, r.size, d_audio or None,
+                                                            int(audio_samples), int(channels), int(fmt), sr or 0, hop, thr, of,
+                                                            d_out or None, int(out_samples), stream or None))
+
     # ------------------------------------------------------------------ tick assembler (shared-pool serving)
     def tick_push(self, slot: int, frame, gate_on: bool = True, i16_scale: int = 32767, sample_rate: Optional[int] = None,
                   law: Optional[str] = None) -> None:

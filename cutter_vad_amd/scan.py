@@ -113,6 +113,29 @@ def _need_render(engine, who: str) -> None:
                                  f"left on the GPU), {type(engine).__name__} has none")
 
 
+def _need_stereo(engine, who: str, what: str) -> None:
+    if not hasattr(engine, what):
+        raise ConfigurationError("keep_channels", "True", f"{who}: keep_channels=True needs an engine with {what} (both channels are "
+                                 f"written from the block a scan left on the GPU), {type(engine).__name__} has none")
+
+
+def _keep_channels_check(who: str, split: bool) -> None:
+    if split:
+        raise ConfigurationError("keep_channels", "True", f"{who}: keep_channels=True delivers both channels of a recording in one payload; "
+                                 "channel='split' asks for one payload per channel - scan 'mix', 0 or 1")
+
+
+def _joint_gains(engine, table, hop: int, denoise, normalize) -> np.ndarray:
+    """``normalize`` for segments whose two channels are both kept: ONE ``Engine.levels`` call lists every segment twice - channel 0,
+    then channel 1 - and a segment's factor is ``np.float32(normalize)`` over the larger of its two peaks (1 where that is 0 or not
+    finite): one factor for both channels keeps their balance"""
+    both = [sg + (0,) for sg in table] + [sg + (1,) for sg in table]
+    peak = engine.levels(both, hop=hop, denoise=denoise)["peak"]
+    peak = np.maximum(peak[:len(table)], peak[len(table):])
+    usable = np.isfinite(peak) & (peak > 0)
+    return np.where(usable, np.float32(normalize) / np.where(usable, peak, np.float32(1)), np.float32(1)).astype(np.float32)
+
+
 def fade_ramp(n: int, shape: str = "linear") -> np.ndarray:
     """A fade table of ``n`` entries for ``Engine.render``, rising from just above 0 to just below 1: ``"linear"`` is
     ``(k + 0.5) / n``, ``"cosine"`` is ``0.5 - 0.5 cos(pi (k + 0.5) / n)`` - computed in float64 and rounded once to float32.
@@ -368,7 +391,7 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
 def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
                    law: Optional[str] = None, channel="mix", layout: str = "frames", wav: bool = True,
                    sample_rate: Optional[int] = None, open_end: bool = False, refine: Optional[SegmentRefine] = None,
-                   normalize: Optional[float] = None) -> List:
+                   normalize: Optional[float] = None, keep_channels: bool = False) -> List:
     """``scan_recordings`` with each finished segment's audio: per recording ``[(start_sample, end_sample, payload), ...]`` (per
     channel for ``"split"``, as there).  ``payload`` is what ``VADWrapper``'s ``voice_end`` callback delivers for the same
     recording - the segment's frames back to back, decoded, mixed and gated as the model read them, as 16-bit PCM behind the WAV
@@ -386,7 +409,14 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
     ``normalize``: a target level, as ``AudioUtils.normalize_audio(target_level=...)`` per segment: each segment's samples are
     multiplied by ``np.float32(np.float32(normalize) / peak)`` ahead of the conversion to PCM - by 1 where the peak is 0 - with the
     peak of ``Engine.levels`` on the same table (the segment's sample range), so the corpus still crosses the link once and the
-    factor is applied on the GPU (``Engine.cut(gains=...)``; an engine object without ``levels``: ``ConfigurationError``)."""
+    factor is applied on the GPU (``Engine.cut(gains=...)``; an engine object without ``levels``: ``ConfigurationError``).
+    ``keep_channels``: ``True`` delivers the audio of a two-channel recording as it was recorded, both channels in place
+    (``Engine.cut_stereo``; an engine object without it: ``ConfigurationError``): the recording is still scanned as ``channel`` says
+    (``"mix"``, 0 or 1; ``"split"`` is a ``ConfigurationError``), ranges count sample frames as before, and the payload is a
+    ``[k, 2]`` int16 array or a WAV with a two-channel header.  ``layout="frames"`` with a ``sample_rate`` other than the engine's
+    is a ``ConfigurationError``: use ``layout="range"``.  ``normalize`` then divides by the larger of the segment's two channel
+    peaks (one ``Engine.levels`` call listing every segment for channel 0 and for channel 1): one factor for both channels, which
+    keeps their balance.  1-D recordings of the same corpus are cut as without it."""
     from .pool import default_pool, resolve_model_path
     from .utils.wav_writer import WAVWriter
     split = isinstance(channel, str) and channel == "split"
@@ -394,9 +424,13 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
         raise ConfigurationError("channel", repr(channel), f"cut_recordings: channel is 'mix', 0, 1 or 'split' for the whole corpus, got {channel!r}")
     if layout not in _ffi.CUT_LAYOUTS:
         raise ConfigurationError("layout", repr(layout), f"cut_recordings: layout is 'frames' or 'range', got {layout!r}")
+    if keep_channels:
+        _keep_channels_check("cut_recordings", split)
     cfg = config or VADConfig()
     if engine is None:
         engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
+    if keep_channels:
+        _need_stereo(engine, "cut_recordings", "cut_stereo")
     if open_end:
         _need_tails(engine, "cut_recordings")
     if refine is not None:
@@ -412,11 +446,15 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
         if rate not in (8000, 16000, 24000, 48000):
             raise ConfigurationError("sample_rate", repr(sample_rate), f"cut_recordings: recordings at 8000, 16000, 24000 or 48000 Hz, got {sample_rate!r}")
         frame = engine.scan_chunk_samples(rate)      # the ranges count input samples
+        if keep_channels and layout == "frames":
+            raise ConfigurationError("layout", repr(layout), f"cut_recordings: keep_channels=True on recordings at {rate} Hz cuts their own "
+                                     "samples: use layout=\"range\" (both channels of the resampled frames are not supported)")
     hop = frame // 2 if hop is None else int(hop)
     recordings = [np.asarray(r) for r in recordings]
     if not recordings:
         return []
     writer = WAVWriter(rate if rate is not None and layout == "range" else cfg.output_wav_sample_rate, 16, 1)
+    writer2 = WAVWriter(writer.sample_rate, 16, 2) if keep_channels else None
     denoise = 0.01 if cfg.enable_denoising else None
     out: List = [None] * len(recordings)
     for two in (False, True):
@@ -434,7 +472,12 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
                 ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, denoise, channel, rate=rate,
                                       open_end=open_end, refine=refine)
                 table = _cut_table(engine, ranges, chans, frame, hop)
-                if table and normalize is not None:
+                if two and keep_channels:
+                    table = [sg[:3] for sg in table]
+                    if table:
+                        gains = None if normalize is None else _joint_gains(engine, table, hop, denoise, normalize)
+                        data, start = engine.cut_stereo(table, hop=hop, denoise=denoise, layout=layout, gains=gains)
+                elif table and normalize is not None:
                     peak = engine.levels(table, hop=hop, denoise=denoise)["peak"]
                     usable = np.isfinite(peak) & (peak > 0)
                     gains = np.where(usable, np.float32(normalize) / np.where(usable, peak, np.float32(1)), np.float32(1)).astype(np.float32)
@@ -454,7 +497,7 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
                     j += 1
                     if wav:
                         raw = pcm.tobytes()
-                        one.append((a, b, writer.header(len(raw)) + raw))
+                        one.append((a, b, (writer2 if two and keep_channels else writer).header(len(raw)) + raw))
                     else:
                         one.append((a, b, pcm.copy()))
                 lists.append(one)
@@ -477,7 +520,7 @@ def _join_places(counts: Sequence[int], nramp: int, gap: int) -> List[int]:
 def render_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
                       law: Optional[str] = None, channel="mix", sample_rate: Optional[int] = None, open_end: bool = False,
                       refine: Optional[SegmentRefine] = None, normalize: Optional[float] = None, mode: str = "join", fade_ms: float = 10.0,
-                      gap_ms: float = 0.0, shape: str = "linear", wav: bool = True) -> List:
+                      gap_ms: float = 0.0, shape: str = "linear", wav: bool = True, keep_channels: bool = False) -> List:
     """One finished piece of audio per recording: per recording ``(payload, timeline)`` (per channel for ``"split"``, as in
     ``scan_recordings``).  ``mode="join"`` is silence removal: the recording's speech segments (their sample ranges, as
     ``cut_recordings(layout="range")`` cuts them) back to back, each faded in and out over ``fade_ms`` by a ``fade_ramp`` of
@@ -491,7 +534,10 @@ def render_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConf
     ``cut_recordings``: per listed segment - in ``"mask"`` per merged one) and one ``Engine.render`` of the block the scan left
     on the GPU, under ``Engine.scan_session()``: only the finished audio crosses the link back.  ``hop``, ``law``, ``sample_rate``,
     ``open_end`` and ``refine`` as in ``cut_recordings``; on recordings at another rate the samples are the recording's own,
-    never gated.  An engine object without ``render``: ``ConfigurationError``."""
+    never gated.  An engine object without ``render``: ``ConfigurationError``.
+    ``keep_channels`` as in ``cut_recordings``: the piece of a two-channel recording keeps both channels (``Engine.render_stereo``;
+    an engine object without it: ``ConfigurationError``) - a ``[k, 2]`` int16 array or a WAV with a two-channel header; places,
+    lengths and the timeline count sample frames and are what they are without it; gain and ramp are the same for both channels."""
     from .pool import default_pool, resolve_model_path
     from .utils.wav_writer import WAVWriter
     who = "render_recordings"
@@ -502,10 +548,14 @@ def render_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConf
         raise ConfigurationError("mode", repr(mode), f"{who}: mode is 'join' or 'mask', got {mode!r}")
     if not (fade_ms >= 0 and gap_ms >= 0):
         raise ConfigurationError("fade_ms", repr((fade_ms, gap_ms)), f"{who}: fade_ms and gap_ms are 0 or more, got {fade_ms!r} and {gap_ms!r}")
+    if keep_channels:
+        _keep_channels_check(who, split)
     cfg = config or VADConfig()
     if engine is None:
         engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
     _need_render(engine, who)
+    if keep_channels:
+        _need_stereo(engine, who, "render_stereo")
     if open_end:
         _need_tails(engine, who)
     if refine is not None:
@@ -531,6 +581,7 @@ def render_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConf
     if not recordings:
         return []
     writer = WAVWriter(int(sample_rate) if sample_rate is not None else cfg.output_wav_sample_rate, 16, 1)
+    writer2 = WAVWriter(writer.sample_rate, 16, 2) if keep_channels else None
     denoise = 0.01 if cfg.enable_denoising else None
     out: List = [None] * len(recordings)
     for two in (False, True):
@@ -577,11 +628,17 @@ def render_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConf
                         lengths.append((base, size, at, counts))
                         base += size
                 gains = None
-                if table and normalize is not None:
-                    peak = engine.levels(table, hop=hop, denoise=denoise)["peak"]
-                    usable = np.isfinite(peak) & (peak > 0)
-                    gains = np.where(usable, np.float32(normalize) / np.where(usable, peak, np.float32(1)), np.float32(1)).astype(np.float32)
-                data = engine.render(table, places, base, hop=hop, ramp=ramp, gains=gains, denoise=denoise)
+                if two and keep_channels:
+                    table = [sg[:3] for sg in table]
+                    if table and normalize is not None:
+                        gains = _joint_gains(engine, table, hop, denoise, normalize)
+                    data = engine.render_stereo(table, places, base, hop=hop, ramp=ramp, gains=gains, denoise=denoise)
+                else:
+                    if table and normalize is not None:
+                        peak = engine.levels(table, hop=hop, denoise=denoise)["peak"]
+                        usable = np.isfinite(peak) & (peak > 0)
+                        gains = np.where(usable, np.float32(normalize) / np.where(usable, peak, np.float32(1)), np.float32(1)).astype(np.float32)
+                    data = engine.render(table, places, base, hop=hop, ramp=ramp, gains=gains, denoise=denoise)
         finally:
             for s in slots:
                 engine.close_stream(int(s))
@@ -597,7 +654,7 @@ def render_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConf
                 timeline = [(p, a, s) for p, (a, _), s in zip(at, rg, counts)]
                 if wav:
                     raw = pcm.tobytes()
-                    lists.append((writer.header(len(raw)) + raw, timeline))
+                    lists.append(((writer2 if two and keep_channels else writer).header(len(raw)) + raw, timeline))
                 else:
                     lists.append((pcm.copy(), timeline))
             out[i] = lists if split else lists[0]

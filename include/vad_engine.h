@@ -809,6 +809,47 @@ VAD_API int vad_scan_render_device(vad_engine *e, const vad_cut_item *items, int
                                    float denoise_thresh, int32_t out_fmt, void *d_out, int64_t out_samples, void *stream);
 
 /*
+ * Two-channel segment audio: the cut and the render of a TWO-CHANNEL block with both channels kept.  The VAD decides on the mix or
+ * on one speaker (the scan's channel); the audio delivered is the recording's.  The argument lists are those of
+ * vad_scan_cut_gain / _device and vad_scan_render / _device.  THE RULE:
+ *   - out_sample, out_samples and vad_cut_samples / vad_rate_cut_samples count sample FRAMES; the output holds 2 * out_samples
+ * values, interleaved L R L R (a two-channel WAV payload for VAD_CUT_PCM16).
+ *   - Value (k, c) of vad_scan_cut_stereo is bit for bit what vad_scan_cut_gain writes for sample k with the same arguments and
+ * every item's channel = c; gains == NULL means no factor: the bytes of vad_scan_cut.  The gate acts per value, so it may zero one
+ * channel of a sample frame and keep the other.
+ *   - Value (s, c) of vad_scan_render_stereo is bit for bit what vad_scan_render writes for sample s with every item's
+ * channel = c: gain and ramp factors are the same for both channels of a sample frame, the sum where two segments meet is one
+ * float32 add per channel, gaps are zeros in both.
+ *   Every rule and refusal of the mono calls applies under these names, in the same order: block, hop, offsets and extents,
+ * out_sample's alignment to 4 (sample frames), overlapping outputs (cut) and three covers (render), the ramp, non-finite gains, the
+ * resident block with audio == NULL, sr_in, the wait for earlier *_device launches.  Refusals of their own, each
+ * VAD_ERR_INVALID_ARG with a message and nothing written: channels != 2 ("two-channel blocks only", behind the frame format's
+ * check) and an item whose channel is not VAD_SCAN_BOTH (where the mono calls check the channel).  VAD_CUT_FRAMES on a rate block
+ * (sr_in 8000 / 24000 / 48000) is VAD_ERR_UNSUPPORTED with a message, behind the layout's check: it would need two resampled rows
+ * per chunk; VAD_CUT_RANGE on rate blocks works - input-rate sample frames, never gated, as in mono.  The mono entry points keep
+ * refusing channel = VAD_SCAN_BOTH in their present words.
+ *   Works on every engine, Silero V4 and VAD_ENGINE_SHARED_GPU included: no model kernel runs.  Device forms: d_audio is 8-byte
+ * aligned, d_out 16-byte aligned and holds 2 * out_samples values; gains and ramp stay HOST arrays.
+ *   VAD_ABI_VERSION is unchanged: the presence of vad_scan_cut_stereo is how a caller detects the feature.
+ */
+#define VAD_SCAN_BOTH (-2)
+VAD_API int vad_scan_cut_stereo(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains /*host [n] or NULL*/,
+                                const void *audio /*or NULL*/, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in,
+                                int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *out, int64_t out_samples);
+VAD_API int vad_scan_cut_stereo_device(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains /*host [n] or NULL*/,
+                                       const void *d_audio, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in,
+                                       int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *d_out,
+                                       int64_t out_samples, void *stream);
+VAD_API int vad_scan_render_stereo(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains /*host [n] or NULL*/,
+                                   const float *ramp /*host [nramp] or NULL*/, int32_t nramp, const void *audio /*or NULL*/,
+                                   int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop,
+                                   float denoise_thresh, int32_t out_fmt, void *out, int64_t out_samples);
+VAD_API int vad_scan_render_stereo_device(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains /*host [n] or NULL*/,
+                                          const float *ramp /*host [nramp] or NULL*/, int32_t nramp, const void *d_audio,
+                                          int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop,
+                                          float denoise_thresh, int32_t out_fmt, void *d_out, int64_t out_samples, void *stream);
+
+/*
  * Pipelined host ingest.  vad_step* on host pointers are copy -> kernel -> copy -> wait; at 8 192 streams the PCIe copy is
  * 5-8 x the kernel, so a serving loop should overlap the copy of tick t+1 with the kernel of tick t:
  *

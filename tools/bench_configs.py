@@ -1525,6 +1525,171 @@ def scan_render():
     return row
 
 
+def scan_cut_stereo():
+    """What segment audio with both channels kept costs: VAD_SCAN_BENCH_N (default 1 024) two-channel int16
+    recordings of 30 s at 16 kHz - speech on the left, other speech at half the level on the right - hop 256, the table of one scan
+    of their mix.  (a) device calls, HIP-event timed as scan_render's (b): vad_scan_cut_stereo_device (VAD_CUT_RANGE, PCM16)
+    against the parent's way to the same samples on the device - two vad_scan_cut_gain_device calls, channel 0 and channel 1, which
+    leave them as two planes - and vad_scan_render_stereo_device (every recording's segments joined with a 10 ms crossfade) against
+    two vad_scan_render_device calls; the stereo call and the pair alternate.  (b) end to end: cut_recordings(keep_channels=True,
+    layout="range", wav=False) against two cut_recordings calls (channel 0, channel 1) and the numpy interleave - timed on arrays
+    of the stereo result's own sizes, since two scans of different channels need not list the same ranges.  One warm-up, then three
+    timed passes of each; medians; the result goes to profiles/scan_cut_stereo.json."""
+    import ctypes as C
+    import json
+    import time
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    from cutter_vad_amd import VADConfig, _ffi, cut_recordings, fade_ramp
+    from cutter_vad_amd.scan import _join_places
+    N = int(os.environ.get("VAD_SCAN_BENCH_N", "1024"))
+    eng = Engine(blob(5), max_streams=max(N, 16))
+    hop, frame, nramp = 256, 512, 160
+    pcm = np.tile(np.load(os.path.join(root, "tests", "golden", "speech16k_i16.npz"))["pcm"].astype(np.int16), 3)
+    rng = np.random.default_rng(N)
+    ns = 30 * 16000
+    recs = [np.ascontiguousarray(np.stack([pcm[a:a + ns], pcm[b:b + ns] >> 1], axis=1))
+            for a, b in zip(rng.integers(0, pcm.size - ns + 1, N), rng.integers(0, pcm.size - ns + 1, N))]
+    med = lambda v: float(np.median(v))
+    row = {"config": f"scan_cut_stereo: {N} two-channel int16 recordings of 30 s at 16 kHz, hop {hop}, both channels kept", "recordings": N,
+           "passes": 3}
+    slots = eng.open_streams(N)
+    eng.set_thresholds_many(slots, (0.4, 0.3, 0.8, 0.95, 6, 12))
+    with eng.scan_session():
+        table = eng.scan_segments(slots, recs, hop=hop, denoise=0.01, channel="mix")
+        last = eng.last_scan
+        offs = [int(o) for o in last["offsets"]]
+        block_samples, fmt = int(last["samples"]), last["fmt"]
+    for s in slots:
+        eng.close_stream(int(s))
+    item = table["item"].tolist()
+    segs = [(offs[i], f, n) for i, f, n in zip(item, table["first_frame"].tolist(), table["nframes"].tolist())]
+    counts = [(n - 1) * hop + frame for _, _, n in segs]
+    total = int(sum(counts))
+    places, base, k = [], 0, 0                       # a recording's segments back to back, crossfaded; the pieces one behind the other
+    while k < len(segs):
+        m = k
+        while m < len(segs) and item[m] == item[k]:
+            m += 1
+        at = _join_places(counts[k:m], nramp, 0)
+        places += [base + p for p in at]
+        base += at[-1] + counts[m - 1]
+        k = m
+    row.update(segments=len(segs), speech_frames=total, render_frames=base, block_frames=block_samples)
+    # (a) on device pointers
+    block = np.zeros((block_samples, 2), np.int16)
+    for r, o in zip(recs, offs):
+        block[o:o + r.shape[0]] = r
+    d_audio = torch.from_numpy(block).cuda()
+    room = max(total, base) + 16
+    d_st = torch.empty((room, 2), dtype=torch.int16, device="cuda")
+    d_pl = torch.empty((2, room), dtype=torch.int16, device="cuda")
+    ts = torch.cuda.Stream()
+    busy = torch.randn(6144, 6144, device="cuda")
+    lib, h, n = eng._lib, eng.handle, len(segs)
+    ramp = fade_ramp(nramp)
+    rp = ramp.ctypes.data_as(C.POINTER(C.c_float))
+    ones = np.ones(n, np.float32)
+    gp = ones.ctypes.data_as(C.POINTER(C.c_float))
+    cut_st, _ = eng._stereo_items(segs, hop, _ffi.VAD_CUT_RANGE)
+    cut_ch = [eng._cut_items([sg + (c,) for sg in segs], hop, _ffi.VAD_CUT_RANGE, 2)[0] for c in (0, 1)]
+    ren_st, _ = eng._stereo_items(segs, hop, _ffi.VAD_CUT_RANGE, places)
+    ren_ch = [eng._cut_items([sg + (c,) for sg in segs], hop, _ffi.VAD_CUT_RANGE, 2, places)[0] for c in (0, 1)]
+    where = (d_audio.data_ptr(), block_samples, 2, fmt)
+    P16, RNG_ = _ffi.VAD_CUT_PCM16, _ffi.VAD_CUT_RANGE
+
+    def pair(one):
+        return lambda: one(0) or one(1)
+
+    calls = {
+        "a_s_cut_stereo_device": lambda: lib.vad_scan_cut_stereo_device(h, cut_st, n, None, *where, 0, hop, 0.01, RNG_, P16, d_st.data_ptr(), total,
+                                                                        ts.cuda_stream),
+        "a_s_two_cut_gain_device": pair(lambda c: lib.vad_scan_cut_gain_device(h, cut_ch[c], n, gp, *where, 0, hop, 0.01, RNG_, P16,
+                                                                               d_pl[c].data_ptr(), total, ts.cuda_stream)),
+        "a_s_render_stereo_device": lambda: lib.vad_scan_render_stereo_device(h, ren_st, n, None, rp, nramp, *where, 0, hop, 0.01, P16,
+                                                                              d_st.data_ptr(), base, ts.cuda_stream),
+        "a_s_two_render_device": pair(lambda c: lib.vad_scan_render_device(h, ren_ch[c], n, None, rp, nramp, *where, 0, hop, 0.01, P16,
+                                                                           d_pl[c].data_ptr(), base, ts.cuda_stream)),
+    }
+    runs = {name: [] for name in calls}
+    equal = {}
+    for k in range(5):                               # two warm-ups; the stereo call and the pair alternate
+        for name, fn in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            with torch.cuda.stream(ts):
+                torch.mm(busy, busy)
+            e0.record(ts)
+            assert fn() == 0, name
+            e1.record(ts)
+            torch.cuda.synchronize()
+            if k >= 2:
+                runs[name].append(e0.elapsed_time(e1) * 1e-3)
+            if k == 0 and "two" in name:
+                size = total if "cut" in name else base
+                equal[name] = bool(torch.equal(d_st[:size, 0], d_pl[0, :size]) and torch.equal(d_st[:size, 1], d_pl[1, :size]))
+    for name, v in runs.items():
+        row[name + "_runs"], row[name] = v, med(v)
+    row["a_cut_equal"], row["a_render_equal"] = equal["a_s_two_cut_gain_device"], equal["a_s_two_render_device"]
+    row["a_ratio_two_cuts_over_stereo"] = row["a_s_two_cut_gain_device"] / row["a_s_cut_stereo_device"]
+    row["a_ratio_two_cuts_over_stereo_spread"] = [min(row["a_s_two_cut_gain_device_runs"]) / max(row["a_s_cut_stereo_device_runs"]),
+                                                  max(row["a_s_two_cut_gain_device_runs"]) / min(row["a_s_cut_stereo_device_runs"])]
+    row["a_ratio_two_renders_over_stereo"] = row["a_s_two_render_device"] / row["a_s_render_stereo_device"]
+    row["a_ratio_two_renders_over_stereo_spread"] = [min(row["a_s_two_render_device_runs"]) / max(row["a_s_render_stereo_device_runs"]),
+                                                     max(row["a_s_two_render_device_runs"]) / min(row["a_s_render_stereo_device_runs"])]
+    row["a_cut_stereo_GBps_read_plus_written"] = 8 * total / row["a_s_cut_stereo_device"] / 1e9
+    del d_audio, d_st, d_pl, busy, block
+    torch.cuda.empty_cache()
+    # (b) end to end
+    cfg = VADConfig(vad_start_probability=0.4, vad_end_probability=0.3, voice_start_frame_count=6, voice_end_frame_count=12)
+    kw = dict(engine=eng, hop=hop, layout="range", wav=False)
+
+    def route_a():
+        return cut_recordings(recs, cfg, keep_channels=True, **kw)
+
+    def route_b(shapes):
+        t0 = time.perf_counter()
+        left = cut_recordings(recs, cfg, channel=0, **kw)
+        right = cut_recordings(recs, cfg, channel=1, **kw)
+        t1 = time.perf_counter()
+        planes = [(np.empty(m, np.int16), np.empty(m, np.int16)) for m in shapes]
+        t2 = time.perf_counter()
+        both = [np.ascontiguousarray(np.stack(p, axis=1)) for p in planes]
+        return (left, right, both), t1 - t0, time.perf_counter() - t2
+
+    got = route_a()
+    shapes = [p.shape[0] for one in got for _, _, p in one]
+    row.update(b_segments=len(shapes), b_speech_frames=int(sum(shapes)))
+    route_b(shapes)
+    a_runs, b_runs, b_cuts, b_np = [], [], [], []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        route_a()
+        a_runs.append(time.perf_counter() - t0)
+        _, c, s = route_b(shapes)
+        b_runs.append(c + s)
+        b_cuts.append(c)
+        b_np.append(s)
+    row.update(b_s_keep_channels_runs=a_runs, b_s_keep_channels=med(a_runs), b_s_two_calls_interleave_runs=b_runs,
+               b_s_two_calls_interleave=med(b_runs), b_s_two_calls=med(b_cuts), b_s_interleave=med(b_np),
+               b_ratio_two_calls_over_keep_channels=med(b_runs) / med(a_runs),
+               b_ratio_two_calls_over_keep_channels_spread=[min(b_runs) / max(a_runs), max(b_runs) / min(a_runs)])
+    eng.close()
+    with open(os.path.join(root, "profiles", "scan_cut_stereo.json"), "w") as f:
+        json.dump({"what": "Segment audio with both channels kept (vad_scan_cut_stereo, vad_scan_render_stereo): DESIGN 2.1r",
+                   "how": "python tools/bench_configs.py scan_cut_stereo on one MI355X, one process.  (a) device forms: HIP events behind a "
+                          "matrix product that keeps the stream busy while the host builds the tables, ctypes items built outside the clock, "
+                          "the stereo call and the pair of mono calls alternating, two warm-ups and three timed passes, medians; the pair "
+                          "leaves two planes, the stereo call the interleaved samples.  (b) cut_recordings(keep_channels=True) against two "
+                          "cut_recordings calls and a numpy interleave of arrays of the same sizes, wall clock, one warm-up and three timed "
+                          "passes.  The spreads are min / max and max / min of the runs.  Not measured: rate blocks, the render in mask mode, "
+                          "other formats, sizes and ramps, the spread between processes and boxes",
+                   "runs": [row]}, f, indent=1)
+        f.write("\n")
+    return row
+
+
 def single_stream_wrapper():
     """configs[0]: ONE stream through the drop-in VADWrapper (host framing + one launch + sync + callbacks per chunk)."""
     import time

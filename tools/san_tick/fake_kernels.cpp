@@ -132,8 +132,11 @@ extern "C" hipError_t vadk_launch_silero_v5_scan16(const StepParams *p, const Sc
 // strict gate, then the float32 itself or clip(x * 32767, -32768, 32767) converted toward zero.  gains (vadk_scan_cut_gain): the
 // gated value times gains[segment], one float32 multiply, ahead of either.  levels (csrc/scan_levels.hip: vadk_seg_levels): nothing
 // is stored - the gated values of a segment are folded into its vad_level (a.out, zeroed by the caller): energy_q32 +=
-// min(rint((double)x * x * 2^32), 2^32), peak = the larger bit pattern of |x|, clipped += |x| >= clip in float32
-static hipError_t fake_cut(const CutArgs *a, const float *gains, bool levels, float clip) {
+// min(rint((double)x * x * 2^32), 2^32), peak = the larger bit pattern of |x|, clipped += |x| >= clip in float32.  stereo
+// (csrc/scan_cut_stereo.hip: vadk_scan_cut_stereo): the mode bits are ignored, sample frame o takes two output values - the left
+// channel's at 2 o, the right one's at 2 o + 1 - each gated, gained and converted on its own
+static hipError_t fake_cut(const CutArgs *a, const float *gains, bool levels, float clip, bool stereo = false) {
+    if (stereo && a->channels != 2) return hipErrorInvalidValue;
     const uint32_t fmask = a->frame_shift >= 31u ? 0x7fffffffu : (1u << a->frame_shift) - 1u;
     const size_t ch = a->channels == 2 ? 2 : 1;
     for (uint32_t b = 0; b < a->nwork; ++b) {
@@ -142,14 +145,15 @@ static hipError_t fake_cut(const CutArgs *a, const float *gains, bool levels, fl
         const uint32_t mode = sg.quad_in >> SCAN_MODE_SHIFT, qin = sg.quad_in & ((1u << SCAN_MODE_SHIFT) - 1u);
         for (uint32_t oq = w.quad0; oq < w.quad0 + (uint32_t)CUT_WG_QUADS && oq < sg.nquads; ++oq) {
             const uint32_t iq = qin + (oq >> a->frame_shift) * a->hopq + (oq & fmask);
-            for (int k = 0; k < 4; ++k) {
-                const size_t i = 4 * (size_t)iq + k, o = 4 * ((size_t)sg.quad_out + oq) + k;
+            for (int kc = 0; kc < (stereo ? 8 : 4); ++kc) {
+                const int k = stereo ? kc >> 1 : kc, c = kc & 1;
+                const size_t i = 4 * (size_t)iq + k, of = 4 * ((size_t)sg.quad_out + oq) + k, o = stereo ? 2 * of + c : of;
                 if ((i + 1) * ch * (a->fmt == VAD_FMT_F32 ? 4 : a->fmt >= VAD_FMT_ULAW8 ? 1 : 2) > a->audio_bytes) return hipErrorInvalidValue;
                 float x;
                 if (ch == 1) x = first_sample(a->audio, i, a->fmt, 1);
                 else {
                     const float l = first_sample(a->audio, 2 * i, a->fmt, 1), r = first_sample(a->audio, 2 * i + 1, a->fmt, 1);
-                    x = mode == SCAN_MIX ? (l + r) * 0.5f : mode == SCAN_RIGHT ? r : l;
+                    x = stereo ? (c ? r : l) : mode == SCAN_MIX ? (l + r) * 0.5f : mode == SCAN_RIGHT ? r : l;
                 }
                 if (a->thresh >= 0.f && !(std::fabs(x) > a->thresh)) x = 0.f;
                 if (levels) {
@@ -179,18 +183,23 @@ static hipError_t fake_cut(const CutArgs *a, const float *gains, bool levels, fl
 extern "C" hipError_t vadk_launch_scan_cut(const CutArgs *a, hipStream_t) { return fake_cut(a, nullptr, false, 0.f); }
 extern "C" hipError_t vadk_launch_scan_cut_gain(const CutArgs *a, const float *gains, hipStream_t) { return fake_cut(a, gains, false, 0.f); }
 extern "C" hipError_t vadk_launch_seg_levels(const CutArgs *a, float clip, hipStream_t) { return fake_cut(a, nullptr, true, clip); }
+extern "C" hipError_t vadk_launch_scan_cut_stereo(const CutArgs *a, const float *gains, hipStream_t) { return fake_cut(a, gains, false, 0.f, true); }
 
 // one finished piece of audio (csrc/scan_render.hip: vadk_scan_render), the kernel's arithmetic in plain C++, output quad by output
 // quad as its workgroups are listed: per covering segment the cut's decoded, channel-selected, gated sample, times the gain, times
 // the fade-in entry (or 1), times the fade-out entry (or 1) - three float32 multiplies - then the sum of the two where two segments
-// cover the sample, zero where none does, and the cut's conversion
-static hipError_t fake_render(const RenderArgs *a) {
+// cover the sample, zero where none does, and the cut's conversion.  stereo (csrc/scan_render_stereo.hip: vadk_scan_render_stereo):
+// the mode bits are ignored, sample frame s takes two output values - left at 2 s, right at 2 s + 1 - under the same gain and ramp
+static hipError_t fake_render(const RenderArgs *a, bool stereo = false) {
+    if (stereo && a->channels != 2) return hipErrorInvalidValue;
     const size_t ch = a->channels == 2 ? 2 : 1;
     const uint32_t nramp = 4 * a->nrampq;
     for (uint32_t b = 0; b < a->nwork; ++b) {
         const RenderWork w = a->work[b];
         if (w.nquads < 1 || w.nquads > (uint32_t)CUT_WG_QUADS) return hipErrorInvalidValue;
-        for (uint64_t s = 4 * w.quad_out; s < 4 * (w.quad_out + w.nquads); ++s) {
+        for (uint64_t sc = (stereo ? 8 : 4) * w.quad_out; sc < (stereo ? 8 : 4) * (w.quad_out + w.nquads); ++sc) {
+            const uint64_t s = stereo ? sc >> 1 : sc;
+            const int c = (int)(sc & 1);
             float acc = 0.f;
             for (int src = 0; src < 2; ++src) {
                 const uint32_t si = src == 0 ? w.seg_a : w.seg_b;
@@ -205,7 +214,7 @@ static hipError_t fake_render(const RenderArgs *a) {
                 if (ch == 1) x = first_sample(a->audio, i, a->fmt, 1);
                 else {
                     const float l = first_sample(a->audio, 2 * i, a->fmt, 1), r = first_sample(a->audio, 2 * i + 1, a->fmt, 1);
-                    x = mode == SCAN_MIX ? (l + r) * 0.5f : mode == SCAN_RIGHT ? r : l;
+                    x = stereo ? (c ? r : l) : mode == SCAN_MIX ? (l + r) * 0.5f : mode == SCAN_RIGHT ? r : l;
                 }
                 if (a->thresh >= 0.f && !(std::fabs(x) > a->thresh)) x = 0.f;
                 if (a->gains) x = x * a->gains[si];
@@ -213,10 +222,10 @@ static hipError_t fake_render(const RenderArgs *a) {
                 volatile float z = y * (back < nramp ? a->ramp[back] : 1.0f);
                 acc = src == 0 || w.seg_a == RENDER_NONE ? (float)z : acc + z;
             }
-            if (a->out_fmt == VAD_CUT_F32) static_cast<float *>(a->out)[s] = acc;
+            if (a->out_fmt == VAD_CUT_F32) static_cast<float *>(a->out)[sc] = acc;
             else {
                 const float v = acc * 32767.0f;
-                static_cast<int16_t *>(a->out)[s] = (int16_t)(int)(v < -32768.0f ? -32768.0f : v > 32767.0f ? 32767.0f : v);
+                static_cast<int16_t *>(a->out)[sc] = (int16_t)(int)(v < -32768.0f ? -32768.0f : v > 32767.0f ? 32767.0f : v);
             }
         }
     }
@@ -224,6 +233,7 @@ static hipError_t fake_render(const RenderArgs *a) {
 }
 
 extern "C" hipError_t vadk_launch_scan_render(const RenderArgs *a, hipStream_t) { return fake_render(a); }
+extern "C" hipError_t vadk_launch_scan_render_stereo(const RenderArgs *a, hipStream_t) { return fake_render(a, true); }
 
 // the segment table of a scan (csrc/scan_segments.hip), the kernels' arithmetic in plain C++ and in one sweep: an END is a byte with
 // VAD_EV_END set and VAD_EV_REJECTED clear, its item the last one whose first index is not above it, the records in ascending
