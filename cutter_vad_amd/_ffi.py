@@ -148,6 +148,17 @@ class Level(C.Structure):
 LEVEL_DTYPE = np.dtype([("energy_q32", np.int64), ("peak", np.float32), ("clipped", np.int32)])
 
 
+class Mel(C.Structure):
+    _fields_ = [("n_fft", C.c_int32), ("hop", C.c_int32), ("n_bins", C.c_int32), ("n_mels", C.c_int32), ("pad", C.c_int32),
+                ("log", C.c_int32), ("floor", C.c_float), ("reserved", C.c_int32)]
+
+
+VAD_MEL_PAD_NONE, VAD_MEL_PAD_REFLECT = 0, 1
+VAD_MEL_LINEAR, VAD_MEL_LN, VAD_MEL_LOG10 = 0, 1, 2
+MEL_PADS = {"none": VAD_MEL_PAD_NONE, "reflect": VAD_MEL_PAD_REFLECT}
+MEL_LOGS = {"linear": VAD_MEL_LINEAR, "ln": VAD_MEL_LN, "log10": VAD_MEL_LOG10}
+
+
 class Segment(C.Structure):
     _fields_ = [("item", C.c_int32), ("first_frame", C.c_int32), ("nframes", C.c_int32), ("counted", C.c_int32),
                 ("mean_prob", C.c_float), ("max_prob", C.c_float)]
@@ -281,6 +292,11 @@ SIGNATURES = {
                                     C.c_float, C.c_int32, C.c_int32, _vp, C.c_int64]),
     "vad_scan_cut_gain_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32,
                                            C.c_int32, C.c_float, C.c_int32, C.c_int32, _vp, C.c_int64, _vp]),
+    "vad_mel_frames": (C.c_int64, [C.POINTER(Mel), C.c_int64]),
+    "vad_scan_mel": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, C.POINTER(Mel), _f32p, _f32p, _f32p, _vp, C.c_int64, C.c_int32, C.c_int,
+                               C.c_int32, C.c_float, _f32p, C.c_int64]),
+    "vad_scan_mel_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, C.POINTER(Mel), _f32p, _f32p, _f32p, _vp, C.c_int64, C.c_int32,
+                                      C.c_int, C.c_int32, C.c_float, _vp, C.c_int64, _vp]),
     "vad_scan_render": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32,
                                   C.c_int32, C.c_float, C.c_int32, _vp, C.c_int64]),
     "vad_scan_render_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int,

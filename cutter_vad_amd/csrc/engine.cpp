@@ -45,6 +45,7 @@ extern "C" hipError_t vadk_launch_silero_v5_scan16(const vadk::StepParams *p, co
 extern "C" hipError_t vadk_launch_scan_cut(const vadk::CutArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_cut_gain(const vadk::CutArgs *a, const float *gains, hipStream_t stream);
 extern "C" hipError_t vadk_launch_seg_levels(const vadk::CutArgs *a, float clip, hipStream_t stream);
+extern "C" hipError_t vadk_launch_seg_mel(const vadk::MelArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_render(const vadk::RenderArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_cut_stereo(const vadk::CutArgs *a, const float *gains, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_render_stereo(const vadk::RenderArgs *a, hipStream_t stream);
@@ -185,6 +186,14 @@ struct vad_engine {
     // vad_scan_render: the workgroups of its output regions and its copy of the caller's ramp, as they were uploaded
     std::vector<vadk::RenderWork> render_work;
     std::vector<float> render_ramp;
+    // vad_scan_mel: the workgroups of its tiles, and the packed operator and filters (vad_layout.h: mel_op_index, mel_filter_index)
+    // in d_mel, operator first.  The pack is CACHED: mel_key / mel_src are the vad_mel and the caller's three arrays (op_re, op_im,
+    // filters, back to back) it was made from, and a call that brings the same bytes neither packs nor uploads again
+    std::vector<vadk::MelWork> mel_work;
+    std::vector<float> mel_src, mel_pack;
+    vad_mel mel_key{};
+    bool mel_packed = false;
+    float *d_mel = nullptr; size_t d_mel_cap = 0;
     // vad_segments_device / vad_scan_segments: the extraction's work area - out_start as int32 [n + 1] (the host copy as it was
     // uploaded), then the chunk counts - and, for vad_scan_segments, the items' CSR positions, the count and the retained table
     uint8_t *d_segwork = nullptr; size_t d_segwork_cap = 0;
@@ -911,7 +920,7 @@ void vad_engine_destroy(vad_engine *e) {
     weights_release(e->d_wstream16x);
     weights_release(e->d_wstream16y);
     void *bufs[] = {e->d_refine, e->d_refine_in, e->d_refine_out, e->d_tail_len, e->d_tailwork, e->d_reseg, e->d_resegtab, e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots, e->d_g711,
-                    e->d_audio, e->d_items, e->d_win, e->d_items_win, e->d_cut, e->d_cut_out, e->d_segwork, e->d_nsegs, e->d_segtab, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
+                    e->d_audio, e->d_items, e->d_win, e->d_items_win, e->d_cut, e->d_cut_out, e->d_mel, e->d_segwork, e->d_nsegs, e->d_segtab, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->scan_done) (void)hipEventDestroy(e->scan_done);
@@ -1707,6 +1716,8 @@ struct CutPlan {
     // vad_scan_cut_stereo / vad_scan_render_stereo: both channels of a two-channel block, interleaved.  Positions and counts stay
     // sample FRAMES, so the tables are the mono call's: an output frame has twice the bytes (ob), and the launcher is another
     bool stereo;
+    // vad_scan_mel: the segments are checked and tabled as for the levels (levels is set too); its workgroups are listed by mel_run
+    bool mel;
     // a. cut_check
     bool rate, rate_frames;
     uint32_t fshift;                         // log2 of the quads of a payload frame
@@ -1820,7 +1831,7 @@ int cut_check(vad_engine *e, CutPlan &c) {
                 return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 frames in one call", who);
             continue;
         }
-        if (c.render) continue;              // its workgroups follow the output, not the segments: render_regions
+        if (c.render || c.mel) continue;     // its workgroups follow the output, not the segments: render_regions (mel: the tiles)
         for (uint32_t q = 0; q < nq; q += vadk::CUT_WG_QUADS) e->cut_work.push_back(vadk::CutWork{(uint32_t)i, q});
         if (e->cut_work.size() > (size_t)INT32_MAX)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d samples in one call", who, VAD_CUT_WG_SAMPLES);
@@ -1839,9 +1850,9 @@ int cut_check(vad_engine *e, CutPlan &c) {
 int cut_block_device(vad_engine *e, CutPlan &c, const void *d_audio, void *d_out) {
     if (!d_audio) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", c.who);
     if (int rc = check_device_audio(e, c.who, d_audio, c.channels)) return rc;
-    if (c.levels && (reinterpret_cast<uintptr_t>(d_out) & 7))
+    if (c.levels && !c.mel && (reinterpret_cast<uintptr_t>(d_out) & 7))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the levels must be 8-byte aligned", c.who);
-    if (!c.levels && (reinterpret_cast<uintptr_t>(d_out) & 15))
+    if ((!c.levels || c.mel) && (reinterpret_cast<uintptr_t>(d_out) & 15))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output must be 16-byte aligned", c.who);
     c.d_audio = d_audio;
     c.d_out = d_out;
@@ -1876,6 +1887,7 @@ int cut_block_host(vad_engine *e, CutPlan &c, const void *audio) {
         if (int rc = ensure(e, e->d_audio, e->d_audio_cap, c.ab + 16)) return rc;
     }
     c.d_audio = e->d_audio;
+    if (c.mel) return VAD_OK;                // the rows of all segments: mel_run sizes them
     if (c.levels) {
         if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, (size_t)c.n * sizeof(vad_level))) return rc;
         c.d_out = e->d_cut_out;
@@ -2178,9 +2190,188 @@ int render_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *ite
     return VAD_OK;
 }
 
+// vad_mel's fields: 0 = all in range, else the number of the first that is not (1 n_fft .. 8 reserved)
+int mel_bad_field(const vad_mel *m) {
+    if (m->n_fft < 64 || m->n_fft > 1024 || (m->n_fft & 15)) return 1;
+    if (m->hop < 4 || m->hop > m->n_fft || (m->hop & 3)) return 2;
+    if (m->n_bins < 1 || m->n_bins > m->n_fft / 2 + 1) return 3;
+    if (m->n_mels < 1 || m->n_mels > 128) return 4;
+    if (m->pad != VAD_MEL_PAD_NONE && m->pad != VAD_MEL_PAD_REFLECT) return 5;
+    if (m->log != VAD_MEL_LINEAR && m->log != VAD_MEL_LN && m->log != VAD_MEL_LOG10) return 6;
+    if (m->log != VAD_MEL_LINEAR && !(std::isfinite(m->floor) && m->floor > 0.0f)) return 7;
+    if (m->reserved != 0) return 8;
+    return 0;
+}
+
+// the analysis frames of a segment of S samples (the header's M); the reflect rule S > n_fft / 2 is the caller's to check
+int64_t mel_frames(const vad_mel *m, int64_t S) {
+    const int64_t len = S + (m->pad == VAD_MEL_PAD_REFLECT ? m->n_fft : 0);
+    return len < m->n_fft ? 0 : (len - m->n_fft) / m->hop + 1;
+}
+
+// vad_scan_mel's own arguments, ahead of the block's and the items' checks
+int mel_check(vad_engine *e, const char *who, const vad_mel *m, const float *op_re, const float *op_im, const float *filters, int64_t out_rows) {
+    if (!m) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null vad_mel", who);
+    switch (mel_bad_field(m)) {
+        case 1: return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n_fft = %d must be a multiple of 16 from 64 to 1024", who, m->n_fft);
+        case 2: return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: hop = %d must be a multiple of 4 from 4 to n_fft = %d", who, m->hop, m->n_fft);
+        case 3: return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n_bins = %d must be 1 .. n_fft / 2 + 1 = %d", who, m->n_bins, m->n_fft / 2 + 1);
+        case 4: return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n_mels = %d must be 1 .. 128", who, m->n_mels);
+        case 5: return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: pad = %d is neither VAD_MEL_PAD_NONE nor VAD_MEL_PAD_REFLECT", who, m->pad);
+        case 6: return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: log = %d is none of VAD_MEL_LINEAR, VAD_MEL_LN, VAD_MEL_LOG10", who, m->log);
+        case 7: return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: floor = %g: a logarithm needs a finite floor > 0", who, (double)m->floor);
+        case 8: return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: vad_mel.reserved = %d must be 0", who, m->reserved);
+        default: break;
+    }
+    if (!op_re || !op_im) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null operator", who);
+    if (!filters) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null filters", who);
+    if (out_rows < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_rows = %lld is negative", who, (long long)out_rows);
+    return VAD_OK;
+}
+
+// the operator and the filters in fragment order in e->d_mel (vad_layout.h), zero-padded to whole tiles of 16 bins and 16 mels.
+// Cached against the bytes of the previous call: the same vad_mel and the same three arrays neither pack nor upload again (the
+// compare reads what a pack would read, and writes nothing)
+int mel_operator(vad_engine *e, const vad_mel *m, const float *op_re, const float *op_im, const float *filters, hipStream_t s) {
+    const size_t nb = (size_t)m->n_bins, no = (size_t)m->n_fft * nb, nf = (size_t)m->n_mels * nb;
+    const uint32_t bins_pad = vadk::mel_pad16((uint32_t)m->n_bins), mels_pad = vadk::mel_pad16((uint32_t)m->n_mels);
+    const bool same = e->mel_packed && e->mel_key.n_fft == m->n_fft && e->mel_key.n_bins == m->n_bins && e->mel_key.n_mels == m->n_mels &&
+                      e->mel_src.size() == 2 * no + nf && !std::memcmp(e->mel_src.data(), op_re, no * sizeof(float)) &&
+                      !std::memcmp(e->mel_src.data() + no, op_im, no * sizeof(float)) &&
+                      !std::memcmp(e->mel_src.data() + 2 * no, filters, nf * sizeof(float));
+    if (same) return VAD_OK;
+    e->mel_packed = false;
+    const size_t po = 2 * (size_t)m->n_fft * bins_pad, pf = (size_t)mels_pad * bins_pad;
+    if (int rc = ensure(e, e->d_mel, e->d_mel_cap, (po + pf) * sizeof(float))) return rc;
+    e->mel_src.resize(2 * no + nf);
+    std::memcpy(e->mel_src.data(), op_re, no * sizeof(float));
+    std::memcpy(e->mel_src.data() + no, op_im, no * sizeof(float));
+    std::memcpy(e->mel_src.data() + 2 * no, filters, nf * sizeof(float));
+    e->mel_pack.assign(po + pf, 0.0f);
+    for (uint32_t n = 0; n < (uint32_t)m->n_fft; ++n)
+        for (uint32_t k = 0; k < (uint32_t)m->n_bins; ++k) {
+            const size_t at = vadk::mel_op_index(n, k, (uint32_t)m->n_fft);
+            e->mel_pack[at] = op_re[(size_t)n * nb + k];
+            e->mel_pack[at + 1] = op_im[(size_t)n * nb + k];
+        }
+    for (uint32_t j = 0; j < (uint32_t)m->n_mels; ++j)
+        for (uint32_t k = 0; k < (uint32_t)m->n_bins; ++k) e->mel_pack[po + vadk::mel_filter_index(j, k, bins_pad)] = filters[(size_t)j * nb + k];
+    HIP_TRY(e, hipMemcpyAsync(e->d_mel, e->mel_pack.data(), (po + pf) * sizeof(float), hipMemcpyHostToDevice, s));
+    e->mel_key = *m;
+    e->mel_packed = true;
+    return VAD_OK;
+}
+
+// vad_scan_mel / _device with e->mu held: the call's own checks, cut_check's refusals under this name (the segments tabled as for
+// the levels: the sample range once, no out_sample), the frames and rows of every segment and one workgroup per tile of MEL_TILE
+// frames, then the block as the cuts find it, the operator (mel_operator), one upload of the tables - segments, workgroups, in this
+// order in e->d_cut - and one launch.
+int mel_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re, const float *op_im,
+            const float *filters, const void *audio, int64_t audio_samples, int32_t channels, int fmt, int32_t hop, float thr, float *out,
+            int64_t out_rows, void *stream) {
+    hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    if (int rc = mel_check(e, who, m, op_re, op_im, filters, out_rows)) return rc;
+    CutPlan c{who, items, n, audio_samples, channels, fmt, hop, thr, VAD_CUT_RANGE, VAD_CUT_F32, 0, 0, 0, nullptr, true, 0.0f};
+    c.mel = true;
+    if (int rc = cut_check(e, c)) return rc;
+    if (n == 0) return VAD_OK;
+    e->mel_work.clear();
+    int64_t rows = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        vadk::CutSeg &sg = e->cut_segs[(size_t)i];
+        const int64_t S = (int64_t)sg.nquads << 2;
+        if (m->pad == VAD_MEL_PAD_REFLECT && S <= m->n_fft / 2)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld has %lld samples: reflect padding needs more than n_fft / 2 = %d",
+                           who, (long long)i, (long long)S, m->n_fft / 2);
+        const int64_t M = mel_frames(m, S);
+        sg.quad_out = (uint64_t)rows;
+        rows += M;
+        if ((int64_t)e->mel_work.size() + (M + vadk::MEL_TILE - 1) / vadk::MEL_TILE > (int64_t)INT32_MAX)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d frames in one call", who, vadk::MEL_TILE);
+        for (int64_t f = 0; f < M; f += vadk::MEL_TILE) e->mel_work.push_back(vadk::MelWork{(uint32_t)i, (uint32_t)f});
+    }
+    if (rows > out_rows)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_rows = %lld, the segments have %lld rows", who, (long long)out_rows,
+                       (long long)rows);
+    if (rows > 0 && !out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    const size_t out_bytes = (size_t)rows * (size_t)m->n_mels * sizeof(float);
+    if (dev) {
+        if (int rc = cut_block_device(e, c, audio, out)) return rc;
+    } else {
+        if (int rc = cut_block_host(e, c, audio)) return rc;
+        if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, out_bytes)) return rc;
+        c.d_out = e->d_cut_out;
+    }
+    const size_t sb = sizeof(vadk::CutSeg) * e->cut_segs.size(), wb = sizeof(vadk::MelWork) * e->mel_work.size();
+    if (int rc = ensure(e, e->d_cut, e->d_cut_cap, sb + wb)) return rc;
+    if (int rc = mel_operator(e, m, op_re, op_im, filters, s)) return rc;
+    if (!dev && audio) {
+        HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, c.ab, hipMemcpyHostToDevice, s));
+        set_resident(e, c.ab, c.channels, c.fmt, 0);
+    }
+    HIP_TRY(e, hipMemcpyAsync(e->d_cut, e->cut_segs.data(), sb, hipMemcpyHostToDevice, s));
+    if (wb) HIP_TRY(e, hipMemcpyAsync(e->d_cut + sb, e->mel_work.data(), wb, hipMemcpyHostToDevice, s));
+    vadk::MelArgs a{};
+    a.audio = c.d_audio;
+    a.out = static_cast<float *>(c.d_out);
+    a.segs = reinterpret_cast<const vadk::CutSeg *>(e->d_cut);
+    a.work = reinterpret_cast<const vadk::MelWork *>(e->d_cut + sb);
+    a.bins_pad = vadk::mel_pad16((uint32_t)m->n_bins);
+    a.op = e->d_mel;
+    a.filters = e->d_mel + 2 * (size_t)m->n_fft * a.bins_pad;
+    a.audio_bytes = (uint32_t)c.ab;
+    a.nwork = (uint32_t)e->mel_work.size();
+    a.n_fft = (uint32_t)m->n_fft;
+    a.hop = (uint32_t)m->hop;
+    a.n_mels = (uint32_t)m->n_mels;
+    a.pad = m->pad;
+    a.log = m->log;
+    a.floor = m->floor;
+    a.thresh = thr;
+    a.fmt = fmt;
+    a.channels = channels;
+    const hipError_t r = vadk_launch_seg_mel(&a, s);
+    const int rc = r != hipSuccess ? e->hip_fail(r, "kernel launch (segment mel)") : VAD_OK;
+    if (dev) {
+        // the launch reads the engine's tables: the next scan or cut waits for it, as behind vad_scan_device
+        if (int rc2 = scan_mark_pending(e, s)) return rc2;
+        return rc;
+    }
+    if (rc) return rc;
+    if (out_bytes) HIP_TRY(e, hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    return VAD_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t vad_mel_frames(const vad_mel *m, int64_t nsamples) {
+    if (!m || mel_bad_field(m) || nsamples < 0 || nsamples > (INT64_MAX >> 1)) return -1;
+    if (m->pad == VAD_MEL_PAD_REFLECT && nsamples <= m->n_fft / 2) return -1;
+    return mel_frames(m, nsamples);
+}
+
+int vad_scan_mel(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re, const float *op_im, const float *filters,
+                 const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t hop, float denoise_thresh, float *out,
+                 int64_t out_rows) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return mel_run(e, false, "vad_scan_mel", items, n, m, op_re, op_im, filters, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, out,
+                   out_rows, nullptr);
+}
+
+int vad_scan_mel_device(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re, const float *op_im,
+                        const float *filters, const void *d_audio, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t hop,
+                        float denoise_thresh, float *d_out, int64_t out_rows, void *stream) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return mel_run(e, true, "vad_scan_mel_device", items, n, m, op_re, op_im, filters, d_audio, audio_samples, channels, frame_fmt, hop,
+                   denoise_thresh, d_out, out_rows, stream);
+}
 
 int64_t vad_cut_samples(const vad_engine *e, int64_t nframes, int32_t hop, int32_t layout) {
     if (!e || nframes < 1 || hop < 4 || (hop & 3) || (layout != VAD_CUT_FRAMES && layout != VAD_CUT_RANGE)) return -1;

@@ -16,6 +16,7 @@
 //   One k-iteration j consumes quad 2j (lanes 0-31) and quad 2j+1 (lanes 32-63): MFMA
 //   k-step i in 0..3 contracts channel 8j+i (lower half-wave) and 8j+4+i (upper half).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #if !defined(__HIPCC__) && !defined(__host__)
 #define __host__
@@ -293,6 +294,60 @@ struct CutArgs {
     int32_t out_fmt;          // 0 = int16 PCM, 1 = float32
     float thresh;             // denoise gate, < 0 = off
 };
+
+// log-mel features of finished segments (csrc/scan_mel.hip: vadk_seg_mel; vad_scan_mel).  A workgroup of MEL_THREADS threads
+// serves MEL_TILE consecutive analysis frames of ONE segment; the host lists the workgroups (MelWork) next to the segments, which
+// are CutSeg of the sample range once with quad_out = the segment's first ROW of the output.  Both matrix products run on
+// v_mfma_f32_16x16x4_f32 and take one operand from a stream the host packed into fragment order (lane l of a 16 x 16 x 4 step
+// holds row / column l & 15 and k = l >> 4), one float4 per lane and block of 64 lanes:
+//   operator  [bin tile bt][pair of k-steps sp][lane]  {re, im}[n = 8 sp + kq][bin], {re, im}[n = 8 sp + 4 + kq][bin]
+//   filters   [mel tile mt][four k-steps sp][lane]     filters[mel][k = 16 sp + 4 t + kq], t = 0 .. 3
+// with bin = 16 bt + (l & 15), mel = 16 mt + (l & 15), kq = l >> 4; bins and mels past the caller's counts are zeros of the pack.
+constexpr int MEL_THREADS = 256;
+constexpr int MEL_TILE = 16;
+struct MelWork {
+    uint32_t seg;             // index into the segment table
+    uint32_t frame0;          // first analysis frame of this workgroup's tile, a multiple of MEL_TILE
+};
+static_assert(sizeof(MelWork) == 8, "MelWork layout");
+__host__ __device__ inline uint32_t mel_pad16(uint32_t v) { return (v + 15u) & ~15u; }
+// float index of op_re[n][bin] in the packed operator (op_im: + 1)
+__host__ __device__ inline size_t mel_op_index(uint32_t n, uint32_t bin, uint32_t n_fft) {
+    const uint32_t lane = ((n & 3u) << 4) | (bin & 15u);
+    return (((size_t)(bin >> 4) * (n_fft >> 3) + (n >> 3)) * 64u + lane) * 4u + ((n >> 2) & 1u) * 2u;
+}
+// float index of filters[mel][k] in the packed filters
+__host__ __device__ inline size_t mel_filter_index(uint32_t mel, uint32_t k, uint32_t bins_pad) {
+    const uint32_t lane = ((k & 3u) << 4) | (mel & 15u);
+    return (((size_t)(mel >> 4) * (bins_pad >> 4) + (k >> 4)) * 64u + lane) * 4u + ((k >> 2) & 3u);
+}
+// The tile's samples in LDS: local sample i of the tile's span lies at float i + skew * (i / hop) with skew = (4 - hop) mod 64, so
+// that frame j's sample n is j * (hop + skew) + n + skew * (n / hop) and the 16 frames x 4 k of one B fragment (stride hop + skew =
+// 4 mod 64 between frames, 1 between k) fall into 64 different banks, whatever the hop; behind them P as [bin][MEL_TILE]
+__host__ __device__ inline uint32_t mel_skew(uint32_t hop) { return (4u - (hop & 63u)) & 63u; }
+__host__ __device__ inline uint32_t mel_lds_span_floats(uint32_t n_fft, uint32_t hop) {
+    const uint32_t span = (MEL_TILE - 1) * hop + n_fft;
+    return ((span + hop - 1) / hop) * (hop + mel_skew(hop));
+}
+struct MelArgs {
+    const void *audio;        // the block, in its wire format
+    float *out;               // [rows][n_mels]
+    const CutSeg *segs;       // quad_out: the segment's first row
+    const MelWork *work;      // [nwork]: one entry per workgroup
+    const float *op;          // the packed operator: 2 n_fft bins_pad floats
+    const float *filters;     // the packed filters: mels_pad bins_pad floats
+    uint32_t audio_bytes;     // the buffer descriptor's range
+    uint32_t nwork;
+    uint32_t n_fft, hop;      // of the analysis (vad_mel), not the scan's
+    uint32_t bins_pad;        // n_bins in whole tiles of 16
+    uint32_t n_mels;
+    int32_t pad, log;         // VAD_MEL_PAD_*, VAD_MEL_*
+    float floor;
+    float thresh;             // denoise gate, < 0 = off
+    int32_t fmt;              // vad_frame_format
+    int32_t channels;         // 1 or 2
+};
+static_assert(sizeof(MelArgs) == 96, "MelArgs layout");
 
 // one finished piece of audio out of a scanned block (csrc/scan_render.hip: vadk_scan_render; vad_scan_render).  The kernel is
 // driven by the OUTPUT: the host sweeps the segments' output spans into regions - maximal runs of output quads covered by the same

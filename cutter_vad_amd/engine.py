@@ -11,6 +11,7 @@ exception classes with the same message prefixes (SURVEY §8 b).
 from __future__ import annotations
 
 import ctypes as C
+import os
 import threading
 from typing import List, Optional, Sequence, Tuple
 
@@ -60,6 +61,7 @@ class Engine:
         self._gather_fn = int(C.cast(self._lib.vad_tick_push_gather, C.c_void_p).value)
         self._rate_gather_fn = int(C.cast(self._lib.vad_tick_push_rate_gather, C.c_void_p).value)
         self._h = C.c_void_p()
+        self._pid = os.getpid()             # the process that owns the handle: see close()
         self._tickets = {}                  # ticket -> the buffers a pipelined call still reads (submit / collect)
         self._scan_block = None             # scan(): the page-locked block the recordings are packed into ...
         self._scan_lock = threading.RLock()  # ... held from the packing to the return of vad_scan: engines are shared between threads
@@ -87,7 +89,9 @@ class Engine:
     def close(self) -> None:
         h, self._h = self._h, C.c_void_p()
         self._scan_block = None             # the engine releases its page-locked blocks
-        if h:
+        # An engine inherited through fork is the parent's: its streams, events and device memory mean nothing in the child, and
+        # destroying them there crashed whenever the child's garbage collector found such an engine.  The child only drops the handle.
+        if h and getattr(self, "_pid", None) == os.getpid():
             self._lib.vad_engine_destroy(h)
 
     def __del__(self):
@@ -840,6 +844,81 @@ class Engine:
         thr = -1.0 if denoise is None else float(denoise)
         self._check(self._lib.vad_scan_levels_device(self._h, items, len(start) - 1, d_audio or None, int(audio_samples), int(channels), int(fmt),
                                                      sr or 0, hop, thr, float(clip), d_levels or None, stream or None))
+
+    # ------------------------------------------------------------------ log-mel features
+    @staticmethod
+    def _mel_arrays(spec):
+        """``spec``: an object with ``operators()`` (``cutter_vad_amd.scan.MelSpec``) or the tuple that returns -
+        ``(fields, op_re [n_fft, n_bins], op_im, filters [n_mels, n_bins])`` with ``fields`` a dict of ``vad_mel``'s fields (``pad`` /
+        ``log`` as names or numbers) -> (_ffi.Mel, op_re, op_im, filters) as contiguous float32"""
+        fields, op_re, op_im, filters = spec.operators() if hasattr(spec, "operators") else spec
+        op_re, op_im, filters = (np.ascontiguousarray(np.asarray(a, np.float32)) for a in (op_re, op_im, filters))
+        if isinstance(fields, _ffi.Mel):
+            m = fields
+        else:
+            f = dict(fields)
+            pad, log = f.get("pad", "reflect"), f.get("log", "log10")
+            pad = Engine._cut_enum(_ffi.MEL_PADS, "pad", pad) if isinstance(pad, str) else int(pad)
+            log = Engine._cut_enum(_ffi.MEL_LOGS, "log", log) if isinstance(log, str) else int(log)
+            m = _ffi.Mel(int(f["n_fft"]), int(f["hop"]), int(f.get("n_bins", op_re.shape[-1])), int(f.get("n_mels", filters.shape[0])),
+                         pad, log, float(f.get("floor", 1e-10)), 0)
+        if op_re.shape != (m.n_fft, m.n_bins) or op_im.shape != op_re.shape or filters.shape != (m.n_mels, m.n_bins):
+            raise AudioProcessingError(f"Model prediction failed: mel: op_re / op_im are [n_fft, n_bins] = [{m.n_fft}, {m.n_bins}] and filters "
+                                       f"[n_mels, n_bins] = [{m.n_mels}, {m.n_bins}], got {op_re.shape}, {op_im.shape}, {filters.shape}")
+        return m, op_re, op_im, filters
+
+    def mel_frames(self, spec, nsamples: int) -> int:
+        """Analysis frames of a segment of ``nsamples`` samples under ``spec`` (``vad_mel_frames``); -1: bad arguments."""
+        m = self._mel_arrays(spec)[0]
+        return int(self._lib.vad_mel_frames(C.byref(m), int(nsamples)))
+
+    def _mel_rows(self, m, segments, hop: int) -> np.ndarray:
+        start = np.zeros(len(segments) + 1, np.int64)
+        for i, sg in enumerate(segments):
+            rows = int(self._lib.vad_mel_frames(C.byref(m), max(0, (int(sg[2]) - 1) * hop + self.frame_samples))) if len(sg) > 2 else 0
+            start[i + 1] = start[i] + max(rows, 0)      # (-1: the call itself refuses the segment, by name)
+        return start
+
+    def mel(self, segments, spec, hop: Optional[int] = None, denoise: Optional[float] = 0.01, audio=None, law: Optional[str] = None,
+            i16_scale: int = 32767):
+        """Log-mel frames of finished segments (``vad_scan_mel``), computed on the GPU from the block: ``segments`` as in ``cut``,
+        ``spec`` a ``cutter_vad_amd.scan.MelSpec`` or ``(fields, op_re, op_im, filters)`` (``_mel_arrays``).  -> ``(features
+        [rows, n_mels] float32, start [n + 1])``: segment i's frames are ``features[start[i]:start[i + 1]]``, computed from exactly
+        the float32 values ``cut(segments, layout="range", out="f32")`` with the same arguments gives.  ``hop`` is the SCAN's hop
+        (the segments' frames), not the analysis hop, which is the spec's.  ``audio``, ``law``, ``i16_scale`` and the
+        ``scan_session()`` rule as in ``cut``; blocks at the engine's own rate only.  Segments may share samples."""
+        m, op_re, op_im, filters = self._mel_arrays(spec)
+        with self._scan_lock:
+            sr, total, channels, fmt, ptr, _keep = self._cut_block("mel", audio, law, i16_scale, None)
+            if sr is not None:
+                raise AudioProcessingError(f"Model prediction failed: mel(audio=None): the block of the last scan is at {sr} Hz; features are "
+                                           "computed from blocks at the engine's own rate")
+            hop = self.frame_samples // 2 if hop is None else int(hop)
+            segs = [tuple(sg) for sg in segments]
+            items, _ = self._cut_items(segs, hop, _ffi.VAD_CUT_RANGE, channels)
+            start = self._mel_rows(m, segs, hop)
+            out = np.empty((int(start[-1]), m.n_mels), np.float32)
+            thr = -1.0 if denoise is None else float(denoise)
+            self._check(self._lib.vad_scan_mel(self._h, items, len(segs), C.byref(m), _ptr(op_re, C.c_float), _ptr(op_im, C.c_float),
+                                               _ptr(filters, C.c_float), ptr, total, channels, fmt, hop, thr,
+                                               out.ctypes.data_as(C.POINTER(C.c_float)), int(start[-1])))
+        return out, start
+
+    def mel_device(self, segments, spec, d_audio: int, audio_samples: int, d_out: int, out_rows: int, hop: Optional[int] = None,
+                   fmt: int = _ffi.VAD_FMT_F32, channels: int = 1, denoise: Optional[float] = 0.01, stream: int = 0) -> np.ndarray:
+        """``mel`` on device pointers (integers; ``vad_scan_mel_device``): the block at ``d_audio`` as ``cut_device`` takes it, the
+        rows to ``d_out`` (16-byte aligned, room for ``out_rows`` rows of ``n_mels`` float32).  The operators stay host arrays, read
+        before the call returns.  Asynchronous on ``stream``.  -> start [n + 1], the segments' first rows."""
+        m, op_re, op_im, filters = self._mel_arrays(spec)
+        hop = self.frame_samples // 2 if hop is None else int(hop)
+        segs = [tuple(sg) for sg in segments]
+        items, _ = self._cut_items(segs, hop, _ffi.VAD_CUT_RANGE, int(channels))
+        start = self._mel_rows(m, segs, hop)
+        thr = -1.0 if denoise is None else float(denoise)
+        self._check(self._lib.vad_scan_mel_device(self._h, items, len(segs), C.byref(m), _ptr(op_re, C.c_float), _ptr(op_im, C.c_float),
+                                                  _ptr(filters, C.c_float), d_audio or None, int(audio_samples), int(channels), int(fmt), hop,
+                                                  thr, d_out or None, int(out_rows), stream or None))
+        return start
 
     # ------------------------------------------------------------------ rendered audio
     @staticmethod

@@ -659,3 +659,151 @@ def render_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConf
                     lists.append((pcm.copy(), timeline))
             out[i] = lists if split else lists[0]
     return out
+
+
+# ---------------------------------------------------------------------------------------------- log-mel features
+def _hz_to_mel(f):
+    """Slaney's scale (Auditory Toolbox): linear below 1 kHz, 3 mel per 200 Hz; logarithmic above, 27 steps per factor 6.4"""
+    f = np.asarray(f, np.float64)
+    return np.where(f >= 1000.0, 15.0 + np.log(np.maximum(f, 1e-300) / 1000.0) * (27.0 / np.log(6.4)), f * (3.0 / 200.0))
+
+
+def _mel_to_hz(m):
+    m = np.asarray(m, np.float64)
+    return np.where(m >= 15.0, 1000.0 * np.exp((m - 15.0) * (np.log(6.4) / 27.0)), m * (200.0 / 3.0))
+
+
+def mel_filterbank(sample_rate: int, n_fft: int, n_mels: int, fmin: float = 0.0, fmax: Optional[float] = None) -> np.ndarray:
+    """Slaney-style triangular mel filters ``[n_mels, n_fft // 2 + 1]`` as float64.  With ``mel(f) = 3 f / 200`` below 1 kHz and
+    ``15 + 27 ln(f / 1000) / ln 6.4`` above, the ``n_mels + 2`` edges ``c_0 .. c_{n_mels + 1}`` are equally spaced in mel between
+    ``fmin`` and ``fmax`` (default ``sample_rate / 2``); filter ``j`` at bin frequency ``f_k = k sample_rate / n_fft`` is
+
+        ``w_j[k] = 2 / (c_{j+2} - c_j) * max(0, min((f_k - c_j) / (c_{j+1} - c_j), (c_{j+2} - f_k) / (c_{j+2} - c_{j+1})))``
+
+    - one triangle from ``c_j`` up to 1 at ``c_{j+1}`` and down to ``c_{j+2}``, scaled by ``2 / (c_{j+2} - c_j)`` so that the
+    CONTINUOUS triangle has area 1 in Hz ("area normalisation": a flat spectrum gives roughly the same energy in every band).  The
+    sampled row sums to about ``n_fft / sample_rate`` (the area over the bin spacing) where the triangle spans several bins."""
+    sample_rate, n_fft, n_mels = int(sample_rate), int(n_fft), int(n_mels)
+    fmax = sample_rate / 2.0 if fmax is None else float(fmax)
+    if not (0.0 <= float(fmin) < fmax <= sample_rate / 2.0) or n_mels < 1:
+        raise ConfigurationError("fmin", repr((fmin, fmax, n_mels)), f"mel_filterbank: 0 <= fmin < fmax <= sample_rate / 2 and n_mels >= 1, got "
+                                 f"fmin = {fmin}, fmax = {fmax}, n_mels = {n_mels}")
+    c = _mel_to_hz(np.linspace(_hz_to_mel(float(fmin)), _hz_to_mel(fmax), n_mels + 2))
+    f = np.arange(n_fft // 2 + 1, dtype=np.float64) * (sample_rate / float(n_fft))
+    up = (f[None, :] - c[:-2, None]) / (c[1:-1] - c[:-2])[:, None]
+    down = (c[2:, None] - f[None, :]) / (c[2:] - c[1:-1])[:, None]
+    return np.maximum(0.0, np.minimum(up, down)) * (2.0 / (c[2:] - c[:-2]))[:, None]
+
+
+@dataclass(frozen=True)
+class MelSpec:
+    """A log-mel front end for ``Engine.mel`` / ``features_recordings``: frames of ``n_fft`` samples every ``hop``, a periodic
+    ``window`` (``"hann"`` or ``"rect"``), ``pad`` ``"reflect"`` (``torch.stft(center=True)``) or ``"none"``, the power spectrum
+    through ``mel_filterbank(sample_rate, n_fft, n_mels, fmin, fmax)``, then ``log`` ``"log10"``, ``"ln"`` or ``"linear"`` of
+    ``max(E, floor)``.  The defaults are Whisper's geometry at 16 kHz; its two remaining lines are the caller's, per clip::
+
+        x = np.maximum(features, features.max() - 8.0)
+        x = (x + 4.0) / 4.0
+    """
+    sample_rate: int
+    n_fft: int = 400
+    hop: int = 160
+    n_mels: int = 80
+    fmin: float = 0.0
+    fmax: Optional[float] = None
+    window: str = "hann"
+    pad: str = "reflect"
+    log: str = "log10"
+    floor: float = 1e-10
+
+    def operators(self):
+        """-> ``(fields, op_re, op_im, filters)`` as ``Engine.mel`` takes them: ``fields`` the ``vad_mel`` fields as a dict,
+        ``op_re[n][k] = w[n] cos(2 pi ((n k) mod n_fft) / n_fft)``, ``op_im[n][k] = -w[n] sin(...)`` with the periodic window
+        ``w[n] = 0.5 - 0.5 cos(2 pi n / n_fft)`` - the angle reduced in integers, everything in float64, rounded once to float32."""
+        if self.window not in ("hann", "rect"):
+            raise ConfigurationError("window", repr(self.window), f"MelSpec: window is 'hann' or 'rect', got {self.window!r}")
+        if self.pad not in _ffi.MEL_PADS or self.log not in _ffi.MEL_LOGS:
+            raise ConfigurationError("pad", repr((self.pad, self.log)), f"MelSpec: pad is one of {sorted(_ffi.MEL_PADS)} and log one of "
+                                     f"{sorted(_ffi.MEL_LOGS)}, got {self.pad!r}, {self.log!r}")
+        n_fft, n_bins = int(self.n_fft), int(self.n_fft) // 2 + 1
+        n = np.arange(n_fft, dtype=np.int64)
+        w = 0.5 - 0.5 * np.cos(2.0 * np.pi * n / n_fft) if self.window == "hann" else np.ones(n_fft)
+        ang = 2.0 * np.pi * ((n[:, None] * np.arange(n_bins, dtype=np.int64)[None, :]) % n_fft).astype(np.float64) / n_fft
+        filters = mel_filterbank(self.sample_rate, n_fft, self.n_mels, self.fmin, self.fmax)
+        fields = {"n_fft": n_fft, "hop": int(self.hop), "n_bins": n_bins, "n_mels": int(self.n_mels), "pad": self.pad, "log": self.log,
+                  "floor": float(self.floor)}
+        return fields, (w[:, None] * np.cos(ang)).astype(np.float32), (-w[:, None] * np.sin(ang)).astype(np.float32), filters.astype(np.float32)
+
+
+def _need_mel(engine, who: str) -> None:
+    if not hasattr(engine, "mel"):
+        raise ConfigurationError("mel", "given", f"{who} needs an engine with mel (the features are computed from the block a scan left "
+                                 f"on the GPU), {type(engine).__name__} has none")
+
+
+def features_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, config: Optional[VADConfig] = None, engine=None,
+                        hop: Optional[int] = None, law: Optional[str] = None, channel="mix", open_end: bool = False,
+                        refine: Optional[SegmentRefine] = None) -> List:
+    """``scan_recordings`` with each finished segment's log-mel frames: per recording ``[(start_sample, end_sample,
+    features [M, n_mels] float32), ...]`` (per channel for ``"split"``, as there).  The features are those of the samples
+    ``cut_recordings(layout="range")`` cuts - decoded, mixed and gated as the model read them - computed on the GPU from the block
+    the scan left there (one scan and one ``Engine.mel(audio=None)`` under ``Engine.scan_session()``; two of each for a corpus of 1-D
+    and 2-D recordings): no sample crosses the link back.  ``hop`` is the scan's; the analysis hop is ``spec.hop``.
+    ``open_end`` and ``refine`` as in ``scan_recordings``.  An engine object without ``mel``: ``ConfigurationError``; so is a
+    ``spec.sample_rate`` other than the engine's (recordings at other rates are not resampled for features)."""
+    from .pool import default_pool, resolve_model_path
+    who = "features_recordings"
+    split = isinstance(channel, str) and channel == "split"
+    if not (channel in ("mix", "split") if isinstance(channel, str) else isinstance(channel, (int, np.integer)) and int(channel) in (0, 1)):
+        raise ConfigurationError("channel", repr(channel), f"{who}: channel is 'mix', 0, 1 or 'split' for the whole corpus, got {channel!r}")
+    cfg = config or VADConfig()
+    if engine is None:
+        engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
+    _need_mel(engine, who)
+    if open_end:
+        _need_tails(engine, who)
+    if refine is not None:
+        _need_refine(engine, who)
+    if int(spec.sample_rate) != int(engine.sample_rate):
+        raise ConfigurationError("sample_rate", repr(spec.sample_rate), f"{who}: the spec is for {spec.sample_rate} Hz, the engine's blocks "
+                                 f"are at {engine.sample_rate} Hz")
+    frame = engine.frame_samples
+    if cfg.buffer_size != frame:
+        raise ConfigurationError(f"{who} frames at the model's frame size: buffer_size = {cfg.buffer_size}, the engine's frames have "
+                                 f"{frame} samples")
+    hop = frame // 2 if hop is None else int(hop)
+    recordings = [np.asarray(r) for r in recordings]
+    if not recordings:
+        return []
+    arrays = spec.operators()
+    denoise = 0.01 if cfg.enable_denoising else None
+    out: List = [None] * len(recordings)
+    for two in (False, True):
+        idx = [i for i, r in enumerate(recordings) if (r.ndim == 2) == two]
+        if not idx:
+            continue
+        per = 2 if two and split else 1
+        chans = (0, 1) if per == 2 else (channel if two else 0,)
+        slots = engine.open_streams(len(idx) * per)
+        try:
+            engine.set_thresholds_many(slots, _thresholds_of(cfg))
+            with engine.scan_session():
+                ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, denoise, channel, open_end=open_end,
+                                      refine=refine)
+                table = _cut_table(engine, ranges, chans, frame, hop)
+                if table:
+                    data, start = engine.mel(table, arrays, hop=hop, denoise=denoise)
+        finally:
+            for s in slots:
+                engine.close_stream(int(s))
+        j = 0
+        for i, rc in zip(idx, ranges):
+            lists = []
+            for rg in rc:
+                one = []
+                for a, b, *_ in rg:
+                    one.append((a, b, data[start[j]:start[j + 1]].copy()))
+                    j += 1
+                lists.append(one)
+            out[i] = lists if split else lists[0]
+    return out

@@ -756,6 +756,70 @@ VAD_API int vad_scan_cut_gain_device(vad_engine *e, const vad_cut_item *items, i
                                      int64_t out_samples, void *stream);
 
 /*
+ * Log-mel features: what an ASR front end, a speaker-embedding model or a classifier takes instead of PCM, computed from the block
+ * a scan left on the GPU.  Whisper's front end is n_fft = 400, hop = 160, a Hann window, reflect padding, 80 or 128 mel bins and
+ * log10 with a floor; Kaldi-style recipes are other geometries of the same shape.  Without this call the samples cross the link as
+ * float32 (vad_scan_cut, VAD_CUT_RANGE, VAD_CUT_F32) and the host runs an STFT.
+ *
+ * vad_scan_mel: a packed float32 matrix out[rows][n_mels] holding the frames of every listed segment.  THE RULE: segment i's values
+ * v[0 .. S - 1] are exactly the float32 values that vad_scan_cut with VAD_CUT_RANGE, VAD_CUT_F32 and the same arguments would write
+ * for the item - decoded, channel-selected and gated; S = vad_cut_samples(e, nframes, hop, VAD_CUT_RANGE), where `hop` is the
+ * SCAN's hop (the last hop argument), not m->hop.  out_sample is NOT read, so two items may name the same samples.
+ *   Padding.  VAD_MEL_PAD_NONE: p = v.  VAD_MEL_PAD_REFLECT: p has S + n_fft samples, p[j] = v[r(j - n_fft / 2)] with r(i) = -i for
+ * i < 0 and 2 (S - 1) - i for i >= S - numpy's 'reflect', torch.stft's center = True.  It needs S > n_fft / 2; otherwise the call
+ * returns VAD_ERR_INVALID_ARG and names the segment.
+ *   Frames.  M = len(p) < n_fft ? 0 : (len(p) - n_fft) / m->hop + 1 (vad_mel_frames).  A segment with M = 0 is legal under
+ * VAD_MEL_PAD_NONE and writes nothing.
+ *   The transform.  re[f][k] = sum over n of p[f * m->hop + n] * op_re[n][k], im the same with op_im; P = re^2 + im^2;
+ * E[f][j] = sum over k of filters[j][k] * P[f][k]; out = E (VAD_MEL_LINEAR), ln(max(E, floor)) (VAD_MEL_LN) or
+ * log10(max(E, floor)) (VAD_MEL_LOG10).  Everything is float32; the order of the sums is the kernel's own.  With u = 2^-24,
+ *     |E - E_exact| <= (2 n_fft + n_bins + 8) u D,   D[f][j] = sum_k filters[j][k] (sum_n |p op_re| + sum_n |p op_im|)^2
+ * - the forward error of two chained float32 dot products around a square in ANY order of summation - and where every intermediate
+ * value is an integer multiple of a power of two below 2^24 in magnitude the result is exact.  The logarithm is the hardware's
+ * log2 (1 ulp) times a constant.
+ *   Window and DFT basis are the caller's: they are folded into op_re / op_im ([n_fft][n_bins], row-major), so n_fft = 400 costs
+ * what it is and not what 512 would.  filters is [n_mels][n_bins].  All three are HOST arrays in both forms, as gains is.
+ *   Rows are packed in item order: segment i's first row is the sum of M_j over j < i, a row is n_mels floats.  out_rows smaller
+ * than the total is refused; rows past the total are not written.
+ *   Blocks at the engine's own rate only (there is no sr_in); audio == NULL names the resident block as in vad_scan_cut - a
+ * resident rate block is refused in the cut's words - and with an audio the call uploads it, and it becomes the resident block.
+ * Works on every engine, Silero V4 and VAD_ENGINE_SHARED_GPU included: no model kernel runs, no stream is touched.  The call first
+ * waits for earlier *_device launches that read the engine's tables.
+ *   A float32 block with non-finite samples: the rows whose frames hold one are unspecified, other rows are unaffected.
+ *   No float atomics, every sum in a fixed order: two calls with the same arguments give the same bytes.
+ *   VAD_ERR_INVALID_ARG, each with a message and nothing written: every refusal of vad_scan_cut that concerns the block and the
+ * items, in the same words under this function's name; a null m; each field of vad_mel out of its range; a floor that is not
+ * finite or not > 0 with a log; a null op_re, op_im or filters; a reflect-padded segment with S <= n_fft / 2; out_rows < 0 or
+ * below the total; a null out with rows to write.  n == 0: VAD_OK.
+ *   vad_scan_mel_device: d_audio as vad_scan_cut_device takes it, d_out (16-byte aligned, out_rows rows) on the engine's GPU;
+ * enqueues the kernel on `stream` (NULL = the engine's own) and returns.
+ *   vad_mel_frames: M for a segment of nsamples samples; -1 for a bad vad_mel, a negative nsamples, or reflect padding with
+ * nsamples <= n_fft / 2.
+ *   VAD_ABI_VERSION is unchanged: the presence of vad_scan_mel is how a caller detects the feature.
+ */
+enum { VAD_MEL_PAD_NONE = 0, VAD_MEL_PAD_REFLECT = 1 };
+enum { VAD_MEL_LINEAR = 0, VAD_MEL_LN = 1, VAD_MEL_LOG10 = 2 };
+typedef struct vad_mel {
+    int32_t n_fft;     /* samples of one analysis frame: 64 .. 1024, a multiple of 16 */
+    int32_t hop;       /* samples between analysis frames: 4 .. n_fft, a multiple of 4 */
+    int32_t n_bins;    /* columns of op_re / op_im / filters: 1 .. n_fft / 2 + 1 */
+    int32_t n_mels;    /* 1 .. 128 */
+    int32_t pad;       /* VAD_MEL_PAD_* */
+    int32_t log;       /* VAD_MEL_* */
+    float   floor;     /* log != VAD_MEL_LINEAR: finite and > 0; VAD_MEL_LINEAR: not read */
+    int32_t reserved;  /* 0 */
+} vad_mel;
+VAD_API int64_t vad_mel_frames(const vad_mel *m, int64_t nsamples);
+VAD_API int vad_scan_mel(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re /*[n_fft][n_bins]*/,
+                         const float *op_im /*[n_fft][n_bins]*/, const float *filters /*[n_mels][n_bins]*/,
+                         const void *audio /*or NULL*/, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t hop,
+                         float denoise_thresh, float *out /*[out_rows][n_mels]*/, int64_t out_rows);
+VAD_API int vad_scan_mel_device(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re /*host*/,
+                                const float *op_im /*host*/, const float *filters /*host*/, const void *d_audio,
+                                int64_t audio_samples, int32_t channels, int frame_fmt, int32_t hop, float denoise_thresh,
+                                float *d_out /*on the GPU: [out_rows][n_mels]*/, int64_t out_rows, void *stream);
+
+/*
  * Rendered audio: one finished piece of audio per call - the segments of a block faded at their edges, crossfaded where two of
  * them share output samples, joined, everything else silence.  The two standard products of a VAD come out of it by where the caller
  * places the segments: silence removal (the segments back to back, neighbours overlapping by the ramp or a fixed pause apart) and

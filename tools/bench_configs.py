@@ -1242,6 +1242,153 @@ def scan_levels():
     return row
 
 
+def scan_mel():
+    """What log-mel features of segment audio cost, on scan_levels' corpus: VAD_SCAN_BENCH_N (default 1 024) int16
+    recordings of 30 s at 16 kHz, hop 256, the table of its scan, Whisper's geometry (n_fft 400, hop 160, 201 bins, 80 mels, Hann,
+    reflect, log10).  (a) Engine.mel on the block the scan left on the GPU; (b) the way to the same features without it:
+    Engine.cut(layout="range", out="f32") of the same table, then frames, two matrix products and the logarithm in numpy float32 on
+    the host (tests/mel_ref.py's rule; threads as the box gives them); (a) and (b) alternate.  Agreement: the first 256 segments of
+    (a) with the logarithm off against the float64 reference, within the header's bound.  (c) vad_scan_mel_device alone, HIP-event
+    timed as scan_levels' (c), against vad_scan_cut_device(RANGE, F32), which moves the samples the host route needs.  One warm-up,
+    then three timed passes of each; medians; the result goes to profiles/scan_mel.json."""
+    import ctypes as C
+    import time
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    from cutter_vad_amd import MelSpec, _ffi
+    from tests import mel_ref as R
+    N = int(os.environ.get("VAD_SCAN_BENCH_N", "1024"))
+    eng = Engine(blob(5), max_streams=max(N, 16))
+    hop, frame = 256, 512
+    pcm = np.tile(np.load(os.path.join(root, "tests", "golden", "speech16k_i16.npz"))["pcm"].astype(np.int16), 3)
+    rng = np.random.default_rng(N)
+    ns = 30 * 16000
+    recs = [pcm[a:a + ns] for a in rng.integers(0, pcm.size - ns + 1, N)]
+    slots = eng.open_streams(N)
+    eng.set_thresholds_many(slots, (0.4, 0.3, 0.8, 0.95, 6, 12))
+    med = lambda v: float(np.median(v))
+    spec = MelSpec(16000)
+    arrays = spec.operators()
+    flds, op_re, op_im, filters = arrays
+    f = R.fields(400, 160, 201, 80, R.REFLECT, R.LOG10, 1e-10)
+    row = {"config": f"scan_mel: {N} int16 recordings of 30 s at 16 kHz in one call, hop {hop}, n_fft 400 / hop 160 / 201 bins / 80 mels",
+           "recordings": N, "passes": 3}
+    op = np.concatenate([op_re, op_im], axis=1)
+
+    def numpy_route(data, start):
+        out = []
+        for i in range(len(start) - 1):
+            p = np.pad(data[start[i]:start[i + 1]], 200, mode="reflect")
+            fr = np.ascontiguousarray(np.lib.stride_tricks.sliding_window_view(p, 400)[::160])      # (a strided view would miss BLAS)
+            z = fr @ op
+            out.append(np.log10(np.maximum((z[:, :201] ** 2 + z[:, 201:] ** 2) @ filters.T, np.float32(1e-10))))
+        return np.concatenate(out)
+
+    with eng.scan_session():
+        table = eng.scan_segments(slots, recs, hop=hop, denoise=0.01)
+        last = eng.last_scan
+        offs = [int(o) for o in last["offsets"]]
+        segs = [(offs[i], a, n) for i, a, n in zip(table["item"].tolist(), table["first_frame"].tolist(), table["nframes"].tolist())]
+        counts = np.array([(n - 1) * hop + frame for _, _, n in segs], np.int64)
+        row.update(segments=len(segs), speech_samples=int(counts.sum()), block_samples=int(last["samples"]))
+
+        def route_b():
+            t0 = time.perf_counter()
+            data, start = eng.cut(segs, hop=hop, denoise=0.01, layout="range", out="f32")
+            t1 = time.perf_counter()
+            return numpy_route(data, start), t1 - t0, time.perf_counter() - t1, data, start
+
+        got, gstart = eng.mel(segs, arrays, hop=hop, denoise=0.01)
+        want, _, _, data, dstart = route_b()
+        row.update(rows=int(gstart[-1]), bytes_back_a=int(got.nbytes), bytes_back_b=int(data.nbytes),
+                   max_abs_log10_difference_a_b=float(np.abs(got - want).max()))
+        # agreement within the header's bound, logarithm off, on the first 256 segments, against float64
+        k = min(256, len(segs))
+        lin, lstart = eng.mel(segs[:k], ({**flds, "log": "linear"}, op_re, op_im, filters), hop=hop, denoise=0.01)
+        worst, worst32, ok = 0.0, 0.0, True
+        for i in range(k):
+            E, D = R.energies(data[dstart[i]:dstart[i + 1]], f, op_re, op_im, filters)
+            g = lin[lstart[i]:lstart[i + 1]].astype(np.float64)
+            fr = R.frames(data[dstart[i]:dstart[i + 1]], f)
+            z = fr @ op
+            E32 = (z[:, :201] ** 2 + z[:, 201:] ** 2) @ filters.T
+            live = D > 0
+            ok = ok and bool((np.abs(g - E) <= R.bound(f) * D).all())
+            if live.any():
+                worst = max(worst, float((np.abs(g - E)[live] / (R.U * D[live])).max()))
+                worst32 = max(worst32, float((np.abs(E32 - E)[live] / (R.U * D[live])).max()))
+        row.update(agree_within_bound=ok, max_err_over_uD_gpu=worst, max_err_over_uD_numpy_f32=worst32, allowed_over_uD=R.bound(f) / R.U)
+        a_runs, b_runs, b_cut, b_np = [], [], [], []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            eng.mel(segs, arrays, hop=hop, denoise=0.01)
+            a_runs.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            _, c, s_, _, _ = route_b()
+            b_runs.append(time.perf_counter() - t0)
+            b_cut.append(c)
+            b_np.append(s_)
+        row.update(a_s_mel_runs=a_runs, a_s_mel=med(a_runs), b_s_cut_numpy_runs=b_runs, b_s_cut_numpy=med(b_runs), b_s_cut_f32=med(b_cut),
+                   b_s_numpy=med(b_np), ratio_b_over_a=med(b_runs) / med(a_runs), host_threads=int(os.environ.get("OMP_NUM_THREADS", "0")))
+    # (c) on device pointers: the kernel call alone
+    block = np.zeros(last["samples"], np.int16)
+    for r, o in zip(recs, offs):
+        block[o:o + r.size] = r
+    d_audio = torch.from_numpy(block).cuda()
+    rows = int(gstart[-1])
+    d_out = torch.empty(max(rows * 80, int(counts.sum())) + 16, dtype=torch.float32, device="cuda")
+    ts = torch.cuda.Stream()
+    busy = torch.randn(6144, 6144, device="cuda")
+    lib, h, n = eng._lib, eng.handle, len(segs)
+    it_range, _ = eng._cut_items(segs, hop, _ffi.VAD_CUT_RANGE, 1)
+    m, a32, b32, w32 = eng._mel_arrays(arrays)
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    where = (d_audio.data_ptr(), block.size, 1, last["fmt"])
+
+    def event_timed(fn):
+        out = []
+        for k in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            with torch.cuda.stream(ts):
+                torch.mm(busy, busy)
+            e0.record(ts)
+            assert fn() == 0
+            e1.record(ts)
+            torch.cuda.synchronize()
+            if k >= 2:                           # two warm-ups
+                out.append(e0.elapsed_time(e1) * 1e-3)
+        return out
+
+    calls = {"c_s_mel_device": lambda: lib.vad_scan_mel_device(h, it_range, n, C.byref(m), fp(a32), fp(b32), fp(w32), *where, hop, 0.01,
+                                                               d_out.data_ptr(), rows, ts.cuda_stream),
+             "c_s_cut_range_f32_device": lambda: lib.vad_scan_cut_device(h, it_range, n, *where, hop, 0.01, _ffi.VAD_CUT_RANGE, _ffi.VAD_CUT_F32,
+                                                                         d_out.data_ptr(), int(counts.sum()), ts.cuda_stream)}
+    for name, fn in calls.items():
+        runs = event_timed(fn)
+        row[name + "_runs"], row[name] = runs, med(runs)
+    assert calls["c_s_mel_device"]() == 0
+    torch.cuda.synchronize()
+    row["c_equal"] = bool(d_out[:rows * 80].cpu().numpy().tobytes() == got.tobytes())
+    flop = 2.0 * rows * (400 * 2 * 208 + 208 * 80)
+    row["c_mfma_TFLOPs_with_padding"] = flop / row["c_s_mel_device"] / 1e12
+    row["c_operator_rereads_GB"] = (rows + 15) // 16 * (2 * 400 * 208 + 80 * 208) * 4 / 1e9
+    row["ratio_b_over_c"] = row["b_s_cut_numpy"] / row["c_s_mel_device"]
+    eng.close()
+    with open(os.path.join(root, "profiles", "scan_mel.json"), "w") as f_:
+        json.dump({"what": "Log-mel features of segment audio (vad_scan_mel, csrc/scan_mel.hip): DESIGN 2.1s",
+                   "how": "python tools/bench_configs.py scan_mel on one MI355X, one process.  (a) Engine.mel and (b) Engine.cut(range, f32) + "
+                          "numpy float32 on the host alternate, wall clock around the Python calls, one warm-up and three timed passes, medians; "
+                          "(b) uses only code the parent has.  (c) device forms: HIP events behind a matrix product that keeps the stream "
+                          "busy while the host builds the tables, ctypes items built outside the clock, two warm-ups and three timed passes; "
+                          "the operator pack is cached after the first call.  c_operator_rereads_GB is computed from the tile count, not "
+                          "counted.  Not measured: other geometries, formats and corpus sizes, L2 hit rates, the spread between "
+                          "processes and boxes", "runs": [row]}, f_, indent=1)
+        f_.write("\n")
+    return row
+
+
 def scan_rate():
     """Whole recordings at 48 kHz, resampled on the GPU in the scan: vad_scan_rate_device on VAD_SCAN_BENCH_N (default
     4 096) int16 recordings of 30 s at 48 kHz - the golden clip, every sample three times - already in device memory, hop = chunk / 2,

@@ -185,6 +185,62 @@ extern "C" hipError_t vadk_launch_scan_cut_gain(const CutArgs *a, const float *g
 extern "C" hipError_t vadk_launch_seg_levels(const CutArgs *a, float clip, hipStream_t) { return fake_cut(a, nullptr, true, clip); }
 extern "C" hipError_t vadk_launch_scan_cut_stereo(const CutArgs *a, const float *gains, hipStream_t) { return fake_cut(a, gains, false, 0.f, true); }
 
+// log-mel frames of finished segments (csrc/scan_mel.hip: vadk_seg_mel), the header's rule in plain float32 loops, tile by tile as
+// the workgroups are listed, over the UNPACKED view of the same tables: the cut's decoded, channel-selected, gated sample, reflected
+// by index, op_re / op_im / filters read back out of the packed streams (vad_layout.h: mel_op_index, mel_filter_index), sums in
+// ascending n and k, P = re * re + im * im, then the floor and std::log / std::log10 in float32
+extern "C" hipError_t vadk_launch_seg_mel(const MelArgs *a, hipStream_t) {
+    const size_t ch = a->channels == 2 ? 2 : 1, bytes = a->fmt == VAD_FMT_F32 ? 4 : a->fmt >= VAD_FMT_ULAW8 ? 1 : 2;
+    std::vector<float> P(a->bins_pad);
+    for (uint32_t b = 0; b < a->nwork; ++b) {
+        const MelWork w = a->work[b];
+        const CutSeg sg = a->segs[w.seg];
+        const uint32_t mode = sg.quad_in >> SCAN_MODE_SHIFT, qin = sg.quad_in & ((1u << SCAN_MODE_SHIFT) - 1u);
+        const int64_t S = (int64_t)sg.nquads * 4, half = a->pad == VAD_MEL_PAD_REFLECT ? a->n_fft / 2 : 0, len = S + 2 * half;
+        if (len < (int64_t)a->n_fft || (w.frame0 % MEL_TILE) != 0) return hipErrorInvalidValue;
+        const int64_t M = (len - a->n_fft) / a->hop + 1;
+        if ((int64_t)w.frame0 >= M) return hipErrorInvalidValue;
+        auto sample = [&](int64_t j, float *x) -> bool {          // p[j] of the header
+            int64_t r = j - half;
+            r = r < 0 ? -r : r >= S ? 2 * (S - 1) - r : r;
+            if (r < 0 || r >= S) return false;
+            const size_t i = 4 * (size_t)qin + (size_t)r;
+            if ((i + 1) * ch * bytes > a->audio_bytes) return false;
+            if (ch == 1) *x = first_sample(a->audio, i, a->fmt, 1);
+            else {
+                const float l = first_sample(a->audio, 2 * i, a->fmt, 1), rr = first_sample(a->audio, 2 * i + 1, a->fmt, 1);
+                *x = mode == SCAN_MIX ? (l + rr) * 0.5f : mode == SCAN_RIGHT ? rr : l;
+            }
+            if (a->thresh >= 0.f && !(std::fabs(*x) > a->thresh)) *x = 0.f;
+            return true;
+        };
+        for (int64_t f = w.frame0; f < M && f < (int64_t)w.frame0 + MEL_TILE; ++f) {
+            for (uint32_t k = 0; k < a->bins_pad; ++k) {
+                float re = 0.f, im = 0.f;
+                for (uint32_t n = 0; n < a->n_fft; ++n) {
+                    float x;
+                    if (!sample(f * a->hop + n, &x)) return hipErrorInvalidValue;
+                    const size_t at = mel_op_index(n, k, a->n_fft);
+                    re += x * a->op[at];
+                    im += x * a->op[at + 1];
+                }
+                P[k] = re * re + im * im;
+            }
+            float *row = a->out + ((size_t)sg.quad_out + (size_t)f) * a->n_mels;
+            for (uint32_t j = 0; j < a->n_mels; ++j) {
+                float e = 0.f;
+                for (uint32_t k = 0; k < a->bins_pad; ++k) e += a->filters[mel_filter_index(j, k, a->bins_pad)] * P[k];
+                if (a->log != VAD_MEL_LINEAR) {
+                    e = e > a->floor ? e : a->floor;
+                    e = a->log == VAD_MEL_LN ? std::log(e) : std::log10(e);
+                }
+                row[j] = e;
+            }
+        }
+    }
+    return hipSuccess;
+}
+
 // one finished piece of audio (csrc/scan_render.hip: vadk_scan_render), the kernel's arithmetic in plain C++, output quad by output
 // quad as its workgroups are listed: per covering segment the cut's decoded, channel-selected, gated sample, times the gain, times
 // the fade-in entry (or 1), times the fade-out entry (or 1) - three float32 multiplies - then the sum of the two where two segments
