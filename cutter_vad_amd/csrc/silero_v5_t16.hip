@@ -337,7 +337,8 @@ __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(STEP16_PARAMS) {
 // Wave (hf, w) is wave w of half-tile hf = tile 2 blockIdx.x + hf, with its own half of the LDS, and runs the body as it is, behind
 // barriers the halves share - but for the bf16-split LSTM halves and encoder.0, where it computes ONE row tile (rt = hf) for BOTH
 // half-tiles' streams: every weight fragment that reaches the CU's registers feeds two stream tiles, and the bytes those layers
-// stream per wave halve.  The body's PAIR branches; results bit for bit those of silero_v5_step16<., false, false, true>.
+// stream per wave halve - and for encoder.1 (one output column, hf, for both half-tiles: two thirds of its units) and encoder.3 (row
+// tile hf for both: half of them).  The body's PAIR branches; results bit for bit those of silero_v5_step16<., false, false, true>.
 template <bool F32IN_>
 __global__ void __launch_bounds__(2 * NTHREADS, 1) silero_v5_pair16(STEP16_PARAMS) {
     constexpr int FMT = F32IN_ ? 0 : 1;

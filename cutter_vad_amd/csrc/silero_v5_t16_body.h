@@ -1024,9 +1024,14 @@
         constexpr int NU0 = (K8 ? 2 : 4) * 3 * (PAIR ? 1 : 2);     // enc0's units: its K-steps x 3 taps x 2 row tiles (PAIR: one)
         f32x4 e1b;
         // enc1's bias and its first X3_D units ride in enc0's last units: the ring goes on, unit v of enc1 in slot NU0 + v
+        // PAIR: enc1 runs by output column (below) - the wave's unit v = (K-step, j) is the stream's unit (K-step, tap j + 1 - hf)
+#define E1P_BLK(v) (ws_y1 + ENC1_X3_F32_BLOCKS + 3 * (3 * ((v) >> 1) + ((v) & 1) + 1 - hf))
 #define E0_EXTRA(u)                                                                                             \
             if constexpr ((u) == NU0 - X3_D) e1b = WY(ws_y1);                                                   \
-            if constexpr ((u) + X3_D >= NU0) { X3_LDY(ws_y1 + ENC1_X3_F32_BLOCKS + 3 * ((u) + X3_D - NU0), (u) + X3_D) }
+            if constexpr ((u) + X3_D >= NU0) {                                                                  \
+                if constexpr (PAIR) { X3_LDY(E1P_BLK((u) + X3_D - NU0), (u) + X3_D) }                           \
+                else { X3_LDY(ws_y1 + ENC1_X3_F32_BLOCKS + 3 * ((u) + X3_D - NU0), (u) + X3_D) }                \
+            }
         if constexpr (PAIR) {
             // wave (hf, w): row tile hf (channels 32 w + 16 hf ..) of the three output columns for BOTH half-tiles: 12 units of 3 KiB
             // where a tile's wave streams 24, the same 336 MFMAs.  acc[o][st], F_[st][c]: st = 0 the wave's own tile, 1 the partner's.
@@ -1126,10 +1131,60 @@
         // The ring goes on through enc2 and enc3 (vad_layout.h, ENC23_X3_BLOCKS; the blocks lie behind the third stream) into the LSTM's
         // input half: enc2's unit v in slot XU_2 + v, enc3's in XU_3 + v, the input half's from XU_L on - every unit requests the
         // one X3_D units behind it, whichever layer that belongs to.
-        constexpr int NU1 = 4 * 3, NU2 = 4, NU3 = 4, XU_2 = NU0 + NU1, XU_3 = XU_2 + NU2, XU_L = XU_3 + NU3;
-        static_assert(NU2 == X3_D && NU3 == X3_D, "enc1's last X3_D units request enc2's units, enc2's units enc3's, enc3's the input half's first");
+        // PAIR: enc1 and enc3 serve both half-tiles from every unit, as the LSTM halves and enc0 do, and stream two thirds | half of the
+        // units: enc1 by output column (8 of the 12), enc3 by row tile (2 of the 4).  The ring's sequence is then enc1's 8, enc2's 4,
+        // enc3's 2, the input half's 16: enc2's units request enc3's two and the input half's first two, enc3's the next two.
+        constexpr int NU1 = PAIR ? 4 * 2 : 4 * 3, NU2 = 4, NU3 = PAIR ? 2 : 4, XU_2 = NU0 + NU1, XU_3 = XU_2 + NU2, XU_L = XU_3 + NU3;
+        static_assert(NU1 >= X3_D && NU2 == X3_D && (PAIR || NU3 == X3_D),
+                      "enc1's last X3_D units request enc2's units, enc2's units enc3's, enc3's the input half's first");
+        static_assert(!PAIR || (NU3 <= X3_D && NU2 + NU3 >= X3_D),
+                      "paired: enc2's units request enc3's NU3 and the input half's first X3_D - NU3, enc3's the input half's next NU3");
         f32x4 e2b, e3b[2];
-        {
+        // enc3's unit v of the wave: PAIR (K-step v, row tile hf) = the stream's unit 2 v + hf
+#define E3_BLK(v) (ws_z + ENC2_X3_BLOCKS + 2 + 3 * (PAIR ? 2 * (v) + hf : (v)))
+        if constexpr (PAIR) {
+            // wave (hf, w): output column hf of row tile w for BOTH half-tiles.  Column 0 = taps 1, 2 on input columns 0, 1; column 1 =
+            // taps 0, 1 on input columns 1, 2: unit v = (K-step s, j) is tap j + 1 - hf on input column hf + j, in the stream's K-step-
+            // major order - an accumulator sees the mfma_x3 it sees in the unpaired form, in the same order.  8 units of 3 KiB where a
+            // tile's wave streams 12, the same 96 MFMAs.  acc[st], F_[st][j]: st = 0 the wave's own tile, 1 the partner's.  One
+            // K-step's 12 pieces are held; the next K-step's replace input column hf + j's behind the unit that read them.
+            f32x4 acc[2] = {e1b, e1b};
+#define E1P_SRC(st, j) (((st) ? ldsO + T_ROW_E0 * QSD : RP0) + 48 * (hf + (j)) * QSD)
+#define E1_EXTRA(u)                                                                                             \
+            if constexpr ((u) == NU1 - X3_D) {     /* the fp32 blocks of the next two layers: their biases */    \
+                e2b = WY(ws_z);                                                                                 \
+                e3b[0] = WY(ws_z + ENC2_X3_BLOCKS + hf);     /* enc3's row tile hf */                           \
+            }                                                                                                   \
+            if constexpr ((u) + X3_D >= NU1) { X3_LDY(ws_z + 1 + 3 * ((u) + X3_D - NU1), XU_2 + (u) + X3_D - NU1) }
+            u32x4 F_[2][2][3];
+#pragma unroll
+            for (int st = 0; st < 2; ++st)
+#pragma unroll
+                for (int j_ = 0; j_ < 2; ++j_)
+#pragma unroll
+                    for (int p_ = 0; p_ < 3; ++p_) F_[st][j_][p_] = PL_RD(E1P_SRC(st, j_), 0, p_);
+            SB();
+            x3_units([&](auto uc_) {
+                constexpr int v_ = decltype(uc_)::value, s_ = v_ >> 1, j_ = v_ & 1;
+                if constexpr (v_ + X3_D < NU1) { X3_LDY(E1P_BLK(v_ + X3_D), NU0 + v_ + X3_D) }
+                E1_EXTRA(v_)
+#pragma unroll
+                for (int st = 0; st < 2; ++st) acc[st] = mfma_x3(xw[(NU0 + v_) % X3_NR], F_[st][j_], acc[st]);
+                if constexpr (s_ + 1 < 4) {
+#pragma unroll
+                    for (int st = 0; st < 2; ++st)
+#pragma unroll
+                        for (int p_ = 0; p_ < 3; ++p_) F_[st][j_][p_] = PL_RD(E1P_SRC(st, j_), s_ + 1, p_);
+                }
+                SB();
+            }, std::make_integer_sequence<int, NU1>{});
+#undef E1P_SRC
+#undef E1_EXTRA
+            // ReLU -> planes: half w & 1 of K-step w >> 1 of output column hf, in each half-tile's plane group 24 hf + 12 (w >> 1)
+#pragma unroll
+            for (int st = 0; st < 2; ++st)
+                st_planes_half((st ? ldsO : ldsH) + (24 * hf + 12 * (w >> 1)) * QSD + nq, w & 1, relu4(acc[st]));
+        } else {
             f32x4 acc[2][1] = {{e1b}, {e1b}};
 #define E1_SRC(c) (RP0 + 48 * (c) * QSD)
 #define E1_EXTRA(u)                                                                                             \
@@ -1146,6 +1201,7 @@
 #pragma unroll
             for (int o = 0; o < 2; ++o) st_planes_half(RX + (24 * o + 12 * (w >> 1)) * QSD + nq, w & 1, relu4(acc[o][0]));
         }
+#undef E1P_BLK
         STAMP(7);
         __syncthreads();   // (4) enc1 out as planes in rows 0..47
         STAMP(8);
@@ -1162,7 +1218,8 @@
             SB();
             x3_units([&](auto uc_) {
                 constexpr int v_ = decltype(uc_)::value;
-                X3_LDY(ws_z + ENC2_X3_BLOCKS + 2 + 3 * v_, XU_3 + v_)              // enc3's unit v
+                if constexpr (v_ < NU3) { X3_LDY(E3_BLK(v_), XU_3 + v_) }           // enc3's unit v
+                else { X3_LDU(ws_x3, v_ - NU3, XU_L) }                              // PAIR: behind enc3's two, the input half's first
                 if constexpr (v_ + 1 < NU2) {
 #pragma unroll
                     for (int p_ = 0; p_ < 3; ++p_) F_[(v_ + 1) & 1][p_] = PL_RD(RX, v_ + 1, p_);
@@ -1179,7 +1236,36 @@
 
         // ---- enc3: 64 -> 128 ch, centre tap, on the bf16 split: two row tiles over two K-steps, units (K-step s, rt); a K-step's
         //      pieces are read once for both row tiles ----
-        {
+        if constexpr (PAIR) {
+            // wave (hf, w): row tile hf of wave w's two (channels 32 w + 16 hf ..) for BOTH half-tiles: unit s = the stream's unit
+            // (K-step s, rt = hf), two units of 3 KiB where a tile's wave streams four, the same 24 MFMAs.  acc[st], F_[st][s]: st = 0 the
+            // wave's own tile, 1 the partner's (its enc2 planes: complete behind barrier (5), which both halves run).
+            f32x4 acc[2] = {e3b[0], e3b[0]};
+#define E3P_SRC(st) ((st) ? ldsO + T_ROW_E * QSD : RE)
+            u32x4 F_[2][2][3];
+#pragma unroll
+            for (int st = 0; st < 2; ++st)
+#pragma unroll
+                for (int p_ = 0; p_ < 3; ++p_) F_[st][0][p_] = PL_RD(E3P_SRC(st), 0, p_);
+            SB();
+            x3_units([&](auto uc_) {
+                constexpr int v_ = decltype(uc_)::value;
+                X3_LDU(ws_x3, v_ + X3_D - NU3, XU_L)                                // the LSTM input half's unit v + 2
+                if constexpr (v_ == 0) {
+#pragma unroll
+                    for (int st = 0; st < 2; ++st)
+#pragma unroll
+                        for (int p_ = 0; p_ < 3; ++p_) F_[st][1][p_] = PL_RD(E3P_SRC(st), 1, p_);
+                }
+#pragma unroll
+                for (int st = 0; st < 2; ++st) acc[st] = mfma_x3(xw[(XU_3 + v_) % X3_NR], F_[st][v_], acc[st]);
+                SB();
+            }, std::make_integer_sequence<int, NU3>{});
+#undef E3P_SRC
+            // ReLU -> planes: half hf of K-step w of the LSTM's input half, in each half-tile's x planes
+#pragma unroll
+            for (int st = 0; st < 2; ++st) st_planes_half((st ? ldsO : ldsH) + 12 * w * QSD + nq, hf, relu4(acc[st]));
+        } else {
             f32x4 acc[2] = {e3b[0], e3b[1]};
             u32x4 F_[2][3];
 #pragma unroll
@@ -1197,6 +1283,7 @@
             }, std::make_integer_sequence<int, NU3>{});
             st_planes(RX + 12 * w * QSD + nq, relu4(acc[0]), relu4(acc[1]));      // channels 32 w .. = K-step w of the LSTM's input half
         }
+#undef E3_BLK
         STAMP(11);
         __syncthreads();   // (6) LSTM input x as planes in rows 0..47
         STAMP(12);
