@@ -92,7 +92,7 @@ constexpr int QSD = 16;                   // dense view of the same memory, used
 // waves that consume it, no VALU work (before: every wave cut every activation it read, 11 instructions per pair of values).
 // Live ranges: the h planes are read in the recurrent half only (barrier (0) .. (1)) and written by the prologue and by the cell
 // behind barrier (7), so they may lie under enc0's output (written behind (2), last read before (4)), in every instantiation (the
-// rejected-frame hold keeps h_{t-1} in registers), and lie past the folded operands (T_ROWS_DFT, T_EVEN_Q below, live (0) .. (1b)); the |STFT| planes are
+// rejected-frame hold keeps h_{t-1} in registers; silero_v5_pair16: written behind (4), read between (5) and (6)), and lie past the folded operands (T_ROWS_DFT, T_EVEN_Q below, live (0) .. (1b)); the |STFT| planes are
 // written behind (1b) and read until (3); enc1's planes are written behind (3) and read until (5), enc2's planes behind (4)
 // until (6); the x planes are written behind (5), when enc1's planes and the |STFT| planes are dead, and read until (7).
 constexpr int T_ROW_E0 = 144;
@@ -106,6 +106,13 @@ static_assert(T_ROW_E0 + 144 <= T_ROWS && T_ROW_E + 32 <= T_ROWS, "enc0's output
 static_assert(T_ROWS_E1 <= T_ROW_E0, "enc1's planes are written while other waves still read enc0's output");
 static_assert(T_ROW_E >= T_ROWS_E1 && T_ROW_E >= 48, "enc2's planes are written while enc1's are read, and read while the x planes are written");
 static_assert(T_ROW_E >= T_ROW_E0 && T_ROW_E + T_ROWS_E2 <= T_ROW_H, "enc2's planes lie in enc0's dead output and stay clear of h");
+// silero_v5_pair16 (the body's XFIRST order) writes the h planes behind barrier (4) and reads them behind (5), in front of (6): enc0's
+// output above them is dead by then, and what is written or read between (4) and (7) - enc2's planes, the x planes (rows 0 ..
+// T_ROWS_H - 1, the input half's) and the paired hand-back rows (T_ROW_E0 .. T_ROW_E0 + 63) - lies below them
+constexpr int T_ROWS_HANDBACK = 64;       // PAIR: 4 waves x 4 gates x 4 quad rows from T_ROW_E0 on, across barrier (7)
+static_assert(T_ROW_E0 + T_ROWS_HANDBACK <= T_ROW_H && T_ROWS_H <= T_ROW_E0 && T_ROW_E + T_ROWS_E2 <= T_ROW_H,
+              "frames first: the h planes, written behind barrier (4), stay clear of the x planes, enc2's planes and the hand-back rows");
+static_assert(T_ROW_H >= T_ROW_E0 && T_ROW_H + T_ROWS_H <= T_ROWS, "frames first: the h planes take the place of enc0's output, dead behind barrier (4)");
 // The folded STFT operands, live (0) .. (1b).  8 kHz sub-model: the loader view from row 0 on (96 rows).  16 kHz model: the odd tile
 // runs on the bf16 split (vad_layout.h, DFT_X3_BLOCKS), so the loader cuts po | qo into planes, DENSE view: column c = rows 48 c ..
 // 48 c + 47 = four plane groups 2 part + s (part 0 po, 1 qo; K-step s = the folded samples n = 32 s .. 32 s + 31), where the |STFT|
@@ -325,7 +332,9 @@ __device__ __forceinline__ void x3_units(F &&f, std::integer_sequence<int, I...>
     constexpr int CH = 1;                               \
     constexpr const ScanItem *k_items = nullptr;        \
     constexpr ScanArgs S{};
-#define STEP16_NO_PAIR constexpr bool PAIR = false;
+#define STEP16_NO_PAIR                                  \
+    constexpr bool PAIR = false;                        \
+    constexpr bool XFIRST = false;
 template <bool F32IN_, bool RS, bool K8 = false, bool ONE = false>
 __global__ void __launch_bounds__(NTHREADS, 1) silero_v5_step16(STEP16_PARAMS) {
     constexpr int FMT = F32IN_ ? 0 : 1;
@@ -343,6 +352,7 @@ template <bool F32IN_>
 __global__ void __launch_bounds__(2 * NTHREADS, 1) silero_v5_pair16(STEP16_PARAMS) {
     constexpr int FMT = F32IN_ ? 0 : 1;
     constexpr bool RS = false, K8 = false, ONE = true, PAIR = true;
+    constexpr bool XFIRST = true;      // frames first, the recurrent half behind enc3 (silero_v5_t16_body.h)
     STEP16_NO_SCAN
 #include "silero_v5_t16_body.h"
 }

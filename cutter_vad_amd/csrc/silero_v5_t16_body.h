@@ -8,6 +8,9 @@
 // CH: the channels of the audio block, 1 everywhere but in the scan of interleaved two-channel recordings (silero_v5_stereo16).
 // PAIR (silero_v5_pair16): the workgroup is TWO tiles - 512 threads, wave (hf, w) = wave w of half-tile hf with its own half of the LDS;
 // `tid` is the thread's index inside its half, tilei its tile, ldsO the partner half's LDS.  Both halves run every barrier.
+// XFIRST (silero_v5_pair16 only): the one-frame launch's phase order - the frame is requested first and folded as it arrives, with
+// nothing of the state in front of barrier (1); h_{t-1} goes to its planes behind barrier (4) and the recurrent gate half runs behind
+// enc3, in front of barrier (6).  Every other entry keeps the order of the frame loop: the recurrent half first, the ingest under it.
 #define KP(f) k_##f
     using namespace vadk::v5;
     constexpr bool F32IN = FMT == 0;
@@ -17,6 +20,7 @@
     static_assert(!SCAN || (!RS && !ONE), "a scan is the frame-loop form on audio in HBM");
     static_assert(CH == 1 || (CH == 2 && SCAN), "two interleaved channels: whole recordings only");
     static_assert(!PAIR || (ONE && !RS && !K8 && !G711 && !SCAN), "paired tiles: one-frame calls of the 16 kHz model, float32 / int16");
+    static_assert(!XFIRST || PAIR, "frames first: the paired one-frame kernel (no next frame whose h the cell would hand on)");
     constexpr int QL = K8 ? 8 : 16;               // loader lanes per stream = quads per quarter column
     constexpr int CS = 4 * QL;                    // folded-operand rows per column
     constexpr int PP = K8 ? 24 : 48;              // quad rows per |STFT| column (enc0's input) as planes: 12 per K-step
@@ -255,19 +259,31 @@
     // first units depend on kernel arguments only, and W_hh is the coldest part of the weight stream; then the window and c, and
     // behind the wait for h the frame's first two columns (below).  Streams past n (the last tile's tail) read slot 0's state and
     // compute on it: a stream is a column of every MFMA, nothing crosses columns, and every store of the kernel is guarded by `live`.
+    // XFIRST: the frame's columns are requested first, then what the fold and the STFT need of the weight stream, and the state
+    // behind them (H_STATE_H, H_STATE_SM below): h_{t-1} feeds only the recurrent half, whose result nothing needs before the input half adds
+    // onto it behind barrier (6), while every phase in front of that depends on the frame.
     f32x4 hv[2];                                   // (tid & 15 == n: ONE slot lookup serves h, c and the state machine)
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt) hv[rt] = *reinterpret_cast<const f32x4 *>(KP(state) + (size_t)slot * 256 + 32 * w + 16 * rt + 4 * kq);
-    SB();
-    auto bias2 = __builtin_amdgcn_raw_buffer_load_b64(wrs, lane * 8, (o_l + T_LSTM_BIAS_BLOCK) * 1024, 0);
+    decltype(__builtin_amdgcn_raw_buffer_load_b64(wrs, 0, 0, 0)) bias2;
+#define H_STATE_H                                                                                               \
+    {                                                                                                           \
+        _Pragma("unroll") for (int rt = 0; rt < 2; ++rt)                                                        \
+            hv[rt] = *reinterpret_cast<const f32x4 *>(KP(state) + (size_t)slot * 256 + 32 * w + 16 * rt + 4 * kq); \
+        SB();                                                                                                   \
+        bias2 = __builtin_amdgcn_raw_buffer_load_b64(wrs, lane * 8, (o_l + T_LSTM_BIAS_BLOCK) * 1024, 0);       \
+    }
+    if constexpr (!XFIRST) H_STATE_H
     const bool sm_thread = (tid < MT16) && live;
     const int sm_slot = slot;
     f32x4 smq[6];
-    if (tid < MT16) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) smq[k] = reinterpret_cast<const f32x4 *>(KP(sm) + slot)[k];
+#define H_STATE_SM                                                                                              \
+    {                                                                                                           \
+        if (tid < MT16) {                                                                                       \
+            _Pragma("unroll") for (int k = 0; k < 6; ++k) smq[k] = reinterpret_cast<const f32x4 *>(KP(sm) + slot)[k]; \
+        }                                                                                                       \
+        SB();                                                                                                   \
     }
-    SB();
+    if constexpr (XFIRST) { X_ISSUE(0, xa_, 0) SB(); }
+    else H_STATE_SM
     // The LSTM's weights come from S_LSTM_X3 (vad_layout.h): per half 32 units u = 8 s + tile (K-step s, tile = 2 q + rt), each the
     // three bf16 pieces of the tile's A fragment (3 blocks).  They stream through a ring of X3_NR units, requested X3_D units ahead.
     // encoder.0 streams its own through the same ring (S_ENC0_X3, X3_CONV).
@@ -275,7 +291,8 @@
     // 16 kHz: the ring runs on from the recurrent half through the STFT's odd tile (vad_layout.h, DFT_X3_BLOCKS: four units, in the third
     // stream's buffer) into encoder.0, whose unit 0 sits in slot 0: the recurrent half's NH units start at XU_H with XU_H + NH + 4 = 0
     // (mod X3_NR), the DFT's unit v has slot XU_D + v
-    constexpr int NH = PAIR ? 16 : 32, XU_H = K8 ? 0 : (2 * X3_NR - (NH + 4) % X3_NR) % X3_NR, XU_D = XU_H + NH;
+    // XFIRST: the ring starts at the DFT's units (requested by the prologue), and the recurrent half's follow enc3's (XU_R below)
+    constexpr int NH = PAIR ? 16 : 32, XU_H = K8 ? 0 : (2 * X3_NR - (NH + 4) % X3_NR) % X3_NR, XU_D = XFIRST ? X3_NR - 4 : XU_H + NH;
     static_assert(K8 || (XU_D + 4) % X3_NR == 0, "encoder.0's units follow the DFT's in the ring");
     [[maybe_unused]] const int o_d = 4 * ENC1_X3_BLOCKS + 4 * ENC23_X3_BLOCKS + w * DFT_X3_BLOCKS;
 #define X3_LDD(v, slot) X3_LDY(o_d + 3 * (v), slot)
@@ -299,10 +316,24 @@
         SB();                                                                                                   \
         if constexpr (RS) { X_ISSUE(2, xc_, tt) SB(); }                                                         \
     }
-    if constexpr (!RS) STAMP(29);
-    if constexpr (!RS) H_FIRST(o_x3, 0, K8)        // frames t > 0 request theirs at the end of frame t - 1; RS: at the top of the frame
+    if constexpr (!RS && !XFIRST) STAMP(29);
+    if constexpr (!RS && !XFIRST) H_FIRST(o_x3, 0, K8)   // frames t > 0 request theirs at the end of frame t - 1; RS: at the top of the frame
     const f32x4 W1 = ldw(wrs, q * 16, o_nyq), W3 = ldw(wrs, (2 * QL + q) * 16, o_nyq);   // w[n], w[128 + n]  (8 kHz: w[64 + n])
     const float w64 = ldw(wrs, QL * 16, o_nyq).x;                                          // w[64]             (8 kHz: w[32])
+    // XFIRST: behind column 0 and the window (the first fold waits for no more than those), the other two columns, the STFT's first
+    // fp32 blocks, the DFT's four ring units - and only then the state
+    [[maybe_unused]] f32x4 SwF[2];
+    if constexpr (XFIRST) {
+        X_ISSUE(1, xb_, 0) X_ISSUE(2, xc_, 0)
+        SB();
+#pragma unroll
+        for (int k = 0; k < 2; ++k) SwF[k] = WL(o_stft + 8 + k);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) { X3_LDD(v, XU_D + v) }
+        SB();
+        H_STATE_H
+        H_STATE_SM
+    }
     f32x4 cst[2];                                  // c of units 32 w + 16 rt + 4 kq + i
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt) cst[rt] = *reinterpret_cast<const f32x4 *>(KP(state) + (size_t)slot * 256 + 128 + 32 * w + 16 * rt + 4 * kq);
@@ -319,16 +350,29 @@
         }
     }
     SB();
+    if constexpr (XFIRST) STAMP(29);
+    // (XFIRST: h, the biases and the state machines go to LDS behind barrier (4) - H_TO_LDS in the frame loop)
+#define H_TO_LDS                                                                                                \
+    {                                                                                                           \
+        STAMP_ON(30, hv[1]);                           /* h has arrived */                                      \
+        st_planes(RH + 12 * w * QSD + nq, hv[0], hv[1]);                                                        \
+        reinterpret_cast<decltype(bias2) *>(biasL + 32 * w)[lane] = bias2;                                      \
+        if (tid < MT16) {                                                                                       \
+            _Pragma("unroll") for (int k = 0; k < 6; ++k) reinterpret_cast<f32x4 *>(smL + tid)[k] = smq[k];     \
+        }                                                                                                       \
+    }
+    if constexpr (!XFIRST) {
     STAMP_ON(30, hv[1]);                           // h has arrived
     st_planes(RH + 12 * w * QSD + nq, hv[0], hv[1]);
+    }
     // The call's first frame is requested HERE, behind the wait for h, and not with the first weight blocks: with two tiles per CU all
     // asking at once the memory system serves the launch's first requests roughly in order (8 192 streams: h arrives 7.5 k cycles
     // after kernel entry, 3.0 k at 4 096), and the frame's 32 KB per tile in front of h and c only delay what the first MFMAs wait
     // for; the first fold is 15 units of MFMAs away.  Same box: 36.81 -> 36.54 us per headline step.
-    if constexpr (!RS && !K8) { SB(); H_FIRSTX(0) SB(); }
-    reinterpret_cast<decltype(bias2) *>(biasL + 32 * w)[lane] = bias2;
+    if constexpr (!RS && !K8 && !XFIRST) { SB(); H_FIRSTX(0) SB(); }
+    if constexpr (!XFIRST) reinterpret_cast<decltype(bias2) *>(biasL + 32 * w)[lane] = bias2;
     int seg_last = 0;
-    if (tid < MT16) {
+    if (!XFIRST && tid < MT16) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) reinterpret_cast<f32x4 *>(smL + tid)[k] = smq[k];
     }
@@ -670,7 +714,7 @@
         f32x4 G[8];                               // gate q, row tile rt -> G[2 q + rt]
         [[maybe_unused]] f32x4 Gp[4][2];          // PAIR: gate q's row tile hf of the wave's own tile [0] and of the partner half's [1]
         {
-            const int wh = ws_x3 + LSTM_X3_HALF_BLOCKS;
+            [[maybe_unused]] const int wh = ws_x3 + LSTM_X3_HALF_BLOCKS;
             f32x4 xcA, xcB;                       // XCARRY: the decoded quads k = 2, 3 of the column folded last
             float xm = 0.f;                       // float32: running max |x| of this thread's raw samples (vadk_device.h absmax4)
             auto decode = [&](XQ b) -> f32x4 {
@@ -794,6 +838,10 @@
         __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);                                                      \
         __builtin_amdgcn_sched_group_barrier(0x002, 28, 0);                                                     \
     }
+            if constexpr (XFIRST) {
+                // the three folds as their columns arrive, on an MFMA pipe that has nothing else to do yet: h is still on its way
+                X_FOLD(0, xa_, 0) X_FOLD(1, xb_, 1) X_FOLD(2, xc_, 2) X_FLAG
+            } else {
             if constexpr (RS) H_FIRST(ws_x3, t, true)           // F is dead once every wave has passed the barrier below
             {   // the accumulators start at the gate biases: G[2 q + rt] register i of a lane = unit 16 rt + 4 kq + i of gate q (the
                 // 16 lanes of a row group read the same 16 bytes: a broadcast).  The wave reads what the wave itself wrote.
@@ -835,6 +883,7 @@
             } else {
             X3_HALF(XU_H, wh, RH, H_EXTRA, H_FOLDREGION)
             }
+            }
 #undef HP_EXTRA
 #undef HP_FOLDREGION
 #undef HP_MIX
@@ -846,7 +895,10 @@
         }
         f32x4 Sw[2];                              // the STFT's first fp32 blocks, cos and -sin: 8 kHz k-iteration 0, 16 kHz the even tile's first
 #pragma unroll
-        for (int k = 0; k < 2; ++k) Sw[k] = WL(ws_stft + (K8 ? 0 : 8) + k);
+        for (int k = 0; k < 2; ++k) {
+            if constexpr (XFIRST) Sw[k] = SwF[k];     // requested by the prologue
+            else Sw[k] = WL(ws_stft + (K8 ? 0 : 8) + k);
+        }
         SB();
         STAMP(1);
         __syncthreads();   // (1) folded x visible
@@ -1134,7 +1186,14 @@
         // PAIR: enc1 and enc3 serve both half-tiles from every unit, as the LSTM halves and enc0 do, and stream two thirds | half of the
         // units: enc1 by output column (8 of the 12), enc3 by row tile (2 of the 4).  The ring's sequence is then enc1's 8, enc2's 4,
         // enc3's 2, the input half's 16: enc2's units request enc3's two and the input half's first two, enc3's the next two.
-        constexpr int NU1 = PAIR ? 4 * 2 : 4 * 3, NU2 = 4, NU3 = PAIR ? 2 : 4, XU_2 = NU0 + NU1, XU_3 = XU_2 + NU2, XU_L = XU_3 + NU3;
+        // XFIRST: the recurrent half's 16 units follow enc3's, from XU_R on, and the input half's follow those - enc2's and enc3's units
+        // request the recurrent half's first four, the recurrent half's last four the input half's first.
+        constexpr int NU1 = PAIR ? 4 * 2 : 4 * 3, NU2 = 4, NU3 = PAIR ? 2 : 4, XU_2 = NU0 + NU1, XU_3 = XU_2 + NU2, XU_R = XU_3 + NU3;
+        constexpr int XU_L = XFIRST ? XU_R + NH : XU_R;
+        static_assert(!XFIRST || ((XU_D + 4) % X3_NR == 0 && XU_R == NU0 + NU1 + NU2 + NU3 && XU_L == XU_R + NH && NH >= X3_D),
+                      "frames first: the ring runs DFT -> enc0 -> enc1 -> enc2 -> enc3 -> recurrent half -> input half, every unit one slot on");
+        // the unit X3_D behind enc2's / enc3's in the ring, counted from the LSTM half that follows enc3
+#define X3_LDN(v) if constexpr (XFIRST) { X3_LDP(ws_x3 + LSTM_X3_HALF_BLOCKS, v, XU_R) } else { X3_LDU(ws_x3, v, XU_L) }
         static_assert(NU1 >= X3_D && NU2 == X3_D && (PAIR || NU3 == X3_D),
                       "enc1's last X3_D units request enc2's units, enc2's units enc3's, enc3's the input half's first");
         static_assert(!PAIR || (NU3 <= X3_D && NU2 + NU3 >= X3_D),
@@ -1205,6 +1264,10 @@
         STAMP(7);
         __syncthreads();   // (4) enc1 out as planes in rows 0..47
         STAMP(8);
+        // XFIRST: h_{t-1} -> its planes, now that enc0's output above them is dead (rows 248..295; enc2's planes, rows 168..191, the x
+        // planes, rows 0..47, and the hand-back rows 144..207 stay clear of them), and the biases and the state machines to their
+        // places: the recurrent half reads the planes of both halves behind barrier (5)
+        if constexpr (XFIRST) H_TO_LDS
 
         // ---- enc2: 64 -> 64 ch, k3 s2 p1, 2 -> 1 column, on the bf16 split: wave w = channels 16 w .. 16 w + 15 (one row tile) over the
         //      whole K = 128: four units (input column c on tap 1 + c - tap 0 meets the padding only -, K-step s) = enc1's plane group
@@ -1219,7 +1282,7 @@
             x3_units([&](auto uc_) {
                 constexpr int v_ = decltype(uc_)::value;
                 if constexpr (v_ < NU3) { X3_LDY(E3_BLK(v_), XU_3 + v_) }           // enc3's unit v
-                else { X3_LDU(ws_x3, v_ - NU3, XU_L) }                              // PAIR: behind enc3's two, the input half's first
+                else { X3_LDN(v_ - NU3) }                                           // PAIR: behind enc3's two, the next LSTM half's first
                 if constexpr (v_ + 1 < NU2) {
 #pragma unroll
                     for (int p_ = 0; p_ < 3; ++p_) F_[(v_ + 1) & 1][p_] = PL_RD(RX, v_ + 1, p_);
@@ -1250,7 +1313,7 @@
             SB();
             x3_units([&](auto uc_) {
                 constexpr int v_ = decltype(uc_)::value;
-                X3_LDU(ws_x3, v_ + X3_D - NU3, XU_L)                                // the LSTM input half's unit v + 2
+                X3_LDN(v_ + X3_D - NU3)                                             // the next LSTM half's unit v + 2
                 if constexpr (v_ == 0) {
 #pragma unroll
                     for (int st = 0; st < 2; ++st)
@@ -1265,6 +1328,21 @@
             // ReLU -> planes: half hf of K-step w of the LSTM's input half, in each half-tile's x planes
 #pragma unroll
             for (int st = 0; st < 2; ++st) st_planes_half((st ? ldsO : ldsH) + 12 * w * QSD + nq, hf, relu4(acc[st]));
+            if constexpr (XFIRST) {
+                // ---- the recurrent gate half W_hh . h_{t-1}, from the biases on (the wave reads what the wave itself wrote), on both
+                //      halves' h planes (complete behind barrier (5)); its last units request the input half's first, and the input
+                //      half adds onto the same accumulators behind barrier (6): every accumulator sees the MFMAs it saw, in their order ----
+                STAMP(31);
+                const f32x4 *const bq = biasL + 32 * w + kq;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) Gp[k][0] = Gp[k][1] = bq[k * 8 + hf * 4];
+#define HX_EXTRA(v) if constexpr ((v) + X3_D >= NH) { X3_LDP(ws_x3, (v) + X3_D - NH, XU_L) }
+#define HX_FOLDREGION(v) false
+                X3P_HALF(XU_R, (ws_x3 + LSTM_X3_HALF_BLOCKS), RH, (ldsO + T_ROW_H * QSD), HX_EXTRA, HX_FOLDREGION)
+#undef HX_EXTRA
+#undef HX_FOLDREGION
+                STAMP(26);
+            }
         } else {
             f32x4 acc[2] = {e3b[0], e3b[1]};
             u32x4 F_[2][3];
@@ -1284,6 +1362,7 @@
             st_planes(RX + 12 * w * QSD + nq, relu4(acc[0]), relu4(acc[1]));      // channels 32 w .. = K-step w of the LSTM's input half
         }
 #undef E3_BLK
+#undef X3_LDN
         STAMP(11);
         __syncthreads();   // (6) LSTM input x as planes in rows 0..47
         STAMP(12);
@@ -1396,6 +1475,9 @@
         if (++t >= T) break;
         if constexpr (!RS) H_FIRST(ws_x3, t, true) // the next frame's first requests
     }
+#undef H_TO_LDS
+#undef H_STATE_SM
+#undef H_STATE_H
 #undef H_FIRST
 #undef H_FIRSTX
 #undef X3_LDU

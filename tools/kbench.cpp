@@ -196,6 +196,13 @@ int main(int argc, char **argv) {
 #ifdef KB_TILE16      // the 16-stream body stamps the end of the LSTM's main loop only, and one ingest group per STFT column
         printf("  total=%.0f | mainloops: lstm=%.0f\n", tot, l3 / tiles);
         const int ngroups = 3;
+        if (kb_pair) {
+            // the paired kernel runs frames first: folds, barrier (1), STFT .. enc3, then the recurrent half (stamps 31 .. 26) inside the
+            // phase printed as enc3, in front of barrier (6); its ingest groups are printed since kernel entry, further down
+            double e3 = 0, rh = 0;
+            for (int b = 0; b < tiles; ++b) { e3 += (double)(S(b, w, 31) - S(b, w, 10)); rh += (double)(S(b, w, 26) - S(b, w, 31)); }
+            printf("        of enc3 above: enc3 itself = %.0f, recurrent half = %.0f\n", e3 / tiles, rh / tiles);
+        }
         printf("        ingest groups (a column's quads have arrived, in front of its fold; cycles since frame start):");
 #else
         printf("  total=%.0f | mainloops: stft=%.0f enc0=%.0f lstm=%.0f\n", tot, l1 / tiles, l2 / tiles, l3 / tiles);
@@ -228,6 +235,18 @@ int main(int argc, char **argv) {
             for (int b = 0; b < tiles; ++b) tl += (double)(S(b, 0, 28) - S(b, 0, 15));
             printf("        head + state machine (32 lanes of wave 0, behind barrier (8)) = %.0f\n", tl / tiles);
         }
+#endif
+#ifdef KB_TILE16
+        if (kb_pair) {
+            double g[3] = {0, 0, 0}, b1 = 0, r1 = 0;
+            for (int b = 0; b < tiles; ++b) {
+                for (int k = 0; k < 3; ++k) g[k] += (double)(S(b, w, 20 + k) - S(b, w, 19));
+                b1 += (double)(S(b, w, 2) - S(b, w, 19)); r1 += (double)(S(b, w, 26) - S(b, w, 19));
+            }
+            printf("        since kernel entry: all first requests issued %.0f, frame column 0 / 1 / 2 arrived %.0f / %.0f / %.0f, past barrier (1) %.0f,\n"
+                   "                            h in LDS (behind barrier (4)) %.0f, recurrent half %.0f .. %.0f\n",
+                   a29 / tiles, g[0] / tiles, g[1] / tiles, g[2] / tiles, b1 / tiles, a30 / tiles, a31 / tiles, r1 / tiles);
+        } else
 #endif
         if (S(0, w, 29)) printf("        since kernel entry: all first requests issued %.0f, h in LDS %.0f, past barrier (0) %.0f\n", a29 / tiles, a30 / tiles, a31 / tiles);
     }
