@@ -136,6 +136,8 @@ VAD_CUT_FRAMES, VAD_CUT_RANGE = 0, 1
 VAD_CUT_PCM16, VAD_CUT_F32 = 0, 1
 VAD_CUT_WG_SAMPLES = 4096
 VAD_RENDER_MAX_RAMP = 65536
+VAD_RESAMPLE_CUT_MAX_TAPS = 511
+VAD_RESAMPLE_CUT_WG_SAMPLES = 2048
 CUT_LAYOUTS = {"frames": VAD_CUT_FRAMES, "range": VAD_CUT_RANGE}
 CUT_OUTPUTS = {"pcm16": VAD_CUT_PCM16, "f32": VAD_CUT_F32}
 
@@ -297,6 +299,15 @@ SIGNATURES = {
                                C.c_int32, C.c_float, _f32p, C.c_int64]),
     "vad_scan_mel_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, C.POINTER(Mel), _f32p, _f32p, _f32p, _vp, C.c_int64, C.c_int32,
                                       C.c_int, C.c_int32, C.c_float, _vp, C.c_int64, _vp]),
+    "vad_resample_cut_samples": (C.c_int64, [_vp, C.c_int64, C.c_int32, C.c_int32]),
+    "vad_scan_resample_cut": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int,
+                                        C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int64]),
+    "vad_scan_resample_cut_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int,
+                                               C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int64, _vp]),
+    "vad_scan_rate_mel": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, C.POINTER(Mel), _f32p, _f32p, _f32p, _f32p, C.c_int32, _vp, C.c_int64,
+                                    C.c_int32, C.c_int, C.c_int32, C.c_int32, _f32p, C.c_int64]),
+    "vad_scan_rate_mel_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, C.POINTER(Mel), _f32p, _f32p, _f32p, _f32p, C.c_int32, _vp,
+                                           C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32, _vp, C.c_int64, _vp]),
     "vad_scan_render": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32,
                                   C.c_int32, C.c_float, C.c_int32, _vp, C.c_int64]),
     "vad_scan_render_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int,

@@ -46,6 +46,7 @@ extern "C" hipError_t vadk_launch_scan_cut(const vadk::CutArgs *a, hipStream_t s
 extern "C" hipError_t vadk_launch_scan_cut_gain(const vadk::CutArgs *a, const float *gains, hipStream_t stream);
 extern "C" hipError_t vadk_launch_seg_levels(const vadk::CutArgs *a, float clip, hipStream_t stream);
 extern "C" hipError_t vadk_launch_seg_mel(const vadk::MelArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_resample_cut(const vadk::ResampleCutArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_render(const vadk::RenderArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_cut_stereo(const vadk::CutArgs *a, const float *gains, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_render_stereo(const vadk::RenderArgs *a, hipStream_t stream);
@@ -194,6 +195,16 @@ struct vad_engine {
     vad_mel mel_key{};
     bool mel_packed = false;
     float *d_mel = nullptr; size_t d_mel_cap = 0;
+    // vad_scan_resample_cut: the segments' input quads, and the packed operator T (vad_layout.h: rsc_pack_index) in d_rsc, CACHED as
+    // the mel operator is: rsc_src are the caller's taps of the previous pack, rsc_rate its sr_in.  vad_scan_rate_mel: the 16 kHz
+    // signals of its segments in d_rsc_mid (float32, back to back) and the mel kernel's segments over them
+    std::vector<uint32_t> rsc_inq;
+    std::vector<float> rsc_src, rsc_pack;
+    int32_t rsc_rate = 0;
+    bool rsc_packed = false;
+    float *d_rsc = nullptr; size_t d_rsc_cap = 0;
+    float *d_rsc_mid = nullptr; size_t d_rsc_mid_cap = 0;
+    std::vector<vadk::CutSeg> rsc_mel_segs;
     // vad_segments_device / vad_scan_segments: the extraction's work area - out_start as int32 [n + 1] (the host copy as it was
     // uploaded), then the chunk counts - and, for vad_scan_segments, the items' CSR positions, the count and the retained table
     uint8_t *d_segwork = nullptr; size_t d_segwork_cap = 0;
@@ -920,7 +931,7 @@ void vad_engine_destroy(vad_engine *e) {
     weights_release(e->d_wstream16x);
     weights_release(e->d_wstream16y);
     void *bufs[] = {e->d_refine, e->d_refine_in, e->d_refine_out, e->d_tail_len, e->d_tailwork, e->d_reseg, e->d_resegtab, e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots, e->d_g711,
-                    e->d_audio, e->d_items, e->d_win, e->d_items_win, e->d_cut, e->d_cut_out, e->d_mel, e->d_segwork, e->d_nsegs, e->d_segtab, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
+                    e->d_audio, e->d_items, e->d_win, e->d_items_win, e->d_cut, e->d_cut_out, e->d_mel, e->d_rsc, e->d_rsc_mid, e->d_segwork, e->d_nsegs, e->d_segtab, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->scan_done) (void)hipEventDestroy(e->scan_done);
@@ -1718,6 +1729,9 @@ struct CutPlan {
     bool stereo;
     // vad_scan_mel: the segments are checked and tabled as for the levels (levels is set too); its workgroups are listed by mel_run
     bool mel;
+    // vad_scan_resample_cut / vad_scan_rate_mel (a rate block, the range once): a segment's count is S16, its samples at 16 kHz - in
+    // the out_sample check, the spans and CutSeg::nquads - its input quads go to e->rsc_inq, and a workgroup has RSC_WG_SAMPLES outputs
+    bool resample;
     // a. cut_check
     bool rate, rate_frames;
     uint32_t fshift;                         // log2 of the quads of a payload frame
@@ -1788,6 +1802,7 @@ int cut_check(vad_engine *e, CutPlan &c) {
     e->cut_segs.resize((size_t)n);
     e->cut_work.clear();
     e->cut_rows.clear();
+    if (c.resample) e->rsc_inq.resize((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         const vad_cut_item &it = c.items[i];
         if (it.sample_offset < 0 || (it.sample_offset & 3))
@@ -1809,7 +1824,8 @@ int cut_check(vad_engine *e, CutPlan &c) {
                            (long long)i, it.channel, c.channels);
         if (it.reserved != 0)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: reserved = %d must be 0", who, (long long)i, it.reserved);
-        const int64_t count = cut_samples(frame, it.nframes, hop, c.layout, out_frame);
+        const int64_t s_in = cut_samples(frame, it.nframes, hop, c.layout, out_frame);
+        const int64_t count = c.resample ? (s_in * vadk::rsc_L(c.sr_in) / vadk::rsc_M(c.sr_in)) & ~(int64_t)3 : s_in;
         if (!c.levels && (it.out_sample < 0 || (it.out_sample & 3) || it.out_sample > c.out_samples || count > c.out_samples - it.out_sample))
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: out_sample = %lld (+%lld samples) must be a multiple of 4 inside "
                            "the output of %lld samples", who, (long long)i, (long long)it.out_sample, (long long)count, (long long)c.out_samples);
@@ -1829,6 +1845,14 @@ int cut_check(vad_engine *e, CutPlan &c) {
             c.rows += it.nframes;
             if (c.rows > INT32_MAX)
                 return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 frames in one call", who);
+            continue;
+        }
+        if (c.resample) {
+            e->rsc_inq[(size_t)i] = (uint32_t)(s_in >> 2);
+            for (uint32_t q = 0; q < nq; q += vadk::RSC_WG_SAMPLES / 4) e->cut_work.push_back(vadk::CutWork{(uint32_t)i, q});
+            if (e->cut_work.size() > (size_t)INT32_MAX)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d samples in one call", who,
+                               VAD_RESAMPLE_CUT_WG_SAMPLES);
             continue;
         }
         if (c.render || c.mel) continue;     // its workgroups follow the output, not the segments: render_regions (mel: the tiles)
@@ -2262,6 +2286,54 @@ int mel_operator(vad_engine *e, const vad_mel *m, const float *op_re, const floa
     return VAD_OK;
 }
 
+// the frames and rows of every segment of `segs` (nquads: its samples / 4; quad_out becomes its first row) and one workgroup per
+// tile of MEL_TILE frames in e->mel_work; *rows: the total
+int mel_tiles(vad_engine *e, const char *who, const vad_mel *m, std::vector<vadk::CutSeg> &segs, int64_t *rows_out) {
+    e->mel_work.clear();
+    int64_t rows = 0;
+    for (size_t i = 0; i < segs.size(); ++i) {
+        vadk::CutSeg &sg = segs[i];
+        const int64_t S = (int64_t)sg.nquads << 2;
+        if (m->pad == VAD_MEL_PAD_REFLECT && S <= m->n_fft / 2)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld has %lld samples: reflect padding needs more than n_fft / 2 = %d",
+                           who, (long long)i, (long long)S, m->n_fft / 2);
+        const int64_t M = mel_frames(m, S);
+        sg.quad_out = (uint64_t)rows;
+        rows += M;
+        if ((int64_t)e->mel_work.size() + (M + vadk::MEL_TILE - 1) / vadk::MEL_TILE > (int64_t)INT32_MAX)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d frames in one call", who, vadk::MEL_TILE);
+        for (int64_t f = 0; f < M; f += vadk::MEL_TILE) e->mel_work.push_back(vadk::MelWork{(uint32_t)i, (uint32_t)f});
+    }
+    *rows_out = rows;
+    return VAD_OK;
+}
+
+// the launch of vadk_seg_mel over a block on the device, its tables (device pointers) and the packed operator in e->d_mel
+int mel_launch(vad_engine *e, const vad_mel *m, const void *d_audio, size_t audio_bytes, int fmt, int32_t channels, float thr, float *d_out,
+               const vadk::CutSeg *d_segs, const vadk::MelWork *d_work, hipStream_t s) {
+    vadk::MelArgs a{};
+    a.audio = d_audio;
+    a.out = d_out;
+    a.segs = d_segs;
+    a.work = d_work;
+    a.bins_pad = vadk::mel_pad16((uint32_t)m->n_bins);
+    a.op = e->d_mel;
+    a.filters = e->d_mel + 2 * (size_t)m->n_fft * a.bins_pad;
+    a.audio_bytes = (uint32_t)audio_bytes;
+    a.nwork = (uint32_t)e->mel_work.size();
+    a.n_fft = (uint32_t)m->n_fft;
+    a.hop = (uint32_t)m->hop;
+    a.n_mels = (uint32_t)m->n_mels;
+    a.pad = m->pad;
+    a.log = m->log;
+    a.floor = m->floor;
+    a.thresh = thr;
+    a.fmt = fmt;
+    a.channels = channels;
+    const hipError_t r = vadk_launch_seg_mel(&a, s);
+    return r != hipSuccess ? e->hip_fail(r, "kernel launch (segment mel)") : VAD_OK;
+}
+
 // vad_scan_mel / _device with e->mu held: the call's own checks, cut_check's refusals under this name (the segments tabled as for
 // the levels: the sample range once, no out_sample), the frames and rows of every segment and one workgroup per tile of MEL_TILE
 // frames, then the block as the cuts find it, the operator (mel_operator), one upload of the tables - segments, workgroups, in this
@@ -2277,21 +2349,8 @@ int mel_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items,
     c.mel = true;
     if (int rc = cut_check(e, c)) return rc;
     if (n == 0) return VAD_OK;
-    e->mel_work.clear();
     int64_t rows = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        vadk::CutSeg &sg = e->cut_segs[(size_t)i];
-        const int64_t S = (int64_t)sg.nquads << 2;
-        if (m->pad == VAD_MEL_PAD_REFLECT && S <= m->n_fft / 2)
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld has %lld samples: reflect padding needs more than n_fft / 2 = %d",
-                           who, (long long)i, (long long)S, m->n_fft / 2);
-        const int64_t M = mel_frames(m, S);
-        sg.quad_out = (uint64_t)rows;
-        rows += M;
-        if ((int64_t)e->mel_work.size() + (M + vadk::MEL_TILE - 1) / vadk::MEL_TILE > (int64_t)INT32_MAX)
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d frames in one call", who, vadk::MEL_TILE);
-        for (int64_t f = 0; f < M; f += vadk::MEL_TILE) e->mel_work.push_back(vadk::MelWork{(uint32_t)i, (uint32_t)f});
-    }
+    if (int rc = mel_tiles(e, who, m, e->cut_segs, &rows)) return rc;
     if (rows > out_rows)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_rows = %lld, the segments have %lld rows", who, (long long)out_rows,
                        (long long)rows);
@@ -2313,27 +2372,8 @@ int mel_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items,
     }
     HIP_TRY(e, hipMemcpyAsync(e->d_cut, e->cut_segs.data(), sb, hipMemcpyHostToDevice, s));
     if (wb) HIP_TRY(e, hipMemcpyAsync(e->d_cut + sb, e->mel_work.data(), wb, hipMemcpyHostToDevice, s));
-    vadk::MelArgs a{};
-    a.audio = c.d_audio;
-    a.out = static_cast<float *>(c.d_out);
-    a.segs = reinterpret_cast<const vadk::CutSeg *>(e->d_cut);
-    a.work = reinterpret_cast<const vadk::MelWork *>(e->d_cut + sb);
-    a.bins_pad = vadk::mel_pad16((uint32_t)m->n_bins);
-    a.op = e->d_mel;
-    a.filters = e->d_mel + 2 * (size_t)m->n_fft * a.bins_pad;
-    a.audio_bytes = (uint32_t)c.ab;
-    a.nwork = (uint32_t)e->mel_work.size();
-    a.n_fft = (uint32_t)m->n_fft;
-    a.hop = (uint32_t)m->hop;
-    a.n_mels = (uint32_t)m->n_mels;
-    a.pad = m->pad;
-    a.log = m->log;
-    a.floor = m->floor;
-    a.thresh = thr;
-    a.fmt = fmt;
-    a.channels = channels;
-    const hipError_t r = vadk_launch_seg_mel(&a, s);
-    const int rc = r != hipSuccess ? e->hip_fail(r, "kernel launch (segment mel)") : VAD_OK;
+    const int rc = mel_launch(e, m, c.d_audio, c.ab, fmt, channels, thr, static_cast<float *>(c.d_out),
+                              reinterpret_cast<const vadk::CutSeg *>(e->d_cut), reinterpret_cast<const vadk::MelWork *>(e->d_cut + sb), s);
     if (dev) {
         // the launch reads the engine's tables: the next scan or cut waits for it, as behind vad_scan_device
         if (int rc2 = scan_mark_pending(e, s)) return rc2;
@@ -2345,9 +2385,197 @@ int mel_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items,
     return VAD_OK;
 }
 
+// what comes before the block's and the items' checks in vad_scan_resample_cut / vad_scan_rate_mel: the engine's frames, the input
+// rate (16000 has nothing to resample) and the taps
+int resample_cut_check(vad_engine *e, const char *who, int32_t sr_in, const float *taps, int32_t ntaps, int *chunk) {
+    if (e->frame_samples != VAD_FRAME_SAMPLES || e->sample_rate != 16000)
+        return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s: this engine runs an 8 kHz sub-model on %d-sample frames; "
+                       "resampled recordings need the 16 kHz one", who, e->frame_samples);
+    *chunk = sr_in == 16000 ? 0 : resample_chunk_len(sr_in);
+    if (*chunk == 0)
+        return e->fail(VAD_ERR_UNSUPPORTED, "Failed to resample audio from %dHz to 16000Hz: %s: supported input rates are 8000, 24000, 48000", sr_in, who);
+    if (!taps) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null taps", who);
+    if (ntaps < 1 || ntaps > VAD_RESAMPLE_CUT_MAX_TAPS || !(ntaps & 1))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: ntaps = %d must be odd, from 1 to %d", who, ntaps, VAD_RESAMPLE_CUT_MAX_TAPS);
+    for (int32_t k = 0; k < ntaps; ++k)
+        if (!std::isfinite(taps[k]))
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: taps[%d] is %s, a tap is a finite number", who, k,
+                           std::isnan(taps[k]) ? "NaN" : "infinite");
+    return VAD_OK;
+}
+
+// T of the taps in fragment order in e->d_rsc (vad_layout.h: rsc_pack_index), zeros outside the taps.  Cached against the bytes of
+// the previous call, as mel_operator is: the same rate and the same taps neither pack nor upload again
+int resample_cut_operator(vad_engine *e, int32_t sr_in, const float *taps, int32_t ntaps, hipStream_t s) {
+    const uint32_t L = vadk::rsc_L(sr_in), M = vadk::rsc_M(sr_in), K = vadk::rsc_K((uint32_t)ntaps, L, M);
+    if (e->rsc_packed && e->rsc_rate == sr_in && e->rsc_src.size() == (size_t)ntaps && !std::memcmp(e->rsc_src.data(), taps, sizeof(float) * (size_t)ntaps))
+        return VAD_OK;
+    e->rsc_packed = false;
+    if (int rc = ensure(e, e->d_rsc, e->d_rsc_cap, sizeof(float) * 16u * K)) return rc;
+    e->rsc_src.assign(taps, taps + ntaps);
+    e->rsc_pack.assign((size_t)16u * K, 0.0f);
+    for (uint32_t o = 0; o < 16u; ++o)
+        for (uint32_t n = 0; n < K; ++n) {
+            const int32_t t = vadk::rsc_tap(o, n, (uint32_t)ntaps, L, M);
+            if (t >= 0 && t < ntaps) e->rsc_pack[vadk::rsc_pack_index(o, n)] = taps[t];
+        }
+    HIP_TRY(e, hipMemcpyAsync(e->d_rsc, e->rsc_pack.data(), sizeof(float) * 16u * K, hipMemcpyHostToDevice, s));
+    e->rsc_rate = sr_in;
+    e->rsc_packed = true;
+    return VAD_OK;
+}
+
+// vad_scan_resample_cut / vad_scan_rate_mel and their _device forms with e->mu held.  The rate cut's plan with the resample flag:
+// its block and item refusals, segment table, block rules and output spans, with S16 samples per segment and one workgroup per
+// RSC_WG_SAMPLES outputs.  m != nullptr (vad_scan_rate_mel): no item's out_sample is read; the resample kernel writes the segments
+// back to back into e->d_rsc_mid, and vadk_seg_mel runs behind it on the same stream over that buffer as a mono float32 block - the
+// header's recipe - with its own segment table and tiles.  In e->d_cut: segments, mel segments, workgroups, mel tiles, input quads,
+// gains.
+int resample_cut_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const float *gains, const float *taps, int32_t ntaps,
+                     const void *audio, int64_t audio_samples, int32_t channels, int fmt, int32_t sr_in, int32_t hop, int32_t out_fmt, void *out,
+                     int64_t out_samples, void *stream, const vad_mel *m = nullptr, const float *op_re = nullptr, const float *op_im = nullptr,
+                     const float *filters = nullptr, bool mel = false) {
+    hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    int chunk = 0;
+    if (int rc = resample_cut_check(e, who, sr_in, taps, ntaps, &chunk)) return rc;
+    CutPlan c{who, items, n, audio_samples, channels, fmt, hop, -1.0f, VAD_CUT_RANGE, out_fmt, mel ? 0 : out_samples, chunk, sr_in, gains, mel, 0.0f};
+    c.mel = mel;
+    c.resample = true;
+    if (int rc = cut_check(e, c)) return rc;
+    if (mel)
+        if (int rc = mel_check(e, who, m, op_re, op_im, filters, out_samples)) return rc;
+    if (n == 0) return VAD_OK;
+    int64_t rows = 0, mid = 0;
+    if (mel) {
+        e->rsc_mel_segs.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i) {
+            vadk::CutSeg &sg = e->cut_segs[(size_t)i];
+            sg.quad_out = (uint64_t)mid >> 2;
+            e->rsc_mel_segs[(size_t)i] = vadk::CutSeg{(uint32_t)(mid >> 2) | (vadk::SCAN_LEFT << vadk::SCAN_MODE_SHIFT), sg.nquads, 0};
+            mid += (int64_t)sg.nquads << 2;
+            if (mid >= (int64_t)1 << 29)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the segments have 2^29 or more samples at 16 kHz in one call", who);
+        }
+        if (int rc = mel_tiles(e, who, m, e->rsc_mel_segs, &rows)) return rc;
+        if (rows > out_samples)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_rows = %lld, the segments have %lld rows", who, (long long)out_samples,
+                           (long long)rows);
+        if (rows > 0 && !out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    } else if (!out) {
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    }
+    const size_t out_bytes = mel ? (size_t)rows * (size_t)m->n_mels * sizeof(float) : 0;
+    if (dev) {
+        if (int rc = cut_block_device(e, c, audio, out)) return rc;
+    } else {
+        if (int rc = cut_block_host(e, c, audio)) return rc;
+        if (mel) {
+            if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, out_bytes)) return rc;
+            c.d_out = e->d_cut_out;
+        }
+    }
+    if (mel)
+        if (int rc = ensure(e, e->d_rsc_mid, e->d_rsc_mid_cap, (size_t)mid * sizeof(float))) return rc;
+    const size_t sb = sizeof(vadk::CutSeg) * e->cut_segs.size(), msb = mel ? sb : 0, wb = sizeof(vadk::CutWork) * e->cut_work.size();
+    const size_t mwb = mel ? sizeof(vadk::MelWork) * e->mel_work.size() : 0, ib = sizeof(uint32_t) * e->rsc_inq.size();
+    const size_t gb = gains ? sizeof(float) * e->cut_gains.size() : 0;
+    if (int rc = ensure(e, e->d_cut, e->d_cut_cap, sb + msb + wb + mwb + ib + gb)) return rc;
+    if (int rc = resample_cut_operator(e, sr_in, taps, ntaps, s)) return rc;
+    if (mel)
+        if (int rc = mel_operator(e, m, op_re, op_im, filters, s)) return rc;
+    if (!dev && audio) {
+        HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, c.ab, hipMemcpyHostToDevice, s));
+        set_resident(e, c.ab, c.channels, c.fmt, sr_in);
+    }
+    uint8_t *t = e->d_cut;
+    HIP_TRY(e, hipMemcpyAsync(t, e->cut_segs.data(), sb, hipMemcpyHostToDevice, s));
+    if (msb) HIP_TRY(e, hipMemcpyAsync(t + sb, e->rsc_mel_segs.data(), msb, hipMemcpyHostToDevice, s));
+    HIP_TRY(e, hipMemcpyAsync(t + sb + msb, e->cut_work.data(), wb, hipMemcpyHostToDevice, s));
+    if (mwb) HIP_TRY(e, hipMemcpyAsync(t + sb + msb + wb, e->mel_work.data(), mwb, hipMemcpyHostToDevice, s));
+    HIP_TRY(e, hipMemcpyAsync(t + sb + msb + wb + mwb, e->rsc_inq.data(), ib, hipMemcpyHostToDevice, s));
+    if (gb) HIP_TRY(e, hipMemcpyAsync(t + sb + msb + wb + mwb + ib, e->cut_gains.data(), gb, hipMemcpyHostToDevice, s));
+    const uint32_t L = vadk::rsc_L(sr_in), M = vadk::rsc_M(sr_in);
+    vadk::ResampleCutArgs a{};
+    a.audio = c.d_audio;
+    a.out = mel ? static_cast<void *>(e->d_rsc_mid) : c.d_out;
+    a.segs = reinterpret_cast<const vadk::CutSeg *>(t);
+    a.inq = reinterpret_cast<const uint32_t *>(t + sb + msb + wb + mwb);
+    a.work = reinterpret_cast<const vadk::CutWork *>(t + sb + msb);
+    a.gains = gb ? reinterpret_cast<const float *>(t + sb + msb + wb + mwb + ib) : nullptr;
+    a.op = e->d_rsc;
+    a.audio_bytes = (uint32_t)c.ab;
+    a.nwork = (uint32_t)e->cut_work.size();
+    a.ksteps = vadk::rsc_K((uint32_t)ntaps, L, M) >> 4;
+    a.n0 = vadk::rsc_n0((uint32_t)ntaps, L);
+    a.fmt = fmt;
+    a.channels = channels;
+    a.out_fmt = mel ? VAD_CUT_F32 : out_fmt;
+    a.sr_in = sr_in;
+    const hipError_t r = vadk_launch_resample_cut(&a, s);
+    int rc = r != hipSuccess ? e->hip_fail(r, "kernel launch (resample cut)") : VAD_OK;
+    if (!rc && mel)
+        rc = mel_launch(e, m, e->d_rsc_mid, (size_t)mid * sizeof(float), VAD_FMT_F32, 1, -1.0f, static_cast<float *>(c.d_out),
+                        reinterpret_cast<const vadk::CutSeg *>(t + sb), reinterpret_cast<const vadk::MelWork *>(t + sb + msb + wb), s);
+    if (dev) {
+        // the launches read the engine's tables and buffers: the next scan or cut waits for them, as behind vad_scan_device
+        if (int rc2 = scan_mark_pending(e, s)) return rc2;
+        return rc;
+    }
+    if (rc) return rc;
+    if (!mel) return cut_copy_back(e, c, out, s);
+    if (out_bytes) HIP_TRY(e, hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    return VAD_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t vad_resample_cut_samples(const vad_engine *e, int64_t nframes, int32_t sr_in, int32_t hop) {
+    if (sr_in == 16000) return -1;
+    const int64_t s_in = vad_rate_cut_samples(e, nframes, sr_in, hop, VAD_CUT_RANGE);
+    if (s_in < 0) return -1;
+    return (s_in * vadk::rsc_L(sr_in) / vadk::rsc_M(sr_in)) & ~(int64_t)3;
+}
+
+int vad_scan_resample_cut(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const float *taps, int32_t ntaps, const void *audio,
+                          int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, int32_t out_fmt, void *out,
+                          int64_t out_samples) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return resample_cut_run(e, false, "vad_scan_resample_cut", items, n, gains, taps, ntaps, audio, audio_samples, channels, frame_fmt, sr_in, hop,
+                            out_fmt, out, out_samples, nullptr);
+}
+
+int vad_scan_resample_cut_device(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const float *taps, int32_t ntaps,
+                                 const void *d_audio, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop,
+                                 int32_t out_fmt, void *d_out, int64_t out_samples, void *stream) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return resample_cut_run(e, true, "vad_scan_resample_cut_device", items, n, gains, taps, ntaps, d_audio, audio_samples, channels, frame_fmt, sr_in,
+                            hop, out_fmt, d_out, out_samples, stream);
+}
+
+int vad_scan_rate_mel(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re, const float *op_im,
+                      const float *filters, const float *taps, int32_t ntaps, const void *audio, int64_t audio_samples, int32_t channels,
+                      int frame_fmt, int32_t sr_in, int32_t hop, float *out, int64_t out_rows) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return resample_cut_run(e, false, "vad_scan_rate_mel", items, n, nullptr, taps, ntaps, audio, audio_samples, channels, frame_fmt, sr_in, hop,
+                            VAD_CUT_F32, out, out_rows, nullptr, m, op_re, op_im, filters, true);
+}
+
+int vad_scan_rate_mel_device(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re, const float *op_im,
+                             const float *filters, const float *taps, int32_t ntaps, const void *d_audio, int64_t audio_samples,
+                             int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float *d_out, int64_t out_rows, void *stream) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return resample_cut_run(e, true, "vad_scan_rate_mel_device", items, n, nullptr, taps, ntaps, d_audio, audio_samples, channels, frame_fmt, sr_in,
+                            hop, VAD_CUT_F32, d_out, out_rows, stream, m, op_re, op_im, filters, true);
+}
 
 int64_t vad_mel_frames(const vad_mel *m, int64_t nsamples) {
     if (!m || mel_bad_field(m) || nsamples < 0 || nsamples > (INT64_MAX >> 1)) return -1;

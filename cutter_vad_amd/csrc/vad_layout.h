@@ -349,6 +349,59 @@ struct MelArgs {
 };
 static_assert(sizeof(MelArgs) == 96, "MelArgs layout");
 
+// finished segments of a rate block as one continuous signal at 16 kHz (csrc/scan_resample_cut.hip: vadk_resample_cut;
+// vad_scan_resample_cut).  L / M = 16000 / sr_in; A = 16 M / L input samples advance under 16 outputs.  A workgroup of RSC_THREADS
+// threads serves RSC_WG_SAMPLES consecutive outputs of ONE segment - RSC_WG_SAMPLES / 256 tiles of 16 row-blocks x 16 outputs, two per
+// wave; the host lists the workgroups as CutWork (quad0: the first OUTPUT quad) next to the segments, which are CutSeg with nquads =
+// S16 / 4, and the segments' INPUT quads (inq).  Output o of row-block r of a tile is
+//     D[o][r] = sum over n < K of T[o][n] * xs[A r + n],   T[o][n] = h[o M - (n - n0) L + C]  (0 outside the taps)
+// where xs starts n0 samples ahead of the tile's first input sample: n0 = C / L rounded up to a multiple of 4 (so that the span
+// starts on a quad), K = n0 + (15 M + C) / L + 1 in whole k-steps of 16.  T is the A operand of v_mfma_f32_16x16x4_f32, packed by the
+// host in fragment order - one float4 per lane and four k-steps: [n >> 4][lane = (n & 3) << 4 | o]{n >> 2 & 3}.
+// LDS: local sample j of the span at float j + RSC_SKEW * (j / A), so that row-block r's sample n is r (A + 4) + n + 4 (n / A) and
+// the 16 row-blocks x 4 k of a B fragment (stride A + 4 = 4 * odd between row-blocks, 1 between k) fall into 64 different banks.
+constexpr int RSC_THREADS = 256;
+constexpr int RSC_WG_SAMPLES = 2048;
+constexpr uint32_t RSC_SKEW = 4;
+__host__ __device__ inline uint32_t rsc_L(int32_t sr_in) { return sr_in == 48000 ? 1u : 2u; }
+__host__ __device__ inline uint32_t rsc_M(int32_t sr_in) { return sr_in == 8000 ? 1u : 3u; }
+__host__ __device__ inline uint32_t rsc_A(int32_t sr_in) { return 16u * rsc_M(sr_in) / rsc_L(sr_in); }
+__host__ __device__ inline uint32_t rsc_n0(uint32_t ntaps, uint32_t L) { return (((ntaps - 1u) / 2u) / L + 3u) & ~3u; }
+__host__ __device__ inline uint32_t rsc_K(uint32_t ntaps, uint32_t L, uint32_t M) {
+    return (rsc_n0(ntaps, L) + (15u * M + (ntaps - 1u) / 2u) / L + 1u + 15u) & ~15u;
+}
+// index into the taps of T[o][n], in [0, ntaps) or outside
+__host__ __device__ inline int32_t rsc_tap(uint32_t o, uint32_t n, uint32_t ntaps, uint32_t L, uint32_t M) {
+    return (int32_t)(o * M) - ((int32_t)n - (int32_t)rsc_n0(ntaps, L)) * (int32_t)L + (int32_t)((ntaps - 1u) / 2u);
+}
+// float index of T[o][n] in the packed operator
+__host__ __device__ inline size_t rsc_pack_index(uint32_t o, uint32_t n) {
+    return (((size_t)(n >> 4) * 64u) + (((n & 3u) << 4) | o)) * 4u + ((n >> 2) & 3u);
+}
+// floats of a workgroup's span in LDS
+__host__ __device__ inline uint32_t rsc_lds_floats(uint32_t A, uint32_t K) {
+    const uint32_t span = (RSC_WG_SAMPLES / 16) * A + K;
+    return span + RSC_SKEW * ((span + A - 1u) / A);
+}
+struct ResampleCutArgs {
+    const void *audio;        // the rate block, in its wire format
+    void *out;                // int16 or float32 samples at 16 kHz
+    const CutSeg *segs;       // quad_in: the segment's first input quad | mode; nquads: S16 / 4; quad_out: out_sample / 4
+    const uint32_t *inq;      // [segments]: S_in / 4
+    const CutWork *work;      // [nwork]: one entry per workgroup, quad0 a multiple of RSC_WG_SAMPLES / 4
+    const float *gains;       // [segments], or nullptr
+    const float *op;          // the packed T: 16 K floats
+    uint32_t audio_bytes;     // of the block
+    uint32_t nwork;
+    uint32_t ksteps;          // K / 16
+    uint32_t n0;
+    int32_t fmt;              // vad_frame_format
+    int32_t channels;         // 1 or 2
+    int32_t out_fmt;          // 0 = int16 PCM, 1 = float32
+    int32_t sr_in;            // 8000, 24000 or 48000
+};
+static_assert(sizeof(ResampleCutArgs) == 88, "ResampleCutArgs layout");
+
 // one finished piece of audio out of a scanned block (csrc/scan_render.hip: vadk_scan_render; vad_scan_render).  The kernel is
 // driven by the OUTPUT: the host sweeps the segments' output spans into regions - maximal runs of output quads covered by the same
 // none, one or two segments - and lists a workgroup per CUT_WG_QUADS quads of a region, so the kind of a workgroup is uniform.

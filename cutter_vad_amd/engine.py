@@ -812,6 +812,72 @@ class Engine:
             self._check(self._lib.vad_scan_cut_device(self._h, items, n, *where, hop, *res))
         return start
 
+    # ------------------------------------------------------------------ segment audio at 16 kHz from a rate block
+    @staticmethod
+    def _resample_taps(rate: int, taps) -> np.ndarray:
+        if taps is None:
+            from .scan import resample_taps
+            return resample_taps(rate)
+        return np.ascontiguousarray(np.asarray(taps, np.float32).reshape(-1))
+
+    def resample_cut_samples(self, nframes: int, sample_rate: int, hop: Optional[int] = None) -> int:
+        """Samples at 16 kHz of a segment of ``nframes`` chunks of a block at ``sample_rate`` (``vad_resample_cut_samples``): ``(nframes
+        - 1) * hop + chunk`` input samples times 16000 / ``sample_rate``, rounded down to a multiple of 4; -1: bad arguments."""
+        hop = self.scan_chunk_samples(sample_rate) // 2 if hop is None else int(hop)
+        return int(self._lib.vad_resample_cut_samples(self._h, int(nframes), int(sample_rate), hop))
+
+    def _resample_items(self, segments, rate: int, hop: int, channels: int, out_samples=None):
+        """``_cut_items`` for ``resample_cut``: a segment's count is ``resample_cut_samples`` of its frames"""
+        segs = [tuple(sg) for sg in segments]
+        items, _ = self._cut_items(segs, hop, _ffi.VAD_CUT_RANGE, channels, None, rate=rate)
+        start = np.zeros(len(segs) + 1, np.int64)
+        for i, sg in enumerate(segs):
+            items[i].out_sample = int(start[i]) if out_samples is None else int(out_samples[i])
+            start[i + 1] = start[i] + max(int(self._lib.vad_resample_cut_samples(self._h, int(sg[2]), rate, hop)), 0)
+        return items, start
+
+    def resample_cut(self, segments, sample_rate: int, taps=None, hop: Optional[int] = None, out="pcm16", audio=None,
+                     law: Optional[str] = None, i16_scale: int = 32767, gains=None):
+        """The audio of finished segments of a block at ``sample_rate`` (8000, 24000 or 48000 Hz) as one continuous signal each at
+        16 kHz (``vad_scan_resample_cut``): the samples ``cut(segments, layout="range", out="f32", sample_rate=...)`` gives - decoded,
+        channel-selected, never gated - zero-extended at the segment's edges and filtered by the polyphase FIR of ``taps`` (odd, at most
+        511 float32 at rate ``L * sample_rate``; default: ``cutter_vad_amd.scan.resample_taps(sample_rate)``), as
+        ``scipy.signal.resample_poly(x, L, M, window=taps)`` does on the cut.  -> (data, start) as ``cut``; a segment has
+        ``resample_cut_samples`` samples.  ``audio``, ``law``, ``i16_scale``, ``gains`` and the ``scan_session()`` rule as in ``cut``:
+        ``audio=None`` is the block ``scan_segments(sample_rate=...)`` left on the GPU."""
+        of = self._cut_enum(_ffi.CUT_OUTPUTS, "out", out)
+        rate = int(sample_rate)
+        h = self._resample_taps(rate, taps)
+        with self._scan_lock:
+            _sr, total, channels, fmt, ptr, _keep = self._cut_block("resample_cut", audio, law, i16_scale, sample_rate)
+            hop = self.scan_chunk_samples(rate) // 2 if hop is None else int(hop)
+            items, start = self._resample_items(segments, rate, hop, channels)
+            n = len(start) - 1
+            data = np.empty(int(start[-1]), np.int16 if of == _ffi.VAD_CUT_PCM16 else np.float32)
+            g = None if gains is None else self._cut_gains(gains, n)
+            self._check(self._lib.vad_scan_resample_cut(self._h, items, n, None if g is None else _ptr(g, C.c_float), _ptr(h, C.c_float), h.size,
+                                                        ptr, total, channels, fmt, rate, hop, of, data.ctypes.data_as(C.c_void_p), data.size))
+        return data, start
+
+    def resample_cut_device(self, segments, sample_rate: int, d_audio: int, audio_samples: int, d_out: int, out_samples: int, taps=None,
+                            hop: Optional[int] = None, fmt: int = _ffi.VAD_FMT_F32, channels: int = 1, out="pcm16", stream: int = 0,
+                            out_start=None, gains=None) -> np.ndarray:
+        """``resample_cut`` on device pointers (integers; ``vad_scan_resample_cut_device``): the block at ``d_audio`` as ``cut_device``
+        takes it, the payloads to ``d_out`` (16-byte aligned, room for ``out_samples`` samples), packed in the order listed or at
+        ``out_start[i]`` (multiples of 4).  ``taps`` and ``gains`` are host arrays, read before the call returns.  Asynchronous on
+        ``stream``.  -> start [n + 1] of the packed order."""
+        of = self._cut_enum(_ffi.CUT_OUTPUTS, "out", out)
+        rate = int(sample_rate)
+        h = self._resample_taps(rate, taps)
+        hop = self.scan_chunk_samples(rate) // 2 if hop is None else int(hop)
+        items, start = self._resample_items(segments, rate, hop, int(channels), out_start)
+        n = len(start) - 1
+        g = None if gains is None else self._cut_gains(gains, n)
+        self._check(self._lib.vad_scan_resample_cut_device(self._h, items, n, None if g is None else _ptr(g, C.c_float), _ptr(h, C.c_float), h.size,
+                                                           d_audio or None, int(audio_samples), int(channels), int(fmt), rate, hop, of,
+                                                           d_out or None, int(out_samples), stream or None))
+        return start
+
     # ------------------------------------------------------------------ segment levels
     def levels(self, segments, hop: Optional[int] = None, denoise: Optional[float] = 0.01, clip: float = 0.95, audio=None,
                law: Optional[str] = None, i16_scale: int = 32767, sample_rate: Optional[int] = None) -> np.ndarray:
@@ -879,15 +945,40 @@ class Engine:
             start[i + 1] = start[i] + max(rows, 0)      # (-1: the call itself refuses the segment, by name)
         return start
 
+    def _mel_rows_16k(self, m, segments, hop: int, rate: int) -> np.ndarray:
+        start = np.zeros(len(segments) + 1, np.int64)
+        for i, sg in enumerate(segments):
+            s16 = int(self._lib.vad_resample_cut_samples(self._h, int(sg[2]), rate, hop)) if len(sg) > 2 else -1
+            rows = int(self._lib.vad_mel_frames(C.byref(m), s16)) if s16 >= 0 else 0
+            start[i + 1] = start[i] + max(rows, 0)      # (-1: the call itself refuses the segment, by name)
+        return start
+
     def mel(self, segments, spec, hop: Optional[int] = None, denoise: Optional[float] = 0.01, audio=None, law: Optional[str] = None,
-            i16_scale: int = 32767):
+            i16_scale: int = 32767, sample_rate: Optional[int] = None, taps=None):
         """Log-mel frames of finished segments (``vad_scan_mel``), computed on the GPU from the block: ``segments`` as in ``cut``,
         ``spec`` a ``cutter_vad_amd.scan.MelSpec`` or ``(fields, op_re, op_im, filters)`` (``_mel_arrays``).  -> ``(features
         [rows, n_mels] float32, start [n + 1])``: segment i's frames are ``features[start[i]:start[i + 1]]``, computed from exactly
         the float32 values ``cut(segments, layout="range", out="f32")`` with the same arguments gives.  ``hop`` is the SCAN's hop
         (the segments' frames), not the analysis hop, which is the spec's.  ``audio``, ``law``, ``i16_scale`` and the
-        ``scan_session()`` rule as in ``cut``; blocks at the engine's own rate only.  Segments may share samples."""
+        ``scan_session()`` rule as in ``cut``.  Segments may share samples.
+        ``sample_rate`` (``vad_scan_rate_mel``), given and not the engine's: the block is at 8000, 24000 or 48000 Hz, and the
+        features are those of each segment's 16 kHz signal as ``resample_cut(segments, sample_rate, taps, out="f32")`` gives it -
+        never gated (``denoise`` is not read), computed on the GPU without the signal crossing the link.  ``taps`` as there."""
         m, op_re, op_im, filters = self._mel_arrays(spec)
+        rate = self._scan_rate(sample_rate)
+        if rate is not None:
+            h = self._resample_taps(rate, taps)
+            with self._scan_lock:
+                sr, total, channels, fmt, ptr, _keep = self._cut_block("mel", audio, law, i16_scale, sample_rate)
+                hop = self.scan_chunk_samples(rate) // 2 if hop is None else int(hop)
+                segs = [tuple(sg) for sg in segments]
+                items, _ = self._cut_items(segs, hop, _ffi.VAD_CUT_RANGE, channels, rate=rate)
+                start = self._mel_rows_16k(m, segs, hop, rate)
+                out = np.empty((int(start[-1]), m.n_mels), np.float32)
+                self._check(self._lib.vad_scan_rate_mel(self._h, items, len(segs), C.byref(m), _ptr(op_re, C.c_float), _ptr(op_im, C.c_float),
+                                                        _ptr(filters, C.c_float), _ptr(h, C.c_float), h.size, ptr, total, channels, fmt, rate,
+                                                        hop, out.ctypes.data_as(C.POINTER(C.c_float)), int(start[-1])))
+            return out, start
         with self._scan_lock:
             sr, total, channels, fmt, ptr, _keep = self._cut_block("mel", audio, law, i16_scale, None)
             if sr is not None:
@@ -905,11 +996,25 @@ class Engine:
         return out, start
 
     def mel_device(self, segments, spec, d_audio: int, audio_samples: int, d_out: int, out_rows: int, hop: Optional[int] = None,
-                   fmt: int = _ffi.VAD_FMT_F32, channels: int = 1, denoise: Optional[float] = 0.01, stream: int = 0) -> np.ndarray:
+                   fmt: int = _ffi.VAD_FMT_F32, channels: int = 1, denoise: Optional[float] = 0.01, stream: int = 0,
+                   sample_rate: Optional[int] = None, taps=None) -> np.ndarray:
         """``mel`` on device pointers (integers; ``vad_scan_mel_device``): the block at ``d_audio`` as ``cut_device`` takes it, the
         rows to ``d_out`` (16-byte aligned, room for ``out_rows`` rows of ``n_mels`` float32).  The operators stay host arrays, read
-        before the call returns.  Asynchronous on ``stream``.  -> start [n + 1], the segments' first rows."""
+        before the call returns.  Asynchronous on ``stream``.  -> start [n + 1], the segments' first rows.  ``sample_rate`` and
+        ``taps`` as in ``mel`` (``vad_scan_rate_mel_device``)."""
         m, op_re, op_im, filters = self._mel_arrays(spec)
+        rate = self._scan_rate(sample_rate)
+        if rate is not None:
+            h = self._resample_taps(rate, taps)
+            hop = self.scan_chunk_samples(rate) // 2 if hop is None else int(hop)
+            segs = [tuple(sg) for sg in segments]
+            items, _ = self._cut_items(segs, hop, _ffi.VAD_CUT_RANGE, int(channels), rate=rate)
+            start = self._mel_rows_16k(m, segs, hop, rate)
+            self._check(self._lib.vad_scan_rate_mel_device(self._h, items, len(segs), C.byref(m), _ptr(op_re, C.c_float), _ptr(op_im, C.c_float),
+                                                           _ptr(filters, C.c_float), _ptr(h, C.c_float), h.size, d_audio or None,
+                                                           int(audio_samples), int(channels), int(fmt), rate, hop, d_out or None,
+                                                           int(out_rows), stream or None))
+            return start
         hop = self.frame_samples // 2 if hop is None else int(hop)
         segs = [tuple(sg) for sg in segments]
         items, _ = self._cut_items(segs, hop, _ffi.VAD_CUT_RANGE, int(channels))

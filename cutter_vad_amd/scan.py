@@ -119,6 +119,36 @@ def _need_stereo(engine, who: str, what: str) -> None:
                                  f"written from the block a scan left on the GPU), {type(engine).__name__} has none")
 
 
+def _need_resample(engine, who: str, what: str) -> None:
+    if not hasattr(engine, "resample_cut"):
+        raise ConfigurationError("sample_rate", "given", f"{who}: {what} needs an engine with resample_cut (the 16 kHz signal is filtered "
+                                 f"from the block a scan left on the GPU), {type(engine).__name__} has none")
+
+
+def resample_taps(sample_rate: int, half_width: int = 16, beta: float = 8.0, cutoff: Optional[float] = None) -> np.ndarray:
+    """The default low-pass of ``Engine.resample_cut`` for recordings at ``sample_rate`` (8000, 24000 or 48000 Hz): with ``L / M =
+    16000 / sample_rate`` in lowest terms, a Kaiser-windowed sinc at rate ``L * sample_rate`` of ``2 * half_width * max(L, M) + 1``
+    taps - ``half_width`` zero crossings of the sinc on either side at the default cutoff - with ``cutoff`` in Hz (default:
+    ``min(sample_rate, 16000) / 2``, the narrower Nyquist) and the window's ``beta``.  Designed in float64, scaled so that the taps
+    sum to ``L`` (every polyphase branch then sums to about 1: unit gain at DC), rounded once to float32.  The defaults give 65, 97
+    and 97 taps at 8, 24 and 48 kHz; ``scipy.signal.resample_poly(x, L, M, window=taps)`` applies the same filter."""
+    sr = int(sample_rate)
+    if sr not in (8000, 24000, 48000):
+        raise ConfigurationError("sample_rate", repr(sample_rate), f"resample_taps: recordings at 8000, 24000 or 48000 Hz, got {sample_rate!r}")
+    L, M = (2, 1) if sr == 8000 else (2, 3) if sr == 24000 else (1, 3)
+    half_width = int(half_width)
+    n = 2 * half_width * max(L, M) + 1
+    if half_width < 0 or n > _ffi.VAD_RESAMPLE_CUT_MAX_TAPS:
+        raise ConfigurationError("half_width", repr(half_width), f"resample_taps: 2 * half_width * {max(L, M)} + 1 taps must be 1 .. "
+                                 f"{_ffi.VAD_RESAMPLE_CUT_MAX_TAPS}, got half_width = {half_width}")
+    fc = min(sr, 16000) / 2.0 if cutoff is None else float(cutoff)
+    if not 0.0 < fc <= min(sr, 16000) / 2.0:
+        raise ConfigurationError("cutoff", repr(cutoff), f"resample_taps: 0 < cutoff <= {min(sr, 16000) / 2.0} Hz, got {cutoff!r}")
+    t = np.arange(n, dtype=np.float64) - (n - 1) // 2
+    h = np.sinc(2.0 * fc / (L * sr) * t) * np.kaiser(n, float(beta))
+    return (h * (L / h.sum())).astype(np.float32)
+
+
 def _keep_channels_check(who: str, split: bool) -> None:
     if split:
         raise ConfigurationError("keep_channels", "True", f"{who}: keep_channels=True delivers both channels of a recording in one payload; "
@@ -391,7 +421,7 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
 def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
                    law: Optional[str] = None, channel="mix", layout: str = "frames", wav: bool = True,
                    sample_rate: Optional[int] = None, open_end: bool = False, refine: Optional[SegmentRefine] = None,
-                   normalize: Optional[float] = None, keep_channels: bool = False) -> List:
+                   normalize: Optional[float] = None, keep_channels: bool = False, resample=False) -> List:
     """``scan_recordings`` with each finished segment's audio: per recording ``[(start_sample, end_sample, payload), ...]`` (per
     channel for ``"split"``, as there).  ``payload`` is what ``VADWrapper``'s ``voice_end`` callback delivers for the same
     recording - the segment's frames back to back, decoded, mixed and gated as the model read them, as 16-bit PCM behind the WAV
@@ -416,7 +446,14 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
     ``[k, 2]`` int16 array or a WAV with a two-channel header.  ``layout="frames"`` with a ``sample_rate`` other than the engine's
     is a ``ConfigurationError``: use ``layout="range"``.  ``normalize`` then divides by the larger of the segment's two channel
     peaks (one ``Engine.levels`` call listing every segment for channel 0 and for channel 1): one factor for both channels, which
-    keeps their balance.  1-D recordings of the same corpus are cut as without it."""
+    keeps their balance.  1-D recordings of the same corpus are cut as without it.
+    ``resample``: ``True`` or a taps array (``Engine.resample_cut``'s ``taps``; ``True``: ``resample_taps(sample_rate)``) delivers
+    each segment of recordings at another rate as ONE continuous signal at the engine's rate: it needs a ``sample_rate`` other than
+    the engine's and ``layout="range"`` (else ``ConfigurationError``).  The ranges stay in input-rate samples; the payload is the
+    16 kHz PCM (``Engine.resample_cut_samples`` samples) behind a header of the engine's rate.  ``normalize`` then divides by the
+    INPUT-rate peak of ``Engine.levels``: the peak of the resampled signal can differ slightly (the filter overshoots between
+    samples), and PCM16 saturates where it exceeds full scale.  With ``keep_channels=True``: ``ConfigurationError`` (two-channel
+    resampled output is not built)."""
     from .pool import default_pool, resolve_model_path
     from .utils.wav_writer import WAVWriter
     split = isinstance(channel, str) and channel == "split"
@@ -442,6 +479,17 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
         raise ConfigurationError(f"cut_recordings frames at the model's frame size: buffer_size = {cfg.buffer_size}, "
                                  f"the engine's frames have {frame} samples")
     rate = None if sample_rate is None or int(sample_rate) == int(engine.sample_rate) else int(sample_rate)
+    resampled = resample is not False and resample is not None
+    if resampled:
+        if rate is None or layout != "range":
+            raise ConfigurationError("resample", "given", f"cut_recordings: resample= delivers the sample range of recordings at another "
+                                     f"rate than the engine's at {engine.sample_rate} Hz: it needs sample_rate= (got {sample_rate!r}) and "
+                                     f"layout=\"range\" (got {layout!r})")
+        if keep_channels:
+            raise ConfigurationError("resample", "given", "cut_recordings: resample= with keep_channels=True: two-channel resampled "
+                                     "output is not supported")
+        _need_resample(engine, "cut_recordings", "resample=")
+    taps = None if resample is True or not resampled else resample
     if rate is not None:
         if rate not in (8000, 16000, 24000, 48000):
             raise ConfigurationError("sample_rate", repr(sample_rate), f"cut_recordings: recordings at 8000, 16000, 24000 or 48000 Hz, got {sample_rate!r}")
@@ -453,7 +501,7 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
     recordings = [np.asarray(r) for r in recordings]
     if not recordings:
         return []
-    writer = WAVWriter(rate if rate is not None and layout == "range" else cfg.output_wav_sample_rate, 16, 1)
+    writer = WAVWriter(int(engine.sample_rate) if resampled else rate if rate is not None and layout == "range" else cfg.output_wav_sample_rate, 16, 1)
     writer2 = WAVWriter(writer.sample_rate, 16, 2) if keep_channels else None
     denoise = 0.01 if cfg.enable_denoising else None
     out: List = [None] * len(recordings)
@@ -481,7 +529,12 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
                     peak = engine.levels(table, hop=hop, denoise=denoise)["peak"]
                     usable = np.isfinite(peak) & (peak > 0)
                     gains = np.where(usable, np.float32(normalize) / np.where(usable, peak, np.float32(1)), np.float32(1)).astype(np.float32)
-                    data, start = engine.cut(table, hop=hop, denoise=denoise, layout=layout, gains=gains)
+                    if resampled:
+                        data, start = engine.resample_cut(table, rate, taps, hop=hop, gains=gains)
+                    else:
+                        data, start = engine.cut(table, hop=hop, denoise=denoise, layout=layout, gains=gains)
+                elif table and resampled:
+                    data, start = engine.resample_cut(table, rate, taps, hop=hop)
                 elif table:
                     data, start = engine.cut(table, hop=hop, denoise=denoise, layout=layout)
         finally:
@@ -743,14 +796,18 @@ def _need_mel(engine, who: str) -> None:
 
 def features_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, config: Optional[VADConfig] = None, engine=None,
                         hop: Optional[int] = None, law: Optional[str] = None, channel="mix", open_end: bool = False,
-                        refine: Optional[SegmentRefine] = None) -> List:
+                        refine: Optional[SegmentRefine] = None, sample_rate: Optional[int] = None, taps=None) -> List:
     """``scan_recordings`` with each finished segment's log-mel frames: per recording ``[(start_sample, end_sample,
     features [M, n_mels] float32), ...]`` (per channel for ``"split"``, as there).  The features are those of the samples
     ``cut_recordings(layout="range")`` cuts - decoded, mixed and gated as the model read them - computed on the GPU from the block
     the scan left there (one scan and one ``Engine.mel(audio=None)`` under ``Engine.scan_session()``; two of each for a corpus of 1-D
     and 2-D recordings): no sample crosses the link back.  ``hop`` is the scan's; the analysis hop is ``spec.hop``.
     ``open_end`` and ``refine`` as in ``scan_recordings``.  An engine object without ``mel``: ``ConfigurationError``; so is a
-    ``spec.sample_rate`` other than the engine's (recordings at other rates are not resampled for features)."""
+    ``spec.sample_rate`` other than the engine's.
+    ``sample_rate``: the recordings are at 8000, 24000 or 48000 Hz - the scan is the rate scan, ``hop`` and the ranges count
+    INPUT-rate samples, and the features are those of each segment's 16 kHz signal (``Engine.mel(sample_rate=..., taps=...)``:
+    ``Engine.resample_cut``'s samples, never gated), so ``spec.sample_rate`` is still the engine's.  ``taps`` as in
+    ``Engine.resample_cut``.  An engine object without ``resample_cut``: ``ConfigurationError``."""
     from .pool import default_pool, resolve_model_path
     who = "features_recordings"
     split = isinstance(channel, str) and channel == "split"
@@ -771,6 +828,14 @@ def features_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, config:
     if cfg.buffer_size != frame:
         raise ConfigurationError(f"{who} frames at the model's frame size: buffer_size = {cfg.buffer_size}, the engine's frames have "
                                  f"{frame} samples")
+    rate = None if sample_rate is None or int(sample_rate) == int(engine.sample_rate) else int(sample_rate)
+    mel_kw = {}
+    if rate is not None:
+        if rate not in (8000, 24000, 48000):
+            raise ConfigurationError("sample_rate", repr(sample_rate), f"{who}: recordings at 8000, 16000, 24000 or 48000 Hz, got {sample_rate!r}")
+        _need_resample(engine, who, "sample_rate=")
+        frame = engine.scan_chunk_samples(rate)      # the ranges count input samples
+        mel_kw = {"sample_rate": rate, "taps": taps}
     hop = frame // 2 if hop is None else int(hop)
     recordings = [np.asarray(r) for r in recordings]
     if not recordings:
@@ -788,11 +853,11 @@ def features_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, config:
         try:
             engine.set_thresholds_many(slots, _thresholds_of(cfg))
             with engine.scan_session():
-                ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, denoise, channel, open_end=open_end,
-                                      refine=refine)
+                ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, denoise, channel, rate=rate,
+                                      open_end=open_end, refine=refine)
                 table = _cut_table(engine, ranges, chans, frame, hop)
                 if table:
-                    data, start = engine.mel(table, arrays, hop=hop, denoise=denoise)
+                    data, start = engine.mel(table, arrays, hop=hop, denoise=denoise, **mel_kw)
         finally:
             for s in slots:
                 engine.close_stream(int(s))

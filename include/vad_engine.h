@@ -820,6 +820,74 @@ VAD_API int vad_scan_mel_device(vad_engine *e, const vad_cut_item *items, int64_
                                 float *d_out /*on the GPU: [out_rows][n_mels]*/, int64_t out_rows, void *stream);
 
 /*
+ * Segment audio and log-mel features at 16 kHz from a rate block: what comes after a VAD - mel front ends, waveform models, speaker
+ * embedders - runs at 16 kHz, and vad_scan_rate_cut(VAD_CUT_RANGE) returns a segment at the INPUT rate (VAD_CUT_FRAMES: overlapping
+ * frames, each resampled on its own - no continuous signal).  vad_scan_resample_cut writes the segment as ONE continuous signal at
+ * 16 kHz, by a polyphase FIR whose taps are the caller's; vad_scan_rate_mel computes vad_scan_mel's rows from that signal.
+ *
+ * THE RULE.  For item i of a rate block at sr_in (8000, 24000 or 48000):
+ *   - L / M = 16000 / sr_in in lowest terms: 2 / 1, 2 / 3, 1 / 3.
+ *   - x[k], k = 0 .. S_in - 1, are exactly the float32 values vad_scan_rate_cut(VAD_CUT_RANGE, VAD_CUT_F32) writes for the item:
+ *     decoded and channel-selected, never gated; S_in = (nframes - 1) * hop + chunk.
+ *   - x[k] = 0 outside that range, EVEN WHERE THE BLOCK HOLDS AUDIO THERE: zero extension at the segment's edges, as
+ *     scipy.signal.resample_poly does on a cut.  The result depends on the item alone.
+ *   - taps is a host float32 array h[0 .. N - 1], the prototype low-pass at rate L * sr_in: N odd, 1 <= N <=
+ *     VAD_RESAMPLE_CUT_MAX_TAPS, every entry finite; C = (N - 1) / 2.
+ *   - S16 = floor(S_in * L / M) rounded down to a multiple of 4 (vad_resample_cut_samples; -1 on the conditions of
+ *     vad_rate_cut_samples, and for sr_in == 16000).
+ *   - For m = 0 .. S16 - 1:  y[m] = sum over k of x[k] * h[m * M - k * L + C], over the k in [0, S_in) whose tap index lies in
+ *     [0, N).  All arithmetic is float32; the order of the sum is the kernel's own.  A sample is then y[m], or y[m] * gains[i] as one
+ *     float32 multiply of its own when gains != NULL.  The cut's conversion follows: VAD_CUT_F32 stores the value, VAD_CUT_PCM16 is
+ *     clip(. * 32767, -32768, 32767) toward zero.
+ *   With u = 2^-24 and D[m] = sum over k of |x[k]| |h[.]|:  |y - y_exact| <= (ceil(N / L) + 4) u D in ANY order of summation - at most
+ * ceil(N / L) terms are non-zero, and the structural zeros of a padded operator add no error.  Where every product and partial sum is
+ * an integer multiple of a power of two below 2^24 in magnitude the result is exact.
+ *
+ * vad_scan_resample_cut: items are vad_cut_item, frames count chunks; segment i owns out[out_sample .. out_sample + S16), out_sample
+ * a multiple of 4; overlapping output ranges are refused as in the cut, samples outside every range are not written.  audio == NULL
+ * names the resident RATE block exactly as vad_scan_rate_cut does; with an audio the call uploads it, and it becomes the resident
+ * rate block.  Works on every 16 kHz engine, Silero V4 and VAD_ENGINE_SHARED_GPU included; waits for earlier *_device launches.  No
+ * float atomics, every sum in a fixed order: two calls give the same bytes.
+ *   Refusals, each with a message under this function's name and nothing written: VAD_ERR_UNSUPPORTED for an engine of an 8 kHz
+ * sub-model and for any sr_in outside 8000 / 24000 / 48000 (16000: there is nothing to resample); a null taps, ntaps even or outside
+ * 1 .. VAD_RESAMPLE_CUT_MAX_TAPS, a tap that is NaN or infinite (the message names the lowest index); every block and item refusal of
+ * vad_scan_rate_cut, in the same words; a non-finite gain, in vad_scan_cut_gain's words.  n == 0: VAD_OK.
+ *   A workgroup of the kernel serves VAD_RESAMPLE_CUT_WG_SAMPLES consecutive output samples of one segment, loads its input span
+ * once and never issues a load outside the segment's own sample range.
+ *
+ * vad_scan_rate_mel: rows byte for byte what vad_scan_mel computes under this recipe - a mono float32 block at the engine's rate
+ * holds segment i's y[0 .. S16) (no gain) at a multiple-of-4 offset o_i; items are (o_i, 0, (S16 - 512) / 4 + 1, 0), hop = 4, gate
+ * off.  That is also how the engine runs it: the resample kernel writes into an engine-owned float32 buffer and vad_scan_mel's
+ * kernel runs behind it on the same stream.  Refusals: those of vad_scan_resample_cut that concern block, items and taps (no item's
+ * out_sample is read), then vad_scan_mel's for m, the operators and out_rows; a reflect-padded segment with S16 <= n_fft / 2; an
+ * intermediate of 2^29 samples or more.  The operator cache is vad_scan_mel's.
+ *   The _device forms take d_audio / d_out as the cuts' and vad_scan_mel_device's do, enqueue on `stream` (NULL = the engine's own)
+ * and return; gains, taps and the operators stay HOST arrays, read before the call returns.
+ *   VAD_ABI_VERSION is unchanged: the presence of vad_scan_resample_cut is how a caller detects the feature.
+ */
+#define VAD_RESAMPLE_CUT_MAX_TAPS 511
+#define VAD_RESAMPLE_CUT_WG_SAMPLES 2048
+VAD_API int64_t vad_resample_cut_samples(const vad_engine *e, int64_t nframes, int32_t sr_in, int32_t hop);
+VAD_API int vad_scan_resample_cut(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains /*host [n] or NULL*/,
+                                  const float *taps /*host [ntaps]*/, int32_t ntaps, const void *audio /*or NULL*/, int64_t audio_samples,
+                                  int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, int32_t out_fmt, void *out,
+                                  int64_t out_samples);
+VAD_API int vad_scan_resample_cut_device(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains /*host [n] or NULL*/,
+                                         const float *taps /*host [ntaps]*/, int32_t ntaps, const void *d_audio, int64_t audio_samples,
+                                         int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, int32_t out_fmt, void *d_out,
+                                         int64_t out_samples, void *stream);
+VAD_API int vad_scan_rate_mel(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re /*[n_fft][n_bins]*/,
+                              const float *op_im /*[n_fft][n_bins]*/, const float *filters /*[n_mels][n_bins]*/,
+                              const float *taps /*host [ntaps]*/, int32_t ntaps, const void *audio /*or NULL*/, int64_t audio_samples,
+                              int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float *out /*[out_rows][n_mels]*/,
+                              int64_t out_rows);
+VAD_API int vad_scan_rate_mel_device(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re /*host*/,
+                                     const float *op_im /*host*/, const float *filters /*host*/, const float *taps /*host [ntaps]*/,
+                                     int32_t ntaps, const void *d_audio, int64_t audio_samples, int32_t channels, int frame_fmt,
+                                     int32_t sr_in, int32_t hop, float *d_out /*on the GPU: [out_rows][n_mels]*/, int64_t out_rows,
+                                     void *stream);
+
+/*
  * Rendered audio: one finished piece of audio per call - the segments of a block faded at their edges, crossfaded where two of
  * them share output samples, joined, everything else silence.  The two standard products of a VAD come out of it by where the caller
  * places the segments: silence removal (the segments back to back, neighbours overlapping by the ramp or a fixed pause apart) and

@@ -1389,6 +1389,200 @@ def scan_mel():
     return row
 
 
+def scan_resample_cut():
+    """What segment audio and log-mel features at 16 kHz from 48 kHz recordings cost: VAD_SCAN_BENCH_N (default 1 024)
+    int16 recordings of 30 s at 48 kHz - the golden clip, every sample three times - hop = chunk / 2, resample_taps' default 97 taps,
+    in calls of VAD_SCAN_BENCH_PER_CALL (default 512) recordings: one call addresses under 2 GiB.  Per call, on the block its scan
+    (vad_scan_rate_segments, client thresholds) left on the GPU:
+      (1) vad_scan_resample_cut_device(F32) against vad_scan_cut_gain_device(RANGE, F32, sr_in = 48000, gains of 1) on the same table,
+          which only moves the samples: HIP events as scan_mel's (c);
+      (2) Engine.resample_cut(f32) against Engine.cut(range, f32, sample_rate=48000) + scipy.signal.resample_poly(x, 1, 3,
+          window=taps) on 16 host threads;
+      (3) Engine.mel(sample_rate=48000), Whisper's geometry, against route (2)'s host side followed by scan_mel's numpy float32 mel.
+    One warm-up, then three timed passes of each, alternating; medians per call, summed over the calls.  Agreement: the first 64
+    segments of the first call against tests/resample_cut_ref.py's float64, within the header's bound.  The result goes to
+    profiles/scan_resample_cut.json."""
+    import ctypes as C
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    from cutter_vad_amd import MelSpec, _ffi, resample_taps
+    from tests import resample_cut_ref as R
+    try:
+        from scipy.signal import resample_poly
+    except ImportError:
+        resample_poly = None
+    N = int(os.environ.get("VAD_SCAN_BENCH_N", "1024"))
+    per_call = int(os.environ.get("VAD_SCAN_BENCH_PER_CALL", "512"))
+    sr, chunk = 48000, 1536
+    hop = chunk // 2
+    taps = resample_taps(sr)
+    pcm = np.tile(np.load(os.path.join(root, "tests", "golden", "speech16k_i16.npz"))["pcm"].astype(np.int16), 3)
+    rng = np.random.default_rng(N)
+    ns16 = 30 * 16000
+    firsts = rng.integers(0, pcm.size - ns16 + 1, N)
+    eng = Engine(blob(5), max_streams=max(per_call, 16))
+    slots = eng.open_streams(min(per_call, N))
+    med = lambda v: float(np.median(v))
+    spec = MelSpec(16000)
+    arrays = spec.operators()
+    flds, op_re, op_im, filters = arrays
+    op = np.concatenate([op_re, op_im], axis=1)
+    threads = 16
+    pool = ThreadPoolExecutor(threads)
+    row = {"config": f"scan_resample_cut: {N} int16 recordings of 30 s at 48 kHz, hop {hop}, {taps.size} taps, calls of {per_call} recordings",
+           "recordings": N, "passes": 3, "host_threads": threads, "scipy": resample_poly is not None}
+    keys = ("1_s_resample_cut_device", "1_s_cut_gain_range_f32_device", "2_s_resample_cut", "2_s_cut_f32", "2_s_resample_poly", "3_s_rate_mel",
+            "3_s_numpy_mel")
+    total = {k: 0.0 for k in keys}
+    per_group = []
+    counts_all = dict(segments=0, speech_samples_48k=0, samples_16k=0, rows=0, tiles=0)
+
+    def host_resample(data, start):
+        if resample_poly is None:
+            return None
+        return list(pool.map(lambda i: resample_poly(data[start[i]:start[i + 1]], 1, 3, window=taps), range(len(start) - 1)))
+
+    def numpy_mel(signals):
+        out = []
+        for y in signals:
+            p = np.pad(y.astype(np.float32), 200, mode="reflect")
+            fr = np.ascontiguousarray(np.lib.stride_tricks.sliding_window_view(p, 400)[::160])
+            z = fr @ op
+            out.append(np.log10(np.maximum((z[:, :201] ** 2 + z[:, 201:] ** 2) @ filters.T, np.float32(1e-10))))
+        return out
+
+    busy = torch.randn(6144, 6144, device="cuda")
+    ts = torch.cuda.Stream()
+
+    def event_timed(fn):
+        out = []
+        for k in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            with torch.cuda.stream(ts):
+                torch.mm(busy, busy)
+            e0.record(ts)
+            assert fn() == 0
+            e1.record(ts)
+            torch.cuda.synchronize()
+            if k >= 2:                           # two warm-ups
+                out.append(e0.elapsed_time(e1) * 1e-3)
+        return out
+
+    for g0 in range(0, N, per_call):
+        recs = [np.repeat(pcm[a:a + ns16], 3) for a in firsts[g0:g0 + per_call]]
+        sl = slots[:len(recs)]
+        eng.reset(sl)
+        eng.set_thresholds_many(sl, (0.4, 0.3, 0.8, 0.95, 6, 12))
+        grp = {"recordings": len(recs)}
+        with eng.scan_session():
+            table = eng.scan_segments(sl, recs, hop=hop, denoise=0.01, sample_rate=sr)
+            last = eng.last_scan
+            offs = [int(o) for o in last["offsets"]]
+            segs = [(offs[i], a, n) for i, a, n in zip(table["item"].tolist(), table["first_frame"].tolist(), table["nframes"].tolist())]
+            s_in = np.array([(n - 1) * hop + chunk for _, _, n in segs], np.int64)
+            s16 = np.array([R.s16(int(s), sr) for s in s_in], np.int64)
+            got, gstart = eng.resample_cut(segs, sr, taps, hop=hop, out="f32")
+            feat, fstart = eng.mel(segs, arrays, hop=hop, sample_rate=sr, taps=taps)
+            grp.update(segments=len(segs), speech_samples_48k=int(s_in.sum()), samples_16k=int(s16.sum()), rows=int(fstart[-1]))
+            if g0 == 0:
+                data, dstart = eng.cut(segs[:64], hop=hop, layout="range", out="f32", sample_rate=sr)
+                worst, ok = 0.0, True
+                for i in range(min(64, len(segs))):
+                    y, D = R.evaluate(data[dstart[i]:dstart[i + 1]], taps, sr)
+                    err = np.abs(got[gstart[i]:gstart[i + 1]].astype(np.float64) - y)
+                    ok = ok and bool((err <= R.bound(taps.size, sr) * D).all())
+                    live = D > 0
+                    if live.any():
+                        worst = max(worst, float((err[live] / (R.U * D[live])).max()))
+                row.update(agree_within_bound=ok, max_err_over_uD_gpu=worst, allowed_over_uD=R.bound(taps.size, sr) / R.U)
+                if resample_poly is not None:
+                    hs = host_resample(data, dstart)
+                    row["max_abs_difference_to_resample_poly"] = max(
+                        float(np.abs(got[gstart[i]:gstart[i] + min(hs[i].size, int(s16[i]))] - hs[i][:int(s16[i])]).max()) for i in range(len(hs)))
+            runs = {k: [] for k in keys if not k.startswith("1_")}
+            for p in range(4):
+                t0 = time.perf_counter()
+                eng.resample_cut(segs, sr, taps, hop=hop, out="f32")
+                t1 = time.perf_counter()
+                data, dstart = eng.cut(segs, hop=hop, layout="range", out="f32", sample_rate=sr)
+                t2 = time.perf_counter()
+                sig = host_resample(data, dstart)
+                t3 = time.perf_counter()
+                eng.mel(segs, arrays, hop=hop, sample_rate=sr, taps=taps)
+                t4 = time.perf_counter()
+                if sig is not None:
+                    numpy_mel(sig)
+                t5 = time.perf_counter()
+                del data, sig
+                if p:                            # the first pass is the warm-up
+                    for k, v in zip(runs, (t1 - t0, t2 - t1, t3 - t2, t4 - t3, t5 - t4)):
+                        runs[k].append(v)
+            for k, v in runs.items():
+                grp[k + "_runs"], grp[k] = v, med(v)
+        # (1) on device pointers: the kernel calls alone
+        block = np.zeros(last["samples"], np.int16)
+        for r, o in zip(recs, offs):
+            block[o:o + r.size] = r
+        d_audio = torch.from_numpy(block).cuda()
+        d_out = torch.empty(int(s_in.sum()) + 16, dtype=torch.float32, device="cuda")
+        lib, h, n = eng._lib, eng.handle, len(segs)
+        it_rs, _ = eng._resample_items(segs, sr, hop, 1)
+        it_cut, _ = eng._cut_items(segs, hop, _ffi.VAD_CUT_RANGE, 1, rate=sr)
+        ones = np.ones(n, np.float32)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        where = (d_audio.data_ptr(), block.size, 1, last["fmt"], sr, hop)
+        calls = {"1_s_resample_cut_device": lambda: lib.vad_scan_resample_cut_device(h, it_rs, n, None, fp(taps), taps.size, *where, _ffi.VAD_CUT_F32,
+                                                                                     d_out.data_ptr(), int(s16.sum()), ts.cuda_stream),
+                 "1_s_cut_gain_range_f32_device": lambda: lib.vad_scan_cut_gain_device(h, it_cut, n, fp(ones), *where, -1.0, _ffi.VAD_CUT_RANGE,
+                                                                                       _ffi.VAD_CUT_F32, d_out.data_ptr(), int(s_in.sum()),
+                                                                                       ts.cuda_stream)}
+        for name, fn in calls.items():
+            r_ = event_timed(fn)
+            grp[name + "_runs"], grp[name] = r_, med(r_)
+        assert calls["1_s_resample_cut_device"]() == 0
+        torch.cuda.synchronize()
+        grp["1_equal"] = bool(d_out[:int(s16.sum())].cpu().numpy().tobytes() == got.tobytes())
+        grp["tiles"] = int(((s16 + 255) // 256).sum())
+        del d_audio, d_out, block, recs, got, feat
+        torch.cuda.empty_cache()
+        for k in keys:
+            total[k] += grp[k]
+        for k in counts_all:
+            counts_all[k] += grp[k]
+        per_group.append(grp)
+    row.update(counts_all)
+    row.update(total)
+    K = 144                                      # vad_layout.h: rsc_K(97, 1, 3)
+    t = total["1_s_resample_cut_device"]
+    row["1_ratio_resample_over_move"] = t / total["1_s_cut_gain_range_f32_device"]
+    row["1_bytes_per_s"] = (counts_all["speech_samples_48k"] * 2 + counts_all["samples_16k"] * 4) / t
+    row["1_mfma_TFLOPs_with_padding"] = 2.0 * K * 256 * counts_all["tiles"] / t / 1e12
+    if resample_poly is not None:
+        row["2_ratio_host_over_gpu"] = (total["2_s_cut_f32"] + total["2_s_resample_poly"]) / total["2_s_resample_cut"]
+        row["3_ratio_host_over_gpu"] = (total["2_s_cut_f32"] + total["2_s_resample_poly"] + total["3_s_numpy_mel"]) / total["3_s_rate_mel"]
+    row["calls"] = per_group
+    eng.close()
+    pool.shutdown()
+    with open(os.path.join(root, "profiles", "scan_resample_cut.json"), "w") as f_:
+        json.dump({"what": "Segment audio and log-mel features at 16 kHz from 48 kHz recordings (vad_scan_resample_cut, vad_scan_rate_mel, "
+                           "csrc/scan_resample_cut.hip): DESIGN 2.1t",
+                   "how": "python tools/bench_configs.py scan_resample_cut on one MI355X, one process; the corpus goes through in calls of 512 "
+                          "recordings, each on the block its own rate scan left on the GPU.  (1) device forms: HIP events behind a matrix "
+                          "product that keeps the stream busy while the host builds the tables, ctypes items built outside the clock, two "
+                          "warm-ups and three timed passes; the operator pack is cached after the first call.  (2), (3): wall clock around the "
+                          "Python calls, one warm-up and three timed passes, alternating, medians per call, summed over the calls; the host "
+                          "routes use only code the parent has plus scipy and numpy.  1_bytes_per_s counts every input sample of a segment "
+                          "once (int16) and every output sample (float32); 1_mfma_TFLOPs_with_padding counts the packed operator's zeros.  Not "
+                          "measured: 8 and 24 kHz, other formats, tap counts and corpus sizes, L2 hit rates, the spread between processes and "
+                          "boxes", "runs": [row]}, f_, indent=1)
+        f_.write("\n")
+    return row
+
+
 def scan_rate():
     """Whole recordings at 48 kHz, resampled on the GPU in the scan: vad_scan_rate_device on VAD_SCAN_BENCH_N (default
     4 096) int16 recordings of 30 s at 48 kHz - the golden clip, every sample three times - already in device memory, hop = chunk / 2,

@@ -241,6 +241,49 @@ extern "C" hipError_t vadk_launch_seg_mel(const MelArgs *a, hipStream_t) {
     return hipSuccess;
 }
 
+// finished segments of a rate block at 16 kHz (csrc/scan_resample_cut.hip: vadk_resample_cut), the header's rule in plain float32:
+// for output m of a segment, y = sum over k ASCENDING of x[k] * h[m M - k L + C] with x the cut's decoded, channel-selected, ungated
+// sample inside [0, S_in) and nothing outside it, h read back out of the packed operator (vad_layout.h: rsc_pack_index; T[o][n]
+// with o = m % 16 and n = k - (m / 16) A + n0), then the gain as a multiply of its own and the cut's conversion
+extern "C" hipError_t vadk_launch_resample_cut(const ResampleCutArgs *a, hipStream_t) {
+    const size_t ch = a->channels == 2 ? 2 : 1, bytes = a->fmt == VAD_FMT_F32 ? 4 : a->fmt >= VAD_FMT_ULAW8 ? 1 : 2;
+    if (a->sr_in != 8000 && a->sr_in != 24000 && a->sr_in != 48000) return hipErrorInvalidValue;
+    const int64_t A = rsc_A(a->sr_in), K = (int64_t)a->ksteps * 16;
+    for (uint32_t b = 0; b < a->nwork; ++b) {
+        const CutWork w = a->work[b];
+        const CutSeg sg = a->segs[w.seg];
+        const uint32_t mode = sg.quad_in >> SCAN_MODE_SHIFT, qin = sg.quad_in & ((1u << SCAN_MODE_SHIFT) - 1u);
+        const int64_t S_in = (int64_t)a->inq[w.seg] * 4;
+        if (w.quad0 % (RSC_WG_SAMPLES / 4) != 0 || w.quad0 >= sg.nquads) return hipErrorInvalidValue;
+        const int64_t m1 = std::min<int64_t>((int64_t)sg.nquads * 4, (int64_t)w.quad0 * 4 + RSC_WG_SAMPLES);
+        for (int64_t m = (int64_t)w.quad0 * 4; m < m1; ++m) {
+            const int64_t k0 = (m / 16) * A - (int64_t)a->n0;
+            float y = 0.f;
+            for (int64_t n = 0; n < K; ++n) {
+                const int64_t k = k0 + n;
+                if (k < 0 || k >= S_in) continue;
+                const size_t i = 4 * (size_t)qin + (size_t)k;
+                if ((i + 1) * ch * bytes > a->audio_bytes) return hipErrorInvalidValue;
+                float x;
+                if (ch == 1) x = first_sample(a->audio, i, a->fmt, 1);
+                else {
+                    const float l = first_sample(a->audio, 2 * i, a->fmt, 1), r = first_sample(a->audio, 2 * i + 1, a->fmt, 1);
+                    x = mode == SCAN_MIX ? (l + r) * 0.5f : mode == SCAN_RIGHT ? r : l;
+                }
+                y += x * a->op[rsc_pack_index((uint32_t)(m % 16), (uint32_t)n)];
+            }
+            if (a->gains) y = y * a->gains[w.seg];
+            const size_t o = 4 * (size_t)sg.quad_out + (size_t)m;
+            if (a->out_fmt == VAD_CUT_F32) static_cast<float *>(a->out)[o] = y;
+            else {
+                const float v = y * 32767.0f;
+                static_cast<int16_t *>(a->out)[o] = (int16_t)(int)(v < -32768.0f ? -32768.0f : v > 32767.0f ? 32767.0f : v);
+            }
+        }
+    }
+    return hipSuccess;
+}
+
 // one finished piece of audio (csrc/scan_render.hip: vadk_scan_render), the kernel's arithmetic in plain C++, output quad by output
 // quad as its workgroups are listed: per covering segment the cut's decoded, channel-selected, gated sample, times the gain, times
 // the fade-in entry (or 1), times the fade-out entry (or 1) - three float32 multiplies - then the sum of the two where two segments
