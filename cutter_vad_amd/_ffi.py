@@ -161,6 +161,27 @@ MEL_PADS = {"none": VAD_MEL_PAD_NONE, "reflect": VAD_MEL_PAD_REFLECT}
 MEL_LOGS = {"linear": VAD_MEL_LINEAR, "ln": VAD_MEL_LN, "log10": VAD_MEL_LOG10}
 
 
+class Batch(C.Structure):
+    _fields_ = [("n_mels", C.c_int32), ("frames", C.c_int32), ("deltas", C.c_int32), ("layout", C.c_int32), ("dtype", C.c_int32),
+                ("pad_mode", C.c_int32), ("pad_value", C.c_float), ("reserved", C.c_int32)]
+
+
+class BatchWindow(C.Structure):
+    _fields_ = [("seg", C.c_int32), ("nrows", C.c_int32), ("row0", C.c_int64)]
+
+
+# the same record as a numpy structured dtype: the windows of a batch are np.ndarray(nw, BATCH_WINDOW_DTYPE)
+BATCH_WINDOW_DTYPE = np.dtype([("seg", np.int32), ("nrows", np.int32), ("row0", np.int64)])
+
+VAD_STATS_MAX_ROWS = 131072
+VAD_BATCH_F32, VAD_BATCH_F16, VAD_BATCH_BF16 = 0, 1, 2
+VAD_BATCH_CHANNEL_MAJOR, VAD_BATCH_TIME_MAJOR = 0, 1
+VAD_BATCH_PAD_VALUE, VAD_BATCH_PAD_FEATURE = 0, 1
+BATCH_DTYPES = {"f32": VAD_BATCH_F32, "f16": VAD_BATCH_F16, "bf16": VAD_BATCH_BF16}
+BATCH_LAYOUTS = {"channel": VAD_BATCH_CHANNEL_MAJOR, "time": VAD_BATCH_TIME_MAJOR}
+BATCH_PADS = {"value": VAD_BATCH_PAD_VALUE, "feature": VAD_BATCH_PAD_FEATURE}
+
+
 class Segment(C.Structure):
     _fields_ = [("item", C.c_int32), ("first_frame", C.c_int32), ("nframes", C.c_int32), ("counted", C.c_int32),
                 ("mean_prob", C.c_float), ("max_prob", C.c_float)]
@@ -308,6 +329,18 @@ SIGNATURES = {
                                     C.c_int32, C.c_int, C.c_int32, C.c_int32, _f32p, C.c_int64]),
     "vad_scan_rate_mel_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, C.POINTER(Mel), _f32p, _f32p, _f32p, _f32p, C.c_int32, _vp,
                                            C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32, _vp, C.c_int64, _vp]),
+    "vad_scan_mel_keep": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, C.POINTER(Mel), _f32p, _f32p, _f32p, _f32p, C.c_int32, _vp, C.c_int64,
+                                    C.c_int32, C.c_int, C.c_int32, C.c_int32, C.c_float, _i64p]),
+    "vad_scan_mel_keep_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, C.POINTER(Mel), _f32p, _f32p, _f32p, _f32p, C.c_int32, _vp,
+                                           C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32, C.c_float, _i64p, _vp]),
+    "vad_mel_resident": (C.c_int, [_vp, _i64p, _i32p, _i64p]),
+    "vad_mel_resident_read": (C.c_int, [_vp, C.c_int64, C.c_int64, _f32p]),
+    "vad_mel_stats": (C.c_int, [_vp, _f32p, C.c_int64, C.c_int32, _i64p, C.c_int64, _f32p, _i64p, C.POINTER(C.c_uint64)]),
+    "vad_mel_stats_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _i64p, C.c_int64, _vp, _vp, _vp, _vp]),
+    "vad_mel_batch": (C.c_int, [_vp, _f32p, C.c_int64, _i64p, C.c_int64, C.POINTER(Batch), C.POINTER(BatchWindow), C.c_int64, _f32p, _f32p,
+                                _f32p, C.c_int64, _vp, C.c_int64]),
+    "vad_mel_batch_device": (C.c_int, [_vp, _vp, C.c_int64, _i64p, C.c_int64, C.POINTER(Batch), C.POINTER(BatchWindow), C.c_int64, _f32p,
+                                       _f32p, _f32p, C.c_int64, _vp, C.c_int64, _vp]),
     "vad_scan_render": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32,
                                   C.c_int32, C.c_float, C.c_int32, _vp, C.c_int64]),
     "vad_scan_render_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int,

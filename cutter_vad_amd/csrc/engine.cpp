@@ -47,6 +47,8 @@ extern "C" hipError_t vadk_launch_scan_cut_gain(const vadk::CutArgs *a, const fl
 extern "C" hipError_t vadk_launch_seg_levels(const vadk::CutArgs *a, float clip, hipStream_t stream);
 extern "C" hipError_t vadk_launch_seg_mel(const vadk::MelArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_resample_cut(const vadk::ResampleCutArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_mel_stats(const vadk::MelStatsArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_mel_batch(const vadk::MelBatchArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_render(const vadk::RenderArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_cut_stereo(const vadk::CutArgs *a, const float *gains, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_render_stereo(const vadk::RenderArgs *a, hipStream_t stream);
@@ -205,6 +207,18 @@ struct vad_engine {
     float *d_rsc = nullptr; size_t d_rsc_cap = 0;
     float *d_rsc_mid = nullptr; size_t d_rsc_mid_cap = 0;
     std::vector<vadk::CutSeg> rsc_mel_segs;
+    // vad_scan_mel_keep: the RESIDENT MATRIX d_melk [melk_start.back()][melk_n_mels] and its segments' first rows (n + 1 entries;
+    // empty: none kept).  vad_mel_stats / vad_mel_batch: a host matrix uploaded to d_melb_in, the tables in d_melb (stats:
+    // workgroups, the maxima's -inf; batch: windows, lo, shift, scale), the host forms' outputs in d_melb_out
+    float *d_melk = nullptr; size_t d_melk_cap = 0;
+    int32_t melk_n_mels = 0;
+    std::vector<int64_t> melk_start;
+    float *d_melb_in = nullptr; size_t d_melb_in_cap = 0;
+    uint8_t *d_melb = nullptr; size_t d_melb_cap = 0;
+    uint8_t *d_melb_out = nullptr; size_t d_melb_out_cap = 0;
+    std::vector<vadk::MelStatsWork> melb_work;
+    std::vector<vadk::MelBatchWin> melb_win;
+    std::vector<float> melb_f;
     // vad_segments_device / vad_scan_segments: the extraction's work area - out_start as int32 [n + 1] (the host copy as it was
     // uploaded), then the chunk counts - and, for vad_scan_segments, the items' CSR positions, the count and the retained table
     uint8_t *d_segwork = nullptr; size_t d_segwork_cap = 0;
@@ -931,7 +945,7 @@ void vad_engine_destroy(vad_engine *e) {
     weights_release(e->d_wstream16x);
     weights_release(e->d_wstream16y);
     void *bufs[] = {e->d_refine, e->d_refine_in, e->d_refine_out, e->d_tail_len, e->d_tailwork, e->d_reseg, e->d_resegtab, e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots, e->d_g711,
-                    e->d_audio, e->d_items, e->d_win, e->d_items_win, e->d_cut, e->d_cut_out, e->d_mel, e->d_rsc, e->d_rsc_mid, e->d_segwork, e->d_nsegs, e->d_segtab, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
+                    e->d_audio, e->d_items, e->d_win, e->d_items_win, e->d_cut, e->d_cut_out, e->d_mel, e->d_rsc, e->d_rsc_mid, e->d_melk, e->d_melb_in, e->d_melb, e->d_melb_out, e->d_segwork, e->d_nsegs, e->d_segtab, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->scan_done) (void)hipEventDestroy(e->scan_done);
@@ -2334,13 +2348,22 @@ int mel_launch(vad_engine *e, const vad_mel *m, const void *d_audio, size_t audi
     return r != hipSuccess ? e->hip_fail(r, "kernel launch (segment mel)") : VAD_OK;
 }
 
+// vad_scan_mel_keep: the segments' first rows (quad_out of the first n of `segs`), the total and n_mels of the resident matrix
+void melk_remember(vad_engine *e, const std::vector<vadk::CutSeg> &segs, size_t n, int64_t rows, int32_t n_mels, int64_t *rows_out) {
+    e->melk_start.resize(n + 1);
+    for (size_t i = 0; i < n; ++i) e->melk_start[i] = (int64_t)segs[i].quad_out;
+    e->melk_start[n] = rows;
+    e->melk_n_mels = n_mels;
+    if (rows_out) *rows_out = rows;
+}
+
 // vad_scan_mel / _device with e->mu held: the call's own checks, cut_check's refusals under this name (the segments tabled as for
 // the levels: the sample range once, no out_sample), the frames and rows of every segment and one workgroup per tile of MEL_TILE
 // frames, then the block as the cuts find it, the operator (mel_operator), one upload of the tables - segments, workgroups, in this
 // order in e->d_cut - and one launch.
 int mel_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re, const float *op_im,
             const float *filters, const void *audio, int64_t audio_samples, int32_t channels, int fmt, int32_t hop, float thr, float *out,
-            int64_t out_rows, void *stream) {
+            int64_t out_rows, void *stream, bool keep = false, int64_t *rows_out = nullptr) {
     hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
     HIP_TRY(e, hipSetDevice(e->device));
     if (int rc = scan_wait(e)) return rc;
@@ -2348,20 +2371,30 @@ int mel_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items,
     CutPlan c{who, items, n, audio_samples, channels, fmt, hop, thr, VAD_CUT_RANGE, VAD_CUT_F32, 0, 0, 0, nullptr, true, 0.0f};
     c.mel = true;
     if (int rc = cut_check(e, c)) return rc;
-    if (n == 0) return VAD_OK;
+    if (n == 0) {
+        if (keep) melk_remember(e, e->cut_segs, 0, 0, m->n_mels, rows_out);
+        return VAD_OK;
+    }
     int64_t rows = 0;
     if (int rc = mel_tiles(e, who, m, e->cut_segs, &rows)) return rc;
-    if (rows > out_rows)
+    if (!keep && rows > out_rows)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_rows = %lld, the segments have %lld rows", who, (long long)out_rows,
                        (long long)rows);
-    if (rows > 0 && !out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if (!keep && rows > 0 && !out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
     const size_t out_bytes = (size_t)rows * (size_t)m->n_mels * sizeof(float);
     if (dev) {
         if (int rc = cut_block_device(e, c, audio, out)) return rc;
     } else {
         if (int rc = cut_block_host(e, c, audio)) return rc;
-        if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, out_bytes)) return rc;
+        if (!keep)
+            if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, out_bytes)) return rc;
         c.d_out = e->d_cut_out;
+    }
+    if (keep) {
+        // every refusal lies behind: the previous matrix ends here
+        e->melk_start.clear();
+        if (int rc = ensure(e, e->d_melk, e->d_melk_cap, out_bytes)) return rc;
+        c.d_out = e->d_melk;
     }
     const size_t sb = sizeof(vadk::CutSeg) * e->cut_segs.size(), wb = sizeof(vadk::MelWork) * e->mel_work.size();
     if (int rc = ensure(e, e->d_cut, e->d_cut_cap, sb + wb)) return rc;
@@ -2374,13 +2407,14 @@ int mel_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items,
     if (wb) HIP_TRY(e, hipMemcpyAsync(e->d_cut + sb, e->mel_work.data(), wb, hipMemcpyHostToDevice, s));
     const int rc = mel_launch(e, m, c.d_audio, c.ab, fmt, channels, thr, static_cast<float *>(c.d_out),
                               reinterpret_cast<const vadk::CutSeg *>(e->d_cut), reinterpret_cast<const vadk::MelWork *>(e->d_cut + sb), s);
+    if (keep && !rc) melk_remember(e, e->cut_segs, (size_t)n, rows, m->n_mels, rows_out);
     if (dev) {
         // the launch reads the engine's tables: the next scan or cut waits for it, as behind vad_scan_device
         if (int rc2 = scan_mark_pending(e, s)) return rc2;
         return rc;
     }
     if (rc) return rc;
-    if (out_bytes) HIP_TRY(e, hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    if (out_bytes && !keep) HIP_TRY(e, hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
     return VAD_OK;
 }
@@ -2434,7 +2468,7 @@ int resample_cut_operator(vad_engine *e, int32_t sr_in, const float *taps, int32
 int resample_cut_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const float *gains, const float *taps, int32_t ntaps,
                      const void *audio, int64_t audio_samples, int32_t channels, int fmt, int32_t sr_in, int32_t hop, int32_t out_fmt, void *out,
                      int64_t out_samples, void *stream, const vad_mel *m = nullptr, const float *op_re = nullptr, const float *op_im = nullptr,
-                     const float *filters = nullptr, bool mel = false) {
+                     const float *filters = nullptr, bool mel = false, bool keep = false, int64_t *rows_out = nullptr) {
     hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
     HIP_TRY(e, hipSetDevice(e->device));
     if (int rc = scan_wait(e)) return rc;
@@ -2446,7 +2480,10 @@ int resample_cut_run(vad_engine *e, bool dev, const char *who, const vad_cut_ite
     if (int rc = cut_check(e, c)) return rc;
     if (mel)
         if (int rc = mel_check(e, who, m, op_re, op_im, filters, out_samples)) return rc;
-    if (n == 0) return VAD_OK;
+    if (n == 0) {
+        if (keep) melk_remember(e, e->rsc_mel_segs, 0, 0, m->n_mels, rows_out);
+        return VAD_OK;
+    }
     int64_t rows = 0, mid = 0;
     if (mel) {
         e->rsc_mel_segs.resize((size_t)n);
@@ -2459,10 +2496,10 @@ int resample_cut_run(vad_engine *e, bool dev, const char *who, const vad_cut_ite
                 return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the segments have 2^29 or more samples at 16 kHz in one call", who);
         }
         if (int rc = mel_tiles(e, who, m, e->rsc_mel_segs, &rows)) return rc;
-        if (rows > out_samples)
+        if (!keep && rows > out_samples)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_rows = %lld, the segments have %lld rows", who, (long long)out_samples,
                            (long long)rows);
-        if (rows > 0 && !out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+        if (!keep && rows > 0 && !out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
     } else if (!out) {
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
     }
@@ -2471,10 +2508,16 @@ int resample_cut_run(vad_engine *e, bool dev, const char *who, const vad_cut_ite
         if (int rc = cut_block_device(e, c, audio, out)) return rc;
     } else {
         if (int rc = cut_block_host(e, c, audio)) return rc;
-        if (mel) {
+        if (mel && !keep) {
             if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, out_bytes)) return rc;
             c.d_out = e->d_cut_out;
         }
+    }
+    if (keep) {
+        // every refusal lies behind: the previous matrix ends here
+        e->melk_start.clear();
+        if (int rc = ensure(e, e->d_melk, e->d_melk_cap, out_bytes)) return rc;
+        c.d_out = e->d_melk;
     }
     if (mel)
         if (int rc = ensure(e, e->d_rsc_mid, e->d_rsc_mid_cap, (size_t)mid * sizeof(float))) return rc;
@@ -2518,6 +2561,7 @@ int resample_cut_run(vad_engine *e, bool dev, const char *who, const vad_cut_ite
     if (!rc && mel)
         rc = mel_launch(e, m, e->d_rsc_mid, (size_t)mid * sizeof(float), VAD_FMT_F32, 1, -1.0f, static_cast<float *>(c.d_out),
                         reinterpret_cast<const vadk::CutSeg *>(t + sb), reinterpret_cast<const vadk::MelWork *>(t + sb + msb + wb), s);
+    if (keep && !rc) melk_remember(e, e->rsc_mel_segs, (size_t)n, rows, m->n_mels, rows_out);
     if (dev) {
         // the launches read the engine's tables and buffers: the next scan or cut waits for them, as behind vad_scan_device
         if (int rc2 = scan_mark_pending(e, s)) return rc2;
@@ -2525,14 +2569,331 @@ int resample_cut_run(vad_engine *e, bool dev, const char *who, const vad_cut_ite
     }
     if (rc) return rc;
     if (!mel) return cut_copy_back(e, c, out, s);
-    if (out_bytes) HIP_TRY(e, hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    if (out_bytes && !keep) HIP_TRY(e, hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
     return VAD_OK;
+}
+
+
+// ---- vad_mel_stats / vad_mel_batch: statistics and batches of a feature matrix
+
+// The matrix and the segments a call names: the caller's, or the resident ones of vad_scan_mel_keep.  Checks only; x is the device
+// matrix where there is one already (a host matrix is uploaded by melb_upload once every refusal lies behind)
+struct MelbSrc { const float *x; int64_t rows; int32_t n_mels; const int64_t *start; int64_t n; };
+
+int melb_source(vad_engine *e, const char *who, bool dev, const float *features, int64_t rows, int32_t n_mels, const int64_t *start, int64_t n,
+                MelbSrc *src) {
+    if ((!features || !start) && e->melk_start.empty())
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: NULL names the resident matrix, and the engine holds none: no "
+                       "vad_scan_mel_keep has kept one", who);
+    if (!features) {
+        rows = e->melk_start.back();
+        n_mels = e->melk_n_mels;
+    } else if (rows < 0) {
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: rows = %lld is negative", who, (long long)rows);
+    }
+    if (n_mels < 1 || n_mels > 128) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n_mels = %d must be 1 .. 128", who, n_mels);
+    if (!start) {
+        start = e->melk_start.data();
+        n = (int64_t)e->melk_start.size() - 1;
+    } else if (n < 0) {
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n = %lld is negative", who, (long long)n);
+    }
+    if (n > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 segments in one call", who);
+    if (start[0] < 0 || start[n] > rows)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: start[0] = %lld .. start[n] = %lld leaves the matrix of %lld rows", who,
+                       (long long)start[0], (long long)start[n], (long long)rows);
+    for (int64_t i = 0; i < n; ++i) {
+        if (start[i + 1] < start[i])
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: start = %lld is followed by %lld, the first rows ascend", who,
+                           (long long)i, (long long)start[i], (long long)start[i + 1]);
+        if (start[i + 1] - start[i] > (int64_t)INT32_MAX)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld has %lld rows, a segment may have less than 2^31", who,
+                           (long long)i, (long long)(start[i + 1] - start[i]));
+    }
+    if (dev && features && (reinterpret_cast<uintptr_t>(features) & 3))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the features must be 4-byte aligned", who);
+    *src = MelbSrc{features ? (dev ? features : nullptr) : e->d_melk, rows, n_mels, start, n};
+    return VAD_OK;
+}
+
+int melb_upload(vad_engine *e, bool dev, const float *features, MelbSrc *src, hipStream_t s) {
+    if (!features || dev) return VAD_OK;
+    const size_t bytes = (size_t)src->rows * (size_t)src->n_mels * sizeof(float);
+    if (int rc = ensure(e, e->d_melb_in, e->d_melb_in_cap, bytes)) return rc;
+    if (bytes) HIP_TRY(e, hipMemcpyAsync(e->d_melb_in, features, bytes, hipMemcpyHostToDevice, s));
+    src->x = e->d_melb_in;
+    return VAD_OK;
+}
+
+// vad_mel_stats / _device with e->mu held
+int mel_stats_run(vad_engine *e, bool dev, const char *who, const float *features, int64_t rows, int32_t n_mels, const int64_t *start, int64_t n,
+                  float *max_out, int64_t *sum_out, uint64_t *sumsq_out, void *stream) {
+    hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    MelbSrc src{};
+    if (int rc = melb_source(e, who, dev, features, rows, n_mels, start, n, &src)) return rc;
+    if (sum_out || sumsq_out)
+        for (int64_t i = 0; i < src.n; ++i)
+            if (src.start[i + 1] - src.start[i] > (int64_t)VAD_STATS_MAX_ROWS)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld has %lld rows, the sums take %d at the most", who,
+                               (long long)i, (long long)(src.start[i + 1] - src.start[i]), VAD_STATS_MAX_ROWS);
+    if (dev && ((reinterpret_cast<uintptr_t>(max_out) & 3) || (reinterpret_cast<uintptr_t>(sum_out) & 7) || (reinterpret_cast<uintptr_t>(sumsq_out) & 7)))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the sums must be 8-byte aligned, the maxima 4-byte", who);
+    if (src.n == 0 || (!max_out && !sum_out && !sumsq_out)) return VAD_OK;
+    e->melb_work.clear();
+    for (int64_t i = 0; i < src.n; ++i)
+        for (int64_t r = src.start[i]; r < src.start[i + 1]; r += vadk::MELB_STATS_ROWS)
+            e->melb_work.push_back(vadk::MelStatsWork{(uint32_t)i, (uint32_t)std::min<int64_t>(vadk::MELB_STATS_ROWS, src.start[i + 1] - r), (uint64_t)r});
+    if (e->melb_work.size() > (size_t)INT32_MAX)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d rows in one call", who, vadk::MELB_STATS_ROWS);
+    const size_t nn = (size_t)src.n, wb = sizeof(vadk::MelStatsWork) * e->melb_work.size(), sumb = nn * (size_t)src.n_mels * 8u, maxb = nn * sizeof(float);
+    if (int rc = ensure(e, e->d_melb, e->d_melb_cap, wb + maxb)) return rc;
+    vadk::MelStatsArgs a{};
+    if (dev) {
+        a.max_out = max_out;
+        a.sum_out = reinterpret_cast<long long *>(sum_out);
+        a.sumsq_out = reinterpret_cast<unsigned long long *>(sumsq_out);
+    } else {
+        if (int rc = ensure(e, e->d_melb_out, e->d_melb_out_cap, 2 * sumb + maxb)) return rc;
+        a.sum_out = sum_out ? reinterpret_cast<long long *>(e->d_melb_out) : nullptr;
+        a.sumsq_out = sumsq_out ? reinterpret_cast<unsigned long long *>(e->d_melb_out + sumb) : nullptr;
+        a.max_out = max_out ? reinterpret_cast<float *>(e->d_melb_out + 2 * sumb) : nullptr;
+    }
+    if (int rc = melb_upload(e, dev, features, &src, s)) return rc;
+    if (wb) HIP_TRY(e, hipMemcpyAsync(e->d_melb, e->melb_work.data(), wb, hipMemcpyHostToDevice, s));
+    // the call's own start values: -inf and zeros
+    if (a.max_out) {
+        e->melb_f.assign(nn, -INFINITY);
+        HIP_TRY(e, hipMemcpyAsync(a.max_out, e->melb_f.data(), maxb, hipMemcpyHostToDevice, s));
+    }
+    if (a.sum_out) HIP_TRY(e, hipMemsetAsync(a.sum_out, 0, sumb, s));
+    if (a.sumsq_out) HIP_TRY(e, hipMemsetAsync(a.sumsq_out, 0, sumb, s));
+    a.x = src.x;
+    a.work = reinterpret_cast<const vadk::MelStatsWork *>(e->d_melb);
+    a.nwork = (uint32_t)e->melb_work.size();
+    a.n_mels = (uint32_t)src.n_mels;
+    const hipError_t r = vadk_launch_mel_stats(&a, s);
+    const int rc = r != hipSuccess ? e->hip_fail(r, "kernel launch (mel stats)") : VAD_OK;
+    if (dev) {
+        // the launch reads the engine's tables: the next scan or cut waits for it, as behind vad_scan_device
+        if (int rc2 = scan_mark_pending(e, s)) return rc2;
+        return rc;
+    }
+    if (rc) return rc;
+    if (sum_out) HIP_TRY(e, hipMemcpyAsync(sum_out, a.sum_out, sumb, hipMemcpyDeviceToHost, s));
+    if (sumsq_out) HIP_TRY(e, hipMemcpyAsync(sumsq_out, a.sumsq_out, sumb, hipMemcpyDeviceToHost, s));
+    if (max_out) HIP_TRY(e, hipMemcpyAsync(max_out, a.max_out, maxb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    return VAD_OK;
+}
+
+// vad_batch's fields, ahead of everything else
+int batch_check(vad_engine *e, const char *who, const vad_batch *b) {
+    if (!b) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null vad_batch", who);
+    if (b->n_mels < 1 || b->n_mels > 128) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n_mels = %d must be 1 .. 128", who, b->n_mels);
+    if (b->frames < 4 || b->frames > 65536 || (b->frames & 3))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: frames = %d must be a multiple of 4 from 4 to 65536", who, b->frames);
+    if (b->deltas < 0 || b->deltas > 2) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: deltas = %d must be 0 .. 2", who, b->deltas);
+    if (b->layout != VAD_BATCH_CHANNEL_MAJOR && b->layout != VAD_BATCH_TIME_MAJOR)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: layout = %d is neither VAD_BATCH_CHANNEL_MAJOR nor VAD_BATCH_TIME_MAJOR", who, b->layout);
+    if (b->dtype != VAD_BATCH_F32 && b->dtype != VAD_BATCH_F16 && b->dtype != VAD_BATCH_BF16)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: dtype = %d is none of VAD_BATCH_F32, VAD_BATCH_F16, VAD_BATCH_BF16", who, b->dtype);
+    if (b->pad_mode != VAD_BATCH_PAD_VALUE && b->pad_mode != VAD_BATCH_PAD_FEATURE)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: pad_mode = %d is neither VAD_BATCH_PAD_VALUE nor VAD_BATCH_PAD_FEATURE", who, b->pad_mode);
+    if (!std::isfinite(b->pad_value))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: pad_value is %s, a pad value is a finite number", who,
+                       std::isnan(b->pad_value) ? "NaN" : "infinite");
+    if (b->reserved != 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: vad_batch.reserved = %d must be 0", who, b->reserved);
+    return VAD_OK;
+}
+
+// vad_mel_batch / _device with e->mu held.  In e->d_melb: the windows, then lo [n], shift and scale [nss][n_mels]
+int mel_batch_run(vad_engine *e, bool dev, const char *who, const float *features, int64_t rows, const int64_t *start, int64_t n, const vad_batch *b,
+                  const vad_batch_window *windows, int64_t nw, const float *lo, const float *shift, const float *scale, int64_t nss, void *out,
+                  int64_t out_bytes, void *stream) {
+    hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    if (int rc = batch_check(e, who, b)) return rc;
+    MelbSrc src{};
+    if (int rc = melb_source(e, who, dev, features, rows, b->n_mels, start, n, &src)) return rc;
+    if (src.n_mels != b->n_mels)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n_mels = %d, the resident matrix has %d", who, b->n_mels, src.n_mels);
+    if (nw < 0 || out_bytes < 0 || (nw > 0 && !windows)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer or bad count", who);
+    if (!shift && !scale) nss = 1;
+    if (nss != 1 && nss != src.n)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: nss = %lld: shift and scale have 1 row or n = %lld", who, (long long)nss,
+                       (long long)src.n);
+    const size_t nm = (size_t)b->n_mels, nn = (size_t)src.n;
+    for (size_t i = 0; lo && i < nn; ++i)
+        if (std::isnan(lo[i])) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: lo[%lld] is NaN", who, (long long)i);
+    for (int which = 0; which < 2; ++which) {
+        const float *v = which ? scale : shift;
+        for (size_t k = 0; v && k < (size_t)nss * nm; ++k)
+            if (!std::isfinite(v[k]))
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %s[%lld][%lld] is %s, a %s is a finite number", who, which ? "scale" : "shift",
+                               (long long)(k / nm), (long long)(k % nm), std::isnan(v[k]) ? "NaN" : "infinite", which ? "scale" : "shift");
+    }
+    e->melb_win.resize((size_t)nw);
+    for (int64_t k = 0; k < nw; ++k) {
+        const vad_batch_window &w = windows[k];
+        if (w.seg < 0 || (int64_t)w.seg >= src.n)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: window %lld names segment %d of %lld", who, (long long)k, w.seg, (long long)src.n);
+        const int64_t M = src.start[w.seg + 1] - src.start[w.seg];
+        if (w.row0 < 0 || w.nrows < 0 || w.nrows > b->frames || w.row0 > M || w.nrows > M - w.row0)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: window %lld: rows %lld .. +%d of segment %d, which has %lld, in %d frames", who,
+                           (long long)k, (long long)w.row0, w.nrows, w.seg, (long long)M, b->frames);
+        e->melb_win[(size_t)k] = vadk::MelBatchWin{(uint64_t)src.start[w.seg], (uint32_t)M, (uint32_t)w.row0, (uint32_t)w.nrows, (uint32_t)w.seg};
+    }
+    const uint32_t tile = vadk::melb_tile((uint32_t)b->n_mels, (uint32_t)b->deltas), tiles = ((uint32_t)b->frames + tile - 1u) / tile;
+    const size_t C = nm * (size_t)(b->deltas + 1), need = (size_t)nw * C * (size_t)b->frames * (b->dtype == VAD_BATCH_F32 ? 4u : 2u);
+    if (need > (size_t)out_bytes)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_bytes = %lld, the windows have %llu bytes", who, (long long)out_bytes,
+                       (unsigned long long)need);
+    if ((uint64_t)nw * tiles > (uint64_t)INT32_MAX)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %u frames in one call", who, tile);
+    if (nw == 0) return VAD_OK;
+    if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if (dev && (reinterpret_cast<uintptr_t>(out) & 15))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output must be 16-byte aligned", who);
+    const size_t wb = sizeof(vadk::MelBatchWin) * (size_t)nw, lb = sizeof(float) * std::max<size_t>(nn, 1), ssb = sizeof(float) * (size_t)nss * nm;
+    if (int rc = ensure(e, e->d_melb, e->d_melb_cap, wb + lb + 2 * ssb)) return rc;
+    if (!dev)
+        if (int rc = ensure(e, e->d_melb_out, e->d_melb_out_cap, need)) return rc;
+    if (int rc = melb_upload(e, dev, features, &src, s)) return rc;
+    e->melb_f.assign(lb / sizeof(float) + 2 * (size_t)nss * nm, 0.0f);
+    float *hl = e->melb_f.data(), *hs = hl + lb / sizeof(float), *hc = hs + (size_t)nss * nm;
+    for (size_t i = 0; i < nn; ++i) hl[i] = lo ? lo[i] : -INFINITY;
+    for (size_t k = 0; k < (size_t)nss * nm; ++k) {
+        hs[k] = shift ? shift[k] : 0.0f;
+        hc[k] = scale ? scale[k] : 1.0f;
+    }
+    HIP_TRY(e, hipMemcpyAsync(e->d_melb, e->melb_win.data(), wb, hipMemcpyHostToDevice, s));
+    HIP_TRY(e, hipMemcpyAsync(e->d_melb + wb, e->melb_f.data(), lb + 2 * ssb, hipMemcpyHostToDevice, s));
+    vadk::MelBatchArgs a{};
+    a.x = src.x;
+    a.out = dev ? out : static_cast<void *>(e->d_melb_out);
+    a.win = reinterpret_cast<const vadk::MelBatchWin *>(e->d_melb);
+    a.lo = reinterpret_cast<const float *>(e->d_melb + wb);
+    a.shift = reinterpret_cast<const float *>(e->d_melb + wb + lb);
+    a.scale = reinterpret_cast<const float *>(e->d_melb + wb + lb + ssb);
+    a.nw = (uint32_t)nw;
+    a.n_mels = (uint32_t)b->n_mels;
+    a.frames = (uint32_t)b->frames;
+    a.deltas = (uint32_t)b->deltas;
+    a.layout = b->layout;
+    a.dtype = b->dtype;
+    a.pad_mode = b->pad_mode;
+    a.pad_value = b->pad_value;
+    a.per_seg = nss == 1 ? 0u : 1u;
+    a.tile = tile;
+    const hipError_t r = vadk_launch_mel_batch(&a, s);
+    const int rc = r != hipSuccess ? e->hip_fail(r, "kernel launch (mel batch)") : VAD_OK;
+    if (dev) {
+        // the launch reads the engine's tables: the next scan or cut waits for it, as behind vad_scan_device
+        if (int rc2 = scan_mark_pending(e, s)) return rc2;
+        return rc;
+    }
+    if (rc) return rc;
+    HIP_TRY(e, hipMemcpyAsync(out, e->d_melb_out, need, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    return VAD_OK;
+}
+
+// vad_scan_mel_keep / _device with e->mu held: the plain call or the rate call under this name, by sr_in
+int mel_keep_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re,
+                 const float *op_im, const float *filters, const float *taps, int32_t ntaps, const void *audio, int64_t audio_samples,
+                 int32_t channels, int fmt, int32_t sr_in, int32_t hop, float thr, int64_t *rows_out, void *stream) {
+    if (sr_in == 0 || sr_in == e->sample_rate)
+        return mel_run(e, dev, who, items, n, m, op_re, op_im, filters, audio, audio_samples, channels, fmt, hop, thr, nullptr, 0, stream, true, rows_out);
+    return resample_cut_run(e, dev, who, items, n, nullptr, taps, ntaps, audio, audio_samples, channels, fmt, sr_in, hop, VAD_CUT_F32, nullptr, 0,
+                            stream, m, op_re, op_im, filters, true, true, rows_out);
 }
 
 }  // namespace
 
 extern "C" {
+
+int vad_scan_mel_keep(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re, const float *op_im,
+                      const float *filters, const float *taps, int32_t ntaps, const void *audio, int64_t audio_samples, int32_t channels,
+                      int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int64_t *rows_out) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return mel_keep_run(e, false, "vad_scan_mel_keep", items, n, m, op_re, op_im, filters, taps, ntaps, audio, audio_samples, channels, frame_fmt,
+                        sr_in, hop, denoise_thresh, rows_out, nullptr);
+}
+
+int vad_scan_mel_keep_device(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re, const float *op_im,
+                             const float *filters, const float *taps, int32_t ntaps, const void *d_audio, int64_t audio_samples,
+                             int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int64_t *rows_out, void *stream) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return mel_keep_run(e, true, "vad_scan_mel_keep_device", items, n, m, op_re, op_im, filters, taps, ntaps, d_audio, audio_samples, channels,
+                        frame_fmt, sr_in, hop, denoise_thresh, rows_out, stream);
+}
+
+int vad_mel_resident(vad_engine *e, int64_t *rows, int32_t *n_mels, int64_t *nsegs) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->melk_start.empty())
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: vad_mel_resident: the engine holds no resident matrix: no vad_scan_mel_keep has kept one");
+    if (rows) *rows = e->melk_start.back();
+    if (n_mels) *n_mels = e->melk_n_mels;
+    if (nsegs) *nsegs = (int64_t)e->melk_start.size() - 1;
+    return VAD_OK;
+}
+
+int vad_mel_resident_read(vad_engine *e, int64_t first_row, int64_t count, float *out) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    const char *who = "vad_mel_resident_read";
+    if (e->melk_start.empty())
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the engine holds no resident matrix: no vad_scan_mel_keep has kept one", who);
+    const int64_t rows = e->melk_start.back();
+    if (first_row < 0 || count < 0 || first_row > rows || count > rows - first_row)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: rows %lld .. +%lld of a matrix of %lld", who, (long long)first_row,
+                       (long long)count, (long long)rows);
+    if (count == 0) return VAD_OK;
+    if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    const size_t nm = (size_t)e->melk_n_mels;
+    HIP_TRY(e, hipMemcpyAsync(out, e->d_melk + (size_t)first_row * nm, (size_t)count * nm * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return VAD_OK;
+}
+
+int vad_mel_stats(vad_engine *e, const float *features, int64_t rows, int32_t n_mels, const int64_t *start, int64_t n, float *max_out,
+                  int64_t *sum_out, uint64_t *sumsq_out) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return mel_stats_run(e, false, "vad_mel_stats", features, rows, n_mels, start, n, max_out, sum_out, sumsq_out, nullptr);
+}
+
+int vad_mel_stats_device(vad_engine *e, const float *d_features, int64_t rows, int32_t n_mels, const int64_t *start, int64_t n, float *d_max_out,
+                         int64_t *d_sum_out, uint64_t *d_sumsq_out, void *stream) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return mel_stats_run(e, true, "vad_mel_stats_device", d_features, rows, n_mels, start, n, d_max_out, d_sum_out, d_sumsq_out, stream);
+}
+
+int vad_mel_batch(vad_engine *e, const float *features, int64_t rows, const int64_t *start, int64_t n, const vad_batch *b,
+                  const vad_batch_window *windows, int64_t nw, const float *lo, const float *shift, const float *scale, int64_t nss, void *out,
+                  int64_t out_bytes) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return mel_batch_run(e, false, "vad_mel_batch", features, rows, start, n, b, windows, nw, lo, shift, scale, nss, out, out_bytes, nullptr);
+}
+
+int vad_mel_batch_device(vad_engine *e, const float *d_features, int64_t rows, const int64_t *start, int64_t n, const vad_batch *b,
+                         const vad_batch_window *windows, int64_t nw, const float *lo, const float *shift, const float *scale, int64_t nss,
+                         void *d_out, int64_t out_bytes, void *stream) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return mel_batch_run(e, true, "vad_mel_batch_device", d_features, rows, start, n, b, windows, nw, lo, shift, scale, nss, d_out, out_bytes, stream);
+}
 
 int64_t vad_resample_cut_samples(const vad_engine *e, int64_t nframes, int32_t sr_in, int32_t hop) {
     if (sr_in == 16000) return -1;

@@ -16,6 +16,7 @@
 //   One k-iteration j consumes quad 2j (lanes 0-31) and quad 2j+1 (lanes 32-63): MFMA
 //   k-step i in 0..3 contracts channel 8j+i (lower half-wave) and 8j+4+i (upper half).
 #pragma once
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #if !defined(__HIPCC__) && !defined(__host__)
@@ -623,5 +624,69 @@ struct RateParams {
     int32_t nseg;
     int32_t total;            // streams of all segments
 };
+
+// statistics and model-ready batches of a feature matrix [rows][n_mels] (csrc/mel_batch.hip; vad_mel_stats, vad_mel_batch).
+// vadk_mel_stats: a workgroup of MELB_THREADS threads reduces MELB_STATS_ROWS consecutive rows of ONE segment (MelStatsWork, listed
+// by the host) and adds its partial results to the segment's with integer atomics; the caller has set max to -inf and the sums to 0.
+constexpr int MELB_THREADS = 256;
+constexpr int MELB_STATS_ROWS = 256;
+struct MelStatsWork {
+    uint32_t seg;             // the segment whose outputs take this workgroup's part
+    uint32_t nrows;           // 1 .. MELB_STATS_ROWS
+    uint64_t row0;            // first row of the part in the matrix
+};
+static_assert(sizeof(MelStatsWork) == 16, "MelStatsWork layout");
+struct MelStatsArgs {
+    const float *x;           // [rows][n_mels]
+    const MelStatsWork *work; // [nwork]
+    float *max_out;           // [n] or nullptr
+    long long *sum_out;       // [n][n_mels] or nullptr
+    unsigned long long *sumsq_out;   // [n][n_mels] or nullptr
+    uint32_t nwork, n_mels;
+};
+static_assert(sizeof(MelStatsArgs) == 48, "MelStatsArgs layout");
+// the fixed-point value of a feature (include/vad_engine.h: vad_mel_stats): exact in float32 up to the conversion
+__host__ __device__ inline int32_t melb_q(float x) {
+    const float c = x < -2048.0f ? -2048.0f : x > 2048.0f ? 2048.0f : x;
+    return (int32_t)rintf(c * 4096.0f);
+}
+
+// vadk_mel_batch: a workgroup serves `tile` consecutive frames of ONE window (workgroup b: window b / tiles, tile b % tiles with
+// tiles = ceil(frames / tile)).  tile is 64, or 32 where the rows of 64 frames with their halo (2 deltas rows on either side), as
+// normalised values and - deltas == 2 - as first differences, would not fit 64 KiB of LDS at the odd pitch n_mels | 1.
+struct MelBatchWin {
+    uint64_t seg_row;         // first row of the window's segment in the matrix
+    uint32_t M;               // rows of the segment
+    uint32_t row0, nrows;     // the window: rows row0 .. row0 + nrows - 1 of the segment, nrows <= frames
+    uint32_t seg;
+};
+static_assert(sizeof(MelBatchWin) == 24, "MelBatchWin layout");
+struct MelBatchArgs {
+    const float *x;           // [rows][n_mels]
+    void *out;                // [nw][C][frames] or [nw][frames][C], C = n_mels (deltas + 1)
+    const MelBatchWin *win;   // [nw]
+    const float *lo;          // [n]
+    const float *shift;       // [nss][n_mels]
+    const float *scale;       // [nss][n_mels]
+    uint32_t nw, n_mels, frames, deltas;
+    int32_t layout, dtype, pad_mode;   // VAD_BATCH_*
+    float pad_value;
+    uint32_t per_seg;         // 1: shift / scale have a row per segment, 0: one row
+    uint32_t tile;            // 64 or 32
+};
+static_assert(sizeof(MelBatchArgs) == 88, "MelBatchArgs layout");
+__host__ __device__ inline uint32_t melb_pitch(uint32_t n_mels) { return n_mels | 1u; }
+__host__ __device__ inline uint32_t melb_lds_floats(uint32_t n_mels, uint32_t deltas, uint32_t tile) {
+    const uint32_t L = tile + 4u * deltas;
+    return (deltas == 2u ? 2u * L - 4u : L) * melb_pitch(n_mels);
+}
+__host__ __device__ inline uint32_t melb_tile(uint32_t n_mels, uint32_t deltas) {
+    return melb_lds_floats(n_mels, deltas, 64u) * 4u <= 65536u ? 64u : 32u;
+}
+// float32 -> bfloat16 bits, round to nearest even; overflow becomes inf, a NaN stays one
+__host__ __device__ inline uint16_t melb_bf16(uint32_t bits) {
+    if ((bits & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((bits >> 16) | 0x40u);
+    return (uint16_t)((bits + 0x7fffu + ((bits >> 16) & 1u)) >> 16);
+}
 
 }  // namespace vadk

@@ -1025,6 +1025,164 @@ class Engine:
                                                   thr, d_out or None, int(out_rows), stream or None))
         return start
 
+    # ------------------------------------------------------------------ model-ready feature batches
+    def mel_keep(self, segments, spec, hop: Optional[int] = None, denoise: Optional[float] = 0.01, audio=None, law: Optional[str] = None,
+                 i16_scale: int = 32767, sample_rate: Optional[int] = None, taps=None) -> np.ndarray:
+        """``mel`` with the rows left on the GPU (``vad_scan_mel_keep``): the same arguments, the same rows byte for byte, in an
+        engine-owned matrix - the RESIDENT MATRIX - that ``mel_stats`` and ``mel_batch`` read with ``features=None``; nothing comes
+        back but -> start [n + 1], the segments' first rows.  The next ``mel_keep`` replaces the matrix; another thread's would too:
+        hold ``scan_session()`` around the scan, the keep and the batch."""
+        m, op_re, op_im, filters = self._mel_arrays(spec)
+        rate = self._scan_rate(sample_rate)
+        h = self._resample_taps(rate, taps) if rate is not None else None
+        with self._scan_lock:
+            sr, total, channels, fmt, ptr, _keep = self._cut_block("mel_keep", audio, law, i16_scale, sample_rate if rate is not None else None)
+            if rate is None and sr is not None:
+                raise AudioProcessingError(f"Model prediction failed: mel_keep(audio=None): the block of the last scan is at {sr} Hz; give "
+                                           "sample_rate")
+            segs = [tuple(sg) for sg in segments]
+            if rate is not None:
+                hop = self.scan_chunk_samples(rate) // 2 if hop is None else int(hop)
+                items, _ = self._cut_items(segs, hop, _ffi.VAD_CUT_RANGE, channels, rate=rate)
+                start = self._mel_rows_16k(m, segs, hop, rate)
+            else:
+                hop = self.frame_samples // 2 if hop is None else int(hop)
+                items, _ = self._cut_items(segs, hop, _ffi.VAD_CUT_RANGE, channels)
+                start = self._mel_rows(m, segs, hop)
+            rows = C.c_int64(-1)
+            thr = -1.0 if denoise is None else float(denoise)
+            self._check(self._lib.vad_scan_mel_keep(self._h, items, len(segs), C.byref(m), _ptr(op_re, C.c_float), _ptr(op_im, C.c_float),
+                                                    _ptr(filters, C.c_float), None if h is None else _ptr(h, C.c_float),
+                                                    0 if h is None else h.size, ptr, total, channels, fmt, rate or 0, hop, thr, C.byref(rows)))
+            if rows.value != int(start[-1]):
+                raise AudioProcessingError(f"Model prediction failed: mel_keep: the engine kept {rows.value} rows, {int(start[-1])} were expected")
+        return start
+
+    def mel_resident(self) -> Tuple[int, int, int]:
+        """-> (rows, n_mels, segments) of the resident matrix (``vad_mel_resident``); an error when none is kept."""
+        rows, nm, ns = C.c_int64(), C.c_int32(), C.c_int64()
+        self._check(self._lib.vad_mel_resident(self._h, C.byref(rows), C.byref(nm), C.byref(ns)))
+        return rows.value, nm.value, ns.value
+
+    def mel_resident_read(self, first_row: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """Rows of the resident matrix copied to the host (``vad_mel_resident_read``) -> float32 [count, n_mels]; default: all."""
+        rows, nm, _ = self.mel_resident()
+        count = rows - int(first_row) if count is None else int(count)
+        out = np.empty((max(count, 0), nm), np.float32)
+        self._check(self._lib.vad_mel_resident_read(self._h, int(first_row), count, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    @staticmethod
+    def _batch_source(features, start):
+        """-> (features or None, its pointer, rows, n_mels or 0, start or None, its pointer, n) for the calls that take a matrix"""
+        x = None if features is None else np.ascontiguousarray(np.asarray(features, np.float32))
+        if x is not None and x.ndim != 2:
+            raise AudioProcessingError(f"Model prediction failed: features are [rows, n_mels], got {x.shape}")
+        st = None if start is None else np.ascontiguousarray(np.asarray(start, np.int64).reshape(-1))
+        if st is not None and st.size < 1:
+            raise AudioProcessingError("Model prediction failed: start has n + 1 entries, got none")
+        return (x, None if x is None else x.ctypes.data_as(C.POINTER(C.c_float)), 0 if x is None else x.shape[0], 0 if x is None else x.shape[1],
+                st, None if st is None else st.ctypes.data_as(C.POINTER(C.c_int64)), 0 if st is None else st.size - 1)
+
+    def mel_stats(self, features=None, start=None, moments: bool = True) -> dict:
+        """Per-segment statistics of a feature matrix, reduced on the GPU (``vad_mel_stats``): ``features`` [rows, n_mels] float32 with
+        the segments' first rows ``start`` [n + 1], or ``None`` for the resident matrix and its starts.  -> ``{"max": float32 [n]}`` -
+        a segment's largest value, -inf for one without rows - and, with ``moments``, ``"sum"`` int64 [n, n_mels] and ``"sumsq"`` uint64
+        [n, n_mels] of ``q = rint(clip(x, -2048, 2048) * 4096)`` and ``q * q``: exact integers, ``cutter_vad_amd.scan.batch_affine`` turns
+        them into means and deviations.  With ``moments`` a segment has 2^17 rows at the most."""
+        x, xp, rows, nm, st, sp, n = self._batch_source(features, start)
+        with self._scan_lock:
+            if x is None or st is None:
+                r_rows, r_nm, r_n = self.mel_resident()
+                rows, nm = (r_rows, r_nm) if x is None else (rows, nm)
+                n = r_n if st is None else n
+            out = {"max": np.empty(n, np.float32)}
+            if moments:
+                out["sum"], out["sumsq"] = np.empty((n, nm), np.int64), np.empty((n, nm), np.uint64)
+            self._check(self._lib.vad_mel_stats(self._h, xp, rows, nm, sp, n, out["max"].ctypes.data_as(C.POINTER(C.c_float)),
+                                                out["sum"].ctypes.data_as(C.POINTER(C.c_int64)) if moments else None,
+                                                out["sumsq"].ctypes.data_as(C.POINTER(C.c_uint64)) if moments else None))
+        return out
+
+    @staticmethod
+    def _batch_record(batch, n_mels: int) -> _ffi.Batch:
+        """``batch``: a ``_ffi.Batch``, an object with ``record(n_mels)`` (``cutter_vad_amd.scan.FeatureBatch``) or a dict of
+        ``vad_batch``'s fields - ``frames``, and optionally ``n_mels``, ``deltas``, ``layout`` / ``dtype`` / ``pad`` (names or numbers),
+        ``pad_value``"""
+        if isinstance(batch, _ffi.Batch):
+            return batch
+        f = dict(batch.record(n_mels) if hasattr(batch, "record") else batch)
+        enum = lambda table, what, v: Engine._cut_enum(table, what, v) if isinstance(v, str) else int(v)
+        return _ffi.Batch(int(f.get("n_mels", n_mels)), int(f["frames"]), int(f.get("deltas", 0)),
+                          enum(_ffi.BATCH_LAYOUTS, "layout", f.get("layout", "channel")), enum(_ffi.BATCH_DTYPES, "dtype", f.get("dtype", "f32")),
+                          enum(_ffi.BATCH_PADS, "pad", f.get("pad", "value")), float(f.get("pad_value", 0.0)), 0)
+
+    @staticmethod
+    def _batch_windows(windows):
+        w = np.ascontiguousarray(np.asarray(windows, _ffi.BATCH_WINDOW_DTYPE).reshape(-1)) if not (
+            isinstance(windows, np.ndarray) and windows.dtype == _ffi.BATCH_WINDOW_DTYPE) else np.ascontiguousarray(windows.reshape(-1))
+        return w, (w if w.size else np.zeros(1, _ffi.BATCH_WINDOW_DTYPE)).ctypes.data_as(C.POINTER(_ffi.BatchWindow))
+
+    @staticmethod
+    def _batch_affine(lo, shift, scale, n_mels: int):
+        """-> (lo, shift, scale as float32 arrays or None, their pointers, nss)"""
+        f32p = C.POINTER(C.c_float)
+        lo = None if lo is None else np.ascontiguousarray(np.asarray(lo, np.float32).reshape(-1))
+        two = []
+        for a in (shift, scale):
+            a = None if a is None else np.asarray(a, np.float32)
+            if a is not None:
+                a = np.full((1, n_mels), a, np.float32) if a.ndim == 0 else np.ascontiguousarray(a.reshape(1, -1) if a.ndim < 2 else a)
+                if a.ndim != 2 or a.shape[1] != n_mels:
+                    raise AudioProcessingError(f"Model prediction failed: shift and scale are [1 or n, n_mels = {n_mels}], got {a.shape}")
+            two.append(a)
+        rows = {a.shape[0] for a in two if a is not None}
+        if len(rows) > 1:
+            raise AudioProcessingError(f"Model prediction failed: shift and scale have the same number of rows, got {sorted(rows)}")
+        ptr = lambda a: None if a is None else a.ctypes.data_as(f32p)
+        return (lo, *two), (ptr(lo), ptr(two[0]), ptr(two[1])), (rows.pop() if rows else 1)
+
+    def mel_batch(self, windows, batch, lo=None, shift=None, scale=None, features=None, start=None) -> np.ndarray:
+        """Normalised, padded windows of a feature matrix in a model's layout and number format (``vad_mel_batch``), one launch:
+        ``windows`` lists ``(seg, nrows, row0)`` - rows ``row0 .. row0 + nrows - 1`` of segment ``seg``
+        (``cutter_vad_amd.scan.batch_windows``) - ``batch`` is a ``cutter_vad_amd.scan.FeatureBatch`` with ``frames`` set, or a dict of
+        ``vad_batch``'s fields.  A value is ``(max(x, lo[seg]) + shift[seg]) * scale[seg]`` in float32 (``lo`` [n] or ``None`` for
+        -inf; ``shift`` / ``scale`` [n_mels], [1, n_mels] or [n, n_mels], ``None`` for 0 and 1), ``deltas`` appends first and second
+        differences over the SEGMENT's rows, frames past ``nrows`` are pad cells (``include/vad_engine.h`` has the rule).
+        ``features`` / ``start`` as in ``mel_stats``; ``None``: the resident matrix.  -> [B, C, T] (``layout="channel"``) or [B, T, C]
+        with C = n_mels * (deltas + 1): float32, ``np.float16``, or the bfloat16 bit patterns as ``np.uint16``."""
+        x, xp, rows, nm, st, sp, n = self._batch_source(features, start)
+        with self._scan_lock:
+            if x is None:
+                nm = self.mel_resident()[1]
+            b = self._batch_record(batch, nm)
+            w, wp = self._batch_windows(windows)
+            _own, ptrs, nss = self._batch_affine(lo, shift, scale, b.n_mels)
+            chans = b.n_mels * (b.deltas + 1)
+            shape = (w.size, chans, b.frames) if b.layout == _ffi.VAD_BATCH_CHANNEL_MAJOR else (w.size, b.frames, chans)
+            out = np.empty(shape, {_ffi.VAD_BATCH_F32: np.float32, _ffi.VAD_BATCH_F16: np.float16}.get(b.dtype, np.uint16))
+            self._check(self._lib.vad_mel_batch(self._h, xp, rows, sp, n, C.byref(b), wp, w.size, *ptrs, nss, out.ctypes.data_as(C.c_void_p),
+                                                out.nbytes))
+        return out
+
+    def mel_batch_device(self, windows, batch, d_out: int, out_bytes: int, lo=None, shift=None, scale=None, d_features: int = 0, rows: int = 0,
+                         n_mels: int = 0, start=None, stream: int = 0) -> Tuple[int, ...]:
+        """``mel_batch`` into device memory (``vad_mel_batch_device``): the windows to ``d_out`` (an integer; 16-byte aligned, room for
+        ``out_bytes``), where a model on the same GPU reads them - nothing crosses the link.  ``d_features`` = 0: the resident matrix,
+        else a float32 matrix [rows, n_mels] on the GPU.  ``windows``, ``lo``, ``shift``, ``scale`` and ``start`` are host arrays, read
+        before the call returns.  Asynchronous on ``stream``.  -> the shape of the batch."""
+        st = None if start is None else np.ascontiguousarray(np.asarray(start, np.int64).reshape(-1))
+        with self._scan_lock:
+            nm = int(n_mels) if d_features else self.mel_resident()[1]
+            b = self._batch_record(batch, nm)
+            w, wp = self._batch_windows(windows)
+            _own, ptrs, nss = self._batch_affine(lo, shift, scale, b.n_mels)
+            self._check(self._lib.vad_mel_batch_device(self._h, d_features or None, int(rows), None if st is None else st.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                       0 if st is None else st.size - 1, C.byref(b), wp, w.size, *ptrs, nss, d_out or None,
+                                                       int(out_bytes), stream or None))
+        chans = b.n_mels * (b.deltas + 1)
+        return (w.size, chans, b.frames) if b.layout == _ffi.VAD_BATCH_CHANNEL_MAJOR else (w.size, b.frames, chans)
+
     # ------------------------------------------------------------------ rendered audio
     @staticmethod
     def _render_ramp(ramp) -> np.ndarray:

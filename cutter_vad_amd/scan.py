@@ -7,7 +7,7 @@ module is for callers who hold many finished recordings of different lengths and
 
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -872,3 +872,185 @@ def features_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, config:
                 lists.append(one)
             out[i] = lists if split else lists[0]
     return out
+
+
+@dataclass(frozen=True)
+class FeatureBatch:
+    """What a model takes of a corpus's log-mel features, for ``batch_recordings`` / ``Engine.mel_batch``: windows of ``frames`` rows
+    every ``stride`` rows of each segment (``stride=None``: ``frames``; ``frames=None``: one window per segment, as long as the longest
+    segment rounded up to a multiple of 4), normalised per SEGMENT by ``norm`` - ``"none"``, ``"whisper"`` (``max(x, max - 8)``, then
+    ``(x + 4) / 4``), ``"cmn"`` (the band's mean taken off) or ``"cmvn"`` (and divided by ``max(std, eps)``) - with ``deltas`` 0, 1 or
+    2 orders of differences appended, laid out ``"channel"`` [B, C, T] or ``"time"`` [B, T, C] as ``dtype`` ``"f32"``, ``"f16"`` or
+    ``"bf16"`` (bit patterns as uint16).  Frames past a segment's end are ``pad_value`` as it is (``pad="value"``) or ``pad_value``
+    through the segment's normalisation (``pad="feature"``: a frame of silence).  Whisper's setting, with ``MelSpec``'s defaults::
+
+        FeatureBatch(frames=3000, norm="whisper", pad="feature", pad_value=-10.0)
+    """
+    frames: Optional[int] = None
+    stride: Optional[int] = None
+    norm: str = "none"
+    eps: float = 1e-5
+    deltas: int = 0
+    layout: str = "channel"
+    dtype: str = "f32"
+    pad: str = "value"
+    pad_value: float = 0.0
+
+    def check(self) -> None:
+        if self.norm not in ("none", "whisper", "cmn", "cmvn"):
+            raise ConfigurationError("norm", repr(self.norm), f"FeatureBatch: norm is 'none', 'whisper', 'cmn' or 'cmvn', got {self.norm!r}")
+        if self.layout not in _ffi.BATCH_LAYOUTS or self.dtype not in _ffi.BATCH_DTYPES or self.pad not in _ffi.BATCH_PADS:
+            raise ConfigurationError("layout", repr((self.layout, self.dtype, self.pad)), f"FeatureBatch: layout is one of {sorted(_ffi.BATCH_LAYOUTS)}, "
+                                     f"dtype one of {sorted(_ffi.BATCH_DTYPES)}, pad one of {sorted(_ffi.BATCH_PADS)}, got {self.layout!r}, "
+                                     f"{self.dtype!r}, {self.pad!r}")
+        if self.frames is not None and (int(self.frames) < 4 or int(self.frames) > 65536 or int(self.frames) % 4):
+            raise ConfigurationError("frames", repr(self.frames), f"FeatureBatch: frames is a multiple of 4 from 4 to 65536, got {self.frames!r}")
+        if self.stride is not None and int(self.stride) < 1:
+            raise ConfigurationError("stride", repr(self.stride), f"FeatureBatch: stride is 1 or more, got {self.stride!r}")
+        if int(self.deltas) not in (0, 1, 2):
+            raise ConfigurationError("deltas", repr(self.deltas), f"FeatureBatch: deltas is 0, 1 or 2, got {self.deltas!r}")
+
+    def record(self, n_mels: int) -> dict:
+        """-> ``vad_batch``'s fields as ``Engine.mel_batch`` takes them (``frames`` must be set)"""
+        self.check()
+        if self.frames is None:
+            raise ConfigurationError("frames", "None", "FeatureBatch: frames=None is resolved by batch_windows; Engine.mel_batch takes a number")
+        return {"n_mels": int(n_mels), "frames": int(self.frames), "deltas": int(self.deltas), "layout": self.layout, "dtype": self.dtype,
+                "pad": self.pad, "pad_value": float(self.pad_value)}
+
+
+def batch_windows(start, frames: Optional[int] = None, stride: Optional[int] = None) -> Tuple[np.ndarray, int]:
+    """The windows of segments whose first rows are ``start`` [n + 1] -> (windows, T): per segment of M rows one window at ``row0 = 0,
+    stride, 2 * stride, ...`` while ``row0 < M``, each of ``min(frames, M - row0)`` rows, as a ``(seg, nrows, row0)`` record array
+    ``Engine.mel_batch`` takes.  ``stride=None``: ``frames``.  ``frames=None``: one window per segment (also one without rows) and T the
+    longest segment rounded up to a multiple of 4 (4 at the least)."""
+    start = np.asarray(start, np.int64).reshape(-1)
+    M = np.diff(start)
+    if start.size < 1 or (M < 0).any():
+        raise ConfigurationError("start", repr(start[:8].tolist()), "batch_windows: start has n + 1 ascending entries")
+    if frames is None:
+        T = max(4, -(-int(M.max(initial=0)) // 4) * 4)
+        if T > 65536:
+            raise ConfigurationError("frames", "None", f"batch_windows: the longest segment has {int(M.max())} rows, a window 65536 at the most: give frames")
+        w = np.zeros(M.size, _ffi.BATCH_WINDOW_DTYPE)
+        w["seg"], w["nrows"] = np.arange(M.size), M
+        return w, T
+    T = int(frames)
+    step = T if stride is None else int(stride)
+    if T < 4 or T > 65536 or T % 4 or step < 1:
+        raise ConfigurationError("frames", repr((frames, stride)), f"batch_windows: frames is a multiple of 4 from 4 to 65536 and stride 1 or more, "
+                                 f"got {frames!r} and {stride!r}")
+    rec = [(i, min(T, int(m) - r), r) for i, m in enumerate(M) for r in range(0, int(m), step)]
+    return np.array(rec, _ffi.BATCH_WINDOW_DTYPE).reshape(-1), T
+
+
+def batch_affine(stats: Optional[dict], start, norm: str = "none", eps: float = 1e-5):
+    """``Engine.mel_stats``'s result -> ``(lo, shift, scale)`` as ``Engine.mel_batch`` takes them, for ``norm``: ``"none"``: three
+    ``None``; ``"whisper"``: ``lo = float32(max) - float32(8)`` per segment, ``shift`` 4, ``scale`` 0.25; ``"cmn"``: ``shift = -mean``
+    per segment and band; ``"cmvn"``: also ``scale = 1 / max(std, eps)`` - ``mean = sum / (4096 M)``, ``var = max(sumsq / (2^24 M) -
+    mean^2, 0)``, in float64, rounded to float32 once.  A segment without rows gets 0 and 1 (and ``lo`` -inf)."""
+    if norm == "none":
+        return None, None, None
+    if norm == "whisper":
+        return np.asarray(stats["max"], np.float32) - np.float32(8.0), np.float32(4.0), np.float32(0.25)
+    if norm not in ("cmn", "cmvn"):
+        raise ConfigurationError("norm", repr(norm), f"batch_affine: norm is 'none', 'whisper', 'cmn' or 'cmvn', got {norm!r}")
+    M = np.diff(np.asarray(start, np.int64).reshape(-1)).astype(np.float64)[:, None]
+    some = M > 0
+    Ms = np.where(some, M, 1.0)
+    mean = np.where(some, np.asarray(stats["sum"]).astype(np.float64) / (4096.0 * Ms), 0.0)
+    shift = (-mean).astype(np.float32)
+    if norm == "cmn":
+        return None, shift, None
+    var = np.maximum(np.asarray(stats["sumsq"]).astype(np.float64) / (16777216.0 * Ms) - mean * mean, 0.0)
+    scale = np.where(some, 1.0 / np.maximum(np.sqrt(var), float(eps)), 1.0).astype(np.float32)
+    return None, shift, scale
+
+
+def _need_batch(engine, who: str) -> None:
+    if not hasattr(engine, "mel_batch"):
+        raise ConfigurationError("batch", "given", f"{who} needs an engine with mel_batch (the windows are normalised and laid out from the "
+                                 f"features a scan left on the GPU), {type(engine).__name__} has none")
+
+
+def batch_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, batch: FeatureBatch, config: Optional[VADConfig] = None, engine=None,
+                     hop: Optional[int] = None, law: Optional[str] = None, channel="mix", open_end: bool = False,
+                     refine: Optional[SegmentRefine] = None, sample_rate: Optional[int] = None, taps=None):
+    """``features_recordings`` as the tensor a model takes: the log-mel features of every finished segment of every recording,
+    windowed, normalised, padded, laid out and converted as ``batch`` says -> ``(array, index)``: ``array`` [B, C, T] or [B, T, C]
+    (``Engine.mel_batch``), ``index`` one ``(recording, channel, start_sample, end_sample, first_frame, nframes)`` per window - the
+    segment it shows (samples of the recording, at its own rate), the window's first row in the segment and its rows.  One scan, one
+    ``Engine.mel_keep``, at most one ``Engine.mel_stats`` and one ``Engine.mel_batch`` under ``Engine.scan_session()``: the features
+    never leave the GPU, only the statistics and the batch cross the link.  The other arguments as in ``features_recordings``.  A
+    corpus of 1-D and 2-D recordings is a ``ConfigurationError``: call it once per kind.  So is an engine object without
+    ``mel_batch``.  No segment anywhere: an array with B = 0."""
+    from .pool import default_pool, resolve_model_path
+    who = "batch_recordings"
+    batch.check()
+    split = isinstance(channel, str) and channel == "split"
+    if not (channel in ("mix", "split") if isinstance(channel, str) else isinstance(channel, (int, np.integer)) and int(channel) in (0, 1)):
+        raise ConfigurationError("channel", repr(channel), f"{who}: channel is 'mix', 0, 1 or 'split' for the whole corpus, got {channel!r}")
+    cfg = config or VADConfig()
+    if engine is None:
+        engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
+    _need_mel(engine, who)
+    _need_batch(engine, who)
+    if open_end:
+        _need_tails(engine, who)
+    if refine is not None:
+        _need_refine(engine, who)
+    if int(spec.sample_rate) != int(engine.sample_rate):
+        raise ConfigurationError("sample_rate", repr(spec.sample_rate), f"{who}: the spec is for {spec.sample_rate} Hz, the engine's blocks "
+                                 f"are at {engine.sample_rate} Hz")
+    frame = engine.frame_samples
+    if cfg.buffer_size != frame:
+        raise ConfigurationError(f"{who} frames at the model's frame size: buffer_size = {cfg.buffer_size}, the engine's frames have "
+                                 f"{frame} samples")
+    rate = None if sample_rate is None or int(sample_rate) == int(engine.sample_rate) else int(sample_rate)
+    mel_kw = {}
+    if rate is not None:
+        if rate not in (8000, 24000, 48000):
+            raise ConfigurationError("sample_rate", repr(sample_rate), f"{who}: recordings at 8000, 16000, 24000 or 48000 Hz, got {sample_rate!r}")
+        _need_resample(engine, who, "sample_rate=")
+        frame = engine.scan_chunk_samples(rate)      # the ranges count input samples
+        mel_kw = {"sample_rate": rate, "taps": taps}
+    hop = frame // 2 if hop is None else int(hop)
+    recordings = [np.asarray(r) for r in recordings]
+    kinds = {r.ndim == 2 for r in recordings}
+    if len(kinds) > 1:
+        raise ConfigurationError("recordings", "1-D and 2-D", f"{who}: one batch holds recordings of one kind; call it once for the 1-D and once "
+                                 "for the two-channel recordings")
+    arrays = spec.operators()
+    n_mels = int(arrays[0]["n_mels"])
+    chans_out = n_mels * (int(batch.deltas) + 1)
+    np_dtype = {"f32": np.float32, "f16": np.float16}.get(batch.dtype, np.uint16)
+    T0 = int(batch.frames) if batch.frames is not None else 4
+    empty = np.empty((0, chans_out, T0) if batch.layout == "channel" else (0, T0, chans_out), np_dtype)
+    if not recordings:
+        return empty, []
+    two = kinds.pop()
+    denoise = 0.01 if cfg.enable_denoising else None
+    per = 2 if two and split else 1
+    chans = (0, 1) if per == 2 else (channel if two else 0,)
+    slots = engine.open_streams(len(recordings) * per)
+    out = None
+    try:
+        engine.set_thresholds_many(slots, _thresholds_of(cfg))
+        with engine.scan_session():
+            ranges = _scan_ranges(engine, slots, recordings, per, frame, hop, law, denoise, channel, rate=rate, open_end=open_end, refine=refine)
+            table = _cut_table(engine, ranges, chans, frame, hop)
+            if table:
+                start = engine.mel_keep(table, arrays, hop=hop, denoise=denoise, **mel_kw)
+                windows, T = batch_windows(start, batch.frames, batch.stride)
+                stats = None if batch.norm == "none" else engine.mel_stats(moments=batch.norm != "whisper")
+                lo, shift, scale = batch_affine(stats, start, batch.norm, batch.eps)
+                rec = replace(batch, frames=T).record(n_mels)
+                out = engine.mel_batch(windows, rec, lo=lo, shift=shift, scale=scale)
+    finally:
+        for s in slots:
+            engine.close_stream(int(s))
+    if out is None:
+        return empty, []
+    where = [(i, chans[c], a, b) for i, rc in enumerate(ranges) for c, rg in enumerate(rc) for a, b, *_ in rg]
+    index = [where[int(w["seg"])] + (int(w["row0"]), int(w["nrows"])) for w in windows]
+    return out, index

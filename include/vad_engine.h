@@ -888,6 +888,103 @@ VAD_API int vad_scan_rate_mel_device(vad_engine *e, const vad_cut_item *items, i
                                      void *stream);
 
 /*
+ * Model-ready feature batches: what an ASR front end, a speaker model or a classifier takes is not the packed matrix of
+ * vad_scan_mel but normalised, padded windows [B][n_mels][T] in its own number format.  Three steps, all on the GPU:
+ *
+ * vad_scan_mel_keep / _device: vad_scan_mel (sr_in = 0 or the engine's rate; taps / ntaps are not read) or vad_scan_rate_mel (sr_in
+ * = 8000, 24000, 48000; denoise_thresh is not read) with the rows left in an engine-owned float32 buffer, the RESIDENT MATRIX,
+ * instead of an `out`: the same kernels, the same refusals in the same words under this function's name, rows byte for byte
+ * those.  The engine remembers n, n_mels and the segments' first rows start[n + 1]; *rows_out (may be NULL) gets start[n].  The
+ * next keep replaces the matrix, a refused keep leaves the previous one, the engine's end frees it; the resident audio block and
+ * the resident segment table are left as the plain calls leave them.  n = 0 keeps a matrix of no rows.  The _device form takes
+ * d_audio as vad_scan_mel_device does and enqueues on `stream`; the calls below wait for it.
+ *   vad_mel_resident: its size (each pointer may be NULL); VAD_ERR_INVALID_ARG with a message when no matrix is kept.
+ *   vad_mel_resident_read: rows first_row .. first_row + count - 1 copied to the host.
+ *
+ * vad_mel_stats / _device: per segment of a matrix features[rows][n_mels] - a host array (_device: on the GPU), or NULL for the
+ * resident matrix, whose rows and n_mels then stand for the arguments - with the segments' first rows start[n + 1] (host in both
+ * forms; 0 <= start[0], ascending, start[n] <= rows), or start = NULL for the resident starts, whose n then stands for the argument.
+ * Each output may be NULL and is then skipped (host arrays; _device: on the GPU, 8-byte aligned):
+ *   max_out[n], float32: the maximum over all values of the segment, by the order of the bit patterns (-0.0 below +0.0); a
+ *     segment without rows has -inf.
+ *   sum_out[n][n_mels], int64, and sumsq_out[n][n_mels], uint64: with q = (int64) rintf(clamp(x, -2048, 2048) * 4096), the sums of q
+ *     and of q * q over the segment's rows.  x * 4096 is exact in float32 and the sums are integers: the result is exact in any
+ *     order.  mean = sum / (4096 M), E[x^2] = sumsq / (2^24 M).  With either requested a segment of more than VAD_STATS_MAX_ROWS =
+ *     2^17 rows is refused by index (2^46 * 2^17 stays inside 64 bits).
+ * The call initialises its outputs itself.  Two runs give the same bytes.  Rows that hold a NaN give unspecified values.
+ *
+ * vad_mel_batch / _device: nw windows of b->frames = T frames each, out[nw][C][T] (VAD_BATCH_CHANNEL_MAJOR) or out[nw][T][C]
+ * (VAD_BATCH_TIME_MAJOR), C = n_mels * (deltas + 1), in float32, float16 or bfloat16.  features, rows, start, n as above (n_mels is
+ * b->n_mels and must be the resident matrix's when that is named).  windows[nw] (host): window w shows rows row0 .. row0 + nrows - 1
+ * of segment seg, 0 <= row0, 0 <= nrows <= T, row0 + nrows <= M (the segment's rows); in any order, overlapping, the same rows twice.
+ * lo[n] (host, or NULL = -inf; no NaN), shift and scale [nss][n_mels] (host, finite; nss = 1: one row for all segments, nss = n: a
+ * row per segment; NULL = 0 and 1, nss is then not read).
+ * THE RULE, all of it float32, each operation rounded on its own.  For segment i, band j, row t in 0 .. M - 1:
+ *     v[t][j] = (fmaxf(x[t][j], lo[i]) + shift[i][j]) * scale[i][j]
+ *   (an add followed by a multiply: nothing to contract into a fused multiply-add).  With c(s) = min(max(s, 0), M - 1):
+ *     d1[t] = ((v[c(t + 1)] - v[c(t - 1)]) + 2 * (v[c(t + 2)] - v[c(t - 2)])) * 0.1f
+ *     d2[t] = ((d1[c(t + 1)] - d1[c(t - 1)]) + 2 * (d1[c(t + 2)] - d1[c(t - 2)])) * 0.1f
+ *   c clamps to the SEGMENT, not to the window: a window inside a segment sees its neighbours' rows.  Channel k * n_mels + j holds
+ *   v for k = 0, d1 for k = 1, d2 for k = 2.  Cell (w, channel, t), t < nrows: the value at segment row row0 + t.  t >= nrows, a
+ *   pad cell: 0 in a delta channel; in a static channel pad_value as it is (VAD_BATCH_PAD_VALUE) or (fmaxf(pad_value, lo[i]) +
+ *   shift[i][j]) * scale[i][j] (VAD_BATCH_PAD_FEATURE: a frame of silence through the same normalisation, as Whisper pads).  Then
+ *   the conversion, round to nearest even; overflow becomes inf.  Every cell of every window is written by the one launch.
+ * Whisper: lo[i] = max_i - 8, shift = 4, scale = 0.25, PAD_FEATURE with pad_value = -10 (log10 of the floor 1e-10), T = 3000.
+ * Refusals (VAD_ERR_INVALID_ARG, a message, the output untouched): a field of vad_batch out of range; n_mels that is not the resident
+ * matrix's; a bad start; a bad window, by index; nss neither 1 nor n; a non-finite scale, shift or pad_value; a NaN lo; out_bytes
+ * below nw * C * T elements; more than 2^31 - 1 workgroups; a device `out` that is not 16-byte aligned; NULL features or start with
+ * no resident matrix.  nw = 0 is VAD_OK.
+ *   The _device forms enqueue on `stream` (NULL = the engine's own) and return; start, windows, lo, shift and scale stay HOST arrays,
+ * read before the call returns.  Every engine is served - V4, 8 kHz, VAD_ENGINE_SHARED_GPU: no model kernel runs.
+ *   VAD_ABI_VERSION is unchanged: the presence of vad_mel_batch is how a caller detects the feature.
+ */
+#define VAD_STATS_MAX_ROWS 131072
+enum { VAD_BATCH_F32 = 0, VAD_BATCH_F16 = 1, VAD_BATCH_BF16 = 2 };
+enum { VAD_BATCH_CHANNEL_MAJOR = 0 /* [B][C][T] */, VAD_BATCH_TIME_MAJOR = 1 /* [B][T][C] */ };
+enum { VAD_BATCH_PAD_VALUE = 0, VAD_BATCH_PAD_FEATURE = 1 };
+typedef struct vad_batch {
+    int32_t n_mels;    /* 1 .. 128 */
+    int32_t frames;    /* T: 4 .. 65536, a multiple of 4 */
+    int32_t deltas;    /* 0 .. 2 */
+    int32_t layout;    /* VAD_BATCH_CHANNEL_MAJOR / VAD_BATCH_TIME_MAJOR */
+    int32_t dtype;     /* VAD_BATCH_F32 / VAD_BATCH_F16 / VAD_BATCH_BF16 */
+    int32_t pad_mode;  /* VAD_BATCH_PAD_VALUE / VAD_BATCH_PAD_FEATURE */
+    float pad_value;   /* finite */
+    int32_t reserved;  /* 0 */
+} vad_batch;
+typedef struct vad_batch_window {
+    int32_t seg;       /* index into the segments */
+    int32_t nrows;     /* 0 .. T */
+    int64_t row0;      /* first row, within the segment */
+} vad_batch_window;
+VAD_API int vad_scan_mel_keep(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re /*[n_fft][n_bins]*/,
+                              const float *op_im /*[n_fft][n_bins]*/, const float *filters /*[n_mels][n_bins]*/,
+                              const float *taps /*host [ntaps]: a rate block*/, int32_t ntaps, const void *audio /*or NULL*/,
+                              int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh,
+                              int64_t *rows_out);
+VAD_API int vad_scan_mel_keep_device(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re /*host*/,
+                                     const float *op_im /*host*/, const float *filters /*host*/, const float *taps /*host [ntaps]*/,
+                                     int32_t ntaps, const void *d_audio, int64_t audio_samples, int32_t channels, int frame_fmt,
+                                     int32_t sr_in, int32_t hop, float denoise_thresh, int64_t *rows_out, void *stream);
+VAD_API int vad_mel_resident(vad_engine *e, int64_t *rows, int32_t *n_mels, int64_t *nsegs);
+VAD_API int vad_mel_resident_read(vad_engine *e, int64_t first_row, int64_t count, float *out /*[count][n_mels]*/);
+VAD_API int vad_mel_stats(vad_engine *e, const float *features /*[rows][n_mels] or NULL*/, int64_t rows, int32_t n_mels,
+                          const int64_t *start /*[n + 1] or NULL*/, int64_t n, float *max_out /*[n] or NULL*/,
+                          int64_t *sum_out /*[n][n_mels] or NULL*/, uint64_t *sumsq_out /*[n][n_mels] or NULL*/);
+VAD_API int vad_mel_stats_device(vad_engine *e, const float *d_features /*on the GPU or NULL*/, int64_t rows, int32_t n_mels,
+                                 const int64_t *start /*host [n + 1] or NULL*/, int64_t n, float *d_max_out, int64_t *d_sum_out,
+                                 uint64_t *d_sumsq_out, void *stream);
+VAD_API int vad_mel_batch(vad_engine *e, const float *features /*[rows][n_mels] or NULL*/, int64_t rows,
+                          const int64_t *start /*[n + 1] or NULL*/, int64_t n, const vad_batch *b, const vad_batch_window *windows,
+                          int64_t nw, const float *lo /*[n] or NULL*/, const float *shift /*[nss][n_mels] or NULL*/,
+                          const float *scale /*[nss][n_mels] or NULL*/, int64_t nss, void *out, int64_t out_bytes);
+VAD_API int vad_mel_batch_device(vad_engine *e, const float *d_features /*on the GPU or NULL*/, int64_t rows,
+                                 const int64_t *start /*host [n + 1] or NULL*/, int64_t n, const vad_batch *b,
+                                 const vad_batch_window *windows /*host*/, int64_t nw, const float *lo /*host*/,
+                                 const float *shift /*host*/, const float *scale /*host*/, int64_t nss, void *d_out, int64_t out_bytes,
+                                 void *stream);
+
+/*
  * Rendered audio: one finished piece of audio per call - the segments of a block faded at their edges, crossfaded where two of
  * them share output samples, joined, everything else silence.  The two standard products of a VAD come out of it by where the caller
  * places the segments: silence removal (the segments back to back, neighbours overlapping by the ramp or a fixed pause apart) and

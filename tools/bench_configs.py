@@ -1389,6 +1389,131 @@ def scan_mel():
     return row
 
 
+def scan_mel_batch():
+    """What model-ready feature batches cost, on scan_mel's corpus and geometry, Whisper's normalisation, float16,
+    windows of 1 000 frames.  (a) Engine.mel_keep + Engine.mel_stats(moments=False) + Engine.mel_batch_device into device memory,
+    up to the synchronise; (b) the parent commit's way to the same bytes: Engine.mel, then per segment the clamp, the scaling, the
+    windows, the padding, the transpose and astype(float16) in numpy on 16 host threads; (a) and (b) alternate, one warm-up and
+    three timed passes, medians.  (c) the two kernels alone on the resident matrix, HIP-event timed as scan_mel's (c), with the
+    bytes each moves.  The result goes to profiles/scan_mel_batch.json."""
+    import ctypes as C
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    from cutter_vad_amd import FeatureBatch, MelSpec, _ffi, batch_windows
+    N = int(os.environ.get("VAD_SCAN_BENCH_N", "1024"))
+    eng = Engine(blob(5), max_streams=max(N, 16))
+    hop, frame, T = 256, 512, 1000
+    pcm = np.tile(np.load(os.path.join(root, "tests", "golden", "speech16k_i16.npz"))["pcm"].astype(np.int16), 3)
+    rng = np.random.default_rng(N)
+    ns = 30 * 16000
+    recs = [pcm[a:a + ns] for a in rng.integers(0, pcm.size - ns + 1, N)]
+    slots = eng.open_streams(N)
+    eng.set_thresholds_many(slots, (0.4, 0.3, 0.8, 0.95, 6, 12))
+    med = lambda v: float(np.median(v))
+    arrays = MelSpec(16000).operators()
+    rec = FeatureBatch(frames=T, norm="whisper", pad="feature", pad_value=-10.0, dtype="f16").record(80)
+    row = {"config": f"scan_mel_batch: {N} int16 recordings of 30 s at 16 kHz in one call, hop {hop}, Whisper's geometry and normalisation, "
+                     f"float16 windows of {T} frames", "recordings": N, "passes": 3, "host_threads": 16}
+    pool = ThreadPoolExecutor(16)
+
+    def numpy_windows(x):
+        """one segment's rows -> its windows [k, 80, T] float16, Whisper's two lines and its padding"""
+        lo = x.max() - np.float32(8.0)
+        v = (np.maximum(x, lo) + np.float32(4.0)) * np.float32(0.25)
+        k = -(-x.shape[0] // T)
+        out = np.empty((k, T, 80), np.float32)
+        out[:] = (np.maximum(np.float32(-10.0), lo) + np.float32(4.0)) * np.float32(0.25)
+        out.reshape(k * T, 80)[:x.shape[0]] = v
+        return out.transpose(0, 2, 1).astype(np.float16)
+
+    with eng.scan_session():
+        table = eng.scan_segments(slots, recs, hop=hop, denoise=0.01)
+        offs = [int(o) for o in eng.last_scan["offsets"]]
+        segs = [(offs[i], a, n) for i, a, n in zip(table["item"].tolist(), table["first_frame"].tolist(), table["nframes"].tolist())]
+        start = eng.mel_keep(segs, arrays, hop=hop, denoise=0.01)
+        windows, _ = batch_windows(start, T)
+        nbytes = windows.size * 80 * T * 2
+        d_out = torch.empty(nbytes // 2 + 8, dtype=torch.float16, device="cuda")
+        row.update(segments=len(segs), rows=int(start[-1]), windows=int(windows.size), batch_bytes=nbytes, matrix_bytes=int(start[-1]) * 320)
+
+        def route_a():
+            eng.mel_keep(segs, arrays, hop=hop, denoise=0.01)
+            lo = eng.mel_stats(moments=False)["max"] - np.float32(8.0)
+            eng.mel_batch_device(windows, rec, d_out.data_ptr(), nbytes, lo=lo, shift=4.0, scale=0.25)
+            eng.synchronize()
+
+        def route_b():
+            t0 = time.perf_counter()
+            feats, st = eng.mel(segs, arrays, hop=hop, denoise=0.01)
+            t1 = time.perf_counter()
+            parts = list(pool.map(numpy_windows, [feats[st[i]:st[i + 1]] for i in range(len(segs)) if st[i + 1] > st[i]]))
+            return np.concatenate(parts), t1 - t0, time.perf_counter() - t1
+
+        route_a()
+        want, _, _ = route_b()
+        row["a_equals_b"] = bool(d_out[:nbytes // 2].cpu().numpy().tobytes() == want.tobytes())
+        a_runs, b_runs, b_mel, b_np = [], [], [], []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            route_a()
+            a_runs.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            _, c, s_ = route_b()
+            b_runs.append(time.perf_counter() - t0)
+            b_mel.append(c)
+            b_np.append(s_)
+        row.update(a_s_keep_stats_batch_runs=a_runs, a_s_keep_stats_batch=med(a_runs), b_s_mel_numpy_runs=b_runs, b_s_mel_numpy=med(b_runs),
+                   b_s_mel=med(b_mel), b_s_numpy=med(b_np), ratio_b_over_a=med(b_runs) / med(a_runs))
+        # (c) the two kernels alone, on the resident matrix
+        ts = torch.cuda.Stream()
+        busy = torch.randn(6144, 6144, device="cuda")
+        lib, h = eng._lib, eng.handle
+        d_max = torch.empty(len(segs), dtype=torch.float32, device="cuda")
+        lo = eng.mel_stats(moments=False)["max"] - np.float32(8.0)
+        b = eng._batch_record(rec, 80)
+        w, wp = eng._batch_windows(windows)
+        sh, sc = np.full((1, 80), 4.0, np.float32), np.full((1, 80), 0.25, np.float32)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+
+        def event_timed(fn):
+            out = []
+            for k in range(5):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                with torch.cuda.stream(ts):
+                    torch.mm(busy, busy)
+                e0.record(ts)
+                assert fn() == 0
+                e1.record(ts)
+                torch.cuda.synchronize()
+                if k >= 2:                           # two warm-ups
+                    out.append(e0.elapsed_time(e1) * 1e-3)
+            return out
+
+        calls = {"c_s_stats_max_device": (lambda: lib.vad_mel_stats_device(h, None, 0, 0, None, 0, d_max.data_ptr(), None, None, ts.cuda_stream),
+                                          int(start[-1]) * 320),
+                 "c_s_batch_device": (lambda: lib.vad_mel_batch_device(h, None, 0, None, 0, C.byref(b), wp, w.size, fp(lo), fp(sh), fp(sc), 1,
+                                                                       d_out.data_ptr(), nbytes, ts.cuda_stream), int(start[-1]) * 320 + nbytes)}
+        for name, (fn, moved) in calls.items():
+            runs = event_timed(fn)
+            row[name + "_runs"], row[name], row[name + "_bytes"], row[name + "_GBps"] = runs, med(runs), moved, moved / med(runs) / 1e9
+    eng.close()
+    with open(os.path.join(root, "profiles", "scan_mel_batch.json"), "w") as f_:
+        json.dump({"what": "Model-ready feature batches (vad_scan_mel_keep, vad_mel_stats, vad_mel_batch, csrc/mel_batch.hip): DESIGN 2.1u",
+                   "how": "python tools/bench_configs.py scan_mel_batch on one MI355X, one process.  (a) and (b) alternate, wall clock around "
+                          "the Python calls up to a device synchronise, one warm-up and three timed passes, medians; (b) uses only code the "
+                          "parent has.  (c) device forms on the resident matrix: HIP events behind a matrix product that keeps the stream "
+                          "busy while the host builds the tables, two warm-ups and three timed passes; the bytes are computed from the "
+                          "shapes (matrix read once, batch written once), not counted.  Not measured: deltas, cmvn statistics, other "
+                          "layouts and number formats, other window lengths, L2 hit rates, the spread between processes and boxes",
+                   "runs": [row]}, f_, indent=1)
+        f_.write("\n")
+    return row
+
+
 def scan_resample_cut():
     """What segment audio and log-mel features at 16 kHz from 48 kHz recordings cost: VAD_SCAN_BENCH_N (default 1 024)
     int16 recordings of 30 s at 48 kHz - the golden clip, every sample three times - hop = chunk / 2, resample_taps' default 97 taps,

@@ -284,6 +284,87 @@ extern "C" hipError_t vadk_launch_resample_cut(const ResampleCutArgs *a, hipStre
     return hipSuccess;
 }
 
+// per-segment statistics of a feature matrix (csrc/mel_batch.hip: vadk_mel_stats), part by part as the workgroups are listed, into
+// the -inf and the zeros the caller stored: the maximum by the order of the bit patterns, the sums of q and q * q in integers
+static bool bits_above(uint32_t y, uint32_t x) {                       // y is the larger float32: -0.0 below +0.0
+    const bool xn = x >> 31, yn = y >> 31;
+    return xn != yn ? xn : xn ? y < x : y > x;
+}
+
+extern "C" hipError_t vadk_launch_mel_stats(const MelStatsArgs *a, hipStream_t) {
+    for (uint32_t b = 0; b < a->nwork; ++b) {
+        const MelStatsWork w = a->work[b];
+        if (w.nrows < 1 || w.nrows > (uint32_t)MELB_STATS_ROWS) return hipErrorInvalidValue;
+        for (uint32_t r = 0; r < w.nrows; ++r)
+            for (uint32_t j = 0; j < a->n_mels; ++j) {
+                const float v = a->x[((size_t)w.row0 + r) * a->n_mels + j];
+                if (a->max_out) {
+                    uint32_t vb, mb;
+                    std::memcpy(&vb, &v, 4);
+                    std::memcpy(&mb, &a->max_out[w.seg], 4);
+                    if (bits_above(vb, mb)) a->max_out[w.seg] = v;
+                }
+                const long long q = melb_q(v);
+                if (a->sum_out) a->sum_out[(size_t)w.seg * a->n_mels + j] += q;
+                if (a->sumsq_out) a->sumsq_out[(size_t)w.seg * a->n_mels + j] += (unsigned long long)(q * q);
+            }
+    }
+    return hipSuccess;
+}
+
+// float32 -> float16 bits, round to nearest even, overflow to inf
+static uint16_t f16_bits(float f) {
+    uint32_t x;
+    std::memcpy(&x, &f, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u;
+    x &= 0x7fffffffu;
+    if (x > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);
+    if (x >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);            // 65520 and above
+    if (x < 0x38800000u) return (uint16_t)(sign | (uint32_t)std::nearbyintf(std::fabs(f) * 16777216.0f));   // below 2^-14: units of 2^-24
+    return (uint16_t)(sign | ((x + 0xfffu + ((x >> 13) & 1u) - 0x38000000u) >> 13));
+}
+
+// model-ready windows of a feature matrix (csrc/mel_batch.hip: vadk_mel_batch): include/vad_engine.h's rule cell by cell, every
+// operation a float32 of its own (volatile: each is rounded where it stands)
+extern "C" hipError_t vadk_launch_mel_batch(const MelBatchArgs *a, hipStream_t) {
+    if (a->tile != melb_tile(a->n_mels, a->deltas)) return hipErrorInvalidValue;
+    const uint32_t nm = a->n_mels, T = a->frames, C = nm * (a->deltas + 1u);
+    for (uint32_t wi = 0; wi < a->nw; ++wi) {
+        const MelBatchWin w = a->win[wi];
+        if (w.nrows > T || (uint64_t)w.row0 + w.nrows > w.M) return hipErrorInvalidValue;
+        const float lo = a->lo[w.seg];
+        const float *shift = a->shift + (size_t)(a->per_seg ? w.seg : 0u) * nm, *scale = a->scale + (size_t)(a->per_seg ? w.seg : 0u) * nm;
+        auto norm = [&](float x, uint32_t j) -> float {
+            volatile float s = (x > lo ? x : lo) + shift[j];
+            return s * scale[j];
+        };
+        auto c = [&](int64_t s) -> int64_t { return s < 0 ? 0 : s > (int64_t)w.M - 1 ? (int64_t)w.M - 1 : s; };
+        auto v = [&](int64_t s, uint32_t j) -> float { return norm(a->x[((size_t)w.seg_row + (size_t)c(s)) * nm + j], j); };
+        auto delta = [&](float m2, float m1, float p1, float p2) -> float {
+            volatile float d1 = p1 - m1, d2 = p2 - m2, t2 = 2.0f * d2, sum = d1 + t2;
+            return sum * 0.1f;
+        };
+        auto d1 = [&](int64_t s, uint32_t j) -> float { s = c(s); return delta(v(s - 2, j), v(s - 1, j), v(s + 1, j), v(s + 2, j)); };
+        auto d2 = [&](int64_t s, uint32_t j) -> float { return delta(d1(s - 2, j), d1(s - 1, j), d1(s + 1, j), d1(s + 2, j)); };
+        for (uint32_t ch = 0; ch < C; ++ch)
+            for (uint32_t t = 0; t < T; ++t) {
+                const uint32_t k = ch / nm, j = ch % nm;
+                const int64_t s = (int64_t)w.row0 + t;
+                float val;
+                if (t >= w.nrows) val = k ? 0.0f : a->pad_mode == VAD_BATCH_PAD_FEATURE ? norm(a->pad_value, j) : a->pad_value;
+                else val = k == 0 ? v(s, j) : k == 1 ? d1(s, j) : d2(s, j);
+                const size_t o = a->layout == VAD_BATCH_TIME_MAJOR ? ((size_t)wi * T + t) * C + ch : ((size_t)wi * C + ch) * T + t;
+                if (a->dtype == VAD_BATCH_F32) static_cast<float *>(a->out)[o] = val;
+                else {
+                    uint32_t bits;
+                    std::memcpy(&bits, &val, 4);
+                    static_cast<uint16_t *>(a->out)[o] = a->dtype == VAD_BATCH_F16 ? f16_bits(val) : melb_bf16(bits);
+                }
+            }
+    }
+    return hipSuccess;
+}
+
 // one finished piece of audio (csrc/scan_render.hip: vadk_scan_render), the kernel's arithmetic in plain C++, output quad by output
 // quad as its workgroups are listed: per covering segment the cut's decoded, channel-selected, gated sample, times the gain, times
 // the fade-in entry (or 1), times the fade-out entry (or 1) - three float32 multiplies - then the sum of the two where two segments
