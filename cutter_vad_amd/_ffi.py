@@ -138,6 +138,9 @@ VAD_CUT_WG_SAMPLES = 4096
 VAD_RENDER_MAX_RAMP = 65536
 VAD_RESAMPLE_CUT_MAX_TAPS = 511
 VAD_RESAMPLE_CUT_WG_SAMPLES = 2048
+VAD_CONVERT_MAX_REACH = 128
+VAD_CONVERT_MIN_RATE, VAD_CONVERT_MAX_RATE, VAD_CONVERT_MAX_PERIOD = 4000, 192000, 640
+VAD_CONVERT_WG_SAMPLES = 2048
 CUT_LAYOUTS = {"frames": VAD_CUT_FRAMES, "range": VAD_CUT_RANGE}
 CUT_OUTPUTS = {"pcm16": VAD_CUT_PCM16, "f32": VAD_CUT_F32}
 
@@ -353,6 +356,13 @@ SIGNATURES = {
                                          C.c_int32, C.c_int32, C.c_float, C.c_int32, _vp, C.c_int64]),
     "vad_scan_render_stereo_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32,
                                                 C.c_int, C.c_int32, C.c_int32, C.c_float, C.c_int32, _vp, C.c_int64, _vp]),
+    "vad_convert_samples": (C.c_int64, [_vp, C.c_int64, C.c_int32]),
+    "vad_convert": (C.c_int, [_vp, C.POINTER(ScanChItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, _f32p, C.c_int32, _f32p,
+                              C.c_int64, _i64p]),
+    "vad_convert_device": (C.c_int, [_vp, C.POINTER(ScanChItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, _f32p, C.c_int32,
+                                     _vp, C.c_int64, _i64p, _vp]),
+    "vad_scan_convert_segments": (C.c_int, [_vp, C.POINTER(ScanChItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, _f32p,
+                                            C.c_int32, C.c_int32, C.c_float, C.POINTER(Segment), C.c_int64, _i64p, _i64p]),
 }
 
 _lib = None

@@ -23,6 +23,7 @@
 #include <chrono>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -47,6 +48,7 @@ extern "C" hipError_t vadk_launch_scan_cut_gain(const vadk::CutArgs *a, const fl
 extern "C" hipError_t vadk_launch_seg_levels(const vadk::CutArgs *a, float clip, hipStream_t stream);
 extern "C" hipError_t vadk_launch_seg_mel(const vadk::MelArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_resample_cut(const vadk::ResampleCutArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_convert(const vadk::ConvertArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_mel_stats(const vadk::MelStatsArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_mel_batch(const vadk::MelBatchArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_render(const vadk::RenderArgs *a, hipStream_t stream);
@@ -207,6 +209,21 @@ struct vad_engine {
     float *d_rsc = nullptr; size_t d_rsc_cap = 0;
     float *d_rsc_mid = nullptr; size_t d_rsc_mid_cap = 0;
     std::vector<vadk::CutSeg> rsc_mel_segs;
+    // vad_convert / vad_scan_convert_segments: the packed operators of all row-tiles (vad_layout.h: cv_pack_index) in d_cv_op, CACHED
+    // by (L, M, the taps' bytes) as the resample cut's operator is; the block in its wire format (d_cv_in: the staging of the host
+    // forms), vad_convert's converted block (d_cv_out; vad_scan_convert_segments converts into d_audio), and the item and workgroup
+    // tables as they were uploaded (d_cv_tab)
+    std::vector<float> cv_src, cv_pack;
+    uint32_t cv_L = 0, cv_M = 0;
+    bool cv_packed = false;
+    float *d_cv_op = nullptr; size_t d_cv_op_cap = 0;
+    uint8_t *d_cv_in = nullptr; size_t d_cv_in_cap = 0;
+    float *d_cv_out = nullptr; size_t d_cv_out_cap = 0;
+    uint8_t *d_cv_tab = nullptr; size_t d_cv_tab_cap = 0;
+    std::vector<vadk::ConvertItem> cv_items;
+    std::vector<vadk::ConvertWork> cv_work;
+    std::vector<int64_t> cv_offset;
+    std::vector<vad_scan_ch_item> cv_scan_items;
     // vad_scan_mel_keep: the RESIDENT MATRIX d_melk [melk_start.back()][melk_n_mels] and its segments' first rows (n + 1 entries;
     // empty: none kept).  vad_mel_stats / vad_mel_batch: a host matrix uploaded to d_melb_in, the tables in d_melb (stats:
     // workgroups, the maxima's -inf; batch: windows, lo, shift, scale), the host forms' outputs in d_melb_out
@@ -945,7 +962,7 @@ void vad_engine_destroy(vad_engine *e) {
     weights_release(e->d_wstream16x);
     weights_release(e->d_wstream16y);
     void *bufs[] = {e->d_refine, e->d_refine_in, e->d_refine_out, e->d_tail_len, e->d_tailwork, e->d_reseg, e->d_resegtab, e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots, e->d_g711,
-                    e->d_audio, e->d_items, e->d_win, e->d_items_win, e->d_cut, e->d_cut_out, e->d_mel, e->d_rsc, e->d_rsc_mid, e->d_melk, e->d_melb_in, e->d_melb, e->d_melb_out, e->d_segwork, e->d_nsegs, e->d_segtab, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
+                    e->d_audio, e->d_items, e->d_win, e->d_items_win, e->d_cut, e->d_cut_out, e->d_mel, e->d_rsc, e->d_rsc_mid, e->d_cv_op, e->d_cv_in, e->d_cv_out, e->d_cv_tab, e->d_melk, e->d_melb_in, e->d_melb, e->d_melb_out, e->d_segwork, e->d_nsegs, e->d_segtab, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->scan_done) (void)hipEventDestroy(e->scan_done);
@@ -1543,7 +1560,8 @@ int scan_enqueue(vad_engine *e, const void *d_audio, int64_t audio_samples, int3
 // it is; the launches write the engine's own d_probs / d_events / d_seg.  resident: the block stays for a cut with audio = NULL,
 // as a block at the engine's rate (chunk == 0) or as a rate block of sr_in - whatever becomes of the launches
 int scan_upload_launch(vad_engine *e, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt, int chunk,
-                       int32_t sr_in, int32_t hop, float denoise_thresh, int64_t total, bool resident) {
+                       int32_t sr_in, int32_t hop, float denoise_thresh, int64_t total, bool resident,
+                       const std::function<int()> *fill = nullptr) {
     const size_t ab = (size_t)audio_samples * (size_t)channels * sample_bytes(frame_fmt);
     e->audio_resident = false;
     e->scan_results = false;
@@ -1553,7 +1571,12 @@ int scan_upload_launch(vad_engine *e, int64_t n, const void *audio, int64_t audi
     if (int rc = ensure(e, e->d_events, e->d_events_cap, (size_t)total)) return rc;
     if (int rc = ensure(e, e->d_seg, e->d_seg_cap, sizeof(int32_t) * (size_t)total)) return rc;
     HIP_TRY(e, hipMemcpyAsync(e->d_items, e->scan_items.data(), sizeof(vadk::ScanItem) * (size_t)n, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, ab, hipMemcpyHostToDevice, e->stream));
+    // fill (vad_scan_convert_segments): the block is made on the device, by launches on the engine's stream
+    if (fill) {
+        if (int rc = (*fill)()) return rc;
+    } else {
+        HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, ab, hipMemcpyHostToDevice, e->stream));
+    }
     if (resident) set_resident(e, ab, channels, frame_fmt, chunk > 0 ? sr_in : 0);
     return scan_enqueue(e, e->d_audio, audio_samples, channels, frame_fmt, chunk, hop, denoise_thresh, e->d_probs, e->d_events, e->d_seg, total,
                         e->stream);
@@ -3207,10 +3230,11 @@ int tail_setup(vad_engine *e, const uint8_t *d_events, const float *d_probs, con
 }
 
 // vad_scan_segments and vad_scan_rate_segments (chunk > 0: the recordings are at sr_in), with e->mu held: the scan of host audio
-// into the engine's own arrays - the block stays resident, of its rate - then the extraction
+// into the engine's own arrays - the block stays resident, of its rate - then the extraction.  fill (vad_scan_convert_segments):
+// there is no host audio, the block is written into e->d_audio by fill's launches
 int scan_segments_run(vad_engine *e, const char *who, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples,
                       int32_t channels, int frame_fmt, int chunk, int32_t sr_in, int32_t hop, float denoise_thresh, vad_segment *segs_out,
-                      int64_t seg_cap, int64_t *nsegs_out) {
+                      int64_t seg_cap, int64_t *nsegs_out, const std::function<int()> *fill = nullptr) {
     HIP_TRY(e, hipSetDevice(e->device));
     if (int rc = scan_wait(e)) return rc;
     // the CSR positions the caller of vad_scan_channels would have passed are the plan's to make: the items packed in their order
@@ -3219,7 +3243,7 @@ int scan_segments_run(vad_engine *e, const char *who, const vad_scan_ch_item *it
     int64_t total = 0;
     if (int rc = scan_plan(e, who, items, n, audio_samples, channels, frame_fmt, hop, (const int64_t *)nullptr, 0, &total, &start, chunk)) return rc;
     if (seg_cap < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: seg_cap = %lld: bad count", who, (long long)seg_cap);
-    if (!nsegs_out || (seg_cap > 0 && !segs_out) || (total > 0 && !audio))
+    if (!nsegs_out || (seg_cap > 0 && !segs_out) || (total > 0 && !audio && !fill))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
     e->segtab_count = -1;
     if (total == 0) {                        // nothing to scan: an empty table
@@ -3228,7 +3252,7 @@ int scan_segments_run(vad_engine *e, const char *who, const vad_scan_ch_item *it
         *nsegs_out = 0;
         return VAD_OK;
     }
-    if (int rc = scan_upload_launch(e, n, audio, audio_samples, channels, frame_fmt, chunk, sr_in, hop, denoise_thresh, total, true)) return rc;
+    if (int rc = scan_upload_launch(e, n, audio, audio_samples, channels, frame_fmt, chunk, sr_in, hop, denoise_thresh, total, true, fill)) return rc;
     {   // the tails' lengths, out of the streams' state machines as the model launches leave them (vad_scan_tails): one small
         // launch on the same stream, no model launch - vad_info.steps and .frames do not move; whatever a later call does to the
         // slots comes behind it
@@ -3339,6 +3363,257 @@ int vad_scan_segments_read(vad_engine *e, int64_t first, int64_t count, vad_segm
     HIP_TRY(e, hipSetDevice(e->device));
     HIP_TRY(e, hipMemcpyAsync(out, e->d_segtab + first, sizeof(vad_segment) * (size_t)count, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return VAD_OK;
+}
+
+}  // extern "C"
+
+// ---- vad_convert / vad_scan_convert_segments: whole recordings at any accepted rate, converted once to the engine's rate -------
+namespace {
+
+// everything about a conversion that follows from the two rates and the tap count (vad_layout.h: the periods)
+struct ConvertPlan {
+    uint32_t L = 0, M = 0, P = 0, PI = 0, ntiles = 0, K = 0, lead = 0, nper = 0;
+    int32_t bmax = 0;
+};
+
+// L / M of the header's rule; false: sr_in is not an accepted rate (L and M are set where they exist, for the message)
+bool convert_ratio(int32_t R, int32_t sr_in, uint32_t *L, uint32_t *M) {
+    *L = *M = 0;
+    if (R < 1 || sr_in < 1) return false;
+    const uint32_t g = vadk::cv_gcd((uint32_t)R, (uint32_t)sr_in);
+    *L = (uint32_t)R / g;
+    *M = (uint32_t)sr_in / g;
+    if (sr_in < VAD_CONVERT_MIN_RATE || sr_in > VAD_CONVERT_MAX_RATE || sr_in == R) return false;
+    return *L / vadk::cv_gcd(*L, 16u) * 16u <= (uint32_t)VAD_CONVERT_MAX_PERIOD && *M <= (uint32_t)VAD_CONVERT_MAX_PERIOD;
+}
+
+// what comes before the block's and the items' checks: the rate, then the taps
+int convert_check(vad_engine *e, const char *who, int32_t sr_in, const float *taps, int32_t ntaps, ConvertPlan *c) {
+    uint32_t L = 0, M = 0;
+    if (!convert_ratio(e->sample_rate, sr_in, &L, &M))
+        return e->fail(VAD_ERR_UNSUPPORTED, "Failed to resample audio from %dHz to %dHz: %s: L / M = %u / %u; accepted are rates from %d to %d Hz other "
+                       "than the engine's whose period lcm(L, 16) is at most %d outputs and whose M is at most %d", sr_in, e->sample_rate, who, L, M,
+                       VAD_CONVERT_MIN_RATE, VAD_CONVERT_MAX_RATE, VAD_CONVERT_MAX_PERIOD, VAD_CONVERT_MAX_PERIOD);
+    if (!taps) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null taps", who);
+    const int64_t most = (int64_t)VAD_CONVERT_MAX_REACH * (int64_t)L;
+    if (ntaps < 1 || (int64_t)ntaps > most || !(ntaps & 1))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: ntaps = %d must be odd, from 1 to %lld (VAD_CONVERT_MAX_REACH * L, L = %u)", who,
+                       ntaps, (long long)most, L);
+    for (int32_t k = 0; k < ntaps; ++k)
+        if (!std::isfinite(taps[k]))
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: taps[%d] is %s, a tap is a finite number", who, k,
+                           std::isnan(taps[k]) ? "NaN" : "infinite");
+    c->L = L;
+    c->M = M;
+    c->P = vadk::cv_P(L);
+    c->PI = vadk::cv_PI(L, M);
+    c->ntiles = c->P / 16u;
+    c->K = vadk::cv_K((uint32_t)ntaps, L, M);
+    c->lead = vadk::cv_lead((uint32_t)ntaps, L);
+    c->bmax = vadk::cv_base(c->ntiles - 1u, (uint32_t)ntaps, L, M);
+    c->nper = vadk::cv_nper(c->P, c->PI, c->lead, c->bmax, c->K);
+    if (c->nper == 0)
+        return e->fail(VAD_ERR_UNSUPPORTED, "Failed to resample audio from %dHz to %dHz: %s: L / M = %u / %u: one period of %u inputs and %d taps "
+                       "does not fit a workgroup's local memory", sr_in, e->sample_rate, who, L, M, c->PI, ntaps);
+    return VAD_OK;
+}
+
+// The block's and the items' refusals, in vad_scan_channels's words (scan_plan's; no hop, no slot and no stream count enter a
+// conversion), and the plan: e->cv_items, e->cv_work, and e->cv_offset [n + 1] = the items' first samples in the converted block
+int convert_plan(vad_engine *e, const char *who, const ConvertPlan &c, const vad_scan_ch_item *items, int64_t n, int64_t audio_samples,
+                 int32_t channels, int fmt) {
+    if (n < 0 || audio_samples < 0 || (n > 0 && !items)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer or bad count", who);
+    if (int rc = check_block_format(e, who, fmt, channels)) return rc;
+    if (int rc = check_block_extent(e, who, 4, audio_samples, channels, fmt)) return rc;
+    if (n > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 items", who);
+    e->cv_items.resize((size_t)n);
+    e->cv_work.clear();
+    e->cv_offset.assign((size_t)n + 1, 0);
+    const uint64_t run = (uint64_t)c.nper * c.P;
+    for (int64_t i = 0; i < n; ++i) {
+        const vad_scan_ch_item &it = items[i];
+        if (it.sample_offset < 0 || (it.sample_offset & 3))
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: recording %lld starts at sample %lld, not a multiple of 4", who,
+                           (long long)i, (long long)it.sample_offset);
+        if (it.nsamples < 0 || it.sample_offset > audio_samples || it.nsamples > audio_samples - it.sample_offset)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: recording %lld (samples %lld .. +%lld) leaves the audio block of %lld samples", who,
+                           (long long)i, (long long)it.sample_offset, (long long)it.nsamples, (long long)audio_samples);
+        if (it.channel != VAD_SCAN_MIX && (it.channel < 0 || it.channel >= channels))
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: recording %lld names channel %d of %d (0 .. channels - 1, or VAD_SCAN_MIX)", who,
+                           (long long)i, it.channel, channels);
+        if (it.reserved != 0)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: recording %lld: reserved = %d must be 0", who, (long long)i, it.reserved);
+        const uint64_t s_out = (uint64_t)it.nsamples * c.L / c.M;        // (nsamples < 2^31, L <= 640)
+        const int64_t at = e->cv_offset[(size_t)i];
+        e->cv_offset[(size_t)i + 1] = at + (int64_t)((s_out + 3u) & ~(uint64_t)3);
+        if (e->cv_offset[(size_t)i + 1] >= (int64_t)1 << 29)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the converted block reaches 2 GiB of float32 at recording %lld; one call "
+                           "may address less", who, (long long)i);
+        const uint32_t mode = channels == 1 ? vadk::SCAN_LEFT : it.channel == VAD_SCAN_MIX ? vadk::SCAN_MIX : (uint32_t)it.channel;
+        e->cv_items[(size_t)i] = vadk::ConvertItem{(uint32_t)(it.sample_offset >> 2) | (mode << vadk::SCAN_MODE_SHIFT), (uint32_t)it.nsamples,
+                                                   (uint32_t)s_out, (uint32_t)(at >> 2)};
+        for (uint64_t r = 0; r * run < s_out; ++r) e->cv_work.push_back(vadk::ConvertWork{(uint32_t)i, (uint32_t)r});
+    }
+    return VAD_OK;
+}
+
+// the operators of all row-tiles in fragment order in e->d_cv_op, zeros outside the taps; cached against the previous call's bytes
+int convert_operator(vad_engine *e, const ConvertPlan &c, const float *taps, int32_t ntaps, hipStream_t s) {
+    if (e->cv_packed && e->cv_L == c.L && e->cv_M == c.M && e->cv_src.size() == (size_t)ntaps &&
+        !std::memcmp(e->cv_src.data(), taps, sizeof(float) * (size_t)ntaps))
+        return VAD_OK;
+    e->cv_packed = false;
+    const size_t floats = (size_t)c.ntiles * 16u * c.K;
+    if (int rc = ensure(e, e->d_cv_op, e->d_cv_op_cap, sizeof(float) * floats)) return rc;
+    e->cv_src.assign(taps, taps + ntaps);
+    e->cv_pack.assign(floats, 0.0f);
+    for (uint32_t r = 0; r < c.ntiles; ++r)
+        for (uint32_t o = 0; o < 16u; ++o)
+            for (uint32_t n = 0; n < c.K; ++n) {
+                const int64_t t = vadk::cv_tap(r, o, n, (uint32_t)ntaps, c.L, c.M);
+                if (t >= 0 && t < ntaps) e->cv_pack[vadk::cv_pack_index(r, o, n, c.K)] = taps[t];
+            }
+    HIP_TRY(e, hipMemcpyAsync(e->d_cv_op, e->cv_pack.data(), sizeof(float) * floats, hipMemcpyHostToDevice, s));
+    e->cv_L = c.L;
+    e->cv_M = c.M;
+    e->cv_packed = true;
+    return VAD_OK;
+}
+
+// the planned conversion on `s`: the operators, the tables, the launch.  d_audio: the block in its wire format; d_out: room for
+// e->cv_offset.back() floats
+int convert_enqueue(vad_engine *e, const ConvertPlan &c, const float *taps, int32_t ntaps, const void *d_audio, int32_t channels, int fmt,
+                    float *d_out, hipStream_t s) {
+    if (e->cv_work.empty()) return VAD_OK;
+    if (int rc = convert_operator(e, c, taps, ntaps, s)) return rc;
+    const size_t ib = sizeof(vadk::ConvertItem) * e->cv_items.size(), wb = sizeof(vadk::ConvertWork) * e->cv_work.size();
+    if (int rc = ensure(e, e->d_cv_tab, e->d_cv_tab_cap, ib + wb)) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->d_cv_tab, e->cv_items.data(), ib, hipMemcpyHostToDevice, s));
+    HIP_TRY(e, hipMemcpyAsync(e->d_cv_tab + ib, e->cv_work.data(), wb, hipMemcpyHostToDevice, s));
+    vadk::ConvertArgs a{};
+    a.audio = d_audio;
+    a.out = d_out;
+    a.items = reinterpret_cast<const vadk::ConvertItem *>(e->d_cv_tab);
+    a.work = reinterpret_cast<const vadk::ConvertWork *>(e->d_cv_tab + ib);
+    a.op = e->d_cv_op;
+    a.nwork = (uint32_t)e->cv_work.size();
+    a.L = c.L;
+    a.M = c.M;
+    a.ntaps = (uint32_t)ntaps;
+    a.P = c.P;
+    a.PI = c.PI;
+    a.ntiles = c.ntiles;
+    a.ksteps = c.K >> 4;
+    a.nper = c.nper;
+    a.bmax = c.bmax;
+    a.fmt = fmt;
+    a.channels = channels;
+    const hipError_t r = vadk_launch_convert(&a, s);
+    if (r != hipSuccess) return e->hip_fail(r, "kernel launch (convert)");
+    return VAD_OK;
+}
+
+// vad_convert and vad_convert_device with e->mu held
+int convert_run(vad_engine *e, bool dev, const char *who, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples,
+                int32_t channels, int fmt, int32_t sr_in, const float *taps, int32_t ntaps, float *out, int64_t out_samples, int64_t *out_offset,
+                void *stream) {
+    hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    ConvertPlan c;
+    if (int rc = convert_check(e, who, sr_in, taps, ntaps, &c)) return rc;
+    if (int rc = convert_plan(e, who, c, items, n, audio_samples, channels, fmt)) return rc;
+    const int64_t total = e->cv_offset.back();
+    if (out_samples < total)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_samples = %lld, the converted block has %lld samples", who,
+                       (long long)out_samples, (long long)total);
+    if (total > 0 && (!audio || !out)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if (dev && total > 0) {
+        if (int rc = check_device_audio(e, who, audio, channels)) return rc;
+        if (reinterpret_cast<uintptr_t>(out) & 15)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output must be 16-byte aligned", who);
+    }
+    if (out_offset) std::copy(e->cv_offset.begin(), e->cv_offset.end(), out_offset);
+    if (total == 0) return VAD_OK;
+    const void *d_in = audio;
+    float *d_out = out;
+    if (!dev) {
+        const size_t ab = (size_t)audio_samples * (size_t)channels * sample_bytes(fmt);
+        if (int rc = ensure(e, e->d_cv_in, e->d_cv_in_cap, ab + 16)) return rc;
+        if (int rc = ensure(e, e->d_cv_out, e->d_cv_out_cap, sizeof(float) * (size_t)total)) return rc;
+        HIP_TRY(e, hipMemcpyAsync(e->d_cv_in, audio, ab, hipMemcpyHostToDevice, s));
+        d_in = e->d_cv_in;
+        d_out = e->d_cv_out;
+    }
+    const int rc = convert_enqueue(e, c, taps, ntaps, d_in, channels, fmt, d_out, s);
+    if (dev) {
+        // the launch reads the engine's tables and operators: the next scan, cut or conversion waits for it
+        if (int rc2 = scan_mark_pending(e, s)) return rc2;
+        return rc;
+    }
+    if (rc) return rc;
+    HIP_TRY(e, hipMemcpyAsync(out, e->d_cv_out, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    return VAD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t vad_convert_samples(const vad_engine *e, int64_t nsamples, int32_t sr_in) {
+    uint32_t L = 0, M = 0;
+    if (!e || nsamples < 0 || nsamples >= ((int64_t)1 << 31) || !convert_ratio(e->sample_rate, sr_in, &L, &M)) return -1;
+    return nsamples * (int64_t)L / (int64_t)M;
+}
+
+int vad_convert(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt,
+                int32_t sr_in, const float *taps, int32_t ntaps, float *out, int64_t out_samples, int64_t *out_offset) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return convert_run(e, false, "vad_convert", items, n, audio, audio_samples, channels, frame_fmt, sr_in, taps, ntaps, out, out_samples, out_offset,
+                       nullptr);
+}
+
+int vad_convert_device(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
+                       int frame_fmt, int32_t sr_in, const float *taps, int32_t ntaps, float *d_out, int64_t out_samples, int64_t *out_offset,
+                       void *stream) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return convert_run(e, true, "vad_convert_device", items, n, d_audio, audio_samples, channels, frame_fmt, sr_in, taps, ntaps, d_out, out_samples,
+                       out_offset, stream);
+}
+
+// the conversion into e->d_audio, then vad_scan_segments' own path over that block: the items {slot, out_offset[i], S_out_i, 0} of a
+// mono float32 block of out_offset[n] samples
+int vad_scan_convert_segments(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
+                              int frame_fmt, int32_t sr_in, const float *taps, int32_t ntaps, int32_t hop, float denoise_thresh,
+                              vad_segment *segs_out, int64_t seg_cap, int64_t *nsegs_out, int64_t *out_offset) {
+    static const char *who = "vad_scan_convert_segments";
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIP_TRY(e, hipSetDevice(e->device));
+    if (int rc = scan_wait(e)) return rc;
+    ConvertPlan c;
+    if (int rc = convert_check(e, who, sr_in, taps, ntaps, &c)) return rc;
+    if (int rc = convert_plan(e, who, c, items, n, audio_samples, channels, frame_fmt)) return rc;
+    const int64_t total = e->cv_offset.back();
+    e->cv_scan_items.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i)
+        e->cv_scan_items[(size_t)i] = vad_scan_ch_item{items[i].slot, e->cv_offset[(size_t)i], (int64_t)e->cv_items[(size_t)i].s_out, 0, 0};
+    if (!audio && !e->cv_work.empty()) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    const std::function<int()> fill = [&]() -> int {
+        const size_t ab = (size_t)audio_samples * (size_t)channels * sample_bytes(frame_fmt);
+        if (int rc = ensure(e, e->d_cv_in, e->d_cv_in_cap, ab + 16)) return rc;
+        HIP_TRY(e, hipMemcpyAsync(e->d_cv_in, audio, ab, hipMemcpyHostToDevice, e->stream));
+        return convert_enqueue(e, c, taps, ntaps, e->d_cv_in, channels, frame_fmt, static_cast<float *>(e->d_audio), e->stream);
+    };
+    // (vad_scan_segments' refusals follow under this function's name; a refused call has written nothing)
+    if (int rc = scan_segments_run(e, who, e->cv_scan_items.data(), n, nullptr, total, 1, VAD_FMT_F32, 0, 0, hop, denoise_thresh, segs_out, seg_cap,
+                                   nsegs_out, &fill))
+        return rc;
+    if (out_offset) std::copy(e->cv_offset.begin(), e->cv_offset.end(), out_offset);
     return VAD_OK;
 }
 

@@ -403,6 +403,88 @@ struct ResampleCutArgs {
 };
 static_assert(sizeof(ResampleCutArgs) == 88, "ResampleCutArgs layout");
 
+// whole recordings of a block at ANY rational rate as one continuous signal each at the engine's rate (csrc/scan_convert.hip:
+// vadk_convert; vad_convert, vad_scan_convert_segments).  L / M = engine rate / sr_in in lowest terms.  16 outputs do not advance a
+// whole number of inputs in general; a PERIOD of P = lcm(L, 16) outputs does: PI = P M / L inputs (441 for the 44.1 kHz family).  A
+// period has NT = P / 16 row-tiles, each with a 16 x K operator and a first-input offset of its own: output 16 r + o of period p is
+//     D_r[o][p] = sum over n < K of T_r[o][n] * x[p PI + base_r + n],   T_r[o][n] = h[(16 r + o) M - (base_r + n) L + C]  (0 outside)
+// with base_r = floor((16 r M - C) / L), the first input the tile's first output reads, and K = (15 M + N - 1) / L + 2 in whole
+// k-steps of 16 - the same for every tile.  T_r is the A operand of v_mfma_f32_16x16x4_f32, the samples are the B operand, column =
+// period; the host packs the tiles back to back, each in the fragment order of the resample cut's T: [r][n >> 4][lane = (n & 3) << 4 |
+// o]{n >> 2 & 3}.  A workgroup of CV_THREADS threads serves `nper` consecutive periods of ONE item (ConvertWork::run counts such
+// runs): cv_nper() asks for CV_WG_SAMPLES outputs in whole column groups of 16 periods and cuts that to what CV_LDS_FLOATS hold.
+// LDS: the run's input span starts `shift` samples ahead of its first period - shift = lead .. lead + 3, lead = ceil(C / L), so that
+// the span starts on a quad of the item - and local sample j lies at float j + skew (j / PI) with skew = (4 - PI) mod 64: column p's
+// sample c = shift + base_r + n is at p (PI + skew) + c + skew (c / PI), and the 16 periods x 4 k of a B fragment (stride PI + skew =
+// 4 mod 64 between periods, 1 between k) fall into 64 different banks, except in the one k-step per PI samples that crosses a period's
+// end, where two of a lane group's four k move by skew.
+constexpr int CV_THREADS = 256;
+constexpr uint32_t CV_WG_SAMPLES = 2048;
+constexpr uint32_t CV_LDS_FLOATS = 16384;   // 64 KiB
+__host__ __device__ inline uint32_t cv_gcd(uint32_t a, uint32_t b) {
+    while (b) { const uint32_t t = a % b; a = b; b = t; }
+    return a;
+}
+__host__ __device__ inline uint32_t cv_P(uint32_t L) { return L * 16u / cv_gcd(L, 16u); }
+__host__ __device__ inline uint32_t cv_PI(uint32_t L, uint32_t M) { return 16u / cv_gcd(L, 16u) * M; }
+__host__ __device__ inline uint32_t cv_K(uint32_t ntaps, uint32_t L, uint32_t M) { return ((15u * M + ntaps - 1u) / L + 2u + 15u) & ~15u; }
+__host__ __device__ inline uint32_t cv_lead(uint32_t ntaps, uint32_t L) { return ((ntaps - 1u) / 2u + L - 1u) / L; }
+// first input of row-tile r, relative to its period's first input (floor division: negative for the first tiles)
+__host__ __device__ inline int32_t cv_base(uint32_t r, uint32_t ntaps, uint32_t L, uint32_t M) {
+    const int32_t v = (int32_t)(16u * r * M) - (int32_t)((ntaps - 1u) / 2u), l = (int32_t)L;
+    return v >= 0 ? v / l : -((-v + l - 1) / l);
+}
+// index into the taps of T_r[o][n], in [0, ntaps) or outside
+__host__ __device__ inline int64_t cv_tap(uint32_t r, uint32_t o, uint32_t n, uint32_t ntaps, uint32_t L, uint32_t M) {
+    return (int64_t)((16u * r + o) * M) - ((int64_t)cv_base(r, ntaps, L, M) + (int64_t)n) * (int64_t)L + (int64_t)((ntaps - 1u) / 2u);
+}
+// float index of T_r[o][n] in the packed operator of NT 16 K floats
+__host__ __device__ inline size_t cv_pack_index(uint32_t r, uint32_t o, uint32_t n, uint32_t K) {
+    return (size_t)r * 16u * K + (((size_t)(n >> 4) * 64u) + (((n & 3u) << 4) | o)) * 4u + ((n >> 2) & 3u);
+}
+__host__ __device__ inline uint32_t cv_skew(uint32_t PI) { return (4u - (PI & 63u)) & 63u; }
+// floats of a run of nper periods in LDS, at the largest shift
+__host__ __device__ inline uint32_t cv_lds_floats(uint32_t nper, uint32_t PI, uint32_t lead, int32_t bmax, uint32_t K) {
+    const uint32_t span = (uint32_t)((int32_t)(lead + 3u + (nper - 1u) * PI + K) + bmax + 3) & ~3u;
+    return span + cv_skew(PI) * (span / PI + 1u);
+}
+// periods of a workgroup's run; 0: not even one period fits
+__host__ __device__ inline uint32_t cv_nper(uint32_t P, uint32_t PI, uint32_t lead, int32_t bmax, uint32_t K) {
+    uint32_t nper = (((CV_WG_SAMPLES + P - 1u) / P) + 15u) & ~15u;
+    while (nper > 0 && cv_lds_floats(nper, PI, lead, bmax, K) > CV_LDS_FLOATS) nper = nper > 16u ? nper - 16u : nper - 1u;
+    return nper;
+}
+struct ConvertItem {
+    uint32_t quad_in;         // sample_offset / 4 | the channel mode << SCAN_MODE_SHIFT, as ScanItem::quad0
+    uint32_t s_in;            // input sample frames of the item: ANY count, the last quad may be partial
+    uint32_t s_out;           // floor(s_in L / M)
+    uint32_t quad_out;        // out_offset / 4; the item owns roundup4(s_out) floats from there
+};
+static_assert(sizeof(ConvertItem) == 16, "ConvertItem layout");
+struct ConvertWork {
+    uint32_t item;            // index into the item table
+    uint32_t run;             // the workgroup serves periods run * nper .. of it
+};
+static_assert(sizeof(ConvertWork) == 8, "ConvertWork layout");
+struct ConvertArgs {
+    const void *audio;        // the block, in its wire format
+    float *out;               // the converted block
+    const ConvertItem *items;
+    const ConvertWork *work;  // [nwork]: one entry per workgroup
+    const float *op;          // the packed operators: ntiles 16 K floats
+    uint32_t nwork;
+    uint32_t L, M;
+    uint32_t ntaps;
+    uint32_t P, PI;           // outputs and inputs of a period
+    uint32_t ntiles;          // P / 16
+    uint32_t ksteps;          // K / 16
+    uint32_t nper;            // periods of a workgroup's run
+    int32_t bmax;             // cv_base(ntiles - 1)
+    int32_t fmt;              // vad_frame_format
+    int32_t channels;         // 1 or 2
+};
+static_assert(sizeof(ConvertArgs) == 88, "ConvertArgs layout");
+
 // one finished piece of audio out of a scanned block (csrc/scan_render.hip: vadk_scan_render; vad_scan_render).  The kernel is
 // driven by the OUTPUT: the host sweeps the segments' output spans into regions - maximal runs of output quads covered by the same
 // none, one or two segments - and lists a workgroup per CUT_WG_QUADS quads of a region, so the kind of a workgroup is uniform.

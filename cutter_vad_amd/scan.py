@@ -149,6 +149,77 @@ def resample_taps(sample_rate: int, half_width: int = 16, beta: float = 8.0, cut
     return (h * (L / h.sum())).astype(np.float32)
 
 
+def convert_ratio(sample_rate: int, engine_rate: int = 16000) -> Tuple[int, int]:
+    """``(L, M)`` of ``Engine.convert`` for recordings at ``sample_rate``: ``engine_rate / sample_rate`` in lowest terms.  A rate the
+    conversion does not accept - outside 4000 .. 192000 Hz, the engine's own, a period ``lcm(L, 16)`` above 640 outputs or ``M`` above
+    640 - is a ``ConfigurationError``."""
+    import math
+    sr, R = int(sample_rate), int(engine_rate)
+    g = math.gcd(sr, R) if sr > 0 and R > 0 else 1
+    L, M = R // g, sr // g
+    if not (_ffi.VAD_CONVERT_MIN_RATE <= sr <= _ffi.VAD_CONVERT_MAX_RATE) or sr == R or R < 1 or \
+            L * 16 // math.gcd(L, 16) > _ffi.VAD_CONVERT_MAX_PERIOD or M > _ffi.VAD_CONVERT_MAX_PERIOD:
+        raise ConfigurationError("sample_rate", repr(sample_rate), f"convert: recordings at {sample_rate!r} Hz on a {R} Hz engine (L / M = {L} / {M}): "
+                                 f"accepted are {_ffi.VAD_CONVERT_MIN_RATE} .. {_ffi.VAD_CONVERT_MAX_RATE} Hz other than the engine's with lcm(L, 16) "
+                                 f"and M of at most {_ffi.VAD_CONVERT_MAX_PERIOD}")
+    return L, M
+
+
+def convert_taps(sample_rate: int, engine_rate: int = 16000, half_width: int = 16, beta: float = 8.0, cutoff: Optional[float] = None) -> np.ndarray:
+    """``resample_taps``' design for any rate ``Engine.convert`` accepts (44100, 22050, 11025, 32000, 12000, 96000 ..): with ``L / M =
+    engine_rate / sample_rate`` in lowest terms, a Kaiser-windowed sinc at rate ``L * sample_rate`` of ``2 * half_width * max(L, M) + 1``
+    taps, cutoff ``min(sample_rate, engine_rate) / 2`` Hz unless given, designed in float64, scaled to sum to ``L``, rounded once to
+    float32 - byte for byte ``resample_taps(sample_rate)`` at 8000, 24000 and 48000 Hz.  The conversion takes at most ``128 * L`` taps:
+    where ``M > 4 L`` (88200, 96000, 176400, 192000 Hz on a 16 kHz engine) the default ``half_width`` is too wide and a narrower one
+    must be named (``Engine.convert``'s own default picks the widest that fits)."""
+    L, M = convert_ratio(sample_rate, engine_rate)
+    sr, R = int(sample_rate), int(engine_rate)
+    half_width = int(half_width)
+    n = 2 * half_width * max(L, M) + 1
+    if half_width < 0 or n > _ffi.VAD_CONVERT_MAX_REACH * L:
+        raise ConfigurationError("half_width", repr(half_width), f"convert_taps: 2 * half_width * {max(L, M)} + 1 taps must be 1 .. "
+                                 f"{_ffi.VAD_CONVERT_MAX_REACH * L} (128 * L), got half_width = {half_width}; at most "
+                                 f"{(_ffi.VAD_CONVERT_MAX_REACH * L - 1) // (2 * max(L, M))} fits")
+    fc = min(sr, R) / 2.0 if cutoff is None else float(cutoff)
+    if not 0.0 < fc <= min(sr, R) / 2.0:
+        raise ConfigurationError("cutoff", repr(cutoff), f"convert_taps: 0 < cutoff <= {min(sr, R) / 2.0} Hz, got {cutoff!r}")
+    t = np.arange(n, dtype=np.float64) - (n - 1) // 2
+    h = np.sinc(2.0 * fc / (L * sr) * t) * np.kaiser(n, float(beta))
+    return (h * (L / h.sum())).astype(np.float32)
+
+
+def input_ranges(ranges, sample_rate: int, engine_rate: int, nsamples: int) -> List[Tuple]:
+    """Ranges of a CONVERTED recording (``scan_recordings(convert=...)``: samples at ``engine_rate``) mapped back to the input samples
+    they cover: ``(a, b, ...) -> (a M // L, min(ceil(b M / L), nsamples), ...)`` with ``L / M = engine_rate / sample_rate`` in lowest
+    terms; whatever follows the two positions (statistics, levels) is kept."""
+    import math
+    g = math.gcd(int(sample_rate), int(engine_rate))
+    L, M = int(engine_rate) // g, int(sample_rate) // g
+    return [(int(a) * M // L, min(-((-int(b) * M) // L), int(nsamples))) + tuple(rest) for a, b, *rest in ranges]
+
+
+def _convert_arg(who: str, engine, sample_rate, convert, split: bool = False, keep_channels: bool = False, resample=False):
+    """``convert=`` of the corpus functions -> None, or ``(input rate, True or taps)``: the recordings are converted once to the engine's
+    rate (``Engine.scan_segments(convert=...)``) and everything downstream treats them as recordings at the engine's own rate"""
+    if convert is None or convert is False:
+        return None
+    if not hasattr(engine, "convert") or not hasattr(engine, "scan_segments"):
+        raise ConfigurationError("convert", "given", f"{who}: convert= needs an engine with convert (the recordings are converted on the GPU "
+                                 f"ahead of the scan), {type(engine).__name__} has none")
+    if sample_rate is None or int(sample_rate) == int(engine.sample_rate):
+        raise ConfigurationError("convert", "given", f"{who}: convert= converts recordings at another rate than the engine's {engine.sample_rate} "
+                                 f"Hz: it needs sample_rate= (got {sample_rate!r})")
+    if keep_channels:
+        raise ConfigurationError("convert", "given", f"{who}: convert= with keep_channels=True: a converted recording is mono, two-channel "
+                                 "converted output is not supported")
+    if resample is not False and resample is not None:
+        raise ConfigurationError("convert", "given", f"{who}: convert= with resample=: a converted recording is at the engine's rate already")
+    if split:
+        raise ConfigurationError("convert", "given", f"{who}: convert= with channel='split': a converted recording is mono - scan 'mix', 0 or 1")
+    convert_ratio(int(sample_rate), int(engine.sample_rate))      # (a rate the conversion refuses: ConfigurationError)
+    return int(sample_rate), convert
+
+
 def _keep_channels_check(who: str, split: bool) -> None:
     if split:
         raise ConfigurationError("keep_channels", "True", f"{who}: keep_channels=True delivers both channels of a recording in one payload; "
@@ -208,7 +279,7 @@ def _append_levels(engine, ranges, chans, frame: int, hop: int, denoise) -> List
 
 
 def _scan_ranges(engine, slots, recordings, per: int, frame: int, hop: int, law, denoise, channel, stats: bool = False,
-                 rate: Optional[int] = None, open_end: bool = False, refine=None, levels: bool = False) -> List[List[List]]:
+                 rate: Optional[int] = None, open_end: bool = False, refine=None, levels: bool = False, convert=None) -> List[List[List]]:
     """One scan of ``recordings`` (all 1-D or all two-channel) on ``slots`` -> per recording, per channel scanned of it (``per``),
     the finished segments ``(start_sample, end_sample)`` - with ``stats``: ``(start_sample, end_sample, mean_prob, max_prob)``.
     An engine with ``scan_segments`` builds the table on the GPU and copies back that alone; any other goes through the per-frame
@@ -216,15 +287,19 @@ def _scan_ranges(engine, slots, recordings, per: int, frame: int, hop: int, law,
     ``hop`` are then a chunk and a hop in input samples; ``vad_scan_rate_segments`` builds the table).  ``open_end``: the segment
     still open at an item's last frame (``Engine.scan_tails``) is its last range.  ``refine``: the table - and, with
     ``open_end``, the tails as each item's last record - goes through ``Engine.refine`` on the GPU; the statistics are the refined records'.
-    ``levels``: every range listed gets ``(rms, peak, clipped)`` appended (``Engine.levels`` on the ranges as listed)."""
+    ``levels``: every range listed gets ``(rms, peak, clipped)`` appended (``Engine.levels`` on the ranges as listed).
+    ``convert`` (``_convert_arg``): the recordings are converted to the engine's rate ahead of the scan; ``rate`` is None then, and
+    ``frame``, ``hop`` and the ranges count samples of the converted signal."""
     if levels:
         _need_levels(engine, "scan_recordings")
         two = recordings[0].ndim == 2
         with engine.scan_session():
-            ranges = _scan_ranges(engine, slots, recordings, per, frame, hop, law, denoise, channel, stats, rate, open_end, refine)
-            return _append_levels(engine, ranges, (0, 1) if per == 2 else (channel if two else 0,), frame, hop, denoise)
+            ranges = _scan_ranges(engine, slots, recordings, per, frame, hop, law, denoise, channel, stats, rate, open_end, refine, convert=convert)
+            return _append_levels(engine, ranges, (0, 1) if per == 2 else (channel if two and convert is None else 0,), frame, hop, denoise)
     sl = np.asarray(slots).reshape(len(recordings), per) if per == 2 else slots
     kw = {} if rate is None else {"sample_rate": rate}
+    if convert is not None:
+        kw = {"sample_rate": convert[0], "convert": convert[1]}
     if refine is not None:
         _need_refine(engine, "scan_recordings")
         if open_end:
@@ -258,7 +333,7 @@ def _scan_ranges(engine, slots, recordings, per: int, frame: int, hop: int, law,
 
 def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
                     law: Optional[str] = None, channel="mix", stats: bool = False, sample_rate: Optional[int] = None,
-                    open_end: bool = False, refine: Optional[SegmentRefine] = None, levels: bool = False) -> List[List[Tuple]]:
+                    open_end: bool = False, refine: Optional[SegmentRefine] = None, levels: bool = False, convert=None) -> List[List[Tuple]]:
     """Speech segments of every recording, one launch sequence for the lot: opens one stream per recording with the config's
     thresholds, scans (frames of ``engine.frame_samples`` at ``hop``, default half a frame as ``VADWrapper`` frames a chunk;
     the config's denoise gate), closes the streams -> per recording ``[(start_sample, end_sample), ...]``.
@@ -282,7 +357,13 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
     ``stats``' two values when both are given: the root mean square, the largest magnitude and the number of samples at or above
     0.95 (``AudioUtils.calculate_rms`` / ``detect_clipping``) of the range's samples as the model heard them - decoded, mixed and
     gated; input-rate samples, not gated, under ``sample_rate`` - reduced on the GPU from the block the scan left there
-    (``Engine.levels``; an engine object without it: ``ConfigurationError``)."""
+    (``Engine.levels``; an engine object without it: ``ConfigurationError``).
+    ``convert``: ``True`` or a taps array (``Engine.convert``'s ``taps``; ``True``: the default design of ``convert_taps``) - the
+    recordings are at ANY rate ``Engine.convert`` accepts (44100, 22050, 11025, 32000, 12000, 96000 .. - and 8000, 24000, 48000 too): each
+    is converted ONCE on the GPU to a continuous signal at the engine's rate (``Engine.scan_segments(convert=...)``) and scanned as a
+    recording at that rate: ``hop`` defaults to half a frame and the ranges count samples of the CONVERTED signal, at the engine's rate
+    (``input_ranges`` maps them back to input samples).  It needs a ``sample_rate`` other than the engine's; ``channel="split"``, or an
+    engine object without ``convert``: ``ConfigurationError``.  Without it ``sample_rate`` means what it meant."""
     from .pool import default_pool, resolve_model_path
     split = isinstance(channel, str) and channel == "split"
     # checked here, not by the scan: a corpus of 1-D recordings alone never shows the value to Engine.scan
@@ -302,6 +383,9 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
         raise ConfigurationError(f"scan_recordings frames at the model's frame size: buffer_size = {cfg.buffer_size}, "
                                  f"the engine's frames have {frame} samples")
     rate = None if sample_rate is None or int(sample_rate) == int(engine.sample_rate) else int(sample_rate)
+    conv = _convert_arg("scan_recordings", engine, sample_rate, convert, split)
+    if conv is not None:
+        rate = None                                  # downstream the recordings are at the engine's own rate
     if rate is not None:
         if rate not in (8000, 16000, 24000, 48000):
             raise ConfigurationError("sample_rate", repr(sample_rate), f"scan_recordings: recordings at 8000, 16000, 24000 or 48000 Hz, got {sample_rate!r}")
@@ -321,7 +405,7 @@ def scan_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig
             engine.set_thresholds_many(slots, (cfg.vad_start_probability, cfg.vad_end_probability, cfg.voice_start_ratio,
                                                cfg.voice_end_ratio, cfg.voice_start_frame_count, cfg.voice_end_frame_count))
             ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, 0.01 if cfg.enable_denoising else None,
-                                  channel, stats, rate, open_end, refine, levels)
+                                  channel, stats, rate, open_end, refine, levels, convert=conv)
         finally:
             for s in slots:
                 engine.close_stream(int(s))
@@ -336,7 +420,7 @@ def _thresholds_of(cfg: VADConfig) -> Tuple:
 
 
 def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConfig], engine=None, hop: Optional[int] = None,
-                     law: Optional[str] = None, channel="mix", stats: bool = False, sample_rate: Optional[int] = None,
+                     law: Optional[str] = None, channel="mix", stats: bool = False, sample_rate: Optional[int] = None, convert=None,
                      open_end: bool = False, refine: Optional[SegmentRefine] = None, levels: bool = False) -> List[List]:
     """``scan_recordings`` under several configs for the price of one scan: ``sweep_recordings(recs, cfgs, **kw)[j] ==
     scan_recordings(recs, cfgs[j], **kw)``.  The model runs once per kind of recording (1-D, 2-D), with the first config's
@@ -346,7 +430,8 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
     ``buffer_size``, ``enable_denoising`` and ``model_path`` - or ``ConfigurationError`` names the field.  An engine object without
     ``resegment`` is served config by config.  ``open_end`` as in ``scan_recordings``: each config's open segments come from the
     same replay (``Engine.resegment_tails``).  ``refine`` as there too: each config's replayed table, with its tails, goes through
-    ``Engine.refine``.  ``levels`` as there: one ``Engine.levels`` call per config on that config's ranges."""
+    ``Engine.refine``.  ``levels`` as there: one ``Engine.levels`` call per config on that config's ranges.  ``convert`` as there:
+    the recordings are converted once (``Engine.scan_segments(convert=...)``) and every config replays the converted scan."""
     from .pool import default_pool, resolve_model_path
     configs = list(configs)
     if not configs:
@@ -362,7 +447,7 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
         engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
     if not hasattr(engine, "resegment") or not hasattr(engine, "scan_segments"):
         return [scan_recordings(recordings, c, engine=engine, hop=hop, law=law, channel=channel, stats=stats, sample_rate=sample_rate,
-                                open_end=open_end, refine=refine, levels=levels) for c in configs]
+                                open_end=open_end, refine=refine, levels=levels, convert=convert) for c in configs]
     if open_end:
         _need_tails(engine, "sweep_recordings", "resegment_tails")
     if refine is not None:
@@ -377,6 +462,9 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
         raise ConfigurationError("buffer_size", repr(cfg.buffer_size), f"sweep_recordings frames at the model's frame size: buffer_size = "
                                  f"{cfg.buffer_size}, the engine's frames have {frame} samples")
     rate = None if sample_rate is None or int(sample_rate) == int(engine.sample_rate) else int(sample_rate)
+    conv = _convert_arg("sweep_recordings", engine, sample_rate, convert, split)
+    if conv is not None:
+        rate = None                                  # (convert= as in scan_recordings)
     if rate is not None:
         if rate not in (8000, 16000, 24000, 48000):
             raise ConfigurationError("sample_rate", repr(sample_rate), f"sweep_recordings: recordings at 8000, 16000, 24000 or 48000 Hz, got {sample_rate!r}")
@@ -385,6 +473,8 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
     recordings = [np.asarray(r) for r in recordings]
     out: List[List] = [[None] * len(recordings) for _ in configs]
     kw = {} if rate is None else {"sample_rate": rate}
+    if conv is not None:
+        kw = {"sample_rate": conv[0], "convert": conv[1]}
     for two in (False, True):
         idx = [i for i, r in enumerate(recordings) if (r.ndim == 2) == two]
         if not idx:
@@ -407,7 +497,7 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
                     tables = [_with_tails(t, tl) for t, tl in zip(tables, tails)]
                 listed = [_table_ranges(t, len(idx), per, frame, hop, stats) for t in tables]
                 if levels:
-                    chans = (0, 1) if per == 2 else (channel if two else 0,)
+                    chans = (0, 1) if per == 2 else (channel if two and conv is None else 0,)
                     listed = [_append_levels(engine, r, chans, frame, hop, 0.01 if cfg.enable_denoising else None) for r in listed]
         finally:
             for s in slots:
@@ -421,7 +511,7 @@ def sweep_recordings(recordings: Sequence[np.ndarray], configs: Sequence[VADConf
 def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
                    law: Optional[str] = None, channel="mix", layout: str = "frames", wav: bool = True,
                    sample_rate: Optional[int] = None, open_end: bool = False, refine: Optional[SegmentRefine] = None,
-                   normalize: Optional[float] = None, keep_channels: bool = False, resample=False) -> List:
+                   normalize: Optional[float] = None, keep_channels: bool = False, resample=False, convert=None) -> List:
     """``scan_recordings`` with each finished segment's audio: per recording ``[(start_sample, end_sample, payload), ...]`` (per
     channel for ``"split"``, as there).  ``payload`` is what ``VADWrapper``'s ``voice_end`` callback delivers for the same
     recording - the segment's frames back to back, decoded, mixed and gated as the model read them, as 16-bit PCM behind the WAV
@@ -453,7 +543,11 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
     16 kHz PCM (``Engine.resample_cut_samples`` samples) behind a header of the engine's rate.  ``normalize`` then divides by the
     INPUT-rate peak of ``Engine.levels``: the peak of the resampled signal can differ slightly (the filter overshoots between
     samples), and PCM16 saturates where it exceeds full scale.  With ``keep_channels=True``: ``ConfigurationError`` (two-channel
-    resampled output is not built)."""
+    resampled output is not built).
+    ``convert`` as in ``scan_recordings``: the recordings, at any rate ``Engine.convert`` accepts, are converted once and are recordings
+    at the engine's rate from there on - ranges, ``hop`` and both layouts (``"frames"`` too) count converted samples, the audio is cut
+    from the converted signal and the WAV header carries ``config.output_wav_sample_rate``.  With ``keep_channels=True`` or
+    ``resample=``: ``ConfigurationError``."""
     from .pool import default_pool, resolve_model_path
     from .utils.wav_writer import WAVWriter
     split = isinstance(channel, str) and channel == "split"
@@ -479,6 +573,9 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
         raise ConfigurationError(f"cut_recordings frames at the model's frame size: buffer_size = {cfg.buffer_size}, "
                                  f"the engine's frames have {frame} samples")
     rate = None if sample_rate is None or int(sample_rate) == int(engine.sample_rate) else int(sample_rate)
+    conv = _convert_arg("cut_recordings", engine, sample_rate, convert, split, keep_channels, resample)
+    if conv is not None:
+        rate = None                                  # downstream the recordings are at the engine's own rate
     resampled = resample is not False and resample is not None
     if resampled:
         if rate is None or layout != "range":
@@ -510,7 +607,7 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
         if not idx:
             continue
         per = 2 if two and split else 1
-        chans = (0, 1) if per == 2 else (channel if two else 0,)
+        chans = (0, 1) if per == 2 else (channel if two and conv is None else 0,)
         slots = engine.open_streams(len(idx) * per)
         try:
             engine.set_thresholds_many(slots, (cfg.vad_start_probability, cfg.vad_end_probability, cfg.voice_start_ratio,
@@ -518,7 +615,7 @@ def cut_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig]
             with engine.scan_session():
                 # (recording, channel) -> its sample ranges; the cut's table lists them in that order
                 ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, denoise, channel, rate=rate,
-                                      open_end=open_end, refine=refine)
+                                      open_end=open_end, refine=refine, convert=conv)
                 table = _cut_table(engine, ranges, chans, frame, hop)
                 if two and keep_channels:
                     table = [sg[:3] for sg in table]
@@ -573,7 +670,7 @@ def _join_places(counts: Sequence[int], nramp: int, gap: int) -> List[int]:
 def render_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConfig] = None, engine=None, hop: Optional[int] = None,
                       law: Optional[str] = None, channel="mix", sample_rate: Optional[int] = None, open_end: bool = False,
                       refine: Optional[SegmentRefine] = None, normalize: Optional[float] = None, mode: str = "join", fade_ms: float = 10.0,
-                      gap_ms: float = 0.0, shape: str = "linear", wav: bool = True, keep_channels: bool = False) -> List:
+                      gap_ms: float = 0.0, shape: str = "linear", wav: bool = True, keep_channels: bool = False, convert=None) -> List:
     """One finished piece of audio per recording: per recording ``(payload, timeline)`` (per channel for ``"split"``, as in
     ``scan_recordings``).  ``mode="join"`` is silence removal: the recording's speech segments (their sample ranges, as
     ``cut_recordings(layout="range")`` cuts them) back to back, each faded in and out over ``fade_ms`` by a ``fade_ramp`` of
@@ -590,7 +687,10 @@ def render_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConf
     never gated.  An engine object without ``render``: ``ConfigurationError``.
     ``keep_channels`` as in ``cut_recordings``: the piece of a two-channel recording keeps both channels (``Engine.render_stereo``;
     an engine object without it: ``ConfigurationError``) - a ``[k, 2]`` int16 array or a WAV with a two-channel header; places,
-    lengths and the timeline count sample frames and are what they are without it; gain and ramp are the same for both channels."""
+    lengths and the timeline count sample frames and are what they are without it; gain and ramp are the same for both channels.
+    ``convert`` as in ``cut_recordings``: the piece is made of the converted signal, at the engine's rate - places, lengths, the
+    timeline and ``"mask"``'s length (``Engine.convert_samples`` of the recording's) count converted samples, and the header carries
+    ``config.output_wav_sample_rate``."""
     from .pool import default_pool, resolve_model_path
     from .utils.wav_writer import WAVWriter
     who = "render_recordings"
@@ -620,6 +720,9 @@ def render_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConf
         raise ConfigurationError(f"{who} frames at the model's frame size: buffer_size = {cfg.buffer_size}, "
                                  f"the engine's frames have {frame} samples")
     rate = None if sample_rate is None or int(sample_rate) == int(engine.sample_rate) else int(sample_rate)
+    conv = _convert_arg(who, engine, sample_rate, convert, split, keep_channels)
+    if conv is not None:
+        rate = None                                  # downstream the recordings are at the engine's own rate
     if rate is not None:
         if rate not in (8000, 16000, 24000, 48000):
             raise ConfigurationError("sample_rate", repr(sample_rate), f"{who}: recordings at 8000, 16000, 24000 or 48000 Hz, got {sample_rate!r}")
@@ -633,7 +736,9 @@ def render_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConf
     recordings = [np.asarray(r) for r in recordings]
     if not recordings:
         return []
-    writer = WAVWriter(int(sample_rate) if sample_rate is not None else cfg.output_wav_sample_rate, 16, 1)
+    writer = WAVWriter(int(sample_rate) if sample_rate is not None and conv is None else cfg.output_wav_sample_rate, 16, 1)
+    # a recording's own length, as "mask" lays it out: of the converted signal under convert=
+    own = (lambda r: int(r.shape[0])) if conv is None else (lambda r: max(engine.convert_samples(int(r.shape[0]), conv[0]), 0))
     writer2 = WAVWriter(writer.sample_rate, 16, 2) if keep_channels else None
     denoise = 0.01 if cfg.enable_denoising else None
     out: List = [None] * len(recordings)
@@ -642,14 +747,14 @@ def render_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConf
         if not idx:
             continue
         per = 2 if two and split else 1
-        chans = (0, 1) if per == 2 else (channel if two else 0,)
+        chans = (0, 1) if per == 2 else (channel if two and conv is None else 0,)
         slots = engine.open_streams(len(idx) * per)
         try:
             engine.set_thresholds_many(slots, (cfg.vad_start_probability, cfg.vad_end_probability, cfg.voice_start_ratio,
                                                cfg.voice_end_ratio, cfg.voice_start_frame_count, cfg.voice_end_frame_count))
             with engine.scan_session():
                 ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, denoise, channel, rate=rate,
-                                      open_end=open_end, refine=refine)
+                                      open_end=open_end, refine=refine, convert=conv)
                 ranges = [[[(a, b) for a, b, *_ in rg] for rg in rc] for rc in ranges]
                 if mode == "mask":
                     # touching or overlapping ranges of one piece (neighbours from a split, small hops) become one, on the same hop grid
@@ -673,7 +778,7 @@ def render_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConf
                     for rg in rc:
                         counts = [b - a for a, b in rg]
                         if mode == "mask":
-                            at, size = [a for a, _ in rg], (int(recordings[idx[k]].shape[0]) + 3) // 4 * 4
+                            at, size = [a for a, _ in rg], (own(recordings[idx[k]]) + 3) // 4 * 4
                         else:
                             at = _join_places(counts, nramp, gap)
                             size = at[-1] + counts[-1] if counts else 0
@@ -702,7 +807,7 @@ def render_recordings(recordings: Sequence[np.ndarray], config: Optional[VADConf
                 lo, size, at, counts = lengths[j]
                 j += 1
                 if mode == "mask":
-                    size = int(recordings[i].shape[0])      # the padding to a multiple of 4 is trimmed
+                    size = own(recordings[i])               # the padding to a multiple of 4 is trimmed
                 pcm = data[lo:lo + size]
                 timeline = [(p, a, s) for p, (a, _), s in zip(at, rg, counts)]
                 if wav:
@@ -796,7 +901,7 @@ def _need_mel(engine, who: str) -> None:
 
 def features_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, config: Optional[VADConfig] = None, engine=None,
                         hop: Optional[int] = None, law: Optional[str] = None, channel="mix", open_end: bool = False,
-                        refine: Optional[SegmentRefine] = None, sample_rate: Optional[int] = None, taps=None) -> List:
+                        refine: Optional[SegmentRefine] = None, sample_rate: Optional[int] = None, taps=None, convert=None) -> List:
     """``scan_recordings`` with each finished segment's log-mel frames: per recording ``[(start_sample, end_sample,
     features [M, n_mels] float32), ...]`` (per channel for ``"split"``, as there).  The features are those of the samples
     ``cut_recordings(layout="range")`` cuts - decoded, mixed and gated as the model read them - computed on the GPU from the block
@@ -807,7 +912,10 @@ def features_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, config:
     ``sample_rate``: the recordings are at 8000, 24000 or 48000 Hz - the scan is the rate scan, ``hop`` and the ranges count
     INPUT-rate samples, and the features are those of each segment's 16 kHz signal (``Engine.mel(sample_rate=..., taps=...)``:
     ``Engine.resample_cut``'s samples, never gated), so ``spec.sample_rate`` is still the engine's.  ``taps`` as in
-    ``Engine.resample_cut``.  An engine object without ``resample_cut``: ``ConfigurationError``."""
+    ``Engine.resample_cut``.  An engine object without ``resample_cut``: ``ConfigurationError``.
+    ``convert`` as in ``scan_recordings``: recordings at any rate ``Engine.convert`` accepts, converted once; the ranges count converted
+    samples and the features are those of the converted signal, gated as the model read it (``Engine.mel(audio=None)``; ``taps`` is
+    not used)."""
     from .pool import default_pool, resolve_model_path
     who = "features_recordings"
     split = isinstance(channel, str) and channel == "split"
@@ -829,6 +937,9 @@ def features_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, config:
         raise ConfigurationError(f"{who} frames at the model's frame size: buffer_size = {cfg.buffer_size}, the engine's frames have "
                                  f"{frame} samples")
     rate = None if sample_rate is None or int(sample_rate) == int(engine.sample_rate) else int(sample_rate)
+    conv = _convert_arg(who, engine, sample_rate, convert, split)
+    if conv is not None:
+        rate = None                                  # downstream the recordings are at the engine's own rate
     mel_kw = {}
     if rate is not None:
         if rate not in (8000, 24000, 48000):
@@ -848,13 +959,13 @@ def features_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, config:
         if not idx:
             continue
         per = 2 if two and split else 1
-        chans = (0, 1) if per == 2 else (channel if two else 0,)
+        chans = (0, 1) if per == 2 else (channel if two and conv is None else 0,)
         slots = engine.open_streams(len(idx) * per)
         try:
             engine.set_thresholds_many(slots, _thresholds_of(cfg))
             with engine.scan_session():
                 ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, denoise, channel, rate=rate,
-                                      open_end=open_end, refine=refine)
+                                      open_end=open_end, refine=refine, convert=conv)
                 table = _cut_table(engine, ranges, chans, frame, hop)
                 if table:
                     data, start = engine.mel(table, arrays, hop=hop, denoise=denoise, **mel_kw)
@@ -975,7 +1086,7 @@ def _need_batch(engine, who: str) -> None:
 
 def batch_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, batch: FeatureBatch, config: Optional[VADConfig] = None, engine=None,
                      hop: Optional[int] = None, law: Optional[str] = None, channel="mix", open_end: bool = False,
-                     refine: Optional[SegmentRefine] = None, sample_rate: Optional[int] = None, taps=None):
+                     refine: Optional[SegmentRefine] = None, sample_rate: Optional[int] = None, taps=None, convert=None):
     """``features_recordings`` as the tensor a model takes: the log-mel features of every finished segment of every recording,
     windowed, normalised, padded, laid out and converted as ``batch`` says -> ``(array, index)``: ``array`` [B, C, T] or [B, T, C]
     (``Engine.mel_batch``), ``index`` one ``(recording, channel, start_sample, end_sample, first_frame, nframes)`` per window - the
@@ -983,7 +1094,7 @@ def batch_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, batch: Fea
     ``Engine.mel_keep``, at most one ``Engine.mel_stats`` and one ``Engine.mel_batch`` under ``Engine.scan_session()``: the features
     never leave the GPU, only the statistics and the batch cross the link.  The other arguments as in ``features_recordings``.  A
     corpus of 1-D and 2-D recordings is a ``ConfigurationError``: call it once per kind.  So is an engine object without
-    ``mel_batch``.  No segment anywhere: an array with B = 0."""
+    ``mel_batch``.  No segment anywhere: an array with B = 0.  ``convert`` as in ``features_recordings``."""
     from .pool import default_pool, resolve_model_path
     who = "batch_recordings"
     batch.check()
@@ -1007,6 +1118,9 @@ def batch_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, batch: Fea
         raise ConfigurationError(f"{who} frames at the model's frame size: buffer_size = {cfg.buffer_size}, the engine's frames have "
                                  f"{frame} samples")
     rate = None if sample_rate is None or int(sample_rate) == int(engine.sample_rate) else int(sample_rate)
+    conv = _convert_arg(who, engine, sample_rate, convert, split)
+    if conv is not None:
+        rate = None                                  # downstream the recordings are at the engine's own rate
     mel_kw = {}
     if rate is not None:
         if rate not in (8000, 24000, 48000):
@@ -1031,13 +1145,14 @@ def batch_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, batch: Fea
     two = kinds.pop()
     denoise = 0.01 if cfg.enable_denoising else None
     per = 2 if two and split else 1
-    chans = (0, 1) if per == 2 else (channel if two else 0,)
+    chans = (0, 1) if per == 2 else (channel if two and conv is None else 0,)
     slots = engine.open_streams(len(recordings) * per)
     out = None
     try:
         engine.set_thresholds_many(slots, _thresholds_of(cfg))
         with engine.scan_session():
-            ranges = _scan_ranges(engine, slots, recordings, per, frame, hop, law, denoise, channel, rate=rate, open_end=open_end, refine=refine)
+            ranges = _scan_ranges(engine, slots, recordings, per, frame, hop, law, denoise, channel, rate=rate, open_end=open_end, refine=refine,
+                                  convert=conv)
             table = _cut_table(engine, ranges, chans, frame, hop)
             if table:
                 start = engine.mel_keep(table, arrays, hop=hop, denoise=denoise, **mel_kw)

@@ -888,6 +888,82 @@ VAD_API int vad_scan_rate_mel_device(vad_engine *e, const vad_cut_item *items, i
                                      void *stream);
 
 /*
+ * Recordings at 44.1 kHz and any other rational rate: a whole recording converted ONCE to the engine's rate, into an engine-owned
+ * mono float32 block.  That block is an ordinary resident block at the engine's own rate: vad_scan_cut(audio = NULL), the levels,
+ * renders, mel features and batches, vad_scan_resegment, the tails and vad_scan_refine work behind it unchanged, and none of them
+ * needs a rate variant.  (The chunk route of vad_scan_rate cannot be stretched: a 512-sample frame is 1411.2 samples at 44.1 kHz.)
+ *
+ * THE RULE.  For item i (vad_scan_ch_item: slot, sample_offset - a multiple of 4 -, nsamples = S_in - ANY count -, channel) of a
+ * block at sr_in, in any wire format, with 1 or 2 interleaved channels:
+ *   - R is the engine's rate (vad_info.sample_rate), g = gcd(R, sr_in), L = R / g, M = sr_in / g.
+ *   - Accepted: VAD_CONVERT_MIN_RATE <= sr_in <= VAD_CONVERT_MAX_RATE, sr_in != R, a period P = lcm(L, 16) of at most
+ *     VAD_CONVERT_MAX_PERIOD outputs and M <= VAD_CONVERT_MAX_PERIOD: 8, 11.025, 12, 22.05, 24, 32, 44.1, 48, 88.2, 96, 176.4 and
+ *     192 kHz on a 16 kHz engine, among others.  Anything else: VAD_ERR_UNSUPPORTED with a message that names L, M and the limits;
+ *     sr_in == R is refused too, there is nothing to convert.
+ *   - x[k], k = 0 .. S_in - 1, are the float32 values the scans' loader hears BEFORE THE GATE: decoded (s / 32767 or s / 32768,
+ *     G.711) and channel-selected, (L + R) * 0.5f for VAD_SCAN_MIX.  Never gated: a scan gates the converted signal.
+ *   - x[k] = 0 outside [0, S_in), EVEN WHERE THE BLOCK HOLDS AUDIO THERE.  The result depends on the item alone.
+ *   - taps is a host float32 array h[0 .. N - 1], the prototype low-pass at rate L * sr_in: N odd, 1 <= N <= VAD_CONVERT_MAX_REACH * L,
+ *     every entry finite; C = (N - 1) / 2.
+ *   - S_out = floor(S_in * L / M): vad_convert_samples(e, nsamples, sr_in); -1 for a null engine, a negative or 2^31-or-larger count
+ *     and a rate that is not accepted.
+ *   - For m = 0 .. S_out - 1:  y[m] = sum over k of x[k] * h[m * M - k * L + C], over the k in [0, S_in) whose tap index lies in
+ *     [0, N).  All arithmetic is float32; the order of the sum is the kernel's own and fixed: two calls give the same bytes.
+ *   - With u = 2^-24 and D[m] = sum over k of |x[k]| |h[.]|:  |y - y_exact| <= (ceil(N / L) + 4) u D - vad_scan_resample_cut's bound,
+ *     which holds in any order of summation.  Where every product and partial sum is an integer multiple of a power of two below
+ *     2^24 in magnitude the result is exact.
+ *   - Layout: item i sits at out_offset[i] = sum over j < i of roundup4(S_out_j); the 0 .. 3 samples between two items are written
+ *     as +0.0, so EVERY sample of the converted block of out_offset[n] samples is written.  A block of 2 GiB of float32 or more
+ *     (2^29 samples) is refused.
+ *   - Non-finite float32 input.  The kernel computes output m from the K inputs that start at floor(m / P) * P * M / L + base_r,
+ *     r = (m mod P) / 16, base_r = floor((16 r M - C) / L), K = (15 M + N - 1) / L + 2 rounded up to a multiple of 16: a window that
+ *     holds the taps of the 16 outputs of m's row-tile, padded with structural zeros of the operator.  Every output whose TAP
+ *     window holds the bad sample is non-finite (which NaN is not specified); an output m with |k - m M / L| >= K for the bad sample
+ *     k is byte for byte what it is with x[k] = 0; an output in between is either (0 * NaN).
+ *
+ * vad_convert: the conversion alone, host to host: the block is uploaded, converted, and out[0 .. out_offset[n]) is copied back;
+ * out_offset (host, [n + 1], or NULL) receives the layout.  Slots are not read, no stream is touched, no model runs and the resident
+ * block stays what it was; works on every engine, Silero V4 and VAD_ENGINE_SHARED_GPU included.  Waits for earlier *_device launches.
+ * vad_convert_device: d_audio -> d_out (16-byte aligned) on `stream` (NULL = the engine's own), returns after enqueueing; d_audio is
+ * aligned as vad_scan_channels_device wants it (4 bytes, 8 for two channels); taps and out_offset are HOST arrays.
+ *   Refusals, each with a message under the function's name and nothing written: the rate (above); a null taps, ntaps even or
+ * outside 1 .. VAD_CONVERT_MAX_REACH * L, a tap that is NaN or infinite (the message names the lowest index); every block and item
+ * refusal of vad_scan_channels, in its words (counts, format, channels, 2 GiB of input, an offset that is not a multiple of 4, an
+ * item that leaves the block, a channel out of range, a non-zero reserved - not hop, slots or max_streams, which no conversion
+ * reads); a converted block of 2 GiB or more; out_samples < out_offset[n]; a null audio or out when there is anything to convert; a
+ * misaligned device pointer.  n == 0: VAD_OK.
+ *
+ * vad_scan_convert_segments: upload the block into a staging buffer, convert it into the engine's audio buffer, and run exactly what
+ * vad_scan_segments runs - the model launches, the tail snapshot, the extraction - on that buffer as a mono VAD_FMT_F32 block at the
+ * engine's rate, with the items {slot, out_offset[i], S_out_i, channel 0}; hop and every position downstream count samples at the
+ * ENGINE's rate.  BY DEFINITION the call is byte-equal to vad_convert followed by vad_scan_segments on the float32 block it
+ * returned: the table, the resident per-frame results (vad_scan_resegment, vad_scan_tails) and the resident block
+ * (vad_scan_cut(audio = NULL, audio_samples = out_offset[n], channels = 1, VAD_FMT_F32)).  Refusals: those of vad_convert for rate,
+ * taps, block and items, then vad_scan_segments's own (hop, max_streams, slots, seg_cap, null buffers; Silero V4 and
+ * VAD_ENGINE_SHARED_GPU engines: VAD_ERR_UNSUPPORTED - only the conversion itself runs there).
+ *   A workgroup of the kernel serves a run of whole periods of one item - VAD_CONVERT_WG_SAMPLES outputs or more where the item has
+ * them and local memory holds their inputs -, loads the run's input span once and never issues a load outside the item's own samples.
+ *   vad_scan_rate*, vad_scan_resample_cut and every other entry point accept the rates they accepted before.
+ *   VAD_ABI_VERSION is unchanged: the presence of vad_convert is how a caller detects the feature.
+ */
+#define VAD_CONVERT_MAX_REACH 128
+#define VAD_CONVERT_MIN_RATE 4000
+#define VAD_CONVERT_MAX_RATE 192000
+#define VAD_CONVERT_MAX_PERIOD 640
+#define VAD_CONVERT_WG_SAMPLES 2048
+VAD_API int64_t vad_convert_samples(const vad_engine *e, int64_t nsamples, int32_t sr_in);
+VAD_API int vad_convert(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
+                        int frame_fmt, int32_t sr_in, const float *taps /*host [ntaps]*/, int32_t ntaps, float *out, int64_t out_samples,
+                        int64_t *out_offset /*[n + 1] host or NULL*/);
+VAD_API int vad_convert_device(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *d_audio, int64_t audio_samples,
+                               int32_t channels, int frame_fmt, int32_t sr_in, const float *taps /*host [ntaps]*/, int32_t ntaps,
+                               float *d_out, int64_t out_samples, int64_t *out_offset /*[n + 1] host or NULL*/, void *stream);
+VAD_API int vad_scan_convert_segments(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples,
+                                      int32_t channels, int frame_fmt, int32_t sr_in, const float *taps /*host [ntaps]*/, int32_t ntaps,
+                                      int32_t hop, float denoise_thresh, vad_segment *segs_out, int64_t seg_cap, int64_t *nsegs_out,
+                                      int64_t *out_offset /*[n + 1] or NULL*/);
+
+/*
  * Model-ready feature batches: what an ASR front end, a speaker model or a classifier takes is not the packed matrix of
  * vad_scan_mel but normalised, padded windows [B][n_mels][T] in its own number format.  Three steps, all on the GPU:
  *

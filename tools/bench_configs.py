@@ -1708,6 +1708,143 @@ def scan_resample_cut():
     return row
 
 
+def scan_convert():
+    """Recordings at 44.1 kHz and any rational rate, converted once on the GPU: VAD_SCAN_BENCH_N (default 1 024) int16
+    recordings of 30 s - the golden clip, stretched by index to the rate - in calls of 256 recordings (a call's block and its converted
+    block stay under 2 GiB).  Three measurements, one warm-up pass and three timed passes each, medians:
+      (a) Engine.scan_segments(sample_rate=44100, convert=True) against the host route - scipy.signal.resample_poly(x, 160, 441,
+          window=taps / 160) of every recording on 16 threads (AudioUtils.resample_audio where scipy is missing), then Engine.scan_segments
+          of the float32 arrays at 16 kHz;
+      (b) vad_convert_device alone on one call's block in device memory, under HIP events, as bytes read and written per second;
+      (c) at 48 kHz, the converted scan against the chunk route, Engine.scan_segments(sample_rate=48000) (vad_scan_rate_segments),
+          hop = half a frame of each.
+    The result goes to profiles/scan_convert.json."""
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    import numpy as np
+    from cutter_vad_amd.scan import convert_taps
+    N = int(os.environ.get("VAD_SCAN_BENCH_N", "1024"))
+    per_call, seconds = 256, 30
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    pcm = np.load(os.path.join(root, "tests", "golden", "speech16k_i16.npz"))["pcm"].astype(np.int16)
+    one16 = np.resize(pcm, seconds * 16000)
+    at_rate = lambda sr: np.ascontiguousarray(one16[(np.arange(seconds * sr, dtype=np.int64) * 16000) // sr])
+    eng = Engine(blob(5), max_streams=per_call)
+    slots = eng.open_streams(per_call)
+    groups = [min(per_call, N - a) for a in range(0, N, per_call)]
+    row = {"config": f"scan_convert: {N} int16 recordings of {seconds} s, calls of {per_call} recordings", "recordings": N, "calls": len(groups)}
+
+    def passes(fn):
+        fn()
+        runs = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            fn()
+            runs.append(time.perf_counter() - t0)
+        return runs
+
+    # (a) 44.1 kHz: the new call against the host route
+    sr = 44100
+    one = at_rate(sr)
+    taps = convert_taps(sr)
+    s16 = seconds * 16000
+    segs = {}
+
+    def converted(rate, rec, key):
+        def run():
+            total = 0
+            for g in groups:
+                eng.reset(slots)
+                total += len(eng.scan_segments(slots[:g], [rec] * g, sample_rate=rate, convert=True))
+            segs[key] = total
+        return run
+
+    try:
+        from scipy.signal import resample_poly
+        # (resample_poly multiplies a window it is given by `up`: taps / L is this project's filter)
+        host_one = lambda x: resample_poly(x.astype(np.float32) / np.float32(32767.0), 160, 441, window=taps.astype(np.float64) / 160.0).astype(np.float32)
+        row["host_resampler"] = "scipy.signal.resample_poly(window=taps / L), 16 threads"
+    except ImportError:
+        from cutter_vad_amd.utils.audio import AudioUtils
+        host_one = lambda x: AudioUtils.resample_audio(x.astype(np.float32) / np.float32(32767.0), sr, 16000)
+        row["host_resampler"] = "AudioUtils.resample_audio, 16 threads"
+    pool = ThreadPoolExecutor(16)
+
+    def host_route():
+        total = 0
+        for g in groups:
+            ys = list(pool.map(host_one, [one] * g))
+            eng.reset(slots)
+            total += len(eng.scan_segments(slots[:g], ys))
+        segs["host"] = total
+
+    row["a_s_convert_runs"] = passes(converted(sr, one, "convert"))
+    row["a_s_host_runs"] = passes(host_route)
+    pool.shutdown()
+    row["a_s_convert"], row["a_s_host"] = float(np.median(row["a_s_convert_runs"])), float(np.median(row["a_s_host_runs"]))
+    row["a_host_over_convert"] = row["a_s_host"] / row["a_s_convert"]
+    row["a_segments"] = dict(segs)
+    row["a_link_GB_convert"], row["a_link_GB_host"] = N * one.size * 2 / 1e9, N * seconds * 16000 * 4 / 1e9
+    y_gpu, y_host = eng.convert([one], sr, taps=taps)[0][:s16], host_one(one)
+    row["a_max_abs_diff_of_the_two_signals"] = float(np.abs(y_gpu - y_host[:s16]).max())
+
+    # (b) the kernel alone
+    g = groups[0]
+    block = torch.from_numpy(np.tile(one, g)).cuda()
+    s_out = eng.convert_samples(one.size, sr)
+    d_out = torch.empty(g * ((s_out + 3) & ~3), device="cuda")
+    offs, lens = np.arange(g, dtype=np.int64) * one.size, np.full(g, one.size, np.int64)
+    stream = torch.cuda.Stream()
+    busy = torch.randn(6144, 6144, device="cuda")
+    ms = []
+    for i in range(4):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(stream):
+            torch.mm(busy, busy)                # keeps the stream busy while the host checks, plans and builds the tables
+            a.record()
+            eng.convert_device(offs, lens, sr, block.data_ptr(), g * one.size, d_out.data_ptr(), d_out.numel(), taps=taps, fmt=1,
+                               stream=stream.cuda_stream)
+            b.record()
+        stream.synchronize()
+        if i:
+            ms.append(a.elapsed_time(b))
+    moved = g * one.size * 2 + d_out.numel() * 4
+    row["b_ms_runs"], row["b_ms"] = ms, float(np.median(ms))
+    row["b_bytes_moved"], row["b_GB_per_s"] = moved, moved / (float(np.median(ms)) * 1e-3) / 1e9
+    row["b_note"] = ("HIP events around vad_convert_device on the caller's stream, behind a matrix product that keeps the stream busy while the "
+                     "host plans: the upload of the item and workgroup tables is inside, the operators' pack is cached")
+    del block, d_out, busy
+    torch.cuda.empty_cache()
+
+    # (c) 48 kHz: the converted scan against the chunk route
+    sr = 48000
+    one48 = at_rate(sr)
+
+    def chunk_route():
+        total = 0
+        for g_ in groups:
+            eng.reset(slots)
+            total += len(eng.scan_segments(slots[:g_], [one48] * g_, sample_rate=sr))
+        segs["chunk_48k"] = total
+
+    row["c_s_convert_runs"] = passes(converted(sr, one48, "convert_48k"))
+    row["c_s_chunk_runs"] = passes(chunk_route)
+    row["c_s_convert"], row["c_s_chunk"] = float(np.median(row["c_s_convert_runs"])), float(np.median(row["c_s_chunk_runs"]))
+    row["c_convert_over_chunk"] = row["c_s_convert"] / row["c_s_chunk"]
+    row["c_segments"] = {k: segs[k] for k in ("convert_48k", "chunk_48k")}
+    eng.close()
+    with open(os.path.join(root, "profiles", "scan_convert.json"), "w") as f_:
+        json.dump({"what": "Recordings at 44.1 kHz and any rational rate converted once on the GPU (vad_convert, vad_scan_convert_segments, "
+                           "csrc/scan_convert.hip): DESIGN 2.1v",
+                   "how": "python tools/bench_configs.py scan_convert on one MI355X, one process; per measurement one warm-up pass over the "
+                          "corpus and three timed ones (time.perf_counter around the Python calls, which pack, upload and wait; (b): HIP "
+                          "events behind a busy stream, the first of four launches dropped); medians.  The parent commit has neither call: (a)'s host route and "
+                          "(c)'s chunk route are what it offers, measured in the same process.  One process on one box: the spread "
+                          "between processes is not known", "result": row}, f_, indent=1)
+        f_.write("\n")
+    return row
+
+
 def scan_rate():
     """Whole recordings at 48 kHz, resampled on the GPU in the scan: vad_scan_rate_device on VAD_SCAN_BENCH_N (default
     4 096) int16 recordings of 30 s at 48 kHz - the golden clip, every sample three times - already in device memory, hop = chunk / 2,

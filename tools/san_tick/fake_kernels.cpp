@@ -286,6 +286,43 @@ extern "C" hipError_t vadk_launch_resample_cut(const ResampleCutArgs *a, hipStre
 
 // per-segment statistics of a feature matrix (csrc/mel_batch.hip: vadk_mel_stats), part by part as the workgroups are listed, into
 // the -inf and the zeros the caller stored: the maximum by the order of the bit patterns, the sums of q and q * q in integers
+// whole recordings converted to the engine's rate (csrc/scan_convert.hip: vadk_convert), the header's rule in plain float32: for
+// output m of an item, y = sum over k ASCENDING of x[k] * h[m M - k L + C] with x the loader's decoded, channel-selected, ungated
+// sample inside [0, S_in) and nothing outside it, h read back out of the packed operators (vad_layout.h: cv_pack_index; T_r[o][n]
+// with r = (m % P) / 16, o = m % 16 and n = k - (m / P) PI - base_r); the samples up to roundup4(S_out) are +0.0
+extern "C" hipError_t vadk_launch_convert(const ConvertArgs *a, hipStream_t) {
+    const size_t ch = a->channels == 2 ? 2 : 1;
+    if (a->nper == 0 || a->ntiles * 16u != a->P) return hipErrorInvalidValue;
+    const int64_t K = (int64_t)a->ksteps * 16, run = (int64_t)a->nper * a->P;
+    for (uint32_t b = 0; b < a->nwork; ++b) {
+        const ConvertWork w = a->work[b];
+        const ConvertItem it = a->items[w.item];
+        const uint32_t mode = it.quad_in >> SCAN_MODE_SHIFT, qin = it.quad_in & ((1u << SCAN_MODE_SHIFT) - 1u);
+        const int64_t S_in = it.s_in, S_out = it.s_out, m0 = (int64_t)w.run * run;
+        if (m0 >= S_out) return hipErrorInvalidValue;
+        const int64_t m1 = std::min<int64_t>((S_out + 3) & ~(int64_t)3, m0 + run);
+        for (int64_t m = m0; m < m1; ++m) {
+            float y = 0.f;
+            const uint32_t r = (uint32_t)((m % a->P) / 16);
+            const int64_t k0 = (m / a->P) * (int64_t)a->PI + cv_base(r, a->ntaps, a->L, a->M);
+            for (int64_t n = 0; n < K && m < S_out; ++n) {
+                const int64_t k = k0 + n;
+                if (k < 0 || k >= S_in) continue;
+                const size_t i = 4 * (size_t)qin + (size_t)k;
+                float x;
+                if (ch == 1) x = first_sample(a->audio, i, a->fmt, 1);
+                else {
+                    const float l = first_sample(a->audio, 2 * i, a->fmt, 1), rr = first_sample(a->audio, 2 * i + 1, a->fmt, 1);
+                    x = mode == SCAN_MIX ? (l + rr) * 0.5f : mode == SCAN_RIGHT ? rr : l;
+                }
+                y += x * a->op[cv_pack_index(r, (uint32_t)(m % 16), (uint32_t)n, (uint32_t)K)];
+            }
+            a->out[4 * (size_t)it.quad_out + (size_t)m] = y;
+        }
+    }
+    return hipSuccess;
+}
+
 static bool bits_above(uint32_t y, uint32_t x) {                       // y is the larger float32: -0.0 below +0.0
     const bool xn = x >> 31, yn = y >> 31;
     return xn != yn ? xn : xn ? y < x : y > x;
