@@ -10,7 +10,7 @@ from cutter_vad_amd import _ffi
 from tests import convert_ref as CR
 from tests.cut_ref import F32, FMT, MIX, RANGE, SENT32, raw_cut, untouched
 from tests.test_gpu_scan import GOLD, THR, _engine
-from tests.test_scan_convert_host import RATES, conv, exact_taps, scan_conv, scan_segs, want_exact
+from tests.test_scan_convert_host import RATES, _check, conv, exact_taps, scan_conv, scan_segs, want_exact
 
 pytestmark = pytest.mark.gpu
 
@@ -20,16 +20,6 @@ def eng():
     e = _engine(16000)
     yield e
     e.close()
-
-
-def _check(out, off, block, kind, items, lens, taps, sr):
-    for i, it in enumerate(items):
-        y = want_exact(block, kind, it[3], it[1], lens[i], taps, sr)
-        a, b = int(off[i]), int(off[i + 1])
-        assert b - a == (y.size + 3) & ~3
-        assert out[a:a + y.size].tobytes() == y.tobytes(), (sr, kind, taps.size, i, lens[i], np.flatnonzero(out[a:a + y.size] != y)[:8])
-        assert out[a + y.size:b].tobytes() == bytes(4 * (b - a - y.size)), (sr, i)       # the padding is +0.0
-    assert untouched(out[int(off[-1]):])                                                  # the sentinel behind the output
 
 
 # ---- exact cases ------------------------------------------------------------------------------------------------------

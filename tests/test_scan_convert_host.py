@@ -1,7 +1,8 @@
 """vad_convert, vad_convert_device, vad_scan_convert_segments and their Python faces on the host side: exports, vad_convert_samples,
 every refusal with its message and an untouched output, n == 0, every kind of engine, the operator pack against h[m M - k L + C], the
 taps cache, convert_taps against resample_taps, values against tests/convert_ref.py, the definitional equality with vad_convert +
-vad_scan_segments, the corpus functions and their ConfigurationErrors - the real csrc/engine.cpp (checks, plan, operator pack) over
+vad_scan_segments, the corpus functions and their ConfigurationErrors, every accepted rate and the covering set of
+tests/convert_cases.py (the bodies tests/test_gpu_scan_convert_family.py runs on the GPU) - the real csrc/engine.cpp (checks, plan, operator pack) over
 the HIP stand-in (tests/standin.py: tools/san_tick/fake_kernels.cpp restates the rule in plain float32, k ascending, over the
 unpacked view of the packed operators).  No GPU."""
 import ctypes as C
@@ -13,6 +14,7 @@ import pytest
 
 from cutter_vad_amd import _ffi, weights_io
 from cutter_vad_amd.core.exceptions import ConfigurationError
+from tests import convert_cases as CC
 from tests import convert_ref as CR
 from tests import standin
 from tests.cut_ref import FMT, INV, MIX, SENT32, heard, untouched
@@ -135,6 +137,72 @@ def want_exact(block, kind, ch, off, S_in, taps, sr, R=16000):
     assert np.array_equal(xi.astype(np.float64), x)
     y = CR.convert_exact(xi, np.asarray(taps, np.float64).astype(np.int64), sr, R)
     return (y.astype(np.float64) / unit).astype(np.float32)
+
+
+def _check(out, off, block, kind, items, lens, taps, sr, R=16000):
+    for i, it in enumerate(items):
+        y = want_exact(block, kind, it[3], it[1], lens[i], taps, sr, R)
+        a, b = int(off[i]), int(off[i + 1])
+        assert b - a == (y.size + 3) & ~3
+        assert out[a:a + y.size].tobytes() == y.tobytes(), (sr, kind, taps.size, i, lens[i], np.flatnonzero(out[a:a + y.size] != y)[:8])
+        assert out[a + y.size:b].tobytes() == bytes(4 * (b - a - y.size)), (sr, i)       # the padding is +0.0
+    assert untouched(out[int(off[-1]):])                                                  # the sentinel behind the output
+
+
+# ---- the bodies that run on the stand-in here and on the GPU in tests/test_gpu_scan_convert_family.py -------------------
+def exact_items(lib, eng, sr, taps, block, items, R=16000):
+    """mono int16 items byte for byte against the int64 reference: values, +0.0 padding, the sentinel, out_offset == CR.layout"""
+    lens = [it[2] for it in items]
+    want_off = CR.layout(lens, sr, R)
+    rc, msg, out, off = conv(lib, eng, items, taps, block, 1, FMT["i16_32768"], sr, int(want_off[-1]))
+    assert rc == _ffi.VAD_OK and off.tolist() == want_off.tolist(), (sr, msg)
+    _check(out, off, block, "i16_32768", items, lens, taps, sr, R)
+    return out[:int(want_off[-1])].tobytes()
+
+
+def every_rate_body(lib, eng, rates, R=16000):
+    """one item of PI + 1 samples - one whole period and a period with a single input - and 2 L + 1 taps at each rate"""
+    for sr in rates:
+        assert CR.accepted(sr, R)
+        rng = np.random.default_rng(sr)
+        n = CR.period_inputs(sr, R) + 1
+        exact_items(lib, eng, sr, exact_taps(rng, 2 * CR.ratio(sr, R)[0] + 1), rng.integers(-64, 65, n).astype(np.int16), [(0, 0, n, 0)], R)
+
+
+def depth_body(lib, eng, sr):
+    """the body of tests/test_gpu_scan_convert.py::test_rates_tap_counts_and_lengths_byte_for_byte, with the largest tap count at
+    every rate"""
+    rng = np.random.default_rng(sr)
+    L, _ = CR.ratio(sr)
+    for N in (1, 3, 2 * L + 1, CR.MAX_REACH * L - 1):
+        block, items = CC.depth_block(rng, CC.depth_lengths(N, sr))
+        assert block.size < 90000
+        exact_items(lib, eng, sr, exact_taps(rng, N), block, items)
+
+
+RATES_8K = {44100: (80, 441), 16000: (1, 2), 11025: (320, 441), 48000: (1, 6)}
+
+
+def engine_8k_body(lib, e8):
+    for sr, LM in RATES_8K.items():
+        assert CR.ratio(sr, 8000) == LM and CR.accepted(sr, 8000)
+        rng = np.random.default_rng(sr)
+        PI = CR.period_inputs(sr, 8000)
+        block, items = CC.depth_block(rng, [1, PI + 1, 3 * PI + 2])
+        exact_items(lib, e8, sr, exact_taps(rng, 2 * LM[0] + 1), block, items, 8000)
+
+
+def cache_body(lib, eng):
+    """the same taps' bytes at the same L and another M, and at the same M and another L: each call has its own operators"""
+    rng = np.random.default_rng(321)
+    h = exact_taps(rng, 321)
+    x = rng.integers(-64, 65, 3001).astype(np.int16)
+    for a, b in ((44100, 63900), (15975, 31950)):
+        (La, Ma), (Lb, Mb) = CR.ratio(a), CR.ratio(b)
+        assert (La == Lb) != (Ma == Mb) and h.size <= CR.MAX_REACH * min(La, Lb)
+        first = exact_items(lib, eng, a, h, x, [(0, 0, x.size, 0)])
+        other = exact_items(lib, eng, b, h, x, [(0, 0, x.size, 0)])
+        assert exact_items(lib, eng, a, h, x, [(0, 0, x.size, 0)]) == first != other
 
 
 # ---- the ABI ----------------------------------------------------------------------------------------------------------
@@ -595,6 +663,61 @@ def test_corpus_functions_take_convert_and_keep_refusing_without_it(lib, make_en
     for fn in (scan_recordings, cut_recordings):
         with pytest.raises(ConfigurationError, match="needs an engine with convert"):
             fn(loud, cfg, engine=Bare(), sample_rate=sr, convert=True)
+
+
+# ---- the whole family of accepted rates (tests/convert_cases.py) -------------------------------------------------------
+@pytest.mark.parametrize("L", CC.CLASSES)
+def test_every_accepted_rate_of_a_class_byte_for_byte(lib, eng, L):
+    """all 3 440 rates the argument check takes on a 16 kHz engine, class of L by class"""
+    c = CC.cover_census()
+    rates = CC.family()[L]
+    assert c["family_size"] == 3440 and L in c["family_classes"] and rates and all(CR.ratio(sr)[0] == L for sr in rates)
+    every_rate_body(lib, eng, rates)
+
+
+@pytest.mark.parametrize("L", CC.CLASSES)
+def test_default_taps_and_sample_counts_at_every_accepted_rate(lib, eng, L):
+    for sr in CC.family()[L]:
+        h = eng._convert_taps(sr, None)
+        assert h.dtype == np.float32 and h.size % 2 == 1 and 1 <= h.size <= CR.MAX_REACH * L and np.isfinite(h).all(), (sr, h.size)
+        for S in (0, 1, CR.ratio(sr)[1] - 1, CR.ratio(sr)[1], 100003):
+            assert eng.convert_samples(S, sr) == S * L // CR.ratio(sr)[1] == CR.samples(S, sr), (sr, S)
+
+
+@pytest.mark.parametrize("sr", CC.COVER)
+def test_the_covering_set_in_depth(lib, eng, sr):
+    CC.cover_census()
+    depth_body(lib, eng, sr)
+
+
+def test_an_8k_engine_converts_against_its_own_rate(lib, make_engine):
+    assert sorted(CC.family(8000)) == [1, 2, 4, 5, 8, 10, 16, 20, 25, 32, 40, 50, 64, 80, 100, 160, 200, 320, 400]
+    engine_8k_body(lib, make_engine(rate=8000))
+
+
+def test_the_operator_cache_keys_on_L_and_on_M(lib, eng):
+    cache_body(lib, eng)
+
+
+def test_a_sample_of_refused_rates_launches_nothing(lib, eng, make_engine):
+    """just outside 4 000 .. 192 000 Hz, the engine's own rate, a period above 640 outputs (L = 125) and M = 641 - and their accepted
+    neighbours"""
+    rng = np.random.default_rng(5)
+    block = rng.integers(-64, 65, 2000).astype(np.int16)
+    h = exact_taps(rng, 3)
+    for sr, words in ((3999, "L / M = 16000 / 3999"), (192001, "L / M = 16000 / 192001"), (16000, "L / M = 1 / 1"), (4096, "L / M = 125 / 32"),
+                      (128200, "L / M = 80 / 641"), (64100, "L / M = 160 / 641"), (10256, "L / M = 1000 / 641")):
+        assert not CR.accepted(sr)
+        for device in (False, True):
+            rc, msg, out, off = conv(lib, eng, [(0, 0, 2000, 0)], h, block, 1, FMT["i16_32768"], sr, 1 << 16, device=device)
+            assert rc == UNSUPPORTED and untouched(out) and (off == -5).all() and words in msg, (sr, rc, msg)
+        assert lib.vad_convert_samples(eng.handle, 1000, sr) == -1 and eng.convert_samples(1000, sr) == -1
+    for sr in (4000, 192000, 127800, 15999 + 26):
+        assert CR.accepted(sr) == (lib.vad_convert_samples(eng.handle, 1000, sr) >= 0), sr
+    assert CR.accepted(4000) and CR.accepted(192000) and CR.accepted(127800)
+    e8 = make_engine(rate=8000)
+    rc, msg, out, off = conv(lib, e8, [(0, 0, 2000, 0)], h, block, 1, FMT["i16_32768"], 8000, 1 << 16)
+    assert rc == UNSUPPORTED and untouched(out) and (off == -5).all() and "L / M = 1 / 1" in msg, msg
 
 
 # ---- the LDS pitch ----------------------------------------------------------------------------------------------------
