@@ -3116,7 +3116,7 @@ int vad_scan_render_device(vad_engine *e, const vad_cut_item *items, int64_t n, 
                       denoise_thresh, out_fmt, d_out, out_samples, stream);
 }
 
-// both channels of a two-channel block, interleaved (csrc/scan_cut_stereo.hip, csrc/scan_render_stereo.hip): the mono calls'
+// both channels of a two-channel block, interleaved (csrc/scan_cut.hip, csrc/scan_render.hip): the mono calls'
 // plans, tables and checks under these names, sample FRAMES where those count samples
 int vad_scan_cut_stereo(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const void *audio, int64_t audio_samples,
                         int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt,

@@ -165,17 +165,12 @@ __global__ void __launch_bounds__(CV_THREADS) vadk_convert(const ConvertArgs a) 
 extern "C" hipError_t vadk_launch_convert(const ConvertArgs *a, hipStream_t stream) {
     (void)hipGetLastError();
     if (a->nwork == 0) return hipSuccess;
-    const int f = a->fmt == VAD_FMT_F32 ? 0 : a->fmt == VAD_FMT_ULAW8 ? 2 : a->fmt == VAD_FMT_ALAW8 ? 3 : 1;
     if (a->nper == 0 || a->ntiles * 16u != a->P) return hipErrorInvalidValue;
     const uint32_t floats = cv_lds_floats(a->nper, a->PI, cv_lead(a->ntaps, a->L), a->bmax, a->ksteps << 4);
     if (floats > CV_LDS_FLOATS) return hipErrorInvalidValue;
     const size_t lds = sizeof(float) * (size_t)floats;
-#define VADK_CV(F, C)                                                                                                               \
-    if (f == F && a->channels == C) {                                                                                               \
-        hipLaunchKernelGGL((vadk_convert<F, C>), dim3(a->nwork), dim3(CV_THREADS), lds, stream, *a);                                \
-        return hipGetLastError();                                                                                                   \
-    }
-    VADK_CV(0, 1) VADK_CV(1, 1) VADK_CV(2, 1) VADK_CV(3, 1) VADK_CV(0, 2) VADK_CV(1, 2) VADK_CV(2, 2) VADK_CV(3, 2)
-#undef VADK_CV
-    return hipErrorInvalidValue;
+    return launch_variant<4, 2>([&](auto F, auto C) {
+        hipLaunchKernelGGL((vadk_convert<F, C + 1>), dim3(a->nwork), dim3(CV_THREADS), lds, stream, *a);
+        return hipGetLastError();
+    }, wire_fmt(a->fmt), (int)a->channels - 1);
 }

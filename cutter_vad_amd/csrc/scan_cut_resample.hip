@@ -82,16 +82,9 @@ extern "C" hipError_t vadk_launch_cut_resample(const CutResampleArgs *a, hipStre
     if (a->rows_end <= a->r0) return hipSuccess;
     if (a->r0 % (uint32_t)MT) return hipErrorInvalidValue;
     const int tiles = (int)((a->rows_end - a->r0 + (uint32_t)MT - 1u) / (uint32_t)MT);
-    const int f = a->fmt == VAD_FMT_F32 ? 0 : a->fmt == VAD_FMT_ULAW8 ? 2 : a->fmt == VAD_FMT_ALAW8 ? 3 : 1;
-#define VADK_CRS(F, C)                                                                                                  \
-    if (f == F && a->channels == C) {                                                                                   \
-        if (tiles <= 256)                                                                                               \
-            hipLaunchKernelGGL((vadk_cut_resample<1, F, C>), dim3(tiles, 2), dim3(NTHREADS), 0, stream, *a);            \
-        else                                                                                                            \
-            hipLaunchKernelGGL((vadk_cut_resample<2, F, C>), dim3(tiles), dim3(NTHREADS), 0, stream, *a);               \
-        return hipGetLastError();                                                                                       \
-    }
-    VADK_CRS(0, 1) VADK_CRS(1, 1) VADK_CRS(2, 1) VADK_CRS(3, 1) VADK_CRS(0, 2) VADK_CRS(1, 2) VADK_CRS(2, 2) VADK_CRS(3, 2)
-#undef VADK_CRS
-    return hipErrorInvalidValue;
+    return launch_variant<4, 2>([&](auto F, auto C) {
+        if (tiles <= 256) hipLaunchKernelGGL((vadk_cut_resample<1, F, C + 1>), dim3(tiles, 2), dim3(NTHREADS), 0, stream, *a);
+        else hipLaunchKernelGGL((vadk_cut_resample<2, F, C + 1>), dim3(tiles), dim3(NTHREADS), 0, stream, *a);
+        return hipGetLastError();
+    }, wire_fmt(a->fmt), (int)a->channels - 1);
 }

@@ -108,13 +108,8 @@ __global__ void __launch_bounds__(CUT_THREADS) vadk_seg_levels(const CutArgs a, 
 extern "C" hipError_t vadk_launch_seg_levels(const CutArgs *a, float clip, hipStream_t stream) {
     (void)hipGetLastError();
     if (a->nwork == 0) return hipSuccess;
-    const int f = a->fmt == VAD_FMT_F32 ? 0 : a->fmt == VAD_FMT_ULAW8 ? 2 : a->fmt == VAD_FMT_ALAW8 ? 3 : 1;
-#define VADK_LV(F, C)                                                                                                   \
-    if (f == F && a->channels == C) {                                                                                   \
-        hipLaunchKernelGGL((vadk_seg_levels<F, C>), dim3(a->nwork), dim3(CUT_THREADS), 0, stream, *a, clip);            \
-        return hipGetLastError();                                                                                       \
-    }
-    VADK_LV(0, 1) VADK_LV(1, 1) VADK_LV(2, 1) VADK_LV(3, 1) VADK_LV(0, 2) VADK_LV(1, 2) VADK_LV(2, 2) VADK_LV(3, 2)
-#undef VADK_LV
-    return hipErrorInvalidValue;
+    return launch_variant<4, 2>([&](auto F, auto C) {
+        hipLaunchKernelGGL((vadk_seg_levels<F, C + 1>), dim3(a->nwork), dim3(CUT_THREADS), 0, stream, *a, clip);
+        return hipGetLastError();
+    }, wire_fmt(a->fmt), (int)a->channels - 1);
 }

@@ -151,18 +151,13 @@ extern "C" hipError_t vadk_launch_seg_mel(const MelArgs *a, hipStream_t stream) 
     (void)hipGetLastError();
     if (a->nwork == 0) return hipSuccess;
     const size_t lds = sizeof(float) * ((size_t)mel_lds_span_floats(a->n_fft, a->hop) + (size_t)a->bins_pad * MEL_TILE);
-    const int f = a->fmt == VAD_FMT_F32 ? 0 : a->fmt == VAD_FMT_ULAW8 ? 2 : a->fmt == VAD_FMT_ALAW8 ? 3 : 1;
-#define VADK_MEL(F, C)                                                                                                              \
-    if (f == F && a->channels == C) {                                                                                               \
-        if (lds > 48u * 1024u) {                                                                                                    \
-            const hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void *>(&vadk_seg_mel<F, C>),                           \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
-            if (r != hipSuccess) return r;                                                                                          \
-        }                                                                                                                           \
-        hipLaunchKernelGGL((vadk_seg_mel<F, C>), dim3(a->nwork), dim3(MEL_THREADS), lds, stream, *a);                               \
-        return hipGetLastError();                                                                                                   \
-    }
-    VADK_MEL(0, 1) VADK_MEL(1, 1) VADK_MEL(2, 1) VADK_MEL(3, 1) VADK_MEL(0, 2) VADK_MEL(1, 2) VADK_MEL(2, 2) VADK_MEL(3, 2)
-#undef VADK_MEL
-    return hipErrorInvalidValue;
+    return launch_variant<4, 2>([&](auto F, auto C) {
+        if (lds > 48u * 1024u) {
+            const hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void *>(&vadk_seg_mel<F, C + 1>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (r != hipSuccess) return r;
+        }
+        hipLaunchKernelGGL((vadk_seg_mel<F, C + 1>), dim3(a->nwork), dim3(MEL_THREADS), lds, stream, *a);
+        return hipGetLastError();
+    }, wire_fmt(a->fmt), (int)a->channels - 1);
 }

@@ -99,16 +99,9 @@ extern "C" hipError_t vadk_launch_scan_resample(const ScanResampleArgs *a, hipSt
     const long long rows = (long long)a->live * a->W;
     if (rows <= 0) return hipSuccess;
     const int tiles = (int)((rows + MT - 1) / MT);
-    const int f = a->fmt == VAD_FMT_F32 ? 0 : a->fmt == VAD_FMT_ULAW8 ? 2 : a->fmt == VAD_FMT_ALAW8 ? 3 : 1;
-#define VADK_SRS(F, C)                                                                                                  \
-    if (f == F && a->channels == C) {                                                                                   \
-        if (tiles <= 256)                                                                                               \
-            hipLaunchKernelGGL((vadk_scan_resample<1, F, C>), dim3(tiles, 2), dim3(NTHREADS), 0, stream, *a);           \
-        else                                                                                                            \
-            hipLaunchKernelGGL((vadk_scan_resample<2, F, C>), dim3(tiles), dim3(NTHREADS), 0, stream, *a);              \
-        return hipGetLastError();                                                                                       \
-    }
-    VADK_SRS(0, 1) VADK_SRS(1, 1) VADK_SRS(2, 1) VADK_SRS(3, 1) VADK_SRS(0, 2) VADK_SRS(1, 2) VADK_SRS(2, 2) VADK_SRS(3, 2)
-#undef VADK_SRS
-    return hipErrorInvalidValue;
+    return launch_variant<4, 2>([&](auto F, auto C) {
+        if (tiles <= 256) hipLaunchKernelGGL((vadk_scan_resample<1, F, C + 1>), dim3(tiles, 2), dim3(NTHREADS), 0, stream, *a);
+        else hipLaunchKernelGGL((vadk_scan_resample<2, F, C + 1>), dim3(tiles), dim3(NTHREADS), 0, stream, *a);
+        return hipGetLastError();
+    }, wire_fmt(a->fmt), (int)a->channels - 1);
 }

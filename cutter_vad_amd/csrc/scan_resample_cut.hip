@@ -11,7 +11,7 @@
 //      order, is the A operand - one coalesced 1 KiB load per wave and four k-steps, shared by the wave's two tiles - and the span
 //      is the B operand out of LDS, column = row-block, in the skew that keeps a fragment's 64 reads in 64 banks.
 //   3. D has four consecutive outputs of one row-block on a lane: one quad, gained (a multiply of its own) and stored as the cut
-//      stores it - 16 bytes of float32 or 8 of int16 PCM.
+//      stores it - 16 bytes of float32 or 8 of int16 PCM (vadk_device.h: pcm16).
 // Every sum has a fixed order and nothing is accumulated across workgroups: two runs give the same bytes.
 #include <hip/hip_runtime.h>
 #include "../../include/vad_engine.h"
@@ -25,13 +25,6 @@ static_assert(VAD_RESAMPLE_CUT_WG_SAMPLES == RSC_WG_SAMPLES, "the header's workg
 static_assert(RSC_WG_SAMPLES == 2 * 256 * (RSC_THREADS / 64), "two tiles of 256 outputs per wave");
 
 namespace {
-
-// scan_cut.hip's conversion: one float32 multiply, the clamp, toward zero
-__device__ __forceinline__ uint32_t pcm16(float x) {
-#pragma clang fp contract(off)
-    const float v = x * 32767.0f;
-    return (uint32_t)(int)fminf(fmaxf(v, -32768.0f), 32767.0f) & 0xffffu;
-}
 
 __device__ __forceinline__ float pick(f32x4 v, uint32_t k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
 
@@ -120,19 +113,12 @@ __global__ void __launch_bounds__(RSC_THREADS) vadk_resample_cut(const ResampleC
 extern "C" hipError_t vadk_launch_resample_cut(const ResampleCutArgs *a, hipStream_t stream) {
     (void)hipGetLastError();
     if (a->nwork == 0) return hipSuccess;
-    const int f = a->fmt == VAD_FMT_F32 ? 0 : a->fmt == VAD_FMT_ULAW8 ? 2 : a->fmt == VAD_FMT_ALAW8 ? 3 : 1;
     const int rate = a->sr_in == 8000 ? 0 : a->sr_in == 24000 ? 1 : a->sr_in == 48000 ? 2 : -1;
     if (rate < 0) return hipErrorInvalidValue;
     const size_t lds = sizeof(float) * (size_t)rsc_lds_floats(rsc_A(a->sr_in), a->ksteps << 4);
     if (lds > 48u * 1024u) return hipErrorInvalidValue;               // (511 taps at 48 kHz: 29 KiB)
-#define VADK_RSC(F, C, R)                                                                                                           \
-    if (f == F && a->channels == C && rate == R) {                                                                                  \
-        hipLaunchKernelGGL((vadk_resample_cut<F, C, R>), dim3(a->nwork), dim3(RSC_THREADS), lds, stream, *a);                       \
-        return hipGetLastError();                                                                                                   \
-    }
-#define VADK_RSC4(C, R) VADK_RSC(0, C, R) VADK_RSC(1, C, R) VADK_RSC(2, C, R) VADK_RSC(3, C, R)
-    VADK_RSC4(1, 0) VADK_RSC4(1, 1) VADK_RSC4(1, 2) VADK_RSC4(2, 0) VADK_RSC4(2, 1) VADK_RSC4(2, 2)
-#undef VADK_RSC4
-#undef VADK_RSC
-    return hipErrorInvalidValue;
+    return launch_variant<4, 2, 3>([&](auto F, auto C, auto R) {
+        hipLaunchKernelGGL((vadk_resample_cut<F, C + 1, R>), dim3(a->nwork), dim3(RSC_THREADS), lds, stream, *a);
+        return hipGetLastError();
+    }, wire_fmt(a->fmt), (int)a->channels - 1, rate);
 }

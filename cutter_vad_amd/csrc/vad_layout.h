@@ -262,7 +262,7 @@ struct ScanArgs {
     int32_t channels;         // interleaved channels of the block: 2, or 0 / 1 = mono
 };
 
-// finished segments cut out of a scanned block (csrc/scan_cut.hip: vadk_scan_cut; vad_scan_cut).  The unit is the loader's quad:
+// finished segments cut out of a scanned block (csrc/scan_cut.hip: vadk_scan_cut, vadk_scan_cut_stereo; vad_scan_cut).  The unit is the loader's quad:
 // output quad oq of a segment comes from input quad quad_in + (oq >> frame_shift) * hopq + (oq & (frame / 4 - 1)) - the segment's
 // frames back to back (VAD_CUT_FRAMES) - or from quad_in + oq (VAD_CUT_RANGE: frame_shift = 31, hopq unused), and goes to quad
 // quad_out + oq of the output.  A workgroup of CUT_THREADS threads serves CUT_WG_QUADS consecutive output quads of ONE segment in
@@ -485,7 +485,7 @@ struct ConvertArgs {
 };
 static_assert(sizeof(ConvertArgs) == 88, "ConvertArgs layout");
 
-// one finished piece of audio out of a scanned block (csrc/scan_render.hip: vadk_scan_render; vad_scan_render).  The kernel is
+// one finished piece of audio out of a scanned block (csrc/scan_render.hip: vadk_scan_render, vadk_scan_render_stereo; vad_scan_render).  The kernel is
 // driven by the OUTPUT: the host sweeps the segments' output spans into regions - maximal runs of output quads covered by the same
 // none, one or two segments - and lists a workgroup per CUT_WG_QUADS quads of a region, so the kind of a workgroup is uniform.
 // The segments are CutSeg, the sample range once (input quad quad_in + k for local quad k = output quad - quad_out).  ramp holds

@@ -1,8 +1,12 @@
 // Device helpers shared by the fused model kernels (gfx950): MFMA fragment convention, quad stores,
 // fenced scheduling, buffer-descriptor weight loads, fast activation functions.  See vad_layout.h.
+// Behind them what the scan kernels share: a block's wire quads (WireQuad), the gate, the PCM16 conversion and the packed store of
+// segment audio (pcm16, store_quad), and the launchers' choice of an instantiation (wire_fmt, launch_variant).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#include <utility>
+#include "../../include/vad_engine.h"
 #include "vad_layout.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -282,7 +286,8 @@ __device__ __forceinline__ f32x4 gate4(f32x4 v, float thr) {
 // One aligned quad of sample frames of a scanned block in its wire format, outside the model kernels (scan_cut.hip,
 // scan_resample.hip): the loads, the decoders and the channel selection of silero_v5_t16_body.h's loader, restated - the
 // instantiations of that file stay the code they were.  FMT: 0 float32, 1 int16 (the divisor is an argument), 2 mu-law, 3 A-law -
-// the numbering of silero_v5_t16.hip's loaders; CH: interleaved channels of the block.  No gate: that is the caller's.
+// the numbering of silero_v5_t16.hip's loaders (a launcher gets it from wire_fmt, below); CH: interleaved channels of the block.
+// No gate: that is the caller's.
 template <int FMT, int CH>
 struct WireQuad {
     static constexpr bool f32in = FMT == 0, G711 = FMT >= 2;
@@ -336,6 +341,32 @@ struct WireQuad {
     }
 };
 
+// The segment-audio kernels' conversion to int16 PCM.  utils/wav_writer.py:41: np.clip(x * 32767, -32768, 32767).astype(np.int16) -
+// one float32 multiply, the clamp, the conversion toward zero (a NaN's result is unspecified there and here)
+__device__ __forceinline__ uint32_t pcm16(float x) {
+#pragma clang fp contract(off)
+    const float v = x * 32767.0f;
+    return (uint32_t)(int)fminf(fmaxf(v, -32768.0f), 32767.0f) & 0xffffu;
+}
+
+// Output quad o of packed segment audio.  One channel (l): 8 bytes of int16 PCM (OUT 0) or 16 of float32 (OUT 1).  BOTH channels
+// kept (l, r): interleaved L0 R0 L1 R1 L2 R2 L3 R3 and twice as wide - one 16-byte store or two.
+template <int OUT, bool BOTH>
+__device__ __forceinline__ void store_quad(void *out, uint64_t o, f32x4 l, [[maybe_unused]] f32x4 r) {
+    if constexpr (!BOTH) {
+        if constexpr (OUT == 0)
+            static_cast<u32x2 *>(out)[o] = u32x2{pcm16(l.x) | (pcm16(l.y) << 16), pcm16(l.z) | (pcm16(l.w) << 16)};
+        else
+            static_cast<f32x4 *>(out)[o] = l;
+    } else if constexpr (OUT == 0) {
+        static_cast<u32x4 *>(out)[o] = u32x4{pcm16(l.x) | (pcm16(r.x) << 16), pcm16(l.y) | (pcm16(r.y) << 16),
+                                             pcm16(l.z) | (pcm16(r.z) << 16), pcm16(l.w) | (pcm16(r.w) << 16)};
+    } else {
+        static_cast<f32x4 *>(out)[2 * o] = f32x4{l.x, r.x, l.y, r.y};
+        static_cast<f32x4 *>(out)[2 * o + 1] = f32x4{l.z, r.z, l.w, r.w};
+    }
+}
+
 // Non-finite input (include/vad_engine.h, VAD_EV_REJECTED): a running maximum of |x| over the raw samples, before the gate, with
 // IEEE maximum semantics - a NaN operand makes the result NaN (v_maximum3_f32, the |.| as source modifiers; fmaxf would drop it).
 // The frame is rejected when the maximum of its samples is NaN or +Inf: nonfinite(m).
@@ -344,6 +375,26 @@ __device__ __forceinline__ float absmax4(float m, f32x4 v) {
     return __builtin_elementwise_maximum(a, __builtin_elementwise_maximum(fabsf(v.z), fabsf(v.w)));
 }
 __device__ __forceinline__ bool nonfinite(float m) { return !(m <= 3.40282347e+38f); }
+
+// ---- host side: the launchers' choice of an instantiation ----
+// VAD_FMT_* -> WireQuad's FMT (the int16 divisor is an argument of the kernel, not a kernel of its own)
+inline int wire_fmt(int fmt) { return fmt == VAD_FMT_F32 ? 0 : fmt == VAD_FMT_ULAW8 ? 2 : fmt == VAD_FMT_ALAW8 ? 3 : 1; }
+
+// launch_variant<N0, N1, ...>(fn, i0, i1, ...): run-time indices i_k in [0, N_k) as compile-time constants - fn(c0, c1, ...) with
+// c_k a std::integral_constant<int, i_k>, usable as a template argument; fn launches and returns hipGetLastError().  An index out
+// of its range launches nothing: hipErrorInvalidValue.  fn is instantiated for every combination, and for nothing else.
+template <class Fn>
+hipError_t launch_variant(Fn &&fn) { return fn(); }
+template <int N, int... Ns, class Fn, class... Is>
+hipError_t launch_variant(Fn &&fn, int i, Is... is);
+template <int... Ns, int... K, class Fn, class... Is>
+hipError_t launch_variant_(std::integer_sequence<int, K...>, Fn &fn, int i, Is... is) {
+    hipError_t r = hipErrorInvalidValue;
+    (void)((i == K && (r = launch_variant<Ns...>([&](auto... c) { return fn(std::integral_constant<int, K>{}, c...); }, is...), true)) || ...);
+    return r;
+}
+template <int N, int... Ns, class Fn, class... Is>
+hipError_t launch_variant(Fn &&fn, int i, Is... is) { return launch_variant_<Ns...>(std::make_integer_sequence<int, N>{}, fn, i, is...); }
 
 } }  // namespace vadk::dev
 

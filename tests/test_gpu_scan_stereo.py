@@ -1,4 +1,4 @@
-"""vad_scan_cut_stereo / vad_scan_render_stereo on the GPU (csrc/scan_cut_stereo.hip, csrc/scan_render_stereo.hip).  The bar is
+"""vad_scan_cut_stereo / vad_scan_render_stereo on the GPU (csrc/scan_cut.hip, csrc/scan_render.hip).  The bar is
 equality, twice: every case is BYTE FOR BYTE the numpy rule of tests/stereo_ref.py (the mono references per channel, interleaved)
 AND what Engine.cut / Engine.render give per channel on the same GPU, interleaved - at the shapes where the kernels can go wrong:
 segment lengths around one lane's pass, one pass of the workgroup, a workgroup's share and two shares, frames at both hops, every

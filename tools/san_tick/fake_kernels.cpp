@@ -133,7 +133,7 @@ extern "C" hipError_t vadk_launch_silero_v5_scan16(const StepParams *p, const Sc
 // gated value times gains[segment], one float32 multiply, ahead of either.  levels (csrc/scan_levels.hip: vadk_seg_levels): nothing
 // is stored - the gated values of a segment are folded into its vad_level (a.out, zeroed by the caller): energy_q32 +=
 // min(rint((double)x * x * 2^32), 2^32), peak = the larger bit pattern of |x|, clipped += |x| >= clip in float32.  stereo
-// (csrc/scan_cut_stereo.hip: vadk_scan_cut_stereo): the mode bits are ignored, sample frame o takes two output values - the left
+// (csrc/scan_cut.hip: vadk_scan_cut_stereo): the mode bits are ignored, sample frame o takes two output values - the left
 // channel's at 2 o, the right one's at 2 o + 1 - each gated, gained and converted on its own
 static hipError_t fake_cut(const CutArgs *a, const float *gains, bool levels, float clip, bool stereo = false) {
     if (stereo && a->channels != 2) return hipErrorInvalidValue;
@@ -405,7 +405,7 @@ extern "C" hipError_t vadk_launch_mel_batch(const MelBatchArgs *a, hipStream_t) 
 // one finished piece of audio (csrc/scan_render.hip: vadk_scan_render), the kernel's arithmetic in plain C++, output quad by output
 // quad as its workgroups are listed: per covering segment the cut's decoded, channel-selected, gated sample, times the gain, times
 // the fade-in entry (or 1), times the fade-out entry (or 1) - three float32 multiplies - then the sum of the two where two segments
-// cover the sample, zero where none does, and the cut's conversion.  stereo (csrc/scan_render_stereo.hip: vadk_scan_render_stereo):
+// cover the sample, zero where none does, and the cut's conversion.  stereo (csrc/scan_render.hip: vadk_scan_render_stereo):
 // the mode bits are ignored, sample frame s takes two output values - left at 2 s, right at 2 s + 1 - under the same gain and ramp
 static hipError_t fake_render(const RenderArgs *a, bool stereo = false) {
     if (stereo && a->channels != 2) return hipErrorInvalidValue;
