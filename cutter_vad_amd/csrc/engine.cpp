@@ -1333,6 +1333,46 @@ int scan_mark_pending(vad_engine *e, hipStream_t s) {
     return VAD_OK;
 }
 
+// The way into a call that rebuilds tables of the engine's, with e->mu held and the call's rate settled: a device call works on the
+// caller's stream (NULL: the engine's), a host call on the engine's, and the launches of an earlier device call are waited for
+int call_begin(vad_engine *e, bool dev, void *stream, hipStream_t *s) {
+    *s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
+    HIP_TRY(e, hipSetDevice(e->device));
+    return scan_wait(e);
+}
+
+// ... and the way out behind its launches, whose status is `launched`.  A device call: the launches read the engine's tables and
+// buffers, so the next scan or cut waits for them, as behind vad_scan_device - after a failed launch too, whose status it returns
+// unless the marking itself fails.  A host call: the status first; behind VAD_OK its caller copies back and synchronises
+int call_end(vad_engine *e, bool dev, hipStream_t s, int launched) {
+    if (!dev) return launched;
+    if (int rc = scan_mark_pending(e, s)) return rc;
+    return launched;
+}
+
+// The tables one call keeps in one of the engine's device buffers, laid out once.  add() appends a table - host pointer, bytes - in
+// the order they lie, each at a multiple of 16 bytes (CutSeg and RenderWork hold 64-bit fields); reserve() is the buffer's one
+// ensure, copy() the uploads on `s`, and at<T>() a table's device pointer, so that the kernel arguments sum no bytes.  An empty
+// table is not copied and is nullptr; a table without a host pointer is room only.  Nothing is allocated: a call has few tables
+struct DevTables {
+    static constexpr int MAX = 6;
+    uint8_t *&buf; size_t &cap;
+    const void *host[MAX]; size_t bytes[MAX], off[MAX]; int n = 0; size_t total = 0;
+    int add(const void *p, size_t b) {
+        host[n] = p; bytes[n] = b; off[n] = total;
+        total += (b + 15) & ~(size_t)15;
+        return n++;
+    }
+    template <class T> int add(const std::vector<T> &v, size_t count) { return add(v.data(), sizeof(T) * count); }
+    int reserve(vad_engine *e) { return ensure(e, buf, cap, total); }
+    int copy(vad_engine *e, hipStream_t s) const {
+        for (int i = 0; i < n; ++i)
+            if (bytes[i] && host[i]) HIP_TRY(e, hipMemcpyAsync(buf + off[i], host[i], bytes[i], hipMemcpyHostToDevice, s));
+        return VAD_OK;
+    }
+    template <class T> T *at(int i) const { return bytes[i] ? reinterpret_cast<T *>(buf + off[i]) : nullptr; }
+};
+
 // the block in e->d_audio stays for a following cut with audio = NULL.  rate: 0 = a block at the engine's own rate (vad_scan_cut's),
 // else a RATE block of that input rate (vad_scan_rate_cut's: its positions and hop count samples at that rate)
 void set_resident(vad_engine *e, size_t bytes, int32_t channels, int fmt, int32_t rate) {
@@ -1718,7 +1758,8 @@ int vad_scan_rate_device(vad_engine *e, const vad_scan_ch_item *items, int64_t n
 // ---- finished segments cut out of a scanned block (vad_scan_cut, vad_scan_rate_cut) --------------------------------------
 namespace {
 
-static_assert(VAD_CUT_WG_SAMPLES == 4 * vadk::CUT_WG_QUADS, "the header's workgroup share is the kernel's");
+static_assert(VAD_CUT_WG_SAMPLES == 4 * vadk::CUT_WG_QUADS && VAD_RESAMPLE_CUT_WG_SAMPLES == vadk::RSC_WG_SAMPLES,
+              "the header's workgroup shares are the kernels'");
 
 // frame: the samples of one frame in the block; out_frame: the samples a frame has in a VAD_CUT_FRAMES payload
 int64_t cut_samples(int64_t frame, int64_t nframes, int64_t hop, int32_t layout, int64_t out_frame) {
@@ -1745,46 +1786,76 @@ int rate_cut_check(vad_engine *e, const char *who, int32_t sr_in, int *chunk) {
 struct CutSpan { int64_t lo, hi, i; };                           // the output samples [lo, hi) of segment i
 struct CutWin { uint32_t r0, r1; size_t seg0, work0, nwork; };   // rows [r0, r1) of a rate cut's frames: their part of the tables
 
-// What cut_run carries from one phase to the next; each phase is a function below, in the order it runs.  The tables themselves
-// are the engine's (e->cut_segs, e->cut_work: one entry per workgroup; e->cut_rows, e->cut_tiles: a rate cut's frames).
-// chunk > 0 (vad_scan_rate_cut / _device): the block is at sr_in and a frame in it is a chunk of `chunk` sample frames.
-// VAD_CUT_RANGE is then the same kernel on the input-rate block with the gate off (no input-rate sample was ever gated);
-// VAD_CUT_FRAMES (rate_frames) resamples the listed chunks window by window into e->d_win (vadk_cut_resample) and cuts each
-// window as a mono float32 block of back-to-back frames with the same kernel, which gates.
-struct CutPlan {
-    // the call
+// what a call of this family makes of its segments
+enum class CutKind {
+    PAYLOAD,        // vad_scan_cut, _rate_cut, _cut_gain, _cut_stereo: each segment's samples at its out_sample
+    LEVELS,         // vad_scan_levels: a vad_level record per segment, reduced where a cut stores
+    RENDER,         // vad_scan_render, _render_stereo: every output sample written; the ranges of two segments may overlap, three not
+    MEL,            // vad_scan_mel, vad_scan_mel_keep at the engine's rate: log-mel rows, the segments back to back
+    RESAMPLE,       // vad_scan_resample_cut: a rate block's segments at 16 kHz, at their out_sample
+    RESAMPLE_MEL    // vad_scan_rate_mel, vad_scan_mel_keep of a rate block: the rows of the segments resampled to 16 kHz
+};
+
+// The call as its entry point received it: cut_call fills the block arguments every call has, the entry point sets its own few
+// fields by name.  Nothing in it is derived; what the phases test is named below the fields.
+struct CutCall {
     const char *who; const vad_cut_item *items; int64_t n, audio_samples; int32_t channels; int fmt; int32_t hop; float thr;
-    int32_t layout, out_fmt; int64_t out_samples; int chunk; int32_t sr_in;
-    // vad_scan_cut_gain: a factor per segment (host), or nullptr.  vad_scan_levels: the call reduces where a cut stores - layout and
-    // out_fmt are the range once as float32, no item's out_sample is read, and `out` is the records
-    const float *gains; bool levels; float clip;
-    // vad_scan_render: the output ranges of two segments may overlap (three may not), every output sample is written, and a
-    // sample is faded by `ramp` (host, nramp entries) from both ends of its segment; layout is the range once
-    bool render; const float *ramp; int32_t nramp;
-    // vad_scan_cut_stereo / vad_scan_render_stereo: both channels of a two-channel block, interleaved.  Positions and counts stay
-    // sample FRAMES, so the tables are the mono call's: an output frame has twice the bytes (ob), and the launcher is another
-    bool stereo;
-    // vad_scan_mel: the segments are checked and tabled as for the levels (levels is set too); its workgroups are listed by mel_run
-    bool mel;
-    // vad_scan_resample_cut / vad_scan_rate_mel (a rate block, the range once): a segment's count is S16, its samples at 16 kHz - in
-    // the out_sample check, the spans and CutSeg::nquads - its input quads go to e->rsc_inq, and a workgroup has RSC_WG_SAMPLES outputs
-    bool resample;
+    CutKind kind = CutKind::PAYLOAD;
+    // the block's rate, settled on the way in (cut_enter; the resampling kinds: resample_cut_check): chunk > 0 - the block is
+    // at sr_in and a frame in it is a chunk of `chunk` sample frames; chunk = 0 - a block at the engine's rate, and sr_in is 0
+    int32_t sr_in = 0; int chunk = 0;
+    // every kind but PAYLOAD reads or writes the sample range once, as float32 where it has no out_fmt of its own
+    int32_t layout = VAD_CUT_RANGE, out_fmt = VAD_CUT_F32; int64_t out_samples = 0;
+    // a factor per segment (host array [n]) or nullptr; vad_scan_cut_gain refuses nullptr
+    const float *gains = nullptr; bool gains_required = false;
+    float clip = 0.0f;                                   // LEVELS
+    const float *ramp = nullptr; int32_t nramp = 0;      // RENDER: a sample is faded by `ramp` (host, nramp entries) from both ends of its segment
+    // both channels of a two-channel block, interleaved.  Positions and counts stay sample FRAMES, so the tables are the mono
+    // call's: an output frame has twice the bytes (CutPlan::ob), and the launcher is another
+    bool stereo = false;
+    const float *taps = nullptr; int32_t ntaps = 0;      // the resampling kinds
+    // the mel kinds.  keep (vad_scan_mel_keep): the rows stay in e->d_melk, the call has no output and no out_rows
+    const vad_mel *m = nullptr; const float *op_re = nullptr, *op_im = nullptr, *filters = nullptr; int64_t out_rows = 0;
+    bool keep = false; int64_t *rows_out = nullptr;
+
+    bool rate() const { return chunk > 0; }
+    // a rate block's frames resampled window by window into e->d_win (vadk_cut_resample), each window cut as a mono float32 block of
+    // back-to-back frames, which gates.  The range once of a rate block is the same kernel on the input-rate block with the gate off
+    bool rate_frames() const { return rate() && layout == VAD_CUT_FRAMES; }
+    bool resamples() const { return kind == CutKind::RESAMPLE || kind == CutKind::RESAMPLE_MEL; }
+    bool mel() const { return kind == CutKind::MEL || kind == CutKind::RESAMPLE_MEL; }
+    // the segments' samples go to the caller at each item's out_sample; without a payload no out_sample is read and segments may
+    // share samples
+    bool has_payload() const { return kind == CutKind::PAYLOAD || kind == CutKind::RENDER || kind == CutKind::RESAMPLE; }
+    // its workgroups follow the output, not the segments: render_regions lists them (mel: mel_tiles)
+    bool work_follows_output() const { return kind == CutKind::RENDER || kind == CutKind::MEL; }
+    bool records_out() const { return kind == CutKind::LEVELS; }     // the output is records, 8-byte aligned; else 16 bytes
+    float gate() const { return rate() && !rate_frames() ? -1.0f : thr; }    // no input-rate sample was ever gated
+};
+
+CutCall cut_call(const char *who, const vad_cut_item *items, int64_t n, int64_t audio_samples, int32_t channels, int fmt, int32_t hop, float thr) {
+    return CutCall{who, items, n, audio_samples, channels, fmt, hop, thr};
+}
+
+// What the phases of a call derive and carry from one to the next; each phase is a function below, in the order it runs.  The tables
+// themselves are the engine's (e->cut_segs, e->cut_work: one entry per workgroup; e->cut_rows, e->cut_tiles: a rate cut's frames).
+struct CutPlan {
+    const CutCall &k;
     // a. cut_check
-    bool rate, rate_frames;
-    uint32_t fshift;                         // log2 of the quads of a payload frame
-    int64_t rows;                            // rate_frames: the frames of all segments
-    size_t ab, ob;                           // bytes of the block, and of one output sample (stereo: sample frame)
+    uint32_t fshift = 0;                     // log2 of the quads of a payload frame
+    int64_t rows = 0;                        // rate_frames: the frames of all segments
+    size_t ab = 0, ob = 0;                   // bytes of the block, and of one output sample (stereo: sample frame)
     std::vector<CutSpan> spans;              // by lo
-    // b. cut_block_device / cut_block_host: the block the kernels read, and where they write
-    const void *d_audio; void *d_out;
+    // b. cut_block: the block the kernels read, and where they write
+    const void *d_audio = nullptr; void *d_out = nullptr;
     // c. cut_windows
-    vad_engine::ResampleOp *op; std::vector<CutWin> wins;
-    // d. cut_upload: bytes of the tables, which lie in e->d_cut in this order - segments, workgroups, rows, tiles
-    size_t sb, wb, rb, tb, gb;
+    vad_engine::ResampleOp *op = nullptr; std::vector<CutWin> wins;
+    // the mel kinds: the rows of all segments (mel_tiles) and their bytes (mel_output)
+    int64_t mel_rows = 0; size_t mel_bytes = 0;
 };
 
 // vad_scan_render's own arguments, between the block's checks and the items': the output's length and the ramp
-int render_check(vad_engine *e, const CutPlan &c) {
+int render_check(vad_engine *e, const CutCall &c) {
     const char *who = c.who;
     if (c.out_samples & 3)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_samples = %lld must be a multiple of 4", who, (long long)c.out_samples);
@@ -1803,45 +1874,46 @@ int render_check(vad_engine *e, const CutPlan &c) {
 // listed per window, by cut_windows) and the output spans.  Writes nothing to the device.  A call without segments (n == 0) is
 // done behind the checks of its own arguments
 int cut_check(vad_engine *e, CutPlan &c) {
-    const char *who = c.who;
-    const int64_t n = c.n, audio_samples = c.audio_samples, hop = c.hop;
-    if (n < 0 || audio_samples < 0 || c.out_samples < 0 || (n > 0 && !c.items))
+    const CutCall &k = c.k;
+    const char *who = k.who;
+    const int64_t n = k.n, audio_samples = k.audio_samples, hop = k.hop;
+    if (n < 0 || audio_samples < 0 || k.out_samples < 0 || (n > 0 && !k.items))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer or bad count", who);
-    if (int rc = check_block_format(e, who, c.fmt, c.channels)) return rc;
-    if (c.stereo && c.channels != 2)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: channels = %d: two-channel blocks only", who, c.channels);
-    if (c.layout != VAD_CUT_FRAMES && c.layout != VAD_CUT_RANGE)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: layout = %d is neither VAD_CUT_FRAMES nor VAD_CUT_RANGE", who, c.layout);
+    if (int rc = check_block_format(e, who, k.fmt, k.channels)) return rc;
+    if (k.stereo && k.channels != 2)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: channels = %d: two-channel blocks only", who, k.channels);
+    if (k.layout != VAD_CUT_FRAMES && k.layout != VAD_CUT_RANGE)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: layout = %d is neither VAD_CUT_FRAMES nor VAD_CUT_RANGE", who, k.layout);
     // two resampled rows per chunk would have to pass vadk_cut_resample's window: not built
-    if (c.stereo && c.chunk > 0 && c.layout == VAD_CUT_FRAMES)
+    if (k.stereo && k.chunk > 0 && k.layout == VAD_CUT_FRAMES)
         return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s: VAD_CUT_FRAMES on a block at %d Hz: both channels of resampled frames "
-                       "are not supported, VAD_CUT_RANGE is", who, c.sr_in);
-    if (c.out_fmt != VAD_CUT_PCM16 && c.out_fmt != VAD_CUT_F32)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_fmt = %d is neither VAD_CUT_PCM16 nor VAD_CUT_F32", who, c.out_fmt);
-    if (int rc = check_block_extent(e, who, c.hop, audio_samples, c.channels, c.fmt)) return rc;
-    if (c.levels && c.clip != c.clip)
+                       "are not supported, VAD_CUT_RANGE is", who, k.sr_in);
+    if (k.out_fmt != VAD_CUT_PCM16 && k.out_fmt != VAD_CUT_F32)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_fmt = %d is neither VAD_CUT_PCM16 nor VAD_CUT_F32", who, k.out_fmt);
+    if (int rc = check_block_extent(e, who, k.hop, audio_samples, k.channels, k.fmt)) return rc;
+    if (k.kind == CutKind::LEVELS && k.clip != k.clip)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: clip_thresh is NaN", who);
-    if (c.render)
-        if (int rc = render_check(e, c)) return rc;
-    c.ab = (size_t)audio_samples * (size_t)c.channels * sample_bytes(c.fmt);
-    c.ob = (size_t)(c.out_fmt == VAD_CUT_PCM16 ? 2 : 4) * (c.stereo ? 2 : 1);
+    if (k.kind == CutKind::RENDER)
+        if (int rc = render_check(e, k)) return rc;
+    c.ab = (size_t)audio_samples * (size_t)k.channels * sample_bytes(k.fmt);
+    c.ob = (size_t)(k.out_fmt == VAD_CUT_PCM16 ? 2 : 4) * (k.stereo ? 2 : 1);
     if (n == 0) return VAD_OK;
-    c.rate = c.chunk > 0;
-    c.rate_frames = c.rate && c.layout == VAD_CUT_FRAMES;
-    const int64_t frame = c.rate ? c.chunk : e->frame_samples, out_frame = c.rate ? VAD_FRAME_SAMPLES : frame;
+    const bool resamples = k.resamples(), has_payload = k.has_payload(), rate_frames = k.rate_frames();
+    const uint32_t wg_quads = resamples ? VAD_RESAMPLE_CUT_WG_SAMPLES / 4 : vadk::CUT_WG_QUADS;      // the output quads of a workgroup
+    const int64_t frame = k.rate() ? k.chunk : e->frame_samples, out_frame = k.rate() ? VAD_FRAME_SAMPLES : frame;
     const uint32_t frameq = (uint32_t)out_frame >> 2;
     while ((1u << c.fshift) < frameq) ++c.fshift;
     // the kernel finds a quad's frame with a shift and a mask: 512 and 256 samples today (the sample range once needs neither:
     // chunks of 768 and 1536 samples pass)
-    if (c.layout == VAD_CUT_FRAMES && ((out_frame & 3) || (1u << c.fshift) != frameq))
+    if (k.layout == VAD_CUT_FRAMES && ((out_frame & 3) || (1u << c.fshift) != frameq))
         return e->fail(VAD_ERR_UNSUPPORTED, "Model prediction failed: %s: frames of %lld samples: the cut kernel needs a power of two", who, (long long)out_frame);
     c.spans.resize((size_t)n);
     e->cut_segs.resize((size_t)n);
     e->cut_work.clear();
     e->cut_rows.clear();
-    if (c.resample) e->rsc_inq.resize((size_t)n);
+    if (resamples) e->rsc_inq.resize((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
-        const vad_cut_item &it = c.items[i];
+        const vad_cut_item &it = k.items[i];
         if (it.sample_offset < 0 || (it.sample_offset & 3))
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: its recording starts at sample %lld, not a multiple of 4", who,
                            (long long)i, (long long)it.sample_offset);
@@ -1853,108 +1925,102 @@ int cut_check(vad_engine *e, CutPlan &c) {
             it.sample_offset + (it.first_frame + it.nframes - 1) * hop + frame > audio_samples)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld (recording at %lld, frames %lld .. +%lld) leaves the audio block of %lld samples",
                            who, (long long)i, (long long)it.sample_offset, (long long)it.first_frame, (long long)it.nframes, (long long)audio_samples);
-        if (c.stereo && it.channel != VAD_SCAN_BOTH)
+        if (k.stereo && it.channel != VAD_SCAN_BOTH)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld names channel %d: both channels are written, "
                            "an item's channel is VAD_SCAN_BOTH", who, (long long)i, it.channel);
-        if (!c.stereo && it.channel != VAD_SCAN_MIX && (it.channel < 0 || it.channel >= c.channels))
+        if (!k.stereo && it.channel != VAD_SCAN_MIX && (it.channel < 0 || it.channel >= k.channels))
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld names channel %d of %d (0 .. channels - 1, or VAD_SCAN_MIX)", who,
-                           (long long)i, it.channel, c.channels);
+                           (long long)i, it.channel, k.channels);
         if (it.reserved != 0)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: reserved = %d must be 0", who, (long long)i, it.reserved);
-        const int64_t s_in = cut_samples(frame, it.nframes, hop, c.layout, out_frame);
-        const int64_t count = c.resample ? (s_in * vadk::rsc_L(c.sr_in) / vadk::rsc_M(c.sr_in)) & ~(int64_t)3 : s_in;
-        if (!c.levels && (it.out_sample < 0 || (it.out_sample & 3) || it.out_sample > c.out_samples || count > c.out_samples - it.out_sample))
+        const int64_t s_in = cut_samples(frame, it.nframes, hop, k.layout, out_frame);
+        const int64_t count = resamples ? (s_in * vadk::rsc_L(k.sr_in) / vadk::rsc_M(k.sr_in)) & ~(int64_t)3 : s_in;
+        if (has_payload && (it.out_sample < 0 || (it.out_sample & 3) || it.out_sample > k.out_samples || count > k.out_samples - it.out_sample))
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: out_sample = %lld (+%lld samples) must be a multiple of 4 inside "
-                           "the output of %lld samples", who, (long long)i, (long long)it.out_sample, (long long)count, (long long)c.out_samples);
+                           "the output of %lld samples", who, (long long)i, (long long)it.out_sample, (long long)count, (long long)k.out_samples);
         if (count >= (int64_t)4 << 31)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld has %lld output samples, a segment may have less than 2^33", who,
                            (long long)i, (long long)count);
-        if (c.gains && !std::isfinite(c.gains[i]))
+        if (k.gains && !std::isfinite(k.gains[i]))
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld: its gain is %s, a gain is a finite number", who, (long long)i,
-                           std::isnan(c.gains[i]) ? "NaN" : "infinite");
+                           std::isnan(k.gains[i]) ? "NaN" : "infinite");
         c.spans[(size_t)i] = CutSpan{it.out_sample, it.out_sample + count, i};
-        const uint32_t mode = c.channels == 1 || c.stereo ? vadk::SCAN_LEFT : it.channel == VAD_SCAN_MIX ? vadk::SCAN_MIX : (uint32_t)it.channel;
+        const uint32_t mode = k.channels == 1 || k.stereo ? vadk::SCAN_LEFT : it.channel == VAD_SCAN_MIX ? vadk::SCAN_MIX : (uint32_t)it.channel;
         const uint32_t nq = (uint32_t)(count >> 2);
         e->cut_segs[(size_t)i] = vadk::CutSeg{(uint32_t)((it.sample_offset + it.first_frame * hop) >> 2) | (mode << vadk::SCAN_MODE_SHIFT), nq,
-                                              c.levels ? 0u : (uint64_t)it.out_sample >> 2};
-        if (c.rate_frames) {
+                                              has_payload ? (uint64_t)it.out_sample >> 2 : 0u};
+        if (rate_frames) {
             e->cut_rows.push_back(vadk::CutResampleSeg{e->cut_segs[(size_t)i].quad_in, (uint32_t)c.rows});
             c.rows += it.nframes;
             if (c.rows > INT32_MAX)
                 return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 frames in one call", who);
             continue;
         }
-        if (c.resample) {
-            e->rsc_inq[(size_t)i] = (uint32_t)(s_in >> 2);
-            for (uint32_t q = 0; q < nq; q += vadk::RSC_WG_SAMPLES / 4) e->cut_work.push_back(vadk::CutWork{(uint32_t)i, q});
-            if (e->cut_work.size() > (size_t)INT32_MAX)
-                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d samples in one call", who,
-                               VAD_RESAMPLE_CUT_WG_SAMPLES);
-            continue;
-        }
-        if (c.render || c.mel) continue;     // its workgroups follow the output, not the segments: render_regions (mel: the tiles)
-        for (uint32_t q = 0; q < nq; q += vadk::CUT_WG_QUADS) e->cut_work.push_back(vadk::CutWork{(uint32_t)i, q});
+        if (resamples) e->rsc_inq[(size_t)i] = (uint32_t)(s_in >> 2);
+        if (k.work_follows_output()) continue;
+        for (uint32_t q = 0; q < nq; q += wg_quads) e->cut_work.push_back(vadk::CutWork{(uint32_t)i, q});
         if (e->cut_work.size() > (size_t)INT32_MAX)
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d samples in one call", who, VAD_CUT_WG_SAMPLES);
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d samples in one call", who,
+                           (int)(4 * wg_quads));
     }
-    if (c.gains) e->cut_gains.assign(c.gains, c.gains + n);
-    if (c.levels) c.spans.clear();           // no payload: segments may share samples
+    if (k.gains) e->cut_gains.assign(k.gains, k.gains + n);
+    if (!has_payload) c.spans.clear();       // segments may share samples
     std::sort(c.spans.begin(), c.spans.end(), [](const CutSpan &a, const CutSpan &b) { return a.lo < b.lo; });
-    for (size_t k = 1; k < c.spans.size() && !c.render; ++k)
-        if (c.spans[k].lo < c.spans[k - 1].hi)
+    for (size_t j = 1; j < c.spans.size() && k.kind != CutKind::RENDER; ++j)     // a render: render_regions refuses three
+        if (c.spans[j].lo < c.spans[j - 1].hi)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output ranges of segments %lld and %lld overlap", who,
-                           (long long)c.spans[k - 1].i, (long long)c.spans[k].i);
+                           (long long)c.spans[j - 1].i, (long long)c.spans[j].i);
     return VAD_OK;
 }
 
-// b. the block the call reads and the output it writes.  A device call: the caller's two pointers
-int cut_block_device(vad_engine *e, CutPlan &c, const void *d_audio, void *d_out) {
-    if (!d_audio) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", c.who);
-    if (int rc = check_device_audio(e, c.who, d_audio, c.channels)) return rc;
-    if (c.levels && !c.mel && (reinterpret_cast<uintptr_t>(d_out) & 7))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the levels must be 8-byte aligned", c.who);
-    if ((!c.levels || c.mel) && (reinterpret_cast<uintptr_t>(d_out) & 15))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output must be 16-byte aligned", c.who);
-    c.d_audio = d_audio;
-    c.d_out = d_out;
-    return VAD_OK;
-}
-
-// ... a host call: e->d_audio - the resident block (audio = NULL: what the last scan or cut uploaded is still in device memory and
-// crosses the link once; a rate block is none of vad_scan_cut's, and the other way round), or room for the upload - and e->d_cut_out
-int cut_block_host(vad_engine *e, CutPlan &c, const void *audio) {
-    const char *who = c.who;
+// b. the block the call reads and the output it writes.  A device call: the caller's two pointers.  A host call: e->d_audio - the
+// resident block (audio = NULL: what the last scan or cut uploaded is still in device memory and crosses the link once; a rate block
+// is none of vad_scan_cut's, and the other way round), or room for the upload - and e->d_cut_out
+int cut_block(vad_engine *e, CutPlan &c, bool dev, const void *audio, void *out) {
+    const CutCall &k = c.k;
+    const char *who = k.who;
+    if (dev) {
+        if (!audio) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+        if (int rc = check_device_audio(e, who, audio, k.channels)) return rc;
+        if (k.records_out() && (reinterpret_cast<uintptr_t>(out) & 7))
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the levels must be 8-byte aligned", who);
+        if (!k.records_out() && (reinterpret_cast<uintptr_t>(out) & 15))
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output must be 16-byte aligned", who);
+        c.d_audio = audio;
+        c.d_out = out;
+        return VAD_OK;
+    }
     if (!audio) {
-        if (!c.rate && (!e->audio_resident || e->audio_rate != 0))
+        if (!k.rate() && (!e->audio_resident || e->audio_rate != 0))
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the engine holds no resident block: no vad_scan or "
                            "vad_scan_channels has uploaded one", who);
-        if (c.rate && (!e->audio_resident || e->audio_rate == 0))
+        if (k.rate() && (!e->audio_resident || e->audio_rate == 0))
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the engine holds no resident rate block: no "
                            "vad_scan_rate_segments or vad_scan_rate_cut has uploaded one", who);
-        if (c.rate && e->audio_rate != c.sr_in)
+        if (k.rate() && e->audio_rate != k.sr_in)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the resident block has sample rate %d, not %d", who,
-                           e->audio_rate, c.sr_in);
-        if (e->audio_fmt != c.fmt)
+                           e->audio_rate, k.sr_in);
+        if (e->audio_fmt != k.fmt)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the resident block has frame format %d, not %d", who,
-                           e->audio_fmt, c.fmt);
-        if (e->audio_channels != c.channels)
+                           e->audio_fmt, k.fmt);
+        if (e->audio_channels != k.channels)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the resident block has %d channels, not %d", who,
-                           e->audio_channels, c.channels);
+                           e->audio_channels, k.channels);
         if (e->audio_bytes != c.ab)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: audio = NULL, and the resident block has %llu bytes, not the %llu of "
-                           "%lld samples", who, (unsigned long long)e->audio_bytes, (unsigned long long)c.ab, (long long)c.audio_samples);
+                           "%lld samples", who, (unsigned long long)e->audio_bytes, (unsigned long long)c.ab, (long long)k.audio_samples);
     } else {
         e->audio_resident = false;
         if (int rc = ensure(e, e->d_audio, e->d_audio_cap, c.ab + 16)) return rc;
     }
     c.d_audio = e->d_audio;
-    if (c.mel) return VAD_OK;                // the rows of all segments: mel_run sizes them
-    if (c.levels) {
-        if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, (size_t)c.n * sizeof(vad_level))) return rc;
+    if (k.mel()) return VAD_OK;              // the rows of all segments: mel_output sizes them
+    if (k.records_out()) {
+        if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, (size_t)k.n * sizeof(vad_level))) return rc;
         c.d_out = e->d_cut_out;
         return VAD_OK;
     }
-    if (c.render) return VAD_OK;             // the whole output, from sample 0: render_run sizes it
+    if (k.kind == CutKind::RENDER) return VAD_OK;    // the whole output, from sample 0: render_run sizes it
     const int64_t out_lo = c.spans.front().lo, out_hi = c.spans.back().hi;
     if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, (size_t)(out_hi - out_lo) * c.ob)) return rc;
     c.d_out = e->d_cut_out;
@@ -1967,7 +2033,7 @@ int cut_block_host(vad_engine *e, CutPlan &c, const void *audio) {
 // the call, window), with its place in the window and in the output - and workgroups; per tile of the call the segment that owns
 // its first row (vad_layout.h: CutResampleArgs)
 int cut_windows(vad_engine *e, CutPlan &c) {
-    if (int rc = get_resample_op(e, c.chunk, &c.op)) return rc;
+    if (int rc = get_resample_op(e, c.k.chunk, &c.op)) return rc;
     const uint32_t total = (uint32_t)c.rows, wr = cut_window_rows(e);
     std::vector<vadk::CutSeg> wsegs;
     std::vector<float> wgains;               // a window's segment carries its call segment's gain
@@ -1977,11 +2043,11 @@ int cut_windows(vad_engine *e, CutPlan &c) {
     for (uint32_t r0 = 0; r0 < total; r0 += wr) {
         const uint32_t r1 = (uint32_t)std::min<uint64_t>(total, (uint64_t)r0 + wr);
         CutWin w{r0, r1, wsegs.size(), e->cut_work.size(), 0};
-        while (si < (size_t)c.n && cr[si].row0 < r1) {
+        while (si < (size_t)c.k.n && cr[si].row0 < r1) {
             const uint32_t lo = std::max(cr[si].row0, r0), hi = std::min(cr[si + 1].row0, r1), nq = (hi - lo) * 128u;
             const uint32_t local = (uint32_t)(wsegs.size() - w.seg0);
             wsegs.push_back(vadk::CutSeg{(lo - r0) * 128u, nq, e->cut_segs[si].quad_out + (uint64_t)(lo - cr[si].row0) * 128u});
-            if (c.gains) wgains.push_back(e->cut_gains[si]);
+            if (c.k.gains) wgains.push_back(e->cut_gains[si]);
             for (uint32_t q = 0; q < nq; q += vadk::CUT_WG_QUADS) e->cut_work.push_back(vadk::CutWork{local, q});
             if (cr[si + 1].row0 > r1) break;     // the segment goes on in the next window
             ++si;
@@ -1996,60 +2062,59 @@ int cut_windows(vad_engine *e, CutPlan &c) {
         e->cut_tiles[t] = (uint32_t)si;
     }
     e->cut_segs.swap(wsegs);
-    if (c.gains) e->cut_gains.swap(wgains);
+    if (c.k.gains) e->cut_gains.swap(wgains);
     return ensure(e, e->d_win, e->d_win_cap, (size_t)std::min(total, wr) * 2048u);
 }
 
-// d. the first writes: host audio (which becomes the resident block, of the call's rate) and the tables, on `s` ...
-int cut_upload(vad_engine *e, CutPlan &c, const void *audio, hipStream_t s) {
-    c.sb = sizeof(vadk::CutSeg) * e->cut_segs.size();
-    c.wb = sizeof(vadk::CutWork) * e->cut_work.size();
-    c.rb = sizeof(vadk::CutResampleSeg) * e->cut_rows.size();
-    c.tb = c.rate_frames ? sizeof(uint32_t) * e->cut_tiles.size() : 0;
-    c.gb = c.gains ? sizeof(float) * e->cut_gains.size() : 0;
-    if (int rc = ensure(e, e->d_cut, e->d_cut_cap, c.sb + c.wb + c.rb + c.tb + c.gb)) return rc;
-    if (audio) {
-        HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, c.ab, hipMemcpyHostToDevice, s));
-        set_resident(e, c.ab, c.channels, c.fmt, c.rate ? c.sr_in : 0);
-    }
-    HIP_TRY(e, hipMemcpyAsync(e->d_cut, e->cut_segs.data(), c.sb, hipMemcpyHostToDevice, s));
-    HIP_TRY(e, hipMemcpyAsync(e->d_cut + c.sb, e->cut_work.data(), c.wb, hipMemcpyHostToDevice, s));
-    if (c.rate_frames) {
-        HIP_TRY(e, hipMemcpyAsync(e->d_cut + c.sb + c.wb, e->cut_rows.data(), c.rb, hipMemcpyHostToDevice, s));
-        HIP_TRY(e, hipMemcpyAsync(e->d_cut + c.sb + c.wb + c.rb, e->cut_tiles.data(), c.tb, hipMemcpyHostToDevice, s));
-    }
-    if (c.gains) HIP_TRY(e, hipMemcpyAsync(e->d_cut + c.sb + c.wb + c.rb + c.tb, e->cut_gains.data(), c.gb, hipMemcpyHostToDevice, s));
-    if (c.levels) HIP_TRY(e, hipMemsetAsync(c.d_out, 0, (size_t)c.n * sizeof(vad_level), s));
+// The one place that says what e->d_audio holds: a host call's audio goes up on `s` and becomes the resident block, of the call's
+// rate.  Every ensure and every refusal of the call lies before it
+int cut_upload_audio(vad_engine *e, const CutPlan &c, bool dev, const void *audio, hipStream_t s) {
+    if (dev || !audio || c.k.n == 0) return VAD_OK;
+    HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, c.ab, hipMemcpyHostToDevice, s));
+    set_resident(e, c.ab, c.k.channels, c.k.fmt, c.k.sr_in);
+    return VAD_OK;
+}
+
+// d. the first writes, on `s`: host audio and the tables, which lie in e->d_cut (`t`) in the order of the names ...
+enum { CUT_SEGS, CUT_WORK, CUT_ROWS, CUT_TILES, CUT_GAINS };
+int cut_upload(vad_engine *e, const CutPlan &c, DevTables &t, bool dev, const void *audio, hipStream_t s) {
+    const CutCall &k = c.k;
+    t.add(e->cut_segs, e->cut_segs.size());
+    t.add(e->cut_work, e->cut_work.size());
+    t.add(e->cut_rows, k.rate_frames() ? e->cut_rows.size() : 0);
+    t.add(e->cut_tiles, k.rate_frames() ? e->cut_tiles.size() : 0);
+    t.add(e->cut_gains, k.gains ? e->cut_gains.size() : 0);
+    if (int rc = t.reserve(e)) return rc;
+    if (int rc = cut_upload_audio(e, c, dev, audio, s)) return rc;
+    if (int rc = t.copy(e, s)) return rc;
+    if (k.records_out()) HIP_TRY(e, hipMemsetAsync(c.d_out, 0, (size_t)k.n * sizeof(vad_level), s));
     return VAD_OK;
 }
 
 // ... and the launches: one cut, or per window of a rate cut's frames the resampler and the cut of what it wrote
-int cut_launches(vad_engine *e, const CutPlan &c, hipStream_t s) {
+int cut_launches(vad_engine *e, const CutPlan &c, const DevTables &t, hipStream_t s) {
+    const CutCall &k = c.k;
+    const float *d_gains = t.at<const float>(CUT_GAINS);
     vadk::CutArgs a{};
     a.audio = c.d_audio;
     a.out = c.d_out;
-    a.segs = reinterpret_cast<const vadk::CutSeg *>(e->d_cut);
-    a.work = reinterpret_cast<const vadk::CutWork *>(e->d_cut + c.sb);
+    a.segs = t.at<const vadk::CutSeg>(CUT_SEGS);
+    a.work = t.at<const vadk::CutWork>(CUT_WORK);
     a.audio_bytes = (uint32_t)c.ab;
     a.nwork = (uint32_t)e->cut_work.size();
-    a.hopq = (uint32_t)c.hop >> 2;
-    a.frame_shift = c.layout == VAD_CUT_FRAMES ? c.fshift : 31u;
-    a.fmt = c.fmt;
-    a.channels = c.channels;
-    a.out_fmt = c.out_fmt;
-    a.thresh = c.rate && !c.rate_frames ? -1.0f : c.thr;
-    const float *d_gains = reinterpret_cast<const float *>(e->d_cut + c.sb + c.wb + c.rb + c.tb);
-    if (c.levels) {
-        const hipError_t r = vadk_launch_seg_levels(&a, c.clip, s);
-        if (r != hipSuccess) return e->hip_fail(r, "kernel launch (segment levels)");
-        return VAD_OK;
-    }
-    if (!c.rate_frames) {
-        const hipError_t r = c.stereo  ? vadk_launch_scan_cut_stereo(&a, c.gains ? d_gains : nullptr, s)
-                             : c.gains ? vadk_launch_scan_cut_gain(&a, d_gains, s)
-                                       : vadk_launch_scan_cut(&a, s);
-        if (r != hipSuccess) return e->hip_fail(r, "kernel launch (scan cut)");
-        return VAD_OK;
+    a.hopq = (uint32_t)k.hop >> 2;
+    a.frame_shift = k.layout == VAD_CUT_FRAMES ? c.fshift : 31u;
+    a.fmt = k.fmt;
+    a.channels = k.channels;
+    a.out_fmt = k.out_fmt;
+    a.thresh = k.gate();
+    if (!k.rate_frames()) {
+        const bool levels = k.kind == CutKind::LEVELS;
+        const hipError_t r = levels    ? vadk_launch_seg_levels(&a, k.clip, s)
+                             : k.stereo ? vadk_launch_scan_cut_stereo(&a, d_gains, s)
+                             : d_gains  ? vadk_launch_scan_cut_gain(&a, d_gains, s)
+                                        : vadk_launch_scan_cut(&a, s);
+        return r != hipSuccess ? e->hip_fail(r, levels ? "kernel launch (segment levels)" : "kernel launch (scan cut)") : VAD_OK;
     }
     vadk::CutResampleArgs ra{};
     ra.wstream = c.op->d_w;
@@ -2058,13 +2123,13 @@ int cut_launches(vad_engine *e, const CutPlan &c, hipStream_t s) {
     ra.row128_block = c.op->row128_block;
     ra.audio_bytes = (uint32_t)c.ab;
     ra.audio = c.d_audio;
-    ra.segs = reinterpret_cast<const vadk::CutResampleSeg *>(e->d_cut + c.sb + c.wb);
-    ra.tile_seg = reinterpret_cast<const uint32_t *>(e->d_cut + c.sb + c.wb + c.rb);
+    ra.segs = t.at<const vadk::CutResampleSeg>(CUT_ROWS);
+    ra.tile_seg = t.at<const uint32_t>(CUT_TILES);
     ra.win = e->d_win;
-    ra.n_in = c.chunk;
-    ra.hopq = (uint32_t)c.hop >> 2;
-    ra.fmt = c.fmt;
-    ra.channels = c.channels;
+    ra.n_in = k.chunk;
+    ra.hopq = (uint32_t)k.hop >> 2;
+    ra.fmt = k.fmt;
+    ra.channels = k.channels;
     // the window as the cut kernel sees it: mono float32 frames of 512 samples, back to back
     a.audio = e->d_win;
     a.hopq = VAD_FRAME_SAMPLES / 4;
@@ -2075,11 +2140,12 @@ int cut_launches(vad_engine *e, const CutPlan &c, hipStream_t s) {
         ra.rows_end = w.r1;
         hipError_t r = vadk_launch_cut_resample(&ra, s);
         if (r != hipSuccess) return e->hip_fail(r, "kernel launch (cut resample)");
-        a.segs = reinterpret_cast<const vadk::CutSeg *>(e->d_cut) + w.seg0;
-        a.work = reinterpret_cast<const vadk::CutWork *>(e->d_cut + c.sb) + w.work0;
+        // the window's slices of the same tables
+        a.segs = t.at<const vadk::CutSeg>(CUT_SEGS) + w.seg0;
+        a.work = t.at<const vadk::CutWork>(CUT_WORK) + w.work0;
         a.nwork = (uint32_t)w.nwork;
         a.audio_bytes = (w.r1 - w.r0) * 2048u;
-        r = c.gains ? vadk_launch_scan_cut_gain(&a, d_gains + w.seg0, s) : vadk_launch_scan_cut(&a, s);
+        r = d_gains ? vadk_launch_scan_cut_gain(&a, d_gains + w.seg0, s) : vadk_launch_scan_cut(&a, s);
         if (r != hipSuccess) return e->hip_fail(r, "kernel launch (scan cut)");
     }
     return VAD_OK;
@@ -2088,8 +2154,8 @@ int cut_launches(vad_engine *e, const CutPlan &c, hipStream_t s) {
 // e. a host call: only speech crosses the link back - one copy per run of adjoining segments (packed payloads: one), the gaps stay
 // the caller's
 int cut_copy_back(vad_engine *e, const CutPlan &c, void *out, hipStream_t s) {
-    if (c.levels) {
-        HIP_TRY(e, hipMemcpyAsync(out, c.d_out, (size_t)c.n * sizeof(vad_level), hipMemcpyDeviceToHost, s));
+    if (c.k.records_out()) {
+        HIP_TRY(e, hipMemcpyAsync(out, c.d_out, (size_t)c.k.n * sizeof(vad_level), hipMemcpyDeviceToHost, s));
         HIP_TRY(e, hipStreamSynchronize(s));
         return VAD_OK;
     }
@@ -2106,34 +2172,22 @@ int cut_copy_back(vad_engine *e, const CutPlan &c, void *out, hipStream_t s) {
     return VAD_OK;
 }
 
-// vad_scan_cut and vad_scan_rate_cut (dev = false: host audio, or NULL = the resident block, and a host `out`) and their _device
-// forms, with e->mu held.  Every check comes before the first write: phases a to c refuse or size buffers, cut_upload writes first.
-// vad_scan_cut_gain (with_gains: `gains` is the host array [n], a factor per segment, which the gained kernel applies) and
-// vad_scan_levels (levels: `out` is n vad_level records, cleared on the stream ahead of the reducing kernel) ride the same phases.
-int cut_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples,
-            int32_t channels, int fmt, int32_t hop, float thr, int32_t layout, int32_t out_fmt, void *out, int64_t out_samples, void *stream,
-            int chunk = 0, int32_t sr_in = 0, const float *gains = nullptr, bool with_gains = false, bool levels = false, float clip = 0.0f,
-            bool stereo = false) {
-    hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
-    CutPlan c{who, items, n, audio_samples, channels, fmt, hop, thr, layout, out_fmt, out_samples, chunk, sr_in, gains, levels, clip};
-    c.stereo = stereo;
-    if (with_gains && n > 0 && !gains) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null gains", who);
+// The PAYLOAD and LEVELS kinds (dev = false: host audio, or NULL = the resident block, and a host `out`; dev: two device pointers),
+// with e->mu held.  Every check comes before the first write: phases a to c refuse or size buffers, cut_upload writes first.  A
+// gained cut's kernel applies the factors; the levels' `out` is n vad_level records, cleared on the stream ahead of the reducing kernel
+int cut_run(vad_engine *e, bool dev, const CutCall &k, const void *audio, void *out, hipStream_t s) {
+    CutPlan c{k};
+    if (k.gains_required && k.n > 0 && !k.gains) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null gains", k.who);
     if (int rc = cut_check(e, c)) return rc;
-    if (n == 0) return VAD_OK;
-    if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    if (int rc = dev ? cut_block_device(e, c, audio, out) : cut_block_host(e, c, audio)) return rc;
-    if (c.rate_frames)
+    if (k.n == 0) return VAD_OK;
+    if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", k.who);
+    if (int rc = cut_block(e, c, dev, audio, out)) return rc;
+    if (k.rate_frames())
         if (int rc = cut_windows(e, c)) return rc;
-    if (int rc = cut_upload(e, c, dev ? nullptr : audio, s)) return rc;
-    const int rc = cut_launches(e, c, s);
-    if (dev) {
-        // the launches read the engine's tables: the next scan or cut waits for them, as behind vad_scan_device
-        if (int rc2 = scan_mark_pending(e, s)) return rc2;
-        return rc;
-    }
-    if (rc) return rc;
+    DevTables t{e->d_cut, e->d_cut_cap};
+    if (int rc = cut_upload(e, c, t, dev, audio, s)) return rc;
+    const int rc = call_end(e, dev, s, cut_launches(e, c, t, s));
+    if (rc || dev) return rc;
     return cut_copy_back(e, c, out, s);
 }
 
@@ -2160,7 +2214,7 @@ int render_regions(vad_engine *e, const CutPlan &c) {
         return true;
     };
     auto too_many = [&]() {
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d samples in one call", c.who, VAD_CUT_WG_SAMPLES);
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d samples in one call", c.k.who, VAD_CUT_WG_SAMPLES);
     };
     size_t is = 0, ie = 0;
     while (ie < ends.size()) {
@@ -2169,7 +2223,7 @@ int render_regions(vad_engine *e, const CutPlan &c) {
             if (!emit(sp.lo)) return too_many();
             if (nopen == 2)
                 return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: output sample %lld is covered by the segments %lld, %lld and %lld, "
-                               "at most two may overlap", c.who, (long long)sp.lo, (long long)open[0], (long long)open[1], (long long)sp.i);
+                               "at most two may overlap", c.k.who, (long long)sp.lo, (long long)open[0], (long long)open[1], (long long)sp.i);
             open[nopen++] = sp.i;
         } else {
             const CutSpan &sp = ends[ie++];
@@ -2178,75 +2232,57 @@ int render_regions(vad_engine *e, const CutPlan &c) {
             --nopen;
         }
     }
-    if (!emit(c.out_samples)) return too_many();
+    if (!emit(c.k.out_samples)) return too_many();
     return VAD_OK;
 }
 
-// vad_scan_render / _device with e->mu held: cut_check's refusals under this name (without the overlap of two), the regions, then
-// the block and the output as the cuts find them, one upload of the tables - segments, ramp, workgroups, gains, in this order in
-// e->d_cut - and one launch, which writes every quad of the output: the gaps are zeroed by workgroups of the same launch (no
-// memset per gap, and no second pass over the samples a memset of the whole output would cost).
-int render_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const float *gains, const float *ramp, int32_t nramp,
-               const void *audio, int64_t audio_samples, int32_t channels, int fmt, int32_t sr_in, int chunk, int32_t hop, float thr, int32_t out_fmt,
-               void *out, int64_t out_samples, void *stream, bool stereo = false) {
-    hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
-    CutPlan c{who, items, n, audio_samples, channels, fmt, hop, thr, VAD_CUT_RANGE, out_fmt, out_samples, chunk, sr_in, gains, false, 0.0f, true, ramp, nramp,
-              stereo};
+// The RENDER kind with e->mu held: cut_check's refusals under this name (without the overlap of two), the regions, then the block
+// and the output as the cuts find them, one upload of the tables - segments, ramp, workgroups, gains, in this order in e->d_cut -
+// and one launch, which writes every quad of the output: the gaps are zeroed by workgroups of the same launch (no memset per gap,
+// and no second pass over the samples a memset of the whole output would cost).
+int render_run(vad_engine *e, bool dev, const CutCall &k, const void *audio, void *out, hipStream_t s) {
+    CutPlan c{k};
     if (int rc = cut_check(e, c)) return rc;
-    if (n == 0) e->cut_segs.clear();
+    if (k.n == 0) e->cut_segs.clear();
     if (int rc = render_regions(e, c)) return rc;
-    if (out_samples == 0) return VAD_OK;
-    if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    if (dev) {
-        if (n > 0) {
-            if (int rc = cut_block_device(e, c, audio, out)) return rc;
-        } else if (reinterpret_cast<uintptr_t>(out) & 15) {
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output must be 16-byte aligned", who);
-        }
-        c.d_out = out;
-    } else {
-        if (n > 0)
-            if (int rc = cut_block_host(e, c, audio)) return rc;
-        if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, (size_t)out_samples * c.ob)) return rc;
+    if (k.out_samples == 0) return VAD_OK;
+    if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", k.who);
+    // a render without segments reads no block: only its output is looked at
+    if (k.n > 0) {
+        if (int rc = cut_block(e, c, dev, audio, out)) return rc;
+    } else if (dev && (reinterpret_cast<uintptr_t>(out) & 15)) {
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output must be 16-byte aligned", k.who);
+    }
+    c.d_out = out;
+    if (!dev) {
+        if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, (size_t)k.out_samples * c.ob)) return rc;
         c.d_out = e->d_cut_out;
     }
-    const size_t sb = sizeof(vadk::CutSeg) * e->cut_segs.size(), pb = sizeof(float) * (size_t)nramp;
-    const size_t wb = sizeof(vadk::RenderWork) * e->render_work.size(), gb = gains && n > 0 ? sizeof(float) * (size_t)n : 0;
-    if (int rc = ensure(e, e->d_cut, e->d_cut_cap, sb + pb + wb + gb)) return rc;
-    if (!dev && audio && n > 0) {
-        HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, c.ab, hipMemcpyHostToDevice, s));
-        set_resident(e, c.ab, c.channels, c.fmt, c.rate ? c.sr_in : 0);
-    }
-    e->render_ramp.assign(ramp, ramp + nramp);
-    if (sb) HIP_TRY(e, hipMemcpyAsync(e->d_cut, e->cut_segs.data(), sb, hipMemcpyHostToDevice, s));
-    if (pb) HIP_TRY(e, hipMemcpyAsync(e->d_cut + sb, e->render_ramp.data(), pb, hipMemcpyHostToDevice, s));
-    HIP_TRY(e, hipMemcpyAsync(e->d_cut + sb + pb, e->render_work.data(), wb, hipMemcpyHostToDevice, s));
-    if (gb) HIP_TRY(e, hipMemcpyAsync(e->d_cut + sb + pb + wb, e->cut_gains.data(), gb, hipMemcpyHostToDevice, s));
+    e->render_ramp.assign(k.ramp, k.ramp + k.nramp);
+    DevTables t{e->d_cut, e->d_cut_cap};
+    const int segs = t.add(e->cut_segs, e->cut_segs.size()), ramp = t.add(e->render_ramp, (size_t)k.nramp);
+    const int work = t.add(e->render_work, e->render_work.size()), gains = t.add(e->cut_gains, k.gains ? (size_t)k.n : 0);
+    if (int rc = t.reserve(e)) return rc;
+    if (int rc = cut_upload_audio(e, c, dev, audio, s)) return rc;
+    if (int rc = t.copy(e, s)) return rc;
     vadk::RenderArgs a{};
-    a.audio = n > 0 ? c.d_audio : nullptr;
+    a.audio = k.n > 0 ? c.d_audio : nullptr;
     a.out = c.d_out;
-    a.segs = reinterpret_cast<const vadk::CutSeg *>(e->d_cut);
-    a.work = reinterpret_cast<const vadk::RenderWork *>(e->d_cut + sb + pb);
-    a.gains = gb ? reinterpret_cast<const float *>(e->d_cut + sb + pb + wb) : nullptr;
-    a.ramp = pb ? reinterpret_cast<const float *>(e->d_cut + sb) : nullptr;
-    a.audio_bytes = n > 0 ? (uint32_t)c.ab : 0u;
+    a.segs = t.at<const vadk::CutSeg>(segs);
+    a.work = t.at<const vadk::RenderWork>(work);
+    a.gains = t.at<const float>(gains);
+    a.ramp = t.at<const float>(ramp);
+    a.audio_bytes = k.n > 0 ? (uint32_t)c.ab : 0u;
     a.nwork = (uint32_t)e->render_work.size();
-    a.nrampq = (uint32_t)nramp >> 2;
-    a.fmt = fmt;
-    a.channels = channels;
-    a.out_fmt = out_fmt;
-    a.thresh = c.rate ? -1.0f : thr;             // no input-rate sample was ever gated
-    const hipError_t r = stereo ? vadk_launch_scan_render_stereo(&a, s) : vadk_launch_scan_render(&a, s);
-    const int rc = r != hipSuccess ? e->hip_fail(r, "kernel launch (scan render)") : VAD_OK;
-    if (dev) {
-        // the launch reads the engine's tables: the next scan or cut waits for it, as behind vad_scan_device
-        if (int rc2 = scan_mark_pending(e, s)) return rc2;
-        return rc;
-    }
-    if (rc) return rc;
-    HIP_TRY(e, hipMemcpyAsync(out, c.d_out, (size_t)out_samples * c.ob, hipMemcpyDeviceToHost, s));
+    a.nrampq = (uint32_t)k.nramp >> 2;
+    a.fmt = k.fmt;
+    a.channels = k.channels;
+    a.out_fmt = k.out_fmt;
+    a.thresh = k.gate();
+    const hipError_t r = k.stereo ? vadk_launch_scan_render_stereo(&a, s) : vadk_launch_scan_render(&a, s);
+    const int rc = call_end(e, dev, s, r != hipSuccess ? e->hip_fail(r, "kernel launch (scan render)") : VAD_OK);
+    if (rc || dev) return rc;
+    HIP_TRY(e, hipMemcpyAsync(out, c.d_out, (size_t)k.out_samples * c.ob, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
     return VAD_OK;
 }
@@ -2271,7 +2307,9 @@ int64_t mel_frames(const vad_mel *m, int64_t S) {
 }
 
 // vad_scan_mel's own arguments, ahead of the block's and the items' checks
-int mel_check(vad_engine *e, const char *who, const vad_mel *m, const float *op_re, const float *op_im, const float *filters, int64_t out_rows) {
+int mel_check(vad_engine *e, const CutCall &k) {
+    const char *who = k.who;
+    const vad_mel *m = k.m;
     if (!m) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null vad_mel", who);
     switch (mel_bad_field(m)) {
         case 1: return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n_fft = %d must be a multiple of 16 from 64 to 1024", who, m->n_fft);
@@ -2284,9 +2322,9 @@ int mel_check(vad_engine *e, const char *who, const vad_mel *m, const float *op_
         case 8: return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: vad_mel.reserved = %d must be 0", who, m->reserved);
         default: break;
     }
-    if (!op_re || !op_im) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null operator", who);
-    if (!filters) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null filters", who);
-    if (out_rows < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_rows = %lld is negative", who, (long long)out_rows);
+    if (!k.op_re || !k.op_im) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null operator", who);
+    if (!k.filters) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null filters", who);
+    if (k.out_rows < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_rows = %lld is negative", who, (long long)k.out_rows);
     return VAD_OK;
 }
 
@@ -2380,66 +2418,63 @@ void melk_remember(vad_engine *e, const std::vector<vadk::CutSeg> &segs, size_t 
     if (rows_out) *rows_out = rows;
 }
 
-// vad_scan_mel / _device with e->mu held: the call's own checks, cut_check's refusals under this name (the segments tabled as for
-// the levels: the sample range once, no out_sample), the frames and rows of every segment and one workgroup per tile of MEL_TILE
-// frames, then the block as the cuts find it, the operator (mel_operator), one upload of the tables - segments, workgroups, in this
-// order in e->d_cut - and one launch.
-int mel_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re, const float *op_im,
-            const float *filters, const void *audio, int64_t audio_samples, int32_t channels, int fmt, int32_t hop, float thr, float *out,
-            int64_t out_rows, void *stream, bool keep = false, int64_t *rows_out = nullptr) {
-    hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
-    if (int rc = mel_check(e, who, m, op_re, op_im, filters, out_rows)) return rc;
-    CutPlan c{who, items, n, audio_samples, channels, fmt, hop, thr, VAD_CUT_RANGE, VAD_CUT_F32, 0, 0, 0, nullptr, true, 0.0f};
-    c.mel = true;
-    if (int rc = cut_check(e, c)) return rc;
-    if (n == 0) {
-        if (keep) melk_remember(e, e->cut_segs, 0, 0, m->n_mels, rows_out);
-        return VAD_OK;
-    }
-    int64_t rows = 0;
-    if (int rc = mel_tiles(e, who, m, e->cut_segs, &rows)) return rc;
-    if (!keep && rows > out_rows)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_rows = %lld, the segments have %lld rows", who, (long long)out_rows,
-                       (long long)rows);
-    if (!keep && rows > 0 && !out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    const size_t out_bytes = (size_t)rows * (size_t)m->n_mels * sizeof(float);
-    if (dev) {
-        if (int rc = cut_block_device(e, c, audio, out)) return rc;
-    } else {
-        if (int rc = cut_block_host(e, c, audio)) return rc;
-        if (!keep)
-            if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, out_bytes)) return rc;
-        c.d_out = e->d_cut_out;
-    }
-    if (keep) {
+// The output rules of the mel kinds, once for vad_scan_mel and vad_scan_rate_mel (c.mel_rows: the rows of all segments).  Ahead of
+// the first write: the refusals of rows and pointer, the block as the cuts find it, then where the rows go - the caller's device
+// pointer, e->d_cut_out for a host call, e->d_melk for a keep
+int mel_output(vad_engine *e, CutPlan &c, bool dev, const void *audio, void *out) {
+    const CutCall &k = c.k;
+    if (!k.keep && c.mel_rows > k.out_rows)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_rows = %lld, the segments have %lld rows", k.who, (long long)k.out_rows,
+                       (long long)c.mel_rows);
+    if (!k.keep && c.mel_rows > 0 && !out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", k.who);
+    if (int rc = cut_block(e, c, dev, audio, out)) return rc;
+    c.mel_bytes = (size_t)c.mel_rows * (size_t)k.m->n_mels * sizeof(float);
+    if (k.keep) {
         // every refusal lies behind: the previous matrix ends here
         e->melk_start.clear();
-        if (int rc = ensure(e, e->d_melk, e->d_melk_cap, out_bytes)) return rc;
+        if (int rc = ensure(e, e->d_melk, e->d_melk_cap, c.mel_bytes)) return rc;
         c.d_out = e->d_melk;
+    } else if (!dev) {
+        if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, c.mel_bytes)) return rc;
+        c.d_out = e->d_cut_out;
     }
-    const size_t sb = sizeof(vadk::CutSeg) * e->cut_segs.size(), wb = sizeof(vadk::MelWork) * e->mel_work.size();
-    if (int rc = ensure(e, e->d_cut, e->d_cut_cap, sb + wb)) return rc;
-    if (int rc = mel_operator(e, m, op_re, op_im, filters, s)) return rc;
-    if (!dev && audio) {
-        HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, c.ab, hipMemcpyHostToDevice, s));
-        set_resident(e, c.ab, c.channels, c.fmt, 0);
-    }
-    HIP_TRY(e, hipMemcpyAsync(e->d_cut, e->cut_segs.data(), sb, hipMemcpyHostToDevice, s));
-    if (wb) HIP_TRY(e, hipMemcpyAsync(e->d_cut + sb, e->mel_work.data(), wb, hipMemcpyHostToDevice, s));
-    const int rc = mel_launch(e, m, c.d_audio, c.ab, fmt, channels, thr, static_cast<float *>(c.d_out),
-                              reinterpret_cast<const vadk::CutSeg *>(e->d_cut), reinterpret_cast<const vadk::MelWork *>(e->d_cut + sb), s);
-    if (keep && !rc) melk_remember(e, e->cut_segs, (size_t)n, rows, m->n_mels, rows_out);
-    if (dev) {
-        // the launch reads the engine's tables: the next scan or cut waits for it, as behind vad_scan_device
-        if (int rc2 = scan_mark_pending(e, s)) return rc2;
-        return rc;
-    }
-    if (rc) return rc;
-    if (out_bytes && !keep) HIP_TRY(e, hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    return VAD_OK;
+}
+
+// ... and behind the launches, whose status is `launched`: a keep remembers its matrix (`segs`: the table vadk_seg_mel read), then
+// the way out, and a host call's rows cross the link back
+int mel_finish(vad_engine *e, const CutPlan &c, bool dev, const std::vector<vadk::CutSeg> &segs, int launched, void *out, hipStream_t s) {
+    const CutCall &k = c.k;
+    if (k.keep && !launched) melk_remember(e, segs, (size_t)k.n, c.mel_rows, k.m->n_mels, k.rows_out);
+    const int rc = call_end(e, dev, s, launched);
+    if (rc || dev) return rc;
+    if (c.mel_bytes && !k.keep) HIP_TRY(e, hipMemcpyAsync(out, c.d_out, c.mel_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
     return VAD_OK;
+}
+
+// The MEL kind with e->mu held: the call's own checks, cut_check's refusals under this name (the sample range once, no out_sample),
+// the frames and rows of every segment and one workgroup per tile of MEL_TILE frames, then the block and the output (mel_output),
+// the operator (mel_operator), one upload of the tables - segments, workgroups, in this order in e->d_cut - and one launch.
+int mel_run(vad_engine *e, bool dev, const CutCall &k, const void *audio, void *out, hipStream_t s) {
+    if (int rc = mel_check(e, k)) return rc;
+    CutPlan c{k};
+    if (int rc = cut_check(e, c)) return rc;
+    if (k.n == 0) {
+        if (k.keep) melk_remember(e, e->cut_segs, 0, 0, k.m->n_mels, k.rows_out);
+        return VAD_OK;
+    }
+    if (int rc = mel_tiles(e, k.who, k.m, e->cut_segs, &c.mel_rows)) return rc;
+    if (int rc = mel_output(e, c, dev, audio, out)) return rc;
+    DevTables t{e->d_cut, e->d_cut_cap};
+    const int segs = t.add(e->cut_segs, e->cut_segs.size()), work = t.add(e->mel_work, e->mel_work.size());
+    if (int rc = t.reserve(e)) return rc;
+    if (int rc = mel_operator(e, k.m, k.op_re, k.op_im, k.filters, s)) return rc;
+    if (int rc = cut_upload_audio(e, c, dev, audio, s)) return rc;
+    if (int rc = t.copy(e, s)) return rc;
+    const int rc = mel_launch(e, k.m, c.d_audio, c.ab, k.fmt, k.channels, k.thr, static_cast<float *>(c.d_out), t.at<const vadk::CutSeg>(segs),
+                              t.at<const vadk::MelWork>(work), s);
+    return mel_finish(e, c, dev, e->cut_segs, rc, out, s);
 }
 
 // what comes before the block's and the items' checks in vad_scan_resample_cut / vad_scan_rate_mel: the engine's frames, the input
@@ -2482,119 +2517,79 @@ int resample_cut_operator(vad_engine *e, int32_t sr_in, const float *taps, int32
     return VAD_OK;
 }
 
-// vad_scan_resample_cut / vad_scan_rate_mel and their _device forms with e->mu held.  The rate cut's plan with the resample flag:
-// its block and item refusals, segment table, block rules and output spans, with S16 samples per segment and one workgroup per
-// RSC_WG_SAMPLES outputs.  m != nullptr (vad_scan_rate_mel): no item's out_sample is read; the resample kernel writes the segments
-// back to back into e->d_rsc_mid, and vadk_seg_mel runs behind it on the same stream over that buffer as a mono float32 block - the
-// header's recipe - with its own segment table and tiles.  In e->d_cut: segments, mel segments, workgroups, mel tiles, input quads,
-// gains.
-int resample_cut_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const float *gains, const float *taps, int32_t ntaps,
-                     const void *audio, int64_t audio_samples, int32_t channels, int fmt, int32_t sr_in, int32_t hop, int32_t out_fmt, void *out,
-                     int64_t out_samples, void *stream, const vad_mel *m = nullptr, const float *op_re = nullptr, const float *op_im = nullptr,
-                     const float *filters = nullptr, bool mel = false, bool keep = false, int64_t *rows_out = nullptr) {
-    hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
-    int chunk = 0;
-    if (int rc = resample_cut_check(e, who, sr_in, taps, ntaps, &chunk)) return rc;
-    CutPlan c{who, items, n, audio_samples, channels, fmt, hop, -1.0f, VAD_CUT_RANGE, out_fmt, mel ? 0 : out_samples, chunk, sr_in, gains, mel, 0.0f};
-    c.mel = mel;
-    c.resample = true;
+// The RESAMPLE and RESAMPLE_MEL kinds with e->mu held (k by value: the check settles its chunk).  The rate cut's plan: its block and
+// item refusals, segment table, block rules and output spans, with S16 samples per segment - its samples at 16 kHz, in the out_sample
+// check, the spans and CutSeg::nquads - its input quads in e->rsc_inq and one workgroup per RSC_WG_SAMPLES outputs.  RESAMPLE_MEL:
+// the resample kernel writes the segments back to back into e->d_rsc_mid, and vadk_seg_mel runs behind it on the same stream over
+// that buffer as a mono float32 block - the header's recipe - with its own segment table and tiles.  In e->d_cut: segments, mel
+// segments, workgroups, mel tiles, input quads, gains.
+int resample_cut_run(vad_engine *e, bool dev, CutCall k, const void *audio, void *out, hipStream_t s) {
+    if (int rc = resample_cut_check(e, k.who, k.sr_in, k.taps, k.ntaps, &k.chunk)) return rc;
+    CutPlan c{k};
     if (int rc = cut_check(e, c)) return rc;
+    const bool mel = k.mel();
     if (mel)
-        if (int rc = mel_check(e, who, m, op_re, op_im, filters, out_samples)) return rc;
-    if (n == 0) {
-        if (keep) melk_remember(e, e->rsc_mel_segs, 0, 0, m->n_mels, rows_out);
+        if (int rc = mel_check(e, k)) return rc;
+    if (k.n == 0) {
+        if (k.keep) melk_remember(e, e->rsc_mel_segs, 0, 0, k.m->n_mels, k.rows_out);
         return VAD_OK;
     }
-    int64_t rows = 0, mid = 0;
+    int64_t mid = 0;
     if (mel) {
-        e->rsc_mel_segs.resize((size_t)n);
-        for (int64_t i = 0; i < n; ++i) {
+        e->rsc_mel_segs.resize((size_t)k.n);
+        for (int64_t i = 0; i < k.n; ++i) {
             vadk::CutSeg &sg = e->cut_segs[(size_t)i];
             sg.quad_out = (uint64_t)mid >> 2;
             e->rsc_mel_segs[(size_t)i] = vadk::CutSeg{(uint32_t)(mid >> 2) | (vadk::SCAN_LEFT << vadk::SCAN_MODE_SHIFT), sg.nquads, 0};
             mid += (int64_t)sg.nquads << 2;
             if (mid >= (int64_t)1 << 29)
-                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the segments have 2^29 or more samples at 16 kHz in one call", who);
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the segments have 2^29 or more samples at 16 kHz in one call", k.who);
         }
-        if (int rc = mel_tiles(e, who, m, e->rsc_mel_segs, &rows)) return rc;
-        if (!keep && rows > out_samples)
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_rows = %lld, the segments have %lld rows", who, (long long)out_samples,
-                           (long long)rows);
-        if (!keep && rows > 0 && !out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    } else if (!out) {
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    }
-    const size_t out_bytes = mel ? (size_t)rows * (size_t)m->n_mels * sizeof(float) : 0;
-    if (dev) {
-        if (int rc = cut_block_device(e, c, audio, out)) return rc;
-    } else {
-        if (int rc = cut_block_host(e, c, audio)) return rc;
-        if (mel && !keep) {
-            if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, out_bytes)) return rc;
-            c.d_out = e->d_cut_out;
-        }
-    }
-    if (keep) {
-        // every refusal lies behind: the previous matrix ends here
-        e->melk_start.clear();
-        if (int rc = ensure(e, e->d_melk, e->d_melk_cap, out_bytes)) return rc;
-        c.d_out = e->d_melk;
-    }
-    if (mel)
+        if (int rc = mel_tiles(e, k.who, k.m, e->rsc_mel_segs, &c.mel_rows)) return rc;
+        if (int rc = mel_output(e, c, dev, audio, out)) return rc;
         if (int rc = ensure(e, e->d_rsc_mid, e->d_rsc_mid_cap, (size_t)mid * sizeof(float))) return rc;
-    const size_t sb = sizeof(vadk::CutSeg) * e->cut_segs.size(), msb = mel ? sb : 0, wb = sizeof(vadk::CutWork) * e->cut_work.size();
-    const size_t mwb = mel ? sizeof(vadk::MelWork) * e->mel_work.size() : 0, ib = sizeof(uint32_t) * e->rsc_inq.size();
-    const size_t gb = gains ? sizeof(float) * e->cut_gains.size() : 0;
-    if (int rc = ensure(e, e->d_cut, e->d_cut_cap, sb + msb + wb + mwb + ib + gb)) return rc;
-    if (int rc = resample_cut_operator(e, sr_in, taps, ntaps, s)) return rc;
-    if (mel)
-        if (int rc = mel_operator(e, m, op_re, op_im, filters, s)) return rc;
-    if (!dev && audio) {
-        HIP_TRY(e, hipMemcpyAsync(e->d_audio, audio, c.ab, hipMemcpyHostToDevice, s));
-        set_resident(e, c.ab, c.channels, c.fmt, sr_in);
+    } else {
+        if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", k.who);
+        if (int rc = cut_block(e, c, dev, audio, out)) return rc;
     }
-    uint8_t *t = e->d_cut;
-    HIP_TRY(e, hipMemcpyAsync(t, e->cut_segs.data(), sb, hipMemcpyHostToDevice, s));
-    if (msb) HIP_TRY(e, hipMemcpyAsync(t + sb, e->rsc_mel_segs.data(), msb, hipMemcpyHostToDevice, s));
-    HIP_TRY(e, hipMemcpyAsync(t + sb + msb, e->cut_work.data(), wb, hipMemcpyHostToDevice, s));
-    if (mwb) HIP_TRY(e, hipMemcpyAsync(t + sb + msb + wb, e->mel_work.data(), mwb, hipMemcpyHostToDevice, s));
-    HIP_TRY(e, hipMemcpyAsync(t + sb + msb + wb + mwb, e->rsc_inq.data(), ib, hipMemcpyHostToDevice, s));
-    if (gb) HIP_TRY(e, hipMemcpyAsync(t + sb + msb + wb + mwb + ib, e->cut_gains.data(), gb, hipMemcpyHostToDevice, s));
-    const uint32_t L = vadk::rsc_L(sr_in), M = vadk::rsc_M(sr_in);
+    DevTables t{e->d_cut, e->d_cut_cap};
+    const int segs = t.add(e->cut_segs, e->cut_segs.size()), msegs = t.add(e->rsc_mel_segs, mel ? (size_t)k.n : 0);
+    const int work = t.add(e->cut_work, e->cut_work.size()), mwork = t.add(e->mel_work, mel ? e->mel_work.size() : 0);
+    const int inq = t.add(e->rsc_inq, e->rsc_inq.size()), gains = t.add(e->cut_gains, k.gains ? e->cut_gains.size() : 0);
+    if (int rc = t.reserve(e)) return rc;
+    if (int rc = resample_cut_operator(e, k.sr_in, k.taps, k.ntaps, s)) return rc;
+    if (mel)
+        if (int rc = mel_operator(e, k.m, k.op_re, k.op_im, k.filters, s)) return rc;
+    if (int rc = cut_upload_audio(e, c, dev, audio, s)) return rc;
+    if (int rc = t.copy(e, s)) return rc;
+    const uint32_t L = vadk::rsc_L(k.sr_in), M = vadk::rsc_M(k.sr_in);
     vadk::ResampleCutArgs a{};
     a.audio = c.d_audio;
     a.out = mel ? static_cast<void *>(e->d_rsc_mid) : c.d_out;
-    a.segs = reinterpret_cast<const vadk::CutSeg *>(t);
-    a.inq = reinterpret_cast<const uint32_t *>(t + sb + msb + wb + mwb);
-    a.work = reinterpret_cast<const vadk::CutWork *>(t + sb + msb);
-    a.gains = gb ? reinterpret_cast<const float *>(t + sb + msb + wb + mwb + ib) : nullptr;
+    a.segs = t.at<const vadk::CutSeg>(segs);
+    a.inq = t.at<const uint32_t>(inq);
+    a.work = t.at<const vadk::CutWork>(work);
+    a.gains = t.at<const float>(gains);
     a.op = e->d_rsc;
     a.audio_bytes = (uint32_t)c.ab;
     a.nwork = (uint32_t)e->cut_work.size();
-    a.ksteps = vadk::rsc_K((uint32_t)ntaps, L, M) >> 4;
-    a.n0 = vadk::rsc_n0((uint32_t)ntaps, L);
-    a.fmt = fmt;
-    a.channels = channels;
-    a.out_fmt = mel ? VAD_CUT_F32 : out_fmt;
-    a.sr_in = sr_in;
+    a.ksteps = vadk::rsc_K((uint32_t)k.ntaps, L, M) >> 4;
+    a.n0 = vadk::rsc_n0((uint32_t)k.ntaps, L);
+    a.fmt = k.fmt;
+    a.channels = k.channels;
+    a.out_fmt = mel ? VAD_CUT_F32 : k.out_fmt;
+    a.sr_in = k.sr_in;
     const hipError_t r = vadk_launch_resample_cut(&a, s);
     int rc = r != hipSuccess ? e->hip_fail(r, "kernel launch (resample cut)") : VAD_OK;
-    if (!rc && mel)
-        rc = mel_launch(e, m, e->d_rsc_mid, (size_t)mid * sizeof(float), VAD_FMT_F32, 1, -1.0f, static_cast<float *>(c.d_out),
-                        reinterpret_cast<const vadk::CutSeg *>(t + sb), reinterpret_cast<const vadk::MelWork *>(t + sb + msb + wb), s);
-    if (keep && !rc) melk_remember(e, e->rsc_mel_segs, (size_t)n, rows, m->n_mels, rows_out);
-    if (dev) {
-        // the launches read the engine's tables and buffers: the next scan or cut waits for them, as behind vad_scan_device
-        if (int rc2 = scan_mark_pending(e, s)) return rc2;
-        return rc;
+    if (!mel) {
+        rc = call_end(e, dev, s, rc);
+        if (rc || dev) return rc;
+        return cut_copy_back(e, c, out, s);
     }
-    if (rc) return rc;
-    if (!mel) return cut_copy_back(e, c, out, s);
-    if (out_bytes && !keep) HIP_TRY(e, hipMemcpyAsync(out, c.d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(e, hipStreamSynchronize(s));
-    return VAD_OK;
+    if (!rc)
+        rc = mel_launch(e, k.m, e->d_rsc_mid, (size_t)mid * sizeof(float), VAD_FMT_F32, 1, -1.0f, static_cast<float *>(c.d_out),
+                        t.at<const vadk::CutSeg>(msegs), t.at<const vadk::MelWork>(mwork), s);
+    return mel_finish(e, c, dev, e->rsc_mel_segs, rc, out, s);
 }
 
 
@@ -2652,9 +2647,8 @@ int melb_upload(vad_engine *e, bool dev, const float *features, MelbSrc *src, hi
 // vad_mel_stats / _device with e->mu held
 int mel_stats_run(vad_engine *e, bool dev, const char *who, const float *features, int64_t rows, int32_t n_mels, const int64_t *start, int64_t n,
                   float *max_out, int64_t *sum_out, uint64_t *sumsq_out, void *stream) {
-    hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
+    hipStream_t s;
+    if (int rc = call_begin(e, dev, stream, &s)) return rc;
     MelbSrc src{};
     if (int rc = melb_source(e, who, dev, features, rows, n_mels, start, n, &src)) return rc;
     if (sum_out || sumsq_out)
@@ -2671,21 +2665,26 @@ int mel_stats_run(vad_engine *e, bool dev, const char *who, const float *feature
             e->melb_work.push_back(vadk::MelStatsWork{(uint32_t)i, (uint32_t)std::min<int64_t>(vadk::MELB_STATS_ROWS, src.start[i + 1] - r), (uint64_t)r});
     if (e->melb_work.size() > (size_t)INT32_MAX)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d rows in one call", who, vadk::MELB_STATS_ROWS);
-    const size_t nn = (size_t)src.n, wb = sizeof(vadk::MelStatsWork) * e->melb_work.size(), sumb = nn * (size_t)src.n_mels * 8u, maxb = nn * sizeof(float);
-    if (int rc = ensure(e, e->d_melb, e->d_melb_cap, wb + maxb)) return rc;
+    const size_t nn = (size_t)src.n, sumb = nn * (size_t)src.n_mels * 8u, maxb = nn * sizeof(float);
+    DevTables t{e->d_melb, e->d_melb_cap};
+    const int work = t.add(e->melb_work, e->melb_work.size());
+    if (int rc = t.reserve(e)) return rc;
     vadk::MelStatsArgs a{};
     if (dev) {
         a.max_out = max_out;
         a.sum_out = reinterpret_cast<long long *>(sum_out);
         a.sumsq_out = reinterpret_cast<unsigned long long *>(sumsq_out);
     } else {
-        if (int rc = ensure(e, e->d_melb_out, e->d_melb_out_cap, 2 * sumb + maxb)) return rc;
-        a.sum_out = sum_out ? reinterpret_cast<long long *>(e->d_melb_out) : nullptr;
-        a.sumsq_out = sumsq_out ? reinterpret_cast<unsigned long long *>(e->d_melb_out + sumb) : nullptr;
-        a.max_out = max_out ? reinterpret_cast<float *>(e->d_melb_out + 2 * sumb) : nullptr;
+        // a host call's results in e->d_melb_out: room only, for the three the caller asked for
+        DevTables o{e->d_melb_out, e->d_melb_out_cap};
+        const int sum = o.add(nullptr, sum_out ? sumb : 0), sumsq = o.add(nullptr, sumsq_out ? sumb : 0), max = o.add(nullptr, max_out ? maxb : 0);
+        if (int rc = o.reserve(e)) return rc;
+        a.sum_out = o.at<long long>(sum);
+        a.sumsq_out = o.at<unsigned long long>(sumsq);
+        a.max_out = o.at<float>(max);
     }
     if (int rc = melb_upload(e, dev, features, &src, s)) return rc;
-    if (wb) HIP_TRY(e, hipMemcpyAsync(e->d_melb, e->melb_work.data(), wb, hipMemcpyHostToDevice, s));
+    if (int rc = t.copy(e, s)) return rc;
     // the call's own start values: -inf and zeros
     if (a.max_out) {
         e->melb_f.assign(nn, -INFINITY);
@@ -2694,17 +2693,12 @@ int mel_stats_run(vad_engine *e, bool dev, const char *who, const float *feature
     if (a.sum_out) HIP_TRY(e, hipMemsetAsync(a.sum_out, 0, sumb, s));
     if (a.sumsq_out) HIP_TRY(e, hipMemsetAsync(a.sumsq_out, 0, sumb, s));
     a.x = src.x;
-    a.work = reinterpret_cast<const vadk::MelStatsWork *>(e->d_melb);
+    a.work = t.at<const vadk::MelStatsWork>(work);
     a.nwork = (uint32_t)e->melb_work.size();
     a.n_mels = (uint32_t)src.n_mels;
     const hipError_t r = vadk_launch_mel_stats(&a, s);
-    const int rc = r != hipSuccess ? e->hip_fail(r, "kernel launch (mel stats)") : VAD_OK;
-    if (dev) {
-        // the launch reads the engine's tables: the next scan or cut waits for it, as behind vad_scan_device
-        if (int rc2 = scan_mark_pending(e, s)) return rc2;
-        return rc;
-    }
-    if (rc) return rc;
+    const int rc = call_end(e, dev, s, r != hipSuccess ? e->hip_fail(r, "kernel launch (mel stats)") : VAD_OK);
+    if (rc || dev) return rc;
     if (sum_out) HIP_TRY(e, hipMemcpyAsync(sum_out, a.sum_out, sumb, hipMemcpyDeviceToHost, s));
     if (sumsq_out) HIP_TRY(e, hipMemcpyAsync(sumsq_out, a.sumsq_out, sumb, hipMemcpyDeviceToHost, s));
     if (max_out) HIP_TRY(e, hipMemcpyAsync(max_out, a.max_out, maxb, hipMemcpyDeviceToHost, s));
@@ -2736,9 +2730,8 @@ int batch_check(vad_engine *e, const char *who, const vad_batch *b) {
 int mel_batch_run(vad_engine *e, bool dev, const char *who, const float *features, int64_t rows, const int64_t *start, int64_t n, const vad_batch *b,
                   const vad_batch_window *windows, int64_t nw, const float *lo, const float *shift, const float *scale, int64_t nss, void *out,
                   int64_t out_bytes, void *stream) {
-    hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
+    hipStream_t s;
+    if (int rc = call_begin(e, dev, stream, &s)) return rc;
     if (int rc = batch_check(e, who, b)) return rc;
     MelbSrc src{};
     if (int rc = melb_source(e, who, dev, features, rows, b->n_mels, start, n, &src)) return rc;
@@ -2781,27 +2774,29 @@ int mel_batch_run(vad_engine *e, bool dev, const char *who, const float *feature
     if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
     if (dev && (reinterpret_cast<uintptr_t>(out) & 15))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output must be 16-byte aligned", who);
-    const size_t wb = sizeof(vadk::MelBatchWin) * (size_t)nw, lb = sizeof(float) * std::max<size_t>(nn, 1), ssb = sizeof(float) * (size_t)nss * nm;
-    if (int rc = ensure(e, e->d_melb, e->d_melb_cap, wb + lb + 2 * ssb)) return rc;
+    // lo, shift and scale go up as one table of floats, in this order
+    const size_t nlo = std::max<size_t>(nn, 1), nsc = (size_t)nss * nm;
+    e->melb_f.assign(nlo + 2 * nsc, 0.0f);
+    DevTables t{e->d_melb, e->d_melb_cap};
+    const int win = t.add(e->melb_win, (size_t)nw), floats = t.add(e->melb_f, e->melb_f.size());
+    if (int rc = t.reserve(e)) return rc;
     if (!dev)
         if (int rc = ensure(e, e->d_melb_out, e->d_melb_out_cap, need)) return rc;
     if (int rc = melb_upload(e, dev, features, &src, s)) return rc;
-    e->melb_f.assign(lb / sizeof(float) + 2 * (size_t)nss * nm, 0.0f);
-    float *hl = e->melb_f.data(), *hs = hl + lb / sizeof(float), *hc = hs + (size_t)nss * nm;
+    float *hl = e->melb_f.data(), *hs = hl + nlo, *hc = hs + nsc;
     for (size_t i = 0; i < nn; ++i) hl[i] = lo ? lo[i] : -INFINITY;
-    for (size_t k = 0; k < (size_t)nss * nm; ++k) {
+    for (size_t k = 0; k < nsc; ++k) {
         hs[k] = shift ? shift[k] : 0.0f;
         hc[k] = scale ? scale[k] : 1.0f;
     }
-    HIP_TRY(e, hipMemcpyAsync(e->d_melb, e->melb_win.data(), wb, hipMemcpyHostToDevice, s));
-    HIP_TRY(e, hipMemcpyAsync(e->d_melb + wb, e->melb_f.data(), lb + 2 * ssb, hipMemcpyHostToDevice, s));
+    if (int rc = t.copy(e, s)) return rc;
     vadk::MelBatchArgs a{};
     a.x = src.x;
     a.out = dev ? out : static_cast<void *>(e->d_melb_out);
-    a.win = reinterpret_cast<const vadk::MelBatchWin *>(e->d_melb);
-    a.lo = reinterpret_cast<const float *>(e->d_melb + wb);
-    a.shift = reinterpret_cast<const float *>(e->d_melb + wb + lb);
-    a.scale = reinterpret_cast<const float *>(e->d_melb + wb + lb + ssb);
+    a.win = t.at<const vadk::MelBatchWin>(win);
+    a.lo = t.at<const float>(floats);
+    a.shift = a.lo + nlo;
+    a.scale = a.shift + nsc;
     a.nw = (uint32_t)nw;
     a.n_mels = (uint32_t)b->n_mels;
     a.frames = (uint32_t)b->frames;
@@ -2813,26 +2808,113 @@ int mel_batch_run(vad_engine *e, bool dev, const char *who, const float *feature
     a.per_seg = nss == 1 ? 0u : 1u;
     a.tile = tile;
     const hipError_t r = vadk_launch_mel_batch(&a, s);
-    const int rc = r != hipSuccess ? e->hip_fail(r, "kernel launch (mel batch)") : VAD_OK;
-    if (dev) {
-        // the launch reads the engine's tables: the next scan or cut waits for it, as behind vad_scan_device
-        if (int rc2 = scan_mark_pending(e, s)) return rc2;
-        return rc;
-    }
-    if (rc) return rc;
+    const int rc = call_end(e, dev, s, r != hipSuccess ? e->hip_fail(r, "kernel launch (mel batch)") : VAD_OK);
+    if (rc || dev) return rc;
     HIP_TRY(e, hipMemcpyAsync(out, e->d_melb_out, need, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
     return VAD_OK;
 }
 
-// vad_scan_mel_keep / _device with e->mu held: the plain call or the rate call under this name, by sr_in
-int mel_keep_run(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re,
-                 const float *op_im, const float *filters, const float *taps, int32_t ntaps, const void *audio, int64_t audio_samples,
-                 int32_t channels, int fmt, int32_t sr_in, int32_t hop, float thr, int64_t *rows_out, void *stream) {
-    if (sr_in == 0 || sr_in == e->sample_rate)
-        return mel_run(e, dev, who, items, n, m, op_re, op_im, filters, audio, audio_samples, channels, fmt, hop, thr, nullptr, 0, stream, true, rows_out);
-    return resample_cut_run(e, dev, who, items, n, nullptr, taps, ntaps, audio, audio_samples, channels, fmt, sr_in, hop, VAD_CUT_F32, nullptr, 0,
-                            stream, m, op_re, op_im, filters, true, true, rows_out);
+// ---- the entry points of the family: each host / _device pair fills the record in one function that takes `dev`
+
+// what an entry point's sr_in may be: the call has none (a block at the engine's rate); an input rate (16000: the call is
+// vad_scan_cut); or, in the calls that take both kinds of block, 0 or the engine's own rate too
+enum class RateArg { NONE, GIVEN, EITHER };
+
+// Around every record: the lock, the rate - ahead of the way in; the resampling kinds check theirs with the taps, behind it - the
+// way in, and the kind's runner on the call's stream
+int cut_enter(vad_engine *e, bool dev, CutCall &k, RateArg arg, int32_t sr_in, const void *audio, void *out, void *stream) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (arg == RateArg::GIVEN || (arg == RateArg::EITHER && sr_in != 0 && sr_in != e->sample_rate)) {
+        if (int rc = rate_cut_check(e, k.who, sr_in, &k.chunk)) return rc;
+        k.sr_in = k.chunk ? sr_in : 0;
+    }
+    hipStream_t s;
+    if (int rc = call_begin(e, dev, stream, &s)) return rc;
+    switch (k.kind) {
+        case CutKind::RENDER: return render_run(e, dev, k, audio, out, s);
+        case CutKind::MEL: return mel_run(e, dev, k, audio, out, s);
+        case CutKind::RESAMPLE:
+        case CutKind::RESAMPLE_MEL: return resample_cut_run(e, dev, k, audio, out, s);
+        default: return cut_run(e, dev, k, audio, out, s);
+    }
+}
+
+// The four PAYLOAD calls: vad_scan_cut has no sr_in and vad_scan_rate_cut no other; only these two have no gains.  vad_scan_cut_gain's
+// `gains` is the host array [n], never nullptr; vad_scan_cut_stereo's may be
+enum class Cut { PLAIN, RATE, GAIN, STEREO };
+int payload_entry(vad_engine *e, bool dev, const char *who, Cut call, const vad_cut_item *items, int64_t n, const float *gains, const void *audio,
+                  int64_t audio_samples, int32_t channels, int fmt, int32_t sr_in, int32_t hop, float thr, int32_t layout, int32_t out_fmt, void *out,
+                  int64_t out_samples, void *stream) {
+    CutCall k = cut_call(who, items, n, audio_samples, channels, fmt, hop, thr);
+    k.layout = layout;
+    k.out_fmt = out_fmt;
+    k.out_samples = out_samples;
+    k.gains = gains;
+    k.gains_required = call == Cut::GAIN;
+    k.stereo = call == Cut::STEREO;
+    return cut_enter(e, dev, k, call == Cut::PLAIN ? RateArg::NONE : call == Cut::RATE ? RateArg::GIVEN : RateArg::EITHER, sr_in, audio, out, stream);
+}
+
+// vad_scan_levels: `out` is n vad_level records
+int levels_entry(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples,
+                 int32_t channels, int fmt, int32_t sr_in, int32_t hop, float thr, float clip, void *out, void *stream) {
+    CutCall k = cut_call(who, items, n, audio_samples, channels, fmt, hop, thr);
+    k.kind = CutKind::LEVELS;
+    k.clip = clip;
+    return cut_enter(e, dev, k, RateArg::EITHER, sr_in, audio, out, stream);
+}
+
+// vad_scan_render and vad_scan_render_stereo (stereo)
+int render_entry(vad_engine *e, bool dev, const char *who, bool stereo, const vad_cut_item *items, int64_t n, const float *gains, const float *ramp,
+                 int32_t nramp, const void *audio, int64_t audio_samples, int32_t channels, int fmt, int32_t sr_in, int32_t hop, float thr,
+                 int32_t out_fmt, void *out, int64_t out_samples, void *stream) {
+    CutCall k = cut_call(who, items, n, audio_samples, channels, fmt, hop, thr);
+    k.kind = CutKind::RENDER;
+    k.out_fmt = out_fmt;
+    k.out_samples = out_samples;
+    k.gains = gains;
+    k.ramp = ramp;
+    k.nramp = nramp;
+    k.stereo = stereo;
+    return cut_enter(e, dev, k, RateArg::EITHER, sr_in, audio, out, stream);
+}
+
+// The mel calls.  vad_scan_mel: MEL, without taps and sr_in.  vad_scan_rate_mel: RESAMPLE_MEL.  vad_scan_mel_keep (keep: no `out`,
+// no out_rows) is the plain call or the rate call under its own name, by sr_in: 0 or the engine's rate, which never changes, is MEL
+int mel_entry(vad_engine *e, bool dev, const char *who, CutKind kind, bool keep, const vad_cut_item *items, int64_t n, const vad_mel *m,
+              const float *op_re, const float *op_im, const float *filters, const float *taps, int32_t ntaps, const void *audio, int64_t audio_samples,
+              int32_t channels, int fmt, int32_t sr_in, int32_t hop, float thr, void *out, int64_t out_rows, int64_t *rows_out, void *stream) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    CutCall k = cut_call(who, items, n, audio_samples, channels, fmt, hop, thr);
+    k.kind = keep && (sr_in == 0 || sr_in == e->sample_rate) ? CutKind::MEL : kind;
+    k.sr_in = k.kind == CutKind::MEL ? 0 : sr_in;
+    k.taps = taps;
+    k.ntaps = ntaps;
+    k.m = m;
+    k.op_re = op_re;
+    k.op_im = op_im;
+    k.filters = filters;
+    k.out_rows = out_rows;
+    k.keep = keep;
+    k.rows_out = rows_out;
+    return cut_enter(e, dev, k, RateArg::NONE, 0, audio, out, stream);
+}
+
+// vad_scan_resample_cut.  A resampled sample was never gated
+int resample_entry(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const float *gains, const float *taps, int32_t ntaps,
+                   const void *audio, int64_t audio_samples, int32_t channels, int fmt, int32_t sr_in, int32_t hop, int32_t out_fmt, void *out,
+                   int64_t out_samples, void *stream) {
+    CutCall k = cut_call(who, items, n, audio_samples, channels, fmt, hop, -1.0f);
+    k.kind = CutKind::RESAMPLE;
+    k.sr_in = sr_in;
+    k.out_fmt = out_fmt;
+    k.out_samples = out_samples;
+    k.gains = gains;
+    k.taps = taps;
+    k.ntaps = ntaps;
+    return cut_enter(e, dev, k, RateArg::NONE, 0, audio, out, stream);
 }
 
 }  // namespace
@@ -2842,19 +2924,15 @@ extern "C" {
 int vad_scan_mel_keep(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re, const float *op_im,
                       const float *filters, const float *taps, int32_t ntaps, const void *audio, int64_t audio_samples, int32_t channels,
                       int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int64_t *rows_out) {
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return mel_keep_run(e, false, "vad_scan_mel_keep", items, n, m, op_re, op_im, filters, taps, ntaps, audio, audio_samples, channels, frame_fmt,
-                        sr_in, hop, denoise_thresh, rows_out, nullptr);
+    return mel_entry(e, false, "vad_scan_mel_keep", CutKind::RESAMPLE_MEL, true, items, n, m, op_re, op_im, filters, taps, ntaps, audio, audio_samples, channels, frame_fmt,
+                     sr_in, hop, denoise_thresh, nullptr, 0, rows_out, nullptr);
 }
 
 int vad_scan_mel_keep_device(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re, const float *op_im,
                              const float *filters, const float *taps, int32_t ntaps, const void *d_audio, int64_t audio_samples,
                              int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int64_t *rows_out, void *stream) {
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return mel_keep_run(e, true, "vad_scan_mel_keep_device", items, n, m, op_re, op_im, filters, taps, ntaps, d_audio, audio_samples, channels,
-                        frame_fmt, sr_in, hop, denoise_thresh, rows_out, stream);
+    return mel_entry(e, true, "vad_scan_mel_keep_device", CutKind::RESAMPLE_MEL, true, items, n, m, op_re, op_im, filters, taps, ntaps, d_audio, audio_samples, channels,
+                     frame_fmt, sr_in, hop, denoise_thresh, nullptr, 0, rows_out, stream);
 }
 
 int vad_mel_resident(vad_engine *e, int64_t *rows, int32_t *n_mels, int64_t *nsegs) {
@@ -2928,37 +3006,29 @@ int64_t vad_resample_cut_samples(const vad_engine *e, int64_t nframes, int32_t s
 int vad_scan_resample_cut(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const float *taps, int32_t ntaps, const void *audio,
                           int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, int32_t out_fmt, void *out,
                           int64_t out_samples) {
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return resample_cut_run(e, false, "vad_scan_resample_cut", items, n, gains, taps, ntaps, audio, audio_samples, channels, frame_fmt, sr_in, hop,
-                            out_fmt, out, out_samples, nullptr);
+    return resample_entry(e, false, "vad_scan_resample_cut", items, n, gains, taps, ntaps, audio, audio_samples, channels, frame_fmt, sr_in, hop,
+                          out_fmt, out, out_samples, nullptr);
 }
 
 int vad_scan_resample_cut_device(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const float *taps, int32_t ntaps,
                                  const void *d_audio, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop,
                                  int32_t out_fmt, void *d_out, int64_t out_samples, void *stream) {
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return resample_cut_run(e, true, "vad_scan_resample_cut_device", items, n, gains, taps, ntaps, d_audio, audio_samples, channels, frame_fmt, sr_in,
-                            hop, out_fmt, d_out, out_samples, stream);
+    return resample_entry(e, true, "vad_scan_resample_cut_device", items, n, gains, taps, ntaps, d_audio, audio_samples, channels, frame_fmt, sr_in,
+                          hop, out_fmt, d_out, out_samples, stream);
 }
 
 int vad_scan_rate_mel(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re, const float *op_im,
                       const float *filters, const float *taps, int32_t ntaps, const void *audio, int64_t audio_samples, int32_t channels,
                       int frame_fmt, int32_t sr_in, int32_t hop, float *out, int64_t out_rows) {
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return resample_cut_run(e, false, "vad_scan_rate_mel", items, n, nullptr, taps, ntaps, audio, audio_samples, channels, frame_fmt, sr_in, hop,
-                            VAD_CUT_F32, out, out_rows, nullptr, m, op_re, op_im, filters, true);
+    return mel_entry(e, false, "vad_scan_rate_mel", CutKind::RESAMPLE_MEL, false, items, n, m, op_re, op_im, filters, taps, ntaps, audio,
+                     audio_samples, channels, frame_fmt, sr_in, hop, -1.0f, out, out_rows, nullptr, nullptr);
 }
 
 int vad_scan_rate_mel_device(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re, const float *op_im,
                              const float *filters, const float *taps, int32_t ntaps, const void *d_audio, int64_t audio_samples,
                              int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float *d_out, int64_t out_rows, void *stream) {
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return resample_cut_run(e, true, "vad_scan_rate_mel_device", items, n, nullptr, taps, ntaps, d_audio, audio_samples, channels, frame_fmt, sr_in,
-                            hop, VAD_CUT_F32, d_out, out_rows, stream, m, op_re, op_im, filters, true);
+    return mel_entry(e, true, "vad_scan_rate_mel_device", CutKind::RESAMPLE_MEL, false, items, n, m, op_re, op_im, filters, taps, ntaps, d_audio,
+                     audio_samples, channels, frame_fmt, sr_in, hop, -1.0f, d_out, out_rows, nullptr, stream);
 }
 
 int64_t vad_mel_frames(const vad_mel *m, int64_t nsamples) {
@@ -2970,19 +3040,15 @@ int64_t vad_mel_frames(const vad_mel *m, int64_t nsamples) {
 int vad_scan_mel(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re, const float *op_im, const float *filters,
                  const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t hop, float denoise_thresh, float *out,
                  int64_t out_rows) {
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return mel_run(e, false, "vad_scan_mel", items, n, m, op_re, op_im, filters, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, out,
-                   out_rows, nullptr);
+    return mel_entry(e, false, "vad_scan_mel", CutKind::MEL, false, items, n, m, op_re, op_im, filters, nullptr, 0, audio, audio_samples, channels, frame_fmt, 0,
+                     hop, denoise_thresh, out, out_rows, nullptr, nullptr);
 }
 
 int vad_scan_mel_device(vad_engine *e, const vad_cut_item *items, int64_t n, const vad_mel *m, const float *op_re, const float *op_im,
                         const float *filters, const void *d_audio, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t hop,
                         float denoise_thresh, float *d_out, int64_t out_rows, void *stream) {
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return mel_run(e, true, "vad_scan_mel_device", items, n, m, op_re, op_im, filters, d_audio, audio_samples, channels, frame_fmt, hop,
-                   denoise_thresh, d_out, out_rows, stream);
+    return mel_entry(e, true, "vad_scan_mel_device", CutKind::MEL, false, items, n, m, op_re, op_im, filters, nullptr, 0, d_audio, audio_samples, channels,
+                     frame_fmt, 0, hop, denoise_thresh, d_out, out_rows, nullptr, stream);
 }
 
 int64_t vad_cut_samples(const vad_engine *e, int64_t nframes, int32_t hop, int32_t layout) {
@@ -3001,119 +3067,68 @@ int64_t vad_rate_cut_samples(const vad_engine *e, int64_t nframes, int32_t sr_in
 
 int vad_scan_cut(vad_engine *e, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt,
                  int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *out, int64_t out_samples) {
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return cut_run(e, false, "vad_scan_cut", items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, out,
-                   out_samples, nullptr);
+    return payload_entry(e, false, "vad_scan_cut", Cut::PLAIN, items, n, nullptr, audio, audio_samples, channels, frame_fmt, 0, hop, denoise_thresh,
+                         layout, out_fmt, out, out_samples, nullptr);
 }
 
 int vad_scan_cut_device(vad_engine *e, const vad_cut_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
                         int frame_fmt, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *d_out, int64_t out_samples,
                         void *stream) {
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    return cut_run(e, true, "vad_scan_cut_device", items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt,
-                   d_out, out_samples, stream);
+    return payload_entry(e, true, "vad_scan_cut_device", Cut::PLAIN, items, n, nullptr, d_audio, audio_samples, channels, frame_fmt, 0, hop,
+                         denoise_thresh, layout, out_fmt, d_out, out_samples, stream);
 }
 
 int vad_scan_rate_cut(vad_engine *e, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt,
                       int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *out, int64_t out_samples) {
-    static const char *who = "vad_scan_rate_cut";
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    int chunk = 0;
-    if (int rc = rate_cut_check(e, who, sr_in, &chunk)) return rc;
-    return cut_run(e, false, who, items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, out, out_samples, nullptr,
-                   chunk, sr_in);
+    return payload_entry(e, false, "vad_scan_rate_cut", Cut::RATE, items, n, nullptr, audio, audio_samples, channels, frame_fmt, sr_in, hop,
+                         denoise_thresh, layout, out_fmt, out, out_samples, nullptr);
 }
 
 int vad_scan_rate_cut_device(vad_engine *e, const vad_cut_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
                              int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *d_out,
                              int64_t out_samples, void *stream) {
-    static const char *who = "vad_scan_rate_cut_device";
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    int chunk = 0;
-    if (int rc = rate_cut_check(e, who, sr_in, &chunk)) return rc;
-    return cut_run(e, true, who, items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, d_out, out_samples,
-                   stream, chunk, sr_in);
-}
-
-// sr_in of the calls that take both kinds of block: 0 or the engine's own rate = a block at the engine's rate (*chunk = 0)
-static int levels_rate(vad_engine *e, const char *who, int32_t sr_in, int *chunk) {
-    *chunk = 0;
-    if (sr_in == 0 || sr_in == e->sample_rate) return VAD_OK;
-    return rate_cut_check(e, who, sr_in, chunk);
+    return payload_entry(e, true, "vad_scan_rate_cut_device", Cut::RATE, items, n, nullptr, d_audio, audio_samples, channels, frame_fmt, sr_in, hop,
+                         denoise_thresh, layout, out_fmt, d_out, out_samples, stream);
 }
 
 int vad_scan_levels(vad_engine *e, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt,
                     int32_t sr_in, int32_t hop, float denoise_thresh, float clip_thresh, vad_level *levels_out) {
-    static const char *who = "vad_scan_levels";
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    int chunk = 0;
-    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
-    return cut_run(e, false, who, items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, VAD_CUT_RANGE, VAD_CUT_F32, levels_out, 0,
-                   nullptr, chunk, chunk ? sr_in : 0, nullptr, false, true, clip_thresh);
+    return levels_entry(e, false, "vad_scan_levels", items, n, audio, audio_samples, channels, frame_fmt, sr_in, hop, denoise_thresh, clip_thresh,
+                        levels_out, nullptr);
 }
 
 int vad_scan_levels_device(vad_engine *e, const vad_cut_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
                            int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, float clip_thresh, vad_level *d_levels, void *stream) {
-    static const char *who = "vad_scan_levels_device";
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    int chunk = 0;
-    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
-    return cut_run(e, true, who, items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, VAD_CUT_RANGE, VAD_CUT_F32, d_levels, 0,
-                   stream, chunk, chunk ? sr_in : 0, nullptr, false, true, clip_thresh);
+    return levels_entry(e, true, "vad_scan_levels_device", items, n, d_audio, audio_samples, channels, frame_fmt, sr_in, hop, denoise_thresh,
+                        clip_thresh, d_levels, stream);
 }
 
 int vad_scan_cut_gain(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const void *audio, int64_t audio_samples,
                       int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt, void *out,
                       int64_t out_samples) {
-    static const char *who = "vad_scan_cut_gain";
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    int chunk = 0;
-    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
-    return cut_run(e, false, who, items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, out, out_samples, nullptr,
-                   chunk, chunk ? sr_in : 0, gains, true);
+    return payload_entry(e, false, "vad_scan_cut_gain", Cut::GAIN, items, n, gains, audio, audio_samples, channels, frame_fmt, sr_in, hop,
+                         denoise_thresh, layout, out_fmt, out, out_samples, nullptr);
 }
 
 int vad_scan_cut_gain_device(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const void *d_audio, int64_t audio_samples,
                              int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt,
                              void *d_out, int64_t out_samples, void *stream) {
-    static const char *who = "vad_scan_cut_gain_device";
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    int chunk = 0;
-    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
-    return cut_run(e, true, who, items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, d_out, out_samples,
-                   stream, chunk, chunk ? sr_in : 0, gains, true);
+    return payload_entry(e, true, "vad_scan_cut_gain_device", Cut::GAIN, items, n, gains, d_audio, audio_samples, channels, frame_fmt, sr_in, hop,
+                         denoise_thresh, layout, out_fmt, d_out, out_samples, stream);
 }
 
 int vad_scan_render(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const float *ramp, int32_t nramp, const void *audio,
                     int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int32_t out_fmt,
                     void *out, int64_t out_samples) {
-    static const char *who = "vad_scan_render";
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    int chunk = 0;
-    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
-    return render_run(e, false, who, items, n, gains, ramp, nramp, audio, audio_samples, channels, frame_fmt, chunk ? sr_in : 0, chunk, hop,
-                      denoise_thresh, out_fmt, out, out_samples, nullptr);
+    return render_entry(e, false, "vad_scan_render", false, items, n, gains, ramp, nramp, audio, audio_samples, channels, frame_fmt, sr_in, hop,
+                        denoise_thresh, out_fmt, out, out_samples, nullptr);
 }
 
 int vad_scan_render_device(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const float *ramp, int32_t nramp,
                            const void *d_audio, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop,
                            float denoise_thresh, int32_t out_fmt, void *d_out, int64_t out_samples, void *stream) {
-    static const char *who = "vad_scan_render_device";
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    int chunk = 0;
-    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
-    return render_run(e, true, who, items, n, gains, ramp, nramp, d_audio, audio_samples, channels, frame_fmt, chunk ? sr_in : 0, chunk, hop,
-                      denoise_thresh, out_fmt, d_out, out_samples, stream);
+    return render_entry(e, true, "vad_scan_render_device", false, items, n, gains, ramp, nramp, d_audio, audio_samples, channels, frame_fmt, sr_in, hop,
+                        denoise_thresh, out_fmt, d_out, out_samples, stream);
 }
 
 // both channels of a two-channel block, interleaved (csrc/scan_cut.hip, csrc/scan_render.hip): the mono calls'
@@ -3121,49 +3136,29 @@ int vad_scan_render_device(vad_engine *e, const vad_cut_item *items, int64_t n, 
 int vad_scan_cut_stereo(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const void *audio, int64_t audio_samples,
                         int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt,
                         void *out, int64_t out_samples) {
-    static const char *who = "vad_scan_cut_stereo";
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    int chunk = 0;
-    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
-    return cut_run(e, false, who, items, n, audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, out, out_samples, nullptr,
-                   chunk, chunk ? sr_in : 0, gains, false, false, 0.0f, true);
+    return payload_entry(e, false, "vad_scan_cut_stereo", Cut::STEREO, items, n, gains, audio, audio_samples, channels, frame_fmt, sr_in, hop,
+                         denoise_thresh, layout, out_fmt, out, out_samples, nullptr);
 }
 
 int vad_scan_cut_stereo_device(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const void *d_audio, int64_t audio_samples,
                                int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, int32_t layout, int32_t out_fmt,
                                void *d_out, int64_t out_samples, void *stream) {
-    static const char *who = "vad_scan_cut_stereo_device";
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    int chunk = 0;
-    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
-    return cut_run(e, true, who, items, n, d_audio, audio_samples, channels, frame_fmt, hop, denoise_thresh, layout, out_fmt, d_out, out_samples,
-                   stream, chunk, chunk ? sr_in : 0, gains, false, false, 0.0f, true);
+    return payload_entry(e, true, "vad_scan_cut_stereo_device", Cut::STEREO, items, n, gains, d_audio, audio_samples, channels, frame_fmt, sr_in,
+                         hop, denoise_thresh, layout, out_fmt, d_out, out_samples, stream);
 }
 
 int vad_scan_render_stereo(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const float *ramp, int32_t nramp,
                            const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop,
                            float denoise_thresh, int32_t out_fmt, void *out, int64_t out_samples) {
-    static const char *who = "vad_scan_render_stereo";
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    int chunk = 0;
-    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
-    return render_run(e, false, who, items, n, gains, ramp, nramp, audio, audio_samples, channels, frame_fmt, chunk ? sr_in : 0, chunk, hop,
-                      denoise_thresh, out_fmt, out, out_samples, nullptr, true);
+    return render_entry(e, false, "vad_scan_render_stereo", true, items, n, gains, ramp, nramp, audio, audio_samples, channels, frame_fmt, sr_in, hop,
+                        denoise_thresh, out_fmt, out, out_samples, nullptr);
 }
 
 int vad_scan_render_stereo_device(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const float *ramp, int32_t nramp,
                                   const void *d_audio, int64_t audio_samples, int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop,
                                   float denoise_thresh, int32_t out_fmt, void *d_out, int64_t out_samples, void *stream) {
-    static const char *who = "vad_scan_render_stereo_device";
-    if (!e) return VAD_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    int chunk = 0;
-    if (int rc = levels_rate(e, who, sr_in, &chunk)) return rc;
-    return render_run(e, true, who, items, n, gains, ramp, nramp, d_audio, audio_samples, channels, frame_fmt, chunk ? sr_in : 0, chunk, hop,
-                      denoise_thresh, out_fmt, d_out, out_samples, stream, true);
+    return render_entry(e, true, "vad_scan_render_stereo_device", true, items, n, gains, ramp, nramp, d_audio, audio_samples, channels, frame_fmt,
+                        sr_in, hop, denoise_thresh, out_fmt, d_out, out_samples, stream);
 }
 
 }  // extern "C"
@@ -3518,9 +3513,8 @@ int convert_enqueue(vad_engine *e, const ConvertPlan &c, const float *taps, int3
 int convert_run(vad_engine *e, bool dev, const char *who, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples,
                 int32_t channels, int fmt, int32_t sr_in, const float *taps, int32_t ntaps, float *out, int64_t out_samples, int64_t *out_offset,
                 void *stream) {
-    hipStream_t s = (dev && stream) ? static_cast<hipStream_t>(stream) : e->stream;
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
+    hipStream_t s;
+    if (int rc = call_begin(e, dev, stream, &s)) return rc;
     ConvertPlan c;
     if (int rc = convert_check(e, who, sr_in, taps, ntaps, &c)) return rc;
     if (int rc = convert_plan(e, who, c, items, n, audio_samples, channels, fmt)) return rc;
@@ -3546,13 +3540,8 @@ int convert_run(vad_engine *e, bool dev, const char *who, const vad_scan_ch_item
         d_in = e->d_cv_in;
         d_out = e->d_cv_out;
     }
-    const int rc = convert_enqueue(e, c, taps, ntaps, d_in, channels, fmt, d_out, s);
-    if (dev) {
-        // the launch reads the engine's tables and operators: the next scan, cut or conversion waits for it
-        if (int rc2 = scan_mark_pending(e, s)) return rc2;
-        return rc;
-    }
-    if (rc) return rc;
+    const int rc = call_end(e, dev, s, convert_enqueue(e, c, taps, ntaps, d_in, channels, fmt, d_out, s));
+    if (rc || dev) return rc;
     HIP_TRY(e, hipMemcpyAsync(out, e->d_cv_out, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
     return VAD_OK;

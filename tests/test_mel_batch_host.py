@@ -538,3 +538,82 @@ def test_batch_recordings_refusals(eng):
     got, index = batch_recordings([mono, mono], spec, FeatureBatch(frames=8, dtype="f16"), cfg, engine=eng)      # no speech anywhere
     assert got.shape == (0, 6, 8) and got.dtype == np.float16 and index == []
     assert batch_recordings([], spec, FeatureBatch(frames=8, layout="time", deltas=2), cfg, engine=eng)[0].shape == (0, 8, 18)
+
+
+# ---- the order of the checks ------------------------------------------------------------------------------------------
+def test_a_batch_with_several_faults_gets_the_first_refusal(lib, eng):
+    """The order of vad_mel_batch's checks is behaviour: vad_batch's fields, the matrix and its segments (the device form's
+    feature alignment with them), the counts, nss, lo, shift, the windows, out_bytes, the output pointer, and last the device
+    form's output alignment.  Every fault at once, then one mended at a time."""
+    from tests import refusal_order as RO
+    nan, inf = float("nan"), float("inf")
+
+    def call(device, n_mels, frames, deltas, layout, dtype, pad_mode, pad_value, rows, n, start, features, nw, nss, lo, shift, windows, out_bytes,
+             out):
+        b = _ffi.Batch(n_mels, frames, deltas, layout, dtype, pad_mode, pad_value, 0)
+        st = np.array(start, np.int64)
+        win = (_ffi.BatchWindow * len(windows))(*[_ffi.BatchWindow(*w) for w in windows])
+        args = (rows, st.ctypes.data_as(C.POINTER(C.c_int64)), n, C.byref(b), win, nw, RO.f32p(lo), RO.f32p(shift), None, nss, RO.addr(out),
+                out_bytes)
+        if device:
+            return lib.vad_mel_batch_device(eng.handle, RO.addr(features), *args, None)
+        return lib.vad_mel_batch(eng.handle, RO.f32p(features), *args)
+
+    good = [(0, 3, 0), (1, 4, 1)]                                # (seg, nrows, row0): segments of 3 and 5 rows
+    faults = dict(n_mels=0, frames=5, deltas=3, layout=2, dtype=3, pad_mode=2, pad_value=nan, rows=-1, n=-1, start=[0, 3, 9],
+                  features=RO.buf(4 * 4 * 8, 2), nw=-1, nss=3, lo=RO.f32(nan, 0.0), shift=RO.f32(0.0, inf, 0.0, 0.0), windows=[(0, 3, 0), (5, 4, 1)],
+                  out_bytes=0, out=None)
+    RO.walk(lib, eng, call, faults, (
+        (INV, "n_mels = 0 must be", "n_mels", 4),
+        (INV, "frames = 5 must be", "frames", 4),
+        (INV, "deltas = 3 must be", "deltas", 0),
+        (INV, "layout = 2 is neither", "layout", 0),
+        (INV, "dtype = 3 is none of", "dtype", 0),
+        (INV, "pad_mode = 2 is neither", "pad_mode", 0),
+        (INV, "pad_value is NaN", "pad_value", 0.0),
+        (INV, "rows = -1 is negative", "rows", 8),
+        (INV, "n = -1 is negative", "n", 2),
+        (INV, r"start\[n\] = 9 leaves the matrix of 8 rows", "start", [0, 3, 8]),
+        (INV, "the features must be 4-byte aligned", "features", RO.buf(4 * 4 * 8), RO.DEVICE),
+        (INV, "null buffer or bad count", "nw", 2),
+        (INV, "nss = 3: shift and scale have 1 row or n = 2", "nss", 1),
+        (INV, r"lo\[0\] is NaN", "lo", None),
+        (INV, r"shift\[0\]\[1\] is infinite", "shift", RO.f32(0.0, 0.0, 0.0, 0.0)),
+        (INV, "window 1 names segment 5 of 2", "windows", good),
+        (INV, "out_bytes = 0, the windows have 128 bytes", "out_bytes", 128),
+        (INV, "vad_mel_batch(_device)?: null buffer$", "out", RO.buf(128, 4)),
+        (INV, "the output must be 16-byte aligned", "out", RO.buf(128), RO.DEVICE)))
+
+
+@pytest.mark.parametrize("rate", [16000, 48000])
+def test_a_keep_with_several_faults_gets_the_first_refusal(lib, eng, rate):
+    """... and vad_scan_mel_keep's, which has no output to refuse.  At the engine's rate vad_mel's fields and the filters come
+    before the block's and the segments' checks, as in vad_scan_mel; at 48 kHz the rate and the taps come first and vad_mel's
+    fields behind the segments, as in vad_scan_rate_mel."""
+    from tests import refusal_order as RO
+    op_re, op_im, filters = RO.mel_ops()
+    good, far = [(0, 0, 1, 0, 0, 0), (0, 1, 2, 0, 0, 0)], [(0, 0, 1, 0, 0, 0), (0, 7, 2, 0, 0, 0)]
+    rows_out = C.c_int64(-1)
+
+    def call(device, sr_in, taps, ntaps, fmt, channels, hop, items, n_fft, floor, fil, audio):
+        m = RO.mel(n_fft=n_fft, floor=floor)
+        args = (eng.handle, RO.cut_items(items), len(items), C.byref(m), RO.f32p(op_re), RO.f32p(op_im), RO.f32p(fil), RO.f32p(taps), ntaps,
+                RO.addr(audio), RO.NS, channels, fmt, sr_in, hop, -1.0, C.byref(rows_out))
+        return lib.vad_scan_mel_keep_device(*args, None) if device else lib.vad_scan_mel_keep(*args)
+
+    faults = dict(sr_in=44100 if rate == 48000 else 0, taps=None, ntaps=2, fmt=9, channels=3, hop=6, items=far, n_fft=100, floor=float("nan"),
+                  fil=None, audio=RO.buf(4 * RO.NS, 2))
+    first = ((RO.UNS, "from 44100Hz to 16000Hz", "sr_in", 48000),
+             (INV, "null taps", "taps", RO.f32(0.25, float("nan"), 0.25)),
+             (INV, "ntaps = 2 must be odd", "ntaps", 3),
+             (INV, r"taps\[1\] is NaN", "taps", RO.f32(0.25, 0.5, 0.25)))
+    block = ((INV, "unknown frame format 9", "fmt", 0),
+             (INV, "channels = 3, the block holds", "channels", 1),
+             (INV, "hop = 6 must be", "hop", 256),
+             (INV, "segment 1 .*leaves the audio block of 2048 samples", "items", good))
+    fields = ((INV, "n_fft = 100 must be", "n_fft", 64),
+              (INV, "floor = -?nan: a logarithm needs", "floor", 1e-5),
+              (INV, "null filters", "fil", filters))
+    last = ((INV, "the audio block must be 4-byte aligned", "audio", RO.buf(4 * RO.NS), RO.DEVICE),)
+    RO.walk(lib, eng, call, faults, first + block + fields + last if rate == 48000 else fields + block + last)
+    assert rows_out.value == (63 if rate == 48000 else 74)

@@ -748,3 +748,38 @@ def test_the_lds_pitch_keeps_a_fragment_in_64_banks(sr, N):
                     assert worst <= 2, (sr, r, n0)
                     crossing += worst == 2
     assert crossing * 100 < steps and (PI % 4 or crossing == 0), (sr, crossing, steps)
+
+
+# ---- the order of the checks ------------------------------------------------------------------------------------------
+def test_a_call_with_several_faults_gets_the_first_refusal(lib, eng):
+    """The order of vad_convert's checks is behaviour: the rate, the taps, frame format, channels, per recording its place in the
+    block and its channel, out_samples against the converted block, the output pointer, and last the device form's two alignments.
+    Every fault at once, then one mended at a time."""
+    from tests import refusal_order as RO
+    far = [(0, 0, 512, 0, 0), (0, 512, 2048, 1, 0)]              # (slot, sample_offset, nsamples, channel, reserved)
+    right = [(0, 0, 512, 0, 0), (0, 512, 1024, 1, 0)]
+    good = [(0, 0, 512, 0, 0), (0, 512, 1024, 0, 0)]
+    offsets = np.full(3, -1, np.int64)
+
+    def call(device, sr_in, taps, ntaps, fmt, channels, items, out_samples, out, audio):
+        arr = (_ffi.ScanChItem * len(items))(*[_ffi.ScanChItem(*it) for it in items])
+        args = (eng.handle, arr, len(items), RO.addr(audio), RO.NS, channels, fmt, sr_in, RO.f32p(taps), ntaps)
+        if device:
+            return lib.vad_convert_device(*args, RO.addr(out), out_samples, offsets.ctypes.data_as(C.POINTER(C.c_int64)), None)
+        return lib.vad_convert(*args, RO.f32p(out), out_samples, offsets.ctypes.data_as(C.POINTER(C.c_int64)))
+
+    faults = dict(sr_in=16000, taps=None, ntaps=2, fmt=9, channels=3, items=far, out_samples=0, out=None, audio=RO.buf(4 * RO.NS, 2))
+    RO.walk(lib, eng, call, faults, (
+        (RO.UNS, "from 16000Hz to 16000Hz", "sr_in", 48000),
+        (INV, "null taps", "taps", RO.f32(0.25, float("nan"), 0.25)),
+        (INV, "ntaps = 2 must be odd", "ntaps", 3),
+        (INV, r"taps\[1\] is NaN", "taps", RO.f32(0.25, 0.5, 0.25)),
+        (INV, "unknown frame format 9", "fmt", FMT["f32"]),
+        (INV, "channels = 3, the block holds", "channels", 1),
+        (INV, "recording 1 .*leaves the audio block of 2048 samples", "items", right),
+        (INV, "recording 1 names channel 1 of 1", "items", good),
+        (INV, "out_samples = 0, the converted block has 516 samples", "out_samples", 2048),
+        (INV, "vad_convert(_device)?: null buffer$", "out", RO.buf(4 * 2048, 4)),
+        (INV, "the audio block must be 4-byte aligned", "audio", RO.buf(4 * RO.NS), RO.DEVICE),
+        (INV, "the output must be 16-byte aligned", "out", RO.buf(4 * 2048), RO.DEVICE)))
+    assert offsets.tolist() == [0, 172, 516]

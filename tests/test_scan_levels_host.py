@@ -596,3 +596,29 @@ def test_the_rule_is_exact_for_int16_over_32768():
     s = np.random.default_rng(0).integers(-32768, 32768, 100000).astype(np.int16)
     q, peak, _ = levels_ref(s.astype(np.float32) / np.float32(32768))
     assert q == 4 * int((s.astype(np.int64) ** 2).sum()) and peak == np.abs(s.astype(np.int64)).max() / 32768
+
+
+# ---- the order of the checks ------------------------------------------------------------------------------------------
+def test_a_call_with_several_faults_gets_the_first_refusal(lib, eng):
+    """The order of vad_scan_levels's checks is behaviour: the rate, frame format, channels, hop, the clip threshold, the segments,
+    the output pointer, and last the device form's two alignments.  Every fault at once, then one mended at a time."""
+    from tests import refusal_order as RO
+    good, far = [(0, 0, 1, 0, 0, 0), (0, 1, 2, 0, 0, 0)], [(0, 0, 1, 0, 0, 0), (0, 7, 2, 0, 0, 0)]
+
+    def call(device, sr_in, fmt, channels, hop, clip, items, out, audio):
+        args = (eng.handle, RO.cut_items(items), len(items), RO.addr(audio), RO.NS, channels, fmt, sr_in, hop, -1.0, clip)
+        if device:
+            return lib.vad_scan_levels_device(*args, RO.addr(out), None)
+        return lib.vad_scan_levels(*args, None if out is None else C.cast(RO.addr(out), C.POINTER(_ffi.Level)))
+
+    faults = dict(sr_in=44100, fmt=9, channels=3, hop=6, clip=float("nan"), items=far, out=None, audio=RO.buf(4 * RO.NS, 2))
+    RO.walk(lib, eng, call, faults, (
+        (RO.UNS, "from 44100Hz to 16000Hz", "sr_in", 0),
+        (INV, "unknown frame format 9", "fmt", FMT["f32"]),
+        (INV, "channels = 3, the block holds", "channels", 1),
+        (INV, "hop = 6 must be", "hop", 256),
+        (INV, "clip_thresh is NaN", "clip", 0.95),
+        (INV, "segment 1 .*leaves the audio block of 2048 samples", "items", good),
+        (INV, "vad_scan_levels(_device)?: null buffer$", "out", RO.buf(2 * 16, 4)),
+        (INV, "the audio block must be 4-byte aligned", "audio", RO.buf(4 * RO.NS), RO.DEVICE),
+        (INV, "the levels must be 8-byte aligned", "out", RO.buf(2 * 16), RO.DEVICE)))

@@ -618,3 +618,36 @@ def test_mel_filterbank_properties(args):
     assert wide and all(abs(w[j].sum() * df - 1.0) < 0.05 for j in wide)
     with pytest.raises(ConfigurationError, match="0 <= fmin < fmax <= sample_rate / 2"):
         mel_filterbank(16000, 400, 80, 0.0, 9000.0)
+
+
+# ---- the order of the checks ------------------------------------------------------------------------------------------
+def test_a_call_with_several_faults_gets_the_first_refusal(lib, eng):
+    """The order of vad_scan_mel's checks is behaviour: vad_mel's fields, the filters, out_rows below 0, frame format, channels,
+    hop, the segments, out_rows against the segments' rows, the output pointer, and last the device form's two alignments.  Every
+    fault at once, then one mended at a time."""
+    from tests import refusal_order as RO
+    op_re, op_im, filters = RO.mel_ops()
+    good, far = [(0, 0, 1, 0, 0, 0), (0, 1, 2, 0, 0, 0)], [(0, 0, 1, 0, 0, 0), (0, 7, 2, 0, 0, 0)]      # 29 + 45 rows
+
+    def call(device, n_fft, floor, fil, out_rows, fmt, channels, hop, items, out, audio):
+        m = RO.mel(n_fft=n_fft, floor=floor)
+        args = (eng.handle, RO.cut_items(items), len(items), C.byref(m), RO.f32p(op_re), RO.f32p(op_im), RO.f32p(fil), RO.addr(audio), RO.NS,
+                channels, fmt, hop, -1.0)
+        if device:
+            return lib.vad_scan_mel_device(*args, RO.addr(out), out_rows, None)
+        return lib.vad_scan_mel(*args, RO.f32p(out), out_rows)
+
+    faults = dict(n_fft=100, floor=float("nan"), fil=None, out_rows=-1, fmt=9, channels=3, hop=6, items=far, out=None, audio=RO.buf(4 * RO.NS, 2))
+    RO.walk(lib, eng, call, faults, (
+        (INV, "n_fft = 100 must be", "n_fft", 64),
+        (INV, "floor = -?nan: a logarithm needs", "floor", 1e-5),
+        (INV, "null filters", "fil", filters),
+        (INV, "out_rows = -1 is negative", "out_rows", 0),
+        (INV, "unknown frame format 9", "fmt", FMT["f32"]),
+        (INV, "channels = 3, the block holds", "channels", 1),
+        (INV, "hop = 6 must be", "hop", 256),
+        (INV, "segment 1 .*leaves the audio block of 2048 samples", "items", good),
+        (INV, "out_rows = 0, the segments have 74 rows", "out_rows", 74),
+        (INV, "vad_scan_mel(_device)?: null buffer$", "out", RO.buf(4 * 4 * 74, 4)),
+        (INV, "the audio block must be 4-byte aligned", "audio", RO.buf(4 * RO.NS), RO.DEVICE),
+        (INV, "the output must be 16-byte aligned", "out", RO.buf(4 * 4 * 74), RO.DEVICE)))

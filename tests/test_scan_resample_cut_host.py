@@ -755,3 +755,74 @@ def test_an_engine_object_without_resample_cut_is_a_configuration_error(make_eng
     with pytest.raises(ConfigurationError, match="features_recordings: sample_rate= needs an engine with resample_cut.*_NoResample has none"):
         features_recordings(corpus, MelSpec(16000), cfg, engine=bare, hop=1536, sample_rate=48000)
     assert eng.info()["open_streams"] == opened
+
+
+# ---- the order of the checks ------------------------------------------------------------------------------------------
+def test_a_resample_cut_with_several_faults_gets_the_first_refusal(lib, eng):
+    """The order of vad_scan_resample_cut's checks is behaviour: the rate, the taps, frame format, channels, out_fmt, hop, per
+    segment its place in the block, its out_sample and its gain, the output pointer, and last the device form's two alignments.
+    Every fault at once, then one mended at a time."""
+    from tests import refusal_order as RO
+    far = [(0, 0, 1, 0, 0, 0), (0, 2, 2, 514, 0, 0)]
+    odd = [(0, 0, 1, 0, 0, 0), (0, 1, 2, 514, 0, 0)]
+    good = [(0, 0, 1, 0, 0, 0), (0, 1, 2, 512, 0, 0)]            # 1536 and 1792 samples at 48 kHz: 512 and 596 at 16 kHz
+
+    def call(device, sr_in, taps, ntaps, fmt, channels, out_fmt, hop, items, gains, out, audio):
+        args = (eng.handle, RO.cut_items(items), len(items), RO.f32p(gains), RO.f32p(taps), ntaps, RO.addr(audio), RO.NS, channels, fmt, sr_in,
+                hop, out_fmt, RO.addr(out), 1108)
+        return lib.vad_scan_resample_cut_device(*args, None) if device else lib.vad_scan_resample_cut(*args)
+
+    faults = dict(sr_in=44100, taps=None, ntaps=2, fmt=9, channels=3, out_fmt=2, hop=6, items=far, gains=RO.f32(1.0, float("inf")), out=None,
+                  audio=RO.buf(4 * RO.NS, 2))
+    RO.walk(lib, eng, call, faults, (
+        (RO.UNS, "from 44100Hz to 16000Hz", "sr_in", 48000),
+        (INV, "null taps", "taps", RO.f32(0.25, float("nan"), 0.25)),
+        (INV, "ntaps = 2 must be odd", "ntaps", 3),
+        (INV, r"taps\[1\] is NaN", "taps", RO.f32(0.25, 0.5, 0.25)),
+        (INV, "unknown frame format 9", "fmt", FMT["f32"]),
+        (INV, "channels = 3, the block holds", "channels", 1),
+        (INV, "out_fmt = 2 is neither", "out_fmt", F32),
+        (INV, "hop = 6 must be", "hop", 256),
+        (INV, "segment 1 .*leaves the audio block of 2048 samples", "items", odd),
+        (INV, r"segment 1: out_sample = 514 \(\+596 samples\)", "items", good),
+        (INV, "segment 1: its gain is infinite", "gains", RO.f32(1.0, 0.5)),
+        (INV, "vad_scan_resample_cut(_device)?: null buffer$", "out", RO.buf(4 * 1108, 4)),
+        (INV, "the audio block must be 4-byte aligned", "audio", RO.buf(4 * RO.NS), RO.DEVICE),
+        (INV, "the output must be 16-byte aligned", "out", RO.buf(4 * 1108), RO.DEVICE)))
+
+
+def test_a_rate_mel_with_several_faults_gets_the_first_refusal(lib, eng):
+    """... and vad_scan_rate_mel's: the rate, the taps, frame format, channels, hop and the segments come before vad_mel's fields,
+    the filters and out_rows - the other way round from vad_scan_mel - then out_rows against the rows, the output pointer and the
+    device form's two alignments."""
+    from tests import refusal_order as RO
+    op_re, op_im, filters = RO.mel_ops()
+    good, far = [(0, 0, 1, 0, 0, 0), (0, 1, 2, 0, 0, 0)], [(0, 0, 1, 0, 0, 0), (0, 2, 2, 0, 0, 0)]      # 29 + 34 rows
+
+    def call(device, sr_in, taps, ntaps, fmt, channels, hop, items, n_fft, floor, fil, out_rows, out, audio):
+        m = RO.mel(n_fft=n_fft, floor=floor)
+        args = (eng.handle, RO.cut_items(items), len(items), C.byref(m), RO.f32p(op_re), RO.f32p(op_im), RO.f32p(fil), RO.f32p(taps), ntaps,
+                RO.addr(audio), RO.NS, channels, fmt, sr_in, hop)
+        if device:
+            return lib.vad_scan_rate_mel_device(*args, RO.addr(out), out_rows, None)
+        return lib.vad_scan_rate_mel(*args, RO.f32p(out), out_rows)
+
+    faults = dict(sr_in=44100, taps=None, ntaps=2, fmt=9, channels=3, hop=6, items=far, n_fft=100, floor=float("nan"), fil=None, out_rows=-1,
+                  out=None, audio=RO.buf(4 * RO.NS, 2))
+    RO.walk(lib, eng, call, faults, (
+        (RO.UNS, "from 44100Hz to 16000Hz", "sr_in", 48000),
+        (INV, "null taps", "taps", RO.f32(0.25, float("nan"), 0.25)),
+        (INV, "ntaps = 2 must be odd", "ntaps", 3),
+        (INV, r"taps\[1\] is NaN", "taps", RO.f32(0.25, 0.5, 0.25)),
+        (INV, "unknown frame format 9", "fmt", FMT["f32"]),
+        (INV, "channels = 3, the block holds", "channels", 1),
+        (INV, "hop = 6 must be", "hop", 256),
+        (INV, "segment 1 .*leaves the audio block of 2048 samples", "items", good),
+        (INV, "n_fft = 100 must be", "n_fft", 64),
+        (INV, "floor = -?nan: a logarithm needs", "floor", 1e-5),
+        (INV, "null filters", "fil", filters),
+        (INV, "out_rows = -1 is negative", "out_rows", 0),
+        (INV, "out_rows = 0, the segments have 63 rows", "out_rows", 63),
+        (INV, "vad_scan_rate_mel(_device)?: null buffer$", "out", RO.buf(4 * 4 * 63, 4)),
+        (INV, "the audio block must be 4-byte aligned", "audio", RO.buf(4 * RO.NS), RO.DEVICE),
+        (INV, "the output must be 16-byte aligned", "out", RO.buf(4 * 4 * 63), RO.DEVICE)))

@@ -498,3 +498,38 @@ def test_without_keep_channels_nothing_new_reaches_the_engine(make_engine):
     for fn, what in ((cut_recordings, "cut_stereo"), (render_recordings, "render_stereo")):
         with pytest.raises(ConfigurationError, match=f"keep_channels=True needs an engine with {what}.*_Recorder has none"):
             fn(corpus, cfg, engine=rec, hop=frame, keep_channels=True)
+
+
+# ---- the order of the checks ------------------------------------------------------------------------------------------
+def test_a_call_with_several_faults_gets_the_first_refusal(lib, eng):
+    """The order of vad_scan_cut_stereo's checks is behaviour: the rate, frame format, channels (1 or 2, then 2), layout, out_fmt,
+    hop, per segment its place in the block, its channel, its out_sample and its gain, the output pointer, and last the device
+    form's two alignments.  Every fault at once, then one mended at a time."""
+    from tests import refusal_order as RO
+    far = [(0, 0, 1, 0, BOTH, 0), (0, 7, 2, 514, 0, 0)]
+    left = [(0, 0, 1, 0, BOTH, 0), (0, 1, 2, 514, 0, 0)]
+    odd = [(0, 0, 1, 0, BOTH, 0), (0, 1, 2, 514, BOTH, 0)]
+    good = [(0, 0, 1, 0, BOTH, 0), (0, 1, 2, 512, BOTH, 0)]          # the range once: 512 and 768 sample frames
+
+    def call(device, sr_in, fmt, channels, layout, out_fmt, hop, items, gains, out, audio):
+        args = (eng.handle, RO.cut_items(items), len(items), RO.f32p(gains), RO.addr(audio), RO.NS, channels, fmt, sr_in, hop, -1.0, layout,
+                out_fmt, RO.addr(out), 1280)
+        return lib.vad_scan_cut_stereo_device(*args, None) if device else lib.vad_scan_cut_stereo(*args)
+
+    faults = dict(sr_in=44100, fmt=9, channels=3, layout=2, out_fmt=2, hop=6, items=far, gains=RO.f32(1.0, float("nan")), out=None,
+                  audio=RO.buf(8 * RO.NS, 4))
+    RO.walk(lib, eng, call, faults, (
+        (RO.UNS, "from 44100Hz to 16000Hz", "sr_in", 0),
+        (INV, "unknown frame format 9", "fmt", FMT["f32"]),
+        (INV, "channels = 3, the block holds", "channels", 1),
+        (INV, "channels = 1: two-channel blocks only", "channels", 2),
+        (INV, "layout = 2 is neither", "layout", RANGE),
+        (INV, "out_fmt = 2 is neither", "out_fmt", F32),
+        (INV, "hop = 6 must be", "hop", 256),
+        (INV, "segment 1 .*leaves the audio block of 2048 samples", "items", left),
+        (INV, "segment 1 names channel 0: both channels are written", "items", odd),
+        (INV, r"segment 1: out_sample = 514 \(\+768 samples\)", "items", good),
+        (INV, "segment 1: its gain is NaN", "gains", RO.f32(1.0, 0.5)),
+        (INV, "vad_scan_cut_stereo(_device)?: null buffer$", "out", RO.buf(8 * 1280, 4)),
+        (INV, "the audio block must be 8-byte aligned", "audio", RO.buf(8 * RO.NS), RO.DEVICE),
+        (INV, "the output must be 16-byte aligned", "out", RO.buf(8 * 1280), RO.DEVICE)))

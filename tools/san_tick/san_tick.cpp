@@ -3,7 +3,8 @@
 // a fifth thread opens and closes streams with frames still queued.  Checked: every stream's frames were stepped exactly once
 // and in push order (the stand-in model returns |first sample|, so the audio scripts the probabilities), events equal a serial
 // replay of the real state machine, segments hold exactly the frames the reference would keep; then, single-threaded: a failing
-// tick keeps the queues aligned, and a stream saved mid-segment continues bit-identically on another slot.
+// tick keeps the queues aligned, and a stream saved mid-segment continues bit-identically on another slot; last, one host call
+// per runner of the segment-audio family (cut, rate cut, render, mel, rate mel), for the layout of their device tables.
 // Built three times by tools/san_tick/run.sh: -fsanitize=thread, -fsanitize=address,undefined, and plain.
 #include "../../include/vad_engine.h"
 #include <hip/hip_runtime.h>
@@ -369,6 +370,38 @@ int main(int argc, char **argv) {
         }
         vad_engine_destroy(eng);
         std::printf("san_tick: batched pushes ok (%d streams x %d frames, %d of them rate batches)\n", B + 20 + RB, KB, RB);
+    }
+    // ---- the segment-audio family: one host call per runner at the smallest shapes, so that the layout of the tables in the
+    //      engine's device buffer (16-byte steps, typed pointers, a rate cut's per-window slices) runs under the sanitizers once
+    {
+        OK(vad_engine_create(&d, &eng));
+        const int64_t NS = 12288;
+        std::vector<float> block((size_t)NS, 0.25f), out(22016, -7.0f);
+        const vad_cut_item two[2] = {{0, 0, 1, 0, 0, 0}, {0, 1, 2, 512, 0, 0}};
+        OK(vad_scan_cut(eng, two, 2, block.data(), NS, 1, VAD_FMT_F32, 256, -1.0f, VAD_CUT_FRAMES, VAD_CUT_F32, out.data(), 1536));
+        CHECK(out[0] == 0.25f && out[1535] == 0.25f && out[1536] == -7.0f);
+        // 43 rows of 48 kHz chunks through windows of 32: the first segment crosses from one window into the next
+        OK(vad_debug_scan_launch_frames(eng, 1));
+        const vad_cut_item rows[2] = {{0, 0, 40, 0, 0, 0}, {0, 2, 3, 40 * 512, 0, 0}};
+        OK(vad_scan_rate_cut(eng, rows, 2, block.data(), NS, 1, VAD_FMT_F32, 48000, 256, -1.0f, VAD_CUT_FRAMES, VAD_CUT_F32, out.data(), 43 * 512));
+        OK(vad_debug_scan_launch_frames(eng, 0));
+        CHECK(std::isfinite(out[0]) && out[0] != -7.0f && out[43 * 512 - 1] != -7.0f);
+        // two segments that overlap in the output by 256 samples, a ramp of 4, a gain each
+        const vad_cut_item lap[2] = {{0, 0, 1, 0, 0, 0}, {0, 1, 1, 256, 0, 0}};
+        const float ramp[4] = {0.2f, 0.4f, 0.6f, 0.8f}, gains[2] = {1.0f, 0.5f};
+        OK(vad_scan_render(eng, lap, 2, gains, ramp, 4, block.data(), NS, 1, VAD_FMT_F32, 0, 256, -1.0f, VAD_CUT_F32, out.data(), 1024));
+        CHECK(std::fabs(out[0] - 0.05f) < 1e-6f && out[768] == 0.0f && out[1023] == 0.0f);
+        vad_mel m{};
+        m.n_fft = 64; m.hop = 16; m.n_bins = 33; m.n_mels = 4; m.pad = VAD_MEL_PAD_NONE; m.log = VAD_MEL_LN; m.floor = 1e-5f;
+        std::vector<float> op(64 * 33, 0.125f), fil(4 * 33, 0.5f);
+        OK(vad_scan_mel(eng, two, 2, &m, op.data(), op.data(), fil.data(), block.data(), NS, 1, VAD_FMT_F32, 256, -1.0f, out.data(), 74));
+        CHECK(std::isfinite(out[0]) && std::isfinite(out[4 * 74 - 1]));
+        // 1536 and 1792 samples at 48 kHz: 512 and 596 at 16 kHz, 29 + 34 rows
+        const float taps[3] = {0.25f, 0.5f, 0.25f};
+        OK(vad_scan_rate_mel(eng, two, 2, &m, op.data(), op.data(), fil.data(), taps, 3, block.data(), NS, 1, VAD_FMT_F32, 48000, 256, out.data(), 63));
+        CHECK(std::isfinite(out[0]) && std::isfinite(out[4 * 63 - 1]));
+        vad_engine_destroy(eng);
+        std::printf("san_tick: segment-audio calls ok (cut, rate cut over 2 windows, render, mel, rate mel)\n");
     }
     std::printf("san_tick: all ok\n");
     return 0;
