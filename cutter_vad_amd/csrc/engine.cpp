@@ -236,28 +236,32 @@ struct vad_engine {
     std::vector<vadk::MelStatsWork> melb_work;
     std::vector<vadk::MelBatchWin> melb_win;
     std::vector<float> melb_f;
-    // vad_segments_device / vad_scan_segments: the extraction's work area - out_start as int32 [n + 1] (the host copy as it was
-    // uploaded), then the chunk counts - and, for vad_scan_segments, the items' CSR positions, the count and the retained table
+    // The calls that make or rewrite segment tables.  Each work area is laid out by one DevTables in the function
+    // named, and has one staging block: what was uploaded, as it was, until the stream has passed the copy.
+    // d_segwork (seg_launches): out_start as int32 [n + 1], the chunk counts; staged in seg_start.  For vad_scan_segments also the
+    // items' CSR positions, the count and the retained table
     uint8_t *d_segwork = nullptr; size_t d_segwork_cap = 0;
     std::vector<int32_t> seg_start;
     std::vector<int64_t> seg_out_start;
     long long *d_nsegs = nullptr; size_t d_nsegs_cap = 0;
     vadk::SegRecord *d_segtab = nullptr; size_t d_segtab_cap = 0;
     int64_t segtab_count = -1;               // records of the table in d_segtab; -1: none
-    // vad_resegment_device / vad_scan_resegment: the replay's work area (reseg_launches lays it out; reseg_up = the part that was
-    // uploaded, as it was), vad_scan_resegment's own table, and the mark that d_probs / d_events / seg_out_start hold the results of
-    // a vad_scan_segments / vad_scan_rate_segments: scan_segments_run sets it, whatever writes or reallocates the two arrays clears it
+    // d_reseg (reseg_setup): out_start as int32, the sets' lane numbers, the sets - staged in reseg_up, one copy - then the scratch
+    // state machines, the sets' counts, the items' counts and, for the tails, the lengths.  vad_scan_resegment's own table, and the
+    // mark that d_probs / d_events / seg_out_start hold the results of a vad_scan_segments / vad_scan_rate_segments:
+    // scan_segments_run sets it, whatever writes or reallocates the two arrays clears it
     uint8_t *d_reseg = nullptr; size_t d_reseg_cap = 0;
-    std::vector<uint8_t> reseg_up;
+    std::vector<int32_t> reseg_up;
     vadk::SegRecord *d_resegtab = nullptr; size_t d_resegtab_cap = 0;
     bool scan_results = false;
     // the tails (vad_scan_tails and its kin): d_tail_len = the snapshot scan_segments_run takes of its streams' state machines, one
-    // length per item of seg_out_start, written by nothing else; d_tailwork = the work area of a tails call (tail_area lays it out)
+    // length per item of seg_out_start, written by nothing else.  d_tailwork (tail_setup): out_start as int32 with the items' slots
+    // behind it - staged in tail_up - then the lengths [nt n] and the records [nt n]
     uint32_t *d_tail_len = nullptr; size_t d_tail_len_cap = 0;
     uint8_t *d_tailwork = nullptr; size_t d_tailwork_cap = 0;
     std::vector<int32_t> tail_up;
-    // vad_refine_device / vad_scan_refine: the work area (refine_count lays it out: out_start as int32, the items' first records,
-    // their counts; refine_up = out_start as it was uploaded), and vad_scan_refine's input - count, table, tails - and output
+    // d_refine (refine_count): out_start as int32 - staged in refine_up - the items' first records, their counts.  vad_scan_refine's
+    // input in d_refine_in (laid out there: the two counts, the caller's table, the caller's tails) and its output in d_refine_out
     uint8_t *d_refine = nullptr; size_t d_refine_cap = 0;
     std::vector<int32_t> refine_up;
     uint8_t *d_refine_in = nullptr; size_t d_refine_in_cap = 0;
@@ -1354,8 +1358,9 @@ int call_end(vad_engine *e, bool dev, hipStream_t s, int launched) {
 // the order they lie, each at a multiple of 16 bytes (CutSeg and RenderWork hold 64-bit fields); reserve() is the buffer's one
 // ensure, copy() the uploads on `s`, and at<T>() a table's device pointer, so that the kernel arguments sum no bytes.  An empty
 // table is not copied and is nullptr; a table without a host pointer is room only.  Nothing is allocated: a call has few tables
+// (the replay's work area has the most: seven)
 struct DevTables {
-    static constexpr int MAX = 6;
+    static constexpr int MAX = 7;
     uint8_t *&buf; size_t &cap;
     const void *host[MAX]; size_t bytes[MAX], off[MAX]; int n = 0; size_t total = 0;
     int add(const void *p, size_t b) {
@@ -3164,12 +3169,96 @@ int vad_scan_render_stereo_device(vad_engine *e, const vad_cut_item *items, int6
 }  // extern "C"
 
 // ---- the segment table of a scan (vad_segments_device, vad_scan_segments, vad_scan_rate_segments) ---------------------------
+// This section and the three behind vad_scan_convert_segments - the replay, the tails, the refinement - are one family: the calls
+// that make or rewrite segment tables from per-frame results.  Every one enters through call_begin and leaves through
+// call_end, keeps its work area in one DevTables, and shares the checks and the small launches below.
 namespace {
 
 static_assert(sizeof(vad_segment) == sizeof(vadk::SegRecord), "the header's record is the kernel's");
 
-// the launches of an extraction on `s`: out_start (checked: starts at 0 or above, never decreases, ends at 2^31 - 1 or below) goes
-// to the device as int32 next to the chunk counts; seg_cap >= 0, the table at d_segs has room for it
+// what a call that is given positions checks about them: the first not negative, never decreasing, at most 2^31 - 1 frames
+// -> *total = out_start[n]
+int check_positions(vad_engine *e, const char *who, const int64_t *out_start, int64_t n, int64_t *total) {
+    if (n > 0 && out_start[0] < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start[0] is negative", who);
+    for (int64_t i = 0; i < n; ++i)
+        if (out_start[i + 1] < out_start[i])
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start decreases at item %lld (%lld after %lld)", who, (long long)i,
+                           (long long)out_start[i + 1], (long long)out_start[i]);
+    *total = n > 0 ? out_start[n] : 0;
+    if (*total > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 frames in one call", who);
+    return VAD_OK;
+}
+
+// what a host form that works on the last scan's per-frame results checks: the mark (scan_segments_run sets it)
+int check_resident(vad_engine *e, const char *who) {
+    if (!e->scan_results || e->seg_out_start.empty())
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: no scan results are resident: the engine's last vad_scan_segments or "
+                                            "vad_scan_rate_segments failed, or a later call has reused its per-frame arrays", who);
+    return VAD_OK;
+}
+
+// What a device form checks about the caller's arrays, behind the positions: the per-frame arrays - the events and `by4` - are
+// there when there is a frame; then the alignments, each list under the entry point's own noun: the events and `by16`, `by4`, `by8`
+struct Ptrs { std::initializer_list<const void *> p; const char *noun; };
+
+bool misaligned(const Ptrs &q, uintptr_t mask) {
+    for (const void *p : q.p)
+        if (reinterpret_cast<uintptr_t>(p) & mask) return true;
+    return false;
+}
+
+int check_device_arrays(vad_engine *e, const char *who, int64_t total, const uint8_t *d_events, const Ptrs &by16, const Ptrs &by4, const Ptrs &by8) {
+    bool missing = !d_events;
+    for (const void *p : by4.p) missing = missing || !p;
+    if (total > 0 && missing) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if ((reinterpret_cast<uintptr_t>(d_events) & 15) || misaligned(by16, 15))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %s must be 16-byte aligned", who, by16.noun);
+    if (misaligned(by4, 3)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %s must be 4-byte aligned", who, by4.noun);
+    if (misaligned(by8, 7)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %s must be 8-byte aligned", who, by8.noun);
+    return VAD_OK;
+}
+
+// the positions as the kernels read them: int32 [n + 1] (no item: one 0) at the front of `up`, a work area's staging block of `ints`
+// entries - what lies behind the positions is the caller's to write.  One block per work area: it is the source of an asynchronous
+// copy, the copy's until the stream has passed it
+void narrow_positions(std::vector<int32_t> &up, size_t ints, const int64_t *out_start, int64_t n) {
+    up.resize(ints);
+    up[0] = 0;
+    for (int64_t i = 0; n > 0 && i <= n; ++i) up[(size_t)i] = (int32_t)out_start[i];
+}
+
+// counts that the launches on `s` left on the device, behind them
+int read_back(vad_engine *e, long long *out, const long long *d, size_t count, hipStream_t s) {
+    HIP_TRY(e, hipMemcpyAsync(out, d, sizeof(long long) * count, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    return VAD_OK;
+}
+
+// `take` records of a table of the engine's to the caller, behind the launches on `s`
+int download_records(vad_engine *e, vad_segment *out, const vadk::SegRecord *d, int64_t take, hipStream_t s) {
+    HIP_TRY(e, hipMemcpyAsync(out, d, sizeof(vad_segment) * (size_t)take, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    return VAD_OK;
+}
+
+// the statistics of the records that a replay or a refinement has written into d_segs; `most` bounds the records there are
+int seg_stats(vad_engine *e, const uint8_t *d_events, const float *d_probs, const int32_t *d_start, int32_t n, vadk::SegRecord *d_segs,
+              uint32_t seg_cap, long long *d_nsegs, int64_t most, hipStream_t s) {
+    vadk::SegArgs st{};
+    st.events = d_events;
+    st.probs = d_probs;
+    st.out_start = d_start;
+    st.segs = d_segs;
+    st.nsegs = d_nsegs;
+    st.seg_cap = seg_cap;
+    st.n = n;
+    const hipError_t r = vadk_launch_seg_stats(&st, (uint32_t)std::min<int64_t>(most, (int64_t)seg_cap), s);
+    if (r != hipSuccess) return e->hip_fail(r, "kernel launch (segment statistics)");
+    return VAD_OK;
+}
+
+// the launches of an extraction on `s`: out_start (checked: check_positions) goes to the device as int32 next to the chunk counts;
+// seg_cap >= 0, the table at d_segs has room for it
 int seg_launches(vad_engine *e, const uint8_t *d_events, const int32_t *d_seg, const float *d_probs, const int64_t *out_start, int64_t n,
                  vadk::SegRecord *d_segs, int64_t seg_cap, long long *d_nsegs, hipStream_t s) {
     const int64_t total = n > 0 ? out_start[n] : 0;
@@ -3185,53 +3274,72 @@ int seg_launches(vad_engine *e, const uint8_t *d_events, const int32_t *d_seg, c
     a.segs = d_segs;
     a.nsegs = d_nsegs;
     if (a.nchunks) {
-        const size_t sb = (sizeof(int32_t) * (size_t)(n + 1) + 15) & ~(size_t)15;
-        if (int rc = ensure(e, e->d_segwork, e->d_segwork_cap, sb + sizeof(uint32_t) * (size_t)a.nchunks)) return rc;
-        e->seg_start.resize((size_t)n + 1);
-        for (int64_t i = 0; i <= n; ++i) e->seg_start[(size_t)i] = (int32_t)out_start[i];
-        HIP_TRY(e, hipMemcpyAsync(e->d_segwork, e->seg_start.data(), sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice, s));
-        a.out_start = reinterpret_cast<const int32_t *>(e->d_segwork);
-        a.chunk = reinterpret_cast<uint32_t *>(e->d_segwork + sb);
+        DevTables t{e->d_segwork, e->d_segwork_cap};
+        narrow_positions(e->seg_start, (size_t)n + 1, out_start, n);
+        const int k_start = t.add(e->seg_start, (size_t)n + 1), k_chunk = t.add(nullptr, sizeof(uint32_t) * (size_t)a.nchunks);
+        if (int rc = t.reserve(e)) return rc;
+        if (int rc = t.copy(e, s)) return rc;
+        a.out_start = t.at<const int32_t>(k_start);
+        a.chunk = t.at<uint32_t>(k_chunk);
     }
     const hipError_t r = vadk_launch_scan_segments(&a, s);
     if (r != hipSuccess) return e->hip_fail(r, "kernel launch (scan segments)");
     return VAD_OK;
 }
 
-// The first half of a tails call on `s`: the work area sized for n items under nt sets, and out_start (checked as seg_launches wants
-// it) with - slots != nullptr - the items' slots behind it go up as int32 in one block.  a->tail_len and a->tails point into the
-// work area; a caller with arrays of its own for either replaces them.
+// The first half of a tails call on `s`: the work area for n > 0 items under nt sets - out_start (checked: check_positions) with,
+// slots != nullptr, the items' slots behind it, as int32 in one block; the lengths; the records.  a->tail_len and a->tails point
+// into the work area; a caller with arrays of its own for either replaces them.
 int tail_setup(vad_engine *e, const uint8_t *d_events, const float *d_probs, const int64_t *out_start, int64_t n, int64_t nt, const int64_t *slots,
                hipStream_t s, vadk::TailArgs *a) {
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t ints = (size_t)(n + 1) + (slots ? (size_t)n : 0), o_len = up16(sizeof(int32_t) * ints);
-    const size_t o_rec = o_len + up16(sizeof(uint32_t) * (size_t)nt * (size_t)n);
-    if (int rc = ensure(e, e->d_tailwork, e->d_tailwork_cap, o_rec + sizeof(vadk::SegRecord) * (size_t)nt * (size_t)n + 16)) return rc;
-    e->tail_up.resize(ints);
-    for (int64_t i = 0; i <= n; ++i) e->tail_up[(size_t)i] = (int32_t)out_start[i];
+    DevTables t{e->d_tailwork, e->d_tailwork_cap};
+    const size_t ints = (size_t)(n + 1) + (slots ? (size_t)n : 0), each = (size_t)nt * (size_t)n;
+    narrow_positions(e->tail_up, ints, out_start, n);
     for (int64_t i = 0; slots && i < n; ++i) e->tail_up[(size_t)(n + 1 + i)] = (int32_t)slots[i];
-    HIP_TRY(e, hipMemcpyAsync(e->d_tailwork, e->tail_up.data(), sizeof(int32_t) * ints, hipMemcpyHostToDevice, s));
+    const int k_start = t.add(e->tail_up, ints), k_len = t.add(nullptr, sizeof(uint32_t) * each), k_rec = t.add(nullptr, sizeof(vadk::SegRecord) * each);
+    if (int rc = t.reserve(e)) return rc;
+    if (int rc = t.copy(e, s)) return rc;
     *a = vadk::TailArgs{};
     a->events = d_events;
     a->probs = d_probs;
-    a->out_start = reinterpret_cast<const int32_t *>(e->d_tailwork);
+    a->out_start = t.at<const int32_t>(k_start);
     a->sm = e->d_sm;
     a->slots = slots ? a->out_start + (n + 1) : nullptr;
-    a->tail_len = reinterpret_cast<uint32_t *>(e->d_tailwork + o_len);
-    a->tails = reinterpret_cast<vadk::SegRecord *>(e->d_tailwork + o_rec);
+    a->tail_len = t.at<uint32_t>(k_len);
+    a->tails = t.at<vadk::SegRecord>(k_rec);
     a->n = (int32_t)n;
     a->nt = (int32_t)nt;
     return VAD_OK;
 }
 
+// the lengths of the segments open in the items' slots, out of the streams' state machines, into a->tail_len
+int tail_snapshot(vad_engine *e, const vadk::TailArgs *a, hipStream_t s) {
+    const hipError_t r = vadk_launch_tail_snapshot(a, s);
+    if (r != hipSuccess) return e->hip_fail(r, "kernel launch (tail snapshot)");
+    return VAD_OK;
+}
+
+// the tails' lengths of a scan, out of the streams' state machines as the model launches leave them (vad_scan_tails): one small
+// launch on the same stream, no model launch - vad_info.steps and .frames do not move; whatever a later call does to the slots
+// comes behind it
+int scan_tail_lengths(vad_engine *e, const vad_scan_ch_item *items, int64_t n, hipStream_t s) {
+    std::vector<int64_t> slots((size_t)n);
+    for (int64_t i = 0; i < n; ++i) slots[(size_t)i] = items[i].slot;
+    if (int rc = ensure(e, e->d_tail_len, e->d_tail_len_cap, sizeof(uint32_t) * (size_t)n)) return rc;
+    vadk::TailArgs ta;
+    if (int rc = tail_setup(e, e->d_events, e->d_probs, e->seg_out_start.data(), n, 1, slots.data(), s, &ta)) return rc;
+    ta.tail_len = e->d_tail_len;
+    return tail_snapshot(e, &ta, s);
+}
+
 // vad_scan_segments and vad_scan_rate_segments (chunk > 0: the recordings are at sr_in), with e->mu held: the scan of host audio
-// into the engine's own arrays - the block stays resident, of its rate - then the extraction.  fill (vad_scan_convert_segments):
-// there is no host audio, the block is written into e->d_audio by fill's launches
+// into the engine's own arrays - the block stays resident, of its rate - then the extraction.  fill: nullptr, or
+// (vad_scan_convert_segments) there is no host audio and the block is written into e->d_audio by fill's launches
 int scan_segments_run(vad_engine *e, const char *who, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples,
                       int32_t channels, int frame_fmt, int chunk, int32_t sr_in, int32_t hop, float denoise_thresh, vad_segment *segs_out,
-                      int64_t seg_cap, int64_t *nsegs_out, const std::function<int()> *fill = nullptr) {
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
+                      int64_t seg_cap, int64_t *nsegs_out, const std::function<int()> *fill) {
+    hipStream_t s;
+    if (int rc = call_begin(e, false, nullptr, &s)) return rc;
     // the CSR positions the caller of vad_scan_channels would have passed are the plan's to make: the items packed in their order
     std::vector<int64_t> &start = e->seg_out_start;
     e->scan_results = false;                 // the plan rewrites the positions
@@ -3247,19 +3355,9 @@ int scan_segments_run(vad_engine *e, const char *who, const vad_scan_ch_item *it
         *nsegs_out = 0;
         return VAD_OK;
     }
-    if (int rc = scan_upload_launch(e, n, audio, audio_samples, channels, frame_fmt, chunk, sr_in, hop, denoise_thresh, total, true, fill)) return rc;
-    {   // the tails' lengths, out of the streams' state machines as the model launches leave them (vad_scan_tails): one small
-        // launch on the same stream, no model launch - vad_info.steps and .frames do not move; whatever a later call does to the
-        // slots comes behind it
-        std::vector<int64_t> slots((size_t)n);
-        for (int64_t i = 0; i < n; ++i) slots[(size_t)i] = items[i].slot;
-        if (int rc = ensure(e, e->d_tail_len, e->d_tail_len_cap, sizeof(uint32_t) * (size_t)n)) return rc;
-        vadk::TailArgs ta;
-        if (int rc = tail_setup(e, e->d_events, e->d_probs, start.data(), n, 1, slots.data(), e->stream, &ta)) return rc;
-        ta.tail_len = e->d_tail_len;
-        const hipError_t r = vadk_launch_tail_snapshot(&ta, e->stream);
-        if (r != hipSuccess) return e->hip_fail(r, "kernel launch (tail snapshot)");
-    }
+    int launched = scan_upload_launch(e, n, audio, audio_samples, channels, frame_fmt, chunk, sr_in, hop, denoise_thresh, total, true, fill);
+    if (launched == VAD_OK) launched = scan_tail_lengths(e, items, n, s);
+    if (int rc = call_end(e, false, s, launched)) return rc;
     if (int rc = ensure(e, e->d_nsegs, e->d_nsegs_cap, sizeof(long long))) return rc;
     // the table's size is known only behind the count: room for the caller's capacity and for a segment per 16 frames first, and
     // the extraction once more (the per-frame arrays are still there) in the rare case that the table is larger
@@ -3267,17 +3365,14 @@ int scan_segments_run(vad_engine *e, const char *who, const vad_scan_ch_item *it
     long long count = 0;
     for (int pass = 0; pass < 2; ++pass) {
         if (int rc = ensure(e, e->d_segtab, e->d_segtab_cap, sizeof(vadk::SegRecord) * (size_t)room)) return rc;
-        if (int rc = seg_launches(e, e->d_events, e->d_seg, e->d_probs, start.data(), n, e->d_segtab, room, e->d_nsegs, e->stream)) return rc;
-        HIP_TRY(e, hipMemcpyAsync(&count, e->d_nsegs, sizeof count, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(e, hipStreamSynchronize(e->stream));
+        if (int rc = seg_launches(e, e->d_events, e->d_seg, e->d_probs, start.data(), n, e->d_segtab, room, e->d_nsegs, s)) return rc;
+        if (int rc = read_back(e, &count, e->d_nsegs, 1, s)) return rc;
         if (count <= room) break;
         room = count;
     }
     const int64_t take = std::min<int64_t>(count, seg_cap);
-    if (take > 0) {
-        HIP_TRY(e, hipMemcpyAsync(segs_out, e->d_segtab, sizeof(vad_segment) * (size_t)take, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(e, hipStreamSynchronize(e->stream));
-    }
+    if (take > 0)
+        if (int rc = download_records(e, segs_out, e->d_segtab, take, s)) return rc;
     e->segtab_count = count;
     e->scan_results = true;
     *nsegs_out = count;
@@ -3293,34 +3388,20 @@ int vad_segments_device(vad_engine *e, const uint8_t *d_events, const int32_t *d
     static const char *who = "vad_segments_device";
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
+    hipStream_t s;
+    if (int rc = call_begin(e, true, stream, &s)) return rc;
     if (n < 0 || seg_cap < 0)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n = %lld, seg_cap = %lld: bad count", who, (long long)n, (long long)seg_cap);
     if (n > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 items", who);
     if ((n > 0 && !out_start) || !d_nsegs || (seg_cap > 0 && !d_segs))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    if (n > 0 && out_start[0] < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start[0] is negative", who);
-    for (int64_t i = 0; i < n; ++i)
-        if (out_start[i + 1] < out_start[i])
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start decreases at item %lld (%lld after %lld)", who, (long long)i,
-                           (long long)out_start[i + 1], (long long)out_start[i]);
-    const int64_t total = n > 0 ? out_start[n] : 0;
-    if (total > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 frames in one call", who);
-    if (total > 0 && (!d_events || !d_seg_frames || !d_probs))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    if ((reinterpret_cast<uintptr_t>(d_events) & 15) || (reinterpret_cast<uintptr_t>(d_segs) & 15))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the events and the segment table must be 16-byte aligned", who);
-    if ((reinterpret_cast<uintptr_t>(d_seg_frames) & 3) || (reinterpret_cast<uintptr_t>(d_probs) & 3))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: seg_frames and probs must be 4-byte aligned", who);
-    if (reinterpret_cast<uintptr_t>(d_nsegs) & 7)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the count must be 8-byte aligned", who);
-    const int rc = seg_launches(e, d_events, d_seg_frames, d_probs, out_start, n, reinterpret_cast<vadk::SegRecord *>(d_segs), seg_cap,
-                                reinterpret_cast<long long *>(d_nsegs), s);
-    // the launches read the engine's work area: the next scan, cut or extraction waits for them, as behind vad_scan_device
-    if (int rc2 = scan_mark_pending(e, s)) return rc2;
-    return rc;
+    int64_t total = 0;
+    if (int rc = check_positions(e, who, out_start, n, &total)) return rc;
+    if (int rc = check_device_arrays(e, who, total, d_events, {{d_segs}, "the events and the segment table"},
+                                     {{d_seg_frames, d_probs}, "seg_frames and probs"}, {{d_nsegs}, "the count"}))
+        return rc;
+    return call_end(e, true, s, seg_launches(e, d_events, d_seg_frames, d_probs, out_start, n, reinterpret_cast<vadk::SegRecord *>(d_segs), seg_cap,
+                                             reinterpret_cast<long long *>(d_nsegs), s));
 }
 
 int vad_scan_segments(vad_engine *e, const vad_scan_ch_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
@@ -3328,7 +3409,7 @@ int vad_scan_segments(vad_engine *e, const vad_scan_ch_item *items, int64_t n, c
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
     return scan_segments_run(e, "vad_scan_segments", items, n, audio, audio_samples, channels, frame_fmt, 0, 0, hop, denoise_thresh, segs_out, seg_cap,
-                             nsegs_out);
+                             nsegs_out, nullptr);
 }
 
 // (sr_in == 16000: scan_rate_check answers chunk = 0, and the call is vad_scan_segments under this name)
@@ -3341,9 +3422,11 @@ int vad_scan_rate_segments(vad_engine *e, const vad_scan_ch_item *items, int64_t
     int chunk = 0;
     if (int rc = scan_rate_check(e, who, sr_in, &chunk)) return rc;
     return scan_segments_run(e, who, items, n, audio, audio_samples, channels, frame_fmt, chunk, sr_in, hop, denoise_thresh, segs_out, seg_cap,
-                             nsegs_out);
+                             nsegs_out, nullptr);
 }
 
+// No call_begin: nothing is launched and no table is rebuilt.  d_segtab is written by scan_segments_run alone, on the engine's stream,
+// which this copy is on too, and no device call reads or writes it: there is no earlier launch to wait for
 int vad_scan_segments_read(vad_engine *e, int64_t first, int64_t count, vad_segment *out) {
     static const char *who = "vad_scan_segments_read";
     if (!e) return VAD_ERR_INVALID_ARG;
@@ -3356,9 +3439,7 @@ int vad_scan_segments_read(vad_engine *e, int64_t first, int64_t count, vad_segm
     if (count == 0) return VAD_OK;
     if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
     HIP_TRY(e, hipSetDevice(e->device));
-    HIP_TRY(e, hipMemcpyAsync(out, e->d_segtab + first, sizeof(vad_segment) * (size_t)count, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    return VAD_OK;
+    return download_records(e, out, e->d_segtab + first, count, e->stream);
 }
 
 }  // extern "C"
@@ -3612,8 +3693,9 @@ int vad_scan_convert_segments(vad_engine *e, const vad_scan_ch_item *items, int6
 namespace {
 
 static_assert(VAD_RESEGMENT_MAX_SETS == vadk::RESEG_MAX_SETS, "the header's limit is the kernel's");
+static_assert(sizeof(vad_thresholds) % sizeof(int32_t) == 0, "the sets lie in the replay's int32 staging block");
 
-// what both entry points check about the sets and the capacity
+// what the replays check about the sets and the capacity
 int reseg_check_sets(vad_engine *e, const char *who, const vad_thresholds *t, int64_t nt, int64_t seg_cap) {
     if (nt < 1 || nt > vadk::RESEG_MAX_SETS)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: nt = %lld: 1 .. %d threshold sets in one call", who, (long long)nt,
@@ -3623,65 +3705,83 @@ int reseg_check_sets(vad_engine *e, const char *who, const vad_thresholds *t, in
     return VAD_OK;
 }
 
-// The first half of a replay on `s`: out_start (checked as seg_launches wants it), the sets and their lane numbers go up in one
-// block; the initial state machines are built by the kernel that serves vad_stream_open and vad_stream_set_thresholds - default,
-// then the set's thresholds - on nt scratch records of the work area (no stream's slot, no (h, c)); then the count and the prefix.
-// d_set_start == nullptr: the counts go to the work area (a->set_start says where).
-// tail_len != nullptr (the tails): the count replay alone, in the form that also keeps the length of the segment open behind each
-// item's last frame - *tail_len = those lengths [nt n], in the work area; no prefix, set_start is not written.
-int reseg_count(vad_engine *e, const uint8_t *d_events, const float *d_probs, const int64_t *out_start, int64_t n, const vad_thresholds *t,
-                int64_t nt, long long *d_set_start, hipStream_t s, vadk::ResegArgs *a, uint32_t **tail_len = nullptr) {
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_slots = up16(sizeof(int32_t) * (size_t)(n + 1)), o_thr = o_slots + up16(sizeof(int32_t) * (size_t)nt);
-    const size_t up_bytes = o_thr + up16(sizeof(vad_thresholds) * (size_t)nt), o_sm = up_bytes;
-    const size_t o_set = o_sm + up16(sizeof(vadk::SmSlot) * (size_t)nt), o_cnt = o_set + up16(sizeof(long long) * (size_t)(nt + 1));
-    const size_t o_tail = o_cnt + up16(sizeof(uint32_t) * (size_t)nt * (size_t)n);
-    if (int rc = ensure(e, e->d_reseg, e->d_reseg_cap, o_tail + (tail_len ? sizeof(uint32_t) * (size_t)nt * (size_t)n : 0) + 16)) return rc;
-    e->reseg_up.assign(up_bytes, 0);
-    int32_t *h_start = reinterpret_cast<int32_t *>(e->reseg_up.data()), *h_slots = reinterpret_cast<int32_t *>(e->reseg_up.data() + o_slots);
-    for (int64_t i = 0; i <= n; ++i) h_start[i] = n > 0 ? (int32_t)out_start[i] : 0;
-    for (int64_t k = 0; k < nt; ++k) h_slots[k] = (int32_t)k;
-    std::memcpy(e->reseg_up.data() + o_thr, t, sizeof(vad_thresholds) * (size_t)nt);
-    HIP_TRY(e, hipMemcpyAsync(e->d_reseg, e->reseg_up.data(), up_bytes, hipMemcpyHostToDevice, s));
-    vadk::SmSlot *d_sm0 = reinterpret_cast<vadk::SmSlot *>(e->d_reseg + o_sm);
-    HIP_TRY(e, vadk_launch_slot_control(d_sm0, nullptr, reinterpret_cast<const int32_t *>(e->d_reseg + o_slots), (int)nt,
-                                        CTL_DEFAULT_SM | CTL_SET_THRESHOLDS, &kDefaultSm,
-                                        reinterpret_cast<const vad_thresholds *>(e->d_reseg + o_thr), (int)nt, s));
+// ... and the device forms about their counts, behind the sets
+int reseg_check_counts(vad_engine *e, const char *who, int64_t n, int64_t nt) {
+    if (n < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n = %lld: bad count", who, (long long)n);
+    if (n * nt > INT32_MAX)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %lld items x %lld sets: more than 2^31 - 1 replays in one call", who,
+                       (long long)n, (long long)nt);
+    return VAD_OK;
+}
+
+// The work area of a replay on `s`, before its launch.  out_start (checked: check_positions), the sets' lane numbers and the sets
+// are three adjoining tables and go up as ONE copy, out of one staging block laid out as they lie; behind them room for the nt
+// scratch state machines, the sets' counts, the items' counts and - tails - the lengths [nt n] of the segments open behind each
+// item's last frame (*tail_len; nullptr without).  The initial state machines are built by the kernel that serves vad_stream_open
+// and vad_stream_set_thresholds - default, then the set's thresholds - on the scratch records (no stream's slot, no (h, c)).
+// d_set_start == nullptr: the sets' counts go to the work area (a->set_start says where).
+int reseg_setup(vad_engine *e, const uint8_t *d_events, const float *d_probs, const int64_t *out_start, int64_t n, const vad_thresholds *t,
+                int64_t nt, bool tails, long long *d_set_start, hipStream_t s, vadk::ResegArgs *a, uint32_t **tail_len) {
+    DevTables w{e->d_reseg, e->d_reseg_cap};
+    const size_t each = (size_t)nt * (size_t)n;
+    const int k_start = w.add(nullptr, sizeof(int32_t) * (size_t)(n + 1)), k_lane = w.add(nullptr, sizeof(int32_t) * (size_t)nt),
+              k_thr = w.add(nullptr, sizeof(vad_thresholds) * (size_t)nt);
+    const size_t up_bytes = w.total;
+    const int k_sm = w.add(nullptr, sizeof(vadk::SmSlot) * (size_t)nt), k_set = w.add(nullptr, sizeof(long long) * (size_t)(nt + 1)),
+              k_cnt = w.add(nullptr, sizeof(uint32_t) * each), k_tail = w.add(nullptr, tails ? sizeof(uint32_t) * each : 0);
+    if (int rc = w.reserve(e)) return rc;
+    narrow_positions(e->reseg_up, up_bytes / sizeof(int32_t), out_start, n);
+    int32_t *up = e->reseg_up.data();
+    for (int64_t k = 0; k < nt; ++k) up[w.off[k_lane] / sizeof(int32_t) + (size_t)k] = (int32_t)k;
+    std::memcpy(up + w.off[k_thr] / sizeof(int32_t), t, sizeof(vad_thresholds) * (size_t)nt);
+    HIP_TRY(e, hipMemcpyAsync(w.at<int32_t>(k_start), up, up_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(e, vadk_launch_slot_control(w.at<vadk::SmSlot>(k_sm), nullptr, w.at<const int32_t>(k_lane), (int)nt, CTL_DEFAULT_SM | CTL_SET_THRESHOLDS,
+                                        &kDefaultSm, w.at<const vad_thresholds>(k_thr), (int)nt, s));
     int shift = 0;
     while ((int64_t(1) << shift) < nt) ++shift;
     *a = vadk::ResegArgs{};
     a->events = d_events;
     a->probs = d_probs;
-    a->out_start = reinterpret_cast<const int32_t *>(e->d_reseg);
-    a->sm0 = d_sm0;
-    a->cnt = reinterpret_cast<uint32_t *>(e->d_reseg + o_cnt);
-    a->set_start = d_set_start ? d_set_start : reinterpret_cast<long long *>(e->d_reseg + o_set);
+    a->out_start = w.at<const int32_t>(k_start);
+    a->sm0 = w.at<vadk::SmSlot>(k_sm);
+    a->cnt = w.at<uint32_t>(k_cnt);
+    a->set_start = d_set_start ? d_set_start : w.at<long long>(k_set);
     a->n = (int32_t)n;
     a->nt = (int32_t)nt;
     a->set_shift = shift;
-    if (tail_len) *tail_len = reinterpret_cast<uint32_t *>(e->d_reseg + o_tail);
-    const hipError_t r = tail_len ? vadk_launch_reseg_tails(a, *tail_len, s) : vadk_launch_reseg_count(a, s);
+    *tail_len = w.at<uint32_t>(k_tail);
+    return VAD_OK;
+}
+
+// the first half of a replay: the items' counts and their prefix, the sets' counts in a->set_start
+int reseg_count(vad_engine *e, const uint8_t *d_events, const float *d_probs, const int64_t *out_start, int64_t n, const vad_thresholds *t,
+                int64_t nt, long long *d_set_start, hipStream_t s, vadk::ResegArgs *a) {
+    uint32_t *none;
+    if (int rc = reseg_setup(e, d_events, d_probs, out_start, n, t, nt, false, d_set_start, s, a, &none)) return rc;
+    const hipError_t r = vadk_launch_reseg_count(a, s);
     if (r != hipSuccess) return e->hip_fail(r, "kernel launch (resegment count)");
     return VAD_OK;
 }
 
-// ... and the second: the records into d_segs (room for seg_cap of them), then their statistics; `most` bounds the records written
+// the tails' replay: the count replay alone, in the form that also keeps the length of the segment open behind each item's last
+// frame - *tail_len = those lengths [nt n], in the work area; no prefix, no set counts
+int reseg_tail_lengths(vad_engine *e, const uint8_t *d_events, const float *d_probs, const int64_t *out_start, int64_t n, const vad_thresholds *t,
+                       int64_t nt, hipStream_t s, uint32_t **tail_len) {
+    vadk::ResegArgs a;
+    if (int rc = reseg_setup(e, d_events, d_probs, out_start, n, t, nt, true, nullptr, s, &a, tail_len)) return rc;
+    const hipError_t r = vadk_launch_reseg_tails(&a, *tail_len, s);
+    if (r != hipSuccess) return e->hip_fail(r, "kernel launch (resegment count)");
+    return VAD_OK;
+}
+
+// ... and the second half behind reseg_count: the records into d_segs (room for seg_cap of them), then their statistics; `most`
+// bounds the records written
 int reseg_fill(vad_engine *e, vadk::ResegArgs *a, vadk::SegRecord *d_segs, int64_t seg_cap, int64_t most, hipStream_t s) {
     a->segs = d_segs;
     a->seg_cap = (uint32_t)std::min<int64_t>(seg_cap, INT32_MAX);
-    hipError_t r = vadk_launch_reseg_fill(a, s);
+    const hipError_t r = vadk_launch_reseg_fill(a, s);
     if (r != hipSuccess) return e->hip_fail(r, "kernel launch (resegment fill)");
-    vadk::SegArgs st{};
-    st.events = a->events;
-    st.probs = a->probs;
-    st.out_start = a->out_start;
-    st.segs = d_segs;
-    st.nsegs = a->set_start + a->nt;
-    st.seg_cap = a->seg_cap;
-    st.n = a->n;
-    r = vadk_launch_seg_stats(&st, (uint32_t)std::min<int64_t>(most, (int64_t)a->seg_cap), s);
-    if (r != hipSuccess) return e->hip_fail(r, "kernel launch (segment statistics)");
-    return VAD_OK;
+    return seg_stats(e, a->events, a->probs, a->out_start, a->n, d_segs, a->seg_cap, a->set_start + a->nt, most, s);
 }
 
 }  // namespace
@@ -3693,64 +3793,48 @@ int vad_resegment_device(vad_engine *e, const uint8_t *d_events, const float *d_
     static const char *who = "vad_resegment_device";
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
+    hipStream_t s;
+    if (int rc = call_begin(e, true, stream, &s)) return rc;
     if (int rc = reseg_check_sets(e, who, t, nt, seg_cap)) return rc;
-    if (n < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n = %lld: bad count", who, (long long)n);
-    if (n * nt > INT32_MAX)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %lld items x %lld sets: more than 2^31 - 1 replays in one call", who,
-                       (long long)n, (long long)nt);
+    if (int rc = reseg_check_counts(e, who, n, nt)) return rc;
     if ((n > 0 && !out_start) || !d_set_start || (seg_cap > 0 && !d_segs))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    if (n > 0 && out_start[0] < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start[0] is negative", who);
-    for (int64_t i = 0; i < n; ++i)
-        if (out_start[i + 1] < out_start[i])
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start decreases at item %lld (%lld after %lld)", who, (long long)i,
-                           (long long)out_start[i + 1], (long long)out_start[i]);
-    const int64_t total = n > 0 ? out_start[n] : 0;
-    if (total > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 frames in one call", who);
-    if (total > 0 && (!d_events || !d_probs)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    if ((reinterpret_cast<uintptr_t>(d_events) & 15) || (reinterpret_cast<uintptr_t>(d_segs) & 15))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the events and the segment table must be 16-byte aligned", who);
-    if (reinterpret_cast<uintptr_t>(d_probs) & 3) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: probs must be 4-byte aligned", who);
-    if (reinterpret_cast<uintptr_t>(d_set_start) & 7)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the set counts must be 8-byte aligned", who);
+    int64_t total = 0;
+    if (int rc = check_positions(e, who, out_start, n, &total)) return rc;
+    if (int rc = check_device_arrays(e, who, total, d_events, {{d_segs}, "the events and the segment table"}, {{d_probs}, "probs"},
+                                     {{d_set_start}, "the set counts"}))
+        return rc;
     vadk::ResegArgs a;
-    int rc = reseg_count(e, d_events, d_probs, out_start, n, t, nt, reinterpret_cast<long long *>(d_set_start), s, &a);
+    int launched = reseg_count(e, d_events, d_probs, out_start, n, t, nt, reinterpret_cast<long long *>(d_set_start), s, &a);
     // a segment has a frame that starts it and a later one that ends it: at most total / 2 records per set
-    if (rc == VAD_OK && seg_cap > 0) rc = reseg_fill(e, &a, reinterpret_cast<vadk::SegRecord *>(d_segs), seg_cap, (total / 2 + 1) * nt, s);
-    // the launches read the engine's work area: the next scan, cut, extraction or replay waits for them, as behind vad_scan_device
-    if (int rc2 = scan_mark_pending(e, s)) return rc2;
-    return rc;
+    if (launched == VAD_OK && seg_cap > 0)
+        launched = reseg_fill(e, &a, reinterpret_cast<vadk::SegRecord *>(d_segs), seg_cap, (total / 2 + 1) * nt, s);
+    return call_end(e, true, s, launched);
 }
 
 int vad_scan_resegment(vad_engine *e, const vad_thresholds *t, int64_t nt, vad_segment *segs_out, int64_t seg_cap, int64_t *set_start_out) {
     static const char *who = "vad_scan_resegment";
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
+    hipStream_t s;
+    if (int rc = call_begin(e, false, nullptr, &s)) return rc;
     if (int rc = reseg_check_sets(e, who, t, nt, seg_cap)) return rc;
     if (!set_start_out || (seg_cap > 0 && !segs_out)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    if (!e->scan_results || e->seg_out_start.empty())
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: no scan results are resident: the engine's last vad_scan_segments or "
-                                            "vad_scan_rate_segments failed, or a later call has reused its per-frame arrays", who);
+    if (int rc = check_resident(e, who)) return rc;
     const int64_t n = (int64_t)e->seg_out_start.size() - 1;
     std::vector<long long> counts((size_t)nt + 1, 0);
     if (e->seg_out_start[(size_t)n] > 0) {
         vadk::ResegArgs a;
-        if (int rc = reseg_count(e, e->d_events, e->d_probs, e->seg_out_start.data(), n, t, nt, nullptr, e->stream, &a)) return rc;
-        HIP_TRY(e, hipMemcpyAsync(counts.data(), a.set_start, sizeof(long long) * counts.size(), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(e, hipStreamSynchronize(e->stream));
+        if (int rc = call_end(e, false, s, reseg_count(e, e->d_events, e->d_probs, e->seg_out_start.data(), n, t, nt, nullptr, s, &a))) return rc;
+        if (int rc = read_back(e, counts.data(), a.set_start, counts.size(), s)) return rc;
         if (counts[(size_t)nt] > INT32_MAX)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %lld records: more than 2^31 - 1 in one call", who, counts[(size_t)nt]);
+        // the table is sized by the count that came back: exactly the records the caller takes
         const int64_t take = std::min<int64_t>(counts[(size_t)nt], seg_cap);
         if (take > 0) {
             if (int rc = ensure(e, e->d_resegtab, e->d_resegtab_cap, sizeof(vadk::SegRecord) * (size_t)take)) return rc;
-            if (int rc = reseg_fill(e, &a, e->d_resegtab, take, take, e->stream)) return rc;
-            HIP_TRY(e, hipMemcpyAsync(segs_out, e->d_resegtab, sizeof(vad_segment) * (size_t)take, hipMemcpyDeviceToHost, e->stream));
-            HIP_TRY(e, hipStreamSynchronize(e->stream));
+            if (int rc = reseg_fill(e, &a, e->d_resegtab, take, take, s)) return rc;
+            if (int rc = download_records(e, segs_out, e->d_resegtab, take, s)) return rc;
         }
     }
     for (int64_t k = 0; k <= nt; ++k) set_start_out[k] = counts[(size_t)k];
@@ -3762,41 +3846,65 @@ int vad_scan_resegment(vad_engine *e, const vad_thresholds *t, int64_t nt, vad_s
 // ---- the segment still open at a recording's last frame (vad_scan_tails, vad_scan_resegment_tails, the two device forms) ------
 namespace {
 
-// what the device forms check about the positions, in vad_segments_device's wording -> *total = out_start[n]
-int tail_check_start(vad_engine *e, const char *who, const int64_t *out_start, int64_t n, int64_t *total) {
-    if (n > 0 && out_start[0] < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start[0] is negative", who);
-    for (int64_t i = 0; i < n; ++i)
-        if (out_start[i + 1] < out_start[i])
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_start decreases at item %lld (%lld after %lld)", who, (long long)i,
-                           (long long)out_start[i + 1], (long long)out_start[i]);
-    *total = n > 0 ? out_start[n] : 0;
-    if (*total > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 frames in one call", who);
-    return VAD_OK;
-}
-
-// what the host forms check: the mark, and that the caller's n is the scan's -> *total = the scan's frames
-int tail_check_resident(vad_engine *e, const char *who, const void *tails_out, int64_t n, int64_t *total) {
-    if (!e->scan_results || e->seg_out_start.empty())
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: no scan results are resident: the engine's last vad_scan_segments or "
-                                            "vad_scan_rate_segments failed, or a later call has reused its per-frame arrays", who);
-    const int64_t have = (int64_t)e->seg_out_start.size() - 1;
-    if (n != have)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n = %lld: the scan had %lld items", who, (long long)n, (long long)have);
-    if (n > 0 && !tails_out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    *total = e->seg_out_start[(size_t)n];
-    return VAD_OK;
-}
-
 int tail_records(vad_engine *e, const vadk::TailArgs *a, hipStream_t s) {
     const hipError_t r = vadk_launch_seg_tails(a, s);
     if (r != hipSuccess) return e->hip_fail(r, "kernel launch (segment tails)");
     return VAD_OK;
 }
 
-int tail_download(vad_engine *e, const vadk::TailArgs &a, vad_segment *tails_out) {
-    HIP_TRY(e, hipMemcpyAsync(tails_out, a.tails, sizeof(vad_segment) * (size_t)a.n * (size_t)a.nt, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    return VAD_OK;
+// vad_scan_tails and - replay: under the nt sets at t - vad_scan_resegment_tails, with e->mu held: the tails of the resident scan,
+// whose item count the caller's n must be.  The lengths are the scan's own snapshot, or the replay's
+int scan_tails_run(vad_engine *e, const char *who, bool replay, const vad_thresholds *t, int64_t nt, vad_segment *tails_out, int64_t n) {
+    hipStream_t s;
+    if (int rc = call_begin(e, false, nullptr, &s)) return rc;
+    if (replay)
+        if (int rc = reseg_check_sets(e, who, t, nt, 0)) return rc;
+    if (int rc = check_resident(e, who)) return rc;
+    const int64_t have = (int64_t)e->seg_out_start.size() - 1;
+    if (n != have)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n = %lld: the scan had %lld items", who, (long long)n, (long long)have);
+    if (n > 0 && !tails_out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if (n == 0) return VAD_OK;
+    if (e->seg_out_start[(size_t)n] == 0) {  // no frame, no tail (and no snapshot was taken)
+        std::memset(tails_out, 0, sizeof(vad_segment) * (size_t)n * (size_t)nt);
+        return VAD_OK;
+    }
+    vadk::TailArgs a;
+    // (a replay's positions go up twice, once per work area and out of that area's own staging block: a few bytes per item)
+    int launched = tail_setup(e, e->d_events, e->d_probs, e->seg_out_start.data(), n, nt, nullptr, s, &a);
+    if (!replay) a.tail_len = e->d_tail_len;
+    else if (launched == VAD_OK) launched = reseg_tail_lengths(e, e->d_events, e->d_probs, e->seg_out_start.data(), n, t, nt, s, &a.tail_len);
+    if (launched == VAD_OK) launched = tail_records(e, &a, s);
+    if (int rc = call_end(e, false, s, launched)) return rc;
+    return download_records(e, tails_out, a.tails, n * nt, s);
+}
+
+// vad_tails_device and - replay: under the nt sets at t, no slots - vad_resegment_tails_device, with e->mu held: the same on the
+// caller's per-frame arrays, the records into d_tails.  The lengths come out of the slots' state machines, or out of the replay
+int tails_device_run(vad_engine *e, const char *who, bool replay, const int64_t *slots, const uint8_t *d_events, const float *d_probs,
+                     const int64_t *out_start, int64_t n, const vad_thresholds *t, int64_t nt, vad_segment *d_tails, void *stream) {
+    hipStream_t s;
+    if (int rc = call_begin(e, true, stream, &s)) return rc;
+    if (replay) {
+        if (int rc = reseg_check_sets(e, who, t, nt, 0)) return rc;
+        if (int rc = reseg_check_counts(e, who, n, nt)) return rc;
+    } else {
+        if (n < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n = %lld: bad count", who, (long long)n);
+        if (n > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 items", who);
+    }
+    if (n > 0 && ((!replay && !slots) || !out_start || !d_tails)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    int64_t total = 0;
+    if (int rc = check_positions(e, who, out_start, n, &total)) return rc;
+    if (int rc = check_device_arrays(e, who, total, d_events, {{d_tails}, "the events and the tails"}, {{d_probs}, "probs"}, {{}, nullptr})) return rc;
+    if (!replay)
+        if (int rc = check_slots(e, slots, n)) return rc;
+    if (n == 0) return VAD_OK;               // nothing was launched: nothing to mark
+    vadk::TailArgs a;
+    int launched = tail_setup(e, d_events, d_probs, out_start, n, nt, replay ? nullptr : slots, s, &a);
+    a.tails = reinterpret_cast<vadk::SegRecord *>(d_tails);
+    if (launched == VAD_OK) launched = replay ? reseg_tail_lengths(e, d_events, d_probs, out_start, n, t, nt, s, &a.tail_len) : tail_snapshot(e, &a, s);
+    if (launched == VAD_OK) launched = tail_records(e, &a, s);
+    return call_end(e, true, s, launched);
 }
 
 }  // namespace
@@ -3804,110 +3912,29 @@ int tail_download(vad_engine *e, const vadk::TailArgs &a, vad_segment *tails_out
 extern "C" {
 
 int vad_scan_tails(vad_engine *e, vad_segment *tails_out, int64_t n) {
-    static const char *who = "vad_scan_tails";
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
-    int64_t total = 0;
-    if (int rc = tail_check_resident(e, who, tails_out, n, &total)) return rc;
-    if (n == 0) return VAD_OK;
-    if (total == 0) {                        // no frame, no tail (and no snapshot was taken)
-        std::memset(tails_out, 0, sizeof(vad_segment) * (size_t)n);
-        return VAD_OK;
-    }
-    vadk::TailArgs a;
-    if (int rc = tail_setup(e, e->d_events, e->d_probs, e->seg_out_start.data(), n, 1, nullptr, e->stream, &a)) return rc;
-    a.tail_len = e->d_tail_len;
-    if (int rc = tail_records(e, &a, e->stream)) return rc;
-    return tail_download(e, a, tails_out);
+    return scan_tails_run(e, "vad_scan_tails", false, nullptr, 1, tails_out, n);
 }
 
 int vad_scan_resegment_tails(vad_engine *e, const vad_thresholds *t, int64_t nt, vad_segment *tails_out, int64_t n) {
-    static const char *who = "vad_scan_resegment_tails";
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
-    if (int rc = reseg_check_sets(e, who, t, nt, 0)) return rc;
-    int64_t total = 0;
-    if (int rc = tail_check_resident(e, who, tails_out, n, &total)) return rc;
-    if (n == 0) return VAD_OK;
-    if (total == 0) {
-        std::memset(tails_out, 0, sizeof(vad_segment) * (size_t)n * (size_t)nt);
-        return VAD_OK;
-    }
-    vadk::ResegArgs ra;
-    vadk::TailArgs a;
-    // (the positions go up twice, once per work area: a few bytes per item)
-    if (int rc = tail_setup(e, e->d_events, e->d_probs, e->seg_out_start.data(), n, nt, nullptr, e->stream, &a)) return rc;
-    if (int rc = reseg_count(e, e->d_events, e->d_probs, e->seg_out_start.data(), n, t, nt, nullptr, e->stream, &ra, &a.tail_len)) return rc;
-    if (int rc = tail_records(e, &a, e->stream)) return rc;
-    return tail_download(e, a, tails_out);
+    return scan_tails_run(e, "vad_scan_resegment_tails", true, t, nt, tails_out, n);
 }
 
 int vad_tails_device(vad_engine *e, const int64_t *slots, const uint8_t *d_events, const float *d_probs, const int64_t *out_start, int64_t n,
                      vad_segment *d_tails, void *stream) {
-    static const char *who = "vad_tails_device";
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
-    if (n < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n = %lld: bad count", who, (long long)n);
-    if (n > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 items", who);
-    if (n > 0 && (!slots || !out_start || !d_tails)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    int64_t total = 0;
-    if (int rc = tail_check_start(e, who, out_start, n, &total)) return rc;
-    if (total > 0 && (!d_events || !d_probs)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    if ((reinterpret_cast<uintptr_t>(d_events) & 15) || (reinterpret_cast<uintptr_t>(d_tails) & 15))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the events and the tails must be 16-byte aligned", who);
-    if (reinterpret_cast<uintptr_t>(d_probs) & 3) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: probs must be 4-byte aligned", who);
-    if (int rc = check_slots(e, slots, n)) return rc;
-    if (n == 0) return VAD_OK;
-    vadk::TailArgs a;
-    int rc = tail_setup(e, d_events, d_probs, out_start, n, 1, slots, s, &a);
-    if (rc == VAD_OK) {
-        a.tails = reinterpret_cast<vadk::SegRecord *>(d_tails);
-        const hipError_t r = vadk_launch_tail_snapshot(&a, s);
-        rc = r != hipSuccess ? e->hip_fail(r, "kernel launch (tail snapshot)") : tail_records(e, &a, s);
-    }
-    // the launches read the engine's work area: the next scan, cut, extraction or replay waits for them, as behind vad_scan_device
-    if (int rc2 = scan_mark_pending(e, s)) return rc2;
-    return rc;
+    return tails_device_run(e, "vad_tails_device", false, slots, d_events, d_probs, out_start, n, nullptr, 1, d_tails, stream);
 }
 
 int vad_resegment_tails_device(vad_engine *e, const uint8_t *d_events, const float *d_probs, const int64_t *out_start, int64_t n,
                                const vad_thresholds *t, int64_t nt, vad_segment *d_tails, void *stream) {
-    static const char *who = "vad_resegment_tails_device";
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
-    if (int rc = reseg_check_sets(e, who, t, nt, 0)) return rc;
-    if (n < 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n = %lld: bad count", who, (long long)n);
-    if (n * nt > INT32_MAX)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %lld items x %lld sets: more than 2^31 - 1 replays in one call", who,
-                       (long long)n, (long long)nt);
-    if (n > 0 && (!out_start || !d_tails)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    int64_t total = 0;
-    if (int rc = tail_check_start(e, who, out_start, n, &total)) return rc;
-    if (total > 0 && (!d_events || !d_probs)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    if ((reinterpret_cast<uintptr_t>(d_events) & 15) || (reinterpret_cast<uintptr_t>(d_tails) & 15))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the events and the tails must be 16-byte aligned", who);
-    if (reinterpret_cast<uintptr_t>(d_probs) & 3) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: probs must be 4-byte aligned", who);
-    if (n == 0) return VAD_OK;
-    vadk::ResegArgs ra;
-    vadk::TailArgs a;
-    int rc = tail_setup(e, d_events, d_probs, out_start, n, nt, nullptr, s, &a);
-    if (rc == VAD_OK) rc = reseg_count(e, d_events, d_probs, out_start, n, t, nt, nullptr, s, &ra, &a.tail_len);
-    if (rc == VAD_OK) {
-        a.tails = reinterpret_cast<vadk::SegRecord *>(d_tails);
-        rc = tail_records(e, &a, s);
-    }
-    if (int rc2 = scan_mark_pending(e, s)) return rc2;
-    return rc;
+    return tails_device_run(e, "vad_resegment_tails_device", true, nullptr, d_events, d_probs, out_start, n, t, nt, d_tails, stream);
 }
 
 }  // extern "C"
@@ -3933,26 +3960,26 @@ int refine_check_rule(vad_engine *e, const char *who, const vad_refine *r, int64
     return VAD_OK;
 }
 
-// The first half of a refinement on `s`: out_start (checked as seg_launches wants it) goes up, then heads, count and prefix - the
-// true count is in *d_nsegs_out behind them.
+// The first half of a refinement on `s`: out_start (checked: check_positions) goes up as int32 next to the items' first records and
+// their counts; then heads, count and prefix - the true count is in *d_nsegs_out behind them.
 int refine_count(vad_engine *e, const vadk::SegRecord *d_segs_in, const long long *d_nsegs_in, int64_t in_cap, const vadk::SegRecord *d_tails,
                  const uint8_t *d_events, const float *d_probs, const int64_t *out_start, int64_t n, const vad_refine *r, long long *d_nsegs_out,
                  hipStream_t s, vadk::RefineArgs *a) {
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_first = up16(sizeof(int32_t) * (size_t)(n + 1)), o_cnt = o_first + up16(sizeof(uint32_t) * (size_t)n);
-    if (int rc = ensure(e, e->d_refine, e->d_refine_cap, o_cnt + sizeof(unsigned long long) * (size_t)n + 16)) return rc;
-    e->refine_up.resize((size_t)n + 1);
-    for (int64_t i = 0; i <= n; ++i) e->refine_up[(size_t)i] = n > 0 ? (int32_t)out_start[i] : 0;
-    HIP_TRY(e, hipMemcpyAsync(e->d_refine, e->refine_up.data(), sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice, s));
+    DevTables w{e->d_refine, e->d_refine_cap};
+    narrow_positions(e->refine_up, (size_t)n + 1, out_start, n);
+    const int k_start = w.add(e->refine_up, (size_t)n + 1), k_first = w.add(nullptr, sizeof(uint32_t) * (size_t)n),
+              k_cnt = w.add(nullptr, sizeof(unsigned long long) * (size_t)n);
+    if (int rc = w.reserve(e)) return rc;
+    if (int rc = w.copy(e, s)) return rc;
     *a = vadk::RefineArgs{};
     a->segs_in = d_segs_in;
     a->nsegs_in = d_nsegs_in;
     a->tails = d_tails;
     a->events = d_events;
     a->probs = d_probs;
-    a->out_start = reinterpret_cast<const int32_t *>(e->d_refine);
-    a->first = reinterpret_cast<uint32_t *>(e->d_refine + o_first);
-    a->cnt = reinterpret_cast<unsigned long long *>(e->d_refine + o_cnt);
+    a->out_start = w.at<const int32_t>(k_start);
+    a->first = w.at<uint32_t>(k_first);
+    a->cnt = w.at<unsigned long long>(k_cnt);
     a->nsegs_out = d_nsegs_out;
     a->in_cap = (uint32_t)in_cap;
     a->n = (int32_t)n;
@@ -3966,23 +3993,14 @@ int refine_count(vad_engine *e, const vadk::SegRecord *d_segs_in, const long lon
     return VAD_OK;
 }
 
-// ... and the second: the records into d_segs (room for seg_cap of them), their cuts, then their statistics
+// ... and the second: the records into d_segs (room for seg_cap of them), their cuts, then - with items - their statistics
 int refine_fill(vad_engine *e, vadk::RefineArgs *a, vadk::SegRecord *d_segs, int64_t seg_cap, hipStream_t s) {
     a->segs_out = d_segs;
     a->seg_cap = (uint32_t)std::min<int64_t>(seg_cap, INT32_MAX);
-    hipError_t r = vadk_launch_refine_fill(a, s);
+    const hipError_t r = vadk_launch_refine_fill(a, s);
     if (r != hipSuccess) return e->hip_fail(r, "kernel launch (refine fill)");
-    vadk::SegArgs st{};
-    st.events = a->events;
-    st.probs = a->probs;
-    st.out_start = a->out_start;
-    st.segs = d_segs;
-    st.nsegs = a->nsegs_out;
-    st.seg_cap = a->seg_cap;
-    st.n = a->n;
-    r = a->n > 0 ? vadk_launch_seg_stats(&st, a->seg_cap, s) : hipSuccess;
-    if (r != hipSuccess) return e->hip_fail(r, "kernel launch (segment statistics)");
-    return VAD_OK;
+    if (a->n <= 0) return VAD_OK;
+    return seg_stats(e, a->events, a->probs, a->out_start, a->n, d_segs, a->seg_cap, a->nsegs_out, a->seg_cap, s);
 }
 
 }  // namespace
@@ -3995,9 +4013,8 @@ int vad_refine_device(vad_engine *e, const vad_segment *d_segs_in, const int64_t
     static const char *who = "vad_refine_device";
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
+    hipStream_t s;
+    if (int rc = call_begin(e, true, stream, &s)) return rc;
     if (int rc = refine_check_rule(e, who, r, seg_cap)) return rc;
     if (n < 0 || in_cap < 0)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n = %lld, in_cap = %lld: bad count", who, (long long)n, (long long)in_cap);
@@ -4006,22 +4023,16 @@ int vad_refine_device(vad_engine *e, const vad_segment *d_segs_in, const int64_t
     if ((n > 0 && !out_start) || !d_nsegs_in || !d_nsegs_out || (in_cap > 0 && !d_segs_in) || (seg_cap > 0 && !d_segs_out))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
     int64_t total = 0;
-    if (int rc = tail_check_start(e, who, out_start, n, &total)) return rc;
-    if (total > 0 && (!d_events || !d_probs)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    if ((reinterpret_cast<uintptr_t>(d_events) & 15) || (reinterpret_cast<uintptr_t>(d_segs_in) & 15) || (reinterpret_cast<uintptr_t>(d_tails) & 15) ||
-        (reinterpret_cast<uintptr_t>(d_segs_out) & 15))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the events, the segment tables and the tails must be 16-byte aligned", who);
-    if (reinterpret_cast<uintptr_t>(d_probs) & 3) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: probs must be 4-byte aligned", who);
-    if ((reinterpret_cast<uintptr_t>(d_nsegs_in) & 7) || (reinterpret_cast<uintptr_t>(d_nsegs_out) & 7))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the counts must be 8-byte aligned", who);
+    if (int rc = check_positions(e, who, out_start, n, &total)) return rc;
+    if (int rc = check_device_arrays(e, who, total, d_events, {{d_segs_in, d_tails, d_segs_out}, "the events, the segment tables and the tails"},
+                                     {{d_probs}, "probs"}, {{d_nsegs_in, d_nsegs_out}, "the counts"}))
+        return rc;
     vadk::RefineArgs a;
-    int rc = refine_count(e, reinterpret_cast<const vadk::SegRecord *>(d_segs_in), reinterpret_cast<const long long *>(d_nsegs_in), in_cap,
-                          reinterpret_cast<const vadk::SegRecord *>(d_tails), d_events, d_probs, out_start, n, r,
-                          reinterpret_cast<long long *>(d_nsegs_out), s, &a);
-    if (rc == VAD_OK && seg_cap > 0) rc = refine_fill(e, &a, reinterpret_cast<vadk::SegRecord *>(d_segs_out), seg_cap, s);
-    // the launches read the engine's work area: the next scan, cut, extraction, replay or refinement waits for them
-    if (int rc2 = scan_mark_pending(e, s)) return rc2;
-    return rc;
+    int launched = refine_count(e, reinterpret_cast<const vadk::SegRecord *>(d_segs_in), reinterpret_cast<const long long *>(d_nsegs_in), in_cap,
+                                reinterpret_cast<const vadk::SegRecord *>(d_tails), d_events, d_probs, out_start, n, r,
+                                reinterpret_cast<long long *>(d_nsegs_out), s, &a);
+    if (launched == VAD_OK && seg_cap > 0) launched = refine_fill(e, &a, reinterpret_cast<vadk::SegRecord *>(d_segs_out), seg_cap, s);
+    return call_end(e, true, s, launched);
 }
 
 int vad_scan_refine(vad_engine *e, const vad_segment *segs_in, int64_t nsegs_in, const vad_segment *tails_in, const vad_refine *r,
@@ -4029,13 +4040,11 @@ int vad_scan_refine(vad_engine *e, const vad_segment *segs_in, int64_t nsegs_in,
     static const char *who = "vad_scan_refine";
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(e, hipSetDevice(e->device));
-    if (int rc = scan_wait(e)) return rc;
+    hipStream_t s;
+    if (int rc = call_begin(e, false, nullptr, &s)) return rc;
     if (int rc = refine_check_rule(e, who, r, seg_cap)) return rc;
     if (!nsegs_out || (seg_cap > 0 && !segs_out)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    if (!e->scan_results || e->seg_out_start.empty())
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: no scan results are resident: the engine's last vad_scan_segments or "
-                                            "vad_scan_rate_segments failed, or a later call has reused its per-frame arrays", who);
+    if (int rc = check_resident(e, who)) return rc;
     const int64_t n = (int64_t)e->seg_out_start.size() - 1;
     if (segs_in) {
         if (nsegs_in < 0 || nsegs_in > INT32_MAX)
@@ -4059,31 +4068,29 @@ int vad_scan_refine(vad_engine *e, const vad_segment *segs_in, int64_t nsegs_in,
         *nsegs_out = 0;
         return VAD_OK;
     }
-    // count, table and tails of a host input, and the output count, in one engine-owned block
-    const size_t o_tab = 16, o_tails = o_tab + sizeof(vad_segment) * (size_t)(segs_in ? nsegs_in : 0);
-    if (int rc = ensure(e, e->d_refine_in, e->d_refine_in_cap, o_tails + (tails_in ? sizeof(vad_segment) * (size_t)n : 0) + 16)) return rc;
+    // the input count and the output count, the table and the tails of a host input, in one engine-owned block
     const long long head[2] = {(long long)nsegs_in, 0};
-    HIP_TRY(e, hipMemcpyAsync(e->d_refine_in, head, sizeof head, hipMemcpyHostToDevice, e->stream));
-    if (segs_in && nsegs_in > 0)
-        HIP_TRY(e, hipMemcpyAsync(e->d_refine_in + o_tab, segs_in, sizeof(vad_segment) * (size_t)nsegs_in, hipMemcpyHostToDevice, e->stream));
-    if (tails_in) HIP_TRY(e, hipMemcpyAsync(e->d_refine_in + o_tails, tails_in, sizeof(vad_segment) * (size_t)n, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));             // `head` is this frame's, the rest the caller's
-    long long *d_count = reinterpret_cast<long long *>(e->d_refine_in);
+    DevTables in{e->d_refine_in, e->d_refine_in_cap};
+    const int k_head = in.add(head, sizeof head), k_tab = in.add(segs_in, sizeof(vad_segment) * (size_t)(segs_in ? nsegs_in : 0)),
+              k_tails = in.add(tails_in, tails_in ? sizeof(vad_segment) * (size_t)n : 0);
+    if (int rc = in.reserve(e)) return rc;
+    if (int rc = in.copy(e, s)) return rc;
+    HIP_TRY(e, hipStreamSynchronize(s));                     // `head` is this frame's, the rest the caller's
+    long long *d_count = in.at<long long>(k_head);
     vadk::RefineArgs a;
-    if (int rc = refine_count(e, segs_in ? reinterpret_cast<const vadk::SegRecord *>(e->d_refine_in + o_tab) : e->d_segtab, d_count, nsegs_in,
-                              tails_in ? reinterpret_cast<const vadk::SegRecord *>(e->d_refine_in + o_tails) : nullptr, e->d_events, e->d_probs,
-                              e->seg_out_start.data(), n, r, d_count + 1, e->stream, &a))
+    if (int rc = call_end(e, false, s, refine_count(e, segs_in ? in.at<const vadk::SegRecord>(k_tab) : e->d_segtab, d_count, nsegs_in,
+                                                    in.at<const vadk::SegRecord>(k_tails), e->d_events, e->d_probs, e->seg_out_start.data(), n, r,
+                                                    d_count + 1, s, &a)))
         return rc;
     long long count = 0;
-    HIP_TRY(e, hipMemcpyAsync(&count, d_count + 1, sizeof count, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    if (int rc = read_back(e, &count, d_count + 1, 1, s)) return rc;
     if (count > INT32_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %lld records: more than 2^31 - 1 in one call", who, count);
+    // the table is sized by the count that came back, as the replay's is - but there is one count, not one per set
     const int64_t take = std::min<int64_t>(count, seg_cap);
     if (take > 0) {
         if (int rc = ensure(e, e->d_refine_out, e->d_refine_out_cap, sizeof(vadk::SegRecord) * (size_t)take)) return rc;
-        if (int rc = refine_fill(e, &a, e->d_refine_out, take, e->stream)) return rc;
-        HIP_TRY(e, hipMemcpyAsync(segs_out, e->d_refine_out, sizeof(vad_segment) * (size_t)take, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(e, hipStreamSynchronize(e->stream));
+        if (int rc = refine_fill(e, &a, e->d_refine_out, take, s)) return rc;
+        if (int rc = download_records(e, segs_out, e->d_refine_out, take, s)) return rc;
     }
     *nsegs_out = count;
     return VAD_OK;

@@ -32,6 +32,43 @@ def f32(*v):
     return np.array(v, np.float32)
 
 
+def i64p(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def segp(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(_ffi.Segment))
+
+
+def i64(*v):
+    return np.array(v, np.int64)
+
+
+def thr(sets):
+    return None if sets is None else (_ffi.Thresholds * max(1, len(sets)))(*[_ffi.Thresholds(*t) for t in sets])
+
+
+def scan_items(rows):
+    return (_ffi.ScanChItem * max(1, len(rows)))(*[_ffi.ScanChItem(*map(int, r)) for r in rows])
+
+
+def resident(lib, eng, slots, p=((0.0, 0.0, 0.0), ())):
+    """vad_scan_segments of one recording per slot whose frame t has the stand-in's probability p[i][t], hop = frame: leaves the
+    per-frame results, the positions (two items of 3 and 0 frames: [0, 3, 3]), the tails' snapshot and the table resident
+    -> the table's count"""
+    f = eng.frame_samples
+    x = np.zeros(max(4, sum(len(q) for q in p) * f), np.float32)
+    rows, at = [], 0
+    for s, q in zip(slots, p):
+        x[at + np.arange(len(q)) * f] = q
+        rows.append((s, at, len(q) * f, 0, 0))
+        at += len(q) * f
+    count = np.full(1, -1, np.int64)
+    rc = lib.vad_scan_segments(eng.handle, scan_items(rows), len(rows), addr(x), x.size, 1, _ffi.VAD_FMT_F32, f, -1.0, None, 0, i64p(count))
+    assert rc == _ffi.VAD_OK, lib.vad_last_error(eng.handle).decode()
+    return int(count[0])
+
+
 def cut_items(rows):
     return (_ffi.CutItem * max(1, len(rows)))(*[_ffi.CutItem(*r) for r in rows])
 
@@ -62,3 +99,17 @@ def walk(lib, eng, call, faults, steps):
         rc = call(device, **kw)
         assert rc == _ffi.VAD_OK, (device, rc, lib.vad_last_error(eng.handle).decode())
         eng.synchronize()
+
+
+def walk_one(lib, eng, call, faults, steps):
+    """walk() for an entry point whose two forms take different arguments: call(**kw) -> rc is one form.
+    steps: (code, pattern, key, mended value)"""
+    kw = dict(faults)
+    for code, pattern, key, value in steps:
+        rc = call(**kw)
+        msg = lib.vad_last_error(eng.handle).decode()
+        assert rc == code and re.search(pattern, msg), (key, rc, msg)
+        kw[key] = value
+    rc = call(**kw)
+    assert rc == _ffi.VAD_OK, (rc, lib.vad_last_error(eng.handle).decode())
+    eng.synchronize()

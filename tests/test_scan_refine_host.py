@@ -609,3 +609,90 @@ def test_the_new_kernels_compile_without_scratch_or_spills(tmp_path):
         seen[m[0]] = m[1:]
     assert set(seen) == {"vadk_refine_init", "vadk_refine_heads", "vadk_refine_count", "vadk_refine_prefix", "vadk_refine_fill", "vadk_refine_cuts"}, seen
     assert all(v == ("0", "0", "0") for v in seen.values()), seen
+
+
+# ---- the order of the refusals ----------------------------------------------------------------------------------------
+def test_a_call_with_several_faults_gets_the_first_refusal(lib, make_engine):
+    """The order of the checks is behaviour.  vad_refine_device: the rule's fields in their order and seg_cap; the counts; 2^31 items,
+    2^31 input records; the null arguments; the positions; the null per-frame arrays; the 16-, 4- and 8-byte alignments.
+    vad_scan_refine: the rule and seg_cap, the null arguments, the resident results, then the caller's table - nsegs_in, an item out
+    of range, items that decrease, a record without frames.  (The refusal of a null segs_in without a resident table lies where the
+    caller's table is checked; a scan leaves results and table together, so no call reaches it behind the resident check.)  Every
+    fault at once, then one mended at a time; and a resident scan without a frame gives *nsegs_out = 0."""
+    from tests import refusal_order as RO
+    eng = make_engine()
+    rules = (
+        (INV, "null rule", "rule", (-1, -2, -3, 0, 1, 9)),
+        (INV, "pad_before = -1, pad_after = -2: a pad is 0 or more", "rule", (0, -2, -3, 0, 1, 9)),
+        (INV, "pad_before = 0, pad_after = -2: a pad is 0 or more", "rule", (0, 0, -3, 0, 1, 9)),
+        (INV, "merge_gap = -3: -1", "rule", (0, 0, -1, 0, 1, 9)),
+        (INV, "max_frames = 1: 0", "rule", (0, 0, -1, 0, 0, 9)),
+        (INV, "reserved = 9: must be 0", "rule", (0, 0, -1, 0, 0, 0)),
+        (INV, "seg_cap = -1: bad count", "cap", 4))
+    table = lambda *rows: np.array([r + (0, 0.0, 0.0) for r in rows], DTYPE)
+
+    def device(tab, nin, in_cap, tails, ev, probs, start, n, rule, out, cap, cnt):
+        r = rule_struct(rule)
+        return lib.vad_refine_device(eng.handle, RO.addr(tab), RO.addr(nin), in_cap, RO.addr(tails), RO.addr(ev), RO.addr(probs), RO.i64p(start), n,
+                                     None if r is None else C.byref(r), RO.addr(out), cap, RO.addr(cnt), None)
+
+    def rows(off=0):
+        b = RO.buf(48, off)
+        b.view(DTYPE)[:] = table((0, 0, 1), (0, 2, 1))
+        return b
+
+    nin = lambda off=0: (lambda b: (b.view(np.int64).__setitem__(0, 2), b)[1])(RO.buf(8, off))
+    who = "vad_refine_device: "
+    faults = dict(tab=None, nin=None, in_cap=-2, tails=RO.buf(48, 8), ev=None, probs=None, start=None, n=-1, rule=None, out=None, cap=-1, cnt=None)
+    RO.walk_one(lib, eng, device, faults, rules + (
+        (INV, "n = -1, in_cap = -2: bad count", "n", 1 << 31),
+        (INV, "n = 2147483648, in_cap = -2: bad count", "in_cap", 1 << 31),
+        (INV, r"more than 2\^31 - 1 items", "n", 2),
+        (INV, r"more than 2\^31 - 1 input records", "in_cap", 2),
+        (INV, who + "null buffer$", "start", RO.i64(-1, 3, 2)),
+        (INV, who + "null buffer$", "nin", nin(4)),
+        (INV, who + "null buffer$", "cnt", RO.buf(8, 4)),
+        (INV, who + "null buffer$", "tab", rows(8)),
+        (INV, who + "null buffer$", "out", RO.buf(96, 8)),
+        (INV, r"out_start\[0\] is negative", "start", RO.i64(0, 3, 2)),
+        (INV, r"out_start decreases at item 1 \(2 after 3\)", "start", RO.i64(0, 3, 1 << 31)),
+        (INV, r"more than 2\^31 - 1 frames in one call", "start", RO.i64(0, 3, 3)),
+        (INV, who + "null buffer$", "ev", RO.buf(16, 8)),
+        (INV, who + "null buffer$", "probs", RO.buf(16, 2)),
+        (INV, "the events, the segment tables and the tails must be 16-byte aligned", "ev", RO.buf(16)),
+        (INV, "the events, the segment tables and the tails must be 16-byte aligned", "tab", rows()),
+        (INV, "the events, the segment tables and the tails must be 16-byte aligned", "tails", RO.buf(48)),
+        (INV, "the events, the segment tables and the tails must be 16-byte aligned", "out", RO.buf(96)),
+        (INV, who + "probs must be 4-byte aligned", "probs", RO.buf(16)),
+        (INV, "the counts must be 8-byte aligned", "nin", nin()),
+        (INV, "the counts must be 8-byte aligned", "cnt", RO.buf(8))))
+
+    slots = eng.open_streams(2)
+    count = np.full(1, -7, np.int64)
+
+    def host(resident, tab, nin, tails, rule, out, cap, cnt):
+        if resident:
+            RO.resident(lib, eng, slots, resident)
+        r = rule_struct(rule)
+        return lib.vad_scan_refine(eng.handle, RO.segp(tab), nin, RO.segp(tails), None if r is None else C.byref(r), RO.segp(out), cap, RO.i64p(cnt))
+
+    try:
+        faults = dict(resident=None, tab=table((2, 0, 0), (0, 0, 0)), nin=-1, tails=np.zeros(2, DTYPE), rule=None, out=None, cap=-1, cnt=None)
+        RO.walk_one(lib, eng, host, faults, rules + (
+            (INV, "vad_scan_refine: null buffer$", "cnt", count),
+            (INV, "vad_scan_refine: null buffer$", "out", RO.buf(96)),
+            (INV, "vad_scan_refine: no scan results are resident: the engine's last vad_scan_segments or vad_scan_rate_segments failed, "
+                  "or a later call has reused its per-frame arrays$", "resident", ((0.0, 0.0, 0.0), ())),
+            (INV, "nsegs_in = -1: bad count", "nin", 2),
+            (INV, "record 0 names item 2: the scan had 2 items", "tab", table((1, 0, 0), (0, 0, 0))),
+            (INV, "record 0 has nframes = 0", "tab", table((1, 0, 1), (0, 0, 0))),
+            (INV, r"the items decrease at record 1 \(0 after 1\)", "tab", table((0, 0, 1), (0, 2, 0))),
+            (INV, "record 1 has nframes = 0", "tab", table((0, 0, 1), (0, 2, 1)))))
+        assert count[0] == 2
+        # a resident scan of no frames: no record, whatever the table
+        count[0] = -7
+        out = RO.buf(96)
+        out[:] = SENT
+        assert host(((), ()), table((0, 0, 1), (0, 2, 1)), 2, None, (0, 0, -1, 0, 0, 0), out, 4, count) == 0 and count[0] == 0 and untouched(out)
+    finally:
+        close(eng, slots)

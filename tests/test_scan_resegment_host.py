@@ -582,3 +582,64 @@ def test_the_kernel_file_compiles_without_scratch_or_spills(tmp_path):
     assert {m[0].split("vadk_reseg_")[1][:4] for m in meta} == {"coun", "pref", "fill"} and len(meta) == 3, meta
     for name, scratch, sspill, vspill in meta:
         assert (scratch, sspill, vspill) == ("0", "0", "0"), (name, scratch, sspill, vspill)
+
+
+# ---- the order of the refusals ----------------------------------------------------------------------------------------
+def test_a_call_with_several_faults_gets_the_first_refusal(lib, make_engine):
+    """The order of the checks is behaviour.  vad_resegment_device: the sets, seg_cap and the null sets; n; n x nt; the null
+    arguments; the positions; the null per-frame arrays; the 16-, 4- and 8-byte alignments.  vad_scan_resegment: the sets, the null
+    arguments, then the resident results.  Every fault at once, then one mended at a time; and a resident scan without a frame."""
+    from tests import refusal_order as RO
+    eng = make_engine()
+    two = [BASE[0], BASE[1]]
+
+    def device(ev, probs, start, n, sets, nt, segs, cap, set_start):
+        return lib.vad_resegment_device(eng.handle, RO.addr(ev), RO.addr(probs), RO.i64p(start), n, RO.thr(sets), nt, RO.addr(segs), cap,
+                                        RO.addr(set_start), None)
+
+    faults = dict(ev=None, probs=None, start=None, n=-1, sets=None, nt=0, segs=None, cap=-1, set_start=None)
+    RO.walk_one(lib, eng, device, faults, (
+        (INV, r"nt = 0: 1 \.\. 64 threshold sets", "nt", 2),
+        (INV, "seg_cap = -1: bad count", "cap", 4),
+        (INV, "vad_resegment_device: null buffer$", "sets", two),
+        (INV, "n = -1: bad count", "n", 1 << 31),
+        (INV, r"2147483648 items x 2 sets: more than 2\^31 - 1 replays", "n", 2),
+        (INV, "vad_resegment_device: null buffer$", "start", RO.i64(-1, 3, 2)),
+        (INV, "vad_resegment_device: null buffer$", "set_start", RO.buf(24, 4)),
+        (INV, "vad_resegment_device: null buffer$", "segs", RO.buf(96, 8)),
+        (INV, r"out_start\[0\] is negative", "start", RO.i64(0, 3, 2)),
+        (INV, r"out_start decreases at item 1 \(2 after 3\)", "start", RO.i64(0, 3, 1 << 31)),
+        (INV, r"more than 2\^31 - 1 frames in one call", "start", RO.i64(0, 3, 3)),
+        (INV, "vad_resegment_device: null buffer$", "ev", RO.buf(16, 8)),
+        (INV, "vad_resegment_device: null buffer$", "probs", RO.buf(16, 2)),
+        (INV, "the events and the segment table must be 16-byte aligned", "ev", RO.buf(16)),
+        (INV, "the events and the segment table must be 16-byte aligned", "segs", RO.buf(96)),
+        (INV, "vad_resegment_device: probs must be 4-byte aligned", "probs", RO.buf(16)),
+        (INV, "the set counts must be 8-byte aligned", "set_start", RO.buf(24))))
+
+    slots = eng.open_streams(2)
+    set_start = np.full(3, -7, np.int64)
+
+    def host(resident, sets, nt, segs, cap, set_start):
+        if resident:
+            RO.resident(lib, eng, slots, resident)
+        return lib.vad_scan_resegment(eng.handle, RO.thr(sets), nt, RO.segp(segs), cap, RO.i64p(set_start))
+
+    try:
+        RO.walk_one(lib, eng, host, dict(resident=None, sets=None, nt=65, segs=None, cap=-1, set_start=None), (
+            (INV, r"nt = 65: 1 \.\. 64 threshold sets", "nt", 2),
+            (INV, "seg_cap = -1: bad count", "cap", 4),
+            (INV, "vad_scan_resegment: null buffer$", "sets", two),
+            (INV, "vad_scan_resegment: null buffer$", "set_start", set_start),
+            (INV, "vad_scan_resegment: null buffer$", "segs", RO.buf(96)),
+            (INV, "vad_scan_resegment: no scan results are resident: the engine's last vad_scan_segments or vad_scan_rate_segments failed, "
+                  "or a later call has reused its per-frame arrays$", "resident", ((0.0, 0.0, 0.0), ()))))
+        assert set_start.tolist() == [0, 0, 0]
+        # a resident scan of no frames: all-zero counts, the table untouched
+        set_start[:] = -7
+        segs = RO.buf(96)
+        segs[:] = SENT
+        assert host(((), ()), two, 2, segs, 4, set_start) == 0 and set_start.tolist() == [0, 0, 0] and untouched(segs)
+    finally:
+        for s in slots:
+            eng.close_stream(int(s))

@@ -578,3 +578,90 @@ def test_the_kernel_file_compiles_without_scratch_or_spills(tmp_path):
         name = next(m[0] for m in meta if flavour in m[0])
         body = re.search(r"^%s:[^\n]*\n(.*?)^\.Lfunc_end" % re.escape(name), text, re.S | re.M).group(1)
         assert re.findall(r"\bbuffer_load_\w+", body) == ["buffer_load_dwordx4"], (name, re.findall(r"\bbuffer_load_\w+", body))
+
+
+# ---- the order of the refusals ----------------------------------------------------------------------------------------
+def test_a_call_with_several_faults_gets_the_first_refusal(lib, make_engine):
+    """The order of the checks is behaviour.  vad_segments_device: the counts, 2^31 items, the null arguments, the positions (first not
+    negative, never decreasing, at most 2^31 - 1 frames), the null per-frame arrays, then the 16-, 4- and 8-byte alignments.
+    vad_scan_segments and vad_scan_rate_segments: the rate, then the scan's own checks in the scan's order, seg_cap, the null
+    arguments.  vad_scan_segments_read: the table, the range, the null output.  Every fault at once, then one mended at a time."""
+    from tests import refusal_order as RO
+    eng = make_engine(max_streams=8)
+    seg = lambda off=0: RO.buf(24 * 4, off).view(np.uint8)
+
+    def device(ev, sf, probs, start, n, segs, cap, nsegs):
+        return lib.vad_segments_device(eng.handle, RO.addr(ev), RO.addr(sf), RO.addr(probs), RO.i64p(start), n, RO.addr(segs), cap, RO.addr(nsegs), None)
+
+    faults = dict(ev=None, sf=None, probs=None, start=None, n=-1, segs=None, cap=-1, nsegs=None)
+    RO.walk_one(lib, eng, device, faults, (
+        (INV, "n = -1, seg_cap = -1: bad count", "n", 1 << 31),
+        (INV, "n = 2147483648, seg_cap = -1: bad count", "cap", 4),
+        (INV, r"more than 2\^31 - 1 items", "n", 2),
+        (INV, "vad_segments_device: null buffer$", "start", RO.i64(-1, 3, 2)),
+        (INV, "vad_segments_device: null buffer$", "nsegs", RO.buf(8, 4)),
+        (INV, "vad_segments_device: null buffer$", "segs", seg(8)),
+        (INV, r"out_start\[0\] is negative", "start", RO.i64(0, 3, 2)),
+        (INV, r"out_start decreases at item 1 \(2 after 3\)", "start", RO.i64(0, 3, 1 << 31)),
+        (INV, r"more than 2\^31 - 1 frames in one call", "start", RO.i64(0, 3, 3)),
+        (INV, "vad_segments_device: null buffer$", "ev", RO.buf(16, 8)),
+        (INV, "vad_segments_device: null buffer$", "sf", RO.buf(16, 2)),
+        (INV, "vad_segments_device: null buffer$", "probs", RO.buf(16, 2)),
+        (INV, "the events and the segment table must be 16-byte aligned", "ev", RO.buf(16)),
+        (INV, "the events and the segment table must be 16-byte aligned", "segs", seg()),
+        (INV, "seg_frames and probs must be 4-byte aligned", "sf", RO.buf(16)),
+        (INV, "seg_frames and probs must be 4-byte aligned", "probs", RO.buf(16)),
+        (INV, "the count must be 8-byte aligned", "nsegs", RO.buf(8))))
+
+    # the host forms: one recording with a segment, one without a frame
+    frame = eng.frame_samples
+    assert lib.vad_scan_segments_read(eng.handle, -1, 5, None) == INV                     # before any table: whatever the range
+    assert "holds no segment table" in lib.vad_last_error(eng.handle).decode()
+    slots = eng.open_streams(2)
+    eng.set_thresholds_many(slots, THR)
+    x = script(ONE, frame, frame, "f32")
+    ns = x.size
+    s0, s1 = int(slots[0]), int(slots[1])
+    count = np.full(1, -7, np.int64)
+
+    def host(rate, sr_in, items, n, audio, audio_samples, channels, fmt, hop, tab, cap, cnt):
+        args = (eng.handle, RO.scan_items(items), len(items) if n is None else n, RO.addr(audio), audio_samples, channels, fmt)
+        if rate:
+            return lib.vad_scan_rate_segments(*args, sr_in, hop, -1.0, RO.segp(tab), cap, RO.i64p(cnt))
+        return lib.vad_scan_segments(*args, hop, -1.0, RO.segp(tab), cap, RO.i64p(cnt))
+
+    rest = lambda *first: [first, (s0, 0, 0, 0, 0)]
+    steps = (
+        (INV, "null buffer or bad count", "n", None),
+        (INV, "unknown frame format 9", "fmt", _ffi.VAD_FMT_F32),
+        (INV, "channels = 3, the block holds", "channels", 1),
+        (INV, "9 recordings, max_streams = 8", "items", rest(s0, 2, ns + 4, 1, 3)),
+        (INV, "hop = 6 must be a positive multiple of 4", "hop", frame),
+        (INV, "2 GiB", "audio_samples", ns),
+        (INV, "recording 0 starts at sample 2, not a multiple of 4", "items", rest(s0, 0, ns + 4, 1, 3)),
+        (INV, "recording 0 .*leaves the audio block", "items", rest(s0, 0, ns, 1, 3)),
+        (INV, "recording 0 names channel 1 of 1", "items", rest(s0, 0, ns, 0, 3)),
+        (INV, "recording 0: reserved = 3 must be 0", "items", rest(s0, 0, ns, 0, 0)),
+        (_ffi.VAD_ERR_BAD_SLOT, f"slot {s0} appears twice", "items", [(s0, 0, ns, 0, 0), (s1, 0, 0, 0, 0)]),
+        (INV, "seg_cap = -1: bad count", "cap", 4),
+        (INV, "segments: null buffer$", "cnt", count),
+        (INV, "segments: null buffer$", "tab", seg()),
+        (INV, "segments: null buffer$", "audio", x))
+    faults = dict(sr_in=11025, items=[(s0, 2, ns + 4, 1, 3)] * 9, n=-1, audio=None, audio_samples=1 << 30, channels=3, fmt=9, hop=6, tab=None,
+                  cap=-1, cnt=None)
+    try:
+        for rate in (False, True):
+            first = ((_ffi.VAD_ERR_UNSUPPORTED, "from 11025Hz to 16000Hz", "sr_in", 8000),) if rate else ()
+            count[0] = -7
+            RO.walk_one(lib, eng, host, dict(faults, rate=rate), first + steps)
+            assert count[0] >= 1
+            eng.reset(slots)
+            eng.set_thresholds_many(slots, THR)
+        read = lambda first, k, out: lib.vad_scan_segments_read(eng.handle, first, k, RO.segp(out))
+        RO.walk_one(lib, eng, read, dict(first=-1, k=5, out=None), (
+            (INV, r"records -1 \.\. \+5 leave the table of 1", "first", 0),
+            (INV, r"records 0 \.\. \+5 leave the table of 1", "k", 1),
+            (INV, "vad_scan_segments_read: null buffer$", "out", seg())))
+    finally:
+        for s in slots:
+            eng.close_stream(int(s))

@@ -685,3 +685,90 @@ def test_the_new_kernels_compile_without_scratch_or_spills(tmp_path):
             seen[m[0]] = m[1:]
     assert {"vadk_tail_snapshot", "vadk_seg_tails", "vadk_tails_reseg_count"} <= set(seen), seen
     assert all(v == ("0", "0", "0") for v in seen.values()), seen
+
+
+# ---- the order of the refusals ----------------------------------------------------------------------------------------
+def test_a_call_with_several_faults_gets_the_first_refusal(lib, make_engine):
+    """The order of the checks is behaviour.  The host forms: the sets (the replay form), the resident results, the scan's item
+    count, the null output.  The device forms: the sets (the replay form), n, 2^31 items or n x nt, the null arguments, the
+    positions, the null per-frame arrays, the 16- and 4-byte alignments, the slots; a call without items comes behind all of them
+    and writes nothing.  Every fault at once, then one mended at a time; and a resident scan without a frame gives zeroed tails."""
+    from tests import refusal_order as RO
+    eng = make_engine()
+    two = [BASE[0], BASE[1]]
+    slots = eng.open_streams(2)
+    s0, s1 = int(slots[0]), int(slots[1])
+    null = lambda who: f"{who}: null buffer$"
+
+    def tails_device(sl, ev, probs, start, n, out):
+        return lib.vad_tails_device(eng.handle, RO.i64p(sl), RO.addr(ev), RO.addr(probs), RO.i64p(start), n, RO.addr(out), None)
+
+    def reseg_device(ev, probs, start, n, sets, nt, out):
+        return lib.vad_resegment_tails_device(eng.handle, RO.addr(ev), RO.addr(probs), RO.i64p(start), n, RO.thr(sets), nt, RO.addr(out), None)
+
+    def host(resident, n, out):
+        if resident:
+            RO.resident(lib, eng, slots, resident)
+        return lib.vad_scan_tails(eng.handle, RO.segp(out), n)
+
+    def reseg_host(resident, sets, nt, n, out):
+        if resident:
+            RO.resident(lib, eng, slots, resident)
+        return lib.vad_scan_resegment_tails(eng.handle, RO.thr(sets), nt, RO.segp(out), n)
+
+    positions = (
+        (INV, r"out_start\[0\] is negative", "start", RO.i64(0, 3, 2)),
+        (INV, r"out_start decreases at item 1 \(2 after 3\)", "start", RO.i64(0, 3, 1 << 31)),
+        (INV, r"more than 2\^31 - 1 frames in one call", "start", RO.i64(0, 3, 3)))
+    arrays = lambda who: (
+        (INV, null(who), "ev", RO.buf(16, 8)),
+        (INV, null(who), "probs", RO.buf(16, 2)),
+        (INV, "the events and the tails must be 16-byte aligned", "ev", RO.buf(16)),
+        (INV, "the events and the tails must be 16-byte aligned", "out", RO.buf(96)),
+        (INV, f"{who}: probs must be 4-byte aligned", "probs", RO.buf(16)))
+    gone = "no scan results are resident: the engine's last vad_scan_segments or vad_scan_rate_segments failed, or a later call has reused " \
+           "its per-frame arrays$"
+    three = ((0.0, 0.0, 0.0), ())
+    try:
+        who = "vad_tails_device"
+        RO.walk_one(lib, eng, tails_device, dict(sl=None, ev=None, probs=None, start=None, n=-1, out=None), (
+            (INV, "n = -1: bad count", "n", 1 << 31),
+            (INV, r"more than 2\^31 - 1 items", "n", 2),
+            (INV, null(who), "sl", RO.i64(s0, s0)),
+            (INV, null(who), "start", RO.i64(-1, 3, 2)),
+            (INV, null(who), "out", RO.buf(96, 8))) + positions + arrays(who) + (
+            (_ffi.VAD_ERR_BAD_SLOT, f"slot {s0} appears twice", "sl", RO.i64(s0, s1)),))
+        who = "vad_resegment_tails_device"
+        RO.walk_one(lib, eng, reseg_device, dict(ev=None, probs=None, start=None, n=-1, sets=None, nt=0, out=None), (
+            (INV, r"nt = 0: 1 \.\. 64 threshold sets", "nt", 2),
+            (INV, null(who), "sets", two),
+            (INV, "n = -1: bad count", "n", 1 << 31),
+            (INV, r"2147483648 items x 2 sets: more than 2\^31 - 1 replays", "n", 2),
+            (INV, null(who), "start", RO.i64(-1, 3, 2)),
+            (INV, null(who), "out", RO.buf(96, 8))) + positions + arrays(who))
+        # no items: behind every check, VAD_OK, nothing written (a misaligned output is still refused)
+        out = RO.buf(96)
+        out[:] = SENT
+        assert tails_device(None, None, None, None, 0, out[8:]) == INV and reseg_device(None, None, None, 0, two, 2, out[8:]) == INV
+        assert tails_device(None, None, None, None, 0, out) == 0 and reseg_device(None, None, None, 0, two, 2, out) == 0
+        eng.synchronize()
+        assert untouched(out)
+
+        out = RO.buf(96)
+        RO.walk_one(lib, eng, host, dict(resident=None, n=5, out=None), (
+            (INV, "vad_scan_tails: " + gone, "resident", three),
+            (INV, "n = 5: the scan had 2 items", "n", 2),
+            (INV, null("vad_scan_tails"), "out", out)))
+        eng.step([s0], np.zeros((1, eng.frame_samples), np.float32))          # writes the per-frame arrays: the results are gone
+        RO.walk_one(lib, eng, reseg_host, dict(resident=None, sets=None, nt=65, n=5, out=None), (
+            (INV, r"nt = 65: 1 \.\. 64 threshold sets", "nt", 2),
+            (INV, null("vad_scan_resegment_tails"), "sets", two),
+            (INV, "vad_scan_resegment_tails: " + gone, "resident", three),
+            (INV, "n = 5: the scan had 2 items", "n", 2),
+            (INV, null("vad_scan_resegment_tails"), "out", out)))
+        # a resident scan of no frames: zeroed tails
+        for call, nbytes in ((lambda: host(((), ()), 2, out), 48), (lambda: reseg_host(((), ()), two, 2, 2, out), 96)):
+            out[:] = SENT
+            assert call() == 0 and out[:nbytes].tobytes() == bytes(nbytes) and untouched(out[nbytes:])
+    finally:
+        close(eng, slots)

@@ -4,7 +4,8 @@
 // and in push order (the stand-in model returns |first sample|, so the audio scripts the probabilities), events equal a serial
 // replay of the real state machine, segments hold exactly the frames the reference would keep; then, single-threaded: a failing
 // tick keeps the queues aligned, and a stream saved mid-segment continues bit-identically on another slot; last, one host call
-// per runner of the segment-audio family (cut, rate cut, render, mel, rate mel), for the layout of their device tables.
+// per runner of the segment-audio family (cut, rate cut, render, mel, rate mel) and of the segment-table family (segments,
+// resegment, tails, resegment-tails, refine), for the layout of their device tables.
 // Built three times by tools/san_tick/run.sh: -fsanitize=thread, -fsanitize=address,undefined, and plain.
 #include "../../include/vad_engine.h"
 #include <hip/hip_runtime.h>
@@ -402,6 +403,34 @@ int main(int argc, char **argv) {
         CHECK(std::isfinite(out[0]) && std::isfinite(out[4 * 63 - 1]));
         vad_engine_destroy(eng);
         std::printf("san_tick: segment-audio calls ok (cut, rate cut over 2 windows, render, mel, rate mel)\n");
+    }
+    // ---- the segment-table family: one host call per runner on the smallest corpus with a record and a tail - two recordings, the
+    //      first ends a segment and is inside the next at its last frame - so that each work area's slots run under the sanitizers
+    {
+        OK(vad_engine_create(&d, &eng));
+        int64_t s2[2];
+        OK(vad_stream_open_many(eng, 2, s2));
+        OK(vad_stream_set_thresholds_many(eng, s2, 2, &THR, 1));
+        const float p0[7] = {0.875f, 0.875f, 0.875f, 0.0f, 0.0f, 0.875f, 0.875f};
+        std::vector<float> block(9 * 512, 0.0f);
+        for (int k = 0; k < 7; ++k) block[(size_t)k * 512] = p0[k];
+        const vad_scan_ch_item recs[2] = {{s2[0], 0, 7 * 512, 0, 0}, {s2[1], 7 * 512, 2 * 512, 0, 0}};
+        vad_segment table[8], other[16], tails[2], tails2[4], fine[8];
+        int64_t count = -1, set_start[3] = {-1, -1, -1}, nfine = -1;
+        OK(vad_scan_segments(eng, recs, 2, block.data(), 9 * 512, 1, VAD_FMT_F32, 512, -1.0f, table, 8, &count));
+        CHECK(count == 1 && table[0].item == 0 && table[0].nframes > 0);
+        const vad_thresholds sets[2] = {THR, {0.9, 0.9, 0.5, 0.5, 1, 1}};
+        OK(vad_scan_resegment(eng, sets, 2, other, 16, set_start));
+        CHECK(set_start[0] == 0 && set_start[1] == 1 && set_start[2] == 1 && other[0].nframes == table[0].nframes);
+        OK(vad_scan_tails(eng, tails, 2));
+        CHECK(tails[0].item == 0 && tails[0].nframes > 0 && tails[1].nframes == 0);
+        OK(vad_scan_resegment_tails(eng, sets, 2, tails2, 2));
+        CHECK(tails2[0].nframes == tails[0].nframes && tails2[2].nframes == 0 && tails2[3].nframes == 0);
+        const vad_refine rule = {1, 1, -1, 0, 0, 0};
+        OK(vad_scan_refine(eng, table, count, tails, &rule, fine, 8, &nfine));
+        CHECK(nfine == 2 && fine[0].nframes >= table[0].nframes && fine[1].item == 0 && fine[1].nframes >= tails[0].nframes);
+        vad_engine_destroy(eng);
+        std::printf("san_tick: segment-table calls ok (segments, resegment, tails, resegment tails, refine)\n");
     }
     std::printf("san_tick: all ok\n");
     return 0;
