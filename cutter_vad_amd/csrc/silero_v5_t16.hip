@@ -108,10 +108,16 @@ static_assert(T_ROW_E >= T_ROWS_E1 && T_ROW_E >= 48, "enc2's planes are written 
 static_assert(T_ROW_E >= T_ROW_E0 && T_ROW_E + T_ROWS_E2 <= T_ROW_H, "enc2's planes lie in enc0's dead output and stay clear of h");
 // silero_v5_pair16 (the body's XFIRST order) writes the h planes behind barrier (4) and reads them behind (5), in front of (6): enc0's
 // output above them is dead by then, and what is written or read between (4) and (7) - enc2's planes, the x planes (rows 0 ..
-// T_ROWS_H - 1, the input half's) and the paired hand-back rows (T_ROW_E0 .. T_ROW_E0 + 63) - lies below them
-constexpr int T_ROWS_HANDBACK = 64;       // PAIR: 4 waves x 4 gates x 4 quad rows from T_ROW_E0 on, across barrier (7)
-static_assert(T_ROW_E0 + T_ROWS_HANDBACK <= T_ROW_H && T_ROWS_H <= T_ROW_E0 && T_ROW_E + T_ROWS_E2 <= T_ROW_H,
-              "frames first: the h planes, written behind barrier (4), stay clear of the x planes, enc2's planes and the hand-back rows");
+// T_ROWS_H - 1, the input half's) and the paired head exchange rows (T_ROW_E0 .. T_ROW_E0 + 31) - lies below them
+// The head exchange (the body's cell in place): half 0's rows T_ROW_E0 + 8 w + 4 half + kq carry wave (0, w)'s row tile 0 terms of both
+// tiles' head partials to wave (1, w) across barrier (8).  They are written with NO barrier since (6), while other waves are still in
+// the input half: those read the x planes (rows 0 .. T_ROWS_H - 1) and nothing else in LDS, enc0's output here has been dead since
+// barrier (4) and enc2's planes (T_ROW_E ..) since (6), whose enc3 and recurrent half are their and the h planes' last readers.
+constexpr int T_ROWS_HEADX = 32;          // PAIR: 4 waves x 2 tiles x 4 quad rows from T_ROW_E0 on, across barrier (8)
+static_assert(T_ROWS_H <= T_ROW_E0 && T_ROW_E0 + T_ROWS_HEADX <= T_ROW_H,
+              "the head exchange rows lie above the x planes, which the input half of other waves is still reading, and below the h planes");
+static_assert(T_ROW_E0 + T_ROWS_HEADX <= T_ROW_H && T_ROWS_H <= T_ROW_E0 && T_ROW_E + T_ROWS_E2 <= T_ROW_H,
+              "frames first: the h planes, written behind barrier (4), stay clear of the x planes, enc2's planes and the head exchange rows");
 static_assert(T_ROW_H >= T_ROW_E0 && T_ROW_H + T_ROWS_H <= T_ROWS, "frames first: the h planes take the place of enc0's output, dead behind barrier (4)");
 // The folded STFT operands, live (0) .. (1b).  8 kHz sub-model: the loader view from row 0 on (96 rows).  16 kHz model: the odd tile
 // runs on the bf16 split (vad_layout.h, DFT_X3_BLOCKS), so the loader cuts po | qo into planes, DENSE view: column c = rows 48 c ..

@@ -80,6 +80,18 @@
     } else {
         slot = live ? (KP(slots) ? KP(slots)[gf] : gf) : 0;
     }
+    // PAIR: the lane's stream in the partner half's tile.  The wave runs the cell of its row tile for both tiles (behind the input
+    // half), so it needs that stream's c_{t-1} and where its h' and c' go; nothing in front of barrier (1) waits for this load.
+    // (a column past n takes stream 0's slot: it reads that c and stores nothing, as such columns of the own tile read slot 0's.  No
+    //  select BEHIND the load - it would put a wait for the load here, in front of the frame's requests)
+    [[maybe_unused]] bool live_o = false;
+    [[maybe_unused]] int slot_o = 0;
+    if constexpr (PAIR) {
+        const int vcol_o = (tilei ^ 1) * MT16 + n;
+        live_o = vcol_o < KP(n);
+        slot_o = live_o ? vcol_o : 0;
+        if (KP(slots)) slot_o = KP(slots)[slot_o];
+    }
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(KP(wstream)), 0, (int)KP(wstream_bytes), 0x00020000);
     const int lane16 = lane * 16;
 #define WL(blk) ldw(wrs, lane16, (blk))
@@ -335,8 +347,13 @@
         H_STATE_SM
     }
     f32x4 cst[2];                                  // c of units 32 w + 16 rt + 4 kq + i
+    if constexpr (PAIR) {                          // PAIR: of units 32 w + 16 hf + 4 kq + i, [0] the lane's own stream, [1] its stream in the partner tile
+        cst[0] = *reinterpret_cast<const f32x4 *>(KP(state) + (size_t)slot * 256 + 128 + 32 * w + 16 * hf + 4 * kq);
+        cst[1] = *reinterpret_cast<const f32x4 *>(KP(state) + (size_t)slot_o * 256 + 128 + 32 * w + 16 * hf + 4 * kq);
+    } else {
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt) cst[rt] = *reinterpret_cast<const f32x4 *>(KP(state) + (size_t)slot * 256 + 128 + 32 * w + 16 * rt + 4 * kq);
+    }
     // RS, first part at 48 kHz (the tiles that set a mixed tick's time): its first chunk is requested right BEHIND the state loads -
     // loads return in order, so the state is not delayed - and has its HBM round trip under the state's waits, the LDS writes and
     // the operator prefetch.  Same box: 43.3 -> 42.9 us (4 096 streams at 48 kHz), configs[3] 46.0 -> 45.5; for 8 / 24 kHz first
@@ -711,7 +728,7 @@
         int ws_stft = o_stft, ws_x0 = o_x0, ws_y1 = o_y1, ws_z = o_z, ws_l = o_l, ws_x3 = o_x3;
         asm volatile("" : "+s"(ws_stft), "+s"(ws_x0), "+s"(ws_y1), "+s"(ws_z), "+s"(ws_l), "+s"(ws_x3));
         // ---- recurrent gate half W_hh . h_{t-1} (4 K-steps x {4 gates x 2 row tiles}, bf16 split) with the frame ingested under it ----
-        f32x4 G[8];                               // gate q, row tile rt -> G[2 q + rt]
+        [[maybe_unused]] f32x4 G[8];              // gate q, row tile rt -> G[2 q + rt] (not PAIR)
         [[maybe_unused]] f32x4 Gp[4][2];          // PAIR: gate q's row tile hf of the wave's own tile [0] and of the partner half's [1]
         {
             [[maybe_unused]] const int wh = ws_x3 + LSTM_X3_HALF_BLOCKS;
@@ -1265,7 +1282,7 @@
         __syncthreads();   // (4) enc1 out as planes in rows 0..47
         STAMP(8);
         // XFIRST: h_{t-1} -> its planes, now that enc0's output above them is dead (rows 248..295; enc2's planes, rows 168..191, the x
-        // planes, rows 0..47, and the hand-back rows 144..207 stay clear of them), and the biases and the state machines to their
+        // planes, rows 0..47, and the head exchange rows 144..175 stay clear of them), and the biases and the state machines to their
         // places: the recurrent half reads the planes of both halves behind barrier (5)
         if constexpr (XFIRST) H_TO_LDS
 
@@ -1373,16 +1390,9 @@
             f32x4 hw[2];
 #define L_EXTRA(u) if constexpr ((u) == 24) { hw[0] = WL(ws + 128); hw[1] = WL(ws + 129); }
 #define L_FOLDREGION(u) false
-#define LP_EXTRA(v) if constexpr ((v) == 12) { hw[0] = WL(ws + 128); hw[1] = WL(ws + 129); }
-            // PAIR, hand-back: the cell below owns both row tiles of its own tile's streams.  The wave gives the partner tile's four quads
-            // (that tile's row tile hf) to wave (1 - hf, w) through the partner half's LDS - rows 144 + 16 w + 4 q + kq: enc0's output,
-            // dead there since barrier (4), and enc2's planes, dead since (6) - across barrier (7), and takes its own tile's row
-            // tile 1 - hf from where its partner put them.  Eight LDS operations per lane; the arithmetic is what it was.
+#define LP_EXTRA(v) if constexpr ((v) == 12) { hw[0] = WL(ws + 128 + hf); }      /* the head weights of the wave's own row tile */
             if constexpr (PAIR) {
                 X3P_HALF(XU_L, ws_x3, RX, ldsO, LP_EXTRA, L_FOLDREGION)
-                f32x4 *const hb = ldsO + (T_ROW_E0 + 16 * w) * QSD + nq;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) hb[4 * k * QSD] = Gp[k][1];
             } else {
             X3_HALF(XU_L, ws_x3, RX, L_EXTRA, L_FOLDREGION)
             }
@@ -1391,17 +1401,70 @@
 #undef L_FOLDREGION
             STAMP(18);
             STAMP(13);
+            if constexpr (PAIR) {
+                // PAIR, the cell in place: the wave holds all four gates of units 32 w + 16 hf + 4 kq + i for both tiles' streams
+                // (Gp[q][st]) and their c_{t-1} (cst[st]), so it runs the cell of its row tile for both tiles the moment its own
+                // MFMAs end - no barrier (7): that barrier orders the cell's rewriting of the h planes against the recurrent half's
+                // reads of them, and a one-frame launch (PAIR implies ONE: the assert below) never rewrites them; what it orders here is
+                // nothing: behind barrier (6) the other waves read the x planes (rows 0 .. T_ROWS_H - 1 of both halves) and
+                // registers only, and this wave writes global state (its own lanes' units) and the exchange rows below.
+                // Gates, c' and h' are lane-local, the parent's formulas and order.  Only the head partial crosses row tiles:
+                // part4 = fma(hw[1], relu(h'_rt1), fma(hw[0], relu(h'_rt0), 0)) - wave (0, w) forms the inner fma (WITH its zero addend:
+                // a negative weight times +0 stays +0) for both tiles and hands the two quads to wave (1, w) across barrier (8) through
+                // half 0's rows T_ROW_E0 + 8 w + 4 (the tile's half) + kq (enc0's output, dead since barrier (4), enc2's planes, dead since (6):
+                // silero_v5_t16.hip, T_ROWS_HEADX); wave (1, w) forms the outer fma, reduces as ever and writes each tile's own headp.
+                static_assert(!PAIR || ONE, "no barrier (7): nothing rewrites the h planes");
+                const uint8_t *const flagO = reinterpret_cast<const uint8_t *>(ldsO + T_LDS_F4);       // the partner half's flagL
+                float *const headpO = reinterpret_cast<float *>(ldsO + (T_ROW_H + T_ROWS_H) * QSD);    // and its headp
+                f32x4 *const hx = lds + (T_ROW_E0 + 8 * w) * QSD + nq;
+                f32x4 hr[2];
+                // (the two slots cross the launch as one register each: opaque here, so that the store addresses are formed here
+                //  and not kept, two registers apiece, from the prologue's loads on - the launch's register peak is in enc0)
+                int sl[2] = {slot, slot_o};
+                asm volatile("" : "+v"(sl[0]), "+v"(sl[1]));
+                // the head weights have long arrived (requested in unit 12); saying so HERE, in front of the state stores, keeps the
+                // wait for them from landing behind the stores, where it is a vmcnt(0) that also waits for the stores' acknowledgement
+                asm volatile("" ::"v"(hw[0]) : "memory");
+#pragma unroll
+                for (int st = 0; st < 2; ++st) {
+                    const f32x4 i4 = Gp[0][st], f4 = Gp[1][st], g4 = Gp[2][st], o4 = Gp[3][st], c4 = cst[st];
+                    const f32x4 cn = pk::fma(pk::sigmoid4(f4), c4, pk::mul(pk::sigmoid4(i4), pk::tanh4(g4)));
+                    const f32x4 hn = pk::mul(pk::sigmoid4(o4), pk::tanh4(cn));
+                    hr[st] = relu4(hn);
+                    // a rejected frame (float32 only) leaves the stream's h and c as they were; per tile, each by its own half's verdict
+                    const bool bad = f32in && (st ? flagO[n] : flagL[n]) != 0;
+                    if ((st ? live_o : live) && !bad) {
+                        float *const sp = KP(state) + (size_t)sl[st] * 256 + 32 * w + 16 * hf + 4 * kq;
+                        *reinterpret_cast<f32x4 *>(sp) = hn;
+                        *reinterpret_cast<f32x4 *>(sp + 128) = cn;
+                    }
+                }
+                if (hf == 0) {
+#pragma unroll
+                    for (int st = 0; st < 2; ++st) hx[4 * st * QSD] = pk::fma(hw[0], hr[st], f32x4{0.f, 0.f, 0.f, 0.f});   // st = the tile's half
+                }
+                STAMP(14);
+                __syncthreads();   // (8) the row tile 0 terms of the head partials are visible
+                STAMP(15);
+                if (hf != 0) {
+                    // the parent's sums in the parent's order.  The exchanges are spelled out on `lane`: __shfl_xor's own lane
+                    // arithmetic is hoisted to its first use in the STFT and held in two registers across enc0, the launch's register
+                    // peak.  (The two tiles' chains written side by side, so that their LDS round trips overlap, build with 242 / 238
+                    // registers instead of 238 / 236: not taken.)
+#pragma unroll
+                    for (int st = 0; st < 2; ++st) {
+                        const f32x4 part4 = pk::fma(hw[0], hr[st], hx[4 * (1 - st) * QSD]);     // this wave's tile st is half 1 - st
+                        float part_ = (part4.x + part4.y) + (part4.z + part4.w);
+                        part_ += __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane ^ 16) << 2, __builtin_bit_cast(int, part_)));
+                        part_ += __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, __builtin_bit_cast(int, part_)));
+                        if (kq == 0) (st ? headpO : headp)[w * 16 + n] = part_;
+                    }
+                }
+                __syncthreads();   // (8b) head partials visible
+                STAMP(16);
+            } else {
             __syncthreads();   // (7) every wave is done reading h_{t-1}
             STAMP(14);
-            if constexpr (PAIR) {
-                const f32x4 *const hb = ldsH + (T_ROW_E0 + 16 * w) * QSD + nq;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const f32x4 o = hb[4 * k * QSD];
-                    G[2 * k] = hf ? o : Gp[k][0];
-                    G[2 * k + 1] = hf ? Gp[k][0] : o;
-                }
-            }
             f32x4 part4 = f32x4{0.f, 0.f, 0.f, 0.f};
             // a rejected frame (float32 only) leaves the stream's h and c as they were: not stored, and held for the next frame
             // SCAN: so does, in every format, a frame past the end of the stream's recording
@@ -1435,9 +1498,12 @@
             part_ += __shfl_xor(part_, 16);
             part_ += __shfl_xor(part_, 32);
             if (kq == 0) headp[w * 16 + n] = part_;
+            }
         }
+        if constexpr (!PAIR) {
         __syncthreads();   // (8) head partials + new h visible
         STAMP(15);
+        }
 
         if (tid < MT16) {
             const float z = hb + ((headp[tid] + headp[16 + tid]) + (headp[32 + tid] + headp[48 + tid]));

@@ -250,6 +250,41 @@ int main(int argc, char **argv) {
 #endif
         if (S(0, w, 29)) printf("        since kernel entry: all first requests issued %.0f, h in LDS %.0f, past barrier (0) %.0f\n", a29 / tiles, a30 / tiles, a31 / tiles);
     }
+#ifdef KB_TILE16
+    if (kb_pair) {
+        // The end of the launch by half: wave (hf, w) = wave w of tile 2 b + hf.  The two tiles of a workgroup share a CU and its
+        // counter, so their stamps compare: cycles since wave (0, w) passed barrier (6).  A build whose cell runs in place (no
+        // barrier (7)) stamps 14 at the end of its cell, 15 behind barrier (8) and 16 behind (8b); before that 14 was behind
+        // barrier (7), 15 behind (8) and 16 is not written.
+        const bool inplace = S(0, 0, 16) != 0;
+        const int wgs = tiles / 2;
+        printf("launch end by half, cycles since wave (0, w) passed barrier (6); %s\n",
+               inplace ? "cell in place: input half end, cell end, behind (8), behind (8b), last store issued, acknowledged"
+                       : "input half end, behind (7), behind (8), last store issued, acknowledged");
+        for (int w = 0; w < 4; ++w) {
+            for (int hf = 0; hf < 2; ++hf) {
+                const int ks[6] = {13, 14, 15, 16, 27, 28};
+                printf("wave (%d, %d):", hf, w);
+                for (int k : ks) {
+                    if (k == 16 && !inplace) continue;
+                    double acc = 0;
+                    for (int b = 0; b < wgs; ++b) acc += (double)((long long)S(2 * b + hf, w, k) - (long long)S(2 * b, w, 12));
+                    printf(" %.0f", acc / wgs);
+                }
+                printf("\n");
+            }
+            double sk = 0, ab = 0, lo = 1e30, hi = -1e30;
+            int older1 = 0;
+            for (int b = 0; b < wgs; ++b) {
+                const double d = (double)((long long)S(2 * b + 1, w, 13) - (long long)S(2 * b, w, 13));
+                sk += d; ab += d < 0 ? -d : d; lo = std::min(lo, d); hi = std::max(hi, d);
+                older1 += d < 0;
+            }
+            printf("        skew at the end of the input half, wave (1, %d) - wave (0, %d): mean %.0f, mean |.| %.0f, min %.0f, max %.0f; wave (1, w) first in %d of %d workgroups\n",
+                   w, w, sk / wgs, ab / wgs, lo, hi, older1, wgs);
+        }
+    }
+#endif
 #endif
     return 0;
 }
