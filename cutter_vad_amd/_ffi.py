@@ -176,6 +176,14 @@ class BatchWindow(C.Structure):
 # the same record as a numpy structured dtype: the windows of a batch are np.ndarray(nw, BATCH_WINDOW_DTYPE)
 BATCH_WINDOW_DTYPE = np.dtype([("seg", np.int32), ("nrows", np.int32), ("row0", np.int64)])
 
+
+class BatchPiece(C.Structure):
+    _fields_ = [("seg", C.c_int32), ("nrows", C.c_int32), ("row0", C.c_int64), ("window", C.c_int32), ("offset", C.c_int32)]
+
+
+# the pieces of a packed batch are np.ndarray(np, BATCH_PIECE_DTYPE)
+BATCH_PIECE_DTYPE = np.dtype([("seg", np.int32), ("nrows", np.int32), ("row0", np.int64), ("window", np.int32), ("offset", np.int32)])
+
 VAD_STATS_MAX_ROWS = 131072
 VAD_BATCH_F32, VAD_BATCH_F16, VAD_BATCH_BF16 = 0, 1, 2
 VAD_BATCH_CHANNEL_MAJOR, VAD_BATCH_TIME_MAJOR = 0, 1
@@ -344,6 +352,15 @@ SIGNATURES = {
                                 _f32p, C.c_int64, _vp, C.c_int64]),
     "vad_mel_batch_device": (C.c_int, [_vp, _vp, C.c_int64, _i64p, C.c_int64, C.POINTER(Batch), C.POINTER(BatchWindow), C.c_int64, _f32p,
                                        _f32p, _f32p, C.c_int64, _vp, C.c_int64, _vp]),
+    "vad_mel_pack_plan": (C.c_int, [_i64p, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(BatchPiece), C.c_int64, _i64p, _i64p]),
+    "vad_mel_batch_packed": (C.c_int, [_vp, _f32p, C.c_int64, _i64p, C.c_int64, C.POINTER(Batch), C.POINTER(BatchPiece), C.c_int64, C.c_int64,
+                                       _f32p, _f32p, _f32p, C.c_int64, _vp, C.c_int64]),
+    "vad_mel_batch_packed_device": (C.c_int, [_vp, _vp, C.c_int64, _i64p, C.c_int64, C.POINTER(Batch), C.POINTER(BatchPiece), C.c_int64, C.c_int64,
+                                              _f32p, _f32p, _f32p, C.c_int64, _vp, C.c_int64, _vp]),
+    "vad_mel_stats_grouped": (C.c_int, [_vp, _f32p, C.c_int64, C.c_int32, _i64p, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _f32p, _i64p,
+                                        C.POINTER(C.c_uint64)]),
+    "vad_mel_stats_grouped_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _i64p, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _vp, _vp, _vp,
+                                               _vp]),
     "vad_scan_render": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32,
                                   C.c_int32, C.c_float, C.c_int32, _vp, C.c_int64]),
     "vad_scan_render_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int,

@@ -51,6 +51,7 @@ extern "C" hipError_t vadk_launch_resample_cut(const vadk::ResampleCutArgs *a, h
 extern "C" hipError_t vadk_launch_convert(const vadk::ConvertArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_mel_stats(const vadk::MelStatsArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_mel_batch(const vadk::MelBatchArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_mel_batch_packed(const vadk::MelPackArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_render(const vadk::RenderArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_cut_stereo(const vadk::CutArgs *a, const float *gains, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_render_stereo(const vadk::RenderArgs *a, hipStream_t stream);
@@ -235,6 +236,9 @@ struct vad_engine {
     uint8_t *d_melb_out = nullptr; size_t d_melb_out_cap = 0;
     std::vector<vadk::MelStatsWork> melb_work;
     std::vector<vadk::MelBatchWin> melb_win;
+    std::vector<vadk::MelPackWork> melb_pack;      // vad_mel_batch_packed: the work list, and the pieces' order by (window, offset)
+    std::vector<int64_t> melb_order;
+    std::vector<int64_t> melb_rows;                // vad_mel_stats_grouped: a group's rows
     std::vector<float> melb_f;
     // The calls that make or rewrite segment tables.  Each work area is laid out by one DevTables in the function
     // named, and has one staging block: what was uploaded, as it was, until the stream has passed the copy.
@@ -2650,27 +2654,46 @@ int melb_upload(vad_engine *e, bool dev, const float *features, MelbSrc *src, hi
 }
 
 // vad_mel_stats / _device with e->mu held
+// group == nullptr: the outputs have an entry per segment (vad_mel_stats); else per group, ngroups of them (vad_mel_stats_grouped)
 int mel_stats_run(vad_engine *e, bool dev, const char *who, const float *features, int64_t rows, int32_t n_mels, const int64_t *start, int64_t n,
-                  float *max_out, int64_t *sum_out, uint64_t *sumsq_out, void *stream) {
+                  const int32_t *group, int64_t ngroups, float *max_out, int64_t *sum_out, uint64_t *sumsq_out, void *stream) {
     hipStream_t s;
     if (int rc = call_begin(e, dev, stream, &s)) return rc;
     MelbSrc src{};
     if (int rc = melb_source(e, who, dev, features, rows, n_mels, start, n, &src)) return rc;
-    if (sum_out || sumsq_out)
+    if (group) {
+        if (ngroups < 0 || ngroups > (int64_t)INT32_MAX)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: ngroups = %lld must be 0 .. 2^31 - 1", who, (long long)ngroups);
+        for (int64_t i = 0; i < src.n; ++i)
+            if (group[i] < 0 || (int64_t)group[i] >= ngroups)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld names group %d of %lld", who, (long long)i, group[i],
+                               (long long)ngroups);
+    }
+    if ((sum_out || sumsq_out) && !group)
         for (int64_t i = 0; i < src.n; ++i)
             if (src.start[i + 1] - src.start[i] > (int64_t)VAD_STATS_MAX_ROWS)
                 return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: segment %lld has %lld rows, the sums take %d at the most", who,
                                (long long)i, (long long)(src.start[i + 1] - src.start[i]), VAD_STATS_MAX_ROWS);
+    if ((sum_out || sumsq_out) && group) {
+        e->melb_rows.assign((size_t)ngroups, 0);
+        for (int64_t i = 0; i < src.n; ++i) e->melb_rows[(size_t)group[i]] += src.start[i + 1] - src.start[i];
+        for (int64_t g = 0; g < ngroups; ++g)
+            if (e->melb_rows[(size_t)g] > (int64_t)VAD_STATS_MAX_ROWS)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: group %lld has %lld rows, the sums take %d at the most", who,
+                               (long long)g, (long long)e->melb_rows[(size_t)g], VAD_STATS_MAX_ROWS);
+    }
     if (dev && ((reinterpret_cast<uintptr_t>(max_out) & 3) || (reinterpret_cast<uintptr_t>(sum_out) & 7) || (reinterpret_cast<uintptr_t>(sumsq_out) & 7)))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the sums must be 8-byte aligned, the maxima 4-byte", who);
-    if (src.n == 0 || (!max_out && !sum_out && !sumsq_out)) return VAD_OK;
+    const int64_t nout = group ? ngroups : src.n;
+    if (nout == 0 || (!max_out && !sum_out && !sumsq_out)) return VAD_OK;
     e->melb_work.clear();
     for (int64_t i = 0; i < src.n; ++i)
         for (int64_t r = src.start[i]; r < src.start[i + 1]; r += vadk::MELB_STATS_ROWS)
-            e->melb_work.push_back(vadk::MelStatsWork{(uint32_t)i, (uint32_t)std::min<int64_t>(vadk::MELB_STATS_ROWS, src.start[i + 1] - r), (uint64_t)r});
+            e->melb_work.push_back(vadk::MelStatsWork{(uint32_t)(group ? group[i] : i), (uint32_t)std::min<int64_t>(vadk::MELB_STATS_ROWS, src.start[i + 1] - r),
+                                                      (uint64_t)r});
     if (e->melb_work.size() > (size_t)INT32_MAX)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d rows in one call", who, vadk::MELB_STATS_ROWS);
-    const size_t nn = (size_t)src.n, sumb = nn * (size_t)src.n_mels * 8u, maxb = nn * sizeof(float);
+    const size_t nn = (size_t)nout, sumb = nn * (size_t)src.n_mels * 8u, maxb = nn * sizeof(float);
     DevTables t{e->d_melb, e->d_melb_cap};
     const int work = t.add(e->melb_work, e->melb_work.size());
     if (int rc = t.reserve(e)) return rc;
@@ -2731,6 +2754,20 @@ int batch_check(vad_engine *e, const char *who, const vad_batch *b) {
     return VAD_OK;
 }
 
+// lo [nlo] without a NaN, shift and scale [nss][nm] finite (each may be null)
+int batch_affine_check(vad_engine *e, const char *who, const float *lo, size_t nlo, const float *shift, const float *scale, size_t nss, size_t nm) {
+    for (size_t i = 0; lo && i < nlo; ++i)
+        if (std::isnan(lo[i])) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: lo[%lld] is NaN", who, (long long)i);
+    for (int which = 0; which < 2; ++which) {
+        const float *v = which ? scale : shift;
+        for (size_t k = 0; v && k < nss * nm; ++k)
+            if (!std::isfinite(v[k]))
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %s[%lld][%lld] is %s, a %s is a finite number", who, which ? "scale" : "shift",
+                               (long long)(k / nm), (long long)(k % nm), std::isnan(v[k]) ? "NaN" : "infinite", which ? "scale" : "shift");
+    }
+    return VAD_OK;
+}
+
 // vad_mel_batch / _device with e->mu held.  In e->d_melb: the windows, then lo [n], shift and scale [nss][n_mels]
 int mel_batch_run(vad_engine *e, bool dev, const char *who, const float *features, int64_t rows, const int64_t *start, int64_t n, const vad_batch *b,
                   const vad_batch_window *windows, int64_t nw, const float *lo, const float *shift, const float *scale, int64_t nss, void *out,
@@ -2748,15 +2785,7 @@ int mel_batch_run(vad_engine *e, bool dev, const char *who, const float *feature
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: nss = %lld: shift and scale have 1 row or n = %lld", who, (long long)nss,
                        (long long)src.n);
     const size_t nm = (size_t)b->n_mels, nn = (size_t)src.n;
-    for (size_t i = 0; lo && i < nn; ++i)
-        if (std::isnan(lo[i])) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: lo[%lld] is NaN", who, (long long)i);
-    for (int which = 0; which < 2; ++which) {
-        const float *v = which ? scale : shift;
-        for (size_t k = 0; v && k < (size_t)nss * nm; ++k)
-            if (!std::isfinite(v[k]))
-                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %s[%lld][%lld] is %s, a %s is a finite number", who, which ? "scale" : "shift",
-                               (long long)(k / nm), (long long)(k % nm), std::isnan(v[k]) ? "NaN" : "infinite", which ? "scale" : "shift");
-    }
+    if (int rc = batch_affine_check(e, who, lo, nn, shift, scale, (size_t)nss, nm)) return rc;
     e->melb_win.resize((size_t)nw);
     for (int64_t k = 0; k < nw; ++k) {
         const vad_batch_window &w = windows[k];
@@ -2814,6 +2843,142 @@ int mel_batch_run(vad_engine *e, bool dev, const char *who, const float *feature
     a.tile = tile;
     const hipError_t r = vadk_launch_mel_batch(&a, s);
     const int rc = call_end(e, dev, s, r != hipSuccess ? e->hip_fail(r, "kernel launch (mel batch)") : VAD_OK);
+    if (rc || dev) return rc;
+    HIP_TRY(e, hipMemcpyAsync(out, e->d_melb_out, need, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    return VAD_OK;
+}
+
+// vad_mel_batch_packed / _device with e->mu held.  In e->d_melb: the work list, then lo [nw], shift and scale [nss][n_mels]
+int mel_batch_packed_run(vad_engine *e, bool dev, const char *who, const float *features, int64_t rows, const int64_t *start, int64_t n,
+                         const vad_batch *b, const vad_batch_piece *pieces, int64_t np, int64_t nw, const float *lo, const float *shift,
+                         const float *scale, int64_t nss, void *out, int64_t out_bytes, void *stream) {
+    hipStream_t s;
+    if (int rc = call_begin(e, dev, stream, &s)) return rc;
+    if (int rc = batch_check(e, who, b)) return rc;
+    MelbSrc src{};
+    if (int rc = melb_source(e, who, dev, features, rows, b->n_mels, start, n, &src)) return rc;
+    if (src.n_mels != b->n_mels)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n_mels = %d, the resident matrix has %d", who, b->n_mels, src.n_mels);
+    if (np < 0 || nw < 0 || out_bytes < 0 || (np > 0 && !pieces)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer or bad count", who);
+    if (!shift && !scale) nss = 1;
+    if (nss != 1 && nss != nw)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: nss = %lld: shift and scale have 1 row or nw = %lld", who, (long long)nss,
+                       (long long)nw);
+    const size_t nm = (size_t)b->n_mels;
+    const int64_t T = b->frames;
+    if (int rc = batch_affine_check(e, who, lo, (size_t)nw, shift, scale, (size_t)nss, nm)) return rc;
+    for (int64_t k = 0; k < np; ++k) {
+        const vad_batch_piece &p = pieces[k];
+        if (p.seg < 0 || (int64_t)p.seg >= src.n)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: piece %lld names segment %d of %lld", who, (long long)k, p.seg, (long long)src.n);
+        const int64_t M = src.start[p.seg + 1] - src.start[p.seg];
+        if (p.row0 < 0 || p.nrows < 1 || p.row0 > M || p.nrows > M - p.row0)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: piece %lld: rows %lld .. +%d of segment %d, which has %lld", who, (long long)k,
+                           (long long)p.row0, p.nrows, p.seg, (long long)M);
+        if (p.window < 0 || (int64_t)p.window >= nw)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: piece %lld names window %d of %lld", who, (long long)k, p.window, (long long)nw);
+        if (p.offset < 0 || (p.offset & 3) || (int64_t)p.offset + p.nrows > T)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: piece %lld: offset = %d with %d rows: a multiple of 4 from 0, offset + nrows <= %d "
+                           "frames", who, (long long)k, p.offset, p.nrows, b->frames);
+    }
+    // the pieces by (window, offset); a piece owns [offset, up4(offset + nrows)) of its window
+    const uint32_t tile = vadk::melb_tile((uint32_t)b->n_mels, (uint32_t)b->deltas), tiles = ((uint32_t)b->frames + tile - 1u) / tile;
+    auto groups_of = [tile](int64_t frames) -> int64_t { return (frames + tile - 1) / tile; };
+    e->melb_order.resize((size_t)np);
+    for (int64_t k = 0; k < np; ++k) e->melb_order[(size_t)k] = k;
+    std::sort(e->melb_order.begin(), e->melb_order.end(), [pieces](int64_t x, int64_t y) {
+        const vad_batch_piece &p = pieces[x], &q = pieces[y];
+        return p.window != q.window ? p.window < q.window : p.offset != q.offset ? p.offset < q.offset : x < y;
+    });
+    int64_t nwork = 0, with_pieces = 0;           // workgroups of the windows that have a piece, and those windows
+    for (int64_t k = 0, used = 0; k < np; ++k) {
+        const int64_t pk = e->melb_order[(size_t)k];
+        const vad_batch_piece &p = pieces[pk];
+        const bool first = k == 0 || pieces[e->melb_order[(size_t)k - 1]].window != p.window;
+        if (first) {
+            if (k) nwork += groups_of(T - used);
+            used = 0;
+            ++with_pieces;
+        } else if (p.offset < used) {
+            const int64_t qk = e->melb_order[(size_t)k - 1];
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: pieces %lld and %lld overlap in window %d: frames %d .. %lld and %d .. %lld",
+                           who, (long long)std::min(pk, qk), (long long)std::max(pk, qk), p.window, pieces[qk].offset, (long long)used - 1, p.offset,
+                           (long long)(((int64_t)p.offset + p.nrows + 3) & ~(int64_t)3) - 1);
+        }
+        nwork += groups_of(p.offset - used) + groups_of(p.nrows);
+        used = ((int64_t)p.offset + p.nrows + 3) & ~(int64_t)3;
+        if (k == np - 1) nwork += groups_of(T - used);
+    }
+    const size_t C = nm * (size_t)(b->deltas + 1), need = (size_t)nw * C * (size_t)b->frames * (b->dtype == VAD_BATCH_F32 ? 4u : 2u);
+    if (need > (size_t)out_bytes)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_bytes = %lld, the windows have %llu bytes", who, (long long)out_bytes,
+                       (unsigned long long)need);
+    if (nw > (int64_t)INT32_MAX || (uint64_t)nwork + (uint64_t)(nw - with_pieces) * tiles > (uint64_t)INT32_MAX)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %u frames in one call", who, tile);
+    if (nw == 0) return VAD_OK;
+    if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if (dev && (reinterpret_cast<uintptr_t>(out) & 15))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output must be 16-byte aligned", who);
+    // the work list, window by window: pad runs before, between and behind the pieces, each piece tile by tile
+    e->melb_pack.clear();
+    e->melb_pack.reserve((size_t)nwork + (size_t)(nw - with_pieces) * tiles);
+    auto pad_run = [&](int64_t w, int64_t from, int64_t to) {
+        for (int64_t t = from; t < to; t += tile)
+            e->melb_pack.push_back(vadk::MelPackWork{0u, 0u, 0u, (uint32_t)w, (uint32_t)t, (uint32_t)std::min<int64_t>(tile, to - t), 0u});
+    };
+    int64_t k = 0;
+    for (int64_t w = 0; w < nw; ++w) {
+        int64_t used = 0;
+        for (; k < np && pieces[e->melb_order[(size_t)k]].window == w; ++k) {
+            const vad_batch_piece &p = pieces[e->melb_order[(size_t)k]];
+            pad_run(w, used, p.offset);
+            const int64_t M = src.start[p.seg + 1] - src.start[p.seg];
+            for (int64_t r = 0; r < p.nrows; r += tile) {
+                const int64_t nv = std::min<int64_t>(tile, p.nrows - r);
+                e->melb_pack.push_back(vadk::MelPackWork{(uint64_t)src.start[p.seg], (uint32_t)M, (uint32_t)(p.row0 + r), (uint32_t)w,
+                                                         (uint32_t)(p.offset + r), (uint32_t)((nv + 3) & ~(int64_t)3), (uint32_t)nv});
+            }
+            used = ((int64_t)p.offset + p.nrows + 3) & ~(int64_t)3;
+        }
+        pad_run(w, used, T);
+    }
+    // lo, shift and scale go up as one table of floats, in this order
+    const size_t nlo = (size_t)nw, nsc = (size_t)nss * nm;
+    e->melb_f.assign(nlo + 2 * nsc, 0.0f);
+    DevTables t{e->d_melb, e->d_melb_cap};
+    const int work = t.add(e->melb_pack, e->melb_pack.size()), floats = t.add(e->melb_f, e->melb_f.size());
+    if (int rc = t.reserve(e)) return rc;
+    if (!dev)
+        if (int rc = ensure(e, e->d_melb_out, e->d_melb_out_cap, need)) return rc;
+    if (int rc = melb_upload(e, dev, features, &src, s)) return rc;
+    float *hl = e->melb_f.data(), *hs = hl + nlo, *hc = hs + nsc;
+    for (size_t i = 0; i < nlo; ++i) hl[i] = lo ? lo[i] : -INFINITY;
+    for (size_t i = 0; i < nsc; ++i) {
+        hs[i] = shift ? shift[i] : 0.0f;
+        hc[i] = scale ? scale[i] : 1.0f;
+    }
+    if (int rc = t.copy(e, s)) return rc;
+    vadk::MelPackArgs a{};
+    a.b.x = src.x;
+    a.b.out = dev ? out : static_cast<void *>(e->d_melb_out);
+    a.b.lo = t.at<const float>(floats);
+    a.b.shift = a.b.lo + nlo;
+    a.b.scale = a.b.shift + nsc;
+    a.b.nw = (uint32_t)nw;
+    a.b.n_mels = (uint32_t)b->n_mels;
+    a.b.frames = (uint32_t)b->frames;
+    a.b.deltas = (uint32_t)b->deltas;
+    a.b.layout = b->layout;
+    a.b.dtype = b->dtype;
+    a.b.pad_mode = b->pad_mode;
+    a.b.pad_value = b->pad_value;
+    a.b.per_seg = nss == 1 ? 0u : 1u;
+    a.b.tile = tile;
+    a.work = t.at<const vadk::MelPackWork>(work);
+    a.nwork = (uint32_t)e->melb_pack.size();
+    const hipError_t r = vadk_launch_mel_batch_packed(&a, s);
+    const int rc = call_end(e, dev, s, r != hipSuccess ? e->hip_fail(r, "kernel launch (mel batch packed)") : VAD_OK);
     if (rc || dev) return rc;
     HIP_TRY(e, hipMemcpyAsync(out, e->d_melb_out, need, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
@@ -2975,14 +3140,14 @@ int vad_mel_stats(vad_engine *e, const float *features, int64_t rows, int32_t n_
                   int64_t *sum_out, uint64_t *sumsq_out) {
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
-    return mel_stats_run(e, false, "vad_mel_stats", features, rows, n_mels, start, n, max_out, sum_out, sumsq_out, nullptr);
+    return mel_stats_run(e, false, "vad_mel_stats", features, rows, n_mels, start, n, nullptr, 0, max_out, sum_out, sumsq_out, nullptr);
 }
 
 int vad_mel_stats_device(vad_engine *e, const float *d_features, int64_t rows, int32_t n_mels, const int64_t *start, int64_t n, float *d_max_out,
                          int64_t *d_sum_out, uint64_t *d_sumsq_out, void *stream) {
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
-    return mel_stats_run(e, true, "vad_mel_stats_device", d_features, rows, n_mels, start, n, d_max_out, d_sum_out, d_sumsq_out, stream);
+    return mel_stats_run(e, true, "vad_mel_stats_device", d_features, rows, n_mels, start, n, nullptr, 0, d_max_out, d_sum_out, d_sumsq_out, stream);
 }
 
 int vad_mel_batch(vad_engine *e, const float *features, int64_t rows, const int64_t *start, int64_t n, const vad_batch *b,
@@ -2999,6 +3164,78 @@ int vad_mel_batch_device(vad_engine *e, const float *d_features, int64_t rows, c
     if (!e) return VAD_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
     return mel_batch_run(e, true, "vad_mel_batch_device", d_features, rows, start, n, b, windows, nw, lo, shift, scale, nss, d_out, out_bytes, stream);
+}
+
+int vad_mel_stats_grouped(vad_engine *e, const float *features, int64_t rows, int32_t n_mels, const int64_t *start, int64_t n, const int32_t *group,
+                          int64_t ngroups, float *max_out, int64_t *sum_out, uint64_t *sumsq_out) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return mel_stats_run(e, false, "vad_mel_stats_grouped", features, rows, n_mels, start, n, group, ngroups, max_out, sum_out, sumsq_out, nullptr);
+}
+
+int vad_mel_stats_grouped_device(vad_engine *e, const float *d_features, int64_t rows, int32_t n_mels, const int64_t *start, int64_t n,
+                                 const int32_t *group, int64_t ngroups, float *d_max_out, int64_t *d_sum_out, uint64_t *d_sumsq_out, void *stream) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return mel_stats_run(e, true, "vad_mel_stats_grouped_device", d_features, rows, n_mels, start, n, group, ngroups, d_max_out, d_sum_out, d_sumsq_out,
+                         stream);
+}
+
+int vad_mel_batch_packed(vad_engine *e, const float *features, int64_t rows, const int64_t *start, int64_t n, const vad_batch *b,
+                         const vad_batch_piece *pieces, int64_t np, int64_t nw, const float *lo, const float *shift, const float *scale, int64_t nss,
+                         void *out, int64_t out_bytes) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return mel_batch_packed_run(e, false, "vad_mel_batch_packed", features, rows, start, n, b, pieces, np, nw, lo, shift, scale, nss, out, out_bytes,
+                                nullptr);
+}
+
+int vad_mel_batch_packed_device(vad_engine *e, const float *d_features, int64_t rows, const int64_t *start, int64_t n, const vad_batch *b,
+                                const vad_batch_piece *pieces, int64_t np, int64_t nw, const float *lo, const float *shift, const float *scale,
+                                int64_t nss, void *d_out, int64_t out_bytes, void *stream) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return mel_batch_packed_run(e, true, "vad_mel_batch_packed_device", d_features, rows, start, n, b, pieces, np, nw, lo, shift, scale, nss, d_out,
+                                out_bytes, stream);
+}
+
+// the packing rule of include/vad_engine.h: host code only, no engine.  Twice over the segments: the counts, then the pieces
+int vad_mel_pack_plan(const int64_t *start, int64_t n, const int32_t *group, int32_t frames, int32_t gap, vad_batch_piece *pieces_out, int64_t cap,
+                      int64_t *npieces, int64_t *nwindows) {
+    if (!start || n < 0 || n > (int64_t)INT32_MAX || frames < 4 || frames > 65536 || (frames & 3) || gap < 0 || gap > frames) return VAD_ERR_INVALID_ARG;
+    for (int64_t i = 0; i < n; ++i)
+        if (start[i + 1] < start[i]) return VAD_ERR_INVALID_ARG;
+    const int64_t T = frames;
+    int64_t np = 0, nw = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        int64_t used = 0;
+        int32_t cur = 0;
+        np = nw = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t M = start[i + 1] - start[i];
+            const int32_t g = group ? group[i] : 0;
+            for (int64_t r = 0; r < M; r += T) {
+                const int64_t k = std::min(T, M - r);
+                int64_t offset = (used + gap + 3) & ~(int64_t)3;
+                if (nw == 0 || g != cur || offset + k > T) {
+                    ++nw;
+                    cur = g;
+                    offset = 0;
+                }
+                if (pass) pieces_out[np] = vad_batch_piece{(int32_t)i, (int32_t)k, r, (int32_t)(nw - 1), (int32_t)offset};
+                ++np;
+                used = offset + k;
+            }
+        }
+        if (pass == 0) {
+            if (nw > (int64_t)INT32_MAX) return VAD_ERR_INVALID_ARG;
+            if (npieces) *npieces = np;
+            if (nwindows) *nwindows = nw;
+            if (!pieces_out) return VAD_OK;
+            if (cap < np) return VAD_ERR_INVALID_ARG;
+        }
+    }
+    return VAD_OK;
 }
 
 int64_t vad_resample_cut_samples(const vad_engine *e, int64_t nframes, int32_t sr_in, int32_t hop) {

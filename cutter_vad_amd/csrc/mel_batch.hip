@@ -11,7 +11,7 @@
 // integer minimum - on the float32 bit patterns both move toward the larger value from the -inf the caller stored.  Integer sums
 // and a maximum do not depend on the order.
 //
-// vadk_mel_batch.  One workgroup per (window, tile of 64 or 32 frames):
+// vadk_mel_batch.  One workgroup per (window, tile of 64 or 32 frames), in melb_tile_body:
 //   1. the rows of the tile and a halo of 2 deltas rows on either side, with the row index clamped to the SEGMENT, are loaded with
 //      the lanes along mel and normalised into LDS - v = (max(x, lo) + shift) * scale - at the odd pitch n_mels | 1.
 //   2. deltas == 2: the first differences of all but the outermost two rows on either side go to a second LDS array, each taken at
@@ -21,6 +21,11 @@
 //      time - float32 one frame per lane, 16-bit types two frames per lane as one packed 4-byte store and two channels per wave -
 //      and time-major output runs them along the channels.
 // Every cell of every window is written by exactly one lane, nothing is accumulated: two runs give the same bytes.
+//
+// vadk_mel_batch_packed.  Several pieces of segments per window (vad_mel_batch_packed): one workgroup per entry of the host's work
+// list (vad_layout.h: MelPackWork) - a tile of a piece, stored at the piece's offset in its window, or a pad run of whole quads that
+// no piece owns - through the same body (melb_tile_body) with the WINDOW's lo, shift and scale.  A piece's workgroups own the cells
+// up to the next multiple of 4 behind its last row, so a packed 16-bit pair or a float32 quad never holds cells of two workgroups.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include "../../include/vad_engine.h"
@@ -88,21 +93,19 @@ __global__ void __launch_bounds__(MELB_THREADS) vadk_mel_stats(const MelStatsArg
     }
 }
 
+// The one body of both batch kernels.  A workgroup owns frames t0 .. t0 + nt - 1 of window wi: the first nv of them show rows
+// row0 .. row0 + nv - 1 of the segment of M rows whose first row in the matrix is seg_row, the rest are pad cells; lo, shift and
+// scale are taken at index aff (vadk_mel_batch: the segment; vadk_mel_batch_packed: the window).
 // DT: VAD_BATCH_F32 / F16 / BF16.  Dynamic LDS: melb_lds_floats(n_mels, deltas, tile) floats
 template <int DT>
-__global__ void __launch_bounds__(MELB_THREADS) vadk_mel_batch(const MelBatchArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float melb_lds[];
-    const uint32_t tiles = (a.frames + a.tile - 1u) / a.tile;
-    const uint32_t wi = blockIdx.x / tiles, t0 = (blockIdx.x % tiles) * a.tile;
-    const MelBatchWin w = a.win[wi];
+__device__ __forceinline__ void melb_tile_body(const MelBatchArgs &a, float *melb_lds, uint32_t wi, uint32_t t0, uint32_t nt, uint32_t nv,
+                                               uint64_t seg_row0, uint32_t M, uint32_t row0, uint32_t aff) {
     const uint32_t nm = a.n_mels, pitch = melb_pitch(nm), H = 2u * a.deltas, L = a.tile + 2u * H, C = nm * (a.deltas + 1u);
-    const uint32_t nt = a.frames - t0 < a.tile ? a.frames - t0 : a.tile;          // frames of this tile
-    const uint32_t nv = w.nrows > t0 ? (w.nrows - t0 < nt ? w.nrows - t0 : nt) : 0u;   // ... that hold a row of the window
-    const float lo = a.lo[w.seg];
-    const float *shift = a.shift + (size_t)(a.per_seg ? w.seg : 0u) * nm, *scale = a.scale + (size_t)(a.per_seg ? w.seg : 0u) * nm;
+    const float lo = a.lo[aff];
+    const float *shift = a.shift + (size_t)(a.per_seg ? aff : 0u) * nm, *scale = a.scale + (size_t)(a.per_seg ? aff : 0u) * nm;
     float *V = melb_lds, *D = melb_lds + (size_t)L * pitch - 2u * pitch;          // D's row l lies at D + l * pitch, l = 2 .. L - 3
     // LDS row l holds segment row clamp(base + l, 0, M - 1); a tile with a row has base + H <= M - 1 and base >= -H
-    const int64_t base = (int64_t)w.row0 + t0 - H, last = (int64_t)w.M - 1;
+    const int64_t base = (int64_t)row0 - H, last = (int64_t)M - 1;
     auto seg_row = [&](int64_t s) -> int64_t { return s < 0 ? 0 : s > last ? last : s; };
 
     if (nv) {
@@ -110,7 +113,7 @@ __global__ void __launch_bounds__(MELB_THREADS) vadk_mel_batch(const MelBatchArg
         const uint32_t nl = nv + 2u * H, step_r = MELB_THREADS / nm, step_j = MELB_THREADS % nm;
         uint32_t l = threadIdx.x / nm, j = threadIdx.x % nm;
         while (l < nl) {
-            const float x = a.x[((size_t)w.seg_row + (size_t)seg_row(base + l)) * nm + j];
+            const float x = a.x[((size_t)seg_row0 + (size_t)seg_row(base + l)) * nm + j];
             V[l * pitch + j] = (fmaxf(x, lo) + shift[j]) * scale[j];
             l += step_r;
             j += step_j;
@@ -141,7 +144,7 @@ __global__ void __launch_bounds__(MELB_THREADS) vadk_mel_batch(const MelBatchArg
             if (k) return 0.0f;
             return a.pad_mode == VAD_BATCH_PAD_FEATURE ? (fmaxf(a.pad_value, lo) + shift[j]) * scale[j] : a.pad_value;
         }
-        const int64_t u = (int64_t)w.row0 + t0 + tt;
+        const int64_t u = (int64_t)row0 + tt;
         if (k == 0u) return V[(H + tt) * pitch + j];
         const float *c = (a.deltas == 2u ? D : V) + j;
         if (k == 1u && a.deltas == 2u) return c[(H + tt) * pitch];
@@ -180,6 +183,25 @@ __global__ void __launch_bounds__(MELB_THREADS) vadk_mel_batch(const MelBatchArg
     }
 }
 
+template <int DT>
+__global__ void __launch_bounds__(MELB_THREADS) vadk_mel_batch(const MelBatchArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float melb_lds[];
+    const uint32_t tiles = (a.frames + a.tile - 1u) / a.tile;
+    const uint32_t wi = blockIdx.x / tiles, t0 = (blockIdx.x % tiles) * a.tile;
+    const MelBatchWin w = a.win[wi];
+    const uint32_t nt = a.frames - t0 < a.tile ? a.frames - t0 : a.tile;          // frames of this tile
+    const uint32_t nv = w.nrows > t0 ? (w.nrows - t0 < nt ? w.nrows - t0 : nt) : 0u;   // ... that hold a row of the window
+    melb_tile_body<DT>(a, melb_lds, wi, t0, nt, nv, w.seg_row, w.M, w.row0 + t0, w.seg);
+}
+
+// one workgroup per entry of the host's work list: a tile of a piece, or a pad run
+template <int DT>
+__global__ void __launch_bounds__(MELB_THREADS) vadk_mel_batch_packed(const MelPackArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float melb_lds[];
+    const MelPackWork w = a.work[blockIdx.x];
+    melb_tile_body<DT>(a.b, melb_lds, w.window, w.t0, w.nt, w.nv, w.seg_row, w.M, w.row0, w.window);
+}
+
 extern "C" hipError_t vadk_launch_mel_stats(const MelStatsArgs *a, hipStream_t stream) {
     (void)hipGetLastError();
     if (a->nwork == 0) return hipSuccess;
@@ -205,5 +227,25 @@ extern "C" hipError_t vadk_launch_mel_batch(const MelBatchArgs *a, hipStream_t s
     }
     VADK_MELB(VAD_BATCH_F32) VADK_MELB(VAD_BATCH_F16) VADK_MELB(VAD_BATCH_BF16)
 #undef VADK_MELB
+    return hipErrorInvalidValue;
+}
+
+extern "C" hipError_t vadk_launch_mel_batch_packed(const MelPackArgs *a, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (a->nwork == 0) return hipSuccess;
+    if (a->b.tile != melb_tile(a->b.n_mels, a->b.deltas)) return hipErrorInvalidValue;
+    const size_t lds = sizeof(float) * (size_t)melb_lds_floats(a->b.n_mels, a->b.deltas, a->b.tile);
+#define VADK_MELP(DT)                                                                                                               \
+    if (a->b.dtype == DT) {                                                                                                         \
+        if (lds > 48u * 1024u) {                                                                                                    \
+            const hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void *>(&vadk_mel_batch_packed<DT>),                    \
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
+            if (r != hipSuccess) return r;                                                                                          \
+        }                                                                                                                           \
+        hipLaunchKernelGGL((vadk_mel_batch_packed<DT>), dim3(a->nwork), dim3(MELB_THREADS), lds, stream, *a);                       \
+        return hipGetLastError();                                                                                                   \
+    }
+    VADK_MELP(VAD_BATCH_F32) VADK_MELP(VAD_BATCH_F16) VADK_MELP(VAD_BATCH_BF16)
+#undef VADK_MELP
     return hipErrorInvalidValue;
 }

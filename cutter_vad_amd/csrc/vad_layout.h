@@ -765,6 +765,26 @@ __host__ __device__ inline uint32_t melb_lds_floats(uint32_t n_mels, uint32_t de
 __host__ __device__ inline uint32_t melb_tile(uint32_t n_mels, uint32_t deltas) {
     return melb_lds_floats(n_mels, deltas, 64u) * 4u <= 65536u ? 64u : 32u;
 }
+// vadk_mel_batch_packed (vad_mel_batch_packed): several pieces of segments per window.  The host lists one workgroup per (piece,
+// tile of `tile` frames of the piece) and one per pad run of at most `tile` frames, a span of whole quads of a window that no piece
+// owns.  A workgroup owns frames t0 .. t0 + nt - 1 of its window - t0 and nt multiples of 4: the packed two-frame 16-bit store and a
+// float32 quad never hold cells of two owners - of which the first nv show segment rows row0 .. row0 + nv - 1 and the rest are pad
+// cells.  MelBatchArgs as above with win unused, lo [nw] and shift / scale [1 or nw][n_mels] indexed by WINDOW.
+struct MelPackWork {
+    uint64_t seg_row;         // first row of the piece's segment in the matrix
+    uint32_t M;               // rows of the segment (a pad run: 0)
+    uint32_t row0;            // the segment row at frame t0
+    uint32_t window, t0;
+    uint32_t nt;              // 4 .. tile, a multiple of 4, t0 + nt <= frames
+    uint32_t nv;              // 0 .. nt (a pad run: 0), row0 + nv <= M
+};
+static_assert(sizeof(MelPackWork) == 32, "MelPackWork layout");
+struct MelPackArgs {
+    MelBatchArgs b;
+    const MelPackWork *work;  // [nwork]
+    uint32_t nwork;
+};
+static_assert(sizeof(MelPackArgs) == 104, "MelPackArgs layout");
 // float32 -> bfloat16 bits, round to nearest even; overflow becomes inf, a NaN stays one
 __host__ __device__ inline uint16_t melb_bf16(uint32_t bits) {
     if ((bits & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((bits >> 16) | 0x40u);

@@ -1194,24 +1194,38 @@ class Engine:
         return (x, None if x is None else x.ctypes.data_as(C.POINTER(C.c_float)), 0 if x is None else x.shape[0], 0 if x is None else x.shape[1],
                 st, None if st is None else st.ctypes.data_as(C.POINTER(C.c_int64)), 0 if st is None else st.size - 1)
 
-    def mel_stats(self, features=None, start=None, moments: bool = True) -> dict:
+    def mel_stats(self, features=None, start=None, moments: bool = True, group=None) -> dict:
         """Per-segment statistics of a feature matrix, reduced on the GPU (``vad_mel_stats``): ``features`` [rows, n_mels] float32 with
         the segments' first rows ``start`` [n + 1], or ``None`` for the resident matrix and its starts.  -> ``{"max": float32 [n]}`` -
         a segment's largest value, -inf for one without rows - and, with ``moments``, ``"sum"`` int64 [n, n_mels] and ``"sumsq"`` uint64
         [n, n_mels] of ``q = rint(clip(x, -2048, 2048) * 4096)`` and ``q * q``: exact integers, ``cutter_vad_amd.scan.batch_affine`` turns
-        them into means and deviations.  With ``moments`` a segment has 2^17 rows at the most."""
+        them into means and deviations.  With ``moments`` a segment has 2^17 rows at the most.  ``group`` [n] (``vad_mel_stats_grouped``):
+        the statistics of every group of segments instead - ``max(group) + 1`` entries, or ``group=(array, ngroups)``; a group without
+        rows has -inf and 0, and the 2^17 rows bound a group."""
         x, xp, rows, nm, st, sp, n = self._batch_source(features, start)
+        gr = ng = None
+        if group is not None:
+            gr, ng = group if isinstance(group, tuple) else (group, None)
+            gr = np.ascontiguousarray(np.asarray(gr, np.int32).reshape(-1))
+            ng = (int(gr.max(initial=-1)) + 1) if ng is None else int(ng)
         with self._scan_lock:
             if x is None or st is None:
                 r_rows, r_nm, r_n = self.mel_resident()
                 rows, nm = (r_rows, r_nm) if x is None else (rows, nm)
                 n = r_n if st is None else n
-            out = {"max": np.empty(n, np.float32)}
+            if gr is not None and gr.size != n:
+                raise AudioProcessingError(f"Model prediction failed: group has an entry per segment, got {gr.size} for {n}")
+            nout = n if gr is None else ng
+            out = {"max": np.empty(nout, np.float32)}
             if moments:
-                out["sum"], out["sumsq"] = np.empty((n, nm), np.int64), np.empty((n, nm), np.uint64)
-            self._check(self._lib.vad_mel_stats(self._h, xp, rows, nm, sp, n, out["max"].ctypes.data_as(C.POINTER(C.c_float)),
-                                                out["sum"].ctypes.data_as(C.POINTER(C.c_int64)) if moments else None,
-                                                out["sumsq"].ctypes.data_as(C.POINTER(C.c_uint64)) if moments else None))
+                out["sum"], out["sumsq"] = np.empty((nout, nm), np.int64), np.empty((nout, nm), np.uint64)
+            outs = (out["max"].ctypes.data_as(C.POINTER(C.c_float)), out["sum"].ctypes.data_as(C.POINTER(C.c_int64)) if moments else None,
+                    out["sumsq"].ctypes.data_as(C.POINTER(C.c_uint64)) if moments else None)
+            if gr is None:
+                self._check(self._lib.vad_mel_stats(self._h, xp, rows, nm, sp, n, *outs))
+            else:
+                gp = (gr if gr.size else np.zeros(1, np.int32)).ctypes.data_as(C.POINTER(C.c_int32))
+                self._check(self._lib.vad_mel_stats_grouped(self._h, xp, rows, nm, sp, n, gp, ng, *outs))
         return out
 
     @staticmethod
@@ -1292,6 +1306,50 @@ class Engine:
                                                        int(out_bytes), stream or None))
         chans = b.n_mels * (b.deltas + 1)
         return (w.size, chans, b.frames) if b.layout == _ffi.VAD_BATCH_CHANNEL_MAJOR else (w.size, b.frames, chans)
+
+    @staticmethod
+    def _batch_pieces(pieces):
+        p = np.ascontiguousarray(np.asarray(pieces, _ffi.BATCH_PIECE_DTYPE).reshape(-1)) if not (
+            isinstance(pieces, np.ndarray) and pieces.dtype == _ffi.BATCH_PIECE_DTYPE) else np.ascontiguousarray(pieces.reshape(-1))
+        return p, (p if p.size else np.zeros(1, _ffi.BATCH_PIECE_DTYPE)).ctypes.data_as(C.POINTER(_ffi.BatchPiece))
+
+    def mel_batch_packed(self, pieces, nw: int, batch, lo=None, shift=None, scale=None, features=None, start=None) -> np.ndarray:
+        """``mel_batch`` with several pieces of segments per window (``vad_mel_batch_packed``), one launch: ``pieces`` lists ``(seg,
+        nrows, row0, window, offset)`` - rows ``row0 .. row0 + nrows - 1`` of segment ``seg`` at frames ``offset ..`` of window
+        ``window`` (``cutter_vad_amd.scan.batch_pack`` places them) - in ``nw`` windows.  ``lo`` [nw], ``shift`` / ``scale`` [n_mels],
+        [1, n_mels] or [nw, n_mels] are indexed by WINDOW; the differences of ``deltas`` run over the SEGMENT's rows; every frame no
+        piece covers is a pad cell (``include/vad_engine.h`` has the rule).  The other arguments and the result as in ``mel_batch``,
+        B = ``nw``."""
+        x, xp, rows, nm, st, sp, n = self._batch_source(features, start)
+        with self._scan_lock:
+            if x is None:
+                nm = self.mel_resident()[1]
+            b = self._batch_record(batch, nm)
+            p, pp = self._batch_pieces(pieces)
+            _own, ptrs, nss = self._batch_affine(lo, shift, scale, b.n_mels)
+            chans = b.n_mels * (b.deltas + 1)
+            shape = (int(nw), chans, b.frames) if b.layout == _ffi.VAD_BATCH_CHANNEL_MAJOR else (int(nw), b.frames, chans)
+            out = np.empty(shape, {_ffi.VAD_BATCH_F32: np.float32, _ffi.VAD_BATCH_F16: np.float16}.get(b.dtype, np.uint16))
+            self._check(self._lib.vad_mel_batch_packed(self._h, xp, rows, sp, n, C.byref(b), pp, p.size, int(nw), *ptrs, nss,
+                                                       out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def mel_batch_packed_device(self, pieces, nw: int, batch, d_out: int, out_bytes: int, lo=None, shift=None, scale=None, d_features: int = 0,
+                                rows: int = 0, n_mels: int = 0, start=None, stream: int = 0) -> Tuple[int, ...]:
+        """``mel_batch_packed`` into device memory (``vad_mel_batch_packed_device``); the arguments as in ``mel_batch_device``.
+        Asynchronous on ``stream``.  -> the shape of the batch."""
+        st = None if start is None else np.ascontiguousarray(np.asarray(start, np.int64).reshape(-1))
+        with self._scan_lock:
+            nm = int(n_mels) if d_features else self.mel_resident()[1]
+            b = self._batch_record(batch, nm)
+            p, pp = self._batch_pieces(pieces)
+            _own, ptrs, nss = self._batch_affine(lo, shift, scale, b.n_mels)
+            self._check(self._lib.vad_mel_batch_packed_device(self._h, d_features or None, int(rows),
+                                                              None if st is None else st.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                              0 if st is None else st.size - 1, C.byref(b), pp, p.size, int(nw), *ptrs, nss,
+                                                              d_out or None, int(out_bytes), stream or None))
+        chans = b.n_mels * (b.deltas + 1)
+        return (int(nw), chans, b.frames) if b.layout == _ffi.VAD_BATCH_CHANNEL_MAJOR else (int(nw), b.frames, chans)
 
     # ------------------------------------------------------------------ rendered audio
     @staticmethod

@@ -7,6 +7,7 @@ module is for callers who hold many finished recordings of different lengths and
 
 from __future__ import annotations
 
+import ctypes as C
 from dataclasses import dataclass, replace
 from typing import List, Optional, Sequence, Tuple
 
@@ -996,6 +997,11 @@ class FeatureBatch:
     through the segment's normalisation (``pad="feature"``: a frame of silence).  Whisper's setting, with ``MelSpec``'s defaults::
 
         FeatureBatch(frames=3000, norm="whisper", pad="feature", pad_value=-10.0)
+
+    ``pack=True`` lays the segments of a recording (and channel) back to back, ``gap`` frames of padding apart, in as few windows
+    of ``frames`` rows as hold them (``batch_pack``), and normalises per WINDOW: Whisper's ``max - 8`` is a property of the 30 s
+    window.  ``scope`` names what the statistics of ``norm`` run over: ``None`` is ``"segment"`` unpacked and ``"window"`` packed;
+    ``"recording"`` (all segments of a recording and channel, the usual scope of CMVN for speaker models) goes with either.
     """
     frames: Optional[int] = None
     stride: Optional[int] = None
@@ -1006,6 +1012,9 @@ class FeatureBatch:
     dtype: str = "f32"
     pad: str = "value"
     pad_value: float = 0.0
+    pack: bool = False
+    gap: int = 0
+    scope: Optional[str] = None
 
     def check(self) -> None:
         if self.norm not in ("none", "whisper", "cmn", "cmvn"):
@@ -1020,6 +1029,17 @@ class FeatureBatch:
             raise ConfigurationError("stride", repr(self.stride), f"FeatureBatch: stride is 1 or more, got {self.stride!r}")
         if int(self.deltas) not in (0, 1, 2):
             raise ConfigurationError("deltas", repr(self.deltas), f"FeatureBatch: deltas is 0, 1 or 2, got {self.deltas!r}")
+        if self.scope not in (None, "segment", "window", "recording"):
+            raise ConfigurationError("scope", repr(self.scope), f"FeatureBatch: scope is None, 'segment', 'window' or 'recording', got {self.scope!r}")
+        if self.pack:
+            if self.frames is None or self.stride is not None or self.scope == "segment":
+                raise ConfigurationError("pack", "True", "FeatureBatch: pack=True takes a number of frames, no stride, and scope 'window' or "
+                                         f"'recording', got frames={self.frames!r}, stride={self.stride!r}, scope={self.scope!r}")
+            if int(self.gap) < 0 or int(self.gap) > int(self.frames):
+                raise ConfigurationError("gap", repr(self.gap), f"FeatureBatch: gap is 0 .. frames = {self.frames}, got {self.gap!r}")
+        elif self.scope == "window":
+            raise ConfigurationError("scope", repr(self.scope), "FeatureBatch: scope='window' goes with pack=True; unpacked windows are normalised per "
+                                     "'segment' or 'recording'")
 
     def record(self, n_mels: int) -> dict:
         """-> ``vad_batch``'s fields as ``Engine.mel_batch`` takes them (``frames`` must be set)"""
@@ -1055,6 +1075,31 @@ def batch_windows(start, frames: Optional[int] = None, stride: Optional[int] = N
     return np.array(rec, _ffi.BATCH_WINDOW_DTYPE).reshape(-1), T
 
 
+def batch_pack(start, frames: int, gap: int = 0, group=None) -> Tuple[np.ndarray, int]:
+    """Several segments per window (``vad_mel_pack_plan``; ``include/vad_engine.h`` has the rule): the segments whose first rows are
+    ``start`` [n + 1], in order, each in pieces of at most ``frames`` rows, a piece behind the window's last one at the next multiple
+    of 4 past ``gap`` frames, or at frame 0 of a new window where it does not fit or its ``group`` [n] differs -> (pieces, nw):
+    ``(seg, nrows, row0, window, offset)`` records as ``Engine.mel_batch_packed`` takes them, and the number of windows.  The
+    pieces tile the rows in order: ``start[0] + cumsum(nrows)`` are their bounds."""
+    st = np.ascontiguousarray(np.asarray(start, np.int64).reshape(-1))
+    gr = None if group is None else np.ascontiguousarray(np.asarray(group, np.int32).reshape(-1))
+    if st.size < 1 or (gr is not None and gr.size != st.size - 1):
+        raise ConfigurationError("start", repr(st[:8].tolist()), "batch_pack: start has n + 1 entries and group n")
+    lib = _ffi.lib()
+    i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+    gp = None if gr is None else (gr if gr.size else np.zeros(1, np.int32)).ctypes.data_as(i32p)
+    np_, nw = C.c_int64(0), C.c_int64(0)
+    head = (st.ctypes.data_as(i64p), st.size - 1, gp, int(frames), int(gap))
+    rc = lib.vad_mel_pack_plan(*head, None, 0, C.byref(np_), C.byref(nw))
+    pieces = np.zeros(max(int(np_.value), 0), _ffi.BATCH_PIECE_DTYPE)
+    if rc == 0 and pieces.size:
+        rc = lib.vad_mel_pack_plan(*head, pieces.ctypes.data_as(C.POINTER(_ffi.BatchPiece)), pieces.size, C.byref(np_), C.byref(nw))
+    if rc != 0:
+        raise ConfigurationError("frames", repr((frames, gap)), "batch_pack: frames is a multiple of 4 from 4 to 65536, gap 0 .. frames and start "
+                                 f"ascends, got frames={frames!r}, gap={gap!r}, start={st[:8].tolist()}")
+    return pieces, int(nw.value)
+
+
 def batch_affine(stats: Optional[dict], start, norm: str = "none", eps: float = 1e-5):
     """``Engine.mel_stats``'s result -> ``(lo, shift, scale)`` as ``Engine.mel_batch`` takes them, for ``norm``: ``"none"``: three
     ``None``; ``"whisper"``: ``lo = float32(max) - float32(8)`` per segment, ``shift`` 4, ``scale`` 0.25; ``"cmn"``: ``shift = -mean``
@@ -1084,6 +1129,17 @@ def _need_batch(engine, who: str) -> None:
                                  f"features a scan left on the GPU), {type(engine).__name__} has none")
 
 
+def _need_pack(engine, who: str, what: str) -> None:
+    if not hasattr(engine, "mel_batch_packed"):
+        raise ConfigurationError("batch", "given", f"{who}: {what} needs an engine with mel_batch_packed and grouped mel_stats, "
+                                 f"{type(engine).__name__} has none")
+
+
+def _expand_affine(affine, which):
+    """(lo, shift, scale) of groups -> of the segments or windows whose groups are ``which``; scalars and ``None`` stay"""
+    return tuple(a if a is None or np.ndim(a) == 0 else np.asarray(a)[which] for a in affine)
+
+
 def batch_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, batch: FeatureBatch, config: Optional[VADConfig] = None, engine=None,
                      hop: Optional[int] = None, law: Optional[str] = None, channel="mix", open_end: bool = False,
                      refine: Optional[SegmentRefine] = None, sample_rate: Optional[int] = None, taps=None, convert=None):
@@ -1094,10 +1150,16 @@ def batch_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, batch: Fea
     ``Engine.mel_keep``, at most one ``Engine.mel_stats`` and one ``Engine.mel_batch`` under ``Engine.scan_session()``: the features
     never leave the GPU, only the statistics and the batch cross the link.  The other arguments as in ``features_recordings``.  A
     corpus of 1-D and 2-D recordings is a ``ConfigurationError``: call it once per kind.  So is an engine object without
-    ``mel_batch``.  No segment anywhere: an array with B = 0.  ``convert`` as in ``features_recordings``."""
+    ``mel_batch``.  No segment anywhere: an array with B = 0.  ``convert`` as in ``features_recordings``.
+
+    ``batch.pack``: the segments of each (recording, channel) packed into windows (``batch_pack``): one scan, one keep, one grouped
+    ``Engine.mel_stats`` and one ``Engine.mel_batch_packed``.  ``array`` has a window per row of B, ``index`` one ``(recording,
+    channel, start_sample, end_sample, first_frame, nframes, window, offset)`` per PIECE.  ``batch.scope="recording"``, packed or
+    not, normalises with the statistics of all segments of the (recording, channel)."""
     from .pool import default_pool, resolve_model_path
     who = "batch_recordings"
     batch.check()
+    by_recording = batch.scope == "recording"
     split = isinstance(channel, str) and channel == "split"
     if not (channel in ("mix", "split") if isinstance(channel, str) else isinstance(channel, (int, np.integer)) and int(channel) in (0, 1)):
         raise ConfigurationError("channel", repr(channel), f"{who}: channel is 'mix', 0, 1 or 'split' for the whole corpus, got {channel!r}")
@@ -1106,6 +1168,8 @@ def batch_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, batch: Fea
         engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
     _need_mel(engine, who)
     _need_batch(engine, who)
+    if batch.pack or by_recording:
+        _need_pack(engine, who, "pack=True" if batch.pack else "scope='recording'")
     if open_end:
         _need_tails(engine, who)
     if refine is not None:
@@ -1156,16 +1220,46 @@ def batch_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, batch: Fea
             table = _cut_table(engine, ranges, chans, frame, hop)
             if table:
                 start = engine.mel_keep(table, arrays, hop=hop, denoise=denoise, **mel_kw)
-                windows, T = batch_windows(start, batch.frames, batch.stride)
-                stats = None if batch.norm == "none" else engine.mel_stats(moments=batch.norm != "whisper")
-                lo, shift, scale = batch_affine(stats, start, batch.norm, batch.eps)
-                rec = replace(batch, frames=T).record(n_mels)
-                out = engine.mel_batch(windows, rec, lo=lo, shift=shift, scale=scale)
+                moments = batch.norm != "whisper"
+                # the group of a segment: its (recording, channel), numbered in the table's order
+                group = np.array([i * per + c for i, rc in enumerate(ranges) for c, rg in enumerate(rc) for _ in rg], np.int32)
+                ngroups = len(recordings) * per
+                rows_of = lambda which, count: np.concatenate([[0], np.cumsum(np.bincount(which, weights=np.diff(start), minlength=count))]).astype(np.int64)
+                if batch.pack:
+                    windows, nw = batch_pack(start, batch.frames, batch.gap, group)
+                    T = int(batch.frames)
+                    if batch.norm == "none":
+                        affine = (None, None, None)
+                    elif by_recording:
+                        stats = engine.mel_stats(moments=moments, group=(group, ngroups))
+                        wgroup = np.zeros(nw, np.int64)
+                        wgroup[windows["window"]] = group[windows["seg"]]
+                        affine = _expand_affine(batch_affine(stats, rows_of(group, ngroups), batch.norm, batch.eps), wgroup)
+                    else:
+                        bounds = np.concatenate([[0], np.cumsum(windows["nrows"], dtype=np.int64)]) + start[0]
+                        stats = engine.mel_stats(start=bounds, moments=moments, group=(windows["window"], nw))
+                        wrows = np.concatenate([[0], np.cumsum(np.bincount(windows["window"], weights=windows["nrows"], minlength=nw))]).astype(np.int64)
+                        affine = batch_affine(stats, wrows, batch.norm, batch.eps)
+                    lo, shift, scale = affine
+                    out = engine.mel_batch_packed(windows, nw, batch.record(n_mels), lo=lo, shift=shift, scale=scale)
+                else:
+                    windows, T = batch_windows(start, batch.frames, batch.stride)
+                    if batch.norm == "none":
+                        lo, shift, scale = None, None, None
+                    elif by_recording:
+                        stats = engine.mel_stats(moments=moments, group=(group, ngroups))
+                        lo, shift, scale = _expand_affine(batch_affine(stats, rows_of(group, ngroups), batch.norm, batch.eps), group)
+                    else:
+                        lo, shift, scale = batch_affine(engine.mel_stats(moments=moments), start, batch.norm, batch.eps)
+                    rec = replace(batch, frames=T).record(n_mels)
+                    out = engine.mel_batch(windows, rec, lo=lo, shift=shift, scale=scale)
     finally:
         for s in slots:
             engine.close_stream(int(s))
     if out is None:
         return empty, []
     where = [(i, chans[c], a, b) for i, rc in enumerate(ranges) for c, rg in enumerate(rc) for a, b, *_ in rg]
+    if batch.pack:
+        return out, [where[int(w["seg"])] + (int(w["row0"]), int(w["nrows"]), int(w["window"]), int(w["offset"])) for w in windows]
     index = [where[int(w["seg"])] + (int(w["row0"]), int(w["nrows"])) for w in windows]
     return out, index

@@ -1061,6 +1061,74 @@ VAD_API int vad_mel_batch_device(vad_engine *e, const float *d_features /*on the
                                  void *stream);
 
 /*
+ * Packed feature batches: several segments per window.  A fixed-window model pays for every frame of a window; with one segment per
+ * window most frames of a corpus of short segments are padding.  Here the segments of a group (a recording, say) lie back to back
+ * in as few windows as hold them, each PIECE at a frame offset, with an index that restores where it came from.
+ *
+ * vad_mel_pack_plan: the packing rule.  Host code only: no engine, no GPU.  start[n + 1] are the segments' first rows (ascending),
+ * group[n] their groups (NULL: one group), frames = T, gap the frames of silence between the pieces of a window.  THE RULE, greedy
+ * and in order, with up4(x) = x rounded up to a multiple of 4:
+ *   1. Walk the segments i = 0 .. n - 1.
+ *   2. Skip a segment without rows.
+ *   3. A segment of M rows is taken in pieces of k = min(T, M - r) rows, at r = 0, T, 2T, ...
+ *   4. A piece goes to the current window at offset = up4(used + gap), where used is the end of the window's last piece.
+ *   5. A piece starts a new window at offset 0 in three cases: there is no window yet, the piece's group differs from the
+ *      window's, or offset + k > T.
+ * So windows never mix groups, a segment longer than T fills whole windows, and its remainder opens a window that later segments
+ * may join.  The pieces tile [start[0], start[n]) in order: their bounds are themselves an ascending start array of npieces + 1
+ * entries.  *npieces and *nwindows (each may be NULL) get the counts; pieces_out = NULL counts only, else it takes the pieces and
+ * cap is its room.  Refusals (VAD_ERR_INVALID_ARG, pieces_out untouched): T not a multiple of 4 in 4 .. 65536; gap outside 0 .. T;
+ * a start that does not ascend; n outside 0 .. 2^31 - 1; cap smaller than the count (the counts are still stored).
+ *
+ * vad_mel_batch_packed / _device: nw windows of b->frames = T frames holding np pieces.  The sources, layouts, number formats,
+ * vad_batch fields and their checks are those of vad_mel_batch.  THE RULE: it is vad_mel_batch's rule, with lo[nw], shift and scale
+ * [nss][n_mels] (nss = 1 or nw) indexed by WINDOW.  For a piece of window w at `offset`, cell (w, channel, offset + t) with t <
+ * nrows is v, d1 or d2 of segment row row0 + t, with v = (fmaxf(x, lo[w]) + shift[w][j]) * scale[w][j]; the deltas are clamped to the
+ * SEGMENT: a later piece of a split segment sees the earlier piece's rows.  Every cell that no piece covers is a pad cell - the
+ * cells between pieces, behind the last piece, a whole window without pieces: 0 in the delta channels, in the static channels
+ * pad_value, or pad_value through the window's normalisation.  Every cell of every window is written exactly once, by ONE launch.
+ * Two runs give the same bytes: no atomics, no float accumulation.  The pieces may come in any order; a segment, or the same rows,
+ * may be shown twice.
+ * Refusals (VAD_ERR_INVALID_ARG, a message, by index, the output untouched), in this order: those of vad_mel_batch up to its
+ * windows, with nss = 1 or nw and lo[nw]; a piece with seg, row0 or nrows outside its segment, or nrows < 1; window outside 0 ..
+ * nw - 1; offset negative, not a multiple of 4, or with offset + nrows > T; two pieces of one window whose spans [offset,
+ * up4(offset + nrows)) overlap; out_bytes below nw * C * T elements; more than 2^31 - 1 workgroups; then the output pointer as in
+ * vad_mel_batch.  np = 0 with nw > 0 writes pad windows.  nw = 0 is VAD_OK.
+ *
+ * vad_mel_stats_grouped / _device: vad_mel_stats with group[n] (host; 0 .. ngroups - 1) and outputs of ngroups entries: group g's
+ * maximum and sums are the reduction over every segment i with group[i] == g; a group without rows gets -inf and 0; the
+ * VAD_STATS_MAX_ROWS bound applies to a group's total rows when a sum is asked for.  group = NULL is the identity (ngroups is not
+ * read): vad_mel_stats's bytes.  Window scope is one call: start = the piece bounds, group = the pieces' windows.
+ *   Every engine is served.  VAD_ABI_VERSION is unchanged: the presence of vad_mel_batch_packed is how a caller detects the feature.
+ */
+typedef struct vad_batch_piece {
+    int32_t seg;       /* index into the segments */
+    int32_t nrows;     /* 1 .. T */
+    int64_t row0;      /* first row, within the segment */
+    int32_t window;    /* 0 .. nw - 1 */
+    int32_t offset;    /* first frame of the piece in its window: a multiple of 4, offset + nrows <= T */
+} vad_batch_piece;     /* 24 bytes */
+VAD_API int vad_mel_pack_plan(const int64_t *start /*[n + 1]*/, int64_t n, const int32_t *group /*[n] or NULL: one group*/, int32_t frames /*T*/,
+                              int32_t gap, vad_batch_piece *pieces_out /*or NULL: count only*/, int64_t cap, int64_t *npieces,
+                              int64_t *nwindows);
+VAD_API int vad_mel_batch_packed(vad_engine *e, const float *features /*or NULL: resident*/, int64_t rows, const int64_t *start /*or NULL*/,
+                                 int64_t n, const vad_batch *b, const vad_batch_piece *pieces /*host*/, int64_t np, int64_t nw,
+                                 const float *lo /*[nw] or NULL*/, const float *shift /*[nss][n_mels] or NULL*/,
+                                 const float *scale /*[nss][n_mels] or NULL*/, int64_t nss /*1 or nw*/, void *out, int64_t out_bytes);
+VAD_API int vad_mel_batch_packed_device(vad_engine *e, const float *d_features /*on the GPU or NULL*/, int64_t rows,
+                                        const int64_t *start /*host [n + 1] or NULL*/, int64_t n, const vad_batch *b,
+                                        const vad_batch_piece *pieces /*host*/, int64_t np, int64_t nw, const float *lo /*host*/,
+                                        const float *shift /*host*/, const float *scale /*host*/, int64_t nss, void *d_out, int64_t out_bytes,
+                                        void *stream);
+VAD_API int vad_mel_stats_grouped(vad_engine *e, const float *features /*[rows][n_mels] or NULL*/, int64_t rows, int32_t n_mels,
+                                  const int64_t *start /*[n + 1] or NULL*/, int64_t n, const int32_t *group /*host [n] or NULL*/,
+                                  int64_t ngroups, float *max_out /*[ngroups] or NULL*/, int64_t *sum_out /*[ngroups][n_mels] or NULL*/,
+                                  uint64_t *sumsq_out /*[ngroups][n_mels] or NULL*/);
+VAD_API int vad_mel_stats_grouped_device(vad_engine *e, const float *d_features /*on the GPU or NULL*/, int64_t rows, int32_t n_mels,
+                                         const int64_t *start /*host [n + 1] or NULL*/, int64_t n, const int32_t *group /*host [n] or NULL*/,
+                                         int64_t ngroups, float *d_max_out, int64_t *d_sum_out, uint64_t *d_sumsq_out, void *stream);
+
+/*
  * Rendered audio: one finished piece of audio per call - the segments of a block faded at their edges, crossfaded where two of
  * them share output samples, joined, everything else silence.  The two standard products of a VAD come out of it by where the caller
  * places the segments: silence removal (the segments back to back, neighbours overlapping by the ramp or a fixed pause apart) and

@@ -1514,6 +1514,128 @@ def scan_mel_batch():
     return row
 
 
+def scan_mel_pack():
+    """What packing several segments into a window saves, on scan_mel_batch's corpus and setting with Whisper's own
+    window: float16, T = 3 000.  The windows and bytes of the unpacked batch (batch_windows: a window per segment) and of the packed
+    one (batch_pack per recording), exact counts.  (a) the unpacked route, the parent's unchanged code - Engine.mel_keep +
+    Engine.mel_stats(moments=False) + Engine.mel_batch_device - and (b) the packed one - mel_keep + batch_pack + the grouped
+    mel_stats over the windows + Engine.mel_batch_packed_device - each up to the synchronise; (a) and (b) alternate, one warm-up and
+    three timed passes, medians.  (c) the two batch calls alone on the resident matrix, HIP-event timed as scan_mel_batch's (c).
+    The result goes to profiles/scan_mel_pack.json."""
+    import ctypes as C
+    import time
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    from cutter_vad_amd import FeatureBatch, MelSpec, batch_pack, batch_windows
+    N = int(os.environ.get("VAD_SCAN_BENCH_N", "1024"))
+    eng = Engine(blob(5), max_streams=max(N, 16))
+    hop, T = 256, 3000
+    pcm = np.tile(np.load(os.path.join(root, "tests", "golden", "speech16k_i16.npz"))["pcm"].astype(np.int16), 3)
+    rng = np.random.default_rng(N)
+    ns = 30 * 16000
+    recs = [pcm[a:a + ns] for a in rng.integers(0, pcm.size - ns + 1, N)]
+    slots = eng.open_streams(N)
+    eng.set_thresholds_many(slots, (0.4, 0.3, 0.8, 0.95, 6, 12))
+    med = lambda v: float(np.median(v))
+    arrays = MelSpec(16000).operators()
+    rec = FeatureBatch(frames=T, norm="whisper", pad="feature", pad_value=-10.0, dtype="f16").record(80)
+    row = {"config": f"scan_mel_pack: {N} int16 recordings of 30 s at 16 kHz in one call, hop {hop}, Whisper's geometry and normalisation, "
+                     f"float16 windows of {T} frames, unpacked against packed per recording", "recordings": N, "passes": 3}
+    with eng.scan_session():
+        table = eng.scan_segments(slots, recs, hop=hop, denoise=0.01)
+        offs = [int(o) for o in eng.last_scan["offsets"]]
+        items = table["item"].tolist()
+        segs = [(offs[i], a, n) for i, a, n in zip(items, table["first_frame"].tolist(), table["nframes"].tolist())]
+        group = np.asarray(items, np.int32)
+        start = eng.mel_keep(segs, arrays, hop=hop, denoise=0.01)
+        windows, _ = batch_windows(start, T)
+        pieces, nw = batch_pack(start, T, 0, group)
+        a_bytes, b_bytes = windows.size * 80 * T * 2, nw * 80 * T * 2
+        d_out = torch.empty(a_bytes // 2 + 8, dtype=torch.float16, device="cuda")
+        rows = int(start[-1])
+        row.update(segments=len(segs), rows=rows, matrix_bytes=rows * 320, a_windows=int(windows.size), a_batch_bytes=a_bytes,
+                   a_padding_share=1.0 - rows / (windows.size * T), b_pieces=int(pieces.size), b_windows=nw, b_batch_bytes=b_bytes,
+                   b_padding_share=1.0 - rows / (nw * T))
+
+        def route_a():
+            eng.mel_keep(segs, arrays, hop=hop, denoise=0.01)
+            lo = eng.mel_stats(moments=False)["max"] - np.float32(8.0)
+            eng.mel_batch_device(windows, rec, d_out.data_ptr(), a_bytes, lo=lo, shift=4.0, scale=0.25)
+            eng.synchronize()
+
+        def route_b():
+            st = eng.mel_keep(segs, arrays, hop=hop, denoise=0.01)
+            p, k = batch_pack(st, T, 0, group)
+            bounds = np.concatenate([[0], np.cumsum(p["nrows"], dtype=np.int64)])
+            lo = eng.mel_stats(start=bounds, moments=False, group=(p["window"], k))["max"] - np.float32(8.0)
+            eng.mel_batch_packed_device(p, k, rec, d_out.data_ptr(), b_bytes, lo=lo, shift=4.0, scale=0.25)
+            eng.synchronize()
+
+        route_a()
+        route_b()
+        a_runs, b_runs = [], []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            route_a()
+            a_runs.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            route_b()
+            b_runs.append(time.perf_counter() - t0)
+        row.update(a_s_keep_stats_batch_runs=a_runs, a_s_keep_stats_batch=med(a_runs), b_s_keep_pack_stats_batch_runs=b_runs,
+                   b_s_keep_pack_stats_batch=med(b_runs), ratio_a_over_b=med(a_runs) / med(b_runs))
+        # (c) the two batch calls alone, on the resident matrix
+        ts = torch.cuda.Stream()
+        busy = torch.randn(6144, 6144, device="cuda")
+        lib, h = eng._lib, eng.handle
+        b = eng._batch_record(rec, 80)
+        w, wp = eng._batch_windows(windows)
+        p, pp = eng._batch_pieces(pieces)
+        lo_a = eng.mel_stats(moments=False)["max"] - np.float32(8.0)
+        bounds = np.concatenate([[0], np.cumsum(pieces["nrows"], dtype=np.int64)])
+        lo_b = eng.mel_stats(start=bounds, moments=False, group=(pieces["window"], nw))["max"] - np.float32(8.0)
+        sh, sc = np.full((1, 80), 4.0, np.float32), np.full((1, 80), 0.25, np.float32)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+
+        def event_timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            with torch.cuda.stream(ts):
+                torch.mm(busy, busy)
+            e0.record(ts)
+            assert fn() == 0
+            e1.record(ts)
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) * 1e-3
+
+        calls = {"c_s_batch_device": (lambda: lib.vad_mel_batch_device(h, None, 0, None, 0, C.byref(b), wp, w.size, fp(lo_a), fp(sh), fp(sc), 1,
+                                                                       d_out.data_ptr(), a_bytes, ts.cuda_stream), rows * 320 + a_bytes),
+                 "c_s_batch_packed_device": (lambda: lib.vad_mel_batch_packed_device(h, None, 0, None, 0, C.byref(b), pp, p.size, nw, fp(lo_b), fp(sh),
+                                                                                     fp(sc), 1, d_out.data_ptr(), b_bytes, ts.cuda_stream),
+                                             rows * 320 + b_bytes)}
+        for k in range(5):                           # the two calls alternate: two warm-up passes, three timed ones
+            for name, (fn, moved) in calls.items():
+                t = event_timed(fn)
+                if k >= 2:
+                    row.setdefault(name + "_runs", []).append(t)
+        for name, (fn, moved) in calls.items():
+            runs = row[name + "_runs"]
+            row[name], row[name + "_bytes"], row[name + "_GBps"] = med(runs), moved, moved / med(runs) / 1e9
+        row["c_ratio_unpacked_over_packed"] = row["c_s_batch_device"] / row["c_s_batch_packed_device"]
+    eng.close()
+    with open(os.path.join(root, "profiles", "scan_mel_pack.json"), "w") as f_:
+        json.dump({"what": "Packed feature batches (vad_mel_pack_plan, vad_mel_stats_grouped, vad_mel_batch_packed, csrc/mel_batch.hip): DESIGN 2.1w",
+                   "how": "python tools/bench_configs.py scan_mel_pack on one MI355X, one process.  The windows and bytes are exact counts.  (a) "
+                          "unpacked and (b) packed alternate, wall clock around the Python calls up to a device synchronise, one warm-up and "
+                          "three timed passes, medians; (a) uses only code the parent has.  (c) device forms on the resident matrix: HIP events "
+                          "behind a matrix product that keeps the stream busy while the host builds the tables, the two calls alternating, "
+                          "two warm-up passes and three timed ones; the bytes are computed from the shapes (matrix read once, batch "
+                          "written once), not counted.  Not measured: deltas, cmvn statistics, other layouts, number formats, window lengths "
+                          "and gaps, L2 hit rates, the spread between processes and boxes", "runs": [row]}, f_, indent=1)
+        f_.write("\n")
+    return row
+
+
 def scan_resample_cut():
     """What segment audio and log-mel features at 16 kHz from 48 kHz recordings cost: VAD_SCAN_BENCH_N (default 1 024)
     int16 recordings of 30 s at 48 kHz - the golden clip, every sample three times - hop = chunk / 2, resample_taps' default 97 taps,

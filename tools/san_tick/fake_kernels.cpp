@@ -402,6 +402,50 @@ extern "C" hipError_t vadk_launch_mel_batch(const MelBatchArgs *a, hipStream_t) 
     return hipSuccess;
 }
 
+// packed windows (csrc/mel_batch.hip: vadk_mel_batch_packed): the same rule cell by cell over the host's work list - the frames a
+// workgroup owns, the first nv of them segment rows, the rest pad cells - with lo, shift and scale of the WINDOW
+extern "C" hipError_t vadk_launch_mel_batch_packed(const MelPackArgs *p, hipStream_t) {
+    const MelBatchArgs *a = &p->b;
+    if (a->tile != melb_tile(a->n_mels, a->deltas)) return hipErrorInvalidValue;
+    const uint32_t nm = a->n_mels, T = a->frames, C = nm * (a->deltas + 1u);
+    for (uint32_t b = 0; b < p->nwork; ++b) {
+        const MelPackWork w = p->work[b];
+        if (w.window >= a->nw || w.nt < 4 || (w.nt & 3) || (w.t0 & 3) || w.nt > a->tile || (uint64_t)w.t0 + w.nt > T || w.nv > w.nt ||
+            (uint64_t)w.row0 + w.nv > w.M)
+            return hipErrorInvalidValue;
+        const float lo = a->lo[w.window];
+        const float *shift = a->shift + (size_t)(a->per_seg ? w.window : 0u) * nm, *scale = a->scale + (size_t)(a->per_seg ? w.window : 0u) * nm;
+        auto norm = [&](float x, uint32_t j) -> float {
+            volatile float s = (x > lo ? x : lo) + shift[j];
+            return s * scale[j];
+        };
+        auto c = [&](int64_t s) -> int64_t { return s < 0 ? 0 : s > (int64_t)w.M - 1 ? (int64_t)w.M - 1 : s; };
+        auto v = [&](int64_t s, uint32_t j) -> float { return norm(a->x[((size_t)w.seg_row + (size_t)c(s)) * nm + j], j); };
+        auto delta = [&](float m2, float m1, float p1, float p2) -> float {
+            volatile float d1 = p1 - m1, d2 = p2 - m2, t2 = 2.0f * d2, sum = d1 + t2;
+            return sum * 0.1f;
+        };
+        auto d1 = [&](int64_t s, uint32_t j) -> float { s = c(s); return delta(v(s - 2, j), v(s - 1, j), v(s + 1, j), v(s + 2, j)); };
+        auto d2 = [&](int64_t s, uint32_t j) -> float { return delta(d1(s - 2, j), d1(s - 1, j), d1(s + 1, j), d1(s + 2, j)); };
+        for (uint32_t ch = 0; ch < C; ++ch)
+            for (uint32_t tt = 0; tt < w.nt; ++tt) {
+                const uint32_t k = ch / nm, j = ch % nm, t = w.t0 + tt;
+                const int64_t s = (int64_t)w.row0 + tt;
+                float val;
+                if (tt >= w.nv) val = k ? 0.0f : a->pad_mode == VAD_BATCH_PAD_FEATURE ? norm(a->pad_value, j) : a->pad_value;
+                else val = k == 0 ? v(s, j) : k == 1 ? d1(s, j) : d2(s, j);
+                const size_t o = a->layout == VAD_BATCH_TIME_MAJOR ? ((size_t)w.window * T + t) * C + ch : ((size_t)w.window * C + ch) * T + t;
+                if (a->dtype == VAD_BATCH_F32) static_cast<float *>(a->out)[o] = val;
+                else {
+                    uint32_t bits;
+                    std::memcpy(&bits, &val, 4);
+                    static_cast<uint16_t *>(a->out)[o] = a->dtype == VAD_BATCH_F16 ? f16_bits(val) : melb_bf16(bits);
+                }
+            }
+    }
+    return hipSuccess;
+}
+
 // one finished piece of audio (csrc/scan_render.hip: vadk_scan_render), the kernel's arithmetic in plain C++, output quad by output
 // quad as its workgroups are listed: per covering segment the cut's decoded, channel-selected, gated sample, times the gain, times
 // the fade-in entry (or 1), times the fade-out entry (or 1) - three float32 multiplies - then the sum of the two where two segments
