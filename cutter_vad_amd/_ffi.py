@@ -193,6 +193,26 @@ BATCH_LAYOUTS = {"channel": VAD_BATCH_CHANNEL_MAJOR, "time": VAD_BATCH_TIME_MAJO
 BATCH_PADS = {"value": VAD_BATCH_PAD_VALUE, "feature": VAD_BATCH_PAD_FEATURE}
 
 
+class Moments(C.Structure):
+    _fields_ = [("sum_q31", C.c_int64), ("energy_q32", C.c_int64)]
+
+
+# the moments of n segments are np.ndarray(n, MOMENTS_DTYPE)
+MOMENTS_DTYPE = np.dtype([("sum_q31", np.int64), ("energy_q32", np.int64)])
+
+
+class AudioBatchRecord(C.Structure):
+    _fields_ = [("samples", C.c_int32), ("dtype", C.c_int32), ("pad_mode", C.c_int32), ("pad_value", C.c_float)]
+
+
+class AudioWindow(C.Structure):
+    _fields_ = [("seg", C.c_int32), ("nsamples", C.c_int32), ("sample0", C.c_int64)]
+
+
+# the windows of an audio batch are np.ndarray(nw, AUDIO_WINDOW_DTYPE)
+AUDIO_WINDOW_DTYPE = np.dtype([("seg", np.int32), ("nsamples", np.int32), ("sample0", np.int64)])
+
+
 class Segment(C.Structure):
     _fields_ = [("item", C.c_int32), ("first_frame", C.c_int32), ("nframes", C.c_int32), ("counted", C.c_int32),
                 ("mean_prob", C.c_float), ("max_prob", C.c_float)]
@@ -361,6 +381,16 @@ SIGNATURES = {
                                         C.POINTER(C.c_uint64)]),
     "vad_mel_stats_grouped_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _i64p, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _vp, _vp, _vp,
                                                _vp]),
+    "vad_scan_moments": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32, C.c_float,
+                                   C.POINTER(Moments)]),
+    "vad_scan_moments_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32,
+                                          C.c_float, _vp, _vp]),
+    "vad_scan_audio_batch": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32, C.c_float,
+                                       C.POINTER(AudioBatchRecord), C.POINTER(AudioWindow), C.c_int64, _f32p, _f32p, C.c_int64, _vp, C.c_int64,
+                                       _vp]),
+    "vad_scan_audio_batch_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32,
+                                              C.c_float, C.POINTER(AudioBatchRecord), C.POINTER(AudioWindow), C.c_int64, _f32p, _f32p, C.c_int64,
+                                              _vp, C.c_int64, _vp, _vp]),
     "vad_scan_render": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32,
                                   C.c_int32, C.c_float, C.c_int32, _vp, C.c_int64]),
     "vad_scan_render_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _f32p, _f32p, C.c_int32, _vp, C.c_int64, C.c_int32, C.c_int,

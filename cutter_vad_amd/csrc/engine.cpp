@@ -46,6 +46,8 @@ extern "C" hipError_t vadk_launch_silero_v5_scan16(const vadk::StepParams *p, co
 extern "C" hipError_t vadk_launch_scan_cut(const vadk::CutArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_cut_gain(const vadk::CutArgs *a, const float *gains, hipStream_t stream);
 extern "C" hipError_t vadk_launch_seg_levels(const vadk::CutArgs *a, float clip, hipStream_t stream);
+extern "C" hipError_t vadk_launch_seg_moments(const vadk::CutArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_audio_batch(const vadk::AudioBatchArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_seg_mel(const vadk::MelArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_resample_cut(const vadk::ResampleCutArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_convert(const vadk::ConvertArgs *a, hipStream_t stream);
@@ -240,6 +242,10 @@ struct vad_engine {
     std::vector<int64_t> melb_order;
     std::vector<int64_t> melb_rows;                // vad_mel_stats_grouped: a group's rows
     std::vector<float> melb_f;
+    // vad_scan_audio_batch: the windows, the work list, and shift and scale back to back, which lie in d_cut behind the segments
+    std::vector<vadk::AudioWin> ab_win;
+    std::vector<vadk::AudioWork> ab_work;
+    std::vector<float> ab_f;
     // The calls that make or rewrite segment tables.  Each work area is laid out by one DevTables in the function
     // named, and has one staging block: what was uploaded, as it was, until the stream has passed the copy.
     // d_segwork (seg_launches): out_start as int32 [n + 1], the chunk counts; staged in seg_start.  For vad_scan_segments also the
@@ -1795,10 +1801,14 @@ int rate_cut_check(vad_engine *e, const char *who, int32_t sr_in, int *chunk) {
 struct CutSpan { int64_t lo, hi, i; };                           // the output samples [lo, hi) of segment i
 struct CutWin { uint32_t r0, r1; size_t seg0, work0, nwork; };   // rows [r0, r1) of a rate cut's frames: their part of the tables
 
+static_assert(sizeof(vad_level) == 16 && sizeof(vad_moments) == 16, "the records of the LEVELS and MOMENTS kinds have one size");
+
 // what a call of this family makes of its segments
 enum class CutKind {
     PAYLOAD,        // vad_scan_cut, _rate_cut, _cut_gain, _cut_stereo: each segment's samples at its out_sample
     LEVELS,         // vad_scan_levels: a vad_level record per segment, reduced where a cut stores
+    MOMENTS,        // vad_scan_moments: a vad_moments record per segment, the levels' runner with another launcher
+    AUDIO_BATCH,    // vad_scan_audio_batch: normalised, padded windows of the segments' ranges; the work follows the output
     RENDER,         // vad_scan_render, _render_stereo: every output sample written; the ranges of two segments may overlap, three not
     MEL,            // vad_scan_mel, vad_scan_mel_keep at the engine's rate: log-mel rows, the segments back to back
     RESAMPLE,       // vad_scan_resample_cut: a rate block's segments at 16 kHz, at their out_sample
@@ -1826,6 +1836,9 @@ struct CutCall {
     // the mel kinds.  keep (vad_scan_mel_keep): the rows stay in e->d_melk, the call has no output and no out_rows
     const vad_mel *m = nullptr; const float *op_re = nullptr, *op_im = nullptr, *filters = nullptr; int64_t out_rows = 0;
     bool keep = false; int64_t *rows_out = nullptr;
+    // AUDIO_BATCH: the windows (host), shift and scale (host [nss] or nullptr), the output's bytes and the mask
+    const vad_audio_batch *ab = nullptr; const vad_audio_window *awin = nullptr; int64_t nw = 0;
+    const float *shift = nullptr, *scale = nullptr; int64_t nss = 1, out_bytes = 0; uint8_t *mask = nullptr;
 
     bool rate() const { return chunk > 0; }
     // a rate block's frames resampled window by window into e->d_win (vadk_cut_resample), each window cut as a mono float32 block of
@@ -1837,8 +1850,9 @@ struct CutCall {
     // share samples
     bool has_payload() const { return kind == CutKind::PAYLOAD || kind == CutKind::RENDER || kind == CutKind::RESAMPLE; }
     // its workgroups follow the output, not the segments: render_regions lists them (mel: mel_tiles)
-    bool work_follows_output() const { return kind == CutKind::RENDER || kind == CutKind::MEL; }
-    bool records_out() const { return kind == CutKind::LEVELS; }     // the output is records, 8-byte aligned; else 16 bytes
+    bool work_follows_output() const { return kind == CutKind::RENDER || kind == CutKind::MEL || kind == CutKind::AUDIO_BATCH; }
+    // the output is records of 16 bytes (vad_level, vad_moments), 8-byte aligned; else 16 bytes
+    bool records_out() const { return kind == CutKind::LEVELS || kind == CutKind::MOMENTS; }
     float gate() const { return rate() && !rate_frames() ? -1.0f : thr; }    // no input-rate sample was ever gated
 };
 
@@ -1992,7 +2006,8 @@ int cut_block(vad_engine *e, CutPlan &c, bool dev, const void *audio, void *out)
         if (!audio) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
         if (int rc = check_device_audio(e, who, audio, k.channels)) return rc;
         if (k.records_out() && (reinterpret_cast<uintptr_t>(out) & 7))
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the levels must be 8-byte aligned", who);
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the %s must be 8-byte aligned", who,
+                           k.kind == CutKind::MOMENTS ? "moments" : "levels");
         if (!k.records_out() && (reinterpret_cast<uintptr_t>(out) & 15))
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output must be 16-byte aligned", who);
         c.d_audio = audio;
@@ -2029,7 +2044,8 @@ int cut_block(vad_engine *e, CutPlan &c, bool dev, const void *audio, void *out)
         c.d_out = e->d_cut_out;
         return VAD_OK;
     }
-    if (k.kind == CutKind::RENDER) return VAD_OK;    // the whole output, from sample 0: render_run sizes it
+    // the whole output, from sample 0: render_run / audio_batch_run sizes it
+    if (k.kind == CutKind::RENDER || k.kind == CutKind::AUDIO_BATCH) return VAD_OK;
     const int64_t out_lo = c.spans.front().lo, out_hi = c.spans.back().hi;
     if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, (size_t)(out_hi - out_lo) * c.ob)) return rc;
     c.d_out = e->d_cut_out;
@@ -2118,12 +2134,14 @@ int cut_launches(vad_engine *e, const CutPlan &c, const DevTables &t, hipStream_
     a.out_fmt = k.out_fmt;
     a.thresh = k.gate();
     if (!k.rate_frames()) {
-        const bool levels = k.kind == CutKind::LEVELS;
-        const hipError_t r = levels    ? vadk_launch_seg_levels(&a, k.clip, s)
+        const bool levels = k.records_out();
+        const hipError_t r = k.kind == CutKind::MOMENTS ? vadk_launch_seg_moments(&a, s)
+                             : levels   ? vadk_launch_seg_levels(&a, k.clip, s)
                              : k.stereo ? vadk_launch_scan_cut_stereo(&a, d_gains, s)
                              : d_gains  ? vadk_launch_scan_cut_gain(&a, d_gains, s)
                                         : vadk_launch_scan_cut(&a, s);
-        return r != hipSuccess ? e->hip_fail(r, levels ? "kernel launch (segment levels)" : "kernel launch (scan cut)") : VAD_OK;
+        return r != hipSuccess ? e->hip_fail(r, k.kind == CutKind::MOMENTS ? "kernel launch (segment moments)"
+                                              : levels ? "kernel launch (segment levels)" : "kernel launch (scan cut)") : VAD_OK;
     }
     vadk::CutResampleArgs ra{};
     ra.wstream = c.op->d_w;
@@ -2181,9 +2199,9 @@ int cut_copy_back(vad_engine *e, const CutPlan &c, void *out, hipStream_t s) {
     return VAD_OK;
 }
 
-// The PAYLOAD and LEVELS kinds (dev = false: host audio, or NULL = the resident block, and a host `out`; dev: two device pointers),
+// The PAYLOAD, LEVELS and MOMENTS kinds (dev = false: host audio, or NULL = the resident block, and a host `out`; dev: two device pointers),
 // with e->mu held.  Every check comes before the first write: phases a to c refuse or size buffers, cut_upload writes first.  A
-// gained cut's kernel applies the factors; the levels' `out` is n vad_level records, cleared on the stream ahead of the reducing kernel
+// gained cut's kernel applies the factors; the levels' (moments') `out` is n vad_level (vad_moments) records, cleared on the stream ahead of the reducing kernel
 int cut_run(vad_engine *e, bool dev, const CutCall &k, const void *audio, void *out, hipStream_t s) {
     CutPlan c{k};
     if (k.gains_required && k.n > 0 && !k.gains) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null gains", k.who);
@@ -2292,6 +2310,113 @@ int render_run(vad_engine *e, bool dev, const CutCall &k, const void *audio, voi
     const int rc = call_end(e, dev, s, r != hipSuccess ? e->hip_fail(r, "kernel launch (scan render)") : VAD_OK);
     if (rc || dev) return rc;
     HIP_TRY(e, hipMemcpyAsync(out, c.d_out, (size_t)k.out_samples * c.ob, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    return VAD_OK;
+}
+
+// The AUDIO_BATCH kind with e->mu held: cut_check's refusals under this name, then the batch's own in the header's order, then the
+// block as the levels find it.  Its work follows the output: a workgroup per CUT_WG_QUADS quads of a window, listed here.  One
+// upload of the tables - segments, windows, workgroups, shift and scale, in this order in e->d_cut - and one launch, which writes
+// every cell of the output and of the mask.  A host call's output and mask lie in e->d_cut_out, the mask behind the windows
+int audio_batch_run(vad_engine *e, bool dev, const CutCall &k, const void *audio, void *out, hipStream_t s) {
+    const char *who = k.who;
+    CutPlan c{k};
+    if (int rc = cut_check(e, c)) return rc;
+    const vad_audio_batch *b = k.ab;
+    if (!b) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null vad_audio_batch", who);
+    if (b->samples < 4 || b->samples > (1 << 24) || (b->samples & 3))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: samples = %d must be a multiple of 4 from 4 to 2^24", who, b->samples);
+    if (b->dtype != VAD_BATCH_F32 && b->dtype != VAD_BATCH_F16 && b->dtype != VAD_BATCH_BF16)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: dtype = %d is none of VAD_BATCH_F32, VAD_BATCH_F16, VAD_BATCH_BF16", who, b->dtype);
+    if (b->pad_mode != VAD_BATCH_PAD_VALUE && b->pad_mode != VAD_BATCH_PAD_FEATURE)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: pad_mode = %d is neither VAD_BATCH_PAD_VALUE nor VAD_BATCH_PAD_FEATURE", who,
+                       b->pad_mode);
+    if (!std::isfinite(b->pad_value))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: pad_value is %s, a pad value is a finite number", who,
+                       std::isnan(b->pad_value) ? "NaN" : "infinite");
+    const int64_t nw = k.nw, n = k.n, T = b->samples;
+    if (nw < 0 || k.out_bytes < 0 || (nw > 0 && !k.awin)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer or bad count", who);
+    const int64_t nss = !k.shift && !k.scale ? 1 : k.nss;
+    if (nss != 1 && nss != n)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: nss = %lld: shift and scale have 1 entry or n = %lld", who, (long long)nss,
+                       (long long)n);
+    for (int which = 0; which < 2; ++which) {
+        const float *v = which ? k.scale : k.shift;
+        for (int64_t i = 0; v && i < nss; ++i)
+            if (!std::isfinite(v[i]))
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %s[%lld] is %s, a %s is a finite number", who, which ? "scale" : "shift",
+                               (long long)i, std::isnan(v[i]) ? "NaN" : "infinite", which ? "scale" : "shift");
+    }
+    e->ab_win.resize((size_t)nw);
+    for (int64_t j = 0; j < nw; ++j) {
+        const vad_audio_window &w = k.awin[j];
+        if (w.seg < 0 || (int64_t)w.seg >= n)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: window %lld names segment %d of %lld", who, (long long)j, w.seg, (long long)n);
+        const int64_t S = (int64_t)e->cut_segs[(size_t)w.seg].nquads * 4;
+        if (w.sample0 < 0 || (w.sample0 & 3) || w.nsamples < 0 || w.nsamples > T || w.sample0 > S || w.nsamples > S - w.sample0)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: window %lld: samples %lld .. +%d of segment %d, which has %lld, in %lld "
+                           "samples (sample0 a multiple of 4)", who, (long long)j, (long long)w.sample0, w.nsamples, w.seg, (long long)S, (long long)T);
+        e->ab_win[(size_t)j] = vadk::AudioWin{(uint32_t)w.seg, (uint32_t)(w.sample0 >> 2), (uint32_t)w.nsamples, 0u};
+    }
+    const size_t esize = b->dtype == VAD_BATCH_F32 ? 4u : 2u, cells = (size_t)nw * (size_t)T, need = cells * esize;
+    if (need > (size_t)k.out_bytes)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_bytes = %lld, the windows have %llu bytes", who, (long long)k.out_bytes,
+                       (unsigned long long)need);
+    const uint32_t tq = (uint32_t)T >> 2, per_win = (tq + vadk::CUT_WG_QUADS - 1u) / vadk::CUT_WG_QUADS;
+    if ((uint64_t)nw * per_win > (uint64_t)INT32_MAX)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d samples in one call", who, VAD_CUT_WG_SAMPLES);
+    if (nw == 0) return VAD_OK;
+    if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
+    if (int rc = cut_block(e, c, dev, audio, out)) return rc;
+    if (dev && (reinterpret_cast<uintptr_t>(k.mask) & 3))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the mask must be 4-byte aligned", who);
+    e->ab_work.clear();
+    e->ab_work.reserve((size_t)nw * per_win);
+    for (int64_t j = 0; j < nw; ++j)
+        for (uint32_t q = 0; q < tq; q += vadk::CUT_WG_QUADS) e->ab_work.push_back(vadk::AudioWork{(uint32_t)j, q});
+    e->ab_f.resize(2 * (size_t)nss);
+    for (int64_t i = 0; i < nss; ++i) {
+        e->ab_f[(size_t)i] = k.shift ? k.shift[i] : 0.0f;
+        e->ab_f[(size_t)(nss + i)] = k.scale ? k.scale[i] : 1.0f;
+    }
+    DevTables t{e->d_cut, e->d_cut_cap};
+    const int segs = t.add(e->cut_segs, e->cut_segs.size()), win = t.add(e->ab_win, e->ab_win.size());
+    const int work = t.add(e->ab_work, e->ab_work.size()), floats = t.add(e->ab_f, e->ab_f.size());
+    if (int rc = t.reserve(e)) return rc;
+    const size_t mask_off = (need + 15) & ~(size_t)15;
+    c.d_out = out;
+    uint8_t *d_mask = k.mask;
+    if (!dev) {
+        if (int rc = ensure(e, e->d_cut_out, e->d_cut_out_cap, mask_off + (k.mask ? cells : 0))) return rc;
+        c.d_out = e->d_cut_out;
+        d_mask = k.mask ? static_cast<uint8_t *>(c.d_out) + mask_off : nullptr;
+    }
+    if (int rc = cut_upload_audio(e, c, dev, audio, s)) return rc;
+    if (int rc = t.copy(e, s)) return rc;
+    vadk::AudioBatchArgs a{};
+    a.audio = c.d_audio;
+    a.out = c.d_out;
+    a.mask = d_mask;
+    a.segs = t.at<const vadk::CutSeg>(segs);
+    a.win = t.at<const vadk::AudioWin>(win);
+    a.work = t.at<const vadk::AudioWork>(work);
+    a.shift = t.at<const float>(floats);
+    a.scale = a.shift + nss;
+    a.audio_bytes = (uint32_t)c.ab;
+    a.nwork = (uint32_t)e->ab_work.size();
+    a.tq = tq;
+    a.per_seg = nss == 1 ? 0u : 1u;
+    a.fmt = k.fmt;
+    a.channels = k.channels;
+    a.dtype = b->dtype;
+    a.pad_mode = b->pad_mode;
+    a.pad_value = b->pad_value;
+    a.thresh = k.gate();
+    const hipError_t r = vadk_launch_audio_batch(&a, s);
+    const int rc = call_end(e, dev, s, r != hipSuccess ? e->hip_fail(r, "kernel launch (audio batch)") : VAD_OK);
+    if (rc || dev) return rc;
+    HIP_TRY(e, hipMemcpyAsync(out, c.d_out, need, hipMemcpyDeviceToHost, s));
+    if (k.mask) HIP_TRY(e, hipMemcpyAsync(k.mask, d_mask, cells, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
     return VAD_OK;
 }
@@ -3005,6 +3130,7 @@ int cut_enter(vad_engine *e, bool dev, CutCall &k, RateArg arg, int32_t sr_in, c
     switch (k.kind) {
         case CutKind::RENDER: return render_run(e, dev, k, audio, out, s);
         case CutKind::MEL: return mel_run(e, dev, k, audio, out, s);
+        case CutKind::AUDIO_BATCH: return audio_batch_run(e, dev, k, audio, out, s);
         case CutKind::RESAMPLE:
         case CutKind::RESAMPLE_MEL: return resample_cut_run(e, dev, k, audio, out, s);
         default: return cut_run(e, dev, k, audio, out, s);
@@ -3033,6 +3159,31 @@ int levels_entry(vad_engine *e, bool dev, const char *who, const vad_cut_item *i
     CutCall k = cut_call(who, items, n, audio_samples, channels, fmt, hop, thr);
     k.kind = CutKind::LEVELS;
     k.clip = clip;
+    return cut_enter(e, dev, k, RateArg::EITHER, sr_in, audio, out, stream);
+}
+
+// vad_scan_moments: `out` is n vad_moments records
+int moments_entry(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples,
+                  int32_t channels, int fmt, int32_t sr_in, int32_t hop, float thr, void *out, void *stream) {
+    CutCall k = cut_call(who, items, n, audio_samples, channels, fmt, hop, thr);
+    k.kind = CutKind::MOMENTS;
+    return cut_enter(e, dev, k, RateArg::EITHER, sr_in, audio, out, stream);
+}
+
+// vad_scan_audio_batch: windows, shift and scale are host arrays in both forms
+int audio_batch_entry(vad_engine *e, bool dev, const char *who, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples,
+                      int32_t channels, int fmt, int32_t sr_in, int32_t hop, float thr, const vad_audio_batch *b, const vad_audio_window *windows,
+                      int64_t nw, const float *shift, const float *scale, int64_t nss, void *out, int64_t out_bytes, uint8_t *mask, void *stream) {
+    CutCall k = cut_call(who, items, n, audio_samples, channels, fmt, hop, thr);
+    k.kind = CutKind::AUDIO_BATCH;
+    k.ab = b;
+    k.awin = windows;
+    k.nw = nw;
+    k.shift = shift;
+    k.scale = scale;
+    k.nss = nss;
+    k.out_bytes = out_bytes;
+    k.mask = mask;
     return cut_enter(e, dev, k, RateArg::EITHER, sr_in, audio, out, stream);
 }
 
@@ -3357,6 +3508,32 @@ int vad_scan_cut_gain_device(vad_engine *e, const vad_cut_item *items, int64_t n
                              void *d_out, int64_t out_samples, void *stream) {
     return payload_entry(e, true, "vad_scan_cut_gain_device", Cut::GAIN, items, n, gains, d_audio, audio_samples, channels, frame_fmt, sr_in, hop,
                          denoise_thresh, layout, out_fmt, d_out, out_samples, stream);
+}
+
+int vad_scan_moments(vad_engine *e, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels, int frame_fmt,
+                     int32_t sr_in, int32_t hop, float denoise_thresh, vad_moments *out) {
+    return moments_entry(e, false, "vad_scan_moments", items, n, audio, audio_samples, channels, frame_fmt, sr_in, hop, denoise_thresh, out, nullptr);
+}
+
+int vad_scan_moments_device(vad_engine *e, const vad_cut_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
+                            int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, vad_moments *d_out, void *stream) {
+    return moments_entry(e, true, "vad_scan_moments_device", items, n, d_audio, audio_samples, channels, frame_fmt, sr_in, hop, denoise_thresh,
+                         d_out, stream);
+}
+
+int vad_scan_audio_batch(vad_engine *e, const vad_cut_item *items, int64_t n, const void *audio, int64_t audio_samples, int32_t channels,
+                         int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, const vad_audio_batch *b, const vad_audio_window *windows,
+                         int64_t nw, const float *shift, const float *scale, int64_t nss, void *out, int64_t out_bytes, uint8_t *mask) {
+    return audio_batch_entry(e, false, "vad_scan_audio_batch", items, n, audio, audio_samples, channels, frame_fmt, sr_in, hop, denoise_thresh, b,
+                             windows, nw, shift, scale, nss, out, out_bytes, mask, nullptr);
+}
+
+int vad_scan_audio_batch_device(vad_engine *e, const vad_cut_item *items, int64_t n, const void *d_audio, int64_t audio_samples, int32_t channels,
+                                int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, const vad_audio_batch *b,
+                                const vad_audio_window *windows, int64_t nw, const float *shift, const float *scale, int64_t nss, void *d_out,
+                                int64_t out_bytes, uint8_t *d_mask, void *stream) {
+    return audio_batch_entry(e, true, "vad_scan_audio_batch_device", items, n, d_audio, audio_samples, channels, frame_fmt, sr_in, hop,
+                             denoise_thresh, b, windows, nw, shift, scale, nss, d_out, out_bytes, d_mask, stream);
 }
 
 int vad_scan_render(vad_engine *e, const vad_cut_item *items, int64_t n, const float *gains, const float *ramp, int32_t nramp, const void *audio,

@@ -12,6 +12,7 @@
 // Integers, so the record does not depend on the order in which lanes, waves and workgroups arrive: two runs give the same bytes.
 // Registers -> wave (xor shuffles) -> the workgroup's waves through LDS -> one atomic per field and workgroup on the segment's
 // record, which the host zeroed (hipMemsetAsync) ahead of the launch.  No float atomics.
+// vad_scan_moments (vadk_seg_moments, below the levels' kernel): a segment's sum and energy by the same skeleton, for its mean and variance.
 #include <hip/hip_runtime.h>
 #include "../../include/vad_engine.h"
 #include "vad_layout.h"
@@ -103,6 +104,79 @@ __global__ void __launch_bounds__(CUT_THREADS) vadk_seg_levels(const CutArgs a, 
     atomicAdd(reinterpret_cast<unsigned long long *>(&rec->energy_q32), t.e);
     atomicMax(reinterpret_cast<unsigned int *>(&rec->peak), t.peak);
     atomicAdd(reinterpret_cast<unsigned int *>(&rec->clipped), t.clipped);
+}
+
+// vad_scan_moments: the sum and the energy of the same values, for a mean and a variance (include/vad_engine.h: vad_moments).
+//   sum     sum of rint(clamp(x, -1, 1) * 2^31): the product is exact in float64, v_rndne_f64 rounds to nearest-even; a thread's <= 16
+//           terms (each |.| <= 2^31) add up exactly in float64 and are converted ONCE to int64.
+//   energy  vad_level's energy_q32, by level1's own expression: the two calls agree on it byte for byte.
+// a.out: vad_moments[segments of a.segs], zeroed.  The loads, the guard in front of the fold and the reduction are vadk_seg_levels':
+// registers -> wave -> LDS -> one 64-bit integer atomic per field and workgroup (the signed sum as its two's complement).
+static_assert(sizeof(vad_moments) == 16, "vad_moments layout");
+
+template <int FMT, int CH>
+__global__ void __launch_bounds__(CUT_THREADS) vadk_seg_moments(const CutArgs a) {
+    using In = WireQuad<FMT, CH>;
+    constexpr int NW = CUT_THREADS / 64;
+    __shared__ unsigned long long part[NW][2];
+    const CutWork w = a.work[blockIdx.x];
+    const CutSeg sg = a.segs[w.seg];
+    const uint32_t mode = sg.quad_in >> SCAN_MODE_SHIFT, qin = sg.quad_in & ((1u << SCAN_MODE_SHIFT) - 1u);
+    const float sc = a.fmt == VAD_FMT_I16_32767 ? 32767.0f : 32768.0f, rsc = 1.0f / sc;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.audio), 0, (int)a.audio_bytes, 0x00020000);
+    typename In::XQ x[CUT_PASSES];
+#pragma unroll
+    for (int p = 0; p < CUT_PASSES; ++p) {
+        const uint32_t oq = w.quad0 + (uint32_t)(p * CUT_THREADS) + threadIdx.x;
+        x[p] = In::load(rs, (int)((qin + oq) << In::qsh));
+    }
+    double s = 0.0, e = 0.0;
+#pragma unroll
+    for (int p = 0; p < CUT_PASSES; ++p) {
+        const uint32_t oq = w.quad0 + (uint32_t)(p * CUT_THREADS) + threadIdx.x;
+        if (oq >= sg.nquads) continue;
+        const f32x4 v = gate4(In::decode(x[p], mode, sc, rsc), a.thresh);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+#pragma clang fp contract(off)
+            const float xk = v[k];
+            s += __builtin_rint((double)fminf(fmaxf(xk, -1.0f), 1.0f) * 2147483648.0);
+            const double y = (double)(fminf(fabsf(xk), 1.0f) * 65536.0f);
+            e += __builtin_rint(y * y);
+        }
+    }
+    unsigned long long ts = (unsigned long long)(long long)s, te = (unsigned long long)e;      // integers, exact
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t slo = (uint32_t)__shfl_xor((int)(uint32_t)ts, m), shi = (uint32_t)__shfl_xor((int)(uint32_t)(ts >> 32), m);
+        const uint32_t elo = (uint32_t)__shfl_xor((int)(uint32_t)te, m), ehi = (uint32_t)__shfl_xor((int)(uint32_t)(te >> 32), m);
+        ts += ((unsigned long long)shi << 32) | slo;
+        te += ((unsigned long long)ehi << 32) | elo;
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        part[wave][0] = ts;
+        part[wave][1] = te;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+#pragma unroll
+    for (int k = 1; k < NW; ++k) {
+        ts += part[k][0];
+        te += part[k][1];
+    }
+    vad_moments *rec = static_cast<vad_moments *>(a.out) + w.seg;
+    atomicAdd(reinterpret_cast<unsigned long long *>(&rec->sum_q31), ts);
+    atomicAdd(reinterpret_cast<unsigned long long *>(&rec->energy_q32), te);
+}
+
+extern "C" hipError_t vadk_launch_seg_moments(const CutArgs *a, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (a->nwork == 0) return hipSuccess;
+    return launch_variant<4, 2>([&](auto F, auto C) {
+        hipLaunchKernelGGL((vadk_seg_moments<F, C + 1>), dim3(a->nwork), dim3(CUT_THREADS), 0, stream, *a);
+        return hipGetLastError();
+    }, wire_fmt(a->fmt), (int)a->channels - 1);
 }
 
 extern "C" hipError_t vadk_launch_seg_levels(const CutArgs *a, float clip, hipStream_t stream) {

@@ -296,6 +296,43 @@ struct CutArgs {
     float thresh;             // denoise gate, < 0 = off
 };
 
+// normalised, padded waveform windows (csrc/audio_batch.hip: vadk_audio_batch; vad_scan_audio_batch).  Window w of T = 4 tq samples
+// shows samples 4 quad0 .. 4 quad0 + nsamples - 1 of segment seg's range once (a CutSeg of it: quad_in + the mode bits; quad_out is
+// not read); the cells behind nsamples are pad cells.  A workgroup of CUT_THREADS threads serves CUT_WG_QUADS consecutive quads of
+// ONE window in CUT_PASSES passes; the host lists the workgroups (AudioWork), so no thread searches a table.
+struct AudioWin {
+    uint32_t seg;             // index into the segment table, and into shift / scale when per_seg
+    uint32_t quad0;           // sample0 / 4, within the segment
+    uint32_t nsamples;        // 0 .. T
+    uint32_t reserved;
+};
+static_assert(sizeof(AudioWin) == 16, "AudioWin layout");
+struct AudioWork {
+    uint32_t window;
+    uint32_t quad0;           // first quad of this workgroup's share of the window, a multiple of CUT_WG_QUADS, < tq
+};
+static_assert(sizeof(AudioWork) == 8, "AudioWork layout");
+struct AudioBatchArgs {
+    const void *audio;        // the block, in its wire format
+    void *out;                // [nw][T] float32 / float16 / bfloat16
+    uint8_t *mask;            // [nw][T] or nullptr
+    const CutSeg *segs;
+    const AudioWin *win;      // [nw]
+    const AudioWork *work;    // [nwork]
+    const float *shift;       // [1 or segments]
+    const float *scale;
+    uint32_t audio_bytes;     // the buffer descriptor's range
+    uint32_t nwork;
+    uint32_t tq;              // T / 4
+    uint32_t per_seg;         // 1: shift / scale have an entry per segment, 0: one
+    int32_t fmt;              // vad_frame_format
+    int32_t channels;         // 1 or 2
+    int32_t dtype, pad_mode;  // VAD_BATCH_*
+    float pad_value;
+    float thresh;             // denoise gate, < 0 = off
+};
+static_assert(sizeof(AudioBatchArgs) == 104, "AudioBatchArgs layout");
+
 // log-mel features of finished segments (csrc/scan_mel.hip: vadk_seg_mel; vad_scan_mel).  A workgroup of MEL_THREADS threads
 // serves MEL_TILE consecutive analysis frames of ONE segment; the host lists the workgroups (MelWork) next to the segments, which
 // are CutSeg of the sample range once with quad_out = the segment's first ROW of the output.  Both matrix products run on

@@ -1021,6 +1021,111 @@ class Engine:
         self._check(self._lib.vad_scan_levels_device(self._h, items, len(start) - 1, d_audio or None, int(audio_samples), int(channels), int(fmt),
                                                      sr or 0, hop, thr, float(clip), d_levels or None, stream or None))
 
+    # ------------------------------------------------------------------ segment moments and audio batches
+    def moments(self, segments, hop: Optional[int] = None, denoise: Optional[float] = 0.01, audio=None, law: Optional[str] = None,
+                i16_scale: int = 32767, sample_rate: Optional[int] = None) -> np.ndarray:
+        """Sum and energy of finished segments (``vad_scan_moments``), reduced on the GPU: ``segments`` and every other argument as
+        in ``levels``.  -> a structured array ``(sum_q31, energy_q32)``, one record per segment, over exactly the float32 values
+        ``cut(segments, layout="range", out="f32")`` gives: ``sum_q31`` the sum of ``rint(clip(x, -1, 1) * 2^31)``, ``energy_q32``
+        the field of ``levels``, byte for byte.  ``mean = sum_q31 / (2^31 N)``, ``var = energy_q32 / (2^32 N) - mean^2``
+        (``cutter_vad_amd.scan.audio_affine``).  Integer reductions: two calls give the same bytes."""
+        with self._scan_lock:
+            sr, total, channels, fmt, ptr, _keep = self._cut_block("moments", audio, law, i16_scale, sample_rate)
+            hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
+            items, start = self._cut_items(segments, hop, _ffi.VAD_CUT_RANGE, channels, rate=sr)
+            n = len(start) - 1
+            out = np.zeros(n, _ffi.MOMENTS_DTYPE)
+            thr = -1.0 if denoise is None else float(denoise)
+            self._check(self._lib.vad_scan_moments(self._h, items, n, ptr, total, channels, fmt, sr or 0, hop, thr,
+                                                   out.ctypes.data_as(C.POINTER(_ffi.Moments))))
+        return out
+
+    def moments_device(self, segments, d_audio: int, audio_samples: int, d_moments: int, hop: Optional[int] = None,
+                       fmt: int = _ffi.VAD_FMT_F32, channels: int = 1, denoise: Optional[float] = 0.01, stream: int = 0,
+                       sample_rate: Optional[int] = None) -> None:
+        """``moments`` on device pointers (integers; ``vad_scan_moments_device``): the block at ``d_audio`` as ``cut_device`` takes it,
+        one 16-byte record per segment to ``d_moments`` (8-byte aligned).  Asynchronous on ``stream``."""
+        sr = self._scan_rate(sample_rate)
+        hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
+        items, start = self._cut_items(segments, hop, _ffi.VAD_CUT_RANGE, int(channels), rate=sr)
+        thr = -1.0 if denoise is None else float(denoise)
+        self._check(self._lib.vad_scan_moments_device(self._h, items, len(start) - 1, d_audio or None, int(audio_samples), int(channels), int(fmt),
+                                                      sr or 0, hop, thr, d_moments or None, stream or None))
+
+    @staticmethod
+    def _audio_batch_record(batch) -> _ffi.AudioBatchRecord:
+        """``batch``: a ``_ffi.AudioBatchRecord``, an object with ``record()`` (``cutter_vad_amd.scan.AudioBatch``) or a dict of
+        ``vad_audio_batch``'s fields - ``samples``, and optionally ``dtype`` / ``pad`` (names or numbers) and ``pad_value``"""
+        if isinstance(batch, _ffi.AudioBatchRecord):
+            return batch
+        f = dict(batch.record() if hasattr(batch, "record") else batch)
+        enum = lambda table, what, v: Engine._cut_enum(table, what, v) if isinstance(v, str) else int(v)
+        return _ffi.AudioBatchRecord(int(f["samples"]), enum(_ffi.BATCH_DTYPES, "dtype", f.get("dtype", "f32")),
+                                     enum(_ffi.BATCH_PADS, "pad", f.get("pad", "value")), float(f.get("pad_value", 0.0)))
+
+    @staticmethod
+    def _audio_windows(windows):
+        w = np.ascontiguousarray(np.asarray(windows, _ffi.AUDIO_WINDOW_DTYPE).reshape(-1)) if not (
+            isinstance(windows, np.ndarray) and windows.dtype == _ffi.AUDIO_WINDOW_DTYPE) else np.ascontiguousarray(windows.reshape(-1))
+        return w, (w if w.size else np.zeros(1, _ffi.AUDIO_WINDOW_DTYPE)).ctypes.data_as(C.POINTER(_ffi.AudioWindow))
+
+    @staticmethod
+    def _audio_affine(shift, scale):
+        """-> (the float32 arrays or None, their pointers, nss); one entry next to an entry per segment is repeated"""
+        two = [None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1)) for a in (shift, scale)]
+        most = max([a.size for a in two if a is not None] or [1])
+        two = [np.full(most, a[0], np.float32) if a is not None and a.size == 1 else a for a in two]
+        sizes = {a.size for a in two if a is not None}
+        if len(sizes) > 1:
+            raise AudioProcessingError(f"Model prediction failed: shift and scale have the same number of entries, got {sorted(sizes)}")
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+        return two, (ptr(two[0]), ptr(two[1])), (sizes.pop() if sizes else 1)
+
+    def audio_batch(self, segments, windows, batch, shift=None, scale=None, mask: bool = False, hop: Optional[int] = None,
+                    denoise: Optional[float] = 0.01, audio=None, law: Optional[str] = None, i16_scale: int = 32767,
+                    sample_rate: Optional[int] = None):
+        """Normalised, zero-padded windows of segment audio in a model's number format (``vad_scan_audio_batch``), one launch:
+        ``segments`` as in ``cut``, ``windows`` lists ``(seg, nsamples, sample0)`` - samples ``sample0 .. sample0 + nsamples - 1`` of
+        segment ``seg``'s range (``cutter_vad_amd.scan.audio_windows``; ``sample0`` a multiple of 4) - ``batch`` is a
+        ``cutter_vad_amd.scan.AudioBatch`` with ``samples`` set, or a dict of ``vad_audio_batch``'s fields.  A value is
+        ``(x + shift[seg]) * scale[seg]`` in float32 over exactly the samples ``cut(segments, layout="range", out="f32")`` gives
+        (``shift`` / ``scale``: one entry or one per segment, ``None`` for 0 and 1); the cells behind ``nsamples`` are pad cells.
+        ``audio``, ``law``, ``i16_scale``, ``sample_rate`` and the ``scan_session()`` rule as in ``cut``.  -> [B, T]: float32,
+        ``np.float16``, or the bfloat16 bit patterns as ``np.uint16``; with ``mask=True`` -> (batch, mask [B, T] uint8)."""
+        with self._scan_lock:
+            sr, total, channels, fmt, ptr, _keep = self._cut_block("audio_batch", audio, law, i16_scale, sample_rate)
+            hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
+            items, start = self._cut_items(segments, hop, _ffi.VAD_CUT_RANGE, channels, rate=sr)
+            b = self._audio_batch_record(batch)
+            w, wp = self._audio_windows(windows)
+            _own, ptrs, nss = self._audio_affine(shift, scale)
+            out = np.empty((w.size, b.samples), {_ffi.VAD_BATCH_F32: np.float32, _ffi.VAD_BATCH_F16: np.float16}.get(b.dtype, np.uint16))
+            m = np.empty((w.size, b.samples), np.uint8) if mask else None
+            thr = -1.0 if denoise is None else float(denoise)
+            self._check(self._lib.vad_scan_audio_batch(self._h, items, len(start) - 1, ptr, total, channels, fmt, sr or 0, hop, thr, C.byref(b),
+                                                       wp, w.size, *ptrs, nss, out.ctypes.data_as(C.c_void_p), out.nbytes,
+                                                       None if m is None else m.ctypes.data_as(C.c_void_p)))
+        return (out, m) if mask else out
+
+    def audio_batch_device(self, segments, windows, batch, d_audio: int, audio_samples: int, d_out: int, out_bytes: int, d_mask: int = 0,
+                           shift=None, scale=None, hop: Optional[int] = None, fmt: int = _ffi.VAD_FMT_F32, channels: int = 1,
+                           denoise: Optional[float] = 0.01, stream: int = 0, sample_rate: Optional[int] = None) -> Tuple[int, int]:
+        """``audio_batch`` on device pointers (integers; ``vad_scan_audio_batch_device``): the block at ``d_audio`` as ``cut_device``
+        takes it, the windows to ``d_out`` (16-byte aligned, room for ``out_bytes``) and the mask to ``d_mask`` (4-byte aligned, or 0:
+        none), where a model on the same GPU reads them.  ``windows``, ``shift`` and ``scale`` are host arrays, read before the call
+        returns.  Asynchronous on ``stream``.  -> the shape of the batch."""
+        sr = self._scan_rate(sample_rate)
+        hop = self.scan_chunk_samples(sr) // 2 if hop is None else int(hop)
+        items, start = self._cut_items(segments, hop, _ffi.VAD_CUT_RANGE, int(channels), rate=sr)
+        b = self._audio_batch_record(batch)
+        w, wp = self._audio_windows(windows)
+        _own, ptrs, nss = self._audio_affine(shift, scale)
+        thr = -1.0 if denoise is None else float(denoise)
+        self._check(self._lib.vad_scan_audio_batch_device(self._h, items, len(start) - 1, d_audio or None, int(audio_samples), int(channels),
+                                                          int(fmt), sr or 0, hop, thr, C.byref(b), wp, w.size, *ptrs, nss, d_out or None,
+                                                          int(out_bytes), d_mask or None, stream or None))
+        return (w.size, b.samples)
+
     # ------------------------------------------------------------------ log-mel features
     @staticmethod
     def _mel_arrays(spec):

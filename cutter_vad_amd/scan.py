@@ -1263,3 +1263,210 @@ def batch_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, batch: Fea
         return out, [where[int(w["seg"])] + (int(w["row0"]), int(w["nrows"]), int(w["window"]), int(w["offset"])) for w in windows]
     index = [where[int(w["seg"])] + (int(w["row0"]), int(w["nrows"])) for w in windows]
     return out, index
+
+
+@dataclass(frozen=True)
+class AudioBatch:
+    """What a model that takes the waveform itself is fed, for ``audio_recordings`` / ``Engine.audio_batch``: windows of ``samples``
+    samples every ``stride`` samples of each segment (``stride=None``: ``samples``; ``samples=None``: one window per segment, as long
+    as the longest segment rounded up to a multiple of 4), normalised by ``norm`` - ``"none"``, ``"mean"`` (the mean taken off),
+    ``"zscore"`` (and divided by ``sqrt(var + eps)``: wav2vec 2.0's feature extractor) or ``"peak"`` (times ``target / peak``:
+    ``AudioUtils.normalize_audio``) - with the statistics of the ``scope``: the ``"segment"``, or all segments of the
+    ``"recording"`` (and channel).  ``dtype`` is ``"f32"``, ``"f16"`` or ``"bf16"`` (bit patterns as uint16).  Samples past a
+    segment's end are ``pad_value`` as it is (``pad="value"``) or silence through the normalisation (``pad="feature"``).  wav2vec
+    2.0's setting::
+
+        AudioBatch(norm="zscore", eps=1e-7)
+    """
+    samples: Optional[int] = None
+    stride: Optional[int] = None
+    norm: str = "none"
+    eps: float = 1e-7
+    target: float = 0.9
+    scope: str = "segment"
+    dtype: str = "f32"
+    pad: str = "value"
+    pad_value: float = 0.0
+
+    def check(self) -> None:
+        if self.norm not in ("none", "mean", "zscore", "peak"):
+            raise ConfigurationError("norm", repr(self.norm), f"AudioBatch: norm is 'none', 'mean', 'zscore' or 'peak', got {self.norm!r}")
+        if self.dtype not in _ffi.BATCH_DTYPES or self.pad not in _ffi.BATCH_PADS:
+            raise ConfigurationError("dtype", repr((self.dtype, self.pad)), f"AudioBatch: dtype is one of {sorted(_ffi.BATCH_DTYPES)}, pad one of "
+                                     f"{sorted(_ffi.BATCH_PADS)}, got {self.dtype!r}, {self.pad!r}")
+        if self.samples is not None and (int(self.samples) < 4 or int(self.samples) > 1 << 24 or int(self.samples) % 4):
+            raise ConfigurationError("samples", repr(self.samples), f"AudioBatch: samples is a multiple of 4 from 4 to 2^24, got {self.samples!r}")
+        if self.stride is not None and (int(self.stride) < 4 or int(self.stride) % 4):
+            raise ConfigurationError("stride", repr(self.stride), f"AudioBatch: stride is a multiple of 4, 4 or more, got {self.stride!r}")
+        if self.scope not in ("segment", "recording"):
+            raise ConfigurationError("scope", repr(self.scope), f"AudioBatch: scope is 'segment' or 'recording', got {self.scope!r}")
+        if not (np.isfinite(self.eps) and float(self.eps) >= 0):
+            raise ConfigurationError("eps", repr(self.eps), f"AudioBatch: eps is a finite number, 0 or more, got {self.eps!r}")
+        if not (np.isfinite(self.target) and float(self.target) > 0):
+            raise ConfigurationError("target", repr(self.target), f"AudioBatch: target is a finite number above 0, got {self.target!r}")
+        if not np.isfinite(self.pad_value):
+            raise ConfigurationError("pad_value", repr(self.pad_value), f"AudioBatch: pad_value is a finite number, got {self.pad_value!r}")
+
+    def record(self) -> dict:
+        """-> ``vad_audio_batch``'s fields as ``Engine.audio_batch`` takes them (``samples`` must be set)"""
+        self.check()
+        if self.samples is None:
+            raise ConfigurationError("samples", "None", "AudioBatch: samples=None is resolved by audio_windows; Engine.audio_batch takes a number")
+        return {"samples": int(self.samples), "dtype": self.dtype, "pad": self.pad, "pad_value": float(self.pad_value)}
+
+
+def audio_windows(nsamples, samples: Optional[int] = None, stride: Optional[int] = None) -> Tuple[np.ndarray, int]:
+    """``batch_windows`` for samples: the windows of segments of ``nsamples`` [n] samples each -> (windows, T): per segment of S
+    samples one window at ``sample0 = 0, stride, 2 * stride, ...`` while ``sample0 < S``, each of ``min(samples, S - sample0)``
+    samples, as a ``(seg, nsamples, sample0)`` record array ``Engine.audio_batch`` takes.  ``stride`` is a multiple of 4;
+    ``stride=None``: ``samples``.  ``samples=None``: one window per segment (also one without samples) and T the longest segment
+    rounded up to a multiple of 4 (4 at the least)."""
+    S = np.asarray(nsamples, np.int64).reshape(-1)
+    if (S < 0).any():
+        raise ConfigurationError("nsamples", repr(S[:8].tolist()), "audio_windows: a segment has 0 or more samples")
+    if samples is None:
+        T = max(4, -(-int(S.max(initial=0)) // 4) * 4)
+        if T > 1 << 24:
+            raise ConfigurationError("samples", "None", f"audio_windows: the longest segment has {int(S.max())} samples, a window 2^24 at the most: "
+                                     "give samples")
+        w = np.zeros(S.size, _ffi.AUDIO_WINDOW_DTYPE)
+        w["seg"], w["nsamples"] = np.arange(S.size), S
+        return w, T
+    T = int(samples)
+    step = T if stride is None else int(stride)
+    if T < 4 or T > 1 << 24 or T % 4 or step < 4 or step % 4:
+        raise ConfigurationError("samples", repr((samples, stride)), "audio_windows: samples is a multiple of 4 from 4 to 2^24 and stride a multiple "
+                                 f"of 4, 4 or more, got {samples!r} and {stride!r}")
+    rec = [(i, min(T, int(s) - r), r) for i, s in enumerate(S) for r in range(0, int(s), step)]
+    return np.array(rec, _ffi.AUDIO_WINDOW_DTYPE).reshape(-1), T
+
+
+def audio_affine(moments, levels, nsamples, norm: str = "none", eps: float = 1e-7, target: float = 0.9):
+    """``Engine.moments`` / ``Engine.levels`` records and the sample counts they run over -> ``(shift, scale)`` as ``Engine.audio_batch``
+    takes them, for ``norm``: ``"none"``: two ``None``; ``"mean"``: ``shift = -mean``; ``"zscore"``: also ``scale = 1 / sqrt(max(var,
+    0) + eps)`` - ``mean = sum_q31 / (2^31 N)``, ``var = energy_q32 / (2^32 N) - mean^2``, in float64 from the integers, rounded to
+    float32 once; ``"peak"``: ``scale = np.float32(np.float32(target) / peak)``, 1 where the peak is 0 or not finite (it needs
+    ``levels``; the other two need ``moments``).  An entry without samples gets 0 and 1."""
+    if norm == "none":
+        return None, None
+    if norm == "peak":
+        peak = np.asarray(levels["peak"], np.float32)
+        usable = np.isfinite(peak) & (peak > 0)
+        return None, np.where(usable, np.float32(target) / np.where(usable, peak, np.float32(1)), np.float32(1)).astype(np.float32)
+    if norm not in ("mean", "zscore"):
+        raise ConfigurationError("norm", repr(norm), f"audio_affine: norm is 'none', 'mean', 'zscore' or 'peak', got {norm!r}")
+    N = np.asarray(nsamples, np.int64).reshape(-1).astype(np.float64)
+    some = N > 0
+    Ns = np.where(some, N, 1.0)
+    mean = np.where(some, np.asarray(moments["sum_q31"]).astype(np.float64) / (2147483648.0 * Ns), 0.0)
+    shift = (-mean).astype(np.float32)
+    if norm == "mean":
+        return shift, None
+    var = np.asarray(moments["energy_q32"]).astype(np.float64) / (4294967296.0 * Ns) - mean * mean
+    scale = np.where(some, 1.0 / np.sqrt(np.maximum(var, 0.0) + float(eps)), 1.0).astype(np.float32)
+    return shift, scale
+
+
+def _need_audio_batch(engine, who: str) -> None:
+    if not hasattr(engine, "audio_batch") or not hasattr(engine, "moments"):
+        raise ConfigurationError("batch", "given", f"{who} needs an engine with audio_batch and moments (the windows are normalised and padded "
+                                 f"from the block a scan left on the GPU), {type(engine).__name__} has none")
+
+
+def audio_recordings(recordings: Sequence[np.ndarray], batch: AudioBatch, config: Optional[VADConfig] = None, engine=None,
+                     hop: Optional[int] = None, law: Optional[str] = None, channel="mix", open_end: bool = False,
+                     refine: Optional[SegmentRefine] = None, sample_rate: Optional[int] = None, convert=None, mask: bool = False):
+    """``cut_recordings(layout="range")`` as the tensor a waveform model takes: the samples of every finished segment of every
+    recording, windowed, normalised, padded and converted as ``batch`` says -> ``(array, index)`` or, with ``mask=True``, ``(array,
+    index, mask)``: ``array`` [B, T] (``Engine.audio_batch``), ``mask`` [B, T] uint8 (1 on a window's samples), ``index`` one
+    ``(recording, channel, start_sample, end_sample, first_sample, nsamples)`` per window - the segment it shows, the window's first
+    sample in the segment and its samples.  One scan, at most one ``Engine.moments`` or ``Engine.levels`` and one
+    ``Engine.audio_batch`` under ``Engine.scan_session()``: the samples never leave the GPU as float32, only 16 bytes per segment
+    and the batch cross the link.  ``batch.scope="recording"`` adds the integer records of a (recording, channel) on the host first.
+    The other arguments as in ``cut_recordings``.  Recordings at another rate than the engine's go through ``convert=`` (as in
+    ``scan_recordings``: the windows and the ranges of ``index`` count samples of the converted signal, ``input_ranges`` maps them
+    back); a ``sample_rate`` other than the engine's without ``convert`` is a ``ConfigurationError``.  A corpus of 1-D and 2-D
+    recordings is a ``ConfigurationError``: call it once per kind.  No segment anywhere: an array with B = 0."""
+    from .pool import default_pool, resolve_model_path
+    who = "audio_recordings"
+    batch.check()
+    split = isinstance(channel, str) and channel == "split"
+    if not (channel in ("mix", "split") if isinstance(channel, str) else isinstance(channel, (int, np.integer)) and int(channel) in (0, 1)):
+        raise ConfigurationError("channel", repr(channel), f"{who}: channel is 'mix', 0, 1 or 'split' for the whole corpus, got {channel!r}")
+    cfg = config or VADConfig()
+    if engine is None:
+        engine = default_pool().engine_for(resolve_model_path(cfg), cfg.model_version, sample_rate=int(cfg.sample_rate))
+    _need_audio_batch(engine, who)
+    if batch.norm == "peak":
+        _need_levels(engine, who, "norm='peak'")
+    if open_end:
+        _need_tails(engine, who)
+    if refine is not None:
+        _need_refine(engine, who)
+    frame = engine.frame_samples
+    if cfg.buffer_size != frame:
+        raise ConfigurationError(f"{who} frames at the model's frame size: buffer_size = {cfg.buffer_size}, the engine's frames have "
+                                 f"{frame} samples")
+    conv = _convert_arg(who, engine, sample_rate, convert, split)
+    if conv is None and sample_rate is not None and int(sample_rate) != int(engine.sample_rate):
+        raise ConfigurationError("sample_rate", repr(sample_rate), f"{who}: recordings at {sample_rate} Hz on an engine at {engine.sample_rate} Hz "
+                                 "need convert= (the batch does not resample: the recordings are converted once, ahead of the scan)")
+    hop = frame // 2 if hop is None else int(hop)
+    recordings = [np.asarray(r) for r in recordings]
+    kinds = {r.ndim == 2 for r in recordings}
+    if len(kinds) > 1:
+        raise ConfigurationError("recordings", "1-D and 2-D", f"{who}: one batch holds recordings of one kind; call it once for the 1-D and once "
+                                 "for the two-channel recordings")
+    np_dtype = {"f32": np.float32, "f16": np.float16}.get(batch.dtype, np.uint16)
+    T0 = int(batch.samples) if batch.samples is not None else 4
+    none = (np.empty((0, T0), np_dtype), []) + ((np.empty((0, T0), np.uint8),) if mask else ())
+    if not recordings:
+        return none
+    two = kinds.pop()
+    denoise = 0.01 if cfg.enable_denoising else None
+    per = 2 if two and split else 1
+    chans = (0, 1) if per == 2 else (channel if two and conv is None else 0,)
+    slots = engine.open_streams(len(recordings) * per)
+    out = None
+    try:
+        engine.set_thresholds_many(slots, _thresholds_of(cfg))
+        with engine.scan_session():
+            ranges = _scan_ranges(engine, slots, recordings, per, frame, hop, law, denoise, channel, open_end=open_end, refine=refine, convert=conv)
+            table = _cut_table(engine, ranges, chans, frame, hop)
+            if table:
+                ns = np.array([(n - 1) * hop + frame for _, _, n, _ in table], np.int64)
+                windows, T = audio_windows(ns, batch.samples, batch.stride)
+                mo = lv = None
+                if batch.norm in ("mean", "zscore"):
+                    mo = engine.moments(table, hop=hop, denoise=denoise)
+                elif batch.norm == "peak":
+                    lv = engine.levels(table, hop=hop, denoise=denoise)
+                if batch.scope == "recording" and batch.norm != "none":
+                    # the group of a segment: its (recording, channel), numbered in the table's order; integers add exactly
+                    group = np.array([i * per + c for i, rc in enumerate(ranges) for c, rg in enumerate(rc) for _ in rg], np.int64)
+                    ngroups = len(recordings) * per
+                    gn = np.zeros(ngroups, np.int64)
+                    np.add.at(gn, group, ns)
+                    if mo is not None:
+                        gm = np.zeros(ngroups, _ffi.MOMENTS_DTYPE)
+                        np.add.at(gm["sum_q31"], group, mo["sum_q31"])
+                        np.add.at(gm["energy_q32"], group, mo["energy_q32"])
+                        mo = gm
+                    else:
+                        gl = np.zeros(ngroups, _ffi.LEVEL_DTYPE)
+                        # (the maximum of the bit patterns of |x|, as the kernel takes it)
+                        np.maximum.at(gl["peak"].view(np.uint32), group, lv["peak"].view(np.uint32))
+                        lv = gl
+                    shift, scale = (None if a is None else a[group] for a in audio_affine(mo, lv, gn, batch.norm, batch.eps, batch.target))
+                else:
+                    shift, scale = audio_affine(mo, lv, ns, batch.norm, batch.eps, batch.target)
+                out = engine.audio_batch(table, windows, replace(batch, samples=T).record(), shift=shift, scale=scale, mask=mask, hop=hop,
+                                         denoise=denoise)
+    finally:
+        for s in slots:
+            engine.close_stream(int(s))
+    if out is None:
+        return none
+    where = [(i, chans[c], a, b) for i, rc in enumerate(ranges) for c, rg in enumerate(rc) for a, b, *_ in rg]
+    index = [where[int(w["seg"])] + (int(w["sample0"]), int(w["nsamples"])) for w in windows]
+    return (out[0], index, out[1]) if mask else (out, index)

@@ -1129,6 +1129,82 @@ VAD_API int vad_mel_stats_grouped_device(vad_engine *e, const float *d_features 
                                          int64_t ngroups, float *d_max_out, int64_t *d_sum_out, uint64_t *d_sumsq_out, void *stream);
 
 /*
+ * Audio batches: what a model that takes the waveform itself is fed - wav2vec 2.0, HuBERT, WavLM, speaker embedders: [B][T] windows
+ * of samples in the model's number format, mean-removed, z-scored or peak-normalised per utterance, zero-padded, with an attention
+ * mask - made from the block a scan left on the GPU, without the samples crossing the link as float32 and coming back.
+ *
+ * THE RULE of both calls: they work on exactly the float32 values that vad_scan_cut / vad_scan_rate_cut would write for each item
+ * with VAD_CUT_RANGE, VAD_CUT_F32 and the same block arguments - decoded, channel-selected and gated; on a rate block (sr_in 8000 /
+ * 24000 / 48000) input-rate samples, never gated.  Every word of vad_scan_levels about the block, the items, sr_in, audio == NULL,
+ * the resident block and which engines are served applies: out_sample is NOT read, items may share samples, no model kernel runs.
+ *
+ * vad_scan_moments: one vad_moments per listed segment, for its mean and variance.
+ *   sum_q31 = sum over the samples of rint((double) clamp(x, -1, 1) * 2^31), rounded to nearest-even.  The product is exact in
+ * float64, so the sum is an integer, exact in any order, and below 2^62 for a block under 2^31 samples.
+ *   energy_q32 is vad_level's field by the same definition: the two calls agree on it byte for byte.
+ *   For int16 / 32768 and G.711 blocks nothing is rounded: sum_q31 = 65536 * sum of s.
+ *   mean = sum_q31 / (2^31 N), var = energy_q32 / (2^32 N) - mean^2, with N the segment's samples.
+ *   All reductions are integer, no float atomics: two calls give the same bytes.  A segment that holds a NaN gets an unspecified
+ * record; other segments are unaffected.
+ *   VAD_ERR_INVALID_ARG / VAD_ERR_UNSUPPORTED, each with a message and nothing written: every refusal of vad_scan_levels about the
+ * rate, the block and the items, in the same words under this function's name; then a null out with n > 0.  n == 0: VAD_OK.
+ *   vad_scan_moments_device: d_audio as vad_scan_cut_device takes it, d_out (8-byte aligned, n records) on the engine's GPU;
+ * enqueues a clear of the records and the kernel on `stream` (NULL = the engine's own) and returns.
+ *
+ * vad_scan_audio_batch / _device: nw windows of b->samples = T samples each, out[nw][T] in float32, float16 or bfloat16 (dtype and
+ * pad_mode are vad_batch's: VAD_BATCH_F32 / F16 / BF16, VAD_BATCH_PAD_VALUE / PAD_FEATURE), and mask[nw][T] bytes when asked.
+ *   Window w shows samples sample0 .. sample0 + nsamples - 1 of segment seg's range: sample0 >= 0 and a multiple of 4, 0 <= nsamples
+ * <= T, sample0 + nsamples <= S = the segment's vad_cut_samples / vad_rate_cut_samples(.., VAD_CUT_RANGE).  T is a multiple of 4 in
+ * 4 .. 2^24.
+ *   cell (w, t), t < nsamples: (x + shift[i]) * scale[i] with i = seg, or 0 when nss == 1 - float32, an add, then a multiply, each
+ * rounded on its own.  shift == NULL is 0, scale == NULL is 1; both are HOST arrays [nss] in both forms.
+ *   cell (w, t), t >= nsamples, a pad cell: pad_value as it is (VAD_BATCH_PAD_VALUE) or (0 + shift[i]) * scale[i]
+ * (VAD_BATCH_PAD_FEATURE: silence through the normalisation).
+ *   Then the conversion, round to nearest even; overflow becomes inf.
+ *   mask[w][t] = 1 for t < nsamples, 0 otherwise.
+ *   Every cell of out and of mask is written exactly once, by ONE launch; nothing is accumulated: two calls give the same bytes.
+ * Windows may come in any order and overlap, the same samples may be shown twice, nsamples == 0 writes a pad window.  nw == 0 is
+ * VAD_OK.
+ *   Refusals, each VAD_ERR_INVALID_ARG or VAD_ERR_UNSUPPORTED with a message that names the function and the output untouched, in
+ * this order: every refusal of vad_scan_levels about the rate, the block and the items; a null b, T out of range, an unknown dtype
+ * or pad_mode, a non-finite pad_value; a negative nw or out_bytes, null windows with nw > 0; nss neither 1 nor n when shift or
+ * scale is given; a non-finite shift or scale, by index; a bad window, by index; out_bytes below nw * T elements; more than 2^31 - 1
+ * workgroups (of VAD_CUT_WG_SAMPLES samples of a window); a null out with nw > 0; then what vad_scan_levels says about the block's
+ * pointer and residency, d_out not 16-byte aligned, d_mask not 4-byte aligned.
+ *   Every engine is served.  VAD_ABI_VERSION is unchanged: the presence of vad_scan_audio_batch is how a caller detects the feature.
+ */
+typedef struct vad_moments {
+    int64_t sum_q31;     /* sum of rint(clamp(x, -1, 1) * 2^31) over the segment's samples */
+    int64_t energy_q32;  /* vad_level's field */
+} vad_moments;           /* 16 bytes */
+typedef struct vad_audio_batch {
+    int32_t samples;   /* T: samples of a window, a multiple of 4 in 4 .. 2^24 */
+    int32_t dtype;     /* VAD_BATCH_F32 / VAD_BATCH_F16 / VAD_BATCH_BF16 */
+    int32_t pad_mode;  /* VAD_BATCH_PAD_VALUE / VAD_BATCH_PAD_FEATURE */
+    float pad_value;
+} vad_audio_batch;
+typedef struct vad_audio_window {
+    int32_t seg;       /* index into the items */
+    int32_t nsamples;  /* 0 .. T */
+    int64_t sample0;   /* first sample, within the segment's range: a multiple of 4 */
+} vad_audio_window;    /* 16 bytes */
+VAD_API int vad_scan_moments(vad_engine *e, const vad_cut_item *items, int64_t n, const void *audio /*or NULL*/, int64_t audio_samples,
+                             int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, vad_moments *out /*[n]*/);
+VAD_API int vad_scan_moments_device(vad_engine *e, const vad_cut_item *items, int64_t n, const void *d_audio, int64_t audio_samples,
+                                    int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh,
+                                    vad_moments *d_out /*on the GPU, [n]*/, void *stream);
+VAD_API int vad_scan_audio_batch(vad_engine *e, const vad_cut_item *items, int64_t n, const void *audio /*or NULL*/, int64_t audio_samples,
+                                 int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh, const vad_audio_batch *b,
+                                 const vad_audio_window *windows /*host*/, int64_t nw, const float *shift /*[nss] or NULL*/,
+                                 const float *scale /*[nss] or NULL*/, int64_t nss /*1 or n*/, void *out, int64_t out_bytes,
+                                 uint8_t *mask /*[nw][T] or NULL*/);
+VAD_API int vad_scan_audio_batch_device(vad_engine *e, const vad_cut_item *items, int64_t n, const void *d_audio, int64_t audio_samples,
+                                        int32_t channels, int frame_fmt, int32_t sr_in, int32_t hop, float denoise_thresh,
+                                        const vad_audio_batch *b, const vad_audio_window *windows /*host*/, int64_t nw,
+                                        const float *shift /*host*/, const float *scale /*host*/, int64_t nss, void *d_out, int64_t out_bytes,
+                                        uint8_t *d_mask /*on the GPU or NULL*/, void *stream);
+
+/*
  * Rendered audio: one finished piece of audio per call - the segments of a block faded at their edges, crossfaded where two of
  * them share output samples, joined, everything else silence.  The two standard products of a VAD come out of it by where the caller
  * places the segments: silence removal (the segments back to back, neighbours overlapping by the ramp or a fixed pause apart) and

@@ -1242,6 +1242,168 @@ def scan_levels():
     return row
 
 
+def scan_audio_batch():
+    """What audio batches cost, on scan_levels' corpus: VAD_SCAN_BENCH_N (default 1 024) int16 recordings of 30 s at
+    16 kHz, hop 256, the table of its scan.  (a) on device pointers, HIP-event timed: vad_scan_moments_device against
+    vad_scan_levels_device on the same table; (b) likewise vad_scan_audio_batch_device (float16, z-score, one window per segment, T the
+    longest segment, with its mask) against vad_scan_cut_gain_device(RANGE, F32), with the bytes each moves; (c) audio_recordings
+    against the way to the same bytes without it: Engine.cut(layout="range", out="f32") behind the same scan, then the moments, the
+    z-score, the padding and the conversion in numpy on 16 host threads - the two alternate, the scan is part of both.  One warm-up,
+    then three timed passes of each; medians.  The result goes to profiles/scan_audio_batch.json."""
+    import ctypes as C
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from cutter_vad_amd import AudioBatch, VADConfig, _ffi, audio_affine, audio_recordings, audio_windows
+    N = int(os.environ.get("VAD_SCAN_BENCH_N", "1024"))
+    eng = Engine(blob(5), max_streams=max(N, 16))
+    hop, frame = 256, 512
+    gold = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "speech16k_i16.npz")
+    pcm = np.tile(np.load(gold)["pcm"].astype(np.int16), 3)
+    rng = np.random.default_rng(N)
+    ns = 30 * 16000
+    recs = [pcm[a:a + ns] for a in rng.integers(0, pcm.size - ns + 1, N)]
+    thr = (0.4, 0.3, 0.8, 0.95, 6, 12)
+    cfg = VADConfig(sample_rate=16000, buffer_size=frame, vad_start_probability=thr[0], vad_end_probability=thr[1], voice_start_ratio=thr[2],
+                    voice_end_ratio=thr[3], voice_start_frame_count=thr[4], voice_end_frame_count=thr[5])
+    batch = AudioBatch(norm="zscore", dtype="f16")
+    med = lambda v: float(np.median(v))
+    row = {"config": f"scan_audio_batch: {N} int16 recordings of 30 s at 16 kHz in one call, hop {hop}, float16, z-score", "recordings": N, "passes": 3}
+    pool = ThreadPoolExecutor(16)
+
+    def numpy_route():
+        """the same scan, the float32 range cut across the link, then numpy on 16 threads -> (batch, mask, seconds of the numpy part)"""
+        slots = eng.open_streams(N)
+        try:
+            eng.set_thresholds_many(slots, thr)
+            with eng.scan_session():
+                table = eng.scan_segments(slots, recs, hop=hop, denoise=0.01)
+                offs = [int(o) for o in eng.last_scan["offsets"]]
+                segs = [(offs[i], f, n) for i, f, n in zip(table["item"].tolist(), table["first_frame"].tolist(), table["nframes"].tolist())]
+                data, start = eng.cut(segs, hop=hop, denoise=0.01, layout="range", out="f32")
+        finally:
+            for s in slots:
+                eng.close_stream(int(s))
+        t0 = time.perf_counter()
+        n = len(segs)
+        mo = np.zeros(n, _ffi.MOMENTS_DTYPE)
+
+        def moment(i):
+            x = data[start[i]:start[i + 1]].astype(np.float64)
+            mo[i] = (np.rint(np.clip(x, -1.0, 1.0) * 2147483648.0).astype(np.int64).sum(),
+                     np.minimum(np.rint(x * x * 4294967296.0), 4294967296.0).astype(np.int64).sum())
+        list(pool.map(moment, range(n)))
+        counts = np.diff(start)
+        shift, scale = audio_affine(mo, None, counts, "zscore", batch.eps)
+        _, T = audio_windows(counts)
+        out, mask = np.zeros((n, T), np.float16), np.zeros((n, T), np.uint8)
+
+        def fill(i):
+            out[i, :counts[i]] = ((data[start[i]:start[i + 1]] + shift[i]) * scale[i]).astype(np.float16)
+            mask[i, :counts[i]] = 1
+        list(pool.map(fill, range(n)))
+        return out, mask, time.perf_counter() - t0, segs, int(data.nbytes)
+
+    got, index, gmask = audio_recordings(recs, batch, cfg, engine=eng, hop=hop, mask=True)
+    want, wmask, _, segs, cut_bytes = numpy_route()
+    row.update(segments=len(segs), windows=int(got.shape[0]), T=int(got.shape[1]),
+               c_equal=bool(got.tobytes() == want.tobytes() and gmask.tobytes() == wmask.tobytes()))
+    a_runs, b_runs, b_np = [], [], []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        audio_recordings(recs, batch, cfg, engine=eng, hop=hop, mask=True)
+        a_runs.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        r = numpy_route()
+        b_runs.append(time.perf_counter() - t0)
+        b_np.append(r[2])
+    block_bytes = int(sum(r.nbytes for r in recs))
+    row.update(c_s_audio_recordings_runs=a_runs, c_s_audio_recordings=med(a_runs), c_s_cut_numpy_runs=b_runs, c_s_cut_numpy=med(b_runs),
+               c_s_numpy_part=med(b_np), c_ratio_numpy_over_gpu=med(b_runs) / med(a_runs),
+               c_link_up_gpu=block_bytes, c_link_back_gpu=int(16 * len(segs) + got.nbytes + gmask.nbytes),
+               c_link_up_numpy=block_bytes, c_link_back_numpy=cut_bytes)
+    del want, wmask, got, gmask
+    # (a), (b) on device pointers: the kernels alone, bracketed by events as scan_levels (c) brackets them
+    counts = np.array([(n - 1) * hop + frame for _, _, n in segs], np.int64)
+    slots = eng.open_streams(N)
+    with eng.scan_session():
+        eng.scan_segments(slots, recs, hop=hop, denoise=0.01)
+        last = eng.last_scan
+        block = np.zeros(last["samples"], np.int16)
+        for r, o in zip(recs, last["offsets"]):
+            block[int(o):int(o) + r.size] = r
+        fmt = last["fmt"]
+    d_audio = torch.from_numpy(block).cuda()
+    windows, T = audio_windows(counts)
+    n = len(segs)
+    d_cut = torch.empty(int(counts.sum()) + 16, dtype=torch.float32, device="cuda")
+    d_out = torch.empty(n * T + 16, dtype=torch.float16, device="cuda")
+    d_mask = torch.empty(n * T + 16, dtype=torch.uint8, device="cuda")
+    d_rec = torch.zeros(2 * n, dtype=torch.int64, device="cuda")
+    ts = torch.cuda.Stream()
+    busy = torch.randn(6144, 6144, device="cuda")
+    lib, h = eng._lib, eng.handle
+    items, _ = eng._cut_items(segs, hop, _ffi.VAD_CUT_RANGE, 1)
+    where = (d_audio.data_ptr(), block.size, 1, fmt)
+    mo = eng.moments(segs, hop=hop, denoise=0.01, audio=block)
+    shift, scale = audio_affine(mo, None, counts, "zscore", batch.eps)
+    f32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    rec = _ffi.AudioBatchRecord(T, _ffi.VAD_BATCH_F16, _ffi.VAD_BATCH_PAD_VALUE, 0.0)
+    wp = windows.ctypes.data_as(C.POINTER(_ffi.AudioWindow))
+
+    def event_timed(fn):
+        out = []
+        for k in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            with torch.cuda.stream(ts):
+                torch.mm(busy, busy)
+            e0.record(ts)
+            assert fn() == 0
+            e1.record(ts)
+            torch.cuda.synchronize()
+            if k >= 2:                           # two warm-ups
+                out.append(e0.elapsed_time(e1) * 1e-3)
+        return out
+
+    calls = {"a_s_moments_device": lambda: lib.vad_scan_moments_device(h, items, n, *where, 0, hop, 0.01, d_rec.data_ptr(), ts.cuda_stream),
+             "a_s_levels_device": lambda: lib.vad_scan_levels_device(h, items, n, *where, 0, hop, 0.01, 0.95, d_rec.data_ptr(), ts.cuda_stream),
+             "b_s_audio_batch_device": lambda: lib.vad_scan_audio_batch_device(h, items, n, *where, 0, hop, 0.01, C.byref(rec), wp, n, f32p(shift),
+                                                                               f32p(scale), n, d_out.data_ptr(), n * T * 2, d_mask.data_ptr(),
+                                                                               ts.cuda_stream),
+             "b_s_cut_gain_range_f32_device": lambda: lib.vad_scan_cut_gain_device(h, items, n, f32p(scale), *where, 0, hop, 0.01, _ffi.VAD_CUT_RANGE,
+                                                                                   _ffi.VAD_CUT_F32, d_cut.data_ptr(), int(counts.sum()),
+                                                                                   ts.cuda_stream)}
+    for name, fn in calls.items():
+        runs = event_timed(fn)
+        row[name + "_runs"], row[name] = runs, med(runs)
+    read = int(counts.sum()) * 2
+    row["a_ratio_moments_over_levels"] = row["a_s_moments_device"] / row["a_s_levels_device"]
+    row["a_moments_GBps_read"] = read / row["a_s_moments_device"] / 1e9
+    row["b_batch_bytes_read"], row["b_batch_bytes_written"] = read, int(n * T * 3)
+    row["b_cut_bytes_read"], row["b_cut_bytes_written"] = read, int(4 * counts.sum())
+    row["b_batch_TBps"] = (read + n * T * 3) / row["b_s_audio_batch_device"] / 1e12
+    row["b_cut_TBps"] = (read + 4 * int(counts.sum())) / row["b_s_cut_gain_range_f32_device"] / 1e12
+    row["b_ratio_batch_over_cut"] = row["b_s_audio_batch_device"] / row["b_s_cut_gain_range_f32_device"]
+    row["not_measured"] = "the bfloat16 and float32 batches, strided windows, the peak and recording scopes, two-channel and rate blocks"
+    for s in slots:
+        eng.close_stream(int(s))
+    eng.close()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "profiles", "scan_audio_batch.json"), "w") as f_:
+        json.dump({"what": "Audio batches (vad_scan_moments, vad_scan_audio_batch, csrc/scan_levels.hip, csrc/audio_batch.hip): DESIGN 2.1x",
+                   "how": "python tools/bench_configs.py scan_audio_batch on one MI355X, one process.  (a), (b) device forms: HIP events "
+                          "behind a matrix product that keeps the stream busy while the host builds the tables, two warm-ups and three timed "
+                          "passes; the bytes are computed from the shapes (samples read once, cells and mask written once), not counted.  "
+                          "(c) the two routes alternate, wall clock around the Python calls, scan included in both, one warm-up and three "
+                          "timed passes, medians; the numpy route uses only code the parent has.  Not measured: " + row["not_measured"] +
+                          ", L2 hit rates, the spread between processes and boxes",
+                   "runs": [row]}, f_, indent=1)
+        f_.write("\n")
+    return row
+
+
 def scan_mel():
     """What log-mel features of segment audio cost, on scan_levels' corpus: VAD_SCAN_BENCH_N (default 1 024) int16
     recordings of 30 s at 16 kHz, hop 256, the table of its scan, Whisper's geometry (n_fft 400, hop 160, 201 bins, 80 mels, Hann,

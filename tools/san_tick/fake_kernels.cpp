@@ -185,6 +185,80 @@ extern "C" hipError_t vadk_launch_scan_cut_gain(const CutArgs *a, const float *g
 extern "C" hipError_t vadk_launch_seg_levels(const CutArgs *a, float clip, hipStream_t) { return fake_cut(a, nullptr, true, clip); }
 extern "C" hipError_t vadk_launch_scan_cut_stereo(const CutArgs *a, const float *gains, hipStream_t) { return fake_cut(a, gains, false, 0.f, true); }
 
+// sample frame i of a block as the cut reads it: decoded, channel-selected by `mode`, gated; false: past the block
+static bool fake_heard(const void *audio, uint32_t audio_bytes, int fmt, int channels, uint32_t mode, float thresh, size_t i, float *x) {
+    const size_t ch = channels == 2 ? 2 : 1;
+    if ((i + 1) * ch * (fmt == VAD_FMT_F32 ? 4 : fmt >= VAD_FMT_ULAW8 ? 1 : 2) > audio_bytes) return false;
+    if (ch == 1) *x = first_sample(audio, i, fmt, 1);
+    else {
+        const float l = first_sample(audio, 2 * i, fmt, 1), r = first_sample(audio, 2 * i + 1, fmt, 1);
+        *x = mode == SCAN_MIX ? (l + r) * 0.5f : mode == SCAN_RIGHT ? r : l;
+    }
+    if (thresh >= 0.f && !(std::fabs(*x) > thresh)) *x = 0.f;
+    return true;
+}
+
+// a segment's moments (csrc/scan_levels.hip: vadk_seg_moments), sample by sample over the levels' work list: sum_q31 +=
+// rint(clamp(x, -1, 1) * 2^31) in float64, energy_q32 as fake_cut's levels have it; a.out is zeroed by the caller
+extern "C" hipError_t vadk_launch_seg_moments(const CutArgs *a, hipStream_t) {
+    for (uint32_t b = 0; b < a->nwork; ++b) {
+        const CutWork w = a->work[b];
+        const CutSeg sg = a->segs[w.seg];
+        const uint32_t mode = sg.quad_in >> SCAN_MODE_SHIFT, qin = sg.quad_in & ((1u << SCAN_MODE_SHIFT) - 1u);
+        vad_moments &mo = static_cast<vad_moments *>(a->out)[w.seg];
+        for (uint32_t oq = w.quad0; oq < w.quad0 + (uint32_t)CUT_WG_QUADS && oq < sg.nquads; ++oq)
+            for (int k = 0; k < 4; ++k) {
+                float x;
+                if (!fake_heard(a->audio, a->audio_bytes, a->fmt, a->channels, mode, a->thresh, 4 * ((size_t)qin + oq) + k, &x)) return hipErrorInvalidValue;
+                const double cl = x < -1.0f ? -1.0 : x > 1.0f ? 1.0 : (double)x;
+                mo.sum_q31 += (int64_t)std::rint(cl * 2147483648.0);                        // (a NaN: unspecified)
+                const double q = std::rint((double)x * (double)x * 4294967296.0);
+                mo.energy_q32 += (int64_t)(q < 4294967296.0 ? q : 4294967296.0);
+            }
+    }
+    return hipSuccess;
+}
+
+static uint16_t f16_bits(float f);
+
+// normalised, padded windows of segment audio (csrc/audio_batch.hip: vadk_audio_batch): include/vad_engine.h's rule cell by cell
+// over the host's work list, every operation a float32 of its own (volatile: each is rounded where it stands)
+extern "C" hipError_t vadk_launch_audio_batch(const AudioBatchArgs *a, hipStream_t) {
+    for (uint32_t b = 0; b < a->nwork; ++b) {
+        const AudioWork w = a->work[b];
+        const AudioWin win = a->win[w.window];
+        const CutSeg sg = a->segs[win.seg];
+        if (w.quad0 >= a->tq || win.nsamples > 4 * a->tq || (uint64_t)4 * win.quad0 + win.nsamples > (uint64_t)4 * sg.nquads) return hipErrorInvalidValue;
+        const uint32_t mode = sg.quad_in >> SCAN_MODE_SHIFT, qin = (sg.quad_in & ((1u << SCAN_MODE_SHIFT) - 1u)) + win.quad0;
+        const float shift = a->shift[a->per_seg ? win.seg : 0u], scale = a->scale[a->per_seg ? win.seg : 0u];
+        auto norm = [&](float x) -> float {
+            volatile float s = x + shift;
+            return s * scale;
+        };
+        for (uint32_t q = w.quad0; q < w.quad0 + (uint32_t)CUT_WG_QUADS && q < a->tq; ++q)
+            for (uint32_t k = 0; k < 4; ++k) {
+                const uint32_t t = 4 * q + k;
+                float val;
+                if (t < win.nsamples) {
+                    float x;
+                    if (!fake_heard(a->audio, a->audio_bytes, a->fmt, a->channels, mode, a->thresh, 4 * (size_t)qin + t, &x)) return hipErrorInvalidValue;
+                    val = norm(x);
+                } else {
+                    val = a->pad_mode == VAD_BATCH_PAD_FEATURE ? norm(0.0f) : a->pad_value;
+                }
+                const size_t o = (size_t)w.window * 4 * a->tq + t;
+                if (a->dtype == VAD_BATCH_F32) static_cast<float *>(a->out)[o] = val;
+                else {
+                    uint32_t bits;
+                    std::memcpy(&bits, &val, 4);
+                    static_cast<uint16_t *>(a->out)[o] = a->dtype == VAD_BATCH_F16 ? f16_bits(val) : melb_bf16(bits);
+                }
+                if (a->mask) a->mask[o] = t < win.nsamples ? 1 : 0;
+            }
+    }
+    return hipSuccess;
+}
+
 // log-mel frames of finished segments (csrc/scan_mel.hip: vadk_seg_mel), the header's rule in plain float32 loops, tile by tile as
 // the workgroups are listed, over the UNPACKED view of the same tables: the cut's decoded, channel-selected, gated sample, reflected
 // by index, op_re / op_im / filters read back out of the packed streams (vad_layout.h: mel_op_index, mel_filter_index), sums in

@@ -401,8 +401,22 @@ int main(int argc, char **argv) {
         const float taps[3] = {0.25f, 0.5f, 0.25f};
         OK(vad_scan_rate_mel(eng, two, 2, &m, op.data(), op.data(), fil.data(), taps, 3, block.data(), NS, 1, VAD_FMT_F32, 48000, 256, out.data(), 63));
         CHECK(std::isfinite(out[0]) && std::isfinite(out[4 * 63 - 1]));
+        // the records of 512 and 768 samples of 0.25: 2^29 a sample in the sum, 2^28 in the energy
+        vad_moments mo[2];
+        OK(vad_scan_moments(eng, two, 2, block.data(), NS, 1, VAD_FMT_F32, 0, 256, -1.0f, mo));
+        CHECK(mo[0].sum_q31 == 512ll << 29 && mo[0].energy_q32 == 512ll << 28 && mo[1].sum_q31 == 768ll << 29 && mo[1].energy_q32 == 768ll << 28);
+        // three windows of 8 samples, the last one a pad window, with a mask: 0.25 - 0.125 per segment, then times 2 and 4
+        const vad_audio_batch ab = {8, VAD_BATCH_F32, VAD_BATCH_PAD_FEATURE, 0.0f};
+        const vad_audio_window wins[3] = {{1, 5, 760}, {0, 8, 0}, {1, 0, 768}};
+        const float shift[2] = {-0.125f, 0.25f}, scale[2] = {2.0f, 4.0f};
+        uint8_t mask[25];
+        std::fill(mask, mask + 25, (uint8_t)9);
+        std::fill(out.begin(), out.end(), -7.0f);
+        OK(vad_scan_audio_batch(eng, two, 2, nullptr, NS, 1, VAD_FMT_F32, 0, 256, -1.0f, &ab, wins, 3, shift, scale, 2, out.data(), 24 * 4, mask));
+        CHECK(out[0] == 2.0f && out[4] == 2.0f && out[5] == 1.0f && out[8] == 0.25f && out[15] == 0.25f && out[16] == 1.0f && out[24] == -7.0f);
+        CHECK(mask[4] == 1 && mask[5] == 0 && mask[15] == 1 && mask[16] == 0 && mask[23] == 0 && mask[24] == 9);
         vad_engine_destroy(eng);
-        std::printf("san_tick: segment-audio calls ok (cut, rate cut over 2 windows, render, mel, rate mel)\n");
+        std::printf("san_tick: segment-audio calls ok (cut, rate cut over 2 windows, render, mel, rate mel, moments, audio batch)\n");
     }
     // ---- the segment-table family: one host call per runner on the smallest corpus with a record and a tail - two recordings, the
     //      first ends a segment and is inside the next at its last frame - so that each work area's slots run under the sanitizers
