@@ -15,7 +15,7 @@ from .core.vad_wrapper import VADWrapper
 from .core.async_vad_wrapper import AsyncVADWrapper
 from .engine import Engine
 from .pool import EnginePool, StreamBatch, default_pool
-from .scan import (AudioBatch, FeatureBatch, MelSpec, audio_affine, audio_recordings, audio_windows, SegmentRefine, batch_affine, batch_pack, batch_recordings, batch_windows, convert_ratio, convert_taps, cut_recordings, fade_ramp, features_recordings, input_ranges, level_stats, mel_filterbank, render_recordings,
+from .scan import (AudioBatch, CepstralSpec, FeatureBatch, MelSpec, audio_affine, audio_recordings, audio_windows, SegmentRefine, batch_affine, batch_pack, batch_recordings, batch_windows, convert_ratio, convert_taps, cut_recordings, dct_operator, fade_ramp, features_recordings, input_ranges, level_stats, mel_filterbank, render_recordings,
                    resample_taps, scan_recordings, segment_ranges, speech_segments, sweep_recordings)
 from .utils.audio import AudioUtils
 from .utils.wav_writer import WAVWriter
@@ -28,4 +28,4 @@ __all__ = ["VADWrapper", "AsyncVADWrapper", "VADConfig", "SampleRate", "SileroMo
            "speech_segments", "segment_ranges", "sweep_recordings", "SegmentRefine", "level_stats", "render_recordings", "fade_ramp",
            "MelSpec", "mel_filterbank", "features_recordings", "resample_taps", "FeatureBatch", "batch_windows", "batch_affine", "batch_pack",
            "batch_recordings", "convert_taps", "convert_ratio", "input_ranges", "AudioBatch", "audio_windows", "audio_affine",
-           "audio_recordings"]
+           "audio_recordings", "CepstralSpec", "dct_operator"]

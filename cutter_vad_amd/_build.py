@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvad_engine.so")
 ARCH = "gfx950"
 
-HIP_SOURCES = ["silero_v5.hip", "silero_v5_t16.hip", "silero_v4.hip", "silero_v4_t16.hip", "resample.hip", "resample_generic.hip", "resample_fft.hip", "vad_util.hip", "scan_cut.hip", "scan_segments.hip", "scan_resegment.hip", "scan_tails.hip", "scan_refine.hip", "scan_resample.hip", "scan_cut_resample.hip", "scan_levels.hip", "scan_render.hip", "scan_mel.hip", "scan_resample_cut.hip", "mel_batch.hip", "scan_convert.hip", "audio_batch.hip"]
+HIP_SOURCES = ["silero_v5.hip", "silero_v5_t16.hip", "silero_v4.hip", "silero_v4_t16.hip", "resample.hip", "resample_generic.hip", "resample_fft.hip", "vad_util.hip", "scan_cut.hip", "scan_segments.hip", "scan_resegment.hip", "scan_tails.hip", "scan_refine.hip", "scan_resample.hip", "scan_cut_resample.hip", "scan_levels.hip", "scan_render.hip", "scan_mel.hip", "scan_resample_cut.hip", "mel_batch.hip", "scan_convert.hip", "audio_batch.hip", "mel_project.hip"]
 CPP_SOURCES = ["engine.cpp", "pack_weights.cpp", "resample_tables.cpp"]
 
 

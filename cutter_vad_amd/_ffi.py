@@ -381,6 +381,8 @@ SIGNATURES = {
                                         C.POINTER(C.c_uint64)]),
     "vad_mel_stats_grouped_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _i64p, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _vp, _vp, _vp,
                                                _vp]),
+    "vad_mel_project": (C.c_int, [_vp, _f32p, C.c_int64, C.c_int32, _f32p, _f32p, C.c_int32, _f32p]),
+    "vad_mel_project_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _f32p, _f32p, C.c_int32, _vp, _vp]),
     "vad_scan_moments": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32, C.c_float,
                                    C.POINTER(Moments)]),
     "vad_scan_moments_device": (C.c_int, [_vp, C.POINTER(CutItem), C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int, C.c_int32, C.c_int32,

@@ -52,6 +52,7 @@ extern "C" hipError_t vadk_launch_seg_mel(const vadk::MelArgs *a, hipStream_t st
 extern "C" hipError_t vadk_launch_resample_cut(const vadk::ResampleCutArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_convert(const vadk::ConvertArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_mel_stats(const vadk::MelStatsArgs *a, hipStream_t stream);
+extern "C" hipError_t vadk_launch_mel_project(const vadk::ProjArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_mel_batch(const vadk::MelBatchArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_mel_batch_packed(const vadk::MelPackArgs *a, hipStream_t stream);
 extern "C" hipError_t vadk_launch_scan_render(const vadk::RenderArgs *a, hipStream_t stream);
@@ -242,6 +243,14 @@ struct vad_engine {
     std::vector<int64_t> melb_order;
     std::vector<int64_t> melb_rows;                // vad_mel_stats_grouped: a group's rows
     std::vector<float> melb_f;
+    // vad_mel_project: the packed operator and bias (vad_layout.h: proj_pack_index) in d_proj, CACHED as the mel operator is - proj_src
+    // are the caller's op and bias (zeros for NULL) of the previous pack, back to back - and the buffer the replace form projects
+    // into, which then changes places with d_melk
+    std::vector<float> proj_src, proj_pack;
+    int32_t proj_n_in = 0, proj_n_out = 0;
+    bool proj_packed = false;
+    float *d_proj = nullptr; size_t d_proj_cap = 0;
+    float *d_melk_alt = nullptr; size_t d_melk_alt_cap = 0;
     // vad_scan_audio_batch: the windows, the work list, and shift and scale back to back, which lie in d_cut behind the segments
     std::vector<vadk::AudioWin> ab_win;
     std::vector<vadk::AudioWork> ab_work;
@@ -976,7 +985,7 @@ void vad_engine_destroy(vad_engine *e) {
     weights_release(e->d_wstream16x);
     weights_release(e->d_wstream16y);
     void *bufs[] = {e->d_refine, e->d_refine_in, e->d_refine_out, e->d_tail_len, e->d_tailwork, e->d_reseg, e->d_resegtab, e->d_state, e->d_sm, e->d_frames, e->d_probs, e->d_events, e->d_seg, e->d_slots, e->d_g711,
-                    e->d_audio, e->d_items, e->d_win, e->d_items_win, e->d_cut, e->d_cut_out, e->d_mel, e->d_rsc, e->d_rsc_mid, e->d_cv_op, e->d_cv_in, e->d_cv_out, e->d_cv_tab, e->d_melk, e->d_melb_in, e->d_melb, e->d_melb_out, e->d_segwork, e->d_nsegs, e->d_segtab, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
+                    e->d_audio, e->d_items, e->d_win, e->d_items_win, e->d_cut, e->d_cut_out, e->d_mel, e->d_rsc, e->d_rsc_mid, e->d_cv_op, e->d_cv_in, e->d_cv_out, e->d_cv_tab, e->d_melk, e->d_melk_alt, e->d_proj, e->d_melb_in, e->d_melb, e->d_melb_out, e->d_segwork, e->d_nsegs, e->d_segtab, e->d_rs_in, e->d_rs_out, e->d_small_in, e->d_small_out, e->d_ctl};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->scan_done) (void)hipEventDestroy(e->scan_done);
@@ -2859,6 +2868,113 @@ int mel_stats_run(vad_engine *e, bool dev, const char *who, const float *feature
     return VAD_OK;
 }
 
+// op [n_in][n_out] and bias [n_out] (nullptr: zeros) in fragment order in e->d_proj (vad_layout.h: proj_pack_index), the bias behind
+// the operator, zeros in the padding.  Cached against the bytes of the previous call, as mel_operator is
+int project_operator(vad_engine *e, int32_t n_in, int32_t n_out, const float *op, const float *bias, hipStream_t s) {
+    const size_t no = (size_t)n_in * (size_t)n_out, nb = (size_t)n_out;
+    const uint32_t K4 = vadk::proj_up4((uint32_t)n_in), N16 = vadk::proj_up16((uint32_t)n_out);
+    bool same = e->proj_packed && e->proj_n_in == n_in && e->proj_n_out == n_out && e->proj_src.size() == no + nb &&
+                !std::memcmp(e->proj_src.data(), op, no * sizeof(float));
+    for (size_t c = 0; same && c < nb; ++c) {
+        const float b = bias ? bias[c] : 0.0f;
+        same = !std::memcmp(&e->proj_src[no + c], &b, sizeof(float));
+    }
+    if (same) return VAD_OK;
+    e->proj_packed = false;
+    const size_t pf = vadk::proj_pack_floats((uint32_t)n_in, (uint32_t)n_out);
+    if (int rc = ensure(e, e->d_proj, e->d_proj_cap, pf * sizeof(float))) return rc;
+    e->proj_src.assign(op, op + no);
+    e->proj_src.resize(no + nb, 0.0f);
+    if (bias) std::memcpy(e->proj_src.data() + no, bias, nb * sizeof(float));
+    e->proj_pack.assign(pf, 0.0f);
+    for (uint32_t k = 0; k < (uint32_t)n_in; ++k)
+        for (uint32_t c = 0; c < (uint32_t)n_out; ++c) e->proj_pack[vadk::proj_pack_index(k, c, K4)] = op[(size_t)k * nb + c];
+    for (uint32_t c = 0; c < (uint32_t)n_out; ++c) e->proj_pack[(size_t)K4 * N16 + c] = e->proj_src[no + c];
+    HIP_TRY(e, hipMemcpyAsync(e->d_proj, e->proj_pack.data(), pf * sizeof(float), hipMemcpyHostToDevice, s));
+    e->proj_n_in = n_in;
+    e->proj_n_out = n_out;
+    e->proj_packed = true;
+    return VAD_OK;
+}
+
+// vad_mel_project / _device with e->mu held.  out == nullptr: the projection goes to e->d_melk_alt, which then becomes the resident
+// matrix; a host call's out is staged in e->d_melb_out
+int mel_project_run(vad_engine *e, bool dev, const char *who, const float *features, int64_t rows, int32_t n_in, const float *op, const float *bias,
+                    int32_t n_out, float *out, void *stream) {
+    hipStream_t s;
+    if (int rc = call_begin(e, dev, stream, &s)) return rc;
+    if (!features) {
+        if (e->melk_start.empty())
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: NULL names the resident matrix, and the engine holds none: no "
+                           "vad_scan_mel_keep has kept one", who);
+        rows = e->melk_start.back();
+        n_in = e->melk_n_mels;
+    } else if (rows < 0) {
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: rows = %lld is negative", who, (long long)rows);
+    }
+    if (n_in < 1 || n_in > vadk::PROJ_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n_in = %d must be 1 .. 128", who, n_in);
+    if (n_out < 1 || n_out > vadk::PROJ_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n_out = %d must be 1 .. 128", who, n_out);
+    if (!op) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null op", who);
+    for (int32_t k = 0; k < n_in; ++k)
+        for (int32_t c = 0; c < n_out; ++c)
+            if (const float v = op[(size_t)k * (size_t)n_out + (size_t)c]; !std::isfinite(v))
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: op[%d][%d] is %s, an operator entry is a finite number", who, k, c,
+                               std::isnan(v) ? "NaN" : "infinite");
+    for (int32_t c = 0; bias && c < n_out; ++c)
+        if (!std::isfinite(bias[c]))
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: bias[%d] is %s, a bias is a finite number", who, c,
+                           std::isnan(bias[c]) ? "NaN" : "infinite");
+    if (!out && features)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out = NULL replaces the resident matrix, which features = NULL names: a "
+                       "matrix of the caller's takes an out", who);
+    if (dev && ((reinterpret_cast<uintptr_t>(features) & 3) || (reinterpret_cast<uintptr_t>(out) & 3)))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the features and the output must be 4-byte aligned", who);
+    const size_t ib = (size_t)rows * (size_t)n_in * sizeof(float), ob = (size_t)rows * (size_t)n_out * sizeof(float);
+    if (dev && out && rows) {
+        const uintptr_t x0 = reinterpret_cast<uintptr_t>(features ? features : e->d_melk), y0 = reinterpret_cast<uintptr_t>(out);
+        if (x0 < y0 + ob && y0 < x0 + ib)
+            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output's %llu bytes overlap the %llu bytes of the features", who,
+                           (unsigned long long)ob, (unsigned long long)ib);
+    }
+    if (((uint64_t)rows + vadk::PROJ_ROWS - 1) / vadk::PROJ_ROWS > (uint64_t)INT32_MAX)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %d rows in one call", who, vadk::PROJ_ROWS);
+    if (rows == 0) {
+        if (!out) e->melk_n_mels = n_out;
+        return VAD_OK;
+    }
+    vadk::ProjArgs a{};
+    if (!out) {
+        if (int rc = ensure(e, e->d_melk_alt, e->d_melk_alt_cap, ob)) return rc;
+        a.out = e->d_melk_alt;
+    } else if (dev) {
+        a.out = out;
+    } else {
+        if (int rc = ensure(e, e->d_melb_out, e->d_melb_out_cap, ob)) return rc;
+        a.out = reinterpret_cast<float *>(e->d_melb_out);
+    }
+    if (int rc = project_operator(e, n_in, n_out, op, bias, s)) return rc;
+    MelbSrc src{features ? (dev ? features : nullptr) : e->d_melk, rows, n_in, nullptr, 0};
+    if (int rc = melb_upload(e, dev, features, &src, s)) return rc;
+    a.x = src.x;
+    a.op = e->d_proj;
+    a.rows = (uint64_t)rows;
+    a.n_in = (uint32_t)n_in;
+    a.n_out = (uint32_t)n_out;
+    const hipError_t r = vadk_launch_mel_project(&a, s);
+    const int launched = r != hipSuccess ? e->hip_fail(r, "kernel launch (mel project)") : VAD_OK;
+    if (!launched && !out) {
+        // the projection is the resident matrix from here on: the calls behind this one wait for the launch (call_begin)
+        std::swap(e->d_melk, e->d_melk_alt);
+        std::swap(e->d_melk_cap, e->d_melk_alt_cap);
+        e->melk_n_mels = n_out;
+    }
+    const int rc = call_end(e, dev, s, launched);
+    if (rc || dev) return rc;
+    if (out) HIP_TRY(e, hipMemcpyAsync(out, a.out, ob, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    return VAD_OK;
+}
+
 // vad_batch's fields, ahead of everything else
 int batch_check(vad_engine *e, const char *who, const vad_batch *b) {
     if (!b) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null vad_batch", who);
@@ -3348,6 +3464,20 @@ int vad_mel_batch_packed_device(vad_engine *e, const float *d_features, int64_t 
     std::lock_guard<std::mutex> lk(e->mu);
     return mel_batch_packed_run(e, true, "vad_mel_batch_packed_device", d_features, rows, start, n, b, pieces, np, nw, lo, shift, scale, nss, d_out,
                                 out_bytes, stream);
+}
+
+int vad_mel_project(vad_engine *e, const float *features, int64_t rows, int32_t n_in, const float *op, const float *bias, int32_t n_out,
+                    float *out) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return mel_project_run(e, false, "vad_mel_project", features, rows, n_in, op, bias, n_out, out, nullptr);
+}
+
+int vad_mel_project_device(vad_engine *e, const float *d_features, int64_t rows, int32_t n_in, const float *op, const float *bias, int32_t n_out,
+                           float *d_out, void *stream) {
+    if (!e) return VAD_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return mel_project_run(e, true, "vad_mel_project_device", d_features, rows, n_in, op, bias, n_out, d_out, stream);
 }
 
 // the packing rule of include/vad_engine.h: host code only, no engine.  Twice over the segments: the counts, then the pieces

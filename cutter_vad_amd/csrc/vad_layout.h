@@ -828,4 +828,31 @@ __host__ __device__ inline uint16_t melb_bf16(uint32_t bits) {
     return (uint16_t)((bits + 0x7fffu + ((bits >> 16) & 1u)) >> 16);
 }
 
+// a projection of a feature matrix, y [rows][n_out] = bias + x [rows][n_in] * op [n_in][n_out] (csrc/mel_project.hip:
+// vadk_mel_project; vad_mel_project).  A workgroup of PROJ_THREADS threads serves PROJ_ROWS consecutive rows (workgroup b: rows
+// PROJ_ROWS b ..), each wave a tile of 16 of them over all column tiles, on v_mfma_f32_16x16x4_f32.  The host packs the operator
+// into the B fragments' order, zero-padded to K4 = up4(n_in) rows and N16 = up16(n_out) columns - entry (k, c) at proj_pack_index:
+// the 64 floats of (column tile c / 16, k-step k / 4) lie together, lane (k % 4) * 16 + c % 16 - followed by the bias, N16 floats,
+// zero-padded.  At most 128 * 128 + 128 floats: it stays in L2.
+constexpr int PROJ_THREADS = 256;
+constexpr int PROJ_ROWS = 64;
+constexpr int PROJ_MAX = 128;                 // n_in and n_out at the most
+constexpr int PROJ_LOADS = 8;                 // loads a thread has in flight: of the matrix into LDS, and of the k-steps' fragments
+__host__ __device__ inline uint32_t proj_up4(uint32_t n) { return (n + 3u) & ~3u; }
+__host__ __device__ inline uint32_t proj_up16(uint32_t n) { return (n + 15u) & ~15u; }
+__host__ __device__ inline uint32_t proj_pack_index(uint32_t k, uint32_t c, uint32_t K4) {
+    return ((c >> 4) * (K4 >> 2) + (k >> 2)) * 64u + (k & 3u) * 16u + (c & 15u);
+}
+__host__ __device__ inline uint32_t proj_pack_floats(uint32_t n_in, uint32_t n_out) { return (proj_up4(n_in) + 1u) * proj_up16(n_out); }
+// the x tile in LDS: PROJ_ROWS rows of K4 floats at an odd pitch
+__host__ __device__ inline uint32_t proj_pitch(uint32_t n_in) { return proj_up4(n_in) | 1u; }
+struct ProjArgs {
+    const float *x;           // [rows][n_in], 4-byte aligned
+    float *out;               // [rows][n_out], 4-byte aligned, apart from x
+    const float *op;          // packed operator, then the bias: proj_pack_floats(n_in, n_out) floats
+    uint64_t rows;
+    uint32_t n_in, n_out;     // 1 .. PROJ_MAX
+};
+static_assert(sizeof(ProjArgs) == 40, "ProjArgs layout");
+
 }  // namespace vadk

@@ -1288,6 +1288,61 @@ class Engine:
         return out
 
     @staticmethod
+    def _project_operator(op, bias):
+        """-> (op float32 [n_in, n_out], bias float32 [n_out] or None, their pointers)"""
+        f32p = C.POINTER(C.c_float)
+        w = np.ascontiguousarray(np.asarray(op, np.float32))
+        if w.ndim != 2 or w.shape[0] < 1 or w.shape[1] < 1:
+            raise AudioProcessingError(f"Model prediction failed: mel_project: op is [n_in, n_out], got {w.shape}")
+        b = None if bias is None else np.ascontiguousarray(np.asarray(bias, np.float32).reshape(-1))
+        if b is not None and b.size != w.shape[1]:
+            raise AudioProcessingError(f"Model prediction failed: mel_project: bias has n_out = {w.shape[1]} entries, got {b.size}")
+        return w, b, w.ctypes.data_as(f32p), None if b is None else b.ctypes.data_as(f32p)
+
+    def mel_project(self, op, bias=None, features=None, out: bool = True):
+        """A linear stage over a feature matrix on the GPU (``vad_mel_project``): ``y = bias + x @ op`` in float32, a fused
+        multiply-add chain along ``k`` from the bias, with ``op`` [n_in, n_out] and ``bias`` [n_out] (``None``: 0), both 1 .. 128
+        wide - the DCT of MFCC / LFCC (``cutter_vad_amd.scan.CepstralSpec.operator``), PCA / LDA, whitening, band selection.
+        ``features`` [rows, n_in] float32, or ``None`` for the resident matrix of ``mel_keep``.  -> float32 [rows, n_out].
+        ``out=False`` (with ``features=None``): the projection REPLACES the resident matrix - ``mel_stats``, ``mel_batch``,
+        ``mel_batch_packed`` and ``mel_resident_read`` then work on it, the segments' first rows stay - and nothing comes back but
+        -> (rows, n_out)."""
+        w, b, wp, bp = self._project_operator(op, bias)
+        x = None if features is None else np.ascontiguousarray(np.asarray(features, np.float32))
+        if x is not None and x.ndim != 2:
+            raise AudioProcessingError(f"Model prediction failed: features are [rows, n_in], got {x.shape}")
+        if x is not None and x.shape[1] != w.shape[0]:
+            raise AudioProcessingError(f"Model prediction failed: mel_project: the features have {x.shape[1]} columns, op has n_in = {w.shape[0]} rows")
+        with self._scan_lock:
+            if x is None:
+                rows, n_in, _ = self.mel_resident()
+                if n_in != w.shape[0]:
+                    raise AudioProcessingError(f"Model prediction failed: mel_project: the resident matrix has {n_in} columns, op has n_in = "
+                                               f"{w.shape[0]} rows")
+            else:
+                rows, n_in = x.shape
+            y = np.empty((rows, w.shape[1]), np.float32) if out else None
+            self._check(self._lib.vad_mel_project(self._h, None if x is None else x.ctypes.data_as(C.POINTER(C.c_float)), rows, n_in, wp, bp,
+                                                  w.shape[1], None if y is None else y.ctypes.data_as(C.POINTER(C.c_float))))
+        return y if out else (rows, w.shape[1])
+
+    def mel_project_device(self, op, bias=None, d_features: int = 0, rows: int = 0, d_out: int = 0, stream: int = 0) -> Tuple[int, int]:
+        """``mel_project`` in device memory (``vad_mel_project_device``): ``d_features`` = 0: the resident matrix, else a float32 matrix
+        [rows, n_in = op.shape[0]] on the GPU (an integer; 4-byte aligned); ``d_out`` a float32 [rows, n_out] there that does not
+        overlap it, or 0: the projection replaces the resident matrix.  ``op`` and ``bias`` are host arrays, read before the call
+        returns.  Asynchronous on ``stream``.  -> (rows, n_out)."""
+        w, b, wp, bp = self._project_operator(op, bias)
+        with self._scan_lock:
+            if not d_features:
+                rows, n_in, _ = self.mel_resident()
+                if n_in != w.shape[0]:
+                    raise AudioProcessingError(f"Model prediction failed: mel_project_device: the resident matrix has {n_in} columns, op has n_in = "
+                                               f"{w.shape[0]} rows")
+            self._check(self._lib.vad_mel_project_device(self._h, d_features or None, int(rows), w.shape[0], wp, bp, w.shape[1], d_out or None,
+                                                         stream or None))
+        return int(rows), w.shape[1]
+
+    @staticmethod
     def _batch_source(features, start):
         """-> (features or None, its pointer, rows, n_mels or 0, start or None, its pointer, n) for the calls that take a matrix"""
         x = None if features is None else np.ascontiguousarray(np.asarray(features, np.float32))

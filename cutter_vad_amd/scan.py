@@ -902,7 +902,7 @@ def _need_mel(engine, who: str) -> None:
 
 def features_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, config: Optional[VADConfig] = None, engine=None,
                         hop: Optional[int] = None, law: Optional[str] = None, channel="mix", open_end: bool = False,
-                        refine: Optional[SegmentRefine] = None, sample_rate: Optional[int] = None, taps=None, convert=None) -> List:
+                        refine: Optional[SegmentRefine] = None, sample_rate: Optional[int] = None, taps=None, convert=None, project=None) -> List:
     """``scan_recordings`` with each finished segment's log-mel frames: per recording ``[(start_sample, end_sample,
     features [M, n_mels] float32), ...]`` (per channel for ``"split"``, as there).  The features are those of the samples
     ``cut_recordings(layout="range")`` cuts - decoded, mixed and gated as the model read them - computed on the GPU from the block
@@ -916,7 +916,10 @@ def features_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, config:
     ``Engine.resample_cut``.  An engine object without ``resample_cut``: ``ConfigurationError``.
     ``convert`` as in ``scan_recordings``: recordings at any rate ``Engine.convert`` accepts, converted once; the ranges count converted
     samples and the features are those of the converted signal, gated as the model read it (``Engine.mel(audio=None)``; ``taps`` is
-    not used)."""
+    not used).
+    ``project``: a ``CepstralSpec`` or an ``(op, bias)`` pair - the features are ``[M, n_out]``, each row of the log-mel matrix through
+    ``Engine.mel_project`` on the GPU (MFCC, LFCC, PCA ...): ``Engine.mel_keep``, the projection in place of the resident matrix, and
+    ``Engine.mel_resident_read`` instead of ``Engine.mel``.  An engine object without ``mel_project``: ``ConfigurationError``."""
     from .pool import default_pool, resolve_model_path
     who = "features_recordings"
     split = isinstance(channel, str) and channel == "split"
@@ -953,6 +956,7 @@ def features_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, config:
     if not recordings:
         return []
     arrays = spec.operators()
+    proj = _project_arg(who, engine, project, int(arrays[0]["n_mels"]))
     denoise = 0.01 if cfg.enable_denoising else None
     out: List = [None] * len(recordings)
     for two in (False, True):
@@ -968,8 +972,12 @@ def features_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, config:
                 ranges = _scan_ranges(engine, slots, [recordings[i] for i in idx], per, frame, hop, law, denoise, channel, rate=rate,
                                       open_end=open_end, refine=refine, convert=conv)
                 table = _cut_table(engine, ranges, chans, frame, hop)
-                if table:
+                if table and proj is None:
                     data, start = engine.mel(table, arrays, hop=hop, denoise=denoise, **mel_kw)
+                elif table:
+                    start = engine.mel_keep(table, arrays, hop=hop, denoise=denoise, **mel_kw)
+                    engine.mel_project(proj[0], proj[1], out=False)
+                    data = engine.mel_resident_read()
         finally:
             for s in slots:
                 engine.close_stream(int(s))
@@ -1123,6 +1131,73 @@ def batch_affine(stats: Optional[dict], start, norm: str = "none", eps: float = 
     return None, shift, scale
 
 
+def _dct64(n_in: int, n_out: int, norm, first: int) -> np.ndarray:
+    n_in, n_out, first = int(n_in), int(n_out), int(first)
+    if norm not in ("ortho", None) or n_in < 1 or n_out < 1 or first < 0 or first + n_out > n_in:
+        raise ConfigurationError("norm", repr((n_in, n_out, norm, first)), "dct_operator: norm is 'ortho' or None, n_in and n_out are 1 or more, and "
+                                 f"coefficients first .. first + n_out - 1 lie below n_in, got n_in={n_in}, n_out={n_out}, norm={norm!r}, first={first}")
+    m = np.arange(n_in, dtype=np.int64)[:, None]
+    c = np.arange(first, first + n_out, dtype=np.int64)[None, :]
+    w = np.cos(np.pi * ((c * (2 * m + 1)) % (4 * n_in)).astype(np.float64) / (2.0 * n_in))
+    if norm == "ortho":
+        return w * np.where(c == 0, np.sqrt(1.0 / n_in), np.sqrt(2.0 / n_in))
+    return 2.0 * w
+
+
+def dct_operator(n_in: int, n_out: int, norm="ortho", first: int = 0) -> np.ndarray:
+    """The DCT-II as an operator ``Engine.mel_project`` takes -> float32 [n_in, n_out]: column ``j`` is coefficient ``c = first + j``,
+    ``op[m][j] = s_c cos(pi c (2 m + 1) / (2 n_in))`` - the angle reduced in integers mod ``4 n_in``, everything in float64, rounded
+    once.  ``norm="ortho"``: ``s_0 = sqrt(1 / n_in)``, ``s_c = sqrt(2 / n_in)`` (Kaldi, ``scipy.fft.dct(norm="ortho")``, librosa,
+    torchaudio); ``None``: ``s_c = 2`` (``scipy.fft.dct``'s default).  ``first=1`` drops c0."""
+    return _dct64(n_in, n_out, norm, first).astype(np.float32)
+
+
+@dataclass(frozen=True)
+class CepstralSpec:
+    """Cepstral coefficients of log-band features, for ``Engine.mel_project`` and ``features_recordings`` / ``batch_recordings(project=)``:
+    coefficients ``first .. first + n_ceps - 1`` of the DCT-II (``dct_operator``'s ``norm``), each times the sine lifter
+    ``1 + (lifter / 2) sin(pi (c + lifter_offset) / lifter)`` (``lifter=0``: none; ``lifter=22``: HTK and Kaldi; ``lifter_offset=1``:
+    librosa's) and times ``scale`` (10 turns ``MelSpec(log="log10")`` into dB).  Over ``MelSpec``'s mel bands that is MFCC, over
+    linear bands LFCC."""
+    n_ceps: int = 13
+    lifter: float = 0
+    lifter_offset: int = 0
+    scale: float = 1.0
+    norm: Optional[str] = "ortho"
+    first: int = 0
+
+    def operator(self, n_mels: int):
+        """-> ``(op float32 [n_mels, n_ceps], bias float32 [n_ceps] of zeros)``: lifter and scale folded into the DCT in float64,
+        rounded once"""
+        w = _dct64(n_mels, self.n_ceps, self.norm, self.first)
+        if not np.isfinite(float(self.scale)) or float(self.lifter) < 0:
+            raise ConfigurationError("lifter", repr((self.lifter, self.scale)), f"CepstralSpec: lifter is 0 or more and scale finite, got "
+                                     f"{self.lifter!r}, {self.scale!r}")
+        lift = np.ones(int(self.n_ceps))
+        if float(self.lifter) > 0:
+            c = np.arange(int(self.first), int(self.first) + int(self.n_ceps), dtype=np.float64) + int(self.lifter_offset)
+            lift = 1.0 + 0.5 * float(self.lifter) * np.sin(np.pi * c / float(self.lifter))
+        return (w * (lift * float(self.scale))[None, :]).astype(np.float32), np.zeros(int(self.n_ceps), np.float32)
+
+
+def _need_project(engine, who: str) -> None:
+    if not hasattr(engine, "mel_project") or not hasattr(engine, "mel_keep"):
+        raise ConfigurationError("project", "given", f"{who}: project= needs an engine with mel_keep and mel_project (the features are projected "
+                                 f"where the scan left them, on the GPU), {type(engine).__name__} has none")
+
+
+def _project_arg(who: str, engine, project, n_mels: int):
+    """``project``: None, a ``CepstralSpec`` or an ``(op, bias)`` pair -> None or (op float32 [n_mels, n_out], bias or None)"""
+    if project is None:
+        return None
+    _need_project(engine, who)
+    op, bias = project.operator(n_mels) if hasattr(project, "operator") else project
+    op = np.ascontiguousarray(np.asarray(op, np.float32))
+    if op.ndim != 2 or op.shape[0] != n_mels or not 1 <= op.shape[1] <= 128:
+        raise ConfigurationError("project", repr(op.shape), f"{who}: project's operator is [n_mels = {n_mels}, 1 .. 128], got {op.shape}")
+    return op, bias
+
+
 def _need_batch(engine, who: str) -> None:
     if not hasattr(engine, "mel_batch"):
         raise ConfigurationError("batch", "given", f"{who} needs an engine with mel_batch (the windows are normalised and laid out from the "
@@ -1142,7 +1217,7 @@ def _expand_affine(affine, which):
 
 def batch_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, batch: FeatureBatch, config: Optional[VADConfig] = None, engine=None,
                      hop: Optional[int] = None, law: Optional[str] = None, channel="mix", open_end: bool = False,
-                     refine: Optional[SegmentRefine] = None, sample_rate: Optional[int] = None, taps=None, convert=None):
+                     refine: Optional[SegmentRefine] = None, sample_rate: Optional[int] = None, taps=None, convert=None, project=None):
     """``features_recordings`` as the tensor a model takes: the log-mel features of every finished segment of every recording,
     windowed, normalised, padded, laid out and converted as ``batch`` says -> ``(array, index)``: ``array`` [B, C, T] or [B, T, C]
     (``Engine.mel_batch``), ``index`` one ``(recording, channel, start_sample, end_sample, first_frame, nframes)`` per window - the
@@ -1155,7 +1230,10 @@ def batch_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, batch: Fea
     ``batch.pack``: the segments of each (recording, channel) packed into windows (``batch_pack``): one scan, one keep, one grouped
     ``Engine.mel_stats`` and one ``Engine.mel_batch_packed``.  ``array`` has a window per row of B, ``index`` one ``(recording,
     channel, start_sample, end_sample, first_frame, nframes, window, offset)`` per PIECE.  ``batch.scope="recording"``, packed or
-    not, normalises with the statistics of all segments of the (recording, channel)."""
+    not, normalises with the statistics of all segments of the (recording, channel).
+
+    ``project`` as in ``features_recordings``: one ``Engine.mel_project`` behind the keep replaces the resident matrix by its
+    projection, and the statistics, the windows and C = n_out * (deltas + 1) are those of the projected features."""
     from .pool import default_pool, resolve_model_path
     who = "batch_recordings"
     batch.check()
@@ -1200,6 +1278,9 @@ def batch_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, batch: Fea
                                  "for the two-channel recordings")
     arrays = spec.operators()
     n_mels = int(arrays[0]["n_mels"])
+    proj = _project_arg(who, engine, project, n_mels)
+    if proj is not None:
+        n_mels = int(proj[0].shape[1])               # downstream the features are the projected ones
     chans_out = n_mels * (int(batch.deltas) + 1)
     np_dtype = {"f32": np.float32, "f16": np.float16}.get(batch.dtype, np.uint16)
     T0 = int(batch.frames) if batch.frames is not None else 4
@@ -1220,6 +1301,8 @@ def batch_recordings(recordings: Sequence[np.ndarray], spec: MelSpec, batch: Fea
             table = _cut_table(engine, ranges, chans, frame, hop)
             if table:
                 start = engine.mel_keep(table, arrays, hop=hop, denoise=denoise, **mel_kw)
+                if proj is not None:
+                    engine.mel_project(proj[0], proj[1], out=False)
                 moments = batch.norm != "whisper"
                 # the group of a segment: its (recording, channel), numbered in the table's order
                 group = np.array([i * per + c for i, rc in enumerate(ranges) for c, rg in enumerate(rc) for _ in rg], np.int32)

@@ -1129,6 +1129,46 @@ VAD_API int vad_mel_stats_grouped_device(vad_engine *e, const float *d_features 
                                          int64_t ngroups, float *d_max_out, int64_t *d_sum_out, uint64_t *d_sumsq_out, void *stream);
 
 /*
+ * Cepstral features and other linear front ends: MFCC and LFCC (a DCT of the log-mel or log-linear bands, a lifter, a scale), PCA /
+ * LDA, global-CMVN whitening, band selection - one small matrix product per row of a feature matrix, done where the rows are.
+ *
+ * vad_mel_project / _device: out[rows][n_out] from features[rows][n_in] - a host array (_device: on the GPU), or NULL for the
+ * resident matrix of vad_scan_mel_keep, whose rows and n_mels then stand for rows and n_in, which are not read - with the operator
+ * op[n_in][n_out] and bias[n_out] (HOST arrays in both forms, finite; bias = NULL is 0), n_in and n_out in 1 .. 128.
+ * THE RULE, in float32:
+ *     y[r][c] = bias[c] + sum over k of x[r][k] * op[k][c]
+ *   as a chain of fused multiply-adds that starts at bias[c] and takes k ascending: acc = fmaf(x[r][k], op[k][c], acc), one rounding
+ *   per term (v_mfma_f32_16x16x4_f32 is this chain, bit for bit).  So with D[r][c] = |bias[c]| + sum over k of |x[r][k]| |op[k][c]| and
+ *   u = 2^-24:
+ *     |y - exact| <= (n_in + 2) u D[r][c]
+ *   - the standard bound of an n_in-term fused-multiply-add sum in any order with the bias (derived, not measured; it holds while no
+ *   term or partial sum is subnormal).  Where float32 is exact - integer x, op and bias with every partial sum below 2^24 - y is the
+ *   exact integer (the sign of a zero result is unspecified: where n_in is no multiple of 4 the chain ends in fmaf(+0, +0, acc) for the
+ *   padded k, and -0.0 becomes +0.0).  A row's value depends on that row, op and bias alone: not on the row's position in the matrix, on rows, or on
+ *   the launch.  Nothing is accumulated across workgroups, there are no atomics: two runs give the same bytes.  A row that holds a NaN
+ *   or an infinity gives unspecified values in that row only.
+ * out == NULL REPLACES the resident matrix by its projection, and requires features == NULL: the matrix becomes [rows][n_out],
+ * vad_mel_resident reports n_mels = n_out, the segments' first rows stay, and vad_mel_stats, vad_mel_stats_grouped, vad_mel_batch,
+ * vad_mel_batch_packed and vad_mel_resident_read work on it as on any resident matrix (the engine projects into a second buffer of
+ * its own and swaps the two).  With an `out` the resident matrix is left alone.  The resident audio block and the resident segment
+ * table are left as vad_mel_stats leaves them.
+ *   Refusals, each VAD_ERR_INVALID_ARG with a message under the function's name, nothing written and the resident matrix as it was,
+ * in this order: features == NULL with no resident matrix; rows < 0; n_in outside 1 .. 128; n_out outside 1 .. 128; a null op; a
+ * non-finite op entry, by index, then a non-finite bias entry, by index; out == NULL with a features; (_device) d_features or d_out
+ * not 4-byte aligned; (_device) a d_out range that overlaps the input's; more than 2^31 - 1 workgroups (of 64 rows).  rows == 0 is
+ * VAD_OK.
+ *   The _device form enqueues on `stream` (NULL = the engine's own) and returns; op and bias are read before the call returns; the
+ * calls that read the resident matrix wait for it.  Every engine is served - V4, 8 kHz, VAD_ENGINE_SHARED_GPU: no model kernel runs.
+ *   VAD_ABI_VERSION is unchanged: the presence of vad_mel_project is how a caller detects the feature.
+ */
+VAD_API int vad_mel_project(vad_engine *e, const float *features /*[rows][n_in] or NULL*/, int64_t rows, int32_t n_in,
+                            const float *op /*host [n_in][n_out]*/, const float *bias /*host [n_out] or NULL = 0*/, int32_t n_out,
+                            float *out /*[rows][n_out] or NULL: replace the resident matrix*/);
+VAD_API int vad_mel_project_device(vad_engine *e, const float *d_features /*on the GPU or NULL*/, int64_t rows, int32_t n_in,
+                                   const float *op /*host [n_in][n_out]*/, const float *bias /*host [n_out] or NULL*/, int32_t n_out,
+                                   float *d_out /*on the GPU or NULL*/, void *stream);
+
+/*
  * Audio batches: what a model that takes the waveform itself is fed - wav2vec 2.0, HuBERT, WavLM, speaker embedders: [B][T] windows
  * of samples in the model's number format, mean-removed, z-scored or peak-normalised per utterance, zero-padded, with an attention
  * mask - made from the block a scan left on the GPU, without the samples crossing the link as float32 and coming back.

@@ -1676,6 +1676,142 @@ def scan_mel_batch():
     return row
 
 
+def mel_project():
+    """What a projection of the resident matrix costs, on scan_mel's corpus and geometry, the 80 -> 13 ortho DCT.
+    (a) vad_mel_project_device in the replace form on the matrix a keep left (a fresh keep before each pass, outside the events)
+    against a device-to-device copy of the same rows x 80 floats in the same run, HIP-event timed as scan_mel_batch's (c).  (b) keep +
+    project + stats + batch (cmvn, float16, windows of 1 000 frames, back on the host) against the parent's only route to the same
+    tensor: keep + mel_resident_read + numpy float32 @ on 16 threads + mel_stats(features=host) + mel_batch(features=host); the two
+    projected matrices are compared with float64 on the first rows.  One warm-up and three timed passes, medians.  The result goes
+    to profiles/mel_project.json."""
+    import ctypes as C
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    from cutter_vad_amd import FeatureBatch, MelSpec, batch_affine, batch_windows, dct_operator
+    N = int(os.environ.get("VAD_SCAN_BENCH_N", "1024"))
+    eng = Engine(blob(5), max_streams=max(N, 16))
+    hop, T, n_in, n_out = 256, 1000, 80, 13
+    pcm = np.tile(np.load(os.path.join(root, "tests", "golden", "speech16k_i16.npz"))["pcm"].astype(np.int16), 3)
+    rng = np.random.default_rng(N)
+    ns = 30 * 16000
+    recs = [pcm[a:a + ns] for a in rng.integers(0, pcm.size - ns + 1, N)]
+    slots = eng.open_streams(N)
+    eng.set_thresholds_many(slots, (0.4, 0.3, 0.8, 0.95, 6, 12))
+    med = lambda v: float(np.median(v))
+    arrays = MelSpec(16000).operators()
+    op = dct_operator(n_in, n_out)
+    rec = FeatureBatch(frames=T, norm="cmvn", dtype="f16").record(n_out)
+    row = {"config": f"mel_project: {N} int16 recordings of 30 s at 16 kHz in one call, hop {hop}, Whisper's geometry, 80 -> 13 ortho DCT, cmvn, "
+                     f"float16 windows of {T} frames", "recordings": N, "passes": 3, "host_threads": 16}
+    pool = ThreadPoolExecutor(16)
+
+    def numpy_project(x):
+        parts = np.array_split(np.arange(x.shape[0]), 16)
+        return np.concatenate(list(pool.map(lambda p: x[p[0]:p[-1] + 1] @ op if p.size else np.empty((0, n_out), np.float32), parts)))
+
+    with eng.scan_session():
+        table = eng.scan_segments(slots, recs, hop=hop, denoise=0.01)
+        offs = [int(o) for o in eng.last_scan["offsets"]]
+        segs = [(offs[i], a, n) for i, a, n in zip(table["item"].tolist(), table["first_frame"].tolist(), table["nframes"].tolist())]
+        start = eng.mel_keep(segs, arrays, hop=hop, denoise=0.01)
+        rows = int(start[-1])
+        windows, _ = batch_windows(start, T)
+        row.update(segments=len(segs), rows=rows, windows=int(windows.size), matrix_bytes=rows * n_in * 4, projected_bytes=rows * n_out * 4)
+
+        def route_a():
+            eng.mel_keep(segs, arrays, hop=hop, denoise=0.01)
+            eng.mel_project(op, out=False)
+            lo, sh, sc = batch_affine(eng.mel_stats(), start, "cmvn")
+            return eng.mel_batch(windows, rec, lo=lo, shift=sh, scale=sc)
+
+        def route_b():
+            t0 = time.perf_counter()
+            eng.mel_keep(segs, arrays, hop=hop, denoise=0.01)
+            x = eng.mel_resident_read()
+            t1 = time.perf_counter()
+            y = numpy_project(x)
+            t2 = time.perf_counter()
+            lo, sh, sc = batch_affine(eng.mel_stats(y, start), start, "cmvn")
+            return eng.mel_batch(windows, rec, lo=lo, shift=sh, scale=sc, features=y, start=start), x, y, t1 - t0, t2 - t1
+
+        got_a = route_a()
+        ya = eng.mel_resident_read()
+        got_b, x, yb, _, _ = route_b()
+        # the two projections against float64 on the first rows, in units of u D (the header's bound: n_in + 2 = 82 for the kernel's
+        # fused chain, 2 n_in + 2 = 162 for a chain of separate multiplies and adds)
+        k = min(rows, 100000)
+        x64, o64 = x[:k].astype(np.float64), op.astype(np.float64)
+        uD = 2.0 ** -24 * np.maximum(np.abs(x64) @ np.abs(o64), 1e-300)
+        row.update(worst_uD_kernel=float((np.abs(ya[:k] - x64 @ o64) / uD).max()), worst_uD_numpy=float((np.abs(yb[:k] - x64 @ o64) / uD).max()),
+                   compared_rows=k, batch_cells_differ=int((got_a.view(np.uint16) != got_b.view(np.uint16)).sum()), batch_cells=int(got_a.size),
+                   batch_max_abs_diff=float(np.abs(got_a.astype(np.float32) - got_b.astype(np.float32)).max(initial=0.0)))
+        a_runs, b_runs, b_read, b_np = [], [], [], []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            route_a()
+            a_runs.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            _, _, _, c, s_ = route_b()
+            b_runs.append(time.perf_counter() - t0)
+            b_read.append(c)
+            b_np.append(s_)
+        row.update(b_s_project_route_runs=a_runs, b_s_project_route=med(a_runs), b_s_host_route_runs=b_runs, b_s_host_route=med(b_runs),
+                   b_s_host_keep_read=med(b_read), b_s_host_numpy=med(b_np), b_ratio_host_over_project=med(b_runs) / med(a_runs))
+        # (a) the kernel alone against a device-to-device copy of the matrix
+        ts = torch.cuda.Stream()
+        busy = torch.randn(6144, 6144, device="cuda")
+        lib, h = eng._lib, eng.handle
+        d_src = torch.empty(rows * n_in, dtype=torch.float32, device="cuda")
+        d_dst = torch.empty(rows * n_in, dtype=torch.float32, device="cuda")
+        fp = op.ctypes.data_as(C.POINTER(C.c_float))
+
+        def event_timed(fn, before=None):
+            out = []
+            for k in range(5):
+                if before:
+                    before()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                with torch.cuda.stream(ts):
+                    torch.mm(busy, busy)
+                e0.record(ts)
+                assert fn() in (0, None)
+                e1.record(ts)
+                torch.cuda.synchronize()
+                if k >= 2:                           # two warm-ups
+                    out.append(e0.elapsed_time(e1) * 1e-3)
+            return out
+
+        def copy():
+            with torch.cuda.stream(ts):
+                d_dst.copy_(d_src)
+
+        moved = rows * (n_in + n_out) * 4
+        runs = event_timed(lambda: lib.vad_mel_project_device(h, None, 0, 0, fp, None, n_out, None, ts.cuda_stream),
+                           before=lambda: (eng.mel_keep(segs, arrays, hop=hop, denoise=0.01), eng.synchronize()))
+        row.update(a_s_project_device_runs=runs, a_s_project_device=med(runs), a_project_bytes=moved, a_project_GBps=moved / med(runs) / 1e9)
+        runs = event_timed(copy)
+        row.update(a_s_copy_d2d_runs=runs, a_s_copy_d2d=med(runs), a_copy_bytes=rows * n_in * 8, a_copy_GBps=rows * n_in * 8 / med(runs) / 1e9,
+                   a_ratio_project_over_copy=row["a_s_project_device"] / med(runs))
+    eng.close()
+    with open(os.path.join(root, "profiles", "mel_project.json"), "w") as f_:
+        json.dump({"what": "Cepstral features: a projection of the resident feature matrix (vad_mel_project, csrc/mel_project.hip): DESIGN 2.1y",
+                   "how": "python tools/bench_configs.py mel_project on one MI355X, one process.  (a) the replace form on the resident matrix "
+                          "and a device-to-device copy of rows x 80 floats: HIP events behind a matrix product that keeps the stream busy "
+                          "while the host checks and packs, a fresh keep before each pass outside the events, two warm-ups and three timed "
+                          "passes; the bytes are computed from the shapes (the copy reads and writes the matrix once), not counted.  (b) the "
+                          "two routes alternate, wall clock around the Python calls with the batch back on the host, one warm-up and three "
+                          "timed passes, medians; the host route uses only code the parent has.  Not measured: other operator shapes "
+                          "(128 -> 128 is MFMA-bound by the arithmetic of DESIGN 2.1y), the with-an-out forms, L2 hit rates, the spread "
+                          "between processes and boxes",
+                   "runs": [row]}, f_, indent=1)
+        f_.write("\n")
+    return row
+
+
 def scan_mel_pack():
     """What packing several segments into a window saves, on scan_mel_batch's corpus and setting with Whisper's own
     window: float16, T = 3 000.  The windows and bytes of the unpacked batch (batch_windows: a window per segment) and of the packed

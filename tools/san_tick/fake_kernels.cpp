@@ -423,6 +423,22 @@ extern "C" hipError_t vadk_launch_mel_stats(const MelStatsArgs *a, hipStream_t) 
     return hipSuccess;
 }
 
+// a projection of a feature matrix (csrc/mel_project.hip: vadk_mel_project): include/vad_engine.h's rule - a chain of fused
+// multiply-adds from the bias, k ascending - over the host's packed operator (vad_layout.h: proj_pack_index)
+extern "C" hipError_t vadk_launch_mel_project(const ProjArgs *a, hipStream_t) {
+    if (a->rows == 0) return hipSuccess;
+    if (a->n_in < 1 || a->n_in > (uint32_t)PROJ_MAX || a->n_out < 1 || a->n_out > (uint32_t)PROJ_MAX) return hipErrorInvalidValue;
+    const uint32_t K4 = proj_up4(a->n_in), N16 = proj_up16(a->n_out);
+    const float *bias = a->op + (size_t)K4 * N16;
+    for (uint64_t r = 0; r < a->rows; ++r)
+        for (uint32_t c = 0; c < a->n_out; ++c) {
+            float acc = bias[c];
+            for (uint32_t k = 0; k < K4; ++k) acc = std::fmaf(k < a->n_in ? a->x[(size_t)r * a->n_in + k] : 0.0f, a->op[proj_pack_index(k, c, K4)], acc);
+            a->out[(size_t)r * a->n_out + c] = acc;
+        }
+    return hipSuccess;
+}
+
 // float32 -> float16 bits, round to nearest even, overflow to inf
 static uint16_t f16_bits(float f) {
     uint32_t x;

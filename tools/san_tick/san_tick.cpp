@@ -415,8 +415,21 @@ int main(int argc, char **argv) {
         OK(vad_scan_audio_batch(eng, two, 2, nullptr, NS, 1, VAD_FMT_F32, 0, 256, -1.0f, &ab, wins, 3, shift, scale, 2, out.data(), 24 * 4, mask));
         CHECK(out[0] == 2.0f && out[4] == 2.0f && out[5] == 1.0f && out[8] == 0.25f && out[15] == 0.25f && out[16] == 1.0f && out[24] == -7.0f);
         CHECK(mask[4] == 1 && mask[5] == 0 && mask[15] == 1 && mask[16] == 0 && mask[23] == 0 && mask[24] == 9);
+        // a projection of a matrix of the caller's, 2 x 3 -> 2 with a bias, exact; then of a kept matrix in the replace form: bands 0 and 2
+        const float px[6] = {1, 2, 3, 4, 5, 6}, pop[6] = {1, 0, 0, 1, 1, 1}, pb[2] = {0.5f, -1.0f}, sel[8] = {1, 0, 0, 0, 0, 1, 0, 0};
+        float py[4];
+        OK(vad_mel_project(eng, px, 2, 3, pop, pb, 2, py));
+        CHECK(py[0] == 4.5f && py[1] == 4.0f && py[2] == 10.5f && py[3] == 10.0f);
+        int64_t kept = -1;
+        int32_t kept_mels = 0;
+        OK(vad_scan_mel_keep(eng, two, 2, &m, op.data(), op.data(), fil.data(), nullptr, 0, block.data(), NS, 1, VAD_FMT_F32, 0, 256, -1.0f, &kept));
+        OK(vad_mel_project(eng, nullptr, 0, 0, sel, nullptr, 2, nullptr));
+        OK(vad_mel_resident(eng, &kept, &kept_mels, nullptr));
+        CHECK(kept == 74 && kept_mels == 2);
+        OK(vad_mel_resident_read(eng, 0, 74, out.data()));
+        CHECK(std::isfinite(out[0]) && std::isfinite(out[2 * 74 - 1]));
         vad_engine_destroy(eng);
-        std::printf("san_tick: segment-audio calls ok (cut, rate cut over 2 windows, render, mel, rate mel, moments, audio batch)\n");
+        std::printf("san_tick: segment-audio calls ok (cut, rate cut over 2 windows, render, mel, rate mel, moments, audio batch, project)\n");
     }
     // ---- the segment-table family: one host call per runner on the smallest corpus with a record and a tail - two recordings, the
     //      first ends a segment and is inside the next at its last frame - so that each work area's slots run under the sanitizers
