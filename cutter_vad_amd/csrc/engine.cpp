@@ -2323,6 +2323,36 @@ int render_run(vad_engine *e, bool dev, const CutCall &k, const void *audio, voi
     return VAD_OK;
 }
 
+// The number format of a batch's cells, which vad_batch and vad_audio_batch name alike: dtype, pad_mode, pad_value, in this order
+int batch_format_check(vad_engine *e, const char *who, int32_t dtype, int32_t pad_mode, float pad_value) {
+    if (dtype != VAD_BATCH_F32 && dtype != VAD_BATCH_F16 && dtype != VAD_BATCH_BF16)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: dtype = %d is none of VAD_BATCH_F32, VAD_BATCH_F16, VAD_BATCH_BF16", who, dtype);
+    if (pad_mode != VAD_BATCH_PAD_VALUE && pad_mode != VAD_BATCH_PAD_FEATURE)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: pad_mode = %d is neither VAD_BATCH_PAD_VALUE nor VAD_BATCH_PAD_FEATURE", who, pad_mode);
+    if (!std::isfinite(pad_value))
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: pad_value is %s, a pad value is a finite number", who,
+                       std::isnan(pad_value) ? "NaN" : "infinite");
+    return VAD_OK;
+}
+
+// The nss rule: without shift and scale nss is not read and is 1; else they have one `row` ("row", "entry") or one per `over` ("n",
+// "nw"), of which the call has `count`
+int batch_nss(vad_engine *e, const char *who, const float *shift, const float *scale, int64_t *nss, const char *row, const char *over, int64_t count) {
+    if (!shift && !scale) *nss = 1;
+    if (*nss != 1 && *nss != count)
+        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: nss = %lld: shift and scale have 1 %s or %s = %lld", who, (long long)*nss, row,
+                       over, (long long)count);
+    return VAD_OK;
+}
+
+// ... and their table as it goes up: shift, else zeros, in hs [count] and scale, else ones, in hc [count]
+void affine_fill(float *hs, float *hc, const float *shift, const float *scale, size_t count) {
+    for (size_t i = 0; i < count; ++i) {
+        hs[i] = shift ? shift[i] : 0.0f;
+        hc[i] = scale ? scale[i] : 1.0f;
+    }
+}
+
 // The AUDIO_BATCH kind with e->mu held: cut_check's refusals under this name, then the batch's own in the header's order, then the
 // block as the levels find it.  Its work follows the output: a workgroup per CUT_WG_QUADS quads of a window, listed here.  One
 // upload of the tables - segments, windows, workgroups, shift and scale, in this order in e->d_cut - and one launch, which writes
@@ -2335,20 +2365,11 @@ int audio_batch_run(vad_engine *e, bool dev, const CutCall &k, const void *audio
     if (!b) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null vad_audio_batch", who);
     if (b->samples < 4 || b->samples > (1 << 24) || (b->samples & 3))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: samples = %d must be a multiple of 4 from 4 to 2^24", who, b->samples);
-    if (b->dtype != VAD_BATCH_F32 && b->dtype != VAD_BATCH_F16 && b->dtype != VAD_BATCH_BF16)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: dtype = %d is none of VAD_BATCH_F32, VAD_BATCH_F16, VAD_BATCH_BF16", who, b->dtype);
-    if (b->pad_mode != VAD_BATCH_PAD_VALUE && b->pad_mode != VAD_BATCH_PAD_FEATURE)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: pad_mode = %d is neither VAD_BATCH_PAD_VALUE nor VAD_BATCH_PAD_FEATURE", who,
-                       b->pad_mode);
-    if (!std::isfinite(b->pad_value))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: pad_value is %s, a pad value is a finite number", who,
-                       std::isnan(b->pad_value) ? "NaN" : "infinite");
+    if (int rc = batch_format_check(e, who, b->dtype, b->pad_mode, b->pad_value)) return rc;
     const int64_t nw = k.nw, n = k.n, T = b->samples;
     if (nw < 0 || k.out_bytes < 0 || (nw > 0 && !k.awin)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer or bad count", who);
-    const int64_t nss = !k.shift && !k.scale ? 1 : k.nss;
-    if (nss != 1 && nss != n)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: nss = %lld: shift and scale have 1 entry or n = %lld", who, (long long)nss,
-                       (long long)n);
+    int64_t nss = k.nss;
+    if (int rc = batch_nss(e, who, k.shift, k.scale, &nss, "entry", "n", n)) return rc;
     for (int which = 0; which < 2; ++which) {
         const float *v = which ? k.scale : k.shift;
         for (int64_t i = 0; v && i < nss; ++i)
@@ -2384,10 +2405,7 @@ int audio_batch_run(vad_engine *e, bool dev, const CutCall &k, const void *audio
     for (int64_t j = 0; j < nw; ++j)
         for (uint32_t q = 0; q < tq; q += vadk::CUT_WG_QUADS) e->ab_work.push_back(vadk::AudioWork{(uint32_t)j, q});
     e->ab_f.resize(2 * (size_t)nss);
-    for (int64_t i = 0; i < nss; ++i) {
-        e->ab_f[(size_t)i] = k.shift ? k.shift[i] : 0.0f;
-        e->ab_f[(size_t)(nss + i)] = k.scale ? k.scale[i] : 1.0f;
-    }
+    affine_fill(e->ab_f.data(), e->ab_f.data() + nss, k.shift, k.scale, (size_t)nss);
     DevTables t{e->d_cut, e->d_cut_cap};
     const int segs = t.add(e->cut_segs, e->cut_segs.size()), win = t.add(e->ab_win, e->ab_win.size());
     const int work = t.add(e->ab_work, e->ab_work.size()), floats = t.add(e->ab_f, e->ab_f.size());
@@ -2737,23 +2755,39 @@ int resample_cut_run(vad_engine *e, bool dev, CutCall k, const void *audio, void
 
 
 // ---- vad_mel_stats / vad_mel_batch: statistics and batches of a feature matrix
+// The family's host path: melb_matrix (and melb_source behind it) for the checks of what a call reads, melb_out / melb_outs for where its
+// results lie on the device, melb_upload for a host matrix once every refusal lies behind, melb_finish for the way out.  The two
+// batch calls are mel_batch_body around what each supplies
 
 // The matrix and the segments a call names: the caller's, or the resident ones of vad_scan_mel_keep.  Checks only; x is the device
 // matrix where there is one already (a host matrix is uploaded by melb_upload once every refusal lies behind)
 struct MelbSrc { const float *x; int64_t rows; int32_t n_mels; const int64_t *start; int64_t n; };
 
-int melb_source(vad_engine *e, const char *who, bool dev, const float *features, int64_t rows, int32_t n_mels, const int64_t *start, int64_t n,
+// The matrix half.  resident: the call names something resident (NULL features; NULL start too, where it has segments).  For
+// features == NULL the resident matrix's rows and width replace the arguments; `noun` names the width in the refusal
+int melb_matrix(vad_engine *e, const char *who, bool dev, bool resident, const float *features, int64_t rows, int32_t width, const char *noun,
                 MelbSrc *src) {
-    if ((!features || !start) && e->melk_start.empty())
+    if (resident && e->melk_start.empty())
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: NULL names the resident matrix, and the engine holds none: no "
                        "vad_scan_mel_keep has kept one", who);
     if (!features) {
         rows = e->melk_start.back();
-        n_mels = e->melk_n_mels;
+        width = e->melk_n_mels;
     } else if (rows < 0) {
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: rows = %lld is negative", who, (long long)rows);
     }
-    if (n_mels < 1 || n_mels > 128) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n_mels = %d must be 1 .. 128", who, n_mels);
+    if (width < 1 || width > 128) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: %s = %d must be 1 .. 128", who, noun, width);
+    src->x = features ? (dev ? features : nullptr) : e->d_melk;
+    src->rows = rows;
+    src->n_mels = width;
+    return VAD_OK;
+}
+
+// ... and the segments behind it, with the device form's alignment of the features last
+int melb_source(vad_engine *e, const char *who, bool dev, const float *features, int64_t rows, int32_t n_mels, const int64_t *start, int64_t n,
+                MelbSrc *src) {
+    if (int rc = melb_matrix(e, who, dev, !features || !start, features, rows, n_mels, "n_mels", src)) return rc;
+    rows = src->rows;
     if (!start) {
         start = e->melk_start.data();
         n = (int64_t)e->melk_start.size() - 1;
@@ -2774,7 +2808,8 @@ int melb_source(vad_engine *e, const char *who, bool dev, const float *features,
     }
     if (dev && features && (reinterpret_cast<uintptr_t>(features) & 3))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the features must be 4-byte aligned", who);
-    *src = MelbSrc{features ? (dev ? features : nullptr) : e->d_melk, rows, n_mels, start, n};
+    src->start = start;
+    src->n = n;
     return VAD_OK;
 }
 
@@ -2784,6 +2819,42 @@ int melb_upload(vad_engine *e, bool dev, const float *features, MelbSrc *src, hi
     if (int rc = ensure(e, e->d_melb_in, e->d_melb_in_cap, bytes)) return rc;
     if (bytes) HIP_TRY(e, hipMemcpyAsync(e->d_melb_in, features, bytes, hipMemcpyHostToDevice, s));
     src->x = e->d_melb_in;
+    return VAD_OK;
+}
+
+// One output of a call: the caller's pointer (nullptr: not asked for), its bytes, and where it lies on the device
+struct MelbOut { void *host; size_t bytes; void *dev; };
+
+// The way out, first half: a device call writes where the caller says, a host call's one output is staged in e->d_melb_out ...
+int melb_out(vad_engine *e, bool dev, void *host, size_t bytes, MelbOut *o) {
+    o->host = o->dev = host;
+    o->bytes = bytes;
+    if (dev) return VAD_OK;
+    if (int rc = ensure(e, e->d_melb_out, e->d_melb_out_cap, o->bytes)) return rc;
+    o->dev = e->d_melb_out;
+    return VAD_OK;
+}
+
+// ... and its several outputs in room-only slots there, for those the caller asked for
+int melb_outs(vad_engine *e, bool dev, MelbOut *o, int count) {
+    for (int i = 0; i < count; ++i) o[i].dev = o[i].host;
+    if (dev) return VAD_OK;
+    DevTables t{e->d_melb_out, e->d_melb_out_cap};
+    int slot[DevTables::MAX];
+    for (int i = 0; i < count; ++i) slot[i] = t.add(nullptr, o[i].host ? o[i].bytes : 0);
+    if (int rc = t.reserve(e)) return rc;
+    for (int i = 0; i < count; ++i) o[i].dev = t.at<uint8_t>(slot[i]);
+    return VAD_OK;
+}
+
+// Second half, behind the launch whose status is `launched`: call_end, and for a host call the outputs in the order listed and one
+// synchronise
+int melb_finish(vad_engine *e, bool dev, hipStream_t s, int launched, const MelbOut *o, int count) {
+    const int rc = call_end(e, dev, s, launched);
+    if (rc || dev) return rc;
+    for (int i = 0; i < count; ++i)
+        if (o[i].host) HIP_TRY(e, hipMemcpyAsync(o[i].host, o[i].dev, o[i].bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
     return VAD_OK;
 }
 
@@ -2831,20 +2902,19 @@ int mel_stats_run(vad_engine *e, bool dev, const char *who, const float *feature
     DevTables t{e->d_melb, e->d_melb_cap};
     const int work = t.add(e->melb_work, e->melb_work.size());
     if (int rc = t.reserve(e)) return rc;
+    // the outputs in the order they lie in e->d_melb_out and come back: the sums, their squares, the maxima
+    enum { SUM, SUMSQ, MAXIMA, OUTS };
+    MelbOut o[OUTS] = {};
+    o[SUM].host = sum_out;
+    o[SUMSQ].host = sumsq_out;
+    o[SUM].bytes = o[SUMSQ].bytes = sumb;
+    o[MAXIMA].host = max_out;
+    o[MAXIMA].bytes = maxb;
+    if (int rc = melb_outs(e, dev, o, OUTS)) return rc;
     vadk::MelStatsArgs a{};
-    if (dev) {
-        a.max_out = max_out;
-        a.sum_out = reinterpret_cast<long long *>(sum_out);
-        a.sumsq_out = reinterpret_cast<unsigned long long *>(sumsq_out);
-    } else {
-        // a host call's results in e->d_melb_out: room only, for the three the caller asked for
-        DevTables o{e->d_melb_out, e->d_melb_out_cap};
-        const int sum = o.add(nullptr, sum_out ? sumb : 0), sumsq = o.add(nullptr, sumsq_out ? sumb : 0), max = o.add(nullptr, max_out ? maxb : 0);
-        if (int rc = o.reserve(e)) return rc;
-        a.sum_out = o.at<long long>(sum);
-        a.sumsq_out = o.at<unsigned long long>(sumsq);
-        a.max_out = o.at<float>(max);
-    }
+    a.sum_out = static_cast<long long *>(o[SUM].dev);
+    a.sumsq_out = static_cast<unsigned long long *>(o[SUMSQ].dev);
+    a.max_out = static_cast<float *>(o[MAXIMA].dev);
     if (int rc = melb_upload(e, dev, features, &src, s)) return rc;
     if (int rc = t.copy(e, s)) return rc;
     // the call's own start values: -inf and zeros
@@ -2859,13 +2929,7 @@ int mel_stats_run(vad_engine *e, bool dev, const char *who, const float *feature
     a.nwork = (uint32_t)e->melb_work.size();
     a.n_mels = (uint32_t)src.n_mels;
     const hipError_t r = vadk_launch_mel_stats(&a, s);
-    const int rc = call_end(e, dev, s, r != hipSuccess ? e->hip_fail(r, "kernel launch (mel stats)") : VAD_OK);
-    if (rc || dev) return rc;
-    if (sum_out) HIP_TRY(e, hipMemcpyAsync(sum_out, a.sum_out, sumb, hipMemcpyDeviceToHost, s));
-    if (sumsq_out) HIP_TRY(e, hipMemcpyAsync(sumsq_out, a.sumsq_out, sumb, hipMemcpyDeviceToHost, s));
-    if (max_out) HIP_TRY(e, hipMemcpyAsync(max_out, a.max_out, maxb, hipMemcpyDeviceToHost, s));
-    HIP_TRY(e, hipStreamSynchronize(s));
-    return VAD_OK;
+    return melb_finish(e, dev, s, r != hipSuccess ? e->hip_fail(r, "kernel launch (mel stats)") : VAD_OK, o, OUTS);
 }
 
 // op [n_in][n_out] and bias [n_out] (nullptr: zeros) in fragment order in e->d_proj (vad_layout.h: proj_pack_index), the bias behind
@@ -2903,16 +2967,10 @@ int mel_project_run(vad_engine *e, bool dev, const char *who, const float *featu
                     int32_t n_out, float *out, void *stream) {
     hipStream_t s;
     if (int rc = call_begin(e, dev, stream, &s)) return rc;
-    if (!features) {
-        if (e->melk_start.empty())
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: NULL names the resident matrix, and the engine holds none: no "
-                           "vad_scan_mel_keep has kept one", who);
-        rows = e->melk_start.back();
-        n_in = e->melk_n_mels;
-    } else if (rows < 0) {
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: rows = %lld is negative", who, (long long)rows);
-    }
-    if (n_in < 1 || n_in > vadk::PROJ_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n_in = %d must be 1 .. 128", who, n_in);
+    MelbSrc src{};
+    if (int rc = melb_matrix(e, who, dev, !features, features, rows, n_in, "n_in", &src)) return rc;
+    rows = src.rows;
+    n_in = src.n_mels;
     if (n_out < 1 || n_out > vadk::PROJ_MAX) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n_out = %d must be 1 .. 128", who, n_out);
     if (!op) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null op", who);
     for (int32_t k = 0; k < n_in; ++k)
@@ -2931,7 +2989,7 @@ int mel_project_run(vad_engine *e, bool dev, const char *who, const float *featu
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the features and the output must be 4-byte aligned", who);
     const size_t ib = (size_t)rows * (size_t)n_in * sizeof(float), ob = (size_t)rows * (size_t)n_out * sizeof(float);
     if (dev && out && rows) {
-        const uintptr_t x0 = reinterpret_cast<uintptr_t>(features ? features : e->d_melk), y0 = reinterpret_cast<uintptr_t>(out);
+        const uintptr_t x0 = reinterpret_cast<uintptr_t>(src.x), y0 = reinterpret_cast<uintptr_t>(out);
         if (x0 < y0 + ob && y0 < x0 + ib)
             return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output's %llu bytes overlap the %llu bytes of the features", who,
                            (unsigned long long)ob, (unsigned long long)ib);
@@ -2942,20 +3000,18 @@ int mel_project_run(vad_engine *e, bool dev, const char *who, const float *featu
         if (!out) e->melk_n_mels = n_out;
         return VAD_OK;
     }
-    vadk::ProjArgs a{};
+    MelbOut o{};
     if (!out) {
         if (int rc = ensure(e, e->d_melk_alt, e->d_melk_alt_cap, ob)) return rc;
-        a.out = e->d_melk_alt;
-    } else if (dev) {
-        a.out = out;
-    } else {
-        if (int rc = ensure(e, e->d_melb_out, e->d_melb_out_cap, ob)) return rc;
-        a.out = reinterpret_cast<float *>(e->d_melb_out);
+        o.dev = e->d_melk_alt;
+    } else if (int rc = melb_out(e, dev, out, ob, &o)) {
+        return rc;
     }
     if (int rc = project_operator(e, n_in, n_out, op, bias, s)) return rc;
-    MelbSrc src{features ? (dev ? features : nullptr) : e->d_melk, rows, n_in, nullptr, 0};
     if (int rc = melb_upload(e, dev, features, &src, s)) return rc;
+    vadk::ProjArgs a{};
     a.x = src.x;
+    a.out = static_cast<float *>(o.dev);
     a.op = e->d_proj;
     a.rows = (uint64_t)rows;
     a.n_in = (uint32_t)n_in;
@@ -2968,11 +3024,7 @@ int mel_project_run(vad_engine *e, bool dev, const char *who, const float *featu
         std::swap(e->d_melk_cap, e->d_melk_alt_cap);
         e->melk_n_mels = n_out;
     }
-    const int rc = call_end(e, dev, s, launched);
-    if (rc || dev) return rc;
-    if (out) HIP_TRY(e, hipMemcpyAsync(out, a.out, ob, hipMemcpyDeviceToHost, s));
-    HIP_TRY(e, hipStreamSynchronize(s));
-    return VAD_OK;
+    return melb_finish(e, dev, s, launched, &o, 1);
 }
 
 // vad_batch's fields, ahead of everything else
@@ -2984,13 +3036,7 @@ int batch_check(vad_engine *e, const char *who, const vad_batch *b) {
     if (b->deltas < 0 || b->deltas > 2) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: deltas = %d must be 0 .. 2", who, b->deltas);
     if (b->layout != VAD_BATCH_CHANNEL_MAJOR && b->layout != VAD_BATCH_TIME_MAJOR)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: layout = %d is neither VAD_BATCH_CHANNEL_MAJOR nor VAD_BATCH_TIME_MAJOR", who, b->layout);
-    if (b->dtype != VAD_BATCH_F32 && b->dtype != VAD_BATCH_F16 && b->dtype != VAD_BATCH_BF16)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: dtype = %d is none of VAD_BATCH_F32, VAD_BATCH_F16, VAD_BATCH_BF16", who, b->dtype);
-    if (b->pad_mode != VAD_BATCH_PAD_VALUE && b->pad_mode != VAD_BATCH_PAD_FEATURE)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: pad_mode = %d is neither VAD_BATCH_PAD_VALUE nor VAD_BATCH_PAD_FEATURE", who, b->pad_mode);
-    if (!std::isfinite(b->pad_value))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: pad_value is %s, a pad value is a finite number", who,
-                       std::isnan(b->pad_value) ? "NaN" : "infinite");
+    if (int rc = batch_format_check(e, who, b->dtype, b->pad_mode, b->pad_value)) return rc;
     if (b->reserved != 0) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: vad_batch.reserved = %d must be 0", who, b->reserved);
     return VAD_OK;
 }
@@ -3009,10 +3055,20 @@ int batch_affine_check(vad_engine *e, const char *who, const float *lo, size_t n
     return VAD_OK;
 }
 
-// vad_mel_batch / _device with e->mu held.  In e->d_melb: the windows, then lo [n], shift and scale [nss][n_mels]
-int mel_batch_run(vad_engine *e, bool dev, const char *who, const float *features, int64_t rows, const int64_t *start, int64_t n, const vad_batch *b,
-                  const vad_batch_window *windows, int64_t nw, const float *lo, const float *shift, const float *scale, int64_t nss, void *out,
-                  int64_t out_bytes, void *stream) {
+// What a kind of batch is to mel_batch_body besides its three callables
+struct BatchKind {
+    bool bad_count;       // its part of the count check: a count or a buffer of its own is wrong
+    bool per_window;      // lo, shift and scale go by window - lo [nw], nss is 1 or nw - else by segment: lo [n], nss is 1 or n
+    const char *what;     // its launch, named for a failed one
+};
+
+// What the two batch calls share, around a kind and its three callables: check(src, tile, &groups) refuses its windows or pieces in
+// its order and counts the workgroups; table(src, tile, groups, t), behind every refusal, adds its table to e->d_melb;
+// launch(a, t, its table, s).  In e->d_melb: the kind's table, then lo [n or nw], shift and scale [nss][n_mels]
+template <class Check, class Table, class Launch>
+int mel_batch_body(vad_engine *e, bool dev, const char *who, const float *features, int64_t rows, const int64_t *start, int64_t n, const vad_batch *b,
+                   int64_t nw, const float *lo, const float *shift, const float *scale, int64_t nss, void *out, int64_t out_bytes, void *stream,
+                   const BatchKind &kind, Check check, Table table, Launch launch) {
     hipStream_t s;
     if (int rc = call_begin(e, dev, stream, &s)) return rc;
     if (int rc = batch_check(e, who, b)) return rc;
@@ -3020,55 +3076,41 @@ int mel_batch_run(vad_engine *e, bool dev, const char *who, const float *feature
     if (int rc = melb_source(e, who, dev, features, rows, b->n_mels, start, n, &src)) return rc;
     if (src.n_mels != b->n_mels)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n_mels = %d, the resident matrix has %d", who, b->n_mels, src.n_mels);
-    if (nw < 0 || out_bytes < 0 || (nw > 0 && !windows)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer or bad count", who);
-    if (!shift && !scale) nss = 1;
-    if (nss != 1 && nss != src.n)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: nss = %lld: shift and scale have 1 row or n = %lld", who, (long long)nss,
-                       (long long)src.n);
-    const size_t nm = (size_t)b->n_mels, nn = (size_t)src.n;
-    if (int rc = batch_affine_check(e, who, lo, nn, shift, scale, (size_t)nss, nm)) return rc;
-    e->melb_win.resize((size_t)nw);
-    for (int64_t k = 0; k < nw; ++k) {
-        const vad_batch_window &w = windows[k];
-        if (w.seg < 0 || (int64_t)w.seg >= src.n)
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: window %lld names segment %d of %lld", who, (long long)k, w.seg, (long long)src.n);
-        const int64_t M = src.start[w.seg + 1] - src.start[w.seg];
-        if (w.row0 < 0 || w.nrows < 0 || w.nrows > b->frames || w.row0 > M || w.nrows > M - w.row0)
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: window %lld: rows %lld .. +%d of segment %d, which has %lld, in %d frames", who,
-                           (long long)k, (long long)w.row0, w.nrows, w.seg, (long long)M, b->frames);
-        e->melb_win[(size_t)k] = vadk::MelBatchWin{(uint64_t)src.start[w.seg], (uint32_t)M, (uint32_t)w.row0, (uint32_t)w.nrows, (uint32_t)w.seg};
-    }
-    const uint32_t tile = vadk::melb_tile((uint32_t)b->n_mels, (uint32_t)b->deltas), tiles = ((uint32_t)b->frames + tile - 1u) / tile;
+    if (nw < 0 || out_bytes < 0 || kind.bad_count) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer or bad count", who);
+    const int64_t over = kind.per_window ? nw : src.n;
+    if (int rc = batch_nss(e, who, shift, scale, &nss, "row", kind.per_window ? "nw" : "n", over)) return rc;
+    const size_t nm = (size_t)b->n_mels;
+    if (int rc = batch_affine_check(e, who, lo, (size_t)over, shift, scale, (size_t)nss, nm)) return rc;
+    const uint32_t tile = vadk::melb_tile((uint32_t)b->n_mels, (uint32_t)b->deltas);
+    uint64_t groups = 0;
+    if (int rc = check(src, tile, &groups)) return rc;
     const size_t C = nm * (size_t)(b->deltas + 1), need = (size_t)nw * C * (size_t)b->frames * (b->dtype == VAD_BATCH_F32 ? 4u : 2u);
     if (need > (size_t)out_bytes)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_bytes = %lld, the windows have %llu bytes", who, (long long)out_bytes,
                        (unsigned long long)need);
-    if ((uint64_t)nw * tiles > (uint64_t)INT32_MAX)
+    if (nw > (int64_t)INT32_MAX || groups > (uint64_t)INT32_MAX)
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %u frames in one call", who, tile);
     if (nw == 0) return VAD_OK;
     if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
     if (dev && (reinterpret_cast<uintptr_t>(out) & 15))
         return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output must be 16-byte aligned", who);
-    // lo, shift and scale go up as one table of floats, in this order
-    const size_t nlo = std::max<size_t>(nn, 1), nsc = (size_t)nss * nm;
-    e->melb_f.assign(nlo + 2 * nsc, 0.0f);
     DevTables t{e->d_melb, e->d_melb_cap};
-    const int win = t.add(e->melb_win, (size_t)nw), floats = t.add(e->melb_f, e->melb_f.size());
+    const int mine = table(src, tile, groups, t);
+    // lo, shift and scale go up as one table of floats, in this order
+    const size_t nlo = std::max<size_t>((size_t)over, 1), nsc = (size_t)nss * nm;
+    e->melb_f.assign(nlo + 2 * nsc, 0.0f);
+    const int floats = t.add(e->melb_f, e->melb_f.size());
     if (int rc = t.reserve(e)) return rc;
-    if (!dev)
-        if (int rc = ensure(e, e->d_melb_out, e->d_melb_out_cap, need)) return rc;
+    MelbOut o{};
+    if (int rc = melb_out(e, dev, out, need, &o)) return rc;
     if (int rc = melb_upload(e, dev, features, &src, s)) return rc;
-    float *hl = e->melb_f.data(), *hs = hl + nlo, *hc = hs + nsc;
-    for (size_t i = 0; i < nn; ++i) hl[i] = lo ? lo[i] : -INFINITY;
-    for (size_t k = 0; k < nsc; ++k) {
-        hs[k] = shift ? shift[k] : 0.0f;
-        hc[k] = scale ? scale[k] : 1.0f;
-    }
+    float *hl = e->melb_f.data();
+    for (size_t i = 0; i < (size_t)over; ++i) hl[i] = lo ? lo[i] : -INFINITY;
+    affine_fill(hl + nlo, hl + nlo + nsc, shift, scale, nsc);
     if (int rc = t.copy(e, s)) return rc;
     vadk::MelBatchArgs a{};
     a.x = src.x;
-    a.out = dev ? out : static_cast<void *>(e->d_melb_out);
-    a.win = t.at<const vadk::MelBatchWin>(win);
+    a.out = o.dev;
     a.lo = t.at<const float>(floats);
     a.shift = a.lo + nlo;
     a.scale = a.shift + nsc;
@@ -3082,148 +3124,132 @@ int mel_batch_run(vad_engine *e, bool dev, const char *who, const float *feature
     a.pad_value = b->pad_value;
     a.per_seg = nss == 1 ? 0u : 1u;
     a.tile = tile;
-    const hipError_t r = vadk_launch_mel_batch(&a, s);
-    const int rc = call_end(e, dev, s, r != hipSuccess ? e->hip_fail(r, "kernel launch (mel batch)") : VAD_OK);
-    if (rc || dev) return rc;
-    HIP_TRY(e, hipMemcpyAsync(out, e->d_melb_out, need, hipMemcpyDeviceToHost, s));
-    HIP_TRY(e, hipStreamSynchronize(s));
-    return VAD_OK;
+    const hipError_t r = launch(a, t, mine, s);
+    return melb_finish(e, dev, s, r != hipSuccess ? e->hip_fail(r, kind.what) : VAD_OK, &o, 1);
 }
 
-// vad_mel_batch_packed / _device with e->mu held.  In e->d_melb: the work list, then lo [nw], shift and scale [nss][n_mels]
+// vad_mel_batch / _device with e->mu held: a window is rows of one segment, under the segment's lo, shift and scale.  Its table:
+// MelBatchWin [nw]
+int mel_batch_run(vad_engine *e, bool dev, const char *who, const float *features, int64_t rows, const int64_t *start, int64_t n, const vad_batch *b,
+                  const vad_batch_window *windows, int64_t nw, const float *lo, const float *shift, const float *scale, int64_t nss, void *out,
+                  int64_t out_bytes, void *stream) {
+    auto check = [&](const MelbSrc &src, uint32_t tile, uint64_t *groups) -> int {
+        e->melb_win.resize((size_t)nw);
+        for (int64_t k = 0; k < nw; ++k) {
+            const vad_batch_window &w = windows[k];
+            if (w.seg < 0 || (int64_t)w.seg >= src.n)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: window %lld names segment %d of %lld", who, (long long)k, w.seg, (long long)src.n);
+            const int64_t M = src.start[w.seg + 1] - src.start[w.seg];
+            if (w.row0 < 0 || w.nrows < 0 || w.nrows > b->frames || w.row0 > M || w.nrows > M - w.row0)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: window %lld: rows %lld .. +%d of segment %d, which has %lld, in %d frames", who,
+                               (long long)k, (long long)w.row0, w.nrows, w.seg, (long long)M, b->frames);
+            e->melb_win[(size_t)k] = vadk::MelBatchWin{(uint64_t)src.start[w.seg], (uint32_t)M, (uint32_t)w.row0, (uint32_t)w.nrows, (uint32_t)w.seg};
+        }
+        *groups = (uint64_t)nw * (((uint32_t)b->frames + tile - 1u) / tile);
+        return VAD_OK;
+    };
+    auto table = [&](const MelbSrc &, uint32_t, uint64_t, DevTables &t) { return t.add(e->melb_win, (size_t)nw); };
+    auto launch = [&](vadk::MelBatchArgs &a, const DevTables &t, int win, hipStream_t s) {
+        a.win = t.at<const vadk::MelBatchWin>(win);
+        return vadk_launch_mel_batch(&a, s);
+    };
+    BatchKind kind{};
+    kind.bad_count = nw > 0 && !windows;
+    kind.per_window = false;
+    kind.what = "kernel launch (mel batch)";
+    return mel_batch_body(e, dev, who, features, rows, start, n, b, nw, lo, shift, scale, nss, out, out_bytes, stream, kind, check, table, launch);
+}
+
+// vad_mel_batch_packed / _device with e->mu held: pieces of segments side by side in a window, under the window's lo, shift and scale.
+// Its table: the work list, a MelPackWork per workgroup
 int mel_batch_packed_run(vad_engine *e, bool dev, const char *who, const float *features, int64_t rows, const int64_t *start, int64_t n,
                          const vad_batch *b, const vad_batch_piece *pieces, int64_t np, int64_t nw, const float *lo, const float *shift,
                          const float *scale, int64_t nss, void *out, int64_t out_bytes, void *stream) {
-    hipStream_t s;
-    if (int rc = call_begin(e, dev, stream, &s)) return rc;
-    if (int rc = batch_check(e, who, b)) return rc;
-    MelbSrc src{};
-    if (int rc = melb_source(e, who, dev, features, rows, b->n_mels, start, n, &src)) return rc;
-    if (src.n_mels != b->n_mels)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: n_mels = %d, the resident matrix has %d", who, b->n_mels, src.n_mels);
-    if (np < 0 || nw < 0 || out_bytes < 0 || (np > 0 && !pieces)) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer or bad count", who);
-    if (!shift && !scale) nss = 1;
-    if (nss != 1 && nss != nw)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: nss = %lld: shift and scale have 1 row or nw = %lld", who, (long long)nss,
-                       (long long)nw);
-    const size_t nm = (size_t)b->n_mels;
-    const int64_t T = b->frames;
-    if (int rc = batch_affine_check(e, who, lo, (size_t)nw, shift, scale, (size_t)nss, nm)) return rc;
-    for (int64_t k = 0; k < np; ++k) {
-        const vad_batch_piece &p = pieces[k];
-        if (p.seg < 0 || (int64_t)p.seg >= src.n)
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: piece %lld names segment %d of %lld", who, (long long)k, p.seg, (long long)src.n);
-        const int64_t M = src.start[p.seg + 1] - src.start[p.seg];
-        if (p.row0 < 0 || p.nrows < 1 || p.row0 > M || p.nrows > M - p.row0)
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: piece %lld: rows %lld .. +%d of segment %d, which has %lld", who, (long long)k,
-                           (long long)p.row0, p.nrows, p.seg, (long long)M);
-        if (p.window < 0 || (int64_t)p.window >= nw)
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: piece %lld names window %d of %lld", who, (long long)k, p.window, (long long)nw);
-        if (p.offset < 0 || (p.offset & 3) || (int64_t)p.offset + p.nrows > T)
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: piece %lld: offset = %d with %d rows: a multiple of 4 from 0, offset + nrows <= %d "
-                           "frames", who, (long long)k, p.offset, p.nrows, b->frames);
-    }
-    // the pieces by (window, offset); a piece owns [offset, up4(offset + nrows)) of its window
-    const uint32_t tile = vadk::melb_tile((uint32_t)b->n_mels, (uint32_t)b->deltas), tiles = ((uint32_t)b->frames + tile - 1u) / tile;
-    auto groups_of = [tile](int64_t frames) -> int64_t { return (frames + tile - 1) / tile; };
-    e->melb_order.resize((size_t)np);
-    for (int64_t k = 0; k < np; ++k) e->melb_order[(size_t)k] = k;
-    std::sort(e->melb_order.begin(), e->melb_order.end(), [pieces](int64_t x, int64_t y) {
-        const vad_batch_piece &p = pieces[x], &q = pieces[y];
-        return p.window != q.window ? p.window < q.window : p.offset != q.offset ? p.offset < q.offset : x < y;
-    });
-    int64_t nwork = 0, with_pieces = 0;           // workgroups of the windows that have a piece, and those windows
-    for (int64_t k = 0, used = 0; k < np; ++k) {
-        const int64_t pk = e->melb_order[(size_t)k];
-        const vad_batch_piece &p = pieces[pk];
-        const bool first = k == 0 || pieces[e->melb_order[(size_t)k - 1]].window != p.window;
-        if (first) {
-            if (k) nwork += groups_of(T - used);
-            used = 0;
-            ++with_pieces;
-        } else if (p.offset < used) {
-            const int64_t qk = e->melb_order[(size_t)k - 1];
-            return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: pieces %lld and %lld overlap in window %d: frames %d .. %lld and %d .. %lld",
-                           who, (long long)std::min(pk, qk), (long long)std::max(pk, qk), p.window, pieces[qk].offset, (long long)used - 1, p.offset,
-                           (long long)(((int64_t)p.offset + p.nrows + 3) & ~(int64_t)3) - 1);
-        }
-        nwork += groups_of(p.offset - used) + groups_of(p.nrows);
-        used = ((int64_t)p.offset + p.nrows + 3) & ~(int64_t)3;
-        if (k == np - 1) nwork += groups_of(T - used);
-    }
-    const size_t C = nm * (size_t)(b->deltas + 1), need = (size_t)nw * C * (size_t)b->frames * (b->dtype == VAD_BATCH_F32 ? 4u : 2u);
-    if (need > (size_t)out_bytes)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: out_bytes = %lld, the windows have %llu bytes", who, (long long)out_bytes,
-                       (unsigned long long)need);
-    if (nw > (int64_t)INT32_MAX || (uint64_t)nwork + (uint64_t)(nw - with_pieces) * tiles > (uint64_t)INT32_MAX)
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: more than 2^31 - 1 workgroups of %u frames in one call", who, tile);
-    if (nw == 0) return VAD_OK;
-    if (!out) return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: null buffer", who);
-    if (dev && (reinterpret_cast<uintptr_t>(out) & 15))
-        return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: the output must be 16-byte aligned", who);
-    // the work list, window by window: pad runs before, between and behind the pieces, each piece tile by tile
-    e->melb_pack.clear();
-    e->melb_pack.reserve((size_t)nwork + (size_t)(nw - with_pieces) * tiles);
-    auto pad_run = [&](int64_t w, int64_t from, int64_t to) {
-        for (int64_t t = from; t < to; t += tile)
-            e->melb_pack.push_back(vadk::MelPackWork{0u, 0u, 0u, (uint32_t)w, (uint32_t)t, (uint32_t)std::min<int64_t>(tile, to - t), 0u});
-    };
-    int64_t k = 0;
-    for (int64_t w = 0; w < nw; ++w) {
-        int64_t used = 0;
-        for (; k < np && pieces[e->melb_order[(size_t)k]].window == w; ++k) {
-            const vad_batch_piece &p = pieces[e->melb_order[(size_t)k]];
-            pad_run(w, used, p.offset);
+    auto check = [&](const MelbSrc &src, uint32_t tile, uint64_t *groups) -> int {
+        const int64_t T = b->frames;
+        for (int64_t k = 0; k < np; ++k) {
+            const vad_batch_piece &p = pieces[k];
+            if (p.seg < 0 || (int64_t)p.seg >= src.n)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: piece %lld names segment %d of %lld", who, (long long)k, p.seg, (long long)src.n);
             const int64_t M = src.start[p.seg + 1] - src.start[p.seg];
-            for (int64_t r = 0; r < p.nrows; r += tile) {
-                const int64_t nv = std::min<int64_t>(tile, p.nrows - r);
-                e->melb_pack.push_back(vadk::MelPackWork{(uint64_t)src.start[p.seg], (uint32_t)M, (uint32_t)(p.row0 + r), (uint32_t)w,
-                                                         (uint32_t)(p.offset + r), (uint32_t)((nv + 3) & ~(int64_t)3), (uint32_t)nv});
-            }
-            used = ((int64_t)p.offset + p.nrows + 3) & ~(int64_t)3;
+            if (p.row0 < 0 || p.nrows < 1 || p.row0 > M || p.nrows > M - p.row0)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: piece %lld: rows %lld .. +%d of segment %d, which has %lld", who, (long long)k,
+                               (long long)p.row0, p.nrows, p.seg, (long long)M);
+            if (p.window < 0 || (int64_t)p.window >= nw)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: piece %lld names window %d of %lld", who, (long long)k, p.window, (long long)nw);
+            if (p.offset < 0 || (p.offset & 3) || (int64_t)p.offset + p.nrows > T)
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: piece %lld: offset = %d with %d rows: a multiple of 4 from 0, offset + nrows <= %d "
+                               "frames", who, (long long)k, p.offset, p.nrows, b->frames);
         }
-        pad_run(w, used, T);
-    }
-    // lo, shift and scale go up as one table of floats, in this order
-    const size_t nlo = (size_t)nw, nsc = (size_t)nss * nm;
-    e->melb_f.assign(nlo + 2 * nsc, 0.0f);
-    DevTables t{e->d_melb, e->d_melb_cap};
-    const int work = t.add(e->melb_pack, e->melb_pack.size()), floats = t.add(e->melb_f, e->melb_f.size());
-    if (int rc = t.reserve(e)) return rc;
-    if (!dev)
-        if (int rc = ensure(e, e->d_melb_out, e->d_melb_out_cap, need)) return rc;
-    if (int rc = melb_upload(e, dev, features, &src, s)) return rc;
-    float *hl = e->melb_f.data(), *hs = hl + nlo, *hc = hs + nsc;
-    for (size_t i = 0; i < nlo; ++i) hl[i] = lo ? lo[i] : -INFINITY;
-    for (size_t i = 0; i < nsc; ++i) {
-        hs[i] = shift ? shift[i] : 0.0f;
-        hc[i] = scale ? scale[i] : 1.0f;
-    }
-    if (int rc = t.copy(e, s)) return rc;
-    vadk::MelPackArgs a{};
-    a.b.x = src.x;
-    a.b.out = dev ? out : static_cast<void *>(e->d_melb_out);
-    a.b.lo = t.at<const float>(floats);
-    a.b.shift = a.b.lo + nlo;
-    a.b.scale = a.b.shift + nsc;
-    a.b.nw = (uint32_t)nw;
-    a.b.n_mels = (uint32_t)b->n_mels;
-    a.b.frames = (uint32_t)b->frames;
-    a.b.deltas = (uint32_t)b->deltas;
-    a.b.layout = b->layout;
-    a.b.dtype = b->dtype;
-    a.b.pad_mode = b->pad_mode;
-    a.b.pad_value = b->pad_value;
-    a.b.per_seg = nss == 1 ? 0u : 1u;
-    a.b.tile = tile;
-    a.work = t.at<const vadk::MelPackWork>(work);
-    a.nwork = (uint32_t)e->melb_pack.size();
-    const hipError_t r = vadk_launch_mel_batch_packed(&a, s);
-    const int rc = call_end(e, dev, s, r != hipSuccess ? e->hip_fail(r, "kernel launch (mel batch packed)") : VAD_OK);
-    if (rc || dev) return rc;
-    HIP_TRY(e, hipMemcpyAsync(out, e->d_melb_out, need, hipMemcpyDeviceToHost, s));
-    HIP_TRY(e, hipStreamSynchronize(s));
-    return VAD_OK;
+        // the pieces by (window, offset); a piece owns [offset, up4(offset + nrows)) of its window
+        auto groups_of = [tile](int64_t frames) -> int64_t { return (frames + tile - 1) / tile; };
+        e->melb_order.resize((size_t)np);
+        for (int64_t k = 0; k < np; ++k) e->melb_order[(size_t)k] = k;
+        std::sort(e->melb_order.begin(), e->melb_order.end(), [pieces](int64_t x, int64_t y) {
+            const vad_batch_piece &p = pieces[x], &q = pieces[y];
+            return p.window != q.window ? p.window < q.window : p.offset != q.offset ? p.offset < q.offset : x < y;
+        });
+        int64_t nwork = 0, with_pieces = 0;           // workgroups of the windows that have a piece, and those windows
+        for (int64_t k = 0, used = 0; k < np; ++k) {
+            const int64_t pk = e->melb_order[(size_t)k];
+            const vad_batch_piece &p = pieces[pk];
+            const bool first = k == 0 || pieces[e->melb_order[(size_t)k - 1]].window != p.window;
+            if (first) {
+                if (k) nwork += groups_of(T - used);
+                used = 0;
+                ++with_pieces;
+            } else if (p.offset < used) {
+                const int64_t qk = e->melb_order[(size_t)k - 1];
+                return e->fail(VAD_ERR_INVALID_ARG, "Model prediction failed: %s: pieces %lld and %lld overlap in window %d: frames %d .. %lld and %d .. %lld",
+                               who, (long long)std::min(pk, qk), (long long)std::max(pk, qk), p.window, pieces[qk].offset, (long long)used - 1, p.offset,
+                               (long long)(((int64_t)p.offset + p.nrows + 3) & ~(int64_t)3) - 1);
+            }
+            nwork += groups_of(p.offset - used) + groups_of(p.nrows);
+            used = ((int64_t)p.offset + p.nrows + 3) & ~(int64_t)3;
+            if (k == np - 1) nwork += groups_of(T - used);
+        }
+        *groups = (uint64_t)nwork + (uint64_t)(nw - with_pieces) * (uint64_t)groups_of(T);
+        return VAD_OK;
+    };
+    // the work list, window by window: pad runs before, between and behind the pieces, each piece tile by tile
+    auto table = [&](const MelbSrc &src, uint32_t tile, uint64_t groups, DevTables &t) {
+        const int64_t T = b->frames;
+        e->melb_pack.clear();
+        e->melb_pack.reserve((size_t)groups);
+        auto pad_run = [&](int64_t w, int64_t from, int64_t to) {
+            for (int64_t f = from; f < to; f += tile)
+                e->melb_pack.push_back(vadk::MelPackWork{0u, 0u, 0u, (uint32_t)w, (uint32_t)f, (uint32_t)std::min<int64_t>(tile, to - f), 0u});
+        };
+        int64_t k = 0;
+        for (int64_t w = 0; w < nw; ++w) {
+            int64_t used = 0;
+            for (; k < np && pieces[e->melb_order[(size_t)k]].window == w; ++k) {
+                const vad_batch_piece &p = pieces[e->melb_order[(size_t)k]];
+                pad_run(w, used, p.offset);
+                const int64_t M = src.start[p.seg + 1] - src.start[p.seg];
+                for (int64_t r = 0; r < p.nrows; r += tile) {
+                    const int64_t nv = std::min<int64_t>(tile, p.nrows - r);
+                    e->melb_pack.push_back(vadk::MelPackWork{(uint64_t)src.start[p.seg], (uint32_t)M, (uint32_t)(p.row0 + r), (uint32_t)w,
+                                                             (uint32_t)(p.offset + r), (uint32_t)((nv + 3) & ~(int64_t)3), (uint32_t)nv});
+                }
+                used = ((int64_t)p.offset + p.nrows + 3) & ~(int64_t)3;
+            }
+            pad_run(w, used, T);
+        }
+        return t.add(e->melb_pack, e->melb_pack.size());
+    };
+    auto launch = [&](const vadk::MelBatchArgs &args, const DevTables &t, int work, hipStream_t s) {
+        vadk::MelPackArgs a{};
+        a.b = args;
+        a.work = t.at<const vadk::MelPackWork>(work);
+        a.nwork = (uint32_t)e->melb_pack.size();
+        return vadk_launch_mel_batch_packed(&a, s);
+    };
+    BatchKind kind{};
+    kind.bad_count = np < 0 || (np > 0 && !pieces);
+    kind.per_window = true;
+    kind.what = "kernel launch (mel batch packed)";
+    return mel_batch_body(e, dev, who, features, rows, start, n, b, nw, lo, shift, scale, nss, out, out_bytes, stream, kind, check, table, launch);
 }
 
 // ---- the entry points of the family: each host / _device pair fills the record in one function that takes `dev`

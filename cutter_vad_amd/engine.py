@@ -1299,6 +1299,13 @@ class Engine:
             raise AudioProcessingError(f"Model prediction failed: mel_project: bias has n_out = {w.shape[1]} entries, got {b.size}")
         return w, b, w.ctypes.data_as(f32p), None if b is None else b.ctypes.data_as(f32p)
 
+    def _project_resident(self, who: str, n_in: int) -> int:
+        """-> the rows of the resident matrix, which has op's ``n_in`` columns"""
+        rows, nm, _ = self.mel_resident()
+        if nm != n_in:
+            raise AudioProcessingError(f"Model prediction failed: {who}: the resident matrix has {nm} columns, op has n_in = {n_in} rows")
+        return rows
+
     def mel_project(self, op, bias=None, features=None, out: bool = True):
         """A linear stage over a feature matrix on the GPU (``vad_mel_project``): ``y = bias + x @ op`` in float32, a fused
         multiply-add chain along ``k`` from the bias, with ``op`` [n_in, n_out] and ``bias`` [n_out] (``None``: 0), both 1 .. 128
@@ -1314,13 +1321,7 @@ class Engine:
         if x is not None and x.shape[1] != w.shape[0]:
             raise AudioProcessingError(f"Model prediction failed: mel_project: the features have {x.shape[1]} columns, op has n_in = {w.shape[0]} rows")
         with self._scan_lock:
-            if x is None:
-                rows, n_in, _ = self.mel_resident()
-                if n_in != w.shape[0]:
-                    raise AudioProcessingError(f"Model prediction failed: mel_project: the resident matrix has {n_in} columns, op has n_in = "
-                                               f"{w.shape[0]} rows")
-            else:
-                rows, n_in = x.shape
+            rows, n_in = (self._project_resident("mel_project", w.shape[0]), w.shape[0]) if x is None else x.shape
             y = np.empty((rows, w.shape[1]), np.float32) if out else None
             self._check(self._lib.vad_mel_project(self._h, None if x is None else x.ctypes.data_as(C.POINTER(C.c_float)), rows, n_in, wp, bp,
                                                   w.shape[1], None if y is None else y.ctypes.data_as(C.POINTER(C.c_float))))
@@ -1334,13 +1335,16 @@ class Engine:
         w, b, wp, bp = self._project_operator(op, bias)
         with self._scan_lock:
             if not d_features:
-                rows, n_in, _ = self.mel_resident()
-                if n_in != w.shape[0]:
-                    raise AudioProcessingError(f"Model prediction failed: mel_project_device: the resident matrix has {n_in} columns, op has n_in = "
-                                               f"{w.shape[0]} rows")
+                rows = self._project_resident("mel_project_device", w.shape[0])
             self._check(self._lib.vad_mel_project_device(self._h, d_features or None, int(rows), w.shape[0], wp, bp, w.shape[1], d_out or None,
                                                          stream or None))
         return int(rows), w.shape[1]
+
+    @staticmethod
+    def _batch_start(start):
+        """-> (start as int64 [n + 1] or None, its pointer, n), as every call of the family passes them on"""
+        st = None if start is None else np.ascontiguousarray(np.asarray(start, np.int64).reshape(-1))
+        return st, None if st is None else st.ctypes.data_as(C.POINTER(C.c_int64)), 0 if st is None else st.size - 1
 
     @staticmethod
     def _batch_source(features, start):
@@ -1348,11 +1352,10 @@ class Engine:
         x = None if features is None else np.ascontiguousarray(np.asarray(features, np.float32))
         if x is not None and x.ndim != 2:
             raise AudioProcessingError(f"Model prediction failed: features are [rows, n_mels], got {x.shape}")
-        st = None if start is None else np.ascontiguousarray(np.asarray(start, np.int64).reshape(-1))
+        st, sp, n = Engine._batch_start(start)
         if st is not None and st.size < 1:
             raise AudioProcessingError("Model prediction failed: start has n + 1 entries, got none")
-        return (x, None if x is None else x.ctypes.data_as(C.POINTER(C.c_float)), 0 if x is None else x.shape[0], 0 if x is None else x.shape[1],
-                st, None if st is None else st.ctypes.data_as(C.POINTER(C.c_int64)), 0 if st is None else st.size - 1)
+        return x, None if x is None else x.ctypes.data_as(C.POINTER(C.c_float)), 0 if x is None else x.shape[0], 0 if x is None else x.shape[1], st, sp, n
 
     def mel_stats(self, features=None, start=None, moments: bool = True, group=None) -> dict:
         """Per-segment statistics of a feature matrix, reduced on the GPU (``vad_mel_stats``): ``features`` [rows, n_mels] float32 with
@@ -1402,10 +1405,11 @@ class Engine:
                           enum(_ffi.BATCH_PADS, "pad", f.get("pad", "value")), float(f.get("pad_value", 0.0)), 0)
 
     @staticmethod
-    def _batch_windows(windows):
-        w = np.ascontiguousarray(np.asarray(windows, _ffi.BATCH_WINDOW_DTYPE).reshape(-1)) if not (
-            isinstance(windows, np.ndarray) and windows.dtype == _ffi.BATCH_WINDOW_DTYPE) else np.ascontiguousarray(windows.reshape(-1))
-        return w, (w if w.size else np.zeros(1, _ffi.BATCH_WINDOW_DTYPE)).ctypes.data_as(C.POINTER(_ffi.BatchWindow))
+    def _batch_table(records, dtype, ctype):
+        """the windows (``_ffi.BATCH_WINDOW_DTYPE``, ``_ffi.BatchWindow``) or the pieces of a batch -> (the flat array, its pointer)"""
+        t = np.ascontiguousarray(np.asarray(records, dtype).reshape(-1)) if not (
+            isinstance(records, np.ndarray) and records.dtype == dtype) else np.ascontiguousarray(records.reshape(-1))
+        return t, (t if t.size else np.zeros(1, dtype)).ctypes.data_as(C.POINTER(ctype))
 
     @staticmethod
     def _batch_affine(lo, shift, scale, n_mels: int):
@@ -1426,6 +1430,17 @@ class Engine:
         ptr = lambda a: None if a is None else a.ctypes.data_as(f32p)
         return (lo, *two), (ptr(lo), ptr(two[0]), ptr(two[1])), (rows.pop() if rows else 1)
 
+    def _batch_plan(self, batch, n_mels: int, records, dtype, ctype, nw, lo, shift, scale):
+        """What the four batch methods share, in the order they raise: the ``vad_batch`` record, the table of windows or pieces, the
+        affine arrays (held by the caller until its call returns), the batch's shape for ``nw`` windows (``None``: one per record)
+        and its numpy dtype.  -> (record, table, its pointer, affine arrays, their pointers with nss, shape, dtype)"""
+        b = self._batch_record(batch, n_mels)
+        t, tp = self._batch_table(records, dtype, ctype)
+        own, ptrs, nss = self._batch_affine(lo, shift, scale, b.n_mels)
+        nw, chans = t.size if nw is None else int(nw), b.n_mels * (b.deltas + 1)
+        shape = (nw, chans, b.frames) if b.layout == _ffi.VAD_BATCH_CHANNEL_MAJOR else (nw, b.frames, chans)
+        return b, t, tp, own, (*ptrs, nss), shape, {_ffi.VAD_BATCH_F32: np.float32, _ffi.VAD_BATCH_F16: np.float16}.get(b.dtype, np.uint16)
+
     def mel_batch(self, windows, batch, lo=None, shift=None, scale=None, features=None, start=None) -> np.ndarray:
         """Normalised, padded windows of a feature matrix in a model's layout and number format (``vad_mel_batch``), one launch:
         ``windows`` lists ``(seg, nrows, row0)`` - rows ``row0 .. row0 + nrows - 1`` of segment ``seg``
@@ -1439,14 +1454,9 @@ class Engine:
         with self._scan_lock:
             if x is None:
                 nm = self.mel_resident()[1]
-            b = self._batch_record(batch, nm)
-            w, wp = self._batch_windows(windows)
-            _own, ptrs, nss = self._batch_affine(lo, shift, scale, b.n_mels)
-            chans = b.n_mels * (b.deltas + 1)
-            shape = (w.size, chans, b.frames) if b.layout == _ffi.VAD_BATCH_CHANNEL_MAJOR else (w.size, b.frames, chans)
-            out = np.empty(shape, {_ffi.VAD_BATCH_F32: np.float32, _ffi.VAD_BATCH_F16: np.float16}.get(b.dtype, np.uint16))
-            self._check(self._lib.vad_mel_batch(self._h, xp, rows, sp, n, C.byref(b), wp, w.size, *ptrs, nss, out.ctypes.data_as(C.c_void_p),
-                                                out.nbytes))
+            b, w, wp, _own, affine, shape, dtype = self._batch_plan(batch, nm, windows, _ffi.BATCH_WINDOW_DTYPE, _ffi.BatchWindow, None, lo, shift, scale)
+            out = np.empty(shape, dtype)
+            self._check(self._lib.vad_mel_batch(self._h, xp, rows, sp, n, C.byref(b), wp, w.size, *affine, out.ctypes.data_as(C.c_void_p), out.nbytes))
         return out
 
     def mel_batch_device(self, windows, batch, d_out: int, out_bytes: int, lo=None, shift=None, scale=None, d_features: int = 0, rows: int = 0,
@@ -1455,23 +1465,13 @@ class Engine:
         ``out_bytes``), where a model on the same GPU reads them - nothing crosses the link.  ``d_features`` = 0: the resident matrix,
         else a float32 matrix [rows, n_mels] on the GPU.  ``windows``, ``lo``, ``shift``, ``scale`` and ``start`` are host arrays, read
         before the call returns.  Asynchronous on ``stream``.  -> the shape of the batch."""
-        st = None if start is None else np.ascontiguousarray(np.asarray(start, np.int64).reshape(-1))
+        _st, sp, n = self._batch_start(start)
         with self._scan_lock:
             nm = int(n_mels) if d_features else self.mel_resident()[1]
-            b = self._batch_record(batch, nm)
-            w, wp = self._batch_windows(windows)
-            _own, ptrs, nss = self._batch_affine(lo, shift, scale, b.n_mels)
-            self._check(self._lib.vad_mel_batch_device(self._h, d_features or None, int(rows), None if st is None else st.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                       0 if st is None else st.size - 1, C.byref(b), wp, w.size, *ptrs, nss, d_out or None,
+            b, w, wp, _own, affine, shape, _ = self._batch_plan(batch, nm, windows, _ffi.BATCH_WINDOW_DTYPE, _ffi.BatchWindow, None, lo, shift, scale)
+            self._check(self._lib.vad_mel_batch_device(self._h, d_features or None, int(rows), sp, n, C.byref(b), wp, w.size, *affine, d_out or None,
                                                        int(out_bytes), stream or None))
-        chans = b.n_mels * (b.deltas + 1)
-        return (w.size, chans, b.frames) if b.layout == _ffi.VAD_BATCH_CHANNEL_MAJOR else (w.size, b.frames, chans)
-
-    @staticmethod
-    def _batch_pieces(pieces):
-        p = np.ascontiguousarray(np.asarray(pieces, _ffi.BATCH_PIECE_DTYPE).reshape(-1)) if not (
-            isinstance(pieces, np.ndarray) and pieces.dtype == _ffi.BATCH_PIECE_DTYPE) else np.ascontiguousarray(pieces.reshape(-1))
-        return p, (p if p.size else np.zeros(1, _ffi.BATCH_PIECE_DTYPE)).ctypes.data_as(C.POINTER(_ffi.BatchPiece))
+        return shape
 
     def mel_batch_packed(self, pieces, nw: int, batch, lo=None, shift=None, scale=None, features=None, start=None) -> np.ndarray:
         """``mel_batch`` with several pieces of segments per window (``vad_mel_batch_packed``), one launch: ``pieces`` lists ``(seg,
@@ -1484,13 +1484,9 @@ class Engine:
         with self._scan_lock:
             if x is None:
                 nm = self.mel_resident()[1]
-            b = self._batch_record(batch, nm)
-            p, pp = self._batch_pieces(pieces)
-            _own, ptrs, nss = self._batch_affine(lo, shift, scale, b.n_mels)
-            chans = b.n_mels * (b.deltas + 1)
-            shape = (int(nw), chans, b.frames) if b.layout == _ffi.VAD_BATCH_CHANNEL_MAJOR else (int(nw), b.frames, chans)
-            out = np.empty(shape, {_ffi.VAD_BATCH_F32: np.float32, _ffi.VAD_BATCH_F16: np.float16}.get(b.dtype, np.uint16))
-            self._check(self._lib.vad_mel_batch_packed(self._h, xp, rows, sp, n, C.byref(b), pp, p.size, int(nw), *ptrs, nss,
+            b, p, pp, _own, affine, shape, dtype = self._batch_plan(batch, nm, pieces, _ffi.BATCH_PIECE_DTYPE, _ffi.BatchPiece, nw, lo, shift, scale)
+            out = np.empty(shape, dtype)
+            self._check(self._lib.vad_mel_batch_packed(self._h, xp, rows, sp, n, C.byref(b), pp, p.size, int(nw), *affine,
                                                        out.ctypes.data_as(C.c_void_p), out.nbytes))
         return out
 
@@ -1498,18 +1494,13 @@ class Engine:
                                 rows: int = 0, n_mels: int = 0, start=None, stream: int = 0) -> Tuple[int, ...]:
         """``mel_batch_packed`` into device memory (``vad_mel_batch_packed_device``); the arguments as in ``mel_batch_device``.
         Asynchronous on ``stream``.  -> the shape of the batch."""
-        st = None if start is None else np.ascontiguousarray(np.asarray(start, np.int64).reshape(-1))
+        _st, sp, n = self._batch_start(start)
         with self._scan_lock:
             nm = int(n_mels) if d_features else self.mel_resident()[1]
-            b = self._batch_record(batch, nm)
-            p, pp = self._batch_pieces(pieces)
-            _own, ptrs, nss = self._batch_affine(lo, shift, scale, b.n_mels)
-            self._check(self._lib.vad_mel_batch_packed_device(self._h, d_features or None, int(rows),
-                                                              None if st is None else st.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                              0 if st is None else st.size - 1, C.byref(b), pp, p.size, int(nw), *ptrs, nss,
+            b, p, pp, _own, affine, shape, _ = self._batch_plan(batch, nm, pieces, _ffi.BATCH_PIECE_DTYPE, _ffi.BatchPiece, nw, lo, shift, scale)
+            self._check(self._lib.vad_mel_batch_packed_device(self._h, d_features or None, int(rows), sp, n, C.byref(b), pp, p.size, int(nw), *affine,
                                                               d_out or None, int(out_bytes), stream or None))
-        chans = b.n_mels * (b.deltas + 1)
-        return (int(nw), chans, b.frames) if b.layout == _ffi.VAD_BATCH_CHANNEL_MAJOR else (int(nw), b.frames, chans)
+        return shape
 
     # ------------------------------------------------------------------ rendered audio
     @staticmethod

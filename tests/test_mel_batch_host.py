@@ -617,3 +617,191 @@ def test_a_keep_with_several_faults_gets_the_first_refusal(lib, eng, rate):
     last = ((INV, "the audio block must be 4-byte aligned", "audio", RO.buf(4 * RO.NS), RO.DEVICE),)
     RO.walk(lib, eng, call, faults, first + block + fields + last if rate == 48000 else fields + block + last)
     assert rows_out.value == (63 if rate == 48000 else 74)
+
+
+# ---- the whole order of the family's checks, on the smallest shapes that reach them ----------------------------------------
+# A matrix of 3 rows x 2 columns, start = [0, 1, 3], frames = 4, one window or one piece - a caller's matrix and a resident one.
+# tests/test_mel_pack_host.py walks vad_mel_batch_packed and vad_mel_stats_grouped with the same helpers
+def keep_3x2(lib, eng):
+    """a keep that leaves 3 rows x 2 columns resident, start = [0, 1, 3]: analysis frames of 512 samples at a hop of 256 over two
+    segments of 512 and 768 samples"""
+    from tests import refusal_order as RO
+    m = RO.mel(n_fft=512, hop=256, n_bins=1, n_mels=2)
+    op, fil, rows = np.zeros(512, np.float32), np.zeros(2, np.float32), C.c_int64(-1)
+    rc = lib.vad_scan_mel_keep(eng.handle, RO.cut_items([(0, 0, 1, 0, 0, 0), (0, 1, 2, 0, 0, 0)]), 2, C.byref(m), RO.f32p(op), RO.f32p(op), RO.f32p(fil),
+                               None, 0, RO.addr(RO.buf(4 * RO.NS)), RO.NS, 1, _ffi.VAD_FMT_F32, 0, 256, -1.0, C.byref(rows))
+    assert rc == 0 and rows.value == 3, lib.vad_last_error(eng.handle).decode()
+
+
+def batch_order_call(lib, eng, packed=False):
+    """call(device, **kw) -> rc of vad_mel_batch, or of vad_mel_batch_packed, for refusal_order.walk.  kw names every argument; items
+    are the windows (seg, nrows, row0) or the pieces (seg, nrows, row0, window, offset); kept = True keeps keep_3x2's matrix first"""
+    from tests import refusal_order as RO
+    rec, name = (_ffi.BatchPiece, "vad_mel_batch_packed") if packed else (_ffi.BatchWindow, "vad_mel_batch")
+
+    def call(device, null_b, n_mels, frames, deltas, layout, dtype, pad_mode, pad_value, reserved, features, rows, start, n, items, nw, lo, shift, scale,
+             nss, out, out_bytes, kept=False):
+        if kept:
+            keep_3x2(lib, eng)
+        b = _ffi.Batch(n_mels, frames, deltas, layout, dtype, pad_mode, pad_value, reserved)
+        st = None if start is None else np.array(start, np.int64)
+        arr = (rec * max(len(items), 1))(*[rec(*i) for i in items])
+        counts = (len(items), nw) if packed else (nw,)
+        args = (rows, RO.i64p(st), n, None if null_b else C.byref(b), arr, *counts, RO.f32p(lo), RO.f32p(shift), RO.f32p(scale), nss, RO.addr(out),
+                out_bytes)
+        if device:
+            return getattr(lib, name + "_device")(eng.handle, RO.addr(features), *args, None)
+        return getattr(lib, name)(eng.handle, RO.f32p(features), *args)
+
+    return call
+
+
+def batch_order(packed, items, item_steps):
+    """(faults, steps) of a batch call on a caller's matrix with every reachable fault at once.  lo is indexed over the n = 2 segments
+    and nss is 1 or n, or both go over the nw = 1 windows (packed).  items: the call's windows or pieces with every fault of theirs;
+    item_steps: (pattern, mended items) in the order of their checks"""
+    from tests import refusal_order as RO
+    nan, inf, per = float("nan"), float("inf"), 1 if packed else 2
+    faults = dict(null_b=True, n_mels=0, frames=5, deltas=3, layout=2, dtype=3, pad_mode=2, pad_value=nan, reserved=1, features=RO.buf(24, 2), rows=-1,
+                  start=[0, 2, 4], n=-1, items=items, nw=-1, lo=RO.f32(*[nan] * per), shift=RO.f32(0.0, inf, *[0.0] * (2 * per - 2)),
+                  scale=RO.f32(*[1.0] * (2 * per - 1), nan), nss=3, out=None, out_bytes=0)
+    steps = ((INV, "null vad_batch", "null_b", False),
+             (INV, "n_mels = 0 must be", "n_mels", 2),
+             (INV, "frames = 5 must be", "frames", 4),
+             (INV, "deltas = 3 must be", "deltas", 0),
+             (INV, "layout = 2 is neither", "layout", 0),
+             (INV, "dtype = 3 is none of", "dtype", 0),
+             (INV, "pad_mode = 2 is neither", "pad_mode", 0),
+             (INV, "pad_value is NaN", "pad_value", 0.0),
+             (INV, "vad_batch.reserved = 1 must be 0", "reserved", 0),
+             (INV, "rows = -1 is negative", "rows", 3),
+             (INV, "n = -1 is negative", "n", 2),
+             (INV, r"start\[0\] = 0 \.\. start\[n\] = 4 leaves the matrix of 3 rows", "start", [0, 2, 1]),
+             (INV, "segment 1: start = 2 is followed by 1", "start", [0, 1, 3]),
+             (INV, "the features must be 4-byte aligned", "features", RO.buf(24), RO.DEVICE),
+             (INV, "null buffer or bad count", "nw", 1),
+             (INV, "nss = 3: shift and scale have 1 row or " + ("nw = 1" if packed else "n = 2"), "nss", per),
+             (INV, r"lo\[0\] is NaN", "lo", RO.f32(*[-1.0] * per)),
+             (INV, r"shift\[0\]\[1\] is infinite", "shift", RO.f32(*[0.5] * (2 * per))),
+             (INV, r"scale\[%d\]\[1\] is NaN" % (per - 1), "scale", RO.f32(*[2.0] * (2 * per))))
+    steps += tuple((INV, pattern, "items", mended) for pattern, mended in item_steps)
+    steps += ((INV, "out_bytes = 0, the windows have 32 bytes", "out_bytes", 32),
+              (INV, r"vad_mel_batch(_packed)?(_device)?: null buffer$", "out", RO.buf(32, 4)),
+              (INV, "the output must be 16-byte aligned", "out", RO.buf(32), RO.DEVICE))
+    return faults, steps
+
+
+def batch_order_walks(lib, make_engine, packed, items, item_steps):
+    """the three parts of a batch call's order: the walk on a caller's matrix, where nw == 0 stands, and the walk on a resident one"""
+    from tests import refusal_order as RO
+    faults, steps = batch_order(packed, items, item_steps)
+    eng = make_engine()
+    call = batch_order_call(lib, eng, packed)
+    RO.walk(lib, eng, call, faults, steps)
+    # nw == 0 is VAD_OK behind out_bytes and ahead of the output's checks: a null or misaligned out passes and nothing is written, while
+    # an infinite shift (no window is read) and a negative out_bytes are still refused
+    done = dict(faults)
+    done.update({s[2]: s[3] for s in steps})
+    for device in (False, True):
+        for out in (None, RO.buf(32, 4)):
+            if out is not None:
+                out[:] = FILL
+            assert call(device, **{**done, "nw": 0, "items": [], "out": out, "out_bytes": 0}) == 0
+            assert out is None or (out == FILL).all()
+        assert call(device, **{**done, "nw": 0, "items": [], "shift": faults["shift"]}) == INV and "shift[0][1] is infinite" in lib.vad_last_error(eng.handle).decode()
+        assert call(device, **{**done, "nw": 0, "items": [], "out_bytes": -1}) == INV
+    # the resident matrix under segments of the caller's, then under its own: its absence first, its width behind the segments
+    for device in (False, True):
+        eng = make_engine()
+        call = batch_order_call(lib, eng, packed)
+        RO.walk_one(lib, eng, lambda **kw: call(device, **kw),
+                    {**done, "features": None, "rows": -1, "n_mels": 3, "start": [0, 1, 4], "nw": -1, "nss": 3, "out": RO.buf(32, 4 if device else 0)},
+                    [(INV, "NULL names the resident matrix, and the engine holds none", "kept", True),
+                     (INV, r"start\[n\] = 4 leaves the matrix of 3 rows", "start", None),
+                     (INV, "n_mels = 3, the resident matrix has 2", "n_mels", 2),
+                     (INV, "null buffer or bad count", "nw", 1),
+                     (INV, "nss = 3: shift and scale have 1 row or " + ("nw = 1" if packed else "n = 2"), "nss", 1 if packed else 2)] +
+                    ([(INV, "the output must be 16-byte aligned", "out", RO.buf(32))] if device else []))
+
+
+def test_the_whole_order_of_a_batch_call(lib, make_engine):
+    """vad_mel_batch / _device, every reachable check: vad_batch's fields in batch_check's order, the matrix and its segments (no
+    resident matrix, rows, n, start[0] / start[n], ascending, the device form's feature alignment), n_mels against the resident
+    matrix, the counts, nss, lo, shift, scale, per window its segment and its rows, out_bytes, nw == 0, the null out, the device
+    form's output alignment.  Left out, as they need more than 2^31 - 1 elements: more than 2^31 - 1 segments, a segment of 2^31
+    rows or more, more than 2^31 - 1 workgroups."""
+    batch_order_walks(lib, make_engine, False, [(5, 3, 0)],
+                      [("window 0 names segment 5 of 2", [(1, 3, 0)]),
+                       (r"window 0: rows 0 \.\. \+3 of segment 1, which has 2, in 4 frames", [(1, 2, 0)])])
+
+
+def stats_order_call(lib, eng, grouped=False):
+    """call(device, **kw) -> rc of vad_mel_stats, or of vad_mel_stats_grouped, for refusal_order.walk; outs = (max, sum, sumsq)"""
+    from tests import refusal_order as RO
+    name = "vad_mel_stats_grouped" if grouped else "vad_mel_stats"
+
+    def call(device, features, rows, n_mels, start, n, outs, group=None, ngroups=0, kept=False):
+        if kept:
+            keep_3x2(lib, eng)
+        st = None if start is None else np.array(start, np.int64)
+        gr = None if group is None else np.array(group, np.int32)
+        head = (rows, n_mels, RO.i64p(st), n) + ((None if gr is None else gr.ctypes.data_as(C.POINTER(C.c_int32)), ngroups) if grouped else ())
+        if device:
+            return getattr(lib, name + "_device")(eng.handle, RO.addr(features), *head, *[RO.addr(o) for o in outs], None)
+        mx, sm, sq = outs
+        return getattr(lib, name)(eng.handle, RO.f32p(features), *head, RO.f32p(mx), RO.i64p(sm), None if sq is None else sq.ctypes.data_as(_u64p))
+
+    return call
+
+
+def stats_order_walks(lib, make_engine, grouped):
+    """the parts of a statistics call's order: a caller's 3 x 2 matrix, the row bound of the sums on one segment of
+    VAD_STATS_MAX_ROWS + 1 rows x 1 column, where the early VAD_OK stands, and a resident matrix"""
+    from tests import refusal_order as RO
+    eng = make_engine()
+    call = stats_order_call(lib, eng, grouped)
+    most = _ffi.VAD_STATS_MAX_ROWS
+    aligned = lambda cols: (RO.buf(8), RO.buf(16 * cols), RO.buf(16 * cols))                      # noqa: E731
+    askew = lambda cols: (RO.buf(8), RO.buf(16 * cols, 4), RO.buf(16 * cols))                     # noqa: E731
+    groups = dict(group=[0, 5], ngroups=-1) if grouped else {}
+    group_steps = ((INV, "ngroups = -1 must be", "ngroups", 2), (INV, "segment 1 names group 5 of 2", "group", [1, 0])) if grouped else ()
+    faults = dict(features=RO.buf(24, 2), rows=-1, n_mels=0, start=[0, 2, 4], n=-1, outs=askew(2), **groups)
+    steps = ((INV, "rows = -1 is negative", "rows", 3),
+             (INV, "n_mels = 0 must be 1 .. 128", "n_mels", 2),
+             (INV, "n = -1 is negative", "n", 2),
+             (INV, r"start\[0\] = 0 \.\. start\[n\] = 4 leaves the matrix of 3 rows", "start", [0, 2, 1]),
+             (INV, "segment 1: start = 2 is followed by 1", "start", [0, 1, 3]),
+             (INV, "the features must be 4-byte aligned", "features", RO.buf(24), RO.DEVICE)) + group_steps + (
+             (INV, "the sums must be 8-byte aligned, the maxima 4-byte", "outs", aligned(2), RO.DEVICE),)
+    RO.walk(lib, eng, call, faults, steps)
+    # the row bound stands behind the groups and ahead of the outputs' alignment
+    one = dict(group=[0], ngroups=1) if grouped else {}
+    RO.walk(lib, eng, call, dict(features=RO.buf(4 * (most + 1)), rows=most + 1, n_mels=1, start=[0, most + 1], n=1, outs=askew(1), **one),
+            ((INV, "%s 0 has %d rows, the sums take %d at the most" % ("group" if grouped else "segment", most + 1, most), "start", [0, most]),
+             (INV, "the sums must be 8-byte aligned, the maxima 4-byte", "outs", aligned(1), RO.DEVICE)))
+    # no entry to write, or no output asked for, is VAD_OK behind the alignment, and nothing is written
+    none = dict(features=RO.buf(24), rows=3, n_mels=2, start=[0], n=0, **(dict(group=[], ngroups=0) if grouped else {}))
+    assert call(True, **none, outs=askew(2)) == INV and "8-byte aligned" in lib.vad_last_error(eng.handle).decode()
+    for device in (False, True):
+        outs = aligned(2)
+        for o in outs:
+            o[:] = FILL
+        assert call(device, **none, outs=outs) == 0 and all((o == FILL).all() for o in outs)
+        assert call(device, **{**none, "start": [0, 1, 3], "n": 2, **(dict(group=[1, 0], ngroups=2) if grouped else {})}, outs=(None, None, None)) == 0
+    # the resident matrix under segments of the caller's: its absence first (n_mels is the resident one's: the argument is not read)
+    for device in (False, True):
+        eng = make_engine()
+        call = stats_order_call(lib, eng, grouped)
+        RO.walk_one(lib, eng, lambda **kw: call(device, **kw),
+                    dict(features=None, rows=-1, n_mels=0, start=[0, 1, 4], n=2, outs=askew(2) if device else aligned(2), **groups),
+                    [(INV, "NULL names the resident matrix, and the engine holds none", "kept", True),
+                     (INV, r"start\[n\] = 4 leaves the matrix of 3 rows", "start", None)] + list(group_steps) +
+                    ([(INV, "the sums must be 8-byte aligned, the maxima 4-byte", "outs", aligned(2))] if device else []))
+
+
+def test_the_whole_order_of_a_stats_call(lib, make_engine):
+    """vad_mel_stats / _device, every reachable check: the matrix and its segments (no resident matrix, rows, n_mels, n,
+    start[0] / start[n], ascending, the device form's feature alignment), the row bound of the sums per segment, the device form's
+    output alignment, then VAD_OK for n == 0 or no output.  Left out, as they need more than 2^31 - 1 elements: more than 2^31 - 1
+    segments, a segment of 2^31 rows or more, more than 2^31 - 1 workgroups."""
+    stats_order_walks(lib, make_engine, False)

@@ -598,3 +598,24 @@ def test_batch_recordings_unpacked_is_unchanged_and_recording_scope(eng, standin
     for bad in (dict(frames=8, pack=True, scope="segment"), dict(pack=True), dict(frames=8, pack=True, stride=4), dict(frames=8, scope="window")):
         with pytest.raises(ConfigurationError):
             batch_recordings([mono], spec, FeatureBatch(**bad), cfg, engine=eng)
+
+
+# ---- the whole order of the checks (the helpers and the shapes: tests/test_mel_batch_host.py) ---------------------------------
+def test_the_whole_order_of_a_packed_call(lib, make_engine):
+    """vad_mel_batch_packed / _device, every reachable check: vad_mel_batch's order with nss and lo over the nw windows, per piece its
+    segment, rows, window and offset, and behind the pieces the overlap of two in a window.  Left out, as they need more than
+    2^31 - 1 elements: more than 2^31 - 1 segments, a segment of 2^31 rows or more, more than 2^31 - 1 windows or workgroups."""
+    from tests.test_mel_batch_host import batch_order_walks
+    batch_order_walks(lib, make_engine, True, [(5, 3, 0, 1, 2)],
+                      [("piece 0 names segment 5 of 2", [(1, 3, 0, 1, 2)]),
+                       (r"piece 0: rows 0 \.\. \+3 of segment 1, which has 2", [(1, 2, 0, 1, 2)]),
+                       ("piece 0 names window 1 of 1", [(1, 2, 0, 0, 2)]),
+                       ("piece 0: offset = 2 with 2 rows", [(1, 2, 0, 0, 0), (0, 1, 0, 0, 0)]),
+                       ("pieces 0 and 1 overlap in window 0: frames 0 .. 3 and 0 .. 3", [(1, 2, 0, 0, 0)])])
+
+
+def test_the_whole_order_of_a_grouped_stats_call(lib, make_engine):
+    """vad_mel_stats_grouped / _device: vad_mel_stats's order with ngroups and group[i] behind the segments and the row bound of the
+    sums per group.  Left out: the same checks as there."""
+    from tests.test_mel_batch_host import stats_order_walks
+    stats_order_walks(lib, make_engine, True)

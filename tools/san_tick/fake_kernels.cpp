@@ -451,87 +451,66 @@ static uint16_t f16_bits(float f) {
     return (uint16_t)(sign | ((x + 0xfffu + ((x >> 13) & 1u) - 0x38000000u) >> 13));
 }
 
-// model-ready windows of a feature matrix (csrc/mel_batch.hip: vadk_mel_batch): include/vad_engine.h's rule cell by cell, every
-// operation a float32 of its own (volatile: each is rounded where it stands)
+// The batch cell rule of include/vad_engine.h, once, as both kernels share melb_tile_body (csrc/mel_batch.hip): frames t0 .. t0 + nt of
+// window `window`, the first nv of them rows row0 .. of the segment of M rows at seg_row, the rest pad cells, under lo, shift and
+// scale number `affine`.  Every operation a float32 of its own (volatile: each is rounded where it stands)
+static void fake_batch_cells(const MelBatchArgs *a, uint32_t window, uint32_t t0, uint32_t nt, uint32_t nv, uint64_t seg_row, uint32_t M, uint32_t row0,
+                             uint32_t affine) {
+    const uint32_t nm = a->n_mels, T = a->frames, C = nm * (a->deltas + 1u);
+    const float lo = a->lo[affine];
+    const float *shift = a->shift + (size_t)(a->per_seg ? affine : 0u) * nm, *scale = a->scale + (size_t)(a->per_seg ? affine : 0u) * nm;
+    auto norm = [&](float x, uint32_t j) -> float {
+        volatile float s = (x > lo ? x : lo) + shift[j];
+        return s * scale[j];
+    };
+    auto c = [&](int64_t s) -> int64_t { return s < 0 ? 0 : s > (int64_t)M - 1 ? (int64_t)M - 1 : s; };
+    auto v = [&](int64_t s, uint32_t j) -> float { return norm(a->x[((size_t)seg_row + (size_t)c(s)) * nm + j], j); };
+    auto delta = [&](float m2, float m1, float p1, float p2) -> float {
+        volatile float d1 = p1 - m1, d2 = p2 - m2, t2 = 2.0f * d2, sum = d1 + t2;
+        return sum * 0.1f;
+    };
+    auto d1 = [&](int64_t s, uint32_t j) -> float { s = c(s); return delta(v(s - 2, j), v(s - 1, j), v(s + 1, j), v(s + 2, j)); };
+    auto d2 = [&](int64_t s, uint32_t j) -> float { return delta(d1(s - 2, j), d1(s - 1, j), d1(s + 1, j), d1(s + 2, j)); };
+    for (uint32_t ch = 0; ch < C; ++ch)
+        for (uint32_t tt = 0; tt < nt; ++tt) {
+            const uint32_t k = ch / nm, j = ch % nm, t = t0 + tt;
+            const int64_t s = (int64_t)row0 + tt;
+            float val;
+            if (tt >= nv) val = k ? 0.0f : a->pad_mode == VAD_BATCH_PAD_FEATURE ? norm(a->pad_value, j) : a->pad_value;
+            else val = k == 0 ? v(s, j) : k == 1 ? d1(s, j) : d2(s, j);
+            const size_t o = a->layout == VAD_BATCH_TIME_MAJOR ? ((size_t)window * T + t) * C + ch : ((size_t)window * C + ch) * T + t;
+            if (a->dtype == VAD_BATCH_F32) static_cast<float *>(a->out)[o] = val;
+            else {
+                uint32_t bits;
+                std::memcpy(&bits, &val, 4);
+                static_cast<uint16_t *>(a->out)[o] = a->dtype == VAD_BATCH_F16 ? f16_bits(val) : melb_bf16(bits);
+            }
+        }
+}
+
+// model-ready windows of a feature matrix (csrc/mel_batch.hip: vadk_mel_batch): a window is its T frames, under its SEGMENT's lo,
+// shift and scale
 extern "C" hipError_t vadk_launch_mel_batch(const MelBatchArgs *a, hipStream_t) {
     if (a->tile != melb_tile(a->n_mels, a->deltas)) return hipErrorInvalidValue;
-    const uint32_t nm = a->n_mels, T = a->frames, C = nm * (a->deltas + 1u);
     for (uint32_t wi = 0; wi < a->nw; ++wi) {
         const MelBatchWin w = a->win[wi];
-        if (w.nrows > T || (uint64_t)w.row0 + w.nrows > w.M) return hipErrorInvalidValue;
-        const float lo = a->lo[w.seg];
-        const float *shift = a->shift + (size_t)(a->per_seg ? w.seg : 0u) * nm, *scale = a->scale + (size_t)(a->per_seg ? w.seg : 0u) * nm;
-        auto norm = [&](float x, uint32_t j) -> float {
-            volatile float s = (x > lo ? x : lo) + shift[j];
-            return s * scale[j];
-        };
-        auto c = [&](int64_t s) -> int64_t { return s < 0 ? 0 : s > (int64_t)w.M - 1 ? (int64_t)w.M - 1 : s; };
-        auto v = [&](int64_t s, uint32_t j) -> float { return norm(a->x[((size_t)w.seg_row + (size_t)c(s)) * nm + j], j); };
-        auto delta = [&](float m2, float m1, float p1, float p2) -> float {
-            volatile float d1 = p1 - m1, d2 = p2 - m2, t2 = 2.0f * d2, sum = d1 + t2;
-            return sum * 0.1f;
-        };
-        auto d1 = [&](int64_t s, uint32_t j) -> float { s = c(s); return delta(v(s - 2, j), v(s - 1, j), v(s + 1, j), v(s + 2, j)); };
-        auto d2 = [&](int64_t s, uint32_t j) -> float { return delta(d1(s - 2, j), d1(s - 1, j), d1(s + 1, j), d1(s + 2, j)); };
-        for (uint32_t ch = 0; ch < C; ++ch)
-            for (uint32_t t = 0; t < T; ++t) {
-                const uint32_t k = ch / nm, j = ch % nm;
-                const int64_t s = (int64_t)w.row0 + t;
-                float val;
-                if (t >= w.nrows) val = k ? 0.0f : a->pad_mode == VAD_BATCH_PAD_FEATURE ? norm(a->pad_value, j) : a->pad_value;
-                else val = k == 0 ? v(s, j) : k == 1 ? d1(s, j) : d2(s, j);
-                const size_t o = a->layout == VAD_BATCH_TIME_MAJOR ? ((size_t)wi * T + t) * C + ch : ((size_t)wi * C + ch) * T + t;
-                if (a->dtype == VAD_BATCH_F32) static_cast<float *>(a->out)[o] = val;
-                else {
-                    uint32_t bits;
-                    std::memcpy(&bits, &val, 4);
-                    static_cast<uint16_t *>(a->out)[o] = a->dtype == VAD_BATCH_F16 ? f16_bits(val) : melb_bf16(bits);
-                }
-            }
+        if (w.nrows > a->frames || (uint64_t)w.row0 + w.nrows > w.M) return hipErrorInvalidValue;
+        fake_batch_cells(a, wi, 0u, a->frames, w.nrows, w.seg_row, w.M, w.row0, w.seg);
     }
     return hipSuccess;
 }
 
-// packed windows (csrc/mel_batch.hip: vadk_mel_batch_packed): the same rule cell by cell over the host's work list - the frames a
-// workgroup owns, the first nv of them segment rows, the rest pad cells - with lo, shift and scale of the WINDOW
+// packed windows (csrc/mel_batch.hip: vadk_mel_batch_packed): the same cells over the host's work list - the frames a workgroup
+// owns, the first nv of them segment rows, the rest pad cells - with lo, shift and scale of the WINDOW
 extern "C" hipError_t vadk_launch_mel_batch_packed(const MelPackArgs *p, hipStream_t) {
     const MelBatchArgs *a = &p->b;
     if (a->tile != melb_tile(a->n_mels, a->deltas)) return hipErrorInvalidValue;
-    const uint32_t nm = a->n_mels, T = a->frames, C = nm * (a->deltas + 1u);
     for (uint32_t b = 0; b < p->nwork; ++b) {
         const MelPackWork w = p->work[b];
-        if (w.window >= a->nw || w.nt < 4 || (w.nt & 3) || (w.t0 & 3) || w.nt > a->tile || (uint64_t)w.t0 + w.nt > T || w.nv > w.nt ||
+        if (w.window >= a->nw || w.nt < 4 || (w.nt & 3) || (w.t0 & 3) || w.nt > a->tile || (uint64_t)w.t0 + w.nt > a->frames || w.nv > w.nt ||
             (uint64_t)w.row0 + w.nv > w.M)
             return hipErrorInvalidValue;
-        const float lo = a->lo[w.window];
-        const float *shift = a->shift + (size_t)(a->per_seg ? w.window : 0u) * nm, *scale = a->scale + (size_t)(a->per_seg ? w.window : 0u) * nm;
-        auto norm = [&](float x, uint32_t j) -> float {
-            volatile float s = (x > lo ? x : lo) + shift[j];
-            return s * scale[j];
-        };
-        auto c = [&](int64_t s) -> int64_t { return s < 0 ? 0 : s > (int64_t)w.M - 1 ? (int64_t)w.M - 1 : s; };
-        auto v = [&](int64_t s, uint32_t j) -> float { return norm(a->x[((size_t)w.seg_row + (size_t)c(s)) * nm + j], j); };
-        auto delta = [&](float m2, float m1, float p1, float p2) -> float {
-            volatile float d1 = p1 - m1, d2 = p2 - m2, t2 = 2.0f * d2, sum = d1 + t2;
-            return sum * 0.1f;
-        };
-        auto d1 = [&](int64_t s, uint32_t j) -> float { s = c(s); return delta(v(s - 2, j), v(s - 1, j), v(s + 1, j), v(s + 2, j)); };
-        auto d2 = [&](int64_t s, uint32_t j) -> float { return delta(d1(s - 2, j), d1(s - 1, j), d1(s + 1, j), d1(s + 2, j)); };
-        for (uint32_t ch = 0; ch < C; ++ch)
-            for (uint32_t tt = 0; tt < w.nt; ++tt) {
-                const uint32_t k = ch / nm, j = ch % nm, t = w.t0 + tt;
-                const int64_t s = (int64_t)w.row0 + tt;
-                float val;
-                if (tt >= w.nv) val = k ? 0.0f : a->pad_mode == VAD_BATCH_PAD_FEATURE ? norm(a->pad_value, j) : a->pad_value;
-                else val = k == 0 ? v(s, j) : k == 1 ? d1(s, j) : d2(s, j);
-                const size_t o = a->layout == VAD_BATCH_TIME_MAJOR ? ((size_t)w.window * T + t) * C + ch : ((size_t)w.window * C + ch) * T + t;
-                if (a->dtype == VAD_BATCH_F32) static_cast<float *>(a->out)[o] = val;
-                else {
-                    uint32_t bits;
-                    std::memcpy(&bits, &val, 4);
-                    static_cast<uint16_t *>(a->out)[o] = a->dtype == VAD_BATCH_F16 ? f16_bits(val) : melb_bf16(bits);
-                }
-            }
+        fake_batch_cells(a, w.window, w.t0, w.nt, w.nv, w.seg_row, w.M, w.row0, w.window);
     }
     return hipSuccess;
 }

@@ -4,8 +4,9 @@
 // and in push order (the stand-in model returns |first sample|, so the audio scripts the probabilities), events equal a serial
 // replay of the real state machine, segments hold exactly the frames the reference would keep; then, single-threaded: a failing
 // tick keeps the queues aligned, and a stream saved mid-segment continues bit-identically on another slot; last, one host call
-// per runner of the segment-audio family (cut, rate cut, render, mel, rate mel) and of the segment-table family (segments,
-// resegment, tails, resegment-tails, refine), for the layout of their device tables.
+// per runner of the segment-audio family (cut, rate cut, render, mel, rate mel), of the feature family (stats, grouped stats, batch,
+// packed batch, project) and of the segment-table family (segments, resegment, tails, resegment-tails, refine), for the layout of
+// their device tables.
 // Built three times by tools/san_tick/run.sh: -fsanitize=thread, -fsanitize=address,undefined, and plain.
 #include "../../include/vad_engine.h"
 #include <hip/hip_runtime.h>
@@ -423,13 +424,49 @@ int main(int argc, char **argv) {
         int64_t kept = -1;
         int32_t kept_mels = 0;
         OK(vad_scan_mel_keep(eng, two, 2, &m, op.data(), op.data(), fil.data(), nullptr, 0, block.data(), NS, 1, VAD_FMT_F32, 0, 256, -1.0f, &kept));
+        // the feature family, one host call per runner on a matrix of the caller's - 3 x 2, segments of 1 and 2 rows - and on the kept
+        // one (74 x 4, segments of 29 and 45 rows): sums, grouped sums, a batch of two windows with deltas, a packed batch with a pad window
+        const float fx[6] = {1, 2, 3, 4, 5, 6};
+        const int64_t fstart[3] = {0, 1, 3};
+        const int32_t fgroup[2] = {0, 0};
+        float fmax[2];
+        int64_t fsum[8];
+        uint64_t fsq[8];
+        OK(vad_mel_stats(eng, fx, 3, 2, fstart, 2, fmax, fsum, fsq));
+        CHECK(fmax[0] == 2.0f && fmax[1] == 6.0f && fsum[0] == 4096 && fsum[3] == 10 * 4096 && fsq[1] == 4ull << 24);
+        OK(vad_mel_stats_grouped(eng, fx, 3, 2, fstart, 2, fgroup, 1, fmax, fsum, fsq));
+        CHECK(fmax[0] == 6.0f && fsum[0] == 9 * 4096 && fsum[1] == 12 * 4096);
+        OK(vad_mel_stats(eng, nullptr, 0, 0, nullptr, 0, fmax, fsum, fsq));
+        CHECK(std::isfinite(fmax[0]) && std::isfinite(fmax[1]));
+        OK(vad_mel_stats_grouped(eng, nullptr, 0, 0, nullptr, 0, fgroup, 1, fmax, fsum, fsq));
+        CHECK(std::isfinite(fmax[0]));
+        const vad_batch fb = {2, 4, 1, VAD_BATCH_CHANNEL_MAJOR, VAD_BATCH_F32, VAD_BATCH_PAD_VALUE, -1.0f, 0};
+        const vad_batch fb8 = {2, 8, 0, VAD_BATCH_CHANNEL_MAJOR, VAD_BATCH_F32, VAD_BATCH_PAD_VALUE, -1.0f, 0};
+        const vad_batch kb = {4, 8, 0, VAD_BATCH_TIME_MAJOR, VAD_BATCH_BF16, VAD_BATCH_PAD_FEATURE, 0.0f, 0};
+        const vad_batch_window fw[2] = {{1, 2, 0}, {0, 1, 0}}, kwin[1] = {{1, 8, 37}};
+        const vad_batch_piece fp[2] = {{1, 2, 0, 0, 4}, {0, 1, 0, 0, 0}}, kp[2] = {{0, 4, 25, 0, 0}, {1, 3, 42, 0, 4}};
+        const float flo[2] = {-INFINITY, 1.5f}, fshift[4] = {0, 0, 1, 1}, fscale[4] = {1, 1, 2, 2};
+        std::fill(out.begin(), out.end(), -7.0f);
+        OK(vad_mel_batch(eng, fx, 3, fstart, 2, &fb, fw, 2, flo, fshift, fscale, 2, out.data(), 2 * 4 * 4 * 4));
+        CHECK(out[0] == 8.0f && out[1] == 12.0f && out[2] == -1.0f && out[16] == 1.0f && out[31] == 0.0f && out[32] == -7.0f);
+        // window 0: segment 0 at frame 0 and segment 1 at frame 4, lo, shift and scale of the window; window 1 has no piece
+        std::fill(out.begin(), out.end(), -7.0f);
+        OK(vad_mel_batch_packed(eng, fx, 3, fstart, 2, &fb8, fp, 2, 2, flo, fshift, fscale, 2, out.data(), 2 * 2 * 8 * 4));
+        CHECK(out[0] == 1.0f && out[1] == -1.0f && out[4] == 3.0f && out[5] == 5.0f && out[6] == -1.0f && out[16] == -1.0f && out[32] == -7.0f);
+        std::fill(out.begin(), out.end(), -7.0f);
+        OK(vad_mel_batch(eng, nullptr, 0, nullptr, 0, &kb, kwin, 1, nullptr, nullptr, nullptr, 1, out.data(), 4 * 8 * 2));
+        CHECK(out[0] != -7.0f && out[15] != -7.0f && out[16] == -7.0f);
+        std::fill(out.begin(), out.end(), -7.0f);
+        OK(vad_mel_batch_packed(eng, nullptr, 0, nullptr, 0, &kb, kp, 2, 1, nullptr, nullptr, nullptr, 1, out.data(), 4 * 8 * 2));
+        CHECK(out[0] != -7.0f && out[15] != -7.0f && out[16] == -7.0f);
         OK(vad_mel_project(eng, nullptr, 0, 0, sel, nullptr, 2, nullptr));
         OK(vad_mel_resident(eng, &kept, &kept_mels, nullptr));
         CHECK(kept == 74 && kept_mels == 2);
         OK(vad_mel_resident_read(eng, 0, 74, out.data()));
         CHECK(std::isfinite(out[0]) && std::isfinite(out[2 * 74 - 1]));
         vad_engine_destroy(eng);
-        std::printf("san_tick: segment-audio calls ok (cut, rate cut over 2 windows, render, mel, rate mel, moments, audio batch, project)\n");
+        std::printf("san_tick: segment-audio calls ok (cut, rate cut over 2 windows, render, mel, rate mel, moments, audio batch, project, stats, "
+                    "grouped stats, batch, packed batch)\n");
     }
     // ---- the segment-table family: one host call per runner on the smallest corpus with a record and a tail - two recordings, the
     //      first ends a segment and is inside the next at its last frame - so that each work area's slots run under the sanitizers
